@@ -15,6 +15,10 @@ touches torch or the GPU) and relays rank 0's line.  Under torchrun it is one ra
 own independent proof per step (weak scaling); the only collective is an RCCL all_gather of the finished proof bytes.
 A second, strong-scaling leg proves a fixed batch of 8 independent proofs sharded round-robin over the ranks.
 
+A plain run sets up, warms up, times the --steps proofs and prints the line.  Every secondary figure (roofline, lone proof, single stream,
+verifier, expanded blinding, batch, throughput, small configurations, one-shot profile, CPU baseline) needs `--full`.
+`--dump-outputs DIR` writes what the last timed step returned to its caller as DIR/*.npy (see dump_outputs).
+
 Prints ONE JSON line on rank 0 (see the driver contract); diagnostics go to stderr.
 """
 import argparse
@@ -79,8 +83,13 @@ def parse_args(argv=None):
     ap.add_argument("--plan-only", action="store_true", help="print what --gpus N would do on this node - per rank: device, NUMA node, CPU set, chain-pool lanes, expected HBM and "
                     "pinned host memory - from the planner the real run uses, WITHOUT touching a GPU; a node with fewer cards is planned on an assumed 2-socket topology")
     ap.add_argument("--lone-proof", action="store_true", help="with --headline-only: also prove once ALONE on the device after the timed steps and report `lone_proof` "
-                    "(phase times of the library clock, sum of the kernels' HIP-event durations, launches) - what the one-shot child of the default run adds to `value_one_shot`")
+                    "(phase times of the library clock, sum of the kernels' HIP-event durations, launches) - what the one-shot child of a --full run adds to `value_one_shot`")
     ap.add_argument("--no-one-shot-leg", action="store_true", help="skip `value_one_shot` (the timed steps once more under the one-shot profile, in a child process)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: the roofline (HIP events in the timed steps, the VALU "
+                    "microbenchmark) and, unless --headline-only, every secondary leg and the CPU baseline. Without it a run does only the set-up, the warm-up "
+                    "and the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last of them returned to its caller (proof bytes and "
+                    "transcript state, one float64 per byte) as DIR/proof.npy and DIR/transcript_state.npy")
     return ap.parse_args(argv)
 
 
@@ -328,6 +337,16 @@ def source_hash():
     return h.hexdigest()[:16]
 
 
+def dump_outputs(folder, out):
+    """--dump-outputs: what ResidentCircuit.prove returned for the last timed step - the proof bytes and the transcript state after the proof -
+    one float64 per byte (0..255, exact).  The instance and the seeds depend on the arguments only, so two builds can be compared byte for byte."""
+    import numpy as np
+    d = pathlib.Path(folder)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, raw in (("proof", out[0]), ("transcript_state", out[1])):
+        np.save(d / (name + ".npy"), np.frombuffer(raw, dtype=np.uint8).astype(np.float64))
+
+
 # ------------------------------------------------------------------------------------------------ secondary legs
 def cpu_baseline(ctx, bpg, workloads, leaves, headline):
     """Time the single-threaded CPU oracle (upstream's algorithms: constant-time Straus for A_I/A_O/S/T, Straus/Pippenger for
@@ -569,7 +588,7 @@ def one_shot_leg(args):
     """`value_one_shot`: the SAME K timed steps (same command, streams, chain pool, seeds) with every context under the ONE-SHOT profile - what a
     drop-in caller of bpg_ctx_create(device) gets: first fold on width-5 NAF tables of scalars cut in two (3.0 GB at 2^20), no 8-bit tail tables.  Run as
     a child process: tables are per process and device, and the serving tables this process holds would count against the one-shot budget."""
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--headline-only", "--lone-proof", "--profile", "oneshot", "--no-one-shot-leg", "--steps", str(args.steps), "--warmup", str(args.warmup),
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--headline-only", "--lone-proof", "--profile", "oneshot", "--no-one-shot-leg", "--steps", str(args.steps), "--warmup", str(args.warmup),
            "--leaves", str(args.leaves), "--streams", str(args.streams), "--chain-workers", str(args.chain_workers), "--chain-lanes", str(args.chain_lanes),
            "--chain-pool", args.chain_pool]
     env = dict(os.environ)
@@ -797,8 +816,9 @@ def run_rank(args):
     # ---- warm-up (not steps: the first proof of a context sizes its device workspaces), then EXACTLY `steps` timed proofs
     lanes.extend(extra_lanes)
     prove_steps([seed_for(2000 + i) for i in range(max(args.warmup, len(lanes)))])
-    for c_, _ in lanes:
-        c_.profile_set(1)       # HIP events around the bucket sweep and the generator folds only (11-13 launches per proof)
+    if args.full:
+        for c_, _ in lanes:
+            c_.profile_set(1)   # HIP events around the bucket sweep and the generator folds only (11-13 launches per proof), for the roofline
     barrier()
     del done_at[:]
     cpu0 = time.process_time()                               # CPU time of every thread of this process (chain pool and proving threads included)
@@ -842,6 +862,8 @@ def run_rank(args):
                                  "ms_per_step": elapsed_local / args.steps * 1e3, "proving_streams": n_streams, "chain_pool_lanes": pool_lanes if pool is not None else None,
                                  "hbm_in_use_GB": hbm_used["in_use_GB"] if hbm_used else None})      # the DEVICE's figure: ranks that share a card (gloo rehearsal) see the sum
     last = outs[-1]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
 
     # ---- strong-scaling leg: a fixed batch of independent proofs, sharded round-robin over the ranks (north_star: 8 proofs, >= 6x at 8 GPUs)
     batch_info = None
@@ -988,117 +1010,119 @@ def run_rank(args):
         expanded = {"ms_per_proof": dte * 1e3, "value": inst.q / dte, "unit": "constraints/s", "verified": res.verify(state, b"".join(a.commitments), pe[0]) == 0,
                     "note": "BPG_FLAG_EXPANDED_BLINDING (include/bpg.h): opt-in, not upstream's blinding derivation; not the headline"}
 
-    # ---- roofline of the dominant kernel (HIP events on the engine's stream inside the timed steps) and of the whole proof
     src = source_hash()
-    traffic_tab, traffic_note = {}, "no PMC profile stored"
-    tfile = ROOT / "profiles" / "pmc_traffic.json"
-    if tfile.exists():
-        try:
-            stored = json.loads(tfile.read_text())
-            if stored.get("_meta", {}).get("source_hash") == src:
-                traffic_tab = stored
-                traffic_note = "rocprofv3 --pmc passes of these sources (profiles/pmc_traffic.json: %s)" % stored["_meta"].get("note", "")
-            else:
-                traffic_note = "profiles/pmc_traffic.json was taken from other sources (hash %s, these are %s): not quoted" % (stored.get("_meta", {}).get("source_hash"), src)
-        except Exception as e:      # noqa: BLE001
-            traffic_note = "profiles/pmc_traffic.json unreadable: %r" % (e,)
-    peak_fm = ctx.bench_fe_mul(2000)
     # the schedule the LIBRARY settled on (bpg_profile_report "_schedule"), not a re-reading of the environment: tail start, fold groups, window caps
     schedule = ctx.schedule()
-    fold_group, tt_lg = int(schedule["fold_group"]), int(schedule["tt_lg"])
-    if a.gens_capacity <= (1 << int(schedule["tt_orig_lg"])):
-        tt_lg = a.gens_capacity.bit_length() - 1              # the original generators are frozen at round 0: no sweep above the tail
-    first_group = min(fold_group, max(a.gens_capacity.bit_length() - 1 - tt_lg, 0))
-    rocprof_name = {"k_fold_points_reg": "k_fold_points_reg<%d>" % ((1 << first_group) - 1)}
-
-    def kernel_roofline(name, table=None):
-        k = (table or prof)[name]
-        secs = k["total_ms"] * 1e-3
-        launches = max(k["count"], 1)
-        t = traffic_tab.get(rocprof_name.get(name, name))
-        return {"kernel": rocprof_name.get(name, name), "launches": k["count"], "avg_launch_ms": k["total_ms"] / launches,
-                "alg_bytes_per_launch": k["alg_bytes"] / launches, "achieved": k["alg_bytes"] / secs / 1e9 if secs > 0 else 0.0,
-                "frac": k["alg_bytes"] / secs / 8e12 if secs > 0 else 0.0,
-                "traffic": t["hbm_bytes_per_launch"] if t else None,
-                "traffic_useful_fetch": t.get("useful_fetch_bytes_per_launch") if t else None,
-                "device_GBps": k["device_bytes"] / secs / 1e9 if secs > 0 else 0.0,
-                "valu": {"unit": "field-mult/s", "achieved": k["field_mults"] / secs if secs > 0 else 0.0, "peak": peak_fm,
-                         "frac": (k["field_mults"] / secs / peak_fm) if secs > 0 and peak_fm > 0 else 0.0,
-                         "peak_source": "k_bench_fe_mul microbenchmark on this device"}}
-    ranked = sorted((n for n in prof if prof[n]["count"]), key=lambda n: -prof[n]["total_ms"])
-    # a tie (within 3 %) goes to the kernel with more launches, so that the line names the same kernel on every run
-    if len(ranked) > 1 and prof[ranked[1]]["total_ms"] > 0.97 * prof[ranked[0]]["total_ms"] and prof[ranked[1]]["count"] > prof[ranked[0]]["count"]:
-        ranked[0], ranked[1] = ranked[1], ranked[0]
-    b_alg = 576.0 * inst.n + 448.0 * a.gens_capacity           # algorithmic bytes of one proof
     t_step = elapsed / args.steps
-    whole = {"alg_bytes": b_alg, "formula": "576 n + 448 N (SURVEY.md 8d)", "seconds": t_step, "achieved": b_alg / t_step / 1e9, "unit": "GB/s", "frac": b_alg / t_step / 8e12}
-    if ranked:
-        dom = kernel_roofline(ranked[0])
-        roofline = {"bound": "hbm", "kernel": dom["kernel"], "achieved": dom["achieved"], "peak": 8000.0, "unit": "GB/s",
-                    "frac": dom["frac"], "traffic": dom["traffic"], "traffic_useful_fetch": dom["traffic_useful_fetch"], "traffic_source": traffic_note, "launches": dom["launches"], "avg_launch_ms": dom["avg_launch_ms"],
-                    "alg_bytes_per_launch": dom["alg_bytes_per_launch"],
-                    "traffic_definition": "HBM-side bytes per launch from the PMC counters: FETCH_SIZE x 2 (gfx950 tallies 64 B per 128-byte request) + WRITE_SIZE; "
-                                          "traffic_useful_fetch = FETCH_SIZE x the factor calibrated on random 96-byte rows (the bytes the kernel asked for, not HBM traffic)",
-                    "alg_bytes_definition": "information content, SURVEY.md 8(d): S + P = 64 B per MSM term for the bucket sweep (once per term, not per window); "
-                                            "32 B per point read or written for a generator fold",
-                    "device_GBps": dom["device_GBps"],
-                    "note": "integer-VALU bound path (255-bit modular arithmetic): the HBM fraction is reported as required, the binding roofline is 'valu'; "
-                            "kernel names as rocprofv3 prints them (profiles/*_kernel_stats.csv)",
-                    "valu": dom["valu"], "whole_proof": whole, "other_kernels": [kernel_roofline(n) for n in ranked[1:]]}
-        # `iso_name` = the kernel that does a kernel's job in the single-stream leg (the same name, unless a kernel has a shared-device shape of its own)
-        def iso_name(n):
-            if not prof_isolated:
-                return None
-            if n in prof_isolated:
-                return n
-            return next((x for x in SWEEPS if n in SWEEPS and x in prof_isolated), None)
-        if n_streams > 1 and iso_name(ranked[0]):
-            # with several proving streams a launch inside the timed steps shares the CUs with kernels of other proofs, and its duration says how
-            # the GPU was shared, not how good the kernel is (14 streams: 2.4 - 3.1 ms per sweep from run to run, 0.97 ms alone).  The headline
-            # figures of `roofline` are therefore the kernel ALONE on the GPU - HIP events in the single-stream leg of this same run, the
-            # command whose rocprofv3 --stats summary is profiles/*_kernel_stats_single_stream.csv - and the shared figures follow beside them
-            shared = {k: roofline[k] for k in ("launches", "avg_launch_ms", "alg_bytes_per_launch", "achieved", "frac", "device_GBps", "valu", "other_kernels")}
-            shared["note"] = ("the same kernel inside the timed steps, where %d proving streams share the GPU (HIP events on each stream, summed); "
-                              "rocprofv3 --stats of the headline command: profiles/*_rocprof_kernel_stats.csv" % n_streams)
-            iso = kernel_roofline(iso_name(ranked[0]), prof_isolated)
-            for k in ("launches", "avg_launch_ms", "alg_bytes_per_launch", "achieved", "frac", "device_GBps", "valu"):
-                roofline[k] = iso[k]
-            if iso["kernel"] != roofline["kernel"]:
-                roofline["traffic"], roofline["traffic_useful_fetch"] = iso["traffic"], iso["traffic_useful_fetch"]      # the counter passes profile one stream alone
-                roofline["kernel_alone"] = iso["kernel"]
-                roofline["note"] += "; alone on the device this kernel's job is done by %s" % iso["kernel"]
-            roofline["other_kernels"] = [kernel_roofline(n, prof_isolated) for n in ranked[1:] if n in prof_isolated]
-            roofline["measured"] = ("kernel alone on the GPU: HIP events on the engine's stream in the single-stream leg of this run (one proving stream, one "
-                                    "chain thread; rocprofv3 --stats of that command: profiles/*_kernel_stats_single_stream.csv). `timed_steps_shared` = the "
-                                    "same kernel inside the timed steps of the headline")
-            roofline["timed_steps_shared"] = shared
-        elif n_streams > 1:
-            roofline["note"] += ("; %d proving streams share the GPU inside the timed steps, so a launch there overlaps kernels of another proof and lasts "
-                                 "longer than it does alone (run without --headline-only for the kernel alone)" % n_streams)
-    else:
-        roofline = {"bound": "hbm", "kernel": None, "achieved": 0.0, "peak": 8000.0, "unit": "GB/s", "frac": 0.0, "traffic": None, "whole_proof": whole,
-                    "note": "no fold / bucket-sweep launch in the timed steps (table-driven schedule at this size)"}
-    if ranked and roofline.get("kernel") in SWEEPS:
-        # both term counts of the bucket sweep: what the launches process - the rounds of a fold group run on the group-start tables
-        # with expanded scalars, so rounds 2 and 3 of a group visit as many terms as round 1 - and what the survey's round sizes add up to
-        # (A_I, A_O, S: 5n terms; L_k, R_k of round k: 2 N_k terms for the rounds above the table-driven tail)
-        N, k = a.gens_capacity, 0
-        survey_terms = 5 * inst.n
-        while (tt_lg == 0 or (N >> k) > (1 << tt_lg)) and (N >> k) > 1:
-            survey_terms += 2 * (N >> k); k += 1
-        iso = n_streams > 1 and prof_isolated and any(x in prof_isolated for x in SWEEPS)
-        src_prof = prof_isolated if iso else prof
-        sweeps = src_prof[next(x for x in SWEEPS if x in src_prof)]
-        proofs_seen = single["steps"] if iso else args.steps
-        processed = sweeps["alg_bytes"] / 64.0
-        secs = sweeps["total_ms"] * 1e-3
-        roofline["alg_terms_processed"] = processed / proofs_seen
-        roofline["alg_terms_survey"] = survey_terms
-        roofline["frac_survey_terms"] = (64.0 * survey_terms * proofs_seen / secs / 8e12) if secs > 0 else 0.0
-        roofline["terms_note"] = ("`frac` counts 64 B for every term a launch processes (alg_terms_processed per proof); `frac_survey_terms` counts the survey's "
-                                  "round sizes only (alg_terms_survey per proof) over the same launch time; per-proof figures assume %d proofs in the profiled "
-                                  "sequence" % proofs_seen)
-    fm_per_proof = sum(prof[n]["field_mults"] for n in prof) / max(args.steps, 1)
+    # ---- roofline of the dominant kernel (HIP events on the engine's stream inside the timed steps) and of the whole proof (--full)
+    roofline = None
+    if args.full:
+        traffic_tab, traffic_note = {}, "no PMC profile stored"
+        tfile = ROOT / "profiles" / "pmc_traffic.json"
+        if tfile.exists():
+            try:
+                stored = json.loads(tfile.read_text())
+                if stored.get("_meta", {}).get("source_hash") == src:
+                    traffic_tab = stored
+                    traffic_note = "rocprofv3 --pmc passes of these sources (profiles/pmc_traffic.json: %s)" % stored["_meta"].get("note", "")
+                else:
+                    traffic_note = "profiles/pmc_traffic.json was taken from other sources (hash %s, these are %s): not quoted" % (stored.get("_meta", {}).get("source_hash"), src)
+            except Exception as e:      # noqa: BLE001
+                traffic_note = "profiles/pmc_traffic.json unreadable: %r" % (e,)
+        peak_fm = ctx.bench_fe_mul(2000)
+        fold_group, tt_lg = int(schedule["fold_group"]), int(schedule["tt_lg"])
+        if a.gens_capacity <= (1 << int(schedule["tt_orig_lg"])):
+            tt_lg = a.gens_capacity.bit_length() - 1              # the original generators are frozen at round 0: no sweep above the tail
+        first_group = min(fold_group, max(a.gens_capacity.bit_length() - 1 - tt_lg, 0))
+        rocprof_name = {"k_fold_points_reg": "k_fold_points_reg<%d>" % ((1 << first_group) - 1)}
+
+        def kernel_roofline(name, table=None):
+            k = (table or prof)[name]
+            secs = k["total_ms"] * 1e-3
+            launches = max(k["count"], 1)
+            t = traffic_tab.get(rocprof_name.get(name, name))
+            return {"kernel": rocprof_name.get(name, name), "launches": k["count"], "avg_launch_ms": k["total_ms"] / launches,
+                    "alg_bytes_per_launch": k["alg_bytes"] / launches, "achieved": k["alg_bytes"] / secs / 1e9 if secs > 0 else 0.0,
+                    "frac": k["alg_bytes"] / secs / 8e12 if secs > 0 else 0.0,
+                    "traffic": t["hbm_bytes_per_launch"] if t else None,
+                    "traffic_useful_fetch": t.get("useful_fetch_bytes_per_launch") if t else None,
+                    "device_GBps": k["device_bytes"] / secs / 1e9 if secs > 0 else 0.0,
+                    "valu": {"unit": "field-mult/s", "achieved": k["field_mults"] / secs if secs > 0 else 0.0, "peak": peak_fm,
+                             "frac": (k["field_mults"] / secs / peak_fm) if secs > 0 and peak_fm > 0 else 0.0,
+                             "peak_source": "k_bench_fe_mul microbenchmark on this device"}}
+        ranked = sorted((n for n in prof if prof[n]["count"]), key=lambda n: -prof[n]["total_ms"])
+        # a tie (within 3 %) goes to the kernel with more launches, so that the line names the same kernel on every run
+        if len(ranked) > 1 and prof[ranked[1]]["total_ms"] > 0.97 * prof[ranked[0]]["total_ms"] and prof[ranked[1]]["count"] > prof[ranked[0]]["count"]:
+            ranked[0], ranked[1] = ranked[1], ranked[0]
+        b_alg = 576.0 * inst.n + 448.0 * a.gens_capacity           # algorithmic bytes of one proof
+        whole = {"alg_bytes": b_alg, "formula": "576 n + 448 N (SURVEY.md 8d)", "seconds": t_step, "achieved": b_alg / t_step / 1e9, "unit": "GB/s", "frac": b_alg / t_step / 8e12}
+        if ranked:
+            dom = kernel_roofline(ranked[0])
+            roofline = {"bound": "hbm", "kernel": dom["kernel"], "achieved": dom["achieved"], "peak": 8000.0, "unit": "GB/s",
+                        "frac": dom["frac"], "traffic": dom["traffic"], "traffic_useful_fetch": dom["traffic_useful_fetch"], "traffic_source": traffic_note, "launches": dom["launches"], "avg_launch_ms": dom["avg_launch_ms"],
+                        "alg_bytes_per_launch": dom["alg_bytes_per_launch"],
+                        "traffic_definition": "HBM-side bytes per launch from the PMC counters: FETCH_SIZE x 2 (gfx950 tallies 64 B per 128-byte request) + WRITE_SIZE; "
+                                              "traffic_useful_fetch = FETCH_SIZE x the factor calibrated on random 96-byte rows (the bytes the kernel asked for, not HBM traffic)",
+                        "alg_bytes_definition": "information content, SURVEY.md 8(d): S + P = 64 B per MSM term for the bucket sweep (once per term, not per window); "
+                                                "32 B per point read or written for a generator fold",
+                        "device_GBps": dom["device_GBps"],
+                        "note": "integer-VALU bound path (255-bit modular arithmetic): the HBM fraction is reported as required, the binding roofline is 'valu'; "
+                                "kernel names as rocprofv3 prints them (profiles/*_kernel_stats.csv)",
+                        "valu": dom["valu"], "whole_proof": whole, "other_kernels": [kernel_roofline(n) for n in ranked[1:]]}
+            # `iso_name` = the kernel that does a kernel's job in the single-stream leg (the same name, unless a kernel has a shared-device shape of its own)
+            def iso_name(n):
+                if not prof_isolated:
+                    return None
+                if n in prof_isolated:
+                    return n
+                return next((x for x in SWEEPS if n in SWEEPS and x in prof_isolated), None)
+            if n_streams > 1 and iso_name(ranked[0]):
+                # with several proving streams a launch inside the timed steps shares the CUs with kernels of other proofs, and its duration says how
+                # the GPU was shared, not how good the kernel is (14 streams: 2.4 - 3.1 ms per sweep from run to run, 0.97 ms alone).  The headline
+                # figures of `roofline` are therefore the kernel ALONE on the GPU - HIP events in the single-stream leg of this same run, the
+                # command whose rocprofv3 --stats summary is profiles/*_kernel_stats_single_stream.csv - and the shared figures follow beside them
+                shared = {k: roofline[k] for k in ("launches", "avg_launch_ms", "alg_bytes_per_launch", "achieved", "frac", "device_GBps", "valu", "other_kernels")}
+                shared["note"] = ("the same kernel inside the timed steps, where %d proving streams share the GPU (HIP events on each stream, summed); "
+                                  "rocprofv3 --stats of the headline command: profiles/*_rocprof_kernel_stats.csv" % n_streams)
+                iso = kernel_roofline(iso_name(ranked[0]), prof_isolated)
+                for k in ("launches", "avg_launch_ms", "alg_bytes_per_launch", "achieved", "frac", "device_GBps", "valu"):
+                    roofline[k] = iso[k]
+                if iso["kernel"] != roofline["kernel"]:
+                    roofline["traffic"], roofline["traffic_useful_fetch"] = iso["traffic"], iso["traffic_useful_fetch"]      # the counter passes profile one stream alone
+                    roofline["kernel_alone"] = iso["kernel"]
+                    roofline["note"] += "; alone on the device this kernel's job is done by %s" % iso["kernel"]
+                roofline["other_kernels"] = [kernel_roofline(n, prof_isolated) for n in ranked[1:] if n in prof_isolated]
+                roofline["measured"] = ("kernel alone on the GPU: HIP events on the engine's stream in the single-stream leg of this run (one proving stream, one "
+                                        "chain thread; rocprofv3 --stats of that command: profiles/*_kernel_stats_single_stream.csv). `timed_steps_shared` = the "
+                                        "same kernel inside the timed steps of the headline")
+                roofline["timed_steps_shared"] = shared
+            elif n_streams > 1:
+                roofline["note"] += ("; %d proving streams share the GPU inside the timed steps, so a launch there overlaps kernels of another proof and lasts "
+                                     "longer than it does alone (run without --headline-only for the kernel alone)" % n_streams)
+        else:
+            roofline = {"bound": "hbm", "kernel": None, "achieved": 0.0, "peak": 8000.0, "unit": "GB/s", "frac": 0.0, "traffic": None, "whole_proof": whole,
+                        "note": "no fold / bucket-sweep launch in the timed steps (table-driven schedule at this size)"}
+        if ranked and roofline.get("kernel") in SWEEPS:
+            # both term counts of the bucket sweep: what the launches process - the rounds of a fold group run on the group-start tables
+            # with expanded scalars, so rounds 2 and 3 of a group visit as many terms as round 1 - and what the survey's round sizes add up to
+            # (A_I, A_O, S: 5n terms; L_k, R_k of round k: 2 N_k terms for the rounds above the table-driven tail)
+            N, k = a.gens_capacity, 0
+            survey_terms = 5 * inst.n
+            while (tt_lg == 0 or (N >> k) > (1 << tt_lg)) and (N >> k) > 1:
+                survey_terms += 2 * (N >> k); k += 1
+            iso = n_streams > 1 and prof_isolated and any(x in prof_isolated for x in SWEEPS)
+            src_prof = prof_isolated if iso else prof
+            sweeps = src_prof[next(x for x in SWEEPS if x in src_prof)]
+            proofs_seen = single["steps"] if iso else args.steps
+            processed = sweeps["alg_bytes"] / 64.0
+            secs = sweeps["total_ms"] * 1e-3
+            roofline["alg_terms_processed"] = processed / proofs_seen
+            roofline["alg_terms_survey"] = survey_terms
+            roofline["frac_survey_terms"] = (64.0 * survey_terms * proofs_seen / secs / 8e12) if secs > 0 else 0.0
+            roofline["terms_note"] = ("`frac` counts 64 B for every term a launch processes (alg_terms_processed per proof); `frac_survey_terms` counts the survey's "
+                                      "round sizes only (alg_terms_survey per proof) over the same launch time; per-proof figures assume %d proofs in the profiled "
+                                      "sequence" % proofs_seen)
+        fm_per_proof = sum(prof[n]["field_mults"] for n in prof) / max(args.steps, 1)
 
     out = {"metric": METRIC, "value": q_total * args.steps / elapsed,
            "unit": "constraints/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1229,14 +1253,23 @@ def run_rank(args):
         dist.destroy_process_group()
 
 
+def settle_legs(args):
+    """Which legs run: without --full only the headline (the secondary legs off, as --headline-only has them); --in-flight-only is a measurement
+    of its own (the throughput leg alone, --in-flight streams) and keeps its streams with or without --full."""
+    if not args.full and not args.in_flight_only:
+        args.headline_only = True
+    if args.headline_only:
+        args.no_cpu_baseline, args.in_flight = True, 0
+    return args
+
+
 def main():
     args = parse_args()
     if args.plan_only:
         topo = discover_topology(args.gpus) or synthetic_topology(args.gpus)
         print(json.dumps(plan_node(args.gpus, args.streams, args.steps if args.steps > 3 else 20, args.profile, topo)), flush=True)
         return
-    if args.headline_only:
-        args.no_cpu_baseline, args.in_flight = True, 0
+    settle_legs(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
     run_rank(args)

@@ -9,6 +9,7 @@ import socket
 import subprocess
 import sys
 import textwrap
+import time
 
 import pytest
 
@@ -103,7 +104,7 @@ def test_bench_spawns_its_own_ranks(leaves, steps):
     env = dict(os.environ, BPG_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", str(steps), "--warmup", "1", "--leaves", str(leaves), "--batch", "4",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--full", "--steps", str(steps), "--warmup", "1", "--leaves", str(leaves), "--batch", "4",
                         "--no-cpu-baseline", "--in-flight", "2", "--in-flight-steps", "4"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -126,6 +127,56 @@ def test_bench_spawns_its_own_ranks(leaves, steps):
     assert lone["profile"] == "serving" and lone["launches"] > 20 and 0 < lone["kernel_ms_sum"] < lone["wall_ms"] and lone["phase_ms"]["ipa"] > 0
     if leaves == 512:
         assert lone["launches"] <= 200, lone["launches"]                       # the round-4 review's bar for a 2^20 proof alone (198 since round 5)
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """bench.py without --full: set-up, warm-up, exactly --steps timed proofs and the line, no secondary leg.  --dump-outputs writes what the last
+    timed step returned (proof bytes, transcript state after the proof): the same on two runs, and the CPU oracle's bytes for that step's seed."""
+    import numpy as np
+    import bulletproofs_gadgets_amd as bpg
+    from bulletproofs_gadgets_amd import workloads
+    import oracle_lib as O
+    steps, dumps = 3, []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--leaves", "8", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == steps and out["warmup"] == 1 and out["value"] > 0 and out["ms_per_step"] > 0
+        assert out["unit"] == "constraints/s" and out["higher_is_better"] is True and out["dtype"] == "u32" and out["metric"]
+        assert out["roofline"] is None and out["lone_proof"] is None and out["single_stream"] is None and out["verify"] is None
+        for key in ("cpu_baseline", "throughput", "throughput_variants", "batch", "small_configs", "end_to_end", "value_one_shot", "gpu_busy"):
+            assert key not in out, key
+        got = {name: np.load(d / (name + ".npy")) for name in ("proof", "transcript_state")}
+        for v in got.values():
+            assert v.dtype == np.float64 and v.min() >= 0 and v.max() <= 255 and np.all(v == np.round(v))
+        dumps.append({name: bytes(v.astype(np.uint8)) for name, v in got.items()})
+    assert dumps[0] == dumps[1]
+    a = workloads.merkle_full_tree(bpg.Context(0), leaves=8)
+    inst = a.prover.instance()
+    oc = O.FlatCircuit(inst.n, inst.m, inst.aL, inst.aR, inst.aO, inst.row_ptr, inst.term_var, inst.term_coef, inst.coef)
+    seed = bytes([0, steps - 1, 0]) + bytes(29)                                # bench.py seed_for(steps - 1) on rank 0
+    rc, want, state = O.prove(O.Gens(a.gens_capacity), a.transcript.state, oc, inst.v_blinding, seed, O.FLAG_FAST_MSM)
+    assert rc == 0 and dumps[0]["proof"] == want and dumps[0]["transcript_state"] == state
+
+
+def test_plain_bench_at_the_headline_size_spends_little_outside_its_steps():
+    """A plain run at 2^20 (20 proving streams, serving tables) in a new process: the whole run from start to exit, less (steps + warmup) x
+    ms_per_step, is what set-up, warm-up beyond its steps and tear-down cost - well inside 30 s (about 5 s measured on one MI355X)."""
+    steps, warmup = 20, 5
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup)],
+                       capture_output=True, text=True, timeout=300)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["steps"] == steps and out["config"]["N"] == 1 << 20 and out["value"] > 0
+    outside = wall - (steps + warmup) * out["ms_per_step"] * 1e-3
+    print("plain run at 2^20: %.1f s in all, %.1f s outside its steps, %.2f ms per step" % (wall, outside, out["ms_per_step"]))
+    assert outside < 30.0, outside
 
 
 RCCL_WORKER = textwrap.dedent('''

@@ -271,6 +271,31 @@ def test_blinding_stream_needs_a_device_context():
     assert rc != 0 and b"" != bpg.lib().bpg_last_error()
 
 
+def test_bench_plain_run_options_and_output_dump(tmp_path):
+    """bench.py runs the secondary legs only under --full; --dump-outputs writes the caller's bytes of the last timed step as float64 arrays."""
+    import sys
+    import numpy as np
+    sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse_args(["--full", "--dump-outputs", str(tmp_path / "d")])
+    assert a.full is True and a.dump_outputs == str(tmp_path / "d")
+    # the legs main() runs: a plain run is the headline alone; --full keeps the defaults; --in-flight-only keeps the streams it is given
+    legs = lambda argv: (lambda x: (x.headline_only, x.no_cpu_baseline, x.in_flight))(bench.settle_legs(bench.parse_args(argv)))
+    assert legs(["--steps", "20"]) == (True, True, 0)
+    assert legs(["--full"]) == (False, False, 6)
+    assert legs(["--full", "--headline-only"]) == (True, True, 0)
+    assert legs(["--in-flight-only"]) == (False, False, 6)
+    assert legs(["--in-flight-only", "--in-flight", "12"]) == (False, False, 12)
+    assert legs(["--in-flight-only", "--in-flight", "12", "--full"]) == (False, False, 12)
+    proof, state = bytes(range(256)) * 3 + b"\x07", bytes(203)
+    bench.dump_outputs(tmp_path / "d" / "sub", (proof, state))
+    got = {n: np.load(tmp_path / "d" / "sub" / (n + ".npy")) for n in ("proof", "transcript_state")}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert bytes(got["proof"].astype(np.uint8)) == proof and bytes(got["transcript_state"].astype(np.uint8)) == state
+
+
 def test_bench_launcher_refuses_a_world_that_is_not_gpus(tmp_path):
     """bench.py --gpus N is one rank of N under torchrun and the launcher of N ranks otherwise; a mismatch must fail loudly, not run 1 rank."""
     import os, subprocess, sys

@@ -7,7 +7,7 @@
 #          one chain thread (kernels alone on the GPU), and of --in-flight-only  -> gpurun_out/<tag>_stats/, <tag>_stats_single/, <tag>_stats_inflight/
 #   pmc    two separate --pmc passes (FETCH_SIZE, WRITE_SIZE), kernel trace only                -> gpurun_out/<tag>_pmc_fetch/, <tag>_pmc_write/, <tag>_pmc_traffic.json
 #   pmcthr the same two --pmc passes over `bench.py --in-flight-only` (the concurrent mix of the throughput leg)               -> gpurun_out/<tag>_pmc_traffic_throughput.json
-#   bench  the default bench line exactly as the driver runs it (cpu_baseline, throughput, batch) -> gpurun_out/<tag>_bench_plain.json
+#   bench  the whole bench line, every leg of bench.py --full (cpu_baseline, throughput, batch)  -> <tag>_bench_plain.json in the same folder
 #   insts  VALU instruction budget of a proof per kernel under the shared-device variants (tools/diag/insts.sh: one --pmc pass, SQ counters) -> <tag>_insts_summary.{txt,json}
 #   mix    rocprofv3 kernel trace of `bench.py --in-flight-only` -> gap analysis (tools/diag/mix_timeline.py) -> <tag>_mix_timeline.txt
 #   mask   the concurrent mix with every gathered point index masked to an L2-resident table against the product build, alternating
@@ -46,19 +46,19 @@ if has inv; then
     echo "inv done"
 fi
 if has stats; then
-    (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/${tag}_stats" -o "$tag" -- python3 "$root/bench.py" --headline-only --steps 20 --warmup 5 > "$out/${tag}_bench_under_rocprof.json" 2> "$out/${tag}_stats.err") || { echo "stats pass failed"; tail -5 "$out/${tag}_stats.err"; exit 1; }
+    (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/${tag}_stats" -o "$tag" -- python3 "$root/bench.py" --full --headline-only --steps 20 --warmup 5 > "$out/${tag}_bench_under_rocprof.json" 2> "$out/${tag}_stats.err") || { echo "stats pass failed"; tail -5 "$out/${tag}_stats.err"; exit 1; }
     echo "stats done"
     # the same kernels alone on the GPU: one proving stream, one chain thread (the `isolated` figures of the bench line, the round-1 command)
-    (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/${tag}_stats_single" -o "$tag" -- python3 "$root/bench.py" --headline-only --streams 1 --chain-workers 1 --steps 5 --warmup 2 > "$out/${tag}_bench_single_under_rocprof.json" 2> "$out/${tag}_stats_single.err") || { echo "single-stream stats pass failed"; tail -5 "$out/${tag}_stats_single.err"; exit 1; }
+    (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/${tag}_stats_single" -o "$tag" -- python3 "$root/bench.py" --full --headline-only --streams 1 --chain-workers 1 --steps 5 --warmup 2 > "$out/${tag}_bench_single_under_rocprof.json" 2> "$out/${tag}_stats_single.err") || { echo "single-stream stats pass failed"; tail -5 "$out/${tag}_stats_single.err"; exit 1; }
     echo "single-stream stats done"
     # the concurrent mix of the throughput leg (6 proving streams, one chain thread with 8 lanes each, 24 proofs per stream): kernels of different proofs share the CUs
     (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/${tag}_stats_inflight" -o "$tag" -- python3 "$root/bench.py" --in-flight-only > "$out/${tag}_bench_inflight_under_rocprof.json" 2> "$out/${tag}_stats_inflight.err") || { echo "in-flight stats pass failed"; tail -5 "$out/${tag}_stats_inflight.err"; exit 1; }
     echo "in-flight stats done"
 fi
 if has pmc; then
-    (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$out/${tag}_pmc_fetch" -o "$tag" -- python3 "$root/bench.py" --headline-only --streams 1 --chain-workers 1 --steps 1 --warmup 1 > /dev/null 2> "$out/${tag}_pmc_fetch.err") || { echo "fetch pass failed"; tail -5 "$out/${tag}_pmc_fetch.err"; exit 1; }
+    (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$out/${tag}_pmc_fetch" -o "$tag" -- python3 "$root/bench.py" --full --headline-only --streams 1 --chain-workers 1 --steps 1 --warmup 1 > /dev/null 2> "$out/${tag}_pmc_fetch.err") || { echo "fetch pass failed"; tail -5 "$out/${tag}_pmc_fetch.err"; exit 1; }
     echo "fetch done"
-    (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$out/${tag}_pmc_write" -o "$tag" -- python3 "$root/bench.py" --headline-only --streams 1 --chain-workers 1 --steps 1 --warmup 1 > /dev/null 2> "$out/${tag}_pmc_write.err") || { echo "write pass failed"; tail -5 "$out/${tag}_pmc_write.err"; exit 1; }
+    (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$out/${tag}_pmc_write" -o "$tag" -- python3 "$root/bench.py" --full --headline-only --streams 1 --chain-workers 1 --steps 1 --warmup 1 > /dev/null 2> "$out/${tag}_pmc_write.err") || { echo "write pass failed"; tail -5 "$out/${tag}_pmc_write.err"; exit 1; }
     echo "write done"
     calib="$out/${tag}_fetch_calibration.json"; [ -f "$calib" ] || calib="$root/profiles/${tag}_fetch_calibration.json"; [ -f "$calib" ] || calib="$root/profiles/r02_fetch_calibration.json"
     python3 "$root/tools/pmc_summarize.py" "$(csv "$out/${tag}_pmc_fetch" counter_collection.csv)" "$(csv "$out/${tag}_pmc_write" counter_collection.csv)" "$calib" "$out/${tag}_pmc_traffic.json" || exit 1
@@ -73,7 +73,7 @@ if has pmcthr; then
     python3 "$root/tools/pmc_summarize.py" "$(csv "$out/${tag}_pmcthr_fetch" counter_collection.csv)" "$(csv "$out/${tag}_pmcthr_write" counter_collection.csv)" "$calib" "$out/${tag}_pmc_traffic_throughput.json" "$out/${tag}_pmcthr_fetch.json" || exit 1
 fi
 if has bench; then
-    timeout -k 10 800 python3 bench.py --steps 20 --warmup 5 > "$out/${tag}_bench_plain.json" 2> "$out/${tag}_bench_plain.err" || { echo "bench failed"; tail -5 "$out/${tag}_bench_plain.err"; exit 1; }
+    timeout -k 10 800 python3 bench.py --full --steps 20 --warmup 5 > "$out/${tag}_bench_plain.json" 2> "$out/${tag}_bench_plain.err" || { echo "bench failed"; tail -5 "$out/${tag}_bench_plain.err"; exit 1; }
     echo "bench done"
 fi
 if has insts; then
@@ -93,7 +93,7 @@ if has mask; then
 fi
 if has clock; then
     python3 "$root/tools/diag/clock_watch.py" "mix (6 proving streams)" -- python3 "$root/bench.py" --in-flight-only --in-flight-steps 48 > "$out/${tag}_clock.txt" 2> "$out/${tag}_clock.err" || true
-    python3 "$root/tools/diag/clock_watch.py" "one stream" -- python3 "$root/bench.py" --headline-only --streams 1 --chain-workers 1 --steps 5 --warmup 2 >> "$out/${tag}_clock.txt" 2>> "$out/${tag}_clock.err" || true
+    python3 "$root/tools/diag/clock_watch.py" "one stream" -- python3 "$root/bench.py" --full --headline-only --streams 1 --chain-workers 1 --steps 5 --warmup 2 >> "$out/${tag}_clock.txt" 2>> "$out/${tag}_clock.err" || true
     echo "clock done"
 fi
 if has lone; then
