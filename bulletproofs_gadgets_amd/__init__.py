@@ -47,6 +47,12 @@ class Timings(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class MsmSeg(C.Structure):
+    """bpg_msm_seg: one segment of bpg_test_msm."""
+    _fields_ = [("table", C.c_uint32), ("result", C.c_uint32), ("first", C.c_uint64), ("len", C.c_uint32), ("lgblk", C.c_uint32),
+                ("skip", C.c_void_p)]
+
+
 class Config(C.Structure):
     """bpg_config (include/bpg.h): zero / None fields fall back to the BPG_* environment variable, then to the profile's default."""
     _fields_ = [("struct_size", C.c_uint32), ("profile", C.c_uint32), ("table_budget_gb", C.c_double), ("chain_workers", C.c_uint32),
@@ -275,6 +281,30 @@ class Context:
         out = _buf(32)
         _chk(lib().bpg_msm_gens(self._h, C.c_uint64(first), C.c_uint64(len(s)), b"".join(s), b"".join(t), out))
         return out.raw
+
+    def test_msm(self, nmsm, segments, scalars):
+        """bpg_test_msm: the bucket-method MSM on a plan of nmsm results and up to 16 segments.  A segment is a dict: table ("G" or "H"),
+        first, len, result, lgblk (31 = contiguous) and skip (None, or a list of (len + 31) // 32 uint32 words: bit e set = element e takes no
+        part).  scalars: the canonical 32-byte scalars of all segments, in order (a list, or their concatenation).  Returns (nmsm compressed results, the evidence dict: the plan
+        the call took and the starts[] / heavy / medium state its kernels left)."""
+        import json
+        segs = (MsmSeg * max(len(segments), 1))()
+        keep = []
+        for k, g in enumerate(segments):
+            table = {"G": 0, "H": 1}.get(g["table"], g["table"])
+            skip = g.get("skip")
+            ptr = None
+            if skip is not None:
+                arr = (C.c_uint32 * max(len(skip), 1))(*skip)
+                keep.append(arr)
+                ptr = C.cast(arr, C.c_void_p)
+            segs[k] = MsmSeg(table, g["result"], g.get("first", 0), g["len"], g.get("lgblk", 31), ptr)
+        out = _buf(32 * max(nmsm, 1))
+        cap = (1 << 16) + 11 * (max(min(nmsm, 4), 1) * (1 << 19) + 1)     # starts[]: at most 2^19 buckets per result (16 windows of 16 bits), 10 digits and a comma each
+        ev = _buf(cap)
+        _chk(lib().bpg_test_msm(self._h, C.c_uint32(nmsm), C.c_uint32(len(segments)), segs, scalars if isinstance(scalars, (bytes, bytearray)) else b"".join(scalars),
+                                     out, ev, C.c_uint64(cap)))
+        return [out.raw[32 * m:32 * m + 32] for m in range(nmsm)], json.loads(ev.value.decode())
 
     def test_fe_ops(self, op, a_list, b_list):
         n = len(a_list)

@@ -214,6 +214,20 @@ bpg_status bpg_test_fe_ops(bpg_ctx *ctx, int32_t op, uint64_t n, const uint8_t *
 bpg_status bpg_msm_gens(bpg_ctx *ctx, uint64_t first, uint64_t count, const uint8_t *s, const uint8_t *t, uint8_t out[32]) {
     return guard([&] { REQUIRE(ctx && out && (count == 0 || (s && t))); ctx->engine->msm_gens(first, count, s, t, out); });
 }
+bpg_status bpg_test_msm(bpg_ctx *ctx, uint32_t nmsm, uint32_t nseg, const bpg_msm_seg *segs, const uint8_t *scalars, uint8_t *out,
+                        char *evidence, uint64_t cap) {
+    return guard([&] {
+        if (!ctx) throw DeviceError("test_msm: no device context (the MSM runs on the GPU only)");
+        REQUIRE(out && evidence && cap);
+        if (nseg > 16) throw std::invalid_argument("test_msm: at most 16 segments");
+        if (nseg && !segs) throw std::invalid_argument("test_msm: no segment array");
+        std::vector<Engine::MsmSegSpec> sp(nseg);
+        for (uint32_t k = 0; k < nseg; k++) sp[k] = {segs[k].table, segs[k].result, segs[k].first, segs[k].len, segs[k].lgblk, segs[k].skip};
+        const std::string r = ctx->engine->test_msm(nmsm, nseg, sp.data(), scalars, out);
+        if (r.size() + 1 > cap) throw std::invalid_argument("test_msm: evidence buffer too small (" + std::to_string(r.size() + 1) + " bytes needed)");
+        std::memcpy(evidence, r.c_str(), r.size() + 1);
+    });
+}
 
 bpg_status bpg_profile_set(bpg_ctx *ctx, int32_t mode) { return guard([&] { REQUIRE(ctx && mode >= 0 && mode <= 2); ctx->engine->profile_set(mode); }); }
 bpg_status bpg_profile_report(bpg_ctx *ctx, char *out, uint64_t cap) {

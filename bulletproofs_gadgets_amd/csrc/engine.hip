@@ -493,6 +493,14 @@ struct Engine::Impl {
     static constexpr uint32_t WS_SLOTS = 8, WS_SLOT_BYTES = 4 * 128 * 128;     // nmsm <= 4, W <= 127 (c >= 2), 128 B per point
     PinBuf h_wsums; uint32_t ws_next = 0;
     MsmTicket msm(const MsmSegs &S, uint32_t nmsm);
+    // what the last msm() call chose (host side only: read by the test hook Engine::test_msm after its stream sync, never on the proving path)
+    struct MsmLast {
+        MsmPlan P;
+        uint32_t nkeys = 0, CH = 0, nchunks = 0, live = 0;
+        bool shared = false, per_bucket = false, quad = false;
+        uint32_t window_blocks = 0, window_threads = 0;     // k_window_sums_quad: blocks per window; k_window_sums: threads per window
+    } msm_last;
+    DevBuf test_skip;                                       // skip bitmaps of Engine::test_msm
     std::vector<h51::pt> msm_points(const MsmTicket &t) const {
         std::vector<h51::pt> out(t.nmsm);
         const uint32_t *w = reinterpret_cast<const uint32_t *>(h_wsums.as<uint8_t>() + (size_t)t.slot * WS_SLOT_BYTES);
@@ -997,11 +1005,12 @@ Engine::Impl::MsmTicket Engine::Impl::msm(const MsmSegs &S, uint32_t nmsm) {
         msm_alg_discount = 0;
         // joining the pieces of buckets that cross chunk boundaries: one thread per boundary where chunks are at least as long as the average bucket
         // (the shared-device shape: 64-entry chunks, ~32 entries per bucket), one thread per bucket where buckets are longer (a proof alone)
-        if ((uint64_t)CH * nkeys >= Mub)
+        msm_last.per_bucket = (uint64_t)CH * nkeys < Mub;
+        if (!msm_last.per_bucket)
             BPG_LAUNCH((*this), k_bucket_combine, dim3(cdiv(nchunks, 256)), dim3(256), starts.as<uint32_t>(), buckets.as<ge_ext>(), slotA, slotB, open_keys.as<uint32_t>(), nkeys, CH, heavy.as<uint32_t>(), medium.as<uint32_t>());
         else
             BPG_LAUNCH_ID((*this), KID_k_bucket_combine, k_bucket_combine_per_bucket, dim3(cdiv(nkeys, 256)), dim3(256), starts.as<uint32_t>(), buckets.as<ge_ext>(), slotA, slotB, nkeys, CH, heavy.as<uint32_t>());
-        BPG_LAUNCH((*this), k_bucket_combine_heavy, dim3(512), dim3(256), starts.as<uint32_t>(), buckets.as<ge_ext>(), slotA, slotB, CH, heavy.as<uint32_t>(), medium.as<uint32_t>());
+        BPG_LAUNCH((*this), k_bucket_combine_heavy, dim3(HEAVY_BLOCKS), dim3(256), starts.as<uint32_t>(), buckets.as<ge_ext>(), slotA, slotB, CH, heavy.as<uint32_t>(), medium.as<uint32_t>());
     }
     const uint32_t nred = nmsm * W * nsegpw;
     BPG_LAUNCH((*this), k_bucket_reduce, dim3(cdiv(nred, 64)), dim3(64), buckets.as<ge_ext>(), starts.as<uint32_t>(), partial.as<ge_ext>(), nb, seg, nsegpw, nred);
@@ -1020,10 +1029,14 @@ Engine::Impl::MsmTicket Engine::Impl::msm(const MsmSegs &S, uint32_t nmsm) {
         if (nwin > 1024) throw std::logic_error("msm: too many windows for the ticket array");
         BPG_LAUNCH((*this), k_window_sums_quad, dim3(nblk, nwin), dim3(256), partial.as<ge_ext>(), wsums.as<ge_ext>(), wq_stage.as<ge_ext>(), wq_tickets.as<uint32_t>(), nsegpw, nred,
                    ceil_log2(seg), lgper);
+        msm_last.quad = true; msm_last.window_blocks = nblk; msm_last.window_threads = 0;
     } else {
     const uint32_t wthreads = std::max<uint32_t>(64, std::min<uint32_t>(nsegpw, shared_now ? 256u : 512u));
     BPG_LAUNCH((*this), k_window_sums, dim3(nmsm * W), dim3(wthreads), partial.as<ge_ext>(), wsums.as<ge_ext>(), nsegpw, nred, ceil_log2(seg));
+    msm_last.quad = false; msm_last.window_blocks = 0; msm_last.window_threads = wthreads;
     }
+    msm_last.P = P; msm_last.nkeys = nkeys; msm_last.CH = CH; msm_last.nchunks = nchunks; msm_last.live = live;
+    msm_last.shared = shared_now;
     HIPCHK(hipGetLastError());
     if ((size_t)nmsm * W * sizeof(ge_ext) > WS_SLOT_BYTES) throw std::logic_error("msm: window sums exceed the host slot");
     h_wsums.ensure((size_t)WS_SLOTS * WS_SLOT_BYTES);
@@ -1062,6 +1075,90 @@ void Engine::msm_gens(uint64_t first, uint64_t count, const uint8_t *s, const ui
     const Impl::MsmTicket tk = I.msm(S, 1);
     HIPCHK(hipStreamSynchronize(I.st));
     h51::pt_compress(out, I.msm_points(tk)[0]);
+}
+
+std::string Engine::test_msm(uint32_t nmsm, uint32_t nseg, const MsmSegSpec *segs, const uint8_t *scalars, uint8_t *out) {
+    // every argument is checked here, before anything is queued: no index the caller chose reaches a kernel unchecked
+    if (nmsm < 1 || nmsm > 4) throw std::invalid_argument("test_msm: 1..4 results");
+    if (nseg > BPG_MAX_SEGS) throw std::invalid_argument("test_msm: at most 16 segments");
+    if (nseg && !segs) throw std::invalid_argument("test_msm: no segment array");
+    uint64_t total = 0, skipped = 0, skip_words = 0;
+    for (uint32_t k = 0; k < nseg; k++) {
+        const MsmSegSpec &g = segs[k];
+        if (g.table > 1) throw std::invalid_argument("test_msm: table is 0 (G) or 1 (H)");
+        if (g.result >= nmsm) throw std::invalid_argument("test_msm: result index out of range");
+        if (k && g.result < segs[k - 1].result) throw std::invalid_argument("test_msm: segments must be grouped by ascending result index");
+        if (g.lgblk > 31) throw std::invalid_argument("test_msm: lgblk is 0..30, or 31 (contiguous)");
+        if (!g.len) continue;
+        const uint64_t e = g.len - 1, lg = g.lgblk;
+        const uint64_t last = lg >= 31 ? e : (((e >> lg) << (lg + 1)) | (e & ((1ull << lg) - 1)));     // msm_point_index of the last element: the highest
+        if (g.first >= gens_cap_ || last >= gens_cap_ - g.first) throw std::invalid_argument("test_msm: segment reaches beyond the generator table");
+        total += g.len;
+        if (g.skip) {
+            for (uint64_t i = 0; i < g.len; i++) skipped += (g.skip[i >> 5] >> (i & 31)) & 1u;
+            skip_words += (g.len + 31) / 32;
+        }
+    }
+    if (total >= (1ull << 31)) throw std::invalid_argument("test_msm: too many terms");
+    if (total && !scalars) throw std::invalid_argument("test_msm: no scalars");
+    for (uint64_t i = 0; i < total; i++) {
+        Scalar s; std::memcpy(s.w, scalars + 32 * i, 32);
+        if (!s.is_canonical()) throw std::invalid_argument("test_msm: scalar " + std::to_string(i) + " is not canonical");
+    }
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    I.shared_now = I.shared_variants();
+    I.small_sc.ensure(total * 32 + 64); I.sLR.ensure(total * sizeof(scm) + 64); I.test_skip.ensure(skip_words * 4 + 4);
+    if (total) {
+        I.h2d(I.small_sc.p, scalars, total * 32);
+        BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(total, 256)), dim3(256), I.small_sc.as<uint32_t>(), I.sLR.as<scm>(), (uint32_t)total);
+    }
+    MsmSegs S = seg_new();
+    uint64_t t0 = 0, w0 = 0;
+    for (uint32_t k = 0; k < nseg; k++) {
+        const MsmSegSpec &g = segs[k];
+        if (!g.len) continue;
+        const uint32_t *skip = nullptr;
+        if (g.skip) {
+            const uint64_t nw = (g.len + 31) / 32;
+            I.h2d(I.test_skip.as<uint32_t>() + w0, g.skip, nw * 4);
+            skip = I.test_skip.as<uint32_t>() + w0; w0 += nw;
+        }
+        seg_push(S, I.sLR.as<scm>() + t0, I.gens.as<ge_niels>() + (g.table ? gens_cap_ : 0) + g.first, g.len, g.result, g.lgblk, skip);
+        t0 += g.len;
+    }
+    I.msm_skipped_terms = (uint32_t)skipped;
+    const Impl::MsmTicket tk = I.msm(S, nmsm);
+    HIPCHK(hipStreamSynchronize(I.st));
+    const std::vector<h51::pt> pts = I.msm_points(tk);
+    for (uint32_t m = 0; m < nmsm; m++) h51::pt_compress(out + 32 * m, pts[m]);
+    // evidence: the plan msm() took, and what its kernels left on the device
+    const Impl::MsmLast &L = I.msm_last;
+    std::vector<uint32_t> st(L.nkeys + 1);
+    uint32_t hm[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(st.data(), I.starts.p, st.size() * 4, hipMemcpyDeviceToHost, I.st));
+    HIPCHK(hipMemcpyAsync(hm, I.heavy.p, 4, hipMemcpyDeviceToHost, I.st));
+    HIPCHK(hipMemcpyAsync(hm + 1, I.medium.p, 4, hipMemcpyDeviceToHost, I.st));
+    HIPCHK(hipStreamSynchronize(I.st));
+    const MsmPlan &P = L.P;
+    std::string j;
+    j.reserve(512 + st.size() * 11);
+    auto u = [&](const char *k, uint64_t v) { j += "\""; j += k; j += "\": "; j += std::to_string(v); j += ", "; };
+    j += "{";
+    u("nmsm", P.nmsm); u("W", P.W); u("nb", P.nb); u("fb", P.fb); u("CB", P.CB); u("lgTile", P.lgTile); u("tmax", P.tmax);
+    u("CH", L.CH); u("nchunks", L.nchunks); u("nkeys", L.nkeys); u("live", L.live); u("skipped", skipped);
+    j += "\"off\": [";
+    for (uint32_t w = 0; w <= P.W; w++) { if (w) j += ", "; j += std::to_string(P.off[w]); }
+    j += "], \"shared\": "; j += L.shared ? "true" : "false";
+    j += ", \"combine\": \""; j += L.per_bucket ? "per_bucket" : "boundary";
+    j += "\", \"window_sums\": \""; j += L.quad ? "quad" : "plain"; j += "\", ";
+    u("window_blocks", L.window_blocks); u("window_threads", L.window_threads);
+    u("sort2_regs", 256u * SORT2_PER); u("msm_stash", MSM_STASH); u("heavy_chunks", HEAVY_CHUNKS); u("heavy_blocks", HEAVY_BLOCKS);
+    u("heavy", hm[0]); u("medium", hm[1]);
+    j += "\"starts\": [";
+    for (size_t i = 0; i < st.size(); i++) { if (i) j += ","; j += std::to_string(st[i]); }
+    j += "]}";
+    return j;
 }
 
 // ------------------------------------------------------------------------------------------------ circuit upload

@@ -65,6 +65,10 @@ public:
     void pedersen_commit(size_t k, const uint8_t *v, const uint8_t *blind, uint8_t *out);
     // multiscalar multiplication over generator-table slices, for tests: sum s_i * G[first+i] + t_i * H[first+i]
     void msm_gens(uint64_t first, uint64_t count, const uint8_t *s, const uint8_t *t, uint8_t out[32]);
+    // the same kernels on any plan the prove path builds (include/bpg.h bpg_test_msm): nmsm compressed results, and a JSON text of the plan the
+    // call took and the device state it left (starts[] of every bucket, the heavy and medium list counts)
+    struct MsmSegSpec { uint32_t table, result; uint64_t first; uint32_t len, lgblk; const uint32_t *skip; };
+    std::string test_msm(uint32_t nmsm, uint32_t nseg, const MsmSegSpec *segs, const uint8_t *scalars, uint8_t *out);
 
     DeviceCircuit *upload(const FlatView &c);
     DeviceCircuit *upload(const FlatCircuit &c) { return upload(FlatView(c)); }

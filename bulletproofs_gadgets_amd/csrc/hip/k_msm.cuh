@@ -391,6 +391,7 @@ __global__ void __launch_bounds__(256) k_bucket_chunks(MsmSegs S, const uint32_t
 // the first IPA round, repeated witness values) goes on the heavy list for k_bucket_combine_heavy.  Empty buckets are never written: the
 // epilogue (k_bucket_reduce) takes the identity for a bucket whose range is empty.
 #define HEAVY_CHUNKS 32
+#define HEAVY_BLOCKS 512                // grid of k_bucket_combine_heavy: a longer heavy list takes several trips of its grid-stride loop
 __global__ void __launch_bounds__(256) k_bucket_combine(const uint32_t *__restrict__ starts, ge_ext *__restrict__ buckets,
                                                         const ge_ext *__restrict__ slotA, const ge_ext *__restrict__ slotB,
                                                         const uint32_t *__restrict__ open_key, uint32_t nkeys, uint32_t CH,

@@ -80,7 +80,7 @@ typedef struct {
 /* ABI version of this header.  Rules: structs the CALLER allocates either carry a struct_size (bpg_config: fields are only ever added at the end and
  * read when struct_size covers them) or are frozen (bpg_timings, bpg_r1cs_instance, bpg_batch_item, bpg_term, bpg_lc); a field never changes type or
  * meaning; BPG_ABI_VERSION grows with every addition.  A host checks bpg_abi_version() >= the BPG_ABI_VERSION it was compiled against. */
-#define BPG_ABI_VERSION 5u
+#define BPG_ABI_VERSION 6u
 uint32_t bpg_abi_version(void);
 const char *bpg_strerror(bpg_status s);
 const char *bpg_last_error(void);                                /* message of the calling thread's last failure */
@@ -189,6 +189,21 @@ uint64_t bpg_table_bytes(bpg_ctx *ctx);
 int32_t bpg_ctx_last_shared_variants(bpg_ctx *ctx);
 /* test hook: compress(sum s_i*G[first+i] + t_i*H[first+i]) through the bucket-method MSM kernels */
 bpg_status bpg_msm_gens(bpg_ctx *ctx, uint64_t first, uint64_t count, const uint8_t *s, const uint8_t *t, uint8_t out[32]);
+/* test hook: the bucket-method MSM on any plan the prove path builds.  A segment (frozen struct) is `len` terms on generator table `table`
+ * (0 = G, 1 = H) from generator `first`; lgblk 31 = contiguous, else element e is point first + ((e >> lgblk) << (lgblk+1)) | (e & (2^lgblk - 1));
+ * skip = NULL or (len + 31) / 32 words, bit e set = element e takes no part.  Segments are grouped by ascending result (< nmsm <= 4), at most 16 of
+ * them; `scalars` holds the canonical 32-byte scalars of all segments in order.  out = nmsm compressed results.  evidence = JSON text of the plan
+ * the call took (W, off[], nb, fb, CB, lgTile, tmax, CH, nchunks, shared-device variants, combine and window-sum variants), the thresholds the
+ * sort and the combine compare against, and the device state it left: starts[0..nkeys] of every bucket, the heavy and medium list counts.
+ * Every argument is checked before a launch (BPG_ERR_INVALID_ARGUMENT); a NULL ctx is BPG_ERR_DEVICE, as on a machine without a GPU. */
+typedef struct {
+    uint32_t table, result;
+    uint64_t first;
+    uint32_t len, lgblk;
+    const uint32_t *skip;
+} bpg_msm_seg;
+bpg_status bpg_test_msm(bpg_ctx *ctx, uint32_t nmsm, uint32_t nseg, const bpg_msm_seg *segs, const uint8_t *scalars, uint8_t *out,
+                        char *evidence, uint64_t cap);
 
 /* ---------------------------------------------------------------------------------------------------- PART 2: host mirror
  * merlin::Transcript, bulletproofs::r1cs::{Prover, Verifier}, and the reference's Gadget trait with BoundsCheck,

@@ -37,6 +37,22 @@ def test_no_device_fails_loudly():
     assert e.value.status == 7
 
 
+def test_msm_hook_without_device_fails_loudly():
+    # bpg_test_msm has no CPU path either: without a context (none can be made without a GPU) it is a DEVICE_ERROR, and nothing is written
+    import ctypes as C
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    with pytest.raises(bpg.BpgError) as e:
+        bpg.Context(0)
+    assert e.value.status == 7
+    segs = (bpg.MsmSeg * 2)(bpg.MsmSeg(0, 0, 0, 1, 31, None), bpg.MsmSeg(1, 0, 0, 1, 31, None))
+    out, ev = C.create_string_buffer(b"\x5a" * 32, 32), C.create_string_buffer(b"\x5a" * 64, 64)
+    assert bpg.lib().bpg_test_msm(None, C.c_uint32(1), C.c_uint32(2), segs, sc(1) + sc(2), out, ev, C.c_uint64(64)) == 7
+    assert b"device" in bpg.lib().bpg_last_error()
+    assert out.raw == b"\x5a" * 32 and ev.raw == b"\x5a" * 64
+
+
 def test_host_scalar_semantics():
     vals = [0, 1, R.L - 1, R.L, R.L + 5, 2**255 - 1, 2**256 - 1] + [int.from_bytes(hashlib.sha256(b"%d" % i).digest(), "little") for i in range(40)]
     for i, a in enumerate(vals):
