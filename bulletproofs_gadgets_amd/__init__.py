@@ -412,6 +412,78 @@ def _verify_flat(ctx, inst, transcript_state, commitments, proof, seed=None, fla
     return lib().bpg_r1cs_verify(ctx._h, C.byref(cs), ts, C.c_uint64(inst.m), commitments, proof, C.c_uint64(len(proof)), seed, C.c_uint32(flags))
 
 
+class VerifyItem(C.Structure):
+    """bpg_verify_item (frozen): one proof of bpg_r1cs_verify_batch."""
+    _fields_ = [("inst", C.POINTER(R1CSInstance)), ("circuit", C.c_void_p), ("transcript_state", C.c_void_p), ("m", C.c_uint64), ("V", C.c_char_p),
+                ("proof", C.c_char_p), ("proof_len", C.c_uint64), ("seed", C.c_char_p), ("flags", C.c_uint32)]
+
+
+def _verify_items(items):
+    """[(FlatInstance | ResidentCircuit, transcript_state, commitments, proof, seed=None, flags=0)] -> (VerifyItem array, state buffers, keep-alive)"""
+    n = len(items)
+    arr = (VerifyItem * max(n, 1))()
+    states, keep = [], []
+    for k, it in enumerate(items):
+        target, state, coms, proof = it[0], it[1], it[2], it[3]
+        seed = _seed32(it[4] if len(it) > 4 else None)
+        flags = it[5] if len(it) > 5 else 0
+        ts = _buf(203); ts.raw = _exact("transcript_state", state, 203)
+        coms, proof = _exact("commitments", coms, 32 * target.m), bytes(proof)
+        if isinstance(target, ResidentCircuit):
+            arr[k].circuit = target._h
+        else:
+            cs = target.cstruct()
+            cs.aL = cs.aR = cs.aO = None                        # verifier side: no assignments
+            arr[k].inst = C.pointer(cs)
+            keep.append(cs)
+        arr[k].transcript_state = C.cast(ts, C.c_void_p); arr[k].m = target.m; arr[k].V = coms
+        arr[k].proof = proof; arr[k].proof_len = len(proof); arr[k].seed = seed; arr[k].flags = flags
+        states.append(ts); keep.append((coms, proof, seed))
+    return arr, states, keep
+
+
+def _context_verify_batch(self, items, batch_seed=None, return_status=False):
+    """bpg_r1cs_verify_batch: items = [(FlatInstance | ResidentCircuit, transcript_state, commitments, proof, seed=None, flags=0)] ->
+    (statuses, transcript states after); each status is what verify_flat / ResidentCircuit.verify gives for that item alone.  All items go into ONE
+    multiscalar multiplication with random weights (batch_seed: fresh randomness unless pinned).  return_status=True: (call status, statuses, states).
+    A refused call (INVALID_ARGUMENT) or a device failure raises BpgError."""
+    arr, states, keep = _verify_items(items)
+    n = len(items)
+    status = (C.c_int32 * max(n, 1))()
+    rc = lib().bpg_r1cs_verify_batch(self._h, C.c_uint64(n), arr, _seed32(batch_seed), status)
+    if rc not in (0, 1, 2, 3):
+        _chk(rc)
+    out = ([status[k] for k in range(n)], [ts.raw[:203] for ts in states])
+    return (rc,) + out if return_status else out
+
+
+Context.verify_batch = _context_verify_batch
+
+
+def verify_batch(ctx, verifiers, proofs, bp_gens, seeds=None, flags=0, batch_seed=None):
+    """Verifier::verify of many bpg.Verifier objects in one bpg_r1cs_verify_batch call -> list of statuses (0 accepted, 1 INVALID_GENERATORS_LENGTH,
+    2 FORMAT_ERROR, 3 VERIFICATION_ERROR), each what Verifier.verify(proof, ctx, bp_gens, seed, flags) decides alone.  The verifiers' own
+    transcripts are left as they are."""
+    capacity = bp_gens.gens_capacity if isinstance(bp_gens, BulletproofGens) else int(bp_gens)
+    ctx.gens_ensure(capacity)
+    statuses, items, where = [None] * len(verifiers), [], []
+    for k, (v, proof) in enumerate(zip(verifiers, proofs)):
+        inst = v.instance()
+        N = 1
+        while N < inst.n:
+            N *= 2
+        if capacity < N:
+            statuses[k] = 1
+            continue
+        items.append((inst, v.transcript.state, inst.commitments, proof, seeds[k] if seeds else None, flags))
+        where.append(k)
+    if items:
+        st, _ = ctx.verify_batch(items, batch_seed)
+        for k, s in zip(where, st):
+            statuses[k] = s
+    return statuses
+
+
 class _BatchItem(C.Structure):
     _fields_ = [("inst", C.POINTER(R1CSInstance)), ("transcript_state", C.c_void_p), ("m", C.c_uint64), ("v_blinding", C.c_char_p),
                 ("rng_seed", C.c_char_p), ("flags", C.c_uint32), ("proof_out", C.c_void_p), ("proof_len", C.POINTER(C.c_uint64))]

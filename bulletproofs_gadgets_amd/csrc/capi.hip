@@ -315,6 +315,48 @@ bpg_status bpg_r1cs_verify_resident(bpg_ctx *ctx, bpg_circuit *c, uint8_t ts[BPG
     });
 }
 
+bpg_status bpg_r1cs_verify_batch(bpg_ctx *ctx, uint64_t count, const bpg_verify_item *items, const uint8_t batch_seed[32], bpg_status *status_out) {
+    return guard([&] {
+        REQUIRE(ctx);
+        if (!count) return;
+        REQUIRE(items && status_out && batch_seed);
+        // every argument first: a refused call launches nothing and touches no transcript state
+        std::vector<FlatView> views(count);
+        std::vector<Transcript> T(count);
+        std::vector<Engine::VerifyItem> ei(count);
+        for (uint64_t k = 0; k < count; k++) {
+            const bpg_verify_item &it = items[k];
+            const std::string who = "verify_batch: item " + std::to_string(k);
+            if ((it.inst != nullptr) == (it.circuit != nullptr)) throw std::invalid_argument(who + ": exactly one of inst and circuit must be set");
+            if (!it.transcript_state || !it.proof || !it.seed || (it.m && !it.V)) throw std::invalid_argument(who + ": null argument");
+            Engine::VerifyItem &e = ei[k];
+            if (it.inst) {
+                views[k] = as_view(it.inst, false, true);               // verifier side: no assignments
+                if (views[k].m != it.m) throw std::invalid_argument(who + ": m does not match the instance");
+                Engine::check_instance(views[k]);
+                e.flat = &views[k];
+            } else {
+                if (it.m != it.circuit->m) throw std::invalid_argument(who + ": m does not match the uploaded circuit");
+                e.dc = it.circuit->dc;
+            }
+            T[k] = Transcript::from_state(it.transcript_state);
+            e.T = &T[k]; e.V = it.V; e.proof = it.proof; e.proof_len = it.proof_len; e.seed = it.seed; e.flags = it.flags;
+        }
+        std::vector<R1CSError> st(count);
+        ctx->engine->verify_batch(count, ei.data(), batch_seed, st.data());
+        uint64_t first = count;
+        for (uint64_t k = 0; k < count; k++) {
+            T[k].export_state(items[k].transcript_state);
+            status_out[k] = (bpg_status)st[k];
+            if (first == count && st[k] != R1CSError::None) first = k;
+        }
+        if (first < count) {
+            const R1CSError e = st[first];
+            throw R1CSException(e, "item " + std::to_string(first) + ": " + (e == R1CSError::VerificationError ? "proof rejected" : e == R1CSError::FormatError ? "malformed proof" : "generator capacity below padded circuit size"));
+        }
+    });
+}
+
 // ---------------------------------------------------------------------------------------- batch pool
 struct bpg_pool { std::vector<bpg_ctx *> ctxs; };
 bpg_status bpg_pool_create(int32_t device, uint32_t workers, uint64_t gens_capacity, bpg_pool **out) { return bpg_pool_create_ex(device, workers, gens_capacity, nullptr, out); }

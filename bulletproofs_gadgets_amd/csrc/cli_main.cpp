@@ -5,6 +5,8 @@
 //     bpg_verifier NAME    reads NAME.gadgets / NAME.inst / NAME.coms / NAME.proof, prints true|false, exit code 0|1
 //
 //     bpg_prover | bpg_verifier --batch FILE [--gpus N] [--workers W]
+//     bpg_verifier --batch FILE [--gpus N] [--workers W] --combine
+//                          the same verdicts, each worker checking up to 64 stems at a time in one bpg_r1cs_verify_batch call
 //                          FILE lists one NAME per line - a batch of independent proofs (the reference's own batch is its CI workflow, prover then
 //                          verifier over twelve stems: .github/workflows/integration_tests.yml:19-58).  One process per GPU (the command starts them
 //                          itself, before it touches the GPU); rank r takes stems r, r + N, ..., deals them to W host threads (default 4) with an
@@ -17,8 +19,10 @@
 // Blinding factors: 64 bytes of /dev/urandom reduced mod l per factor (the reference uses thread_rng()); with BPG_CLI_SEED set they
 // come from SHAKE256(seed || counter) so that two runs - and the Python driver bulletproofs_gadgets_amd/cli.py - produce the same
 // files.  BPG_CLI_RNG_SEED (64 hex digits) fixes the 32 bytes that replace upstream's thread_rng() inside prove().
+#include <array>
 #include <cctype>
 #include <chrono>
+#include <memory>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -547,11 +551,13 @@ struct VerifierRun {
         if (closing) fail("unexpected end of input");
         return i;
     }
-    int run() {
+    Bytes proof;
+    // everything up to verify(): the files read, the commitments made, the gadgets assembled on the verifier
+    void assemble() {
         chk(bpg_transcript_new(reinterpret_cast<const uint8_t *>(name.data()), name.size(), &tr), "Transcript::new");
         chk(bpg_verifier_new(tr, &v), "Verifier::new");
         std::ifstream pf(name + ".proof", std::ios::binary); if (!pf) fail("cannot open " + name + ".proof");
-        Bytes proof((std::istreambuf_iterator<char>(pf)), std::istreambuf_iterator<char>());
+        proof.assign(std::istreambuf_iterator<char>(pf), std::istreambuf_iterator<char>());
         for (auto &kv : read_vars(name + ".inst")) instance[kv.first] = kv.second;
         for (auto &kv : read_vars(name + ".coms")) {                      // parse_coms: every line, file order
             if (kv.second.size() != 32) fail("commitment " + kv.first + " is not 32 bytes");
@@ -560,6 +566,9 @@ struct VerifierRun {
         lines = read_lines(name + ".gadgets");
         Cs top; top.v = v;
         run_block(0, top, 0);
+    }
+    int run() {
+        assemble();
         if (assemble_only) return 0;
         if (!ctx) chk(bpg_ctx_create(0, &ctx), "bpg_ctx_create");
         const uint64_t cap = round_pow2(bpg_verifier_num_vars(v));
@@ -591,7 +600,11 @@ std::vector<std::string> read_batch(const std::string &path) {
 // (0.5 s at 2^20) and the GPU for 30 ms, so a few workers per GPU multiply the rate of a batch; every stem is still proved exactly as a lone
 // `bpg_prover NAME` run would prove it (own transcript, own blinding stream).  A result line per stem on `out`:
 // "<index>\t<constraints>\t<proof bytes>" (prover) or "<index>\t<true|false>" (verifier)
-int run_batch_rank(const std::string &mode, const std::vector<std::string> &stems, uint32_t rank, uint32_t world, uint32_t workers, FILE *out) {
+// --combine (verifier): a worker takes up to COMBINE_CHUNK stems at a time, assembles their verifiers and checks them in ONE bpg_r1cs_verify_batch
+// call (one weighted multiscalar multiplication); the result lines and exit codes are those of the run without --combine
+constexpr size_t COMBINE_CHUNK = 64;
+std::string one_line(std::string msg) { for (char &ch : msg) if (ch == '\n' || ch == '\t' || ch == '\r') ch = ' '; return msg; }
+int run_batch_rank(const std::string &mode, const std::vector<std::string> &stems, uint32_t rank, uint32_t world, uint32_t workers, FILE *out, bool combine = false) {
     const int32_t ndev = bpg_device_count();
     if (ndev <= 0) fail("no AMD GPU visible: the library has no CPU path");
     std::vector<size_t> mine;
@@ -602,10 +615,77 @@ int run_batch_rank(const std::string &mode, const std::vector<std::string> &stem
     std::atomic<int> rc(0);
     std::mutex out_mu; std::string first_error;
     auto note_error = [&](const std::string &what) { std::lock_guard<std::mutex> lk(out_mu); if (first_error.empty()) first_error = what; rc.store(101); };
+    auto combined = [&](bpg_ctx *ctx) {
+        for (;;) {
+            const size_t k0 = next.fetch_add(COMBINE_CHUNK);
+            if (k0 >= mine.size()) break;
+            const size_t k1 = std::min(mine.size(), k0 + COMBINE_CHUNK);
+            std::vector<std::unique_ptr<VerifierRun>> runs;
+            std::vector<std::string> text(k1 - k0);
+            std::vector<size_t> at;                                  // runs[j] is stem mine[at[j]]
+            std::vector<bpg_r1cs_instance> insts(k1 - k0);
+            std::vector<std::array<uint8_t, 203>> ts(k1 - k0);
+            std::vector<Bytes> seeds;
+            std::vector<const uint8_t *> coms;
+            uint64_t cap = 1;
+            for (size_t k = k0; k < k1; k++) {
+                const size_t i = mine[k];
+                std::unique_ptr<VerifierRun> r(new VerifierRun());
+                r->name = stems[i]; r->ctx = ctx; r->own_ctx = false; r->quiet = true;
+                try {
+                    r->assemble();                                   // a stem whose files do not parse is an ERROR line of its own
+                    const uint8_t *c = nullptr;
+                    chk(bpg_verifier_instance(r->v, &insts[runs.size()], &c), "Verifier::instance");
+                    chk(bpg_transcript_state(r->tr, ts[runs.size()].data()), "transcript state");
+                    cap = std::max<uint64_t>(cap, round_pow2(bpg_verifier_num_vars(r->v)));
+                    Bytes seed(32); { std::ifstream u("/dev/urandom", std::ios::binary); u.read(reinterpret_cast<char *>(seed.data()), 32); }
+                    seeds.push_back(seed); coms.push_back(c);
+                    runs.push_back(std::move(r)); at.push_back(k);
+                } catch (const std::exception &e) {
+                    text[k - k0] = std::to_string(i) + "\tERROR\t" + one_line(e.what()) + "\n";
+                    note_error(stems[i] + ": " + one_line(e.what()));
+                }
+            }
+            if (!runs.empty()) {
+                std::vector<bpg_verify_item> items(runs.size());
+                for (size_t j = 0; j < runs.size(); j++) {
+                    bpg_verify_item &it = items[j];
+                    std::memset(&it, 0, sizeof it);
+                    it.inst = &insts[j]; it.transcript_state = ts[j].data(); it.m = insts[j].m; it.V = coms[j];
+                    it.proof = runs[j]->proof.data(); it.proof_len = runs[j]->proof.size(); it.seed = seeds[j].data(); it.flags = 0;
+                }
+                std::vector<bpg_status> st(runs.size(), BPG_ERR_INTERNAL);
+                Bytes batch_seed(32); { std::ifstream u("/dev/urandom", std::ios::binary); u.read(reinterpret_cast<char *>(batch_seed.data()), 32); }
+                bpg_status s = bpg_gens_ensure(ctx, cap);
+                std::string err = s == BPG_OK ? "" : std::string("BulletproofGens::new: ") + bpg_last_error();
+                if (s == BPG_OK) {
+                    s = bpg_r1cs_verify_batch(ctx, items.size(), items.data(), batch_seed.data(), st.data());
+                    if (s != BPG_OK && s != BPG_ERR_VERIFICATION && s != BPG_ERR_FORMAT && s != BPG_ERR_INVALID_GENERATORS_LENGTH)
+                        err = std::string("Verifier::verify: ") + bpg_last_error();
+                }
+                for (size_t j = 0; j < runs.size(); j++) {
+                    const size_t i = mine[at[j]];
+                    if (err.empty() && st[j] == BPG_OK) text[at[j] - k0] = std::to_string(i) + "\ttrue\n";
+                    else if (err.empty() && (st[j] == BPG_ERR_VERIFICATION || st[j] == BPG_ERR_FORMAT)) {
+                        text[at[j] - k0] = std::to_string(i) + "\tfalse\n";
+                        int want = 0; rc.compare_exchange_strong(want, 1);
+                    } else {
+                        const std::string msg = one_line(err.empty() ? std::string("Verifier::verify: ") + bpg_strerror(st[j]) : err);
+                        text[at[j] - k0] = std::to_string(i) + "\tERROR\t" + msg + "\n";
+                        note_error(stems[i] + ": " + msg);
+                    }
+                }
+            }
+            std::lock_guard<std::mutex> lk(out_mu);
+            for (const std::string &t : text) std::fputs(t.c_str(), out);
+            std::fflush(out);
+        }
+    };
     auto work = [&]() {
         bpg_ctx *ctx = nullptr;
         try { chk(bpg_ctx_create((int32_t)(rank % (uint32_t)ndev), &ctx), "bpg_ctx_create"); }
         catch (const std::exception &e) { note_error(e.what()); return; }       // no context, no work: the stems go to the other workers
+        if (combine) { combined(ctx); bpg_ctx_destroy(ctx); return; }
         for (;;) {
             const size_t k = next.fetch_add(1);
             if (k >= mine.size()) break;
@@ -656,7 +736,7 @@ bool profiler_preloaded() {
 }
 // the batch command: with one GPU it is the rank; with --gpus N it starts N ranks of this executable (nothing here has touched the GPU), reads their
 // result lines from pipes and prints the summary in file order.  Exit code: 0, 1 when a proof was rejected, 101 when a rank failed (the reference panics).
-int run_batch(const std::string &self_path, const std::string &mode, const std::string &file, uint32_t gpus, uint32_t workers) {
+int run_batch(const std::string &self_path, const std::string &mode, const std::string &file, uint32_t gpus, uint32_t workers, bool combine = false) {
     const std::vector<std::string> stems = read_batch(file);
     std::vector<std::string> result(stems.size());
     int rc = 0;
@@ -670,7 +750,7 @@ int run_batch(const std::string &self_path, const std::string &mode, const std::
         char *buf = nullptr; size_t len = 0;
         FILE *mem = open_memstream(&buf, &len);
         if (!mem) fail("open_memstream");
-        try { rc = run_batch_rank(mode, stems, 0, 1, workers, mem); } catch (...) { std::fclose(mem); std::free(buf); throw; }
+        try { rc = run_batch_rank(mode, stems, 0, 1, workers, mem, combine); } catch (...) { std::fclose(mem); std::free(buf); throw; }
         std::fclose(mem);
         std::istringstream is(std::string(buf, len)); std::free(buf);
         for (std::string l; std::getline(is, l);) take(l);
@@ -686,7 +766,8 @@ int run_batch(const std::string &self_path, const std::string &mode, const std::
                 close(pfd[0]);
                 dup2(pfd[1], 3); if (pfd[1] != 3) close(pfd[1]);
                 const std::string rs = std::to_string(r), ws = std::to_string(gpus), ks = std::to_string(workers);
-                const char *args[] = {self_path.c_str(), mode.c_str(), "--batch", file.c_str(), "--rank", rs.c_str(), "--world", ws.c_str(), "--workers", ks.c_str(), nullptr};
+                const char *args[] = {self_path.c_str(), mode.c_str(), "--batch", file.c_str(), "--rank", rs.c_str(), "--world", ws.c_str(), "--workers", ks.c_str(),
+                                      combine ? "--combine" : nullptr, nullptr};
                 execv(self_path.c_str(), const_cast<char *const *>(args));
                 std::perror("execv"); _exit(127);
             }
@@ -742,6 +823,12 @@ int main(int argc, char **argv) {
         std::vector<std::string> a(argv + 1, argv + argc);
         std::string bmode = self.find("verifier") != std::string::npos ? "verifier" : "prover";
         if (!a.empty() && (a[0] == "prover" || a[0] == "verifier")) { bmode = a[0]; a.erase(a.begin()); }
+        bool combine = false;
+        for (auto it = a.begin(); it != a.end();) { if (*it == "--combine") { combine = true; it = a.erase(it); } else ++it; }
+        if (combine && (a.size() < 2 || a[0] != "--batch" || bmode != "verifier")) {
+            std::fprintf(stderr, "--combine: bpg_verifier --batch FILE [--gpus N] [--workers W] --combine only\n");
+            return 2;
+        }
         if (a.size() >= 2 && a[0] == "--batch") {
             try {
                 uint32_t gpus = 1, rank = 0, world = 0, workers = 4;
@@ -756,7 +843,7 @@ int main(int argc, char **argv) {
                 if (world) {
                     FILE *out = fdopen(3, "w");
                     if (!out) { std::fprintf(stderr, "rank %u: no result pipe\n", rank); return 101; }
-                    const int rc = run_batch_rank(bmode, read_batch(a[1]), rank, world, workers, out);
+                    const int rc = run_batch_rank(bmode, read_batch(a[1]), rank, world, workers, out, combine);
                     std::fclose(out);
                     return rc;
                 }
@@ -768,7 +855,7 @@ int main(int argc, char **argv) {
                     return 2;
                 }
                 char exe[4096]; const ssize_t n = readlink("/proc/self/exe", exe, sizeof exe - 1);
-                return run_batch(n > 0 ? std::string(exe, (size_t)n) : std::string(argv[0]), bmode, a[1], gpus, workers);
+                return run_batch(n > 0 ? std::string(exe, (size_t)n) : std::string(argv[0]), bmode, a[1], gpus, workers, combine);
             } catch (const std::exception &e) {
                 std::fprintf(stderr, "%s --batch: %s\n", bmode.c_str(), e.what());
                 return 101;

@@ -209,7 +209,7 @@ struct DeviceCircuit {
 #define BPG_KERNELS(X) X(k_gens_derive) X(k_normalize_niels) X(k_compress_niels) X(k_pedersen) X(k_sc_from_bytes) \
     X(k_sc_from_wide) X(k_blind_poison) X(k_exp_table) X(k_reduce_partials) X(k_flatten) X(k_flatten_const) X(k_poly_t) X(k_poly_eval) X(k_ipa_prep) \
     X(k_ipa_fold_scalars) X(k_fold_points) X(k_fold_points_reg) X(k_fold_points_split) X(k_fold_points_wnaf) X(k_fold_points_quad) X(k_fold_points_quadw) X(k_fold_points_regw) X(k_odd_start) X(k_odd_start_ext) X(k_dbl_times) X(k_odd_step) X(k_msm_digits) X(k_msm_scatter1) X(k_msm_sort2) X(k_scan_blocksums) \
-    X(k_scan_apply) X(k_bucket_chunks) X(k_bucket_combine) X(k_bucket_combine_heavy) X(k_bucket_reduce) X(k_window_sums) X(k_window_sums_quad) X(k_decompress) X(k_ipa_s) X(k_verify_scalars) X(k_bench_fe_mul) \
+    X(k_scan_apply) X(k_bucket_chunks) X(k_bucket_combine) X(k_bucket_combine_heavy) X(k_bucket_reduce) X(k_window_sums) X(k_window_sums_quad) X(k_decompress) X(k_ipa_s) X(k_verify_scalars) X(k_verify_scalars_acc) X(k_bench_fe_mul) \
     X(k_tt_bases) X(k_tt_multiples) X(k_tt_bases8) X(k_tt_multiples8) X(k_tt_round8) X(k_tt_factors) X(k_tt_advance) X(k_tt_round) X(k_tt_finish) X(k_blind_expand) X(k_tt_commit3) X(k_tt_commit3_finish) X(k_csc_count) X(k_csc_fill) X(k_csc_colptr) X(k_merge_insert) X(k_merge_plan) X(k_merge_groups) X(k_merge_members) X(k_merge_sum)
 enum KernelId {
 #define X(n) KID_##n,
@@ -298,6 +298,7 @@ struct Engine::Impl {
     DevBuf sLR, yinvpow, lv, rv, red_partial, red_out, raw_rng, extras;      // (y^i, z^j and the flattened weights: in the arena)
     DevBuf stale_flag;              // one word, zero unless k_sc_from_wide met a poisoned (never uploaded) draw: checked before a proof leaves prove()
     DevBuf ipa_s, ipa_tabA, ipa_tabB, naf, qsteps, vfy_in, vfy_pts, vfy_ok, vfy_sc, vfy_ch;
+    DevBuf vfy_small;               // verify_batch: per proof [w_V (m) | w_c | delta]
     // table-driven IPA tail (kernels.cuh k_tt_*): frozen-generator window tables, per-point factors, coefficient tables
     DevBuf tt_bases, tt_table, tt_f, tt_c, tt_partial, grp_c, ped_table, s_parts;
     // tt_table holds the tables of the ORIGINAL generators G[0..M0), H[0..M0) when tt_orig_M0 != 0: they survive across proofs (a circuit
@@ -662,7 +663,7 @@ Engine::~Engine() {
     DevBuf *bufs[] = {&impl_->bases, &impl_->scratch_ext, &impl_->comp, &impl_->small_in, &impl_->small_sc, &impl_->counts,
                       &impl_->starts, &impl_->cursor, &impl_->blocksum, &impl_->arena, &impl_->buckets, &impl_->partial, &impl_->msm_result,
                       &impl_->sLR, &impl_->yinvpow, &impl_->lv, &impl_->rv, &impl_->red_partial,
-                      &impl_->red_out, &impl_->raw_rng, &impl_->extras, &impl_->ipa_s, &impl_->ipa_tabA, &impl_->ipa_tabB, &impl_->naf, &impl_->qsteps, &impl_->wsums, &impl_->wq_stage, &impl_->wq_tickets, &impl_->vfy_in, &impl_->vfy_pts, &impl_->vfy_ok, &impl_->vfy_sc, &impl_->vfy_ch,
+                      &impl_->red_out, &impl_->raw_rng, &impl_->extras, &impl_->ipa_s, &impl_->ipa_tabA, &impl_->ipa_tabB, &impl_->naf, &impl_->qsteps, &impl_->wsums, &impl_->wq_stage, &impl_->wq_tickets, &impl_->vfy_in, &impl_->vfy_pts, &impl_->vfy_ok, &impl_->vfy_sc, &impl_->vfy_ch, &impl_->vfy_small,
                       &impl_->stale_flag, &impl_->tile_hist, &impl_->heavy, &impl_->plain, &impl_->open_keys, &impl_->medium, &impl_->tt_bases, &impl_->tt_table, &impl_->tt_f, &impl_->tt_c, &impl_->tt_partial, &impl_->grp_c, &impl_->ped_table, &impl_->s_parts, &impl_->starts1};
     for (DevBuf *b : bufs) b->release();
     impl_->shared.reset();                                   // the generator tables go with their last context
@@ -1162,6 +1163,24 @@ std::string Engine::test_msm(uint32_t nmsm, uint32_t nseg, const MsmSegSpec *seg
 }
 
 // ------------------------------------------------------------------------------------------------ circuit upload
+void Engine::check_instance(const FlatView &c) {
+    const uint64_t n = c.n, m = c.m, q = c.q, nnz = c.nnz, ncoef = c.ncoef;
+    const bool has_witness = !(!c.aL && !c.aR && !c.aO && n > 0);
+    if (has_witness && n > 0 && (!c.aL || !c.aR || !c.aO)) throw std::invalid_argument("upload: witness vectors must hold n scalars");
+    if (!c.row_ptr || c.row_ptr[0] != 0 || c.row_ptr[q] != nnz || (nnz && (!c.term_var || !c.term_coef)) || (ncoef && !c.coef)) throw std::invalid_argument("upload: malformed CSR");
+    if (n >= (1u << 27)) throw std::invalid_argument("upload: too many multipliers");
+    const uint64_t ncols = 3 * n + m + 1;
+    if (q >= (1ull << 32) || nnz >= (1ull << 32) || ncols >= (1ull << 32)) throw std::invalid_argument("upload: circuit too large");
+    for (uint64_t k = 0; k < nnz; k++) {
+        const uint32_t pv = c.term_var[k], kind = pv >> 29, idx = pv & 0x1fffffffu;
+        if (c.term_coef[k] >= ncoef) throw std::invalid_argument("upload: coefficient index out of range");
+        if (kind <= 2) { if (idx >= n) throw std::invalid_argument("upload: multiplier index out of range"); }
+        else if (kind == 3) { if (idx >= m) throw std::invalid_argument("upload: committed index out of range"); }
+        else if (kind != 4) throw std::invalid_argument("upload: bad variable kind");
+    }
+    for (uint64_t r = 0; r < q; r++) if (c.row_ptr[r] > c.row_ptr[r + 1]) throw std::invalid_argument("upload: malformed CSR");
+}
+
 DeviceCircuit *Engine::upload(const FlatView &c) {
     HIPCHK(hipSetDevice(device_));
     Impl &I = *impl_;
@@ -1980,31 +1999,40 @@ std::vector<uint8_t> Engine::prove(DeviceCircuit *c, Transcript &T, const std::v
 // ------------------------------------------------------------------------------------------------ verify
 // Verifier::verify (dalek r1cs/verifier.rs; reference call site src/bin/verifier.rs:89-90): Fiat-Shamir replay on the host,
 // then ONE multiscalar multiplication of 2N + m + 2 lgN + 13 terms through the same bucket-method kernels; accept iff it is the identity.
-R1CSError Engine::verify(DeviceCircuit *c, Transcript &T, const uint8_t *V, const uint8_t *proof, size_t proof_len, const uint8_t seed[32], uint32_t flags) {
-    HIPCHK(hipSetDevice(device_));
-    Impl &I = *impl_;
-    hipStream_t st = I.st;
-    I.shared_now = I.shared_variants();
-    const uint64_t n = c->n, m = c->m, q = c->q;
+namespace {
+const uint8_t kIdentity[32] = {0};      // compressed identity
+// R1CSProof::from_bytes and the Fiat-Shamir replay of Verifier::verify on the host: everything verify() and verify_batch() decide before device work
+struct VerifyReplay {
+    uint64_t n = 0, m = 0, N = 1;
+    uint32_t lgN = 0;
+    const uint8_t *pA[6] = {}, *pT[5] = {}, *pLR = nullptr;
+    Scalar tx, txb, eb, ipa, ipb, y, z, u_ch, x, w, r, yinv;
+    std::vector<Scalar> uk, ukinv;
+    uint32_t npts() const { return (uint32_t)(6 + m + 5 + 2 * lgN); }
+};
+R1CSError verify_replay(uint64_t n, uint64_t m, uint64_t gens_cap, Transcript &T, const uint8_t *proof, size_t proof_len, const uint8_t seed[32],
+                        uint32_t flags, VerifyReplay &R) {
     uint64_t N = 1; while (N < n) N <<= 1;
     const uint32_t lgN = ceil_log2(N);
+    R.n = n; R.m = m; R.N = N; R.lgN = lgN;
     const bool compact = flags & 1u, no_1phase = flags & 2u;
     const size_t need = (compact ? 1 + 11 * 32 : 14 * 32) + (2 * (size_t)lgN + 2) * 32;
     if (proof_len != need) return R1CSError::FormatError;
-    if (gens_cap_ < N) return R1CSError::InvalidGeneratorsLength;
+    if (gens_cap < N) return R1CSError::InvalidGeneratorsLength;
     if (lgN > 32) return R1CSError::FormatError;
     const uint8_t *in = proof;
     static const uint8_t ident[32] = {0};
     if (compact) { if (*in++ != 0) return R1CSError::FormatError; }
-    const uint8_t *pA[6] = {in, in + 32, in + 64, ident, ident, ident}; in += 96;
+    const uint8_t **pA = R.pA, **pT = R.pT;
+    pA[0] = in; pA[1] = in + 32; pA[2] = in + 64; pA[3] = pA[4] = pA[5] = ident; in += 96;
     if (!compact) { pA[3] = in; pA[4] = in + 32; pA[5] = in + 64; in += 96; }
-    const uint8_t *pT[5]; for (int k = 0; k < 5; k++) { pT[k] = in; in += 32; }
+    for (int k = 0; k < 5; k++) { pT[k] = in; in += 32; }
     Scalar sc5[5];                                   // t_x, t_x_blinding, e_blinding, a, b : must be canonical (R1CSProof::from_bytes)
     const uint8_t *ps[5] = {in, in + 32, in + 64, proof + proof_len - 64, proof + proof_len - 32};
     for (int k = 0; k < 5; k++) { std::memcpy(sc5[k].w, ps[k], 32); if (!sc5[k].is_canonical()) return R1CSError::FormatError; }
     in += 96;
-    const uint8_t *pLR = in;
-    const Scalar &tx = sc5[0], &txb = sc5[1], &eb = sc5[2], &ipa = sc5[3], &ipb = sc5[4];
+    R.pLR = in;
+    R.tx = sc5[0]; R.txb = sc5[1]; R.eb = sc5[2]; R.ipa = sc5[3]; R.ipb = sc5[4];
     auto is_ident = [](const uint8_t *p) { return std::memcmp(p, ident, 32) == 0; };
 
     T.append_u64("m", m);
@@ -2012,46 +2040,63 @@ R1CSError Engine::verify(DeviceCircuit *c, Transcript &T, const uint8_t *V, cons
     T.append_point("A_I1", pA[0]); T.append_point("A_O1", pA[1]); T.append_point("S1", pA[2]);
     if (!no_1phase) T.r1cs_1phase_domain_sep();
     T.append_point("A_I2", pA[3]); T.append_point("A_O2", pA[4]); T.append_point("S2", pA[5]);
-    const Scalar y = T.challenge_scalar("y"), z = T.challenge_scalar("z");
+    R.y = T.challenge_scalar("y"); R.z = T.challenge_scalar("z");
     static const char *tl[5] = {"T_1", "T_3", "T_4", "T_5", "T_6"};
     for (int k = 0; k < 5; k++) { if (is_ident(pT[k])) return R1CSError::VerificationError; T.append_point(tl[k], pT[k]); }
-    const Scalar u_ch = T.challenge_scalar("u"), x = T.challenge_scalar("x");
-    T.append_scalar("t_x", tx); T.append_scalar("t_x_blinding", txb); T.append_scalar("e_blinding", eb);
-    const Scalar w = T.challenge_scalar("w");
+    R.u_ch = T.challenge_scalar("u"); R.x = T.challenge_scalar("x");
+    T.append_scalar("t_x", R.tx); T.append_scalar("t_x_blinding", R.txb); T.append_scalar("e_blinding", R.eb);
+    R.w = T.challenge_scalar("w");
     T.innerproduct_domain_sep(N);
-    std::vector<Scalar> uk(lgN), ukinv(lgN);
+    R.uk.assign(lgN, Scalar()); R.ukinv.assign(lgN, Scalar());
     bool lr_ident = false;
     for (uint32_t k = 0; k < lgN; k++) {
-        const uint8_t *L = pLR + 64 * k, *R = L + 32;
-        lr_ident |= is_ident(L) || is_ident(R);
-        T.append_point("L", L); T.append_point("R", R);
-        uk[k] = T.challenge_scalar("u"); ukinv[k] = uk[k];
+        const uint8_t *Lp = R.pLR + 64 * k, *Rp = Lp + 32;
+        lr_ident |= is_ident(Lp) || is_ident(Rp);
+        T.append_point("L", Lp); T.append_point("R", Rp);
+        R.uk[k] = T.challenge_scalar("u"); R.ukinv[k] = R.uk[k];
     }
     if (lr_ident) return R1CSError::VerificationError;
-    if (lgN) Scalar::batch_invert(ukinv);
+    if (lgN) Scalar::batch_invert(R.ukinv);
     TranscriptRng rng = T.build_rng({}, seed);
-    const Scalar r = rng.random_scalar();
-    const Scalar yinv = y.invert();
-
-    // ---- device side
-    const uint32_t npts = (uint32_t)(6 + m + 5 + 2 * lgN);
-    std::vector<uint8_t> hpts((size_t)npts * 32);
-    {
-        size_t o = 0;
-        for (int k = 0; k < 6; k++) { std::memcpy(&hpts[o], pA[k], 32); o += 32; }
-        if (m) { std::memcpy(&hpts[o], V, m * 32); o += m * 32; }
-        for (int k = 0; k < 5; k++) { std::memcpy(&hpts[o], pT[k], 32); o += 32; }
-        for (uint32_t k = 0; k < lgN; k++) { std::memcpy(&hpts[o], pLR + 64 * k, 32); o += 32; }
-        for (uint32_t k = 0; k < lgN; k++) { std::memcpy(&hpts[o], pLR + 64 * k + 32, 32); o += 32; }
-    }
+    R.r = rng.random_scalar();
+    R.yinv = R.y.invert();
+    return R1CSError::None;
+}
+// the compressed points of one replayed proof in the order of its MSM terms: A_I1, A_O1, S1, A_I2, A_O2, S2, V, T_1, T_3..T_6, L_k, R_k
+void verify_points(const VerifyReplay &R, const uint8_t *V, uint8_t *out) {
+    size_t o = 0;
+    for (int k = 0; k < 6; k++) { std::memcpy(out + o, R.pA[k], 32); o += 32; }
+    if (R.m) { std::memcpy(out + o, V, R.m * 32); o += R.m * 32; }
+    for (int k = 0; k < 5; k++) { std::memcpy(out + o, R.pT[k], 32); o += 32; }
+    for (uint32_t k = 0; k < R.lgN; k++) { std::memcpy(out + o, R.pLR + 64 * k, 32); o += 32; }
+    for (uint32_t k = 0; k < R.lgN; k++) { std::memcpy(out + o, R.pLR + 64 * k + 32, 32); o += 32; }
+}
+// the scalars of those points, then of B and B_blinding (npts + 2 of them); wV: the m weights of V, then w_c.  rho: the proof's weight in a batch (nullptr: none)
+void verify_small_scalars(const VerifyReplay &R, const scm *wV, const Scalar &delta, const Scalar *rho, std::vector<Scalar> &hs) {
+    const Scalar &x = R.x, &r = R.r, &u_ch = R.u_ch;
+    const Scalar wc = from_scm(wV[R.m]);
+    const Scalar xx = x * x, rxx = r * xx, xxx = x * xx;
+    hs.assign(R.npts() + 2, Scalar());
+    size_t o = 0;
+    hs[o++] = x; hs[o++] = xx; hs[o++] = xxx;
+    hs[o++] = u_ch * x; hs[o++] = u_ch * xx; hs[o++] = u_ch * xxx;
+    for (uint64_t j = 0; j < R.m; j++) hs[o++] = from_scm(wV[j]) * rxx;
+    hs[o++] = r * x; hs[o++] = rxx * x; hs[o++] = rxx * xx; hs[o++] = rxx * xxx; hs[o++] = rxx * xx * xx;
+    for (uint32_t k = 0; k < R.lgN; k++) hs[o++] = R.uk[k] * R.uk[k];
+    for (uint32_t k = 0; k < R.lgN; k++) hs[o++] = R.ukinv[k] * R.ukinv[k];
+    hs[o++] = R.w * (R.tx - R.ipa * R.ipb) + r * (xx * (wc + delta) - R.tx);      // B
+    hs[o++] = -R.eb - r * R.txb;                                                  // B_blinding
+    if (rho) for (Scalar &s : hs) s = s * *rho;
+}
+// y^-i (yinvpow), z^j, the flattened weights (w_c into wV[m]) and the s vector of one replayed proof, queued on the engine stream; all but y^-i in the
+// arena, read by k_verify_scalars(_acc) and nothing later.  ch: the proof's challenges on the device
+struct VerifyVecs { scm *wL, *wR, *wO, *wV, *svec; };
+VerifyVecs verify_prep(Engine::Impl &I, const DeviceCircuit *c, const VerifyReplay &R, const IpaChallenges *ch) {
+    const uint64_t n = c->n, m = c->m, q = c->q, N = R.N;
     I.red_partial.ensure((size_t)4096 * sizeof(scm)); I.red_out.ensure(16 * sizeof(scm));      // [0,1024): delta partials, [1024,1536): w_c partials
-    I.vfy_in.ensure((size_t)npts * 32); I.vfy_pts.ensure((size_t)npts * sizeof(ge_niels)); I.vfy_ok.ensure((size_t)npts * 4);
-    I.vfy_sc.ensure((size_t)(npts + 2) * sizeof(scm)); I.vfy_ch.ensure(sizeof(IpaChallenges));
-    HIPCHK(hipMemcpyAsync(I.vfy_in.p, hpts.data(), hpts.size(), hipMemcpyHostToDevice, st));
-    BPG_LAUNCH(I, k_decompress, dim3(cdiv(npts, 64)), dim3(64), I.vfy_in.as<uint8_t>(), I.vfy_pts.as<ge_niels>(), I.vfy_ok.as<uint32_t>(), npts);
     I.yinvpow.ensure(N * sizeof(scm));
     // powers of z, the flattened weights and the s vector are read by k_verify_scalars and earlier kernels only: in the arena, ahead of the one MSM
-    const size_t b_w = Impl::al256(c->ncols * sizeof(scm)), b_z = Impl::al256((q + 2) * sizeof(scm)), b_y = Impl::al256(N * sizeof(scm));
+    const size_t b_w = Engine::Impl::al256(c->ncols * sizeof(scm)), b_z = Engine::Impl::al256((q + 2) * sizeof(scm)), b_y = Engine::Impl::al256(N * sizeof(scm));
     I.arena.ensure(b_w + b_z + b_y);
     scm *const wAll_p = reinterpret_cast<scm *>(I.arena_at(0)), *const zpow_p = reinterpret_cast<scm *>(I.arena_at(b_w)), *const ypow_p = reinterpret_cast<scm *>(I.arena_at(b_w + b_z));
     {   // y^-i, z^j: one launch
@@ -2061,7 +2106,7 @@ R1CSError Engine::verify(DeviceCircuit *c, Transcript &T, const uint8_t *V, cons
             uint32_t lgT = ceil_log2(count); if (lgT > 16) lgT = 16;
             E.base[k] = to_scm(base); E.out[k] = out; E.count[k] = (uint32_t)count; E.lgT[k] = lgT; lgmax = std::max(lgmax, lgT); k++;
         };
-        add(yinv, I.yinvpow.as<scm>(), N); add(z, zpow_p, q + 1);
+        add(R.yinv, I.yinvpow.as<scm>(), N); add(R.z, zpow_p, q + 1);
         BPG_LAUNCH(I, k_exp_table, dim3(cdiv(1u << lgmax, 256), k), dim3(256), E);
     }
     if (c->ncols > 1)
@@ -2075,17 +2120,43 @@ R1CSError Engine::verify(DeviceCircuit *c, Transcript &T, const uint8_t *V, cons
                    I.red_partial.as<scm>() + 1024);
         BPG_LAUNCH(I, k_reduce_partials, dim3(1), dim3(256), I.red_partial.as<scm>() + 1024, cb, 1u, wV + m);
     }
+    BPG_LAUNCH(I, k_ipa_s, dim3(cdiv(N, 256)), dim3(256), ch, ypow_p, R.lgN, (uint32_t)N);
+    return VerifyVecs{wL, wR, wO, wV, ypow_p};
+}
+}  // namespace
+
+R1CSError Engine::verify(DeviceCircuit *c, Transcript &T, const uint8_t *V, const uint8_t *proof, size_t proof_len, const uint8_t seed[32], uint32_t flags) {
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    hipStream_t st = I.st;
+    I.shared_now = I.shared_variants();
+    VerifyReplay R;
+    const R1CSError e = verify_replay(c->n, c->m, gens_cap_, T, proof, proof_len, seed, flags, R);
+    if (e != R1CSError::None) return e;
+    const uint64_t n = c->n, m = c->m, N = R.N;
+    const uint32_t lgN = R.lgN;
+
+    // ---- device side
+    const uint32_t npts = R.npts();
+    std::vector<uint8_t> hpts((size_t)npts * 32);
+    verify_points(R, V, hpts.data());
+    I.red_partial.ensure((size_t)4096 * sizeof(scm)); I.red_out.ensure(16 * sizeof(scm));      // [0,1024): delta partials, [1024,1536): w_c partials
+    I.vfy_in.ensure((size_t)npts * 32); I.vfy_pts.ensure((size_t)npts * sizeof(ge_niels)); I.vfy_ok.ensure((size_t)npts * 4);
+    I.vfy_sc.ensure((size_t)(npts + 2) * sizeof(scm)); I.vfy_ch.ensure(sizeof(IpaChallenges));
+    HIPCHK(hipMemcpyAsync(I.vfy_in.p, hpts.data(), hpts.size(), hipMemcpyHostToDevice, st));
+    BPG_LAUNCH(I, k_decompress, dim3(cdiv(npts, 64)), dim3(64), I.vfy_in.as<uint8_t>(), I.vfy_pts.as<ge_niels>(), I.vfy_ok.as<uint32_t>(), npts);
     {
         I.h_small.ensure(1 << 16);
         IpaChallenges *hc = reinterpret_cast<IpaChallenges *>(I.h_small.as<uint8_t>() + 8192);
-        for (uint32_t k = 0; k < lgN; k++) { hc->u[k] = to_scm(uk[k]); hc->uinv[k] = to_scm(ukinv[k]); }
+        for (uint32_t k = 0; k < lgN; k++) { hc->u[k] = to_scm(R.uk[k]); hc->uinv[k] = to_scm(R.ukinv[k]); }
         HIPCHK(hipMemcpyAsync(I.vfy_ch.p, hc, sizeof(IpaChallenges), hipMemcpyHostToDevice, st));
     }
+    const VerifyVecs W = verify_prep(I, c, R, I.vfy_ch.as<IpaChallenges>());
+    scm *const wV = W.wV;
     I.lv.ensure(N * sizeof(scm)); I.rv.ensure(N * sizeof(scm));
-    scm *svec = ypow_p, *gsc = I.lv.as<scm>(), *hsc = I.rv.as<scm>();
-    BPG_LAUNCH(I, k_ipa_s, dim3(cdiv(N, 256)), dim3(256), I.vfy_ch.as<IpaChallenges>(), svec, lgN, (uint32_t)N);
+    scm *gsc = I.lv.as<scm>(), *hsc = I.rv.as<scm>();
     const uint32_t blocks = std::min<uint32_t>(cdiv(N, 256), 1024);
-    BPG_LAUNCH(I, k_verify_scalars, dim3(blocks), dim3(256), wL, wR, wO, I.yinvpow.as<scm>(), svec, to_scm(x), to_scm(ipa), to_scm(ipb), to_scm(u_ch),
+    BPG_LAUNCH(I, k_verify_scalars, dim3(blocks), dim3(256), W.wL, W.wR, W.wO, I.yinvpow.as<scm>(), W.svec, to_scm(R.x), to_scm(R.ipa), to_scm(R.ipb), to_scm(R.u_ch),
                gsc, hsc, I.red_partial.as<scm>(), (uint32_t)n, (uint32_t)N);
     BPG_LAUNCH(I, k_reduce_partials, dim3(1), dim3(256), I.red_partial.as<scm>(), blocks, 1u, I.red_out.as<scm>());
     HIPCHK(hipGetLastError());
@@ -2095,20 +2166,10 @@ R1CSError Engine::verify(DeviceCircuit *c, Transcript &T, const uint8_t *V, cons
     HIPCHK(hipMemcpyAsync(h_ok.data(), I.vfy_ok.p, npts * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     for (uint32_t k = 0; k < npts; k++) if (!h_ok[k]) return R1CSError::VerificationError;      // optional_multiscalar_mul: a point failed to decompress
-    const Scalar delta = from_scm(h_delta), wc = from_scm(h_wV[m]);
-    const Scalar xx = x * x, rxx = r * xx, xxx = x * xx;
+    std::vector<Scalar> hsv;
+    verify_small_scalars(R, h_wV.data(), from_scm(h_delta), nullptr, hsv);
     std::vector<scm> hs(npts + 2);
-    {
-        size_t o = 0;
-        hs[o++] = to_scm(x); hs[o++] = to_scm(xx); hs[o++] = to_scm(xxx);
-        hs[o++] = to_scm(u_ch * x); hs[o++] = to_scm(u_ch * xx); hs[o++] = to_scm(u_ch * xxx);
-        for (uint64_t j = 0; j < m; j++) hs[o++] = to_scm(from_scm(h_wV[j]) * rxx);
-        hs[o++] = to_scm(r * x); hs[o++] = to_scm(rxx * x); hs[o++] = to_scm(rxx * xx); hs[o++] = to_scm(rxx * xxx); hs[o++] = to_scm(rxx * xx * xx);
-        for (uint32_t k = 0; k < lgN; k++) hs[o++] = to_scm(uk[k] * uk[k]);
-        for (uint32_t k = 0; k < lgN; k++) hs[o++] = to_scm(ukinv[k] * ukinv[k]);
-        hs[o++] = to_scm(w * (tx - ipa * ipb) + r * (xx * (wc + delta) - tx));      // B
-        hs[o++] = to_scm(-eb - r * txb);                                              // B_blinding
-    }
+    for (size_t k = 0; k < hs.size(); k++) hs[k] = to_scm(hsv[k]);
     HIPCHK(hipMemcpyAsync(I.vfy_sc.p, hs.data(), hs.size() * sizeof(scm), hipMemcpyHostToDevice, st));
     Impl::MsmTicket tk;
     {
@@ -2122,7 +2183,152 @@ R1CSError Engine::verify(DeviceCircuit *c, Transcript &T, const uint8_t *V, cons
     HIPCHK(hipStreamSynchronize(st));
     uint8_t out[32];
     h51::pt_compress(out, I.msm_points(tk)[0]);
-    return is_ident(out) ? R1CSError::None : R1CSError::VerificationError;
+    return std::memcmp(out, kIdentity, 32) == 0 ? R1CSError::None : R1CSError::VerificationError;
+}
+
+// ------------------------------------------------------------------------------------------------ batch verification
+// K proofs, each equation weighted by a random rho_k, summed into ONE multiscalar multiplication of 2 N_max + sum_k (npts_k) + 2 terms: the G / H scalars
+// of all proofs go into two accumulators of N_max (k_verify_scalars_acc), every proof's own points keep their terms.  The sum is the identity for
+// valid proofs; for an invalid one it is not, except with probability ~1/l over rho.  Host synchronisations on the accept path:
+// one after the decompression, one before the small terms, one after the MSM - plus one per FLAT item, whose circuit is uploaded, used and freed.
+void Engine::verify_batch(size_t count, const VerifyItem *items, const uint8_t batch_seed[32], R1CSError *status_out) {
+    if (!count) return;
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    hipStream_t st = I.st;
+    I.shared_now = I.shared_variants();
+    // ---- host phase: format checks and Fiat-Shamir replay of every item (the states before, for the item-by-item pass of a rejected batch)
+    std::vector<VerifyReplay> R(count);
+    std::vector<std::array<uint8_t, 203>> before(count);
+    std::vector<uint8_t> live(count, 0);
+    for (size_t k = 0; k < count; k++) {
+        const VerifyItem &it = items[k];
+        const uint64_t n = it.dc ? it.dc->n : it.flat->n, m = it.dc ? it.dc->m : it.flat->m;
+        it.T->export_state(before[k].data());
+        status_out[k] = verify_replay(n, m, gens_cap_, *it.T, it.proof, it.proof_len, it.seed, it.flags, R[k]);
+        live[k] = status_out[k] == R1CSError::None;
+    }
+    // ---- the weights: a transcript of the whole batch (every proof and its replayed transcript), keyed with the caller's fresh randomness
+    std::vector<Scalar> rho(count);
+    {
+        static const char label[] = "bpg-verify-batch-v1";
+        Transcript B(reinterpret_cast<const uint8_t *>(label), sizeof label - 1);
+        B.append_u64("count", count);
+        for (size_t k = 0; k < count; k++) {
+            uint8_t s[203]; items[k].T->export_state(s);
+            B.append_message("proof", items[k].proof, items[k].proof_len);
+            B.append_message("state", s, 203);
+        }
+        TranscriptRng rng = B.build_rng({}, batch_seed);
+        for (size_t k = 0; k < count; k++) rho[k] = rng.random_scalar();
+    }
+    // ---- every live item's points in one decompression
+    std::vector<uint32_t> pt_off(count + 1, 0);
+    for (size_t k = 0; k < count; k++) pt_off[k + 1] = pt_off[k] + (live[k] ? R[k].npts() : 0);
+    const uint32_t npts = pt_off[count];
+    if (!npts) return;
+    {
+        std::vector<uint8_t> hpts((size_t)npts * 32);
+        std::vector<IpaChallenges> hch(count);
+        std::memset(hch.data(), 0, count * sizeof(IpaChallenges));
+        for (size_t k = 0; k < count; k++) {
+            if (!live[k]) continue;
+            verify_points(R[k], items[k].V, &hpts[(size_t)pt_off[k] * 32]);
+            for (uint32_t j = 0; j < R[k].lgN; j++) { hch[k].u[j] = to_scm(R[k].uk[j]); hch[k].uinv[j] = to_scm(R[k].ukinv[j]); }
+        }
+        I.vfy_in.ensure((size_t)npts * 32); I.vfy_pts.ensure((size_t)npts * sizeof(ge_niels)); I.vfy_ok.ensure((size_t)npts * 4);
+        I.vfy_ch.ensure(count * sizeof(IpaChallenges));
+        I.h2d(I.vfy_in.p, hpts.data(), hpts.size());
+        I.h2d(I.vfy_ch.p, hch.data(), count * sizeof(IpaChallenges));
+        BPG_LAUNCH(I, k_decompress, dim3(cdiv(npts, 64)), dim3(64), I.vfy_in.as<uint8_t>(), I.vfy_pts.as<ge_niels>(), I.vfy_ok.as<uint32_t>(), npts);
+        HIPCHK(hipGetLastError());
+        std::vector<uint32_t> h_ok(npts);
+        HIPCHK(hipMemcpyAsync(h_ok.data(), I.vfy_ok.p, (size_t)npts * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (size_t k = 0; k < count; k++) {
+            if (!live[k]) continue;
+            for (uint32_t j = pt_off[k]; j < pt_off[k + 1]; j++)
+                if (!h_ok[j]) { status_out[k] = R1CSError::VerificationError; live[k] = 0; break; }     // optional_multiscalar_mul: a point failed to decompress
+        }
+    }
+    // ---- device phase: per item the weighted G / H scalars into the accumulators, its w_V, w_c and delta into its slot [w_V.. | w_c | delta]
+    uint64_t Nmax = 0; size_t nsmall = 0;
+    std::vector<size_t> slot(count, 0);
+    size_t b_arena = 0;
+    for (size_t k = 0; k < count; k++) {
+        if (!live[k]) continue;
+        Nmax = std::max<uint64_t>(Nmax, R[k].N); slot[k] = nsmall; nsmall += R[k].m + 2;
+        const uint64_t ncols = 3 * R[k].n + R[k].m + 1, q = items[k].dc ? items[k].dc->q : items[k].flat->q;
+        b_arena = std::max(b_arena, Impl::al256(ncols * sizeof(scm)) + Impl::al256((q + 2) * sizeof(scm)) + Impl::al256(R[k].N * sizeof(scm)));
+    }
+    if (!Nmax) return;
+    I.lv.ensure(Nmax * sizeof(scm)); I.rv.ensure(Nmax * sizeof(scm)); I.yinvpow.ensure(Nmax * sizeof(scm)); I.arena.ensure(b_arena);
+    I.vfy_small.ensure(nsmall * sizeof(scm));
+    HIPCHK(hipMemsetAsync(I.lv.p, 0, Nmax * sizeof(scm), st));
+    HIPCHK(hipMemsetAsync(I.rv.p, 0, Nmax * sizeof(scm), st));
+    for (size_t k = 0; k < count; k++) {
+        if (!live[k]) continue;
+        DeviceCircuit *c = items[k].dc;
+        const bool own = c == nullptr;
+        if (own) c = upload(*items[k].flat);                    // (synchronises the stream itself)
+        try {
+            const VerifyReplay &Rk = R[k];
+            const VerifyVecs W = verify_prep(I, c, Rk, I.vfy_ch.as<IpaChallenges>() + k);
+            const uint32_t blocks = std::min<uint32_t>(cdiv(Rk.N, 256), 1024);
+            BPG_LAUNCH(I, k_verify_scalars_acc, dim3(blocks), dim3(256), W.wL, W.wR, W.wO, I.yinvpow.as<scm>(), W.svec, to_scm(Rk.x), to_scm(Rk.ipa), to_scm(Rk.ipb),
+                       to_scm(Rk.u_ch), to_scm(rho[k]), I.lv.as<scm>(), I.rv.as<scm>(), I.red_partial.as<scm>(), (uint32_t)Rk.n, (uint32_t)Rk.N);
+            scm *sl = I.vfy_small.as<scm>() + slot[k];
+            BPG_LAUNCH(I, k_reduce_partials, dim3(1), dim3(256), I.red_partial.as<scm>(), blocks, 1u, sl + Rk.m + 1);
+            HIPCHK(hipMemcpyAsync(sl, W.wV, (Rk.m + 1) * sizeof(scm), hipMemcpyDeviceToDevice, st));
+            HIPCHK(hipGetLastError());
+            // a flat circuit is freed only once the kernels that read it have run: one synchronisation per flat item
+            if (own) { HIPCHK(hipStreamSynchronize(st)); free_circuit(c); }
+        } catch (...) { if (own) { (void)hipStreamSynchronize(st); free_circuit(c); } throw; }
+    }
+    // ---- small terms: every live item's point scalars times rho_k; the B, B_blinding scalars summed over the items
+    std::vector<scm> h_slots(nsmall);
+    HIPCHK(hipMemcpyAsync(h_slots.data(), I.vfy_small.p, nsmall * sizeof(scm), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::vector<scm> hs(npts + 2);
+    std::memset(hs.data(), 0, hs.size() * sizeof(scm));                // points of items that left at the decompression: scalar 0, no bucket entries
+    Scalar sB, sBb;
+    std::vector<Scalar> hsv;
+    for (size_t k = 0; k < count; k++) {
+        if (!live[k]) continue;
+        const scm *sl = &h_slots[slot[k]];
+        verify_small_scalars(R[k], sl, from_scm(sl[R[k].m + 1]), &rho[k], hsv);
+        const uint32_t np = R[k].npts();
+        for (uint32_t j = 0; j < np; j++) hs[pt_off[k] + j] = to_scm(hsv[j]);
+        sB = sB + hsv[np]; sBb = sBb + hsv[np + 1];
+    }
+    hs[npts] = to_scm(sB); hs[npts + 1] = to_scm(sBb);
+    I.vfy_sc.ensure((size_t)(npts + 2) * sizeof(scm));
+    I.h2d(I.vfy_sc.p, hs.data(), hs.size() * sizeof(scm));
+    // ---- one MSM for the whole batch
+    Impl::MsmTicket tk;
+    {
+        MsmSegs S = seg_new();
+        seg_push(S, I.lv.as<scm>(), I.gens.as<ge_niels>(), (uint32_t)Nmax, 0);
+        seg_push(S, I.rv.as<scm>(), I.gens.as<ge_niels>() + gens_cap_, (uint32_t)Nmax, 0);
+        seg_push(S, I.vfy_sc.as<scm>(), I.vfy_pts.as<ge_niels>(), npts, 0);
+        seg_push(S, I.vfy_sc.as<scm>() + npts, I.bases.as<ge_niels>(), 2, 0);
+        tk = I.msm(S, 1);
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    uint8_t out[32];
+    h51::pt_compress(out, I.msm_points(tk)[0]);
+    if (std::memcmp(out, kIdentity, 32) == 0) return;                  // every live item is accepted
+    // ---- a rejected batch: each live item alone, from its state before, for its exact status (costs only when the batch holds a bad proof)
+    for (size_t k = 0; k < count; k++) {
+        if (!live[k]) continue;
+        const VerifyItem &it = items[k];
+        *it.T = Transcript::from_state(before[k].data());
+        DeviceCircuit *c = it.dc;
+        const bool own = c == nullptr;
+        if (own) c = upload(*it.flat);
+        try { status_out[k] = verify(c, *it.T, it.V, it.proof, it.proof_len, it.seed, it.flags); } catch (...) { if (own) free_circuit(c); throw; }
+        if (own) free_circuit(c);
+    }
 }
 
 }  // namespace bpg

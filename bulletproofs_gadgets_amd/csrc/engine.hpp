@@ -94,6 +94,18 @@ public:
     // Verifier::verify on a resident (assignment-free) circuit. transcript: state after Verifier::new + every "V" append.
     R1CSError verify(DeviceCircuit *c, Transcript &transcript, const uint8_t *V, const uint8_t *proof, size_t proof_len,
                      const uint8_t seed[32], uint32_t flags);
+    // One proof of a batch (include/bpg.h bpg_r1cs_verify_batch): a resident circuit (dc) or a verifier-side instance (flat) that is uploaded,
+    // used and freed inside the call; T is updated in place exactly as verify() updates it.
+    struct VerifyItem {
+        DeviceCircuit *dc = nullptr; const FlatView *flat = nullptr;
+        Transcript *T = nullptr; const uint8_t *V = nullptr; const uint8_t *proof = nullptr; size_t proof_len = 0;
+        const uint8_t *seed = nullptr; uint32_t flags = 0;
+    };
+    // Every proof's verification equation weighted by a random rho_k, all of them in ONE multiscalar multiplication; status_out[k] is what verify()
+    // returns for item k alone (a rejected batch is re-verified item by item).
+    void verify_batch(size_t count, const VerifyItem *items, const uint8_t batch_seed[32], R1CSError *status_out);
+    // the host-side checks upload() makes on an instance (CSR shape, index ranges, sizes): std::invalid_argument, no device work
+    static void check_instance(const FlatView &c);
     void synchronize();
     // HIP-event profile on the engine's own stream: mode 0 off, 1 = dominant kernel (k_fold_points) only, 2 = all kernels
     void profile_set(int mode);

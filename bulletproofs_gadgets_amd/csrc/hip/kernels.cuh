@@ -16,6 +16,7 @@
 //                                       shapes those two do not take (first groups, outputs that do not fill whole blocks); below: k_tt_bases,
 //                                       k_tt_multiples, k_tt_factors, then k_tt_advance, k_tt_round, k_tt_finish per round
 //   f1  Verifier::verify                k_decompress, k_flatten_const, k_ipa_s, k_verify_scalars + one MSM
+//       batch verification              the same per proof with k_verify_scalars_acc (weighted g_i, h_i added into two shared accumulators) + one MSM per batch
 // The kernels live in k_points.cuh, k_scalars.cuh, k_ipa.cuh, k_verify.cuh and k_msm.cuh, included at the end of this file in that order.
 // Data layout in HBM: scalars = 8 x u32 Montgomery form, 32 B each, AoS (lane i <-> element i: 2 x 16 B coalesced
 // loads); generator tables = affine Niels (y+x, y-x, 2dxy), 96 B per point, G at [0,N) and H at [N,2N); window tables =

@@ -80,7 +80,7 @@ typedef struct {
 /* ABI version of this header.  Rules: structs the CALLER allocates either carry a struct_size (bpg_config: fields are only ever added at the end and
  * read when struct_size covers them) or are frozen (bpg_timings, bpg_r1cs_instance, bpg_batch_item, bpg_term, bpg_lc); a field never changes type or
  * meaning; BPG_ABI_VERSION grows with every addition.  A host checks bpg_abi_version() >= the BPG_ABI_VERSION it was compiled against. */
-#define BPG_ABI_VERSION 6u
+#define BPG_ABI_VERSION 7u
 uint32_t bpg_abi_version(void);
 const char *bpg_strerror(bpg_status s);
 const char *bpg_last_error(void);                                /* message of the calling thread's last failure */
@@ -147,6 +147,30 @@ bpg_status bpg_r1cs_verify(bpg_ctx *ctx, const bpg_r1cs_instance *inst, uint8_t 
  * keeps the constraint matrix in HBM. */
 bpg_status bpg_r1cs_verify_resident(bpg_ctx *ctx, bpg_circuit *circuit, uint8_t transcript_state[BPG_TRANSCRIPT_STATE_BYTES],
                                     uint64_t m, const uint8_t *V, const uint8_t *proof, uint64_t proof_len, const uint8_t seed[32], uint32_t flags);
+
+/* Batch verification: many proofs in ONE multiscalar multiplication.  Each item is the argument list of bpg_r1cs_verify (inst) or of
+ * bpg_r1cs_verify_resident (circuit, uploaded on this ctx): exactly one of the two is non-NULL.  Items may differ in circuit, n, m and flags.
+ * Every item's verification equation is multiplied by an independent random weight rho_k and all of them are summed into one MSM of about
+ * 2 N_max + sum_k (npts_k + 2) terms; the batch is accepted iff that sum is the identity.  If it is not, every item is verified alone.
+ *   status_out[i] = exactly what bpg_r1cs_verify / bpg_r1cs_verify_resident returns for item i with the same seed (BPG_OK, BPG_ERR_VERIFICATION,
+ *                   BPG_ERR_FORMAT or BPG_ERR_INVALID_GENERATORS_LENGTH); transcript_state is left as that call leaves it.
+ *   return value  = BPG_OK when every item is accepted, else the status of the first failing item (as bpg_pool_prove).
+ * Every argument is checked before any device work: a NULL ctx, NULL items / status_out / batch_seed with count > 0, an item with both or neither of
+ * inst / circuit, an m that does not match the item's instance or circuit, or a malformed instance refuse the whole call with BPG_ERR_INVALID_ARGUMENT
+ * (no launch, no transcript state touched).  count == 0 returns BPG_OK.
+ * The weights rho_k come from a Merlin transcript "bpg-verify-batch-v1" over count, every proof and its replayed transcript state, finalised
+ * with batch_seed.  batch_seed MUST be fresh randomness in production, just as each item's seed: a prover who can predict the weights can make
+ * two invalid proofs whose errors cancel.  Flat items are uploaded, used and freed one at a time (peak HBM: one flat circuit + 2 N_max scalars). */
+typedef struct {
+    const bpg_r1cs_instance *inst;   /* verifier-side instance ... */
+    bpg_circuit *circuit;            /* ... or a circuit uploaded on this ctx: exactly one of the two is non-NULL */
+    uint8_t *transcript_state;       /* 203 B, state after Verifier::new + every "V" append; updated in place as bpg_r1cs_verify does */
+    uint64_t m; const uint8_t *V;    /* the m commitments */
+    const uint8_t *proof; uint64_t proof_len;
+    const uint8_t *seed;             /* 32 B: this item's verifier thread_rng draw, as in bpg_r1cs_verify */
+    uint32_t flags;                  /* dialect flags of this item (BPG_FLAG_COMPACT_1PHASE / BPG_FLAG_NO_1PHASE_DOMSEP) */
+} bpg_verify_item;
+bpg_status bpg_r1cs_verify_batch(bpg_ctx *ctx, uint64_t count, const bpg_verify_item *items, const uint8_t batch_seed[32], bpg_status *status_out);
 
 /* A batch of INDEPENDENT proofs on one GPU.  One proof keeps the device busy for ~45 ms of 340 (the rest is the host's serial Merlin
  * TranscriptRng chain, upstream-exact), so a pool of `workers` engine contexts + host threads proves items concurrently: the chain of
