@@ -489,6 +489,42 @@ class _BatchItem(C.Structure):
                 ("rng_seed", C.c_char_p), ("flags", C.c_uint32), ("proof_out", C.c_void_p), ("proof_len", C.POINTER(C.c_uint64))]
 
 
+def _batch_items(items):
+    """bpg_batch_item array of [(FlatInstance, transcript_state, v_blinding, rng_seed, flags)] and the buffers it points into:
+    (instance, transcript state, proof buffer, proof length, v_blinding, seed) per item"""
+    n = len(items)
+    arr = (_BatchItem * max(n, 1))()
+    keep = []
+    for k, (inst, state, vb, seed, flags) in enumerate(items):
+        cs = inst.cstruct()
+        ts = _buf(203); ts.raw = bytes(state)
+        cap = lib().bpg_proof_size(inst.n, flags)
+        out = _buf(cap); ln = C.c_uint64(cap)
+        keep.append((cs, ts, out, ln, vb, seed))
+        arr[k].inst = C.pointer(cs); arr[k].transcript_state = C.cast(ts, C.c_void_p); arr[k].m = inst.m
+        arr[k].v_blinding = vb; arr[k].rng_seed = seed; arr[k].flags = flags
+        arr[k].proof_out = C.cast(out, C.c_void_p); arr[k].proof_len = C.pointer(ln)
+    return arr, keep
+
+
+def _context_prove_batch(self, items, return_status=False):
+    """bpg_r1cs_prove_batch: items = [(FlatInstance, transcript_state, v_blinding, rng_seed, flags)] (as ProverPool.prove_batch) ->
+    [(proof, transcript state after)], each exactly what prove_flat gives for that item alone; small circuits (N <= 2^14) share every launch.
+    Raises BpgError on the first failing item; return_status=True returns (results, statuses) instead, with (None, state as given) for a failed item."""
+    arr, keep = _batch_items(items)
+    n = len(items)
+    status = (C.c_int32 * max(n, 1))()
+    rc = lib().bpg_r1cs_prove_batch(self._h, C.c_uint64(n), arr, status)
+    if not return_status:
+        _chk(rc)
+    st = [status[k] for k in range(n)]
+    res = [(k[2].raw[:k[3].value] if s == 0 else None, k[1].raw[:203]) for k, s in zip(keep, st)]
+    return (res, st) if return_status else res
+
+
+Context.prove_batch = _context_prove_batch
+
+
 class ProverPool:
     """bpg_pool_*: `workers` engine contexts + host threads on one GPU that prove a batch of independent instances concurrently (the
     serial TranscriptRng chain of one proof overlaps the kernels of the others). Same bytes as proving the items one by one."""
@@ -501,20 +537,9 @@ class ProverPool:
 
     def prove_batch(self, items):
         """items: [(FlatInstance, transcript_state, v_blinding, rng_seed, flags)] -> [(proof bytes, transcript state after)]"""
-        n = len(items)
-        arr = (_BatchItem * max(n, 1))()
-        keep = []
-        for k, (inst, state, vb, seed, flags) in enumerate(items):
-            cs = inst.cstruct()
-            ts = _buf(203); ts.raw = bytes(state)
-            cap = lib().bpg_proof_size(inst.n, flags)
-            out = _buf(cap); ln = C.c_uint64(cap)
-            keep.append((cs, ts, out, ln, vb, seed))
-            arr[k].inst = C.pointer(cs); arr[k].transcript_state = C.cast(ts, C.c_void_p); arr[k].m = inst.m
-            arr[k].v_blinding = vb; arr[k].rng_seed = seed; arr[k].flags = flags
-            arr[k].proof_out = C.cast(out, C.c_void_p); arr[k].proof_len = C.pointer(ln)
-        status = (C.c_int32 * max(n, 1))()
-        _chk(lib().bpg_pool_prove(self._h, C.c_uint64(n), arr, status))
+        arr, keep = _batch_items(items)
+        status = (C.c_int32 * max(len(items), 1))()
+        _chk(lib().bpg_pool_prove(self._h, C.c_uint64(len(items)), arr, status))
         return [(k[2].raw[:k[3].value], k[1].raw[:203]) for k in keep]
 
     def close(self):

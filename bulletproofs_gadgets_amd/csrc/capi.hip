@@ -287,6 +287,62 @@ bpg_status bpg_r1cs_prove(bpg_ctx *ctx, const bpg_r1cs_instance *inst, uint8_t t
     return s;
 }
 
+bpg_status bpg_r1cs_prove_batch(bpg_ctx *ctx, uint64_t count, const bpg_batch_item *items, bpg_status *status_out) {
+    if (!ctx || (count && (!items || !status_out))) { g_last_error = "null or invalid argument: ctx, items and status_out"; return BPG_ERR_INVALID_ARGUMENT; }
+    if (!count) { g_last_error.clear(); return BPG_OK; }
+    std::vector<bpg_status> st(count, BPG_OK);
+    std::vector<std::string> msg(count);
+    std::vector<FlatView> views(count);
+    std::vector<Transcript> T(count);
+    std::vector<std::vector<Scalar>> vb(count);
+    std::vector<Engine::ProveItem> lock;
+    std::vector<uint64_t> lock_at, single_at;
+    for (uint64_t k = 0; k < count; k++) {
+        const bpg_batch_item &it = items[k];
+        // the checks of bpg_r1cs_prove (upload, then bpg_r1cs_prove_resident), in its order: an item fails alone, with that call's status
+        st[k] = guard([&] {
+            const FlatView f = as_view(it.inst, true);
+            Engine::check_instance(f);
+            REQUIRE(it.transcript_state && it.rng_seed && it.proof_out && it.proof_len && (it.m == 0 || it.v_blinding));
+            if (it.m != f.m) throw std::invalid_argument("prove: m does not match the uploaded circuit");
+            if (*it.proof_len < bpg_proof_size(f.n, it.flags)) throw std::invalid_argument("prove: proof buffer too small");
+            uint64_t N = 1; while (N < f.n) N <<= 1;
+            if (ctx->engine->gens_capacity() < N) throw R1CSException(R1CSError::InvalidGeneratorsLength, "generator capacity below padded circuit size (call bpg_gens_ensure)");
+            views[k] = f;
+        });
+        if (st[k] != BPG_OK) { msg[k] = g_last_error; continue; }
+        if (!ctx->engine->lockstep_eligible(views[k].n, it.flags)) { single_at.push_back(k); continue; }
+        T[k] = Transcript::from_state(it.transcript_state);
+        vb[k].resize(it.m);
+        for (uint64_t i = 0; i < it.m; i++) vb[k][i] = Scalar::from_bytes_mod_order(it.v_blinding + 32 * i);
+        Engine::ProveItem p; p.flat = &views[k]; p.T = &T[k]; p.vb = &vb[k]; p.seed = it.rng_seed; p.flags = it.flags;
+        lock.push_back(std::move(p)); lock_at.push_back(k);
+    }
+    if (!lock.empty()) {
+        const bpg_status s = guard([&] { ctx->engine->prove_batch(lock.size(), lock.data()); });
+        const std::string why = g_last_error;
+        for (size_t j = 0; j < lock.size(); j++) {
+            const uint64_t k = lock_at[j];
+            st[k] = s;
+            if (s != BPG_OK) { msg[k] = why; continue; }
+            std::memcpy(items[k].proof_out, lock[j].proof.data(), lock[j].proof.size()); *items[k].proof_len = lock[j].proof.size();
+            T[k].export_state(items[k].transcript_state);
+        }
+    }
+    for (uint64_t k : single_at) {      // larger circuits and expanded blinding: the single path, same bytes
+        const bpg_batch_item &it = items[k];
+        st[k] = bpg_r1cs_prove(ctx, it.inst, it.transcript_state, it.m, it.v_blinding, it.rng_seed, it.flags, it.proof_out, it.proof_len);
+        if (st[k] != BPG_OK) msg[k] = g_last_error;
+    }
+    bpg_status first = BPG_OK;
+    g_last_error.clear();
+    for (uint64_t k = 0; k < count; k++) {
+        status_out[k] = st[k];
+        if (first == BPG_OK && st[k] != BPG_OK) { first = st[k]; g_last_error = "item " + std::to_string(k) + ": " + msg[k]; }
+    }
+    return first;
+}
+
 bpg_status bpg_r1cs_verify(bpg_ctx *ctx, const bpg_r1cs_instance *inst, uint8_t ts[BPG_TRANSCRIPT_STATE_BYTES], uint64_t m, const uint8_t *V,
                            const uint8_t *proof, uint64_t proof_len, const uint8_t seed[32], uint32_t flags) {
     return guard([&] {

@@ -13,6 +13,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -210,7 +211,9 @@ struct DeviceCircuit {
     X(k_sc_from_wide) X(k_blind_poison) X(k_exp_table) X(k_reduce_partials) X(k_flatten) X(k_flatten_const) X(k_poly_t) X(k_poly_eval) X(k_ipa_prep) \
     X(k_ipa_fold_scalars) X(k_fold_points) X(k_fold_points_reg) X(k_fold_points_split) X(k_fold_points_wnaf) X(k_fold_points_quad) X(k_fold_points_quadw) X(k_fold_points_regw) X(k_odd_start) X(k_odd_start_ext) X(k_dbl_times) X(k_odd_step) X(k_msm_digits) X(k_msm_scatter1) X(k_msm_sort2) X(k_scan_blocksums) \
     X(k_scan_apply) X(k_bucket_chunks) X(k_bucket_combine) X(k_bucket_combine_heavy) X(k_bucket_reduce) X(k_window_sums) X(k_window_sums_quad) X(k_decompress) X(k_ipa_s) X(k_verify_scalars) X(k_verify_scalars_acc) X(k_bench_fe_mul) \
-    X(k_tt_bases) X(k_tt_multiples) X(k_tt_bases8) X(k_tt_multiples8) X(k_tt_round8) X(k_tt_factors) X(k_tt_advance) X(k_tt_round) X(k_tt_finish) X(k_blind_expand) X(k_tt_commit3) X(k_tt_commit3_finish) X(k_csc_count) X(k_csc_fill) X(k_csc_colptr) X(k_merge_insert) X(k_merge_plan) X(k_merge_groups) X(k_merge_members) X(k_merge_sum)
+    X(k_tt_bases) X(k_tt_multiples) X(k_tt_bases8) X(k_tt_multiples8) X(k_tt_round8) X(k_tt_factors) X(k_tt_advance) X(k_tt_round) X(k_tt_finish) X(k_blind_expand) X(k_tt_commit3) X(k_tt_commit3_finish) X(k_csc_count) X(k_csc_fill) X(k_csc_colptr) X(k_merge_insert) X(k_merge_plan) X(k_merge_groups) X(k_merge_members) X(k_merge_sum) \
+    X(k_bt_commit3) X(k_bt_commit3_finish) X(k_bt_compress) X(k_bt_exp) X(k_bt_poly_t) X(k_bt_poly_eval) X(k_bt_factors) X(k_bt_advance) X(k_bt_round) \
+    X(k_bt_finish) X(k_bt_fold_scalars)
 enum KernelId {
 #define X(n) KID_##n,
     BPG_KERNELS(X)
@@ -308,10 +311,10 @@ struct Engine::Impl {
     void tt_build(const ge_niels *G, const ge_niels *H, const ge_niels *B, uint32_t M0, bool original) {
         const uint32_t npts = 2 * M0 + 1;
         if (original && tt_orig_M0 == M0 && tt_orig_gens == gens.p) { tt_table_p = tt_table.as<ge_pniels>(); return; }
-        tt_orig_M0 = 0;
         const size_t bb = al256((size_t)npts * TT_WINDOWS * sizeof(ge_ext)), tb = (size_t)npts * TT_WINDOWS * TT_MULTS * sizeof(ge_pniels);
         ge_ext *basesp;
         if (original) {     // tables of the ORIGINAL generators outlive the proof (and serve A_I, A_O, S of the next one): buffers of their own
+            tt_orig_M0 = 0;                             // (tables of folded generators live in the arena and leave these alone)
             tt_bases.ensure(bb); tt_table.ensure(tb);
             basesp = tt_bases.as<ge_ext>(); tt_table_p = tt_table.as<ge_pniels>();
         } else {            // tables of FOLDED generators live for the tail of one proof: in the arena, where the MSM workspace of the rounds before was
@@ -441,6 +444,8 @@ struct Engine::Impl {
     uint32_t tt_lg = 12;            // freeze the FOLDED generators once a round is down to 2^tt_lg per side: their window tables are built per proof (BPG_TT_LG; 0 = never)
     uint32_t tt_orig_lg = 14;       // a circuit of N <= 2^tt_orig_lg freezes the ORIGINAL generators at round 0: those tables are built once and also serve A_I, A_O, S
                                     // (BPG_TT_ORIG_LG; BPG_TT_LG sets both).  Measured at 2^20 (profiles/r03_tail_start.txt): 12 beats 14 alone and in flight
+    uint32_t batch_wave_mb = 512;   // lockstep batches (prove_batch): device state of one wave at most this many MB (BPG_BATCH_WAVE_MB; 0 = one proof per wave)
+    DevBuf bt_dev; PinBuf bt_pin;   // prove_batch: the wave's device buffers and its pinned upload / read-back area
     PinBuf h_raw, h_small;
     // Speculative blinding streams (Engine::blinding_begin): the leading draws of Prover::prove's TranscriptRng, produced on the context's
     // chain worker (ONE host thread, FIFO) before the circuit is known - or, for a sequence of proofs, while the previous proof's kernels run.
@@ -608,6 +613,7 @@ Engine::Engine(int device, const EngineConfig &cfg) : device_(device) {
     if (env_present("BPG_FOLD_WNAF")) { const long v = env_int_strict("BPG_FOLD_WNAF", 0, 8); if (v == 1 || v == 2) throw std::invalid_argument("BPG_FOLD_WNAF: 0 (register kernels) or 3..8"); K->fold_wnaf = (uint32_t)v; }
     if (env_present("BPG_TT_LG")) K->tt_lg = K->tt_orig_lg = (uint32_t)env_int_strict("BPG_TT_LG", 0, 20);
     env_set("BPG_TT_ORIG_LG", 0, 20, K->tt_orig_lg);
+    env_set("BPG_BATCH_WAVE_MB", 0, 1 << 20, K->batch_wave_mb);
     if (env_present("BPG_GENS_SHARE")) K->gens_share = env_int_strict("BPG_GENS_SHARE", 0, 1) != 0;
 
     int count = 0;
@@ -1994,6 +2000,357 @@ std::vector<uint8_t> Engine::prove(DeviceCircuit *c, Transcript &T, const std::v
     I.inner_product(T, proof, n, N, yinv, u_ch, w, Gtab, Htab, Bn, tm, t0);
     if (tm) { tm->ipa = tm->ipa_msm + tm->ipa_fold; tm->total += now_ms() - t_begin; }
     return proof;
+}
+
+// ------------------------------------------------------------------------------------------------ lockstep batch proving (include/bpg.h bpg_r1cs_prove_batch)
+// K proofs of circuits with N <= 2^tt_orig_lg run prove()'s table-driven path together: every device stage is one launch for all items of a wave
+// (hip/k_batch.cuh), and the Fiat-Shamir work of the items between two stages runs on a few host threads.  The draws and the transcript operations of
+// each item happen in exactly prove()'s order, and every point and scalar is computed by the same arithmetic, so each proof is byte-identical.
+namespace {
+// host threads of a batch: the cores this process may run on (its affinity mask: what bench.py's rank placement sets), capped by the cgroup CPU quota,
+// and never more than 16
+uint32_t batch_host_threads() {
+    cpu_set_t set; CPU_ZERO(&set);
+    long n = sched_getaffinity(0, sizeof set, &set) == 0 ? CPU_COUNT(&set) : 1;
+    if (FILE *f = std::fopen("/sys/fs/cgroup/cpu.max", "r")) {
+        char quota[32] = {0}; long period = 0;
+        if (std::fscanf(f, "%31s %ld", quota, &period) == 2 && std::strcmp(quota, "max") != 0 && period > 0) n = std::min(n, std::max(1L, (std::atol(quota) + period - 1) / period));
+        std::fclose(f);
+    }
+    return (uint32_t)std::max(1L, std::min(n, 16L));
+}
+// fn(lo, hi) over chunks of [0, count) on the caller and nthreads - 1 helpers that live for the whole call
+class StageThreads {
+public:
+    explicit StageThreads(uint32_t n) { for (uint32_t t = 1; t < n; t++) th_.emplace_back([this] { loop(); }); }
+    ~StageThreads() { { std::lock_guard<std::mutex> lk(mu_); quit_ = true; } cv_.notify_all(); for (std::thread &t : th_) t.join(); }
+    void run(size_t count, const std::function<void(size_t, size_t)> &fn) {
+        const size_t parts = std::min<size_t>(count, 4 * (th_.size() + 1));
+        if (parts <= 1 || th_.empty()) { if (count) fn(0, count); return; }
+        { std::lock_guard<std::mutex> lk(mu_); fn_ = &fn; count_ = count; parts_ = parts; next_.store(0); busy_.store((int)th_.size()); gen_++; }
+        cv_.notify_all();
+        work();
+        while (busy_.load(std::memory_order_acquire) != 0) std::this_thread::yield();
+        fn_ = nullptr;
+        if (err_) { std::exception_ptr e = err_; err_ = nullptr; std::rethrow_exception(e); }
+    }
+private:
+    void work() {
+        try {
+            for (size_t p; (p = next_.fetch_add(1)) < parts_;) (*fn_)(count_ * p / parts_, count_ * (p + 1) / parts_);
+        } catch (...) { std::lock_guard<std::mutex> lk(err_mu_); if (!err_) err_ = std::current_exception(); next_.store(parts_); }
+    }
+    void loop() {
+        uint64_t seen = 0;
+        for (;;) {
+            { std::unique_lock<std::mutex> lk(mu_); cv_.wait(lk, [&] { return quit_ || gen_ != seen; }); if (quit_) return; seen = gen_; }
+            work();
+            busy_.fetch_sub(1, std::memory_order_release);
+        }
+    }
+    std::vector<std::thread> th_;
+    std::mutex mu_, err_mu_; std::condition_variable cv_;
+    bool quit_ = false; uint64_t gen_ = 0;
+    const std::function<void(size_t, size_t)> *fn_ = nullptr;
+    size_t count_ = 0, parts_ = 0;
+    std::atomic<size_t> next_{0}; std::atomic<int> busy_{0};
+    std::exception_ptr err_;
+};
+// x[i] -> x[i]^-1 for i in [lo, hi) with one inversion (Montgomery's trick); a zero stays zero, as Scalar::invert leaves it
+void batch_invert(Scalar *x, Scalar *out, size_t lo, size_t hi) {
+    std::vector<Scalar> pre(hi - lo);
+    Scalar acc = Scalar::one();
+    for (size_t i = lo; i < hi; i++) { pre[i - lo] = acc; if (!x[i].is_zero_mod_l()) acc = acc * x[i]; }
+    Scalar inv = acc.invert();
+    for (size_t i = hi; i-- > lo;) {
+        if (x[i].is_zero_mod_l()) { out[i] = Scalar::zero(); continue; }
+        out[i] = inv * pre[i - lo]; inv = inv * x[i];
+    }
+}
+}  // namespace
+
+bool Engine::lockstep_eligible(uint64_t n, uint32_t flags) const {
+    const uint32_t lg = impl_->tt_orig_lg;
+    return n > 0 && !(flags & 4u) && lg > 0 && ceil_log2(n) <= lg;
+}
+
+void Engine::prove_batch(size_t count, ProveItem *items) {
+    if (!count) return;
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    ProvingGuard in_flight(device_);                // the whole batch is one proof in flight: its kernel variants are chosen once
+    I.shared_now = I.shared_variants();
+    const uint32_t quad = I.shared_now ? 0u : 1u;
+    uint32_t lgmax = 0;
+    for (size_t k = 0; k < count; k++) {
+        if (!lockstep_eligible(items[k].flat->n, items[k].flags)) throw std::logic_error("prove_batch: an item that is not lockstep-eligible");
+        lgmax = std::max(lgmax, ceil_log2(items[k].flat->n));
+    }
+    if (gens_cap_ < (1ull << lgmax)) throw R1CSException(R1CSError::InvalidGeneratorsLength, "generator capacity below padded circuit size");
+    // ONE set of window tables of the original generators, for the largest N of the batch (an item of smaller N reads the first N rows of each half)
+    const ge_niels *Gtab = I.gens.as<ge_niels>(), *Htab = Gtab + gens_cap_;
+    const uint32_t M0T = 1u << lgmax;
+    I.tt_build(Gtab, Htab, I.bases.as<ge_niels>(), M0T, true);
+    const ge_pniels *table = I.tt_table_p, *tabB = I.ped_table.as<ge_pniels>(), *tabBb = tabB + (size_t)TT_WINDOWS * TT_MULTS;
+    StageThreads pool(std::min<uint32_t>(batch_host_threads(), (uint32_t)std::max<size_t>(1, count / 8)));
+
+    // groups of equal lg N, waves of at most batch_wave_mb of device state (and index ranges the 29-bit variable field of the upload holds)
+    std::vector<size_t> order(count);
+    for (size_t k = 0; k < count; k++) order[k] = k;
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return ceil_log2(items[a].flat->n) < ceil_log2(items[b].flat->n); });
+    const uint64_t cap = (uint64_t)I.batch_wave_mb << 20;
+    auto item_bytes = [&](const FlatView &f, uint64_t N) { return 28 * N * 32 + f.q * 48 + f.nnz * 24 + f.ncoef * 64 + f.m * 32 + 1024; };
+    for (size_t g0 = 0; g0 < count;) {
+        const uint32_t lgN = ceil_log2(items[order[g0]].flat->n);
+        const uint64_t N = 1ull << lgN;
+        size_t g1 = g0; uint64_t bytes = 0;
+        while (g1 < count && ceil_log2(items[order[g1]].flat->n) == lgN) {
+            const uint64_t b = item_bytes(*items[order[g1]].flat, N);
+            if (g1 > g0 && (bytes + b > cap || (g1 - g0 + 1) * N > (1ull << 26) || g1 - g0 >= 16384)) break;
+            bytes += b; g1++;
+        }
+        const size_t K = g1 - g0;
+        std::vector<ProveItem *> W(K);
+        for (size_t k = 0; k < K; k++) W[k] = &items[order[g0 + k]];
+        g0 = g1;
+        const uint64_t KN = K * N;
+
+        // ---- offsets of every item in the packed (block-diagonal) instance
+        std::vector<uint64_t> rbase(K + 1), ebase(K + 1), cbase(K + 1), vbase(K + 1);
+        for (size_t k = 0; k < K; k++) {
+            const FlatView &f = *W[k]->flat;
+            rbase[k + 1] = rbase[k] + f.q; ebase[k + 1] = ebase[k] + f.nnz; cbase[k + 1] = cbase[k] + f.ncoef; vbase[k + 1] = vbase[k] + f.m;
+        }
+        const uint64_t qT = rbase[K], nnzT = ebase[K], ncoefT = cbase[K], mT = vbase[K];
+        const uint64_t ncols = 3 * KN + mT + 1, nvar = ncols - 1;
+        if (qT >= (1ull << 32) || nnzT >= (1ull << 32) || ncols >= (1ull << 29)) throw std::invalid_argument("prove_batch: wave too large");
+
+        // ---- pinned upload area (mirrored 1:1 on the device) and the read-back area
+        size_t off = 0;
+        auto take = [&](size_t b) { const size_t o = off; off += Impl::al256(b ? b : 1); return o; };
+        const size_t o_wit = take(3 * KN * 32), o_coef = take(ncoefT * 32), o_raw = take(2 * KN * 64), o_rp = take((qT + 1) * 8), o_tv = take(nnzT * 4),
+                     o_tc = take(nnzT * 4), o_nk = take(K * 4), o_qk = take(K * 4), o_rb = take(K * 4), o_bsc = take(K * BSC * 32), o_bases = take(K * 3 * 32);
+        const size_t up_bytes = off;
+        const size_t o_back = take(std::max<size_t>(K * 3 * 32 + 64, (6 * K + mT + 1) * 32 + 64));
+        I.bt_pin.ensure(off);
+        uint8_t *pin = I.bt_pin.as<uint8_t>();
+        // device: the mirror, then the scalar vectors, the transposed matrix and the workspace
+        const uint32_t nblkC = cdiv(16 * N, 256), nblkR = cdiv(8 * N, 256), pblocks = std::min<uint32_t>(cdiv(N, 256), 1024);
+        const uint32_t nb1 = cdiv(nvar, SCAN_CHUNK), nb2 = cdiv(qT ? qT : 1, SCAN_CHUNK);
+        const size_t d_abc = take(3 * KN * 32), d_coef = take(ncoefT * 32), d_sLR = take(2 * KN * 32), d_ypow = take(KN * 32), d_yinv = take(KN * 32),
+                     d_z = take((qT + 1) * 32), d_w = take(ncols * 32), d_lv = take(KN * 32), d_rv = take(KN * 32), d_fG = take(KN * 32), d_fH = take(KN * 32),
+                     d_c = take(4 * KN * 32), d_tpart = take((size_t)pblocks * 6 * K * 32), d_t = take(6 * K * 32), d_ab = take(2 * K * 32),
+                     d_colptr = take((ncols + 1) * 8), d_erow = take(nnzT * 4), d_ecoef = take(nnzT * 4), d_counts = take((nvar + 2) * 4),
+                     d_starts = take((nvar + 2) * 4), d_cursor = take((nvar + 2) * 4), d_rowc = take((qT + 2) * 4), d_rowcs = take((qT + 2) * 4),
+                     d_bsum = take((std::max(nb1, nb2) + 2) * 4), d_part = take((size_t)K * std::max(3 * nblkC, 2 * nblkR) * sizeof(ge_ext)),
+                     d_pts = take(K * 3 * sizeof(ge_ext)), d_comp = take(K * 3 * 32), d_misc = take(64);
+        I.bt_dev.ensure(off);
+        uint8_t *dev = I.bt_dev.as<uint8_t>();
+        auto D = [&](size_t o) { return dev + o; };
+        scm *aL = reinterpret_cast<scm *>(D(d_abc)), *aR = aL + KN, *aO = aR + KN, *sL = reinterpret_cast<scm *>(D(d_sLR)), *sR = sL + KN;
+        scm *ypow = reinterpret_cast<scm *>(D(d_ypow)), *yinvpow = reinterpret_cast<scm *>(D(d_yinv)), *wAll = reinterpret_cast<scm *>(D(d_w));
+        scm *lv = reinterpret_cast<scm *>(D(d_lv)), *rv = reinterpret_cast<scm *>(D(d_rv)), *bsc = reinterpret_cast<scm *>(D(o_bsc));
+        uint32_t *stale = reinterpret_cast<uint32_t *>(D(d_misc)), *totals = stale + 4;
+        const uint32_t *nk = reinterpret_cast<const uint32_t *>(D(o_nk));
+        scm *h_bsc = reinterpret_cast<scm *>(pin + o_bsc);
+
+        // ---- host, per item: transcript, RNG, the first three blindings and the 2n draws, packed with the instance
+        std::vector<TranscriptRng> rng; rng.reserve(K);
+        for (size_t k = 0; k < K; k++) { W[k]->T->append_u64("m", W[k]->flat->m); rng.push_back(W[k]->T->build_rng(*W[k]->vb, W[k]->seed)); }
+        std::vector<Scalar> ib(K), ob(K), sb(K);
+        pool.run(K, [&](size_t lo, size_t hi) {
+            for (size_t k = lo; k < hi; k++) {
+                const FlatView &f = *W[k]->flat;
+                const uint64_t n = f.n, b = k * N;
+                ib[k] = rng[k].random_scalar(); ob[k] = rng[k].random_scalar(); sb[k] = rng[k].random_scalar();
+                h_bsc[k * BSC + 0] = to_scm(ib[k]); h_bsc[k * BSC + 1] = to_scm(ob[k]); h_bsc[k * BSC + 2] = to_scm(sb[k]);
+                // s_L then s_R: 64 uniform bytes each, in prove()'s order; the padding draws are zero
+                uint8_t *raw = pin + o_raw;
+                rng[k].fill_draws64(raw + 64 * b, n); std::memset(raw + 64 * (b + n), 0, 64 * (N - n));
+                rng[k].fill_draws64(raw + 64 * (KN + b), n); std::memset(raw + 64 * (KN + b + n), 0, 64 * (N - n));
+                const uint8_t *src[3] = {f.aL, f.aR, f.aO};
+                for (int v = 0; v < 3; v++) {
+                    uint8_t *dst = pin + o_wit + 32 * (v * KN + b);
+                    std::memcpy(dst, src[v], 32 * n); std::memset(dst + 32 * n, 0, 32 * (N - n));
+                }
+                if (f.ncoef) std::memcpy(pin + o_coef + 32 * cbase[k], f.coef, 32 * f.ncoef);
+                // the block-diagonal matrix: rows after the earlier items' rows, multiplier i of item k -> column k*N + i of its block (L, R, O),
+                // committed j -> 3KN + vbase + j; coefficient indices after the earlier items' coefficients
+                uint64_t *rp = reinterpret_cast<uint64_t *>(pin + o_rp) + rbase[k];
+                for (uint64_t r = 0; r < f.q; r++) rp[r] = ebase[k] + f.row_ptr[r];
+                uint32_t *tv = reinterpret_cast<uint32_t *>(pin + o_tv) + ebase[k], *tc = reinterpret_cast<uint32_t *>(pin + o_tc) + ebase[k];
+                for (uint64_t e = 0; e < f.nnz; e++) {
+                    const uint32_t pv = f.term_var[e], kind = pv >> 29, idx = pv & 0x1fffffffu;
+                    tv[e] = kind <= 2 ? (kind << 29) | (uint32_t)(b + idx) : (kind == 3 ? (3u << 29) | (uint32_t)(vbase[k] + idx) : pv);
+                    tc[e] = (uint32_t)cbase[k] + f.term_coef[e];
+                }
+                reinterpret_cast<uint32_t *>(pin + o_nk)[k] = (uint32_t)n;
+                reinterpret_cast<uint32_t *>(pin + o_qk)[k] = (uint32_t)f.q;
+                reinterpret_cast<uint32_t *>(pin + o_rb)[k] = (uint32_t)rbase[k];
+            }
+        });
+        reinterpret_cast<uint64_t *>(pin + o_rp)[qT] = nnzT;
+
+        // ---- one upload; witness, coefficients and draws to scalars; the block-diagonal CSR -> CSC in one pass (prove()'s upload kernels)
+        HIPCHK(hipMemcpyAsync(dev, pin, up_bytes, hipMemcpyHostToDevice, I.st));
+        HIPCHK(hipMemsetAsync(stale, 0, 64, I.st));
+        BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(3 * KN, 256)), dim3(256), reinterpret_cast<const uint32_t *>(D(o_wit)), aL, (uint32_t)(3 * KN));
+        if (ncoefT) BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(ncoefT, 256)), dim3(256), reinterpret_cast<const uint32_t *>(D(o_coef)), reinterpret_cast<scm *>(D(d_coef)), (uint32_t)ncoefT);
+        BPG_LAUNCH(I, k_sc_from_wide, dim3(cdiv(2 * KN, 256)), dim3(256), reinterpret_cast<const uint32_t *>(D(o_raw)), sL, (uint32_t)(2 * KN), stale);
+        {
+            const uint64_t *rp = reinterpret_cast<const uint64_t *>(D(o_rp));
+            const uint32_t *tv = reinterpret_cast<const uint32_t *>(D(o_tv)), *tc = reinterpret_cast<const uint32_t *>(D(o_tc));
+            uint32_t *counts = reinterpret_cast<uint32_t *>(D(d_counts)), *starts = reinterpret_cast<uint32_t *>(D(d_starts)), *cursor = reinterpret_cast<uint32_t *>(D(d_cursor));
+            uint32_t *rowconst = reinterpret_cast<uint32_t *>(D(d_rowc)), *rowconst_start = reinterpret_cast<uint32_t *>(D(d_rowcs)), *bsum = reinterpret_cast<uint32_t *>(D(d_bsum));
+            HIPCHK(hipMemsetAsync(counts, 0, (nvar + 1) * 4, I.st));
+            HIPCHK(hipMemsetAsync(rowconst, 0, (qT + 1) * 4, I.st));
+            if (qT) BPG_LAUNCH(I, k_csc_count, dim3(cdiv(qT, 256)), dim3(256), rp, tv, (uint32_t)qT, (uint32_t)KN, (uint32_t)mT, counts, rowconst);
+            BPG_LAUNCH(I, k_scan_blocksums, dim3(nb1), dim3(256), counts, (uint32_t)nvar, bsum);
+            BPG_LAUNCH(I, k_scan_apply, dim3(nb1), dim3(256), counts, (uint32_t)nvar, bsum, starts, cursor);
+            BPG_LAUNCH(I, k_scan_blocksums, dim3(nb2), dim3(256), rowconst, (uint32_t)qT, bsum);
+            BPG_LAUNCH(I, k_scan_apply, dim3(nb2), dim3(256), rowconst, (uint32_t)qT, bsum, rowconst_start, counts /* scratch */);
+            BPG_LAUNCH(I, k_csc_colptr, dim3(cdiv(nvar + 1, 256)), dim3(256), starts, rowconst_start, (uint32_t)nvar, (uint32_t)qT, reinterpret_cast<uint64_t *>(D(d_colptr)), totals);
+            if (qT) BPG_LAUNCH(I, k_csc_fill, dim3(cdiv(qT, 256)), dim3(256), rp, tv, tc, (uint32_t)qT, (uint32_t)KN, (uint32_t)mT, cursor, rowconst_start,
+                               starts + nvar, reinterpret_cast<uint32_t *>(D(d_erow)), reinterpret_cast<uint32_t *>(D(d_ecoef)));
+        }
+        // ---- A_I, A_O, S of every item on the window tables, encoded on the device
+        ge_ext *part = reinterpret_cast<ge_ext *>(D(d_part)), *pts = reinterpret_cast<ge_ext *>(D(d_pts));
+        uint8_t *comp = D(d_comp), *back = pin + o_back;
+        BPG_LAUNCH(I, k_bt_commit3, dim3(nblkC, 3, (uint32_t)K), dim3(256), table, M0T, aL, aR, aO, sL, sR, nk, lgN, part, quad);
+        BPG_LAUNCH(I, k_bt_commit3_finish, dim3(3, (uint32_t)K), dim3(256), part, nblkC, bsc, tabBb, pts, quad);
+        BPG_LAUNCH(I, k_bt_compress, dim3(cdiv(3 * K, 64)), dim3(64), pts, comp, (uint32_t)(3 * K));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(back, comp, 3 * K * 32, hipMemcpyDeviceToHost, I.st));
+        HIPCHK(hipMemcpyAsync(back + 3 * K * 32, totals, 8, hipMemcpyDeviceToHost, I.st));
+        I.wait_stream();
+        if (reinterpret_cast<const uint32_t *>(back + 3 * K * 32)[1] != nnzT) throw std::logic_error("prove_batch: transposition lost entries");
+
+        // ---- host: A_I1, A_O1, S1 -> y, z of every item
+        std::vector<Scalar> y(K), yinv(K), z(K);
+        pool.run(K, [&](size_t lo, size_t hi) {
+            for (size_t k = lo; k < hi; k++) {
+                Transcript &T = *W[k]->T;
+                std::vector<uint8_t> &proof = W[k]->proof;
+                const uint8_t *p3 = back + 96 * k;
+                const bool compact = W[k]->flags & 1u, no_1phase = W[k]->flags & 2u;
+                proof.clear(); proof.reserve(14 * 32 + (2 * lgN + 2) * 32 + 1);
+                if (compact) proof.push_back(0);
+                proof.insert(proof.end(), p3, p3 + 96);
+                T.append_point("A_I1", p3); T.append_point("A_O1", p3 + 32); T.append_point("S1", p3 + 64);
+                if (!no_1phase) T.r1cs_1phase_domain_sep();
+                const uint8_t ident[32] = {0};
+                T.append_point("A_I2", ident); T.append_point("A_O2", ident); T.append_point("S2", ident);
+                if (!compact) proof.insert(proof.end(), 96, 0);
+                y[k] = T.challenge_scalar("y"); z[k] = T.challenge_scalar("z");
+            }
+            batch_invert(y.data(), yinv.data(), lo, hi);
+            scm *hb = reinterpret_cast<scm *>(pin + o_bases);
+            for (size_t k = lo; k < hi; k++) { hb[3 * k] = to_scm(y[k]); hb[3 * k + 1] = to_scm(yinv[k]); hb[3 * k + 2] = to_scm(z[k]); }
+        });
+        // ---- device: powers, flattened weights (block-diagonal CSC, z indexed by global row), t-polynomial of every item
+        HIPCHK(hipMemcpyAsync(D(o_bases), pin + o_bases, K * 3 * 32, hipMemcpyHostToDevice, I.st));
+        {
+            uint64_t qmax = 0; for (size_t k = 0; k < K; k++) qmax = std::max<uint64_t>(qmax, W[k]->flat->q);
+            const uint32_t lgT = std::min<uint32_t>(ceil_log2(std::max<uint64_t>(N, qmax)), 10);
+            BPG_LAUNCH(I, k_bt_exp, dim3(cdiv(1u << lgT, 256), 3, (uint32_t)K), dim3(256), reinterpret_cast<const scm *>(D(o_bases)),
+                       reinterpret_cast<const uint32_t *>(D(o_qk)), reinterpret_cast<const uint32_t *>(D(o_rb)), lgN, lgT, ypow, yinvpow, reinterpret_cast<scm *>(D(d_z)));
+        }
+        BPG_LAUNCH(I, k_flatten, dim3(cdiv(nvar, 256)), dim3(256), reinterpret_cast<const uint64_t *>(D(d_colptr)), reinterpret_cast<const uint32_t *>(D(d_erow)),
+                   reinterpret_cast<const uint32_t *>(D(d_ecoef)), reinterpret_cast<const scm *>(D(d_coef)), reinterpret_cast<const scm *>(D(d_z)), wAll,
+                   (uint32_t)nvar, (uint32_t)(3 * KN));
+        scm *wL = wAll, *wR = wL + KN, *wO = wR + KN, *wV = wO + KN;
+        BPG_LAUNCH(I, k_bt_poly_t, dim3(pblocks, (uint32_t)K), dim3(256), aL, aR, aO, sL, sR, wL, wR, wO, ypow, yinvpow, nk, lgN, reinterpret_cast<scm *>(D(d_tpart)));
+        BPG_LAUNCH(I, k_reduce_partials, dim3((uint32_t)(6 * K)), dim3(256), reinterpret_cast<const scm *>(D(d_tpart)), pblocks, (uint32_t)(6 * K), reinterpret_cast<scm *>(D(d_t)));
+        HIPCHK(hipGetLastError());
+        const scm *h_t = reinterpret_cast<const scm *>(back), *h_wV = h_t + 6 * K;
+        const uint32_t *h_stale = reinterpret_cast<const uint32_t *>(h_wV + mT);
+        HIPCHK(hipMemcpyAsync(back, D(d_t), 6 * K * 32, hipMemcpyDeviceToHost, I.st));
+        if (mT) HIPCHK(hipMemcpyAsync(back + 6 * K * 32, wV, mT * 32, hipMemcpyDeviceToHost, I.st));
+        HIPCHK(hipMemcpyAsync(back + (6 * K + mT) * 32, stale, 4, hipMemcpyDeviceToHost, I.st));
+        I.wait_stream();
+        if (*h_stale) throw DeviceError("a blinding draw of the batch did not reach the device: proofs withheld");
+
+        // ---- host: t_k, tau_k -> T_1, T_3..T_6 of every item in ONE Pedersen launch
+        std::vector<std::array<Scalar, 7>> tk(K), tbk(K);
+        std::vector<uint8_t> vv(5 * K * 32), rr(5 * K * 32), tcom(5 * K * 32);
+        pool.run(K, [&](size_t lo, size_t hi) {
+            static const int idx[5] = {1, 3, 4, 5, 6};
+            for (size_t k = lo; k < hi; k++) {
+                for (int j = 0; j < 6; j++) tk[k][j + 1] = from_scm(h_t[6 * k + j]);
+                Scalar *tb = tbk[k].data();
+                tb[1] = rng[k].random_scalar(); tb[3] = rng[k].random_scalar(); tb[4] = rng[k].random_scalar(); tb[5] = rng[k].random_scalar(); tb[6] = rng[k].random_scalar();
+                for (int j = 0; j < 5; j++) { tk[k][idx[j]].to_bytes(&vv[32 * (5 * k + j)]); tb[idx[j]].to_bytes(&rr[32 * (5 * k + j)]); }
+            }
+        });
+        pedersen_commit(5 * K, vv.data(), rr.data(), tcom.data());
+        // ---- host: u, x, t_x, its blinding, e_blinding, w
+        pool.run(K, [&](size_t lo, size_t hi) {
+            static const char *labels[5] = {"T_1", "T_3", "T_4", "T_5", "T_6"};
+            for (size_t k = lo; k < hi; k++) {
+                Transcript &T = *W[k]->T;
+                std::vector<uint8_t> &proof = W[k]->proof;
+                const uint8_t *out = &tcom[32 * 5 * k];
+                for (int j = 0; j < 5; j++) T.append_point(labels[j], out + 32 * j);
+                proof.insert(proof.end(), out, out + 160);
+                const Scalar u_ch = T.challenge_scalar("u"), x = T.challenge_scalar("x");
+                Scalar *t = tk[k].data(), *tb = tbk[k].data();
+                const std::vector<Scalar> &vb = *W[k]->vb;
+                for (uint64_t j = 0; j < vb.size(); j++) tb[2] += from_scm(h_wV[vbase[k] + j]) * vb[j];
+                Scalar tx, txb;
+                for (int j = 6; j >= 1; j--) { tx = (tx + t[j]) * x; txb = (txb + tb[j]) * x; }
+                const Scalar eb = x * (ib[k] + x * (ob[k] + x * sb[k]));
+                T.append_scalar("t_x", tx); T.append_scalar("t_x_blinding", txb); T.append_scalar("e_blinding", eb);
+                { uint8_t b[96]; tx.to_bytes(b); txb.to_bytes(b + 32); eb.to_bytes(b + 64); proof.insert(proof.end(), b, b + 96); }
+                const Scalar w = T.challenge_scalar("w");
+                T.innerproduct_domain_sep(N);
+                h_bsc[k * BSC + BSC_X] = to_scm(x); h_bsc[k * BSC + BSC_UCH] = to_scm(u_ch); h_bsc[k * BSC + BSC_W] = to_scm(w);
+            }
+        });
+        HIPCHK(hipMemcpyAsync(bsc, h_bsc, K * BSC * 32, hipMemcpyHostToDevice, I.st));
+
+        // ---- device: l(x), r(x), then the inner-product argument of every item: lg N table-driven rounds on the frozen original generators
+        scm *fG = reinterpret_cast<scm *>(D(d_fG)), *fH = reinterpret_cast<scm *>(D(d_fH)), *cc = reinterpret_cast<scm *>(D(d_c));
+        BPG_LAUNCH(I, k_bt_poly_eval, dim3(cdiv(N, 256), (uint32_t)K), dim3(256), aL, aR, aO, sL, sR, wL, wR, wO, ypow, yinvpow, bsc, nk, lgN, lv, rv);
+        if (lgN) BPG_LAUNCH(I, k_bt_factors, dim3(cdiv(N, 256), (uint32_t)K), dim3(256), yinvpow, bsc, nk, lgN, fG, fH, cc);
+        std::vector<Scalar> u(K), uinv(K);
+        uint32_t cur = 0;
+        for (uint32_t j = 0; j < lgN; j++) {
+            const uint32_t h = (uint32_t)(N >> (j + 1));
+            if (j > 0) {
+                const uint32_t hadv = (uint32_t)(N >> j), cnt = 1u << (j - 1);
+                BPG_LAUNCH(I, k_bt_advance, dim3(cdiv(std::max(hadv, cnt), 256), (uint32_t)K), dim3(256), lv, rv, bsc, hadv, cc, cur, cnt, lgN);
+                cur ^= 1u;
+            }
+            BPG_LAUNCH(I, k_bt_round, dim3(nblkR, 2, (uint32_t)K), dim3(256), table, M0T, lv, rv, fG, fH, cc, cur, lgN, j, part, quad);
+            BPG_LAUNCH(I, k_bt_finish, dim3(2, (uint32_t)K), dim3(256), part, nblkR, lv, rv, h, lgN, bsc, tabB, pts, quad);
+            BPG_LAUNCH(I, k_bt_compress, dim3(cdiv(2 * K, 64)), dim3(64), pts, comp, (uint32_t)(2 * K));
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(back, comp, 2 * K * 32, hipMemcpyDeviceToHost, I.st));
+            I.wait_stream();
+            pool.run(K, [&](size_t lo, size_t hi) {
+                for (size_t k = lo; k < hi; k++) {
+                    Transcript &T = *W[k]->T;
+                    const uint8_t *lr = back + 64 * k;
+                    T.append_point("L", lr); T.append_point("R", lr + 32);
+                    W[k]->proof.insert(W[k]->proof.end(), lr, lr + 64);
+                    u[k] = T.challenge_scalar("u");
+                }
+                batch_invert(u.data(), uinv.data(), lo, hi);
+                for (size_t k = lo; k < hi; k++) { h_bsc[k * BSC + BSC_U] = to_scm(u[k]); h_bsc[k * BSC + BSC_UINV] = to_scm(uinv[k]); }
+            });
+            HIPCHK(hipMemcpyAsync(bsc, h_bsc, K * BSC * 32, hipMemcpyHostToDevice, I.st));
+        }
+        // the last round's scalar fold, then the final a, b of every item
+        BPG_LAUNCH(I, k_bt_fold_scalars, dim3(cdiv(K, 256)), dim3(256), lv, rv, bsc, lgN, reinterpret_cast<scm *>(D(d_ab)), (uint32_t)K);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(back, D(d_ab), 2 * K * 32, hipMemcpyDeviceToHost, I.st));
+        I.wait_stream();
+        const scm *h_ab = reinterpret_cast<const scm *>(back);
+        for (size_t k = 0; k < K; k++) {
+            uint8_t o[64]; from_scm(h_ab[2 * k]).to_bytes(o); from_scm(h_ab[2 * k + 1]).to_bytes(o + 32);
+            W[k]->proof.insert(W[k]->proof.end(), o, o + 64);
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ verify

@@ -104,6 +104,16 @@ public:
     // Every proof's verification equation weighted by a random rho_k, all of them in ONE multiscalar multiplication; status_out[k] is what verify()
     // returns for item k alone (a rejected batch is re-verified item by item).
     void verify_batch(size_t count, const VerifyItem *items, const uint8_t batch_seed[32], R1CSError *status_out);
+    // One proof of a lockstep batch (include/bpg.h bpg_r1cs_prove_batch): an instance with its witness that passed the checks of bpg_r1cs_prove and
+    // lockstep_eligible(); T is updated in place and proof filled exactly as prove() does for the item alone.
+    struct ProveItem {
+        const FlatView *flat = nullptr; Transcript *T = nullptr; const std::vector<Scalar> *vb = nullptr; const uint8_t *seed = nullptr; uint32_t flags = 0;
+        std::vector<uint8_t> proof;
+    };
+    // does a proof of n multipliers with these flags take the lockstep path (0 < n, padded N <= 2^tt_orig_lg, no expanded blinding)
+    bool lockstep_eligible(uint64_t n, uint32_t flags) const;
+    // every item proved in lockstep: grouped by lg N, each group in waves of at most BPG_BATCH_WAVE_MB of device state, one launch per stage per wave
+    void prove_batch(size_t count, ProveItem *items);
     // the host-side checks upload() makes on an instance (CSR shape, index ranges, sizes): std::invalid_argument, no device work
     static void check_instance(const FlatView &c);
     void synchronize();

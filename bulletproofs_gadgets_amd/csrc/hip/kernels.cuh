@@ -17,7 +17,10 @@
 //                                       k_tt_multiples, k_tt_factors, then k_tt_advance, k_tt_round, k_tt_finish per round
 //   f1  Verifier::verify                k_decompress, k_flatten_const, k_ipa_s, k_verify_scalars + one MSM
 //       batch verification              the same per proof with k_verify_scalars_acc (weighted g_i, h_i added into two shared accumulators) + one MSM per batch
-// The kernels live in k_points.cuh, k_scalars.cuh, k_ipa.cuh, k_verify.cuh and k_msm.cuh, included at the end of this file in that order.
+//       lockstep batch proving          (N <= 2^tt_orig_lg, k_batch.cuh) one launch per stage for every proof of a wave: the upload kernels on one block-diagonal
+//                                       matrix, k_bt_commit3(_finish), k_bt_compress, k_bt_exp, k_flatten, k_bt_poly_t, k_pedersen, k_bt_poly_eval, k_bt_factors,
+//                                       then k_bt_advance, k_bt_round, k_bt_finish, k_bt_compress per round and k_bt_fold_scalars
+// The kernels live in k_points.cuh, k_scalars.cuh, k_ipa.cuh, k_verify.cuh, k_msm.cuh, k_merge.cuh and k_batch.cuh, included at the end of this file in that order.
 // Data layout in HBM: scalars = 8 x u32 Montgomery form, 32 B each, AoS (lane i <-> element i: 2 x 16 B coalesced
 // loads); generator tables = affine Niels (y+x, y-x, 2dxy), 96 B per point, G at [0,N) and H at [N,2N); window tables =
 // projective Niels (y+x, y-x, z, 2dt), 128 B per entry.
@@ -58,3 +61,4 @@ __device__ __forceinline__ uint32_t msm_point_index(const MsmSegs &S, uint32_t s
 #include "k_verify.cuh"
 #include "k_msm.cuh"
 #include "k_merge.cuh"
+#include "k_batch.cuh"

@@ -190,6 +190,18 @@ bpg_status bpg_pool_create(int32_t device, uint32_t workers, uint64_t gens_capac
 bpg_status bpg_pool_create_ex(int32_t device, uint32_t workers, uint64_t gens_capacity, const bpg_config *config /* of every context; NULL = defaults */, bpg_pool **out);
 void bpg_pool_destroy(bpg_pool *pool);
 bpg_status bpg_pool_prove(bpg_pool *pool, uint64_t count, const bpg_batch_item *items, bpg_status *status_out);
+/* Many SMALL proofs in lockstep on one context: the proofs of a batch share every launch of the prove pipeline (one per stage for all of them),
+ * and their Fiat-Shamir steps run between the stages on up to 16 host threads (the cores the process may use, capped by its CPU quota).
+ * proof_out, *proof_len, transcript_state and status_out[i] of each item are exactly what bpg_r1cs_prove(ctx, item...) gives for it alone,
+ * byte for byte, whatever the batch around it.  Lockstep: items with 0 < n and padded N <= 2^14 (BPG_TT_ORIG_LG), dialect flags 1 and 2 included;
+ * every other item - larger circuits, n = 0, BPG_TT_ORIG_LG=0, and BPG_FLAG_EXPANDED_BLINDING, which always takes this path - is proved by
+ * bpg_r1cs_prove inside the same call.  Items are grouped by lg N and each group runs in waves of at most BPG_BATCH_WAVE_MB (default 512;
+ * 0 = one proof per wave) of device state (about 30 N x 32 B per proof).
+ * A NULL ctx, or NULL items / status_out with count > 0, refuses the whole call (BPG_ERR_INVALID_ARGUMENT, nothing launched or written);
+ * count == 0 returns BPG_OK.  Anything else fails per item with bpg_r1cs_prove's status while the other items are proved (NULL pointers in the
+ * item, a malformed instance, an m mismatch, a proof buffer below bpg_proof_size, a generator capacity below N).  Returns BPG_OK when every item
+ * succeeded, else the status of the first failing item; bpg_last_error names it.  (An addition to ABI version 7.) */
+bpg_status bpg_r1cs_prove_batch(bpg_ctx *ctx, uint64_t count, const bpg_batch_item *items, bpg_status *status_out);
 
 /* measurement hooks (bench.py): HIP events on the engine's own stream. mode 0 off, 1 = dominant kernel only, 2 = all kernels;
  * report = JSON text {kernel: {count, total_ms, alg_bytes, device_bytes, field_mults}} accumulated since the last set. */
