@@ -40,6 +40,11 @@ class R1CSInstance(C.Structure):
                 ("term_var", C.c_void_p), ("term_coef", C.c_void_p), ("coef", C.c_void_p)]
 
 
+class WitnessProgramView(C.Structure):
+    """bpg_witness_program (frozen)."""
+    _fields_ = [("lc_ptr", C.c_void_p), ("term_var", C.c_void_p), ("term_coef", C.c_void_p), ("n_params", C.c_uint64), ("param_rows", C.c_void_p)]
+
+
 class Timings(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("rng_host", "msm_aiao", "msm_s", "poly", "ipa", "total", "ipa_msm", "ipa_fold", "ipa_sync")]
 
@@ -346,6 +351,13 @@ class Context:
         _chk(lib().bpg_r1cs_upload(self._h, C.byref(cs), C.byref(h)))
         return ResidentCircuit(self, h, inst.n, inst.m)
 
+    def upload_template(self, inst: "FlatInstance", program: "WitnessProgram"):
+        """bpg_r1cs_upload_template: the instance (with or without a witness) plus its witness program; ResidentCircuit.assign gives it fresh witnesses."""
+        h = C.c_void_p()
+        cs, cp = inst.cstruct(), program.cstruct()
+        _chk(lib().bpg_r1cs_upload_template(self._h, C.byref(cs), C.byref(cp), C.byref(h)))
+        return ResidentCircuit(self, h, inst.n, inst.m, n_params=len(program.param_rows))
+
     def blinding_begin(self, transcript_state, v_blinding, rng_seed, max_multipliers):
         """bpg_blinding_begin: start the blinding chain of the next prove on this context (state after every "V" append, m x 32 blinding bytes)."""
         ts = _buf(203); ts.raw = _exact("transcript_state", transcript_state, 203)
@@ -555,8 +567,18 @@ class ProverPool:
 
 
 class ResidentCircuit:
-    def __init__(self, ctx, h, n, m):
+    def __init__(self, ctx, h, n, m, n_params=None):
         self.ctx, self._h, self.n, self.m = ctx, h, n, m
+        self.n_params = n_params            # None: a plain upload; a number: a circuit template (Prover.template / Context.upload_template)
+
+    def assign(self, values, params=()):
+        """bpg_r1cs_assign: a fresh witness for a circuit template - the m committed values (and the constant term of every parameter row); the device
+        computes a_L, a_R, a_O.  The caller commits to the same values and proves with prove()."""
+        v = _scalars32("values", values, self.m)
+        pv = bytes(params) if isinstance(params, (bytes, bytearray)) else b"".join(_exact("params", x, 32) for x in params)
+        if len(pv) % 32:
+            raise ValueError("params must be a multiple of 32 bytes")
+        _chk(lib().bpg_r1cs_assign(self.ctx._h, self._h, C.c_uint64(self.m), v if self.m else None, C.c_uint64(len(pv) // 32), pv if pv else None))
 
     def prove(self, transcript_state, v_blinding, rng_seed=None, flags=0, timings=False):
         ts = _buf(203); ts.raw = _exact("transcript_state", transcript_state, 203)
@@ -584,6 +606,33 @@ class ResidentCircuit:
             self.free()
         except Exception:
             pass
+
+
+class WitnessProgram:
+    """Owned copy of a bpg_witness_program: multiplier i has left = terms [lc_ptr[2i], lc_ptr[2i+1]) and right = [lc_ptr[2i+1], lc_ptr[2i+2]); a term is
+    (term_var = kind << 29 | index, term_coef = index into the instance's coefficient table); param_rows: constraint rows whose constant term is assigned per witness."""
+
+    def __init__(self, lc_ptr, term_var, term_coef, param_rows=()):
+        import numpy as np
+        self.lc_ptr = np.ascontiguousarray(lc_ptr, dtype=np.uint64)
+        self.term_var = np.ascontiguousarray(term_var, dtype=np.uint32)
+        self.term_coef = np.ascontiguousarray(term_coef, dtype=np.uint32)
+        self.param_rows = [int(r) for r in param_rows]
+
+    def cstruct(self):
+        import numpy as np
+        rows = np.ascontiguousarray(self.param_rows, dtype=np.uint64)
+        c = WitnessProgramView()
+        c.lc_ptr, c.term_var, c.term_coef = self.lc_ptr.ctypes.data, self.term_var.ctypes.data, self.term_coef.ctypes.data
+        c.n_params, c.param_rows = len(rows), rows.ctypes.data if len(rows) else None
+        c._owner = (self, rows)
+        return c
+
+
+def _scalars32(name, values, count):
+    """count x 32 bytes from bytes or a sequence of 32-byte strings"""
+    data = bytes(values) if isinstance(values, (bytes, bytearray)) else b"".join(_exact(name, x, 32) for x in values)
+    return _exact(name, data, 32 * count)
 
 
 class FlatInstance:
@@ -725,6 +774,29 @@ class Prover:
         _chk(lib().bpg_prover_instance(self._h, C.byref(view), C.byref(v), C.byref(vb)))
         m = view.m
         return FlatInstance(view, v=C.string_at(v, 32 * m) if m else b"", v_blinding=C.string_at(vb, 32 * m) if m else b"")
+
+    def witness_program(self) -> WitnessProgram:
+        """bpg_prover_witness_program: how every multiplier's assignment follows from committed values and earlier multipliers (owned copy).
+        INVALID_ARGUMENT for a circuit with free multipliers (allocate / allocate_multiplier) or with none."""
+        import numpy as np
+        view = WitnessProgramView()
+        _chk(lib().bpg_prover_witness_program(self._h, C.byref(view)))
+        n = self.get_num_multiplications()
+        lc_ptr = np.frombuffer(C.string_at(view.lc_ptr, 8 * (2 * n + 1)), dtype=np.uint64).copy()
+        nt = int(lc_ptr[-1])
+        grab = lambda ptr, dt, k: np.frombuffer(C.string_at(ptr, k * np.dtype(dt).itemsize) if k else b"", dtype=dt).copy()
+        return WitnessProgram(lc_ptr, grab(view.term_var, np.uint32, nt), grab(view.term_coef, np.uint32, nt), grab(view.param_rows, np.uint64, view.n_params))
+
+    def mark_param_row(self, row: int):
+        """bpg_prover_mark_param_row: the constant term of constraint `row` changes with the witness (num_constraints() - 1 right after the constrain call)."""
+        _chk(lib().bpg_prover_mark_param_row(self._h, C.c_uint64(row)))
+
+    def template(self, ctx: "Context", param_rows=()) -> "ResidentCircuit":
+        """This circuit as a template resident on `ctx` (with this prover's witness): ResidentCircuit.assign(values, params) then gives it the witness of
+        further proofs of the same shape without another host assembly.  param_rows: rows whose constant term is assigned per witness, besides the marked ones."""
+        prog = self.witness_program()
+        prog.param_rows = prog.param_rows + [int(r) for r in param_rows]
+        return ctx.upload_template(self.instance(), prog)
 
     def start_blinding(self, rng_seed: bytes = None, max_multipliers: int = 1 << 20):
         """Extension (include/bpg.h bpg_prover_start_blinding): all commitments made - start the serial TranscriptRng chain of the coming

@@ -111,9 +111,9 @@ void Prover::start_blinding(const uint8_t rng_seed[32], uint64_t max_multipliers
 
 // ---------------------------------------------------------------------------------------- handles
 struct bpg_ctx { Engine *engine; };
-struct bpg_circuit { DeviceCircuit *dc; uint64_t n, m; };
+struct bpg_circuit { DeviceCircuit *dc; uint64_t n, m; bool is_template = false; uint64_t n_params = 0; };     // dc == nullptr: bpg_test_circuit_handle
 struct bpg_transcript { Transcript t; };
-struct bpg_prover { Prover *p; FlatCircuit flat; std::vector<uint8_t> v_bytes, vb_bytes; };
+struct bpg_prover { Prover *p; FlatCircuit flat; std::vector<uint8_t> v_bytes, vb_bytes; WitnessProgram program; };
 struct bpg_verifier { Verifier *v; FlatCircuit flat; };
 struct bpg_gadget { std::unique_ptr<Gadget> g; };
 struct bpg_buffer { OpBuffer b; };
@@ -248,7 +248,63 @@ bpg_status bpg_r1cs_upload(bpg_ctx *ctx, const bpg_r1cs_instance *inst, bpg_circ
         *out = new bpg_circuit{dc, f.n, f.m};
     });
 }
-void bpg_r1cs_free(bpg_ctx *ctx, bpg_circuit *c) { if (ctx && c) { ctx->engine->free_circuit(c->dc); delete c; } }
+void bpg_r1cs_free(bpg_ctx *ctx, bpg_circuit *c) {
+    if (!c || (c->dc && !ctx)) return;
+    if (c->dc) ctx->engine->free_circuit(c->dc);
+    delete c;
+}
+
+static WitnessProgramView program_view(const bpg_witness_program *w) {
+    REQUIRE(w);
+    WitnessProgramView v; v.lc_ptr = w->lc_ptr; v.term_var = w->term_var; v.term_coef = w->term_coef; v.n_params = w->n_params; v.param_rows = w->param_rows;
+    return v;
+}
+bpg_status bpg_r1cs_upload_template(bpg_ctx *ctx, const bpg_r1cs_instance *inst, const bpg_witness_program *program, bpg_circuit **out) {
+    return guard([&] {
+        REQUIRE(out); *out = nullptr;
+        REQUIRE(ctx && inst && program);
+        const FlatView f = as_view(inst, false);
+        const WitnessProgramView w = program_view(program);
+        const TemplatePlan plan = Engine::plan_template(f, w);      // every check, the level cap included, before the context is touched
+        DeviceCircuit *dc = ctx->engine->upload_template(f, plan);
+        bpg_circuit *c = new bpg_circuit{dc, f.n, f.m}; c->is_template = true; c->n_params = w.n_params;
+        *out = c;
+    });
+}
+bpg_status bpg_r1cs_assign(bpg_ctx *ctx, bpg_circuit *c, uint64_t m, const uint8_t *v, uint64_t n_params, const uint8_t *param_values) {
+    return guard([&] {
+        REQUIRE(ctx && c);
+        if (!c->is_template) throw std::invalid_argument("assign: the circuit is not a template (bpg_r1cs_upload_template)");
+        if (m != c->m) throw std::invalid_argument("assign: m does not match the template");
+        if (n_params != c->n_params) throw std::invalid_argument("assign: n_params does not match the template");
+        REQUIRE((m == 0 || v) && (n_params == 0 || param_values));
+        if (!c->dc) throw std::invalid_argument("assign: the handle has no device state (bpg_test_circuit_handle)");
+        ctx->engine->assign(c->dc, v, param_values);
+    });
+}
+bpg_status bpg_test_template_schedule(const bpg_r1cs_instance *inst, const bpg_witness_program *program, char *out, uint64_t cap) {
+    return guard([&] {
+        REQUIRE(inst && program && out && cap);
+        const std::string r = witness_schedule_json(Engine::plan_template(as_view(inst, false), program_view(program)).schedule);
+        if (r.size() + 1 > cap) throw std::invalid_argument("template_schedule: buffer too small (" + std::to_string(r.size() + 1) + " bytes needed)");
+        std::memcpy(out, r.c_str(), r.size() + 1);
+    });
+}
+bpg_status bpg_test_template_eval(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const uint8_t *v, uint8_t *aL, uint8_t *aR, uint8_t *aO) {
+    return guard([&] {
+        REQUIRE(inst && program && aL && aR && aO && (inst->m == 0 || v));
+        Engine::template_eval_host(as_view(inst, false), program_view(program), v, aL, aR, aO);
+    });
+}
+bpg_status bpg_test_circuit_handle(const bpg_r1cs_instance *inst, const bpg_witness_program *program, bpg_circuit **out) {
+    return guard([&] {
+        REQUIRE(out); *out = nullptr;
+        const FlatView f = as_view(inst, false);
+        if (program) (void)Engine::plan_template(f, program_view(program)); else Engine::check_instance(f);
+        bpg_circuit *c = new bpg_circuit{nullptr, f.n, f.m}; c->is_template = program != nullptr; c->n_params = program ? program->n_params : 0;
+        *out = c;
+    });
+}
 
 static void copy_timings(const ProveTimings &t, bpg_timings *o) {
     if (!o) return;
@@ -259,7 +315,7 @@ static void copy_timings(const ProveTimings &t, bpg_timings *o) {
 bpg_status bpg_r1cs_prove_resident(bpg_ctx *ctx, bpg_circuit *c, uint8_t ts[BPG_TRANSCRIPT_STATE_BYTES], uint64_t m, const uint8_t *v_blinding,
                                    const uint8_t seed[32], uint32_t flags, uint8_t *proof_out, uint64_t *proof_len, bpg_timings *timings) {
     return guard([&] {
-        REQUIRE(ctx && c && ts && seed && proof_out && proof_len && (m == 0 || v_blinding));
+        REQUIRE(ctx && c && c->dc && ts && seed && proof_out && proof_len && (m == 0 || v_blinding));
         if (m != c->m) throw std::invalid_argument("prove: m does not match the uploaded circuit");
         if (*proof_len < bpg_proof_size(c->n, flags)) throw std::invalid_argument("prove: proof buffer too small");
         uint64_t N = 1; while (N < c->n) N <<= 1;
@@ -362,7 +418,7 @@ bpg_status bpg_r1cs_verify(bpg_ctx *ctx, const bpg_r1cs_instance *inst, uint8_t 
 bpg_status bpg_r1cs_verify_resident(bpg_ctx *ctx, bpg_circuit *c, uint8_t ts[BPG_TRANSCRIPT_STATE_BYTES], uint64_t m, const uint8_t *V,
                                     const uint8_t *proof, uint64_t proof_len, const uint8_t seed[32], uint32_t flags) {
     return guard([&] {
-        REQUIRE(ctx && c && ts && proof && seed && (m == 0 || V));
+        REQUIRE(ctx && c && c->dc && ts && proof && seed && (m == 0 || V));
         if (m != c->m) throw std::invalid_argument("verify: m does not match the uploaded circuit");
         Transcript T = Transcript::from_state(ts);
         const R1CSError e = ctx->engine->verify(c->dc, T, V, proof, proof_len, seed, flags);
@@ -393,6 +449,7 @@ bpg_status bpg_r1cs_verify_batch(bpg_ctx *ctx, uint64_t count, const bpg_verify_
                 e.flat = &views[k];
             } else {
                 if (it.m != it.circuit->m) throw std::invalid_argument(who + ": m does not match the uploaded circuit");
+                if (!it.circuit->dc) throw std::invalid_argument(who + ": the circuit handle has no device state");
                 e.dc = it.circuit->dc;
             }
             T[k] = Transcript::from_state(it.transcript_state);
@@ -548,6 +605,16 @@ bpg_status bpg_prover_instance(bpg_prover *p, bpg_r1cs_instance *out, const uint
         if (vb_out) *vb_out = p->vb_bytes.data();
     });
 }
+
+bpg_status bpg_prover_witness_program(bpg_prover *p, bpg_witness_program *out) {
+    return guard([&] {
+        REQUIRE(p && out);
+        p->program = p->p->witness_program();
+        out->lc_ptr = p->program.lc_ptr.data(); out->term_var = p->program.term_var.data(); out->term_coef = p->program.term_coef.data();
+        out->n_params = p->program.param_rows.size(); out->param_rows = p->program.param_rows.data();
+    });
+}
+bpg_status bpg_prover_mark_param_row(bpg_prover *p, uint64_t row) { return guard([&] { REQUIRE(p); p->p->mark_param_row(row); }); }
 
 bpg_status bpg_prover_start_blinding(bpg_prover *p, const uint8_t seed[32], uint64_t max_multipliers) {
     return guard([&] { REQUIRE(p && seed); p->p->start_blinding(seed, max_multipliers); });

@@ -204,6 +204,12 @@ struct DeviceCircuit {
     struct MergeSet { uint32_t groups = 0, skipped = 0; DevBuf skipA, skipB, sc, pts; };
     bool merge_tried = false;
     MergeSet mI, mO;
+    // circuit template (upload_template): the packed witness program and its schedule in HBM, the committed values of the last assign(), and where the
+    // per-witness constant terms live in `coef` (slots [param_first, param_first + n_params))
+    bool is_template = false;
+    DevBuf wit_stream, wit_segs, wit_v;
+    std::vector<uint32_t> wit_level_ptr;    // level l = segments [wit_level_ptr[l], wit_level_ptr[l + 1]) of wit_segs
+    uint64_t n_params = 0, param_first = 0;
 };
 
 // kernel ids for the optional HIP-event profile (bpg_profile_*)
@@ -213,7 +219,7 @@ struct DeviceCircuit {
     X(k_scan_apply) X(k_bucket_chunks) X(k_bucket_combine) X(k_bucket_combine_heavy) X(k_bucket_reduce) X(k_window_sums) X(k_window_sums_quad) X(k_decompress) X(k_ipa_s) X(k_verify_scalars) X(k_verify_scalars_acc) X(k_bench_fe_mul) \
     X(k_tt_bases) X(k_tt_multiples) X(k_tt_bases8) X(k_tt_multiples8) X(k_tt_round8) X(k_tt_factors) X(k_tt_advance) X(k_tt_round) X(k_tt_finish) X(k_blind_expand) X(k_tt_commit3) X(k_tt_commit3_finish) X(k_csc_count) X(k_csc_fill) X(k_csc_colptr) X(k_merge_insert) X(k_merge_plan) X(k_merge_groups) X(k_merge_members) X(k_merge_sum) \
     X(k_bt_commit3) X(k_bt_commit3_finish) X(k_bt_compress) X(k_bt_exp) X(k_bt_poly_t) X(k_bt_poly_eval) X(k_bt_factors) X(k_bt_advance) X(k_bt_round) \
-    X(k_bt_finish) X(k_bt_fold_scalars)
+    X(k_bt_finish) X(k_bt_fold_scalars) X(k_witness_eval)
 enum KernelId {
 #define X(n) KID_##n,
     BPG_KERNELS(X)
@@ -235,6 +241,7 @@ struct Engine::Impl {
     std::vector<ProfRec> prof_open;
     std::vector<hipEvent_t> prof_pool;
     double prof_ms[KID_COUNT] = {0};
+    std::vector<float> prof_wit_ms;     // the first 1024 k_witness_eval launches since the last reset, in launch order (a launch = a level of an assign)
     uint64_t prof_count[KID_COUNT] = {0};
     double prof_alg_bytes[KID_COUNT] = {0}, prof_act_bytes[KID_COUNT] = {0}, prof_fm[KID_COUNT] = {0};
     bool prof_on(int id) const { return prof_mode == 2 || (prof_mode == 1 && (id == KID_k_fold_points || id == KID_k_fold_points_reg || id == KID_k_fold_points_split || id == KID_k_fold_points_wnaf || id == KID_k_fold_points_quad || id == KID_k_fold_points_quadw || id == KID_k_fold_points_regw || id == KID_k_bucket_chunks)); }
@@ -245,10 +252,10 @@ struct Engine::Impl {
     void prof_collect() {
         if (prof_open.empty()) return;
         HIPCHK(hipStreamSynchronize(st));
-        for (ProfRec &r : prof_open) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, r.a, r.b)); prof_ms[r.id] += ms; prof_count[r.id]++; prof_pool.push_back(r.a); prof_pool.push_back(r.b); }
+        for (ProfRec &r : prof_open) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, r.a, r.b)); prof_ms[r.id] += ms; prof_count[r.id]++; if (r.id == KID_k_witness_eval && prof_wit_ms.size() < 1024) prof_wit_ms.push_back(ms); prof_pool.push_back(r.a); prof_pool.push_back(r.b); }
         prof_open.clear();
     }
-    void prof_reset() { prof_collect(); for (int i = 0; i < KID_COUNT; i++) { prof_ms[i] = 0; prof_count[i] = 0; prof_alg_bytes[i] = prof_act_bytes[i] = prof_fm[i] = 0; } }
+    void prof_reset() { prof_collect(); for (int i = 0; i < KID_COUNT; i++) { prof_ms[i] = 0; prof_count[i] = 0; prof_alg_bytes[i] = prof_act_bytes[i] = prof_fm[i] = 0; } prof_wit_ms.clear(); }
     std::shared_ptr<SharedTables> shared;       // the generation of generator tables this context works on
     DevBuf gens;                                // view of shared->gens (not owned)
     DevBuf bases, scratch_ext, comp, small_in, small_sc;
@@ -289,6 +296,7 @@ struct Engine::Impl {
     uint32_t profile = 1;           // 1 one-shot, 2 serving (what bpg_config / BPG_PROFILE settled on)
     bool shared_now = false;        // sampled ONCE per prove()/verify(): does this call take the shared-device variants (shared_variants())
     uint32_t msm_cmin = 2;          // BPG_MSM_CMIN: narrowest window (tests: wide windows on small sums)
+    uint32_t wit_waves = 1024;      // waves k_witness_eval spreads a level's lanes over: one per SIMD of the device the context is created on
     uint32_t merge_equal = 1;       // BPG_MERGE: 0 A_I and A_O term by term; 1 equal scalars grouped once per uploaded witness (at its first proof); 2 grouped afresh in EVERY
                                     // proof (what a host that proves each witness once pays: the measurement behind bench.py's `merge_per_proof`); same bytes
     uint32_t merged_last = 0, merged_skipped_last = 0;   // witness of the last prove(): groups of equal scalars in A_I and A_O, and the terms they replace (0: none, or the table-driven path)
@@ -627,6 +635,7 @@ Engine::Engine(int device, const EngineConfig &cfg) : device_(device) {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) {
             if (!resident_set) K->sweep_blocks_resident = (uint32_t)cus * 4u;
+            K->wit_waves = (uint32_t)cus * 4u;
             if (!env_present("BPG_WINDOW_QUAD_BLOCKS")) K->window_quad_blocks = (uint32_t)cus + (uint32_t)cus / 8u;
         }
     }
@@ -699,6 +708,11 @@ std::string Engine::profile_report() {
                   impl_->fold_adapt, impl_->fold_split_max, (unsigned)impl_->fold_quad, impl_->msm_cmax, impl_->msm_cmax_shared, impl_->msm_cmin, impl_->rseg, impl_->lgch,
                   impl_->sweep_blocks_resident, (unsigned)impl_->shared_now, (unsigned)impl_->merge_equal, impl_->merged_last, impl_->merged_skipped_last, impl_->merge_ms_last, (unsigned long long)impl_->table_budget, (unsigned long long)table_bytes_held(device_));
     std::string out = sch;
+    if (!impl_->prof_wit_ms.empty()) {
+        out += ", \"_witness_launch_ms\": [";
+        for (size_t i = 0; i < impl_->prof_wit_ms.size(); i++) { char b[32]; std::snprintf(b, sizeof b, "%s%.4f", i ? "," : "", impl_->prof_wit_ms[i]); out += b; }
+        out += "]";
+    }
     bool first = false;
     for (int i = 0; i < KID_COUNT; i++) {
         if (!impl_->prof_count[i]) continue;
@@ -1268,11 +1282,87 @@ DeviceCircuit *Engine::upload(const FlatView &c) {
 void Engine::free_circuit(DeviceCircuit *c) {
     if (!c) return;
     (void)hipSetDevice(device_);
-    DevBuf *b[] = {&c->aL, &c->aR, &c->aO, &c->col_ptr, &c->ent_row, &c->ent_coef, &c->coef, &c->mI.skipA, &c->mI.skipB, &c->mI.sc, &c->mI.pts, &c->mO.skipA, &c->mO.skipB, &c->mO.sc, &c->mO.pts};
+    DevBuf *b[] = {&c->wit_stream, &c->wit_segs, &c->wit_v, &c->aL, &c->aR, &c->aO, &c->col_ptr, &c->ent_row, &c->ent_coef, &c->coef, &c->mI.skipA, &c->mI.skipB, &c->mI.sc, &c->mI.pts, &c->mO.skipA, &c->mO.skipB, &c->mO.sc, &c->mO.pts};
     for (DevBuf *x : b) x->release();
     delete c;
 }
 
+// ------------------------------------------------------------------------------------------------ circuit templates (host/template.hpp, hip/k_witness.cuh)
+TemplatePlan Engine::plan_template(const FlatView &c, const WitnessProgramView &p) {
+    check_instance(c);
+    check_witness_program(c, p);
+    TemplatePlan T;
+    T.schedule = build_witness_schedule(c.n, c.m, p);
+    T.packed = pack_witness_program(c, p, T.schedule);              // the classes come from the caller's table: slots are constants of rows only
+    T.slotted = with_parameter_slots(c, p);
+    T.n_params = p.n_params; T.param_first = c.ncoef;
+    return T;
+}
+// TEST HOOK (bpg_test_template_eval): the interpreter of k_witness.cuh compiled for the HOST, over the same packed program in the same level order
+void Engine::template_eval_host(const FlatView &c, const WitnessProgramView &p, const uint8_t *v, uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out) {
+    const TemplatePlan T = plan_template(c, p);
+    const PackedWitnessProgram &P = T.packed;
+    auto load = [](const uint8_t *b, size_t count) {
+        std::vector<scm> out(count ? count : 1);
+        for (size_t i = 0; i < count; i++) { uint32_t w[8]; std::memcpy(w, b + 32 * i, 32); out[i] = sc_from_words(w); }
+        return out;
+    };
+    const std::vector<scm> coef = load(c.coef, c.ncoef), vv = load(v, c.m);
+    std::vector<scm> aL(c.n), aR(c.n), aO(c.n);
+    for (const WitnessSegment &s : P.segs) witness_eval_segment(s.first, s.count, P.stream.data() + s.stream, coef.data(), vv.data(), aL.data(), aR.data(), aO.data());
+    for (size_t i = 0; i < c.n; i++) {
+        uint32_t w[8];
+        sc_to_words(w, aL[i]); std::memcpy(aL_out + 32 * i, w, 32);
+        sc_to_words(w, aR[i]); std::memcpy(aR_out + 32 * i, w, 32);
+        sc_to_words(w, aO[i]); std::memcpy(aO_out + 32 * i, w, 32);
+    }
+}
+
+DeviceCircuit *Engine::upload_template(const FlatView &c, const TemplatePlan &T) {
+    const PackedWitnessProgram &P = T.packed;
+    FlatView f(T.slotted); f.aL = c.aL; f.aR = c.aR; f.aO = c.aO;
+    DeviceCircuit *d = upload(f);
+    try {
+        Impl &I = *impl_;
+        d->is_template = true; d->n_params = T.n_params; d->param_first = T.param_first;
+        d->wit_level_ptr = T.schedule.level_ptr;
+        d->wit_stream.ensure(P.stream.size() * 4); d->wit_segs.ensure(P.segs.size() * sizeof(WitnessSegment)); d->wit_v.ensure((c.m ? c.m : 1) * sizeof(scm));
+        I.h2d(d->wit_stream.p, P.stream.data(), P.stream.size() * 4);
+        I.h2d(d->wit_segs.p, P.segs.data(), P.segs.size() * sizeof(WitnessSegment));
+        HIPCHK(hipStreamSynchronize(I.st));
+    } catch (...) { free_circuit(d); throw; }
+    return d;
+}
+
+void Engine::assign(DeviceCircuit *d, const uint8_t *v, const uint8_t *param_values) {
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    if (!d || !d->is_template) throw std::invalid_argument("assign: the circuit is not a template (bpg_r1cs_upload_template)");
+    // the previous witness is gone from here on: a failure below must not leave its caches behind either
+    d->has_witness = false;
+    d->merge_tried = false; d->mI.groups = d->mI.skipped = 0; d->mO.groups = d->mO.skipped = 0;   // the equal-scalar sets belong to the witness they were built from
+    const uint64_t cnt[2] = {d->m, d->n_params};
+    const uint8_t *src[2] = {v, param_values};
+    scm *dst[2] = {d->wit_v.as<scm>(), d->coef.as<scm>() + d->param_first};
+    I.small_sc.ensure((std::max(cnt[0], cnt[1]) + 1) * 32);
+    for (int k = 0; k < 2; k++) {
+        if (!cnt[k]) continue;
+        I.h2d(I.small_sc.p, src[k], cnt[k] * 32);
+        BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(cnt[k], 256)), dim3(256), I.small_sc.as<uint32_t>(), dst[k], (uint32_t)cnt[k]);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(I.st));                                     // small_sc is staged again below
+    }
+    // a level's lanes are few (a 512-leaf tree: at most 256): spread them over waves until every SIMD of the device has one
+    for (size_t l = 0; l + 1 < d->wit_level_ptr.size(); l++) {
+        const uint32_t s0 = d->wit_level_ptr[l], ns = d->wit_level_ptr[l + 1] - s0;
+        const uint32_t lanes = std::min(64u, std::max(1u, cdiv(ns, I.wit_waves)));
+        BPG_LAUNCH(I, k_witness_eval, dim3(cdiv(ns, lanes)), dim3(lanes), d->wit_segs.as<uint4>() + s0, ns, d->wit_stream.as<uint32_t>(), d->coef.as<scm>(),
+                   d->wit_v.as<scm>(), d->aL.as<scm>(), d->aR.as<scm>(), d->aO.as<scm>());
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(I.st));
+    d->has_witness = true;
+}
 // ------------------------------------------------------------------------------------------------ equal-scalar merging of A_I, A_O (hip/k_merge.cuh)
 // Built once per uploaded witness, at its first prove() on the bucket-method path (the generator tables must exist; upload() may precede them).  Cost at
 // n = 993,384: a hash-table pass over the scalars, two scans over the table, one point addition per merged-away term and a batched normalisation.

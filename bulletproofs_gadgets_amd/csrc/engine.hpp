@@ -7,6 +7,7 @@
 #include "host/scalar.hpp"
 #include "host/merlin.hpp"
 #include "host/r1cs.hpp"
+#include "host/template.hpp"
 
 namespace bpg {
 
@@ -73,6 +74,17 @@ public:
     DeviceCircuit *upload(const FlatView &c);
     DeviceCircuit *upload(const FlatCircuit &c) { return upload(FlatView(c)); }
     void free_circuit(DeviceCircuit *c);
+    // Circuit template (include/bpg.h bpg_r1cs_upload_template): upload() plus the witness program, packed and scheduled (host/template.hpp), in HBM.  The
+    // witness arrays are allocated either way; a witness in `c` is uploaded as upload() does, so the first proof needs no assign().  Each parameter row's
+    // constant terms become one coefficient slot of its own.  Constants that flow into multiplications are part of the program and stay fixed.
+    // plan_template: every host-side check (instance and program: std::invalid_argument) and the schedule, packed program and parameter slots, no device work.
+    static TemplatePlan plan_template(const FlatView &c, const WitnessProgramView &p);
+    DeviceCircuit *upload_template(const FlatView &c, const TemplatePlan &plan);
+    // A fresh witness for a template: m committed values (32 bytes each, any 256-bit value: reduced mod l on the device) and the constant term of every
+    // parameter row; a_L, a_R, a_O are computed on the device (k_witness_eval, one launch per schedule level), everything cached for the previous witness
+    // (the equal-scalar merge sets) is dropped.  Returns once the witness is in place.
+    void assign(DeviceCircuit *c, const uint8_t *v, const uint8_t *param_values);
+    static void template_eval_host(const FlatView &c, const WitnessProgramView &p, const uint8_t *v, uint8_t *aL, uint8_t *aR, uint8_t *aO);   // test hook
     // Prover::prove on a resident circuit. transcript: state after Prover::new + every "V" append (updated in place).
     std::vector<uint8_t> prove(DeviceCircuit *c, Transcript &transcript, const std::vector<Scalar> &v_blinding,
                                const uint8_t rng_seed[32], uint32_t flags, ProveTimings *timings = nullptr);

@@ -1,0 +1,61 @@
+// Circuit templates: a_L, a_R, a_O of a resident circuit computed on the device from the committed values (Engine::assign).
+// The kernel INTERPRETS the packed witness program (record format: host/witness_record.hpp, written by host/template.hpp); nothing here knows a gadget.
+//   one launch per level of the schedule, one lane per segment of that level; the lane walks its multipliers in order:
+//   left = sum of its terms, right likewise (or the same value when the record says the two lists are one), output = left * right.
+// Everything a lane reads was written by an EARLIER launch (lower level) or by the lane itself: there is no flag, no spin and no wait on another lane.
+// Values are Montgomery form, canonical - what upload() leaves in aL / aR / aO (k_sc_from_bytes) - so a proof cannot tell which of the two filled them.
+// A lane is a latency chain (a MiMC block: 972 dependent products); the last multiplier's three values stay in registers because the programs the
+// gadgets record read them back at once (a MiMC round reads the previous output, then the square's left value).
+#pragma once
+#include "sc.cuh"
+#include "../host/witness_record.hpp"
+
+namespace bpg {
+
+struct WitPrev { scm l, r, o; uint32_t idx; };
+
+// sum of `count` terms at t[0 .. 2 count): (packed variable, class << 30 | coefficient index)
+BPG_HD scm witness_eval_lc(const uint32_t *t, uint32_t count, const WitPrev &prev, const scm *coef, const scm *v, const scm *aL, const scm *aR, const scm *aO) {
+    scm acc = sc_zero();
+    for (uint32_t k = 0; k < count; k++) {
+        const uint32_t var = t[2 * k], cw = t[2 * k + 1];
+        const uint32_t kind = var >> 29, idx = var & 0x1fffffffu, cls = cw >> WIT_CLASS_SHIFT, ci = cw & WIT_COEF_INDEX_MASK;
+        if (kind == 4) {                                            // the constant One: the coefficient itself, no product
+            acc = sc_add(acc, cls == WIT_COEF_PLUS_ONE ? SC_R1() : cls == WIT_COEF_MINUS_ONE ? sc_neg(SC_R1()) : coef[ci]);
+            continue;
+        }
+        scm x;
+        if (kind <= 2 && idx == prev.idx) x = kind == 0 ? prev.l : kind == 1 ? prev.r : prev.o;
+        else x = (kind == 0 ? aL : kind == 1 ? aR : kind == 2 ? aO : v)[idx];
+        if (cls == WIT_COEF_PLUS_ONE) acc = sc_add(acc, x);
+        else if (cls == WIT_COEF_MINUS_ONE) acc = sc_sub(acc, x);
+        else acc = sc_add(acc, sc_mont_mul(coef[ci], x));
+    }
+    return acc;
+}
+
+// multipliers [first, first + count) from the records at `rec`
+BPG_HD void witness_eval_segment(uint32_t first, uint32_t count, const uint32_t *rec, const scm *coef, const scm *v, scm *aL, scm *aR, scm *aO) {
+    WitPrev prev; prev.l = prev.r = prev.o = sc_zero(); prev.idx = 0xffffffffu;
+    for (uint32_t i = first; i < first + count; i++) {
+        const uint32_t nl = rec[0], w1 = rec[1], same = w1 & WIT_SAME_AS_LEFT, nr = w1 & ~WIT_SAME_AS_LEFT;
+        const scm l = witness_eval_lc(rec + 2, nl, prev, coef, v, aL, aR, aO);
+        const scm r = same ? l : witness_eval_lc(rec + 2 + 2 * nl, nr, prev, coef, v, aL, aR, aO);
+        const scm o = sc_mont_mul(l, r);
+        aL[i] = l; aR[i] = r; aO[i] = o;
+        prev.l = l; prev.r = r; prev.o = o; prev.idx = i;
+        rec += 2 + 2 * (nl + nr);
+    }
+}
+
+// segs: (first multiplier, count, first record word, -) per segment of ONE level.  Blocks are small (the engine spreads a level's few hundred lanes
+// over many waves: a lane alone in its wave reads one cache line per load, 64 lanes read 64).
+__global__ void __launch_bounds__(64) k_witness_eval(const uint4 *__restrict__ segs, uint32_t nseg, const uint32_t *__restrict__ stream,
+                                                     const scm *__restrict__ coef, const scm *__restrict__ v, scm *aL, scm *aR, scm *aO) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= nseg) return;
+    const uint4 sd = segs[s];
+    witness_eval_segment(sd.x, sd.y, stream + sd.z, coef, v, aL, aR, aO);
+}
+
+}  // namespace bpg

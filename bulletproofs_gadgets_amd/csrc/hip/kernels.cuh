@@ -20,7 +20,9 @@
 //       lockstep batch proving          (N <= 2^tt_orig_lg, k_batch.cuh) one launch per stage for every proof of a wave: the upload kernels on one block-diagonal
 //                                       matrix, k_bt_commit3(_finish), k_bt_compress, k_bt_exp, k_flatten, k_bt_poly_t, k_pedersen, k_bt_poly_eval, k_bt_factors,
 //                                       then k_bt_advance, k_bt_round, k_bt_finish, k_bt_compress per round and k_bt_fold_scalars
-// The kernels live in k_points.cuh, k_scalars.cuh, k_ipa.cuh, k_verify.cuh, k_msm.cuh, k_merge.cuh and k_batch.cuh, included at the end of this file in that order.
+//       circuit templates               k_witness_eval (k_witness.cuh): a_L, a_R, a_O of a resident circuit from the committed values of a fresh witness, by interpreting the
+//                                       recorded witness program - one launch per level of its schedule, one lane per segment (replaces the host's assembly + upload)
+// The kernels live in k_points.cuh, k_scalars.cuh, k_ipa.cuh, k_verify.cuh, k_msm.cuh, k_merge.cuh, k_batch.cuh and k_witness.cuh, included at the end of this file in that order.
 // Data layout in HBM: scalars = 8 x u32 Montgomery form, 32 B each, AoS (lane i <-> element i: 2 x 16 B coalesced
 // loads); generator tables = affine Niels (y+x, y-x, 2dxy), 96 B per point, G at [0,N) and H at [N,2N); window tables =
 // projective Niels (y+x, y-x, z, 2dt), 128 B per entry.
@@ -62,3 +64,4 @@ __device__ __forceinline__ uint32_t msm_point_index(const MsmSegs &S, uint32_t s
 #include "k_msm.cuh"
 #include "k_merge.cuh"
 #include "k_batch.cuh"
+#include "k_witness.cuh"

@@ -125,6 +125,24 @@ struct FlatView {
           row_ptr(f.row_ptr.data()), term_var(f.term_var.data()), term_coef(f.term_coef.data()), coef(f.coef.data()) {}
 };
 
+// Witness program of a circuit whose every multiplier came from multiply(left, right) (include/bpg.h bpg_witness_program): multiplier i has
+// left = terms [lc_ptr[2i], lc_ptr[2i+1]) and right = terms [lc_ptr[2i+1], lc_ptr[2i+2]); a term is (packed variable, index into the instance's coefficient table)
+// and may name committed values, the constant One and multipliers BELOW i only.  param_rows: constraint rows whose constant term is assigned per witness.
+struct WitnessProgram {
+    std::vector<uint64_t> lc_ptr{0};
+    std::vector<uint32_t> term_var, term_coef;
+    std::vector<uint64_t> param_rows;
+};
+struct WitnessProgramView {
+    const uint64_t *lc_ptr = nullptr;
+    const uint32_t *term_var = nullptr, *term_coef = nullptr;
+    uint64_t n_params = 0;
+    const uint64_t *param_rows = nullptr;
+    WitnessProgramView() {}
+    explicit WitnessProgramView(const WitnessProgram &w)
+        : lc_ptr(w.lc_ptr.data()), term_var(w.term_var.data()), term_coef(w.term_coef.data()), n_params(w.param_rows.size()), param_rows(w.param_rows.data()) {}
+};
+
 // Shared bookkeeping of Prover and Verifier: constraint rows with a coefficient dictionary.
 class CircuitCore {
 protected:
@@ -190,6 +208,7 @@ public:
         uint32_t i = (uint32_t)aL_.size();
         MulVars mv{{Variable::MultiplierLeft, i}, {Variable::MultiplierRight, i}, {Variable::MultiplierOutput, i}};
         aL_.push_back(l); aR_.push_back(r); aO_.push_back(o);
+        made_by_.push_back(num_constraints());
         left.terms.emplace_back(mv.l, -Scalar::one());
         right.terms.emplace_back(mv.r, -Scalar::one());
         constrain(left); constrain(right);
@@ -200,6 +219,7 @@ public:
         if (pending_ < 0) {
             uint32_t i = (uint32_t)aL_.size(); pending_ = i;
             aL_.push_back(a.v); aR_.push_back(Scalar::zero()); aO_.push_back(Scalar::zero());
+            made_by_.push_back(FREE_MULTIPLIER);
             return Variable{Variable::MultiplierLeft, i};
         }
         uint32_t i = (uint32_t)pending_; pending_ = -1;
@@ -210,6 +230,7 @@ public:
         if (!some) throw R1CSException(R1CSError::MissingAssignment, "missing assignment");
         uint32_t i = (uint32_t)aL_.size();
         aL_.push_back(l); aR_.push_back(r); aO_.push_back(l * r);
+        made_by_.push_back(FREE_MULTIPLIER);
         return MulVars{{Variable::MultiplierLeft, i}, {Variable::MultiplierRight, i}, {Variable::MultiplierOutput, i}};
     }
     void constrain(const LinearCombination &lc) override { push_row(lc); }
@@ -251,6 +272,34 @@ public:
         return f;
     }
 
+    // The witness program (include/bpg.h bpg_witness_program): how each multiplier's assignment follows from earlier variables.  Recording is ALWAYS ON and costs
+    // one 8-byte push per multiplier: multiply() notes the constraint row it is about to make (its two rows ARE the program: left - a_L[i], right - a_R[i], so
+    // the linear combinations as they were before those terms are the rows without their last term); allocate() / allocate_multiplier() note a free multiplier,
+    // whose assignment is no function of linear combinations.  Nothing the prover exports today (instance, transcript, proof) reads the record.
+    // Throws std::invalid_argument when the circuit has a free multiplier or none at all.
+    WitnessProgram witness_program() const {
+        if (aL_.empty()) throw std::invalid_argument("witness program: the circuit has no multipliers");
+        WitnessProgram w;
+        w.lc_ptr.reserve(2 * aL_.size() + 1);
+        for (size_t i = 0; i < made_by_.size(); i++) {
+            if (made_by_[i] == FREE_MULTIPLIER)
+                throw std::invalid_argument("witness program: multiplier " + std::to_string(i) + " is a free multiplier (allocate / allocate_multiplier: its assignment is a hint, not a function of linear combinations)");
+            for (uint64_t r = made_by_[i]; r < made_by_[i] + 2; r++) {
+                w.term_var.insert(w.term_var.end(), term_var_.begin() + row_ptr_[r], term_var_.begin() + row_ptr_[r + 1] - 1);
+                w.term_coef.insert(w.term_coef.end(), term_coef_.begin() + row_ptr_[r], term_coef_.begin() + row_ptr_[r + 1] - 1);
+                w.lc_ptr.push_back(w.term_var.size());
+            }
+        }
+        w.param_rows = param_rows_;
+        return w;
+    }
+    // the constant term of constraint row `row` is assigned per witness (bpg_r1cs_assign); the row a constrain() call made is num_constraints() - 1 right after it
+    void mark_param_row(uint64_t row) {
+        if (row >= num_constraints()) throw std::invalid_argument("mark_param_row: no such constraint row");
+        if (std::find(param_rows_.begin(), param_rows_.end(), row) != param_rows_.end()) throw std::invalid_argument("mark_param_row: the row is marked already");
+        param_rows_.push_back(row);
+    }
+
     // Prover::prove(&bp_gens) -> R1CSProof::to_bytes(). rng_seed replaces thread_rng() (32 external bytes).
     std::vector<uint8_t> prove(uint64_t gens_capacity, const uint8_t rng_seed[32], uint32_t flags);
     // extension: start drawing prove()'s blinding scalars now (all commitments made), while the constraints are still being assembled
@@ -265,6 +314,9 @@ private:
     bool deferred_ = false; size_t flushed_ = 0;
     bool stub_commitments_ = false;
     int64_t pending_ = -1;
+    static constexpr uint64_t FREE_MULTIPLIER = ~0ull;
+    std::vector<uint64_t> made_by_;     // per multiplier: the first of the two constraint rows multiply() made for it, or FREE_MULTIPLIER
+    std::vector<uint64_t> param_rows_;
 };
 
 class Verifier : public ConstraintSystem, public CircuitCore {

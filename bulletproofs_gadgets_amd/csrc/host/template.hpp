@@ -1,0 +1,184 @@
+// Circuit templates, host side: the checks on a witness program, its schedule, and the packed form the device interprets (hip/k_witness.cuh).
+//
+// A witness program (r1cs.hpp WitnessProgram) says how a_L[i], a_R[i] follow from committed values and EARLIER multipliers; a_O[i] is their product.
+// The schedule cuts [0, n) into SEGMENTS of consecutive multipliers - one GPU lane walks a segment in order - and gives each a LEVEL such that everything
+// a segment reads from another segment lies at a lower level (committed values: level -1).  One kernel launch per level, so no lane ever waits for another.
+// Cutting rule: walk the multipliers in order; a multiplier that names a committed value, or a multiplier outside the current segment, which the segment
+// has not named before opens a new segment.  (A MiMC sponge names the block it absorbs in every round of that block and nothing else from outside: one
+// segment per absorbed block; a Merkle node absorbs two children: two segments per node, the second one level above the first.)
+#pragma once
+#include <cstdint>
+#include <stdexcept>
+#include <string>
+#include <vector>
+#include "r1cs.hpp"
+#include "witness_record.hpp"
+
+namespace bpg {
+
+// A launch per level: a circuit that is one long chain of dependent segments is no GPU job.  A 512-leaf Merkle tree has 18 levels, a 1 MB MiMC preimage
+// 32,768 (refused: assemble it on the host); 4,096 launches of a few microseconds each stay below the 0.3 s blinding chain the evaluation runs beside.
+constexpr uint32_t WITNESS_MAX_LEVELS = 4096;
+
+struct WitnessSchedule {
+    std::vector<uint32_t> seg_first;    // nseg + 1: segment s = multipliers [seg_first[s], seg_first[s + 1])
+    std::vector<uint32_t> seg_level;    // nseg
+    std::vector<uint32_t> order;        // segments sorted by level (stable); level l = order[level_ptr[l] .. level_ptr[l + 1])
+    std::vector<uint32_t> level_ptr;    // levels + 1
+    uint32_t levels() const { return (uint32_t)level_ptr.size() - 1; }
+    uint32_t segments() const { return (uint32_t)seg_level.size(); }
+};
+
+// Every check on a program against its instance (shape, index ranges, forward references, parameter rows): std::invalid_argument, no device work.
+inline void check_witness_program(const FlatView &c, const WitnessProgramView &p) {
+    if (c.n == 0) throw std::invalid_argument("template: the circuit has no multipliers");
+    if (!p.lc_ptr) throw std::invalid_argument("template: the witness program has no lc_ptr");
+    if (p.lc_ptr[0] != 0) throw std::invalid_argument("template: lc_ptr[0] must be 0");
+    for (uint64_t k = 0; k < 2 * c.n; k++) if (p.lc_ptr[k] > p.lc_ptr[k + 1]) throw std::invalid_argument("template: lc_ptr must not decrease");
+    const uint64_t nterms = p.lc_ptr[2 * c.n];
+    if (nterms && (!p.term_var || !p.term_coef)) throw std::invalid_argument("template: the witness program has no term arrays");
+    if (nterms >= (1ull << 31)) throw std::invalid_argument("template: witness program too large");
+    for (uint64_t i = 0; i < c.n; i++)
+        for (uint64_t k = p.lc_ptr[2 * i]; k < p.lc_ptr[2 * i + 2]; k++) {
+            const uint32_t kind = p.term_var[k] >> 29, idx = p.term_var[k] & 0x1fffffffu;
+            if (p.term_coef[k] >= c.ncoef) throw std::invalid_argument("template: coefficient index out of range in the witness program");
+            if (kind <= 2) { if (idx >= i) throw std::invalid_argument("template: multiplier " + std::to_string(i) + " refers to multiplier " + std::to_string(idx) + " (a multiplier may read only earlier multipliers and committed values)"); }
+            else if (kind == 3) { if (idx >= c.m) throw std::invalid_argument("template: committed index out of range in the witness program"); }
+            else if (kind != 4) throw std::invalid_argument("template: bad variable kind in the witness program");
+        }
+    if (p.n_params && !p.param_rows) throw std::invalid_argument("template: n_params without param_rows");
+    for (uint64_t k = 0; k < p.n_params; k++) {
+        if (p.param_rows[k] >= c.q) throw std::invalid_argument("template: parameter row out of range");
+        for (uint64_t j = 0; j < k; j++) if (p.param_rows[j] == p.param_rows[k]) throw std::invalid_argument("template: parameter row named twice");
+    }
+}
+
+// (a checked program) -> schedule; refuses more than WITNESS_MAX_LEVELS levels
+inline WitnessSchedule build_witness_schedule(uint64_t n, uint64_t m, const WitnessProgramView &p) {
+    WitnessSchedule S;
+    const uint32_t NONE = UINT32_MAX;
+    std::vector<uint32_t> seg_of(n), seen_mul(n, NONE), seen_v(m, NONE);    // seen_*: the last segment that named this value from outside
+    uint32_t seg = NONE, first = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        bool cut = (seg == NONE);
+        for (uint64_t k = p.lc_ptr[2 * i]; k < p.lc_ptr[2 * i + 2] && !cut; k++) {
+            const uint32_t kind = p.term_var[k] >> 29, idx = p.term_var[k] & 0x1fffffffu;
+            if (kind == 3) cut = seen_v[idx] != seg;
+            else if (kind <= 2 && idx < first) cut = seen_mul[idx] != seg;
+        }
+        if (cut) { seg = (uint32_t)S.seg_first.size(); first = (uint32_t)i; S.seg_first.push_back(first); S.seg_level.push_back(0); }
+        seg_of[i] = seg;
+        for (uint64_t k = p.lc_ptr[2 * i]; k < p.lc_ptr[2 * i + 2]; k++) {
+            const uint32_t kind = p.term_var[k] >> 29, idx = p.term_var[k] & 0x1fffffffu;
+            if (kind == 3) seen_v[idx] = seg;
+            else if (kind <= 2 && idx < first) { seen_mul[idx] = seg; S.seg_level[seg] = std::max(S.seg_level[seg], S.seg_level[seg_of[idx]] + 1); }
+        }
+    }
+    S.seg_first.push_back((uint32_t)n);
+    uint32_t levels = 0;
+    for (uint32_t l : S.seg_level) levels = std::max(levels, l + 1);
+    if (levels > WITNESS_MAX_LEVELS)
+        throw std::invalid_argument("template: the witness program is a chain of " + std::to_string(levels) + " dependent levels (at most " + std::to_string(WITNESS_MAX_LEVELS) + ": one launch per level)");
+    S.level_ptr.assign(levels + 1, 0);
+    for (uint32_t l : S.seg_level) S.level_ptr[l + 1]++;
+    for (uint32_t l = 0; l < levels; l++) S.level_ptr[l + 1] += S.level_ptr[l];
+    S.order.resize(S.seg_level.size());
+    std::vector<uint32_t> at(S.level_ptr.begin(), S.level_ptr.end() - 1);
+    for (uint32_t s = 0; s < S.seg_level.size(); s++) S.order[at[S.seg_level[s]]++] = s;
+    return S;
+}
+
+inline std::string witness_schedule_json(const WitnessSchedule &S) {
+    std::string j = "{\"levels\": " + std::to_string(S.levels()) + ", \"segments\": " + std::to_string(S.segments()) + ", \"max_levels\": " + std::to_string(WITNESS_MAX_LEVELS) + ", \"seg_first\": [";
+    for (size_t i = 0; i < S.seg_first.size(); i++) { if (i) j += ","; j += std::to_string(S.seg_first[i]); }
+    j += "], \"seg_level\": [";
+    for (size_t i = 0; i < S.seg_level.size(); i++) { if (i) j += ","; j += std::to_string(S.seg_level[i]); }
+    j += "], \"level_segments\": [";
+    for (uint32_t l = 0; l < S.levels(); l++) { if (l) j += ","; j += std::to_string(S.level_ptr[l + 1] - S.level_ptr[l]); }
+    return j + "]}";
+}
+
+// The packed program the device walks: record format in witness_record.hpp.
+struct WitnessSegment { uint32_t first, count, stream, pad; };     // multipliers [first, first + count), records from word `stream`
+
+struct PackedWitnessProgram {
+    std::vector<uint32_t> stream;
+    std::vector<WitnessSegment> segs;       // in WitnessSchedule::order
+};
+inline PackedWitnessProgram pack_witness_program(const FlatView &c, const WitnessProgramView &p, const WitnessSchedule &S) {
+    static const uint8_t MINUS_ONE[32] = {0xec, 0xd3, 0xf5, 0x5c, 0x1a, 0x63, 0x12, 0x58, 0xd6, 0x9c, 0xf7, 0xa2, 0xde, 0xf9, 0xde, 0x14,
+                                          0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0x10};
+    std::vector<uint8_t> cls(c.ncoef);      // 0 general, 1 plus one, 2 minus one, 3 zero
+    for (uint64_t k = 0; k < c.ncoef; k++) {
+        const Scalar s = Scalar::from_bytes_mod_order(c.coef + 32 * k);
+        uint8_t b[32]; s.to_bytes(b);
+        bool zero = true, one = b[0] == 1, minus = true;
+        for (int i = 0; i < 32; i++) { zero = zero && b[i] == 0; one = one && (i == 0 || b[i] == 0); minus = minus && b[i] == MINUS_ONE[i]; }
+        cls[k] = zero ? 3 : one ? WIT_COEF_PLUS_ONE : minus ? WIT_COEF_MINUS_ONE : WIT_COEF_GENERAL;
+    }
+    PackedWitnessProgram P;
+    std::vector<uint64_t> rec_at(c.n);
+    P.stream.reserve(2 * c.n + 2 * p.lc_ptr[2 * c.n]);
+    auto emit = [&](uint64_t a, uint64_t b) {
+        uint32_t cnt = 0;
+        for (uint64_t k = a; k < b; k++) {
+            const uint32_t cl = cls[p.term_coef[k]];
+            if (cl == 3) continue;
+            P.stream.push_back(p.term_var[k]); P.stream.push_back(cl << WIT_CLASS_SHIFT | p.term_coef[k]); cnt++;
+        }
+        return cnt;
+    };
+    for (uint64_t i = 0; i < c.n; i++) {
+        const uint64_t l0 = p.lc_ptr[2 * i], l1 = p.lc_ptr[2 * i + 1], r1 = p.lc_ptr[2 * i + 2];
+        bool same = (l1 - l0 == r1 - l1);
+        for (uint64_t k = 0; same && k < l1 - l0; k++) same = p.term_var[l0 + k] == p.term_var[l1 + k] && p.term_coef[l0 + k] == p.term_coef[l1 + k];
+        rec_at[i] = P.stream.size();
+        P.stream.push_back(0); P.stream.push_back(0);
+        const uint64_t h = rec_at[i];
+        const uint32_t nl = emit(l0, l1);
+        const uint32_t nr = same ? 0u : emit(l1, r1);
+        P.stream[h] = nl; P.stream[h + 1] = same ? WIT_SAME_AS_LEFT : nr;
+    }
+    if (c.ncoef > WIT_COEF_INDEX_MASK || P.stream.size() >= (1ull << 32)) throw std::invalid_argument("template: witness program too large");
+    P.segs.resize(S.segments());
+    for (uint32_t k = 0; k < S.segments(); k++) {
+        const uint32_t s = S.order[k];
+        P.segs[k] = WitnessSegment{S.seg_first[s], S.seg_first[s + 1] - S.seg_first[s], (uint32_t)rec_at[S.seg_first[s]], 0};
+    }
+    return P;
+}
+
+// Parameter rows (bpg_witness_program.param_rows): row r's constant terms become ONE term on a coefficient slot of its own, ncoef + k for parameter k, which
+// starts at the sum of the constants it replaces (zero when the row had none) and is overwritten by every assign().  The other terms keep their order.
+inline FlatCircuit with_parameter_slots(const FlatView &c, const WitnessProgramView &p) {
+    FlatCircuit f; f.n = c.n; f.m = c.m;
+    std::vector<int64_t> param_of(c.q, -1);
+    for (uint64_t k = 0; k < p.n_params; k++) param_of[p.param_rows[k]] = (int64_t)k;
+    f.coef.assign(c.coef, c.coef + 32 * c.ncoef);
+    f.coef.resize(32 * (c.ncoef + p.n_params));
+    f.term_var.reserve(c.nnz + p.n_params); f.term_coef.reserve(c.nnz + p.n_params);
+    f.row_ptr.reserve(c.q + 1);
+    for (uint64_t r = 0; r < c.q; r++) {
+        Scalar sum;
+        for (uint64_t k = c.row_ptr[r]; k < c.row_ptr[r + 1]; k++) {
+            if (param_of[r] >= 0 && (c.term_var[k] >> 29) == Variable::One) { sum += Scalar::from_bytes_mod_order(c.coef + 32 * c.term_coef[k]); continue; }
+            f.term_var.push_back(c.term_var[k]); f.term_coef.push_back(c.term_coef[k]);
+        }
+        if (param_of[r] >= 0) {
+            f.term_var.push_back(Variable::one().packed()); f.term_coef.push_back((uint32_t)(c.ncoef + param_of[r]));
+            (sum.is_canonical() ? sum : sum.reduced()).to_bytes(&f.coef[32 * (c.ncoef + param_of[r])]);
+        }
+        f.row_ptr.push_back(f.term_var.size());
+    }
+    return f;
+}
+
+// Everything upload_template needs from the host, made in ONE pass over the program (checks first): Engine::plan_template
+struct TemplatePlan {
+    WitnessSchedule schedule;
+    PackedWitnessProgram packed;
+    FlatCircuit slotted;            // the instance's rows with parameter slots (no witness)
+    uint64_t n_params = 0, param_first = 0;
+};
+
+}  // namespace bpg

@@ -17,6 +17,8 @@
  * scatter and gather) and, in the table-driven paths, through digit-indexed table reads with zero digits skipped; the host's Horner
  * recombination and the scalar arithmetic of host/scalar.hpp are variable-time as well.  Memory access pattern and running time therefore depend
  * on secret data.  The proof bytes are the same; the posture is that of a prover on a machine its operator trusts.
+ * The witness evaluation of a circuit template (bpg_r1cs_assign) is variable-time in the same sense: it skips products by coefficients +1 / -1 and reduces
+ * with data-dependent selects.
  */
 #ifndef BPG_H
 #define BPG_H
@@ -78,8 +80,10 @@ typedef struct {
 
 /* ---------------------------------------------------------------------------------------------------- PART 1: hot path */
 /* ABI version of this header.  Rules: structs the CALLER allocates either carry a struct_size (bpg_config: fields are only ever added at the end and
- * read when struct_size covers them) or are frozen (bpg_timings, bpg_r1cs_instance, bpg_batch_item, bpg_term, bpg_lc); a field never changes type or
- * meaning; BPG_ABI_VERSION grows with every addition.  A host checks bpg_abi_version() >= the BPG_ABI_VERSION it was compiled against. */
+ * read when struct_size covers them) or are frozen (bpg_timings, bpg_r1cs_instance, bpg_batch_item, bpg_witness_program, bpg_term, bpg_lc); a field never changes type or
+ * meaning.  BPG_ABI_VERSION grows when something a version-7 host relies on is extended (a new field, a new flag value); functions ADDED since
+ * version 7 (bpg_r1cs_prove_batch, the circuit-template calls) did not raise it: a host that needs one looks the symbol up (dlsym) and treats its
+ * absence as "not supported".  A host checks bpg_abi_version() >= the BPG_ABI_VERSION it was compiled against. */
 #define BPG_ABI_VERSION 7u
 uint32_t bpg_abi_version(void);
 const char *bpg_strerror(bpg_status s);
@@ -203,6 +207,52 @@ bpg_status bpg_pool_prove(bpg_pool *pool, uint64_t count, const bpg_batch_item *
  * succeeded, else the status of the first failing item; bpg_last_error names it.  (An addition to ABI version 7.) */
 bpg_status bpg_r1cs_prove_batch(bpg_ctx *ctx, uint64_t count, const bpg_batch_item *items, bpg_status *status_out);
 
+/* Circuit templates: assemble once, assign fresh witnesses on the device.  (Additions to ABI version 7, like bpg_r1cs_prove_batch: a host that needs them
+ * looks the symbols up.)
+ * The shape of a circuit - constraints and wiring - does not depend on the witness.  When every multiplier came from multiply(left, right), its three
+ * values are functions of committed values and earlier multipliers, and the device can compute a_L, a_R, a_O itself: a further proof of the same shape
+ * needs the m committed values (and the public constants that changed), not a host assembly and a 96 MB upload.
+ *
+ * The frozen struct bpg_witness_program says how: multiplier i has left = terms [lc_ptr[2i], lc_ptr[2i+1]) and right = [lc_ptr[2i+1], lc_ptr[2i+2]) - the linear
+ * combinations handed to multiply(), WITHOUT the -a_L[i] / -a_R[i] terms the constraint rows carry.  A term may name committed values, the constant One
+ * and multipliers below i.  param_rows names constraint rows whose CONSTANT TERM changes with the witness (the root in `hash - root = 0`, the image of a
+ * preimage proof, the right-hand side of an equality): each such row's constant terms are replaced by one term on a coefficient slot of its own, which
+ * starts at their sum (zero for a row without one) and is overwritten by every bpg_r1cs_assign.  Constants that flow INTO MULTIPLICATIONS (instance
+ * leaves of a Merkle pattern, MiMC keys, round constants) are part of the program and stay fixed for the life of the template.
+ *
+ * bpg_r1cs_upload_template = bpg_r1cs_upload plus the program: the witness of `inst`, if it carries one, is uploaded as usual (the first proof needs no
+ * assign); with aL = aR = aO = NULL the circuit has no witness until the first bpg_r1cs_assign (proving it before: BPG_ERR_MISSING_ASSIGNMENT).
+ * Refused with BPG_ERR_INVALID_ARGUMENT, before any device work, bpg_last_error naming the reason: NULL arguments, n = 0, a malformed instance or program,
+ * a term index out of range or naming a multiplier >= i, a parameter row >= q or named twice, and a program whose schedule has more than 4096 levels
+ * (the device runs one launch per level of dependent segments; a circuit that is one long dependent chain is assembled on the host).  A circuit with
+ * FREE multipliers (allocate / allocate_multiplier: BoundsCheck, LessThan, Inequality, SetMembership) has no program: bpg_prover_witness_program refuses it.
+ *
+ * bpg_r1cs_assign: m committed values (32 bytes each; any value below 2^255 as Scalar::from_bits admits, reduced mod l on the device) and n_params
+ * constant terms in the order of param_rows (for `hash - root = 0` the constant term is -root mod l).  m and n_params must match the template, v and
+ * param_values must be non-NULL when their count is not zero, the circuit must be a template: else BPG_ERR_INVALID_ARGUMENT, nothing launched.  On
+ * return the witness is resident - exactly the scalars a host assembly of the same values uploads - and everything kept for the previous witness (the
+ * equal-scalar sets of BPG_MERGE) is dropped.  The circuit is then proved with bpg_r1cs_prove_resident; the caller makes the commitments
+ * (bpg_pedersen_commit) and the transcript state itself, as for any resident proof.  bpg_r1cs_verify_resident on a template checks against the constant
+ * terms of the last assign. */
+typedef struct {
+    const uint64_t *lc_ptr;      /* 2n + 1 */
+    const uint32_t *term_var;    /* kind << 29 | index, as in bpg_r1cs_instance */
+    const uint32_t *term_coef;   /* index into the instance's coef table */
+    uint64_t n_params;
+    const uint64_t *param_rows;  /* n_params constraint rows whose constant term is assigned per witness */
+} bpg_witness_program;
+bpg_status bpg_r1cs_upload_template(bpg_ctx *ctx, const bpg_r1cs_instance *inst, const bpg_witness_program *program, bpg_circuit **out);
+bpg_status bpg_r1cs_assign(bpg_ctx *ctx, bpg_circuit *c, uint64_t m, const uint8_t *v, uint64_t n_params, const uint8_t *param_values);
+/* TEST HOOKS, no device needed.  bpg_test_template_schedule: the checks of bpg_r1cs_upload_template and the schedule as JSON {"levels", "segments",
+ * "max_levels", "seg_first": [segments + 1], "seg_level": [...], "level_segments": [...]}: segment s is multipliers [seg_first[s], seg_first[s+1]), one
+ * device lane walks it in order, and everything it reads from another segment lies at a lower level.  bpg_test_template_eval: the device's interpreter
+ * compiled for the host over the same packed program (a_L, a_R, a_O out, n x 32 bytes each).  bpg_test_circuit_handle: a handle WITHOUT device state for
+ * the argument checks of bpg_r1cs_assign (program NULL: a plain circuit); every call that needs the device refuses it, bpg_r1cs_free(NULL, c) frees it.
+ * Any function added later that takes a bpg_circuit must refuse such a handle (its device state is NULL) before it touches the device. */
+bpg_status bpg_test_template_schedule(const bpg_r1cs_instance *inst, const bpg_witness_program *program, char *out, uint64_t cap);
+bpg_status bpg_test_template_eval(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const uint8_t *v, uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out);
+bpg_status bpg_test_circuit_handle(const bpg_r1cs_instance *inst, const bpg_witness_program *program, bpg_circuit **out);
+
 /* measurement hooks (bench.py): HIP events on the engine's own stream. mode 0 off, 1 = dominant kernel only, 2 = all kernels;
  * report = JSON text {kernel: {count, total_ms, alg_bytes, device_bytes, field_mults}} accumulated since the last set. */
 bpg_status bpg_profile_set(bpg_ctx *ctx, int32_t mode);
@@ -288,6 +338,13 @@ bpg_status bpg_prover_allocate(bpg_prover *p, int32_t has_assignment, const uint
 bpg_status bpg_prover_constrain(bpg_prover *p, const bpg_lc *lc);
 /* borrowed view of the assembled instance (valid until the prover is next mutated or freed) */
 bpg_status bpg_prover_instance(bpg_prover *p, bpg_r1cs_instance *out, const uint8_t **v_out, const uint8_t **v_blinding_out);
+/* Circuit templates (PART 1, bpg_r1cs_upload_template) for hosts of this mirror.  The prover records, for every multiplier, how it was made - always, at
+ * the cost of eight bytes per multiplier; nothing else it exports changes.  bpg_prover_witness_program: borrowed view of the program (valid until the
+ * prover is next mutated or freed; term_coef indexes the coefficient table of bpg_prover_instance); BPG_ERR_INVALID_ARGUMENT when the circuit has a free
+ * multiplier (allocate / allocate_multiplier) or no multiplier at all.  bpg_prover_mark_param_row: the constant term of constraint `row` is assigned per
+ * witness; the row a bpg_prover_constrain call made is bpg_prover_num_constraints(p) - 1 right after it (a gadget's closing constraint likewise). */
+bpg_status bpg_prover_witness_program(bpg_prover *p, bpg_witness_program *out);
+bpg_status bpg_prover_mark_param_row(bpg_prover *p, uint64_t row);
 /* Extension (no upstream counterpart; the proof bytes do not change): start drawing the blinding scalars of the coming prove() now.
  * Upstream's Prover::prove builds its TranscriptRng from the transcript after the last commitment (+ the "m" suffix), the commitment
  * blindings and thread_rng() - not from the constraints - and then draws 2n + 3 scalars serially (0.30 s of a 0.34 s proof at n = 2^20).
