@@ -317,6 +317,15 @@ class Context:
         _chk(lib().bpg_test_fe_ops(self._h, C.c_int32(op), C.c_uint64(n), b"".join(a_list), b"".join(b_list), out))
         return [out.raw[32 * i:32 * i + 32] for i in range(n)]
 
+    def test_decompress(self, encodings):
+        """bpg_test_decompress: k_decompress on a list of 32-byte encodings -> (ok flags, [(x, y)] as integers - the affine coordinates the kernel
+        wrote for every entry, meaningful where the flag is 1)."""
+        n = len(encodings)
+        ok, xy = (C.c_uint32 * max(n, 1))(), _buf(64 * n)
+        _chk(lib().bpg_test_decompress(self._h, C.c_uint64(n), b"".join(_exact("encoding", e, 32) for e in encodings), ok, xy))
+        return [int(ok[i]) for i in range(n)], [(int.from_bytes(xy.raw[64 * i:64 * i + 32], "little"), int.from_bytes(xy.raw[64 * i + 32:64 * i + 64], "little"))
+                                                for i in range(n)]
+
     def profile_set(self, mode):
         _chk(lib().bpg_profile_set(self._h, C.c_int32(mode)))
 
@@ -422,6 +431,16 @@ def _verify_flat(ctx, inst, transcript_state, commitments, proof, seed=None, fla
     cs = inst.cstruct()
     cs.aL = cs.aR = cs.aO = None
     return lib().bpg_r1cs_verify(ctx._h, C.byref(cs), ts, C.c_uint64(inst.m), commitments, proof, C.c_uint64(len(proof)), seed, C.c_uint32(flags))
+
+
+def test_verify_replay(n, m, gens_capacity, transcript_state, proof, seed, flags=0):
+    """bpg_test_verify_replay (no device): the host half of bpg_r1cs_verify - R1CSProof::from_bytes and the Fiat-Shamir replay - alone ->
+    (status, decided): decided = False means the proof got past it and the device decides."""
+    status, decided = C.c_int32(-1), C.c_int32(-1)
+    proof = bytes(proof)
+    _chk(lib().bpg_test_verify_replay(C.c_uint64(n), C.c_uint64(m), C.c_uint64(gens_capacity), _exact("transcript_state", transcript_state, 203), proof,
+                                      C.c_uint64(len(proof)), _exact("seed", seed, 32), C.c_uint32(flags), C.byref(status), C.byref(decided)))
+    return status.value, bool(decided.value)
 
 
 class VerifyItem(C.Structure):

@@ -229,6 +229,25 @@ bpg_status bpg_test_msm(bpg_ctx *ctx, uint32_t nmsm, uint32_t nseg, const bpg_ms
     });
 }
 
+bpg_status bpg_test_decompress(bpg_ctx *ctx, uint64_t n, const uint8_t *in, uint32_t *ok_out, uint8_t *xy_out) {
+    return guard([&] {
+        if (!ctx) throw DeviceError("test_decompress: no device context (k_decompress runs on the GPU only)");
+        REQUIRE(n == 0 || (in && ok_out && xy_out));
+        if (n > (1ull << 24)) throw std::invalid_argument("test_decompress: at most 2^24 encodings");
+        ctx->engine->test_decompress(n, in, ok_out, xy_out);
+    });
+}
+bpg_status bpg_test_verify_replay(uint64_t n, uint64_t m, uint64_t gens_capacity, const uint8_t ts[BPG_TRANSCRIPT_STATE_BYTES], const uint8_t *proof,
+                                  uint64_t proof_len, const uint8_t seed[32], uint32_t flags, bpg_status *status_out, int32_t *decided_out) {
+    return guard([&] {
+        REQUIRE(ts && seed && status_out && decided_out && (proof_len == 0 || proof));
+        if (n > (1ull << 32)) throw std::invalid_argument("test_verify_replay: n above 2^32");
+        Transcript T = Transcript::from_state(ts);
+        static const uint8_t none = 0;
+        const R1CSError e = Engine::test_verify_replay(n, m, gens_capacity, T, proof ? proof : &none, proof_len, seed, flags);
+        *status_out = (bpg_status)e; *decided_out = e != R1CSError::None;
+    });
+}
 bpg_status bpg_profile_set(bpg_ctx *ctx, int32_t mode) { return guard([&] { REQUIRE(ctx && mode >= 0 && mode <= 2); ctx->engine->profile_set(mode); }); }
 bpg_status bpg_profile_report(bpg_ctx *ctx, char *out, uint64_t cap) {
     return guard([&] { REQUIRE(ctx && out && cap); std::string r = ctx->engine->profile_report(); if (r.size() + 1 > cap) throw std::invalid_argument("profile_report: buffer too small"); std::memcpy(out, r.c_str(), r.size() + 1); });

@@ -755,6 +755,26 @@ void Engine::test_fe_ops(int op, size_t n, const uint8_t *a, const uint8_t *b, u
     HIPCHK(hipStreamSynchronize(I.st));
 }
 
+// bpg_test_decompress: k_decompress as verify() launches it; the affine x, y of every entry recovered on the host from the halved Niels form
+void Engine::test_decompress(size_t n, const uint8_t *in, uint32_t *ok_out, uint8_t *xy_out) {
+    if (!n) return;
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    I.vfy_in.ensure(n * 32); I.vfy_pts.ensure(n * sizeof(ge_niels)); I.vfy_ok.ensure(n * 4);
+    HIPCHK(hipMemcpyAsync(I.vfy_in.p, in, n * 32, hipMemcpyHostToDevice, I.st));
+    BPG_LAUNCH(I, k_decompress, dim3(cdiv(n, 64)), dim3(64), I.vfy_in.as<uint8_t>(), I.vfy_pts.as<ge_niels>(), I.vfy_ok.as<uint32_t>(), (uint32_t)n);
+    HIPCHK(hipGetLastError());
+    std::vector<ge_niels> pts(n);
+    HIPCHK(hipMemcpyAsync(pts.data(), I.vfy_pts.p, n * sizeof(ge_niels), hipMemcpyDeviceToHost, I.st));
+    HIPCHK(hipMemcpyAsync(ok_out, I.vfy_ok.p, n * 4, hipMemcpyDeviceToHost, I.st));
+    HIPCHK(hipStreamSynchronize(I.st));
+    for (size_t i = 0; i < n; i++) {
+        const h51::fe51 ypx = h51::fe_from_words(pts[i].ypx.v), ymx = h51::fe_from_words(pts[i].ymx.v);
+        h51::fe_tobytes(xy_out + 64 * i, h51::fe_sub(ypx, ymx));
+        h51::fe_tobytes(xy_out + 64 * i + 32, h51::fe_add(ypx, ymx));
+    }
+}
+
 void Engine::synchronize() { HIPCHK(hipSetDevice(device_)); HIPCHK(hipStreamSynchronize(impl_->st)); }
 
 // ------------------------------------------------------------------------------------------------ generators
@@ -2571,6 +2591,13 @@ VerifyVecs verify_prep(Engine::Impl &I, const DeviceCircuit *c, const VerifyRepl
     return VerifyVecs{wL, wR, wO, wV, ypow_p};
 }
 }  // namespace
+
+// bpg_test_verify_replay: what verify() and verify_batch() decide on the host, without a device
+R1CSError Engine::test_verify_replay(uint64_t n, uint64_t m, uint64_t gens_cap, Transcript &T, const uint8_t *proof, size_t proof_len, const uint8_t seed[32],
+                                     uint32_t flags) {
+    VerifyReplay R;
+    return verify_replay(n, m, gens_cap, T, proof, proof_len, seed, flags, R);
+}
 
 R1CSError Engine::verify(DeviceCircuit *c, Transcript &T, const uint8_t *V, const uint8_t *proof, size_t proof_len, const uint8_t seed[32], uint32_t flags) {
     HIPCHK(hipSetDevice(device_));

@@ -103,6 +103,11 @@ public:
     bool last_shared_variants() const;   // did the last prove()/verify() on this context take the shared-device kernel variants
     int chain_cpu() const;      // host core the chain worker last drew a stream on (-1: none yet); diagnostics for bench.py
     void test_fe_ops(int op, size_t n, const uint8_t *a, const uint8_t *b, uint8_t *out);   // unit-test hook (k_test_fe)
+    // unit-test hook (bpg_test_decompress): k_decompress on n encodings; ok flags and canonical affine x || y (from the halved Niels form) of every entry
+    void test_decompress(size_t n, const uint8_t *in, uint32_t *ok_out, uint8_t *xy_out);
+    // unit-test hook (bpg_test_verify_replay): R1CSProof::from_bytes and the Fiat-Shamir replay alone - None means "left to the device"; no device work
+    static R1CSError test_verify_replay(uint64_t n, uint64_t m, uint64_t gens_cap, Transcript &T, const uint8_t *proof, size_t proof_len,
+                                        const uint8_t seed[32], uint32_t flags);
     // Verifier::verify on a resident (assignment-free) circuit. transcript: state after Verifier::new + every "V" append.
     R1CSError verify(DeviceCircuit *c, Transcript &transcript, const uint8_t *V, const uint8_t *proof, size_t proof_len,
                      const uint8_t seed[32], uint32_t flags);

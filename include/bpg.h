@@ -291,6 +291,19 @@ typedef struct {
 bpg_status bpg_test_msm(bpg_ctx *ctx, uint32_t nmsm, uint32_t nseg, const bpg_msm_seg *segs, const uint8_t *scalars, uint8_t *out,
                         char *evidence, uint64_t cap);
 
+/* test hook: k_decompress, the verifier's RFC 9496 decoder, on n encodings of 32 bytes, launched as bpg_r1cs_verify launches it.  ok_out[i] = 1 when
+ * encoding i is accepted; xy_out holds, for EVERY entry, the affine x || y (32 + 32 bytes, canonical) the kernel wrote, recovered on the host from
+ * its halved Niels form (x = ypx - ymx, y = ypx + ymx) - meaningful where ok_out[i] = 1.  Arguments are checked before any launch
+ * (BPG_ERR_INVALID_ARGUMENT: a NULL pointer with n > 0, n above 2^24); a NULL ctx is BPG_ERR_DEVICE; n = 0 returns BPG_OK.  (An addition to ABI version 7.) */
+bpg_status bpg_test_decompress(bpg_ctx *ctx, uint64_t n, const uint8_t *in, uint32_t *ok_out, uint8_t *xy_out);
+/* test hook, no device needed: the host half of bpg_r1cs_verify alone - R1CSProof::from_bytes and the Fiat-Shamir replay - for a circuit of n multipliers
+ * and m commitments on a context of gens_capacity generators.  *decided_out = 1 and *status_out = BPG_ERR_FORMAT, BPG_ERR_INVALID_GENERATORS_LENGTH or
+ * BPG_ERR_VERIFICATION when the replay refuses the proof itself (length, lead byte, non-canonical scalar, capacity, an identity encoding where upstream
+ * validates one); *decided_out = 0 and *status_out = BPG_OK when the decision is left to the device (decompression and the one MSM).  transcript_state is
+ * not written.  (An addition to ABI version 7.) */
+bpg_status bpg_test_verify_replay(uint64_t n, uint64_t m, uint64_t gens_capacity, const uint8_t transcript_state[BPG_TRANSCRIPT_STATE_BYTES],
+                                  const uint8_t *proof, uint64_t proof_len, const uint8_t seed[32], uint32_t flags, bpg_status *status_out, int32_t *decided_out);
+
 /* ---------------------------------------------------------------------------------------------------- PART 2: host mirror
  * merlin::Transcript, bulletproofs::r1cs::{Prover, Verifier}, and the reference's Gadget trait with BoundsCheck,
  * MimcHash256 and MerkleTree256 (reference src/gadget.rs:6-59 and the gadget modules), implemented in C++. */

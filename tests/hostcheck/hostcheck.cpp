@@ -55,6 +55,16 @@ void hc_scalarmul_uniform(uint8_t *out, const uint8_t *k32, const uint8_t *in64)
     acc = ge_madd_signed(ge_madd_signed(acc, Pn, 1), Pn, 0);
     ge_compress(out, acc);
 }
+// k_decompress for the host: the decoder and the Niels conversion of the kernel, then x = ypx - ymx, y = ypx + ymx (canonical), as bpg_test_decompress gives them
+void hc_decompress(uint32_t n, const uint8_t *in, uint32_t *ok_out, uint8_t *xy_out) {
+    for (uint32_t i = 0; i < n; i++) {
+        ge_ext p; uint32_t good = ge_decompress(p, in + 32 * (size_t)i);
+        ge_niels q = ge_to_niels(p, fe_one());
+        ok_out[i] = good;
+        fe_tobytes(xy_out + 64 * (size_t)i, fe_sub(q.ypx, q.ymx));
+        fe_tobytes(xy_out + 64 * (size_t)i + 32, fe_add(q.ypx, q.ymx));
+    }
+}
 // ---- host/fe51.hpp (the serial epilogues of the product: Horner recombination and point encoding on the host)
 // op as hc_fe_op (0 mul 1 sq 2 add 3 sub 4 neg 6 pow22523 7 freeze), inputs raw 256-bit values as the device hands them over
 void hc_fe51_op(int op, uint8_t *out, const uint8_t *a, const uint8_t *b) {
