@@ -585,6 +585,11 @@ class ProverPool:
             pass
 
 
+class _TemplateItem(C.Structure):
+    _fields_ = [("v", C.c_char_p), ("param_values", C.c_char_p), ("transcript_state", C.c_void_p), ("v_blinding", C.c_char_p),
+                ("rng_seed", C.c_char_p), ("flags", C.c_uint32), ("proof_out", C.c_void_p), ("proof_len", C.POINTER(C.c_uint64))]
+
+
 class ResidentCircuit:
     def __init__(self, ctx, h, n, m, n_params=None):
         self.ctx, self._h, self.n, self.m = ctx, h, n, m
@@ -608,6 +613,38 @@ class ResidentCircuit:
         _chk(lib().bpg_r1cs_prove_resident(self.ctx._h, self._h, ts, C.c_uint64(self.m), v_blinding, rng_seed, C.c_uint32(flags),
                                            out, C.byref(ln), C.byref(tm) if timings else None))
         return (out.raw[:ln.value], ts.raw[:203], tm.as_dict()) if timings else (out.raw[:ln.value], ts.raw[:203])
+
+    def _template_items(self, items):
+        """bpg_template_item array of [(values, params, transcript_state, v_blinding, rng_seed, flags)] and the buffers it points into:
+        (transcript state, proof buffer, proof length, values, params, v_blinding, seed) per item.  values / params of None stay NULL."""
+        arr = (_TemplateItem * max(len(items), 1))()
+        keep = []
+        for k, (values, params, state, vb, seed, flags) in enumerate(items):
+            v = None if values is None else bytes(values)
+            pv = None if params is None else (bytes(params) if isinstance(params, (bytes, bytearray)) else b"".join(_exact("params", x, 32) for x in params))
+            ts = _buf(203); ts.raw = bytes(state)
+            cap = lib().bpg_proof_size(self.n, flags)
+            out = _buf(cap); ln = C.c_uint64(cap)
+            keep.append((ts, out, ln, v, pv, vb, seed))
+            arr[k].v = v; arr[k].param_values = pv if pv else None; arr[k].transcript_state = C.cast(ts, C.c_void_p)
+            arr[k].v_blinding = vb; arr[k].rng_seed = seed; arr[k].flags = flags
+            arr[k].proof_out = C.cast(out, C.c_void_p); arr[k].proof_len = C.pointer(ln)
+        return arr, keep
+
+    def prove_batch(self, items, return_status=False):
+        """bpg_r1cs_prove_template_batch: items = [(values, params, transcript_state, v_blinding, rng_seed, flags)] - fresh witnesses of this template ->
+        [(proof, transcript state after)], each exactly what assign(values, params) + prove(...) gives for that item alone; a template of N <= 2^14
+        computes all the witnesses in shared launches.  The template holds no witness afterwards.  Raises BpgError on the first failing item;
+        return_status=True returns (results, statuses) instead, with (None, state as given) for a failed item (the conventions of Context.prove_batch)."""
+        arr, keep = self._template_items(items)
+        n = len(items)
+        status = (C.c_int32 * max(n, 1))()
+        rc = lib().bpg_r1cs_prove_template_batch(self.ctx._h, self._h, C.c_uint64(n), arr, status)
+        if not return_status:
+            _chk(rc)
+        st = [status[k] for k in range(n)]
+        res = [(k[1].raw[:k[2].value] if s == 0 else None, k[0].raw[:203]) for k, s in zip(keep, st)]
+        return (res, st) if return_status else res
 
     def verify(self, transcript_state, commitments, proof, seed=None, flags=0):
         """bpg_r1cs_verify_resident: 0 = accepted, 3 = VERIFICATION_ERROR, 2 = FORMAT_ERROR, 1 = INVALID_GENERATORS_LENGTH."""
@@ -675,7 +712,10 @@ class FlatInstance:
         # a batch holds many structs of the same instance at once)
         src = (self.aL, self.aR, self.aO, self.coef)
         if getattr(self, "_cbufs_src", None) is None or any(a is not b for a, b in zip(self._cbufs_src, src)):
-            self._cbufs = [C.create_string_buffer(x, max(len(x), 1)) for x in src]
+            # a witness-free instance (a verifier's) still hands out non-NULL a_L, a_R, a_O, which bpg_r1cs_upload reads as n scalars each: the
+            # buffers hold n zero scalars then, never fewer bytes than the struct claims (a 1-byte buffer let upload() read past the heap block)
+            need = (32 * self.n, 32 * self.n, 32 * self.n, 0)
+            self._cbufs = [C.create_string_buffer(x, max(len(x), k, 1)) for x, k in zip(src, need)]
             self._cbufs_src = src
         c.aL, c.aR, c.aO, c.coef = [C.cast(k, C.c_void_p).value for k in self._cbufs]
         c.row_ptr, c.term_var, c.term_coef = self.row_ptr.ctypes.data, self.term_var.ctypes.data, self.term_coef.ctypes.data

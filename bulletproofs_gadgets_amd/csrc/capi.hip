@@ -315,6 +315,13 @@ bpg_status bpg_test_template_eval(const bpg_r1cs_instance *inst, const bpg_witne
         Engine::template_eval_host(as_view(inst, false), program_view(program), v, aL, aR, aO);
     });
 }
+bpg_status bpg_test_template_eval_batch(const bpg_r1cs_instance *inst, const bpg_witness_program *program, uint64_t count, const uint8_t *v,
+                                        uint8_t *aL, uint8_t *aR, uint8_t *aO) {
+    return guard([&] {
+        REQUIRE(inst && program && aL && aR && aO && (inst->m == 0 || count == 0 || v));
+        Engine::template_eval_batch_host(as_view(inst, false), program_view(program), count, v, aL, aR, aO);
+    });
+}
 bpg_status bpg_test_circuit_handle(const bpg_r1cs_instance *inst, const bpg_witness_program *program, bpg_circuit **out) {
     return guard([&] {
         REQUIRE(out); *out = nullptr;
@@ -409,6 +416,68 @@ bpg_status bpg_r1cs_prove_batch(bpg_ctx *ctx, uint64_t count, const bpg_batch_it
         st[k] = bpg_r1cs_prove(ctx, it.inst, it.transcript_state, it.m, it.v_blinding, it.rng_seed, it.flags, it.proof_out, it.proof_len);
         if (st[k] != BPG_OK) msg[k] = g_last_error;
     }
+    bpg_status first = BPG_OK;
+    g_last_error.clear();
+    for (uint64_t k = 0; k < count; k++) {
+        status_out[k] = st[k];
+        if (first == BPG_OK && st[k] != BPG_OK) { first = st[k]; g_last_error = "item " + std::to_string(k) + ": " + msg[k]; }
+    }
+    return first;
+}
+
+bpg_status bpg_r1cs_prove_template_batch(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, const bpg_template_item *items, bpg_status *status_out) {
+    // the whole call is refused before anything is written or launched; a handle without device state first, whatever else was passed
+    if (tmpl && !tmpl->dc) { g_last_error = "prove_template_batch: the handle has no device state (bpg_test_circuit_handle)"; return BPG_ERR_INVALID_ARGUMENT; }
+    if (!ctx || !tmpl || (count && (!items || !status_out))) { g_last_error = "null or invalid argument: ctx, tmpl, items and status_out"; return BPG_ERR_INVALID_ARGUMENT; }
+    if (!tmpl->is_template) { g_last_error = "prove_template_batch: the circuit is not a template (bpg_r1cs_upload_template)"; return BPG_ERR_INVALID_ARGUMENT; }
+    if (!count) { g_last_error.clear(); return BPG_OK; }
+    const uint64_t m = tmpl->m, n = tmpl->n, n_params = tmpl->n_params;
+    std::vector<bpg_status> st(count, BPG_OK);
+    std::vector<std::string> msg(count);
+    std::vector<Transcript> T(count);
+    std::vector<std::vector<Scalar>> vb(count);
+    std::vector<Engine::ProveItem> lock;
+    std::vector<uint64_t> lock_at;
+    std::vector<uint8_t> route(count, 0);       // 0 failed its checks, 1 lockstep, 2 assign + prove_resident
+    const bool host_copy = Engine::template_lockstep(tmpl->dc);
+    for (uint64_t k = 0; k < count; k++) {
+        const bpg_template_item &it = items[k];
+        // the checks of bpg_r1cs_assign, then those of bpg_r1cs_prove_resident, in their order: an item fails alone, with that call's status
+        st[k] = guard([&] {
+            REQUIRE((m == 0 || it.v) && (n_params == 0 || it.param_values));
+            REQUIRE(it.transcript_state && it.rng_seed && it.proof_out && it.proof_len && (m == 0 || it.v_blinding));
+            if (*it.proof_len < bpg_proof_size(n, it.flags)) throw std::invalid_argument("prove: proof buffer too small");
+            uint64_t N = 1; while (N < n) N <<= 1;
+            if (ctx->engine->gens_capacity() < N) throw R1CSException(R1CSError::InvalidGeneratorsLength, "generator capacity below padded circuit size (call bpg_gens_ensure)");
+        });
+        if (st[k] != BPG_OK) { msg[k] = g_last_error; continue; }
+        if (!host_copy || !ctx->engine->lockstep_eligible(n, it.flags)) { route[k] = 2; continue; }
+        route[k] = 1;
+        T[k] = Transcript::from_state(it.transcript_state);
+        vb[k].resize(m);
+        for (uint64_t i = 0; i < m; i++) vb[k][i] = Scalar::from_bytes_mod_order(it.v_blinding + 32 * i);
+        Engine::ProveItem p; p.T = &T[k]; p.vb = &vb[k]; p.seed = it.rng_seed; p.flags = it.flags; p.values = it.v; p.params = it.param_values;
+        lock.push_back(std::move(p)); lock_at.push_back(k);
+    }
+    if (!lock.empty()) {
+        const bpg_status s = guard([&] { ctx->engine->prove_template_batch(tmpl->dc, lock.size(), lock.data()); });
+        const std::string why = g_last_error;
+        for (size_t j = 0; j < lock.size(); j++) {
+            const uint64_t k = lock_at[j];
+            st[k] = s;
+            if (s != BPG_OK) { msg[k] = why; continue; }
+            std::memcpy(items[k].proof_out, lock[j].proof.data(), lock[j].proof.size()); *items[k].proof_len = lock[j].proof.size();
+            T[k].export_state(items[k].transcript_state);
+        }
+    }
+    for (uint64_t k = 0; k < count; k++) {      // larger templates, BPG_TT_ORIG_LG=0 and expanded blinding: assign + the single path, one at a time, same bytes
+        if (route[k] != 2) continue;
+        const bpg_template_item &it = items[k];
+        st[k] = bpg_r1cs_assign(ctx, tmpl, m, it.v, n_params, it.param_values);
+        if (st[k] == BPG_OK) st[k] = bpg_r1cs_prove_resident(ctx, tmpl, it.transcript_state, m, it.v_blinding, it.rng_seed, it.flags, it.proof_out, it.proof_len, nullptr);
+        if (st[k] != BPG_OK) msg[k] = g_last_error;
+    }
+    Engine::drop_witness(tmpl->dc);             // on either path: a caller never depends on which one its items took
     bpg_status first = BPG_OK;
     g_last_error.clear();
     for (uint64_t k = 0; k < count; k++) {

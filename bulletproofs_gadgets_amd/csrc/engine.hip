@@ -163,6 +163,7 @@ Scalar scalar_bits(const Scalar &s, uint32_t from, uint32_t count) {
 }
 
 uint32_t ceil_log2(uint64_t x) { uint32_t l = 0; while ((1ULL << l) < x) l++; return l; }
+constexpr uint32_t TEMPLATE_HOST_COPY_LG = 14;     // templates up to this padded size keep a host copy of their rows (the widest lockstep proof: BPG_TT_ORIG_LG <= 14)
 
 // On-disk cache of the generator tables (reference src/bin/prover.rs:92 re-derives them on every run).  Opt-in:
 // BPG_GENS_CACHE_DIR names a directory; the file gens_<capacity>.bpg holds a header and the affine Niels table [G | H] exactly as it lives
@@ -210,6 +211,11 @@ struct DeviceCircuit {
     DevBuf wit_stream, wit_segs, wit_v;
     std::vector<uint32_t> wit_level_ptr;    // level l = segments [wit_level_ptr[l], wit_level_ptr[l + 1]) of wit_segs
     uint64_t n_params = 0, param_first = 0;
+    // host copy of the rows with their parameter slots (TemplatePlan::slotted), which the lockstep packer of prove_template_batch reads: kept only for
+    // padded N <= 2^14 - a larger template never takes the lockstep path, and a 2^20 one would hold hundreds of MB of host memory for nothing
+    bool has_host = false;
+    FlatCircuit host;
+    FlatView host_view;
 };
 
 // kernel ids for the optional HIP-event profile (bpg_profile_*)
@@ -219,7 +225,7 @@ struct DeviceCircuit {
     X(k_scan_apply) X(k_bucket_chunks) X(k_bucket_combine) X(k_bucket_combine_heavy) X(k_bucket_reduce) X(k_window_sums) X(k_window_sums_quad) X(k_decompress) X(k_ipa_s) X(k_verify_scalars) X(k_verify_scalars_acc) X(k_bench_fe_mul) \
     X(k_tt_bases) X(k_tt_multiples) X(k_tt_bases8) X(k_tt_multiples8) X(k_tt_round8) X(k_tt_factors) X(k_tt_advance) X(k_tt_round) X(k_tt_finish) X(k_blind_expand) X(k_tt_commit3) X(k_tt_commit3_finish) X(k_csc_count) X(k_csc_fill) X(k_csc_colptr) X(k_merge_insert) X(k_merge_plan) X(k_merge_groups) X(k_merge_members) X(k_merge_sum) \
     X(k_bt_commit3) X(k_bt_commit3_finish) X(k_bt_compress) X(k_bt_exp) X(k_bt_poly_t) X(k_bt_poly_eval) X(k_bt_factors) X(k_bt_advance) X(k_bt_round) \
-    X(k_bt_finish) X(k_bt_fold_scalars) X(k_witness_eval)
+    X(k_bt_finish) X(k_bt_fold_scalars) X(k_witness_eval) X(k_witness_eval_batch)
 enum KernelId {
 #define X(n) KID_##n,
     BPG_KERNELS(X)
@@ -1338,6 +1344,33 @@ void Engine::template_eval_host(const FlatView &c, const WitnessProgramView &p, 
     }
 }
 
+// TEST HOOK (bpg_test_template_eval_batch): k_witness_eval_batch on the host - one pass per level, per segment every item, into the wave layout
+void Engine::template_eval_batch_host(const FlatView &c, const WitnessProgramView &p, uint64_t count, const uint8_t *v, uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out) {
+    const TemplatePlan T = plan_template(c, p);
+    const PackedWitnessProgram &P = T.packed;
+    const uint64_t N = 1ull << ceil_log2(c.n);
+    if (count > (1ull << 26) / N) throw std::invalid_argument("template_eval_batch: too many items");
+    auto load = [](const uint8_t *b, size_t cnt) {
+        std::vector<scm> out(cnt ? cnt : 1);
+        for (size_t i = 0; i < cnt; i++) { uint32_t w[8]; std::memcpy(w, b + 32 * i, 32); out[i] = sc_from_words(w); }
+        return out;
+    };
+    const std::vector<scm> coef = load(c.coef, c.ncoef), vv = load(v, count * c.m);
+    std::vector<scm> aL(count * N, sc_zero()), aR(count * N, sc_zero()), aO(count * N, sc_zero());
+    const std::vector<uint32_t> &lp = T.schedule.level_ptr;
+    for (size_t l = 0; l + 1 < lp.size(); l++)
+        for (uint32_t s = lp[l]; s < lp[l + 1]; s++)
+            for (uint64_t k = 0; k < count; k++)
+                witness_eval_segment(P.segs[s].first, P.segs[s].count, P.stream.data() + P.segs[s].stream, coef.data(), vv.data() + k * c.m,
+                                     aL.data() + k * N, aR.data() + k * N, aO.data() + k * N);
+    for (size_t i = 0; i < count * N; i++) {
+        uint32_t w[8];
+        sc_to_words(w, aL[i]); std::memcpy(aL_out + 32 * i, w, 32);
+        sc_to_words(w, aR[i]); std::memcpy(aR_out + 32 * i, w, 32);
+        sc_to_words(w, aO[i]); std::memcpy(aO_out + 32 * i, w, 32);
+    }
+}
+
 DeviceCircuit *Engine::upload_template(const FlatView &c, const TemplatePlan &T) {
     const PackedWitnessProgram &P = T.packed;
     FlatView f(T.slotted); f.aL = c.aL; f.aR = c.aR; f.aO = c.aO;
@@ -1346,6 +1379,7 @@ DeviceCircuit *Engine::upload_template(const FlatView &c, const TemplatePlan &T)
         Impl &I = *impl_;
         d->is_template = true; d->n_params = T.n_params; d->param_first = T.param_first;
         d->wit_level_ptr = T.schedule.level_ptr;
+        if (ceil_log2(c.n) <= TEMPLATE_HOST_COPY_LG) { d->host = T.slotted; d->host_view = FlatView(d->host); d->has_host = true; }
         d->wit_stream.ensure(P.stream.size() * 4); d->wit_segs.ensure(P.segs.size() * sizeof(WitnessSegment)); d->wit_v.ensure((c.m ? c.m : 1) * sizeof(scm));
         I.h2d(d->wit_stream.p, P.stream.data(), P.stream.size() * 4);
         I.h2d(d->wit_segs.p, P.segs.data(), P.segs.size() * sizeof(WitnessSegment));
@@ -2184,7 +2218,24 @@ bool Engine::lockstep_eligible(uint64_t n, uint32_t flags) const {
     return n > 0 && !(flags & 4u) && lg > 0 && ceil_log2(n) <= lg;
 }
 
-void Engine::prove_batch(size_t count, ProveItem *items) {
+bool Engine::template_lockstep(const DeviceCircuit *d) { return d && d->is_template && d->has_host; }
+void Engine::drop_witness(DeviceCircuit *d) {
+    d->has_witness = false;
+    d->merge_tried = false; d->mI.groups = d->mI.skipped = 0; d->mO.groups = d->mO.skipped = 0;
+}
+void Engine::prove_template_batch(DeviceCircuit *d, size_t count, ProveItem *items) {
+    if (!template_lockstep(d)) throw std::logic_error("prove_template_batch: the circuit is not a template with a host copy of its rows");
+    drop_witness(d);
+    for (size_t k = 0; k < count; k++) {
+        if (!items[k].values && d->m) throw std::invalid_argument("prove_template_batch: an item without committed values");
+        if (!items[k].params && d->n_params) throw std::invalid_argument("prove_template_batch: an item without parameter values");
+        items[k].flat = &d->host_view;
+    }
+    prove_batch(count, items, d);
+}
+
+// tmpl != nullptr: every item is a fresh witness of that template (flat = its host copy; values, params per item)
+void Engine::prove_batch(size_t count, ProveItem *items, DeviceCircuit *tmpl) {
     if (!count) return;
     HIPCHK(hipSetDevice(device_));
     Impl &I = *impl_;
@@ -2238,7 +2289,8 @@ void Engine::prove_batch(size_t count, ProveItem *items) {
         // ---- pinned upload area (mirrored 1:1 on the device) and the read-back area
         size_t off = 0;
         auto take = [&](size_t b) { const size_t o = off; off += Impl::al256(b ? b : 1); return o; };
-        const size_t o_wit = take(3 * KN * 32), o_coef = take(ncoefT * 32), o_raw = take(2 * KN * 64), o_rp = take((qT + 1) * 8), o_tv = take(nnzT * 4),
+        // (a template wave uploads its committed values where a host-assembled wave uploads 3 K N witness scalars)
+        const size_t o_wit = take(tmpl ? mT * 32 : 3 * KN * 32), o_coef = take(ncoefT * 32), o_raw = take(2 * KN * 64), o_rp = take((qT + 1) * 8), o_tv = take(nnzT * 4),
                      o_tc = take(nnzT * 4), o_nk = take(K * 4), o_qk = take(K * 4), o_rb = take(K * 4), o_bsc = take(K * BSC * 32), o_bases = take(K * 3 * 32);
         const size_t up_bytes = off;
         const size_t o_back = take(std::max<size_t>(K * 3 * 32 + 64, (6 * K + mT + 1) * 32 + 64));
@@ -2253,7 +2305,7 @@ void Engine::prove_batch(size_t count, ProveItem *items) {
                      d_colptr = take((ncols + 1) * 8), d_erow = take(nnzT * 4), d_ecoef = take(nnzT * 4), d_counts = take((nvar + 2) * 4),
                      d_starts = take((nvar + 2) * 4), d_cursor = take((nvar + 2) * 4), d_rowc = take((qT + 2) * 4), d_rowcs = take((qT + 2) * 4),
                      d_bsum = take((std::max(nb1, nb2) + 2) * 4), d_part = take((size_t)K * std::max(3 * nblkC, 2 * nblkR) * sizeof(ge_ext)),
-                     d_pts = take(K * 3 * sizeof(ge_ext)), d_comp = take(K * 3 * 32), d_misc = take(64);
+                     d_pts = take(K * 3 * sizeof(ge_ext)), d_comp = take(K * 3 * 32), d_misc = take(64), d_v = take(tmpl ? mT * 32 : 0);
         I.bt_dev.ensure(off);
         uint8_t *dev = I.bt_dev.as<uint8_t>();
         auto D = [&](size_t o) { return dev + o; };
@@ -2279,11 +2331,15 @@ void Engine::prove_batch(size_t count, ProveItem *items) {
                 rng[k].fill_draws64(raw + 64 * b, n); std::memset(raw + 64 * (b + n), 0, 64 * (N - n));
                 rng[k].fill_draws64(raw + 64 * (KN + b), n); std::memset(raw + 64 * (KN + b + n), 0, 64 * (N - n));
                 const uint8_t *src[3] = {f.aL, f.aR, f.aO};
-                for (int v = 0; v < 3; v++) {
+                for (int v = 0; v < 3 && !tmpl; v++) {
                     uint8_t *dst = pin + o_wit + 32 * (v * KN + b);
                     std::memcpy(dst, src[v], 32 * n); std::memset(dst + 32 * n, 0, 32 * (N - n));
                 }
                 if (f.ncoef) std::memcpy(pin + o_coef + 32 * cbase[k], f.coef, 32 * f.ncoef);
+                if (tmpl) {     // the item's committed values, and its constant terms in the parameter slots of ITS range of the wave's coefficient table
+                    if (f.m) std::memcpy(pin + o_wit + 32 * vbase[k], W[k]->values, 32 * f.m);
+                    if (tmpl->n_params) std::memcpy(pin + o_coef + 32 * (cbase[k] + tmpl->param_first), W[k]->params, 32 * tmpl->n_params);
+                }
                 // the block-diagonal matrix: rows after the earlier items' rows, multiplier i of item k -> column k*N + i of its block (L, R, O),
                 // committed j -> 3KN + vbase + j; coefficient indices after the earlier items' coefficients
                 uint64_t *rp = reinterpret_cast<uint64_t *>(pin + o_rp) + rbase[k];
@@ -2304,7 +2360,20 @@ void Engine::prove_batch(size_t count, ProveItem *items) {
         // ---- one upload; witness, coefficients and draws to scalars; the block-diagonal CSR -> CSC in one pass (prove()'s upload kernels)
         HIPCHK(hipMemcpyAsync(dev, pin, up_bytes, hipMemcpyHostToDevice, I.st));
         HIPCHK(hipMemsetAsync(stale, 0, 64, I.st));
-        BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(3 * KN, 256)), dim3(256), reinterpret_cast<const uint32_t *>(D(o_wit)), aL, (uint32_t)(3 * KN));
+        if (!tmpl) BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(3 * KN, 256)), dim3(256), reinterpret_cast<const uint32_t *>(D(o_wit)), aL, (uint32_t)(3 * KN));
+        else {
+            // the wave's witnesses are computed here: committed values reduced once for the whole wave, padding rows [n, N) of the 3 K vectors zeroed (one
+            // strided fill), then one launch per level with a lane per (segment, item) - everything below cannot tell where a_L, a_R, a_O came from
+            const uint64_t n = tmpl->n, m = tmpl->m;
+            scm *vd = reinterpret_cast<scm *>(D(d_v));
+            if (mT) BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(mT, 256)), dim3(256), reinterpret_cast<const uint32_t *>(D(o_wit)), vd, (uint32_t)mT);
+            if (N > n) HIPCHK(hipMemset2DAsync(aL + n, N * sizeof(scm), 0, (N - n) * sizeof(scm), 3 * K, I.st));
+            for (size_t l = 0; l + 1 < tmpl->wit_level_ptr.size(); l++) {
+                const uint32_t s0 = tmpl->wit_level_ptr[l], ns = tmpl->wit_level_ptr[l + 1] - s0;
+                BPG_LAUNCH(I, k_witness_eval_batch, dim3(cdiv(K, 64), ns), dim3(64), tmpl->wit_segs.as<uint4>() + s0, tmpl->wit_stream.as<uint32_t>(),
+                           tmpl->coef.as<scm>(), vd, (uint32_t)m, lgN, (uint32_t)K, aL, aR, aO);
+            }
+        }
         if (ncoefT) BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(ncoefT, 256)), dim3(256), reinterpret_cast<const uint32_t *>(D(o_coef)), reinterpret_cast<scm *>(D(d_coef)), (uint32_t)ncoefT);
         BPG_LAUNCH(I, k_sc_from_wide, dim3(cdiv(2 * KN, 256)), dim3(256), reinterpret_cast<const uint32_t *>(D(o_raw)), sL, (uint32_t)(2 * KN), stale);
         {

@@ -85,6 +85,9 @@ public:
     // (the equal-scalar merge sets) is dropped.  Returns once the witness is in place.
     void assign(DeviceCircuit *c, const uint8_t *v, const uint8_t *param_values);
     static void template_eval_host(const FlatView &c, const WitnessProgramView &p, const uint8_t *v, uint8_t *aL, uint8_t *aR, uint8_t *aO);   // test hook
+    // test hook (bpg_test_template_eval_batch): the BATCHED interpreter (k_witness_eval_batch) compiled for the host - level by level, every item of a
+    // segment side by side, into the wave layout (count x N x 32 bytes per vector, item-major, N = padded size, padding rows zero); v: count x m x 32
+    static void template_eval_batch_host(const FlatView &c, const WitnessProgramView &p, uint64_t count, const uint8_t *v, uint8_t *aL, uint8_t *aR, uint8_t *aO);
     // Prover::prove on a resident circuit. transcript: state after Prover::new + every "V" append (updated in place).
     std::vector<uint8_t> prove(DeviceCircuit *c, Transcript &transcript, const std::vector<Scalar> &v_blinding,
                                const uint8_t rng_seed[32], uint32_t flags, ProveTimings *timings = nullptr);
@@ -122,15 +125,25 @@ public:
     // returns for item k alone (a rejected batch is re-verified item by item).
     void verify_batch(size_t count, const VerifyItem *items, const uint8_t batch_seed[32], R1CSError *status_out);
     // One proof of a lockstep batch (include/bpg.h bpg_r1cs_prove_batch): an instance with its witness that passed the checks of bpg_r1cs_prove and
-    // lockstep_eligible(); T is updated in place and proof filled exactly as prove() does for the item alone.
+    // lockstep_eligible(); T is updated in place and proof filled exactly as prove() does for the item alone.  An item of prove_template_batch has no
+    // instance of its own: its witness source is the template plus `values` (m x 32 committed values) and `params` (n_params x 32), and flat is left null.
     struct ProveItem {
         const FlatView *flat = nullptr; Transcript *T = nullptr; const std::vector<Scalar> *vb = nullptr; const uint8_t *seed = nullptr; uint32_t flags = 0;
+        const uint8_t *values = nullptr, *params = nullptr;
         std::vector<uint8_t> proof;
     };
     // does a proof of n multipliers with these flags take the lockstep path (0 < n, padded N <= 2^tt_orig_lg, no expanded blinding)
     bool lockstep_eligible(uint64_t n, uint32_t flags) const;
     // every item proved in lockstep: grouped by lg N, each group in waves of at most BPG_BATCH_WAVE_MB of device state, one launch per stage per wave
-    void prove_batch(size_t count, ProveItem *items);
+    void prove_batch(size_t count, ProveItem *items) { prove_batch(count, items, nullptr); }
+    // K fresh witnesses of ONE template in lockstep (include/bpg.h bpg_r1cs_prove_template_batch): prove_batch with the witness of every item computed
+    // on the device, all items of a wave in one launch per schedule level (k_witness_eval_batch), straight into the wave's a_L, a_R, a_O.  The template
+    // must be lockstep-eligible with every item's flags (template_lockstep()).  Whatever happens, the template holds no witness afterwards.
+    void prove_template_batch(DeviceCircuit *tmpl, size_t count, ProveItem *items);
+    // the template kept the host copy of its rows that the lockstep packer needs (padded N <= 2^14)
+    static bool template_lockstep(const DeviceCircuit *tmpl);
+    // what a template batch leaves behind on either path: no witness, no equal-scalar sets
+    static void drop_witness(DeviceCircuit *tmpl);
     // the host-side checks upload() makes on an instance (CSR shape, index ranges, sizes): std::invalid_argument, no device work
     static void check_instance(const FlatView &c);
     void synchronize();
@@ -146,6 +159,7 @@ private:
     void *stream_ = nullptr;
     uint64_t gens_cap_ = 0;
     Impl *impl_ = nullptr;
+    void prove_batch(size_t count, ProveItem *items, DeviceCircuit *tmpl);
     void init_device();             // second half of the constructor: everything that touches the GPU
 };
 

@@ -58,4 +58,18 @@ __global__ void __launch_bounds__(64) k_witness_eval(const uint4 *__restrict__ s
     witness_eval_segment(sd.x, sd.y, stream + sd.z, coef, v, aL, aR, aO);
 }
 
+// K witnesses of ONE template in the wave layout of a lockstep batch (k_batch.cuh: item k's vectors of length N live at [k*N, (k+1)*N)); item k's
+// committed values at v[k*m .. (k+1)*m).  One launch per level: blockIdx.y = segment of the level, x = item, so the 64 lanes of a wave are consecutive
+// ITEMS of one segment.  They walk the same records - same term counts, same classes, no divergence - and segment, record words and coefficients are
+// wave-uniform loads; only the values differ.  (Consecutive segments of one item, the map of k_witness_eval, diverge on record length and leave each lane
+// alone in its cache lines.)  The stream and the coefficient table are the template's own: a program reads no parameter slot.
+__global__ void __launch_bounds__(64) k_witness_eval_batch(const uint4 *__restrict__ segs, const uint32_t *__restrict__ stream, const scm *__restrict__ coef,
+                                                           const scm *__restrict__ v, uint32_t m, uint32_t lgN, uint32_t K, scm *aL, scm *aR, scm *aO) {
+    const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
+    if (item >= K) return;
+    const uint4 sd = segs[blockIdx.y];
+    const size_t b = (size_t)item << lgN;
+    witness_eval_segment(sd.x, sd.y, stream + sd.z, coef, v + (size_t)item * m, aL + b, aR + b, aO + b);
+}
+
 }  // namespace bpg

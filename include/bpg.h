@@ -18,7 +18,7 @@
  * recombination and the scalar arithmetic of host/scalar.hpp are variable-time as well.  Memory access pattern and running time therefore depend
  * on secret data.  The proof bytes are the same; the posture is that of a prover on a machine its operator trusts.
  * The witness evaluation of a circuit template (bpg_r1cs_assign) is variable-time in the same sense: it skips products by coefficients +1 / -1 and reduces
- * with data-dependent selects.
+ * with data-dependent selects.  The batched evaluation of bpg_r1cs_prove_template_batch runs the same interpreter and is variable-time in the same sense.
  */
 #ifndef BPG_H
 #define BPG_H
@@ -80,7 +80,7 @@ typedef struct {
 
 /* ---------------------------------------------------------------------------------------------------- PART 1: hot path */
 /* ABI version of this header.  Rules: structs the CALLER allocates either carry a struct_size (bpg_config: fields are only ever added at the end and
- * read when struct_size covers them) or are frozen (bpg_timings, bpg_r1cs_instance, bpg_batch_item, bpg_witness_program, bpg_term, bpg_lc); a field never changes type or
+ * read when struct_size covers them) or are frozen (bpg_timings, bpg_r1cs_instance, bpg_batch_item, bpg_template_item, bpg_witness_program, bpg_term, bpg_lc); a field never changes type or
  * meaning.  BPG_ABI_VERSION grows when something a version-7 host relies on is extended (a new field, a new flag value); functions ADDED since
  * version 7 (bpg_r1cs_prove_batch, the circuit-template calls) did not raise it: a host that needs one looks the symbol up (dlsym) and treats its
  * absence as "not supported".  A host checks bpg_abi_version() >= the BPG_ABI_VERSION it was compiled against. */
@@ -243,14 +243,45 @@ typedef struct {
 } bpg_witness_program;
 bpg_status bpg_r1cs_upload_template(bpg_ctx *ctx, const bpg_r1cs_instance *inst, const bpg_witness_program *program, bpg_circuit **out);
 bpg_status bpg_r1cs_assign(bpg_ctx *ctx, bpg_circuit *c, uint64_t m, const uint8_t *v, uint64_t n_params, const uint8_t *param_values);
+/* K fresh witnesses of ONE template proved in lockstep: bpg_r1cs_prove_batch without the host assembly and without the witness upload.  Each item brings
+ * what bpg_r1cs_assign takes (v: m committed values, any value below 2^255; param_values: n_params constant terms in the order of param_rows) and what
+ * bpg_r1cs_prove_resident takes (transcript state after every "V" append, m blindings, the seed, flags, the proof buffer).  proof_out, *proof_len,
+ * transcript_state and status_out[k] of item k are exactly what bpg_r1cs_assign(ctx, tmpl, m, v, n_params, param_values) followed by
+ * bpg_r1cs_prove_resident(ctx, tmpl, ...) gives for it alone, byte for byte, whatever the batch around it and however it is cut into waves.
+ * Lockstep: a template with padded N <= 2^14 (BPG_TT_ORIG_LG), dialect flags 1 and 2 included.  The witnesses of a wave are computed on the device in
+ * one launch per schedule level for ALL its items (a lane per segment and item), straight into the wave's a_L, a_R, a_O; every later stage is shared
+ * as in bpg_r1cs_prove_batch, in waves of at most BPG_BATCH_WAVE_MB (same rule).  Every other item - a template with N > 2^14, BPG_TT_ORIG_LG=0, and
+ * BPG_FLAG_EXPANDED_BLINDING - is proved inside the call by bpg_r1cs_assign + bpg_r1cs_prove_resident, one at a time, in item order.
+ * The whole call is refused with BPG_ERR_INVALID_ARGUMENT, nothing launched and nothing written, for a NULL ctx or tmpl, a circuit that is not a
+ * template, a handle without device state (bpg_test_circuit_handle), and NULL items / status_out with count > 0; count == 0 returns BPG_OK.
+ * Anything else fails per item while the other items are proved: a NULL v with m > 0, a NULL param_values with n_params > 0, a NULL transcript,
+ * blinding, seed, proof or length pointer and a proof buffer below bpg_proof_size (BPG_ERR_INVALID_ARGUMENT), a generator capacity below N
+ * (BPG_ERR_INVALID_GENERATORS_LENGTH).  Returns BPG_OK when every item succeeded, else the status of the first failing item; bpg_last_error names it.
+ * AFTERWARDS (count > 0, whole-call checks passed, on either path) the template holds NO witness: bpg_r1cs_prove_resident returns
+ * BPG_ERR_MISSING_ASSIGNMENT until the next bpg_r1cs_assign, the equal-scalar sets of BPG_MERGE are dropped, and the parameter slots are unspecified
+ * (assign before bpg_r1cs_verify_resident).  (An addition to ABI version 7.) */
+typedef struct {
+    const uint8_t *v;                     /* m x 32: committed values, as bpg_r1cs_assign takes them */
+    const uint8_t *param_values;          /* n_params x 32, in the order of param_rows */
+    uint8_t *transcript_state;            /* 203 B, after every "V" append; updated in place */
+    const uint8_t *v_blinding;            /* m x 32 */
+    const uint8_t *rng_seed;              /* 32 B */
+    uint32_t flags;
+    uint8_t *proof_out; uint64_t *proof_len;   /* in = capacity, out = bytes written */
+} bpg_template_item;
+bpg_status bpg_r1cs_prove_template_batch(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, const bpg_template_item *items, bpg_status *status_out);
 /* TEST HOOKS, no device needed.  bpg_test_template_schedule: the checks of bpg_r1cs_upload_template and the schedule as JSON {"levels", "segments",
  * "max_levels", "seg_first": [segments + 1], "seg_level": [...], "level_segments": [...]}: segment s is multipliers [seg_first[s], seg_first[s+1]), one
  * device lane walks it in order, and everything it reads from another segment lies at a lower level.  bpg_test_template_eval: the device's interpreter
- * compiled for the host over the same packed program (a_L, a_R, a_O out, n x 32 bytes each).  bpg_test_circuit_handle: a handle WITHOUT device state for
+ * compiled for the host over the same packed program (a_L, a_R, a_O out, n x 32 bytes each).  bpg_test_template_eval_batch: the BATCHED interpreter
+ * likewise, `count` witnesses (v: count x m x 32) into the wave layout of a lockstep batch: count x N x 32 bytes per vector, item-major, N = n padded to a
+ * power of two, rows [n, N) of every item zero.  bpg_test_circuit_handle: a handle WITHOUT device state for
  * the argument checks of bpg_r1cs_assign (program NULL: a plain circuit); every call that needs the device refuses it, bpg_r1cs_free(NULL, c) frees it.
  * Any function added later that takes a bpg_circuit must refuse such a handle (its device state is NULL) before it touches the device. */
 bpg_status bpg_test_template_schedule(const bpg_r1cs_instance *inst, const bpg_witness_program *program, char *out, uint64_t cap);
 bpg_status bpg_test_template_eval(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const uint8_t *v, uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out);
+bpg_status bpg_test_template_eval_batch(const bpg_r1cs_instance *inst, const bpg_witness_program *program, uint64_t count, const uint8_t *v,
+                                        uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out);
 bpg_status bpg_test_circuit_handle(const bpg_r1cs_instance *inst, const bpg_witness_program *program, bpg_circuit **out);
 
 /* measurement hooks (bench.py): HIP events on the engine's own stream. mode 0 off, 1 = dominant kernel only, 2 = all kernels;
