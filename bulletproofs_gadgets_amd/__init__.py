@@ -45,6 +45,14 @@ class WitnessProgramView(C.Structure):
     _fields_ = [("lc_ptr", C.c_void_p), ("term_var", C.c_void_p), ("term_coef", C.c_void_p), ("n_params", C.c_uint64), ("param_rows", C.c_void_p)]
 
 
+class WitnessHintsView(C.Structure):
+    """bpg_witness_hints (frozen)."""
+    _fields_ = [("n_hints", C.c_uint64), ("hint_mul", C.c_void_p), ("hint_kind", C.c_void_p), ("hint_arg", C.c_void_p)]
+
+
+HINT_BIT_PAIR = 1
+
+
 class Timings(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("rng_host", "msm_aiao", "msm_s", "poly", "ipa", "total", "ipa_msm", "ipa_fold", "ipa_sync")]
 
@@ -360,11 +368,16 @@ class Context:
         _chk(lib().bpg_r1cs_upload(self._h, C.byref(cs), C.byref(h)))
         return ResidentCircuit(self, h, inst.n, inst.m)
 
-    def upload_template(self, inst: "FlatInstance", program: "WitnessProgram"):
-        """bpg_r1cs_upload_template: the instance (with or without a witness) plus its witness program; ResidentCircuit.assign gives it fresh witnesses."""
+    def upload_template(self, inst: "FlatInstance", program: "WitnessProgram", hints: "WitnessHints" = None):
+        """bpg_r1cs_upload_template: the instance (with or without a witness) plus its witness program; ResidentCircuit.assign gives it fresh witnesses.
+        hints (a circuit with range proofs, Prover.witness_program(hints=True)): bpg_r1cs_upload_template_hinted."""
         h = C.c_void_p()
         cs, cp = inst.cstruct(), program.cstruct()
-        _chk(lib().bpg_r1cs_upload_template(self._h, C.byref(cs), C.byref(cp), C.byref(h)))
+        if hints is not None and len(hints):
+            ch = hints.cstruct()
+            _chk(lib().bpg_r1cs_upload_template_hinted(self._h, C.byref(cs), C.byref(cp), C.byref(ch), C.byref(h)))
+        else:
+            _chk(lib().bpg_r1cs_upload_template(self._h, C.byref(cs), C.byref(cp), C.byref(h)))
         return ResidentCircuit(self, h, inst.n, inst.m, n_params=len(program.param_rows))
 
     def blinding_begin(self, transcript_state, v_blinding, rng_seed, max_multipliers):
@@ -685,6 +698,29 @@ class WitnessProgram:
         return c
 
 
+class WitnessHints:
+    """Owned copy of a bpg_witness_hints: multiplier mul[k] (strictly ascending) is a hint of kind[k] (HINT_BIT_PAIR: a_L = 1 - b, a_R = b, a_O = 0) with
+    b = bit arg[k] of the canonical value of its source, the left list of that multiplier in the witness program (its right list is empty)."""
+
+    def __init__(self, mul=(), kind=(), arg=()):
+        import numpy as np
+        self.mul = np.ascontiguousarray(mul, dtype=np.uint32)
+        self.kind = np.ascontiguousarray(kind, dtype=np.uint32)
+        self.arg = np.ascontiguousarray(arg, dtype=np.uint32)
+        if not len(self.mul) == len(self.kind) == len(self.arg):
+            raise ValueError("mul, kind and arg must have one entry per hint")
+
+    def __len__(self):
+        return len(self.mul)
+
+    def cstruct(self):
+        c = WitnessHintsView()
+        c.n_hints = len(self.mul)
+        c.hint_mul, c.hint_kind, c.hint_arg = (a.ctypes.data if len(a) else None for a in (self.mul, self.kind, self.arg))
+        c._owner = self
+        return c
+
+
 def _scalars32(name, values, count):
     """count x 32 bytes from bytes or a sequence of 32-byte strings"""
     data = bytes(values) if isinstance(values, (bytes, bytearray)) else b"".join(_exact(name, x, 32) for x in values)
@@ -834,17 +870,31 @@ class Prover:
         m = view.m
         return FlatInstance(view, v=C.string_at(v, 32 * m) if m else b"", v_blinding=C.string_at(vb, 32 * m) if m else b"")
 
-    def witness_program(self) -> WitnessProgram:
+    def witness_program(self, hints=False):
         """bpg_prover_witness_program: how every multiplier's assignment follows from committed values and earlier multipliers (owned copy).
-        INVALID_ARGUMENT for a circuit with free multipliers (allocate / allocate_multiplier) or with none."""
+        INVALID_ARGUMENT for a circuit with free multipliers (allocate / allocate_multiplier) or with none.
+        hints=True (bpg_prover_witness_program_hinted) -> (program, WitnessHints): the multipliers of range proofs are exported as bit hints, not refused."""
         import numpy as np
-        view = WitnessProgramView()
-        _chk(lib().bpg_prover_witness_program(self._h, C.byref(view)))
+        view, hv = WitnessProgramView(), WitnessHintsView()
+        if hints:
+            _chk(lib().bpg_prover_witness_program_hinted(self._h, C.byref(view), C.byref(hv)))
+        else:
+            _chk(lib().bpg_prover_witness_program(self._h, C.byref(view)))
         n = self.get_num_multiplications()
         lc_ptr = np.frombuffer(C.string_at(view.lc_ptr, 8 * (2 * n + 1)), dtype=np.uint64).copy()
         nt = int(lc_ptr[-1])
         grab = lambda ptr, dt, k: np.frombuffer(C.string_at(ptr, k * np.dtype(dt).itemsize) if k else b"", dtype=dt).copy()
-        return WitnessProgram(lc_ptr, grab(view.term_var, np.uint32, nt), grab(view.term_coef, np.uint32, nt), grab(view.param_rows, np.uint64, view.n_params))
+        prog = WitnessProgram(lc_ptr, grab(view.term_var, np.uint32, nt), grab(view.term_coef, np.uint32, nt), grab(view.param_rows, np.uint64, view.n_params))
+        if not hints:
+            return prog
+        return prog, WitnessHints(*(grab(ptr, np.uint32, hv.n_hints) for ptr in (hv.hint_mul, hv.hint_kind, hv.hint_arg)))
+
+    def allocate_bit(self, source, bit: int, source_value: bytes):
+        """bpg_prover_allocate_bit: the multiplier range_proof makes for bit `bit` of `source` (a_L = 1 - b, a_R = b), recorded as a hint."""
+        out = (C.c_uint32 * 3)()
+        lc = LinearCombination.of(source)._c()
+        _chk(lib().bpg_prover_allocate_bit(self._h, C.byref(lc), C.c_uint32(bit), _exact("source_value", source_value, 32), out))
+        return Variable(out[0]), Variable(out[1]), Variable(out[2])
 
     def mark_param_row(self, row: int):
         """bpg_prover_mark_param_row: the constant term of constraint `row` changes with the witness (num_constraints() - 1 right after the constrain call)."""
@@ -853,9 +903,11 @@ class Prover:
     def template(self, ctx: "Context", param_rows=()) -> "ResidentCircuit":
         """This circuit as a template resident on `ctx` (with this prover's witness): ResidentCircuit.assign(values, params) then gives it the witness of
         further proofs of the same shape without another host assembly.  param_rows: rows whose constant term is assigned per witness, besides the marked ones."""
-        prog = self.witness_program()
+        prog, hints = self.witness_program(hints=True)
         prog.param_rows = prog.param_rows + [int(r) for r in param_rows]
-        return ctx.upload_template(self.instance(), prog)
+        if ctx is None:
+            raise BpgError(4, "template: no device context")
+        return ctx.upload_template(self.instance(), prog, hints)
 
     def start_blinding(self, rng_seed: bytes = None, max_multipliers: int = 1 << 20):
         """Extension (include/bpg.h bpg_prover_start_blinding): all commitments made - start the serial TranscriptRng chain of the coming

@@ -273,17 +273,22 @@ void bpg_r1cs_free(bpg_ctx *ctx, bpg_circuit *c) {
     delete c;
 }
 
-static WitnessProgramView program_view(const bpg_witness_program *w) {
+static WitnessProgramView program_view(const bpg_witness_program *w, const bpg_witness_hints *h = nullptr) {
     REQUIRE(w);
     WitnessProgramView v; v.lc_ptr = w->lc_ptr; v.term_var = w->term_var; v.term_coef = w->term_coef; v.n_params = w->n_params; v.param_rows = w->param_rows;
+    if (h) { v.n_hints = h->n_hints; v.hint_mul = h->hint_mul; v.hint_kind = h->hint_kind; v.hint_arg = h->hint_arg; }
     return v;
 }
 bpg_status bpg_r1cs_upload_template(bpg_ctx *ctx, const bpg_r1cs_instance *inst, const bpg_witness_program *program, bpg_circuit **out) {
+    return bpg_r1cs_upload_template_hinted(ctx, inst, program, nullptr, out);
+}
+bpg_status bpg_r1cs_upload_template_hinted(bpg_ctx *ctx, const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                           bpg_circuit **out) {
     return guard([&] {
         REQUIRE(out); *out = nullptr;
         REQUIRE(ctx && inst && program);
         const FlatView f = as_view(inst, false);
-        const WitnessProgramView w = program_view(program);
+        const WitnessProgramView w = program_view(program, hints);
         const TemplatePlan plan = Engine::plan_template(f, w);      // every check, the level cap included, before the context is touched
         DeviceCircuit *dc = ctx->engine->upload_template(f, plan);
         bpg_circuit *c = new bpg_circuit{dc, f.n, f.m}; c->is_template = true; c->n_params = w.n_params;
@@ -302,31 +307,45 @@ bpg_status bpg_r1cs_assign(bpg_ctx *ctx, bpg_circuit *c, uint64_t m, const uint8
     });
 }
 bpg_status bpg_test_template_schedule(const bpg_r1cs_instance *inst, const bpg_witness_program *program, char *out, uint64_t cap) {
+    return bpg_test_template_schedule_hinted(inst, program, nullptr, out, cap);
+}
+bpg_status bpg_test_template_schedule_hinted(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, char *out, uint64_t cap) {
     return guard([&] {
         REQUIRE(inst && program && out && cap);
-        const std::string r = witness_schedule_json(Engine::plan_template(as_view(inst, false), program_view(program)).schedule);
+        const std::string r = witness_schedule_json(Engine::plan_template(as_view(inst, false), program_view(program, hints)).schedule);
         if (r.size() + 1 > cap) throw std::invalid_argument("template_schedule: buffer too small (" + std::to_string(r.size() + 1) + " bytes needed)");
         std::memcpy(out, r.c_str(), r.size() + 1);
     });
 }
 bpg_status bpg_test_template_eval(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const uint8_t *v, uint8_t *aL, uint8_t *aR, uint8_t *aO) {
+    return bpg_test_template_eval_hinted(inst, program, nullptr, v, aL, aR, aO);
+}
+bpg_status bpg_test_template_eval_hinted(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, const uint8_t *v,
+                                         uint8_t *aL, uint8_t *aR, uint8_t *aO) {
     return guard([&] {
         REQUIRE(inst && program && aL && aR && aO && (inst->m == 0 || v));
-        Engine::template_eval_host(as_view(inst, false), program_view(program), v, aL, aR, aO);
+        Engine::template_eval_host(as_view(inst, false), program_view(program, hints), v, aL, aR, aO);
     });
 }
 bpg_status bpg_test_template_eval_batch(const bpg_r1cs_instance *inst, const bpg_witness_program *program, uint64_t count, const uint8_t *v,
                                         uint8_t *aL, uint8_t *aR, uint8_t *aO) {
+    return bpg_test_template_eval_batch_hinted(inst, program, nullptr, count, v, aL, aR, aO);
+}
+bpg_status bpg_test_template_eval_batch_hinted(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, uint64_t count,
+                                               const uint8_t *v, uint8_t *aL, uint8_t *aR, uint8_t *aO) {
     return guard([&] {
         REQUIRE(inst && program && aL && aR && aO && (inst->m == 0 || count == 0 || v));
-        Engine::template_eval_batch_host(as_view(inst, false), program_view(program), count, v, aL, aR, aO);
+        Engine::template_eval_batch_host(as_view(inst, false), program_view(program, hints), count, v, aL, aR, aO);
     });
 }
 bpg_status bpg_test_circuit_handle(const bpg_r1cs_instance *inst, const bpg_witness_program *program, bpg_circuit **out) {
+    return bpg_test_circuit_handle_hinted(inst, program, nullptr, out);
+}
+bpg_status bpg_test_circuit_handle_hinted(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, bpg_circuit **out) {
     return guard([&] {
         REQUIRE(out); *out = nullptr;
         const FlatView f = as_view(inst, false);
-        if (program) (void)Engine::plan_template(f, program_view(program)); else Engine::check_instance(f);
+        if (program) (void)Engine::plan_template(f, program_view(program, hints)); else Engine::check_instance(f);
         bpg_circuit *c = new bpg_circuit{nullptr, f.n, f.m}; c->is_template = program != nullptr; c->n_params = program ? program->n_params : 0;
         *out = c;
     });
@@ -694,13 +713,28 @@ bpg_status bpg_prover_instance(bpg_prover *p, bpg_r1cs_instance *out, const uint
     });
 }
 
+static void put_program(const WitnessProgram &w, bpg_witness_program *out) {
+    out->lc_ptr = w.lc_ptr.data(); out->term_var = w.term_var.data(); out->term_coef = w.term_coef.data();
+    out->n_params = w.param_rows.size(); out->param_rows = w.param_rows.data();
+}
 bpg_status bpg_prover_witness_program(bpg_prover *p, bpg_witness_program *out) {
     return guard([&] {
         REQUIRE(p && out);
         p->program = p->p->witness_program();
-        out->lc_ptr = p->program.lc_ptr.data(); out->term_var = p->program.term_var.data(); out->term_coef = p->program.term_coef.data();
-        out->n_params = p->program.param_rows.size(); out->param_rows = p->program.param_rows.data();
+        put_program(p->program, out);
     });
+}
+bpg_status bpg_prover_witness_program_hinted(bpg_prover *p, bpg_witness_program *program_out, bpg_witness_hints *hints_out) {
+    return guard([&] {
+        REQUIRE(p && program_out && hints_out);
+        p->program = p->p->witness_program(true);
+        put_program(p->program, program_out);
+        hints_out->n_hints = p->program.hint_mul.size(); hints_out->hint_mul = p->program.hint_mul.data();
+        hints_out->hint_kind = p->program.hint_kind.data(); hints_out->hint_arg = p->program.hint_arg.data();
+    });
+}
+bpg_status bpg_prover_allocate_bit(bpg_prover *p, const bpg_lc *source, uint32_t bit, const uint8_t source_value[32], uint32_t vars_out[3]) {
+    return guard([&] { REQUIRE(p && source_value && bit < 256); put_vars(p->p->allocate_bit(lc_from(source), bit, OptScalar(Scalar::from_bits(source_value))), vars_out); });
 }
 bpg_status bpg_prover_mark_param_row(bpg_prover *p, uint64_t row) { return guard([&] { REQUIRE(p); p->p->mark_param_row(row); }); }
 

@@ -1319,7 +1319,9 @@ TemplatePlan Engine::plan_template(const FlatView &c, const WitnessProgramView &
     check_witness_program(c, p);
     TemplatePlan T;
     T.schedule = build_witness_schedule(c.n, c.m, p);
-    T.packed = pack_witness_program(c, p, T.schedule);              // the classes come from the caller's table: slots are constants of rows only
+    // BPG_WIT_HINT_SHARE=0 (measurement only, tools/diag/range_template.py): every bit hint reduces its source again
+    const bool share = !env_present("BPG_WIT_HINT_SHARE") || env_int_strict("BPG_WIT_HINT_SHARE", 0, 1) != 0;
+    T.packed = pack_witness_program(c, p, T.schedule, share);       // the classes come from the caller's table: slots are constants of rows only
     T.slotted = with_parameter_slots(c, p);
     T.n_params = p.n_params; T.param_first = c.ncoef;
     return T;

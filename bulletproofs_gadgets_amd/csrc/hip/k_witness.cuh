@@ -6,6 +6,10 @@
 // Values are Montgomery form, canonical - what upload() leaves in aL / aR / aO (k_sc_from_bytes) - so a proof cannot tell which of the two filled them.
 // A lane is a latency chain (a MiMC block: 972 dependent products); the last multiplier's three values stay in registers because the programs the
 // gadgets record read them back at once (a MiMC round reads the previous output, then the square's left value).
+// A HINTED record (a range proof's bit: WIT_HINT_BIT_PAIR) is no product: the lane evaluates the record's source, takes it out of Montgomery form once, and
+// keeps the eight canonical words in registers for the records that follow with WIT_HINT_SAME_SOURCE - a 64-bit range costs one reduction and 64 bit
+// extractions.  Which branch a record takes is a property of the RECORD (the same for every lane that walks it); the bit itself, the only thing that differs
+// between the items of a batch, selects by mask.
 #pragma once
 #include "sc.cuh"
 #include "../host/witness_record.hpp"
@@ -34,11 +38,33 @@ BPG_HD scm witness_eval_lc(const uint32_t *t, uint32_t count, const WitPrev &pre
     return acc;
 }
 
+// bit `bit` (0..255) of the little-endian words w[0..8): the word is picked by compares, not by an indexed read of a register array
+BPG_HD uint32_t witness_bit(const uint32_t *w, uint32_t bit) {
+    const uint32_t k = bit >> 5;
+    uint32_t x = w[0];
+    BPG_UNROLL for (uint32_t j = 1; j < 8; j++) x = k == j ? w[j] : x;
+    return (x >> (bit & 31u)) & 1u;
+}
+
 // multipliers [first, first + count) from the records at `rec`
 BPG_HD void witness_eval_segment(uint32_t first, uint32_t count, const uint32_t *rec, const scm *coef, const scm *v, scm *aL, scm *aR, scm *aO) {
     WitPrev prev; prev.l = prev.r = prev.o = sc_zero(); prev.idx = 0xffffffffu;
+    uint32_t src[8];                                                // canonical words of the last hint source (the packer never shares across segments)
+    BPG_UNROLL for (int k = 0; k < 8; k++) src[k] = 0;
     for (uint32_t i = first; i < first + count; i++) {
-        const uint32_t nl = rec[0], w1 = rec[1], same = w1 & WIT_SAME_AS_LEFT, nr = w1 & ~WIT_SAME_AS_LEFT;
+        const uint32_t nl = rec[0], w1 = rec[1];
+        if (w1 & WIT_HINT_BIT_PAIR) {
+            if (!(w1 & WIT_HINT_SAME_SOURCE)) sc_to_words(src, witness_eval_lc(rec + 2, nl, prev, coef, v, aL, aR, aO));
+            const uint32_t set = 0u - witness_bit(src, w1 & WIT_HINT_ARG_MASK);     // all ones when the bit is set
+            const scm one = SC_R1();
+            scm l, r;
+            BPG_UNROLL for (int k = 0; k < 8; k++) { l.v[k] = one.v[k] & ~set; r.v[k] = one.v[k] & set; }
+            aL[i] = l; aR[i] = r; aO[i] = sc_zero();
+            prev.l = l; prev.r = r; prev.o = sc_zero(); prev.idx = i;
+            rec += 2 + 2 * nl;
+            continue;
+        }
+        const uint32_t same = w1 & WIT_SAME_AS_LEFT, nr = w1 & WIT_RIGHT_COUNT_MASK;
         const scm l = witness_eval_lc(rec + 2, nl, prev, coef, v, aL, aR, aO);
         const scm r = same ? l : witness_eval_lc(rec + 2 + 2 * nl, nr, prev, coef, v, aL, aR, aO);
         const scm o = sc_mont_mul(l, r);

@@ -41,15 +41,10 @@ inline std::vector<LinearCombination> vars_to_lc(const std::vector<Variable> &v)
 
 // ------------------------------------------------------------------------------------------ utils.rs:5-35
 inline void range_proof(ConstraintSystem &cs, LinearCombination x, uint8_t n, const OptScalar &x_assignment) {
+    const LinearCombination x_original = x;                 // what every bit is a bit OF: the hint a Prover records (ConstraintSystem::allocate_bit)
     Scalar exp_2 = Scalar::one();
     for (uint8_t i = 0; i < n; i++) {
-        Scalar l, r;
-        if (x_assignment.some) {
-            uint8_t off = i / 8;
-            uint8_t bit = (x_assignment.v.as_bytes()[off] >> (i - off * 8)) & 1u;
-            l = Scalar::from_u64(1u - bit); r = Scalar::from_u64(bit);
-        }
-        MulVars mv = cs.allocate_multiplier(x_assignment.some, l, r);
+        MulVars mv = cs.allocate_bit(x_original, i, x_assignment);
         cs.constrain(LinearCombination(mv.o));                                                   // a * b = 0
         cs.constrain(LinearCombination(mv.l) + (LinearCombination(mv.r) - LinearCombination(Scalar::one())));   // a = 1 - b
         x = x - LinearCombination(mv.r) * exp_2;

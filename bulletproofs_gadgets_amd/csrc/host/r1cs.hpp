@@ -100,6 +100,19 @@ public:
     virtual Variable allocate(const OptScalar &assignment) = 0;
     virtual MulVars allocate_multiplier(bool some, const Scalar &l, const Scalar &r) = 0;
     virtual void constrain(const LinearCombination &lc) = 0;
+    // The multiplier a range proof makes for bit `bit` (0..255) of `source`: a_L = 1 - b, a_R = b, with b read off the little-endian bytes of the value
+    // the caller assigns to the source (utils.rs:9-21).  To a verifier and to a recording buffer it is allocate_multiplier and nothing more; a Prover also
+    // notes WHERE the bit comes from, so that the circuit stays a template (bpg_witness_hints).  `source` is constrained by the caller, not here.
+    virtual MulVars allocate_bit(const LinearCombination &source, uint32_t bit, const OptScalar &source_assignment) {
+        (void)source;
+        if (bit >= 256) throw std::invalid_argument("allocate_bit: a scalar has 256 bits");
+        Scalar l, r;
+        if (source_assignment.some) {
+            const uint32_t b = (source_assignment.v.as_bytes()[bit / 8] >> (bit % 8)) & 1u;
+            l = Scalar::from_u64(1u - b); r = Scalar::from_u64(b);
+        }
+        return allocate_multiplier(source_assignment.some, l, r);
+    }
 };
 
 // Flattened instance handed to the engine / exported for the oracle (layout of include/bpg.h bpg_r1cs_upload)
@@ -128,19 +141,26 @@ struct FlatView {
 // Witness program of a circuit whose every multiplier came from multiply(left, right) (include/bpg.h bpg_witness_program): multiplier i has
 // left = terms [lc_ptr[2i], lc_ptr[2i+1]) and right = terms [lc_ptr[2i+1], lc_ptr[2i+2]); a term is (packed variable, index into the instance's coefficient table)
 // and may name committed values, the constant One and multipliers BELOW i only.  param_rows: constraint rows whose constant term is assigned per witness.
+// Hints (bpg_witness_hints): multiplier hint_mul[k] (strictly ascending) is no product of two linear combinations; its left list is the SOURCE of the hint,
+// its right list is empty, and hint_kind / hint_arg say what to take from the source's value (WITNESS_HINT_BIT_PAIR: a_L = 1 - b, a_R = b, b = bit arg).
+constexpr uint32_t WITNESS_HINT_BIT_PAIR = 1;
 struct WitnessProgram {
     std::vector<uint64_t> lc_ptr{0};
     std::vector<uint32_t> term_var, term_coef;
     std::vector<uint64_t> param_rows;
+    std::vector<uint32_t> hint_mul, hint_kind, hint_arg;
 };
 struct WitnessProgramView {
     const uint64_t *lc_ptr = nullptr;
     const uint32_t *term_var = nullptr, *term_coef = nullptr;
     uint64_t n_params = 0;
     const uint64_t *param_rows = nullptr;
+    uint64_t n_hints = 0;
+    const uint32_t *hint_mul = nullptr, *hint_kind = nullptr, *hint_arg = nullptr;
     WitnessProgramView() {}
     explicit WitnessProgramView(const WitnessProgram &w)
-        : lc_ptr(w.lc_ptr.data()), term_var(w.term_var.data()), term_coef(w.term_coef.data()), n_params(w.param_rows.size()), param_rows(w.param_rows.data()) {}
+        : lc_ptr(w.lc_ptr.data()), term_var(w.term_var.data()), term_coef(w.term_coef.data()), n_params(w.param_rows.size()), param_rows(w.param_rows.data()),
+          n_hints(w.hint_mul.size()), hint_mul(w.hint_mul.data()), hint_kind(w.hint_kind.data()), hint_arg(w.hint_arg.data()) {}
 };
 
 // Shared bookkeeping of Prover and Verifier: constraint rows with a coefficient dictionary.
@@ -152,19 +172,21 @@ protected:
     std::vector<Scalar> coef_;
     std::unordered_map<Scalar, uint32_t, KeyHash> coef_index_;
     std::pair<Scalar, uint32_t> last_[2] = {{Scalar(), UINT32_MAX}, {Scalar(), UINT32_MAX}};
-    void push_row(const LinearCombination &lc) {
-        for (auto &t : lc.terms) {
-            Scalar c = t.second.is_canonical() ? t.second : t.second.reduced();
-            uint32_t id;
-            if (last_[0].second != UINT32_MAX && c == last_[0].first) id = last_[0].second;           // two-entry memo in front of the hash map
-            else if (last_[1].second != UINT32_MAX && c == last_[1].first) { id = last_[1].second; std::swap(last_[0], last_[1]); }
-            else {
-                auto it = coef_index_.find(c);
-                if (it == coef_index_.end()) { id = (uint32_t)coef_.size(); coef_.push_back(c); coef_index_.emplace(c, id); } else id = it->second;
-                last_[1] = last_[0]; last_[0] = {c, id};
-            }
-            term_var_.push_back(t.first.packed()); term_coef_.push_back(id);
+    // index of a coefficient in the dictionary (appended when new)
+    uint32_t intern(const Scalar &s) {
+        Scalar c = s.is_canonical() ? s : s.reduced();
+        uint32_t id;
+        if (last_[0].second != UINT32_MAX && c == last_[0].first) id = last_[0].second;           // two-entry memo in front of the hash map
+        else if (last_[1].second != UINT32_MAX && c == last_[1].first) { id = last_[1].second; std::swap(last_[0], last_[1]); }
+        else {
+            auto it = coef_index_.find(c);
+            if (it == coef_index_.end()) { id = (uint32_t)coef_.size(); coef_.push_back(c); coef_index_.emplace(c, id); } else id = it->second;
+            last_[1] = last_[0]; last_[0] = {c, id};
         }
+        return id;
+    }
+    void push_row(const LinearCombination &lc) {
+        for (auto &t : lc.terms) { term_var_.push_back(t.first.packed()); term_coef_.push_back(intern(t.second)); }
         row_ptr_.push_back(term_var_.size());
     }
     void export_rows(FlatCircuit &f) const {
@@ -233,6 +255,21 @@ public:
         made_by_.push_back(FREE_MULTIPLIER);
         return MulVars{{Variable::MultiplierLeft, i}, {Variable::MultiplierRight, i}, {Variable::MultiplierOutput, i}};
     }
+    // the base multiplier, plus the record of its source: the terms are kept as given and enter the coefficient dictionary only when the instance or the
+    // program is exported (resolve_hints) - a range proof constrains its source afterwards, so its coefficients are in the dictionary by then and neither the
+    // table nor its order differs from an assembly that records nothing
+    MulVars allocate_bit(const LinearCombination &source, uint32_t bit, const OptScalar &source_assignment) override {
+        const MulVars mv = ConstraintSystem::allocate_bit(source, bit, source_assignment);
+        Hint h; h.bit = bit;
+        bool same = !hints_.empty() && hints_.back().t1 - hints_.back().t0 == source.terms.size();
+        for (size_t k = 0; same && k < source.terms.size(); k++)
+            same = hint_terms_[hints_.back().t0 + k].first.packed() == source.terms[k].first.packed() && hint_terms_[hints_.back().t0 + k].second == source.terms[k].second;
+        if (same) { h.t0 = hints_.back().t0; h.t1 = hints_.back().t1; }         // the bits of one range share one copy of their source
+        else { h.t0 = hint_terms_.size(); hint_terms_.insert(hint_terms_.end(), source.terms.begin(), source.terms.end()); h.t1 = hint_terms_.size(); }
+        made_by_.back() = HINT_MULTIPLIER | hints_.size();
+        hints_.push_back(h);
+        return mv;
+    }
     void constrain(const LinearCombination &lc) override { push_row(lc); }
 
     size_t get_num_multiplications() const { return aL_.size(); }
@@ -264,7 +301,8 @@ public:
         return acc;
     }
 
-    FlatCircuit flatten() const {
+    FlatCircuit flatten() {
+        resolve_hints();
         FlatCircuit f; f.n = aL_.size(); f.m = v_.size();
         f.aL.resize(f.n * 32); f.aR.resize(f.n * 32); f.aO.resize(f.n * 32);
         for (size_t i = 0; i < f.n; i++) { red(aL_[i]).to_bytes(&f.aL[32 * i]); red(aR_[i]).to_bytes(&f.aR[32 * i]); red(aO_[i]).to_bytes(&f.aO[32 * i]); }
@@ -277,13 +315,23 @@ public:
     // the linear combinations as they were before those terms are the rows without their last term); allocate() / allocate_multiplier() note a free multiplier,
     // whose assignment is no function of linear combinations.  Nothing the prover exports today (instance, transcript, proof) reads the record.
     // Throws std::invalid_argument when the circuit has a free multiplier or none at all.
-    WitnessProgram witness_program() const {
+    // with_hints (bpg_prover_witness_program_hinted): a multiplier made by allocate_bit is exported as a hint - its left list is the source, its right list
+    // empty; without, it is refused like any free multiplier.
+    WitnessProgram witness_program(bool with_hints = false) {
         if (aL_.empty()) throw std::invalid_argument("witness program: the circuit has no multipliers");
+        if (with_hints) resolve_hints();
         WitnessProgram w;
         w.lc_ptr.reserve(2 * aL_.size() + 1);
         for (size_t i = 0; i < made_by_.size(); i++) {
-            if (made_by_[i] == FREE_MULTIPLIER)
+            if (made_by_[i] == FREE_MULTIPLIER || (!with_hints && (made_by_[i] & HINT_MULTIPLIER)))
                 throw std::invalid_argument("witness program: multiplier " + std::to_string(i) + " is a free multiplier (allocate / allocate_multiplier: its assignment is a hint, not a function of linear combinations)");
+            if (made_by_[i] & HINT_MULTIPLIER) {
+                const Hint &h = hints_[made_by_[i] & ~HINT_MULTIPLIER];
+                for (uint64_t k = h.t0; k < h.t1; k++) { w.term_var.push_back(hint_terms_[k].first.packed()); w.term_coef.push_back(hint_coef_[k]); }
+                w.lc_ptr.push_back(w.term_var.size()); w.lc_ptr.push_back(w.term_var.size());
+                w.hint_mul.push_back((uint32_t)i); w.hint_kind.push_back(WITNESS_HINT_BIT_PAIR); w.hint_arg.push_back(h.bit);
+                continue;
+            }
             for (uint64_t r = made_by_[i]; r < made_by_[i] + 2; r++) {
                 w.term_var.insert(w.term_var.end(), term_var_.begin() + row_ptr_[r], term_var_.begin() + row_ptr_[r + 1] - 1);
                 w.term_coef.insert(w.term_coef.end(), term_coef_.begin() + row_ptr_[r], term_coef_.begin() + row_ptr_[r + 1] - 1);
@@ -314,8 +362,13 @@ private:
     bool deferred_ = false; size_t flushed_ = 0;
     bool stub_commitments_ = false;
     int64_t pending_ = -1;
-    static constexpr uint64_t FREE_MULTIPLIER = ~0ull;
-    std::vector<uint64_t> made_by_;     // per multiplier: the first of the two constraint rows multiply() made for it, or FREE_MULTIPLIER
+    static constexpr uint64_t FREE_MULTIPLIER = ~0ull, HINT_MULTIPLIER = 1ull << 63;
+    std::vector<uint64_t> made_by_;     // per multiplier: the first of the two constraint rows multiply() made for it, FREE_MULTIPLIER, or HINT_MULTIPLIER | index into hints_
+    struct Hint { uint32_t bit; uint64_t t0, t1; };                     // allocate_bit: bit `bit` of the source hint_terms_[t0, t1)
+    std::vector<Hint> hints_;
+    std::vector<std::pair<Variable, Scalar>> hint_terms_;
+    std::vector<uint32_t> hint_coef_;   // dictionary index per hint term, filled by resolve_hints
+    void resolve_hints() { while (hint_coef_.size() < hint_terms_.size()) hint_coef_.push_back(intern(hint_terms_[hint_coef_.size()].second)); }
     std::vector<uint64_t> param_rows_;
 };
 

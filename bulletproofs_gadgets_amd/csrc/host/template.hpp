@@ -6,6 +6,10 @@
 // Cutting rule: walk the multipliers in order; a multiplier that names a committed value, or a multiplier outside the current segment, which the segment
 // has not named before opens a new segment.  (A MiMC sponge names the block it absorbs in every round of that block and nothing else from outside: one
 // segment per absorbed block; a Merkle node absorbs two children: two segments per node, the second one level above the first.)
+// A HINTED multiplier (a bit of a source, WitnessProgramView::hint_*) reads its source's terms under the same rules, and one more: a hinted multiplier whose
+// source is not the source of the hinted multiplier right before it opens a segment.  A run of bit hints over one source - a range proof - is thus a lane of
+// its own that reduces the source once (WIT_HINT_SAME_SOURCE), one level above whatever made the source, and is never hung onto the end of a 972-product
+// chain.  (A 64-bit range proof over one committed value: one segment at level 0.)
 #pragma once
 #include <cstdint>
 #include <stdexcept>
@@ -46,11 +50,29 @@ inline void check_witness_program(const FlatView &c, const WitnessProgramView &p
             else if (kind == 3) { if (idx >= c.m) throw std::invalid_argument("template: committed index out of range in the witness program"); }
             else if (kind != 4) throw std::invalid_argument("template: bad variable kind in the witness program");
         }
+    if (p.n_hints && (!p.hint_mul || !p.hint_kind || !p.hint_arg)) throw std::invalid_argument("template: n_hints without hint arrays");
+    for (uint64_t k = 0; k < p.n_hints; k++) {
+        const uint64_t i = p.hint_mul[k];
+        if (i >= c.n) throw std::invalid_argument("template: hint " + std::to_string(k) + " names multiplier " + std::to_string(i) + " (out of range)");
+        if (k && p.hint_mul[k - 1] >= i) throw std::invalid_argument("template: hinted multipliers must be strictly ascending");
+        if (p.hint_kind[k] != WITNESS_HINT_BIT_PAIR) throw std::invalid_argument("template: unknown hint kind " + std::to_string(p.hint_kind[k]));
+        if (p.hint_arg[k] >= 256) throw std::invalid_argument("template: hint bit " + std::to_string(p.hint_arg[k]) + " (a scalar has 256 bits)");
+        if (p.lc_ptr[2 * i + 1] != p.lc_ptr[2 * i + 2]) throw std::invalid_argument("template: hinted multiplier " + std::to_string(i) + " has a right list (its left list is the source, the right list is empty)");
+    }
     if (p.n_params && !p.param_rows) throw std::invalid_argument("template: n_params without param_rows");
     for (uint64_t k = 0; k < p.n_params; k++) {
         if (p.param_rows[k] >= c.q) throw std::invalid_argument("template: parameter row out of range");
         for (uint64_t j = 0; j < k; j++) if (p.param_rows[j] == p.param_rows[k]) throw std::invalid_argument("template: parameter row named twice");
     }
+}
+
+// hint k reads the source of hint k - 1, which sits on the multiplier right before: the same terms in the same order
+inline bool hint_same_source(const WitnessProgramView &p, uint64_t k) {
+    if (k == 0 || p.hint_mul[k - 1] + 1 != p.hint_mul[k]) return false;
+    const uint64_t a = p.lc_ptr[2 * (uint64_t)p.hint_mul[k - 1]], b = p.lc_ptr[2 * (uint64_t)p.hint_mul[k]], cnt = p.lc_ptr[2 * (uint64_t)p.hint_mul[k] + 1] - b;
+    if (b - a != cnt) return false;
+    for (uint64_t t = 0; t < cnt; t++) if (p.term_var[a + t] != p.term_var[b + t] || p.term_coef[a + t] != p.term_coef[b + t]) return false;
+    return true;
 }
 
 // (a checked program) -> schedule; refuses more than WITNESS_MAX_LEVELS levels
@@ -59,8 +81,10 @@ inline WitnessSchedule build_witness_schedule(uint64_t n, uint64_t m, const Witn
     const uint32_t NONE = UINT32_MAX;
     std::vector<uint32_t> seg_of(n), seen_mul(n, NONE), seen_v(m, NONE);    // seen_*: the last segment that named this value from outside
     uint32_t seg = NONE, first = 0;
+    uint64_t h = 0;                                                          // next hint
     for (uint64_t i = 0; i < n; i++) {
         bool cut = (seg == NONE);
+        if (h < p.n_hints && p.hint_mul[h] == i) { cut = cut || !hint_same_source(p, h); h++; }
         for (uint64_t k = p.lc_ptr[2 * i]; k < p.lc_ptr[2 * i + 2] && !cut; k++) {
             const uint32_t kind = p.term_var[k] >> 29, idx = p.term_var[k] & 0x1fffffffu;
             if (kind == 3) cut = seen_v[idx] != seg;
@@ -105,7 +129,8 @@ struct PackedWitnessProgram {
     std::vector<uint32_t> stream;
     std::vector<WitnessSegment> segs;       // in WitnessSchedule::order
 };
-inline PackedWitnessProgram pack_witness_program(const FlatView &c, const WitnessProgramView &p, const WitnessSchedule &S) {
+// share_sources = false (a measurement switch, BPG_WIT_HINT_SHARE=0): every hinted record carries its source and the reader reduces it again
+inline PackedWitnessProgram pack_witness_program(const FlatView &c, const WitnessProgramView &p, const WitnessSchedule &S, bool share_sources = true) {
     static const uint8_t MINUS_ONE[32] = {0xec, 0xd3, 0xf5, 0x5c, 0x1a, 0x63, 0x12, 0x58, 0xd6, 0x9c, 0xf7, 0xa2, 0xde, 0xf9, 0xde, 0x14,
                                           0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0x10};
     std::vector<uint8_t> cls(c.ncoef);      // 0 general, 1 plus one, 2 minus one, 3 zero
@@ -128,13 +153,24 @@ inline PackedWitnessProgram pack_witness_program(const FlatView &c, const Witnes
         }
         return cnt;
     };
+    std::vector<uint8_t> seg_start(c.n, 0);
+    for (uint32_t s = 0; s < S.segments(); s++) seg_start[S.seg_first[s]] = 1;
+    uint64_t hk = 0;                                                         // next hint
     for (uint64_t i = 0; i < c.n; i++) {
         const uint64_t l0 = p.lc_ptr[2 * i], l1 = p.lc_ptr[2 * i + 1], r1 = p.lc_ptr[2 * i + 2];
-        bool same = (l1 - l0 == r1 - l1);
-        for (uint64_t k = 0; same && k < l1 - l0; k++) same = p.term_var[l0 + k] == p.term_var[l1 + k] && p.term_coef[l0 + k] == p.term_coef[l1 + k];
         rec_at[i] = P.stream.size();
         P.stream.push_back(0); P.stream.push_back(0);
         const uint64_t h = rec_at[i];
+        if (hk < p.n_hints && p.hint_mul[hk] == i) {
+            const bool shared = share_sources && !seg_start[i] && hint_same_source(p, hk);     // the reader starts every segment with no source held
+            const uint32_t ns = shared ? 0u : emit(l0, l1);
+            P.stream[h] = ns; P.stream[h + 1] = WIT_HINT_BIT_PAIR | (shared ? WIT_HINT_SAME_SOURCE : 0u) | (p.hint_arg[hk] & WIT_HINT_ARG_MASK);
+            hk++;
+            continue;
+        }
+        bool same = (l1 - l0 == r1 - l1);
+        for (uint64_t k = 0; same && k < l1 - l0; k++) same = p.term_var[l0 + k] == p.term_var[l1 + k] && p.term_coef[l0 + k] == p.term_coef[l1 + k];
+        if (r1 - l1 > WIT_RIGHT_COUNT_MASK) throw std::invalid_argument("template: witness program too large");
         const uint32_t nl = emit(l0, l1);
         const uint32_t nr = same ? 0u : emit(l1, r1);
         P.stream[h] = nl; P.stream[h + 1] = same ? WIT_SAME_AS_LEFT : nr;

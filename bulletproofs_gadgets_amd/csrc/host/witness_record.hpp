@@ -3,12 +3,17 @@
 //   word 0: number of left terms; word 1: number of right terms, or WIT_SAME_AS_LEFT alone when the right list IS the left list (no right terms follow);
 //   then two words per term: the packed variable (kind << 29 | index) and coefficient class << WIT_CLASS_SHIFT | index into the coefficient table.
 // Classes: +1 and -1 need no product (as in Prover::eval); a zero coefficient adds nothing and its term is dropped by the packer.
+// A HINTED multiplier (bpg_witness_hints, kind BIT_PAIR) is no product: word 1 = WIT_HINT_BIT_PAIR | bit index (low 8 bits), word 0 = number of terms of the
+// SOURCE, which follow; a_L = 1 - b, a_R = b, a_O = 0 with b that bit of the canonical value (mod l) of the source.  WIT_HINT_SAME_SOURCE beside it: the
+// source is the previous record's (a hinted record of the same segment) - word 0 is 0, no terms follow, and the reader still holds the reduced value.
+// The flags leave 29 bits for a right-term count.
 #pragma once
 #include <cstdint>
 
 namespace bpg {
 
-constexpr uint32_t WIT_SAME_AS_LEFT = 1u << 31;
+constexpr uint32_t WIT_SAME_AS_LEFT = 1u << 31, WIT_HINT_BIT_PAIR = 1u << 30, WIT_HINT_SAME_SOURCE = 1u << 29;
+constexpr uint32_t WIT_RIGHT_COUNT_MASK = WIT_HINT_SAME_SOURCE - 1u, WIT_HINT_ARG_MASK = 0xffu;
 constexpr uint32_t WIT_CLASS_SHIFT = 30, WIT_COEF_INDEX_MASK = (1u << WIT_CLASS_SHIFT) - 1u;
 constexpr uint32_t WIT_COEF_GENERAL = 0, WIT_COEF_PLUS_ONE = 1, WIT_COEF_MINUS_ONE = 2;
 

@@ -2,7 +2,7 @@
 reference's tests do (library path of SURVEY.md section 3.2).  Seeds: SHAKE256("bpg-synth" || cfg || index)."""
 import hashlib
 
-from . import (BoundsCheck, MerkleTree256, MimcHash256, Prover, Transcript, be_to_scalar, commit, commit_all_single,
+from . import (BoundsCheck, LessThan, MerkleTree256, MimcHash256, Prover, Transcript, be_to_scalar, commit, commit_all_single,
                commit_single, hash_pattern, mimc_hash, scalar_to_be, vars_to_lc, L)
 
 
@@ -45,6 +45,28 @@ def bounds_check_64(ctx, seed=0, label=b"BoundsCheck", prover_cls=Prover):
         dv = verifier_commit(v, dcoms)
         BoundsCheck(lo, hi).verify(v, wv, dv)
     return Assembled(p, t, wcoms + dcoms, 128, replay)
+
+
+def less_than_126(ctx, seed=0, label=b"LessThan", prover_cls=Prover):
+    """One LESS W0 W1 over two committed 15-byte values, the smaller one on the left: three 126-bit range proofs (left, right, right - left) and the
+    product delta * delta^-1: n = 3 * 126 + 1 = 379, N = 512, m = 4 (left, right, delta, delta^-1)."""
+    cfg = "lt-%d" % seed
+    lo, hi = sorted((synth(cfg, 0, 15), synth(cfg, 1, 15)))
+    if lo == hi:
+        hi = (int.from_bytes(hi, "big") + 1).to_bytes(15, "big")
+    t = Transcript(label)
+    p = prover_cls(ctx, t)
+    ls, lcom, lvar = commit_single(p, lo, blinding(cfg, 0))
+    rs, rcom, rvar = commit_single(p, hi, blinding(cfg, 1))
+    g = LessThan(lvar, ls, rvar, rs)
+    dcoms, derived = _setup(g, p, [], [blinding(cfg, 2), blinding(cfg, 3)])
+    g.prove(p, [], derived)
+
+    def replay(v):
+        from . import verifier_commit
+        vs = verifier_commit(v, [lcom, rcom] + dcoms)
+        LessThan(vs[0], None, vs[1], None).verify(v, [], vs[2:])
+    return Assembled(p, t, [lcom, rcom] + dcoms, 512, replay)
 
 
 def mimc_preimage(ctx, nbytes=2130, seed=0, label=b"MiMCHash", prover_cls=Prover):

@@ -19,6 +19,7 @@
  * on secret data.  The proof bytes are the same; the posture is that of a prover on a machine its operator trusts.
  * The witness evaluation of a circuit template (bpg_r1cs_assign) is variable-time in the same sense: it skips products by coefficients +1 / -1 and reduces
  * with data-dependent selects.  The batched evaluation of bpg_r1cs_prove_template_batch runs the same interpreter and is variable-time in the same sense.
+ * The bit hints of a range-proof template (bpg_witness_hints) are read by that interpreter too: no claim of constant time is made for them either.
  */
 #ifndef BPG_H
 #define BPG_H
@@ -80,7 +81,7 @@ typedef struct {
 
 /* ---------------------------------------------------------------------------------------------------- PART 1: hot path */
 /* ABI version of this header.  Rules: structs the CALLER allocates either carry a struct_size (bpg_config: fields are only ever added at the end and
- * read when struct_size covers them) or are frozen (bpg_timings, bpg_r1cs_instance, bpg_batch_item, bpg_template_item, bpg_witness_program, bpg_term, bpg_lc); a field never changes type or
+ * read when struct_size covers them) or are frozen (bpg_timings, bpg_r1cs_instance, bpg_batch_item, bpg_template_item, bpg_witness_program, bpg_witness_hints, bpg_term, bpg_lc); a field never changes type or
  * meaning.  BPG_ABI_VERSION grows when something a version-7 host relies on is extended (a new field, a new flag value); functions ADDED since
  * version 7 (bpg_r1cs_prove_batch, the circuit-template calls) did not raise it: a host that needs one looks the symbol up (dlsym) and treats its
  * absence as "not supported".  A host checks bpg_abi_version() >= the BPG_ABI_VERSION it was compiled against. */
@@ -225,7 +226,10 @@ bpg_status bpg_r1cs_prove_batch(bpg_ctx *ctx, uint64_t count, const bpg_batch_it
  * Refused with BPG_ERR_INVALID_ARGUMENT, before any device work, bpg_last_error naming the reason: NULL arguments, n = 0, a malformed instance or program,
  * a term index out of range or naming a multiplier >= i, a parameter row >= q or named twice, and a program whose schedule has more than 4096 levels
  * (the device runs one launch per level of dependent segments; a circuit that is one long dependent chain is assembled on the host).  A circuit with
- * FREE multipliers (allocate / allocate_multiplier: BoundsCheck, LessThan, Inequality, SetMembership) has no program: bpg_prover_witness_program refuses it.
+ * FREE multipliers (allocate / allocate_multiplier) has no program: bpg_prover_witness_program refuses it.  Of the gadgets only range_proof - BoundsCheck,
+ * LessThan - allocates multipliers of its own (Inequality and SetMembership use multiply() alone, their derived values are committed), and what it
+ * allocates is a function of earlier values after all: see the HINTS below, which make those circuits templates.  An OR block replays its clauses through
+ * a recording buffer that keeps the two scalars only: range proofs inside OR blocks stay free multipliers.
  *
  * bpg_r1cs_assign: m committed values (32 bytes each; any value below 2^255 as Scalar::from_bits admits, reduced mod l on the device) and n_params
  * constant terms in the order of param_rows (for `hash - root = 0` the constant term is -root mod l).  m and n_params must match the template, v and
@@ -242,6 +246,26 @@ typedef struct {
     const uint64_t *param_rows;  /* n_params constraint rows whose constant term is assigned per witness */
 } bpg_witness_program;
 bpg_status bpg_r1cs_upload_template(bpg_ctx *ctx, const bpg_r1cs_instance *inst, const bpg_witness_program *program, bpg_circuit **out);
+/* HINTS: templates for circuits with range proofs.  (Additions to ABI version 7; bpg_witness_program itself is unchanged.)  utils::range_proof allocates,
+ * for bit j of a linear combination x, a multiplier with a_L = 1 - b, a_R = b, a_O = 0.  The frozen struct bpg_witness_hints names such multipliers: for a
+ * hinted multiplier i the program's LEFT list [lc_ptr[2i], lc_ptr[2i+1]) is the SOURCE x and its right list is empty.
+ * SEMANTICS: the device takes bit `arg` of the CANONICAL representative (mod l) of the source's value.  The host's range_proof reads the raw little-endian
+ * bytes of the assignment it was handed.  The two agree whenever that assignment is canonical - everything Gadget::setup derives is, and so is every source
+ * that is not one single unreduced committed value - and byte identity of proofs with a host assembly is promised for canonical source values only.  Bits
+ * above a range's width are ignored on both sides: an out-of-range value gives the same (unsatisfying) witness, and the same proof bytes, as the host.
+ * bpg_r1cs_upload_template_hinted: hints == NULL or n_hints == 0 makes it bpg_r1cs_upload_template.  Refused besides, before any device work, with
+ * BPG_ERR_INVALID_ARGUMENT and bpg_last_error naming the reason: NULL arrays with n_hints > 0, an index >= n or indices not strictly ascending, an unknown
+ * kind, arg >= 256, a hinted multiplier with a non-empty right list, a source naming a multiplier >= i.  bpg_r1cs_assign, bpg_r1cs_prove_resident,
+ * bpg_r1cs_verify_resident and bpg_r1cs_prove_template_batch serve a hinted template exactly as they are documented for any template.  In the schedule a
+ * run of hints over one source is a segment of its own, one level above what made the source; the source is reduced once per run. */
+#define BPG_HINT_BIT_PAIR 1u      /* a_L = 1 - b, a_R = b, a_O = 0; b = bit `arg` (0..255) of the canonical value of the source */
+typedef struct {                  /* frozen */
+    uint64_t n_hints;
+    const uint32_t *hint_mul;     /* strictly ascending multiplier indices */
+    const uint32_t *hint_kind;    /* BPG_HINT_* */
+    const uint32_t *hint_arg;
+} bpg_witness_hints;
+bpg_status bpg_r1cs_upload_template_hinted(bpg_ctx *ctx, const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, bpg_circuit **out);
 bpg_status bpg_r1cs_assign(bpg_ctx *ctx, bpg_circuit *c, uint64_t m, const uint8_t *v, uint64_t n_params, const uint8_t *param_values);
 /* K fresh witnesses of ONE template proved in lockstep: bpg_r1cs_prove_batch without the host assembly and without the witness upload.  Each item brings
  * what bpg_r1cs_assign takes (v: m committed values, any value below 2^255; param_values: n_params constant terms in the order of param_rows) and what
@@ -283,6 +307,13 @@ bpg_status bpg_test_template_eval(const bpg_r1cs_instance *inst, const bpg_witne
 bpg_status bpg_test_template_eval_batch(const bpg_r1cs_instance *inst, const bpg_witness_program *program, uint64_t count, const uint8_t *v,
                                         uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out);
 bpg_status bpg_test_circuit_handle(const bpg_r1cs_instance *inst, const bpg_witness_program *program, bpg_circuit **out);
+/* the same four for a program with hints (hints == NULL: the calls above) */
+bpg_status bpg_test_template_schedule_hinted(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, char *out, uint64_t cap);
+bpg_status bpg_test_template_eval_hinted(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, const uint8_t *v,
+                                         uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out);
+bpg_status bpg_test_template_eval_batch_hinted(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, uint64_t count,
+                                               const uint8_t *v, uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out);
+bpg_status bpg_test_circuit_handle_hinted(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, bpg_circuit **out);
 
 /* measurement hooks (bench.py): HIP events on the engine's own stream. mode 0 off, 1 = dominant kernel only, 2 = all kernels;
  * report = JSON text {kernel: {count, total_ms, alg_bytes, device_bytes, field_mults}} accumulated since the last set. */
@@ -388,6 +419,14 @@ bpg_status bpg_prover_instance(bpg_prover *p, bpg_r1cs_instance *out, const uint
  * multiplier (allocate / allocate_multiplier) or no multiplier at all.  bpg_prover_mark_param_row: the constant term of constraint `row` is assigned per
  * witness; the row a bpg_prover_constrain call made is bpg_prover_num_constraints(p) - 1 right after it (a gadget's closing constraint likewise). */
 bpg_status bpg_prover_witness_program(bpg_prover *p, bpg_witness_program *out);
+/* The same with hints: succeeds when every multiplier came from multiply() or from a range proof (bpg_range_proof_prove, BoundsCheck, LessThan,
+ * bpg_prover_allocate_bit), else the "free multiplier" refusal above.  Both views are borrowed under the same rule and replace those of an earlier export
+ * call on this prover; export the instance (bpg_prover_instance) AFTER the last bpg_prover_allocate_bit.  bpg_prover_witness_program itself still refuses a
+ * circuit with a hinted multiplier.
+ * bpg_prover_allocate_bit: ConstraintSystem::allocate_bit for hosts that drive the mirror directly - the multiplier range_proof makes for bit `bit` (0..255)
+ * of `source`, whose assigned value is source_value (raw little-endian bytes, as range_proof reads them): a_L = 1 - b, a_R = b.  It adds no constraint. */
+bpg_status bpg_prover_witness_program_hinted(bpg_prover *p, bpg_witness_program *program_out, bpg_witness_hints *hints_out);
+bpg_status bpg_prover_allocate_bit(bpg_prover *p, const bpg_lc *source, uint32_t bit, const uint8_t source_value[32], uint32_t vars_out[3]);
 bpg_status bpg_prover_mark_param_row(bpg_prover *p, uint64_t row);
 /* Extension (no upstream counterpart; the proof bytes do not change): start drawing the blinding scalars of the coming prove() now.
  * Upstream's Prover::prove builds its TranscriptRng from the transcript after the last commitment (+ the "m" suffix), the commitment
