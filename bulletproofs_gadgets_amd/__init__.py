@@ -603,6 +603,11 @@ class _TemplateItem(C.Structure):
                 ("rng_seed", C.c_char_p), ("flags", C.c_uint32), ("proof_out", C.c_void_p), ("proof_len", C.POINTER(C.c_uint64))]
 
 
+class _TemplateCommitItem(C.Structure):
+    """bpg_template_commit_item (frozen): bpg_template_item and the buffer of the item's commitments."""
+    _fields_ = _TemplateItem._fields_ + [("commitments_out", C.c_void_p)]
+
+
 class ResidentCircuit:
     def __init__(self, ctx, h, n, m, n_params=None):
         self.ctx, self._h, self.n, self.m = ctx, h, n, m
@@ -627,10 +632,11 @@ class ResidentCircuit:
                                            out, C.byref(ln), C.byref(tm) if timings else None))
         return (out.raw[:ln.value], ts.raw[:203], tm.as_dict()) if timings else (out.raw[:ln.value], ts.raw[:203])
 
-    def _template_items(self, items):
+    def _template_items(self, items, struct=_TemplateItem):
         """bpg_template_item array of [(values, params, transcript_state, v_blinding, rng_seed, flags)] and the buffers it points into:
-        (transcript state, proof buffer, proof length, values, params, v_blinding, seed) per item.  values / params of None stay NULL."""
-        arr = (_TemplateItem * max(len(items), 1))()
+        (transcript state, proof buffer, proof length, values, params, v_blinding, seed) per item.  values / params of None stay NULL.
+        struct=_TemplateCommitItem: the same fields in a bpg_template_commit_item array (commitments_out left NULL)."""
+        arr = (struct * max(len(items), 1))()
         keep = []
         for k, (values, params, state, vb, seed, flags) in enumerate(items):
             v = None if values is None else bytes(values)
@@ -657,6 +663,24 @@ class ResidentCircuit:
             _chk(rc)
         st = [status[k] for k in range(n)]
         res = [(k[1].raw[:k[2].value] if s == 0 else None, k[0].raw[:203]) for k, s in zip(keep, st)]
+        return (res, st) if return_status else res
+
+    def prove_batch_commit(self, items, return_status=False):
+        """bpg_r1cs_prove_template_batch_commit: items = [(values, params, state_before_commitments, blindings, rng_seed, flags)] ->
+        [(proof, transcript state after, commitments)]: prove_batch that makes the m Pedersen commitments of every item itself (a wave's in one launch)
+        and appends them to the item's transcript as "V", as Prover.commit does, before it proves.  commitments: m x 32 bytes in commit order.  Raises
+        BpgError on the first failing item; return_status=True returns (results, statuses) instead, with (None, state as given, None) for a failed item."""
+        arr, keep = self._template_items(items, _TemplateCommitItem)
+        n = len(items)
+        coms = [_buf(32 * self.m) for _ in range(n)]
+        for k in range(n):
+            arr[k].commitments_out = C.cast(coms[k], C.c_void_p)
+        status = (C.c_int32 * max(n, 1))()
+        rc = lib().bpg_r1cs_prove_template_batch_commit(self.ctx._h, self._h, C.c_uint64(n), arr, status)
+        if not return_status:
+            _chk(rc)
+        st = [status[k] for k in range(n)]
+        res = [(k[1].raw[:k[2].value], k[0].raw[:203], c.raw[:32 * self.m]) if s == 0 else (None, k[0].raw[:203], None) for k, c, s in zip(keep, coms, st)]
         return (res, st) if return_status else res
 
     def verify(self, transcript_state, commitments, proof, seed=None, flags=0):

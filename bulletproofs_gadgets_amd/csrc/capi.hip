@@ -444,12 +444,16 @@ bpg_status bpg_r1cs_prove_batch(bpg_ctx *ctx, uint64_t count, const bpg_batch_it
     return first;
 }
 
-bpg_status bpg_r1cs_prove_template_batch(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, const bpg_template_item *items, bpg_status *status_out) {
-    // the whole call is refused before anything is written or launched; a handle without device state first, whatever else was passed
+// the whole call is refused before anything is written or launched; a handle without device state first, whatever else was passed
+static bpg_status template_batch_refusal(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, const void *items, bpg_status *status_out) {
     if (tmpl && !tmpl->dc) { g_last_error = "prove_template_batch: the handle has no device state (bpg_test_circuit_handle)"; return BPG_ERR_INVALID_ARGUMENT; }
     if (!ctx || !tmpl || (count && (!items || !status_out))) { g_last_error = "null or invalid argument: ctx, tmpl, items and status_out"; return BPG_ERR_INVALID_ARGUMENT; }
     if (!tmpl->is_template) { g_last_error = "prove_template_batch: the circuit is not a template (bpg_r1cs_upload_template)"; return BPG_ERR_INVALID_ARGUMENT; }
-    if (!count) { g_last_error.clear(); return BPG_OK; }
+    return BPG_OK;
+}
+// count > 0 items that passed template_batch_refusal.  coms == nullptr: bpg_r1cs_prove_template_batch.  Else bpg_r1cs_prove_template_batch_commit: the
+// transcript states are those BEFORE the "V" appends and coms[k] receives item k's m encodings (the caller checked m > 0)
+static bpg_status template_batch(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, const bpg_template_item *items, uint8_t *const *coms, bpg_status *status_out) {
     const uint64_t m = tmpl->m, n = tmpl->n, n_params = tmpl->n_params;
     std::vector<bpg_status> st(count, BPG_OK);
     std::vector<std::string> msg(count);
@@ -465,6 +469,7 @@ bpg_status bpg_r1cs_prove_template_batch(bpg_ctx *ctx, bpg_circuit *tmpl, uint64
         st[k] = guard([&] {
             REQUIRE((m == 0 || it.v) && (n_params == 0 || it.param_values));
             REQUIRE(it.transcript_state && it.rng_seed && it.proof_out && it.proof_len && (m == 0 || it.v_blinding));
+            if (coms && !coms[k]) throw std::invalid_argument("prove_template_batch_commit: an item without a commitment buffer");
             if (*it.proof_len < bpg_proof_size(n, it.flags)) throw std::invalid_argument("prove: proof buffer too small");
             uint64_t N = 1; while (N < n) N <<= 1;
             if (ctx->engine->gens_capacity() < N) throw R1CSException(R1CSError::InvalidGeneratorsLength, "generator capacity below padded circuit size (call bpg_gens_ensure)");
@@ -479,7 +484,7 @@ bpg_status bpg_r1cs_prove_template_batch(bpg_ctx *ctx, bpg_circuit *tmpl, uint64
         lock.push_back(std::move(p)); lock_at.push_back(k);
     }
     if (!lock.empty()) {
-        const bpg_status s = guard([&] { ctx->engine->prove_template_batch(tmpl->dc, lock.size(), lock.data()); });
+        const bpg_status s = guard([&] { ctx->engine->prove_template_batch(tmpl->dc, lock.size(), lock.data(), coms != nullptr); });
         const std::string why = g_last_error;
         for (size_t j = 0; j < lock.size(); j++) {
             const uint64_t k = lock_at[j];
@@ -487,14 +492,36 @@ bpg_status bpg_r1cs_prove_template_batch(bpg_ctx *ctx, bpg_circuit *tmpl, uint64
             if (s != BPG_OK) { msg[k] = why; continue; }
             std::memcpy(items[k].proof_out, lock[j].proof.data(), lock[j].proof.size()); *items[k].proof_len = lock[j].proof.size();
             T[k].export_state(items[k].transcript_state);
+            if (coms) std::memcpy(coms[k], lock[j].commitments.data(), 32 * m);
         }
     }
-    for (uint64_t k = 0; k < count; k++) {      // larger templates, BPG_TT_ORIG_LG=0 and expanded blinding: assign + the single path, one at a time, same bytes
-        if (route[k] != 2) continue;
+    // larger templates, BPG_TT_ORIG_LG=0 and expanded blinding: assign + the single path, one at a time, same bytes.  Their commitments (coms) are made
+    // up front, ALL of them in one Pedersen launch, and appended to a copy of each transcript: an item that fails keeps its state and its buffer
+    std::vector<uint64_t> single_at;
+    for (uint64_t k = 0; k < count; k++) if (route[k] == 2) single_at.push_back(k);
+    std::vector<uint8_t> scom;
+    if (coms && !single_at.empty()) {
+        std::vector<uint8_t> sv(single_at.size() * m * 32), sb(sv.size());
+        for (size_t j = 0; j < single_at.size(); j++) {
+            std::memcpy(&sv[j * m * 32], items[single_at[j]].v, m * 32); std::memcpy(&sb[j * m * 32], items[single_at[j]].v_blinding, m * 32);
+        }
+        scom.resize(sv.size());
+        const bpg_status s = guard([&] { ctx->engine->pedersen_commit(single_at.size() * m, sv.data(), sb.data(), scom.data()); });
+        if (s != BPG_OK) { for (uint64_t k : single_at) { st[k] = s; msg[k] = g_last_error; } single_at.clear(); }
+    }
+    for (size_t j = 0; j < single_at.size(); j++) {
+        const uint64_t k = single_at[j];
         const bpg_template_item &it = items[k];
+        uint8_t state[BPG_TRANSCRIPT_STATE_BYTES];
+        if (coms) {
+            Transcript t = Transcript::from_state(it.transcript_state);
+            for (uint64_t i = 0; i < m; i++) t.append_point("V", &scom[(j * m + i) * 32]);
+            t.export_state(state);
+        }
         st[k] = bpg_r1cs_assign(ctx, tmpl, m, it.v, n_params, it.param_values);
-        if (st[k] == BPG_OK) st[k] = bpg_r1cs_prove_resident(ctx, tmpl, it.transcript_state, m, it.v_blinding, it.rng_seed, it.flags, it.proof_out, it.proof_len, nullptr);
-        if (st[k] != BPG_OK) msg[k] = g_last_error;
+        if (st[k] == BPG_OK) st[k] = bpg_r1cs_prove_resident(ctx, tmpl, coms ? state : it.transcript_state, m, it.v_blinding, it.rng_seed, it.flags, it.proof_out, it.proof_len, nullptr);
+        if (st[k] != BPG_OK) { msg[k] = g_last_error; continue; }
+        if (coms) { std::memcpy(it.transcript_state, state, sizeof state); std::memcpy(coms[k], &scom[j * m * 32], m * 32); }
     }
     Engine::drop_witness(tmpl->dc);             // on either path: a caller never depends on which one its items took
     bpg_status first = BPG_OK;
@@ -504,6 +531,36 @@ bpg_status bpg_r1cs_prove_template_batch(bpg_ctx *ctx, bpg_circuit *tmpl, uint64
         if (first == BPG_OK && st[k] != BPG_OK) { first = st[k]; g_last_error = "item " + std::to_string(k) + ": " + msg[k]; }
     }
     return first;
+}
+
+bpg_status bpg_r1cs_prove_template_batch(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, const bpg_template_item *items, bpg_status *status_out) {
+    const bpg_status s = template_batch_refusal(ctx, tmpl, count, items, status_out);
+    if (s != BPG_OK) return s;
+    if (!count) { g_last_error.clear(); return BPG_OK; }
+    return template_batch(ctx, tmpl, count, items, nullptr, status_out);
+}
+
+bpg_status bpg_r1cs_prove_template_batch_commit(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, const bpg_template_commit_item *items, bpg_status *status_out) {
+    const bpg_status s = template_batch_refusal(ctx, tmpl, count, items, status_out);
+    if (s != BPG_OK) return s;
+    if (!count) { g_last_error.clear(); return BPG_OK; }
+    std::vector<bpg_template_item> plain(count);
+    std::vector<uint8_t *> coms(count);
+    for (uint64_t k = 0; k < count; k++) {
+        const bpg_template_commit_item &it = items[k];
+        plain[k] = bpg_template_item{it.v, it.param_values, it.transcript_state, it.v_blinding, it.rng_seed, it.flags, it.proof_out, it.proof_len};
+        coms[k] = it.commitments_out;
+    }
+    return template_batch(ctx, tmpl, count, plain.data(), tmpl->m ? coms.data() : nullptr, status_out);      // nothing to commit to: the existing call
+}
+
+bpg_status bpg_test_append_commitments(const uint8_t state_in[BPG_TRANSCRIPT_STATE_BYTES], uint64_t m, const uint8_t *coms, uint8_t state_out[BPG_TRANSCRIPT_STATE_BYTES]) {
+    return guard([&] {
+        REQUIRE(state_in && state_out && (m == 0 || coms));
+        Transcript t = Transcript::from_state(state_in);
+        for (uint64_t i = 0; i < m; i++) t.append_point("V", coms + 32 * i);
+        t.export_state(state_out);
+    });
 }
 
 bpg_status bpg_r1cs_verify(bpg_ctx *ctx, const bpg_r1cs_instance *inst, uint8_t ts[BPG_TRANSCRIPT_STATE_BYTES], uint64_t m, const uint8_t *V,

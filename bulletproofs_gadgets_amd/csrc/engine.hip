@@ -225,7 +225,7 @@ struct DeviceCircuit {
     X(k_scan_apply) X(k_bucket_chunks) X(k_bucket_combine) X(k_bucket_combine_heavy) X(k_bucket_reduce) X(k_window_sums) X(k_window_sums_quad) X(k_decompress) X(k_ipa_s) X(k_verify_scalars) X(k_verify_scalars_acc) X(k_bench_fe_mul) \
     X(k_tt_bases) X(k_tt_multiples) X(k_tt_bases8) X(k_tt_multiples8) X(k_tt_round8) X(k_tt_factors) X(k_tt_advance) X(k_tt_round) X(k_tt_finish) X(k_blind_expand) X(k_tt_commit3) X(k_tt_commit3_finish) X(k_csc_count) X(k_csc_fill) X(k_csc_colptr) X(k_merge_insert) X(k_merge_plan) X(k_merge_groups) X(k_merge_members) X(k_merge_sum) \
     X(k_bt_commit3) X(k_bt_commit3_finish) X(k_bt_compress) X(k_bt_exp) X(k_bt_poly_t) X(k_bt_poly_eval) X(k_bt_factors) X(k_bt_advance) X(k_bt_round) \
-    X(k_bt_finish) X(k_bt_fold_scalars) X(k_witness_eval) X(k_witness_eval_batch)
+    X(k_bt_finish) X(k_bt_fold_scalars) X(k_witness_eval) X(k_witness_eval_batch) X(k_bt_commit_v)
 enum KernelId {
 #define X(n) KID_##n,
     BPG_KERNELS(X)
@@ -460,6 +460,11 @@ struct Engine::Impl {
                                     // (BPG_TT_ORIG_LG; BPG_TT_LG sets both).  Measured at 2^20 (profiles/r03_tail_start.txt): 12 beats 14 alone and in flight
     uint32_t batch_wave_mb = 512;   // lockstep batches (prove_batch): device state of one wave at most this many MB (BPG_BATCH_WAVE_MB; 0 = one proof per wave)
     DevBuf bt_dev; PinBuf bt_pin;   // prove_batch: the wave's device buffers and its pinned upload / read-back area
+    // prove_template_batch with commitments (k_bt_commit_v): commitments per wave of the kernel (1..4, a block makes four times as many).  4 measured
+    // fastest at 3072 commitments (profiles/template_commit.json); BPG_COMMIT_CPW stays for that measurement only (tools/diag/template_commit.py), same bytes.
+    // commit_ev: recorded behind the read-back of a wave's commitments, so that the host waits for them and not for the witness evaluation queued behind
+    uint32_t commit_cpw = 4;
+    hipEvent_t commit_ev = nullptr;
     PinBuf h_raw, h_small;
     // Speculative blinding streams (Engine::blinding_begin): the leading draws of Prover::prove's TranscriptRng, produced on the context's
     // chain worker (ONE host thread, FIFO) before the circuit is known - or, for a sequence of proofs, while the previous proof's kernels run.
@@ -628,6 +633,7 @@ Engine::Engine(int device, const EngineConfig &cfg) : device_(device) {
     if (env_present("BPG_TT_LG")) K->tt_lg = K->tt_orig_lg = (uint32_t)env_int_strict("BPG_TT_LG", 0, 20);
     env_set("BPG_TT_ORIG_LG", 0, 20, K->tt_orig_lg);
     env_set("BPG_BATCH_WAVE_MB", 0, 1 << 20, K->batch_wave_mb);
+    env_set("BPG_COMMIT_CPW", 1, 4, K->commit_cpw);
     if (env_present("BPG_GENS_SHARE")) K->gens_share = env_int_strict("BPG_GENS_SHARE", 0, 1) != 0;
 
     int count = 0;
@@ -695,6 +701,7 @@ Engine::~Engine() {
         sd->d.release();
     }
     for (int k = 0; k < 2; k++) if (impl_->stage_ev[k]) (void)hipEventDestroy(impl_->stage_ev[k]);
+    if (impl_->commit_ev) (void)hipEventDestroy(impl_->commit_ev);
     (void)hipStreamDestroy(impl_->st);
     delete impl_;
 }
@@ -2225,7 +2232,7 @@ void Engine::drop_witness(DeviceCircuit *d) {
     d->has_witness = false;
     d->merge_tried = false; d->mI.groups = d->mI.skipped = 0; d->mO.groups = d->mO.skipped = 0;
 }
-void Engine::prove_template_batch(DeviceCircuit *d, size_t count, ProveItem *items) {
+void Engine::prove_template_batch(DeviceCircuit *d, size_t count, ProveItem *items, bool commit) {
     if (!template_lockstep(d)) throw std::logic_error("prove_template_batch: the circuit is not a template with a host copy of its rows");
     drop_witness(d);
     for (size_t k = 0; k < count; k++) {
@@ -2233,11 +2240,12 @@ void Engine::prove_template_batch(DeviceCircuit *d, size_t count, ProveItem *ite
         if (!items[k].params && d->n_params) throw std::invalid_argument("prove_template_batch: an item without parameter values");
         items[k].flat = &d->host_view;
     }
-    prove_batch(count, items, d);
+    prove_batch(count, items, d, commit && d->m);
 }
 
-// tmpl != nullptr: every item is a fresh witness of that template (flat = its host copy; values, params per item)
-void Engine::prove_batch(size_t count, ProveItem *items, DeviceCircuit *tmpl) {
+// tmpl != nullptr: every item is a fresh witness of that template (flat = its host copy; values, params per item).  commit (a template with m > 0): the
+// transcripts come in as they are BEFORE the commitments; every wave makes its own (k_bt_commit_v) and appends them before anything is drawn
+void Engine::prove_batch(size_t count, ProveItem *items, DeviceCircuit *tmpl, bool commit) {
     if (!count) return;
     HIPCHK(hipSetDevice(device_));
     Impl &I = *impl_;
@@ -2292,7 +2300,8 @@ void Engine::prove_batch(size_t count, ProveItem *items, DeviceCircuit *tmpl) {
         size_t off = 0;
         auto take = [&](size_t b) { const size_t o = off; off += Impl::al256(b ? b : 1); return o; };
         // (a template wave uploads its committed values where a host-assembled wave uploads 3 K N witness scalars)
-        const size_t o_wit = take(tmpl ? mT * 32 : 3 * KN * 32), o_coef = take(ncoefT * 32), o_raw = take(2 * KN * 64), o_rp = take((qT + 1) * 8), o_tv = take(nnzT * 4),
+        // (... and, when it makes the commitments, their reduced blindings right behind: the two go up ahead of the rest)
+        const size_t o_wit = take(tmpl ? mT * 32 : 3 * KN * 32), o_vbl = take(commit ? mT * 32 : 0), o_coef = take(ncoefT * 32), o_raw = take(2 * KN * 64), o_rp = take((qT + 1) * 8), o_tv = take(nnzT * 4),
                      o_tc = take(nnzT * 4), o_nk = take(K * 4), o_qk = take(K * 4), o_rb = take(K * 4), o_bsc = take(K * BSC * 32), o_bases = take(K * 3 * 32);
         const size_t up_bytes = off;
         const size_t o_back = take(std::max<size_t>(K * 3 * 32 + 64, (6 * K + mT + 1) * 32 + 64));
@@ -2307,7 +2316,8 @@ void Engine::prove_batch(size_t count, ProveItem *items, DeviceCircuit *tmpl) {
                      d_colptr = take((ncols + 1) * 8), d_erow = take(nnzT * 4), d_ecoef = take(nnzT * 4), d_counts = take((nvar + 2) * 4),
                      d_starts = take((nvar + 2) * 4), d_cursor = take((nvar + 2) * 4), d_rowc = take((qT + 2) * 4), d_rowcs = take((qT + 2) * 4),
                      d_bsum = take((std::max(nb1, nb2) + 2) * 4), d_part = take((size_t)K * std::max(3 * nblkC, 2 * nblkR) * sizeof(ge_ext)),
-                     d_pts = take(K * 3 * sizeof(ge_ext)), d_comp = take(K * 3 * 32), d_misc = take(64), d_v = take(tmpl ? mT * 32 : 0);
+                     d_pts = take(K * 3 * sizeof(ge_ext)), d_comp = take(K * 3 * 32), d_misc = take(64), d_v = take(tmpl ? mT * 32 : 0),
+                     d_vcom = take(commit ? mT * 32 : 0);
         I.bt_dev.ensure(off);
         uint8_t *dev = I.bt_dev.as<uint8_t>();
         auto D = [&](size_t o) { return dev + o; };
@@ -2318,6 +2328,51 @@ void Engine::prove_batch(size_t count, ProveItem *items, DeviceCircuit *tmpl) {
         const uint32_t *nk = reinterpret_cast<const uint32_t *>(D(o_nk));
         scm *h_bsc = reinterpret_cast<scm *>(pin + o_bsc);
 
+        // the wave's witnesses: committed values reduced once for the whole wave, padding rows [n, N) of the 3 K vectors zeroed (one strided fill), then one
+        // launch per level with a lane per (segment, item) - everything below cannot tell where a_L, a_R, a_O came from
+        auto reduce_values = [&] {
+            if (mT) BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(mT, 256)), dim3(256), reinterpret_cast<const uint32_t *>(D(o_wit)), reinterpret_cast<scm *>(D(d_v)), (uint32_t)mT);
+        };
+        auto eval_witnesses = [&] {
+            const uint64_t n = tmpl->n;
+            if (N > n) HIPCHK(hipMemset2DAsync(aL + n, N * sizeof(scm), 0, (N - n) * sizeof(scm), 3 * K, I.st));
+            for (size_t l = 0; l + 1 < tmpl->wit_level_ptr.size(); l++) {
+                const uint32_t s0 = tmpl->wit_level_ptr[l], ns = tmpl->wit_level_ptr[l + 1] - s0;
+                BPG_LAUNCH(I, k_witness_eval_batch, dim3(cdiv(K, 64), ns), dim3(64), tmpl->wit_segs.as<uint4>() + s0, tmpl->wit_stream.as<uint32_t>(),
+                           tmpl->coef.as<scm>(), reinterpret_cast<const scm *>(D(d_v)), (uint32_t)tmpl->m, lgN, (uint32_t)K, aL, aR, aO);
+            }
+        };
+        // ---- the wave's Pedersen commitments (commit): values and reduced blindings go up first, ONE launch makes the K m encodings from the reduced values
+        // the witness evaluation reads, one copy brings them back; the witness evaluation is queued behind and runs while the host threads append the
+        // encodings as "V" - the transcripts are needed next, by the stage that draws the blindings of A_I
+        if (commit) {
+            pool.run(K, [&](size_t lo, size_t hi) {
+                for (size_t k = lo; k < hi; k++) {
+                    const uint64_t m = W[k]->flat->m;
+                    std::memcpy(pin + o_wit + 32 * vbase[k], W[k]->values, 32 * m);
+                    for (uint64_t j = 0; j < m; j++) (*W[k]->vb)[j].to_bytes(pin + o_vbl + 32 * (vbase[k] + j));     // reduced, as pedersen_commit uploads them
+                }
+            });
+            if (!I.commit_ev) HIPCHK(hipEventCreateWithFlags(&I.commit_ev, hipEventDisableTiming));
+            HIPCHK(hipMemcpyAsync(D(o_wit), pin + o_wit, o_coef - o_wit, hipMemcpyHostToDevice, I.st));
+            reduce_values();
+            BPG_LAUNCH(I, k_bt_commit_v, dim3(cdiv(mT, 4 * I.commit_cpw)), dim3(256), reinterpret_cast<const scm *>(D(d_v)), reinterpret_cast<const uint32_t *>(D(o_vbl)),
+                       I.ped_table.as<ge_pniels>(), D(d_vcom), (uint32_t)mT, I.commit_cpw);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(pin + o_back, D(d_vcom), mT * 32, hipMemcpyDeviceToHost, I.st));
+            HIPCHK(hipEventRecord(I.commit_ev, I.st));
+            eval_witnesses();
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventSynchronize(I.commit_ev));
+            pool.run(K, [&](size_t lo, size_t hi) {
+                for (size_t k = lo; k < hi; k++) {
+                    const uint64_t m = W[k]->flat->m;
+                    const uint8_t *com = pin + o_back + 32 * vbase[k];
+                    W[k]->commitments.assign(com, com + 32 * m);
+                    for (uint64_t j = 0; j < m; j++) W[k]->T->append_point("V", com + 32 * j);
+                }
+            });
+        }
         // ---- host, per item: transcript, RNG, the first three blindings and the 2n draws, packed with the instance
         std::vector<TranscriptRng> rng; rng.reserve(K);
         for (size_t k = 0; k < K; k++) { W[k]->T->append_u64("m", W[k]->flat->m); rng.push_back(W[k]->T->build_rng(*W[k]->vb, W[k]->seed)); }
@@ -2360,22 +2415,10 @@ void Engine::prove_batch(size_t count, ProveItem *items, DeviceCircuit *tmpl) {
         reinterpret_cast<uint64_t *>(pin + o_rp)[qT] = nnzT;
 
         // ---- one upload; witness, coefficients and draws to scalars; the block-diagonal CSR -> CSC in one pass (prove()'s upload kernels)
-        HIPCHK(hipMemcpyAsync(dev, pin, up_bytes, hipMemcpyHostToDevice, I.st));
+        { const size_t up0 = commit ? o_coef : 0; HIPCHK(hipMemcpyAsync(dev + up0, pin + up0, up_bytes - up0, hipMemcpyHostToDevice, I.st)); }   // (values and blindings of a committing wave are up already)
         HIPCHK(hipMemsetAsync(stale, 0, 64, I.st));
         if (!tmpl) BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(3 * KN, 256)), dim3(256), reinterpret_cast<const uint32_t *>(D(o_wit)), aL, (uint32_t)(3 * KN));
-        else {
-            // the wave's witnesses are computed here: committed values reduced once for the whole wave, padding rows [n, N) of the 3 K vectors zeroed (one
-            // strided fill), then one launch per level with a lane per (segment, item) - everything below cannot tell where a_L, a_R, a_O came from
-            const uint64_t n = tmpl->n, m = tmpl->m;
-            scm *vd = reinterpret_cast<scm *>(D(d_v));
-            if (mT) BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(mT, 256)), dim3(256), reinterpret_cast<const uint32_t *>(D(o_wit)), vd, (uint32_t)mT);
-            if (N > n) HIPCHK(hipMemset2DAsync(aL + n, N * sizeof(scm), 0, (N - n) * sizeof(scm), 3 * K, I.st));
-            for (size_t l = 0; l + 1 < tmpl->wit_level_ptr.size(); l++) {
-                const uint32_t s0 = tmpl->wit_level_ptr[l], ns = tmpl->wit_level_ptr[l + 1] - s0;
-                BPG_LAUNCH(I, k_witness_eval_batch, dim3(cdiv(K, 64), ns), dim3(64), tmpl->wit_segs.as<uint4>() + s0, tmpl->wit_stream.as<uint32_t>(),
-                           tmpl->coef.as<scm>(), vd, (uint32_t)m, lgN, (uint32_t)K, aL, aR, aO);
-            }
-        }
+        else if (!commit) { reduce_values(); eval_witnesses(); }
         if (ncoefT) BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(ncoefT, 256)), dim3(256), reinterpret_cast<const uint32_t *>(D(o_coef)), reinterpret_cast<scm *>(D(d_coef)), (uint32_t)ncoefT);
         BPG_LAUNCH(I, k_sc_from_wide, dim3(cdiv(2 * KN, 256)), dim3(256), reinterpret_cast<const uint32_t *>(D(o_raw)), sL, (uint32_t)(2 * KN), stale);
         {

@@ -131,6 +131,7 @@ public:
         const FlatView *flat = nullptr; Transcript *T = nullptr; const std::vector<Scalar> *vb = nullptr; const uint8_t *seed = nullptr; uint32_t flags = 0;
         const uint8_t *values = nullptr, *params = nullptr;
         std::vector<uint8_t> proof;
+        std::vector<uint8_t> commitments;       // prove_template_batch(commit = true): the m encodings this item's wave made and appended to T as "V"
     };
     // does a proof of n multipliers with these flags take the lockstep path (0 < n, padded N <= 2^tt_orig_lg, no expanded blinding)
     bool lockstep_eligible(uint64_t n, uint32_t flags) const;
@@ -139,7 +140,10 @@ public:
     // K fresh witnesses of ONE template in lockstep (include/bpg.h bpg_r1cs_prove_template_batch): prove_batch with the witness of every item computed
     // on the device, all items of a wave in one launch per schedule level (k_witness_eval_batch), straight into the wave's a_L, a_R, a_O.  The template
     // must be lockstep-eligible with every item's flags (template_lockstep()).  Whatever happens, the template holds no witness afterwards.
-    void prove_template_batch(DeviceCircuit *tmpl, size_t count, ProveItem *items);
+    // commit (include/bpg.h bpg_r1cs_prove_template_batch_commit): T is the transcript BEFORE the "V" appends; each wave makes the commitments
+    // values[j] * B + vb[j] * B_blinding of its items in one launch (k_bt_commit_v) from the values it uploaded for the witness evaluation, fills
+    // `commitments` and appends them to T before anything is drawn from it.  Nothing after that point differs.
+    void prove_template_batch(DeviceCircuit *tmpl, size_t count, ProveItem *items, bool commit = false);
     // the template kept the host copy of its rows that the lockstep packer needs (padded N <= 2^14)
     static bool template_lockstep(const DeviceCircuit *tmpl);
     // what a template batch leaves behind on either path: no witness, no equal-scalar sets
@@ -159,7 +163,7 @@ private:
     void *stream_ = nullptr;
     uint64_t gens_cap_ = 0;
     Impl *impl_ = nullptr;
-    void prove_batch(size_t count, ProveItem *items, DeviceCircuit *tmpl);
+    void prove_batch(size_t count, ProveItem *items, DeviceCircuit *tmpl, bool commit = false);
     void init_device();             // second half of the constructor: everything that touches the GPU
 };
 

@@ -64,6 +64,55 @@ __global__ void __launch_bounds__(256) k_bt_commit3_finish(const ge_ext *__restr
     }
     ge_block_sum_store(acc, lds, quad, out + (size_t)item * 3 + cls);
 }
+// The Pedersen commitments of a wave's committed values (bpg_r1cs_prove_template_batch_commit): out[c] = compress(v[c] * B + r[c] * B_blinding) for the
+// `count` = K m commitments of the wave, from the window tables k_pedersen reads.  v is the wave's device block of REDUCED values in Montgomery form
+// (what the witness evaluation reads: B has order l, so the reduced value gives the same point), r the reduced blindings as plain little-endian
+// words.  Both are below l < 2^253, so the digits come from the biased form (tt_biased_words: nibble - 8 in [-8, 7], no carry chain) instead of
+// ped_digit's serial recoding - another signed representation of the same integer, and the encoding of a point does not depend on how it was summed.
+// Layout: a block of four waves makes 4 * cpw commitments (cpw in 1..4).  Wave w makes commitments first + w * cpw + i one after the other (lane =
+// window: the first table entry is taken as it is, the second added), the 64 partial sums meet in the wave's own LDS region as four lanes per point
+// (three additions through LDS, four shuffle levels: seven quad_add of ~750 instructions where k_pedersen's binary tree does six ge_add of ~1,650 -
+// that tree was measured here too and lost at every cpw) and the sum is parked in LDS.  The encodings, the longest chain by far
+// (~250 dependent squarings each), are then made SIDE BY SIDE in the lanes of the block's first wave: 4 * cpw encodings for the instructions of
+// one, where k_pedersen spends a wave per encoding.
+// Precondition: count >= 1 (the caller launches nothing for a wave without commitments; count - 1 below would wrap).  The tail of the launch computes
+// commitment count - 1 again in the lanes past the end (every lane reaches every barrier; at most 4 * cpw - 1 redundant sums) and keeps its stores.
+__global__ void __launch_bounds__(256) k_bt_commit_v(const scm *__restrict__ v, const uint32_t *__restrict__ r, const ge_pniels *__restrict__ table /* [2][64][8] */,
+                                                     uint8_t *__restrict__ out, uint32_t count, uint32_t cpw) {
+    __shared__ ge_ext lds[256];
+    __shared__ ge_ext sums[16];
+    const uint32_t wv = threadIdx.x >> 6, win = threadIdx.x & 63u, per = 4u * cpw, first = blockIdx.x * per;
+    ge_ext *L = lds + 64 * wv;
+    for (uint32_t i = 0; i < cpw; i++) {
+        const uint32_t c = min(first + wv * cpw + i, count - 1u);
+        uint32_t vw[8], rw[8];
+        tt_biased_words(vw, v[c]);
+        {
+            uint64_t carry = 0;
+#pragma unroll
+            for (int k = 0; k < 8; k++) { const uint64_t t = (uint64_t)r[8 * (size_t)c + k] + 0x88888888ull + carry; rw[k] = (uint32_t)t; carry = t >> 32; }
+        }
+        const int32_t dv = (int32_t)((vw[win >> 3] >> (4 * (win & 7u))) & 15u) - 8, dr = (int32_t)((rw[win >> 3] >> (4 * (win & 7u))) & 15u) - 8;
+        ge_ext acc = ge_identity();
+        if (dv != 0) acc = ge_from_pniels_signed(table[(size_t)win * TT_MULTS + (dv < 0 ? -dv : dv) - 1], dv < 0);
+        if (dr != 0) {
+            const ge_pniels q = table[(size_t)(TT_WINDOWS + win) * TT_MULTS + (dr < 0 ? -dr : dr) - 1];
+            acc = dv != 0 ? ge_add_pniels_signed(acc, q, dr < 0) : ge_from_pniels_signed(q, dr < 0);
+        }
+        L[win] = acc;
+        __syncthreads();
+        const uint32_t cr = win & 3u, slot = win >> 2;
+        const fe *F = reinterpret_cast<const fe *>(L);
+        fe s = F[(4 * slot + 0) * 4 + cr];
+#pragma unroll 1
+        for (uint32_t k = 1; k < 4; k++) s = quad_add(s, F[(4 * slot + k) * 4 + cr], cr);
+        for (uint32_t d = 8; d > 0; d >>= 1) { const fe o = fe_shfl_down(s, 4u * d); s = quad_add(s, o, cr); }
+        if (slot == 0) reinterpret_cast<fe *>(sums + wv * cpw + i)[cr] = s;
+        __syncthreads();                                            // the wave's region is written again by its next commitment
+    }
+    // (the last barrier of the loop has published sums[0 .. per))
+    if (wv == 0 && win < per && first + win < count) ge_compress(out + 32 * (size_t)(first + win), sums[win]);
+}
 // extended points -> 32-byte encodings, one thread per point (what the host's h51::pt_compress gives)
 __global__ void __launch_bounds__(64) k_bt_compress(const ge_ext *__restrict__ in, uint8_t *__restrict__ out, uint32_t count) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

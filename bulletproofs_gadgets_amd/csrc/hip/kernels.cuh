@@ -20,6 +20,8 @@
 //       lockstep batch proving          (N <= 2^tt_orig_lg, k_batch.cuh) one launch per stage for every proof of a wave: the upload kernels on one block-diagonal
 //                                       matrix, k_bt_commit3(_finish), k_bt_compress, k_bt_exp, k_flatten, k_bt_poly_t, k_pedersen, k_bt_poly_eval, k_bt_factors,
 //                                       then k_bt_advance, k_bt_round, k_bt_finish, k_bt_compress per round and k_bt_fold_scalars
+//                                       k_bt_commit_v: the Pedersen commitments of a template wave's committed values, from the values the wave uploaded for its
+//                                       witness evaluation - one launch per wave (bpg_r1cs_prove_template_batch_commit)
 //       circuit templates               k_witness_eval (k_witness.cuh): a_L, a_R, a_O of a resident circuit from the committed values of a fresh witness, by interpreting the
 //                                       recorded witness program - one launch per level of its schedule, one lane per segment (replaces the host's assembly + upload)
 // The kernels live in k_points.cuh, k_scalars.cuh, k_ipa.cuh, k_verify.cuh, k_msm.cuh, k_merge.cuh, k_batch.cuh and k_witness.cuh, included at the end of this file in that order.

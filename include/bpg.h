@@ -81,7 +81,7 @@ typedef struct {
 
 /* ---------------------------------------------------------------------------------------------------- PART 1: hot path */
 /* ABI version of this header.  Rules: structs the CALLER allocates either carry a struct_size (bpg_config: fields are only ever added at the end and
- * read when struct_size covers them) or are frozen (bpg_timings, bpg_r1cs_instance, bpg_batch_item, bpg_template_item, bpg_witness_program, bpg_witness_hints, bpg_term, bpg_lc); a field never changes type or
+ * read when struct_size covers them) or are frozen (bpg_timings, bpg_r1cs_instance, bpg_batch_item, bpg_template_item, bpg_template_commit_item, bpg_witness_program, bpg_witness_hints, bpg_term, bpg_lc); a field never changes type or
  * meaning.  BPG_ABI_VERSION grows when something a version-7 host relies on is extended (a new field, a new flag value); functions ADDED since
  * version 7 (bpg_r1cs_prove_batch, the circuit-template calls) did not raise it: a host that needs one looks the symbol up (dlsym) and treats its
  * absence as "not supported".  A host checks bpg_abi_version() >= the BPG_ABI_VERSION it was compiled against. */
@@ -294,6 +294,33 @@ typedef struct {
     uint8_t *proof_out; uint64_t *proof_len;   /* in = capacity, out = bytes written */
 } bpg_template_item;
 bpg_status bpg_r1cs_prove_template_batch(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, const bpg_template_item *items, bpg_status *status_out);
+/* The same batch MAKING ITS OWN PEDERSEN COMMITMENTS: from (values, blindings, transcript before the commitments) to (commitments, proofs, transcripts) in
+ * one call, where bpg_r1cs_prove_template_batch has the caller create a transcript and a prover per item, commit m times (a launch and a round trip each)
+ * and append.  The frozen struct bpg_template_commit_item has the fields of bpg_template_item, with two differences: transcript_state comes IN as the state
+ * BEFORE the "V" appends - as Prover::new leaves it - and goes OUT as the state after the proof; commitments_out receives the item's m commitments (m x 32
+ * bytes, RFC 9496 encodings, in commit order).  Commitment j of item k is what bpg_pedersen_commit(ctx, 1, v + 32 j, v_blinding + 32 j, ...) writes: v with
+ * Scalar::from_bits semantics (any value below 2^255), the blinding reduced mod l.  The library appends the m encodings to the item's transcript in order, as
+ * append_point(b"V", ...), exactly as Prover::commit does; proof_out, *proof_len, the out-state and status_out[k] are then byte for byte those of
+ * bpg_r1cs_prove_template_batch given that post-commit state, whatever the batch around the item and however it is cut into waves.
+ * A caller that interleaves OTHER transcript appends between its commits (or commits in another order than v lists them) cannot use this call: all m
+ * appends happen back to back on the state handed in.  Such a caller commits itself and calls bpg_r1cs_prove_template_batch.
+ * Lockstep (the rule of bpg_r1cs_prove_template_batch): a wave's commitments are made in ONE launch from the values the wave has uploaded for its witness
+ * evaluation and read back with one copy; the witness evaluation runs while the host appends.  The other items (a template with N > 2^14, BPG_TT_ORIG_LG=0,
+ * BPG_FLAG_EXPANDED_BLINDING) get all their commitments from one Pedersen launch up front and are then proved one at a time as before.
+ * Whole-call and per-item refusals are those of bpg_r1cs_prove_template_batch, and a NULL commitments_out with m > 0 fails that item alone
+ * (BPG_ERR_INVALID_ARGUMENT).  For an item that fails, no commitment is written and its transcript is untouched; the other items are proved.  m = 0: the
+ * existing call (commitments_out is not looked at).  The template AFTERWARDS: as documented above.  (An addition to ABI version 7: look the symbol up.) */
+typedef struct {
+    const uint8_t *v;                     /* m x 32: committed values, as bpg_r1cs_assign takes them */
+    const uint8_t *param_values;          /* n_params x 32, in the order of param_rows */
+    uint8_t *transcript_state;            /* 203 B, in: BEFORE the "V" appends; out: after the proof */
+    const uint8_t *v_blinding;            /* m x 32 */
+    const uint8_t *rng_seed;              /* 32 B */
+    uint32_t flags;
+    uint8_t *proof_out; uint64_t *proof_len;   /* in = capacity, out = bytes written */
+    uint8_t *commitments_out;             /* m x 32: the commitments, in commit order */
+} bpg_template_commit_item;
+bpg_status bpg_r1cs_prove_template_batch_commit(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, const bpg_template_commit_item *items, bpg_status *status_out);
 /* TEST HOOKS, no device needed.  bpg_test_template_schedule: the checks of bpg_r1cs_upload_template and the schedule as JSON {"levels", "segments",
  * "max_levels", "seg_first": [segments + 1], "seg_level": [...], "level_segments": [...]}: segment s is multipliers [seg_first[s], seg_first[s+1]), one
  * device lane walks it in order, and everything it reads from another segment lies at a lower level.  bpg_test_template_eval: the device's interpreter
@@ -307,6 +334,8 @@ bpg_status bpg_test_template_eval(const bpg_r1cs_instance *inst, const bpg_witne
 bpg_status bpg_test_template_eval_batch(const bpg_r1cs_instance *inst, const bpg_witness_program *program, uint64_t count, const uint8_t *v,
                                         uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out);
 bpg_status bpg_test_circuit_handle(const bpg_r1cs_instance *inst, const bpg_witness_program *program, bpg_circuit **out);
+/* the append step of bpg_r1cs_prove_template_batch_commit alone: state_out = state_in after append_point(b"V", coms + 32 j) for j = 0 .. m - 1 */
+bpg_status bpg_test_append_commitments(const uint8_t state_in[BPG_TRANSCRIPT_STATE_BYTES], uint64_t m, const uint8_t *coms, uint8_t state_out[BPG_TRANSCRIPT_STATE_BYTES]);
 /* the same four for a program with hints (hints == NULL: the calls above) */
 bpg_status bpg_test_template_schedule_hinted(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, char *out, uint64_t cap);
 bpg_status bpg_test_template_eval_hinted(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, const uint8_t *v,
