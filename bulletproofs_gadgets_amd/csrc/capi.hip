@@ -90,8 +90,7 @@ std::vector<uint8_t> Prover::prove(uint64_t gens_capacity, const uint8_t rng_see
     if (stub_commitments_) throw DeviceError("this prover holds stub (hash) commitments: prove() is refused");      // (test hook; cannot be set on a prover with an engine)
     flush_commitments();
     engine_->gens_ensure(gens_capacity);
-    uint64_t N = 1; while (N < aL_.size()) N <<= 1;
-    if (gens_capacity < N) throw R1CSException(R1CSError::InvalidGeneratorsLength, "generator capacity below padded circuit size");
+    require_gens_capacity(gens_capacity, aL_.size());
     FlatCircuit f = flatten();
     DeviceCircuit *dc = engine_->upload(f);
     try {
@@ -255,8 +254,7 @@ bpg_status bpg_profile_report(bpg_ctx *ctx, char *out, uint64_t cap) {
 bpg_status bpg_bench_fe_mul(bpg_ctx *ctx, uint32_t iters, double *out) { return guard([&] { REQUIRE(ctx && out && iters); *out = ctx->engine->bench_fe_mul(iters); }); }
 
 uint64_t bpg_proof_size(uint64_t n, uint32_t flags) {
-    uint64_t N = 1, lg = 0; while (N < n) { N <<= 1; lg++; }
-    return ((flags & BPG_FLAG_COMPACT_1PHASE) ? 1 + 11 * 32 : 14 * 32) + (2 * lg + 2) * 32;
+    return ((flags & BPG_FLAG_COMPACT_1PHASE) ? 1 + 11 * 32 : 14 * 32) + (2 * (uint64_t)ceil_log2(n) + 2) * 32;
 }
 
 bpg_status bpg_r1cs_upload(bpg_ctx *ctx, const bpg_r1cs_instance *inst, bpg_circuit **out) {
@@ -363,8 +361,7 @@ bpg_status bpg_r1cs_prove_resident(bpg_ctx *ctx, bpg_circuit *c, uint8_t ts[BPG_
         REQUIRE(ctx && c && c->dc && ts && seed && proof_out && proof_len && (m == 0 || v_blinding));
         if (m != c->m) throw std::invalid_argument("prove: m does not match the uploaded circuit");
         if (*proof_len < bpg_proof_size(c->n, flags)) throw std::invalid_argument("prove: proof buffer too small");
-        uint64_t N = 1; while (N < c->n) N <<= 1;
-        if (ctx->engine->gens_capacity() < N) throw R1CSException(R1CSError::InvalidGeneratorsLength, "generator capacity below padded circuit size (call bpg_gens_ensure)");
+        require_gens_capacity(ctx->engine->gens_capacity(), c->n, " (call bpg_gens_ensure)");
         Transcript T = Transcript::from_state(ts);
         std::vector<Scalar> vb(m);
         for (uint64_t i = 0; i < m; i++) vb[i] = Scalar::from_bytes_mod_order(v_blinding + 32 * i);
@@ -388,6 +385,17 @@ bpg_status bpg_r1cs_prove(bpg_ctx *ctx, const bpg_r1cs_instance *inst, uint8_t t
     return s;
 }
 
+// what a batch call returns: every item's status, and the first failure with its message as the call's own
+static bpg_status batch_status(const std::vector<bpg_status> &st, const std::vector<std::string> &msg, bpg_status *status_out) {
+    bpg_status first = BPG_OK;
+    g_last_error.clear();
+    for (size_t k = 0; k < st.size(); k++) {
+        status_out[k] = st[k];
+        if (first == BPG_OK && st[k] != BPG_OK) { first = st[k]; g_last_error = "item " + std::to_string(k) + ": " + msg[k]; }
+    }
+    return first;
+}
+
 bpg_status bpg_r1cs_prove_batch(bpg_ctx *ctx, uint64_t count, const bpg_batch_item *items, bpg_status *status_out) {
     if (!ctx || (count && (!items || !status_out))) { g_last_error = "null or invalid argument: ctx, items and status_out"; return BPG_ERR_INVALID_ARGUMENT; }
     if (!count) { g_last_error.clear(); return BPG_OK; }
@@ -407,8 +415,7 @@ bpg_status bpg_r1cs_prove_batch(bpg_ctx *ctx, uint64_t count, const bpg_batch_it
             REQUIRE(it.transcript_state && it.rng_seed && it.proof_out && it.proof_len && (it.m == 0 || it.v_blinding));
             if (it.m != f.m) throw std::invalid_argument("prove: m does not match the uploaded circuit");
             if (*it.proof_len < bpg_proof_size(f.n, it.flags)) throw std::invalid_argument("prove: proof buffer too small");
-            uint64_t N = 1; while (N < f.n) N <<= 1;
-            if (ctx->engine->gens_capacity() < N) throw R1CSException(R1CSError::InvalidGeneratorsLength, "generator capacity below padded circuit size (call bpg_gens_ensure)");
+            require_gens_capacity(ctx->engine->gens_capacity(), f.n, " (call bpg_gens_ensure)");
             views[k] = f;
         });
         if (st[k] != BPG_OK) { msg[k] = g_last_error; continue; }
@@ -435,13 +442,7 @@ bpg_status bpg_r1cs_prove_batch(bpg_ctx *ctx, uint64_t count, const bpg_batch_it
         st[k] = bpg_r1cs_prove(ctx, it.inst, it.transcript_state, it.m, it.v_blinding, it.rng_seed, it.flags, it.proof_out, it.proof_len);
         if (st[k] != BPG_OK) msg[k] = g_last_error;
     }
-    bpg_status first = BPG_OK;
-    g_last_error.clear();
-    for (uint64_t k = 0; k < count; k++) {
-        status_out[k] = st[k];
-        if (first == BPG_OK && st[k] != BPG_OK) { first = st[k]; g_last_error = "item " + std::to_string(k) + ": " + msg[k]; }
-    }
-    return first;
+    return batch_status(st, msg, status_out);
 }
 
 // the whole call is refused before anything is written or launched; a handle without device state first, whatever else was passed
@@ -451,9 +452,10 @@ static bpg_status template_batch_refusal(bpg_ctx *ctx, bpg_circuit *tmpl, uint64
     if (!tmpl->is_template) { g_last_error = "prove_template_batch: the circuit is not a template (bpg_r1cs_upload_template)"; return BPG_ERR_INVALID_ARGUMENT; }
     return BPG_OK;
 }
-// count > 0 items that passed template_batch_refusal.  coms == nullptr: bpg_r1cs_prove_template_batch.  Else bpg_r1cs_prove_template_batch_commit: the
+// items that passed template_batch_refusal (none: BPG_OK, nothing touched).  coms == nullptr: bpg_r1cs_prove_template_batch.  Else bpg_r1cs_prove_template_batch_commit: the
 // transcript states are those BEFORE the "V" appends and coms[k] receives item k's m encodings (the caller checked m > 0)
 static bpg_status template_batch(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, const bpg_template_item *items, uint8_t *const *coms, bpg_status *status_out) {
+    if (!count) { g_last_error.clear(); return BPG_OK; }
     const uint64_t m = tmpl->m, n = tmpl->n, n_params = tmpl->n_params;
     std::vector<bpg_status> st(count, BPG_OK);
     std::vector<std::string> msg(count);
@@ -471,8 +473,7 @@ static bpg_status template_batch(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count
             REQUIRE(it.transcript_state && it.rng_seed && it.proof_out && it.proof_len && (m == 0 || it.v_blinding));
             if (coms && !coms[k]) throw std::invalid_argument("prove_template_batch_commit: an item without a commitment buffer");
             if (*it.proof_len < bpg_proof_size(n, it.flags)) throw std::invalid_argument("prove: proof buffer too small");
-            uint64_t N = 1; while (N < n) N <<= 1;
-            if (ctx->engine->gens_capacity() < N) throw R1CSException(R1CSError::InvalidGeneratorsLength, "generator capacity below padded circuit size (call bpg_gens_ensure)");
+            require_gens_capacity(ctx->engine->gens_capacity(), n, " (call bpg_gens_ensure)");
         });
         if (st[k] != BPG_OK) { msg[k] = g_last_error; continue; }
         if (!host_copy || !ctx->engine->lockstep_eligible(n, it.flags)) { route[k] = 2; continue; }
@@ -524,26 +525,18 @@ static bpg_status template_batch(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count
         if (coms) { std::memcpy(it.transcript_state, state, sizeof state); std::memcpy(coms[k], &scom[j * m * 32], m * 32); }
     }
     Engine::drop_witness(tmpl->dc);             // on either path: a caller never depends on which one its items took
-    bpg_status first = BPG_OK;
-    g_last_error.clear();
-    for (uint64_t k = 0; k < count; k++) {
-        status_out[k] = st[k];
-        if (first == BPG_OK && st[k] != BPG_OK) { first = st[k]; g_last_error = "item " + std::to_string(k) + ": " + msg[k]; }
-    }
-    return first;
+    return batch_status(st, msg, status_out);
 }
 
 bpg_status bpg_r1cs_prove_template_batch(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, const bpg_template_item *items, bpg_status *status_out) {
     const bpg_status s = template_batch_refusal(ctx, tmpl, count, items, status_out);
     if (s != BPG_OK) return s;
-    if (!count) { g_last_error.clear(); return BPG_OK; }
     return template_batch(ctx, tmpl, count, items, nullptr, status_out);
 }
 
 bpg_status bpg_r1cs_prove_template_batch_commit(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, const bpg_template_commit_item *items, bpg_status *status_out) {
     const bpg_status s = template_batch_refusal(ctx, tmpl, count, items, status_out);
     if (s != BPG_OK) return s;
-    if (!count) { g_last_error.clear(); return BPG_OK; }
     std::vector<bpg_template_item> plain(count);
     std::vector<uint8_t *> coms(count);
     for (uint64_t k = 0; k < count; k++) {
@@ -852,8 +845,7 @@ bpg_status bpg_verifier_verify(bpg_verifier *v, bpg_ctx *ctx, uint64_t gens_capa
     return guard([&] {
         REQUIRE(v && ctx && proof && seed);
         ctx->engine->gens_ensure(gens_capacity);
-        uint64_t N = 1; while (N < v->v->get_num_vars()) N <<= 1;
-        if (gens_capacity < N) throw R1CSException(R1CSError::InvalidGeneratorsLength, "generator capacity below padded circuit size");
+        require_gens_capacity(gens_capacity, v->v->get_num_vars());
         FlatCircuit f = v->v->flatten();
         DeviceCircuit *dc = ctx->engine->upload(f);
         R1CSError e;

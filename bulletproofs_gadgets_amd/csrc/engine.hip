@@ -25,6 +25,7 @@
 #include "engine.hpp"
 #include "host/fe51.hpp"
 #include "host/chain.hpp"
+#include "host/fiat_shamir.hpp"
 #include "hip/kernels.cuh"
 
 namespace bpg {
@@ -162,7 +163,6 @@ Scalar scalar_bits(const Scalar &s, uint32_t from, uint32_t count) {
     return r;
 }
 
-uint32_t ceil_log2(uint64_t x) { uint32_t l = 0; while ((1ULL << l) < x) l++; return l; }
 constexpr uint32_t TEMPLATE_HOST_COPY_LG = 14;     // templates up to this padded size keep a host copy of their rows (the widest lockstep proof: BPG_TT_ORIG_LG <= 14)
 
 // On-disk cache of the generator tables (reference src/bin/prover.rs:92 re-derives them on every run).  Opt-in:
@@ -495,6 +495,11 @@ struct Engine::Impl {
         while (!b->finished.load(std::memory_order_acquire)) std::this_thread::yield();
         const int c = b->cpu.load(std::memory_order_relaxed); if (c >= 0) last_chain_cpu = c;
     }
+    // done with a stream inside prove(): its worker stops at the next snapshot, and the stream leaves the alive list
+    void blind_release(const std::shared_ptr<BlindStream> &b) {
+        blind_stop(b);
+        for (auto it = blinds.begin(); it != blinds.end(); ++it) if (it->get() == b.get()) { blinds.erase(it); break; }
+    }
     void blind_cancel() {
         while (!blinds.empty()) { blind_retire(blinds.front()); blinds.pop_front(); }
     }
@@ -550,6 +555,20 @@ struct Engine::Impl {
             HIPCHK(hipEventRecord(stage_ev[slot], st));
         }
     }
+    // base^i for i < count into out, for up to three tables in one launch
+    struct PowTable { Scalar base; scm *out; uint64_t count; };
+    void exp_tables(std::initializer_list<PowTable> tabs) {
+        ExpTables E; std::memset(&E, 0, sizeof E);
+        uint32_t k = 0, lgmax = 0;
+        for (const PowTable &t : tabs) {
+            const uint32_t lgT = std::min<uint32_t>(ceil_log2(t.count), 16);
+            E.base[k] = to_scm(t.base); E.out[k] = t.out; E.count[k] = (uint32_t)t.count; E.lgT[k] = lgT; lgmax = std::max(lgmax, lgT); k++;
+        }
+        BPG_LAUNCH((*this), k_exp_table, dim3(cdiv(1u << lgmax, 256), k), dim3(256), E);
+    }
+    struct CscWork { uint32_t *counts, *starts, *cursor, *rowconst, *rowconst_start, *bsum; };
+    void transpose_csr(const uint64_t *rp, const uint32_t *tv, const uint32_t *tc, uint64_t q, uint64_t nmul, uint64_t m, const CscWork &W,
+                       uint64_t *col_ptr, uint32_t *ent_row, uint32_t *ent_coef, uint32_t *totals);
     void inner_product(Transcript &T, std::vector<uint8_t> &proof, uint64_t n, uint64_t N, const Scalar &yinv, const Scalar &u_ch, const Scalar &w,
                        const ge_niels *Gtab, const ge_niels *Htab, const ge_niels *Bn, ProveTimings *tm, double &t0);
 };
@@ -1216,6 +1235,26 @@ std::string Engine::test_msm(uint32_t nmsm, uint32_t nseg, const MsmSegSpec *seg
 }
 
 // ------------------------------------------------------------------------------------------------ circuit upload
+// CSR (by constraint) -> CSC (by variable) on the stream: q rows over nmul multipliers per side (columns [0, 3 nmul)) and m committed variables, the constant
+// terms as the last column.  W: counts, starts, cursor (3 nmul + m + 2 words each), rowconst, rowconst_start (q + 2 words), the scans' block sums.
+// totals[0] = first entry of the constant-terms column, totals[1] = entries written: the caller reads them back and checks that none was lost
+void Engine::Impl::transpose_csr(const uint64_t *rp, const uint32_t *tv, const uint32_t *tc, uint64_t q, uint64_t nmul, uint64_t m, const CscWork &W,
+                                 uint64_t *col_ptr, uint32_t *ent_row, uint32_t *ent_coef, uint32_t *totals) {
+    const uint64_t nvar = 3 * nmul + m;
+    const uint32_t nb1 = cdiv(nvar ? nvar : 1, SCAN_CHUNK), nb2 = cdiv(q ? q : 1, SCAN_CHUNK);
+    HIPCHK(hipMemsetAsync(W.counts, 0, (nvar + 1) * 4, st));
+    HIPCHK(hipMemsetAsync(W.rowconst, 0, (q + 1) * 4, st));
+    if (q) BPG_LAUNCH((*this), k_csc_count, dim3(cdiv(q, 256)), dim3(256), rp, tv, (uint32_t)q, (uint32_t)nmul, (uint32_t)m, W.counts, W.rowconst);
+    // exclusive scans: variable columns -> starts / cursor, constant terms per row -> rowconst_start
+    BPG_LAUNCH((*this), k_scan_blocksums, dim3(nb1), dim3(256), W.counts, (uint32_t)nvar, W.bsum);
+    BPG_LAUNCH((*this), k_scan_apply, dim3(nb1), dim3(256), W.counts, (uint32_t)nvar, W.bsum, W.starts, W.cursor);
+    BPG_LAUNCH((*this), k_scan_blocksums, dim3(nb2), dim3(256), W.rowconst, (uint32_t)q, W.bsum);
+    BPG_LAUNCH((*this), k_scan_apply, dim3(nb2), dim3(256), W.rowconst, (uint32_t)q, W.bsum, W.rowconst_start, W.counts /* scratch */);
+    BPG_LAUNCH((*this), k_csc_colptr, dim3(cdiv(nvar + 1, 256)), dim3(256), W.starts, W.rowconst_start, (uint32_t)nvar, (uint32_t)q, col_ptr, totals);
+    if (q) BPG_LAUNCH((*this), k_csc_fill, dim3(cdiv(q, 256)), dim3(256), rp, tv, tc, (uint32_t)q, (uint32_t)nmul, (uint32_t)m, W.cursor, W.rowconst_start,
+                      W.starts + nvar, ent_row, ent_coef);
+}
+
 void Engine::check_instance(const FlatView &c) {
     const uint64_t n = c.n, m = c.m, q = c.q, nnz = c.nnz, ncoef = c.ncoef;
     const bool has_witness = !(!c.aL && !c.aR && !c.aO && n > 0);
@@ -1238,22 +1277,11 @@ DeviceCircuit *Engine::upload(const FlatView &c) {
     HIPCHK(hipSetDevice(device_));
     Impl &I = *impl_;
     const uint64_t n = c.n, m = c.m, q = c.q, nnz = c.nnz, ncoef = c.ncoef;
+    check_instance(c);
     const bool has_witness = !(!c.aL && !c.aR && !c.aO && n > 0);
-    if (has_witness && n > 0 && (!c.aL || !c.aR || !c.aO)) throw std::invalid_argument("upload: witness vectors must hold n scalars");
-    if (!c.row_ptr || c.row_ptr[0] != 0 || c.row_ptr[q] != nnz || (nnz && (!c.term_var || !c.term_coef)) || (ncoef && !c.coef)) throw std::invalid_argument("upload: malformed CSR");
-    if (n >= (1u << 27)) throw std::invalid_argument("upload: too many multipliers");
-    // validation on the host (one sequential pass), transposition CSR (by constraint) -> CSC (by variable) on the device (k_csc_*);
+    // transposition CSR (by constraint) -> CSC (by variable) on the device (transpose_csr);
     // columns: [0,n) left, [n,2n) right, [2n,3n) output, [3n,3n+m) committed, 3n+m = the constant terms (only the verifier's w_c needs them)
     const uint64_t ncols = 3 * n + m + 1, nvar = ncols - 1;
-    if (q >= (1ull << 32) || nnz >= (1ull << 32) || ncols >= (1ull << 32)) throw std::invalid_argument("upload: circuit too large");
-    for (uint64_t k = 0; k < nnz; k++) {
-        const uint32_t pv = c.term_var[k], kind = pv >> 29, idx = pv & 0x1fffffffu;
-        if (c.term_coef[k] >= ncoef) throw std::invalid_argument("upload: coefficient index out of range");
-        if (kind <= 2) { if (idx >= n) throw std::invalid_argument("upload: multiplier index out of range"); }
-        else if (kind == 3) { if (idx >= m) throw std::invalid_argument("upload: committed index out of range"); }
-        else if (kind != 4) throw std::invalid_argument("upload: bad variable kind");
-    }
-    for (uint64_t r = 0; r < q; r++) if (c.row_ptr[r] > c.row_ptr[r + 1]) throw std::invalid_argument("upload: malformed CSR");
     DeviceCircuit *d = new DeviceCircuit();
     d->n = n; d->m = m; d->q = q; d->ncols = ncols; d->has_witness = has_witness;
     try {
@@ -1266,29 +1294,15 @@ DeviceCircuit *Engine::upload(const FlatView &c) {
             I.plain.ensure((q + 2) * 8 + 64);                                   // row_ptr
             I.counts.ensure((std::max<uint64_t>(nvar, q) + 2) * 4); I.starts.ensure((std::max<uint64_t>(nvar, q) + 2) * 4);
             I.cursor.ensure((std::max<uint64_t>(nvar, q) + 2) * 4); I.heavy.ensure((q + 2) * 4); I.tile_hist.ensure((q + 2) * 4 + 64);
-            const uint32_t nb1 = cdiv(nvar ? nvar : 1, SCAN_CHUNK), nb2 = cdiv(q ? q : 1, SCAN_CHUNK);
-            I.blocksum.ensure((size_t)(std::max(nb1, nb2) + 2) * 4);
+            I.blocksum.ensure((size_t)(std::max(cdiv(nvar ? nvar : 1, SCAN_CHUNK), cdiv(q ? q : 1, SCAN_CHUNK)) + 2) * 4);
+            I.extras.ensure(16 * sizeof(scm));
             uint32_t *tv = I.arena.as<uint32_t>(), *tc = tv + (nnz ? nnz : 1);
             uint64_t *rp = I.plain.as<uint64_t>();
-            uint32_t *rowconst = I.heavy.as<uint32_t>(), *rowconst_start = I.tile_hist.as<uint32_t>();
-            if (nnz) {
-                I.h2d(tv, c.term_var, nnz * 4);
-                I.h2d(tc, c.term_coef, nnz * 4);
-            }
-            I.h2d(rp, c.row_ptr, (q + 1) * 8);
-            HIPCHK(hipMemsetAsync(I.counts.p, 0, (nvar + 1) * 4, I.st));
-            HIPCHK(hipMemsetAsync(rowconst, 0, (q + 1) * 4, I.st));
-            if (q) BPG_LAUNCH(I, k_csc_count, dim3(cdiv(q, 256)), dim3(256), rp, tv, (uint32_t)q, (uint32_t)n, (uint32_t)m, I.counts.as<uint32_t>(), rowconst);
-            // exclusive scans: variable columns -> starts / cursor, constant terms per row -> rowconst_start
-            BPG_LAUNCH(I, k_scan_blocksums, dim3(nb1), dim3(256), I.counts.as<uint32_t>(), (uint32_t)nvar, I.blocksum.as<uint32_t>());
-            BPG_LAUNCH(I, k_scan_apply, dim3(nb1), dim3(256), I.counts.as<uint32_t>(), (uint32_t)nvar, I.blocksum.as<uint32_t>(), I.starts.as<uint32_t>(), I.cursor.as<uint32_t>());
-            BPG_LAUNCH(I, k_scan_blocksums, dim3(nb2), dim3(256), rowconst, (uint32_t)q, I.blocksum.as<uint32_t>());
-            BPG_LAUNCH(I, k_scan_apply, dim3(nb2), dim3(256), rowconst, (uint32_t)q, I.blocksum.as<uint32_t>(), rowconst_start, I.counts.as<uint32_t>() /* scratch */);
-            I.extras.ensure(16 * sizeof(scm));
             uint32_t *totals = reinterpret_cast<uint32_t *>(I.extras.as<scm>() + 8);
-            BPG_LAUNCH(I, k_csc_colptr, dim3(cdiv(nvar + 1, 256)), dim3(256), I.starts.as<uint32_t>(), rowconst_start, (uint32_t)nvar, (uint32_t)q, d->col_ptr.as<uint64_t>(), totals);
-            if (q) BPG_LAUNCH(I, k_csc_fill, dim3(cdiv(q, 256)), dim3(256), rp, tv, tc, (uint32_t)q, (uint32_t)n, (uint32_t)m, I.cursor.as<uint32_t>(), rowconst_start,
-                              I.starts.as<uint32_t>() + nvar, d->ent_row.as<uint32_t>(), d->ent_coef.as<uint32_t>());
+            if (nnz) { I.h2d(tv, c.term_var, nnz * 4); I.h2d(tc, c.term_coef, nnz * 4); }
+            I.h2d(rp, c.row_ptr, (q + 1) * 8);
+            I.transpose_csr(rp, tv, tc, q, n, m, {I.counts.as<uint32_t>(), I.starts.as<uint32_t>(), I.cursor.as<uint32_t>(), I.heavy.as<uint32_t>(), I.tile_hist.as<uint32_t>(), I.blocksum.as<uint32_t>()},
+                            d->col_ptr.as<uint64_t>(), d->ent_row.as<uint32_t>(), d->ent_coef.as<uint32_t>(), totals);
             HIPCHK(hipGetLastError());
             uint32_t h_tot[2] = {0, 0};
             HIPCHK(hipMemcpyAsync(h_tot, totals, 8, hipMemcpyDeviceToHost, I.st));
@@ -1333,38 +1347,34 @@ TemplatePlan Engine::plan_template(const FlatView &c, const WitnessProgramView &
     T.n_params = p.n_params; T.param_first = c.ncoef;
     return T;
 }
+namespace {
+// 32-byte scalars <-> the interpreter's scalars, as the test hooks below take and return them
+std::vector<scm> scalars_from_bytes(const uint8_t *b, size_t count) {
+    std::vector<scm> out(count ? count : 1);
+    for (size_t i = 0; i < count; i++) { uint32_t w[8]; std::memcpy(w, b + 32 * i, 32); out[i] = sc_from_words(w); }
+    return out;
+}
+void scalars_to_bytes(const std::vector<scm> &v, uint8_t *out) {
+    for (size_t i = 0; i < v.size(); i++) { uint32_t w[8]; sc_to_words(w, v[i]); std::memcpy(out + 32 * i, w, 32); }
+}
+}  // namespace
 // TEST HOOK (bpg_test_template_eval): the interpreter of k_witness.cuh compiled for the HOST, over the same packed program in the same level order
 void Engine::template_eval_host(const FlatView &c, const WitnessProgramView &p, const uint8_t *v, uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out) {
     const TemplatePlan T = plan_template(c, p);
     const PackedWitnessProgram &P = T.packed;
-    auto load = [](const uint8_t *b, size_t count) {
-        std::vector<scm> out(count ? count : 1);
-        for (size_t i = 0; i < count; i++) { uint32_t w[8]; std::memcpy(w, b + 32 * i, 32); out[i] = sc_from_words(w); }
-        return out;
-    };
-    const std::vector<scm> coef = load(c.coef, c.ncoef), vv = load(v, c.m);
+    const std::vector<scm> coef = scalars_from_bytes(c.coef, c.ncoef), vv = scalars_from_bytes(v, c.m);
     std::vector<scm> aL(c.n), aR(c.n), aO(c.n);
     for (const WitnessSegment &s : P.segs) witness_eval_segment(s.first, s.count, P.stream.data() + s.stream, coef.data(), vv.data(), aL.data(), aR.data(), aO.data());
-    for (size_t i = 0; i < c.n; i++) {
-        uint32_t w[8];
-        sc_to_words(w, aL[i]); std::memcpy(aL_out + 32 * i, w, 32);
-        sc_to_words(w, aR[i]); std::memcpy(aR_out + 32 * i, w, 32);
-        sc_to_words(w, aO[i]); std::memcpy(aO_out + 32 * i, w, 32);
-    }
+    scalars_to_bytes(aL, aL_out); scalars_to_bytes(aR, aR_out); scalars_to_bytes(aO, aO_out);
 }
 
 // TEST HOOK (bpg_test_template_eval_batch): k_witness_eval_batch on the host - one pass per level, per segment every item, into the wave layout
 void Engine::template_eval_batch_host(const FlatView &c, const WitnessProgramView &p, uint64_t count, const uint8_t *v, uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out) {
     const TemplatePlan T = plan_template(c, p);
     const PackedWitnessProgram &P = T.packed;
-    const uint64_t N = 1ull << ceil_log2(c.n);
+    const uint64_t N = padded_size(c.n);
     if (count > (1ull << 26) / N) throw std::invalid_argument("template_eval_batch: too many items");
-    auto load = [](const uint8_t *b, size_t cnt) {
-        std::vector<scm> out(cnt ? cnt : 1);
-        for (size_t i = 0; i < cnt; i++) { uint32_t w[8]; std::memcpy(w, b + 32 * i, 32); out[i] = sc_from_words(w); }
-        return out;
-    };
-    const std::vector<scm> coef = load(c.coef, c.ncoef), vv = load(v, count * c.m);
+    const std::vector<scm> coef = scalars_from_bytes(c.coef, c.ncoef), vv = scalars_from_bytes(v, count * c.m);
     std::vector<scm> aL(count * N, sc_zero()), aR(count * N, sc_zero()), aO(count * N, sc_zero());
     const std::vector<uint32_t> &lp = T.schedule.level_ptr;
     for (size_t l = 0; l + 1 < lp.size(); l++)
@@ -1372,12 +1382,7 @@ void Engine::template_eval_batch_host(const FlatView &c, const WitnessProgramVie
             for (uint64_t k = 0; k < count; k++)
                 witness_eval_segment(P.segs[s].first, P.segs[s].count, P.stream.data() + P.segs[s].stream, coef.data(), vv.data() + k * c.m,
                                      aL.data() + k * N, aR.data() + k * N, aO.data() + k * N);
-    for (size_t i = 0; i < count * N; i++) {
-        uint32_t w[8];
-        sc_to_words(w, aL[i]); std::memcpy(aL_out + 32 * i, w, 32);
-        sc_to_words(w, aR[i]); std::memcpy(aR_out + 32 * i, w, 32);
-        sc_to_words(w, aO[i]); std::memcpy(aO_out + 32 * i, w, 32);
-    }
+    scalars_to_bytes(aL, aL_out); scalars_to_bytes(aR, aR_out); scalars_to_bytes(aO, aO_out);
 }
 
 DeviceCircuit *Engine::upload_template(const FlatView &c, const TemplatePlan &T) {
@@ -1402,8 +1407,7 @@ void Engine::assign(DeviceCircuit *d, const uint8_t *v, const uint8_t *param_val
     Impl &I = *impl_;
     if (!d || !d->is_template) throw std::invalid_argument("assign: the circuit is not a template (bpg_r1cs_upload_template)");
     // the previous witness is gone from here on: a failure below must not leave its caches behind either
-    d->has_witness = false;
-    d->merge_tried = false; d->mI.groups = d->mI.skipped = 0; d->mO.groups = d->mO.skipped = 0;   // the equal-scalar sets belong to the witness they were built from
+    drop_witness(d);                                // (the equal-scalar sets belong to the witness they were built from)
     const uint64_t cnt[2] = {d->m, d->n_params};
     const uint8_t *src[2] = {v, param_values};
     scm *dst[2] = {d->wit_v.as<scm>(), d->coef.as<scm>() + d->param_first};
@@ -1545,9 +1549,8 @@ void Engine::Impl::inner_product(Transcript &T, std::vector<uint8_t> &proof, uin
             I.wait_stream();
             h51::pt_compress(lr, h51::pt_from_device(hp)); h51::pt_compress(lr + 32, h51::pt_from_device(hp + 32));
             lap(tm ? &tm->ipa_msm : nullptr);
-            T.append_point("L", lr); T.append_point("R", lr + 32);
             proof.insert(proof.end(), lr, lr + 64);
-            tt_u = T.challenge_scalar("u"); tt_uinv = tt_u.invert();
+            tt_u = fs_ipa_round(T, lr, lr + 32); tt_uinv = tt_u.invert();
             tt_j++;
             mcur = h;
             if (round + 1 == lgN) {   // last round: only the scalar fold remains
@@ -1592,9 +1595,8 @@ void Engine::Impl::inner_product(Transcript &T, std::vector<uint8_t> &proof, uin
         I.wait_stream();
         { const std::vector<h51::pt> LR = I.msm_points(tk); h51::pt_compress(lr, LR[0]); h51::pt_compress(lr + 32, LR[1]); }
         lap(tm ? &tm->ipa_msm : nullptr);
-        T.append_point("L", lr); T.append_point("R", lr + 32);
         proof.insert(proof.end(), lr, lr + 64);
-        const Scalar u = T.challenge_scalar("u"), uinv = u.invert();
+        const Scalar u = fs_ipa_round(T, lr, lr + 32), uinv = u.invert();
         g_us.push_back(u);
         {   // fold a, b and extend the coefficient tables cG, cH (2^g_j -> 2^(g_j+1) entries)
             scm *c1 = I.grp_c.as<scm>() + (size_t)(g_cur ^ 1u) * 2 * GRP_STRIDE;
@@ -1872,10 +1874,9 @@ std::vector<uint8_t> Engine::prove(DeviceCircuit *c, Transcript &T, const std::v
     const uint64_t n = c->n, m = c->m, q = c->q;
     if (v_blinding.size() != m) throw std::invalid_argument("prove: need one blinding factor per committed variable");
     if (!c->has_witness) throw R1CSException(R1CSError::MissingAssignment, "prove: the uploaded circuit carries no assignments (verifier-side instance)");
-    uint64_t N = 1; while (N < n) N <<= 1;
+    const uint64_t N = padded_size(n);
     const uint32_t lgN = ceil_log2(N);
-    if (gens_cap_ < N) throw R1CSException(R1CSError::InvalidGeneratorsLength, "generator capacity below padded circuit size");
-    const bool compact = flags & 1u, no_1phase = flags & 2u;
+    require_gens_capacity(gens_cap_, n);
     const double t_begin = now_ms();
     double t0 = t_begin;
     auto lap = [&](double *slot) { if (tm) { I.wait_stream(); double t1 = now_ms(); *slot += t1 - t0; t0 = t1; } };
@@ -1965,6 +1966,11 @@ std::vector<uint8_t> Engine::prove(DeviceCircuit *c, Transcript &T, const std::v
             tk_s[nparts++] = I.msm(S, 1);
         }
     };
+    // the slab on the device may still hold an earlier proof's draws: s_L, s_R must never be built from a stream whose upload failed
+    auto upload_failed = [&] {
+        const int uerr = bs->err.load(std::memory_order_acquire);
+        if (uerr) { I.blind_release(bs); throw DeviceError(std::string("upload of the blinding draws failed: ") + hipGetErrorString((hipError_t)uerr)); }
+    };
     if (expanded) {     // (include/bpg.h): one draw K, the 2n scalars are expanded from it on the device
         uint8_t msg[80]; std::memset(msg, 0, sizeof msg);
         std::memcpy(msg, "bpg blinding v1", 15);
@@ -1984,11 +1990,7 @@ std::vector<uint8_t> Engine::prove(DeviceCircuit *c, Transcript &T, const std::v
                 if (bs->finished.load(std::memory_order_acquire) && bs->uploaded_blocks.load(std::memory_order_acquire) < nblk) break;     // stopped short: handled below
                 std::this_thread::sleep_for(std::chrono::microseconds(40));
             }
-            if (const int uerr = bs->err.load(std::memory_order_acquire)) {
-                Impl::blind_stop(bs);
-                for (auto it = I.blinds.begin(); it != I.blinds.end(); ++it) if (it->get() == bs.get()) { I.blinds.erase(it); break; }
-                throw DeviceError(std::string("upload of the blinding draws failed: ") + hipGetErrorString((hipError_t)uerr));
-            }
+            upload_failed();
             if (bs->uploaded_blocks.load(std::memory_order_acquire) < nblk) throw DeviceError("the blinding stream ended before its draws were uploaded");
             for (uint64_t k = 0; k < nblk; k++) HIPCHK(hipStreamWaitEvent(st, (*static_cast<std::vector<hipEvent_t> *>(bs->ev))[k], 0));
             BPG_LAUNCH(I, k_sc_from_wide, dim3(cdiv(2 * n, 256)), dim3(256), reinterpret_cast<const uint32_t *>(bs->d_raw), sL, (uint32_t)(2 * n), I.stale_flag.as<uint32_t>());
@@ -2010,12 +2012,7 @@ std::vector<uint8_t> Engine::prove(DeviceCircuit *c, Transcript &T, const std::v
                 // stream, then make this stream wait for its event - no host copy, no copy on this stream
                 const uint64_t k = i / Impl::BlindStream::UP;
                 while (bs->uploaded_blocks.load(std::memory_order_acquire) <= k) std::this_thread::sleep_for(std::chrono::microseconds(40));
-                if (const int uerr = bs->err.load(std::memory_order_acquire)) {
-                    // the slab on the device may still hold an earlier proof's draws: s_L, s_R must never be built from it
-                    Impl::blind_stop(bs);
-                    for (auto it = I.blinds.begin(); it != I.blinds.end(); ++it) if (it->get() == bs.get()) { I.blinds.erase(it); break; }
-                    throw DeviceError(std::string("upload of the blinding draws failed: ") + hipGetErrorString((hipError_t)uerr));
-                }
+                upload_failed();
                 HIPCHK(hipStreamWaitEvent(st, (*static_cast<std::vector<hipEvent_t> *>(bs->ev))[k], 0));
             } else {
                 rng.fill_draws64(raw + 64 * i, cnt);
@@ -2033,8 +2030,7 @@ std::vector<uint8_t> Engine::prove(DeviceCircuit *c, Transcript &T, const std::v
         if (rem) { std::vector<uint8_t> skip(rem * 64); rng.fill_draws64(skip.data(), rem); }
         // done with the stream: the worker stops at its next snapshot and moves on to the next queued one; the pinned slab stays allocated
         // (the queued uploads still read it) and is not handed out again before this prove() has synchronised the stream
-        Impl::blind_stop(bs);
-        for (auto it = I.blinds.begin(); it != I.blinds.end(); ++it) if (it->get() == bs.get()) { I.blinds.erase(it); break; }
+        I.blind_release(bs);
         { const int c = bs->cpu.load(std::memory_order_relaxed); if (c >= 0) I.last_chain_cpu = c; }
         bs.reset();
     }
@@ -2073,16 +2069,9 @@ std::vector<uint8_t> Engine::prove(DeviceCircuit *c, Transcript &T, const std::v
     lap(tm ? &tm->msm_s : nullptr);
 
     std::vector<uint8_t> proof;
-    proof.reserve(14 * 32 + (2 * lgN + 2) * 32 + 1);
-    if (compact) proof.push_back(0);
-    proof.insert(proof.end(), pts, pts + 96);
-    T.append_point("A_I1", pts); T.append_point("A_O1", pts + 32); T.append_point("S1", pts + 64);
-    if (!no_1phase) T.r1cs_1phase_domain_sep();
-    const uint8_t ident[32] = {0};
-    T.append_point("A_I2", ident); T.append_point("A_O2", ident); T.append_point("S2", ident);
-    if (!compact) proof.insert(proof.end(), 96, 0);
-
-    const Scalar y = T.challenge_scalar("y"), z = T.challenge_scalar("z");
+    proof_open(proof, lgN, flags, pts);
+    Scalar y, z;
+    fs_commitments(T, pts, nullptr, flags, y, z);
     const Scalar yinv = y.invert();
 
     // ---- powers, flattened weights, t-polynomial
@@ -2092,16 +2081,7 @@ std::vector<uint8_t> Engine::prove(DeviceCircuit *c, Transcript &T, const std::v
     const size_t b_w = Impl::al256((c->ncols ? c->ncols : 1) * sizeof(scm)), b_z = Impl::al256((q + 2) * sizeof(scm)), b_y = Impl::al256(N * sizeof(scm));
     I.arena.ensure(b_w + b_z + b_y);
     scm *const wAll_p = reinterpret_cast<scm *>(I.arena_at(0)), *const zpow_p = reinterpret_cast<scm *>(I.arena_at(b_w)), *const ypow_p = reinterpret_cast<scm *>(I.arena_at(b_w + b_z));
-    {   // y^i, y^-i, z^j: one launch
-        ExpTables E; std::memset(&E, 0, sizeof E);
-        uint32_t k = 0, lgmax = 0;
-        auto add = [&](const Scalar &base, scm *out, uint64_t count) {
-            uint32_t lgT = ceil_log2(count); if (lgT > 16) lgT = 16;
-            E.base[k] = to_scm(base); E.out[k] = out; E.count[k] = (uint32_t)count; E.lgT[k] = lgT; lgmax = std::max(lgmax, lgT); k++;
-        };
-        add(y, ypow_p, N); add(yinv, I.yinvpow.as<scm>(), N); add(z, zpow_p, q + 1);
-        BPG_LAUNCH(I, k_exp_table, dim3(cdiv(1u << lgmax, 256), k), dim3(256), E);
-    }
+    I.exp_tables({{y, ypow_p, N}, {yinv, I.yinvpow.as<scm>(), N}, {z, zpow_p, q + 1}});      // y^i, y^-i, z^j: one launch
     if (c->ncols > 1)      // every column but the last (constant terms: verifier only)
         BPG_LAUNCH(I, k_flatten, dim3(cdiv(c->ncols - 1, 256)), dim3(256), c->col_ptr.as<uint64_t>(), c->ent_row.as<uint32_t>(),
                            c->ent_coef.as<uint32_t>(), c->coef.as<scm>(), zpow_p, wAll_p, (uint32_t)(c->ncols - 1), (uint32_t)(3 * n));
@@ -2124,24 +2104,15 @@ std::vector<uint8_t> Engine::prove(DeviceCircuit *c, Transcript &T, const std::v
     }
     Scalar t[7], tb[7];
     for (int k = 0; k < 6; k++) t[k + 1] = from_scm(h_t[k]);
-    tb[1] = rng.random_scalar(); tb[3] = rng.random_scalar(); tb[4] = rng.random_scalar(); tb[5] = rng.random_scalar(); tb[6] = rng.random_scalar();
-    {   // T_1, T_3, T_4, T_5, T_6 = t_k * B + tau_k * B_blinding
-        uint8_t vv[5 * 32], rr[5 * 32], out[5 * 32];
-        const int idx[5] = {1, 3, 4, 5, 6};
-        for (int k = 0; k < 5; k++) { t[idx[k]].to_bytes(vv + 32 * k); tb[idx[k]].to_bytes(rr + 32 * k); }
-        pedersen_commit(5, vv, rr, out);
-        static const char *labels[5] = {"T_1", "T_3", "T_4", "T_5", "T_6"};
-        for (int k = 0; k < 5; k++) T.append_point(labels[k], out + 32 * k);
-        proof.insert(proof.end(), out, out + 160);
-    }
-    const Scalar u_ch = T.challenge_scalar("u"), x = T.challenge_scalar("x");
-    for (uint64_t j = 0; j < m; j++) tb[2] += from_scm(h_wV[j]) * v_blinding[j];
-    Scalar tx, txb;
-    for (int k = 6; k >= 1; k--) { tx = (tx + t[k]) * x; txb = (txb + tb[k]) * x; }
-    const Scalar eb = x * (ib + x * (ob + x * sb));
-    T.append_scalar("t_x", tx); T.append_scalar("t_x_blinding", txb); T.append_scalar("e_blinding", eb);
-    { uint8_t b[96]; tx.to_bytes(b); txb.to_bytes(b + 32); eb.to_bytes(b + 64); proof.insert(proof.end(), b, b + 96); }
-    const Scalar w = T.challenge_scalar("w");
+    Scalar u_ch, x;
+    uint8_t vv[5 * 32], rr[5 * 32], tcom[5 * 32];       // T_1, T_3, T_4, T_5, T_6 = t_k * B + tau_k * B_blinding
+    poly_commit_inputs(rng, t, tb, vv, rr);
+    pedersen_commit(5, vv, rr, tcom);
+    fs_poly_commitments(T, tcom, u_ch, x);
+    proof.insert(proof.end(), tcom, tcom + 160);
+    const PolyAtX px = poly_at_x(t, tb, [&](uint64_t j) { return from_scm(h_wV[j]); }, v_blinding, ib, ob, sb, x);
+    const Scalar w = fs_poly_scalars(T, px.tx, px.txb, px.eb);
+    proof_poly_scalars(proof, px);
 
     I.lv.ensure(N * sizeof(scm)); I.rv.ensure(N * sizeof(scm));
     BPG_LAUNCH(I, k_poly_eval, dim3(cdiv(N, 256)), dim3(256), c->aL.as<scm>(), c->aR.as<scm>(), c->aO.as<scm>(), sL, sR, wL, wR, wO,
@@ -2243,34 +2214,15 @@ void Engine::prove_template_batch(DeviceCircuit *d, size_t count, ProveItem *ite
     prove_batch(count, items, d, commit && d->m);
 }
 
-// tmpl != nullptr: every item is a fresh witness of that template (flat = its host copy; values, params per item).  commit (a template with m > 0): the
-// transcripts come in as they are BEFORE the commitments; every wave makes its own (k_bt_commit_v) and appends them before anything is drawn
-void Engine::prove_batch(size_t count, ProveItem *items, DeviceCircuit *tmpl, bool commit) {
-    if (!count) return;
-    HIPCHK(hipSetDevice(device_));
-    Impl &I = *impl_;
-    ProvingGuard in_flight(device_);                // the whole batch is one proof in flight: its kernel variants are chosen once
-    I.shared_now = I.shared_variants();
-    const uint32_t quad = I.shared_now ? 0u : 1u;
-    uint32_t lgmax = 0;
-    for (size_t k = 0; k < count; k++) {
-        if (!lockstep_eligible(items[k].flat->n, items[k].flags)) throw std::logic_error("prove_batch: an item that is not lockstep-eligible");
-        lgmax = std::max(lgmax, ceil_log2(items[k].flat->n));
-    }
-    if (gens_cap_ < (1ull << lgmax)) throw R1CSException(R1CSError::InvalidGeneratorsLength, "generator capacity below padded circuit size");
-    // ONE set of window tables of the original generators, for the largest N of the batch (an item of smaller N reads the first N rows of each half)
-    const ge_niels *Gtab = I.gens.as<ge_niels>(), *Htab = Gtab + gens_cap_;
-    const uint32_t M0T = 1u << lgmax;
-    I.tt_build(Gtab, Htab, I.bases.as<ge_niels>(), M0T, true);
-    const ge_pniels *table = I.tt_table_p, *tabB = I.ped_table.as<ge_pniels>(), *tabBb = tabB + (size_t)TT_WINDOWS * TT_MULTS;
-    StageThreads pool(std::min<uint32_t>(batch_host_threads(), (uint32_t)std::max<size_t>(1, count / 8)));
-
-    // groups of equal lg N, waves of at most batch_wave_mb of device state (and index ranges the 29-bit variable field of the upload holds)
+namespace {
+using ProveItem = Engine::ProveItem;
+// ---- wave planning: groups of equal lg N, waves of at most `cap` bytes of device state (and index ranges the 29-bit variable field of the upload holds)
+std::vector<std::vector<ProveItem *>> plan_waves(size_t count, ProveItem *items, uint64_t cap) {
     std::vector<size_t> order(count);
     for (size_t k = 0; k < count; k++) order[k] = k;
     std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return ceil_log2(items[a].flat->n) < ceil_log2(items[b].flat->n); });
-    const uint64_t cap = (uint64_t)I.batch_wave_mb << 20;
     auto item_bytes = [&](const FlatView &f, uint64_t N) { return 28 * N * 32 + f.q * 48 + f.nnz * 24 + f.ncoef * 64 + f.m * 32 + 1024; };
+    std::vector<std::vector<ProveItem *>> waves;
     for (size_t g0 = 0; g0 < count;) {
         const uint32_t lgN = ceil_log2(items[order[g0]].flat->n);
         const uint64_t N = 1ull << lgN;
@@ -2280,103 +2232,153 @@ void Engine::prove_batch(size_t count, ProveItem *items, DeviceCircuit *tmpl, bo
             if (g1 > g0 && (bytes + b > cap || (g1 - g0 + 1) * N > (1ull << 26) || g1 - g0 >= 16384)) break;
             bytes += b; g1++;
         }
-        const size_t K = g1 - g0;
-        std::vector<ProveItem *> W(K);
-        for (size_t k = 0; k < K; k++) W[k] = &items[order[g0 + k]];
-        g0 = g1;
-        const uint64_t KN = K * N;
+        waves.emplace_back();
+        for (; g0 < g1; g0++) waves.back().push_back(&items[order[g0]]);
+    }
+    return waves;
+}
 
-        // ---- offsets of every item in the packed (block-diagonal) instance
-        std::vector<uint64_t> rbase(K + 1), ebase(K + 1), cbase(K + 1), vbase(K + 1);
+// ---- where everything of one wave lives: the items' offsets in the packed (block-diagonal) instance, the pinned area and the device area.
+// from_values: the witness area holds the items' committed values (a template wave) where a host-assembled wave uploads 3 K N witness scalars;
+// commit: the reduced blindings of the commitments lie right behind them, and the two go up ahead of the rest (up_begin)
+struct WaveLayout {
+    size_t K; uint32_t lgN; uint64_t N, KN, qT, nnzT, ncoefT, mT, ncols, nvar, qmax = 0;
+    std::vector<uint64_t> rbase, ebase, cbase, vbase;
+    uint32_t nblkC, nblkR, pblocks;
+    // pinned upload area [0, up_bytes), mirrored 1:1 on the device, then the read-back area
+    size_t o_wit, o_vbl, o_coef, o_raw, o_rp, o_tv, o_tc, o_nk, o_qk, o_rb, o_bsc, o_bases, up_begin, up_bytes, o_back, pin_bytes;
+    // device, behind the mirror: the scalar vectors, the transposed matrix and the workspace
+    size_t d_abc, d_coef, d_sLR, d_ypow, d_yinv, d_z, d_w, d_lv, d_rv, d_fG, d_fH, d_c, d_tpart, d_t, d_ab, d_colptr, d_erow, d_ecoef, d_counts, d_starts, d_cursor,
+           d_rowc, d_rowcs, d_bsum, d_part, d_pts, d_comp, d_misc, d_v, d_vcom, dev_bytes;
+    WaveLayout(const std::vector<ProveItem *> &W, bool from_values, bool commit)
+        : K(W.size()), lgN(ceil_log2(W[0]->flat->n)), N(1ull << lgN), KN(K * N), rbase(K + 1), ebase(K + 1), cbase(K + 1), vbase(K + 1) {
         for (size_t k = 0; k < K; k++) {
             const FlatView &f = *W[k]->flat;
             rbase[k + 1] = rbase[k] + f.q; ebase[k + 1] = ebase[k] + f.nnz; cbase[k + 1] = cbase[k] + f.ncoef; vbase[k + 1] = vbase[k] + f.m;
+            qmax = std::max<uint64_t>(qmax, f.q);
         }
-        const uint64_t qT = rbase[K], nnzT = ebase[K], ncoefT = cbase[K], mT = vbase[K];
-        const uint64_t ncols = 3 * KN + mT + 1, nvar = ncols - 1;
+        qT = rbase[K]; nnzT = ebase[K]; ncoefT = cbase[K]; mT = vbase[K];
+        ncols = 3 * KN + mT + 1; nvar = ncols - 1;
         if (qT >= (1ull << 32) || nnzT >= (1ull << 32) || ncols >= (1ull << 29)) throw std::invalid_argument("prove_batch: wave too large");
-
-        // ---- pinned upload area (mirrored 1:1 on the device) and the read-back area
+        nblkC = cdiv(16 * N, 256); nblkR = cdiv(8 * N, 256); pblocks = std::min<uint32_t>(cdiv(N, 256), 1024);
         size_t off = 0;
-        auto take = [&](size_t b) { const size_t o = off; off += Impl::al256(b ? b : 1); return o; };
-        // (a template wave uploads its committed values where a host-assembled wave uploads 3 K N witness scalars)
-        // (... and, when it makes the commitments, their reduced blindings right behind: the two go up ahead of the rest)
-        const size_t o_wit = take(tmpl ? mT * 32 : 3 * KN * 32), o_vbl = take(commit ? mT * 32 : 0), o_coef = take(ncoefT * 32), o_raw = take(2 * KN * 64), o_rp = take((qT + 1) * 8), o_tv = take(nnzT * 4),
-                     o_tc = take(nnzT * 4), o_nk = take(K * 4), o_qk = take(K * 4), o_rb = take(K * 4), o_bsc = take(K * BSC * 32), o_bases = take(K * 3 * 32);
-        const size_t up_bytes = off;
-        const size_t o_back = take(std::max<size_t>(K * 3 * 32 + 64, (6 * K + mT + 1) * 32 + 64));
-        I.bt_pin.ensure(off);
-        uint8_t *pin = I.bt_pin.as<uint8_t>();
-        // device: the mirror, then the scalar vectors, the transposed matrix and the workspace
-        const uint32_t nblkC = cdiv(16 * N, 256), nblkR = cdiv(8 * N, 256), pblocks = std::min<uint32_t>(cdiv(N, 256), 1024);
-        const uint32_t nb1 = cdiv(nvar, SCAN_CHUNK), nb2 = cdiv(qT ? qT : 1, SCAN_CHUNK);
-        const size_t d_abc = take(3 * KN * 32), d_coef = take(ncoefT * 32), d_sLR = take(2 * KN * 32), d_ypow = take(KN * 32), d_yinv = take(KN * 32),
-                     d_z = take((qT + 1) * 32), d_w = take(ncols * 32), d_lv = take(KN * 32), d_rv = take(KN * 32), d_fG = take(KN * 32), d_fH = take(KN * 32),
-                     d_c = take(4 * KN * 32), d_tpart = take((size_t)pblocks * 6 * K * 32), d_t = take(6 * K * 32), d_ab = take(2 * K * 32),
-                     d_colptr = take((ncols + 1) * 8), d_erow = take(nnzT * 4), d_ecoef = take(nnzT * 4), d_counts = take((nvar + 2) * 4),
-                     d_starts = take((nvar + 2) * 4), d_cursor = take((nvar + 2) * 4), d_rowc = take((qT + 2) * 4), d_rowcs = take((qT + 2) * 4),
-                     d_bsum = take((std::max(nb1, nb2) + 2) * 4), d_part = take((size_t)K * std::max(3 * nblkC, 2 * nblkR) * sizeof(ge_ext)),
-                     d_pts = take(K * 3 * sizeof(ge_ext)), d_comp = take(K * 3 * 32), d_misc = take(64), d_v = take(tmpl ? mT * 32 : 0),
-                     d_vcom = take(commit ? mT * 32 : 0);
-        I.bt_dev.ensure(off);
-        uint8_t *dev = I.bt_dev.as<uint8_t>();
-        auto D = [&](size_t o) { return dev + o; };
-        scm *aL = reinterpret_cast<scm *>(D(d_abc)), *aR = aL + KN, *aO = aR + KN, *sL = reinterpret_cast<scm *>(D(d_sLR)), *sR = sL + KN;
-        scm *ypow = reinterpret_cast<scm *>(D(d_ypow)), *yinvpow = reinterpret_cast<scm *>(D(d_yinv)), *wAll = reinterpret_cast<scm *>(D(d_w));
-        scm *lv = reinterpret_cast<scm *>(D(d_lv)), *rv = reinterpret_cast<scm *>(D(d_rv)), *bsc = reinterpret_cast<scm *>(D(o_bsc));
-        uint32_t *stale = reinterpret_cast<uint32_t *>(D(d_misc)), *totals = stale + 4;
-        const uint32_t *nk = reinterpret_cast<const uint32_t *>(D(o_nk));
-        scm *h_bsc = reinterpret_cast<scm *>(pin + o_bsc);
+        auto take = [&](size_t b) { const size_t o = off; off += Engine::Impl::al256(b ? b : 1); return o; };
+        o_wit = take(from_values ? mT * 32 : 3 * KN * 32); o_vbl = take(commit ? mT * 32 : 0); o_coef = take(ncoefT * 32); o_raw = take(2 * KN * 64);
+        o_rp = take((qT + 1) * 8); o_tv = take(nnzT * 4); o_tc = take(nnzT * 4); o_nk = take(K * 4); o_qk = take(K * 4); o_rb = take(K * 4);
+        o_bsc = take(K * BSC * 32); o_bases = take(K * 3 * 32);
+        up_begin = commit ? o_coef : 0; up_bytes = off;
+        o_back = take(std::max<size_t>(K * 3 * 32 + 64, (6 * K + mT + 1) * 32 + 64));
+        pin_bytes = off;
+        d_abc = take(3 * KN * 32); d_coef = take(ncoefT * 32); d_sLR = take(2 * KN * 32); d_ypow = take(KN * 32); d_yinv = take(KN * 32);
+        d_z = take((qT + 1) * 32); d_w = take(ncols * 32); d_lv = take(KN * 32); d_rv = take(KN * 32); d_fG = take(KN * 32); d_fH = take(KN * 32);
+        d_c = take(4 * KN * 32); d_tpart = take((size_t)pblocks * 6 * K * 32); d_t = take(6 * K * 32); d_ab = take(2 * K * 32);
+        d_colptr = take((ncols + 1) * 8); d_erow = take(nnzT * 4); d_ecoef = take(nnzT * 4); d_counts = take((nvar + 2) * 4);
+        d_starts = take((nvar + 2) * 4); d_cursor = take((nvar + 2) * 4); d_rowc = take((qT + 2) * 4); d_rowcs = take((qT + 2) * 4);
+        d_bsum = take((std::max(cdiv(nvar, SCAN_CHUNK), cdiv(qT ? qT : 1, SCAN_CHUNK)) + 2) * 4); d_part = take((size_t)K * std::max(3 * nblkC, 2 * nblkR) * sizeof(ge_ext));
+        d_pts = take(K * 3 * sizeof(ge_ext)); d_comp = take(K * 3 * 32); d_misc = take(64); d_v = take(from_values ? mT * 32 : 0);
+        d_vcom = take(commit ? mT * 32 : 0);
+        dev_bytes = off;
+    }
+};
 
-        // the wave's witnesses: committed values reduced once for the whole wave, padding rows [n, N) of the 3 K vectors zeroed (one strided fill), then one
-        // launch per level with a lane per (segment, item) - everything below cannot tell where a_L, a_R, a_O came from
-        auto reduce_values = [&] {
-            if (mT) BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(mT, 256)), dim3(256), reinterpret_cast<const uint32_t *>(D(o_wit)), reinterpret_cast<scm *>(D(d_v)), (uint32_t)mT);
-        };
-        auto eval_witnesses = [&] {
-            const uint64_t n = tmpl->n;
-            if (N > n) HIPCHK(hipMemset2DAsync(aL + n, N * sizeof(scm), 0, (N - n) * sizeof(scm), 3 * K, I.st));
-            for (size_t l = 0; l + 1 < tmpl->wit_level_ptr.size(); l++) {
-                const uint32_t s0 = tmpl->wit_level_ptr[l], ns = tmpl->wit_level_ptr[l + 1] - s0;
-                BPG_LAUNCH(I, k_witness_eval_batch, dim3(cdiv(K, 64), ns), dim3(64), tmpl->wit_segs.as<uint4>() + s0, tmpl->wit_stream.as<uint32_t>(),
-                           tmpl->coef.as<scm>(), reinterpret_cast<const scm *>(D(d_v)), (uint32_t)tmpl->m, lgN, (uint32_t)K, aL, aR, aO);
-            }
-        };
-        // ---- the wave's Pedersen commitments (commit): values and reduced blindings go up first, ONE launch makes the K m encodings from the reduced values
-        // the witness evaluation reads, one copy brings them back; the witness evaluation is queued behind and runs while the host threads append the
-        // encodings as "V" - the transcripts are needed next, by the stage that draws the blindings of A_I
-        if (commit) {
-            pool.run(K, [&](size_t lo, size_t hi) {
-                for (size_t k = lo; k < hi; k++) {
-                    const uint64_t m = W[k]->flat->m;
-                    std::memcpy(pin + o_wit + 32 * vbase[k], W[k]->values, 32 * m);
-                    for (uint64_t j = 0; j < m; j++) (*W[k]->vb)[j].to_bytes(pin + o_vbl + 32 * (vbase[k] + j));     // reduced, as pedersen_commit uploads them
-                }
-            });
-            if (!I.commit_ev) HIPCHK(hipEventCreateWithFlags(&I.commit_ev, hipEventDisableTiming));
-            HIPCHK(hipMemcpyAsync(D(o_wit), pin + o_wit, o_coef - o_wit, hipMemcpyHostToDevice, I.st));
-            reduce_values();
-            BPG_LAUNCH(I, k_bt_commit_v, dim3(cdiv(mT, 4 * I.commit_cpw)), dim3(256), reinterpret_cast<const scm *>(D(d_v)), reinterpret_cast<const uint32_t *>(D(o_vbl)),
-                       I.ped_table.as<ge_pniels>(), D(d_vcom), (uint32_t)mT, I.commit_cpw);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(pin + o_back, D(d_vcom), mT * 32, hipMemcpyDeviceToHost, I.st));
-            HIPCHK(hipEventRecord(I.commit_ev, I.st));
-            eval_witnesses();
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventSynchronize(I.commit_ev));
-            pool.run(K, [&](size_t lo, size_t hi) {
-                for (size_t k = lo; k < hi; k++) {
-                    const uint64_t m = W[k]->flat->m;
-                    const uint8_t *com = pin + o_back + 32 * vbase[k];
-                    W[k]->commitments.assign(com, com + 32 * m);
-                    for (uint64_t j = 0; j < m; j++) W[k]->T->append_point("V", com + 32 * j);
-                }
-            });
+// ONE set of window tables of the original generators for every wave of a batch, and the kernel variant the batch took
+struct BatchTables { const ge_pniels *table, *tabB, *tabBb; uint32_t M0T, quad; };
+
+// ---- one wave: its buffers, the host state of its items between two stages, and the stages in the order prove_batch() calls them.  Where a_L, a_R, a_O
+// come from (tmpl, commit) is read by make_commitments(), by witness_and_scalars() and by its host half pack_witness() only; every other stage works on the
+// wave's a_L, a_R, a_O and on what WaveLayout laid out, and must stay that way
+struct Wave {
+    Engine &E; Engine::Impl &I; StageThreads &pool; const BatchTables &B;
+    const std::vector<ProveItem *> &W; const DeviceCircuit *tmpl; const bool commit;
+    const WaveLayout L;
+    const size_t K; const uint64_t N, KN; const uint32_t lgN;
+    uint8_t *pin, *dev, *back, *comp;
+    template <class T> T *D(size_t o) const { return reinterpret_cast<T *>(dev + o); }
+    scm *aL, *aR, *aO, *sL, *sR, *ypow, *yinvpow, *wL, *wR, *wO, *wV, *lv, *rv, *bsc, *h_bsc, *fG, *fH, *cc;
+    uint32_t *stale, *totals; const uint32_t *nk;
+    ge_ext *part, *pts;
+    std::vector<TranscriptRng> rng;
+    std::vector<Scalar> ib, ob, sb, y, yinv, z, u, uinv;
+    std::vector<std::array<Scalar, 7>> tk, tbk;
+
+    Wave(Engine &E_, Engine::Impl &I_, StageThreads &pool_, const BatchTables &B_, const std::vector<ProveItem *> &W_, const DeviceCircuit *tmpl_, bool commit_)
+        : E(E_), I(I_), pool(pool_), B(B_), W(W_), tmpl(tmpl_), commit(commit_), L(W, tmpl_ != nullptr, commit_), K(L.K), N(L.N), KN(L.KN), lgN(L.lgN),
+          ib(K), ob(K), sb(K), y(K), yinv(K), z(K), u(K), uinv(K), tk(K), tbk(K) {
+        I.bt_pin.ensure(L.pin_bytes); I.bt_dev.ensure(L.dev_bytes);
+        pin = I.bt_pin.as<uint8_t>(); dev = I.bt_dev.as<uint8_t>(); back = pin + L.o_back; comp = dev + L.d_comp;
+        aL = D<scm>(L.d_abc); aR = aL + KN; aO = aR + KN; sL = D<scm>(L.d_sLR); sR = sL + KN;
+        ypow = D<scm>(L.d_ypow); yinvpow = D<scm>(L.d_yinv); wL = D<scm>(L.d_w); wR = wL + KN; wO = wR + KN; wV = wO + KN;
+        lv = D<scm>(L.d_lv); rv = D<scm>(L.d_rv); bsc = D<scm>(L.o_bsc); h_bsc = reinterpret_cast<scm *>(pin + L.o_bsc);
+        fG = D<scm>(L.d_fG); fH = D<scm>(L.d_fH); cc = D<scm>(L.d_c);
+        stale = D<uint32_t>(L.d_misc); totals = stale + 4; nk = D<uint32_t>(L.o_nk);
+        part = D<ge_ext>(L.d_part); pts = D<ge_ext>(L.d_pts);
+    }
+
+    // the wave's witnesses: committed values reduced once for the whole wave, padding rows [n, N) of the 3 K vectors zeroed (one strided fill), then one
+    // launch per level with a lane per (segment, item)
+    void reduce_values() {
+        if (L.mT) BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(L.mT, 256)), dim3(256), D<const uint32_t>(L.o_wit), D<scm>(L.d_v), (uint32_t)L.mT);
+    }
+    void eval_witnesses() {
+        const uint64_t n = tmpl->n;
+        if (N > n) HIPCHK(hipMemset2DAsync(aL + n, N * sizeof(scm), 0, (N - n) * sizeof(scm), 3 * K, I.st));
+        for (size_t l = 0; l + 1 < tmpl->wit_level_ptr.size(); l++) {
+            const uint32_t s0 = tmpl->wit_level_ptr[l], ns = tmpl->wit_level_ptr[l + 1] - s0;
+            BPG_LAUNCH(I, k_witness_eval_batch, dim3(cdiv(K, 64), ns), dim3(64), tmpl->wit_segs.as<uint4>() + s0, tmpl->wit_stream.as<uint32_t>(),
+                       tmpl->coef.as<scm>(), D<const scm>(L.d_v), (uint32_t)tmpl->m, lgN, (uint32_t)K, aL, aR, aO);
         }
-        // ---- host, per item: transcript, RNG, the first three blindings and the 2n draws, packed with the instance
-        std::vector<TranscriptRng> rng; rng.reserve(K);
+    }
+    // ---- stage 1, a committing wave only: values and reduced blindings go up first, ONE launch makes the K m encodings from the reduced values the witness
+    // evaluation reads, one copy brings them back; the witness evaluation is queued behind and runs while the host threads append the encodings as "V" -
+    // the transcripts are needed next, by the stage that draws the blindings of A_I
+    void make_commitments() {
+        if (!commit) return;
+        pool.run(K, [&](size_t lo, size_t hi) {
+            for (size_t k = lo; k < hi; k++) {
+                const uint64_t m = W[k]->flat->m;
+                std::memcpy(pin + L.o_wit + 32 * L.vbase[k], W[k]->values, 32 * m);
+                for (uint64_t j = 0; j < m; j++) (*W[k]->vb)[j].to_bytes(pin + L.o_vbl + 32 * (L.vbase[k] + j));     // reduced, as pedersen_commit uploads them
+            }
+        });
+        if (!I.commit_ev) HIPCHK(hipEventCreateWithFlags(&I.commit_ev, hipEventDisableTiming));
+        HIPCHK(hipMemcpyAsync(dev + L.o_wit, pin + L.o_wit, L.o_coef - L.o_wit, hipMemcpyHostToDevice, I.st));
+        reduce_values();
+        BPG_LAUNCH(I, k_bt_commit_v, dim3(cdiv(L.mT, 4 * I.commit_cpw)), dim3(256), D<const scm>(L.d_v), D<const uint32_t>(L.o_vbl),
+                   I.ped_table.as<ge_pniels>(), dev + L.d_vcom, (uint32_t)L.mT, I.commit_cpw);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(back, dev + L.d_vcom, L.mT * 32, hipMemcpyDeviceToHost, I.st));
+        HIPCHK(hipEventRecord(I.commit_ev, I.st));
+        eval_witnesses();
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventSynchronize(I.commit_ev));
+        pool.run(K, [&](size_t lo, size_t hi) {
+            for (size_t k = lo; k < hi; k++) {
+                const uint64_t m = W[k]->flat->m;
+                const uint8_t *com = back + 32 * L.vbase[k];
+                W[k]->commitments.assign(com, com + 32 * m);
+                for (uint64_t j = 0; j < m; j++) W[k]->T->append_point("V", com + 32 * j);
+            }
+        });
+    }
+    // what item k uploads for its witness: the three vectors padded to N, or (a template) its committed values and its constant terms in the parameter
+    // slots of ITS range of the wave's coefficient table
+    void pack_witness(size_t k) {
+        const FlatView &f = *W[k]->flat;
+        const uint8_t *src[3] = {f.aL, f.aR, f.aO};
+        for (int v = 0; v < 3 && !tmpl; v++) {
+            uint8_t *dst = pin + L.o_wit + 32 * (v * KN + k * N);
+            std::memcpy(dst, src[v], 32 * f.n); std::memset(dst + 32 * f.n, 0, 32 * (N - f.n));
+        }
+        if (f.ncoef) std::memcpy(pin + L.o_coef + 32 * L.cbase[k], f.coef, 32 * f.ncoef);
+        if (tmpl) {
+            if (f.m) std::memcpy(pin + L.o_wit + 32 * L.vbase[k], W[k]->values, 32 * f.m);
+            if (tmpl->n_params) std::memcpy(pin + L.o_coef + 32 * (L.cbase[k] + tmpl->param_first), W[k]->params, 32 * tmpl->n_params);
+        }
+    }
+    // ---- stage 2, host, per item: transcript, RNG, the first three blindings and the 2n draws, packed with the instance
+    void pack_and_draw() {
+        rng.reserve(K);
         for (size_t k = 0; k < K; k++) { W[k]->T->append_u64("m", W[k]->flat->m); rng.push_back(W[k]->T->build_rng(*W[k]->vb, W[k]->seed)); }
-        std::vector<Scalar> ib(K), ob(K), sb(K);
         pool.run(K, [&](size_t lo, size_t hi) {
             for (size_t k = lo; k < hi; k++) {
                 const FlatView &f = *W[k]->flat;
@@ -2384,159 +2386,115 @@ void Engine::prove_batch(size_t count, ProveItem *items, DeviceCircuit *tmpl, bo
                 ib[k] = rng[k].random_scalar(); ob[k] = rng[k].random_scalar(); sb[k] = rng[k].random_scalar();
                 h_bsc[k * BSC + 0] = to_scm(ib[k]); h_bsc[k * BSC + 1] = to_scm(ob[k]); h_bsc[k * BSC + 2] = to_scm(sb[k]);
                 // s_L then s_R: 64 uniform bytes each, in prove()'s order; the padding draws are zero
-                uint8_t *raw = pin + o_raw;
+                uint8_t *raw = pin + L.o_raw;
                 rng[k].fill_draws64(raw + 64 * b, n); std::memset(raw + 64 * (b + n), 0, 64 * (N - n));
                 rng[k].fill_draws64(raw + 64 * (KN + b), n); std::memset(raw + 64 * (KN + b + n), 0, 64 * (N - n));
-                const uint8_t *src[3] = {f.aL, f.aR, f.aO};
-                for (int v = 0; v < 3 && !tmpl; v++) {
-                    uint8_t *dst = pin + o_wit + 32 * (v * KN + b);
-                    std::memcpy(dst, src[v], 32 * n); std::memset(dst + 32 * n, 0, 32 * (N - n));
-                }
-                if (f.ncoef) std::memcpy(pin + o_coef + 32 * cbase[k], f.coef, 32 * f.ncoef);
-                if (tmpl) {     // the item's committed values, and its constant terms in the parameter slots of ITS range of the wave's coefficient table
-                    if (f.m) std::memcpy(pin + o_wit + 32 * vbase[k], W[k]->values, 32 * f.m);
-                    if (tmpl->n_params) std::memcpy(pin + o_coef + 32 * (cbase[k] + tmpl->param_first), W[k]->params, 32 * tmpl->n_params);
-                }
+                pack_witness(k);
                 // the block-diagonal matrix: rows after the earlier items' rows, multiplier i of item k -> column k*N + i of its block (L, R, O),
                 // committed j -> 3KN + vbase + j; coefficient indices after the earlier items' coefficients
-                uint64_t *rp = reinterpret_cast<uint64_t *>(pin + o_rp) + rbase[k];
-                for (uint64_t r = 0; r < f.q; r++) rp[r] = ebase[k] + f.row_ptr[r];
-                uint32_t *tv = reinterpret_cast<uint32_t *>(pin + o_tv) + ebase[k], *tc = reinterpret_cast<uint32_t *>(pin + o_tc) + ebase[k];
+                uint64_t *rp = reinterpret_cast<uint64_t *>(pin + L.o_rp) + L.rbase[k];
+                for (uint64_t r = 0; r < f.q; r++) rp[r] = L.ebase[k] + f.row_ptr[r];
+                uint32_t *tv = reinterpret_cast<uint32_t *>(pin + L.o_tv) + L.ebase[k], *tc = reinterpret_cast<uint32_t *>(pin + L.o_tc) + L.ebase[k];
                 for (uint64_t e = 0; e < f.nnz; e++) {
                     const uint32_t pv = f.term_var[e], kind = pv >> 29, idx = pv & 0x1fffffffu;
-                    tv[e] = kind <= 2 ? (kind << 29) | (uint32_t)(b + idx) : (kind == 3 ? (3u << 29) | (uint32_t)(vbase[k] + idx) : pv);
-                    tc[e] = (uint32_t)cbase[k] + f.term_coef[e];
+                    tv[e] = kind <= 2 ? (kind << 29) | (uint32_t)(b + idx) : (kind == 3 ? (3u << 29) | (uint32_t)(L.vbase[k] + idx) : pv);
+                    tc[e] = (uint32_t)L.cbase[k] + f.term_coef[e];
                 }
-                reinterpret_cast<uint32_t *>(pin + o_nk)[k] = (uint32_t)n;
-                reinterpret_cast<uint32_t *>(pin + o_qk)[k] = (uint32_t)f.q;
-                reinterpret_cast<uint32_t *>(pin + o_rb)[k] = (uint32_t)rbase[k];
+                reinterpret_cast<uint32_t *>(pin + L.o_nk)[k] = (uint32_t)n;
+                reinterpret_cast<uint32_t *>(pin + L.o_qk)[k] = (uint32_t)f.q;
+                reinterpret_cast<uint32_t *>(pin + L.o_rb)[k] = (uint32_t)L.rbase[k];
             }
         });
-        reinterpret_cast<uint64_t *>(pin + o_rp)[qT] = nnzT;
-
-        // ---- one upload; witness, coefficients and draws to scalars; the block-diagonal CSR -> CSC in one pass (prove()'s upload kernels)
-        { const size_t up0 = commit ? o_coef : 0; HIPCHK(hipMemcpyAsync(dev + up0, pin + up0, up_bytes - up0, hipMemcpyHostToDevice, I.st)); }   // (values and blindings of a committing wave are up already)
+        reinterpret_cast<uint64_t *>(pin + L.o_rp)[L.qT] = L.nnzT;
+    }
+    // ---- stage 3: one upload (what a committing wave sent ahead is up already)
+    void upload() {
+        HIPCHK(hipMemcpyAsync(dev + L.up_begin, pin + L.up_begin, L.up_bytes - L.up_begin, hipMemcpyHostToDevice, I.st));
         HIPCHK(hipMemsetAsync(stale, 0, 64, I.st));
-        if (!tmpl) BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(3 * KN, 256)), dim3(256), reinterpret_cast<const uint32_t *>(D(o_wit)), aL, (uint32_t)(3 * KN));
-        else if (!commit) { reduce_values(); eval_witnesses(); }
-        if (ncoefT) BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(ncoefT, 256)), dim3(256), reinterpret_cast<const uint32_t *>(D(o_coef)), reinterpret_cast<scm *>(D(d_coef)), (uint32_t)ncoefT);
-        BPG_LAUNCH(I, k_sc_from_wide, dim3(cdiv(2 * KN, 256)), dim3(256), reinterpret_cast<const uint32_t *>(D(o_raw)), sL, (uint32_t)(2 * KN), stale);
-        {
-            const uint64_t *rp = reinterpret_cast<const uint64_t *>(D(o_rp));
-            const uint32_t *tv = reinterpret_cast<const uint32_t *>(D(o_tv)), *tc = reinterpret_cast<const uint32_t *>(D(o_tc));
-            uint32_t *counts = reinterpret_cast<uint32_t *>(D(d_counts)), *starts = reinterpret_cast<uint32_t *>(D(d_starts)), *cursor = reinterpret_cast<uint32_t *>(D(d_cursor));
-            uint32_t *rowconst = reinterpret_cast<uint32_t *>(D(d_rowc)), *rowconst_start = reinterpret_cast<uint32_t *>(D(d_rowcs)), *bsum = reinterpret_cast<uint32_t *>(D(d_bsum));
-            HIPCHK(hipMemsetAsync(counts, 0, (nvar + 1) * 4, I.st));
-            HIPCHK(hipMemsetAsync(rowconst, 0, (qT + 1) * 4, I.st));
-            if (qT) BPG_LAUNCH(I, k_csc_count, dim3(cdiv(qT, 256)), dim3(256), rp, tv, (uint32_t)qT, (uint32_t)KN, (uint32_t)mT, counts, rowconst);
-            BPG_LAUNCH(I, k_scan_blocksums, dim3(nb1), dim3(256), counts, (uint32_t)nvar, bsum);
-            BPG_LAUNCH(I, k_scan_apply, dim3(nb1), dim3(256), counts, (uint32_t)nvar, bsum, starts, cursor);
-            BPG_LAUNCH(I, k_scan_blocksums, dim3(nb2), dim3(256), rowconst, (uint32_t)qT, bsum);
-            BPG_LAUNCH(I, k_scan_apply, dim3(nb2), dim3(256), rowconst, (uint32_t)qT, bsum, rowconst_start, counts /* scratch */);
-            BPG_LAUNCH(I, k_csc_colptr, dim3(cdiv(nvar + 1, 256)), dim3(256), starts, rowconst_start, (uint32_t)nvar, (uint32_t)qT, reinterpret_cast<uint64_t *>(D(d_colptr)), totals);
-            if (qT) BPG_LAUNCH(I, k_csc_fill, dim3(cdiv(qT, 256)), dim3(256), rp, tv, tc, (uint32_t)qT, (uint32_t)KN, (uint32_t)mT, cursor, rowconst_start,
-                               starts + nvar, reinterpret_cast<uint32_t *>(D(d_erow)), reinterpret_cast<uint32_t *>(D(d_ecoef)));
-        }
-        // ---- A_I, A_O, S of every item on the window tables, encoded on the device
-        ge_ext *part = reinterpret_cast<ge_ext *>(D(d_part)), *pts = reinterpret_cast<ge_ext *>(D(d_pts));
-        uint8_t *comp = D(d_comp), *back = pin + o_back;
-        BPG_LAUNCH(I, k_bt_commit3, dim3(nblkC, 3, (uint32_t)K), dim3(256), table, M0T, aL, aR, aO, sL, sR, nk, lgN, part, quad);
-        BPG_LAUNCH(I, k_bt_commit3_finish, dim3(3, (uint32_t)K), dim3(256), part, nblkC, bsc, tabBb, pts, quad);
+    }
+    // ---- stage 4, the witness source: a_L, a_R, a_O from wherever this wave has them; then coefficients and draws to scalars
+    void witness_and_scalars() {
+        if (!tmpl) BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(3 * KN, 256)), dim3(256), D<const uint32_t>(L.o_wit), aL, (uint32_t)(3 * KN));
+        else if (!commit) { reduce_values(); eval_witnesses(); }       // (a committing wave queued them behind its commitments)
+        if (L.ncoefT) BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(L.ncoefT, 256)), dim3(256), D<const uint32_t>(L.o_coef), D<scm>(L.d_coef), (uint32_t)L.ncoefT);
+        BPG_LAUNCH(I, k_sc_from_wide, dim3(cdiv(2 * KN, 256)), dim3(256), D<const uint32_t>(L.o_raw), sL, (uint32_t)(2 * KN), stale);
+    }
+    // ---- stage 5: the block-diagonal CSR -> CSC in one pass, as upload() transposes a single instance
+    void transpose() {
+        I.transpose_csr(D<const uint64_t>(L.o_rp), D<const uint32_t>(L.o_tv), D<const uint32_t>(L.o_tc), L.qT, KN, L.mT,
+                        {D<uint32_t>(L.d_counts), D<uint32_t>(L.d_starts), D<uint32_t>(L.d_cursor), D<uint32_t>(L.d_rowc), D<uint32_t>(L.d_rowcs), D<uint32_t>(L.d_bsum)},
+                        D<uint64_t>(L.d_colptr), D<uint32_t>(L.d_erow), D<uint32_t>(L.d_ecoef), totals);
+    }
+    // ---- stage 6: A_I, A_O, S of every item on the window tables, encoded on the device
+    void commit3() {
+        BPG_LAUNCH(I, k_bt_commit3, dim3(L.nblkC, 3, (uint32_t)K), dim3(256), B.table, B.M0T, aL, aR, aO, sL, sR, nk, lgN, part, B.quad);
+        BPG_LAUNCH(I, k_bt_commit3_finish, dim3(3, (uint32_t)K), dim3(256), part, L.nblkC, bsc, B.tabBb, pts, B.quad);
         BPG_LAUNCH(I, k_bt_compress, dim3(cdiv(3 * K, 64)), dim3(64), pts, comp, (uint32_t)(3 * K));
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(back, comp, 3 * K * 32, hipMemcpyDeviceToHost, I.st));
         HIPCHK(hipMemcpyAsync(back + 3 * K * 32, totals, 8, hipMemcpyDeviceToHost, I.st));
         I.wait_stream();
-        if (reinterpret_cast<const uint32_t *>(back + 3 * K * 32)[1] != nnzT) throw std::logic_error("prove_batch: transposition lost entries");
-
-        // ---- host: A_I1, A_O1, S1 -> y, z of every item
-        std::vector<Scalar> y(K), yinv(K), z(K);
+        if (reinterpret_cast<const uint32_t *>(back + 3 * K * 32)[1] != L.nnzT) throw std::logic_error("prove_batch: transposition lost entries");
+    }
+    // ---- stage 7: host: A_I1, A_O1, S1 -> y, z of every item; device: powers, flattened weights (block-diagonal CSC, z indexed by global row), t-polynomial
+    void poly_t() {
         pool.run(K, [&](size_t lo, size_t hi) {
             for (size_t k = lo; k < hi; k++) {
-                Transcript &T = *W[k]->T;
-                std::vector<uint8_t> &proof = W[k]->proof;
-                const uint8_t *p3 = back + 96 * k;
-                const bool compact = W[k]->flags & 1u, no_1phase = W[k]->flags & 2u;
-                proof.clear(); proof.reserve(14 * 32 + (2 * lgN + 2) * 32 + 1);
-                if (compact) proof.push_back(0);
-                proof.insert(proof.end(), p3, p3 + 96);
-                T.append_point("A_I1", p3); T.append_point("A_O1", p3 + 32); T.append_point("S1", p3 + 64);
-                if (!no_1phase) T.r1cs_1phase_domain_sep();
-                const uint8_t ident[32] = {0};
-                T.append_point("A_I2", ident); T.append_point("A_O2", ident); T.append_point("S2", ident);
-                if (!compact) proof.insert(proof.end(), 96, 0);
-                y[k] = T.challenge_scalar("y"); z[k] = T.challenge_scalar("z");
+                proof_open(W[k]->proof, lgN, W[k]->flags, back + 96 * k);
+                fs_commitments(*W[k]->T, back + 96 * k, nullptr, W[k]->flags, y[k], z[k]);
             }
             batch_invert(y.data(), yinv.data(), lo, hi);
-            scm *hb = reinterpret_cast<scm *>(pin + o_bases);
+            scm *hb = reinterpret_cast<scm *>(pin + L.o_bases);
             for (size_t k = lo; k < hi; k++) { hb[3 * k] = to_scm(y[k]); hb[3 * k + 1] = to_scm(yinv[k]); hb[3 * k + 2] = to_scm(z[k]); }
         });
-        // ---- device: powers, flattened weights (block-diagonal CSC, z indexed by global row), t-polynomial of every item
-        HIPCHK(hipMemcpyAsync(D(o_bases), pin + o_bases, K * 3 * 32, hipMemcpyHostToDevice, I.st));
-        {
-            uint64_t qmax = 0; for (size_t k = 0; k < K; k++) qmax = std::max<uint64_t>(qmax, W[k]->flat->q);
-            const uint32_t lgT = std::min<uint32_t>(ceil_log2(std::max<uint64_t>(N, qmax)), 10);
-            BPG_LAUNCH(I, k_bt_exp, dim3(cdiv(1u << lgT, 256), 3, (uint32_t)K), dim3(256), reinterpret_cast<const scm *>(D(o_bases)),
-                       reinterpret_cast<const uint32_t *>(D(o_qk)), reinterpret_cast<const uint32_t *>(D(o_rb)), lgN, lgT, ypow, yinvpow, reinterpret_cast<scm *>(D(d_z)));
-        }
-        BPG_LAUNCH(I, k_flatten, dim3(cdiv(nvar, 256)), dim3(256), reinterpret_cast<const uint64_t *>(D(d_colptr)), reinterpret_cast<const uint32_t *>(D(d_erow)),
-                   reinterpret_cast<const uint32_t *>(D(d_ecoef)), reinterpret_cast<const scm *>(D(d_coef)), reinterpret_cast<const scm *>(D(d_z)), wAll,
-                   (uint32_t)nvar, (uint32_t)(3 * KN));
-        scm *wL = wAll, *wR = wL + KN, *wO = wR + KN, *wV = wO + KN;
-        BPG_LAUNCH(I, k_bt_poly_t, dim3(pblocks, (uint32_t)K), dim3(256), aL, aR, aO, sL, sR, wL, wR, wO, ypow, yinvpow, nk, lgN, reinterpret_cast<scm *>(D(d_tpart)));
-        BPG_LAUNCH(I, k_reduce_partials, dim3((uint32_t)(6 * K)), dim3(256), reinterpret_cast<const scm *>(D(d_tpart)), pblocks, (uint32_t)(6 * K), reinterpret_cast<scm *>(D(d_t)));
+        HIPCHK(hipMemcpyAsync(dev + L.o_bases, pin + L.o_bases, K * 3 * 32, hipMemcpyHostToDevice, I.st));
+        const uint32_t lgT = std::min<uint32_t>(ceil_log2(std::max<uint64_t>(N, L.qmax)), 10);
+        BPG_LAUNCH(I, k_bt_exp, dim3(cdiv(1u << lgT, 256), 3, (uint32_t)K), dim3(256), D<const scm>(L.o_bases), D<const uint32_t>(L.o_qk), D<const uint32_t>(L.o_rb),
+                   lgN, lgT, ypow, yinvpow, D<scm>(L.d_z));
+        BPG_LAUNCH(I, k_flatten, dim3(cdiv(L.nvar, 256)), dim3(256), D<const uint64_t>(L.d_colptr), D<const uint32_t>(L.d_erow), D<const uint32_t>(L.d_ecoef),
+                   D<const scm>(L.d_coef), D<const scm>(L.d_z), wL, (uint32_t)L.nvar, (uint32_t)(3 * KN));
+        BPG_LAUNCH(I, k_bt_poly_t, dim3(L.pblocks, (uint32_t)K), dim3(256), aL, aR, aO, sL, sR, wL, wR, wO, ypow, yinvpow, nk, lgN, D<scm>(L.d_tpart));
+        BPG_LAUNCH(I, k_reduce_partials, dim3((uint32_t)(6 * K)), dim3(256), D<const scm>(L.d_tpart), L.pblocks, (uint32_t)(6 * K), D<scm>(L.d_t));
         HIPCHK(hipGetLastError());
-        const scm *h_t = reinterpret_cast<const scm *>(back), *h_wV = h_t + 6 * K;
-        const uint32_t *h_stale = reinterpret_cast<const uint32_t *>(h_wV + mT);
-        HIPCHK(hipMemcpyAsync(back, D(d_t), 6 * K * 32, hipMemcpyDeviceToHost, I.st));
-        if (mT) HIPCHK(hipMemcpyAsync(back + 6 * K * 32, wV, mT * 32, hipMemcpyDeviceToHost, I.st));
-        HIPCHK(hipMemcpyAsync(back + (6 * K + mT) * 32, stale, 4, hipMemcpyDeviceToHost, I.st));
+        HIPCHK(hipMemcpyAsync(back, dev + L.d_t, 6 * K * 32, hipMemcpyDeviceToHost, I.st));
+        if (L.mT) HIPCHK(hipMemcpyAsync(back + 6 * K * 32, wV, L.mT * 32, hipMemcpyDeviceToHost, I.st));
+        HIPCHK(hipMemcpyAsync(back + (6 * K + L.mT) * 32, stale, 4, hipMemcpyDeviceToHost, I.st));
         I.wait_stream();
-        if (*h_stale) throw DeviceError("a blinding draw of the batch did not reach the device: proofs withheld");
-
-        // ---- host: t_k, tau_k -> T_1, T_3..T_6 of every item in ONE Pedersen launch
-        std::vector<std::array<Scalar, 7>> tk(K), tbk(K);
+        if (*reinterpret_cast<const uint32_t *>(back + (6 * K + L.mT) * 32)) throw DeviceError("a blinding draw of the batch did not reach the device: proofs withheld");
+    }
+    // ---- stage 8, host: t_k, tau_k -> T_1, T_3..T_6 of every item in ONE Pedersen launch; then u, x, t_x, its blinding, e_blinding, w
+    void t_commitments() {
+        const scm *h_t = reinterpret_cast<const scm *>(back), *h_wV = h_t + 6 * K;
         std::vector<uint8_t> vv(5 * K * 32), rr(5 * K * 32), tcom(5 * K * 32);
         pool.run(K, [&](size_t lo, size_t hi) {
-            static const int idx[5] = {1, 3, 4, 5, 6};
             for (size_t k = lo; k < hi; k++) {
                 for (int j = 0; j < 6; j++) tk[k][j + 1] = from_scm(h_t[6 * k + j]);
-                Scalar *tb = tbk[k].data();
-                tb[1] = rng[k].random_scalar(); tb[3] = rng[k].random_scalar(); tb[4] = rng[k].random_scalar(); tb[5] = rng[k].random_scalar(); tb[6] = rng[k].random_scalar();
-                for (int j = 0; j < 5; j++) { tk[k][idx[j]].to_bytes(&vv[32 * (5 * k + j)]); tb[idx[j]].to_bytes(&rr[32 * (5 * k + j)]); }
+                poly_commit_inputs(rng[k], tk[k].data(), tbk[k].data(), &vv[160 * k], &rr[160 * k]);
             }
         });
-        pedersen_commit(5 * K, vv.data(), rr.data(), tcom.data());
-        // ---- host: u, x, t_x, its blinding, e_blinding, w
+        E.pedersen_commit(5 * K, vv.data(), rr.data(), tcom.data());
         pool.run(K, [&](size_t lo, size_t hi) {
-            static const char *labels[5] = {"T_1", "T_3", "T_4", "T_5", "T_6"};
             for (size_t k = lo; k < hi; k++) {
-                Transcript &T = *W[k]->T;
-                std::vector<uint8_t> &proof = W[k]->proof;
-                const uint8_t *out = &tcom[32 * 5 * k];
-                for (int j = 0; j < 5; j++) T.append_point(labels[j], out + 32 * j);
-                proof.insert(proof.end(), out, out + 160);
-                const Scalar u_ch = T.challenge_scalar("u"), x = T.challenge_scalar("x");
-                Scalar *t = tk[k].data(), *tb = tbk[k].data();
-                const std::vector<Scalar> &vb = *W[k]->vb;
-                for (uint64_t j = 0; j < vb.size(); j++) tb[2] += from_scm(h_wV[vbase[k] + j]) * vb[j];
-                Scalar tx, txb;
-                for (int j = 6; j >= 1; j--) { tx = (tx + t[j]) * x; txb = (txb + tb[j]) * x; }
-                const Scalar eb = x * (ib[k] + x * (ob[k] + x * sb[k]));
-                T.append_scalar("t_x", tx); T.append_scalar("t_x_blinding", txb); T.append_scalar("e_blinding", eb);
-                { uint8_t b[96]; tx.to_bytes(b); txb.to_bytes(b + 32); eb.to_bytes(b + 64); proof.insert(proof.end(), b, b + 96); }
-                const Scalar w = T.challenge_scalar("w");
-                T.innerproduct_domain_sep(N);
+                ProveItem &it = *W[k];
+                Scalar u_ch, x;
+                fs_poly_commitments(*it.T, &tcom[160 * k], u_ch, x);
+                it.proof.insert(it.proof.end(), &tcom[160 * k], &tcom[160 * k] + 160);
+                const PolyAtX px = poly_at_x(tk[k].data(), tbk[k].data(), [&](uint64_t j) { return from_scm(h_wV[L.vbase[k] + j]); }, *it.vb, ib[k], ob[k], sb[k], x);
+                const Scalar w = fs_poly_scalars(*it.T, px.tx, px.txb, px.eb);
+                proof_poly_scalars(it.proof, px);
+                it.T->innerproduct_domain_sep(N);
                 h_bsc[k * BSC + BSC_X] = to_scm(x); h_bsc[k * BSC + BSC_UCH] = to_scm(u_ch); h_bsc[k * BSC + BSC_W] = to_scm(w);
             }
         });
         HIPCHK(hipMemcpyAsync(bsc, h_bsc, K * BSC * 32, hipMemcpyHostToDevice, I.st));
-
-        // ---- device: l(x), r(x), then the inner-product argument of every item: lg N table-driven rounds on the frozen original generators
-        scm *fG = reinterpret_cast<scm *>(D(d_fG)), *fH = reinterpret_cast<scm *>(D(d_fH)), *cc = reinterpret_cast<scm *>(D(d_c));
+    }
+    // ---- stage 9, device: l(x), r(x) and the factors of the frozen original generators
+    void poly_eval() {
         BPG_LAUNCH(I, k_bt_poly_eval, dim3(cdiv(N, 256), (uint32_t)K), dim3(256), aL, aR, aO, sL, sR, wL, wR, wO, ypow, yinvpow, bsc, nk, lgN, lv, rv);
         if (lgN) BPG_LAUNCH(I, k_bt_factors, dim3(cdiv(N, 256), (uint32_t)K), dim3(256), yinvpow, bsc, nk, lgN, fG, fH, cc);
-        std::vector<Scalar> u(K), uinv(K);
+    }
+    // ---- stage 10: the inner-product argument of every item: lg N table-driven rounds
+    void ipa_rounds() {
         uint32_t cur = 0;
         for (uint32_t j = 0; j < lgN; j++) {
             const uint32_t h = (uint32_t)(N >> (j + 1));
@@ -2545,29 +2503,29 @@ void Engine::prove_batch(size_t count, ProveItem *items, DeviceCircuit *tmpl, bo
                 BPG_LAUNCH(I, k_bt_advance, dim3(cdiv(std::max(hadv, cnt), 256), (uint32_t)K), dim3(256), lv, rv, bsc, hadv, cc, cur, cnt, lgN);
                 cur ^= 1u;
             }
-            BPG_LAUNCH(I, k_bt_round, dim3(nblkR, 2, (uint32_t)K), dim3(256), table, M0T, lv, rv, fG, fH, cc, cur, lgN, j, part, quad);
-            BPG_LAUNCH(I, k_bt_finish, dim3(2, (uint32_t)K), dim3(256), part, nblkR, lv, rv, h, lgN, bsc, tabB, pts, quad);
+            BPG_LAUNCH(I, k_bt_round, dim3(L.nblkR, 2, (uint32_t)K), dim3(256), B.table, B.M0T, lv, rv, fG, fH, cc, cur, lgN, j, part, B.quad);
+            BPG_LAUNCH(I, k_bt_finish, dim3(2, (uint32_t)K), dim3(256), part, L.nblkR, lv, rv, h, lgN, bsc, B.tabB, pts, B.quad);
             BPG_LAUNCH(I, k_bt_compress, dim3(cdiv(2 * K, 64)), dim3(64), pts, comp, (uint32_t)(2 * K));
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpyAsync(back, comp, 2 * K * 32, hipMemcpyDeviceToHost, I.st));
             I.wait_stream();
             pool.run(K, [&](size_t lo, size_t hi) {
                 for (size_t k = lo; k < hi; k++) {
-                    Transcript &T = *W[k]->T;
                     const uint8_t *lr = back + 64 * k;
-                    T.append_point("L", lr); T.append_point("R", lr + 32);
                     W[k]->proof.insert(W[k]->proof.end(), lr, lr + 64);
-                    u[k] = T.challenge_scalar("u");
+                    u[k] = fs_ipa_round(*W[k]->T, lr, lr + 32);
                 }
                 batch_invert(u.data(), uinv.data(), lo, hi);
                 for (size_t k = lo; k < hi; k++) { h_bsc[k * BSC + BSC_U] = to_scm(u[k]); h_bsc[k * BSC + BSC_UINV] = to_scm(uinv[k]); }
             });
             HIPCHK(hipMemcpyAsync(bsc, h_bsc, K * BSC * 32, hipMemcpyHostToDevice, I.st));
         }
-        // the last round's scalar fold, then the final a, b of every item
-        BPG_LAUNCH(I, k_bt_fold_scalars, dim3(cdiv(K, 256)), dim3(256), lv, rv, bsc, lgN, reinterpret_cast<scm *>(D(d_ab)), (uint32_t)K);
+    }
+    // ---- stage 11: the last round's scalar fold, then the final a, b of every item
+    void final_ab() {
+        BPG_LAUNCH(I, k_bt_fold_scalars, dim3(cdiv(K, 256)), dim3(256), lv, rv, bsc, lgN, D<scm>(L.d_ab), (uint32_t)K);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(back, D(d_ab), 2 * K * 32, hipMemcpyDeviceToHost, I.st));
+        HIPCHK(hipMemcpyAsync(back, dev + L.d_ab, 2 * K * 32, hipMemcpyDeviceToHost, I.st));
         I.wait_stream();
         const scm *h_ab = reinterpret_cast<const scm *>(back);
         for (size_t k = 0; k < K; k++) {
@@ -2575,74 +2533,49 @@ void Engine::prove_batch(size_t count, ProveItem *items, DeviceCircuit *tmpl, bo
             W[k]->proof.insert(W[k]->proof.end(), o, o + 64);
         }
     }
+};
+}  // namespace
+
+// tmpl != nullptr: every item is a fresh witness of that template (flat = its host copy; values, params per item).  commit (a template with m > 0): the
+// transcripts come in as they are BEFORE the commitments; every wave makes its own (k_bt_commit_v) and appends them before anything is drawn
+void Engine::prove_batch(size_t count, ProveItem *items, DeviceCircuit *tmpl, bool commit) {
+    if (!count) return;
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    ProvingGuard in_flight(device_);                // the whole batch is one proof in flight: its kernel variants are chosen once
+    I.shared_now = I.shared_variants();
+    uint32_t lgmax = 0;
+    for (size_t k = 0; k < count; k++) {
+        if (!lockstep_eligible(items[k].flat->n, items[k].flags)) throw std::logic_error("prove_batch: an item that is not lockstep-eligible");
+        lgmax = std::max(lgmax, ceil_log2(items[k].flat->n));
+    }
+    require_gens_capacity(gens_cap_, 1ull << lgmax);
+    // ONE set of window tables of the original generators, for the largest N of the batch (an item of smaller N reads the first N rows of each half)
+    const uint32_t M0T = 1u << lgmax;
+    I.tt_build(I.gens.as<ge_niels>(), I.gens.as<ge_niels>() + gens_cap_, I.bases.as<ge_niels>(), M0T, true);
+    const BatchTables B{I.tt_table_p, I.ped_table.as<ge_pniels>(), I.ped_table.as<ge_pniels>() + (size_t)TT_WINDOWS * TT_MULTS, M0T, I.shared_now ? 0u : 1u};
+    StageThreads pool(std::min<uint32_t>(batch_host_threads(), (uint32_t)std::max<size_t>(1, count / 8)));
+    for (const std::vector<ProveItem *> &W : plan_waves(count, items, (uint64_t)I.batch_wave_mb << 20)) {
+        Wave w(*this, I, pool, B, W, tmpl, commit);
+        w.make_commitments();
+        w.pack_and_draw();
+        w.upload();
+        w.witness_and_scalars();
+        w.transpose();
+        w.commit3();
+        w.poly_t();
+        w.t_commitments();
+        w.poly_eval();
+        w.ipa_rounds();
+        w.final_ab();
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ verify
 // Verifier::verify (dalek r1cs/verifier.rs; reference call site src/bin/verifier.rs:89-90): Fiat-Shamir replay on the host,
 // then ONE multiscalar multiplication of 2N + m + 2 lgN + 13 terms through the same bucket-method kernels; accept iff it is the identity.
 namespace {
-const uint8_t kIdentity[32] = {0};      // compressed identity
-// R1CSProof::from_bytes and the Fiat-Shamir replay of Verifier::verify on the host: everything verify() and verify_batch() decide before device work
-struct VerifyReplay {
-    uint64_t n = 0, m = 0, N = 1;
-    uint32_t lgN = 0;
-    const uint8_t *pA[6] = {}, *pT[5] = {}, *pLR = nullptr;
-    Scalar tx, txb, eb, ipa, ipb, y, z, u_ch, x, w, r, yinv;
-    std::vector<Scalar> uk, ukinv;
-    uint32_t npts() const { return (uint32_t)(6 + m + 5 + 2 * lgN); }
-};
-R1CSError verify_replay(uint64_t n, uint64_t m, uint64_t gens_cap, Transcript &T, const uint8_t *proof, size_t proof_len, const uint8_t seed[32],
-                        uint32_t flags, VerifyReplay &R) {
-    uint64_t N = 1; while (N < n) N <<= 1;
-    const uint32_t lgN = ceil_log2(N);
-    R.n = n; R.m = m; R.N = N; R.lgN = lgN;
-    const bool compact = flags & 1u, no_1phase = flags & 2u;
-    const size_t need = (compact ? 1 + 11 * 32 : 14 * 32) + (2 * (size_t)lgN + 2) * 32;
-    if (proof_len != need) return R1CSError::FormatError;
-    if (gens_cap < N) return R1CSError::InvalidGeneratorsLength;
-    if (lgN > 32) return R1CSError::FormatError;
-    const uint8_t *in = proof;
-    static const uint8_t ident[32] = {0};
-    if (compact) { if (*in++ != 0) return R1CSError::FormatError; }
-    const uint8_t **pA = R.pA, **pT = R.pT;
-    pA[0] = in; pA[1] = in + 32; pA[2] = in + 64; pA[3] = pA[4] = pA[5] = ident; in += 96;
-    if (!compact) { pA[3] = in; pA[4] = in + 32; pA[5] = in + 64; in += 96; }
-    for (int k = 0; k < 5; k++) { pT[k] = in; in += 32; }
-    Scalar sc5[5];                                   // t_x, t_x_blinding, e_blinding, a, b : must be canonical (R1CSProof::from_bytes)
-    const uint8_t *ps[5] = {in, in + 32, in + 64, proof + proof_len - 64, proof + proof_len - 32};
-    for (int k = 0; k < 5; k++) { std::memcpy(sc5[k].w, ps[k], 32); if (!sc5[k].is_canonical()) return R1CSError::FormatError; }
-    in += 96;
-    R.pLR = in;
-    R.tx = sc5[0]; R.txb = sc5[1]; R.eb = sc5[2]; R.ipa = sc5[3]; R.ipb = sc5[4];
-    auto is_ident = [](const uint8_t *p) { return std::memcmp(p, ident, 32) == 0; };
-
-    T.append_u64("m", m);
-    if (is_ident(pA[0]) || is_ident(pA[1]) || is_ident(pA[2])) return R1CSError::VerificationError;      // validate_and_append_point
-    T.append_point("A_I1", pA[0]); T.append_point("A_O1", pA[1]); T.append_point("S1", pA[2]);
-    if (!no_1phase) T.r1cs_1phase_domain_sep();
-    T.append_point("A_I2", pA[3]); T.append_point("A_O2", pA[4]); T.append_point("S2", pA[5]);
-    R.y = T.challenge_scalar("y"); R.z = T.challenge_scalar("z");
-    static const char *tl[5] = {"T_1", "T_3", "T_4", "T_5", "T_6"};
-    for (int k = 0; k < 5; k++) { if (is_ident(pT[k])) return R1CSError::VerificationError; T.append_point(tl[k], pT[k]); }
-    R.u_ch = T.challenge_scalar("u"); R.x = T.challenge_scalar("x");
-    T.append_scalar("t_x", R.tx); T.append_scalar("t_x_blinding", R.txb); T.append_scalar("e_blinding", R.eb);
-    R.w = T.challenge_scalar("w");
-    T.innerproduct_domain_sep(N);
-    R.uk.assign(lgN, Scalar()); R.ukinv.assign(lgN, Scalar());
-    bool lr_ident = false;
-    for (uint32_t k = 0; k < lgN; k++) {
-        const uint8_t *Lp = R.pLR + 64 * k, *Rp = Lp + 32;
-        lr_ident |= is_ident(Lp) || is_ident(Rp);
-        T.append_point("L", Lp); T.append_point("R", Rp);
-        R.uk[k] = T.challenge_scalar("u"); R.ukinv[k] = R.uk[k];
-    }
-    if (lr_ident) return R1CSError::VerificationError;
-    if (lgN) Scalar::batch_invert(R.ukinv);
-    TranscriptRng rng = T.build_rng({}, seed);
-    R.r = rng.random_scalar();
-    R.yinv = R.y.invert();
-    return R1CSError::None;
-}
+// (VerifyReplay and verify_replay: host/fiat_shamir.hpp)
 // the compressed points of one replayed proof in the order of its MSM terms: A_I1, A_O1, S1, A_I2, A_O2, S2, V, T_1, T_3..T_6, L_k, R_k
 void verify_points(const VerifyReplay &R, const uint8_t *V, uint8_t *out) {
     size_t o = 0;
@@ -2680,16 +2613,7 @@ VerifyVecs verify_prep(Engine::Impl &I, const DeviceCircuit *c, const VerifyRepl
     const size_t b_w = Engine::Impl::al256(c->ncols * sizeof(scm)), b_z = Engine::Impl::al256((q + 2) * sizeof(scm)), b_y = Engine::Impl::al256(N * sizeof(scm));
     I.arena.ensure(b_w + b_z + b_y);
     scm *const wAll_p = reinterpret_cast<scm *>(I.arena_at(0)), *const zpow_p = reinterpret_cast<scm *>(I.arena_at(b_w)), *const ypow_p = reinterpret_cast<scm *>(I.arena_at(b_w + b_z));
-    {   // y^-i, z^j: one launch
-        ExpTables E; std::memset(&E, 0, sizeof E);
-        uint32_t k = 0, lgmax = 0;
-        auto add = [&](const Scalar &base, scm *out, uint64_t count) {
-            uint32_t lgT = ceil_log2(count); if (lgT > 16) lgT = 16;
-            E.base[k] = to_scm(base); E.out[k] = out; E.count[k] = (uint32_t)count; E.lgT[k] = lgT; lgmax = std::max(lgmax, lgT); k++;
-        };
-        add(R.yinv, I.yinvpow.as<scm>(), N); add(R.z, zpow_p, q + 1);
-        BPG_LAUNCH(I, k_exp_table, dim3(cdiv(1u << lgmax, 256), k), dim3(256), E);
-    }
+    I.exp_tables({{R.yinv, I.yinvpow.as<scm>(), N}, {R.z, zpow_p, q + 1}});      // y^-i, z^j: one launch
     if (c->ncols > 1)
         BPG_LAUNCH(I, k_flatten, dim3(cdiv(c->ncols - 1, 256)), dim3(256), c->col_ptr.as<uint64_t>(), c->ent_row.as<uint32_t>(), c->ent_coef.as<uint32_t>(),
                    c->coef.as<scm>(), zpow_p, wAll_p, (uint32_t)(c->ncols - 1), (uint32_t)(3 * n));
@@ -2703,6 +2627,20 @@ VerifyVecs verify_prep(Engine::Impl &I, const DeviceCircuit *c, const VerifyRepl
     }
     BPG_LAUNCH(I, k_ipa_s, dim3(cdiv(N, 256)), dim3(256), ch, ypow_p, R.lgN, (uint32_t)N);
     return VerifyVecs{wL, wR, wO, wV, ypow_p};
+}
+// the ONE multiscalar multiplication of a verification: lv, rv on the first N generators of each half, vfy_sc on the proofs' own points and on B, B_blinding
+// behind them; true iff the sum is the identity.  Synchronises the stream
+bool verify_msm(Engine::Impl &I, uint64_t N, uint32_t npts) {
+    MsmSegs S = seg_new();
+    seg_push(S, I.lv.as<scm>(), I.gens.as<ge_niels>(), (uint32_t)N, 0);
+    seg_push(S, I.rv.as<scm>(), I.gens.as<ge_niels>() + I.gens_cap, (uint32_t)N, 0);
+    seg_push(S, I.vfy_sc.as<scm>(), I.vfy_pts.as<ge_niels>(), npts, 0);
+    seg_push(S, I.vfy_sc.as<scm>() + npts, I.bases.as<ge_niels>(), 2, 0);
+    const Engine::Impl::MsmTicket tk = I.msm(S, 1);
+    HIPCHK(hipStreamSynchronize(I.st));
+    uint8_t out[32];
+    h51::pt_compress(out, I.msm_points(tk)[0]);
+    return std::memcmp(out, kIdentity, 32) == 0;
 }
 }  // namespace
 
@@ -2742,10 +2680,9 @@ R1CSError Engine::verify(DeviceCircuit *c, Transcript &T, const uint8_t *V, cons
     const VerifyVecs W = verify_prep(I, c, R, I.vfy_ch.as<IpaChallenges>());
     scm *const wV = W.wV;
     I.lv.ensure(N * sizeof(scm)); I.rv.ensure(N * sizeof(scm));
-    scm *gsc = I.lv.as<scm>(), *hsc = I.rv.as<scm>();
     const uint32_t blocks = std::min<uint32_t>(cdiv(N, 256), 1024);
     BPG_LAUNCH(I, k_verify_scalars, dim3(blocks), dim3(256), W.wL, W.wR, W.wO, I.yinvpow.as<scm>(), W.svec, to_scm(R.x), to_scm(R.ipa), to_scm(R.ipb), to_scm(R.u_ch),
-               gsc, hsc, I.red_partial.as<scm>(), (uint32_t)n, (uint32_t)N);
+               I.lv.as<scm>(), I.rv.as<scm>(), I.red_partial.as<scm>(), (uint32_t)n, (uint32_t)N);
     BPG_LAUNCH(I, k_reduce_partials, dim3(1), dim3(256), I.red_partial.as<scm>(), blocks, 1u, I.red_out.as<scm>());
     HIPCHK(hipGetLastError());
     scm h_delta; std::vector<scm> h_wV(m + 1); std::vector<uint32_t> h_ok(npts);
@@ -2759,19 +2696,7 @@ R1CSError Engine::verify(DeviceCircuit *c, Transcript &T, const uint8_t *V, cons
     std::vector<scm> hs(npts + 2);
     for (size_t k = 0; k < hs.size(); k++) hs[k] = to_scm(hsv[k]);
     HIPCHK(hipMemcpyAsync(I.vfy_sc.p, hs.data(), hs.size() * sizeof(scm), hipMemcpyHostToDevice, st));
-    Impl::MsmTicket tk;
-    {
-        MsmSegs S = seg_new();
-        seg_push(S, gsc, I.gens.as<ge_niels>(), (uint32_t)N, 0);
-        seg_push(S, hsc, I.gens.as<ge_niels>() + gens_cap_, (uint32_t)N, 0);
-        seg_push(S, I.vfy_sc.as<scm>(), I.vfy_pts.as<ge_niels>(), npts, 0);
-        seg_push(S, I.vfy_sc.as<scm>() + npts, I.bases.as<ge_niels>(), 2, 0);
-        tk = I.msm(S, 1);
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    uint8_t out[32];
-    h51::pt_compress(out, I.msm_points(tk)[0]);
-    return std::memcmp(out, kIdentity, 32) == 0 ? R1CSError::None : R1CSError::VerificationError;
+    return verify_msm(I, N, npts) ? R1CSError::None : R1CSError::VerificationError;
 }
 
 // ------------------------------------------------------------------------------------------------ batch verification
@@ -2892,20 +2817,7 @@ void Engine::verify_batch(size_t count, const VerifyItem *items, const uint8_t b
     hs[npts] = to_scm(sB); hs[npts + 1] = to_scm(sBb);
     I.vfy_sc.ensure((size_t)(npts + 2) * sizeof(scm));
     I.h2d(I.vfy_sc.p, hs.data(), hs.size() * sizeof(scm));
-    // ---- one MSM for the whole batch
-    Impl::MsmTicket tk;
-    {
-        MsmSegs S = seg_new();
-        seg_push(S, I.lv.as<scm>(), I.gens.as<ge_niels>(), (uint32_t)Nmax, 0);
-        seg_push(S, I.rv.as<scm>(), I.gens.as<ge_niels>() + gens_cap_, (uint32_t)Nmax, 0);
-        seg_push(S, I.vfy_sc.as<scm>(), I.vfy_pts.as<ge_niels>(), npts, 0);
-        seg_push(S, I.vfy_sc.as<scm>() + npts, I.bases.as<ge_niels>(), 2, 0);
-        tk = I.msm(S, 1);
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    uint8_t out[32];
-    h51::pt_compress(out, I.msm_points(tk)[0]);
-    if (std::memcmp(out, kIdentity, 32) == 0) return;                  // every live item is accepted
+    if (verify_msm(I, Nmax, npts)) return;                             // one MSM for the whole batch: every live item is accepted
     // ---- a rejected batch: each live item alone, from its state before, for its exact status (costs only when the batch holds a bad proof)
     for (size_t k = 0; k < count; k++) {
         if (!live[k]) continue;

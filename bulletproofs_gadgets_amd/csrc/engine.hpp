@@ -148,7 +148,7 @@ public:
     static bool template_lockstep(const DeviceCircuit *tmpl);
     // what a template batch leaves behind on either path: no witness, no equal-scalar sets
     static void drop_witness(DeviceCircuit *tmpl);
-    // the host-side checks upload() makes on an instance (CSR shape, index ranges, sizes): std::invalid_argument, no device work
+    // the host-side checks of an instance (CSR shape, index ranges, sizes), which upload() and plan_template() start with: std::invalid_argument, no device work
     static void check_instance(const FlatView &c);
     void synchronize();
     // HIP-event profile on the engine's own stream: mode 0 off, 1 = dominant kernel (k_fold_points) only, 2 = all kernels

@@ -15,6 +15,7 @@
 #include <vector>
 #include "scalar.hpp"
 #include "merlin.hpp"
+#include "r1cs_error.hpp"
 
 namespace bpg {
 
@@ -82,12 +83,6 @@ struct LinearCombination {
     LinearCombination operator-(const LinearCombination &o) const { LinearCombination r = *this; for (auto &t : o.terms) r.terms.emplace_back(t.first, -t.second); return r; }
     LinearCombination operator-() const { LinearCombination r; for (auto &t : terms) r.terms.emplace_back(t.first, -t.second); return r; }
     LinearCombination operator*(const Scalar &s) const { LinearCombination r; for (auto &t : terms) r.terms.emplace_back(t.first, t.second * s); return r; }
-};
-
-enum class R1CSError { None = 0, InvalidGeneratorsLength = 1, FormatError = 2, VerificationError = 3, MissingAssignment = 5, GadgetError = 6 };
-struct R1CSException : std::runtime_error {
-    R1CSError code;
-    R1CSException(R1CSError c, const std::string &m) : std::runtime_error(m), code(c) {}
 };
 
 struct OptScalar { bool some; Scalar v; OptScalar() : some(false) {} OptScalar(const Scalar &s) : some(true), v(s) {} };

@@ -171,6 +171,38 @@ def test_failures_stay_with_their_item(ctx):
         c2.close()
 
 
+def _verify(ctx, inst, state, coms, proof, flags):
+    """bpg_r1cs_verify from the state before the proof: (status, transcript state after)"""
+    ts = C.create_string_buffer(bytes(state), 203)
+    cs = inst.cstruct()
+    cs.aL = cs.aR = cs.aO = None
+    s = bpg.lib().bpg_r1cs_verify(ctx._h, C.byref(cs), ts, C.c_uint64(inst.m), bytes(coms), bytes(proof), C.c_uint64(len(proof)), SEED, C.c_uint32(flags))
+    return s, ts.raw[:203]
+
+
+def test_prover_and_verifier_share_one_script_at_its_edges(ctx):
+    """The transcript steps that prove(), prove_batch() and the verifier share, where they can go wrong: n = 1 (lg N = 0: no inner-product round), n = 2,
+    n = 3 (padded to N = 4), the range8 fixture and a 64-bit bounds check (m > 0: commitments, t_x_blinding takes <w_V, v_blinding>), each under flags
+    0..3, all in ONE call.  Every item: the bytes and the final transcript state of bpg_r1cs_prove for it alone; bpg_r1cs_verify accepts it from the
+    state before the proof and leaves the PROVER's final state.  What this guards: the code AROUND the shared steps (which step each path calls when,
+    the `if lg N` branches, padding, the proof-byte layout, the tb[2] sum) at shapes other tests reach by accident.  What it cannot catch: a wrong label or
+    a wrong order INSIDE a shared step - all three roles would follow it together.  The reference's recorded proofs guard that (test_proof_fixtures.py,
+    test_gpu_parity.py, test_all_fixtures_in_one_call above)."""
+    circuits = [_rand_circuit(n, 40 + n) + (b"", b"") for n in (1, 2, 3)]
+    r8, r8_state, _ = G.build("range8")
+    circuits.append((r8, r8_state, r8.v_blinding, b""))
+    (c2, c2_state, c2_vb, _, _), c2_coms = _cfg2(ctx, 7)
+    circuits.append((c2, c2_state, c2_vb, c2_coms))
+    assert [c[0].n for c in circuits[:3]] == [1, 2, 3] and circuits[3][0].n == 8 and circuits[4][0].m > 0
+    items = [(inst, state, vb, hashlib.sha256(b"edge %d %d" % (k, fl)).digest(), fl) for k, (inst, state, vb, _) in enumerate(circuits) for fl in range(4)]
+    res, st = ctx.prove_batch(items, return_status=True)
+    assert st == [0] * len(items)
+    for k, (it, (proof, state)) in enumerate(zip(items, res)):
+        assert (0, proof, state) == _alone(ctx, it), k
+        assert len(proof) == (353 if it[4] & 1 else 448) + 64 * max(it[0].n - 1, 0).bit_length() + 64, k
+        assert _verify(ctx, it[0], it[1], circuits[k // 4][3], proof, it[4]) == (0, state), k
+
+
 def _launches(ctx, items):
     ctx.profile_set(2)
     ctx.prove_batch(items)
