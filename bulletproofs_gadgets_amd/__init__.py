@@ -180,6 +180,17 @@ def mimc_hash(preimage: bytes):
     return out.raw
 
 
+def mimc_sponge(blocks):
+    """mimc::mimc_sponge_1 (src/mimc_hash/mimc.rs:26-40) on the host: blocks is a list of 32-byte little-endian values (or their concatenation), each
+    any 256-bit value (taken mod l) -> Scalar bytes.  A Merkle node is mimc_sponge([left, right])."""
+    data = bytes(blocks) if isinstance(blocks, (bytes, bytearray)) else b"".join(_exact("block", b, 32) for b in blocks)
+    if len(data) % 32:
+        raise ValueError("blocks must be a whole number of 32-byte values")
+    out = _buf(32)
+    _chk(lib().bpg_mimc_sponge(data, C.c_uint64(len(data) // 32), out))
+    return out.raw
+
+
 def scalar_op(op, a, b=None):
     out = _buf(32)
     _chk(lib().bpg_scalar_op(C.c_int32({"add": 0, "sub": 1, "mul": 2, "invert": 3, "reduce": 4, "from_wide": 5}[op]), a, b, out))
@@ -334,6 +345,26 @@ class Context:
         return [int(ok[i]) for i in range(n)], [(int.from_bytes(xy.raw[64 * i:64 * i + 32], "little"), int.from_bytes(xy.raw[64 * i + 32:64 * i + 64], "little"))
                                                 for i in range(n)]
 
+    def mimc_sponge_many(self, items, blocks_per_item):
+        """bpg_mimc_sponge_many: one mimc_sponge per item on the GPU.  items: a list of items (each blocks_per_item x 32 bytes, or a list of that many
+        32-byte blocks), or the concatenation of all of them -> list of 32-byte digests."""
+        if isinstance(items, (bytes, bytearray)):
+            data = bytes(items)
+        else:
+            data = b"".join(bytes(it) if isinstance(it, (bytes, bytearray)) else b"".join(it) for it in items)
+        size = 32 * blocks_per_item
+        if size <= 0 or len(data) % size:
+            raise ValueError("items must hold a whole number of items of blocks_per_item x 32 bytes")
+        count = len(data) // size
+        out = _buf(32 * count)
+        _chk(lib().bpg_mimc_sponge_many(self._h, C.c_uint64(count), C.c_uint64(blocks_per_item), data, out))
+        raw = out.raw                 # one copy of the buffer, not one per item
+        return [raw[32 * i:32 * i + 32] for i in range(count)]
+
+    def merkle_tree(self, leaves) -> "MerkleTree":
+        """bpg_merkle_build: the full MiMC Merkle tree over 2^depth leaves (a list of 32-byte values, or their concatenation), resident on the GPU."""
+        return MerkleTree(self, leaves)
+
     def profile_set(self, mode):
         _chk(lib().bpg_profile_set(self._h, C.c_int32(mode)))
 
@@ -414,6 +445,65 @@ class Context:
         cs = inst.cstruct()
         _chk(lib().bpg_r1cs_prove(self._h, C.byref(cs), ts, C.c_uint64(inst.m), v_blinding, rng_seed, C.c_uint32(flags), out, C.byref(ln)))
         return out.raw[:ln.value], ts.raw[:203]
+
+
+class MerkleTree:
+    """A full binary MiMC Merkle tree resident on the GPU of a context (bpg_merkle_*): node = mimc_sponge([left, right]) over the children as they are,
+    which is what MerkleTree256 constrains for a "(W W)" node.  Level 0 is the root, level `depth` the leaves."""
+
+    def __init__(self, ctx: "Context", leaves):
+        data = bytes(leaves) if isinstance(leaves, (bytes, bytearray)) else b"".join(_exact("leaf", x, 32) for x in leaves)
+        n = len(data) // 32
+        if len(data) % 32 or n < 1 or n & (n - 1):
+            raise ValueError("a full tree has 2^depth leaves of 32 bytes each")
+        self.ctx, self.depth, self._h = ctx, n.bit_length() - 1, C.c_void_p()
+        _chk(lib().bpg_merkle_build(ctx._h, C.c_uint32(self.depth), data, C.byref(self._h)))
+
+    def _handle(self):
+        if not self._h:
+            raise ValueError("this tree has been freed")
+        return self._h
+
+    def root(self):
+        out = _buf(32)
+        _chk(lib().bpg_merkle_root(self.ctx._h, self._handle(), out))
+        return out.raw
+
+    def nodes(self, level, first=0, count=None):
+        """`count` nodes of `level` from node `first` (default: the rest of the level) as 32-byte scalars."""
+        if count is None:
+            count = (1 << level) - first
+        out = _buf(32 * max(count, 0))
+        _chk(lib().bpg_merkle_nodes(self.ctx._h, self._handle(), C.c_uint32(level), C.c_uint64(first), C.c_uint64(count), out))
+        raw = out.raw
+        return [raw[32 * i:32 * i + 32] for i in range(count)]
+
+    def paths(self, indices):
+        """For every leaf index its `depth` siblings from the leaf level upward: [[sibling of the leaf, sibling of its parent, ...], ...]."""
+        k, d = len(indices), self.depth
+        out = _buf(32 * d * k)
+        _chk(lib().bpg_merkle_paths(self.ctx._h, self._handle(), C.c_uint64(k), (C.c_uint64 * max(k, 1))(*indices), out))
+        raw = out.raw
+        return [[raw[32 * (i * d + j):32 * (i * d + j) + 32] for j in range(d)] for i in range(k)]
+
+    def update(self, indices, leaves):
+        """Replace leaf indices[i] by leaves[i] (distinct indices) and recompute their ancestors."""
+        k = len(indices)
+        data = bytes(leaves) if isinstance(leaves, (bytes, bytearray)) else b"".join(_exact("leaf", x, 32) for x in leaves)
+        if len(data) != 32 * k:
+            raise ValueError("one 32-byte leaf per index")
+        _chk(lib().bpg_merkle_update(self.ctx._h, self._handle(), C.c_uint64(k), (C.c_uint64 * max(k, 1))(*indices), data))
+
+    def free(self):
+        if getattr(self, "_h", None):
+            lib().bpg_merkle_free(getattr(self.ctx, "_h", None), self._h)      # (a closed context released the tree's memory; the handle goes here)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 class ChainPool:

@@ -110,6 +110,7 @@ void Prover::start_blinding(const uint8_t rng_seed[32], uint64_t max_multipliers
 
 // ---------------------------------------------------------------------------------------- handles
 struct bpg_ctx { Engine *engine; };
+struct bpg_merkle { DeviceMerkle *t; };
 struct bpg_circuit { DeviceCircuit *dc; uint64_t n, m; bool is_template = false; uint64_t n_params = 0; };     // dc == nullptr: bpg_test_circuit_handle
 struct bpg_transcript { Transcript t; };
 struct bpg_prover { Prover *p; FlatCircuit flat; std::vector<uint8_t> v_bytes, vb_bytes; WitnessProgram program; };
@@ -967,6 +968,43 @@ bpg_status bpg_range_proof_verify(bpg_verifier *v, const bpg_lc *x, uint32_t n_b
 }
 bpg_status bpg_mimc_hash(const uint8_t *pre, uint64_t len, uint8_t out[32]) {
     return guard([&] { REQUIRE(pre && out && len > 0); mimc_hash(Bytes(pre, pre + len)).to_bytes(out); });
+}
+bpg_status bpg_mimc_sponge(const uint8_t *blocks, uint64_t n_blocks, uint8_t out[32]) {
+    return guard([&] {
+        REQUIRE(blocks && out && n_blocks > 0);
+        std::vector<Scalar> pre(n_blocks);
+        for (uint64_t i = 0; i < n_blocks; i++) std::memcpy(pre[i].w, blocks + 32 * i, 32);     // all 256 bits: `state += b` reduces them
+        mimc_sponge_1(pre, mimc_round_constants()).to_bytes(out);
+    });
+}
+// ---- MiMC Merkle trees on the device: the arguments that need no tree are checked here, the rest by the engine, all of it before the device is touched
+bpg_status bpg_mimc_sponge_many(bpg_ctx *ctx, uint64_t count, uint64_t blocks_per_item, const uint8_t *in, uint8_t *out) {
+    return guard([&] { REQUIRE(count > 0 && blocks_per_item > 0 && blocks_per_item <= (1ull << 22) && in && out && ctx); ctx->engine->mimc_sponge_many(count, blocks_per_item, in, out); });
+}
+bpg_status bpg_merkle_build(bpg_ctx *ctx, uint32_t depth, const uint8_t *leaves, bpg_merkle **out) {
+    return guard([&] {
+        REQUIRE(out); *out = nullptr;
+        REQUIRE(depth >= 1 && depth <= 24 && leaves && ctx);
+        std::unique_ptr<bpg_merkle> h(new bpg_merkle{nullptr});
+        h->t = ctx->engine->merkle_build(depth, leaves);
+        *out = h.release();
+    });
+}
+bpg_status bpg_merkle_root(bpg_ctx *ctx, bpg_merkle *t, uint8_t out[32]) { return guard([&] { REQUIRE(ctx && t && out); ctx->engine->merkle_nodes(t->t, 0, 0, 1, out); }); }
+bpg_status bpg_merkle_nodes(bpg_ctx *ctx, bpg_merkle *t, uint32_t level, uint64_t first, uint64_t count, uint8_t *out) {
+    return guard([&] { REQUIRE(ctx && t && (out || count == 0)); ctx->engine->merkle_nodes(t->t, level, first, count, out); });
+}
+bpg_status bpg_merkle_paths(bpg_ctx *ctx, bpg_merkle *t, uint64_t count, const uint64_t *indices, uint8_t *siblings_out) {
+    return guard([&] { REQUIRE(ctx && t && (count == 0 || (indices && siblings_out))); ctx->engine->merkle_paths(t->t, count, indices, siblings_out); });
+}
+bpg_status bpg_merkle_update(bpg_ctx *ctx, bpg_merkle *t, uint64_t count, const uint64_t *indices, const uint8_t *leaves) {
+    return guard([&] { REQUIRE(ctx && t && (count == 0 || (indices && leaves))); ctx->engine->merkle_update(t->t, count, indices, leaves); });
+}
+void bpg_merkle_free(bpg_ctx *ctx, bpg_merkle *t) {
+    (void)ctx;                      // the tree knows its context: its memory is released there whatever is passed here
+    if (!t) return;
+    Engine::merkle_free(t->t);
+    delete t;
 }
 bpg_status bpg_be_to_scalars(const uint8_t *be, uint64_t len, uint8_t *out, uint64_t *n_out) {
     return guard([&] {

@@ -100,6 +100,14 @@ struct SharedTables {
         table_bytes_add(device, -(int64_t)held);
     }
 };
+// The 486 MiMC round constants in Montgomery form, once per device: contexts created on one device share the buffer, and it goes with the last of them.
+struct MimcConstants {
+    int device = 0; DevBuf rc;
+    ~MimcConstants() { (void)hipSetDevice(device); rc.release(); }
+};
+static std::mutex g_mimc_mutex;
+void merkle_orphan(DeviceMerkle *t);                // (defined with DeviceMerkle, below) releases the device memory of a tree whose context is being destroyed
+static std::map<int, std::weak_ptr<MimcConstants>> g_mimc;
 static std::mutex g_tables_mutex;                   // held across a derivation: contexts created side by side derive once
 static std::map<std::pair<int, uint64_t>, std::weak_ptr<SharedTables>> g_tables;
 
@@ -225,7 +233,8 @@ struct DeviceCircuit {
     X(k_scan_apply) X(k_bucket_chunks) X(k_bucket_combine) X(k_bucket_combine_heavy) X(k_bucket_reduce) X(k_window_sums) X(k_window_sums_quad) X(k_decompress) X(k_ipa_s) X(k_verify_scalars) X(k_verify_scalars_acc) X(k_bench_fe_mul) \
     X(k_tt_bases) X(k_tt_multiples) X(k_tt_bases8) X(k_tt_multiples8) X(k_tt_round8) X(k_tt_factors) X(k_tt_advance) X(k_tt_round) X(k_tt_finish) X(k_blind_expand) X(k_tt_commit3) X(k_tt_commit3_finish) X(k_csc_count) X(k_csc_fill) X(k_csc_colptr) X(k_merge_insert) X(k_merge_plan) X(k_merge_groups) X(k_merge_members) X(k_merge_sum) \
     X(k_bt_commit3) X(k_bt_commit3_finish) X(k_bt_compress) X(k_bt_exp) X(k_bt_poly_t) X(k_bt_poly_eval) X(k_bt_factors) X(k_bt_advance) X(k_bt_round) \
-    X(k_bt_finish) X(k_bt_fold_scalars) X(k_witness_eval) X(k_witness_eval_batch) X(k_bt_commit_v)
+    X(k_bt_finish) X(k_bt_fold_scalars) X(k_witness_eval) X(k_witness_eval_batch) X(k_bt_commit_v) \
+    X(k_mimc_sponge) X(k_merkle_leaves) X(k_merkle_level) X(k_merkle_top) X(k_merkle_level_list) X(k_merkle_set_leaves) X(k_merkle_paths) X(k_merkle_export)
 enum KernelId {
 #define X(n) KID_##n,
     BPG_KERNELS(X)
@@ -248,6 +257,7 @@ struct Engine::Impl {
     std::vector<hipEvent_t> prof_pool;
     double prof_ms[KID_COUNT] = {0};
     std::vector<float> prof_wit_ms;     // the first 1024 k_witness_eval launches since the last reset, in launch order (a launch = a level of an assign)
+    std::vector<std::pair<int, float>> prof_merkle_ms;   // the first 512 launches of the tree-hashing kernels (k_merkle_level, _top, _level_list) since the last reset, in launch order
     uint64_t prof_count[KID_COUNT] = {0};
     double prof_alg_bytes[KID_COUNT] = {0}, prof_act_bytes[KID_COUNT] = {0}, prof_fm[KID_COUNT] = {0};
     bool prof_on(int id) const { return prof_mode == 2 || (prof_mode == 1 && (id == KID_k_fold_points || id == KID_k_fold_points_reg || id == KID_k_fold_points_split || id == KID_k_fold_points_wnaf || id == KID_k_fold_points_quad || id == KID_k_fold_points_quadw || id == KID_k_fold_points_regw || id == KID_k_bucket_chunks)); }
@@ -258,13 +268,18 @@ struct Engine::Impl {
     void prof_collect() {
         if (prof_open.empty()) return;
         HIPCHK(hipStreamSynchronize(st));
-        for (ProfRec &r : prof_open) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, r.a, r.b)); prof_ms[r.id] += ms; prof_count[r.id]++; if (r.id == KID_k_witness_eval && prof_wit_ms.size() < 1024) prof_wit_ms.push_back(ms); prof_pool.push_back(r.a); prof_pool.push_back(r.b); }
+        for (ProfRec &r : prof_open) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, r.a, r.b)); prof_ms[r.id] += ms; prof_count[r.id]++; if (r.id == KID_k_witness_eval && prof_wit_ms.size() < 1024) prof_wit_ms.push_back(ms); if ((r.id == KID_k_merkle_level || r.id == KID_k_merkle_top || r.id == KID_k_merkle_level_list) && prof_merkle_ms.size() < 512) prof_merkle_ms.emplace_back(r.id, ms); prof_pool.push_back(r.a); prof_pool.push_back(r.b); }
         prof_open.clear();
     }
-    void prof_reset() { prof_collect(); for (int i = 0; i < KID_COUNT; i++) { prof_ms[i] = 0; prof_count[i] = 0; prof_alg_bytes[i] = prof_act_bytes[i] = prof_fm[i] = 0; } prof_wit_ms.clear(); }
+    void prof_reset() { prof_collect(); for (int i = 0; i < KID_COUNT; i++) { prof_ms[i] = 0; prof_count[i] = 0; prof_alg_bytes[i] = prof_act_bytes[i] = prof_fm[i] = 0; } prof_wit_ms.clear(); prof_merkle_ms.clear(); }
     std::shared_ptr<SharedTables> shared;       // the generation of generator tables this context works on
     DevBuf gens;                                // view of shared->gens (not owned)
     DevBuf bases, scratch_ext, comp, small_in, small_sc;
+    // MiMC sponges and Merkle trees (hip/k_mimc.cuh): the round constants of this device (shared by its contexts), the staging buffers of the calls, and the trees
+    // this context built and has not freed (the destructor releases their device memory; bpg_merkle_free then only deletes the handle)
+    std::shared_ptr<MimcConstants> mimc;
+    DevBuf mk_in, mk_out;
+    std::vector<DeviceMerkle *> trees;
     // One arena for the large per-stream buffers whose lifetimes never overlap in stream order (round 5: 20 proving streams held 2.9 GB each):
     //   an MSM:        [digits | entries1] (dead once k_msm_sort2 has run) overlaid by the sweep's partial sums (slots); entries behind them
     //   poly phase:    flattened weights, powers of z and y (between the S sums and the first round of the inner-product argument)
@@ -710,8 +725,10 @@ Engine::~Engine() {
                       &impl_->starts, &impl_->cursor, &impl_->blocksum, &impl_->arena, &impl_->buckets, &impl_->partial, &impl_->msm_result,
                       &impl_->sLR, &impl_->yinvpow, &impl_->lv, &impl_->rv, &impl_->red_partial,
                       &impl_->red_out, &impl_->raw_rng, &impl_->extras, &impl_->ipa_s, &impl_->ipa_tabA, &impl_->ipa_tabB, &impl_->naf, &impl_->qsteps, &impl_->wsums, &impl_->wq_stage, &impl_->wq_tickets, &impl_->vfy_in, &impl_->vfy_pts, &impl_->vfy_ok, &impl_->vfy_sc, &impl_->vfy_ch, &impl_->vfy_small,
-                      &impl_->stale_flag, &impl_->tile_hist, &impl_->heavy, &impl_->plain, &impl_->open_keys, &impl_->medium, &impl_->tt_bases, &impl_->tt_table, &impl_->tt_f, &impl_->tt_c, &impl_->tt_partial, &impl_->grp_c, &impl_->ped_table, &impl_->s_parts, &impl_->starts1};
+                      &impl_->stale_flag, &impl_->tile_hist, &impl_->heavy, &impl_->plain, &impl_->open_keys, &impl_->medium, &impl_->tt_bases, &impl_->tt_table, &impl_->tt_f, &impl_->tt_c, &impl_->tt_partial, &impl_->grp_c, &impl_->ped_table, &impl_->s_parts, &impl_->starts1, &impl_->mk_in, &impl_->mk_out};
     for (DevBuf *b : bufs) b->release();
+    for (DeviceMerkle *t : impl_->trees) merkle_orphan(t);       // trees the host has not freed: their memory goes with the context, their handles stay valid
+    impl_->mimc.reset();
     impl_->shared.reset();                                   // the generator tables go with their last context
     impl_->h_raw.release(); impl_->h_small.release(); impl_->h_naf.release(); impl_->h_qsteps.release(); impl_->stage.release(); for (PinBuf &b : impl_->h_blind) b.release();
     for (auto &sd : impl_->slab_dev) {
@@ -743,6 +760,13 @@ std::string Engine::profile_report() {
     if (!impl_->prof_wit_ms.empty()) {
         out += ", \"_witness_launch_ms\": [";
         for (size_t i = 0; i < impl_->prof_wit_ms.size(); i++) { char b[32]; std::snprintf(b, sizeof b, "%s%.4f", i ? "," : "", impl_->prof_wit_ms[i]); out += b; }
+        out += "]";
+    }
+    if (!impl_->prof_merkle_ms.empty()) {
+        out += ", \"_merkle_launch_ms\": [";
+        for (size_t i = 0; i < impl_->prof_merkle_ms.size(); i++) {
+            char b[64]; std::snprintf(b, sizeof b, "%s[\"%s\", %.4f]", i ? "," : "", kKernelNames[impl_->prof_merkle_ms[i].first], impl_->prof_merkle_ms[i].second); out += b;
+        }
         out += "]";
     }
     bool first = false;
@@ -2829,6 +2853,202 @@ void Engine::verify_batch(size_t count, const VerifyItem *items, const uint8_t b
         try { status_out[k] = verify(c, *it.T, it.V, it.proof, it.proof_len, it.seed, it.flags); } catch (...) { if (own) free_circuit(c); throw; }
         if (own) free_circuit(c);
     }
+}
+
+// ------------------------------------------------------------------------------------------------ MiMC sponges and Merkle trees (hip/k_mimc.cuh)
+const std::vector<Scalar> &mimc_round_constants();      // host/gadgets.hpp (defined in capi.hip)
+
+struct DeviceMerkle {
+    Engine *owner = nullptr; uint32_t depth = 0;
+    DevBuf tree;            // 2^(depth+1) scm in heap order, Montgomery form; entry 0 is unused
+};
+
+namespace {
+void merkle_orphan(DeviceMerkle *t) { t->tree.release(); t->owner = nullptr; }
+constexpr uint32_t kMerkleMaxDepth = 24;
+constexpr uint64_t kSpongeMaxBlocks = 1ull << 22;                  // blocks of one item: 128 MB of input, what one piece of a call stages
+constexpr double kNodeProducts = 4.0 * BPG_MIMC_ROUNDS;             // Montgomery products of one two-block node
+// the round constants of the context's device, converted and uploaded by the first context that asks
+const scm *mimc_rc(Engine::Impl &I, int device) {
+    if (I.mimc) return I.mimc->rc.as<scm>();
+    std::lock_guard<std::mutex> lk(g_mimc_mutex);
+    std::shared_ptr<MimcConstants> sp = g_mimc[device].lock();
+    if (!sp) {
+        const std::vector<Scalar> &rc = mimc_round_constants();
+        std::vector<scm> h(rc.size());
+        for (size_t i = 0; i < rc.size(); i++) h[i] = to_scm(rc[i]);
+        sp = std::make_shared<MimcConstants>();
+        sp->device = device; sp->rc.ensure(h.size() * sizeof(scm));
+        HIPCHK(hipMemcpyAsync(sp->rc.p, h.data(), h.size() * sizeof(scm), hipMemcpyHostToDevice, I.st));
+        HIPCHK(hipStreamSynchronize(I.st));
+        g_mimc[device] = sp;
+    }
+    I.mimc = sp;
+    return sp->rc.as<scm>();
+}
+// `nodes` evaluations of the node function: 64 bytes read and 32 written each, 1,944 products (what the launch log of an update is checked against)
+void note_nodes(Engine::Impl &I, int id, uint64_t nodes) { I.prof_note(id, 96.0 * (double)nodes, 96.0 * (double)nodes, kNodeProducts * (double)nodes); }
+}  // namespace
+
+void Engine::mimc_sponge_many(uint64_t count, uint64_t blocks, const uint8_t *in, uint8_t *out) {
+    if (!in || !out || count == 0 || blocks == 0) throw std::invalid_argument("mimc_sponge_many: a null pointer, or no items, or no blocks per item");
+    if (blocks > kSpongeMaxBlocks || count > (1ull << 40)) throw std::invalid_argument("mimc_sponge_many: more than 2^22 blocks per item, or more than 2^40 items");
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    const scm *rc = mimc_rc(I, device_);
+    // pieces of at most 2^22 input scalars (128 MB); an item has at most that many blocks, so a piece holds at least one
+    const uint64_t per = kSpongeMaxBlocks / blocks;
+    for (uint64_t first = 0; first < count; first += per) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(per, count - first);
+        const size_t in_bytes = (size_t)n * blocks * 32;
+        I.mk_in.ensure(in_bytes); I.mk_out.ensure((size_t)n * 32);
+        HIPCHK(hipMemcpyAsync(I.mk_in.p, in + (size_t)first * blocks * 32, in_bytes, hipMemcpyHostToDevice, I.st));
+        BPG_LAUNCH(I, k_mimc_sponge, dim3(cdiv(n, 256)), dim3(256), I.mk_in.as<uint32_t>(), I.mk_out.as<uint32_t>(), n, (uint32_t)blocks, rc);
+        HIPCHK(hipGetLastError());
+        I.prof_note(KID_k_mimc_sponge, (double)in_bytes + 32.0 * n, (double)in_bytes + 32.0 * n, 2.0 * BPG_MIMC_ROUNDS * (double)n * (double)blocks);
+        HIPCHK(hipMemcpyAsync(out + (size_t)first * 32, I.mk_out.p, (size_t)n * 32, hipMemcpyDeviceToHost, I.st));
+        HIPCHK(hipStreamSynchronize(I.st));         // the staging buffers may grow (and move) for the next piece
+    }
+}
+
+DeviceMerkle *Engine::merkle_build(uint32_t depth, const uint8_t *leaves) {
+    if (depth < 1 || depth > kMerkleMaxDepth) throw std::invalid_argument("merkle_build: depth must be 1..24");
+    if (!leaves) throw std::invalid_argument("merkle_build: null leaves");
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    const scm *rc = mimc_rc(I, device_);
+    const uint32_t nleaves = 1u << depth;
+    const size_t bytes = (size_t)2 * nleaves * sizeof(scm);
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    if (bytes + (64u << 20) > free_b)             // the tree and some room to work in: a failed 1 GB hipMalloc is a worse way to find out
+        throw DeviceError("merkle_build: a tree of depth " + std::to_string(depth) + " takes " + std::to_string(bytes >> 20) + " MB and the device has " + std::to_string(free_b >> 20) + " MB free");
+    std::unique_ptr<DeviceMerkle> t(new DeviceMerkle());
+    t->owner = this; t->depth = depth;
+    try {
+        t->tree.ensure(bytes);
+        scm *tree = t->tree.as<scm>();
+        HIPCHK(hipMemsetAsync(tree, 0, 2 * sizeof(scm), I.st));         // entry 0 is no node; the root is written last
+        HIPCHK(hipMemcpyAsync(tree + nleaves, leaves, (size_t)nleaves * 32, hipMemcpyHostToDevice, I.st));
+        BPG_LAUNCH(I, k_merkle_leaves, dim3(cdiv(nleaves, 256)), dim3(256), tree + nleaves, nleaves);
+        // one launch per level while a level has more parents than one block holds, then the rest of the way to the root in one launch
+        int level = (int)depth - 1;
+        for (; (1u << level) > BPG_MERKLE_TOP_PARENTS; level--) {
+            BPG_LAUNCH(I, k_merkle_level, dim3(cdiv(1u << level, 256)), dim3(256), tree, (uint32_t)level, rc);
+            note_nodes(I, KID_k_merkle_level, 1ull << level);
+        }
+        BPG_LAUNCH(I, k_merkle_top, dim3(1), dim3(256), tree, (uint32_t)level, rc);
+        note_nodes(I, KID_k_merkle_top, (2ull << level) - 1);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(I.st));
+    } catch (...) { (void)hipStreamSynchronize(I.st); t->tree.release(); throw; }
+    I.trees.push_back(t.get());
+    return t.release();
+}
+
+// The tree's memory is released on the context that built it, whichever caller frees it; a tree whose context is gone already (the destructor released its
+// memory and cleared `owner`) is only deleted.
+void Engine::merkle_free(DeviceMerkle *t) {
+    if (!t) return;
+    if (Engine *e = t->owner) {
+        (void)hipSetDevice(e->device_);
+        (void)hipStreamSynchronize(e->impl_->st);
+        t->tree.release();
+        std::vector<DeviceMerkle *> &live = e->impl_->trees;
+        live.erase(std::remove(live.begin(), live.end(), t), live.end());
+    }
+    delete t;
+}
+
+void Engine::merkle_nodes(DeviceMerkle *t, uint32_t level, uint64_t first, uint64_t count, uint8_t *out) {
+    if (!t || t->owner != this) throw std::invalid_argument("merkle_nodes: not a tree of this context");
+    if (level > t->depth || first > (1ull << level) || count > (1ull << level) - first) throw std::invalid_argument("merkle_nodes: level above the depth, or nodes beyond the level");
+    if (!count) return;
+    if (!out) throw std::invalid_argument("merkle_nodes: null output");
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    const scm *src = t->tree.as<scm>() + (1ull << level) + first;
+    const uint64_t per = 1ull << 20;
+    I.mk_out.ensure((size_t)std::min(count, per) * 32);
+    for (uint64_t at = 0; at < count; at += per) {          // stream order keeps a piece's kernel behind the copy of the piece before
+        const uint32_t n = (uint32_t)std::min(per, count - at);
+        BPG_LAUNCH(I, k_merkle_export, dim3(cdiv(n, 256)), dim3(256), src + at, n, I.mk_out.as<uint32_t>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out + (size_t)at * 32, I.mk_out.p, (size_t)n * 32, hipMemcpyDeviceToHost, I.st));
+    }
+    HIPCHK(hipStreamSynchronize(I.st));
+}
+
+void Engine::merkle_paths(DeviceMerkle *t, uint64_t count, const uint64_t *indices, uint8_t *out) {
+    if (!t || t->owner != this) throw std::invalid_argument("merkle_paths: not a tree of this context");
+    if (!count) return;
+    if (!indices || !out) throw std::invalid_argument("merkle_paths: null pointer");
+    const uint32_t d = t->depth;
+    std::vector<uint32_t> idx(count);
+    for (uint64_t i = 0; i < count; i++) {
+        if (indices[i] >> d) throw std::invalid_argument("merkle_paths: leaf index " + std::to_string(indices[i]) + " is beyond 2^depth");
+        idx[i] = (uint32_t)indices[i];
+    }
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    const uint64_t per = 1ull << 16;                        // items per launch: at most 2^16 * 24 threads and 50 MB of siblings
+    const size_t row = (size_t)d * 32;
+    I.mk_in.ensure((size_t)std::min(count, per) * 4); I.mk_out.ensure((size_t)std::min(count, per) * row);
+    for (uint64_t at = 0; at < count; at += per) {
+        const uint32_t n = (uint32_t)std::min(per, count - at);
+        HIPCHK(hipMemcpyAsync(I.mk_in.p, idx.data() + at, (size_t)n * 4, hipMemcpyHostToDevice, I.st));
+        BPG_LAUNCH(I, k_merkle_paths, dim3(cdiv((uint64_t)n * d, 256)), dim3(256), t->tree.as<scm>(), d, I.mk_in.as<uint32_t>(), n, I.mk_out.as<uint32_t>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out + (size_t)at * row, I.mk_out.p, (size_t)n * row, hipMemcpyDeviceToHost, I.st));
+    }
+    HIPCHK(hipStreamSynchronize(I.st));                     // (idx outlives every copy that reads it)
+}
+
+void Engine::merkle_update(DeviceMerkle *t, uint64_t count, const uint64_t *indices, const uint8_t *leaves) {
+    if (!t || t->owner != this) throw std::invalid_argument("merkle_update: not a tree of this context");
+    if (!count) return;
+    if (!indices || !leaves) throw std::invalid_argument("merkle_update: null pointer");
+    const uint32_t d = t->depth;
+    if (count > (1ull << d)) throw std::invalid_argument("merkle_update: more leaves than the tree has (an index is given twice)");
+    // every check first: a refused call leaves the tree as it was
+    std::vector<uint32_t> cur(count);
+    for (uint64_t i = 0; i < count; i++) {
+        if (indices[i] >> d) throw std::invalid_argument("merkle_update: leaf index " + std::to_string(indices[i]) + " is beyond 2^depth");
+        cur[i] = (uint32_t)indices[i];
+    }
+    // one staging buffer: [new leaves, 32 bytes each | their indices | the parents to recompute, level d-1 first: heap indices, sorted, each once]
+    const size_t idx_off = (size_t)count * 32, lists_off = idx_off + (size_t)count * 4;
+    std::vector<uint8_t> stage(lists_off);
+    std::memcpy(stage.data(), leaves, idx_off);
+    std::memcpy(stage.data() + idx_off, cur.data(), (size_t)count * 4);
+    std::sort(cur.begin(), cur.end());
+    if (std::adjacent_find(cur.begin(), cur.end()) != cur.end()) throw std::invalid_argument("merkle_update: a leaf index is given twice");
+    for (uint32_t &h : cur) h += 1u << d;
+    std::vector<uint32_t> level_count(d);
+    for (uint32_t lv = 0; lv < d; lv++) {                   // lv levels above the leaves' parents
+        for (uint32_t &h : cur) h >>= 1;
+        cur.erase(std::unique(cur.begin(), cur.end()), cur.end());      // two children of one parent recompute it once (halving keeps the order)
+        level_count[lv] = (uint32_t)cur.size();
+        const size_t at = stage.size();
+        stage.resize(at + cur.size() * 4);
+        std::memcpy(stage.data() + at, cur.data(), cur.size() * 4);
+    }
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    const scm *rc = mimc_rc(I, device_);
+    I.mk_in.ensure(stage.size());
+    scm *tree = t->tree.as<scm>();
+    HIPCHK(hipMemcpyAsync(I.mk_in.p, stage.data(), stage.size(), hipMemcpyHostToDevice, I.st));
+    BPG_LAUNCH(I, k_merkle_set_leaves, dim3(cdiv(count, 256)), dim3(256), tree, d, reinterpret_cast<const uint32_t *>(I.mk_in.as<uint8_t>() + idx_off),
+               I.mk_in.as<uint32_t>(), (uint32_t)count);
+    const uint32_t *list = reinterpret_cast<const uint32_t *>(I.mk_in.as<uint8_t>() + lists_off);
+    for (uint32_t lv = 0; lv < d; lv++) {
+        BPG_LAUNCH(I, k_merkle_level_list, dim3(cdiv(level_count[lv], 256)), dim3(256), tree, list, level_count[lv], rc);
+        note_nodes(I, KID_k_merkle_level_list, level_count[lv]);
+        list += level_count[lv];
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(I.st));
 }
 
 }  // namespace bpg

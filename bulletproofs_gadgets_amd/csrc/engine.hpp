@@ -20,6 +20,7 @@ struct ProveTimings {       // milliseconds, host wall clock around each phase (
 };
 
 struct DeviceCircuit;       // HBM-resident flattened R1CS instance
+struct DeviceMerkle;        // HBM-resident MiMC Merkle tree
 
 // What a host chooses at context creation (include/bpg.h bpg_config).  A field left at its "unset" value falls back to the environment
 // variable named beside it, then to the profile's default.
@@ -150,6 +151,16 @@ public:
     static void drop_witness(DeviceCircuit *tmpl);
     // the host-side checks of an instance (CSR shape, index ranges, sizes), which upload() and plan_template() start with: std::invalid_argument, no device work
     static void check_instance(const FlatView &c);
+    // MiMC sponges and Merkle trees on the device (include/bpg.h, "MiMC Merkle trees"; hip/k_mimc.cuh).  Every argument is checked before the device is touched
+    // (std::invalid_argument); the calls run on the context's stream and return synchronised.
+    // mimc_sponge_1 of count items of `blocks` 32-byte blocks each (any 256-bit value, taken mod l) -> count canonical scalars
+    void mimc_sponge_many(uint64_t count, uint64_t blocks, const uint8_t *in, uint8_t *out);
+    // the full tree over 2^depth leaves (depth 1..24; a leaf is any 256-bit value, taken mod l): node = sponge(left, right), resident in Montgomery form
+    DeviceMerkle *merkle_build(uint32_t depth, const uint8_t *leaves);
+    void merkle_nodes(DeviceMerkle *t, uint32_t level, uint64_t first, uint64_t count, uint8_t *out);      // level 0 = the root, level depth = the leaves
+    void merkle_paths(DeviceMerkle *t, uint64_t count, const uint64_t *indices, uint8_t *siblings_out);    // count x depth x 32, the leaf's sibling first
+    void merkle_update(DeviceMerkle *t, uint64_t count, const uint64_t *indices, const uint8_t *leaves);   // distinct indices; only their ancestors are recomputed
+    static void merkle_free(DeviceMerkle *t);       // on the tree's own context; a tree that outlived its context lost its memory then and is only deleted
     void synchronize();
     // HIP-event profile on the engine's own stream: mode 0 off, 1 = dominant kernel (k_fold_points) only, 2 = all kernels
     void profile_set(int mode);

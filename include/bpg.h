@@ -542,6 +542,35 @@ bpg_status bpg_range_proof_verify(bpg_verifier *v, const bpg_lc *x, uint32_t n_b
 /* mimc::mimc_hash(preimage) -> Scalar bytes (little-endian); conversions */
 bpg_status bpg_mimc_hash(const uint8_t *preimage, uint64_t len, uint8_t out[32]);
 bpg_status bpg_be_to_scalars(const uint8_t *be, uint64_t len, uint8_t *out, uint64_t *n_out);   /* conversions::be_to_scalars */
+/* MiMC Merkle trees: the native hash in front of Prover::commit - the root a verifier takes as its public input, the sibling lists that become the committed
+ * values of a path proof, and both again after an insertion.  bpg_mimc_sponge is mimc::mimc_sponge_1 on the host (no context): n_blocks blocks of 32
+ * little-endian bytes, each any 256-bit value (taken mod l, as the sponge's `state += block` takes it), canonical output.  The other calls run on the GPU of ctx:
+ *   bpg_mimc_sponge_many   count sponges of blocks_per_item blocks each (in: count x blocks_per_item x 32, out: count x 32), one lane per item; at most 2^22
+ *                          blocks per item (BPG_ERR_INVALID_ARGUMENT beyond).
+ *   bpg_merkle_build       the full binary tree over 2^depth leaves, depth 1..24 (depth 24 holds 1 GB of device memory; the size is checked against the free
+ *                          memory of the device first: BPG_ERR_DEVICE).  A node is sponge(left, right) over its children AS THEY ARE - leaves are not hashed
+ *                          first - which is what MerkleTree256 constrains for a "(W W)" node.  The tree stays resident until bpg_merkle_free.
+ *   bpg_merkle_root        the root; bpg_merkle_nodes: `count` nodes of `level` from node `first` (level 0 = the root, level depth = the leaves, 2^level nodes).
+ *   bpg_merkle_paths       for each leaf index its `depth` siblings from the leaf level upward (siblings_out[i][0] is the sibling of leaf indices[i]); an index
+ *                          may be given more than once.
+ *   bpg_merkle_update      replaces leaf indices[i] by leaves[i] and recomputes only the ancestors of the replaced leaves, level by level, each once.  The indices
+ *                          of one call are distinct: a repeated index is refused (there is no "last one wins"), and a refused call leaves the tree as it was.
+ * A depth of 0 or above 24, a NULL pointer, an index >= 2^depth, a level above depth, nodes beyond a level and count x blocks_per_item == 0 are
+ * BPG_ERR_INVALID_ARGUMENT before the device is touched.  The calls run on the context's stream and return synchronised; a tree belongs to the context that built
+ * it (another context's tree is BPG_ERR_INVALID_ARGUMENT); like every call on a context they are not re-entrant.  bpg_merkle_free releases the tree on the context
+ * that built it, whatever ctx is passed (NULL included).  Destroying a context releases the device memory of the trees it still holds: their handles stay valid
+ * for bpg_merkle_free alone, and every other call on them is BPG_ERR_INVALID_ARGUMENT.
+ * Out of scope: trees that are not full, the byte-preimage padding of mimc_hash on the device (pad on the host with bpg_be_to_scalars / bpg_mimc_hash's rules
+ * and hand the blocks over), flags of the file drivers, and a tree spread over more than one GPU.  (Additions to ABI version 7: no struct changes.) */
+typedef struct bpg_merkle bpg_merkle;
+bpg_status bpg_mimc_sponge(const uint8_t *blocks, uint64_t n_blocks, uint8_t out[32]);
+bpg_status bpg_mimc_sponge_many(bpg_ctx *ctx, uint64_t count, uint64_t blocks_per_item, const uint8_t *in, uint8_t *out);
+bpg_status bpg_merkle_build(bpg_ctx *ctx, uint32_t depth, const uint8_t *leaves /* 2^depth x 32 */, bpg_merkle **out);
+bpg_status bpg_merkle_root(bpg_ctx *ctx, bpg_merkle *t, uint8_t out[32]);
+bpg_status bpg_merkle_nodes(bpg_ctx *ctx, bpg_merkle *t, uint32_t level, uint64_t first, uint64_t count, uint8_t *out);
+bpg_status bpg_merkle_paths(bpg_ctx *ctx, bpg_merkle *t, uint64_t count, const uint64_t *indices, uint8_t *siblings_out /* count x depth x 32 */);
+bpg_status bpg_merkle_update(bpg_ctx *ctx, bpg_merkle *t, uint64_t count, const uint64_t *indices, const uint8_t *leaves /* count x 32 */);
+void bpg_merkle_free(bpg_ctx *ctx, bpg_merkle *t);
 /* test hook: `count` 64-byte TranscriptRng draws (merlin build_rng().rekey_with_witness_bytes("v_blinding")*.finalize(seed)), after
  * `skip` draws through the generic STROBE operations; bulk != 0 uses the prover's in-register bulk path. Same bytes either way. */
 bpg_status bpg_rng_draws(const uint8_t transcript_state[203], uint64_t m, const uint8_t *v_blinding, const uint8_t rng_seed[32],
