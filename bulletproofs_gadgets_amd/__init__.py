@@ -546,6 +546,34 @@ def test_verify_replay(n, m, gens_capacity, transcript_state, proof, seed, flags
     return status.value, bool(decided.value)
 
 
+def test_template_repeat_instance(inst, program, hints, count, param_values=None):
+    """bpg_test_template_repeat_instance (no device): the instance of `program`'s template repeated `count` times, row-major, as it stands after an assign of
+    param_values (count x n_params scalars, item-major; None: the constants of the template's own rows) -> (row_ptr, term_var, term_coef, coef bytes)"""
+    import numpy as np
+    cs, cp = inst.cstruct(), program.cstruct()
+    ch = hints.cstruct() if hints is not None and len(hints) else None
+    npar = len(program.param_rows)
+    rows, terms, ncoef = count * inst.q + 1, count * (inst.nnz + npar), inst.ncoef + count * npar
+    row_ptr, tv, tc, coef = np.zeros(rows, np.uint64), np.zeros(max(terms, 1), np.uint32), np.zeros(max(terms, 1), np.uint32), _buf(32 * ncoef)
+    nnz, nc = C.c_uint64(), C.c_uint64()
+    pv = None if param_values is None else _scalars32("param_values", param_values, count * npar)
+    _chk(lib().bpg_test_template_repeat_instance(C.byref(cs), C.byref(cp), C.byref(ch) if ch is not None else None, C.c_uint64(count), pv,
+                                                 C.c_void_p(row_ptr.ctypes.data), C.c_uint64(rows), C.c_void_p(tv.ctypes.data), C.c_void_p(tc.ctypes.data),
+                                                 C.c_uint64(terms), coef, C.c_uint64(ncoef), C.byref(nnz), C.byref(nc)))
+    return row_ptr, tv[:nnz.value].copy(), tc[:nnz.value].copy(), coef.raw[:32 * nc.value]
+
+
+def test_template_eval_repeat(inst, program, hints, count, values):
+    """bpg_test_template_eval_repeat (no device): the repeat-layout witness interpreter compiled for the host: count x m committed values ->
+    (a_L, a_R, a_O) of count x n scalars each"""
+    cs, cp = inst.cstruct(), program.cstruct()
+    ch = hints.cstruct() if hints is not None and len(hints) else None
+    out = [_buf(32 * count * inst.n) for _ in range(3)]
+    v = _scalars32("values", values, count * inst.m)
+    _chk(lib().bpg_test_template_eval_repeat(C.byref(cs), C.byref(cp), C.byref(ch) if ch is not None else None, C.c_uint64(count), v if v else None, *out))
+    return tuple(o.raw[:32 * count * inst.n] for o in out)
+
+
 class VerifyItem(C.Structure):
     """bpg_verify_item (frozen): one proof of bpg_r1cs_verify_batch."""
     _fields_ = [("inst", C.POINTER(R1CSInstance)), ("circuit", C.c_void_p), ("transcript_state", C.c_void_p), ("m", C.c_uint64), ("V", C.c_char_p),
@@ -711,6 +739,14 @@ class ResidentCircuit:
         if len(pv) % 32:
             raise ValueError("params must be a multiple of 32 bytes")
         _chk(lib().bpg_r1cs_assign(self.ctx._h, self._h, C.c_uint64(self.m), v if self.m else None, C.c_uint64(len(pv) // 32), pv if pv else None))
+
+    def repeat(self, count) -> "ResidentCircuit":
+        """bpg_r1cs_template_repeat: this template `count` times over as ONE resident template - the circuit of `count` host assemblies of the same gadget
+        code in one prover, replicated on the device (item k at multipliers k n.., committed values k m.., parameters k n_params..).  assign() then takes
+        count x m values and count x n_params constants, item-major; one prove() gives one proof for all the items.  Independent of this template."""
+        h = C.c_void_p()
+        _chk(lib().bpg_r1cs_template_repeat(self.ctx._h, self._h, C.c_uint64(count), C.byref(h)))
+        return ResidentCircuit(self.ctx, h, count * self.n, count * self.m, n_params=count * self.n_params)
 
     def prove(self, transcript_state, v_blinding, rng_seed=None, flags=0, timings=False):
         ts = _buf(203); ts.raw = _exact("transcript_state", transcript_state, 203)

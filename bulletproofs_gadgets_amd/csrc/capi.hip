@@ -349,6 +349,41 @@ bpg_status bpg_test_circuit_handle_hinted(const bpg_r1cs_instance *inst, const b
         *out = c;
     });
 }
+bpg_status bpg_r1cs_template_repeat(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, bpg_circuit **out) {
+    return guard([&] {
+        REQUIRE(out); *out = nullptr;
+        REQUIRE(ctx && tmpl);
+        if (count == 0) throw std::invalid_argument("template_repeat: count must be at least 1");
+        if (!tmpl->is_template) throw std::invalid_argument("template_repeat: the circuit is not a template (bpg_r1cs_upload_template)");
+        if (!tmpl->dc) throw std::invalid_argument("template_repeat: the handle has no device state (bpg_test_circuit_handle)");
+        DeviceCircuit *dc = ctx->engine->repeat_template(tmpl->dc, count);          // count 0, a repeat, sizes: refused there, before any device work
+        bpg_circuit *c = new bpg_circuit{dc, count * tmpl->n, count * tmpl->m}; c->is_template = true; c->n_params = count * tmpl->n_params;
+        *out = c;
+    });
+}
+bpg_status bpg_test_template_repeat_instance(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, uint64_t count,
+                                             const uint8_t *param_values, uint64_t *row_ptr, uint64_t row_cap, uint32_t *term_var, uint32_t *term_coef,
+                                             uint64_t term_cap, uint8_t *coef, uint64_t coef_cap, uint64_t *nnz_out, uint64_t *ncoef_out) {
+    return guard([&] {
+        REQUIRE(inst && program && row_ptr && nnz_out && ncoef_out);
+        const FlatCircuit f = Engine::template_repeat_instance_host(as_view(inst, false), program_view(program, hints), count, param_values);
+        const uint64_t nnz = f.term_var.size(), ncoef = f.coef.size() / 32;
+        if (row_cap < f.row_ptr.size()) throw std::invalid_argument("template_repeat_instance: row_ptr too short (" + std::to_string(f.row_ptr.size()) + " entries needed)");
+        if (term_cap < nnz || (nnz && (!term_var || !term_coef))) throw std::invalid_argument("template_repeat_instance: term_var / term_coef too short (" + std::to_string(nnz) + " entries needed)");
+        if (coef_cap < ncoef || (ncoef && !coef)) throw std::invalid_argument("template_repeat_instance: coef too short (" + std::to_string(ncoef) + " scalars needed)");
+        std::memcpy(row_ptr, f.row_ptr.data(), f.row_ptr.size() * 8);
+        if (nnz) { std::memcpy(term_var, f.term_var.data(), nnz * 4); std::memcpy(term_coef, f.term_coef.data(), nnz * 4); }
+        if (ncoef) std::memcpy(coef, f.coef.data(), ncoef * 32);
+        *nnz_out = nnz; *ncoef_out = ncoef;
+    });
+}
+bpg_status bpg_test_template_eval_repeat(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, uint64_t count,
+                                         const uint8_t *v, uint8_t *aL, uint8_t *aR, uint8_t *aO) {
+    return guard([&] {
+        REQUIRE(inst && program && aL && aR && aO && (inst->m == 0 || count == 0 || v));
+        Engine::template_eval_repeat_host(as_view(inst, false), program_view(program, hints), count, v, aL, aR, aO);
+    });
+}
 
 static void copy_timings(const ProveTimings &t, bpg_timings *o) {
     if (!o) return;

@@ -224,6 +224,9 @@ struct DeviceCircuit {
     bool has_host = false;
     FlatCircuit host;
     FlatView host_view;
+    // a template repeated on the device (repeat_template, hip/k_repeat.cuh): rep_count copies of a source template of rep_n multipliers and rep_m committed
+    // values, whose packed program (wit_stream, wit_segs, wit_level_ptr: copies of the source's) assign() walks once per (segment, item).  0: not a repeat.
+    uint64_t rep_count = 0, rep_n = 0, rep_m = 0;
 };
 
 // kernel ids for the optional HIP-event profile (bpg_profile_*)
@@ -233,7 +236,7 @@ struct DeviceCircuit {
     X(k_scan_apply) X(k_bucket_chunks) X(k_bucket_combine) X(k_bucket_combine_heavy) X(k_bucket_reduce) X(k_window_sums) X(k_window_sums_quad) X(k_decompress) X(k_ipa_s) X(k_verify_scalars) X(k_verify_scalars_acc) X(k_bench_fe_mul) \
     X(k_tt_bases) X(k_tt_multiples) X(k_tt_bases8) X(k_tt_multiples8) X(k_tt_round8) X(k_tt_factors) X(k_tt_advance) X(k_tt_round) X(k_tt_finish) X(k_blind_expand) X(k_tt_commit3) X(k_tt_commit3_finish) X(k_csc_count) X(k_csc_fill) X(k_csc_colptr) X(k_merge_insert) X(k_merge_plan) X(k_merge_groups) X(k_merge_members) X(k_merge_sum) \
     X(k_bt_commit3) X(k_bt_commit3_finish) X(k_bt_compress) X(k_bt_exp) X(k_bt_poly_t) X(k_bt_poly_eval) X(k_bt_factors) X(k_bt_advance) X(k_bt_round) \
-    X(k_bt_finish) X(k_bt_fold_scalars) X(k_witness_eval) X(k_witness_eval_batch) X(k_bt_commit_v) \
+    X(k_bt_finish) X(k_bt_fold_scalars) X(k_witness_eval) X(k_witness_eval_batch) X(k_bt_commit_v) X(k_repeat_colptr) X(k_repeat_entries) X(k_repeat_coef) X(k_witness_eval_repeat) \
     X(k_mimc_sponge) X(k_merkle_leaves) X(k_merkle_level) X(k_merkle_top) X(k_merkle_level_list) X(k_merkle_set_leaves) X(k_merkle_paths) X(k_merkle_export)
 enum KernelId {
 #define X(n) KID_##n,
@@ -256,7 +259,7 @@ struct Engine::Impl {
     std::vector<ProfRec> prof_open;
     std::vector<hipEvent_t> prof_pool;
     double prof_ms[KID_COUNT] = {0};
-    std::vector<float> prof_wit_ms;     // the first 1024 k_witness_eval launches since the last reset, in launch order (a launch = a level of an assign)
+    std::vector<float> prof_wit_ms;     // the first 1024 k_witness_eval / k_witness_eval_repeat launches since the last reset, in launch order (a launch = a level of an assign)
     std::vector<std::pair<int, float>> prof_merkle_ms;   // the first 512 launches of the tree-hashing kernels (k_merkle_level, _top, _level_list) since the last reset, in launch order
     uint64_t prof_count[KID_COUNT] = {0};
     double prof_alg_bytes[KID_COUNT] = {0}, prof_act_bytes[KID_COUNT] = {0}, prof_fm[KID_COUNT] = {0};
@@ -268,7 +271,7 @@ struct Engine::Impl {
     void prof_collect() {
         if (prof_open.empty()) return;
         HIPCHK(hipStreamSynchronize(st));
-        for (ProfRec &r : prof_open) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, r.a, r.b)); prof_ms[r.id] += ms; prof_count[r.id]++; if (r.id == KID_k_witness_eval && prof_wit_ms.size() < 1024) prof_wit_ms.push_back(ms); if ((r.id == KID_k_merkle_level || r.id == KID_k_merkle_top || r.id == KID_k_merkle_level_list) && prof_merkle_ms.size() < 512) prof_merkle_ms.emplace_back(r.id, ms); prof_pool.push_back(r.a); prof_pool.push_back(r.b); }
+        for (ProfRec &r : prof_open) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, r.a, r.b)); prof_ms[r.id] += ms; prof_count[r.id]++; if ((r.id == KID_k_witness_eval || r.id == KID_k_witness_eval_repeat) && prof_wit_ms.size() < 1024) prof_wit_ms.push_back(ms); if ((r.id == KID_k_merkle_level || r.id == KID_k_merkle_top || r.id == KID_k_merkle_level_list) && prof_merkle_ms.size() < 512) prof_merkle_ms.emplace_back(r.id, ms); prof_pool.push_back(r.a); prof_pool.push_back(r.b); }
         prof_open.clear();
     }
     void prof_reset() { prof_collect(); for (int i = 0; i < KID_COUNT; i++) { prof_ms[i] = 0; prof_count[i] = 0; prof_alg_bytes[i] = prof_act_bytes[i] = prof_fm[i] = 0; } prof_wit_ms.clear(); prof_merkle_ms.clear(); }
@@ -1446,6 +1449,13 @@ void Engine::assign(DeviceCircuit *d, const uint8_t *v, const uint8_t *param_val
     // a level's lanes are few (a 512-leaf tree: at most 256): spread them over waves until every SIMD of the device has one
     for (size_t l = 0; l + 1 < d->wit_level_ptr.size(); l++) {
         const uint32_t s0 = d->wit_level_ptr[l], ns = d->wit_level_ptr[l + 1] - s0;
+        if (d->rep_count) {         // a repeat: the source's level, a lane per (segment, item), consecutive lanes = consecutive items of one segment
+            const uint32_t K = (uint32_t)d->rep_count;
+            const uint32_t bps = cdiv(K, 64);                                       // 64 consecutive items of a segment per block, as k_witness_eval_batch has them
+            BPG_LAUNCH(I, k_witness_eval_repeat, dim3(ns * bps), dim3(64), d->wit_segs.as<uint4>() + s0, ns, bps, d->wit_stream.as<uint32_t>(), d->coef.as<scm>(),
+                       d->wit_v.as<scm>(), (uint32_t)d->rep_n, (uint32_t)d->rep_m, K, d->aL.as<scm>(), d->aR.as<scm>(), d->aO.as<scm>());
+            continue;
+        }
         const uint32_t lanes = std::min(64u, std::max(1u, cdiv(ns, I.wit_waves)));
         BPG_LAUNCH(I, k_witness_eval, dim3(cdiv(ns, lanes)), dim3(lanes), d->wit_segs.as<uint4>() + s0, ns, d->wit_stream.as<uint32_t>(), d->coef.as<scm>(),
                    d->wit_v.as<scm>(), d->aL.as<scm>(), d->aR.as<scm>(), d->aO.as<scm>());
@@ -1454,6 +1464,104 @@ void Engine::assign(DeviceCircuit *d, const uint8_t *v, const uint8_t *param_val
     HIPCHK(hipStreamSynchronize(I.st));
     d->has_witness = true;
 }
+// ------------------------------------------------------------------------------------------------ a template repeated on the device (hip/k_repeat.cuh)
+namespace {
+// what the instance format and the device layout hold (check_instance, the 29-bit variable index, 32-bit entry and row indices, the packer's slot index)
+void check_repeat_sizes(uint64_t count, uint64_t n, uint64_t m, uint64_t q, uint64_t nnz, uint64_t shared_coef, uint64_t n_params) {
+    if (count == 0) throw std::invalid_argument("template_repeat: count must be at least 1");
+    auto over = [&](uint64_t a, uint64_t limit) { return a && count > (limit - 1) / a; };       // count * a >= limit
+    if (over(n, 1ull << 27)) throw std::invalid_argument("template_repeat: count x n multipliers are too many (below 2^27)");
+    if (over(m, 1ull << 29)) throw std::invalid_argument("template_repeat: count x m committed values exceed the 29-bit variable index");
+    if (over(q, 1ull << 32)) throw std::invalid_argument("template_repeat: count x q constraints are too many (below 2^32)");
+    if (over(nnz, 1ull << 32)) throw std::invalid_argument("template_repeat: count x nnz terms are too many (below 2^32)");
+    if (over(3 * n + m, (1ull << 32) - 1)) throw std::invalid_argument("template_repeat: the repeated circuit has too many columns");
+    if (over(n_params, (uint64_t)WIT_COEF_INDEX_MASK + 1 - std::min<uint64_t>(shared_coef, WIT_COEF_INDEX_MASK)))
+        throw std::invalid_argument("template_repeat: count x n_params coefficient slots are too many");
+}
+}  // namespace
+
+DeviceCircuit *Engine::repeat_template(DeviceCircuit *src, uint64_t count) {
+    // every refusal first: nothing below this block runs for a refused call
+    if (!src) throw std::invalid_argument("template_repeat: no circuit");
+    if (!src->is_template) throw std::invalid_argument("template_repeat: the circuit is not a template (bpg_r1cs_upload_template)");
+    if (src->rep_count) throw std::invalid_argument("template_repeat: the circuit is itself a repeat (repeat the template it was made from)");
+    check_repeat_sizes(count, src->n, src->m, src->q, src->nnz, src->param_first, src->n_params);
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    const uint64_t K = count, n = K * src->n, m = K * src->m, q = K * src->q, nnz = K * src->nnz, ncols = 3 * n + m + 1, ncoef = src->param_first + K * src->n_params;
+    const RepeatDims D{(uint32_t)src->n, (uint32_t)src->m, (uint32_t)src->q, (uint32_t)src->param_first, (uint32_t)src->n_params};
+    DeviceCircuit *d = new DeviceCircuit();
+    d->n = n; d->m = m; d->q = q; d->ncols = ncols; d->nnz = nnz; d->const_begin = K * src->const_begin; d->has_witness = false;
+    d->is_template = true; d->n_params = K * src->n_params; d->param_first = src->param_first; d->wit_level_ptr = src->wit_level_ptr;
+    d->rep_count = K; d->rep_n = src->n; d->rep_m = src->m;
+    try {
+        d->aL.ensure(n * sizeof(scm)); d->aR.ensure(n * sizeof(scm)); d->aO.ensure(n * sizeof(scm));
+        d->col_ptr.ensure((ncols + 1) * 8); d->ent_row.ensure((nnz ? nnz : 1) * 4); d->ent_coef.ensure((nnz ? nnz : 1) * 4);
+        d->coef.ensure((ncoef ? ncoef : 1) * sizeof(scm));
+        d->wit_stream.ensure(src->wit_stream.cap); d->wit_segs.ensure(src->wit_segs.cap); d->wit_v.ensure((m ? m : 1) * sizeof(scm));
+        HIPCHK(hipMemcpyAsync(d->wit_stream.p, src->wit_stream.p, src->wit_stream.cap, hipMemcpyDeviceToDevice, I.st));
+        HIPCHK(hipMemcpyAsync(d->wit_segs.p, src->wit_segs.p, src->wit_segs.cap, hipMemcpyDeviceToDevice, I.st));
+        const uint32_t gy = (uint32_t)std::min<uint64_t>(K, 1024);           // copies beyond the grid's y extent are a loop in the kernels
+        BPG_LAUNCH(I, k_repeat_colptr, dim3(cdiv(3 * src->n + src->m + 1, 256), gy), dim3(256), src->col_ptr.as<uint64_t>(), D, (uint32_t)K, d->col_ptr.as<uint64_t>());
+        if (src->nnz) BPG_LAUNCH(I, k_repeat_entries, dim3(cdiv(src->nnz, 256), gy), dim3(256), src->col_ptr.as<uint64_t>(), src->ent_row.as<uint32_t>(),
+                                 src->ent_coef.as<uint32_t>(), D, (uint32_t)K, src->nnz, d->ent_row.as<uint32_t>(), d->ent_coef.as<uint32_t>());
+        if (ncoef) BPG_LAUNCH(I, k_repeat_coef, dim3(cdiv(ncoef, 256)), dim3(256), src->coef.as<scm>(), D, (uint32_t)K, d->coef.as<scm>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(I.st));
+    } catch (...) { free_circuit(d); throw; }
+    return d;
+}
+
+namespace {
+// the rows of the repeat from the template's rows with their parameter slots: what k_repeat_* leave in HBM, row-major
+FlatCircuit repeat_rows(const TemplatePlan &T, uint64_t count) {
+    const FlatCircuit &s = T.slotted;
+    const uint64_t q = s.row_ptr.size() - 1, nnz = s.term_var.size();
+    check_repeat_sizes(count, s.n, s.m, q, nnz, T.param_first, T.n_params);
+    const RepeatDims D{(uint32_t)s.n, (uint32_t)s.m, (uint32_t)q, (uint32_t)T.param_first, (uint32_t)T.n_params};
+    FlatCircuit f; f.n = count * s.n; f.m = count * s.m;
+    f.row_ptr.reserve(count * q + 1); f.term_var.reserve(count * nnz); f.term_coef.reserve(count * nnz);
+    for (uint64_t k = 0; k < count; k++)
+        for (uint64_t r = 0; r < q; r++) {
+            for (uint64_t t = s.row_ptr[r]; t < s.row_ptr[r + 1]; t++) {
+                uint32_t var, coef, row;
+                repeat_map(D, (uint32_t)k, s.term_var[t], s.term_coef[t], (uint32_t)r, var, coef, row);
+                if (row + 1 != f.row_ptr.size()) throw std::logic_error("template_repeat: row map out of step");
+                f.term_var.push_back(var); f.term_coef.push_back(coef);
+            }
+            f.row_ptr.push_back(f.term_var.size());
+        }
+    f.coef.assign(s.coef.begin(), s.coef.begin() + 32 * T.param_first);
+    for (uint64_t k = 0; k < count; k++) f.coef.insert(f.coef.end(), s.coef.begin() + 32 * T.param_first, s.coef.end());
+    return f;
+}
+}  // namespace
+// TEST HOOK (bpg_test_template_repeat_instance): the repeated instance, row-major, as it stands after an assign of param_values (count x n_params x 32,
+// item-major, reduced as assign() reduces them; null: the slots keep the constants the template's rows carried)
+FlatCircuit Engine::template_repeat_instance_host(const FlatView &c, const WitnessProgramView &p, uint64_t count, const uint8_t *param_values) {
+    const TemplatePlan T = plan_template(c, p);
+    FlatCircuit f = repeat_rows(T, count);
+    if (param_values)
+        for (uint64_t i = 0; i < count * T.n_params; i++) Scalar::from_bytes_mod_order(param_values + 32 * i).to_bytes(&f.coef[32 * (T.param_first + i)]);
+    return f;
+}
+// TEST HOOK (bpg_test_template_eval_repeat): k_witness_eval_repeat on the host - one pass per level of the SOURCE, per segment every item, into the repeat's
+// layout (count x n scalars per vector, no padding rows); v: count x m x 32
+void Engine::template_eval_repeat_host(const FlatView &c, const WitnessProgramView &p, uint64_t count, const uint8_t *v, uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out) {
+    const TemplatePlan T = plan_template(c, p);
+    const PackedWitnessProgram &P = T.packed;
+    check_repeat_sizes(count, c.n, c.m, c.q, T.slotted.term_var.size(), T.param_first, T.n_params);
+    const std::vector<scm> coef = scalars_from_bytes(c.coef, c.ncoef), vv = scalars_from_bytes(v, count * c.m);
+    std::vector<scm> aL(count * c.n), aR(count * c.n), aO(count * c.n);
+    const std::vector<uint32_t> &lp = T.schedule.level_ptr;
+    for (size_t l = 0; l + 1 < lp.size(); l++)
+        for (uint32_t s = lp[l]; s < lp[l + 1]; s++)
+            for (uint64_t k = 0; k < count; k++)
+                witness_eval_repeat_lane(P.segs[s].first, P.segs[s].count, P.stream.data() + P.segs[s].stream, coef.data(), vv.data(), (uint32_t)c.n, (uint32_t)c.m, k,
+                                         aL.data(), aR.data(), aO.data());
+    scalars_to_bytes(aL, aL_out); scalars_to_bytes(aR, aR_out); scalars_to_bytes(aO, aO_out);
+}
+
 // ------------------------------------------------------------------------------------------------ equal-scalar merging of A_I, A_O (hip/k_merge.cuh)
 // Built once per uploaded witness, at its first prove() on the bucket-method path (the generator tables must exist; upload() may precede them).  Cost at
 // n = 993,384: a hash-table pass over the scalars, two scans over the table, one point addition per merged-away term and a batched normalisation.
@@ -2223,6 +2331,7 @@ bool Engine::lockstep_eligible(uint64_t n, uint32_t flags) const {
 }
 
 bool Engine::template_lockstep(const DeviceCircuit *d) { return d && d->is_template && d->has_host; }
+bool Engine::is_repeat(const DeviceCircuit *d) { return d && d->rep_count != 0; }
 void Engine::drop_witness(DeviceCircuit *d) {
     d->has_witness = false;
     d->merge_tried = false; d->mI.groups = d->mI.skipped = 0; d->mO.groups = d->mO.skipped = 0;

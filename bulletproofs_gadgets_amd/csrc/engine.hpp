@@ -89,6 +89,16 @@ public:
     // test hook (bpg_test_template_eval_batch): the BATCHED interpreter (k_witness_eval_batch) compiled for the host - level by level, every item of a
     // segment side by side, into the wave layout (count x N x 32 bytes per vector, item-major, N = padded size, padding rows zero); v: count x m x 32
     static void template_eval_batch_host(const FlatView &c, const WitnessProgramView &p, uint64_t count, const uint8_t *v, uint8_t *aL, uint8_t *aR, uint8_t *aO);
+    // A template repeated `count` times (include/bpg.h bpg_r1cs_template_repeat; hip/k_repeat.cuh): a new resident template of count x (n, q, m, n_params), built on
+    // the device from the source's resident matrix - copy k at multipliers k n.., committed values k m.., rows k q.., parameter slots k n_params.., everything else
+    // shared.  It owns copies of all it needs, holds no witness and no host rows; assign() evaluates it with the source's program, a lane per (segment, item).
+    // Refused (std::invalid_argument, before any device work): not a template, a repeat, count 0, sizes beyond the instance format.
+    DeviceCircuit *repeat_template(DeviceCircuit *tmpl, uint64_t count);
+    static bool is_repeat(const DeviceCircuit *c);
+    // test hooks (bpg_test_template_repeat_instance, bpg_test_template_eval_repeat): the repeated rows as k_repeat_* leave them, and the repeat-layout interpreter
+    // (k_witness_eval_repeat) compiled for the host; no device
+    static FlatCircuit template_repeat_instance_host(const FlatView &c, const WitnessProgramView &p, uint64_t count, const uint8_t *param_values);
+    static void template_eval_repeat_host(const FlatView &c, const WitnessProgramView &p, uint64_t count, const uint8_t *v, uint8_t *aL, uint8_t *aR, uint8_t *aO);
     // Prover::prove on a resident circuit. transcript: state after Prover::new + every "V" append (updated in place).
     std::vector<uint8_t> prove(DeviceCircuit *c, Transcript &transcript, const std::vector<Scalar> &v_blinding,
                                const uint8_t rng_seed[32], uint32_t flags, ProveTimings *timings = nullptr);

@@ -74,6 +74,7 @@ BPG_HD void witness_eval_segment(uint32_t first, uint32_t count, const uint32_t 
     }
 }
 
+#if defined(__HIPCC__)     // the kernels; everything above also compiles for the host alone (tests/hostcheck/template_repeat.cpp)
 // segs: (first multiplier, count, first record word, -) per segment of ONE level.  Blocks are small (the engine spreads a level's few hundred lanes
 // over many waves: a lane alone in its wave reads one cache line per load, 64 lanes read 64).
 __global__ void __launch_bounds__(64) k_witness_eval(const uint4 *__restrict__ segs, uint32_t nseg, const uint32_t *__restrict__ stream,
@@ -97,5 +98,6 @@ __global__ void __launch_bounds__(64) k_witness_eval_batch(const uint4 *__restri
     const size_t b = (size_t)item << lgN;
     witness_eval_segment(sd.x, sd.y, stream + sd.z, coef, v + (size_t)item * m, aL + b, aR + b, aO + b);
 }
+#endif  // __HIPCC__
 
 }  // namespace bpg

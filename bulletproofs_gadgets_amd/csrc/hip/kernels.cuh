@@ -24,11 +24,13 @@
 //                                       witness evaluation - one launch per wave (bpg_r1cs_prove_template_batch_commit)
 //       circuit templates               k_witness_eval (k_witness.cuh): a_L, a_R, a_O of a resident circuit from the committed values of a fresh witness, by interpreting the
 //                                       recorded witness program - one launch per level of its schedule, one lane per segment (replaces the host's assembly + upload)
+//       a template repeated K times      (k_repeat.cuh) k_repeat_colptr, k_repeat_entries, k_repeat_coef: the K-fold circuit's column-major matrix from the template's
+//                                       resident one; k_witness_eval_repeat: its witness by the template's program, a lane per (segment, item) (one proof for K witnesses)
 //       MiMC sponges, Merkle trees       (k_mimc.cuh; no row of the survey: the native hash in front of Prover::commit) k_mimc_sponge: one lane per item; a tree of 2^d leaves in
 //                                       one heap-ordered array: k_merkle_leaves, k_merkle_level (one launch per level, one lane per parent), k_merkle_top (the levels of at
 //                                       most 256 parents in one launch), k_merkle_level_list + k_merkle_set_leaves (leaf updates: the ancestors only), k_merkle_paths
 //                                       (sibling lists), k_merkle_export (nodes as bytes)
-// The kernels live in k_points.cuh, k_scalars.cuh, k_ipa.cuh, k_verify.cuh, k_msm.cuh, k_merge.cuh, k_batch.cuh, k_witness.cuh and k_mimc.cuh, included at the end of this file in that
+// The kernels live in k_points.cuh, k_scalars.cuh, k_ipa.cuh, k_verify.cuh, k_msm.cuh, k_merge.cuh, k_batch.cuh, k_witness.cuh, k_repeat.cuh and k_mimc.cuh, included at the end of this file in that
 // order.
 // Data layout in HBM: scalars = 8 x u32 Montgomery form, 32 B each, AoS (lane i <-> element i: 2 x 16 B coalesced
 // loads); generator tables = affine Niels (y+x, y-x, 2dxy), 96 B per point, G at [0,N) and H at [N,2N); window tables =
@@ -72,4 +74,5 @@ __device__ __forceinline__ uint32_t msm_point_index(const MsmSegs &S, uint32_t s
 #include "k_merge.cuh"
 #include "k_batch.cuh"
 #include "k_witness.cuh"
+#include "k_repeat.cuh"
 #include "k_mimc.cuh"

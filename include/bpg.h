@@ -343,6 +343,35 @@ bpg_status bpg_test_template_eval_hinted(const bpg_r1cs_instance *inst, const bp
 bpg_status bpg_test_template_eval_batch_hinted(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, uint64_t count,
                                                const uint8_t *v, uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out);
 bpg_status bpg_test_circuit_handle_hinted(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, bpg_circuit **out);
+/* A TEMPLATE REPEATED K TIMES ON THE DEVICE: one proof for K witnesses of one circuit shape.  bpg_r1cs_template_repeat makes a new resident TEMPLATE from a
+ * template uploaded with bpg_r1cs_upload_template(_hinted): the circuit a host gets by assembling the template's gadget code `count` times in a row into ONE
+ * prover, each time with fresh variables.  Sizes: n' = count n, q' = count q, m' = count m, n_params' = count n_params.  Copy k of the template:
+ * multiplier i -> k n + i, committed value j -> k m + j, constraint row r -> k q + r, parameter row p -> parameter k n_params + p (item-major); the
+ * constant One and every coefficient that is no parameter slot are shared.  The matrix is replicated on the device from the template's resident copy; the
+ * host never sees a row, so a template of any size can be repeated.  The proof of the repeat has bpg_proof_size(count n, flags) bytes - it grows with
+ * log(count n), where count separate proofs grow with count - and is checked by ONE verification.
+ * The result is a template like any other: bpg_r1cs_assign takes count m values and count n_params constants, both item-major, and evaluates every item
+ * with the source's witness program, one launch per schedule level of the SOURCE and a lane per (segment, item), hinted segments included;
+ * bpg_r1cs_prove_resident, bpg_r1cs_verify_resident, bpg_r1cs_verify_batch and bpg_r1cs_free serve it as documented for templates.  It starts WITHOUT a
+ * witness, whatever the source holds (its parameter slots start as the source's stand), owns copies of everything it needs - the source may be freed
+ * first, the two are used independently - and keeps no host copy of its rows: bpg_r1cs_prove_template_batch(_commit) prove its items one at a time.
+ * The caller makes the count m commitments itself (one bpg_pedersen_commit launch) and appends them to the transcript in item order.
+ * Refused with BPG_ERR_INVALID_ARGUMENT before any device work (bpg_last_error names the reason): a NULL ctx, tmpl or out; count == 0; a circuit that
+ * is not a template; a handle without device state (bpg_test_circuit_handle); a circuit that is itself a repeat; count n >= 2^27, count m >= 2^29,
+ * count q or count nnz >= 2^32, 3 count n + count m + 1 >= 2^32, or 2^30 and more coefficient slots.  The generator capacity is checked when the repeat
+ * is proved or verified, as for every circuit.  (An addition to ABI version 7: look the symbol up.) */
+bpg_status bpg_r1cs_template_repeat(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, bpg_circuit **out);
+/* TEST HOOKS, no device needed (hints may be NULL).  bpg_test_template_repeat_instance: the repeated instance, row-major, as it stands after a
+ * bpg_r1cs_assign with param_values (count x n_params x 32, item-major; NULL: the slots keep the constants the template's rows carry).  Every parameter
+ * row's constant terms are ONE term on a slot of its own, the last of its row (as in the resident template).  row_ptr: count q + 1 entries (row_cap);
+ * term_var / term_coef: *nnz_out entries, at most count (nnz + n_params) (term_cap); coef: *ncoef_out = ncoef + count n_params scalars (coef_cap, in
+ * scalars).  A buffer that is too short is refused and named.  bpg_test_template_eval_repeat: the repeat-layout interpreter of bpg_r1cs_assign compiled for
+ * the host: v = count x m x 32 in, count x n x 32 bytes per vector out. */
+bpg_status bpg_test_template_repeat_instance(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, uint64_t count,
+                                             const uint8_t *param_values, uint64_t *row_ptr, uint64_t row_cap, uint32_t *term_var, uint32_t *term_coef,
+                                             uint64_t term_cap, uint8_t *coef, uint64_t coef_cap, uint64_t *nnz_out, uint64_t *ncoef_out);
+bpg_status bpg_test_template_eval_repeat(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, uint64_t count,
+                                         const uint8_t *v, uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out);
 
 /* measurement hooks (bench.py): HIP events on the engine's own stream. mode 0 off, 1 = dominant kernel only, 2 = all kernels;
  * report = JSON text {kernel: {count, total_ms, alg_bytes, device_bytes, field_mults}} accumulated since the last set. */
