@@ -120,56 +120,28 @@ const Scalar &Rinv_plain() { static Scalar r = R1_plain().invert(); return r; }
 scm to_scm(const Scalar &s) { Scalar m = s * R1_plain(); scm o; std::memcpy(o.v, m.w, 32); return o; }
 Scalar from_scm(const scm &m) { Scalar s; std::memcpy(s.w, m.v, 32); return s * Rinv_plain(); }
 
-// non-adjacent form of a canonical scalar; returns index of the top non-zero digit (-1 for zero)
-int32_t naf256(const Scalar &s, int8_t d[256]) {
-    uint64_t k[5] = {s.w[0], s.w[1], s.w[2], s.w[3], 0};
-    std::memset(d, 0, 256);
-    int32_t top = -1;
-    for (int i = 0; i < 256; i++) {
-        if ((k[0] | k[1] | k[2] | k[3] | k[4]) == 0) break;
-        if (k[0] & 1) {
-            int dig = 2 - (int)(k[0] & 3);           // +1 or -1
-            d[i] = (int8_t)dig; top = i;
-            if (dig == 1) k[0] -= 1;                  // low bit set, no borrow
-            else { for (int j = 0; j < 5; j++) { if (++k[j] != 0) break; } }
-        }
-        for (int j = 0; j < 4; j++) k[j] = (k[j] >> 1) | (k[j + 1] << 63);
-        k[4] >>= 1;
-    }
-    return top;
+// One msm() call: the segments (a kernel argument, layout fixed) and, beside them, what only the host needs to know about them.  The counts travel with
+// the segments they describe, so no call can be sized by what was pushed for another.
+struct MsmJob {
+    MsmSegs S;
+    uint32_t skipped;        // terms whose skip bit is set (they make no entries): the window width and the entry lists are sized for the rest
+    uint32_t alg_discount;   // terms that are not terms of the sum the call computes (merged-point terms stand in for terms that were skipped): roofline bookkeeping only
+};
+MsmJob job_new() { MsmJob J; std::memset(&J, 0, sizeof J); return J; }
+void seg_push(MsmJob &J, const scm *sc, const ge_niels *pts, uint32_t len, uint32_t msm, uint32_t lgblk = 31, const uint32_t *skip = nullptr) {
+    if (!len) return;
+    MsmSegs &S = J.S;
+    if (S.nseg >= BPG_MAX_SEGS) throw std::logic_error("too many MSM segments");
+    uint32_t k = S.nseg++;
+    S.sc[k] = sc; S.pts[k] = pts; S.len[k] = len; S.msm[k] = msm; S.lgblk[k] = lgblk; S.skip[k] = skip;
+    S.start[k + 1] = S.start[k] + len;
 }
-
-// width-w non-adjacent form of a canonical scalar: odd digits in (-2^(w-1), 2^(w-1)), at most one non-zero in any w consecutive positions;
-// returns the index of the top non-zero digit (-1 for zero).  Scalars are < 2^253, so position 255 is never reached.
-int32_t wnaf256(const Scalar &s, uint32_t w, int8_t d[256]) {
-    uint64_t k[5] = {s.w[0], s.w[1], s.w[2], s.w[3], 0};
-    std::memset(d, 0, 256);
-    int32_t top = -1;
-    const int64_t full = 1ll << w, half = 1ll << (w - 1);
-    for (int i = 0; i < 256; i++) {
-        if ((k[0] | k[1] | k[2] | k[3] | k[4]) == 0) break;
-        if (k[0] & 1) {
-            int64_t dig = (int64_t)(k[0] & (uint64_t)(full - 1));
-            if (dig >= half) dig -= full;
-            d[i] = (int8_t)dig; top = i;
-            if (dig > 0) { k[0] -= (uint64_t)dig; }                                                   // low bits cleared, no borrow
-            else { uint64_t add = (uint64_t)(-dig); for (int j = 0; j < 5; j++) { uint64_t t = k[j] + add; add = t < add ? 1 : 0; k[j] = t; if (!add) break; } }
-        }
-        for (int j = 0; j < 4; j++) k[j] = (k[j] >> 1) | (k[j + 1] << 63);
-        k[4] >>= 1;
-    }
-    return top;
+// the segment of merged points (hip/k_merge.cuh): `groups` terms that stand in for the `skipped` terms whose skip bits the other segments of the job carry
+void seg_push_merged(MsmJob &J, const scm *sc, const ge_niels *pts, uint32_t groups, uint32_t msm, uint32_t skipped) {
+    seg_push(J, sc, pts, groups, msm);
+    J.alg_discount += groups; J.skipped += skipped;
 }
-
-// bits [from, from + count) of a canonical scalar as a scalar of its own (count <= 128)
-Scalar scalar_bits(const Scalar &s, uint32_t from, uint32_t count) {
-    Scalar r = Scalar::zero();
-    for (uint32_t k = 0; k < count && from + k < 256; k++) {
-        const uint32_t b = from + k;
-        if ((s.w[b >> 6] >> (b & 63)) & 1ull) r.w[k >> 6] |= 1ull << (k & 63);
-    }
-    return r;
-}
+static_assert(sizeof(ge_ext) == MSM_POINT_BYTES, "host/msm_plan.hpp sizes the MSM workspace in extended points");
 
 constexpr uint32_t TEMPLATE_HOST_COPY_LG = 14;     // templates up to this padded size keep a host copy of their rows (the widest lockstep proof: BPG_TT_ORIG_LG <= 14)
 
@@ -324,8 +296,6 @@ struct Engine::Impl {
     uint32_t merge_equal = 1;       // BPG_MERGE: 0 A_I and A_O term by term; 1 equal scalars grouped once per uploaded witness (at its first proof); 2 grouped afresh in EVERY
                                     // proof (what a host that proves each witness once pays: the measurement behind bench.py's `merge_per_proof`); same bytes
     uint32_t merged_last = 0, merged_skipped_last = 0;   // witness of the last prove(): groups of equal scalars in A_I and A_O, and the terms they replace (0: none, or the table-driven path)
-    uint32_t msm_skipped_terms = 0; // terms of the next msm() call whose skip bit is set (they make no entries): the window width and the entry bound are sized for the rest
-    uint32_t msm_alg_discount = 0;  // terms of the next msm() call that are not terms of the sum it computes (merged-point terms stand in for terms that were skipped): roofline bookkeeping only
     void merge_witness(DeviceCircuit *c, const ge_niels *Gtab, const ge_niels *Htab);
     void merge_build(DeviceCircuit::MergeSet &M, const scm *A, const ge_niels *PA, uint32_t nA, const scm *B, const ge_niels *PB, uint32_t nB);
     double merge_ms_last = 0;       // host wall time of the last merge_witness() that did something (BPG_MERGE=1: to the end of its kernels; 2: to the end of the group count's read-back)
@@ -470,6 +440,11 @@ struct Engine::Impl {
     bool fold_quad = true;          // small folds: four lanes per output (BPG_FOLD_QUAD=0: the four-wave split kernel)
     bool fold_quad_w = true;        // ... with width-4 NAF against multiples the quads make themselves, in the groups after the first (BPG_FOLD_QUAD_W=0: plain NAF, addends in registers)
     bool fold_reg_w = true;         // the same steps with one lane per output where the register kernels would run (BPG_FOLD_REG_W=0: plain NAF, addends in registers)
+    FoldKnobs fold_knobs() const {
+        FoldKnobs k;
+        k.fold_wnaf = fold_wnaf; k.fold_split_max = fold_split_max; k.fold_quad = fold_quad; k.fold_quad_w = fold_quad_w; k.fold_reg_w = fold_reg_w; k.shared = shared_now;
+        return k;
+    }
     bool window_quad = true;        // window sums of a proof alone: four lanes per point, several blocks per window (BPG_WINDOW_QUAD=0: k_window_sums always)
     uint32_t window_quad_blocks = 288;   // ... at most this many blocks of four waves per launch (about one wave per SIMD on 256 CUs; BPG_WINDOW_QUAD_BLOCKS)
     uint32_t fold_group = 3;        // rounds per generator fold (BPG_FOLD_GROUP overrides, 1..5)
@@ -538,16 +513,16 @@ struct Engine::Impl {
     // sum_j 2^off(j) S_j (~254 dependent doublings of one point) and the point encoding run on the host (host/fe51.hpp).  msm() queues the
     // kernels and the copy and returns a ticket; msm_points() is called after the stream has been synchronised.
     struct MsmTicket { uint32_t slot, nmsm, W; };
-    static constexpr uint32_t WS_SLOTS = 8, WS_SLOT_BYTES = 4 * 128 * 128;     // nmsm <= 4, W <= 127 (c >= 2), 128 B per point
+    static constexpr uint32_t WS_SLOTS = 8, WS_SLOT_BYTES = (uint32_t)MSM_WS_SLOT_BYTES;
     PinBuf h_wsums; uint32_t ws_next = 0;
-    MsmTicket msm(const MsmSegs &S, uint32_t nmsm);
-    // what the last msm() call chose (host side only: read by the test hook Engine::test_msm after its stream sync, never on the proving path)
-    struct MsmLast {
-        MsmPlan P;
-        uint32_t nkeys = 0, CH = 0, nchunks = 0, live = 0;
-        bool shared = false, per_bucket = false, quad = false;
-        uint32_t window_blocks = 0, window_threads = 0;     // k_window_sums_quad: blocks per window; k_window_sums: threads per window
-    } msm_last;
+    MsmTicket msm(const MsmJob &J, uint32_t nmsm);
+    MsmKnobs msm_knobs() const {
+        MsmKnobs k;
+        k.cmin = msm_cmin; k.cmax = msm_cmax; k.cmax_shared = msm_cmax_shared; k.rseg = rseg; k.lgch = lgch; k.sweep_blocks_resident = sweep_blocks_resident;
+        k.window_quad = window_quad; k.window_quad_blocks = window_quad_blocks; k.shared = shared_now;
+        return k;
+    }
+    MsmRun msm_last{};                                      // the plan of the last msm() call (host side only: read by the test hook Engine::test_msm after its stream sync, never on the proving path)
     DevBuf test_skip;                                       // skip bitmaps of Engine::test_msm
     std::vector<h51::pt> msm_points(const MsmTicket &t) const {
         std::vector<h51::pt> out(t.nmsm);
@@ -1005,157 +980,60 @@ void Engine::pedersen_commit(size_t k, const uint8_t *v, const uint8_t *blind, u
 }
 
 // ------------------------------------------------------------------------------------------------ MSM pipeline
-Engine::Impl::MsmTicket Engine::Impl::msm(const MsmSegs &S, uint32_t nmsm) {
-    const uint32_t total = S.start[S.nseg];
-    if (nmsm < 1 || nmsm > 4) throw std::logic_error("msm: 1..4 results per call");
-    const uint32_t live = total - std::min(total, msm_skipped_terms);       // terms that can make entries (the others were merged away: MsmSegs::skip)
-    msm_skipped_terms = 0;
-    uint32_t per = live / nmsm; if (per < 1) per = 1;
-    const int cap = (int)(shared_now ? msm_cmax_shared : msm_cmax);
-    int cc = (int)ceil_log2(per) - 4; if (cc < (int)msm_cmin) cc = (int)msm_cmin; if (cc > cap) cc = cap;
-    uint32_t maxseg = 1; for (uint32_t k = 0; k < S.nseg; k++) maxseg = std::max(maxseg, S.len[k]);
-    // two-level sort: entry = sign | fb fine bits | 4 segment bits | index in segment -> 27 - fb index bits; at most 512 coarse bins
-    uint32_t fb = 0;
-    {
-        const uint32_t lgseg = ceil_log2(maxseg);
-        if (lgseg > 27) throw std::invalid_argument("msm: segment too long");
-        const uint32_t fbmax = std::min<uint32_t>(7, 27 - lgseg);
-        if (cc - 1 > (int)fbmax + 9) cc = (int)fbmax + 10;
-        fb = std::min<uint32_t>(fbmax, (uint32_t)cc - 1);
-    }
-    // W near-equal windows over 254 bits (window j starts at bit j * 254 / W: MsmPlan::off); the widest has cmax bits -> 2^(cmax-1) buckets per window
-    const uint32_t W = (254 + (uint32_t)cc - 1) / (uint32_t)cc, cmax = (254 + W - 1) / W, nb = 1u << (cmax - 1);
-    if (fb > cmax - 1) fb = cmax - 1;
-    const uint32_t nkeys = nmsm * W * nb;
-    const uint32_t seg = std::min(rseg, nb), nsegpw = nb / seg;        // both powers of two (rseg is validated at context creation)
-    // tiling plan: the segments of one MSM are contiguous; tiles never span two MSMs
-    MsmPlan P; std::memset(&P, 0, sizeof P);
-    P.nmsm = nmsm; P.W = W; P.nb = nb; P.fb = fb; P.CB = nb >> fb;
-    {
-        const uint32_t lg = 12;                                 // k_msm_scatter1 stages one tile of entries in LDS (MSM_TILE1_MAX)
-        P.lgTile = lg;
-        uint32_t k = 0;
-        for (uint32_t m = 0; m < nmsm; m++) {
-            P.term_start[m] = k < S.nseg ? S.start[k] : total;
-            while (k < S.nseg && S.msm[k] == m) k++;
-        }
-        if (k != S.nseg) throw std::logic_error("msm: segments must be grouped by result in ascending order");
-        P.term_start[nmsm] = total;
-        for (uint32_t m = 0; m < nmsm; m++) {
-            const uint32_t nt = cdiv(P.term_start[m + 1] - P.term_start[m], 1u << lg);
-            P.tile_start[m + 1] = P.tile_start[m] + nt; if (nt > P.tmax) P.tmax = nt;
-        }
-        if (P.tmax == 0) P.tmax = 1;
-        for (uint32_t j = 0; j < W; j++) { const uint32_t bit = ((j + 1) * 254u) / W - 1; P.bias[bit >> 5] |= 1u << (bit & 31); }
-        for (uint32_t j = 0; j <= W; j++) P.off[j] = (uint8_t)((j * 254u) / W);
-    }
-    const uint32_t ntiles = P.tile_start[nmsm];
-    starts.ensure((size_t)(nkeys + 1) * 4);
-    buckets.ensure((size_t)nkeys * sizeof(ge_ext));
-    partial.ensure((size_t)2 * nmsm * W * nsegpw * sizeof(ge_ext));       // acc and run of every segment
-    // balanced sweep: CH sorted entries per thread.  About 32, adjusted so that the launch's blocks fill the device a whole number of times: the
-    // sweep keeps sweep_blocks_resident blocks of 256 threads on the CUs at once (4 waves per SIMD at its register count), and 4.25 rounds of
-    // blocks cost what 5 do.  BPG_LGCH pins a power of two instead (diagnostics).
-    const uint64_t Mub = (uint64_t)live * W;                    // upper bound of the entry count (zero digits are skipped)
-    uint32_t CH = 32;
-    if (lgch) CH = 1u << lgch;
-    else if (shared_now && Mub >= (uint64_t)sweep_blocks_resident * 256 * 64) CH = 64;      // other proofs fill the device and this sweep is long: longer chunks, half the boundary pieces to combine (18.7 against 19.2 ms per proof sustained)
-    else {
-        const uint64_t slots = (uint64_t)sweep_blocks_resident * 256;
-        uint64_t rounds = (Mub + slots * 16) / (slots * 32);    // nearest whole number of rounds at 32 entries per thread
-        if (rounds < 1) rounds = 1;
-        CH = (uint32_t)std::max<uint64_t>(4, (Mub + slots * rounds - 1) / (slots * rounds));
-    }
-    const uint32_t nchunks = cdiv(Mub ? Mub : 1, CH);
-    // arena layout of this call: [digits | entries1] overlaid by the sweep's partial sums, then entries
-    const size_t b_digits = al256((size_t)(total ? total : 1) * W * 2), b_e1 = al256((size_t)(live ? live : 1) * W * 4), b_entries = b_e1;
-    const size_t b_slots = al256((size_t)nchunks * 2 * sizeof(ge_ext));
-    const size_t b_front = std::max(b_digits + b_e1, b_slots);
-    arena.ensure(b_front + b_entries);
+// plan (host/msm_plan.hpp: every choice and every size), size the workspace from the plan, launch from the plan, ticket
+Engine::Impl::MsmTicket Engine::Impl::msm(const MsmJob &J, uint32_t nmsm) {
+    const MsmSegs &S = J.S;
+    const MsmRun R = plan_msm(MsmShape{S.nseg, S.len, S.msm, nmsm, J.skipped}, msm_knobs());
+    const MsmPlan &P = R.P;
+    const uint32_t total = R.total, W = P.W, nkeys = R.nkeys, nchunks = R.nchunks, CH = R.CH;
+    msm_last = R;
+    starts.ensure(R.bytes_starts);
+    buckets.ensure(R.bytes_buckets);
+    partial.ensure(R.bytes_partial);
+    arena.ensure(R.b_front + R.b_entries);
     uint16_t *digits_p = reinterpret_cast<uint16_t *>(arena_at(0));
-    uint32_t *entries1_p = reinterpret_cast<uint32_t *>(arena_at(b_digits)), *entries_p = reinterpret_cast<uint32_t *>(arena_at(b_front));
-    ge_ext *slots_p = reinterpret_cast<ge_ext *>(arena_at(0));
-    heavy.ensure(((size_t)nchunks / HEAVY_CHUNKS + 2) * 4); medium.ensure(((size_t)nchunks / 2 + 2) * 4);      // a bucket on the medium list crosses at least two boundaries
-    {
-        // (kernels.cuh, "two-level sort"): digits once, coarse partition with coalesced runs, fine counting sort inside each coarse bin
-        const uint64_t nflat64 = (uint64_t)nmsm * W * P.CB * P.tmax;
-        if (nflat64 >= (1ull << 31)) throw std::invalid_argument("msm: too many tiles");
-        const uint32_t nflat = (uint32_t)nflat64, nblk1 = cdiv(nflat, SCAN_CHUNK), K = nmsm * W * P.CB;
-        counts.ensure((size_t)(nflat + 1) * 4); starts1.ensure((size_t)(nflat + 1) * 4); cursor.ensure((size_t)(nflat + 1) * 4);
-        blocksum.ensure((size_t)(nblk1 + 1) * 4);
-        HIPCHK(hipMemsetAsync(counts.p, 0, (size_t)nflat * 4, st));        // tiles an MSM does not have (tmax is the longest MSM's count)
-        if ((size_t)W * P.CB * 4 > 64 * 1024) throw std::logic_error("msm: coarse histograms exceed the LDS of a block");
-        BPG_LAUNCH_LDS((*this), KID_k_msm_digits, k_msm_digits, dim3(ntiles ? ntiles : 1), dim3(512), (size_t)W * P.CB * 4, S, P, total, digits_p, counts.as<uint32_t>(), heavy.as<uint32_t>(), medium.as<uint32_t>());
-        BPG_LAUNCH((*this), k_scan_blocksums, dim3(nblk1), dim3(256), counts.as<uint32_t>(), nflat, blocksum.as<uint32_t>());
-        BPG_LAUNCH((*this), k_scan_apply, dim3(nblk1), dim3(256), counts.as<uint32_t>(), nflat, blocksum.as<uint32_t>(), starts1.as<uint32_t>(), cursor.as<uint32_t>());
-        if (ntiles) BPG_LAUNCH((*this), k_msm_scatter1, dim3(ntiles, W), dim3(256), S, P, digits_p, total, starts1.as<uint32_t>(), entries1_p);
-        BPG_LAUNCH((*this), k_msm_sort2, dim3(K), dim3(256), P, starts1.as<uint32_t>(), nflat, entries1_p, starts.as<uint32_t>(), entries_p);
-    }
-    {
-        open_keys.ensure((size_t)nchunks * 4);
-        ge_ext *slotA = slots_p, *slotB = slotA + nchunks;
-        // the true entry count is starts[nkeys] (device side); threads past it exit immediately
-        BPG_LAUNCH((*this), k_bucket_chunks, dim3(cdiv(nchunks, 256)), dim3(256), S, starts.as<uint32_t>(), entries_p,
-                   buckets.as<ge_ext>(), slotA, slotB, open_keys.as<uint32_t>(), nkeys, CH);
-        // roofline bookkeeping.  Algorithmic bytes: the information content of the MSM this launch sweeps, one scalar + one
-        // point = 64 B per TERM, counted once however many windows the term is cut into.  Device bytes: every (term, window) entry is a
-        // 4-byte index and a 96-byte affine Niels point.  Work: one mixed addition (7 field multiplications) per entry; Mub counts zero
-        // digits too (probability 2^-c each for full-width scalars).
-        prof_note(KID_k_bucket_chunks, 64.0 * (double)(total - std::min(total, msm_alg_discount)), 100.0 * (double)Mub, 7.0 * (double)Mub);
-        msm_alg_discount = 0;
-        // joining the pieces of buckets that cross chunk boundaries: one thread per boundary where chunks are at least as long as the average bucket
-        // (the shared-device shape: 64-entry chunks, ~32 entries per bucket), one thread per bucket where buckets are longer (a proof alone)
-        msm_last.per_bucket = (uint64_t)CH * nkeys < Mub;
-        if (!msm_last.per_bucket)
-            BPG_LAUNCH((*this), k_bucket_combine, dim3(cdiv(nchunks, 256)), dim3(256), starts.as<uint32_t>(), buckets.as<ge_ext>(), slotA, slotB, open_keys.as<uint32_t>(), nkeys, CH, heavy.as<uint32_t>(), medium.as<uint32_t>());
-        else
-            BPG_LAUNCH_ID((*this), KID_k_bucket_combine, k_bucket_combine_per_bucket, dim3(cdiv(nkeys, 256)), dim3(256), starts.as<uint32_t>(), buckets.as<ge_ext>(), slotA, slotB, nkeys, CH, heavy.as<uint32_t>());
-        BPG_LAUNCH((*this), k_bucket_combine_heavy, dim3(HEAVY_BLOCKS), dim3(256), starts.as<uint32_t>(), buckets.as<ge_ext>(), slotA, slotB, CH, heavy.as<uint32_t>(), medium.as<uint32_t>());
-    }
-    const uint32_t nred = nmsm * W * nsegpw;
-    BPG_LAUNCH((*this), k_bucket_reduce, dim3(cdiv(nred, 64)), dim3(64), buckets.as<ge_ext>(), starts.as<uint32_t>(), partial.as<ge_ext>(), nb, seg, nsegpw, nred);
-    wsums.ensure((size_t)nmsm * W * sizeof(ge_ext));
-    // a window's block: as many threads as it has segments, at most 512 for a proof alone (shortest chain) and 256 while the device is shared (fewest additions)
-    if (!shared_now && window_quad) {
-        // a proof alone: four lanes per point, a window spread over nblk blocks of 64 slots so that the launch is about one wave per SIMD (k_msm.cuh k_window_sums_quad);
-        // per = segments per slot, nblk = blocks per window (at most 64: one slot each in the last block's second stage)
-        const uint32_t nwin = nmsm * W;
-        uint32_t lgper = 0;
-        auto nblk_of = [&](uint32_t lp) { return std::max<uint32_t>(1u, nsegpw >> (6 + lp)); };
-        while (nblk_of(lgper) > 1 && ((uint64_t)nwin * nblk_of(lgper) > window_quad_blocks || nblk_of(lgper) > 64)) lgper++;
-        const uint32_t nblk = nblk_of(lgper);
-        wq_stage.ensure((size_t)nwin * nblk * 2 * sizeof(ge_ext));
-        if (!wq_tickets.p) { wq_tickets.ensure(1024 * 4); HIPCHK(hipMemsetAsync(wq_tickets.p, 0, 1024 * 4, st)); }
-        if (nwin > 1024) throw std::logic_error("msm: too many windows for the ticket array");
-        BPG_LAUNCH((*this), k_window_sums_quad, dim3(nblk, nwin), dim3(256), partial.as<ge_ext>(), wsums.as<ge_ext>(), wq_stage.as<ge_ext>(), wq_tickets.as<uint32_t>(), nsegpw, nred,
-                   ceil_log2(seg), lgper);
-        msm_last.quad = true; msm_last.window_blocks = nblk; msm_last.window_threads = 0;
-    } else {
-    const uint32_t wthreads = std::max<uint32_t>(64, std::min<uint32_t>(nsegpw, shared_now ? 256u : 512u));
-    BPG_LAUNCH((*this), k_window_sums, dim3(nmsm * W), dim3(wthreads), partial.as<ge_ext>(), wsums.as<ge_ext>(), nsegpw, nred, ceil_log2(seg));
-    msm_last.quad = false; msm_last.window_blocks = 0; msm_last.window_threads = wthreads;
-    }
-    msm_last.P = P; msm_last.nkeys = nkeys; msm_last.CH = CH; msm_last.nchunks = nchunks; msm_last.live = live;
-    msm_last.shared = shared_now;
+    uint32_t *entries1_p = reinterpret_cast<uint32_t *>(arena_at(R.b_digits)), *entries_p = reinterpret_cast<uint32_t *>(arena_at(R.b_front));
+    ge_ext *slotA = reinterpret_cast<ge_ext *>(arena_at(0)), *slotB = slotA + nchunks;
+    heavy.ensure(R.bytes_heavy); medium.ensure(R.bytes_medium);
+    counts.ensure(R.bytes_counts); starts1.ensure(R.bytes_counts); cursor.ensure(R.bytes_counts);
+    blocksum.ensure(R.bytes_blocksum);
+    // (kernels.cuh, "two-level sort"): digits once, coarse partition with coalesced runs, fine counting sort inside each coarse bin
+    HIPCHK(hipMemsetAsync(counts.p, 0, (size_t)R.nflat * 4, st));        // tiles an MSM does not have (tmax is the longest MSM's count)
+    BPG_LAUNCH_LDS((*this), KID_k_msm_digits, k_msm_digits, dim3(R.ntiles ? R.ntiles : 1), dim3(512), R.lds_digits, S, P, total, digits_p, counts.as<uint32_t>(), heavy.as<uint32_t>(), medium.as<uint32_t>());
+    BPG_LAUNCH((*this), k_scan_blocksums, dim3(R.nblk1), dim3(256), counts.as<uint32_t>(), R.nflat, blocksum.as<uint32_t>());
+    BPG_LAUNCH((*this), k_scan_apply, dim3(R.nblk1), dim3(256), counts.as<uint32_t>(), R.nflat, blocksum.as<uint32_t>(), starts1.as<uint32_t>(), cursor.as<uint32_t>());
+    if (R.ntiles) BPG_LAUNCH((*this), k_msm_scatter1, dim3(R.ntiles, W), dim3(256), S, P, digits_p, total, starts1.as<uint32_t>(), entries1_p);
+    BPG_LAUNCH((*this), k_msm_sort2, dim3(R.K), dim3(256), P, starts1.as<uint32_t>(), R.nflat, entries1_p, starts.as<uint32_t>(), entries_p);
+    open_keys.ensure(R.bytes_open_keys);
+    // the true entry count is starts[nkeys] (device side); threads past it exit immediately
+    BPG_LAUNCH((*this), k_bucket_chunks, dim3(cdiv(nchunks, 256)), dim3(256), S, starts.as<uint32_t>(), entries_p,
+               buckets.as<ge_ext>(), slotA, slotB, open_keys.as<uint32_t>(), nkeys, CH);
+    // roofline bookkeeping.  Algorithmic bytes: the information content of the MSM this launch sweeps, one scalar + one
+    // point = 64 B per TERM, counted once however many windows the term is cut into.  Device bytes: every (term, window) entry is a
+    // 4-byte index and a 96-byte affine Niels point.  Work: one mixed addition (7 field multiplications) per entry; Mub counts zero
+    // digits too (probability 2^-c each for full-width scalars).
+    prof_note(KID_k_bucket_chunks, 64.0 * (double)(total - std::min(total, J.alg_discount)), 100.0 * (double)R.Mub, 7.0 * (double)R.Mub);
+    if (!R.per_bucket)
+        BPG_LAUNCH((*this), k_bucket_combine, dim3(cdiv(nchunks, 256)), dim3(256), starts.as<uint32_t>(), buckets.as<ge_ext>(), slotA, slotB, open_keys.as<uint32_t>(), nkeys, CH, heavy.as<uint32_t>(), medium.as<uint32_t>());
+    else
+        BPG_LAUNCH_ID((*this), KID_k_bucket_combine, k_bucket_combine_per_bucket, dim3(cdiv(nkeys, 256)), dim3(256), starts.as<uint32_t>(), buckets.as<ge_ext>(), slotA, slotB, nkeys, CH, heavy.as<uint32_t>());
+    BPG_LAUNCH((*this), k_bucket_combine_heavy, dim3(HEAVY_BLOCKS), dim3(256), starts.as<uint32_t>(), buckets.as<ge_ext>(), slotA, slotB, CH, heavy.as<uint32_t>(), medium.as<uint32_t>());
+    BPG_LAUNCH((*this), k_bucket_reduce, dim3(cdiv(R.nred, 64)), dim3(64), buckets.as<ge_ext>(), starts.as<uint32_t>(), partial.as<ge_ext>(), P.nb, R.seg, R.nsegpw, R.nred);
+    wsums.ensure(R.bytes_wsums);
+    if (R.quad) {
+        wq_stage.ensure(R.bytes_wq_stage);
+        if (!wq_tickets.p) { wq_tickets.ensure(MSM_TICKETS * 4); HIPCHK(hipMemsetAsync(wq_tickets.p, 0, MSM_TICKETS * 4, st)); }
+        BPG_LAUNCH((*this), k_window_sums_quad, dim3(R.window_blocks, nmsm * W), dim3(256), partial.as<ge_ext>(), wsums.as<ge_ext>(), wq_stage.as<ge_ext>(), wq_tickets.as<uint32_t>(), R.nsegpw, R.nred,
+                   ceil_log2(R.seg), R.lgper);
+    } else
+        BPG_LAUNCH((*this), k_window_sums, dim3(nmsm * W), dim3(R.window_threads), partial.as<ge_ext>(), wsums.as<ge_ext>(), R.nsegpw, R.nred, ceil_log2(R.seg));
     HIPCHK(hipGetLastError());
-    if ((size_t)nmsm * W * sizeof(ge_ext) > WS_SLOT_BYTES) throw std::logic_error("msm: window sums exceed the host slot");
     h_wsums.ensure((size_t)WS_SLOTS * WS_SLOT_BYTES);
     MsmTicket t{ws_next, nmsm, W};
     ws_next = (ws_next + 1) % WS_SLOTS;
-    HIPCHK(hipMemcpyAsync(h_wsums.as<uint8_t>() + (size_t)t.slot * WS_SLOT_BYTES, wsums.p, (size_t)nmsm * W * sizeof(ge_ext), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h_wsums.as<uint8_t>() + (size_t)t.slot * WS_SLOT_BYTES, wsums.p, R.bytes_wsums, hipMemcpyDeviceToHost, st));
     return t;
 }
-
-namespace {
-void seg_push(MsmSegs &S, const scm *sc, const ge_niels *pts, uint32_t len, uint32_t msm, uint32_t lgblk = 31, const uint32_t *skip = nullptr) {
-    if (!len) return;
-    if (S.nseg >= BPG_MAX_SEGS) throw std::logic_error("too many MSM segments");
-    uint32_t k = S.nseg++;
-    S.sc[k] = sc; S.pts[k] = pts; S.len[k] = len; S.msm[k] = msm; S.lgblk[k] = lgblk; S.skip[k] = skip;
-    S.start[k + 1] = S.start[k] + len;
-}
-MsmSegs seg_new() { MsmSegs S; std::memset(&S, 0, sizeof S); return S; }
-}  // namespace
 
 void Engine::msm_gens(uint64_t first, uint64_t count, const uint8_t *s, const uint8_t *t, uint8_t out[32]) {
     if (first + count > gens_cap_) throw std::invalid_argument("msm_gens: range beyond capacity");
@@ -1169,10 +1047,10 @@ void Engine::msm_gens(uint64_t first, uint64_t count, const uint8_t *s, const ui
         HIPCHK(hipMemcpyAsync(I.small_sc.as<uint8_t>() + count * 32, t, count * 32, hipMemcpyHostToDevice, I.st));
         BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(2 * count, 256)), dim3(256), I.small_sc.as<uint32_t>(), I.sLR.as<scm>(), (uint32_t)(2 * count));
     }
-    MsmSegs S = seg_new();
-    seg_push(S, I.sLR.as<scm>(), I.gens.as<ge_niels>() + first, (uint32_t)count, 0);
-    seg_push(S, I.sLR.as<scm>() + count, I.gens.as<ge_niels>() + gens_cap_ + first, (uint32_t)count, 0);
-    const Impl::MsmTicket tk = I.msm(S, 1);
+    MsmJob J = job_new();
+    seg_push(J, I.sLR.as<scm>(), I.gens.as<ge_niels>() + first, (uint32_t)count, 0);
+    seg_push(J, I.sLR.as<scm>() + count, I.gens.as<ge_niels>() + gens_cap_ + first, (uint32_t)count, 0);
+    const Impl::MsmTicket tk = I.msm(J, 1);
     HIPCHK(hipStreamSynchronize(I.st));
     h51::pt_compress(out, I.msm_points(tk)[0]);
 }
@@ -1213,7 +1091,7 @@ std::string Engine::test_msm(uint32_t nmsm, uint32_t nseg, const MsmSegSpec *seg
         I.h2d(I.small_sc.p, scalars, total * 32);
         BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(total, 256)), dim3(256), I.small_sc.as<uint32_t>(), I.sLR.as<scm>(), (uint32_t)total);
     }
-    MsmSegs S = seg_new();
+    MsmJob J = job_new();
     uint64_t t0 = 0, w0 = 0;
     for (uint32_t k = 0; k < nseg; k++) {
         const MsmSegSpec &g = segs[k];
@@ -1224,16 +1102,16 @@ std::string Engine::test_msm(uint32_t nmsm, uint32_t nseg, const MsmSegSpec *seg
             I.h2d(I.test_skip.as<uint32_t>() + w0, g.skip, nw * 4);
             skip = I.test_skip.as<uint32_t>() + w0; w0 += nw;
         }
-        seg_push(S, I.sLR.as<scm>() + t0, I.gens.as<ge_niels>() + (g.table ? gens_cap_ : 0) + g.first, g.len, g.result, g.lgblk, skip);
+        seg_push(J, I.sLR.as<scm>() + t0, I.gens.as<ge_niels>() + (g.table ? gens_cap_ : 0) + g.first, g.len, g.result, g.lgblk, skip);
         t0 += g.len;
     }
-    I.msm_skipped_terms = (uint32_t)skipped;
-    const Impl::MsmTicket tk = I.msm(S, nmsm);
+    J.skipped = (uint32_t)skipped;
+    const Impl::MsmTicket tk = I.msm(J, nmsm);
     HIPCHK(hipStreamSynchronize(I.st));
     const std::vector<h51::pt> pts = I.msm_points(tk);
     for (uint32_t m = 0; m < nmsm; m++) h51::pt_compress(out + 32 * m, pts[m]);
     // evidence: the plan msm() took, and what its kernels left on the device
-    const Impl::MsmLast &L = I.msm_last;
+    const MsmRun &L = I.msm_last;
     std::vector<uint32_t> st(L.nkeys + 1);
     uint32_t hm[2] = {0, 0};
     HIPCHK(hipMemcpyAsync(st.data(), I.starts.p, st.size() * 4, hipMemcpyDeviceToHost, I.st));
@@ -1713,15 +1591,15 @@ void Engine::Impl::inner_product(Transcript &T, std::vector<uint8_t> &proof, uin
         BPG_LAUNCH_ID(I, KID_k_reduce_partials, k_reduce_partials_scaled, dim3(2), dim3(256), I.red_partial.as<scm>(), blocks, 2u, I.extras.as<scm>() + 3, w_m);
         Impl::MsmTicket tk;
         {
-            MsmSegs S = seg_new();
+            MsmJob J = job_new();
             const uint32_t lgblk = g_j ? lgh : 31u;                         // every other block of h points of the group-start tables
-            seg_push(S, sLG, Gst + h, (uint32_t)cnt, 0, lgblk);
-            seg_push(S, sLH, Hst, (uint32_t)cnt, 0, lgblk);
-            seg_push(S, I.extras.as<scm>() + 3, Bn, 1, 0);
-            seg_push(S, sRG, Gst, (uint32_t)cnt, 1, lgblk);
-            seg_push(S, sRH, Hst + h, (uint32_t)cnt, 1, lgblk);
-            seg_push(S, I.extras.as<scm>() + 4, Bn, 1, 1);
-            tk = I.msm(S, 2);
+            seg_push(J, sLG, Gst + h, (uint32_t)cnt, 0, lgblk);
+            seg_push(J, sLH, Hst, (uint32_t)cnt, 0, lgblk);
+            seg_push(J, I.extras.as<scm>() + 3, Bn, 1, 0);
+            seg_push(J, sRG, Gst, (uint32_t)cnt, 1, lgblk);
+            seg_push(J, sRH, Hst + h, (uint32_t)cnt, 1, lgblk);
+            seg_push(J, I.extras.as<scm>() + 4, Bn, 1, 1);
+            tk = I.msm(J, 2);
         }
         uint8_t lr[64];
         I.wait_stream();
@@ -1738,141 +1616,64 @@ void Engine::Impl::inner_product(Transcript &T, std::vector<uint8_t> &proof, uin
         }
         g_j++;
         if (g_j == g_r) {
-            // generator fold of the whole group: Gst'[i] = Gst[i] + sum_{t>=1} sG_t Gst[i + t*Mr], same for H, with
-            // sG_t = prod_k (u_k^2)^bit_k(t), sH_t = prod_k (u_k^-2 y^-(g_M/2^k))^bit_k(t), bit_k(t) = bit (g_r - k) of t
+            // generator fold of the whole group (host/fold_plan.hpp): the group scalars, which kernel folds, the scalars recoded for that kernel, one launch
             const uint32_t Mr = (uint32_t)(g_M >> g_r), nterms = (1u << g_r) - 1u;
-            std::vector<Scalar> fG(g_r), fH(g_r);
-            for (uint32_t k = 1; k <= g_r; k++) {
-                const Scalar &uk = g_us[k - 1]; const Scalar ukinv = uk.invert();
-                fG[k - 1] = uk * uk; fH[k - 1] = ukinv * ukinv * yinv_pow2[ceil_log2(g_M >> k)];
-            }
+            std::vector<Scalar> sG, sH;
+            fold_group_scalars(g_us, yinv_pow2, g_M, g_r, sG, sH);
             ge_niels *dst = (g_index & 1) ? I.ipa_tabB.as<ge_niels>() : I.ipa_tabA.as<ge_niels>();
             I.scratch_ext.ensure((size_t)2 * Mr * sizeof(ge_ext));         // the folded points before their normalisation (2^18 of them after the first group of three rounds at 2^20)
             // the group-start tables are the original generators: width-w NAF against their precomputed odd multiples (k_fold_points_wnaf) -
-            // unless no table fits the budget of this device, in which case the register kernels below fold them
-            const bool use_wnaf = I.fold_wnaf >= 3 && Gst == Gtab && Hst == Htab && Gtab == I.gens.as<ge_niels>() && 2 * Mr > I.fold_split_max
-                                  && I.odd_ensure();
-            if (use_wnaf) {
-                const uint32_t parts = I.eff_parts, L = I.fold_part_bits(), nq = nterms * parts;
-                const size_t dbytes = (size_t)4 * nq * 256;
-                I.h_naf.ensure(dbytes); I.naf.ensure(dbytes);
-                int8_t *hd = I.h_naf.as<int8_t>();
-                std::memset(hd, 0, dbytes);
-                int32_t top = -1; double adds_fm = 0;
-                for (uint32_t q = 0; q < nterms; q++) {
-                    const uint32_t t = q + 1;
-                    Scalar sg = Scalar::one(), sh = Scalar::one();
-                    for (uint32_t k = 1; k <= g_r; k++) if ((t >> (g_r - k)) & 1u) { sg = sg * fG[k - 1]; sh = sh * fH[k - 1]; }
-                    const Scalar cls_s[4] = {sg, sg * u_ch, sh, sh * u_ch};
-                    const uint64_t lo = (uint64_t)t * Mr, nB = !g_first ? 0 : (lo >= n ? Mr : (lo + Mr > n ? lo + Mr - n : 0));
-                    for (int cls = 0; cls < 4; cls++) {
-                        if ((cls & 1) && !g_first) continue;
-                        for (uint32_t part = 0; part < parts; part++) {
-                            int8_t *d = hd + ((size_t)cls * nq + (size_t)part * nterms + q) * 256;
-                            const int32_t tp = wnaf256(scalar_bits(cls_s[cls], part * L, L), I.eff_wnaf, d);
-                            if (tp > top) top = tp;
-                            int adds = 0; for (int k = 0; k < 256; k++) adds += d[k] != 0;
-                            adds_fm += 7.0 * adds * ((cls & 1) ? (double)nB : (double)(Mr - nB));
-                        }
-                    }
-                }
-                HIPCHK(hipMemcpyAsync(I.naf.p, hd, dbytes, hipMemcpyHostToDevice, st));
-                FoldWnaf fw; fw.Mr = Mr; fw.nterms = nterms; fw.first_group = g_first; fw.n = (uint32_t)n; fw.cap = (uint32_t)gens_cap; fw.top = top;
-                fw.parts = parts; fw.NM = 1u << (I.eff_wnaf - 2);
-                BPG_LAUNCH(I, k_fold_points_wnaf, dim3(cdiv(2 * Mr, 256)), dim3(256), I.gens.as<ge_niels>(), I.gens_odd.as<ge_niels>(), I.scratch_ext.as<ge_ext>(),
-                           I.naf.as<uint32_t>(), fw);
-                I.prof_note(KID_k_fold_points_wnaf, 32.0 * (2.0 * g_M + 2.0 * Mr), 96.0 * (2.0 * Mr + adds_fm / 7.0) + 128.0 * 2 * Mr, 2.0 * Mr * (8.0 * (top + 1) + 7.0) + adds_fm);
-            } else {
-            I.h_naf.ensure((size_t)4 * nterms * 16 * 4); I.naf.ensure((size_t)4 * nterms * 16 * 4);
-            uint32_t *hn = I.h_naf.as<uint32_t>();
-            std::memset(hn, 0, (size_t)4 * nterms * 16 * 4);
-            int32_t top = -1; double adds_fm = 0;
-            for (uint32_t q = 0; q < nterms; q++) {
-                const uint32_t t = q + 1;
-                Scalar sg = Scalar::one(), sh = Scalar::one();
-                for (uint32_t k = 1; k <= g_r; k++) if ((t >> (g_r - k)) & 1u) { sg = sg * fG[k - 1]; sh = sh * fH[k - 1]; }
-                const Scalar cls_s[4] = {sg, sg * u_ch, sh, sh * u_ch};
-                // lanes of term t that are padding generators (first group): i + t*Mr >= n
-                const uint64_t lo = (uint64_t)t * Mr, nB = !g_first ? 0 : (lo >= n ? Mr : (lo + Mr > n ? lo + Mr - n : 0));
-                for (int cls = 0; cls < 4; cls++) {
-                    if ((cls & 1) && !g_first) continue;
-                    int8_t dg[256]; const int32_t tp = naf256(cls_s[cls], dg);
-                    if (tp > top) top = tp;
-                    uint32_t *d = hn + ((size_t)cls * nterms + q) * 16; int adds = 0;
-                    for (int k = 0; k < 256; k++) { if (dg[k]) { d[k >> 5] |= 1u << (k & 31); adds++; } if (dg[k] < 0) d[8 + (k >> 5)] |= 1u << (k & 31); }
-                    adds_fm += 7.0 * adds * ((cls & 1) ? (double)nB : (double)(Mr - nB));
-                }
+            // unless no table fits the budget of this device, in which case the other kernels fold them
+            const FoldShape shape{Mr, nterms, g_first, Gst == Gtab && Hst == Htab && Gtab == I.gens.as<ge_niels>()};
+            const FoldKnobs knobs = I.fold_knobs();
+            const FoldKernel kernel = choose_fold(shape, knobs, fold_wants_tables(shape, knobs) && I.odd_ensure());
+            static const int kid_of[] = {KID_k_fold_points_wnaf, KID_k_fold_points_quadw, KID_k_fold_points_quad, KID_k_fold_points_split, KID_k_fold_points_regw,
+                                         KID_k_fold_points_reg, KID_k_fold_points};          // in the order of FoldKernel
+            const int fold_kid = kid_of[(int)kernel];
+            const dim3 grid(cdiv(2 * Mr, 256)), grid64(cdiv(2 * Mr, 64)), block(256);     // one lane per output; four lanes per output (and the split kernel)
+            ge_ext *fo = I.scratch_ext.as<ge_ext>();
+            // the scalars in the format the kernel reads, written to pinned memory and uploaded
+            FoldRecode rc; FoldWnaf fw; FoldQuadW fq; FoldGroup fg;
+            const bool wnaf = kernel == FoldKernel::Wnaf, steps = kernel == FoldKernel::QuadW || kernel == FoldKernel::RegW;
+            PinBuf &hbuf = steps ? I.h_qsteps : I.h_naf;
+            DevBuf &dbuf = steps ? I.qsteps : I.naf;
+            const size_t bytes = wnaf ? fold_wnaf_bytes(nterms, I.eff_parts) : steps ? (size_t)2 * QW_MAXSTEPS * 4 : fold_naf_words(nterms) * 4;
+            hbuf.ensure(bytes); dbuf.ensure(bytes);
+            if (wnaf) {                                         // width-w NAF digits per part, against the odd multiples odd_ensure() settled on
+                rc = fold_recode_wnaf(sG, sH, u_ch, Mr, n, g_first, I.eff_wnaf, I.eff_parts, I.fold_part_bits(), hbuf.as<int8_t>());
+                fw.Mr = Mr; fw.nterms = nterms; fw.first_group = g_first; fw.n = (uint32_t)n; fw.cap = (uint32_t)gens_cap; fw.top = rc.top;
+                fw.parts = I.eff_parts; fw.NM = 1u << (I.eff_wnaf - 2);
+            } else if (steps) {                                 // width-4 NAF steps; the multiples the kernel makes live in the arena - no multiscalar sum of this context is in flight during a fold
+                rc = fold_recode_steps(sG, sH, Mr, hbuf.as<uint32_t>(), fq);
+                I.arena.ensure((size_t)3 * nterms * 2 * Mr * sizeof(ge_pniels));
+            } else {                                            // plain NAF bitmaps
+                rc = fold_recode_naf(sG, sH, u_ch, Mr, n, g_first, hbuf.as<uint32_t>());
+                fg.Mr = Mr; fg.nterms = nterms; fg.first_group = g_first; fg.n = (uint32_t)n; fg.top = rc.top;
             }
-            HIPCHK(hipMemcpyAsync(I.naf.p, hn, (size_t)4 * nterms * 16 * 4, hipMemcpyHostToDevice, st));
-            FoldGroup fg; fg.Mr = Mr; fg.nterms = nterms; fg.first_group = g_first; fg.n = (uint32_t)n; fg.top = top;
-            int fold_kid = KID_k_fold_points;
-            {   // addends in registers when the group size has an instantiation (r = 1..4), from memory otherwise (r = 5)
-                const dim3 grid(cdiv(2 * Mr, 256)), block(256);
-                ge_ext *fo = I.scratch_ext.as<ge_ext>(); const uint32_t *nf = I.naf.as<uint32_t>();
-                const bool regs = nterms == 1 || nterms == 3 || nterms == 7 || nterms == 15;
-                const uint32_t split_max = (regs && I.shared_now) ? 0 : I.fold_split_max;    // other proofs fill the device: fewest instructions
-                // width-4 NAF steps against odd multiples that the fold kernel makes itself (k_ipa.cuh k_fold_points_quadw / _regw): one list of steps per class (G, H),
-                // the multiples in the arena - no multiscalar sum of this context is in flight during a fold
-                FoldQuadW fq; std::memset(&fq, 0, sizeof fq); fq.Mr = Mr; fq.nterms = nterms;
-                auto make_steps = [&]() {
-                    I.h_qsteps.ensure((size_t)2 * QW_MAXSTEPS * 4); I.qsteps.ensure((size_t)2 * QW_MAXSTEPS * 4);
-                    uint32_t *hs = I.h_qsteps.as<uint32_t>();
-                    double adds_w = 0, dbls_w = 0;
-                    for (uint32_t cls = 0; cls < 2; cls++) {
-                        std::vector<std::array<int8_t, 256>> dg(nterms);
-                        int32_t tp = -1;
-                        for (uint32_t q = 0; q < nterms; q++) {
-                            const uint32_t t = q + 1;
-                            Scalar sc1 = Scalar::one();
-                            for (uint32_t k = 1; k <= g_r; k++) if ((t >> (g_r - k)) & 1u) sc1 = sc1 * (cls ? fH[k - 1] : fG[k - 1]);
-                            tp = std::max(tp, wnaf256(sc1, 4, dg[q].data()));
-                        }
-                        uint32_t ns = 0, pending = 0;
-                        for (int32_t k = tp; k >= 0; k--) {
-                            if (ns) pending++;                              // doubling the identity ahead of the first addition is skipped
-                            for (uint32_t q = 0; q < nterms; q++) {
-                                const int d = dg[q][k];
-                                if (!d) continue;
-                                if (ns >= QW_MAXSTEPS || pending > 255) throw std::logic_error("fold: step list overflow");
-                                const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
-                                hs[cls * QW_MAXSTEPS + ns++] = pending | (q << 8) | ((mag >> 1) << 11) | ((d < 0 ? 1u : 0u) << 13);
-                                dbls_w += pending; pending = 0;
-                            }
-                        }
-                        fq.nsteps[cls] = ns; fq.tail[cls] = pending; adds_w += ns; dbls_w += pending;
-                    }
-                    HIPCHK(hipMemcpyAsync(I.qsteps.p, hs, (size_t)2 * QW_MAXSTEPS * 4, hipMemcpyHostToDevice, st));
-                    I.arena.ensure((size_t)3 * nterms * 2 * Mr * sizeof(ge_pniels));
-                    // bookkeeping below: field multiplications of the whole launch (8 per addition against a projective multiple; P, 2P, 3P, 5P, 7P and three conversions per term)
-                    adds_fm = (adds_w * 8.0 + nterms * 2.0 * (7.0 + 8.0 + 7.0 + 2 * 9.0 + 3.0)) * Mr; top = (int32_t)(dbls_w / 2.0) - 1;
-                };
-                if (2 * Mr <= split_max && nterms >= 1 && nterms <= 7 && I.fold_quad && I.fold_quad_w && !g_first && Mr % 64 == 0) {
-                    fold_kid = KID_k_fold_points_quadw;    // four lanes per output
-                    make_steps();
-                    BPG_LAUNCH_ID(I, fold_kid, k_fold_points_quadw, dim3(cdiv(2 * Mr, 64)), block, Gst, Hst, fo, I.qsteps.as<uint32_t>(), reinterpret_cast<fe *>(I.arena_at(0)), fq);
-                } else if (2 * Mr <= split_max && nterms >= 1 && nterms <= 7 && I.fold_quad) {
-                    fold_kid = KID_k_fold_points_quad;     // four lanes per output (kernels: k_points.cuh quad_*, k_ipa.cuh)
-                    BPG_LAUNCH_ID(I, fold_kid, k_fold_points_quad, dim3(cdiv(2 * Mr, 64)), block, Gst, Hst, fo, nf, fg);
-                } else if (2 * Mr <= split_max && nterms >= 3 && nterms <= 15) {
-                    fold_kid = KID_k_fold_points_split;
-                    BPG_LAUNCH_ID(I, fold_kid, k_fold_points_split, dim3(cdiv(2 * Mr, 64)), block, Gst, Hst, fo, nf, fg);
-                } else if (2 * Mr > split_max && I.fold_reg_w && !g_first && nterms >= 1 && nterms <= 7 && Mr % 256 == 0) {
-                    fold_kid = KID_k_fold_points_regw;     // one lane per output, every operand from memory: fewest instructions (a device shared with other proofs)
-                    make_steps();
-                    BPG_LAUNCH_ID(I, fold_kid, k_fold_points_regw, grid, block, Gst, Hst, fo, I.qsteps.as<uint32_t>(), reinterpret_cast<ge_pniels *>(I.arena_at(0)), fq);
-                } else if (regs) {
-                    fold_kid = KID_k_fold_points_reg;
-                    if (nterms == 1) BPG_LAUNCH_ID(I, fold_kid, k_fold_points_reg<1>, grid, block, Gst, Hst, fo, nf, fg);
-                    else if (nterms == 3) BPG_LAUNCH_ID(I, fold_kid, k_fold_points_reg<3>, grid, block, Gst, Hst, fo, nf, fg);
-                    else if (nterms == 7) BPG_LAUNCH_ID(I, fold_kid, k_fold_points_reg<7>, grid, block, Gst, Hst, fo, nf, fg);
-                    else BPG_LAUNCH_ID(I, fold_kid, k_fold_points_reg<15>, grid, block, Gst, Hst, fo, nf, fg);
-                } else BPG_LAUNCH(I, k_fold_points, grid, block, Gst, Hst, fo, nf, fg);
+            HIPCHK(hipMemcpyAsync(dbuf.p, hbuf.p, bytes, hipMemcpyHostToDevice, st));
+            const uint32_t *nf = dbuf.as<uint32_t>();
+            double device_bytes = 96.0 * 2 * g_M + 128.0 * 2 * Mr;          // 2*g_M points read at 96 B, 2*Mr written at 128 B
+            switch (kernel) {
+            case FoldKernel::Wnaf:
+                BPG_LAUNCH(I, k_fold_points_wnaf, grid, block, I.gens.as<ge_niels>(), I.gens_odd.as<ge_niels>(), fo, nf, fw);
+                device_bytes = 96.0 * (2.0 * Mr + rc.adds_fm / 7.0) + 128.0 * 2 * Mr;       // one point read per output and per addition
+                break;
+            case FoldKernel::QuadW: BPG_LAUNCH(I, k_fold_points_quadw, grid64, block, Gst, Hst, fo, nf, reinterpret_cast<fe *>(I.arena_at(0)), fq); break;
+            case FoldKernel::Quad: BPG_LAUNCH(I, k_fold_points_quad, grid64, block, Gst, Hst, fo, nf, fg); break;
+            case FoldKernel::Split: BPG_LAUNCH(I, k_fold_points_split, grid64, block, Gst, Hst, fo, nf, fg); break;
+            case FoldKernel::RegW: BPG_LAUNCH(I, k_fold_points_regw, grid, block, Gst, Hst, fo, nf, reinterpret_cast<ge_pniels *>(I.arena_at(0)), fq); break;
+            case FoldKernel::Reg:       // addends in registers: one instantiation per group size (r = 1..4)
+                if (nterms == 1) BPG_LAUNCH_ID(I, fold_kid, k_fold_points_reg<1>, grid, block, Gst, Hst, fo, nf, fg);
+                else if (nterms == 3) BPG_LAUNCH_ID(I, fold_kid, k_fold_points_reg<3>, grid, block, Gst, Hst, fo, nf, fg);
+                else if (nterms == 7) BPG_LAUNCH_ID(I, fold_kid, k_fold_points_reg<7>, grid, block, Gst, Hst, fo, nf, fg);
+                else BPG_LAUNCH_ID(I, fold_kid, k_fold_points_reg<15>, grid, block, Gst, Hst, fo, nf, fg);
+                break;
+            case FoldKernel::Mem: BPG_LAUNCH(I, k_fold_points, grid, block, Gst, Hst, fo, nf, fg); break;
             }
-            // bookkeeping for the roofline: 2*g_M points read + 2*Mr written at 32 B (information content) resp. 96/128 B (device formats);
-            // field multiplications: 8 per doubling, 7 per mixed addition (the split variant runs the doublings once per wave of a block)
-            I.prof_note(fold_kid, 32.0 * (2.0 * g_M + 2.0 * Mr), 96.0 * 2 * g_M + 128.0 * 2 * Mr,
-                        2.0 * Mr * (8.0 * (top + 1) * (fold_kid == KID_k_fold_points_split ? (nterms < 4 ? nterms : 4) : 1) + 7.0) + adds_fm);
-            }
+            // bookkeeping for the roofline: 2*g_M points read + 2*Mr written at 32 B (information content) resp. in the device formats; field
+            // multiplications: 8 per doubling, 7 per mixed addition (the split variant runs the doublings once per wave of a block)
+            I.prof_note(fold_kid, 32.0 * (2.0 * g_M + 2.0 * Mr), device_bytes,
+                        2.0 * Mr * (8.0 * (rc.top + 1) * (kernel == FoldKernel::Split ? (nterms < 4 ? nterms : 4) : 1) + 7.0) + rc.adds_fm);
             BPG_LAUNCH(I, k_normalize_niels, dim3(cdiv(cdiv(2 * Mr, NORM_K), 256)), dim3(256), I.scratch_ext.as<ge_ext>(), dst, 2 * Mr);
             HIPCHK(hipGetLastError());
             I.wait_stream();                               // h_naf is reused by the next group
@@ -2057,23 +1858,23 @@ std::vector<uint8_t> Engine::prove(DeviceCircuit *c, Transcript &T, const std::v
     // A_I's terms with equal scalars share their bucket entries (hip/k_merge.cuh): grouped once per uploaded witness, here at its first proof
     if (!tabled) { if (I.merge_equal == 2) c->merge_tried = false; I.merge_witness(c, Gtab, Htab); }
     I.merged_last = tabled ? 0u : c->mI.groups + c->mO.groups; I.merged_skipped_last = tabled ? 0u : c->mI.skipped + c->mO.skipped;
-    auto push_AI = [&](MsmSegs &S) {        // <a_L, G> + <a_R, H> + i_blinding * B_blinding as result 0
+    auto push_AI = [&](MsmJob &J) {        // <a_L, G> + <a_R, H> + i_blinding * B_blinding as result 0
         const bool mg = c->mI.groups != 0;
-        seg_push(S, c->aL.as<scm>(), Gtab, (uint32_t)n, 0, 31, mg ? c->mI.skipA.as<uint32_t>() : nullptr);
-        seg_push(S, c->aR.as<scm>(), Htab, (uint32_t)n, 0, 31, mg ? c->mI.skipB.as<uint32_t>() : nullptr);
-        if (mg) { seg_push(S, c->mI.sc.as<scm>(), c->mI.pts.as<ge_niels>(), c->mI.groups, 0); I.msm_alg_discount += c->mI.groups; I.msm_skipped_terms += c->mI.skipped; }
-        seg_push(S, I.extras.as<scm>() + 0, Bbn, 1, 0);
+        seg_push(J, c->aL.as<scm>(), Gtab, (uint32_t)n, 0, 31, mg ? c->mI.skipA.as<uint32_t>() : nullptr);
+        seg_push(J, c->aR.as<scm>(), Htab, (uint32_t)n, 0, 31, mg ? c->mI.skipB.as<uint32_t>() : nullptr);
+        if (mg) seg_push_merged(J, c->mI.sc.as<scm>(), c->mI.pts.as<ge_niels>(), c->mI.groups, 0, c->mI.skipped);
+        seg_push(J, I.extras.as<scm>() + 0, Bbn, 1, 0);
     };
-    auto push_AO = [&](MsmSegs &S) {        // <a_O, G> + o_blinding * B_blinding as result 1
+    auto push_AO = [&](MsmJob &J) {        // <a_O, G> + o_blinding * B_blinding as result 1
         const bool mg = c->mO.groups != 0;
-        seg_push(S, c->aO.as<scm>(), Gtab, (uint32_t)n, 1, 31, mg ? c->mO.skipA.as<uint32_t>() : nullptr);
-        if (mg) { seg_push(S, c->mO.sc.as<scm>(), c->mO.pts.as<ge_niels>(), c->mO.groups, 1); I.msm_alg_discount += c->mO.groups; I.msm_skipped_terms += c->mO.skipped; }
-        seg_push(S, I.extras.as<scm>() + 1, Bbn, 1, 1);
+        seg_push(J, c->aO.as<scm>(), Gtab, (uint32_t)n, 1, 31, mg ? c->mO.skipA.as<uint32_t>() : nullptr);
+        if (mg) seg_push_merged(J, c->mO.sc.as<scm>(), c->mO.pts.as<ge_niels>(), c->mO.groups, 1, c->mO.skipped);
+        seg_push(J, I.extras.as<scm>() + 1, Bbn, 1, 1);
     };
     if (!merged) {
-        MsmSegs S = seg_new();
-        push_AI(S); push_AO(S);
-        tk_aiao = I.msm(S, 2);
+        MsmJob J = job_new();
+        push_AI(J); push_AO(J);
+        tk_aiao = I.msm(J, 2);
     }
     const double t_rng0 = now_ms();
     if (!bs && !expanded) { I.h_raw.ensure((2 * n ? 2 * n : 1) * 64); I.raw_rng.ensure((2 * n ? 2 * n : 1) * 64); }      // the draws of a chain made inside this call; a blinding stream brings its own slabs
@@ -2091,11 +1892,11 @@ std::vector<uint8_t> Engine::prove(DeviceCircuit *c, Transcript &T, const std::v
             const bool last = next_piece == 2;
             next_piece++;
             if (pc.b == pc.a && !last) continue;
-            MsmSegs S = seg_new();
-            if (pc.a < n) seg_push(S, sL + pc.a, Gtab + pc.a, (uint32_t)(std::min<uint64_t>(pc.b, n) - pc.a), 0);
-            if (pc.b > n) { const uint64_t a2 = std::max<uint64_t>(pc.a, n) - n; seg_push(S, sR + a2, Htab + a2, (uint32_t)(pc.b - n - a2), 0); }
-            if (last) seg_push(S, I.extras.as<scm>() + 2, Bbn, 1, 0);
-            tk_s[nparts++] = I.msm(S, 1);
+            MsmJob J = job_new();
+            if (pc.a < n) seg_push(J, sL + pc.a, Gtab + pc.a, (uint32_t)(std::min<uint64_t>(pc.b, n) - pc.a), 0);
+            if (pc.b > n) { const uint64_t a2 = std::max<uint64_t>(pc.a, n) - n; seg_push(J, sR + a2, Htab + a2, (uint32_t)(pc.b - n - a2), 0); }
+            if (last) seg_push(J, I.extras.as<scm>() + 2, Bbn, 1, 0);
+            tk_s[nparts++] = I.msm(J, 1);
         }
     };
     // the slab on the device may still hold an earlier proof's draws: s_L, s_R must never be built from a stream whose upload failed
@@ -2181,12 +1982,12 @@ std::vector<uint8_t> Engine::prove(DeviceCircuit *c, Transcript &T, const std::v
         I.wait_stream();
         for (int k = 0; k < 3; k++) h51::pt_compress(pts + 32 * k, h51::pt_from_device(hp + 32 * k));
     } else if (merged) {
-        MsmSegs S = seg_new();
-        push_AI(S); push_AO(S);
-        seg_push(S, sL, Gtab, (uint32_t)n, 2);
-        seg_push(S, sR, Htab, (uint32_t)n, 2);
-        seg_push(S, I.extras.as<scm>() + 2, Bbn, 1, 2);
-        const Impl::MsmTicket tk = I.msm(S, 3);
+        MsmJob J = job_new();
+        push_AI(J); push_AO(J);
+        seg_push(J, sL, Gtab, (uint32_t)n, 2);
+        seg_push(J, sR, Htab, (uint32_t)n, 2);
+        seg_push(J, I.extras.as<scm>() + 2, Bbn, 1, 2);
+        const Impl::MsmTicket tk = I.msm(J, 3);
         I.wait_stream();
         const std::vector<h51::pt> P3 = I.msm_points(tk);
         for (int k = 0; k < 3; k++) h51::pt_compress(pts + 32 * k, P3[k]);
@@ -2764,12 +2565,12 @@ VerifyVecs verify_prep(Engine::Impl &I, const DeviceCircuit *c, const VerifyRepl
 // the ONE multiscalar multiplication of a verification: lv, rv on the first N generators of each half, vfy_sc on the proofs' own points and on B, B_blinding
 // behind them; true iff the sum is the identity.  Synchronises the stream
 bool verify_msm(Engine::Impl &I, uint64_t N, uint32_t npts) {
-    MsmSegs S = seg_new();
-    seg_push(S, I.lv.as<scm>(), I.gens.as<ge_niels>(), (uint32_t)N, 0);
-    seg_push(S, I.rv.as<scm>(), I.gens.as<ge_niels>() + I.gens_cap, (uint32_t)N, 0);
-    seg_push(S, I.vfy_sc.as<scm>(), I.vfy_pts.as<ge_niels>(), npts, 0);
-    seg_push(S, I.vfy_sc.as<scm>() + npts, I.bases.as<ge_niels>(), 2, 0);
-    const Engine::Impl::MsmTicket tk = I.msm(S, 1);
+    MsmJob J = job_new();
+    seg_push(J, I.lv.as<scm>(), I.gens.as<ge_niels>(), (uint32_t)N, 0);
+    seg_push(J, I.rv.as<scm>(), I.gens.as<ge_niels>() + I.gens_cap, (uint32_t)N, 0);
+    seg_push(J, I.vfy_sc.as<scm>(), I.vfy_pts.as<ge_niels>(), npts, 0);
+    seg_push(J, I.vfy_sc.as<scm>() + npts, I.bases.as<ge_niels>(), 2, 0);
+    const Engine::Impl::MsmTicket tk = I.msm(J, 1);
     HIPCHK(hipStreamSynchronize(I.st));
     uint8_t out[32];
     h51::pt_compress(out, I.msm_points(tk)[0]);

@@ -385,7 +385,7 @@ __global__ void __launch_bounds__(64) k_pedersen(const uint32_t *__restrict__ v,
 // group.  naf holds, per (class, t), the non-adjacent form as two 256-bit masks (nz, neg): [4][nterms][16] words, class =
 // 2*isH + isB.  A wave whose lanes agree on the class of every term takes the scalar path (s_cbranch on the digit: the
 // addition is skipped, not masked); the few waves that straddle a class boundary take the per-lane path.
-struct FoldGroup { uint32_t Mr, nterms, first_group, n; int32_t top; };
+// (FoldGroup and, further down, FoldWnaf, FoldQuadW and QW_MAXSTEPS: host/fold_plan.hpp, with the recoders that fill them)
 __global__ void __launch_bounds__(256) k_fold_points(const ge_niels *__restrict__ G, const ge_niels *__restrict__ H,
                                                      ge_ext *__restrict__ out /* 2*Mr */, const uint32_t *__restrict__ naf, const FoldGroup fg) {
     uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -478,7 +478,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
 // and a scalar s = sum_j s_j 2^(j*L) becomes `parts` short scalars on different tables: ONE chain of L doublings instead of 253 for the same
 // number of additions.  Table (part j, multiple 2m+1) sits at odd[(j * NM + m - 1) * tab] (NM = 2^(w-2); j = 0, m = 0 is the generator table itself).
 // dig: [4 classes][parts * nterms][256] with entry part * nterms + q holding the width-w NAF of part `part` of term q's scalar.
-struct FoldWnaf { uint32_t Mr, nterms, first_group, n, cap; int32_t top; uint32_t parts, NM; };
 __device__ __forceinline__ int32_t fold_wnaf_digit(const uint32_t *__restrict__ dig32, uint32_t cls, uint32_t nterms, uint32_t q, int k) {
     const uint32_t w = dig32[(cls * nterms + q) * 64u + ((uint32_t)k >> 2)];
     return (int32_t)(int8_t)(w >> (8u * ((uint32_t)k & 3u)));
@@ -618,8 +617,6 @@ __global__ void __launch_bounds__(256) k_fold_points_quad(const ge_niels *__rest
 // write consecutive addresses) and read back by the lanes that wrote them; 1P stays in registers.  The host turns the shared scalars into ONE list of steps per class
 // (G, H): step = doublings before the addition | term << 8 | multiple << 11 | sign << 13; the operand of the next step is loaded while the current one is computed.
 // Groups after the first only (no padding class); a block of 64 outputs lies in G or in H (Mr is a multiple of 64).
-#define QW_MAXSTEPS 1024
-struct FoldQuadW { uint32_t Mr, nterms, nsteps[2], tail[2]; };
 __global__ void __launch_bounds__(256) k_fold_points_quadw(const ge_niels *__restrict__ G, const ge_niels *__restrict__ H, ge_ext *__restrict__ out /* 2*Mr */,
                                                            const uint32_t *__restrict__ steps /* [2][QW_MAXSTEPS] */, fe *tabq /* [3*nterms][2*Mr][4] */, const FoldQuadW fg) {
     const uint32_t r = threadIdx.x & 3u;

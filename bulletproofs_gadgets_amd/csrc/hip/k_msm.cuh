@@ -19,14 +19,7 @@ __device__ __forceinline__ uint32_t msm_find_seg(const MsmSegs &S, uint32_t g) {
 // key = (msm * W + window) * nb + (|digit| - 1); entry = sign << 31 | seg (4 bits) << 27 | index-in-segment.
 // Signed digits come from a carry-free recoding: with bias = sum_j 2^(off(j)+wd(j)-1) added to the scalar once, digit j is
 // field_j(s + bias) - 2^(wd(j)-1), in [-2^(wd-1), 2^(wd-1)).
-struct MsmPlan {
-    uint32_t nmsm, W, nb, lgTile, tmax;
-    uint8_t off[132];            // off[j] = j * 254 / W, the first bit of window j, j <= W (the host fills it: the kernel divided by W twice per digit)
-    uint32_t fb, CB;             // two-level sort: a bucket index splits into CB coarse bins x 2^fb fine slots (nb = CB << fb)
-    uint32_t term_start[5];      // first global term of MSM m (term_start[nmsm] = total)
-    uint32_t tile_start[5];      // first tile of MSM m
-    uint32_t bias[8];
-};
+// (struct MsmPlan: host/msm_plan.hpp, with the planner that fills it)
 __device__ __forceinline__ int32_t msm_digit_biased(const uint32_t w[8], const MsmPlan &P, uint32_t win) {
     const uint32_t off = P.off[win], wd = P.off[win + 1] - off, wi = off >> 5, sh = off & 31;
     const uint64_t two = (uint64_t)w[wi] | ((uint64_t)(wi + 1 < 8 ? w[wi + 1] : 0u) << 32);
@@ -279,7 +272,6 @@ __global__ void __launch_bounds__(256) k_msm_sort2(MsmPlan P, const uint32_t *__
 // exclusive scan of counts[0..nkeys) in two launches (chunk = 2048 keys per block): the block sums, then every block adds up the block sums before it
 // (a few thousand values for the sums of a 2^20-gate proof, read from L2) and scans its own chunk - no serial pass over the block sums in between
 // (rounds 1-4 had a one-wave launch for it: twelve launches per proof with nothing else to run beside them)
-#define SCAN_CHUNK 2048
 __global__ void __launch_bounds__(256) k_scan_blocksums(const uint32_t *__restrict__ counts, uint32_t nkeys, uint32_t *__restrict__ blocksum) {
     __shared__ uint32_t lds[256];
     uint32_t base = blockIdx.x * SCAN_CHUNK, s = 0;
@@ -390,7 +382,6 @@ __global__ void __launch_bounds__(256) k_bucket_chunks(MsmSegs S, const uint32_t
 // every lane does one addition.  A bucket spread over more than HEAVY_CHUNKS chunks (thousands of identical scalars: the -y^h padding terms of
 // the first IPA round, repeated witness values) goes on the heavy list for k_bucket_combine_heavy.  Empty buckets are never written: the
 // epilogue (k_bucket_reduce) takes the identity for a bucket whose range is empty.
-#define HEAVY_CHUNKS 32
 #define HEAVY_BLOCKS 512                // grid of k_bucket_combine_heavy: a longer heavy list takes several trips of its grid-stride loop
 __global__ void __launch_bounds__(256) k_bucket_combine(const uint32_t *__restrict__ starts, ge_ext *__restrict__ buckets,
                                                         const ge_ext *__restrict__ slotA, const ge_ext *__restrict__ slotB,

@@ -6,7 +6,7 @@
 //                                       k_bucket_combine(_per_bucket, _heavy), k_bucket_reduce, k_window_sums (a shared device) / k_window_sums_quad (a proof alone)
 //                                       (bucket method: digits -> coarse partition in LDS -> fine counting sort -> balanced bucket sweep -> reductions;
 //                                       the 17 window sums are recombined and encoded on the host, host/fe51.hpp)
-//       equal scalars of a_L, a_R        k_merge_insert, k_merge_flags, k_merge_members, k_merge_sum (k_merge.cuh): terms of A_I that carry the same value share one
+//       equal scalars of a_L, a_R        k_merge_insert, k_merge_plan, k_merge_groups, k_merge_members, k_merge_sum (k_merge.cuh): terms of A_I that carry the same value share one
 //                                       bucket entry per window on the sum of their generators; once per uploaded witness
 //   a10 vector-polynomial phase         k_exp_table, k_flatten, k_poly_t, k_poly_eval, k_reduce_partials
 //   a11 inner-product argument          above 2^12 generators (a circuit of N <= 2^14: none): k_ipa_prep, the MSM kernels, k_tt_advance, one generator fold per group of rounds -
@@ -39,6 +39,8 @@
 #include <hip/hip_runtime.h>
 #include "ge.cuh"
 #include "sc.cuh"
+#include "../host/msm_plan.hpp"    // MsmPlan (argument of the MSM kernels) and the planner that fills it
+#include "../host/fold_plan.hpp"   // FoldGroup, FoldWnaf, FoldQuadW (arguments of the fold kernels) and the recoders that fill them
 
 namespace bpg {
 
