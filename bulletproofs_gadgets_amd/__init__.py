@@ -53,6 +53,37 @@ class WitnessHintsView(C.Structure):
 HINT_BIT_PAIR = 1
 
 
+class CheckReportView(C.Structure):
+    """bpg_check_report (frozen)."""
+    _fields_ = [("bad_multipliers", C.c_uint64), ("first_bad_multiplier", C.c_uint64), ("bad_rows", C.c_uint64), ("first_bad_row", C.c_uint64)]
+
+
+class CheckReport:
+    """What bpg_r1cs_check found: the exact counts, the first bad multiplier and row (None when there is none) and `rows`, the lowest violated constraint rows
+    in ascending order (at most the max_rows asked for).  Row j is the j-th constrain() call."""
+
+    def __init__(self, view: CheckReportView, rows):
+        none = lambda x: None if x == 2**64 - 1 else int(x)
+        self.bad_multipliers, self.first_bad_multiplier = int(view.bad_multipliers), none(view.first_bad_multiplier)
+        self.bad_rows, self.first_bad_row = int(view.bad_rows), none(view.first_bad_row)
+        self.rows = [int(r) for r in rows]
+
+    @property
+    def ok(self):
+        return self.bad_multipliers == 0 and self.bad_rows == 0
+
+    def items(self, q_src):
+        """on a repeat of a template of q_src constraints: `rows` as (copy, row of the source template) pairs"""
+        return [(r // q_src, r % q_src) for r in self.rows]
+
+    def __eq__(self, o):
+        return isinstance(o, CheckReport) and self.__dict__ == o.__dict__
+
+    def __repr__(self):
+        return "CheckReport(bad_multipliers=%d, first_bad_multiplier=%r, bad_rows=%d, first_bad_row=%r, rows=%r)" % (
+            self.bad_multipliers, self.first_bad_multiplier, self.bad_rows, self.first_bad_row, self.rows)
+
+
 class Timings(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("rng_host", "msm_aiao", "msm_s", "poly", "ipa", "total", "ipa_msm", "ipa_fold", "ipa_sync")]
 
@@ -118,6 +149,10 @@ def lib():
                      "bpg_verifier_num_vars"):
             getattr(_lib, name).restype = C.c_uint64
         _lib.bpg_proof_size.argtypes = [C.c_uint64, C.c_uint32]
+        _lib.bpg_r1cs_check.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                        C.POINTER(CheckReportView)]
+        _lib.bpg_test_check_host.argtypes = [C.POINTER(R1CSInstance), C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                             C.POINTER(CheckReportView)]
     return _lib
 
 
@@ -397,7 +432,15 @@ class Context:
         h = C.c_void_p()
         cs = inst.cstruct()
         _chk(lib().bpg_r1cs_upload(self._h, C.byref(cs), C.byref(h)))
-        return ResidentCircuit(self, h, inst.n, inst.m)
+        return ResidentCircuit(self, h, inst.n, inst.m, q=inst.q)
+
+    def check_flat(self, inst: "FlatInstance", max_rows=16) -> "CheckReport":
+        """upload + ResidentCircuit.check(inst.v) + free: does the instance's own witness satisfy it, and which constraints does it break"""
+        rc = self.upload(inst)
+        try:
+            return rc.check(inst.v if inst.m else None, max_rows)
+        finally:
+            rc.free()
 
     def upload_template(self, inst: "FlatInstance", program: "WitnessProgram", hints: "WitnessHints" = None):
         """bpg_r1cs_upload_template: the instance (with or without a witness) plus its witness program; ResidentCircuit.assign gives it fresh witnesses.
@@ -409,7 +452,7 @@ class Context:
             _chk(lib().bpg_r1cs_upload_template_hinted(self._h, C.byref(cs), C.byref(cp), C.byref(ch), C.byref(h)))
         else:
             _chk(lib().bpg_r1cs_upload_template(self._h, C.byref(cs), C.byref(cp), C.byref(h)))
-        return ResidentCircuit(self, h, inst.n, inst.m, n_params=len(program.param_rows))
+        return ResidentCircuit(self, h, inst.n, inst.m, n_params=len(program.param_rows), q=inst.q)
 
     def blinding_begin(self, transcript_state, v_blinding, rng_seed, max_multipliers):
         """bpg_blinding_begin: start the blinding chain of the next prove on this context (state after every "V" append, m x 32 blinding bytes)."""
@@ -544,6 +587,18 @@ def test_verify_replay(n, m, gens_capacity, transcript_state, proof, seed, flags
     _chk(lib().bpg_test_verify_replay(C.c_uint64(n), C.c_uint64(m), C.c_uint64(gens_capacity), _exact("transcript_state", transcript_state, 203), proof,
                                       C.c_uint64(len(proof)), _exact("seed", seed, 32), C.c_uint32(flags), C.byref(status), C.byref(decided)))
     return status.value, bool(decided.value)
+
+
+def test_check_host(inst, v=None, max_rows=16) -> "CheckReport":
+    """bpg_test_check_host (no device): the definition of bpg_r1cs_check in host C++ on an instance with its witness; v: the m committed values (None: inst.v)"""
+    v = inst.v if v is None else v
+    cs = inst.cstruct()
+    if not inst.aL and inst.n:
+        cs.aL = cs.aR = cs.aO = None
+    rows = (C.c_uint64 * max(max_rows, 1))()
+    have, rep = C.c_uint64(), CheckReportView()
+    _chk(lib().bpg_test_check_host(C.byref(cs), _scalars32("v", v, inst.m) if inst.m else None, C.c_uint64(max_rows), rows if max_rows else None, C.byref(have), C.byref(rep)))
+    return CheckReport(rep, rows[:have.value])
 
 
 def test_template_repeat_instance(inst, program, hints, count, param_values=None):
@@ -727,9 +782,10 @@ class _TemplateCommitItem(C.Structure):
 
 
 class ResidentCircuit:
-    def __init__(self, ctx, h, n, m, n_params=None):
+    def __init__(self, ctx, h, n, m, n_params=None, q=None):
         self.ctx, self._h, self.n, self.m = ctx, h, n, m
         self.n_params = n_params            # None: a plain upload; a number: a circuit template (Prover.template / Context.upload_template)
+        self.q = q                          # constraint rows (None: made by a caller that did not say)
 
     def assign(self, values, params=()):
         """bpg_r1cs_assign: a fresh witness for a circuit template - the m committed values (and the constant term of every parameter row); the device
@@ -746,7 +802,42 @@ class ResidentCircuit:
         count x m values and count x n_params constants, item-major; one prove() gives one proof for all the items.  Independent of this template."""
         h = C.c_void_p()
         _chk(lib().bpg_r1cs_template_repeat(self.ctx._h, self._h, C.c_uint64(count), C.byref(h)))
-        return ResidentCircuit(self.ctx, h, count * self.n, count * self.m, n_params=count * self.n_params)
+        return ResidentCircuit(self.ctx, h, count * self.n, count * self.m, n_params=count * self.n_params, q=None if self.q is None else count * self.q)
+
+    def check(self, values=None, max_rows=16) -> "CheckReport":
+        """bpg_r1cs_check: which multipliers (a_L * a_R against a_O) and which constraint rows does the resident witness break - evaluated on the device, the
+        witness stays where it is.  values: the m committed values (a plain upload does not keep them); None on a template: those of the last assign().
+        max_rows: how many violated rows to list (the lowest, ascending); the counts are exact whatever it is.  An unsatisfying witness is no error."""
+        v = None if values is None else _scalars32("values", values, self.m)
+        rows = (C.c_uint64 * max(max_rows, 1))()
+        have, rep = C.c_uint64(), CheckReportView()
+        _chk(lib().bpg_r1cs_check(self.ctx._h, self._h, C.c_uint64(self.m), v if v else None, C.c_uint64(max_rows), rows if max_rows else None, C.byref(have), C.byref(rep)))
+        return CheckReport(rep, rows[:have.value])
+
+    CHECK_BATCH_ROWS = 1 << 22      # constraint rows of one repeat made by check_batch
+
+    def check_batch(self, items, max_rows=16):
+        """"Which of my witnesses is bad": items = [(values, params)] - fresh witnesses of this template -> per item the list of violated rows OF THE TEMPLATE
+        (ascending, at most max_rows each; empty: the item is satisfying).  Composition of repeat(), assign() and ONE check() per chunk of at most
+        CHECK_BATCH_ROWS constraint rows; this template's own witness is left alone."""
+        if self.q is None:
+            raise ValueError("check_batch needs the template's row count (a circuit from Context.upload_template or Prover.template)")
+        out = []
+        per = max(1, self.CHECK_BATCH_ROWS // max(self.q, 1))
+        join = lambda x: bytes(x) if isinstance(x, (bytes, bytearray)) else b"".join(bytes(y) for y in x)
+        for first in range(0, len(items), per):
+            chunk = items[first:first + per]
+            rep = self.repeat(len(chunk))
+            try:
+                rep.assign(b"".join(join(v) for v, _ in chunk), b"".join(join(p) for _, p in chunk))
+                found = [[] for _ in chunk]
+                for k, r in rep.check(None, len(chunk) * self.q).items(self.q):
+                    if len(found[k]) < max_rows:
+                        found[k].append(r)
+                out += found
+            finally:
+                rep.free()
+        return out
 
     def prove(self, transcript_state, v_blinding, rng_seed=None, flags=0, timings=False):
         ts = _buf(203); ts.raw = _exact("transcript_state", transcript_state, 203)

@@ -361,6 +361,33 @@ bpg_status bpg_r1cs_template_repeat(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t co
         *out = c;
     });
 }
+bpg_status bpg_r1cs_check(bpg_ctx *ctx, bpg_circuit *c, uint64_t m, const uint8_t *v, uint64_t cap, uint64_t *rows_out, uint64_t *n_rows_out, bpg_check_report *report) {
+    return guard([&] {
+        REQUIRE(ctx && c && n_rows_out && report);
+        if (cap && !rows_out) throw std::invalid_argument("check: rows_out is null with cap > 0");
+        if (m != c->m) throw std::invalid_argument("check: m does not match the circuit");
+        if (!v && m && !c->is_template) throw std::invalid_argument("check: a plain upload does not keep its committed values: pass v");
+        if (!c->dc) throw std::invalid_argument("check: the handle has no device state (bpg_test_circuit_handle)");
+        uint64_t have = 0;
+        const CheckReport r = ctx->engine->check(c->dc, v, cap, rows_out, &have);        // no witness: refused there, before any device work
+        *n_rows_out = have;
+        report->bad_multipliers = r.bad_multipliers; report->first_bad_multiplier = r.first_bad_multiplier; report->bad_rows = r.bad_rows; report->first_bad_row = r.first_bad_row;
+    });
+}
+bpg_status bpg_test_check_host(const bpg_r1cs_instance *inst, const uint8_t *v, uint64_t cap, uint64_t *rows_out, uint64_t *n_rows_out, bpg_check_report *report) {
+    return guard([&] {
+        REQUIRE(inst && n_rows_out && report);
+        const FlatView f = as_view(inst, false);
+        Engine::check_instance(f);
+        if (f.n && !f.aL) throw R1CSException(R1CSError::MissingAssignment, "check: the instance carries no witness");
+        if (!v && f.m) throw std::invalid_argument("check: v is null with m > 0");
+        if (cap && !rows_out) throw std::invalid_argument("check: rows_out is null with cap > 0");
+        uint64_t have = 0;
+        const CheckReport r = check_host(f, v, cap, rows_out, &have);
+        *n_rows_out = have;
+        report->bad_multipliers = r.bad_multipliers; report->first_bad_multiplier = r.first_bad_multiplier; report->bad_rows = r.bad_rows; report->first_bad_row = r.first_bad_row;
+    });
+}
 bpg_status bpg_test_template_repeat_instance(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, uint64_t count,
                                              const uint8_t *param_values, uint64_t *row_ptr, uint64_t row_cap, uint32_t *term_var, uint32_t *term_coef,
                                              uint64_t term_cap, uint8_t *coef, uint64_t coef_cap, uint64_t *nnz_out, uint64_t *ncoef_out) {

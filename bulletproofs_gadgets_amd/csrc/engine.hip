@@ -189,6 +189,7 @@ struct DeviceCircuit {
     // per-witness constant terms live in `coef` (slots [param_first, param_first + n_params))
     bool is_template = false;
     DevBuf wit_stream, wit_segs, wit_v;
+    bool wit_v_set = false;                 // wit_v holds the values of an assign() (a template uploaded WITH its witness has a_L, a_R, a_O and no values yet)
     std::vector<uint32_t> wit_level_ptr;    // level l = segments [wit_level_ptr[l], wit_level_ptr[l + 1]) of wit_segs
     uint64_t n_params = 0, param_first = 0;
     // host copy of the rows with their parameter slots (TemplatePlan::slotted), which the lockstep packer of prove_template_batch reads: kept only for
@@ -199,6 +200,12 @@ struct DeviceCircuit {
     // a template repeated on the device (repeat_template, hip/k_repeat.cuh): rep_count copies of a source template of rep_n multipliers and rep_m committed
     // values, whose packed program (wit_stream, wit_segs, wit_level_ptr: copies of the source's) assign() walks once per (segment, item).  0: not a repeat.
     uint64_t rep_count = 0, rep_n = 0, rep_m = 0;
+    // row-major view of the matrix for check() (hip/k_check.cuh), derived from the column-major one at the first check and kept until the circuit is freed (the
+    // matrix never changes; parameter values live in `coef`, which the view indexes): rv_ptr = q + 1 row starts, rv_ent = nnz pairs (column, coefficient slot),
+    // rv_long = [count | the rows of more than rv_threshold terms].  Plain device memory: no part of the table budget.
+    bool rv_built = false;
+    uint32_t rv_threshold = 0;
+    DevBuf rv_ptr, rv_ent, rv_long;
 };
 
 // kernel ids for the optional HIP-event profile (bpg_profile_*)
@@ -209,7 +216,8 @@ struct DeviceCircuit {
     X(k_tt_bases) X(k_tt_multiples) X(k_tt_bases8) X(k_tt_multiples8) X(k_tt_round8) X(k_tt_factors) X(k_tt_advance) X(k_tt_round) X(k_tt_finish) X(k_blind_expand) X(k_tt_commit3) X(k_tt_commit3_finish) X(k_csc_count) X(k_csc_fill) X(k_csc_colptr) X(k_merge_insert) X(k_merge_plan) X(k_merge_groups) X(k_merge_members) X(k_merge_sum) \
     X(k_bt_commit3) X(k_bt_commit3_finish) X(k_bt_compress) X(k_bt_exp) X(k_bt_poly_t) X(k_bt_poly_eval) X(k_bt_factors) X(k_bt_advance) X(k_bt_round) \
     X(k_bt_finish) X(k_bt_fold_scalars) X(k_witness_eval) X(k_witness_eval_batch) X(k_bt_commit_v) X(k_repeat_colptr) X(k_repeat_entries) X(k_repeat_coef) X(k_witness_eval_repeat) \
-    X(k_mimc_sponge) X(k_merkle_leaves) X(k_merkle_level) X(k_merkle_top) X(k_merkle_level_list) X(k_merkle_set_leaves) X(k_merkle_paths) X(k_merkle_export)
+    X(k_mimc_sponge) X(k_merkle_leaves) X(k_merkle_level) X(k_merkle_top) X(k_merkle_level_list) X(k_merkle_set_leaves) X(k_merkle_paths) X(k_merkle_export) \
+    X(k_rowview_count) X(k_rowview_fill) X(k_rowview_long) X(k_check_mul) X(k_check_rows) X(k_check_rows_long) X(k_check_count)
 enum KernelId {
 #define X(n) KID_##n,
     BPG_KERNELS(X)
@@ -255,6 +263,10 @@ struct Engine::Impl {
     std::shared_ptr<MimcConstants> mimc;
     DevBuf mk_in, mk_out;
     std::vector<DeviceMerkle *> trees;
+    // check() (hip/k_check.cuh): the caller's committed values of a plain upload, the violation bitmap (a bit per row), the four counters of the report
+    DevBuf chk_v, chk_bitmap, chk_report;
+    uint32_t check_threshold = CHECK_ROW_THRESHOLD;     // rows of more terms get a wave each (BPG_CHECK_THRESHOLD)
+    void rowview_build(DeviceCircuit *c);
     // One arena for the large per-stream buffers whose lifetimes never overlap in stream order (round 5: 20 proving streams held 2.9 GB each):
     //   an MSM:        [digits | entries1] (dead once k_msm_sort2 has run) overlaid by the sweep's partial sums (slots); entries behind them
     //   poly phase:    flattened weights, powers of z and y (between the S sums and the first round of the inner-product argument)
@@ -646,6 +658,7 @@ Engine::Engine(int device, const EngineConfig &cfg) : device_(device) {
     env_set("BPG_TT_ORIG_LG", 0, 20, K->tt_orig_lg);
     env_set("BPG_BATCH_WAVE_MB", 0, 1 << 20, K->batch_wave_mb);
     env_set("BPG_COMMIT_CPW", 1, 4, K->commit_cpw);
+    env_set("BPG_CHECK_THRESHOLD", 0, 1 << 20, K->check_threshold);
     if (env_present("BPG_GENS_SHARE")) K->gens_share = env_int_strict("BPG_GENS_SHARE", 0, 1) != 0;
 
     int count = 0;
@@ -703,7 +716,7 @@ Engine::~Engine() {
                       &impl_->starts, &impl_->cursor, &impl_->blocksum, &impl_->arena, &impl_->buckets, &impl_->partial, &impl_->msm_result,
                       &impl_->sLR, &impl_->yinvpow, &impl_->lv, &impl_->rv, &impl_->red_partial,
                       &impl_->red_out, &impl_->raw_rng, &impl_->extras, &impl_->ipa_s, &impl_->ipa_tabA, &impl_->ipa_tabB, &impl_->naf, &impl_->qsteps, &impl_->wsums, &impl_->wq_stage, &impl_->wq_tickets, &impl_->vfy_in, &impl_->vfy_pts, &impl_->vfy_ok, &impl_->vfy_sc, &impl_->vfy_ch, &impl_->vfy_small,
-                      &impl_->stale_flag, &impl_->tile_hist, &impl_->heavy, &impl_->plain, &impl_->open_keys, &impl_->medium, &impl_->tt_bases, &impl_->tt_table, &impl_->tt_f, &impl_->tt_c, &impl_->tt_partial, &impl_->grp_c, &impl_->ped_table, &impl_->s_parts, &impl_->starts1, &impl_->mk_in, &impl_->mk_out};
+                      &impl_->stale_flag, &impl_->tile_hist, &impl_->heavy, &impl_->plain, &impl_->open_keys, &impl_->medium, &impl_->tt_bases, &impl_->tt_table, &impl_->tt_f, &impl_->tt_c, &impl_->tt_partial, &impl_->grp_c, &impl_->ped_table, &impl_->s_parts, &impl_->starts1, &impl_->mk_in, &impl_->mk_out, &impl_->chk_v, &impl_->chk_bitmap, &impl_->chk_report};
     for (DevBuf *b : bufs) b->release();
     for (DeviceMerkle *t : impl_->trees) merkle_orphan(t);       // trees the host has not freed: their memory goes with the context, their handles stay valid
     impl_->mimc.reset();
@@ -727,13 +740,13 @@ std::string Engine::profile_report() {
     impl_->prof_collect();
     // the effective schedule of this context first (what the knobs, the profile and the table budget settled on): bench.py derives its term
     // counts from THIS, not from its own reading of the environment
-    char sch[896];
+    char sch[1024];
     std::snprintf(sch, sizeof sch, "{\"_schedule\": {\"profile\": %u, \"tt_lg\": %u, \"tt_orig_lg\": %u, \"fold_group\": %u, \"fold_wnaf\": %u, \"fold_parts\": %u, "
                   "\"eff_wnaf\": %u, \"eff_parts\": %u, \"fold_adapt\": %u, \"fold_split_max\": %u, \"fold_quad\": %u, \"msm_cmax\": %u, \"msm_cmax_shared\": %u, \"msm_cmin\": %u, "
-                  "\"rseg\": %u, \"lgch\": %u, \"sweep_blocks_resident\": %u, \"shared_variants_last\": %u, \"merge_equal\": %u, \"merged_last\": %u, \"merged_skipped_last\": %u, \"merge_ms_last\": %.3f, \"table_budget\": %llu, \"table_bytes\": %llu}",
+                  "\"rseg\": %u, \"lgch\": %u, \"sweep_blocks_resident\": %u, \"shared_variants_last\": %u, \"merge_equal\": %u, \"merged_last\": %u, \"merged_skipped_last\": %u, \"merge_ms_last\": %.3f, \"table_budget\": %llu, \"table_bytes\": %llu, \"check_threshold\": %u}",
                   impl_->profile, impl_->tt_lg, impl_->tt_orig_lg, impl_->fold_group, impl_->fold_wnaf, impl_->fold_parts, impl_->eff_wnaf, impl_->eff_parts,
                   impl_->fold_adapt, impl_->fold_split_max, (unsigned)impl_->fold_quad, impl_->msm_cmax, impl_->msm_cmax_shared, impl_->msm_cmin, impl_->rseg, impl_->lgch,
-                  impl_->sweep_blocks_resident, (unsigned)impl_->shared_now, (unsigned)impl_->merge_equal, impl_->merged_last, impl_->merged_skipped_last, impl_->merge_ms_last, (unsigned long long)impl_->table_budget, (unsigned long long)table_bytes_held(device_));
+                  impl_->sweep_blocks_resident, (unsigned)impl_->shared_now, (unsigned)impl_->merge_equal, impl_->merged_last, impl_->merged_skipped_last, impl_->merge_ms_last, (unsigned long long)impl_->table_budget, (unsigned long long)table_bytes_held(device_), impl_->check_threshold);
     std::string out = sch;
     if (!impl_->prof_wit_ms.empty()) {
         out += ", \"_witness_launch_ms\": [";
@@ -1234,7 +1247,7 @@ DeviceCircuit *Engine::upload(const FlatView &c) {
 void Engine::free_circuit(DeviceCircuit *c) {
     if (!c) return;
     (void)hipSetDevice(device_);
-    DevBuf *b[] = {&c->wit_stream, &c->wit_segs, &c->wit_v, &c->aL, &c->aR, &c->aO, &c->col_ptr, &c->ent_row, &c->ent_coef, &c->coef, &c->mI.skipA, &c->mI.skipB, &c->mI.sc, &c->mI.pts, &c->mO.skipA, &c->mO.skipB, &c->mO.sc, &c->mO.pts};
+    DevBuf *b[] = {&c->wit_stream, &c->wit_segs, &c->wit_v, &c->aL, &c->aR, &c->aO, &c->col_ptr, &c->ent_row, &c->ent_coef, &c->coef, &c->mI.skipA, &c->mI.skipB, &c->mI.sc, &c->mI.pts, &c->mO.skipA, &c->mO.skipB, &c->mO.sc, &c->mO.pts, &c->rv_ptr, &c->rv_ent, &c->rv_long};
     for (DevBuf *x : b) x->release();
     delete c;
 }
@@ -1340,7 +1353,83 @@ void Engine::assign(DeviceCircuit *d, const uint8_t *v, const uint8_t *param_val
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(I.st));
-    d->has_witness = true;
+    d->has_witness = true; d->wit_v_set = true;
+}
+// ------------------------------------------------------------------------------------------------ R1CS check on the device (hip/k_check.cuh, host/check.hpp)
+// The row-major view of a resident matrix, from its column-major form: entries per row, an exclusive scan, (column, coefficient slot) pairs per row, and the
+// list of rows that are too long for one lane.  Workspace: the scan buffers of the MSM (no MSM runs on this context during a check).  Queued, not waited for.
+void Engine::Impl::rowview_build(DeviceCircuit *c) {
+    const uint64_t q = c->q, nnz = c->nnz;
+    c->rv_ptr.ensure((q + 1) * 4); c->rv_ent.ensure((nnz ? nnz : 1) * 8); c->rv_long.ensure((q + 1) * 4);
+    counts.ensure((q + 2) * 4); cursor.ensure((q + 2) * 4); blocksum.ensure((size_t)(cdiv(q, SCAN_CHUNK) + 2) * 4);
+    HIPCHK(hipMemsetAsync(counts.p, 0, (q + 1) * 4, st));
+    HIPCHK(hipMemsetAsync(c->rv_long.p, 0, 4, st));
+    if (nnz) BPG_LAUNCH((*this), k_rowview_count, dim3(cdiv(nnz, 256)), dim3(256), c->ent_row.as<uint32_t>(), c->const_begin, nnz, counts.as<uint32_t>());
+    const uint32_t nb = cdiv(q, SCAN_CHUNK);
+    BPG_LAUNCH((*this), k_scan_blocksums, dim3(nb), dim3(256), counts.as<uint32_t>(), (uint32_t)q, blocksum.as<uint32_t>());
+    BPG_LAUNCH((*this), k_scan_apply, dim3(nb), dim3(256), counts.as<uint32_t>(), (uint32_t)q, blocksum.as<uint32_t>(), c->rv_ptr.as<uint32_t>(), cursor.as<uint32_t>());
+    if (nnz) BPG_LAUNCH((*this), k_rowview_fill, dim3(cdiv(nnz, 256)), dim3(256), c->col_ptr.as<uint64_t>(), c->ent_row.as<uint32_t>(), c->ent_coef.as<uint32_t>(),
+                        (uint32_t)c->ncols, c->const_begin, nnz, cursor.as<uint32_t>(), c->rv_ent.as<uint2>());
+    BPG_LAUNCH((*this), k_rowview_long, dim3(cdiv(q, 256)), dim3(256), c->rv_ptr.as<uint32_t>(), (uint32_t)q, check_threshold, c->rv_long.as<uint32_t>());
+    HIPCHK(hipGetLastError());
+    c->rv_threshold = check_threshold; c->rv_built = true;
+}
+
+CheckReport Engine::check(DeviceCircuit *c, const uint8_t *v, uint64_t cap, uint64_t *rows_out, uint64_t *n_rows_out) {
+    // every refusal first: nothing below this block runs for a refused call
+    if (!c) throw std::invalid_argument("check: no circuit");
+    if (!c->has_witness) throw R1CSException(R1CSError::MissingAssignment, "check: the circuit holds no witness (a verifier-side upload, or a template before assign / after a template batch)");
+    if (!v && c->m && !c->is_template) throw std::invalid_argument("check: a plain upload does not keep its committed values: pass v");
+    if (!v && c->m && !c->wit_v_set) throw std::invalid_argument("check: the template was uploaded with its witness and has had no assign: pass v");
+    if (cap && !rows_out) throw std::invalid_argument("check: rows_out is null with cap > 0");
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    const uint64_t n = c->n, m = c->m, q = c->q;
+    const scm *vals = c->wit_v.as<scm>();
+    if (v && m) {                                   // the caller's values, reduced mod l as assign() reduces them; the circuit's own (wit_v) stay as they are
+        I.small_sc.ensure(m * 32); I.chk_v.ensure(m * sizeof(scm));
+        I.h2d(I.small_sc.p, v, m * 32);
+        BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(m, 256)), dim3(256), I.small_sc.as<uint32_t>(), I.chk_v.as<scm>(), (uint32_t)m);
+        vals = I.chk_v.as<scm>();
+    }
+    static const uint64_t kFresh[4] = {0, CHECK_NONE, 0, CHECK_NONE};
+    I.chk_report.ensure(32);
+    HIPCHK(hipMemcpyAsync(I.chk_report.p, kFresh, 32, hipMemcpyHostToDevice, I.st));
+    unsigned long long *rep = I.chk_report.as<unsigned long long>();
+    if (n) BPG_LAUNCH(I, k_check_mul, dim3(cdiv(n, 256)), dim3(256), c->aL.as<scm>(), c->aR.as<scm>(), c->aO.as<scm>(), (uint32_t)n, rep);
+    const uint64_t nwords = check_bitmap_words(q);
+    if (q) {
+        if (!c->rv_built) I.rowview_build(c);
+        I.chk_bitmap.ensure(nwords * 8);
+        const CheckOperands P{c->aL.as<scm>(), c->aR.as<scm>(), c->aO.as<scm>(), vals, (uint32_t)n, (uint32_t)m};
+        unsigned long long *bitmap = I.chk_bitmap.as<unsigned long long>();
+        BPG_LAUNCH(I, k_check_rows, dim3(cdiv(q, 256)), dim3(256), c->rv_ptr.as<uint32_t>(), c->rv_ent.as<uint2>(), c->coef.as<scm>(), P, (uint32_t)q, c->rv_threshold, bitmap);
+        // a wave per long row, one wave per SIMD of the device at most: how many rows are long stays on the device (rv_long[0])
+        BPG_LAUNCH(I, k_check_rows_long, dim3(std::min<uint32_t>(cdiv(q, 4), std::max(1u, I.wit_waves / 4))), dim3(256), c->rv_ptr.as<uint32_t>(), c->rv_ent.as<uint2>(),
+                   c->coef.as<scm>(), P, c->rv_long.as<uint32_t>(), bitmap);
+        BPG_LAUNCH(I, k_check_count, dim3(cdiv(nwords, 256)), dim3(256), bitmap, (uint32_t)nwords, rep);
+    }
+    HIPCHK(hipGetLastError());
+    uint64_t h[4];
+    HIPCHK(hipMemcpyAsync(h, rep, 32, hipMemcpyDeviceToHost, I.st));        // the one read-back of a satisfied witness
+    HIPCHK(hipStreamSynchronize(I.st));
+    CheckReport R;
+    R.bad_multipliers = h[0]; R.first_bad_multiplier = h[1]; R.bad_rows = h[2]; R.first_bad_row = h[3];
+    uint64_t have = 0;
+    if (R.bad_rows && cap) {                        // the bitmap, from the word of the first bad row on, a piece at a time until the list is full
+        const uint64_t want = std::min(cap, R.bad_rows), PIECE = 1u << 17;
+        std::vector<uint64_t> words;
+        for (uint64_t w0 = check_word_of(R.first_bad_row); w0 < nwords && have < want; w0 += PIECE) {
+            const uint64_t cnt = std::min(PIECE, nwords - w0);
+            words.resize(cnt);
+            HIPCHK(hipMemcpyAsync(words.data(), I.chk_bitmap.as<uint64_t>() + w0, cnt * 8, hipMemcpyDeviceToHost, I.st));
+            HIPCHK(hipStreamSynchronize(I.st));
+            have = check_bitmap_rows(words.data(), cnt, w0, q, want, rows_out, have);
+        }
+        if (have != want) throw std::logic_error("check: the violation bitmap and its count disagree");
+    }
+    if (n_rows_out) *n_rows_out = have;
+    return R;
 }
 // ------------------------------------------------------------------------------------------------ a template repeated on the device (hip/k_repeat.cuh)
 namespace {

@@ -8,6 +8,7 @@
 #include "host/merlin.hpp"
 #include "host/r1cs.hpp"
 #include "host/template.hpp"
+#include "host/check.hpp"
 
 namespace bpg {
 
@@ -85,6 +86,12 @@ public:
     // parameter row; a_L, a_R, a_O are computed on the device (k_witness_eval, one launch per schedule level), everything cached for the previous witness
     // (the equal-scalar merge sets) is dropped.  Returns once the witness is in place.
     void assign(DeviceCircuit *c, const uint8_t *v, const uint8_t *param_values);
+    // Which multiplier, which constraint row does the resident witness break (include/bpg.h bpg_r1cs_check; hip/k_check.cuh): a_L * a_R against a_O per multiplier, and
+    // every row of the matrix over the operand vector [a_L | a_R | a_O | v | 1].  v: m x 32 bytes (reduced mod l on the device), or null on a template: the values
+    // of its last assign().  rows_out receives the lowest min(cap, bad_rows) bad rows, ascending.  The first check of a circuit derives a row-major view of its
+    // matrix on the device and keeps it in the circuit.  Refused before any device work: no witness (R1CSException MissingAssignment), null v where the circuit keeps
+    // no values, null rows_out with cap > 0 (std::invalid_argument).  Leaves the witness, the equal-scalar sets and every proof that follows as they were.
+    CheckReport check(DeviceCircuit *c, const uint8_t *v, uint64_t cap, uint64_t *rows_out, uint64_t *n_rows_out);
     static void template_eval_host(const FlatView &c, const WitnessProgramView &p, const uint8_t *v, uint8_t *aL, uint8_t *aR, uint8_t *aO);   // test hook
     // test hook (bpg_test_template_eval_batch): the BATCHED interpreter (k_witness_eval_batch) compiled for the host - level by level, every item of a
     // segment side by side, into the wave layout (count x N x 32 bytes per vector, item-major, N = padded size, padding rows zero); v: count x m x 32

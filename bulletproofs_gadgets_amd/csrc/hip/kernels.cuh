@@ -30,8 +30,12 @@
 //                                       one heap-ordered array: k_merkle_leaves, k_merkle_level (one launch per level, one lane per parent), k_merkle_top (the levels of at
 //                                       most 256 parents in one launch), k_merkle_level_list + k_merkle_set_leaves (leaf updates: the ancestors only), k_merkle_paths
 //                                       (sibling lists), k_merkle_export (nodes as bytes)
-// The kernels live in k_points.cuh, k_scalars.cuh, k_ipa.cuh, k_verify.cuh, k_msm.cuh, k_merge.cuh, k_batch.cuh, k_witness.cuh, k_repeat.cuh and k_mimc.cuh, included at the end of this file in that
-// order.
+//       R1CS check                       (k_check.cuh; bpg_r1cs_check: which multiplier, which constraint does the resident witness break) the row-major view of the resident
+//                                       matrix, once per circuit: k_rowview_count, k_scan_blocksums / _apply, k_rowview_fill, k_rowview_long; per check: k_check_mul (a lane
+//                                       per multiplier), k_check_rows (a lane per short row, the wave's ballot = one word of the violation bitmap), k_check_rows_long (a
+//                                       wave per long row), k_check_count (bad rows and the first of them)
+// The kernels live in k_points.cuh, k_scalars.cuh, k_ipa.cuh, k_verify.cuh, k_msm.cuh, k_merge.cuh, k_batch.cuh, k_witness.cuh, k_repeat.cuh, k_mimc.cuh and k_check.cuh, included at the end of
+// this file in that order.
 // Data layout in HBM: scalars = 8 x u32 Montgomery form, 32 B each, AoS (lane i <-> element i: 2 x 16 B coalesced
 // loads); generator tables = affine Niels (y+x, y-x, 2dxy), 96 B per point, G at [0,N) and H at [N,2N); window tables =
 // projective Niels (y+x, y-x, z, 2dt), 128 B per entry.
@@ -78,3 +82,4 @@ __device__ __forceinline__ uint32_t msm_point_index(const MsmSegs &S, uint32_t s
 #include "k_witness.cuh"
 #include "k_repeat.cuh"
 #include "k_mimc.cuh"
+#include "k_check.cuh"

@@ -81,7 +81,7 @@ typedef struct {
 
 /* ---------------------------------------------------------------------------------------------------- PART 1: hot path */
 /* ABI version of this header.  Rules: structs the CALLER allocates either carry a struct_size (bpg_config: fields are only ever added at the end and
- * read when struct_size covers them) or are frozen (bpg_timings, bpg_r1cs_instance, bpg_batch_item, bpg_template_item, bpg_template_commit_item, bpg_witness_program, bpg_witness_hints, bpg_term, bpg_lc); a field never changes type or
+ * read when struct_size covers them) or are frozen (bpg_timings, bpg_r1cs_instance, bpg_batch_item, bpg_template_item, bpg_template_commit_item, bpg_witness_program, bpg_witness_hints, bpg_check_report, bpg_term, bpg_lc); a field never changes type or
  * meaning.  BPG_ABI_VERSION grows when something a version-7 host relies on is extended (a new field, a new flag value); functions ADDED since
  * version 7 (bpg_r1cs_prove_batch, the circuit-template calls) did not raise it: a host that needs one looks the symbol up (dlsym) and treats its
  * absence as "not supported".  A host checks bpg_abi_version() >= the BPG_ABI_VERSION it was compiled against. */
@@ -372,6 +372,34 @@ bpg_status bpg_test_template_repeat_instance(const bpg_r1cs_instance *inst, cons
                                              uint64_t term_cap, uint8_t *coef, uint64_t coef_cap, uint64_t *nnz_out, uint64_t *ncoef_out);
 bpg_status bpg_test_template_eval_repeat(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, uint64_t count,
                                          const uint8_t *v, uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out);
+
+/* R1CS CHECK ON THE DEVICE: is the resident witness satisfying, and if not, where does it fail.  (An addition to ABI version 7: look the symbol up.)
+ * The witness of a template never visits the host (bpg_r1cs_assign, bpg_r1cs_template_repeat), and a proof of an unsatisfying witness is made all the same - the
+ * host learns from the verifier that it is worthless, never which item or constraint was wrong.  bpg_r1cs_check evaluates, on the device, every multiplier
+ * (a_L[i] * a_R[i] against a_O[i]) and every constraint row (its linear combination over a_L, a_R, a_O, the committed values and the constant One, mod l) of a
+ * resident circuit.  Row j is the j-th constrain() call, as in bpg_r1cs_instance; on a repeat, row k q + j is constraint j of copy k.
+ * v: the m committed values (32 bytes each, reduced mod l as bpg_r1cs_assign reduces them).  A plain upload does not keep them: the caller passes them.  A
+ * template or a repeat may pass NULL: the values and the parameter slots stand as the last bpg_r1cs_assign left them (a template uploaded WITH a witness and
+ * never assigned has no values: pass v).  m = 0: v is not looked at.
+ * rows_out receives the lowest min(cap, bad_rows) violated row indices in ascending order, *n_rows_out how many - the same list whatever the launch order; the
+ * frozen struct bpg_check_report the exact counts.  A satisfying witness: BPG_OK, zero counts.  An unsatisfying one is NOT an error: BPG_OK, counts above 0.
+ * Refused before any device work: a NULL ctx, c, n_rows_out or report, a NULL rows_out with cap > 0, an m that does not match the circuit's, a NULL v where the
+ * circuit keeps no values, a handle without device state (BPG_ERR_INVALID_ARGUMENT); a circuit without a witness - a verifier's upload, a template before its
+ * first bpg_r1cs_assign or after a template batch (BPG_ERR_MISSING_ASSIGNMENT).
+ * The first check of a circuit derives a row-major view of its matrix on the device (8 bytes per term and 8 per row, kept until bpg_r1cs_free; no part of the
+ * table budget); no other call builds it.  The call changes nothing a later bpg_r1cs_prove_resident or bpg_r1cs_verify_resident sees: same proof bytes.  A host
+ * may call it before it proves.  Variable-time, like every witness computation here (see SIDE CHANNELS above). */
+typedef struct {                      /* frozen, like bpg_timings */
+    uint64_t bad_multipliers;         /* i in [0,n) with a_L[i]*a_R[i] != a_O[i] */
+    uint64_t first_bad_multiplier;    /* UINT64_MAX when none */
+    uint64_t bad_rows;                /* constraints j in [0,q) whose linear combination is not 0 */
+    uint64_t first_bad_row;           /* UINT64_MAX when none */
+} bpg_check_report;
+bpg_status bpg_r1cs_check(bpg_ctx *ctx, bpg_circuit *c, uint64_t m, const uint8_t *v, uint64_t cap, uint64_t *rows_out, uint64_t *n_rows_out, bpg_check_report *report);
+/* TEST HOOK, no device and no context needed: the same definition in host C++ (csrc/host/check.hpp) on an instance WITH its witness.  Refused with
+ * BPG_ERR_INVALID_ARGUMENT: NULL inst, n_rows_out or report, a malformed instance, a NULL v with m > 0, a NULL rows_out with cap > 0; an instance without a_L,
+ * a_R, a_O (n > 0): BPG_ERR_MISSING_ASSIGNMENT. */
+bpg_status bpg_test_check_host(const bpg_r1cs_instance *inst, const uint8_t *v, uint64_t cap, uint64_t *rows_out, uint64_t *n_rows_out, bpg_check_report *report);
 
 /* measurement hooks (bench.py): HIP events on the engine's own stream. mode 0 off, 1 = dominant kernel only, 2 = all kernels;
  * report = JSON text {kernel: {count, total_ms, alg_bytes, device_bytes, field_mults}} accumulated since the last set. */
