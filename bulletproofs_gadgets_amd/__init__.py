@@ -288,6 +288,16 @@ def _lc_array(lcs):
 
 
 # ------------------------------------------------------------------------------------------------ context / generators
+LIVE_RESOURCE_KEYS = ("device_buffers", "device_bytes", "pinned_buffers", "pinned_bytes", "streams", "events")
+
+
+def live_resources():
+    """bpg_test_live_resources: what the process holds from the HIP runtime at this moment, every context together; all zero once everything is freed."""
+    out = (C.c_uint64 * 6)()
+    _chk(lib().bpg_test_live_resources(out))
+    return dict(zip(LIVE_RESOURCE_KEYS, (int(x) for x in out)))
+
+
 class Context:
     """One GPU: PedersenGens (fixed bases) + the BulletproofGens tables resident in HBM."""
 

@@ -197,6 +197,7 @@ bpg_status bpg_ctx_create(int32_t device, bpg_ctx **out) { return bpg_ctx_create
 int32_t bpg_device_count(void) { return Engine::device_count(); }
 bpg_status bpg_test_fail_next_upload(bpg_ctx *ctx) { return guard([&] { REQUIRE(ctx); ctx->engine->test_fail_next_upload(); }); }
 bpg_status bpg_test_drop_next_upload(bpg_ctx *ctx) { return guard([&] { REQUIRE(ctx); ctx->engine->test_drop_next_upload(); }); }
+bpg_status bpg_test_live_resources(uint64_t out[6]) { return guard([&] { REQUIRE(out); live_resources(out); }); }
 uint64_t bpg_table_bytes(bpg_ctx *ctx) { return ctx ? ctx->engine->table_bytes() : 0; }
 int32_t bpg_ctx_last_shared_variants(bpg_ctx *ctx) { return ctx && ctx->engine->last_shared_variants() ? 1 : 0; }
 void bpg_ctx_destroy(bpg_ctx *ctx) { if (ctx) { delete ctx->engine; delete ctx; } }

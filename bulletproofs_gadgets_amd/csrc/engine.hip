@@ -23,6 +23,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 #include "engine.hpp"
+#include "hip_handles.hpp"
 #include "host/fe51.hpp"
 #include "host/chain.hpp"
 #include "host/fiat_shamir.hpp"
@@ -30,37 +31,12 @@
 
 namespace bpg {
 
-#define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) throw DeviceError(std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
-
 // launch on the engine stream, bracketed by HIP events when the profile asks for this kernel
 #define BPG_LAUNCH_ID(I, id, kernel, grid, block, ...) do { (I).prof_begin(id); hipLaunchKernelGGL(kernel, grid, block, 0, (I).st, __VA_ARGS__); (I).prof_end(id); } while (0)
 #define BPG_LAUNCH(I, kernel, grid, block, ...) BPG_LAUNCH_ID(I, KID_##kernel, kernel, grid, block, __VA_ARGS__)
 #define BPG_LAUNCH_LDS(I, id, kernel, grid, block, lds, ...) do { (I).prof_begin(id); hipLaunchKernelGGL(kernel, grid, block, lds, (I).st, __VA_ARGS__); (I).prof_end(id); } while (0)
 
 namespace {
-
-struct DevBuf {
-    void *p = nullptr; size_t cap = 0;
-    void ensure(size_t bytes) {
-        if (bytes <= cap) return;
-        if (p) HIPCHK(hipFree(p));
-        p = nullptr; cap = 0;
-        HIPCHK(hipMalloc(&p, bytes)); cap = bytes;
-    }
-    void release() { if (p) { (void)hipFree(p); p = nullptr; cap = 0; } }
-    template <class T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-struct PinBuf {
-    void *p = nullptr; size_t cap = 0;
-    void ensure(size_t bytes) {
-        if (bytes <= cap) return;
-        if (p) HIPCHK(hipHostFree(p));
-        p = nullptr; cap = 0;
-        HIPCHK(hipHostMalloc(&p, bytes, hipHostMallocDefault)); cap = bytes;
-    }
-    void release() { if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; } }
-    template <class T> T *as() const { return reinterpret_cast<T *>(p); }
-};
 
 // Generator tables of one (device, capacity), shared by every context of the process on that device: the affine-Niels table [G | H] and, built on
 // first use, the odd multiples for the width-w NAF fold (one set per w).  Immutable once published, so contexts on different streams read them
@@ -92,18 +68,18 @@ struct SharedTables {
     std::map<uint32_t, DevBuf> odd;                 // (w | parts << 8) -> [parts * 2^(w-2) - 1][2*cap] Niels points: (2m+1) * 2^(j*L) * P, see FoldWnaf
     std::map<uint64_t, uint64_t> refused;           // table key (odd: w | parts << 8; wide: 1 << 32 | M0) -> bytes held on the device when its allocation failed:
                                                     // not tried again until the device holds less (no failing 50 GB hipMalloc per proof)
-    ~SharedTables() {
-        (void)hipSetDevice(device); gens.release();
+    ~SharedTables() {       // on the tables' device, and their share of the table budget given back; the members then free themselves
+        (void)hipSetDevice(device);
         uint64_t held = 0;
-        for (auto &kv : odd) { held += kv.second.cap; kv.second.release(); }
-        for (auto &kv : wide) { held += kv.second.cap; kv.second.release(); }
+        for (auto &kv : odd) held += kv.second.cap;
+        for (auto &kv : wide) held += kv.second.cap;
         table_bytes_add(device, -(int64_t)held);
     }
 };
 // The 486 MiMC round constants in Montgomery form, once per device: contexts created on one device share the buffer, and it goes with the last of them.
 struct MimcConstants {
     int device = 0; DevBuf rc;
-    ~MimcConstants() { (void)hipSetDevice(device); rc.release(); }
+    ~MimcConstants() { (void)hipSetDevice(device); }
 };
 static std::mutex g_mimc_mutex;
 void merkle_orphan(DeviceMerkle *t);                // (defined with DeviceMerkle, below) releases the device memory of a tree whose context is being destroyed
@@ -231,32 +207,34 @@ static const char *const kKernelNames[KID_COUNT] = {
 };
 
 struct Engine::Impl {
-    hipStream_t st = nullptr;
+    Stream st;                                  // the first member: destroyed last, after every buffer, event and copy stream below
+    int device = 0;
+    ~Impl();                                    // waits for the context's work, then the members free themselves (defined below the constructor)
     // profiling: mode 0 off, 1 = the generator-fold kernels and the bucket sweep only (a few launches per proof: cheap enough for
     // timed regions), 2 = every kernel
     int prof_mode = 0;
-    struct ProfRec { int id; hipEvent_t a, b; };
+    struct ProfRec { int id; Event a, b; };
     std::vector<ProfRec> prof_open;
-    std::vector<hipEvent_t> prof_pool;
+    std::vector<Event> prof_pool;
     double prof_ms[KID_COUNT] = {0};
     std::vector<float> prof_wit_ms;     // the first 1024 k_witness_eval / k_witness_eval_repeat launches since the last reset, in launch order (a launch = a level of an assign)
     std::vector<std::pair<int, float>> prof_merkle_ms;   // the first 512 launches of the tree-hashing kernels (k_merkle_level, _top, _level_list) since the last reset, in launch order
     uint64_t prof_count[KID_COUNT] = {0};
     double prof_alg_bytes[KID_COUNT] = {0}, prof_act_bytes[KID_COUNT] = {0}, prof_fm[KID_COUNT] = {0};
     bool prof_on(int id) const { return prof_mode == 2 || (prof_mode == 1 && (id == KID_k_fold_points || id == KID_k_fold_points_reg || id == KID_k_fold_points_split || id == KID_k_fold_points_wnaf || id == KID_k_fold_points_quad || id == KID_k_fold_points_quadw || id == KID_k_fold_points_regw || id == KID_k_bucket_chunks)); }
-    hipEvent_t prof_event() { if (!prof_pool.empty()) { hipEvent_t e = prof_pool.back(); prof_pool.pop_back(); return e; } hipEvent_t e; HIPCHK(hipEventCreate(&e)); return e; }
-    void prof_begin(int id) { if (!prof_on(id)) return; ProfRec r{id, prof_event(), prof_event()}; HIPCHK(hipEventRecord(r.a, st)); prof_open.push_back(r); }
+    Event prof_event() { if (prof_pool.empty()) return Event::timed(); Event e = std::move(prof_pool.back()); prof_pool.pop_back(); return e; }
+    void prof_begin(int id) { if (!prof_on(id)) return; ProfRec r{id, prof_event(), prof_event()}; HIPCHK(hipEventRecord(r.a, st)); prof_open.push_back(std::move(r)); }
     void prof_end(int id) { if (!prof_on(id)) return; HIPCHK(hipEventRecord(prof_open.back().b, st)); }
     void prof_note(int id, double alg_bytes, double act_bytes, double fm) { if (!prof_on(id)) return; prof_alg_bytes[id] += alg_bytes; prof_act_bytes[id] += act_bytes; prof_fm[id] += fm; }
     void prof_collect() {
         if (prof_open.empty()) return;
         HIPCHK(hipStreamSynchronize(st));
-        for (ProfRec &r : prof_open) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, r.a, r.b)); prof_ms[r.id] += ms; prof_count[r.id]++; if ((r.id == KID_k_witness_eval || r.id == KID_k_witness_eval_repeat) && prof_wit_ms.size() < 1024) prof_wit_ms.push_back(ms); if ((r.id == KID_k_merkle_level || r.id == KID_k_merkle_top || r.id == KID_k_merkle_level_list) && prof_merkle_ms.size() < 512) prof_merkle_ms.emplace_back(r.id, ms); prof_pool.push_back(r.a); prof_pool.push_back(r.b); }
+        for (ProfRec &r : prof_open) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, r.a, r.b)); prof_ms[r.id] += ms; prof_count[r.id]++; if ((r.id == KID_k_witness_eval || r.id == KID_k_witness_eval_repeat) && prof_wit_ms.size() < 1024) prof_wit_ms.push_back(ms); if ((r.id == KID_k_merkle_level || r.id == KID_k_merkle_top || r.id == KID_k_merkle_level_list) && prof_merkle_ms.size() < 512) prof_merkle_ms.emplace_back(r.id, ms); prof_pool.push_back(std::move(r.a)); prof_pool.push_back(std::move(r.b)); }
         prof_open.clear();
     }
     void prof_reset() { prof_collect(); for (int i = 0; i < KID_COUNT; i++) { prof_ms[i] = 0; prof_count[i] = 0; prof_alg_bytes[i] = prof_act_bytes[i] = prof_fm[i] = 0; } prof_wit_ms.clear(); prof_merkle_ms.clear(); }
     std::shared_ptr<SharedTables> shared;       // the generation of generator tables this context works on
-    DevBuf gens;                                // view of shared->gens (not owned)
+    const ge_niels *gens = nullptr;             // shared->gens, [G | H]: a view, the generation owns the table
     DevBuf bases, scratch_ext, comp, small_in, small_sc;
     // MiMC sponges and Merkle trees (hip/k_mimc.cuh): the round constants of this device (shared by its contexts), the staging buffers of the calls, and the trees
     // this context built and has not freed (the destructor releases their device memory; bpg_merkle_free then only deletes the handle)
@@ -324,7 +302,7 @@ struct Engine::Impl {
     ge_pniels *tt_table_p = nullptr;            // the window tables in use: tt_table (original generators) or the arena (folded ones), set by tt_build
     void tt_build(const ge_niels *G, const ge_niels *H, const ge_niels *B, uint32_t M0, bool original) {
         const uint32_t npts = 2 * M0 + 1;
-        if (original && tt_orig_M0 == M0 && tt_orig_gens == gens.p) { tt_table_p = tt_table.as<ge_pniels>(); return; }
+        if (original && tt_orig_M0 == M0 && tt_orig_gens == gens) { tt_table_p = tt_table.as<ge_pniels>(); return; }
         const size_t bb = al256((size_t)npts * TT_WINDOWS * sizeof(ge_ext)), tb = (size_t)npts * TT_WINDOWS * TT_MULTS * sizeof(ge_pniels);
         ge_ext *basesp;
         if (original) {     // tables of the ORIGINAL generators outlive the proof (and serve A_I, A_O, S of the next one): buffers of their own
@@ -338,7 +316,7 @@ struct Engine::Impl {
         tt_partial.ensure((size_t)3 * cdiv((uint64_t)M0 * 16, 256) * sizeof(ge_ext));
         BPG_LAUNCH((*this), k_tt_bases, dim3(cdiv(npts, 64)), dim3(256), G, H, B, basesp, M0);
         BPG_LAUNCH((*this), k_tt_multiples, dim3(cdiv((uint64_t)npts * TT_WINDOWS, 256)), dim3(256), basesp, tt_table_p, npts * TT_WINDOWS);
-        if (original) { tt_orig_M0 = M0; tt_orig_gens = gens.p; }
+        if (original) { tt_orig_M0 = M0; tt_orig_gens = gens; }
     }
     // 8-bit window tables of the original generators (kernels.cuh k_tt_round8): shared per device like the fold tables, built on first use
     // Budgets.  table_budget bounds the CUMULATIVE bytes of precomputed multiples (fold tables + wide tail tables, every capacity) this process
@@ -370,26 +348,24 @@ struct Engine::Impl {
         DevBuf table, bases8;
         try { table.ensure(bytes); bases8.ensure((size_t)2 * M0 * TT8_WINDOWS * sizeof(ge_ext)); }
         catch (const std::exception &) {
-            (void)hipGetLastError(); table.release(); bases8.release();
+            (void)hipGetLastError();
             table_bytes_add(shared->device, -(int64_t)bytes); shared->refused[key] = table_bytes_held(shared->device); return nullptr;
         }
         try {
-            BPG_LAUNCH((*this), k_tt_bases8, dim3(cdiv(2 * M0, 64)), dim3(256), gens.as<ge_niels>(), gens.as<ge_niels>() + gens_cap, bases8.as<ge_ext>(), M0);
+            BPG_LAUNCH((*this), k_tt_bases8, dim3(cdiv(2 * M0, 64)), dim3(256), gens, gens + gens_cap, bases8.as<ge_ext>(), M0);
             BPG_LAUNCH((*this), k_tt_multiples8, dim3(cdiv((uint64_t)2 * M0 * TT8_WINDOWS, 256)), dim3(256), bases8.as<ge_ext>(), table.as<ge_pniels>(), 2 * M0 * TT8_WINDOWS);
             HIPCHK(hipGetLastError());
             HIPCHK(hipStreamSynchronize(st));
-        } catch (...) {   // a table that was not built is not published: give its memory and its share of the budget back (as odd_ensure does)
-            (void)hipStreamSynchronize(st); bases8.release(); table.release(); table_bytes_add(shared->device, -(int64_t)bytes);
+        } catch (...) {   // a table that was not built is not published: its share of the budget goes back here, its memory as the exception leaves (as in odd_ensure)
+            (void)hipStreamSynchronize(st); table_bytes_add(shared->device, -(int64_t)bytes);
             throw;
         }
-        bases8.release();
-        shared->wide[M0] = table;                                               // (its bytes were reserved above)
-        return table.as<ge_pniels>();
+        return (shared->wide[M0] = std::move(table)).as<ge_pniels>();           // (its bytes were reserved above)
     }
     PinBuf h_naf, h_qsteps;
     // odd multiples (2m+1) * 2^(j*L) * P of the original generators for the width-w NAF fold of the first group (k_fold_points_wnaf, scalars
     // cut into `fold_parts` pieces of L bits); built on first use for the device's generator tables and shared with them
-    DevBuf gens_odd;                 // view of shared->odd[fold_wnaf | fold_parts << 8] (not owned)
+    const ge_niels *gens_odd = nullptr;      // shared->odd[eff_wnaf | eff_parts << 8]: a view (nullptr: no table)
     uint32_t fold_wnaf = 5;          // width of the NAF the first fold recodes its scalars in (BPG_FOLD_WNAF; one-shot profile 5, serving 8; 0 = register kernels)
     uint32_t fold_parts = 2;         // the scalars of the first fold are cut into this many parts on tables of 2^(j*L) * P (BPG_FOLD_PARTS: 1, 2, 4 or 8; one-shot 2, serving 4)
     uint64_t fold_table_budget = 64ull << 30;       // per-kind cap of the fold tables (BPG_FOLD_TABLE_GB); the cumulative bound is table_budget
@@ -405,13 +381,13 @@ struct Engine::Impl {
         for (;;) {   // the widest profile that is already built, or fits the budgets and the device (other tenants): the next smaller one otherwise
             const uint32_t key = eff_wnaf | (eff_parts << 8);
             auto it = shared->odd.find(key);
-            if (it != shared->odd.end()) { gens_odd = it->second; return true; }
+            if (it != shared->odd.end()) { gens_odd = it->second.as<ge_niels>(); return true; }
             const uint64_t bytes = table_bytes(eff_wnaf, eff_parts);
             if (bytes <= fold_table_budget && table_reserve(key, bytes)) {
                 try { odd.ensure(bytes); break; }
-                catch (const std::exception &) { (void)hipGetLastError(); odd.release(); table_bytes_add(shared->device, -(int64_t)bytes); shared->refused[key] = table_bytes_held(shared->device); }
+                catch (const std::exception &) { (void)hipGetLastError(); table_bytes_add(shared->device, -(int64_t)bytes); shared->refused[key] = table_bytes_held(shared->device); }
             }
-            if (!smaller()) { gens_odd = DevBuf(); return false; }
+            if (!smaller()) { gens_odd = nullptr; return false; }
         }
         const uint32_t key_built = eff_wnaf | (eff_parts << 8);
         const uint32_t NM = 1u << (eff_wnaf - 2), cnt = (uint32_t)(2 * gens_cap), L = fold_part_bits();
@@ -423,9 +399,9 @@ struct Engine::Impl {
         const dim3 grid(cdiv(cnt, 256)), ngrid(cdiv(cdiv(cnt, NORM_K), 256));
         for (uint32_t part = 0; part < eff_parts; part++) {
             ge_niels *tab0 = odd.as<ge_niels>() + ((ptrdiff_t)part * NM - 1) * (ptrdiff_t)cnt;          // table (part, m) = tab0 + m * cnt; (0, 0) is the generator table
-            if (part == 0) BPG_LAUNCH((*this), k_odd_start, grid, dim3(256), gens.as<ge_niels>(), scratch_ext.as<ge_ext>(), dbl.as<ge_ext>(), cnt);
+            if (part == 0) BPG_LAUNCH((*this), k_odd_start, grid, dim3(256), gens, scratch_ext.as<ge_ext>(), dbl.as<ge_ext>(), cnt);
             else {
-                BPG_LAUNCH((*this), k_dbl_times, grid, dim3(256), gens.as<ge_niels>(), base.as<ge_ext>(), cnt, L, part == 1 ? 1u : 0u);      // 2^(part*L) * P
+                BPG_LAUNCH((*this), k_dbl_times, grid, dim3(256), gens, base.as<ge_ext>(), cnt, L, part == 1 ? 1u : 0u);      // 2^(part*L) * P
                 BPG_LAUNCH((*this), k_normalize_niels, ngrid, dim3(256), base.as<ge_ext>(), tab0, cnt);
                 BPG_LAUNCH((*this), k_odd_start_ext, grid, dim3(256), base.as<ge_ext>(), scratch_ext.as<ge_ext>(), dbl.as<ge_ext>(), cnt);
             }
@@ -436,14 +412,11 @@ struct Engine::Impl {
         }
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));
-        } catch (...) {   // a table that was not built is not published: give its memory and its share of the budget back
-            (void)hipStreamSynchronize(st); dbl.release(); base.release();
-            const uint64_t held = odd.cap; odd.release(); table_bytes_add(shared->device, -(int64_t)held);
+        } catch (...) {   // a table that was not built is not published: its share of the budget goes back here, its memory as the exception leaves (after this wait)
+            (void)hipStreamSynchronize(st); table_bytes_add(shared->device, -(int64_t)odd.cap);
             throw;
         }
-        dbl.release(); base.release();
-        shared->odd[key_built] = odd;                                           // (its bytes were reserved above)
-        gens_odd = odd;
+        gens_odd = (shared->odd[key_built] = std::move(odd)).as<ge_niels>();    // (its bytes were reserved above)
         return true;
     }
     uint32_t fold_split_max = 65536; // folds with at most this many outputs use the 4-wave latency variant (BPG_FOLD_SPLIT overrides; 0 = never)
@@ -469,7 +442,7 @@ struct Engine::Impl {
     // fastest at 3072 commitments (profiles/template_commit.json); BPG_COMMIT_CPW stays for that measurement only (tools/diag/template_commit.py), same bytes.
     // commit_ev: recorded behind the read-back of a wave's commitments, so that the host waits for them and not for the witness evaluation queued behind
     uint32_t commit_cpw = 4;
-    hipEvent_t commit_ev = nullptr;
+    Event commit_ev;
     PinBuf h_raw, h_small;
     // Speculative blinding streams (Engine::blinding_begin): the leading draws of Prover::prove's TranscriptRng, produced on the context's
     // chain worker (ONE host thread, FIFO) before the circuit is known - or, for a sequence of proofs, while the previous proof's kernels run.
@@ -484,7 +457,8 @@ struct Engine::Impl {
     std::deque<std::shared_ptr<BlindStream>> blinds;        // alive streams, oldest first
     std::vector<std::shared_ptr<BlindStream>> slab_owner;   // last stream that wrote each pinned slab (workers + 1 slabs)
     std::vector<PinBuf> h_blind;
-    struct SlabDev { DevBuf d; hipStream_t copy_st = nullptr; std::vector<hipEvent_t> ev; };
+    struct SlabDev { Stream copy_st; DevBuf d; std::vector<Event> ev; };                 // (the copy stream goes last)
+    static hipEvent_t block_event(const BlindStream &bs, uint64_t k) { return (*static_cast<const std::vector<Event> *>(bs.ev))[k]; }      // BlindStream::ev is SlabDev::ev, opaque to host/chain.hpp
     std::vector<std::unique_ptr<SlabDev>> slab_dev;         // device side of each slab: the uploaded draws, the copy stream, one event per block
     int last_chain_cpu = -1;
     int test_fail_upload = 0;       // test hooks: 1 the next stream's upload reports an error, 2 its copies are silently dropped
@@ -517,8 +491,8 @@ struct Engine::Impl {
     uint64_t gens_cap = 0;
     // BPG_GENS_CACHE_DIR (see gens_cache_path): load = read + checksum + upload + compare 2 x 64 sampled points with points derived afresh from
     // the SHAKE256 stream (k_gens_derive on 128 generators); anything that does not agree falls back to the full derivation
-    bool gens_load_cached(const std::string &path, uint64_t cap, DevBuf &out);
-    void adopt(const std::shared_ptr<SharedTables> &sp) { shared = sp; gens = sp->gens; gens_cap = sp->cap; gens_odd = DevBuf(); }
+    DevBuf gens_load_cached(const std::string &path, uint64_t cap);        // the table, or an empty buffer
+    void adopt(const std::shared_ptr<SharedTables> &sp) { shared = sp; gens = sp->gens.as<ge_niels>(); gens_cap = sp->cap; gens_odd = nullptr; }
     void gens_store_cached(const std::string &path, uint64_t cap);
 
     // An MSM runs on the GPU down to its W window sums per result; those (W x 128 B) travel to a pinned slot and the serial recombination
@@ -545,11 +519,11 @@ struct Engine::Impl {
     // Host -> device copy of caller-owned pageable memory through two pinned bounce slots.  A direct hipMemcpyAsync from pageable memory
     // lets the runtime pin the caller's pages for the DMA; several contexts uploading the SAME arrays from different threads (a pool
     // proving many witnesses of one circuit) then pin and unpin the same pages concurrently, which faulted the GPU.
-    PinBuf stage; hipEvent_t stage_ev[2] = {nullptr, nullptr};
+    PinBuf stage; Event stage_ev[2];
     void h2d(void *dst, const void *src, size_t bytes) {
         const size_t SLOT = 8u << 20;
         stage.ensure(2 * SLOT);
-        for (int k = 0; k < 2; k++) if (!stage_ev[k]) HIPCHK(hipEventCreateWithFlags(&stage_ev[k], hipEventDisableTiming));
+        for (int k = 0; k < 2; k++) if (!stage_ev[k]) stage_ev[k] = Event::untimed();
         const uint8_t *s8 = static_cast<const uint8_t *>(src); uint8_t *d8 = static_cast<uint8_t *>(dst);
         int slot = 0;
         for (size_t off = 0; off < bytes; off += SLOT, slot ^= 1) {
@@ -611,6 +585,7 @@ Engine::Engine(int device, const EngineConfig &cfg) : device_(device) {
     // What the host chose (bpg_config): the struct first, then the environment variable, then the profile's default.  Everything is settled
     // in this local Impl before the first HIP call, so a bad knob costs nothing and leaks nothing.
     std::unique_ptr<Impl> K(new Impl());
+    K->device = device;
     int blocking = cfg.blocking_sync == 2 ? 0 : cfg.blocking_sync;          // -1 unset, 0 spin, 1 blocking (2: what one header revision called spin)
     if (blocking < 0 && env_present("BPG_SYNC_BLOCKING")) blocking = env_int_strict("BPG_SYNC_BLOCKING", 0, 1) ? 1 : 0;
     uint32_t profile = cfg.profile;
@@ -676,14 +651,14 @@ Engine::Engine(int device, const EngineConfig &cfg) : device_(device) {
             if (!env_present("BPG_WINDOW_QUAD_BLOCKS")) K->window_quad_blocks = (uint32_t)cus + (uint32_t)cus / 8u;
         }
     }
-    impl_ = K.release();
-    try { init_device(); }
-    catch (...) { if (impl_->st) (void)hipStreamDestroy(impl_->st); delete impl_; impl_ = nullptr; throw; }
+    impl_ = K.get();
+    try { init_device(); } catch (...) { impl_ = nullptr; throw; }        // K still owns the Impl: what init_device() had allocated goes with it
+    K.release();
 }
 
 void Engine::init_device() {
-    HIPCHK(hipStreamCreate(&impl_->st));
-    stream_ = impl_->st;
+    impl_->st = Stream::blocking();
+    stream_ = (hipStream_t)impl_->st;
     // Pedersen bases: B_blinding = from_uniform(SHA3-512(compress(B)))  (PedersenGens::default, reference src/bin/prover.rs:53)
     static const uint8_t Bc[32] = {0xe2, 0xf2, 0xae, 0x0a, 0x6a, 0xbc, 0x4e, 0x71, 0xa8, 0x84, 0xa9, 0x61, 0xc5, 0x00, 0x51, 0x5f,
                                    0x58, 0xe3, 0x0b, 0x6a, 0xa5, 0x82, 0xdd, 0x8d, 0xb6, 0xa6, 0x59, 0x45, 0xe0, 0x8d, 0x2d, 0x76};
@@ -704,35 +679,21 @@ void Engine::init_device() {
     HIPCHK(hipStreamSynchronize(impl_->st));
 }
 
-Engine::~Engine() {
-    if (!impl_) return;
-    // order: (1) no host thread of ours issues work for this context any more (the chain threads have left its streams), (2) everything this
-    // context queued has finished - the engine stream AND the slabs' copy streams, whose uploads read the pinned slabs - (3) only then memory goes
-    impl_->chain_shutdown();
-    (void)hipSetDevice(device_);
-    (void)hipStreamSynchronize(impl_->st);
-    for (auto &sd : impl_->slab_dev) if (sd->copy_st) (void)hipStreamSynchronize(sd->copy_st);
-    DevBuf *bufs[] = {&impl_->bases, &impl_->scratch_ext, &impl_->comp, &impl_->small_in, &impl_->small_sc, &impl_->counts,
-                      &impl_->starts, &impl_->cursor, &impl_->blocksum, &impl_->arena, &impl_->buckets, &impl_->partial, &impl_->msm_result,
-                      &impl_->sLR, &impl_->yinvpow, &impl_->lv, &impl_->rv, &impl_->red_partial,
-                      &impl_->red_out, &impl_->raw_rng, &impl_->extras, &impl_->ipa_s, &impl_->ipa_tabA, &impl_->ipa_tabB, &impl_->naf, &impl_->qsteps, &impl_->wsums, &impl_->wq_stage, &impl_->wq_tickets, &impl_->vfy_in, &impl_->vfy_pts, &impl_->vfy_ok, &impl_->vfy_sc, &impl_->vfy_ch, &impl_->vfy_small,
-                      &impl_->stale_flag, &impl_->tile_hist, &impl_->heavy, &impl_->plain, &impl_->open_keys, &impl_->medium, &impl_->tt_bases, &impl_->tt_table, &impl_->tt_f, &impl_->tt_c, &impl_->tt_partial, &impl_->grp_c, &impl_->ped_table, &impl_->s_parts, &impl_->starts1, &impl_->mk_in, &impl_->mk_out, &impl_->chk_v, &impl_->chk_bitmap, &impl_->chk_report};
-    for (DevBuf *b : bufs) b->release();
-    for (DeviceMerkle *t : impl_->trees) merkle_orphan(t);       // trees the host has not freed: their memory goes with the context, their handles stay valid
-    impl_->mimc.reset();
-    impl_->shared.reset();                                   // the generator tables go with their last context
-    impl_->h_raw.release(); impl_->h_small.release(); impl_->h_naf.release(); impl_->h_qsteps.release(); impl_->stage.release(); for (PinBuf &b : impl_->h_blind) b.release();
-    for (auto &sd : impl_->slab_dev) {
-        if (sd->copy_st) { (void)hipStreamSynchronize(sd->copy_st); (void)hipStreamDestroy(sd->copy_st); }
-        for (hipEvent_t e : sd->ev) (void)hipEventDestroy(e);
-        sd->d.release();
-    }
-    for (int k = 0; k < 2; k++) if (impl_->stage_ev[k]) (void)hipEventDestroy(impl_->stage_ev[k]);
-    if (impl_->commit_ev) (void)hipEventDestroy(impl_->commit_ev);
-    (void)hipStreamDestroy(impl_->st);
-    delete impl_;
+Engine::~Engine() { delete impl_; }
+// order: (1) no host thread of ours issues work for this context any more (the chain threads have left its streams), (2) everything this
+// context queued has finished - the engine stream AND the slabs' copy streams, whose uploads read the pinned slabs - (3) only then memory goes:
+// the trees the host has not freed lose theirs here (their handles stay valid), the members free themselves in reverse order of declaration - the
+// generator tables and the MiMC constants with their last context - and the engine stream, the first member, goes last
+Engine::Impl::~Impl() {
+    chain_shutdown();
+    if (!st) return;                            // the constructor failed before init_device(): nothing of this context is on a device
+    (void)hipSetDevice(device);
+    (void)hipStreamSynchronize(st);
+    for (auto &sd : slab_dev) if (sd->copy_st) (void)hipStreamSynchronize(sd->copy_st);
+    for (DeviceMerkle *t : trees) merkle_orphan(t);
 }
 
+void live_resources(uint64_t out[6]) { for (int k = 0; k < LIVE_COUNT; k++) out[k] = g_live[k].load(std::memory_order_relaxed); }
 int Engine::device_count() { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess) { (void)hipGetLastError(); return 0; } return n; }
 void Engine::profile_set(int mode) { HIPCHK(hipSetDevice(device_)); impl_->prof_reset(); impl_->prof_mode = mode; }
 std::string Engine::profile_report() {
@@ -777,7 +738,7 @@ double Engine::bench_fe_mul(uint32_t iters) {
     Impl &I = *impl_;
     const uint32_t blocks = 256 * 16, threads = 256;
     I.small_sc.ensure((size_t)blocks * threads * sizeof(fe));
-    hipEvent_t a, b; HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
+    const Event a = Event::timed(), b = Event::timed();
     hipLaunchKernelGGL(k_bench_fe_mul, dim3(blocks), dim3(threads), 0, I.st, I.small_sc.as<fe>(), 8u);     // warm-up
     HIPCHK(hipEventRecord(a, I.st));
     hipLaunchKernelGGL(k_bench_fe_mul, dim3(blocks), dim3(threads), 0, I.st, I.small_sc.as<fe>(), iters);
@@ -785,7 +746,6 @@ double Engine::bench_fe_mul(uint32_t iters) {
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventSynchronize(b));
     float ms = 0; HIPCHK(hipEventElapsedTime(&ms, a, b));
-    (void)hipEventDestroy(a); (void)hipEventDestroy(b);
     return (double)blocks * threads * iters * 4.0 / (ms * 1e-3);
 }
 
@@ -845,13 +805,13 @@ void Engine::gens_ensure(uint64_t capacity) {
     }
     auto publish = [&](DevBuf fresh) {
         auto sp = std::make_shared<SharedTables>();
-        sp->device = device_; sp->cap = cap; sp->gens = fresh;
+        sp->device = device_; sp->cap = cap; sp->gens = std::move(fresh);
         if (share) g_tables[{device_, cap}] = sp;
         I.adopt(sp); gens_cap_ = cap;
     };
     const std::string cache_file = gens_cache_path(I.gens_cache_dir, cap);
     const bool cache_ok = !cache_file.empty() && gens_cache_trusted(I.gens_cache_dir, cache_file);       // else: derive, never read or write the cache
-    if (cache_ok) { DevBuf loaded; if (I.gens_load_cached(cache_file, cap, loaded)) { publish(loaded); return; } }
+    if (cache_ok) { DevBuf loaded = I.gens_load_cached(cache_file, cap); if (loaded.p) { publish(std::move(loaded)); return; } }
     I.h_raw.ensure(2 * cap * 64);
     {   // the two chains are independent XOF streams: squeeze them on two threads; the streams are prefixes of one another across
         // capacities, so a process-wide cache keeps the longest one squeezed so far (contexts of a batch share it)
@@ -885,15 +845,15 @@ void Engine::gens_ensure(uint64_t capacity) {
     BPG_LAUNCH(I, k_normalize_niels, dim3(cdiv(cdiv(cnt, NORM_K), 256)), dim3(256), I.scratch_ext.as<ge_ext>(), fresh.as<ge_niels>(), cnt);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(I.st));
-    publish(fresh);
+    publish(std::move(fresh));
     I.raw_rng.release(); I.scratch_ext.release(); I.h_raw.release();      // one-off derivation buffers (0.4 GB of device memory at 2^20); the prove path sizes its own
     if (cache_ok) I.gens_store_cached(cache_file, cap);
 }
 
-bool Engine::Impl::gens_load_cached(const std::string &path, uint64_t cap, DevBuf &out) {
+DevBuf Engine::Impl::gens_load_cached(const std::string &path, uint64_t cap) {
     const int fd = ::open(path.c_str(), O_RDONLY | O_NOFOLLOW | O_CLOEXEC);
     FILE *f = fd >= 0 ? ::fdopen(fd, "rb") : nullptr;
-    if (!f) { if (fd >= 0) ::close(fd); return false; }
+    if (!f) { if (fd >= 0) ::close(fd); return DevBuf(); }
     const size_t bytes = (size_t)2 * cap * sizeof(ge_niels);
     GensCacheHeader hd;
     bool ok = std::fread(&hd, sizeof hd, 1, f) == 1 && std::memcmp(hd.magic, kGensMagic, 8) == 0 && hd.version == 2 && hd.capacity == cap && hd.bytes == bytes;
@@ -901,7 +861,7 @@ bool Engine::Impl::gens_load_cached(const std::string &path, uint64_t cap, DevBu
     if (ok) { host.ensure(bytes); ok = std::fread(host.p, 1, bytes, f) == bytes && std::fgetc(f) == EOF; }
     std::fclose(f);
     if (ok) ok = gens_checksum(host.as<uint8_t>(), bytes) == hd.checksum;
-    if (!ok) { host.release(); return false; }
+    if (!ok) return DevBuf();
     DevBuf fresh; fresh.ensure(bytes);
     HIPCHK(hipMemcpyAsync(fresh.p, host.p, bytes, hipMemcpyHostToDevice, st));
     // sample: the first 64 generators of G and of H, derived afresh (the head of each SHAKE256 chain: 4 KB) and normalised the usual way
@@ -926,15 +886,13 @@ bool Engine::Impl::gens_load_cached(const std::string &path, uint64_t cap, DevBu
     std::vector<uint8_t> enc((size_t)4 * SAMPLE * 32);
     HIPCHK(hipMemcpyAsync(enc.data(), comp.p, enc.size(), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    host.release(); smp.release();
-    if (std::memcmp(enc.data(), enc.data() + (size_t)2 * SAMPLE * 32, (size_t)2 * SAMPLE * 32) != 0) { fresh.release(); return false; }
-    out = fresh;
-    return true;
+    if (std::memcmp(enc.data(), enc.data() + (size_t)2 * SAMPLE * 32, (size_t)2 * SAMPLE * 32) != 0) return DevBuf();
+    return fresh;
 }
 void Engine::Impl::gens_store_cached(const std::string &path, uint64_t cap) {
     const size_t bytes = (size_t)2 * cap * sizeof(ge_niels);
     std::vector<uint8_t> host(bytes);
-    HIPCHK(hipMemcpyAsync(host.data(), gens.p, bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(host.data(), gens, bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     GensCacheHeader hd; std::memcpy(hd.magic, kGensMagic, 8); hd.version = 2; hd.capacity = cap; hd.bytes = bytes; hd.checksum = gens_checksum(host.data(), bytes);
     std::string tmp = path + ".tmp.XXXXXX";
@@ -952,7 +910,7 @@ void Engine::gens_export(uint64_t first, uint64_t count, uint8_t *G_out, uint8_t
     Impl &I = *impl_;
     I.comp.ensure(count * 32);
     for (int which = 0; which < 2; which++) {
-        const ge_niels *src = I.gens.as<ge_niels>() + (which ? gens_cap_ : 0) + first;
+        const ge_niels *src = I.gens + (which ? gens_cap_ : 0) + first;
         BPG_LAUNCH(I, k_compress_niels, dim3(cdiv(count, 64)), dim3(64), src, I.comp.as<uint8_t>(), (uint32_t)count);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(which ? H_out : G_out, I.comp.p, count * 32, hipMemcpyDeviceToHost, I.st));
@@ -1061,8 +1019,8 @@ void Engine::msm_gens(uint64_t first, uint64_t count, const uint8_t *s, const ui
         BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(2 * count, 256)), dim3(256), I.small_sc.as<uint32_t>(), I.sLR.as<scm>(), (uint32_t)(2 * count));
     }
     MsmJob J = job_new();
-    seg_push(J, I.sLR.as<scm>(), I.gens.as<ge_niels>() + first, (uint32_t)count, 0);
-    seg_push(J, I.sLR.as<scm>() + count, I.gens.as<ge_niels>() + gens_cap_ + first, (uint32_t)count, 0);
+    seg_push(J, I.sLR.as<scm>(), I.gens + first, (uint32_t)count, 0);
+    seg_push(J, I.sLR.as<scm>() + count, I.gens + gens_cap_ + first, (uint32_t)count, 0);
     const Impl::MsmTicket tk = I.msm(J, 1);
     HIPCHK(hipStreamSynchronize(I.st));
     h51::pt_compress(out, I.msm_points(tk)[0]);
@@ -1115,7 +1073,7 @@ std::string Engine::test_msm(uint32_t nmsm, uint32_t nseg, const MsmSegSpec *seg
             I.h2d(I.test_skip.as<uint32_t>() + w0, g.skip, nw * 4);
             skip = I.test_skip.as<uint32_t>() + w0; w0 += nw;
         }
-        seg_push(J, I.sLR.as<scm>() + t0, I.gens.as<ge_niels>() + (g.table ? gens_cap_ : 0) + g.first, g.len, g.result, g.lgblk, skip);
+        seg_push(J, I.sLR.as<scm>() + t0, I.gens + (g.table ? gens_cap_ : 0) + g.first, g.len, g.result, g.lgblk, skip);
         t0 += g.len;
     }
     J.skipped = (uint32_t)skipped;
@@ -1200,55 +1158,51 @@ DeviceCircuit *Engine::upload(const FlatView &c) {
     // transposition CSR (by constraint) -> CSC (by variable) on the device (transpose_csr);
     // columns: [0,n) left, [n,2n) right, [2n,3n) output, [3n,3n+m) committed, 3n+m = the constant terms (only the verifier's w_c needs them)
     const uint64_t ncols = 3 * n + m + 1, nvar = ncols - 1;
-    DeviceCircuit *d = new DeviceCircuit();
+    std::unique_ptr<DeviceCircuit> d(new DeviceCircuit());       // (the device is current: a failure below frees what it holds as it leaves)
     d->n = n; d->m = m; d->q = q; d->ncols = ncols; d->has_witness = has_witness;
-    try {
-        d->aL.ensure((n ? n : 1) * sizeof(scm)); d->aR.ensure((n ? n : 1) * sizeof(scm)); d->aO.ensure((n ? n : 1) * sizeof(scm));
-        d->col_ptr.ensure((ncols + 1) * 8); d->ent_row.ensure((nnz ? nnz : 1) * 4); d->ent_coef.ensure((nnz ? nnz : 1) * 4);
-        d->coef.ensure((ncoef ? ncoef : 1) * sizeof(scm));
-        {
-            // the CSR arrays travel as they are; workspace: the MSM sort buffers (no MSM runs on this context during an upload)
-            I.arena.ensure((nnz ? nnz : 1) * 8);                                // term_var | term_coef
-            I.plain.ensure((q + 2) * 8 + 64);                                   // row_ptr
-            I.counts.ensure((std::max<uint64_t>(nvar, q) + 2) * 4); I.starts.ensure((std::max<uint64_t>(nvar, q) + 2) * 4);
-            I.cursor.ensure((std::max<uint64_t>(nvar, q) + 2) * 4); I.heavy.ensure((q + 2) * 4); I.tile_hist.ensure((q + 2) * 4 + 64);
-            I.blocksum.ensure((size_t)(std::max(cdiv(nvar ? nvar : 1, SCAN_CHUNK), cdiv(q ? q : 1, SCAN_CHUNK)) + 2) * 4);
-            I.extras.ensure(16 * sizeof(scm));
-            uint32_t *tv = I.arena.as<uint32_t>(), *tc = tv + (nnz ? nnz : 1);
-            uint64_t *rp = I.plain.as<uint64_t>();
-            uint32_t *totals = reinterpret_cast<uint32_t *>(I.extras.as<scm>() + 8);
-            if (nnz) { I.h2d(tv, c.term_var, nnz * 4); I.h2d(tc, c.term_coef, nnz * 4); }
-            I.h2d(rp, c.row_ptr, (q + 1) * 8);
-            I.transpose_csr(rp, tv, tc, q, n, m, {I.counts.as<uint32_t>(), I.starts.as<uint32_t>(), I.cursor.as<uint32_t>(), I.heavy.as<uint32_t>(), I.tile_hist.as<uint32_t>(), I.blocksum.as<uint32_t>()},
-                            d->col_ptr.as<uint64_t>(), d->ent_row.as<uint32_t>(), d->ent_coef.as<uint32_t>(), totals);
-            HIPCHK(hipGetLastError());
-            uint32_t h_tot[2] = {0, 0};
-            HIPCHK(hipMemcpyAsync(h_tot, totals, 8, hipMemcpyDeviceToHost, I.st));
-            HIPCHK(hipStreamSynchronize(I.st));
-            d->const_begin = h_tot[0]; d->nnz = h_tot[1];
-            if (d->nnz != nnz) throw std::logic_error("upload: transposition lost entries");
-        }
-        const size_t maxn = std::max<uint64_t>(n, ncoef);
-        I.small_sc.ensure((maxn ? maxn : 1) * 32);
-        const uint8_t *src[4] = {c.aL, c.aR, c.aO, c.coef};
-        DevBuf *dst[4] = {&d->aL, &d->aR, &d->aO, &d->coef};
-        const uint64_t cnts[4] = {n, n, n, ncoef};
-        for (int k = 0; k < 4; k++) {
-            if (!cnts[k] || (k < 3 && !has_witness)) continue;
-            I.h2d(I.small_sc.p, src[k], cnts[k] * 32);
-            BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(cnts[k], 256)), dim3(256), I.small_sc.as<uint32_t>(), dst[k]->as<scm>(), (uint32_t)cnts[k]);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(I.st));
-        }
-    } catch (...) { free_circuit(d); throw; }
-    return d;
+    d->aL.ensure((n ? n : 1) * sizeof(scm)); d->aR.ensure((n ? n : 1) * sizeof(scm)); d->aO.ensure((n ? n : 1) * sizeof(scm));
+    d->col_ptr.ensure((ncols + 1) * 8); d->ent_row.ensure((nnz ? nnz : 1) * 4); d->ent_coef.ensure((nnz ? nnz : 1) * 4);
+    d->coef.ensure((ncoef ? ncoef : 1) * sizeof(scm));
+    {
+        // the CSR arrays travel as they are; workspace: the MSM sort buffers (no MSM runs on this context during an upload)
+        I.arena.ensure((nnz ? nnz : 1) * 8);                                // term_var | term_coef
+        I.plain.ensure((q + 2) * 8 + 64);                                   // row_ptr
+        I.counts.ensure((std::max<uint64_t>(nvar, q) + 2) * 4); I.starts.ensure((std::max<uint64_t>(nvar, q) + 2) * 4);
+        I.cursor.ensure((std::max<uint64_t>(nvar, q) + 2) * 4); I.heavy.ensure((q + 2) * 4); I.tile_hist.ensure((q + 2) * 4 + 64);
+        I.blocksum.ensure((size_t)(std::max(cdiv(nvar ? nvar : 1, SCAN_CHUNK), cdiv(q ? q : 1, SCAN_CHUNK)) + 2) * 4);
+        I.extras.ensure(16 * sizeof(scm));
+        uint32_t *tv = I.arena.as<uint32_t>(), *tc = tv + (nnz ? nnz : 1);
+        uint64_t *rp = I.plain.as<uint64_t>();
+        uint32_t *totals = reinterpret_cast<uint32_t *>(I.extras.as<scm>() + 8);
+        if (nnz) { I.h2d(tv, c.term_var, nnz * 4); I.h2d(tc, c.term_coef, nnz * 4); }
+        I.h2d(rp, c.row_ptr, (q + 1) * 8);
+        I.transpose_csr(rp, tv, tc, q, n, m, {I.counts.as<uint32_t>(), I.starts.as<uint32_t>(), I.cursor.as<uint32_t>(), I.heavy.as<uint32_t>(), I.tile_hist.as<uint32_t>(), I.blocksum.as<uint32_t>()},
+                        d->col_ptr.as<uint64_t>(), d->ent_row.as<uint32_t>(), d->ent_coef.as<uint32_t>(), totals);
+        HIPCHK(hipGetLastError());
+        uint32_t h_tot[2] = {0, 0};
+        HIPCHK(hipMemcpyAsync(h_tot, totals, 8, hipMemcpyDeviceToHost, I.st));
+        HIPCHK(hipStreamSynchronize(I.st));
+        d->const_begin = h_tot[0]; d->nnz = h_tot[1];
+        if (d->nnz != nnz) throw std::logic_error("upload: transposition lost entries");
+    }
+    const size_t maxn = std::max<uint64_t>(n, ncoef);
+    I.small_sc.ensure((maxn ? maxn : 1) * 32);
+    const uint8_t *src[4] = {c.aL, c.aR, c.aO, c.coef};
+    scm *const dst[4] = {d->aL.as<scm>(), d->aR.as<scm>(), d->aO.as<scm>(), d->coef.as<scm>()};
+    const uint64_t cnts[4] = {n, n, n, ncoef};
+    for (int k = 0; k < 4; k++) {
+        if (!cnts[k] || (k < 3 && !has_witness)) continue;
+        I.h2d(I.small_sc.p, src[k], cnts[k] * 32);
+        BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(cnts[k], 256)), dim3(256), I.small_sc.as<uint32_t>(), dst[k], (uint32_t)cnts[k]);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(I.st));
+    }
+    return d.release();
 }
 
 void Engine::free_circuit(DeviceCircuit *c) {
     if (!c) return;
     (void)hipSetDevice(device_);
-    DevBuf *b[] = {&c->wit_stream, &c->wit_segs, &c->wit_v, &c->aL, &c->aR, &c->aO, &c->col_ptr, &c->ent_row, &c->ent_coef, &c->coef, &c->mI.skipA, &c->mI.skipB, &c->mI.sc, &c->mI.pts, &c->mO.skipA, &c->mO.skipB, &c->mO.sc, &c->mO.pts, &c->rv_ptr, &c->rv_ent, &c->rv_long};
-    for (DevBuf *x : b) x->release();
     delete c;
 }
 
@@ -1306,18 +1260,16 @@ void Engine::template_eval_batch_host(const FlatView &c, const WitnessProgramVie
 DeviceCircuit *Engine::upload_template(const FlatView &c, const TemplatePlan &T) {
     const PackedWitnessProgram &P = T.packed;
     FlatView f(T.slotted); f.aL = c.aL; f.aR = c.aR; f.aO = c.aO;
-    DeviceCircuit *d = upload(f);
-    try {
-        Impl &I = *impl_;
-        d->is_template = true; d->n_params = T.n_params; d->param_first = T.param_first;
-        d->wit_level_ptr = T.schedule.level_ptr;
-        if (ceil_log2(c.n) <= TEMPLATE_HOST_COPY_LG) { d->host = T.slotted; d->host_view = FlatView(d->host); d->has_host = true; }
-        d->wit_stream.ensure(P.stream.size() * 4); d->wit_segs.ensure(P.segs.size() * sizeof(WitnessSegment)); d->wit_v.ensure((c.m ? c.m : 1) * sizeof(scm));
-        I.h2d(d->wit_stream.p, P.stream.data(), P.stream.size() * 4);
-        I.h2d(d->wit_segs.p, P.segs.data(), P.segs.size() * sizeof(WitnessSegment));
-        HIPCHK(hipStreamSynchronize(I.st));
-    } catch (...) { free_circuit(d); throw; }
-    return d;
+    std::unique_ptr<DeviceCircuit> d(upload(f));
+    Impl &I = *impl_;
+    d->is_template = true; d->n_params = T.n_params; d->param_first = T.param_first;
+    d->wit_level_ptr = T.schedule.level_ptr;
+    if (ceil_log2(c.n) <= TEMPLATE_HOST_COPY_LG) { d->host = T.slotted; d->host_view = FlatView(d->host); d->has_host = true; }
+    d->wit_stream.ensure(P.stream.size() * 4); d->wit_segs.ensure(P.segs.size() * sizeof(WitnessSegment)); d->wit_v.ensure((c.m ? c.m : 1) * sizeof(scm));
+    I.h2d(d->wit_stream.p, P.stream.data(), P.stream.size() * 4);
+    I.h2d(d->wit_segs.p, P.segs.data(), P.segs.size() * sizeof(WitnessSegment));
+    HIPCHK(hipStreamSynchronize(I.st));
+    return d.release();
 }
 
 void Engine::assign(DeviceCircuit *d, const uint8_t *v, const uint8_t *param_values) {
@@ -1457,26 +1409,24 @@ DeviceCircuit *Engine::repeat_template(DeviceCircuit *src, uint64_t count) {
     Impl &I = *impl_;
     const uint64_t K = count, n = K * src->n, m = K * src->m, q = K * src->q, nnz = K * src->nnz, ncols = 3 * n + m + 1, ncoef = src->param_first + K * src->n_params;
     const RepeatDims D{(uint32_t)src->n, (uint32_t)src->m, (uint32_t)src->q, (uint32_t)src->param_first, (uint32_t)src->n_params};
-    DeviceCircuit *d = new DeviceCircuit();
+    std::unique_ptr<DeviceCircuit> d(new DeviceCircuit());
     d->n = n; d->m = m; d->q = q; d->ncols = ncols; d->nnz = nnz; d->const_begin = K * src->const_begin; d->has_witness = false;
     d->is_template = true; d->n_params = K * src->n_params; d->param_first = src->param_first; d->wit_level_ptr = src->wit_level_ptr;
     d->rep_count = K; d->rep_n = src->n; d->rep_m = src->m;
-    try {
-        d->aL.ensure(n * sizeof(scm)); d->aR.ensure(n * sizeof(scm)); d->aO.ensure(n * sizeof(scm));
-        d->col_ptr.ensure((ncols + 1) * 8); d->ent_row.ensure((nnz ? nnz : 1) * 4); d->ent_coef.ensure((nnz ? nnz : 1) * 4);
-        d->coef.ensure((ncoef ? ncoef : 1) * sizeof(scm));
-        d->wit_stream.ensure(src->wit_stream.cap); d->wit_segs.ensure(src->wit_segs.cap); d->wit_v.ensure((m ? m : 1) * sizeof(scm));
-        HIPCHK(hipMemcpyAsync(d->wit_stream.p, src->wit_stream.p, src->wit_stream.cap, hipMemcpyDeviceToDevice, I.st));
-        HIPCHK(hipMemcpyAsync(d->wit_segs.p, src->wit_segs.p, src->wit_segs.cap, hipMemcpyDeviceToDevice, I.st));
-        const uint32_t gy = (uint32_t)std::min<uint64_t>(K, 1024);           // copies beyond the grid's y extent are a loop in the kernels
-        BPG_LAUNCH(I, k_repeat_colptr, dim3(cdiv(3 * src->n + src->m + 1, 256), gy), dim3(256), src->col_ptr.as<uint64_t>(), D, (uint32_t)K, d->col_ptr.as<uint64_t>());
-        if (src->nnz) BPG_LAUNCH(I, k_repeat_entries, dim3(cdiv(src->nnz, 256), gy), dim3(256), src->col_ptr.as<uint64_t>(), src->ent_row.as<uint32_t>(),
-                                 src->ent_coef.as<uint32_t>(), D, (uint32_t)K, src->nnz, d->ent_row.as<uint32_t>(), d->ent_coef.as<uint32_t>());
-        if (ncoef) BPG_LAUNCH(I, k_repeat_coef, dim3(cdiv(ncoef, 256)), dim3(256), src->coef.as<scm>(), D, (uint32_t)K, d->coef.as<scm>());
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(I.st));
-    } catch (...) { free_circuit(d); throw; }
-    return d;
+    d->aL.ensure(n * sizeof(scm)); d->aR.ensure(n * sizeof(scm)); d->aO.ensure(n * sizeof(scm));
+    d->col_ptr.ensure((ncols + 1) * 8); d->ent_row.ensure((nnz ? nnz : 1) * 4); d->ent_coef.ensure((nnz ? nnz : 1) * 4);
+    d->coef.ensure((ncoef ? ncoef : 1) * sizeof(scm));
+    d->wit_stream.ensure(src->wit_stream.cap); d->wit_segs.ensure(src->wit_segs.cap); d->wit_v.ensure((m ? m : 1) * sizeof(scm));
+    HIPCHK(hipMemcpyAsync(d->wit_stream.p, src->wit_stream.p, src->wit_stream.cap, hipMemcpyDeviceToDevice, I.st));
+    HIPCHK(hipMemcpyAsync(d->wit_segs.p, src->wit_segs.p, src->wit_segs.cap, hipMemcpyDeviceToDevice, I.st));
+    const uint32_t gy = (uint32_t)std::min<uint64_t>(K, 1024);           // copies beyond the grid's y extent are a loop in the kernels
+    BPG_LAUNCH(I, k_repeat_colptr, dim3(cdiv(3 * src->n + src->m + 1, 256), gy), dim3(256), src->col_ptr.as<uint64_t>(), D, (uint32_t)K, d->col_ptr.as<uint64_t>());
+    if (src->nnz) BPG_LAUNCH(I, k_repeat_entries, dim3(cdiv(src->nnz, 256), gy), dim3(256), src->col_ptr.as<uint64_t>(), src->ent_row.as<uint32_t>(),
+                             src->ent_coef.as<uint32_t>(), D, (uint32_t)K, src->nnz, d->ent_row.as<uint32_t>(), d->ent_coef.as<uint32_t>());
+    if (ncoef) BPG_LAUNCH(I, k_repeat_coef, dim3(cdiv(ncoef, 256)), dim3(256), src->coef.as<scm>(), D, (uint32_t)K, d->coef.as<scm>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(I.st));
+    return d.release();
 }
 
 namespace {
@@ -1623,7 +1573,7 @@ void Engine::Impl::inner_product(Transcript &T, std::vector<uint8_t> &proof, uin
             const uint32_t M0 = (uint32_t)mcur;
             I.tt_f.ensure((size_t)2 * M0 * sizeof(scm)); I.tt_c.ensure((size_t)4 * M0 * sizeof(scm));
             I.tt_build(Gst, Hst, Bn, M0, Gst == Gtab && Hst == Htab);          // no-op when this context already holds them (N <= 2^tt_orig_lg)
-            tt_wide = (Gst == Gtab && Hst == Htab && Gtab == I.gens.as<ge_niels>()) ? I.wide_ensure(M0) : nullptr;       // original generators: 8-bit windows, built once per device
+            tt_wide = (Gst == Gtab && Hst == Htab && Gtab == I.gens) ? I.wide_ensure(M0) : nullptr;       // original generators: 8-bit windows, built once per device
             BPG_LAUNCH(I, k_tt_factors, dim3(cdiv(M0, 256)), dim3(256), I.yinvpow.as<scm>(), uch_m, (uint32_t)first, (uint32_t)n, M0, to_scm(Gamma), to_scm(Eta),
                        I.tt_f.as<scm>(), I.tt_f.as<scm>() + M0, I.tt_c.as<scm>());
         }
@@ -1713,7 +1663,7 @@ void Engine::Impl::inner_product(Transcript &T, std::vector<uint8_t> &proof, uin
             I.scratch_ext.ensure((size_t)2 * Mr * sizeof(ge_ext));         // the folded points before their normalisation (2^18 of them after the first group of three rounds at 2^20)
             // the group-start tables are the original generators: width-w NAF against their precomputed odd multiples (k_fold_points_wnaf) -
             // unless no table fits the budget of this device, in which case the other kernels fold them
-            const FoldShape shape{Mr, nterms, g_first, Gst == Gtab && Hst == Htab && Gtab == I.gens.as<ge_niels>()};
+            const FoldShape shape{Mr, nterms, g_first, Gst == Gtab && Hst == Htab && Gtab == I.gens};
             const FoldKnobs knobs = I.fold_knobs();
             const FoldKernel kernel = choose_fold(shape, knobs, fold_wants_tables(shape, knobs) && I.odd_ensure());
             static const int kid_of[] = {KID_k_fold_points_wnaf, KID_k_fold_points_quadw, KID_k_fold_points_quad, KID_k_fold_points_split, KID_k_fold_points_regw,
@@ -1744,7 +1694,7 @@ void Engine::Impl::inner_product(Transcript &T, std::vector<uint8_t> &proof, uin
             double device_bytes = 96.0 * 2 * g_M + 128.0 * 2 * Mr;          // 2*g_M points read at 96 B, 2*Mr written at 128 B
             switch (kernel) {
             case FoldKernel::Wnaf:
-                BPG_LAUNCH(I, k_fold_points_wnaf, grid, block, I.gens.as<ge_niels>(), I.gens_odd.as<ge_niels>(), fo, nf, fw);
+                BPG_LAUNCH(I, k_fold_points_wnaf, grid, block, I.gens, I.gens_odd, fo, nf, fw);
                 device_bytes = 96.0 * (2.0 * Mr + rc.adds_fm / 7.0) + 128.0 * 2 * Mr;       // one point read per output and per addition
                 break;
             case FoldKernel::QuadW: BPG_LAUNCH(I, k_fold_points_quadw, grid64, block, Gst, Hst, fo, nf, reinterpret_cast<fe *>(I.arena_at(0)), fq); break;
@@ -1816,11 +1766,11 @@ void Engine::blinding_begin(const Transcript &after_commitments, const std::vect
     b->slot = slot;
     if (I.slab_owner[slot]) { I.blind_retire(I.slab_owner[slot]); I.slab_owner[slot].reset(); }
     Impl::SlabDev &sd = *I.slab_dev[slot];
-    if (!sd.copy_st) HIPCHK(hipStreamCreateWithFlags(&sd.copy_st, hipStreamNonBlocking));
+    if (!sd.copy_st) sd.copy_st = Stream::non_blocking();
     HIPCHK(hipStreamSynchronize(sd.copy_st));                  // no copy of the previous owner still reads the slab
     I.h_blind[slot].ensure(b->max_draws * 64);
     sd.d.ensure(b->max_draws * 64);
-    while (sd.ev.size() < b->max_draws / BS::UP + 1) { hipEvent_t e; HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); sd.ev.push_back(e); }
+    while (sd.ev.size() < b->max_draws / BS::UP + 1) sd.ev.push_back(Event::untimed());
     // The device slab changes owner here.  Two things keep this proof from reading the previous owner's draws: BlindStream::err - an upload that
     // fails is recorded BEFORE its block is published and prove() refuses the stream - and a canary against a copy that is dropped WITHOUT an error:
     // the first draw of every block is overwritten with a pattern here (1 KB of stores for a 2^20 proof, on the copy stream, ahead of the uploads),
@@ -1832,13 +1782,13 @@ void Engine::blinding_begin(const Transcript &after_commitments, const std::vect
         HIPCHK(hipGetLastError());
     }
     b->raw = I.h_blind[slot].as<uint8_t>();
-    b->device = device_; b->copy_st = sd.copy_st; b->d_raw = sd.d.as<uint8_t>(); b->ev = &sd.ev;
+    b->device = device_; b->copy_st = (hipStream_t)sd.copy_st; b->d_raw = sd.d.as<uint8_t>(); b->ev = &sd.ev;
     // how a drawn block reaches the device (called on the chain thread; host/chain.hpp publishes the block afterwards): an asynchronous copy on the
     // slab's own copy stream, then the block's event; the threads of a pool serve contexts of different devices, hence the hipSetDevice
     b->upload = [](BlindStream &bs, uint64_t from, uint64_t to, uint64_t k) -> int {
         hipError_t e = hipSetDevice(bs.device);
         if (e == hipSuccess && bs.inject_fail != 2) e = hipMemcpyAsync(bs.d_raw + 64 * from, bs.raw + 64 * from, (to - from) * 64, hipMemcpyHostToDevice, static_cast<hipStream_t>(bs.copy_st));
-        if (e == hipSuccess) e = hipEventRecord((*static_cast<std::vector<hipEvent_t> *>(bs.ev))[k], static_cast<hipStream_t>(bs.copy_st));
+        if (e == hipSuccess) e = hipEventRecord(Impl::block_event(bs, k), static_cast<hipStream_t>(bs.copy_st));
         return (int)e;
     };
     b->snaps.assign(b->max_draws / BS::SNAP + 1, rng);
@@ -1903,7 +1853,7 @@ std::vector<uint8_t> Engine::prove(DeviceCircuit *c, Transcript &T, const std::v
     double t0 = t_begin;
     auto lap = [&](double *slot) { if (tm) { I.wait_stream(); double t1 = now_ms(); *slot += t1 - t0; t0 = t1; } };
 
-    const ge_niels *Gtab = I.gens.as<ge_niels>(), *Htab = I.gens.as<ge_niels>() + gens_cap_;
+    const ge_niels *Gtab = I.gens, *Htab = I.gens + gens_cap_;
     const ge_niels *Bn = I.bases.as<ge_niels>(), *Bbn = Bn + 1;
 
     // ---- transcript, RNG, first blindings
@@ -2014,7 +1964,7 @@ std::vector<uint8_t> Engine::prove(DeviceCircuit *c, Transcript &T, const std::v
             }
             upload_failed();
             if (bs->uploaded_blocks.load(std::memory_order_acquire) < nblk) throw DeviceError("the blinding stream ended before its draws were uploaded");
-            for (uint64_t k = 0; k < nblk; k++) HIPCHK(hipStreamWaitEvent(st, (*static_cast<std::vector<hipEvent_t> *>(bs->ev))[k], 0));
+            for (uint64_t k = 0; k < nblk; k++) HIPCHK(hipStreamWaitEvent(st, Impl::block_event(*bs, k), 0));
             BPG_LAUNCH(I, k_sc_from_wide, dim3(cdiv(2 * n, 256)), dim3(256), reinterpret_cast<const uint32_t *>(bs->d_raw), sL, (uint32_t)(2 * n), I.stale_flag.as<uint32_t>());
         } else
         {
@@ -2035,7 +1985,7 @@ std::vector<uint8_t> Engine::prove(DeviceCircuit *c, Transcript &T, const std::v
                 const uint64_t k = i / Impl::BlindStream::UP;
                 while (bs->uploaded_blocks.load(std::memory_order_acquire) <= k) std::this_thread::sleep_for(std::chrono::microseconds(40));
                 upload_failed();
-                HIPCHK(hipStreamWaitEvent(st, (*static_cast<std::vector<hipEvent_t> *>(bs->ev))[k], 0));
+                HIPCHK(hipStreamWaitEvent(st, Impl::block_event(*bs, k), 0));
             } else {
                 rng.fill_draws64(raw + 64 * i, cnt);
                 HIPCHK(hipMemcpyAsync(I.raw_rng.as<uint8_t>() + 64 * i, raw + 64 * i, cnt * 64, hipMemcpyHostToDevice, st));
@@ -2363,7 +2313,7 @@ struct Wave {
                 for (uint64_t j = 0; j < m; j++) (*W[k]->vb)[j].to_bytes(pin + L.o_vbl + 32 * (L.vbase[k] + j));     // reduced, as pedersen_commit uploads them
             }
         });
-        if (!I.commit_ev) HIPCHK(hipEventCreateWithFlags(&I.commit_ev, hipEventDisableTiming));
+        if (!I.commit_ev) I.commit_ev = Event::untimed();
         HIPCHK(hipMemcpyAsync(dev + L.o_wit, pin + L.o_wit, L.o_coef - L.o_wit, hipMemcpyHostToDevice, I.st));
         reduce_values();
         BPG_LAUNCH(I, k_bt_commit_v, dim3(cdiv(L.mT, 4 * I.commit_cpw)), dim3(256), D<const scm>(L.d_v), D<const uint32_t>(L.o_vbl),
@@ -2575,7 +2525,7 @@ void Engine::prove_batch(size_t count, ProveItem *items, DeviceCircuit *tmpl, bo
     require_gens_capacity(gens_cap_, 1ull << lgmax);
     // ONE set of window tables of the original generators, for the largest N of the batch (an item of smaller N reads the first N rows of each half)
     const uint32_t M0T = 1u << lgmax;
-    I.tt_build(I.gens.as<ge_niels>(), I.gens.as<ge_niels>() + gens_cap_, I.bases.as<ge_niels>(), M0T, true);
+    I.tt_build(I.gens, I.gens + gens_cap_, I.bases.as<ge_niels>(), M0T, true);
     const BatchTables B{I.tt_table_p, I.ped_table.as<ge_pniels>(), I.ped_table.as<ge_pniels>() + (size_t)TT_WINDOWS * TT_MULTS, M0T, I.shared_now ? 0u : 1u};
     StageThreads pool(std::min<uint32_t>(batch_host_threads(), (uint32_t)std::max<size_t>(1, count / 8)));
     for (const std::vector<ProveItem *> &W : plan_waves(count, items, (uint64_t)I.batch_wave_mb << 20)) {
@@ -2655,8 +2605,8 @@ VerifyVecs verify_prep(Engine::Impl &I, const DeviceCircuit *c, const VerifyRepl
 // behind them; true iff the sum is the identity.  Synchronises the stream
 bool verify_msm(Engine::Impl &I, uint64_t N, uint32_t npts) {
     MsmJob J = job_new();
-    seg_push(J, I.lv.as<scm>(), I.gens.as<ge_niels>(), (uint32_t)N, 0);
-    seg_push(J, I.rv.as<scm>(), I.gens.as<ge_niels>() + I.gens_cap, (uint32_t)N, 0);
+    seg_push(J, I.lv.as<scm>(), I.gens, (uint32_t)N, 0);
+    seg_push(J, I.rv.as<scm>(), I.gens + I.gens_cap, (uint32_t)N, 0);
     seg_push(J, I.vfy_sc.as<scm>(), I.vfy_pts.as<ge_niels>(), npts, 0);
     seg_push(J, I.vfy_sc.as<scm>() + npts, I.bases.as<ge_niels>(), 2, 0);
     const Engine::Impl::MsmTicket tk = I.msm(J, 1);
@@ -2940,7 +2890,7 @@ DeviceMerkle *Engine::merkle_build(uint32_t depth, const uint8_t *leaves) {
         note_nodes(I, KID_k_merkle_top, (2ull << level) - 1);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(I.st));
-    } catch (...) { (void)hipStreamSynchronize(I.st); t->tree.release(); throw; }
+    } catch (...) { (void)hipStreamSynchronize(I.st); throw; }         // (the tree goes with `t`, after this wait)
     I.trees.push_back(t.get());
     return t.release();
 }

@@ -20,6 +20,10 @@ struct ProveTimings {       // milliseconds, host wall clock around each phase (
     uint32_t shared_variants = 0;   // 1: this proof took the shared-device kernel variants (decided once, when prove() was entered)
 };
 
+// What the process holds from the HIP runtime at this moment, all contexts and all devices together (include/bpg.h bpg_test_live_resources; counted in
+// hip_handles.hpp): device buffers, their bytes, pinned buffers, their bytes, streams, events.  Reads six counters: no device work.
+void live_resources(uint64_t out[6]);
+
 struct DeviceCircuit;       // HBM-resident flattened R1CS instance
 struct DeviceMerkle;        // HBM-resident MiMC Merkle tree
 

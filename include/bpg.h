@@ -416,6 +416,9 @@ bpg_status bpg_test_fail_next_upload(bpg_ctx *ctx);
 /* test hook: the copies of the next blinding stream started on ctx are skipped WITHOUT an error (a dropped DMA): the device slab keeps the pattern its
  * blocks were marked with when the slab changed owner, the conversion kernel notices, and the prove that adopts the stream fails with BPG_ERR_DEVICE */
 bpg_status bpg_test_drop_next_upload(bpg_ctx *ctx);
+/* test hook: what the whole process holds from the HIP runtime at this moment, every context and device together - out = device buffers, their bytes, pinned
+ * buffers, their bytes, streams, events.  No context and no device work: six counters are read.  All zero once every context, circuit and tree is freed. */
+bpg_status bpg_test_live_resources(uint64_t out[6]);
 /* diagnostics: bytes of precomputed generator multiples (fold tables + wide tail tables) this process holds on the context's device */
 uint64_t bpg_table_bytes(bpg_ctx *ctx);
 /* diagnostics: 1 when the last bpg_r1cs_prove* / bpg_prover_prove on ctx took the kernel variants for a shared device (another prove() was in flight on the
