@@ -25,13 +25,15 @@ VAR_MULTIPLIER_LEFT, VAR_MULTIPLIER_RIGHT, VAR_MULTIPLIER_OUTPUT, VAR_COMMITTED,
 L = 2**252 + 27742317777372353535851937790883648493
 
 STATUS_NAMES = {0: "OK", 1: "INVALID_GENERATORS_LENGTH", 2: "FORMAT_ERROR", 3: "VERIFICATION_ERROR", 4: "INVALID_ARGUMENT",
-                5: "MISSING_ASSIGNMENT", 6: "GADGET_ERROR", 7: "DEVICE_ERROR", 8: "INTERNAL"}
+                5: "MISSING_ASSIGNMENT", 6: "GADGET_ERROR", 7: "DEVICE_ERROR", 8: "INTERNAL", 9: "CHECKPOINT_MISMATCH"}
+ERR_CHECKPOINT_MISMATCH = 9
 
 
 class BpgError(RuntimeError):
     def __init__(self, status, message):
         super().__init__("%s: %s" % (STATUS_NAMES.get(status, status), message))
         self.status = status
+        self.first_mismatch = None      # CHECKPOINT_MISMATCH (ResidentCircuit.assign): the lowest flat index item * n_ck + k whose value was wrong
 
 
 class R1CSInstance(C.Structure):
@@ -48,6 +50,20 @@ class WitnessProgramView(C.Structure):
 class WitnessHintsView(C.Structure):
     """bpg_witness_hints (frozen)."""
     _fields_ = [("n_hints", C.c_uint64), ("hint_mul", C.c_void_p), ("hint_kind", C.c_void_p), ("hint_arg", C.c_void_p)]
+
+
+class WitnessCheckpointsView(C.Structure):
+    """bpg_witness_checkpoints (frozen)."""
+    _fields_ = [("n_checkpoints", C.c_uint64), ("vars", C.c_void_p)]
+
+
+def _checkpoints_cstruct(checkpoints):
+    import numpy as np
+    arr = np.ascontiguousarray([int(x) for x in checkpoints], dtype=np.uint32)
+    c = WitnessCheckpointsView()
+    c.n_checkpoints, c.vars = len(arr), arr.ctypes.data if len(arr) else None
+    c._owner = arr
+    return c
 
 
 HINT_BIT_PAIR = 1
@@ -224,6 +240,17 @@ def mimc_sponge(blocks):
     out = _buf(32)
     _chk(lib().bpg_mimc_sponge(data, C.c_uint64(len(data) // 32), out))
     return out.raw
+
+
+def mimc_sponge_states(blocks):
+    """bpg_mimc_sponge_states: mimc_sponge on the host, returning the state after EVERY absorbed block (the last one is the digest) - the checkpoint
+    values of a preimage template (Prover.noted)."""
+    data = bytes(blocks) if isinstance(blocks, (bytes, bytearray)) else b"".join(_exact("block", b, 32) for b in blocks)
+    if len(data) % 32:
+        raise ValueError("blocks must be a whole number of 32-byte values")
+    out = _buf(len(data))
+    _chk(lib().bpg_mimc_sponge_states(data, C.c_uint64(len(data) // 32), out))
+    return [out.raw[32 * i:32 * i + 32] for i in range(len(data) // 32)]
 
 
 def scalar_op(op, a, b=None):
@@ -452,11 +479,18 @@ class Context:
         finally:
             rc.free()
 
-    def upload_template(self, inst: "FlatInstance", program: "WitnessProgram", hints: "WitnessHints" = None):
+    def upload_template(self, inst: "FlatInstance", program: "WitnessProgram", hints: "WitnessHints" = None, checkpoints=None):
         """bpg_r1cs_upload_template: the instance (with or without a witness) plus its witness program; ResidentCircuit.assign gives it fresh witnesses.
-        hints (a circuit with range proofs, Prover.witness_program(hints=True)): bpg_r1cs_upload_template_hinted."""
+        hints (a circuit with range proofs, Prover.witness_program(hints=True)): bpg_r1cs_upload_template_hinted.
+        checkpoints (bpg_r1cs_upload_template_checkpointed): multiplier Variables whose values the caller hands to assign(..., checkpoints=values); the
+        segments that read them stop waiting for the ones that compute them."""
         h = C.c_void_p()
         cs, cp = inst.cstruct(), program.cstruct()
+        if checkpoints is not None and len(checkpoints):
+            ch = hints.cstruct() if hints is not None and len(hints) else None
+            ck = _checkpoints_cstruct(checkpoints)
+            _chk(lib().bpg_r1cs_upload_template_checkpointed(self._h, C.byref(cs), C.byref(cp), C.byref(ch) if ch is not None else None, C.byref(ck), C.byref(h)))
+            return ResidentCircuit(self, h, inst.n, inst.m, n_params=len(program.param_rows), q=inst.q, n_ck=len(checkpoints))
         if hints is not None and len(hints):
             ch = hints.cstruct()
             _chk(lib().bpg_r1cs_upload_template_hinted(self._h, C.byref(cs), C.byref(cp), C.byref(ch), C.byref(h)))
@@ -536,6 +570,15 @@ class MerkleTree:
         k, d = len(indices), self.depth
         out = _buf(32 * d * k)
         _chk(lib().bpg_merkle_paths(self.ctx._h, self._handle(), C.c_uint64(k), (C.c_uint64 * max(k, 1))(*indices), out))
+        raw = out.raw
+        return [[raw[32 * (i * d + j):32 * (i * d + j) + 32] for j in range(d)] for i in range(k)]
+
+    def path_nodes(self, indices):
+        """bpg_merkle_path_nodes: for every leaf index the `depth` nodes ON its path, from the leaf's parent upward, the root last - the checkpoint values of
+        a path template (workloads.merkle_path_pattern), where paths() gives its committed values."""
+        k, d = len(indices), self.depth
+        out = _buf(32 * d * k)
+        _chk(lib().bpg_merkle_path_nodes(self.ctx._h, self._handle(), C.c_uint64(k), (C.c_uint64 * max(k, 1))(*indices), out))
         raw = out.raw
         return [[raw[32 * (i * d + j):32 * (i * d + j) + 32] for j in range(d)] for i in range(k)]
 
@@ -792,18 +835,35 @@ class _TemplateCommitItem(C.Structure):
 
 
 class ResidentCircuit:
-    def __init__(self, ctx, h, n, m, n_params=None, q=None):
+    def __init__(self, ctx, h, n, m, n_params=None, q=None, n_ck=0):
         self.ctx, self._h, self.n, self.m = ctx, h, n, m
+        self.n_ck = n_ck                    # checkpoint values assign() takes (a template uploaded with checkpoints; a repeat of one: count x as many)
         self.n_params = n_params            # None: a plain upload; a number: a circuit template (Prover.template / Context.upload_template)
         self.q = q                          # constraint rows (None: made by a caller that did not say)
 
-    def assign(self, values, params=()):
+    def assign(self, values, params=(), checkpoints=None):
         """bpg_r1cs_assign: a fresh witness for a circuit template - the m committed values (and the constant term of every parameter row); the device
-        computes a_L, a_R, a_O.  The caller commits to the same values and proves with prove()."""
+        computes a_L, a_R, a_O.  The caller commits to the same values and proves with prove().
+        checkpoints (bpg_r1cs_assign_checkpointed, a template uploaded with checkpoints): their values, in the order they were named (a repeat: item-major).
+        A value that is not what the circuit computes raises BpgError(CHECKPOINT_MISMATCH) whose .first_mismatch is the lowest such flat index; the circuit
+        then holds no witness."""
         v = _scalars32("values", values, self.m)
         pv = bytes(params) if isinstance(params, (bytes, bytearray)) else b"".join(_exact("params", x, 32) for x in params)
         if len(pv) % 32:
             raise ValueError("params must be a multiple of 32 bytes")
+        if checkpoints is not None:
+            ck = bytes(checkpoints) if isinstance(checkpoints, (bytes, bytearray)) else b"".join(_exact("checkpoints", x, 32) for x in checkpoints)
+            if len(ck) % 32:
+                raise ValueError("checkpoints must be a multiple of 32 bytes")
+            first = C.c_uint64()
+            st = lib().bpg_r1cs_assign_checkpointed(self.ctx._h, self._h, C.c_uint64(self.m), v if self.m else None, C.c_uint64(len(pv) // 32), pv if pv else None,
+                                                    C.c_uint64(len(ck) // 32), ck if ck else None, C.byref(first))
+            if st != 0:
+                e = BpgError(st, lib().bpg_last_error().decode())
+                if st == ERR_CHECKPOINT_MISMATCH:
+                    e.first_mismatch = int(first.value)
+                raise e
+            return
         _chk(lib().bpg_r1cs_assign(self.ctx._h, self._h, C.c_uint64(self.m), v if self.m else None, C.c_uint64(len(pv) // 32), pv if pv else None))
 
     def repeat(self, count) -> "ResidentCircuit":
@@ -812,7 +872,8 @@ class ResidentCircuit:
         count x m values and count x n_params constants, item-major; one prove() gives one proof for all the items.  Independent of this template."""
         h = C.c_void_p()
         _chk(lib().bpg_r1cs_template_repeat(self.ctx._h, self._h, C.c_uint64(count), C.byref(h)))
-        return ResidentCircuit(self.ctx, h, count * self.n, count * self.m, n_params=count * self.n_params, q=None if self.q is None else count * self.q)
+        return ResidentCircuit(self.ctx, h, count * self.n, count * self.m, n_params=count * self.n_params, q=None if self.q is None else count * self.q,
+                               n_ck=count * self.n_ck)
 
     def check(self, values=None, max_rows=16) -> "CheckReport":
         """bpg_r1cs_check: which multipliers (a_L * a_R against a_O) and which constraint rows does the resident witness break - evaluated on the device, the
@@ -1147,18 +1208,31 @@ class Prover:
         _chk(lib().bpg_prover_allocate_bit(self._h, C.byref(lc), C.c_uint32(bit), _exact("source_value", source_value, 32), out))
         return Variable(out[0]), Variable(out[1]), Variable(out[2])
 
+    NOTE_LAST_BLOCK = 1 << 31
+
+    def noted(self):
+        """bpg_prover_noted: the checkpoint candidates the gadgets pointed out, in the order they were made -> [(Variable, block, is_last)].  MimcHash256 (and
+        MerkleTree256 through it) notes the sponge state after every absorbed block; is_last marks a sponge's digest (a Merkle node)."""
+        n = C.c_uint64()
+        _chk(lib().bpg_prover_noted(self._h, None, None, C.c_uint64(0), C.byref(n)))
+        k = n.value
+        vs, ts = (C.c_uint32 * max(k, 1))(), (C.c_uint32 * max(k, 1))()
+        _chk(lib().bpg_prover_noted(self._h, vs, ts, C.c_uint64(k), C.byref(n)))
+        return [(Variable(vs[i]), ts[i] & (self.NOTE_LAST_BLOCK - 1), bool(ts[i] & self.NOTE_LAST_BLOCK)) for i in range(k)]
+
     def mark_param_row(self, row: int):
         """bpg_prover_mark_param_row: the constant term of constraint `row` changes with the witness (num_constraints() - 1 right after the constrain call)."""
         _chk(lib().bpg_prover_mark_param_row(self._h, C.c_uint64(row)))
 
-    def template(self, ctx: "Context", param_rows=()) -> "ResidentCircuit":
+    def template(self, ctx: "Context", param_rows=(), checkpoints=()) -> "ResidentCircuit":
         """This circuit as a template resident on `ctx` (with this prover's witness): ResidentCircuit.assign(values, params) then gives it the witness of
-        further proofs of the same shape without another host assembly.  param_rows: rows whose constant term is assigned per witness, besides the marked ones."""
+        further proofs of the same shape without another host assembly.  param_rows: rows whose constant term is assigned per witness, besides the marked ones.
+        checkpoints: multiplier Variables (noted() lists candidates) whose values assign(..., checkpoints=) takes from the caller."""
         prog, hints = self.witness_program(hints=True)
         prog.param_rows = prog.param_rows + [int(r) for r in param_rows]
         if ctx is None:
             raise BpgError(4, "template: no device context")
-        return ctx.upload_template(self.instance(), prog, hints)
+        return ctx.upload_template(self.instance(), prog, hints, checkpoints=list(checkpoints))
 
     def start_blinding(self, rng_seed: bytes = None, max_multipliers: int = 1 << 20):
         """Extension (include/bpg.h bpg_prover_start_blinding): all commitments made - start the serial TranscriptRng chain of the coming

@@ -111,7 +111,7 @@ void Prover::start_blinding(const uint8_t rng_seed[32], uint64_t max_multipliers
 // ---------------------------------------------------------------------------------------- handles
 struct bpg_ctx { Engine *engine; };
 struct bpg_merkle { DeviceMerkle *t; };
-struct bpg_circuit { DeviceCircuit *dc; uint64_t n, m; bool is_template = false; uint64_t n_params = 0; };     // dc == nullptr: bpg_test_circuit_handle
+struct bpg_circuit { DeviceCircuit *dc; uint64_t n, m; bool is_template = false; uint64_t n_params = 0; uint64_t n_ck = 0; };     // dc == nullptr: bpg_test_circuit_handle
 struct bpg_transcript { Transcript t; };
 struct bpg_prover { Prover *p; FlatCircuit flat; std::vector<uint8_t> v_bytes, vb_bytes; WitnessProgram program; };
 struct bpg_verifier { Verifier *v; FlatCircuit flat; };
@@ -167,6 +167,7 @@ const char *bpg_strerror(bpg_status s) {
     case BPG_ERR_MISSING_ASSIGNMENT: return "missing assignment";
     case BPG_ERR_GADGET: return "gadget error";
     case BPG_ERR_DEVICE: return "device error";
+    case BPG_ERR_CHECKPOINT_MISMATCH: return "checkpoint mismatch";
     default: return "internal error";
     }
 }
@@ -273,10 +274,11 @@ void bpg_r1cs_free(bpg_ctx *ctx, bpg_circuit *c) {
     delete c;
 }
 
-static WitnessProgramView program_view(const bpg_witness_program *w, const bpg_witness_hints *h = nullptr) {
+static WitnessProgramView program_view(const bpg_witness_program *w, const bpg_witness_hints *h = nullptr, const bpg_witness_checkpoints *k = nullptr) {
     REQUIRE(w);
     WitnessProgramView v; v.lc_ptr = w->lc_ptr; v.term_var = w->term_var; v.term_coef = w->term_coef; v.n_params = w->n_params; v.param_rows = w->param_rows;
     if (h) { v.n_hints = h->n_hints; v.hint_mul = h->hint_mul; v.hint_kind = h->hint_kind; v.hint_arg = h->hint_arg; }
+    if (k) { v.n_ck = k->n_checkpoints; v.ck_var = k->vars; }
     return v;
 }
 bpg_status bpg_r1cs_upload_template(bpg_ctx *ctx, const bpg_r1cs_instance *inst, const bpg_witness_program *program, bpg_circuit **out) {
@@ -284,37 +286,87 @@ bpg_status bpg_r1cs_upload_template(bpg_ctx *ctx, const bpg_r1cs_instance *inst,
 }
 bpg_status bpg_r1cs_upload_template_hinted(bpg_ctx *ctx, const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
                                            bpg_circuit **out) {
+    return bpg_r1cs_upload_template_checkpointed(ctx, inst, program, hints, nullptr, out);
+}
+bpg_status bpg_r1cs_upload_template_checkpointed(bpg_ctx *ctx, const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                                 const bpg_witness_checkpoints *checkpoints, bpg_circuit **out) {
     return guard([&] {
         REQUIRE(out); *out = nullptr;
         REQUIRE(ctx && inst && program);
         const FlatView f = as_view(inst, false);
-        const WitnessProgramView w = program_view(program, hints);
+        const WitnessProgramView w = program_view(program, hints, checkpoints);
         const TemplatePlan plan = Engine::plan_template(f, w);      // every check, the level cap included, before the context is touched
         DeviceCircuit *dc = ctx->engine->upload_template(f, plan);
-        bpg_circuit *c = new bpg_circuit{dc, f.n, f.m}; c->is_template = true; c->n_params = w.n_params;
+        bpg_circuit *c = new bpg_circuit{dc, f.n, f.m}; c->is_template = true; c->n_params = w.n_params; c->n_ck = w.n_ck;
         *out = c;
     });
 }
+// the argument checks the two assign calls share
+static void assign_checks(bpg_ctx *ctx, bpg_circuit *c, uint64_t m, const uint8_t *v, uint64_t n_params, const uint8_t *param_values) {
+    REQUIRE(ctx && c);
+    if (!c->is_template) throw std::invalid_argument("assign: the circuit is not a template (bpg_r1cs_upload_template)");
+    if (m != c->m) throw std::invalid_argument("assign: m does not match the template");
+    if (n_params != c->n_params) throw std::invalid_argument("assign: n_params does not match the template");
+    REQUIRE((m == 0 || v) && (n_params == 0 || param_values));
+}
 bpg_status bpg_r1cs_assign(bpg_ctx *ctx, bpg_circuit *c, uint64_t m, const uint8_t *v, uint64_t n_params, const uint8_t *param_values) {
     return guard([&] {
-        REQUIRE(ctx && c);
-        if (!c->is_template) throw std::invalid_argument("assign: the circuit is not a template (bpg_r1cs_upload_template)");
-        if (m != c->m) throw std::invalid_argument("assign: m does not match the template");
-        if (n_params != c->n_params) throw std::invalid_argument("assign: n_params does not match the template");
-        REQUIRE((m == 0 || v) && (n_params == 0 || param_values));
+        assign_checks(ctx, c, m, v, n_params, param_values);
+        if (c->n_ck) throw std::invalid_argument("assign: the template was uploaded with checkpoints and needs their values (bpg_r1cs_assign_checkpointed)");
         if (!c->dc) throw std::invalid_argument("assign: the handle has no device state (bpg_test_circuit_handle)");
         ctx->engine->assign(c->dc, v, param_values);
     });
+}
+bpg_status bpg_r1cs_assign_checkpointed(bpg_ctx *ctx, bpg_circuit *c, uint64_t m, const uint8_t *v, uint64_t n_params, const uint8_t *param_values,
+                                        uint64_t n_ck, const uint8_t *ck_values, uint64_t *first_mismatch) {
+    if (first_mismatch) *first_mismatch = UINT64_MAX;
+    uint64_t first = Engine::CHECKPOINTS_HOLD;
+    const bpg_status st = guard([&] {
+        assign_checks(ctx, c, m, v, n_params, param_values);
+        if (n_ck != c->n_ck) throw std::invalid_argument("assign: n_ck does not match the template (" + std::to_string(c->n_ck) + " checkpoint values)");
+        REQUIRE(n_ck == 0 || ck_values);
+        if (!c->dc) throw std::invalid_argument("assign: the handle has no device state (bpg_test_circuit_handle)");
+        first = ctx->engine->assign_checkpointed(c->dc, v, param_values, ck_values);
+    });
+    if (st != BPG_OK || first == Engine::CHECKPOINTS_HOLD) return st;
+    if (first_mismatch) *first_mismatch = first;
+    const uint64_t per = Engine::checkpoints_per_item(c->dc);
+    g_last_error = "assign: checkpoint " + std::to_string(first % per) + (per != c->n_ck ? " of item " + std::to_string(first / per) : std::string()) +
+                   " (flat index " + std::to_string(first) + ") is not the value the circuit computes; the circuit holds no witness";
+    return BPG_ERR_CHECKPOINT_MISMATCH;
 }
 bpg_status bpg_test_template_schedule(const bpg_r1cs_instance *inst, const bpg_witness_program *program, char *out, uint64_t cap) {
     return bpg_test_template_schedule_hinted(inst, program, nullptr, out, cap);
 }
 bpg_status bpg_test_template_schedule_hinted(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, char *out, uint64_t cap) {
+    return bpg_test_template_schedule_checkpointed(inst, program, hints, nullptr, out, cap);
+}
+bpg_status bpg_test_template_schedule_checkpointed(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                                   const bpg_witness_checkpoints *checkpoints, char *out, uint64_t cap) {
     return guard([&] {
         REQUIRE(inst && program && out && cap);
-        const std::string r = witness_schedule_json(Engine::plan_template(as_view(inst, false), program_view(program, hints)).schedule);
+        const std::string r = witness_schedule_json(Engine::plan_template(as_view(inst, false), program_view(program, hints, checkpoints)).schedule);
         if (r.size() + 1 > cap) throw std::invalid_argument("template_schedule: buffer too small (" + std::to_string(r.size() + 1) + " bytes needed)");
         std::memcpy(out, r.c_str(), r.size() + 1);
+    });
+}
+bpg_status bpg_test_template_eval_checkpointed(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                               const bpg_witness_checkpoints *checkpoints, const uint8_t *v, const uint8_t *ck_values,
+                                               uint8_t *aL, uint8_t *aR, uint8_t *aO, uint64_t *first_mismatch) {
+    return guard([&] {
+        REQUIRE(inst && program && aL && aR && aO && first_mismatch && (inst->m == 0 || v));
+        REQUIRE(!checkpoints || checkpoints->n_checkpoints == 0 || ck_values);
+        *first_mismatch = Engine::template_eval_checkpointed_host(as_view(inst, false), program_view(program, hints, checkpoints), v, ck_values, aL, aR, aO);
+    });
+}
+bpg_status bpg_test_template_packed(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                    const bpg_witness_checkpoints *checkpoints, uint32_t *stream_out, uint64_t cap, uint64_t *words_out) {
+    return guard([&] {
+        REQUIRE(inst && program && words_out && (cap == 0 || stream_out));
+        const TemplatePlan T = Engine::plan_template(as_view(inst, false), program_view(program, hints, checkpoints));
+        *words_out = T.packed.stream.size();
+        if (cap < T.packed.stream.size()) { if (cap) throw std::invalid_argument("template_packed: buffer too small (" + std::to_string(T.packed.stream.size()) + " words needed)"); return; }
+        std::memcpy(stream_out, T.packed.stream.data(), T.packed.stream.size() * 4);
     });
 }
 bpg_status bpg_test_template_eval(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const uint8_t *v, uint8_t *aL, uint8_t *aR, uint8_t *aO) {
@@ -358,7 +410,7 @@ bpg_status bpg_r1cs_template_repeat(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t co
         if (!tmpl->is_template) throw std::invalid_argument("template_repeat: the circuit is not a template (bpg_r1cs_upload_template)");
         if (!tmpl->dc) throw std::invalid_argument("template_repeat: the handle has no device state (bpg_test_circuit_handle)");
         DeviceCircuit *dc = ctx->engine->repeat_template(tmpl->dc, count);          // count 0, a repeat, sizes: refused there, before any device work
-        bpg_circuit *c = new bpg_circuit{dc, count * tmpl->n, count * tmpl->m}; c->is_template = true; c->n_params = count * tmpl->n_params;
+        bpg_circuit *c = new bpg_circuit{dc, count * tmpl->n, count * tmpl->m}; c->is_template = true; c->n_params = count * tmpl->n_params; c->n_ck = count * tmpl->n_ck;
         *out = c;
     });
 }
@@ -514,6 +566,7 @@ static bpg_status template_batch_refusal(bpg_ctx *ctx, bpg_circuit *tmpl, uint64
     if (tmpl && !tmpl->dc) { g_last_error = "prove_template_batch: the handle has no device state (bpg_test_circuit_handle)"; return BPG_ERR_INVALID_ARGUMENT; }
     if (!ctx || !tmpl || (count && (!items || !status_out))) { g_last_error = "null or invalid argument: ctx, tmpl, items and status_out"; return BPG_ERR_INVALID_ARGUMENT; }
     if (!tmpl->is_template) { g_last_error = "prove_template_batch: the circuit is not a template (bpg_r1cs_upload_template)"; return BPG_ERR_INVALID_ARGUMENT; }
+    if (tmpl->n_ck) { g_last_error = "prove_template_batch: the template has checkpoints, and a batch item carries no values for them (bpg_r1cs_assign_checkpointed + bpg_r1cs_prove_resident)"; return BPG_ERR_INVALID_ARGUMENT; }
     return BPG_OK;
 }
 // items that passed template_batch_refusal (none: BPG_OK, nothing touched).  coms == nullptr: bpg_r1cs_prove_template_batch.  Else bpg_r1cs_prove_template_batch_commit: the
@@ -847,6 +900,16 @@ bpg_status bpg_prover_witness_program_hinted(bpg_prover *p, bpg_witness_program 
         hints_out->hint_kind = p->program.hint_kind.data(); hints_out->hint_arg = p->program.hint_arg.data();
     });
 }
+bpg_status bpg_prover_noted(bpg_prover *p, uint32_t *vars_out, uint32_t *tags_out, uint64_t cap, uint64_t *n_out) {
+    return guard([&] {
+        REQUIRE(p && n_out);
+        const std::vector<uint32_t> &vars = p->p->noted_vars(), &tags = p->p->noted_tags();
+        *n_out = vars.size();
+        REQUIRE(cap == 0 || (vars_out && tags_out));
+        const uint64_t k = std::min<uint64_t>(cap, vars.size());
+        if (k) { std::memcpy(vars_out, vars.data(), k * 4); std::memcpy(tags_out, tags.data(), k * 4); }
+    });
+}
 bpg_status bpg_prover_allocate_bit(bpg_prover *p, const bpg_lc *source, uint32_t bit, const uint8_t source_value[32], uint32_t vars_out[3]) {
     return guard([&] { REQUIRE(p && source_value && bit < 256); put_vars(p->p->allocate_bit(lc_from(source), bit, OptScalar(Scalar::from_bits(source_value))), vars_out); });
 }
@@ -1040,6 +1103,18 @@ bpg_status bpg_mimc_sponge(const uint8_t *blocks, uint64_t n_blocks, uint8_t out
         mimc_sponge_1(pre, mimc_round_constants()).to_bytes(out);
     });
 }
+bpg_status bpg_mimc_sponge_states(const uint8_t *blocks, uint64_t n_blocks, uint8_t *out) {
+    return guard([&] {
+        REQUIRE(blocks && out && n_blocks > 0);
+        const std::vector<Scalar> &rc = mimc_round_constants();
+        Scalar state;
+        for (uint64_t i = 0; i < n_blocks; i++) {                 // mimc_sponge_1, keeping the state after every block
+            Scalar b; std::memcpy(b.w, blocks + 32 * i, 32);
+            state += b; state = mimc_encryption(state, Scalar::zero(), rc);
+            state.to_bytes(out + 32 * i);
+        }
+    });
+}
 // ---- MiMC Merkle trees on the device: the arguments that need no tree are checked here, the rest by the engine, all of it before the device is touched
 bpg_status bpg_mimc_sponge_many(bpg_ctx *ctx, uint64_t count, uint64_t blocks_per_item, const uint8_t *in, uint8_t *out) {
     return guard([&] { REQUIRE(count > 0 && blocks_per_item > 0 && blocks_per_item <= (1ull << 22) && in && out && ctx); ctx->engine->mimc_sponge_many(count, blocks_per_item, in, out); });
@@ -1059,6 +1134,9 @@ bpg_status bpg_merkle_nodes(bpg_ctx *ctx, bpg_merkle *t, uint32_t level, uint64_
 }
 bpg_status bpg_merkle_paths(bpg_ctx *ctx, bpg_merkle *t, uint64_t count, const uint64_t *indices, uint8_t *siblings_out) {
     return guard([&] { REQUIRE(ctx && t && (count == 0 || (indices && siblings_out))); ctx->engine->merkle_paths(t->t, count, indices, siblings_out); });
+}
+bpg_status bpg_merkle_path_nodes(bpg_ctx *ctx, bpg_merkle *t, uint64_t count, const uint64_t *indices, uint8_t *out) {
+    return guard([&] { REQUIRE(ctx && t && (count == 0 || (indices && out))); ctx->engine->merkle_paths(t->t, count, indices, out, true); });
 }
 bpg_status bpg_merkle_update(bpg_ctx *ctx, bpg_merkle *t, uint64_t count, const uint64_t *indices, const uint8_t *leaves) {
     return guard([&] { REQUIRE(ctx && t && (count == 0 || (indices && leaves))); ctx->engine->merkle_update(t->t, count, indices, leaves); });

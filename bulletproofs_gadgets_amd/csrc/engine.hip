@@ -165,6 +165,9 @@ struct DeviceCircuit {
     // per-witness constant terms live in `coef` (slots [param_first, param_first + n_params))
     bool is_template = false;
     DevBuf wit_stream, wit_segs, wit_v;
+    // checkpoints (WitnessProgramView::ck_var): the variables, and the values of the last assign_checkpointed (a repeat: rep_count x n_ck of them)
+    uint64_t n_ck = 0;
+    DevBuf wit_ck_var, wit_ck;
     bool wit_v_set = false;                 // wit_v holds the values of an assign() (a template uploaded WITH its witness has a_L, a_R, a_O and no values yet)
     std::vector<uint32_t> wit_level_ptr;    // level l = segments [wit_level_ptr[l], wit_level_ptr[l + 1]) of wit_segs
     uint64_t n_params = 0, param_first = 0;
@@ -191,7 +194,7 @@ struct DeviceCircuit {
     X(k_scan_apply) X(k_bucket_chunks) X(k_bucket_combine) X(k_bucket_combine_heavy) X(k_bucket_reduce) X(k_window_sums) X(k_window_sums_quad) X(k_decompress) X(k_ipa_s) X(k_verify_scalars) X(k_verify_scalars_acc) X(k_bench_fe_mul) \
     X(k_tt_bases) X(k_tt_multiples) X(k_tt_bases8) X(k_tt_multiples8) X(k_tt_round8) X(k_tt_factors) X(k_tt_advance) X(k_tt_round) X(k_tt_finish) X(k_blind_expand) X(k_tt_commit3) X(k_tt_commit3_finish) X(k_csc_count) X(k_csc_fill) X(k_csc_colptr) X(k_merge_insert) X(k_merge_plan) X(k_merge_groups) X(k_merge_members) X(k_merge_sum) \
     X(k_bt_commit3) X(k_bt_commit3_finish) X(k_bt_compress) X(k_bt_exp) X(k_bt_poly_t) X(k_bt_poly_eval) X(k_bt_factors) X(k_bt_advance) X(k_bt_round) \
-    X(k_bt_finish) X(k_bt_fold_scalars) X(k_witness_eval) X(k_witness_eval_batch) X(k_bt_commit_v) X(k_repeat_colptr) X(k_repeat_entries) X(k_repeat_coef) X(k_witness_eval_repeat) \
+    X(k_bt_finish) X(k_bt_fold_scalars) X(k_witness_eval) X(k_witness_eval_batch) X(k_bt_commit_v) X(k_repeat_colptr) X(k_repeat_entries) X(k_repeat_coef) X(k_witness_eval_repeat) X(k_witness_ck_verify) \
     X(k_mimc_sponge) X(k_merkle_leaves) X(k_merkle_level) X(k_merkle_top) X(k_merkle_level_list) X(k_merkle_set_leaves) X(k_merkle_paths) X(k_merkle_export) \
     X(k_rowview_count) X(k_rowview_fill) X(k_rowview_long) X(k_check_mul) X(k_check_rows) X(k_check_rows_long) X(k_check_count)
 enum KernelId {
@@ -243,6 +246,7 @@ struct Engine::Impl {
     std::vector<DeviceMerkle *> trees;
     // check() (hip/k_check.cuh): the caller's committed values of a plain upload, the violation bitmap (a bit per row), the four counters of the report
     DevBuf chk_v, chk_bitmap, chk_report;
+    DevBuf ck_first;                            // assign_checkpointed: the lowest mismatching checkpoint (8 bytes)
     uint32_t check_threshold = CHECK_ROW_THRESHOLD;     // rows of more terms get a wave each (BPG_CHECK_THRESHOLD)
     void rowview_build(DeviceCircuit *c);
     // One arena for the large per-stream buffers whose lifetimes never overlap in stream order (round 5: 20 proving streams held 2.9 GB each):
@@ -1217,6 +1221,7 @@ TemplatePlan Engine::plan_template(const FlatView &c, const WitnessProgramView &
     T.packed = pack_witness_program(c, p, T.schedule, share);       // the classes come from the caller's table: slots are constants of rows only
     T.slotted = with_parameter_slots(c, p);
     T.n_params = p.n_params; T.param_first = c.ncoef;
+    T.ck_var.assign(p.ck_var, p.ck_var + p.n_ck);
     return T;
 }
 namespace {
@@ -1238,6 +1243,26 @@ void Engine::template_eval_host(const FlatView &c, const WitnessProgramView &p, 
     std::vector<scm> aL(c.n), aR(c.n), aO(c.n);
     for (const WitnessSegment &s : P.segs) witness_eval_segment(s.first, s.count, P.stream.data() + s.stream, coef.data(), vv.data(), aL.data(), aR.data(), aO.data());
     scalars_to_bytes(aL, aL_out); scalars_to_bytes(aR, aR_out); scalars_to_bytes(aO, aO_out);
+}
+
+// TEST HOOK (bpg_test_template_eval_checkpointed): poison, every level's segments in reverse order, then the step of k_witness_ck_verify
+uint64_t Engine::template_eval_checkpointed_host(const FlatView &c, const WitnessProgramView &p, const uint8_t *v, const uint8_t *ck_values,
+                                                 uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out) {
+    const TemplatePlan T = plan_template(c, p);
+    const PackedWitnessProgram &P = T.packed;
+    const std::vector<scm> coef = scalars_from_bytes(c.coef, c.ncoef), vv = scalars_from_bytes(v, c.m), ck = scalars_from_bytes(ck_values, p.n_ck);
+    static const uint8_t kPoison[32] = {0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a,
+                                        0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x0a};
+    const scm poison = scalars_from_bytes(kPoison, 1)[0];
+    std::vector<scm> aL(c.n, poison), aR(c.n, poison), aO(c.n, poison);
+    const std::vector<uint32_t> &lp = T.schedule.level_ptr;
+    for (size_t l = 0; l + 1 < lp.size(); l++)
+        for (uint32_t s = lp[l + 1]; s-- > lp[l];)
+            witness_eval_segment(P.segs[s].first, P.segs[s].count, P.stream.data() + P.segs[s].stream, coef.data(), vv.data(), aL.data(), aR.data(), aO.data(), ck.data());
+    uint64_t first = CHECKPOINTS_HOLD;
+    for (uint64_t k = p.n_ck; k-- > 0;) if (!witness_ck_holds(p.ck_var[k], ck[k], aL.data(), aR.data(), aO.data())) first = k;
+    scalars_to_bytes(aL, aL_out); scalars_to_bytes(aR, aR_out); scalars_to_bytes(aO, aO_out);
+    return first;
 }
 
 // TEST HOOK (bpg_test_template_eval_batch): k_witness_eval_batch on the host - one pass per level, per segment every item, into the wave layout
@@ -1268,27 +1293,40 @@ DeviceCircuit *Engine::upload_template(const FlatView &c, const TemplatePlan &T)
     d->wit_stream.ensure(P.stream.size() * 4); d->wit_segs.ensure(P.segs.size() * sizeof(WitnessSegment)); d->wit_v.ensure((c.m ? c.m : 1) * sizeof(scm));
     I.h2d(d->wit_stream.p, P.stream.data(), P.stream.size() * 4);
     I.h2d(d->wit_segs.p, P.segs.data(), P.segs.size() * sizeof(WitnessSegment));
+    d->n_ck = T.ck_var.size();
+    if (d->n_ck) {
+        d->wit_ck_var.ensure(d->n_ck * 4); d->wit_ck.ensure(d->n_ck * sizeof(scm));
+        I.h2d(d->wit_ck_var.p, T.ck_var.data(), d->n_ck * 4);
+    }
     HIPCHK(hipStreamSynchronize(I.st));
     return d.release();
 }
 
+uint64_t Engine::checkpoints_per_item(const DeviceCircuit *d) { return d ? d->n_ck : 0; }
 void Engine::assign(DeviceCircuit *d, const uint8_t *v, const uint8_t *param_values) {
+    if (d && d->n_ck) throw std::invalid_argument("assign: the template was uploaded with checkpoints and needs their values (bpg_r1cs_assign_checkpointed)");
+    (void)assign_checkpointed(d, v, param_values, nullptr);
+}
+uint64_t Engine::assign_checkpointed(DeviceCircuit *d, const uint8_t *v, const uint8_t *param_values, const uint8_t *ck_values) {
+    if (!d || !d->is_template) throw std::invalid_argument("assign: the circuit is not a template (bpg_r1cs_upload_template)");
+    const uint64_t items = d->rep_count ? d->rep_count : 1, total_ck = d->n_ck * items;
+    if (total_ck && !ck_values) throw std::invalid_argument("assign: the template has checkpoints and no values were given for them");
     HIPCHK(hipSetDevice(device_));
     Impl &I = *impl_;
-    if (!d || !d->is_template) throw std::invalid_argument("assign: the circuit is not a template (bpg_r1cs_upload_template)");
     // the previous witness is gone from here on: a failure below must not leave its caches behind either
     drop_witness(d);                                // (the equal-scalar sets belong to the witness they were built from)
-    const uint64_t cnt[2] = {d->m, d->n_params};
-    const uint8_t *src[2] = {v, param_values};
-    scm *dst[2] = {d->wit_v.as<scm>(), d->coef.as<scm>() + d->param_first};
-    I.small_sc.ensure((std::max(cnt[0], cnt[1]) + 1) * 32);
-    for (int k = 0; k < 2; k++) {
+    const uint64_t cnt[3] = {d->m, d->n_params, total_ck};
+    const uint8_t *src[3] = {v, param_values, ck_values};
+    scm *dst[3] = {d->wit_v.as<scm>(), d->coef.as<scm>() + d->param_first, d->wit_ck.as<scm>()};       // checkpoint values go up and into Montgomery form as v does
+    I.small_sc.ensure((std::max(std::max(cnt[0], cnt[1]), cnt[2]) + 1) * 32);
+    for (int k = 0; k < 3; k++) {
         if (!cnt[k]) continue;
         I.h2d(I.small_sc.p, src[k], cnt[k] * 32);
         BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(cnt[k], 256)), dim3(256), I.small_sc.as<uint32_t>(), dst[k], (uint32_t)cnt[k]);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(I.st));                                     // small_sc is staged again below
     }
+    const scm *ck = total_ck ? d->wit_ck.as<scm>() : nullptr;
     // a level's lanes are few (a 512-leaf tree: at most 256): spread them over waves until every SIMD of the device has one
     for (size_t l = 0; l + 1 < d->wit_level_ptr.size(); l++) {
         const uint32_t s0 = d->wit_level_ptr[l], ns = d->wit_level_ptr[l + 1] - s0;
@@ -1296,16 +1334,28 @@ void Engine::assign(DeviceCircuit *d, const uint8_t *v, const uint8_t *param_val
             const uint32_t K = (uint32_t)d->rep_count;
             const uint32_t bps = cdiv(K, 64);                                       // 64 consecutive items of a segment per block, as k_witness_eval_batch has them
             BPG_LAUNCH(I, k_witness_eval_repeat, dim3(ns * bps), dim3(64), d->wit_segs.as<uint4>() + s0, ns, bps, d->wit_stream.as<uint32_t>(), d->coef.as<scm>(),
-                       d->wit_v.as<scm>(), (uint32_t)d->rep_n, (uint32_t)d->rep_m, K, d->aL.as<scm>(), d->aR.as<scm>(), d->aO.as<scm>());
+                       d->wit_v.as<scm>(), ck, (uint32_t)d->n_ck, (uint32_t)d->rep_n, (uint32_t)d->rep_m, K, d->aL.as<scm>(), d->aR.as<scm>(), d->aO.as<scm>());
             continue;
         }
         const uint32_t lanes = std::min(64u, std::max(1u, cdiv(ns, I.wit_waves)));
         BPG_LAUNCH(I, k_witness_eval, dim3(cdiv(ns, lanes)), dim3(lanes), d->wit_segs.as<uint4>() + s0, ns, d->wit_stream.as<uint32_t>(), d->coef.as<scm>(),
-                   d->wit_v.as<scm>(), d->aL.as<scm>(), d->aR.as<scm>(), d->aO.as<scm>());
+                   d->wit_v.as<scm>(), ck, d->aL.as<scm>(), d->aR.as<scm>(), d->aO.as<scm>());
+    }
+    uint64_t first = CHECKPOINTS_HOLD;
+    if (total_ck) {                                 // were the caller's values the circuit's own?  one launch, one 8-byte read-back
+        I.ck_first.ensure(8);
+        static const uint64_t kHold = CHECKPOINTS_HOLD;
+        HIPCHK(hipMemcpyAsync(I.ck_first.p, &kHold, 8, hipMemcpyHostToDevice, I.st));
+        BPG_LAUNCH(I, k_witness_ck_verify, dim3(cdiv(total_ck, 256)), dim3(256), d->wit_ck_var.as<uint32_t>(), (uint32_t)d->n_ck, total_ck,
+                   (uint32_t)(d->rep_count ? d->rep_n : d->n), ck, d->aL.as<scm>(), d->aR.as<scm>(), d->aO.as<scm>(), I.ck_first.as<unsigned long long>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&first, I.ck_first.p, 8, hipMemcpyDeviceToHost, I.st));
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(I.st));
+    if (first != CHECKPOINTS_HOLD) return first;    // an inconsistent witness is never provable: the circuit stays without one (drop_witness above)
     d->has_witness = true; d->wit_v_set = true;
+    return first;
 }
 // ------------------------------------------------------------------------------------------------ R1CS check on the device (hip/k_check.cuh, host/check.hpp)
 // The row-major view of a resident matrix, from its column-major form: entries per row, an exclusive scan, (column, coefficient slot) pairs per row, and the
@@ -1412,13 +1462,17 @@ DeviceCircuit *Engine::repeat_template(DeviceCircuit *src, uint64_t count) {
     std::unique_ptr<DeviceCircuit> d(new DeviceCircuit());
     d->n = n; d->m = m; d->q = q; d->ncols = ncols; d->nnz = nnz; d->const_begin = K * src->const_begin; d->has_witness = false;
     d->is_template = true; d->n_params = K * src->n_params; d->param_first = src->param_first; d->wit_level_ptr = src->wit_level_ptr;
-    d->rep_count = K; d->rep_n = src->n; d->rep_m = src->m;
+    d->rep_count = K; d->rep_n = src->n; d->rep_m = src->m; d->n_ck = src->n_ck;
     d->aL.ensure(n * sizeof(scm)); d->aR.ensure(n * sizeof(scm)); d->aO.ensure(n * sizeof(scm));
     d->col_ptr.ensure((ncols + 1) * 8); d->ent_row.ensure((nnz ? nnz : 1) * 4); d->ent_coef.ensure((nnz ? nnz : 1) * 4);
     d->coef.ensure((ncoef ? ncoef : 1) * sizeof(scm));
     d->wit_stream.ensure(src->wit_stream.cap); d->wit_segs.ensure(src->wit_segs.cap); d->wit_v.ensure((m ? m : 1) * sizeof(scm));
     HIPCHK(hipMemcpyAsync(d->wit_stream.p, src->wit_stream.p, src->wit_stream.cap, hipMemcpyDeviceToDevice, I.st));
     HIPCHK(hipMemcpyAsync(d->wit_segs.p, src->wit_segs.p, src->wit_segs.cap, hipMemcpyDeviceToDevice, I.st));
+    if (d->n_ck) {                                  // the source's checkpoints, per item: K n_ck values, item-major
+        d->wit_ck_var.ensure(d->n_ck * 4); d->wit_ck.ensure(K * d->n_ck * sizeof(scm));
+        HIPCHK(hipMemcpyAsync(d->wit_ck_var.p, src->wit_ck_var.p, d->n_ck * 4, hipMemcpyDeviceToDevice, I.st));
+    }
     const uint32_t gy = (uint32_t)std::min<uint64_t>(K, 1024);           // copies beyond the grid's y extent are a loop in the kernels
     BPG_LAUNCH(I, k_repeat_colptr, dim3(cdiv(3 * src->n + src->m + 1, 256), gy), dim3(256), src->col_ptr.as<uint64_t>(), D, (uint32_t)K, d->col_ptr.as<uint64_t>());
     if (src->nnz) BPG_LAUNCH(I, k_repeat_entries, dim3(cdiv(src->nnz, 256), gy), dim3(256), src->col_ptr.as<uint64_t>(), src->ent_row.as<uint32_t>(),
@@ -2178,6 +2232,7 @@ void Engine::drop_witness(DeviceCircuit *d) {
 }
 void Engine::prove_template_batch(DeviceCircuit *d, size_t count, ProveItem *items, bool commit) {
     if (!template_lockstep(d)) throw std::logic_error("prove_template_batch: the circuit is not a template with a host copy of its rows");
+    if (d->n_ck) throw std::invalid_argument("prove_template_batch: the template has checkpoints, and a batch item carries no values for them");
     drop_witness(d);
     for (size_t k = 0; k < count; k++) {
         if (!items[k].values && d->m) throw std::invalid_argument("prove_template_batch: an item without committed values");
@@ -2928,7 +2983,7 @@ void Engine::merkle_nodes(DeviceMerkle *t, uint32_t level, uint64_t first, uint6
     HIPCHK(hipStreamSynchronize(I.st));
 }
 
-void Engine::merkle_paths(DeviceMerkle *t, uint64_t count, const uint64_t *indices, uint8_t *out) {
+void Engine::merkle_paths(DeviceMerkle *t, uint64_t count, const uint64_t *indices, uint8_t *out, bool ancestors) {
     if (!t || t->owner != this) throw std::invalid_argument("merkle_paths: not a tree of this context");
     if (!count) return;
     if (!indices || !out) throw std::invalid_argument("merkle_paths: null pointer");
@@ -2946,7 +3001,7 @@ void Engine::merkle_paths(DeviceMerkle *t, uint64_t count, const uint64_t *indic
     for (uint64_t at = 0; at < count; at += per) {
         const uint32_t n = (uint32_t)std::min(per, count - at);
         HIPCHK(hipMemcpyAsync(I.mk_in.p, idx.data() + at, (size_t)n * 4, hipMemcpyHostToDevice, I.st));
-        BPG_LAUNCH(I, k_merkle_paths, dim3(cdiv((uint64_t)n * d, 256)), dim3(256), t->tree.as<scm>(), d, I.mk_in.as<uint32_t>(), n, I.mk_out.as<uint32_t>());
+        BPG_LAUNCH(I, k_merkle_paths, dim3(cdiv((uint64_t)n * d, 256)), dim3(256), t->tree.as<scm>(), d, I.mk_in.as<uint32_t>(), n, ancestors ? 1u : 0u, I.mk_out.as<uint32_t>());
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(out + (size_t)at * row, I.mk_out.p, (size_t)n * row, hipMemcpyDeviceToHost, I.st));
     }

@@ -90,6 +90,14 @@ public:
     // parameter row; a_L, a_R, a_O are computed on the device (k_witness_eval, one launch per schedule level), everything cached for the previous witness
     // (the equal-scalar merge sets) is dropped.  Returns once the witness is in place.
     void assign(DeviceCircuit *c, const uint8_t *v, const uint8_t *param_values);
+    // The same for a template uploaded with checkpoints (include/bpg.h bpg_r1cs_assign_checkpointed; WitnessProgramView::ck_var): ck_values are the values of the
+    // checkpointed variables (32 bytes each, reduced mod l on the device; a repeat: count x n_ck, item-major).  The levels read them wherever the program names a
+    // checkpoint; one more launch (k_witness_ck_verify) then compares each with what the circuit computed.  Returns CHECKPOINTS_HOLD, or the lowest flat index
+    // (item * n_ck + k) that differs - the circuit then holds NO witness.  A template without checkpoints takes null ck_values and is plain assign().
+    // Plain assign() on a checkpointed template: std::invalid_argument.
+    static constexpr uint64_t CHECKPOINTS_HOLD = ~0ull;
+    uint64_t assign_checkpointed(DeviceCircuit *c, const uint8_t *v, const uint8_t *param_values, const uint8_t *ck_values);
+    static uint64_t checkpoints_per_item(const DeviceCircuit *c);   // n_ck of the template (a repeat: of its source; it takes count x n_ck values)
     // Which multiplier, which constraint row does the resident witness break (include/bpg.h bpg_r1cs_check; hip/k_check.cuh): a_L * a_R against a_O per multiplier, and
     // every row of the matrix over the operand vector [a_L | a_R | a_O | v | 1].  v: m x 32 bytes (reduced mod l on the device), or null on a template: the values
     // of its last assign().  rows_out receives the lowest min(cap, bad_rows) bad rows, ascending.  The first check of a circuit derives a row-major view of its
@@ -99,6 +107,9 @@ public:
     static void template_eval_host(const FlatView &c, const WitnessProgramView &p, const uint8_t *v, uint8_t *aL, uint8_t *aR, uint8_t *aO);   // test hook
     // test hook (bpg_test_template_eval_batch): the BATCHED interpreter (k_witness_eval_batch) compiled for the host - level by level, every item of a
     // segment side by side, into the wave layout (count x N x 32 bytes per vector, item-major, N = padded size, padding rows zero); v: count x m x 32
+    // test hook (bpg_test_template_eval_checkpointed): template_eval_host for a program with checkpoints, made to show what in-order execution on one thread
+    // hides - a_L, a_R, a_O start as a poison value, the segments of every level run in REVERSE order, then the verify step; returns the first mismatch
+    static uint64_t template_eval_checkpointed_host(const FlatView &c, const WitnessProgramView &p, const uint8_t *v, const uint8_t *ck_values, uint8_t *aL, uint8_t *aR, uint8_t *aO);
     static void template_eval_batch_host(const FlatView &c, const WitnessProgramView &p, uint64_t count, const uint8_t *v, uint8_t *aL, uint8_t *aR, uint8_t *aO);
     // A template repeated `count` times (include/bpg.h bpg_r1cs_template_repeat; hip/k_repeat.cuh): a new resident template of count x (n, q, m, n_params), built on
     // the device from the source's resident matrix - copy k at multipliers k n.., committed values k m.., rows k q.., parameter slots k n_params.., everything else
@@ -179,7 +190,8 @@ public:
     // the full tree over 2^depth leaves (depth 1..24; a leaf is any 256-bit value, taken mod l): node = sponge(left, right), resident in Montgomery form
     DeviceMerkle *merkle_build(uint32_t depth, const uint8_t *leaves);
     void merkle_nodes(DeviceMerkle *t, uint32_t level, uint64_t first, uint64_t count, uint8_t *out);      // level 0 = the root, level depth = the leaves
-    void merkle_paths(DeviceMerkle *t, uint64_t count, const uint64_t *indices, uint8_t *siblings_out);    // count x depth x 32, the leaf's sibling first
+    // count x depth x 32, the leaf's sibling first; ancestors (bpg_merkle_path_nodes): the nodes ON each path instead, the leaf's parent first, the root last
+    void merkle_paths(DeviceMerkle *t, uint64_t count, const uint64_t *indices, uint8_t *siblings_out, bool ancestors = false);
     void merkle_update(DeviceMerkle *t, uint64_t count, const uint64_t *indices, const uint8_t *leaves);   // distinct indices; only their ancestors are recomputed
     static void merkle_free(DeviceMerkle *t);       // on the tree's own context; a tree that outlived its context lost its memory then and is only deleted
     void synchronize();

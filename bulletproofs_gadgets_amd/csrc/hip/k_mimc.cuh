@@ -100,13 +100,15 @@ __global__ void __launch_bounds__(256) k_merkle_set_leaves(scm *tree, uint32_t d
     tree[(1u << depth) + index[i]] = sc_from_words(w);
 }
 // authentication paths: one thread per (item, level); out[item][lv] = the sibling of leaf index[item]'s ancestor lv levels above the leaves (lv = 0: the
-// leaf's own sibling), canonical bytes
-__global__ void __launch_bounds__(256) k_merkle_paths(const scm *__restrict__ tree, uint32_t depth, const uint32_t *__restrict__ index, uint32_t count, uint32_t *__restrict__ out) {
+// leaf's own sibling), canonical bytes.  ancestors != 0 (bpg_merkle_path_nodes): out[item][lv] = that ancestor's PARENT instead - the nodes ON the path, from
+// the leaf's parent up to the root (lv = depth - 1), the values a path circuit computes where the siblings are what it is given
+__global__ void __launch_bounds__(256) k_merkle_paths(const scm *__restrict__ tree, uint32_t depth, const uint32_t *__restrict__ index, uint32_t count, uint32_t ancestors,
+                                                      uint32_t *__restrict__ out) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;          // count * depth < 2^32 (the engine cuts longer lists into several launches)
     if (t >= count * depth) return;
     const uint32_t item = t / depth, lv = t - item * depth;
-    const uint32_t h = ((1u << depth) + index[item]) >> lv;
-    sc_store_canonical(out + 8 * (size_t)t, tree[h ^ 1u]);
+    const uint32_t h = ((1u << depth) + index[item]) >> lv;            // lv < depth: h >= 2, so h >> 1 >= 1 is a node of the heap
+    sc_store_canonical(out + 8 * (size_t)t, tree[ancestors ? h >> 1 : h ^ 1u]);
 }
 // a run of nodes as canonical bytes (bpg_merkle_root, bpg_merkle_nodes)
 __global__ void __launch_bounds__(256) k_merkle_export(const scm *__restrict__ nodes, uint32_t count, uint32_t *__restrict__ out) {

@@ -36,10 +36,11 @@ BPG_HD uint32_t repeat_var_of(uint32_t col, uint32_t n, uint32_t m) {
 BPG_HD uint64_t repeat_entry_pos(uint64_t K, uint64_t k, uint64_t s0, uint64_t s1, uint64_t e) { return K * s0 + k * (s1 - s0) + (e - s0); }
 
 // one lane of the repeat evaluation: segment sd = (first, count, stream word) of the source for item k
+// (ck, n_ck: the checkpoint values of a checkpointed source, item k's at ck + k n_ck; null, 0 otherwise)
 BPG_HD void witness_eval_repeat_lane(uint32_t first, uint32_t count, const uint32_t *rec, const scm *coef, const scm *v, uint32_t n, uint32_t m, uint64_t k,
-                                     scm *aL, scm *aR, scm *aO) {
+                                     scm *aL, scm *aR, scm *aO, const scm *ck = nullptr, uint32_t n_ck = 0) {
     const size_t b = (size_t)k * n;
-    witness_eval_segment(first, count, rec, coef, v + (size_t)k * m, aL + b, aR + b, aO + b);
+    witness_eval_segment(first, count, rec, coef, v + (size_t)k * m, aL + b, aR + b, aO + b, ck ? ck + (size_t)k * n_ck : nullptr);
 }
 
 #if defined(__HIPCC__)
@@ -86,12 +87,12 @@ __global__ void __launch_bounds__(256) k_repeat_coef(const scm *__restrict__ coe
 // One launch per schedule level of the SOURCE; segs = that level's segments.  A block holds 64 consecutive ITEMS of one segment, the lane
 // map of k_witness_eval_batch: same records, same classes, no divergence; blocks_per_seg = ceil(K / 64) blocks per segment, segment-major in x.
 __global__ void __launch_bounds__(64) k_witness_eval_repeat(const uint4 *__restrict__ segs, uint32_t nseg, uint32_t blocks_per_seg, const uint32_t *__restrict__ stream,
-                                                            const scm *__restrict__ coef, const scm *__restrict__ v, uint32_t n, uint32_t m, uint32_t K,
-                                                            scm *aL, scm *aR, scm *aO) {
+                                                            const scm *__restrict__ coef, const scm *__restrict__ v, const scm *__restrict__ ck, uint32_t n_ck,
+                                                            uint32_t n, uint32_t m, uint32_t K, scm *aL, scm *aR, scm *aO) {
     const uint32_t s = blockIdx.x / blocks_per_seg, item = (blockIdx.x % blocks_per_seg) * blockDim.x + threadIdx.x;
     if (s >= nseg || item >= K) return;
     const uint4 sd = segs[s];
-    witness_eval_repeat_lane(sd.x, sd.y, stream + sd.z, coef, v, n, m, item, aL, aR, aO);
+    witness_eval_repeat_lane(sd.x, sd.y, stream + sd.z, coef, v, n, m, item, aL, aR, aO, ck, n_ck);
 }
 #endif  // __HIPCC__
 

@@ -10,6 +10,9 @@
 // keeps the eight canonical words in registers for the records that follow with WIT_HINT_SAME_SOURCE - a 64-bit range costs one reduction and 64 bit
 // extractions.  Which branch a record takes is a property of the RECORD (the same for every lane that walks it); the bit itself, the only thing that differs
 // between the items of a batch, selects by mask.
+// A term of kind WIT_KIND_CHECKPOINT reads `ck`, the values the caller handed to assign (Engine::assign_checkpointed), by its position in the checkpoint
+// list - never a_L, a_R, a_O and never the register copy of the last multiplier, whoever computes that variable.  So a level still reads only what an earlier
+// launch, the lane itself or the caller wrote.  k_witness_ck_verify, after the last level, compares every checkpoint with what the circuit computed for it.
 #pragma once
 #include "sc.cuh"
 #include "../host/witness_record.hpp"
@@ -19,7 +22,8 @@ namespace bpg {
 struct WitPrev { scm l, r, o; uint32_t idx; };
 
 // sum of `count` terms at t[0 .. 2 count): (packed variable, class << 30 | coefficient index)
-BPG_HD scm witness_eval_lc(const uint32_t *t, uint32_t count, const WitPrev &prev, const scm *coef, const scm *v, const scm *aL, const scm *aR, const scm *aO) {
+BPG_HD scm witness_eval_lc(const uint32_t *t, uint32_t count, const WitPrev &prev, const scm *coef, const scm *v, const scm *aL, const scm *aR, const scm *aO,
+                           const scm *ck) {
     scm acc = sc_zero();
     for (uint32_t k = 0; k < count; k++) {
         const uint32_t var = t[2 * k], cw = t[2 * k + 1];
@@ -30,7 +34,7 @@ BPG_HD scm witness_eval_lc(const uint32_t *t, uint32_t count, const WitPrev &pre
         }
         scm x;
         if (kind <= 2 && idx == prev.idx) x = kind == 0 ? prev.l : kind == 1 ? prev.r : prev.o;
-        else x = (kind == 0 ? aL : kind == 1 ? aR : kind == 2 ? aO : v)[idx];
+        else x = (kind == 0 ? aL : kind == 1 ? aR : kind == 2 ? aO : kind == WIT_KIND_CHECKPOINT ? ck : v)[idx];
         if (cls == WIT_COEF_PLUS_ONE) acc = sc_add(acc, x);
         else if (cls == WIT_COEF_MINUS_ONE) acc = sc_sub(acc, x);
         else acc = sc_add(acc, sc_mont_mul(coef[ci], x));
@@ -46,15 +50,16 @@ BPG_HD uint32_t witness_bit(const uint32_t *w, uint32_t bit) {
     return (x >> (bit & 31u)) & 1u;
 }
 
-// multipliers [first, first + count) from the records at `rec`
-BPG_HD void witness_eval_segment(uint32_t first, uint32_t count, const uint32_t *rec, const scm *coef, const scm *v, scm *aL, scm *aR, scm *aO) {
+// multipliers [first, first + count) from the records at `rec`; ck: the checkpoint values (null for a program without checkpoints: no term names one)
+BPG_HD void witness_eval_segment(uint32_t first, uint32_t count, const uint32_t *rec, const scm *coef, const scm *v, scm *aL, scm *aR, scm *aO,
+                                 const scm *ck = nullptr) {
     WitPrev prev; prev.l = prev.r = prev.o = sc_zero(); prev.idx = 0xffffffffu;
     uint32_t src[8];                                                // canonical words of the last hint source (the packer never shares across segments)
     BPG_UNROLL for (int k = 0; k < 8; k++) src[k] = 0;
     for (uint32_t i = first; i < first + count; i++) {
         const uint32_t nl = rec[0], w1 = rec[1];
         if (w1 & WIT_HINT_BIT_PAIR) {
-            if (!(w1 & WIT_HINT_SAME_SOURCE)) sc_to_words(src, witness_eval_lc(rec + 2, nl, prev, coef, v, aL, aR, aO));
+            if (!(w1 & WIT_HINT_SAME_SOURCE)) sc_to_words(src, witness_eval_lc(rec + 2, nl, prev, coef, v, aL, aR, aO, ck));
             const uint32_t set = 0u - witness_bit(src, w1 & WIT_HINT_ARG_MASK);     // all ones when the bit is set
             const scm one = SC_R1();
             scm l, r;
@@ -65,8 +70,8 @@ BPG_HD void witness_eval_segment(uint32_t first, uint32_t count, const uint32_t 
             continue;
         }
         const uint32_t same = w1 & WIT_SAME_AS_LEFT, nr = w1 & WIT_RIGHT_COUNT_MASK;
-        const scm l = witness_eval_lc(rec + 2, nl, prev, coef, v, aL, aR, aO);
-        const scm r = same ? l : witness_eval_lc(rec + 2 + 2 * nl, nr, prev, coef, v, aL, aR, aO);
+        const scm l = witness_eval_lc(rec + 2, nl, prev, coef, v, aL, aR, aO, ck);
+        const scm r = same ? l : witness_eval_lc(rec + 2 + 2 * nl, nr, prev, coef, v, aL, aR, aO, ck);
         const scm o = sc_mont_mul(l, r);
         aL[i] = l; aR[i] = r; aO[i] = o;
         prev.l = l; prev.r = r; prev.o = o; prev.idx = i;
@@ -74,15 +79,36 @@ BPG_HD void witness_eval_segment(uint32_t first, uint32_t count, const uint32_t 
     }
 }
 
+// Does checkpoint k of an item hold?  var = ck_var[k]; aL, aR, aO and ck are the ITEM's (both sides canonical Montgomery form: equal values, equal words)
+BPG_HD bool witness_ck_holds(uint32_t var, const scm &given, const scm *aL, const scm *aR, const scm *aO) {
+    const uint32_t kind = var >> 29, idx = var & 0x1fffffffu;
+    const scm x = (kind == 0 ? aL : kind == 1 ? aR : aO)[idx];
+    uint32_t diff = 0;
+    BPG_UNROLL for (int j = 0; j < 8; j++) diff |= x.v[j] ^ given.v[j];
+    return diff == 0;
+}
+
 #if defined(__HIPCC__)     // the kernels; everything above also compiles for the host alone (tests/hostcheck/template_repeat.cpp)
 // segs: (first multiplier, count, first record word, -) per segment of ONE level.  Blocks are small (the engine spreads a level's few hundred lanes
 // over many waves: a lane alone in its wave reads one cache line per load, 64 lanes read 64).
 __global__ void __launch_bounds__(64) k_witness_eval(const uint4 *__restrict__ segs, uint32_t nseg, const uint32_t *__restrict__ stream,
-                                                     const scm *__restrict__ coef, const scm *__restrict__ v, scm *aL, scm *aR, scm *aO) {
+                                                     const scm *__restrict__ coef, const scm *__restrict__ v, const scm *__restrict__ ck, scm *aL, scm *aR, scm *aO) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= nseg) return;
     const uint4 sd = segs[s];
-    witness_eval_segment(sd.x, sd.y, stream + sd.z, coef, v, aL, aR, aO);
+    witness_eval_segment(sd.x, sd.y, stream + sd.z, coef, v, aL, aR, aO, ck);
+}
+
+// After the last level of a checkpointed assign: one lane per (item, checkpoint), flat index t = item * n_ck + k; item's vectors at item * n (a plain template:
+// one item).  The lowest flat index whose value differs from what the circuit computed goes to *first (64-bit atomicMin; the host set it to all ones).
+__global__ void __launch_bounds__(256) k_witness_ck_verify(const uint32_t *__restrict__ ck_var, uint32_t n_ck, uint64_t total, uint32_t n, const scm *__restrict__ ck,
+                                                           const scm *__restrict__ aL, const scm *__restrict__ aR, const scm *__restrict__ aO, unsigned long long *first) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const uint64_t item = t / n_ck;
+    const uint32_t k = (uint32_t)(t - item * n_ck);
+    const size_t b = (size_t)item * n;
+    if (!witness_ck_holds(ck_var[k], ck[t], aL + b, aR + b, aO + b)) atomicMin(first, (unsigned long long)t);
 }
 
 // K witnesses of ONE template in the wave layout of a lockstep batch (k_batch.cuh: item k's vectors of length N live at [k*N, (k+1)*N)); item k's

@@ -23,13 +23,14 @@
 //                                       k_bt_commit_v: the Pedersen commitments of a template wave's committed values, from the values the wave uploaded for its
 //                                       witness evaluation - one launch per wave (bpg_r1cs_prove_template_batch_commit)
 //       circuit templates               k_witness_eval (k_witness.cuh): a_L, a_R, a_O of a resident circuit from the committed values of a fresh witness, by interpreting the
-//                                       recorded witness program - one launch per level of its schedule, one lane per segment (replaces the host's assembly + upload)
+//                                       recorded witness program - one launch per level of its schedule, one lane per segment (replaces the host's assembly + upload);
+//                                       k_witness_ck_verify: after a checkpointed assign, the caller's intermediate values against the computed ones, a lane per checkpoint
 //       a template repeated K times      (k_repeat.cuh) k_repeat_colptr, k_repeat_entries, k_repeat_coef: the K-fold circuit's column-major matrix from the template's
 //                                       resident one; k_witness_eval_repeat: its witness by the template's program, a lane per (segment, item) (one proof for K witnesses)
 //       MiMC sponges, Merkle trees       (k_mimc.cuh; no row of the survey: the native hash in front of Prover::commit) k_mimc_sponge: one lane per item; a tree of 2^d leaves in
 //                                       one heap-ordered array: k_merkle_leaves, k_merkle_level (one launch per level, one lane per parent), k_merkle_top (the levels of at
 //                                       most 256 parents in one launch), k_merkle_level_list + k_merkle_set_leaves (leaf updates: the ancestors only), k_merkle_paths
-//                                       (sibling lists), k_merkle_export (nodes as bytes)
+//                                       (sibling lists, or the nodes on the paths), k_merkle_export (nodes as bytes)
 //       R1CS check                       (k_check.cuh; bpg_r1cs_check: which multiplier, which constraint does the resident witness break) the row-major view of the resident
 //                                       matrix, once per circuit: k_rowview_count, k_scan_blocksums / _apply, k_rowview_fill, k_rowview_long; per check: k_check_mul (a lane
 //                                       per multiplier), k_check_rows (a lane per short row, the wave's ballot = one word of the violation bitmap), k_check_rows_long (a

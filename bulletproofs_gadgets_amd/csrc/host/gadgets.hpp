@@ -125,6 +125,7 @@ inline Scalar mimc_hash(const Bytes &preimage) {                                
 class MimcHash256 : public Gadget {
 public:
     static constexpr size_t ROUNDS = 486;
+    static constexpr uint32_t NOTE_LAST_BLOCK = 1u << 31;     // tag of ConstraintSystem::note_value: the block index, this bit on the sponge's last block
     MimcHash256() : image_(LinearCombination(Scalar::zero())) {}                                   // init()   :58-63
     explicit MimcHash256(const LinearCombination &image) : image_(image) {}                        // new()    :65-70
     std::vector<Scalar> preprocess(const std::vector<Scalar> &w) const override {                  // :15-37
@@ -140,7 +141,12 @@ public:
     }
     LinearCombination mimc_sponge(ConstraintSystem &cs, const std::vector<LinearCombination> &pre) const {   // :108-122
         LinearCombination key_zero(Scalar::zero()), state(Scalar::zero());
-        for (auto &v : pre) { state = state + v; state = mimc_encryption_lc(cs, state, key_zero); }
+        uint32_t block = 0;
+        for (auto &v : pre) {
+            state = state + v; state = mimc_encryption_lc(cs, state, key_zero);
+            cs.note_value(state, block | (block + 1 == pre.size() ? NOTE_LAST_BLOCK : 0u));      // a value the native sponge gives too: a checkpoint candidate
+            block++;
+        }
         return state;
     }
 private:

@@ -108,6 +108,10 @@ public:
         }
         return allocate_multiplier(source_assignment.some, l, r);
     }
+    // "The value of `lc` is one a caller may know without this circuit" (a sponge state after an absorbed block, a Merkle node): a Prover remembers the
+    // variable as a candidate CHECKPOINT of a circuit template (bpg_witness_checkpoints); to everybody else it is nothing.  It adds no multiplier, no
+    // constraint and no transcript byte.
+    virtual void note_value(const LinearCombination &lc, uint32_t tag) { (void)lc; (void)tag; }
 };
 
 // Flattened instance handed to the engine / exported for the oracle (layout of include/bpg.h bpg_r1cs_upload)
@@ -152,6 +156,10 @@ struct WitnessProgramView {
     const uint64_t *param_rows = nullptr;
     uint64_t n_hints = 0;
     const uint32_t *hint_mul = nullptr, *hint_kind = nullptr, *hint_arg = nullptr;
+    // Checkpoints (bpg_witness_checkpoints): ck_var[k] is a multiplier variable (kind 0..2, index < n, each named once) whose value the caller hands to
+    // assign; every term that names it reads the caller's value (host/template.hpp), and the device compares it with what the circuit computed
+    uint64_t n_ck = 0;
+    const uint32_t *ck_var = nullptr;
     WitnessProgramView() {}
     explicit WitnessProgramView(const WitnessProgram &w)
         : lc_ptr(w.lc_ptr.data()), term_var(w.term_var.data()), term_coef(w.term_coef.data()), n_params(w.param_rows.size()), param_rows(w.param_rows.data()),
@@ -266,6 +274,20 @@ public:
         return mv;
     }
     void constrain(const LinearCombination &lc) override { push_row(lc); }
+    // recorded when lc is exactly ONE multiplier variable with coefficient one plus constants that sum to zero (a sponge state is `cube.o + 0`); else ignored
+    void note_value(const LinearCombination &lc, uint32_t tag) override {
+        const Variable *var = nullptr;
+        Scalar constant;
+        for (auto &t : lc.terms) {
+            if (t.first.kind == Variable::One) { constant += t.second; continue; }
+            if (var || t.first.kind > Variable::MultiplierOutput || !(red(t.second) == Scalar::one())) return;
+            var = &t.first;
+        }
+        if (!var || !(red(constant) == Scalar::zero())) return;
+        noted_var_.push_back(var->packed()); noted_tag_.push_back(tag);
+    }
+    const std::vector<uint32_t> &noted_vars() const { return noted_var_; }
+    const std::vector<uint32_t> &noted_tags() const { return noted_tag_; }
 
     size_t get_num_multiplications() const { return aL_.size(); }
     size_t num_committed() const { return v_.size(); }
@@ -365,6 +387,7 @@ private:
     std::vector<uint32_t> hint_coef_;   // dictionary index per hint term, filled by resolve_hints
     void resolve_hints() { while (hint_coef_.size() < hint_terms_.size()) hint_coef_.push_back(intern(hint_terms_[hint_coef_.size()].second)); }
     std::vector<uint64_t> param_rows_;
+    std::vector<uint32_t> noted_var_, noted_tag_;     // note_value: packed variable and the caller's tag, in call order
 };
 
 class Verifier : public ConstraintSystem, public CircuitCore {

@@ -10,10 +10,18 @@
 // source is not the source of the hinted multiplier right before it opens a segment.  A run of bit hints over one source - a range proof - is thus a lane of
 // its own that reduces the source once (WIT_HINT_SAME_SOURCE), one level above whatever made the source, and is never hung onto the end of a 972-product
 // chain.  (A 64-bit range proof over one committed value: one segment at level 0.)
+// A CHECKPOINTED multiplier variable (WitnessProgramView::ck_var) is a value the caller hands to assign beside the committed ones.  It is WRITTEN like any
+// multiplier and READ like a committed value: a multiplier that names a checkpoint its segment has not named before opens a new segment (also when the named
+// multiplier lies inside the current segment), and the read adds nothing to the segment's level.  The packer writes every term that names it - left lists,
+// right lists, hint sources - with the packed kind WIT_KIND_CHECKPOINT and the position in the checkpoint list, so the reader takes the caller's value and
+// never another lane's.  (A sponge whose block states are checkpointed: every block a segment at level 0.  A Merkle path whose node hashes are: two levels.)
+// Whether the caller's values ARE what the circuit computes is checked on the device after the last level (k_witness_ck_verify).  No checkpoints: the
+// schedule and the stream are bit for bit what they were.
 #pragma once
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <unordered_map>
 #include <vector>
 #include "r1cs.hpp"
 #include "witness_record.hpp"
@@ -64,6 +72,23 @@ inline void check_witness_program(const FlatView &c, const WitnessProgramView &p
         if (p.param_rows[k] >= c.q) throw std::invalid_argument("template: parameter row out of range");
         for (uint64_t j = 0; j < k; j++) if (p.param_rows[j] == p.param_rows[k]) throw std::invalid_argument("template: parameter row named twice");
     }
+    if (p.n_ck && !p.ck_var) throw std::invalid_argument("template: n_checkpoints without vars");
+    if (p.n_ck > 3 * c.n) throw std::invalid_argument("template: more checkpoints than multiplier variables (a variable is named twice)");
+    std::unordered_map<uint32_t, uint32_t> seen;
+    for (uint64_t k = 0; k < p.n_ck; k++) {
+        const uint32_t kind = p.ck_var[k] >> 29, idx = p.ck_var[k] & 0x1fffffffu;
+        if (kind > 2) throw std::invalid_argument("template: checkpoint " + std::to_string(k) + " is no multiplier variable (kind " + std::to_string(kind) + "; a checkpoint is a_L, a_R or a_O of a multiplier)");
+        if (idx >= c.n) throw std::invalid_argument("template: checkpoint " + std::to_string(k) + " names multiplier " + std::to_string(idx) + " (out of range)");
+        if (!seen.emplace(p.ck_var[k], (uint32_t)k).second) throw std::invalid_argument("template: checkpoint " + std::to_string(k) + " names a variable that checkpoint " + std::to_string(seen[p.ck_var[k]]) + " names already");
+    }
+}
+
+// packed variable -> position in the checkpoint list (empty without checkpoints)
+inline std::unordered_map<uint32_t, uint32_t> checkpoint_index(const WitnessProgramView &p) {
+    std::unordered_map<uint32_t, uint32_t> at;
+    at.reserve(p.n_ck);
+    for (uint64_t k = 0; k < p.n_ck; k++) at.emplace(p.ck_var[k], (uint32_t)k);
+    return at;
 }
 
 // hint k reads the source of hint k - 1, which sits on the multiplier right before: the same terms in the same order
@@ -79,7 +104,9 @@ inline bool hint_same_source(const WitnessProgramView &p, uint64_t k) {
 inline WitnessSchedule build_witness_schedule(uint64_t n, uint64_t m, const WitnessProgramView &p) {
     WitnessSchedule S;
     const uint32_t NONE = UINT32_MAX;
-    std::vector<uint32_t> seg_of(n), seen_mul(n, NONE), seen_v(m, NONE);    // seen_*: the last segment that named this value from outside
+    std::vector<uint32_t> seg_of(n), seen_mul(n, NONE), seen_v(m, NONE), seen_ck(p.n_ck, NONE);    // seen_*: the last segment that named this value from outside
+    const std::unordered_map<uint32_t, uint32_t> ck_at = checkpoint_index(p);
+    auto ck_of = [&](uint32_t var) { if (ck_at.empty()) return NONE; const auto it = ck_at.find(var); return it == ck_at.end() ? NONE : it->second; };
     uint32_t seg = NONE, first = 0;
     uint64_t h = 0;                                                          // next hint
     for (uint64_t i = 0; i < n; i++) {
@@ -87,14 +114,18 @@ inline WitnessSchedule build_witness_schedule(uint64_t n, uint64_t m, const Witn
         if (h < p.n_hints && p.hint_mul[h] == i) { cut = cut || !hint_same_source(p, h); h++; }
         for (uint64_t k = p.lc_ptr[2 * i]; k < p.lc_ptr[2 * i + 2] && !cut; k++) {
             const uint32_t kind = p.term_var[k] >> 29, idx = p.term_var[k] & 0x1fffffffu;
+            const uint32_t ck = kind <= 2 ? ck_of(p.term_var[k]) : NONE;
             if (kind == 3) cut = seen_v[idx] != seg;
+            else if (ck != NONE) cut = seen_ck[ck] != seg;
             else if (kind <= 2 && idx < first) cut = seen_mul[idx] != seg;
         }
         if (cut) { seg = (uint32_t)S.seg_first.size(); first = (uint32_t)i; S.seg_first.push_back(first); S.seg_level.push_back(0); }
         seg_of[i] = seg;
         for (uint64_t k = p.lc_ptr[2 * i]; k < p.lc_ptr[2 * i + 2]; k++) {
             const uint32_t kind = p.term_var[k] >> 29, idx = p.term_var[k] & 0x1fffffffu;
+            const uint32_t ck = kind <= 2 ? ck_of(p.term_var[k]) : NONE;
             if (kind == 3) seen_v[idx] = seg;
+            else if (ck != NONE) seen_ck[ck] = seg;                                  // the caller's value: no level, whoever computes it
             else if (kind <= 2 && idx < first) { seen_mul[idx] = seg; S.seg_level[seg] = std::max(S.seg_level[seg], S.seg_level[seg_of[idx]] + 1); }
         }
     }
@@ -142,6 +173,12 @@ inline PackedWitnessProgram pack_witness_program(const FlatView &c, const Witnes
         cls[k] = zero ? 3 : one ? WIT_COEF_PLUS_ONE : minus ? WIT_COEF_MINUS_ONE : WIT_COEF_GENERAL;
     }
     PackedWitnessProgram P;
+    const std::unordered_map<uint32_t, uint32_t> ck_at = checkpoint_index(p);
+    auto packed_var = [&](uint32_t var) {
+        if (ck_at.empty()) return var;
+        const auto it = ck_at.find(var);
+        return it == ck_at.end() ? var : (WIT_KIND_CHECKPOINT << 29 | it->second);
+    };
     std::vector<uint64_t> rec_at(c.n);
     P.stream.reserve(2 * c.n + 2 * p.lc_ptr[2 * c.n]);
     auto emit = [&](uint64_t a, uint64_t b) {
@@ -149,7 +186,7 @@ inline PackedWitnessProgram pack_witness_program(const FlatView &c, const Witnes
         for (uint64_t k = a; k < b; k++) {
             const uint32_t cl = cls[p.term_coef[k]];
             if (cl == 3) continue;
-            P.stream.push_back(p.term_var[k]); P.stream.push_back(cl << WIT_CLASS_SHIFT | p.term_coef[k]); cnt++;
+            P.stream.push_back(packed_var(p.term_var[k])); P.stream.push_back(cl << WIT_CLASS_SHIFT | p.term_coef[k]); cnt++;
         }
         return cnt;
     };
@@ -215,6 +252,7 @@ struct TemplatePlan {
     PackedWitnessProgram packed;
     FlatCircuit slotted;            // the instance's rows with parameter slots (no witness)
     uint64_t n_params = 0, param_first = 0;
+    std::vector<uint32_t> ck_var;   // the checkpointed variables, in the caller's order (empty: none)
 };
 
 }  // namespace bpg

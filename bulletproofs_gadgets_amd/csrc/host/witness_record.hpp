@@ -7,6 +7,8 @@
 // SOURCE, which follow; a_L = 1 - b, a_R = b, a_O = 0 with b that bit of the canonical value (mod l) of the source.  WIT_HINT_SAME_SOURCE beside it: the
 // source is the previous record's (a hinted record of the same segment) - word 0 is 0, no terms follow, and the reader still holds the reduced value.
 // The flags leave 29 bits for a right-term count.
+// A term that names a CHECKPOINTED variable (bpg_witness_checkpoints) carries the kind WIT_KIND_CHECKPOINT and, as its index, the position in the checkpoint
+// list: the reader takes the value the caller handed to assign.  The kind exists in this stream only; the variable kinds of include/bpg.h stay 0..4.
 #pragma once
 #include <cstdint>
 
@@ -16,5 +18,6 @@ constexpr uint32_t WIT_SAME_AS_LEFT = 1u << 31, WIT_HINT_BIT_PAIR = 1u << 30, WI
 constexpr uint32_t WIT_RIGHT_COUNT_MASK = WIT_HINT_SAME_SOURCE - 1u, WIT_HINT_ARG_MASK = 0xffu;
 constexpr uint32_t WIT_CLASS_SHIFT = 30, WIT_COEF_INDEX_MASK = (1u << WIT_CLASS_SHIFT) - 1u;
 constexpr uint32_t WIT_COEF_GENERAL = 0, WIT_COEF_PLUS_ONE = 1, WIT_COEF_MINUS_ONE = 2;
+constexpr uint32_t WIT_KIND_CHECKPOINT = 5;
 
 }  // namespace bpg

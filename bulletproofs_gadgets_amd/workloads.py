@@ -103,6 +103,21 @@ def full_tree_pattern(leaves: int) -> str:
     return pat
 
 
+def merkle_path_pattern(index: int, depth: int):
+    """The MerkleTree256 pattern of the authentication path of leaf `index` in a full tree of 2^depth leaves, every value a committed witness: start from W (the
+    leaf); for bit k of the index, k = 0 first, wrap (W P) when the bit is set - the sibling is the left child - and (P W) when it is clear.
+    -> (pattern, order): `order` says in which order the gadget consumes the witness values, as ("leaf", None) and ("sibling", k) with k the position in
+    MerkleTree.paths (0 = the leaf's own sibling).  The sponge digests the prover notes (Prover.noted, is_last) are the nodes of MerkleTree.path_nodes,
+    bottom up."""
+    pat, order = "W", [("leaf", None)]
+    for k in range(depth):
+        if (index >> k) & 1:
+            pat, order = hash_pattern("W", pat), [("sibling", k)] + order
+        else:
+            pat, order = hash_pattern(pat, "W"), order + [("sibling", k)]
+    return pat, order
+
+
 def merkle_full_tree(ctx, leaves=512, seed=None, label=b"MerkleTree", prover_cls=Prover):
     """cfg 4: MerkleTree256 over a full binary tree with every leaf a committed witness
     (reference src/merkle_tree/merkle_tree_gadget.rs:473-545: 512 leaves, n = 993,384, N = 2^20, m = 512).

@@ -39,6 +39,7 @@ typedef int32_t bpg_status;
 #define BPG_ERR_GADGET 6                      /* R1CSError::GadgetError        (reference src/cs_buffer.rs:100) */
 #define BPG_ERR_DEVICE 7
 #define BPG_ERR_INTERNAL 8
+#define BPG_ERR_CHECKPOINT_MISMATCH 9         /* bpg_r1cs_assign_checkpointed: a checkpoint value is not what the circuit computes */
 
 /* dialect flags of the proof encoding / transcript (the fork's revision is unpinned) */
 #define BPG_FLAG_COMPACT_1PHASE 1u            /* v2.0.0 encoding: version byte 0x00 + 11 points */
@@ -81,7 +82,7 @@ typedef struct {
 
 /* ---------------------------------------------------------------------------------------------------- PART 1: hot path */
 /* ABI version of this header.  Rules: structs the CALLER allocates either carry a struct_size (bpg_config: fields are only ever added at the end and
- * read when struct_size covers them) or are frozen (bpg_timings, bpg_r1cs_instance, bpg_batch_item, bpg_template_item, bpg_template_commit_item, bpg_witness_program, bpg_witness_hints, bpg_check_report, bpg_term, bpg_lc); a field never changes type or
+ * read when struct_size covers them) or are frozen (bpg_timings, bpg_r1cs_instance, bpg_batch_item, bpg_template_item, bpg_template_commit_item, bpg_witness_program, bpg_witness_hints, bpg_witness_checkpoints, bpg_check_report, bpg_term, bpg_lc); a field never changes type or
  * meaning.  BPG_ABI_VERSION grows when something a version-7 host relies on is extended (a new field, a new flag value); functions ADDED since
  * version 7 (bpg_r1cs_prove_batch, the circuit-template calls) did not raise it: a host that needs one looks the symbol up (dlsym) and treats its
  * absence as "not supported".  A host checks bpg_abi_version() >= the BPG_ABI_VERSION it was compiled against. */
@@ -267,6 +268,34 @@ typedef struct {                  /* frozen */
 } bpg_witness_hints;
 bpg_status bpg_r1cs_upload_template_hinted(bpg_ctx *ctx, const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, bpg_circuit **out);
 bpg_status bpg_r1cs_assign(bpg_ctx *ctx, bpg_circuit *c, uint64_t m, const uint8_t *v, uint64_t n_params, const uint8_t *param_values);
+/* CHECKPOINTS: known intermediate values flatten bpg_r1cs_assign.  (Additions to ABI version 7; no struct changes.)  The device runs one launch per level of
+ * dependent segments, and a hash chain - a preimage of many blocks, a Merkle path - is nothing but dependent segments.  Often the caller knows the values that
+ * link them: the sponge states of a preimage (bpg_mimc_sponge_states, microseconds per block on the host), the nodes of a resident tree
+ * (bpg_merkle_path_nodes, bpg_merkle_nodes).  The frozen struct bpg_witness_checkpoints names such values: an ordered list of distinct multiplier variables
+ * (kind 0, 1 or 2, index below n; bpg_prover_noted lists the candidates a gadget pointed out).  A checkpointed variable is computed like any other, but every term
+ * of the program that names it reads the caller's value: the segments stop depending on each other (a preimage: one level; a Merkle path or tree: two), and
+ * one more launch compares each value with what the circuit computed for it.
+ * bpg_r1cs_upload_template_checkpointed: checkpoints == NULL or n_checkpoints == 0 makes it bpg_r1cs_upload_template_hinted (same schedule, same program bits).
+ * Refused besides, before any device work, with BPG_ERR_INVALID_ARGUMENT and bpg_last_error naming the reason: NULL vars, an index >= n, a kind that is no
+ * multiplier kind (committed, One), a variable named twice.
+ * bpg_r1cs_assign_checkpointed: bpg_r1cs_assign plus the n_ck checkpoint values in the order of vars (32 bytes each, any value below 2^255, reduced mod l on
+ * the device as v is).  n_ck must match the template; ck_values non-NULL when n_ck > 0.  When every value is the circuit's own, the resident witness is
+ * exactly what bpg_r1cs_assign leaves on a template of the same circuit without checkpoints, and the call returns BPG_OK with *first_mismatch = UINT64_MAX.
+ * Otherwise it returns BPG_ERR_CHECKPOINT_MISMATCH, *first_mismatch (NULL allowed) is the lowest flat index item * n_ck + k that differs, bpg_last_error names
+ * it, and the circuit is left WITHOUT a witness (bpg_r1cs_prove_resident: BPG_ERR_MISSING_ASSIGNMENT) - an inconsistent witness is never provable.  Either way
+ * the equal-scalar sets of the previous witness are dropped, and the call returns synchronised: the host reads the 8-byte result of the comparison back.
+ * On a template with checkpoints: bpg_r1cs_template_repeat(K) gives a repeat whose bpg_r1cs_assign_checkpointed takes K x n_ck values, item-major; plain
+ * bpg_r1cs_assign, bpg_r1cs_prove_template_batch and bpg_r1cs_prove_template_batch_commit are refused with BPG_ERR_INVALID_ARGUMENT before any work (their
+ * frozen arguments carry no checkpoint values); bpg_r1cs_check, bpg_r1cs_prove_resident and bpg_r1cs_verify_resident serve it unchanged.  On a template
+ * without checkpoints bpg_r1cs_assign_checkpointed with n_ck = 0 is bpg_r1cs_assign. */
+typedef struct {                  /* frozen */
+    uint64_t n_checkpoints;
+    const uint32_t *vars;         /* kind << 29 | index: distinct multiplier variables (kind 0..2) */
+} bpg_witness_checkpoints;
+bpg_status bpg_r1cs_upload_template_checkpointed(bpg_ctx *ctx, const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                                 const bpg_witness_checkpoints *checkpoints, bpg_circuit **out);
+bpg_status bpg_r1cs_assign_checkpointed(bpg_ctx *ctx, bpg_circuit *c, uint64_t m, const uint8_t *v, uint64_t n_params, const uint8_t *param_values,
+                                        uint64_t n_ck, const uint8_t *ck_values /* n_ck x 32 */, uint64_t *first_mismatch);
 /* K fresh witnesses of ONE template proved in lockstep: bpg_r1cs_prove_batch without the host assembly and without the witness upload.  Each item brings
  * what bpg_r1cs_assign takes (v: m committed values, any value below 2^255; param_values: n_params constant terms in the order of param_rows) and what
  * bpg_r1cs_prove_resident takes (transcript state after every "V" append, m blindings, the seed, flags, the proof buffer).  proof_out, *proof_len,
@@ -342,6 +371,17 @@ bpg_status bpg_test_template_eval_hinted(const bpg_r1cs_instance *inst, const bp
                                          uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out);
 bpg_status bpg_test_template_eval_batch_hinted(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, uint64_t count,
                                                const uint8_t *v, uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out);
+/* The same hooks for a program with checkpoints (no device).  bpg_test_template_eval_checkpointed shows what one thread running the segments in order would hide -
+ * a term the packer did not redirect to the caller's value, which reads another lane of the same level: a_L, a_R, a_O start as a poison value, the segments of every
+ * level run in REVERSE order, then the comparison step; *first_mismatch as bpg_r1cs_assign_checkpointed reports it.  bpg_test_template_packed: the packed record
+ * stream (host/witness_record.hpp) - *words_out its length; cap = 0 only asks for the length. */
+bpg_status bpg_test_template_schedule_checkpointed(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                                   const bpg_witness_checkpoints *checkpoints, char *out, uint64_t cap);
+bpg_status bpg_test_template_eval_checkpointed(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                               const bpg_witness_checkpoints *checkpoints, const uint8_t *v, const uint8_t *ck_values,
+                                               uint8_t *aL, uint8_t *aR, uint8_t *aO, uint64_t *first_mismatch);
+bpg_status bpg_test_template_packed(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                    const bpg_witness_checkpoints *checkpoints, uint32_t *stream_out, uint64_t cap, uint64_t *words_out);
 bpg_status bpg_test_circuit_handle_hinted(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, bpg_circuit **out);
 /* A TEMPLATE REPEATED K TIMES ON THE DEVICE: one proof for K witnesses of one circuit shape.  bpg_r1cs_template_repeat makes a new resident TEMPLATE from a
  * template uploaded with bpg_r1cs_upload_template(_hinted): the circuit a host gets by assembling the template's gadget code `count` times in a row into ONE
@@ -515,6 +555,11 @@ bpg_status bpg_prover_witness_program(bpg_prover *p, bpg_witness_program *out);
  * bpg_prover_allocate_bit: ConstraintSystem::allocate_bit for hosts that drive the mirror directly - the multiplier range_proof makes for bit `bit` (0..255)
  * of `source`, whose assigned value is source_value (raw little-endian bytes, as range_proof reads them): a_L = 1 - b, a_R = b.  It adds no constraint. */
 bpg_status bpg_prover_witness_program_hinted(bpg_prover *p, bpg_witness_program *program_out, bpg_witness_hints *hints_out);
+/* Checkpoint candidates (bpg_witness_checkpoints).  A gadget that computes a value its caller may know anyway says so through ConstraintSystem::note_value;
+ * MimcHash256 - and MerkleTree256 through it - notes the sponge state after every absorbed block, tag = the block index, bit 31 set on the sponge's last block
+ * (its digest: a Merkle node).  A prover keeps the note when the value is exactly one multiplier variable; it costs no multiplier, constraint or transcript byte.
+ * bpg_prover_noted: *n_out = how many notes there are; the first min(cap, *n_out) go to vars_out / tags_out, in the order they were made. */
+bpg_status bpg_prover_noted(bpg_prover *p, uint32_t *vars_out, uint32_t *tags_out, uint64_t cap, uint64_t *n_out);
 bpg_status bpg_prover_allocate_bit(bpg_prover *p, const bpg_lc *source, uint32_t bit, const uint8_t source_value[32], uint32_t vars_out[3]);
 bpg_status bpg_prover_mark_param_row(bpg_prover *p, uint64_t row);
 /* Extension (no upstream counterpart; the proof bytes do not change): start drawing the blinding scalars of the coming prove() now.
@@ -629,6 +674,11 @@ bpg_status bpg_merkle_build(bpg_ctx *ctx, uint32_t depth, const uint8_t *leaves 
 bpg_status bpg_merkle_root(bpg_ctx *ctx, bpg_merkle *t, uint8_t out[32]);
 bpg_status bpg_merkle_nodes(bpg_ctx *ctx, bpg_merkle *t, uint32_t level, uint64_t first, uint64_t count, uint8_t *out);
 bpg_status bpg_merkle_paths(bpg_ctx *ctx, bpg_merkle *t, uint64_t count, const uint64_t *indices, uint8_t *siblings_out /* count x depth x 32 */);
+/* What a checkpointed template wants from these: bpg_mimc_sponge_states is bpg_mimc_sponge returning the state after EVERY block (out: n_blocks x 32; the last
+ * entry is the digest); bpg_merkle_path_nodes gives for each leaf index the `depth` nodes ON its path, from the leaf's parent upward, the root last - the same
+ * bytes bpg_merkle_nodes gives node by node - under the argument rules of bpg_merkle_paths. */
+bpg_status bpg_mimc_sponge_states(const uint8_t *blocks, uint64_t n_blocks, uint8_t *out /* n_blocks x 32 */);
+bpg_status bpg_merkle_path_nodes(bpg_ctx *ctx, bpg_merkle *t, uint64_t count, const uint64_t *indices, uint8_t *out /* count x depth x 32 */);
 bpg_status bpg_merkle_update(bpg_ctx *ctx, bpg_merkle *t, uint64_t count, const uint64_t *indices, const uint8_t *leaves /* count x 32 */);
 void bpg_merkle_free(bpg_ctx *ctx, bpg_merkle *t);
 /* test hook: `count` 64-byte TranscriptRng draws (merlin build_rng().rekey_with_witness_bytes("v_blinding")*.finalize(seed)), after
