@@ -92,12 +92,29 @@ class CheckReport:
         """on a repeat of a template of q_src constraints: `rows` as (copy, row of the source template) pairs"""
         return [(r // q_src, r % q_src) for r in self.rows]
 
+    def parts(self, layout):
+        """on a join (Context.join; layout = its .layout): `rows` as (part, item, row of the part's template) triples"""
+        return [_join_place(layout, r, "q") for r in self.rows]
+
+    def multiplier_part(self, layout):
+        """on a join: the first bad multiplier as (part, item, multiplier of the part's template); None when there is none"""
+        return None if self.first_bad_multiplier is None else _join_place(layout, self.first_bad_multiplier, "n")
+
     def __eq__(self, o):
         return isinstance(o, CheckReport) and self.__dict__ == o.__dict__
 
     def __repr__(self):
         return "CheckReport(bad_multipliers=%d, first_bad_multiplier=%r, bad_rows=%d, first_bad_row=%r, rows=%r)" % (
             self.bad_multipliers, self.first_bad_multiplier, self.bad_rows, self.first_bad_row, self.rows)
+
+
+def _join_place(layout, index, what):
+    """index of a joined circuit (what = "q": constraint row, "n": multiplier, "m": committed value, "n_params", "n_ck") -> (part, item, index in the part's template)"""
+    for p, part in enumerate(layout):
+        local = index - part["base_" + what]
+        if 0 <= local < part["count"] * part[what]:
+            return p, local // part[what], local % part[what]
+    raise IndexError("%s index %d is outside the join" % (what, index))
 
 
 class Timings(C.Structure):
@@ -671,6 +688,81 @@ def test_template_repeat_instance(inst, program, hints, count, param_values=None
     return row_ptr, tv[:nnz.value].copy(), tc[:nnz.value].copy(), coef.raw[:32 * nc.value]
 
 
+class TemplatePart(C.Structure):
+    """bpg_template_part (frozen): one part of bpg_r1cs_template_join."""
+    _fields_ = [("tmpl", C.c_void_p), ("count", C.c_uint64)]
+
+
+class TestJoinPart(C.Structure):
+    """bpg_test_join_part: one part of the join test hooks."""
+    _fields_ = [("inst", C.POINTER(R1CSInstance)), ("program", C.POINTER(WitnessProgramView)), ("hints", C.POINTER(WitnessHintsView)),
+                ("checkpoints", C.POINTER(WitnessCheckpointsView)), ("count", C.c_uint64)]
+
+
+def join_layout(dims):
+    """[(n, m, q, n_params, n_ck, count)] -> per part a dict of these and the five bases (base_n, base_m, base_q, base_n_params, base_n_ck): where the part's
+    first copy starts in the joined multipliers, committed values, constraint rows, parameters and checkpoints (include/bpg.h bpg_r1cs_template_join)"""
+    names = ("n", "m", "q", "n_params", "n_ck")
+    base, out = dict.fromkeys(names, 0), []
+    for d in dims:
+        part = dict(zip(names + ("count",), (int(x) for x in d)))
+        for k in names:
+            part["base_" + k] = base[k]
+            base[k] += part["count"] * part[k]
+        out.append(part)
+    return out
+
+
+def _test_join_parts(parts):
+    """[(inst, program, hints, count) or (inst, program, hints, count, checkpoint variables)] -> (bpg_test_join_part array, keep-alive, layout)"""
+    arr, keep, dims = (TestJoinPart * max(len(parts), 1))(), [], []
+    for k, part in enumerate(parts):
+        inst, program, hints, count = part[:4]
+        cks = list(part[4]) if len(part) > 4 and part[4] is not None else []
+        cs, cp = inst.cstruct(), program.cstruct()
+        ch = hints.cstruct() if hints is not None and len(hints) else None
+        ck = _checkpoints_cstruct(cks) if cks else None
+        keep.append((cs, cp, ch, ck))
+        arr[k].inst, arr[k].program, arr[k].count = C.pointer(cs), C.pointer(cp), count
+        if ch is not None:
+            arr[k].hints = C.pointer(ch)
+        if ck is not None:
+            arr[k].checkpoints = C.pointer(ck)
+        dims.append((inst.n, inst.m, inst.q, len(program.param_rows), len(cks), count))
+    return arr, keep, dims
+
+
+def test_template_join_instance(parts, param_values=None):
+    """bpg_test_template_join_instance (no device): the instance of the templates joined - parts = [(inst, program, hints, count[, checkpoints])] - row-major, as
+    it stands after an assign of param_values (the joined parameters in order; None: the constants of the templates' own rows) ->
+    (row_ptr, term_var, term_coef, coef bytes)"""
+    import numpy as np
+    arr, keep, dims = _test_join_parts(parts)
+    rows = sum(c * q for _, _, q, _, _, c in dims) + 1
+    terms = sum(part[3] * (part[0].nnz + len(part[1].param_rows)) for part in parts)
+    ncoef = sum(part[0].ncoef + part[3] * len(part[1].param_rows) for part in parts)
+    npar = sum(c * p for _, _, _, p, _, c in dims)
+    row_ptr, tv, tc, coef = np.zeros(rows, np.uint64), np.zeros(max(terms, 1), np.uint32), np.zeros(max(terms, 1), np.uint32), _buf(32 * ncoef)
+    nnz, nc = C.c_uint64(), C.c_uint64()
+    pv = None if param_values is None else _scalars32("param_values", param_values, npar)
+    _chk(lib().bpg_test_template_join_instance(C.c_uint64(len(parts)), arr, pv, C.c_void_p(row_ptr.ctypes.data), C.c_uint64(rows), C.c_void_p(tv.ctypes.data),
+                                               C.c_void_p(tc.ctypes.data), C.c_uint64(terms), coef, C.c_uint64(ncoef), C.byref(nnz), C.byref(nc)))
+    return row_ptr, tv[:nnz.value].copy(), tc[:nnz.value].copy(), coef.raw[:32 * nc.value]
+
+
+def test_template_eval_join(parts, values, ck_values=None):
+    """bpg_test_template_eval_join (no device): the join-layout witness interpreter compiled for the host (levels in order; parts, segments and items of a level
+    in reverse): the joined committed values (and checkpoint values) -> (a_L, a_R, a_O, first mismatching flat checkpoint index or None)"""
+    arr, keep, dims = _test_join_parts(parts)
+    n, m, nck = (sum(d[5] * d[i] for d in dims) for i in (0, 1, 4))
+    out = [_buf(32 * n) for _ in range(3)]
+    v = _scalars32("values", values, m)
+    ck = None if ck_values is None else _scalars32("ck_values", ck_values, nck)
+    first = C.c_uint64()
+    _chk(lib().bpg_test_template_eval_join(C.c_uint64(len(parts)), arr, v if v else None, ck if ck else None, *out, C.byref(first)))
+    return tuple(o.raw[:32 * n] for o in out) + (None if first.value == 2**64 - 1 else int(first.value),)
+
+
 def test_template_eval_repeat(inst, program, hints, count, values):
     """bpg_test_template_eval_repeat (no device): the repeat-layout witness interpreter compiled for the host: count x m committed values ->
     (a_L, a_R, a_O) of count x n scalars each"""
@@ -728,6 +820,29 @@ def _context_verify_batch(self, items, batch_seed=None, return_status=False):
 
 
 Context.verify_batch = _context_verify_batch
+
+
+def _context_join(self, parts):
+    """bpg_r1cs_template_join: parts = [(template, count)] -> ONE resident template that holds count_0 copies of part 0, then count_1 of part 1, ... - the
+    circuit of one host assembly of the parts' gadget code in that order, made on the device from the resident templates (a mixed statement, one proof).
+    .layout lists per part n, m, q, n_params, n_ck, count and the bases of its first copy (join_layout).  assign(values, params, checkpoints=) takes the
+    concatenated lists, part-major then item-major; CheckReport.parts(layout) maps the rows of check() back.  Independent of its sources."""
+    parts = [(t, int(c)) for t, c in parts]
+    arr = (TemplatePart * max(len(parts), 1))()
+    for k, (t, c) in enumerate(parts):
+        if c < 0 or c >= 2**64:
+            raise ValueError("count out of range")
+        arr[k].tmpl, arr[k].count = (t._h if t is not None else None), c
+    h = C.c_void_p()
+    _chk(lib().bpg_r1cs_template_join(self._h, C.c_uint64(len(parts)), arr, C.byref(h)))
+    layout = join_layout([(t.n, t.m, t.q or 0, t.n_params, t.n_ck, c) for t, c in parts])
+    tot = lambda k: sum(p["count"] * p[k] for p in layout)
+    res = ResidentCircuit(self, h, tot("n"), tot("m"), n_params=tot("n_params"), q=None if any(t.q is None for t, _ in parts) else tot("q"), n_ck=tot("n_ck"))
+    res.layout = layout
+    return res
+
+
+Context.join = _context_join
 
 
 def verify_batch(ctx, verifiers, proofs, bp_gens, seeds=None, flags=0, batch_seed=None):
@@ -840,6 +955,7 @@ class ResidentCircuit:
         self.n_ck = n_ck                    # checkpoint values assign() takes (a template uploaded with checkpoints; a repeat of one: count x as many)
         self.n_params = n_params            # None: a plain upload; a number: a circuit template (Prover.template / Context.upload_template)
         self.q = q                          # constraint rows (None: made by a caller that did not say)
+        self.layout = None                  # Context.join: the parts of the join and where each starts (join_layout)
 
     def assign(self, values, params=(), checkpoints=None):
         """bpg_r1cs_assign: a fresh witness for a circuit template - the m committed values (and the constant term of every parameter row); the device
@@ -862,6 +978,8 @@ class ResidentCircuit:
                 e = BpgError(st, lib().bpg_last_error().decode())
                 if st == ERR_CHECKPOINT_MISMATCH:
                     e.first_mismatch = int(first.value)
+                    if self.layout is not None:             # a join: (part, item, checkpoint of the part's template); the message names them too
+                        e.place = _join_place(self.layout, e.first_mismatch, "n_ck")
                 raise e
             return
         _chk(lib().bpg_r1cs_assign(self.ctx._h, self._h, C.c_uint64(self.m), v if self.m else None, C.c_uint64(len(pv) // 32), pv if pv else None))
@@ -869,7 +987,8 @@ class ResidentCircuit:
     def repeat(self, count) -> "ResidentCircuit":
         """bpg_r1cs_template_repeat: this template `count` times over as ONE resident template - the circuit of `count` host assemblies of the same gadget
         code in one prover, replicated on the device (item k at multipliers k n.., committed values k m.., parameters k n_params..).  assign() then takes
-        count x m values and count x n_params constants, item-major; one prove() gives one proof for all the items.  Independent of this template."""
+        count x m values and count x n_params constants, item-major; one prove() gives one proof for all the items.  Independent of this template.
+        Refused on a repeat and on a join (Context.join with larger counts is that circuit); check_batch, which repeats, with it."""
         h = C.c_void_p()
         _chk(lib().bpg_r1cs_template_repeat(self.ctx._h, self._h, C.c_uint64(count), C.byref(h)))
         return ResidentCircuit(self.ctx, h, count * self.n, count * self.m, n_params=count * self.n_params, q=None if self.q is None else count * self.q,

@@ -331,8 +331,14 @@ bpg_status bpg_r1cs_assign_checkpointed(bpg_ctx *ctx, bpg_circuit *c, uint64_t m
     if (st != BPG_OK || first == Engine::CHECKPOINTS_HOLD) return st;
     if (first_mismatch) *first_mismatch = first;
     const uint64_t per = Engine::checkpoints_per_item(c->dc);
-    g_last_error = "assign: checkpoint " + std::to_string(first % per) + (per != c->n_ck ? " of item " + std::to_string(first / per) : std::string()) +
-                   " (flat index " + std::to_string(first) + ") is not the value the circuit computes; the circuit holds no witness";
+    uint64_t jp = 0, ji = 0, jc = 0;
+    if (Engine::join_checkpoint_place(c->dc, first, &jp, &ji, &jc)) {     // a join: `per` is its total, no divisor
+        g_last_error = "assign: checkpoint " + std::to_string(jc) + " of item " + std::to_string(ji) + " of part " + std::to_string(jp) +
+                       " (flat index " + std::to_string(first) + ") is not the value the circuit computes; the circuit holds no witness";
+    } else {
+        g_last_error = "assign: checkpoint " + std::to_string(first % per) + (per != c->n_ck ? " of item " + std::to_string(first / per) : std::string()) +
+                       " (flat index " + std::to_string(first) + ") is not the value the circuit computes; the circuit holds no witness";
+    }
     return BPG_ERR_CHECKPOINT_MISMATCH;
 }
 bpg_status bpg_test_template_schedule(const bpg_r1cs_instance *inst, const bpg_witness_program *program, char *out, uint64_t cap) {
@@ -409,9 +415,72 @@ bpg_status bpg_r1cs_template_repeat(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t co
         if (count == 0) throw std::invalid_argument("template_repeat: count must be at least 1");
         if (!tmpl->is_template) throw std::invalid_argument("template_repeat: the circuit is not a template (bpg_r1cs_upload_template)");
         if (!tmpl->dc) throw std::invalid_argument("template_repeat: the handle has no device state (bpg_test_circuit_handle)");
+        if (Engine::is_join(tmpl->dc)) throw std::invalid_argument("template_repeat: the circuit is a join (join its parts with larger counts instead)");
         DeviceCircuit *dc = ctx->engine->repeat_template(tmpl->dc, count);          // count 0, a repeat, sizes: refused there, before any device work
         bpg_circuit *c = new bpg_circuit{dc, count * tmpl->n, count * tmpl->m}; c->is_template = true; c->n_params = count * tmpl->n_params; c->n_ck = count * tmpl->n_ck;
         *out = c;
+    });
+}
+bpg_status bpg_r1cs_template_join(bpg_ctx *ctx, uint64_t n_parts, const bpg_template_part *parts, bpg_circuit **out) {
+    return guard([&] {
+        REQUIRE(out); *out = nullptr;
+        REQUIRE(ctx && parts);
+        if (n_parts == 0) throw std::invalid_argument("template_join: no parts (n_parts must be at least 1)");
+        if (n_parts > 256) throw std::invalid_argument("template_join: too many parts (" + std::to_string(n_parts) + "; at most 256)");
+        std::vector<std::pair<DeviceCircuit *, uint64_t>> src;
+        for (uint64_t p = 0; p < n_parts; p++) {
+            const bpg_circuit *t = parts[p].tmpl;
+            const std::string at = "template_join: part " + std::to_string(p) + ": ";
+            if (!t) throw std::invalid_argument(at + "null template");
+            if (parts[p].count == 0) throw std::invalid_argument(at + "count must be at least 1");
+            if (!t->is_template) throw std::invalid_argument(at + "the circuit is not a template (bpg_r1cs_upload_template)");
+            if (!t->dc) throw std::invalid_argument(at + "the handle has no device state (bpg_test_circuit_handle)");
+            src.emplace_back(t->dc, parts[p].count);
+        }
+        DeviceCircuit *dc = ctx->engine->join_templates(src);                       // a repeat, a join, another device, sizes: refused there, before any device work
+        bpg_circuit *c = new bpg_circuit{dc, 0, 0}; c->is_template = true;
+        for (uint64_t p = 0; p < n_parts; p++) {
+            const bpg_circuit *t = parts[p].tmpl;
+            c->n += parts[p].count * t->n; c->m += parts[p].count * t->m; c->n_params += parts[p].count * t->n_params; c->n_ck += parts[p].count * t->n_ck;
+        }
+        *out = c;
+    });
+}
+static std::vector<Engine::JoinSource> join_sources(uint64_t n_parts, const bpg_test_join_part *parts) {
+    if (n_parts == 0) throw std::invalid_argument("template_join: no parts (n_parts must be at least 1)");
+    if (n_parts > 256) throw std::invalid_argument("template_join: too many parts (" + std::to_string(n_parts) + "; at most 256)");
+    std::vector<Engine::JoinSource> src;
+    for (uint64_t p = 0; p < n_parts; p++) {
+        if (!parts[p].inst || !parts[p].program) throw std::invalid_argument("template_join: part " + std::to_string(p) + ": null instance or program");
+        src.push_back({as_view(parts[p].inst, false), program_view(parts[p].program, parts[p].hints, parts[p].checkpoints), parts[p].count});
+    }
+    return src;
+}
+bpg_status bpg_test_template_join_instance(uint64_t n_parts, const bpg_test_join_part *parts, const uint8_t *param_values, uint64_t *row_ptr, uint64_t row_cap,
+                                           uint32_t *term_var, uint32_t *term_coef, uint64_t term_cap, uint8_t *coef, uint64_t coef_cap, uint64_t *nnz_out,
+                                           uint64_t *ncoef_out) {
+    return guard([&] {
+        REQUIRE(parts && row_ptr && nnz_out && ncoef_out);
+        const FlatCircuit f = Engine::template_join_instance_host(join_sources(n_parts, parts), param_values);
+        const uint64_t nnz = f.term_var.size(), ncoef = f.coef.size() / 32;
+        if (row_cap < f.row_ptr.size()) throw std::invalid_argument("template_join_instance: row_ptr too short (" + std::to_string(f.row_ptr.size()) + " entries needed)");
+        if (term_cap < nnz || (nnz && (!term_var || !term_coef))) throw std::invalid_argument("template_join_instance: term_var / term_coef too short (" + std::to_string(nnz) + " entries needed)");
+        if (coef_cap < ncoef || (ncoef && !coef)) throw std::invalid_argument("template_join_instance: coef too short (" + std::to_string(ncoef) + " scalars needed)");
+        std::memcpy(row_ptr, f.row_ptr.data(), f.row_ptr.size() * 8);
+        if (nnz) { std::memcpy(term_var, f.term_var.data(), nnz * 4); std::memcpy(term_coef, f.term_coef.data(), nnz * 4); }
+        if (ncoef) std::memcpy(coef, f.coef.data(), ncoef * 32);
+        *nnz_out = nnz; *ncoef_out = ncoef;
+    });
+}
+bpg_status bpg_test_template_eval_join(uint64_t n_parts, const bpg_test_join_part *parts, const uint8_t *v, const uint8_t *ck_values, uint8_t *aL,
+                                       uint8_t *aR, uint8_t *aO, uint64_t *first_mismatch) {
+    return guard([&] {
+        REQUIRE(parts && aL && aR && aO && first_mismatch);
+        const std::vector<Engine::JoinSource> src = join_sources(n_parts, parts);
+        uint64_t m = 0;
+        for (const Engine::JoinSource &s : src) m += s.c.m;
+        REQUIRE(m == 0 || v);
+        *first_mismatch = Engine::template_eval_join_host(src, v, ck_values, aL, aR, aO);
     });
 }
 bpg_status bpg_r1cs_check(bpg_ctx *ctx, bpg_circuit *c, uint64_t m, const uint8_t *v, uint64_t cap, uint64_t *rows_out, uint64_t *n_rows_out, bpg_check_report *report) {

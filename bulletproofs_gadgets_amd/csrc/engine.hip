@@ -179,6 +179,13 @@ struct DeviceCircuit {
     // a template repeated on the device (repeat_template, hip/k_repeat.cuh): rep_count copies of a source template of rep_n multipliers and rep_m committed
     // values, whose packed program (wit_stream, wit_segs, wit_level_ptr: copies of the source's) assign() walks once per (segment, item).  0: not a repeat.
     uint64_t rep_count = 0, rep_n = 0, rep_m = 0;
+    // templates joined on the device (join_templates, hip/k_join.cuh): the descriptors of the parts (host copy and device array), the parts' programs one after
+    // the other in wit_stream / wit_segs / wit_ck_var, and the block table of assign(): level l = blocks [join_level_ptr[l], join_level_ptr[l + 1]) of join_blocks.
+    // n_ck is the total over all parts and items.  No part: not a join.
+    std::vector<JoinPart> join_parts;
+    DevBuf join_desc, join_blocks;
+    std::vector<uint32_t> join_level_ptr;
+    int device = 0;                         // the device the buffers live on
     // row-major view of the matrix for check() (hip/k_check.cuh), derived from the column-major one at the first check and kept until the circuit is freed (the
     // matrix never changes; parameter values live in `coef`, which the view indexes): rv_ptr = q + 1 row starts, rv_ent = nnz pairs (column, coefficient slot),
     // rv_long = [count | the rows of more than rv_threshold terms].  Plain device memory: no part of the table budget.
@@ -195,6 +202,7 @@ struct DeviceCircuit {
     X(k_tt_bases) X(k_tt_multiples) X(k_tt_bases8) X(k_tt_multiples8) X(k_tt_round8) X(k_tt_factors) X(k_tt_advance) X(k_tt_round) X(k_tt_finish) X(k_blind_expand) X(k_tt_commit3) X(k_tt_commit3_finish) X(k_csc_count) X(k_csc_fill) X(k_csc_colptr) X(k_merge_insert) X(k_merge_plan) X(k_merge_groups) X(k_merge_members) X(k_merge_sum) \
     X(k_bt_commit3) X(k_bt_commit3_finish) X(k_bt_compress) X(k_bt_exp) X(k_bt_poly_t) X(k_bt_poly_eval) X(k_bt_factors) X(k_bt_advance) X(k_bt_round) \
     X(k_bt_finish) X(k_bt_fold_scalars) X(k_witness_eval) X(k_witness_eval_batch) X(k_bt_commit_v) X(k_repeat_colptr) X(k_repeat_entries) X(k_repeat_coef) X(k_witness_eval_repeat) X(k_witness_ck_verify) \
+    X(k_join_colptr) X(k_join_entries) X(k_join_coef) X(k_witness_eval_join) X(k_witness_ck_verify_join) \
     X(k_mimc_sponge) X(k_merkle_leaves) X(k_merkle_level) X(k_merkle_top) X(k_merkle_level_list) X(k_merkle_set_leaves) X(k_merkle_paths) X(k_merkle_export) \
     X(k_rowview_count) X(k_rowview_fill) X(k_rowview_long) X(k_check_mul) X(k_check_rows) X(k_check_rows_long) X(k_check_count)
 enum KernelId {
@@ -220,7 +228,7 @@ struct Engine::Impl {
     std::vector<ProfRec> prof_open;
     std::vector<Event> prof_pool;
     double prof_ms[KID_COUNT] = {0};
-    std::vector<float> prof_wit_ms;     // the first 1024 k_witness_eval / k_witness_eval_repeat launches since the last reset, in launch order (a launch = a level of an assign)
+    std::vector<float> prof_wit_ms;     // the first 1024 k_witness_eval / k_witness_eval_repeat / k_witness_eval_join launches since the last reset, in launch order (a launch = a level of an assign)
     std::vector<std::pair<int, float>> prof_merkle_ms;   // the first 512 launches of the tree-hashing kernels (k_merkle_level, _top, _level_list) since the last reset, in launch order
     uint64_t prof_count[KID_COUNT] = {0};
     double prof_alg_bytes[KID_COUNT] = {0}, prof_act_bytes[KID_COUNT] = {0}, prof_fm[KID_COUNT] = {0};
@@ -232,7 +240,7 @@ struct Engine::Impl {
     void prof_collect() {
         if (prof_open.empty()) return;
         HIPCHK(hipStreamSynchronize(st));
-        for (ProfRec &r : prof_open) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, r.a, r.b)); prof_ms[r.id] += ms; prof_count[r.id]++; if ((r.id == KID_k_witness_eval || r.id == KID_k_witness_eval_repeat) && prof_wit_ms.size() < 1024) prof_wit_ms.push_back(ms); if ((r.id == KID_k_merkle_level || r.id == KID_k_merkle_top || r.id == KID_k_merkle_level_list) && prof_merkle_ms.size() < 512) prof_merkle_ms.emplace_back(r.id, ms); prof_pool.push_back(std::move(r.a)); prof_pool.push_back(std::move(r.b)); }
+        for (ProfRec &r : prof_open) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, r.a, r.b)); prof_ms[r.id] += ms; prof_count[r.id]++; if ((r.id == KID_k_witness_eval || r.id == KID_k_witness_eval_repeat || r.id == KID_k_witness_eval_join) && prof_wit_ms.size() < 1024) prof_wit_ms.push_back(ms); if ((r.id == KID_k_merkle_level || r.id == KID_k_merkle_top || r.id == KID_k_merkle_level_list) && prof_merkle_ms.size() < 512) prof_merkle_ms.emplace_back(r.id, ms); prof_pool.push_back(std::move(r.a)); prof_pool.push_back(std::move(r.b)); }
         prof_open.clear();
     }
     void prof_reset() { prof_collect(); for (int i = 0; i < KID_COUNT; i++) { prof_ms[i] = 0; prof_count[i] = 0; prof_alg_bytes[i] = prof_act_bytes[i] = prof_fm[i] = 0; } prof_wit_ms.clear(); prof_merkle_ms.clear(); }
@@ -1163,6 +1171,7 @@ DeviceCircuit *Engine::upload(const FlatView &c) {
     // columns: [0,n) left, [n,2n) right, [2n,3n) output, [3n,3n+m) committed, 3n+m = the constant terms (only the verifier's w_c needs them)
     const uint64_t ncols = 3 * n + m + 1, nvar = ncols - 1;
     std::unique_ptr<DeviceCircuit> d(new DeviceCircuit());       // (the device is current: a failure below frees what it holds as it leaves)
+    d->device = device_;
     d->n = n; d->m = m; d->q = q; d->ncols = ncols; d->has_witness = has_witness;
     d->aL.ensure((n ? n : 1) * sizeof(scm)); d->aR.ensure((n ? n : 1) * sizeof(scm)); d->aO.ensure((n ? n : 1) * sizeof(scm));
     d->col_ptr.ensure((ncols + 1) * 8); d->ent_row.ensure((nnz ? nnz : 1) * 4); d->ent_coef.ensure((nnz ? nnz : 1) * 4);
@@ -1327,6 +1336,12 @@ uint64_t Engine::assign_checkpointed(DeviceCircuit *d, const uint8_t *v, const u
         HIPCHK(hipStreamSynchronize(I.st));                                     // small_sc is staged again below
     }
     const scm *ck = total_ck ? d->wit_ck.as<scm>() : nullptr;
+    // a join: ONE launch per level for all its parts (levels 0 .. the most any part has), that level's rows of the block table
+    for (size_t l = 0; l + 1 < d->join_level_ptr.size(); l++) {
+        const uint32_t b0 = d->join_level_ptr[l], nb = d->join_level_ptr[l + 1] - b0;
+        BPG_LAUNCH(I, k_witness_eval_join, dim3(nb), dim3(64), d->join_blocks.as<uint4>() + b0, d->join_desc.as<JoinPart>(), d->wit_segs.as<uint4>(),
+                   d->wit_stream.as<uint32_t>(), d->coef.as<scm>(), d->wit_v.as<scm>(), ck, d->aL.as<scm>(), d->aR.as<scm>(), d->aO.as<scm>());
+    }
     // a level's lanes are few (a 512-leaf tree: at most 256): spread them over waves until every SIMD of the device has one
     for (size_t l = 0; l + 1 < d->wit_level_ptr.size(); l++) {
         const uint32_t s0 = d->wit_level_ptr[l], ns = d->wit_level_ptr[l + 1] - s0;
@@ -1346,8 +1361,12 @@ uint64_t Engine::assign_checkpointed(DeviceCircuit *d, const uint8_t *v, const u
         I.ck_first.ensure(8);
         static const uint64_t kHold = CHECKPOINTS_HOLD;
         HIPCHK(hipMemcpyAsync(I.ck_first.p, &kHold, 8, hipMemcpyHostToDevice, I.st));
-        BPG_LAUNCH(I, k_witness_ck_verify, dim3(cdiv(total_ck, 256)), dim3(256), d->wit_ck_var.as<uint32_t>(), (uint32_t)d->n_ck, total_ck,
-                   (uint32_t)(d->rep_count ? d->rep_n : d->n), ck, d->aL.as<scm>(), d->aR.as<scm>(), d->aO.as<scm>(), I.ck_first.as<unsigned long long>());
+        if (!d->join_parts.empty())
+            BPG_LAUNCH(I, k_witness_ck_verify_join, dim3(cdiv(total_ck, 256)), dim3(256), d->wit_ck_var.as<uint32_t>(), d->join_desc.as<JoinPart>(),
+                       (uint32_t)d->join_parts.size(), total_ck, ck, d->aL.as<scm>(), d->aR.as<scm>(), d->aO.as<scm>(), I.ck_first.as<unsigned long long>());
+        else
+            BPG_LAUNCH(I, k_witness_ck_verify, dim3(cdiv(total_ck, 256)), dim3(256), d->wit_ck_var.as<uint32_t>(), (uint32_t)d->n_ck, total_ck,
+                       (uint32_t)(d->rep_count ? d->rep_n : d->n), ck, d->aL.as<scm>(), d->aR.as<scm>(), d->aO.as<scm>(), I.ck_first.as<unsigned long long>());
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(&first, I.ck_first.p, 8, hipMemcpyDeviceToHost, I.st));
     }
@@ -1531,6 +1550,222 @@ void Engine::template_eval_repeat_host(const FlatView &c, const WitnessProgramVi
                 witness_eval_repeat_lane(P.segs[s].first, P.segs[s].count, P.stream.data() + P.segs[s].stream, coef.data(), vv.data(), (uint32_t)c.n, (uint32_t)c.m, k,
                                          aL.data(), aR.data(), aO.data());
     scalars_to_bytes(aL, aL_out); scalars_to_bytes(aR, aR_out); scalars_to_bytes(aO, aO_out);
+}
+
+// ------------------------------------------------------------------------------------------------ templates joined on the device (hip/k_join.cuh)
+namespace {
+// The refusals every road to a join shares: parts holds (n, m, q, shared, n_params, n_ck, count) and sec[5] = the terms of each part's template.  The totals
+// stay inside what the instance format and the device layout hold (check_repeat_sizes, summed over the parts).
+void check_join_sizes(const std::vector<JoinPart> &parts) {
+    if (parts.empty()) throw std::invalid_argument("template_join: no parts (n_parts must be at least 1)");
+    if (parts.size() > 256) throw std::invalid_argument("template_join: too many parts (" + std::to_string(parts.size()) + "; at most 256)");
+    uint64_t n = 0, m = 0, q = 0, nnz = 0, cols = 0, coefs = 0, ck = 0;
+    // total + count * a stays below limit
+    auto add = [](uint64_t &total, uint64_t a, uint64_t count, uint64_t limit) { if (a && count > (limit - 1 - total) / a) return false; total += count * a; return true; };
+    for (size_t p = 0; p < parts.size(); p++) {
+        const JoinPart &P = parts[p];
+        const std::string at = "template_join: part " + std::to_string(p) + ": ";
+        if (P.count == 0) throw std::invalid_argument(at + "count must be at least 1");
+        if (!add(n, P.n, P.count, 1ull << 27)) throw std::invalid_argument(at + "the joined multipliers are too many (below 2^27)");
+        if (!add(m, P.m, P.count, 1ull << 29)) throw std::invalid_argument(at + "the joined committed values exceed the 29-bit variable index");
+        if (!add(q, P.q, P.count, 1ull << 32)) throw std::invalid_argument(at + "the joined constraints are too many (below 2^32)");
+        if (!add(nnz, P.sec[5], P.count, 1ull << 32)) throw std::invalid_argument(at + "the joined terms are too many (below 2^32)");
+        if (!add(cols, 3 * (uint64_t)P.n + P.m, P.count, (1ull << 32) - 1)) throw std::invalid_argument(at + "the joined circuit has too many columns");
+        if (!add(coefs, P.shared, 1, (uint64_t)WIT_COEF_INDEX_MASK + 1) || !add(coefs, P.n_params, P.count, (uint64_t)WIT_COEF_INDEX_MASK + 1))
+            throw std::invalid_argument(at + "the joined coefficient slots are too many");
+        if (!add(ck, P.n_ck, P.count, 1ull << 32)) throw std::invalid_argument(at + "the joined checkpoints are too many (below 2^32)");
+    }
+}
+// the block table of a join's assign(): per level, per part that has the level, per segment of it, a block for every 64 items - (part, segment in the joined
+// list, first item, -).  levels[p]: the part's wit_level_ptr.
+void join_block_table(const std::vector<JoinPart> &parts, const std::vector<const std::vector<uint32_t> *> &levels, std::vector<uint32_t> &table, std::vector<uint32_t> &level_ptr) {
+    size_t nlev = 0;
+    for (const auto *lp : levels) nlev = std::max(nlev, lp->empty() ? (size_t)0 : lp->size() - 1);
+    table.clear(); level_ptr.assign(1, 0);
+    for (size_t l = 0; l < nlev; l++) {
+        for (size_t p = 0; p < parts.size(); p++) {
+            const std::vector<uint32_t> &lp = *levels[p];
+            if (l + 1 >= lp.size()) continue;
+            for (uint32_t s = lp[l]; s < lp[l + 1]; s++)
+                for (uint64_t first = 0; first < parts[p].count; first += 64) { table.push_back((uint32_t)p); table.push_back(parts[p].seg_first + s); table.push_back((uint32_t)first); table.push_back(0); }
+        }
+        if (table.size() / 4 >= (1ull << 31)) throw std::invalid_argument("template_join: too many (segment, 64 items) blocks in one assign");
+        level_ptr.push_back((uint32_t)(table.size() / 4));
+    }
+}
+}  // namespace
+
+DeviceCircuit *Engine::join_templates(const std::vector<std::pair<DeviceCircuit *, uint64_t>> &src) {
+    // every refusal first: nothing below this block runs for a refused call
+    if (src.empty()) throw std::invalid_argument("template_join: no parts (n_parts must be at least 1)");
+    if (src.size() > 256) throw std::invalid_argument("template_join: too many parts (" + std::to_string(src.size()) + "; at most 256)");
+    std::vector<JoinPart> parts(src.size());
+    for (size_t p = 0; p < src.size(); p++) {
+        const DeviceCircuit *s = src[p].first;
+        const std::string at = "template_join: part " + std::to_string(p) + ": ";
+        if (!s) throw std::invalid_argument(at + "no circuit");
+        if (src[p].second == 0) throw std::invalid_argument(at + "count must be at least 1");
+        if (!s->is_template) throw std::invalid_argument(at + "the circuit is not a template (bpg_r1cs_upload_template)");
+        if (s->rep_count) throw std::invalid_argument(at + "the circuit is itself a repeat (name the template it was made from and a count)");
+        if (!s->join_parts.empty()) throw std::invalid_argument(at + "the circuit is itself a join (name its parts instead)");
+        if (s->device != device_) throw std::invalid_argument(at + "the circuit lives on the device of another context");
+        if (src[p].second >= (1ull << 32)) throw std::invalid_argument(at + "the joined multipliers are too many (below 2^27)");
+        JoinPart &P = parts[p];
+        std::memset(&P, 0, sizeof P);
+        P.n = (uint32_t)s->n; P.m = (uint32_t)s->m; P.q = (uint32_t)s->q; P.shared = (uint32_t)s->param_first; P.n_params = (uint32_t)s->n_params;
+        P.n_ck = (uint32_t)s->n_ck; P.count = (uint32_t)src[p].second;
+        P.sec[4] = s->const_begin; P.sec[5] = s->nnz;
+    }
+    check_join_sizes(parts);
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    // the sections of every part's entry list: three column pointers each (the constants column's start and the total are known here)
+    for (size_t p = 0; p < parts.size(); p++)
+        for (uint32_t k = 1; k <= 3; k++)
+            HIPCHK(hipMemcpyAsync(&parts[p].sec[k], src[p].first->col_ptr.as<uint64_t>() + (size_t)k * parts[p].n, 8, hipMemcpyDeviceToHost, I.st));
+    HIPCHK(hipStreamSynchronize(I.st));
+    const JoinTotals T = join_fill_bases(parts.data(), parts.size());
+    uint64_t nsegs = 0, nwords = 0, nckv = 0;
+    std::vector<const std::vector<uint32_t> *> levels;
+    for (size_t p = 0; p < parts.size(); p++) {
+        parts[p].seg_first = (uint32_t)nsegs; parts[p].stream_first = (uint32_t)nwords; parts[p].ck_var_first = (uint32_t)nckv;
+        nsegs += src[p].first->wit_segs.cap / sizeof(WitnessSegment); nwords += src[p].first->wit_stream.cap / 4; nckv += parts[p].n_ck;
+        levels.push_back(&src[p].first->wit_level_ptr);
+    }
+    if (nsegs >= (1ull << 32) || nwords >= (1ull << 32)) throw std::invalid_argument("template_join: the parts' witness programs are too long together");
+    std::unique_ptr<DeviceCircuit> d(new DeviceCircuit());
+    std::vector<uint32_t> table;
+    join_block_table(parts, levels, table, d->join_level_ptr);
+    const uint64_t n = T.n, m = T.m, nnz = T.nnz, ncols = 3 * n + m + 1, ncoef = T.shared + T.n_params;
+    d->device = device_;
+    d->n = n; d->m = m; d->q = T.q; d->ncols = ncols; d->nnz = nnz; d->const_begin = parts[0].sec_base[4]; d->has_witness = false;
+    d->is_template = true; d->n_params = T.n_params; d->param_first = T.shared; d->n_ck = T.n_ck;
+    d->aL.ensure((n ? n : 1) * sizeof(scm)); d->aR.ensure((n ? n : 1) * sizeof(scm)); d->aO.ensure((n ? n : 1) * sizeof(scm));
+    d->col_ptr.ensure((ncols + 1) * 8); d->ent_row.ensure((nnz ? nnz : 1) * 4); d->ent_coef.ensure((nnz ? nnz : 1) * 4);
+    d->coef.ensure((ncoef ? ncoef : 1) * sizeof(scm));
+    d->wit_stream.ensure((nwords ? nwords : 1) * 4); d->wit_segs.ensure((nsegs ? nsegs : 1) * sizeof(WitnessSegment)); d->wit_v.ensure((m ? m : 1) * sizeof(scm));
+    if (T.n_ck) { d->wit_ck_var.ensure(nckv * 4); d->wit_ck.ensure(T.n_ck * sizeof(scm)); }
+    d->join_desc.ensure(parts.size() * sizeof(JoinPart)); d->join_blocks.ensure((table.empty() ? 4 : table.size()) * 4);
+    I.h2d(d->join_desc.p, parts.data(), parts.size() * sizeof(JoinPart));
+    if (!table.empty()) I.h2d(d->join_blocks.p, table.data(), table.size() * 4);
+    const JoinPart *desc = d->join_desc.as<JoinPart>();
+    for (size_t p = 0; p < parts.size(); p++) {
+        const DeviceCircuit *s = src[p].first;
+        const JoinPart &P = parts[p];
+        if (s->wit_stream.cap) HIPCHK(hipMemcpyAsync(d->wit_stream.as<uint32_t>() + P.stream_first, s->wit_stream.p, s->wit_stream.cap, hipMemcpyDeviceToDevice, I.st));
+        if (s->wit_segs.cap) HIPCHK(hipMemcpyAsync(d->wit_segs.as<WitnessSegment>() + P.seg_first, s->wit_segs.p, s->wit_segs.cap, hipMemcpyDeviceToDevice, I.st));
+        if (P.n_ck) HIPCHK(hipMemcpyAsync(d->wit_ck_var.as<uint32_t>() + P.ck_var_first, s->wit_ck_var.p, (size_t)P.n_ck * 4, hipMemcpyDeviceToDevice, I.st));
+        const uint32_t gy = std::min<uint32_t>(P.count, 1024);              // copies beyond the grid's y extent are a loop in the kernels
+        BPG_LAUNCH(I, k_join_colptr, dim3(cdiv(3 * s->n + s->m + 1, 256), gy), dim3(256), s->col_ptr.as<uint64_t>(), desc, (uint32_t)p, (uint32_t)n, (uint32_t)m, nnz,
+                   d->col_ptr.as<uint64_t>());
+        if (s->nnz) BPG_LAUNCH(I, k_join_entries, dim3(cdiv(s->nnz, 256), gy), dim3(256), s->ent_row.as<uint32_t>(), s->ent_coef.as<uint32_t>(), desc, (uint32_t)p,
+                               d->ent_row.as<uint32_t>(), d->ent_coef.as<uint32_t>());
+        const uint64_t pc = (uint64_t)P.shared + (uint64_t)P.count * P.n_params;
+        if (pc) BPG_LAUNCH(I, k_join_coef, dim3(cdiv(pc, 256)), dim3(256), s->coef.as<scm>(), desc, (uint32_t)p, d->coef.as<scm>());
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(I.st));
+    d->join_parts = std::move(parts);
+    return d.release();
+}
+bool Engine::is_join(const DeviceCircuit *d) { return d && !d->join_parts.empty(); }
+bool Engine::join_checkpoint_place(const DeviceCircuit *d, uint64_t flat, uint64_t *part, uint64_t *item, uint64_t *ck) {
+    if (!is_join(d) || flat >= d->n_ck) return false;
+    uint32_t p, i, c;
+    join_ck_place(d->join_parts.data(), (uint32_t)d->join_parts.size(), flat, p, i, c);
+    *part = p; *item = i; *ck = c;
+    return true;
+}
+
+namespace {
+// the parts of a join as the host hooks get them: every part's plan, and the descriptors with their bases (no sections: the hooks work on rows)
+struct HostJoin { std::vector<TemplatePlan> plans; std::vector<JoinPart> parts; JoinTotals T; };
+HostJoin plan_join(const std::vector<Engine::JoinSource> &src) {
+    HostJoin J;
+    if (src.empty()) throw std::invalid_argument("template_join: no parts (n_parts must be at least 1)");
+    if (src.size() > 256) throw std::invalid_argument("template_join: too many parts (" + std::to_string(src.size()) + "; at most 256)");
+    J.parts.resize(src.size());
+    for (size_t p = 0; p < src.size(); p++) {
+        if (src[p].count == 0 || src[p].count >= (1ull << 32))
+            throw std::invalid_argument("template_join: part " + std::to_string(p) + (src[p].count ? ": the joined multipliers are too many (below 2^27)" : ": count must be at least 1"));
+        J.plans.push_back(Engine::plan_template(src[p].c, src[p].p));
+        const TemplatePlan &T = J.plans.back();
+        JoinPart &P = J.parts[p];
+        std::memset(&P, 0, sizeof P);
+        P.n = (uint32_t)T.slotted.n; P.m = (uint32_t)T.slotted.m; P.q = (uint32_t)(T.slotted.row_ptr.size() - 1); P.shared = (uint32_t)T.param_first;
+        P.n_params = (uint32_t)T.n_params; P.n_ck = (uint32_t)T.ck_var.size(); P.count = (uint32_t)src[p].count;
+        P.sec[5] = T.slotted.term_var.size();
+    }
+    check_join_sizes(J.parts);
+    J.T = join_fill_bases(J.parts.data(), J.parts.size());
+    return J;
+}
+}  // namespace
+// TEST HOOK (bpg_test_template_join_instance): the joined instance, row-major - what k_join_* leave in HBM - as it stands after an assign of param_values (the
+// joined slots' values in order; null: every slot keeps the constant its part's rows carried)
+FlatCircuit Engine::template_join_instance_host(const std::vector<JoinSource> &src, const uint8_t *param_values) {
+    const HostJoin J = plan_join(src);
+    FlatCircuit f; f.n = J.T.n; f.m = J.T.m;
+    f.row_ptr.reserve(J.T.q + 1); f.term_var.reserve(J.T.nnz); f.term_coef.reserve(J.T.nnz);
+    f.coef.assign(32 * (J.T.shared + J.T.n_params), 0);
+    for (size_t p = 0; p < J.parts.size(); p++) {
+        const FlatCircuit &s = J.plans[p].slotted;
+        const JoinPart &P = J.parts[p];
+        for (uint64_t k = 0; k < P.count; k++)
+            for (uint64_t r = 0; r < P.q; r++) {
+                for (uint64_t t = s.row_ptr[r]; t < s.row_ptr[r + 1]; t++) {
+                    uint32_t var, coef, row;
+                    join_map(J.parts.data(), (uint32_t)p, (uint32_t)k, s.term_var[t], s.term_coef[t], (uint32_t)r, var, coef, row);
+                    if (row + 1 != f.row_ptr.size()) throw std::logic_error("template_join: row map out of step");
+                    f.term_var.push_back(var); f.term_coef.push_back(coef);
+                }
+                f.row_ptr.push_back(f.term_var.size());
+            }
+        std::memcpy(&f.coef[32 * (size_t)P.base_shared], s.coef.data(), 32 * (size_t)P.shared);
+        for (uint64_t k = 0; k < P.count; k++)
+            if (P.n_params) std::memcpy(&f.coef[32 * ((size_t)P.base_slot + k * P.n_params)], s.coef.data() + 32 * (size_t)P.shared, 32 * (size_t)P.n_params);
+    }
+    if (param_values)
+        for (uint64_t i = 0; i < J.T.n_params; i++) Scalar::from_bytes_mod_order(param_values + 32 * i).to_bytes(&f.coef[32 * (J.T.shared + i)]);
+    return f;
+}
+// TEST HOOK (bpg_test_template_eval_join): k_witness_eval_join and k_witness_ck_verify_join on the host, in the order that shows what in-order execution
+// hides - poisoned vectors, the levels in order and within a level the parts and their segments in REVERSE order, then the verify step; returns the first
+// mismatch.  v: the joined committed values; ck_values: the joined checkpoint values (null when no part has any)
+uint64_t Engine::template_eval_join_host(const std::vector<JoinSource> &src, const uint8_t *v, const uint8_t *ck_values, uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out) {
+    const HostJoin J = plan_join(src);
+    if (J.T.n_ck && !ck_values) throw std::invalid_argument("template_eval_join: a part has checkpoints and no values were given for them");
+    std::vector<scm> coef(J.T.shared ? J.T.shared : 1);
+    size_t nlev = 0;
+    for (size_t p = 0; p < J.parts.size(); p++) {
+        const std::vector<scm> c = scalars_from_bytes(src[p].c.coef, J.parts[p].shared);
+        std::copy(c.begin(), c.begin() + J.parts[p].shared, coef.begin() + J.parts[p].base_shared);
+        nlev = std::max(nlev, J.plans[p].schedule.level_ptr.size() - 1);
+    }
+    const std::vector<scm> vv = scalars_from_bytes(v, J.T.m), ck = scalars_from_bytes(ck_values, J.T.n_ck);
+    static const uint8_t kPoison[32] = {0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a,
+                                        0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x0a};
+    const scm poison = scalars_from_bytes(kPoison, 1)[0];
+    std::vector<scm> aL(J.T.n, poison), aR(J.T.n, poison), aO(J.T.n, poison);
+    for (size_t l = 0; l < nlev; l++)
+        for (size_t p = J.parts.size(); p-- > 0;) {
+            const std::vector<uint32_t> &lp = J.plans[p].schedule.level_ptr;
+            const PackedWitnessProgram &P = J.plans[p].packed;
+            if (l + 1 >= lp.size()) continue;
+            for (uint32_t s = lp[l + 1]; s-- > lp[l];)
+                for (uint64_t k = J.parts[p].count; k-- > 0;)
+                    witness_eval_join_lane(J.parts[p], P.segs[s].first, P.segs[s].count, P.stream.data() + P.segs[s].stream, coef.data(), vv.data(), k,
+                                           aL.data(), aR.data(), aO.data(), J.T.n_ck ? ck.data() : nullptr);
+        }
+    uint64_t first = CHECKPOINTS_HOLD;
+    for (uint64_t t = J.T.n_ck; t-- > 0;) {
+        uint32_t p, item, c;
+        join_ck_place(J.parts.data(), (uint32_t)J.parts.size(), t, p, item, c);
+        const size_t b = (size_t)J.parts[p].base_n + (size_t)item * J.parts[p].n;
+        if (!witness_ck_holds(J.plans[p].ck_var[c], ck[t], aL.data() + b, aR.data() + b, aO.data() + b)) first = t;
+    }
+    scalars_to_bytes(aL, aL_out); scalars_to_bytes(aR, aR_out); scalars_to_bytes(aO, aO_out);
+    return first;
 }
 
 // ------------------------------------------------------------------------------------------------ equal-scalar merging of A_I, A_O (hip/k_merge.cuh)

@@ -3,6 +3,7 @@
 #pragma once
 #include <cstdint>
 #include <string>
+#include <utility>
 #include <vector>
 #include "host/scalar.hpp"
 #include "host/merlin.hpp"
@@ -121,6 +122,20 @@ public:
     // (k_witness_eval_repeat) compiled for the host; no device
     static FlatCircuit template_repeat_instance_host(const FlatView &c, const WitnessProgramView &p, uint64_t count, const uint8_t *param_values);
     static void template_eval_repeat_host(const FlatView &c, const WitnessProgramView &p, uint64_t count, const uint8_t *v, uint8_t *aL, uint8_t *aR, uint8_t *aO);
+    // Templates joined (include/bpg.h bpg_r1cs_template_join; hip/k_join.cuh): a new resident template that holds count_0 copies of part 0, then count_1 of part 1,
+    // and so on - the circuit of ONE host assembly of the parts' gadget code in that order - built on the device from the parts' resident matrices.  It owns copies
+    // of all it needs, holds no witness and no host rows; assign() evaluates every part's program in ONE launch per level (the most levels any part has).
+    // Refused (std::invalid_argument that names the part, before any device work): no part or more than 256, a null part, count 0, not a template, a repeat or a
+    // join, a part on another device, totals beyond the instance format.
+    DeviceCircuit *join_templates(const std::vector<std::pair<DeviceCircuit *, uint64_t>> &parts);
+    static bool is_join(const DeviceCircuit *c);
+    // flat index of the joined checkpoint list -> (part, item, checkpoint of the part's template); false: not a join, or no such index
+    static bool join_checkpoint_place(const DeviceCircuit *c, uint64_t flat, uint64_t *part, uint64_t *item, uint64_t *ck);
+    // test hooks (bpg_test_template_join_instance, bpg_test_template_eval_join): the joined rows as k_join_* leave them, and the join-layout interpreter
+    // (k_witness_eval_join, k_witness_ck_verify_join) compiled for the host; no device
+    struct JoinSource { FlatView c; WitnessProgramView p; uint64_t count; };
+    static FlatCircuit template_join_instance_host(const std::vector<JoinSource> &parts, const uint8_t *param_values);
+    static uint64_t template_eval_join_host(const std::vector<JoinSource> &parts, const uint8_t *v, const uint8_t *ck_values, uint8_t *aL, uint8_t *aR, uint8_t *aO);
     // Prover::prove on a resident circuit. transcript: state after Prover::new + every "V" append (updated in place).
     std::vector<uint8_t> prove(DeviceCircuit *c, Transcript &transcript, const std::vector<Scalar> &v_blinding,
                                const uint8_t rng_seed[32], uint32_t flags, ProveTimings *timings = nullptr);

@@ -27,6 +27,9 @@
 //                                       k_witness_ck_verify: after a checkpointed assign, the caller's intermediate values against the computed ones, a lane per checkpoint
 //       a template repeated K times      (k_repeat.cuh) k_repeat_colptr, k_repeat_entries, k_repeat_coef: the K-fold circuit's column-major matrix from the template's
 //                                       resident one; k_witness_eval_repeat: its witness by the template's program, a lane per (segment, item) (one proof for K witnesses)
+//       templates joined                 (k_join.cuh) k_join_colptr, k_join_entries, k_join_coef: the matrix of count_0 copies of part 0, then count_1 of part 1, ... from the
+//                                       parts' resident ones; k_witness_eval_join: one launch per level for ALL parts, a block = 64 items of one segment of one part;
+//                                       k_witness_ck_verify_join: the checkpoints of all parts in one launch (one proof for a mixed statement)
 //       MiMC sponges, Merkle trees       (k_mimc.cuh; no row of the survey: the native hash in front of Prover::commit) k_mimc_sponge: one lane per item; a tree of 2^d leaves in
 //                                       one heap-ordered array: k_merkle_leaves, k_merkle_level (one launch per level, one lane per parent), k_merkle_top (the levels of at
 //                                       most 256 parents in one launch), k_merkle_level_list + k_merkle_set_leaves (leaf updates: the ancestors only), k_merkle_paths
@@ -35,7 +38,7 @@
 //                                       matrix, once per circuit: k_rowview_count, k_scan_blocksums / _apply, k_rowview_fill, k_rowview_long; per check: k_check_mul (a lane
 //                                       per multiplier), k_check_rows (a lane per short row, the wave's ballot = one word of the violation bitmap), k_check_rows_long (a
 //                                       wave per long row), k_check_count (bad rows and the first of them)
-// The kernels live in k_points.cuh, k_scalars.cuh, k_ipa.cuh, k_verify.cuh, k_msm.cuh, k_merge.cuh, k_batch.cuh, k_witness.cuh, k_repeat.cuh, k_mimc.cuh and k_check.cuh, included at the end of
+// The kernels live in k_points.cuh, k_scalars.cuh, k_ipa.cuh, k_verify.cuh, k_msm.cuh, k_merge.cuh, k_batch.cuh, k_witness.cuh, k_repeat.cuh, k_join.cuh, k_mimc.cuh and k_check.cuh, included at the end of
 // this file in that order.
 // Data layout in HBM: scalars = 8 x u32 Montgomery form, 32 B each, AoS (lane i <-> element i: 2 x 16 B coalesced
 // loads); generator tables = affine Niels (y+x, y-x, 2dxy), 96 B per point, G at [0,N) and H at [N,2N); window tables =
@@ -82,5 +85,6 @@ __device__ __forceinline__ uint32_t msm_point_index(const MsmSegs &S, uint32_t s
 #include "k_batch.cuh"
 #include "k_witness.cuh"
 #include "k_repeat.cuh"
+#include "k_join.cuh"
 #include "k_mimc.cuh"
 #include "k_check.cuh"

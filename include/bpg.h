@@ -397,7 +397,8 @@ bpg_status bpg_test_circuit_handle_hinted(const bpg_r1cs_instance *inst, const b
  * first, the two are used independently - and keeps no host copy of its rows: bpg_r1cs_prove_template_batch(_commit) prove its items one at a time.
  * The caller makes the count m commitments itself (one bpg_pedersen_commit launch) and appends them to the transcript in item order.
  * Refused with BPG_ERR_INVALID_ARGUMENT before any device work (bpg_last_error names the reason): a NULL ctx, tmpl or out; count == 0; a circuit that
- * is not a template; a handle without device state (bpg_test_circuit_handle); a circuit that is itself a repeat; count n >= 2^27, count m >= 2^29,
+ * is not a template; a handle without device state (bpg_test_circuit_handle); a circuit that is itself a repeat or a join (bpg_r1cs_template_join: join
+ * its parts with larger counts instead); count n >= 2^27, count m >= 2^29,
  * count q or count nnz >= 2^32, 3 count n + count m + 1 >= 2^32, or 2^30 and more coefficient slots.  The generator capacity is checked when the repeat
  * is proved or verified, as for every circuit.  (An addition to ABI version 7: look the symbol up.) */
 bpg_status bpg_r1cs_template_repeat(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, bpg_circuit **out);
@@ -412,6 +413,42 @@ bpg_status bpg_test_template_repeat_instance(const bpg_r1cs_instance *inst, cons
                                              uint64_t term_cap, uint8_t *coef, uint64_t coef_cap, uint64_t *nnz_out, uint64_t *ncoef_out);
 bpg_status bpg_test_template_eval_repeat(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, uint64_t count,
                                          const uint8_t *v, uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out);
+/* TEMPLATES JOINED ON THE DEVICE: one proof for a mixed statement - "these k1 values are in range AND these k2 leaves are in the tree AND this preimage
+ * hashes to that image".  bpg_r1cs_template_join makes a new resident TEMPLATE from n_parts pairs (template, count): the circuit a host gets by assembling, in
+ * ONE prover, part 0's gadget code count_0 times, then part 1's count_1 times, and so on, each time with fresh variables.  bpg_r1cs_template_repeat(K) is the
+ * join of one part.  Write n_p, m_p, q_p, n_params_p, n_ck_p, K_p for part p and B^x_p for the sum of K x over the parts before p.  Copy k of part p:
+ * multiplier i -> B^n_p + k n_p + i, committed value j -> B^m_p + k m_p + j, constraint row r -> B^q_p + k q_p + r, parameter s -> B^par_p + k n_params_p + s,
+ * checkpoint c -> B^ck_p + k n_ck_p + c: part-major, then item-major.  The coefficient table is [shared of part 0 | shared of part 1 | ... | the parameter
+ * slots in the order above]; shared coefficients are not merged across parts (no proof byte can tell).  The matrices are replicated on the device from the
+ * parts' resident copies - no host assembly per (k1, k2), no template cache per shape; the same template may be named by several parts.
+ * The result is a template like any other: bpg_r1cs_assign takes the sum of K_p m_p values and the sum of K_p n_params_p constants in the order above and
+ * evaluates every part with its own witness program in ONE launch per level - as many launches as the part with the most levels has, so a level of a hash
+ * part runs beside the other parts' lanes, not after them.  When any part has checkpoints, plain bpg_r1cs_assign is refused and
+ * bpg_r1cs_assign_checkpointed takes the sum of K_p n_ck_p values; *first_mismatch is the flat index in that joined list and bpg_last_error names (part,
+ * item, checkpoint).  bpg_r1cs_prove_resident, bpg_r1cs_verify_resident, bpg_r1cs_verify_batch, bpg_r1cs_check and bpg_r1cs_free serve it as documented for
+ * templates.  It starts WITHOUT a witness (its parameter slots start as the sources' stand), owns copies of everything it needs - any source may be freed
+ * first - and keeps no host copy of its rows: bpg_r1cs_prove_template_batch(_commit) prove its items one at a time.
+ * Refused with BPG_ERR_INVALID_ARGUMENT before any device work (bpg_last_error names the part and the reason): a NULL ctx, parts or out; n_parts == 0 or
+ * above 256; a NULL part or count == 0; a part that is no template, has no device state (bpg_test_circuit_handle), is itself a repeat or a join (name the
+ * source template and a count instead), or lives on another context's device; totals beyond the limits of bpg_r1cs_template_repeat (n' >= 2^27,
+ * m' >= 2^29, q' or nnz' >= 2^32, columns, coefficient slots).  (An addition to ABI version 7: look the symbol up.) */
+typedef struct { bpg_circuit *tmpl; uint64_t count; } bpg_template_part;      /* frozen */
+bpg_status bpg_r1cs_template_join(bpg_ctx *ctx, uint64_t n_parts, const bpg_template_part *parts, bpg_circuit **out);
+/* TEST HOOKS, no device needed.  A part of a join for them: the template's instance, program, hints and checkpoints (either may be NULL) and its count.
+ * bpg_test_template_join_instance: the joined instance, row-major, in the form bpg_test_template_repeat_instance returns, as it stands after a
+ * bpg_r1cs_assign with param_values (the joined parameters x 32; NULL: the slots keep the constants the parts' rows carry).  row_ptr: q' + 1 entries;
+ * term_var / term_coef: *nnz_out entries; coef: *ncoef_out scalars.  A buffer that is too short is refused and named.
+ * bpg_test_template_eval_join: the join-layout interpreter of bpg_r1cs_assign(_checkpointed) compiled for the host, in the order that shows what in-order
+ * execution would hide: the vectors start as a poison value, the levels run in order and within a level the parts and their segments in REVERSE order, then
+ * the checkpoints are compared.  v = m' x 32, ck_values = n_ck' x 32 (NULL when no part has checkpoints) in; n' x 32 bytes per vector and the first
+ * mismatching flat checkpoint index (UINT64_MAX: none) out. */
+typedef struct { const bpg_r1cs_instance *inst; const bpg_witness_program *program; const bpg_witness_hints *hints; const bpg_witness_checkpoints *checkpoints;
+                 uint64_t count; } bpg_test_join_part;
+bpg_status bpg_test_template_join_instance(uint64_t n_parts, const bpg_test_join_part *parts, const uint8_t *param_values, uint64_t *row_ptr, uint64_t row_cap,
+                                           uint32_t *term_var, uint32_t *term_coef, uint64_t term_cap, uint8_t *coef, uint64_t coef_cap, uint64_t *nnz_out,
+                                           uint64_t *ncoef_out);
+bpg_status bpg_test_template_eval_join(uint64_t n_parts, const bpg_test_join_part *parts, const uint8_t *v, const uint8_t *ck_values, uint8_t *aL_out,
+                                       uint8_t *aR_out, uint8_t *aO_out, uint64_t *first_mismatch);
 
 /* R1CS CHECK ON THE DEVICE: is the resident witness satisfying, and if not, where does it fail.  (An addition to ABI version 7: look the symbol up.)
  * The witness of a template never visits the host (bpg_r1cs_assign, bpg_r1cs_template_repeat), and a proof of an unsatisfying witness is made all the same - the
