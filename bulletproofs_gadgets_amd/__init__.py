@@ -34,6 +34,7 @@ class BpgError(RuntimeError):
         super().__init__("%s: %s" % (STATUS_NAMES.get(status, status), message))
         self.status = status
         self.first_mismatch = None      # CHECKPOINT_MISMATCH (ResidentCircuit.assign): the lowest flat index item * n_ck + k whose value was wrong
+        self.item = None                # ResidentCircuit.prove_batch_checkpointed: the first failing item (first_mismatch is then that item's lowest bad checkpoint)
 
 
 class R1CSInstance(C.Structure):
@@ -949,6 +950,11 @@ class _TemplateCommitItem(C.Structure):
     _fields_ = _TemplateItem._fields_ + [("commitments_out", C.c_void_p)]
 
 
+class _TemplateCkItem(C.Structure):
+    """bpg_template_ck_item (frozen): bpg_template_commit_item, the item's checkpoint values and where its lowest mismatch goes."""
+    _fields_ = _TemplateCommitItem._fields_ + [("ck_values", C.c_char_p), ("first_mismatch", C.POINTER(C.c_uint64))]
+
+
 class ResidentCircuit:
     def __init__(self, ctx, h, n, m, n_params=None, q=None, n_ck=0):
         self.ctx, self._h, self.n, self.m = ctx, h, n, m
@@ -1089,6 +1095,50 @@ class ResidentCircuit:
         st = [status[k] for k in range(n)]
         res = [(k[1].raw[:k[2].value], k[0].raw[:203], c.raw[:32 * self.m]) if s == 0 else (None, k[0].raw[:203], None) for k, c, s in zip(keep, coms, st)]
         return (res, st) if return_status else res
+
+    def prove_batch_checkpointed(self, items, commit=False, return_status=False):
+        """bpg_r1cs_prove_template_batch_checkpointed: items = [(values, params, transcript_state, v_blinding, rng_seed, flags, checkpoints)] - fresh witnesses
+        of this checkpointed template, each with what assign(checkpoints=...) takes -> [(proof, transcript state after)], or with commit=True (the state comes
+        in BEFORE the commitments, as for prove_batch_commit) [(proof, transcript state after, commitments)]: each exactly what assign + prove give for that
+        item alone, the witnesses of a wave evaluated in the one or two levels of the checkpointed schedule.  The template holds no witness afterwards.
+        Raises BpgError on the first failing item; a checkpoint mismatch carries .item and .first_mismatch (the item's lowest bad checkpoint).
+        return_status=True returns (results, statuses, first_mismatches) instead, with (None, state as given[, None]) for a failed item and None for an
+        item without a mismatch.  On a template without checkpoints: prove_batch / prove_batch_commit (checkpoints of None or empty)."""
+        arr, keep = self._template_items([it[:6] for it in items], _TemplateCkItem)
+        n = len(items)
+        coms = [_buf(32 * self.m) for _ in range(n)] if commit else []
+        firsts = [C.c_uint64(2**64 - 1) for _ in range(n)]
+        cks = []
+        for k in range(n):
+            ck = items[k][6]
+            ck = None if ck is None else (bytes(ck) if isinstance(ck, (bytes, bytearray)) else b"".join(_exact("checkpoints", x, 32) for x in ck))
+            cks.append(ck)
+            arr[k].ck_values = ck if ck else None
+            arr[k].first_mismatch = C.pointer(firsts[k])
+            if commit:
+                arr[k].commitments_out = C.cast(coms[k], C.c_void_p)
+        status = (C.c_int32 * max(n, 1))()
+        rc = lib().bpg_r1cs_prove_template_batch_checkpointed(self.ctx._h, self._h, C.c_uint64(n), arr, C.c_int32(1 if commit else 0), status)
+        st = [status[k] for k in range(n)]
+        first = [None if f.value == 2**64 - 1 else int(f.value) for f in firsts]
+        bad = [k for k in range(n) if st[k] != 0]
+        if rc != 0 and not (return_status and bad):
+            e = BpgError(rc, lib().bpg_last_error().decode())
+            if bad:                                             # (a whole-call refusal fills no status)
+                e.item = bad[0]
+                if st[bad[0]] == ERR_CHECKPOINT_MISMATCH:
+                    e.first_mismatch = first[bad[0]]
+            raise e
+        res = []
+        for k in range(n):
+            ts, out, ln = keep[k][:3]
+            if st[k] != 0:
+                res.append((None, ts.raw[:203], None) if commit else (None, ts.raw[:203]))
+            elif commit:
+                res.append((out.raw[:ln.value], ts.raw[:203], coms[k].raw[:32 * self.m]))
+            else:
+                res.append((out.raw[:ln.value], ts.raw[:203]))
+        return (res, st, first) if return_status else res
 
     def verify(self, transcript_state, commitments, proof, seed=None, flags=0):
         """bpg_r1cs_verify_resident: 0 = accepted, 3 = VERIFICATION_ERROR, 2 = FORMAT_ERROR, 1 = INVALID_GENERATORS_LENGTH."""

@@ -396,6 +396,15 @@ bpg_status bpg_test_template_eval_batch_hinted(const bpg_r1cs_instance *inst, co
         Engine::template_eval_batch_host(as_view(inst, false), program_view(program, hints), count, v, aL, aR, aO);
     });
 }
+bpg_status bpg_test_template_eval_batch_checkpointed(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                                     const bpg_witness_checkpoints *checkpoints, uint64_t count, const uint8_t *v, const uint8_t *ck_values,
+                                                     uint8_t *aL, uint8_t *aR, uint8_t *aO, uint64_t *first_mismatch_out) {
+    return guard([&] {
+        REQUIRE(inst && program && aL && aR && aO && (inst->m == 0 || count == 0 || v) && (count == 0 || first_mismatch_out));
+        REQUIRE(!checkpoints || checkpoints->n_checkpoints == 0 || count == 0 || ck_values);
+        Engine::template_eval_batch_checkpointed_host(as_view(inst, false), program_view(program, hints, checkpoints), count, v, ck_values, aL, aR, aO, first_mismatch_out);
+    });
+}
 bpg_status bpg_test_circuit_handle(const bpg_r1cs_instance *inst, const bpg_witness_program *program, bpg_circuit **out) {
     return bpg_test_circuit_handle_hinted(inst, program, nullptr, out);
 }
@@ -631,18 +640,23 @@ bpg_status bpg_r1cs_prove_batch(bpg_ctx *ctx, uint64_t count, const bpg_batch_it
 }
 
 // the whole call is refused before anything is written or launched; a handle without device state first, whatever else was passed
-static bpg_status template_batch_refusal(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, const void *items, bpg_status *status_out) {
+// (checkpointed: bpg_r1cs_prove_template_batch_checkpointed, whose items carry the values the two frozen calls have no place for)
+static bpg_status template_batch_refusal(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, const void *items, bpg_status *status_out, bool checkpointed = false) {
     if (tmpl && !tmpl->dc) { g_last_error = "prove_template_batch: the handle has no device state (bpg_test_circuit_handle)"; return BPG_ERR_INVALID_ARGUMENT; }
     if (!ctx || !tmpl || (count && (!items || !status_out))) { g_last_error = "null or invalid argument: ctx, tmpl, items and status_out"; return BPG_ERR_INVALID_ARGUMENT; }
     if (!tmpl->is_template) { g_last_error = "prove_template_batch: the circuit is not a template (bpg_r1cs_upload_template)"; return BPG_ERR_INVALID_ARGUMENT; }
-    if (tmpl->n_ck) { g_last_error = "prove_template_batch: the template has checkpoints, and a batch item carries no values for them (bpg_r1cs_assign_checkpointed + bpg_r1cs_prove_resident)"; return BPG_ERR_INVALID_ARGUMENT; }
+    if (tmpl->n_ck && !checkpointed) { g_last_error = "prove_template_batch: the template has checkpoints, and a batch item carries no values for them (bpg_r1cs_prove_template_batch_checkpointed, or bpg_r1cs_assign_checkpointed + bpg_r1cs_prove_resident)"; return BPG_ERR_INVALID_ARGUMENT; }
     return BPG_OK;
 }
 // items that passed template_batch_refusal (none: BPG_OK, nothing touched).  coms == nullptr: bpg_r1cs_prove_template_batch.  Else bpg_r1cs_prove_template_batch_commit: the
-// transcript states are those BEFORE the "V" appends and coms[k] receives item k's m encodings (the caller checked m > 0)
-static bpg_status template_batch(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, const bpg_template_item *items, uint8_t *const *coms, bpg_status *status_out) {
+// transcript states are those BEFORE the "V" appends and coms[k] receives item k's m encodings (the caller checked m > 0).
+// cks != nullptr: bpg_r1cs_prove_template_batch_checkpointed on a template with checkpoints - cks[k] item k's n_ck values, firsts[k] (null allowed) where its
+// lowest mismatch goes.  A mismatching item fails alone on either path, with nothing of it written
+static bpg_status template_batch(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, const bpg_template_item *items, uint8_t *const *coms, bpg_status *status_out,
+                                 const uint8_t *const *cks = nullptr, uint64_t *const *firsts = nullptr) {
     if (!count) { g_last_error.clear(); return BPG_OK; }
-    const uint64_t m = tmpl->m, n = tmpl->n, n_params = tmpl->n_params;
+    const uint64_t m = tmpl->m, n = tmpl->n, n_params = tmpl->n_params, n_ck = cks ? tmpl->n_ck : 0;
+    for (uint64_t k = 0; k < count && firsts; k++) if (firsts[k]) *firsts[k] = UINT64_MAX;
     std::vector<bpg_status> st(count, BPG_OK);
     std::vector<std::string> msg(count);
     std::vector<Transcript> T(count);
@@ -658,6 +672,7 @@ static bpg_status template_batch(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count
             REQUIRE((m == 0 || it.v) && (n_params == 0 || it.param_values));
             REQUIRE(it.transcript_state && it.rng_seed && it.proof_out && it.proof_len && (m == 0 || it.v_blinding));
             if (coms && !coms[k]) throw std::invalid_argument("prove_template_batch_commit: an item without a commitment buffer");
+            if (n_ck && !cks[k]) throw std::invalid_argument("prove_template_batch_checkpointed: an item without checkpoint values (the template takes " + std::to_string(n_ck) + ")");
             if (*it.proof_len < bpg_proof_size(n, it.flags)) throw std::invalid_argument("prove: proof buffer too small");
             require_gens_capacity(ctx->engine->gens_capacity(), n, " (call bpg_gens_ensure)");
         });
@@ -668,15 +683,22 @@ static bpg_status template_batch(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count
         vb[k].resize(m);
         for (uint64_t i = 0; i < m; i++) vb[k][i] = Scalar::from_bytes_mod_order(it.v_blinding + 32 * i);
         Engine::ProveItem p; p.T = &T[k]; p.vb = &vb[k]; p.seed = it.rng_seed; p.flags = it.flags; p.values = it.v; p.params = it.param_values;
+        if (n_ck) p.ck = cks[k];
         lock.push_back(std::move(p)); lock_at.push_back(k);
     }
     if (!lock.empty()) {
-        const bpg_status s = guard([&] { ctx->engine->prove_template_batch(tmpl->dc, lock.size(), lock.data(), coms != nullptr); });
+        const bpg_status s = guard([&] { ctx->engine->prove_template_batch(tmpl->dc, lock.size(), lock.data(), coms != nullptr, cks != nullptr); });
         const std::string why = g_last_error;
         for (size_t j = 0; j < lock.size(); j++) {
             const uint64_t k = lock_at[j];
             st[k] = s;
             if (s != BPG_OK) { msg[k] = why; continue; }
+            if (lock[j].ck_first != Engine::CHECKPOINTS_HOLD) {       // its wave went on without it mattering: no proof, no commitments, the state as given
+                st[k] = BPG_ERR_CHECKPOINT_MISMATCH;
+                msg[k] = "checkpoint " + std::to_string(lock[j].ck_first) + " is not the value the circuit computes; no proof was made for the item";
+                if (firsts && firsts[k]) *firsts[k] = lock[j].ck_first;
+                continue;
+            }
             std::memcpy(items[k].proof_out, lock[j].proof.data(), lock[j].proof.size()); *items[k].proof_len = lock[j].proof.size();
             T[k].export_state(items[k].transcript_state);
             if (coms) std::memcpy(coms[k], lock[j].commitments.data(), 32 * m);
@@ -705,7 +727,8 @@ static bpg_status template_batch(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count
             for (uint64_t i = 0; i < m; i++) t.append_point("V", &scom[(j * m + i) * 32]);
             t.export_state(state);
         }
-        st[k] = bpg_r1cs_assign(ctx, tmpl, m, it.v, n_params, it.param_values);
+        st[k] = n_ck ? bpg_r1cs_assign_checkpointed(ctx, tmpl, m, it.v, n_params, it.param_values, n_ck, cks[k], firsts ? firsts[k] : nullptr)
+                     : bpg_r1cs_assign(ctx, tmpl, m, it.v, n_params, it.param_values);
         if (st[k] == BPG_OK) st[k] = bpg_r1cs_prove_resident(ctx, tmpl, coms ? state : it.transcript_state, m, it.v_blinding, it.rng_seed, it.flags, it.proof_out, it.proof_len, nullptr);
         if (st[k] != BPG_OK) { msg[k] = g_last_error; continue; }
         if (coms) { std::memcpy(it.transcript_state, state, sizeof state); std::memcpy(coms[k], &scom[j * m * 32], m * 32); }
@@ -731,6 +754,23 @@ bpg_status bpg_r1cs_prove_template_batch_commit(bpg_ctx *ctx, bpg_circuit *tmpl,
         coms[k] = it.commitments_out;
     }
     return template_batch(ctx, tmpl, count, plain.data(), tmpl->m ? coms.data() : nullptr, status_out);      // nothing to commit to: the existing call
+}
+
+bpg_status bpg_r1cs_prove_template_batch_checkpointed(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, const bpg_template_ck_item *items, int32_t commit,
+                                                      bpg_status *status_out) {
+    const bpg_status s = template_batch_refusal(ctx, tmpl, count, items, status_out, true);
+    if (s != BPG_OK) return s;
+    std::vector<bpg_template_item> plain(count);
+    std::vector<uint8_t *> coms(count);
+    std::vector<const uint8_t *> cks(count);
+    std::vector<uint64_t *> firsts(count);
+    for (uint64_t k = 0; k < count; k++) {
+        const bpg_template_ck_item &it = items[k];
+        plain[k] = bpg_template_item{it.v, it.param_values, it.transcript_state, it.v_blinding, it.rng_seed, it.flags, it.proof_out, it.proof_len};
+        coms[k] = it.commitments_out; cks[k] = it.ck_values; firsts[k] = it.first_mismatch;
+    }
+    // a template without checkpoints: exactly the frozen call `commit` selects (ck_values is not looked at; *first_mismatch, where given, reads UINT64_MAX)
+    return template_batch(ctx, tmpl, count, plain.data(), commit && tmpl->m ? coms.data() : nullptr, status_out, tmpl->n_ck ? cks.data() : nullptr, firsts.data());
 }
 
 bpg_status bpg_test_append_commitments(const uint8_t state_in[BPG_TRANSCRIPT_STATE_BYTES], uint64_t m, const uint8_t *coms, uint8_t state_out[BPG_TRANSCRIPT_STATE_BYTES]) {

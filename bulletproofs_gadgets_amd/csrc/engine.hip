@@ -201,7 +201,7 @@ struct DeviceCircuit {
     X(k_scan_apply) X(k_bucket_chunks) X(k_bucket_combine) X(k_bucket_combine_heavy) X(k_bucket_reduce) X(k_window_sums) X(k_window_sums_quad) X(k_decompress) X(k_ipa_s) X(k_verify_scalars) X(k_verify_scalars_acc) X(k_bench_fe_mul) \
     X(k_tt_bases) X(k_tt_multiples) X(k_tt_bases8) X(k_tt_multiples8) X(k_tt_round8) X(k_tt_factors) X(k_tt_advance) X(k_tt_round) X(k_tt_finish) X(k_blind_expand) X(k_tt_commit3) X(k_tt_commit3_finish) X(k_csc_count) X(k_csc_fill) X(k_csc_colptr) X(k_merge_insert) X(k_merge_plan) X(k_merge_groups) X(k_merge_members) X(k_merge_sum) \
     X(k_bt_commit3) X(k_bt_commit3_finish) X(k_bt_compress) X(k_bt_exp) X(k_bt_poly_t) X(k_bt_poly_eval) X(k_bt_factors) X(k_bt_advance) X(k_bt_round) \
-    X(k_bt_finish) X(k_bt_fold_scalars) X(k_witness_eval) X(k_witness_eval_batch) X(k_bt_commit_v) X(k_repeat_colptr) X(k_repeat_entries) X(k_repeat_coef) X(k_witness_eval_repeat) X(k_witness_ck_verify) \
+    X(k_bt_finish) X(k_bt_fold_scalars) X(k_witness_eval) X(k_witness_eval_batch) X(k_bt_commit_v) X(k_repeat_colptr) X(k_repeat_entries) X(k_repeat_coef) X(k_witness_eval_repeat) X(k_witness_ck_verify) X(k_witness_ck_verify_batch) \
     X(k_join_colptr) X(k_join_entries) X(k_join_coef) X(k_witness_eval_join) X(k_witness_ck_verify_join) \
     X(k_mimc_sponge) X(k_merkle_leaves) X(k_merkle_level) X(k_merkle_top) X(k_merkle_level_list) X(k_merkle_set_leaves) X(k_merkle_paths) X(k_merkle_export) \
     X(k_rowview_count) X(k_rowview_fill) X(k_rowview_long) X(k_check_mul) X(k_check_rows) X(k_check_rows_long) X(k_check_count)
@@ -1288,6 +1288,37 @@ void Engine::template_eval_batch_host(const FlatView &c, const WitnessProgramVie
             for (uint64_t k = 0; k < count; k++)
                 witness_eval_segment(P.segs[s].first, P.segs[s].count, P.stream.data() + P.segs[s].stream, coef.data(), vv.data() + k * c.m,
                                      aL.data() + k * N, aR.data() + k * N, aO.data() + k * N);
+    scalars_to_bytes(aL, aL_out); scalars_to_bytes(aR, aR_out); scalars_to_bytes(aO, aO_out);
+}
+
+// TEST HOOK (bpg_test_template_eval_batch_checkpointed): the batched interpreter with item k's checkpoint values at ck_values[k * n_ck ..), under the
+// discipline of template_eval_checkpointed_host - rows [0, n) of every item poisoned, the segments of every level in reverse order (per segment every
+// item, as a launch has them) - then the step of k_witness_ck_verify_batch: first_out[k] = the lowest mismatching checkpoint of item k, or CHECKPOINTS_HOLD
+void Engine::template_eval_batch_checkpointed_host(const FlatView &c, const WitnessProgramView &p, uint64_t count, const uint8_t *v, const uint8_t *ck_values,
+                                                   uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out, uint64_t *first_out) {
+    const TemplatePlan T = plan_template(c, p);
+    const PackedWitnessProgram &P = T.packed;
+    const uint64_t N = padded_size(c.n);
+    if (count > (1ull << 26) / N) throw std::invalid_argument("template_eval_batch: too many items");
+    if (p.n_ck && count && !ck_values) throw std::invalid_argument("template_eval_batch: the program has checkpoints and no values were given for them");
+    const std::vector<scm> coef = scalars_from_bytes(c.coef, c.ncoef), vv = scalars_from_bytes(v, count * c.m), ck = scalars_from_bytes(ck_values, count * p.n_ck);
+    static const uint8_t kPoison[32] = {0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a,
+                                        0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x0a};
+    const scm poison = scalars_from_bytes(kPoison, 1)[0];
+    std::vector<scm> aL(count * N, sc_zero()), aR(count * N, sc_zero()), aO(count * N, sc_zero());
+    for (uint64_t k = 0; k < count; k++)
+        for (uint64_t i = 0; i < c.n; i++) aL[k * N + i] = aR[k * N + i] = aO[k * N + i] = poison;
+    const std::vector<uint32_t> &lp = T.schedule.level_ptr;
+    for (size_t l = 0; l + 1 < lp.size(); l++)
+        for (uint32_t s = lp[l + 1]; s-- > lp[l];)
+            for (uint64_t k = 0; k < count; k++)
+                witness_eval_segment(P.segs[s].first, P.segs[s].count, P.stream.data() + P.segs[s].stream, coef.data(), vv.data() + k * c.m,
+                                     aL.data() + k * N, aR.data() + k * N, aO.data() + k * N, p.n_ck ? ck.data() + k * p.n_ck : nullptr);
+    for (uint64_t k = 0; k < count; k++) {
+        first_out[k] = CHECKPOINTS_HOLD;
+        for (uint64_t j = p.n_ck; j-- > 0;)
+            if (!witness_ck_holds(p.ck_var[j], ck[k * p.n_ck + j], aL.data() + k * N, aR.data() + k * N, aO.data() + k * N)) first_out[k] = j;
+    }
     scalars_to_bytes(aL, aL_out); scalars_to_bytes(aR, aR_out); scalars_to_bytes(aO, aO_out);
 }
 
@@ -2465,26 +2496,30 @@ void Engine::drop_witness(DeviceCircuit *d) {
     d->has_witness = false;
     d->merge_tried = false; d->mI.groups = d->mI.skipped = 0; d->mO.groups = d->mO.skipped = 0;
 }
-void Engine::prove_template_batch(DeviceCircuit *d, size_t count, ProveItem *items, bool commit) {
+void Engine::prove_template_batch(DeviceCircuit *d, size_t count, ProveItem *items, bool commit, bool checkpointed) {
     if (!template_lockstep(d)) throw std::logic_error("prove_template_batch: the circuit is not a template with a host copy of its rows");
-    if (d->n_ck) throw std::invalid_argument("prove_template_batch: the template has checkpoints, and a batch item carries no values for them");
+    if (d->n_ck && !checkpointed) throw std::invalid_argument("prove_template_batch: the template has checkpoints, and a batch item carries no values for them");
     drop_witness(d);
     for (size_t k = 0; k < count; k++) {
         if (!items[k].values && d->m) throw std::invalid_argument("prove_template_batch: an item without committed values");
         if (!items[k].params && d->n_params) throw std::invalid_argument("prove_template_batch: an item without parameter values");
-        items[k].flat = &d->host_view;
+        if (!items[k].ck && d->n_ck) throw std::invalid_argument("prove_template_batch: an item without checkpoint values");
+        items[k].flat = &d->host_view; items[k].ck_first = CHECKPOINTS_HOLD;
     }
-    prove_batch(count, items, d, commit && d->m);
+    prove_batch(count, items, d, commit && d->m);       // (a template with n_ck > 0 gets this far only when the items carry the values: the waves read d->n_ck)
+    // an item whose checkpoint values were not the circuit's own rode its wave to the end: nothing it made leaves this call
+    for (size_t k = 0; k < count; k++) if (items[k].ck_first != CHECKPOINTS_HOLD) { items[k].proof.clear(); items[k].commitments.clear(); }
 }
 
 namespace {
 using ProveItem = Engine::ProveItem;
 // ---- wave planning: groups of equal lg N, waves of at most `cap` bytes of device state (and index ranges the 29-bit variable field of the upload holds)
-std::vector<std::vector<ProveItem *>> plan_waves(size_t count, ProveItem *items, uint64_t cap) {
+// n_ck: the checkpoint values every item of a checkpointed template wave brings (raw in the pinned area and its mirror, reduced behind them, 4 bytes of result)
+std::vector<std::vector<ProveItem *>> plan_waves(size_t count, ProveItem *items, uint64_t cap, uint64_t n_ck) {
     std::vector<size_t> order(count);
     for (size_t k = 0; k < count; k++) order[k] = k;
     std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return ceil_log2(items[a].flat->n) < ceil_log2(items[b].flat->n); });
-    auto item_bytes = [&](const FlatView &f, uint64_t N) { return 28 * N * 32 + f.q * 48 + f.nnz * 24 + f.ncoef * 64 + f.m * 32 + 1024; };
+    auto item_bytes = [&](const FlatView &f, uint64_t N) { return 28 * N * 32 + f.q * 48 + f.nnz * 24 + f.ncoef * 64 + f.m * 32 + n_ck * 64 + (n_ck ? 4 : 0) + 1024; };
     std::vector<std::vector<ProveItem *>> waves;
     for (size_t g0 = 0; g0 < count;) {
         const uint32_t lgN = ceil_log2(items[order[g0]].flat->n);
@@ -2503,18 +2538,20 @@ std::vector<std::vector<ProveItem *>> plan_waves(size_t count, ProveItem *items,
 
 // ---- where everything of one wave lives: the items' offsets in the packed (block-diagonal) instance, the pinned area and the device area.
 // from_values: the witness area holds the items' committed values (a template wave) where a host-assembled wave uploads 3 K N witness scalars;
-// commit: the reduced blindings of the commitments lie right behind them, and the two go up ahead of the rest (up_begin)
+// commit: the reduced blindings of the commitments lie right behind them, and the two go up ahead of the rest (up_begin).  n_ck > 0 (a checkpointed
+// template wave): K n_ck checkpoint values, item-major, behind those and ahead of the coefficients - inside the range a committing wave sends ahead, because
+// it queues the witness evaluation before upload()
 struct WaveLayout {
-    size_t K; uint32_t lgN; uint64_t N, KN, qT, nnzT, ncoefT, mT, ncols, nvar, qmax = 0;
+    size_t K; uint32_t lgN; uint64_t N, KN, qT, nnzT, ncoefT, mT, ckT, ncols, nvar, qmax = 0;
     std::vector<uint64_t> rbase, ebase, cbase, vbase;
     uint32_t nblkC, nblkR, pblocks;
     // pinned upload area [0, up_bytes), mirrored 1:1 on the device, then the read-back area
-    size_t o_wit, o_vbl, o_coef, o_raw, o_rp, o_tv, o_tc, o_nk, o_qk, o_rb, o_bsc, o_bases, up_begin, up_bytes, o_back, pin_bytes;
+    size_t o_wit, o_vbl, o_ck, o_coef, o_raw, o_rp, o_tv, o_tc, o_nk, o_qk, o_rb, o_bsc, o_bases, up_begin, up_bytes, o_back, pin_bytes;
     // device, behind the mirror: the scalar vectors, the transposed matrix and the workspace
     size_t d_abc, d_coef, d_sLR, d_ypow, d_yinv, d_z, d_w, d_lv, d_rv, d_fG, d_fH, d_c, d_tpart, d_t, d_ab, d_colptr, d_erow, d_ecoef, d_counts, d_starts, d_cursor,
-           d_rowc, d_rowcs, d_bsum, d_part, d_pts, d_comp, d_misc, d_v, d_vcom, dev_bytes;
-    WaveLayout(const std::vector<ProveItem *> &W, bool from_values, bool commit)
-        : K(W.size()), lgN(ceil_log2(W[0]->flat->n)), N(1ull << lgN), KN(K * N), rbase(K + 1), ebase(K + 1), cbase(K + 1), vbase(K + 1) {
+           d_rowc, d_rowcs, d_bsum, d_part, d_pts, d_comp, d_misc, d_v, d_vcom, d_ck, d_ckfirst, dev_bytes;
+    WaveLayout(const std::vector<ProveItem *> &W, bool from_values, bool commit, uint64_t n_ck)
+        : K(W.size()), lgN(ceil_log2(W[0]->flat->n)), N(1ull << lgN), KN(K * N), ckT(from_values ? K * n_ck : 0), rbase(K + 1), ebase(K + 1), cbase(K + 1), vbase(K + 1) {
         for (size_t k = 0; k < K; k++) {
             const FlatView &f = *W[k]->flat;
             rbase[k + 1] = rbase[k] + f.q; ebase[k + 1] = ebase[k] + f.nnz; cbase[k + 1] = cbase[k] + f.ncoef; vbase[k + 1] = vbase[k] + f.m;
@@ -2526,11 +2563,11 @@ struct WaveLayout {
         nblkC = cdiv(16 * N, 256); nblkR = cdiv(8 * N, 256); pblocks = std::min<uint32_t>(cdiv(N, 256), 1024);
         size_t off = 0;
         auto take = [&](size_t b) { const size_t o = off; off += Engine::Impl::al256(b ? b : 1); return o; };
-        o_wit = take(from_values ? mT * 32 : 3 * KN * 32); o_vbl = take(commit ? mT * 32 : 0); o_coef = take(ncoefT * 32); o_raw = take(2 * KN * 64);
+        o_wit = take(from_values ? mT * 32 : 3 * KN * 32); o_vbl = take(commit ? mT * 32 : 0); o_ck = take(ckT * 32); o_coef = take(ncoefT * 32); o_raw = take(2 * KN * 64);
         o_rp = take((qT + 1) * 8); o_tv = take(nnzT * 4); o_tc = take(nnzT * 4); o_nk = take(K * 4); o_qk = take(K * 4); o_rb = take(K * 4);
         o_bsc = take(K * BSC * 32); o_bases = take(K * 3 * 32);
         up_begin = commit ? o_coef : 0; up_bytes = off;
-        o_back = take(std::max<size_t>(K * 3 * 32 + 64, (6 * K + mT + 1) * 32 + 64));
+        o_back = take(std::max<size_t>(K * 3 * 32 + 64 + K * 4, (6 * K + mT + 1) * 32 + 64));        // (commit3: A_I, A_O, S, the totals, the checkpoint results)
         pin_bytes = off;
         d_abc = take(3 * KN * 32); d_coef = take(ncoefT * 32); d_sLR = take(2 * KN * 32); d_ypow = take(KN * 32); d_yinv = take(KN * 32);
         d_z = take((qT + 1) * 32); d_w = take(ncols * 32); d_lv = take(KN * 32); d_rv = take(KN * 32); d_fG = take(KN * 32); d_fH = take(KN * 32);
@@ -2539,7 +2576,7 @@ struct WaveLayout {
         d_starts = take((nvar + 2) * 4); d_cursor = take((nvar + 2) * 4); d_rowc = take((qT + 2) * 4); d_rowcs = take((qT + 2) * 4);
         d_bsum = take((std::max(cdiv(nvar, SCAN_CHUNK), cdiv(qT ? qT : 1, SCAN_CHUNK)) + 2) * 4); d_part = take((size_t)K * std::max(3 * nblkC, 2 * nblkR) * sizeof(ge_ext));
         d_pts = take(K * 3 * sizeof(ge_ext)); d_comp = take(K * 3 * 32); d_misc = take(64); d_v = take(from_values ? mT * 32 : 0);
-        d_vcom = take(commit ? mT * 32 : 0);
+        d_vcom = take(commit ? mT * 32 : 0); d_ck = take(ckT * 32); d_ckfirst = take(ckT ? K * 4 : 0);
         dev_bytes = off;
     }
 };
@@ -2565,7 +2602,7 @@ struct Wave {
     std::vector<std::array<Scalar, 7>> tk, tbk;
 
     Wave(Engine &E_, Engine::Impl &I_, StageThreads &pool_, const BatchTables &B_, const std::vector<ProveItem *> &W_, const DeviceCircuit *tmpl_, bool commit_)
-        : E(E_), I(I_), pool(pool_), B(B_), W(W_), tmpl(tmpl_), commit(commit_), L(W, tmpl_ != nullptr, commit_), K(L.K), N(L.N), KN(L.KN), lgN(L.lgN),
+        : E(E_), I(I_), pool(pool_), B(B_), W(W_), tmpl(tmpl_), commit(commit_), L(W, tmpl_ != nullptr, commit_, tmpl_ ? tmpl_->n_ck : 0), K(L.K), N(L.N), KN(L.KN), lgN(L.lgN),
           ib(K), ob(K), sb(K), y(K), yinv(K), z(K), u(K), uinv(K), tk(K), tbk(K) {
         I.bt_pin.ensure(L.pin_bytes); I.bt_dev.ensure(L.dev_bytes);
         pin = I.bt_pin.as<uint8_t>(); dev = I.bt_dev.as<uint8_t>(); back = pin + L.o_back; comp = dev + L.d_comp;
@@ -2578,18 +2615,25 @@ struct Wave {
     }
 
     // the wave's witnesses: committed values reduced once for the whole wave, padding rows [n, N) of the 3 K vectors zeroed (one strided fill), then one
-    // launch per level with a lane per (segment, item)
+    // launch per level with a lane per (segment, item).  A checkpointed template: the items' checkpoint values are reduced as the committed values are, the
+    // levels are those of the checkpointed schedule, and one more launch leaves every item's lowest mismatch (all ones: none) where commit3() copies it back
     void reduce_values() {
         if (L.mT) BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(L.mT, 256)), dim3(256), D<const uint32_t>(L.o_wit), D<scm>(L.d_v), (uint32_t)L.mT);
+        if (L.ckT) BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(L.ckT, 256)), dim3(256), D<const uint32_t>(L.o_ck), D<scm>(L.d_ck), (uint32_t)L.ckT);
     }
     void eval_witnesses() {
         const uint64_t n = tmpl->n;
+        const uint32_t n_ck = L.ckT ? (uint32_t)tmpl->n_ck : 0;
         if (N > n) HIPCHK(hipMemset2DAsync(aL + n, N * sizeof(scm), 0, (N - n) * sizeof(scm), 3 * K, I.st));
         for (size_t l = 0; l + 1 < tmpl->wit_level_ptr.size(); l++) {
             const uint32_t s0 = tmpl->wit_level_ptr[l], ns = tmpl->wit_level_ptr[l + 1] - s0;
             BPG_LAUNCH(I, k_witness_eval_batch, dim3(cdiv(K, 64), ns), dim3(64), tmpl->wit_segs.as<uint4>() + s0, tmpl->wit_stream.as<uint32_t>(),
-                       tmpl->coef.as<scm>(), D<const scm>(L.d_v), (uint32_t)tmpl->m, lgN, (uint32_t)K, aL, aR, aO);
+                       tmpl->coef.as<scm>(), D<const scm>(L.d_v), D<const scm>(L.d_ck), n_ck, (uint32_t)tmpl->m, lgN, (uint32_t)K, aL, aR, aO);
         }
+        if (!n_ck) return;
+        HIPCHK(hipMemsetAsync(dev + L.d_ckfirst, 0xff, K * 4, I.st));
+        BPG_LAUNCH(I, k_witness_ck_verify_batch, dim3(cdiv(L.ckT, 256)), dim3(256), tmpl->wit_ck_var.as<uint32_t>(), n_ck, (uint64_t)L.ckT, lgN, D<const scm>(L.d_ck),
+                   aL, aR, aO, D<uint32_t>(L.d_ckfirst));
     }
     // ---- stage 1, a committing wave only: values and reduced blindings go up first, ONE launch makes the K m encodings from the reduced values the witness
     // evaluation reads, one copy brings them back; the witness evaluation is queued behind and runs while the host threads append the encodings as "V" -
@@ -2601,6 +2645,7 @@ struct Wave {
                 const uint64_t m = W[k]->flat->m;
                 std::memcpy(pin + L.o_wit + 32 * L.vbase[k], W[k]->values, 32 * m);
                 for (uint64_t j = 0; j < m; j++) (*W[k]->vb)[j].to_bytes(pin + L.o_vbl + 32 * (L.vbase[k] + j));     // reduced, as pedersen_commit uploads them
+                pack_checkpoints(k);
             }
         });
         if (!I.commit_ev) I.commit_ev = Event::untimed();
@@ -2623,6 +2668,10 @@ struct Wave {
             }
         });
     }
+    // item k's checkpoint values, raw, at its place in the wave's list (a committing wave: before the range goes up ahead of the rest)
+    void pack_checkpoints(size_t k) {
+        if (L.ckT) std::memcpy(pin + L.o_ck + 32 * k * tmpl->n_ck, W[k]->ck, 32 * tmpl->n_ck);
+    }
     // what item k uploads for its witness: the three vectors padded to N, or (a template) its committed values and its constant terms in the parameter
     // slots of ITS range of the wave's coefficient table
     void pack_witness(size_t k) {
@@ -2635,6 +2684,7 @@ struct Wave {
         if (f.ncoef) std::memcpy(pin + L.o_coef + 32 * L.cbase[k], f.coef, 32 * f.ncoef);
         if (tmpl) {
             if (f.m) std::memcpy(pin + L.o_wit + 32 * L.vbase[k], W[k]->values, 32 * f.m);
+            if (!commit) pack_checkpoints(k);
             if (tmpl->n_params) std::memcpy(pin + L.o_coef + 32 * (L.cbase[k] + tmpl->param_first), W[k]->params, 32 * tmpl->n_params);
         }
     }
@@ -2696,8 +2746,15 @@ struct Wave {
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(back, comp, 3 * K * 32, hipMemcpyDeviceToHost, I.st));
         HIPCHK(hipMemcpyAsync(back + 3 * K * 32, totals, 8, hipMemcpyDeviceToHost, I.st));
+        if (L.ckT) HIPCHK(hipMemcpyAsync(back + 3 * K * 32 + 64, dev + L.d_ckfirst, K * 4, hipMemcpyDeviceToHost, I.st));
         I.wait_stream();
         if (reinterpret_cast<const uint32_t *>(back + 3 * K * 32)[1] != L.nnzT) throw std::logic_error("prove_batch: transposition lost entries");
+        // a checkpointed wave: which items were handed values that are not the circuit's own.  Such an item stays in the wave - nothing of the plan changes -
+        // and prove_template_batch() throws away what it made
+        for (size_t k = 0; k < K && L.ckT; k++) {
+            const uint32_t first = reinterpret_cast<const uint32_t *>(back + 3 * K * 32 + 64)[k];
+            if (first != 0xffffffffu) W[k]->ck_first = first;
+        }
     }
     // ---- stage 7: host: A_I1, A_O1, S1 -> y, z of every item; device: powers, flattened weights (block-diagonal CSC, z indexed by global row), t-polynomial
     void poly_t() {
@@ -2818,7 +2875,7 @@ void Engine::prove_batch(size_t count, ProveItem *items, DeviceCircuit *tmpl, bo
     I.tt_build(I.gens, I.gens + gens_cap_, I.bases.as<ge_niels>(), M0T, true);
     const BatchTables B{I.tt_table_p, I.ped_table.as<ge_pniels>(), I.ped_table.as<ge_pniels>() + (size_t)TT_WINDOWS * TT_MULTS, M0T, I.shared_now ? 0u : 1u};
     StageThreads pool(std::min<uint32_t>(batch_host_threads(), (uint32_t)std::max<size_t>(1, count / 8)));
-    for (const std::vector<ProveItem *> &W : plan_waves(count, items, (uint64_t)I.batch_wave_mb << 20)) {
+    for (const std::vector<ProveItem *> &W : plan_waves(count, items, (uint64_t)I.batch_wave_mb << 20, tmpl ? tmpl->n_ck : 0)) {
         Wave w(*this, I, pool, B, W, tmpl, commit);
         w.make_commitments();
         w.pack_and_draw();

@@ -112,6 +112,10 @@ public:
     // hides - a_L, a_R, a_O start as a poison value, the segments of every level run in REVERSE order, then the verify step; returns the first mismatch
     static uint64_t template_eval_checkpointed_host(const FlatView &c, const WitnessProgramView &p, const uint8_t *v, const uint8_t *ck_values, uint8_t *aL, uint8_t *aR, uint8_t *aO);
     static void template_eval_batch_host(const FlatView &c, const WitnessProgramView &p, uint64_t count, const uint8_t *v, uint8_t *aL, uint8_t *aR, uint8_t *aO);
+    // test hook (bpg_test_template_eval_batch_checkpointed): the two combined - the batched interpreter with count x n_ck checkpoint values (item-major) under
+    // the poison / reverse-order discipline, then the step of k_witness_ck_verify_batch: first_out[k] = item k's lowest mismatch, or CHECKPOINTS_HOLD
+    static void template_eval_batch_checkpointed_host(const FlatView &c, const WitnessProgramView &p, uint64_t count, const uint8_t *v, const uint8_t *ck_values,
+                                                      uint8_t *aL, uint8_t *aR, uint8_t *aO, uint64_t *first_out);
     // A template repeated `count` times (include/bpg.h bpg_r1cs_template_repeat; hip/k_repeat.cuh): a new resident template of count x (n, q, m, n_params), built on
     // the device from the source's resident matrix - copy k at multipliers k n.., committed values k m.., rows k q.., parameter slots k n_params.., everything else
     // shared.  It owns copies of all it needs, holds no witness and no host rows; assign() evaluates it with the source's program, a lane per (segment, item).
@@ -180,6 +184,10 @@ public:
         const uint8_t *values = nullptr, *params = nullptr;
         std::vector<uint8_t> proof;
         std::vector<uint8_t> commitments;       // prove_template_batch(commit = true): the m encodings this item's wave made and appended to T as "V"
+        // prove_template_batch(checkpointed = true): in, the template's n_ck checkpoint values (n_ck x 32, as assign_checkpointed takes them); out, the lowest
+        // checkpoint that is not the circuit's own value, or CHECKPOINTS_HOLD.  An item that reports one rode its wave to the end and leaves with an EMPTY
+        // proof and no commitments; its T is spent (the caller proves on a copy and exports it on success only)
+        const uint8_t *ck = nullptr; uint64_t ck_first = ~0ull;
     };
     // does a proof of n multipliers with these flags take the lockstep path (0 < n, padded N <= 2^tt_orig_lg, no expanded blinding)
     bool lockstep_eligible(uint64_t n, uint32_t flags) const;
@@ -191,7 +199,10 @@ public:
     // commit (include/bpg.h bpg_r1cs_prove_template_batch_commit): T is the transcript BEFORE the "V" appends; each wave makes the commitments
     // values[j] * B + vb[j] * B_blinding of its items in one launch (k_bt_commit_v) from the values it uploaded for the witness evaluation, fills
     // `commitments` and appends them to T before anything is drawn from it.  Nothing after that point differs.
-    void prove_template_batch(DeviceCircuit *tmpl, size_t count, ProveItem *items, bool commit = false);
+    // checkpointed (include/bpg.h bpg_r1cs_prove_template_batch_checkpointed): every item brings ProveItem::ck; a wave evaluates the CHECKPOINTED schedule
+    // (a preimage: one level, a Merkle path: two) and one more launch (k_witness_ck_verify_batch) compares, per item; the result comes back with the copy of
+    // A_I, A_O, S.  Without it a template with checkpoints is refused (std::invalid_argument), as the frozen batch calls document.
+    void prove_template_batch(DeviceCircuit *tmpl, size_t count, ProveItem *items, bool commit = false, bool checkpointed = false);
     // the template kept the host copy of its rows that the lockstep packer needs (padded N <= 2^14)
     static bool template_lockstep(const DeviceCircuit *tmpl);
     // what a template batch leaves behind on either path: no witness, no equal-scalar sets

@@ -116,13 +116,29 @@ __global__ void __launch_bounds__(256) k_witness_ck_verify(const uint32_t *__res
 // ITEMS of one segment.  They walk the same records - same term counts, same classes, no divergence - and segment, record words and coefficients are
 // wave-uniform loads; only the values differ.  (Consecutive segments of one item, the map of k_witness_eval, diverge on record length and leave each lane
 // alone in its cache lines.)  The stream and the coefficient table are the template's own: a program reads no parameter slot.
+// ck: item k's n_ck checkpoint values at ck[k * n_ck ..) (a checkpointed template; n_ck = 0: none, ck is not read).  The position a term names is a word of the
+// record - wave-uniform like everything else the lanes walk; only the values differ.
 __global__ void __launch_bounds__(64) k_witness_eval_batch(const uint4 *__restrict__ segs, const uint32_t *__restrict__ stream, const scm *__restrict__ coef,
-                                                           const scm *__restrict__ v, uint32_t m, uint32_t lgN, uint32_t K, scm *aL, scm *aR, scm *aO) {
+                                                           const scm *__restrict__ v, const scm *__restrict__ ck, uint32_t n_ck, uint32_t m, uint32_t lgN, uint32_t K,
+                                                           scm *aL, scm *aR, scm *aO) {
     const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
     if (item >= K) return;
     const uint4 sd = segs[blockIdx.y];
     const size_t b = (size_t)item << lgN;
-    witness_eval_segment(sd.x, sd.y, stream + sd.z, coef, v + (size_t)item * m, aL + b, aR + b, aO + b);
+    witness_eval_segment(sd.x, sd.y, stream + sd.z, coef, v + (size_t)item * m, aL + b, aR + b, aO + b, n_ck ? ck + (size_t)item * n_ck : nullptr);
+}
+
+// After the last level of a checkpointed wave: one lane per (item, checkpoint), flat index t = item * n_ck + k, item's vectors at item << lgN.  The lowest
+// checkpoint of an item whose value differs from what the circuit computed goes to first[item] (32-bit atomicMin; the wave set the K words to all ones).
+__global__ void __launch_bounds__(256) k_witness_ck_verify_batch(const uint32_t *__restrict__ ck_var, uint32_t n_ck, uint64_t total, uint32_t lgN,
+                                                                 const scm *__restrict__ ck, const scm *__restrict__ aL, const scm *__restrict__ aR,
+                                                                 const scm *__restrict__ aO, uint32_t *first) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const uint64_t item = t / n_ck;
+    const uint32_t k = (uint32_t)(t - item * n_ck);
+    const size_t b = (size_t)item << lgN;
+    if (!witness_ck_holds(ck_var[k], ck[t], aL + b, aR + b, aO + b)) atomicMin(first + item, k);
 }
 #endif  // __HIPCC__
 

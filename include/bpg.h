@@ -82,7 +82,7 @@ typedef struct {
 
 /* ---------------------------------------------------------------------------------------------------- PART 1: hot path */
 /* ABI version of this header.  Rules: structs the CALLER allocates either carry a struct_size (bpg_config: fields are only ever added at the end and
- * read when struct_size covers them) or are frozen (bpg_timings, bpg_r1cs_instance, bpg_batch_item, bpg_template_item, bpg_template_commit_item, bpg_witness_program, bpg_witness_hints, bpg_witness_checkpoints, bpg_check_report, bpg_term, bpg_lc); a field never changes type or
+ * read when struct_size covers them) or are frozen (bpg_timings, bpg_r1cs_instance, bpg_batch_item, bpg_template_item, bpg_template_commit_item, bpg_template_ck_item, bpg_witness_program, bpg_witness_hints, bpg_witness_checkpoints, bpg_check_report, bpg_term, bpg_lc); a field never changes type or
  * meaning.  BPG_ABI_VERSION grows when something a version-7 host relies on is extended (a new field, a new flag value); functions ADDED since
  * version 7 (bpg_r1cs_prove_batch, the circuit-template calls) did not raise it: a host that needs one looks the symbol up (dlsym) and treats its
  * absence as "not supported".  A host checks bpg_abi_version() >= the BPG_ABI_VERSION it was compiled against. */
@@ -286,7 +286,7 @@ bpg_status bpg_r1cs_assign(bpg_ctx *ctx, bpg_circuit *c, uint64_t m, const uint8
  * the equal-scalar sets of the previous witness are dropped, and the call returns synchronised: the host reads the 8-byte result of the comparison back.
  * On a template with checkpoints: bpg_r1cs_template_repeat(K) gives a repeat whose bpg_r1cs_assign_checkpointed takes K x n_ck values, item-major; plain
  * bpg_r1cs_assign, bpg_r1cs_prove_template_batch and bpg_r1cs_prove_template_batch_commit are refused with BPG_ERR_INVALID_ARGUMENT before any work (their
- * frozen arguments carry no checkpoint values); bpg_r1cs_check, bpg_r1cs_prove_resident and bpg_r1cs_verify_resident serve it unchanged.  On a template
+ * frozen arguments carry no checkpoint values: bpg_r1cs_prove_template_batch_checkpointed is the lockstep batch that does); bpg_r1cs_check, bpg_r1cs_prove_resident and bpg_r1cs_verify_resident serve it unchanged.  On a template
  * without checkpoints bpg_r1cs_assign_checkpointed with n_ck = 0 is bpg_r1cs_assign. */
 typedef struct {                  /* frozen */
     uint64_t n_checkpoints;
@@ -350,6 +350,40 @@ typedef struct {
     uint8_t *commitments_out;             /* m x 32: the commitments, in commit order */
 } bpg_template_commit_item;
 bpg_status bpg_r1cs_prove_template_batch_commit(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, const bpg_template_commit_item *items, bpg_status *status_out);
+/* The same batches for a CHECKPOINTED template: K hash-chain proofs - preimages, Merkle paths against a resident tree - whose witnesses a wave evaluates in
+ * the one or two levels of the checkpointed schedule where the template without checkpoints runs one launch per dependent block.  The frozen struct
+ * bpg_template_ck_item has the nine fields of bpg_template_commit_item, same order and meaning, then ck_values - what bpg_r1cs_assign_checkpointed takes for
+ * this template, n_ck x 32 bytes, any value below 2^255 - and first_mismatch.  commit == 0: the semantics of bpg_r1cs_prove_template_batch (transcript_state
+ * comes in AFTER the "V" appends, commitments_out is not looked at); commit != 0: those of bpg_r1cs_prove_template_batch_commit (the state comes in BEFORE
+ * the commitments; the library commits and appends).
+ * For an item whose checkpoint values are the circuit's own, proof_out, *proof_len, the out-state, commitments_out and status_out[k] are byte for byte what
+ * bpg_r1cs_assign_checkpointed followed by bpg_r1cs_prove_resident gives for that item alone (with bpg_pedersen_commit and the "V" appends first when commit
+ * is set), whatever the batch around it and however it is cut into waves; *first_mismatch (NULL allowed) reads UINT64_MAX.
+ * An item with a value that is NOT the circuit's own fails alone with BPG_ERR_CHECKPOINT_MISMATCH: nothing of it is written - no proof, no commitment, its
+ * transcript state as given - *first_mismatch receives its lowest bad checkpoint (on a repeat or join: the flat index bpg_r1cs_assign_checkpointed reports),
+ * bpg_last_error names the item and the checkpoint when it is the first failure, and every other item is proved.  In a lockstep wave such an item rides to
+ * the wave's end - the comparison (k_witness_ck_verify_batch, one launch per wave) comes back with the copy of A_I, A_O, S the wave makes anyway - and what it
+ * made is thrown away: an inconsistent witness never leaves the call as a proof.
+ * Whole-call and per-item refusals are those of the two calls above; a NULL ck_values with n_ck > 0 fails that item alone (BPG_ERR_INVALID_ARGUMENT).
+ * Lockstep: the rule of bpg_r1cs_prove_template_batch.  Every other item - a template with N > 2^14, BPG_TT_ORIG_LG=0, BPG_FLAG_EXPANDED_BLINDING, and a
+ * repeat or join, which keep no host copy of their rows - runs bpg_r1cs_assign_checkpointed + bpg_r1cs_prove_resident in item order (with commit set, all
+ * their commitments come from one Pedersen launch up front), and a mismatch is reported in the same way.  On a template WITHOUT checkpoints the call is
+ * exactly the call above that `commit` selects, byte for byte (ck_values is not looked at).  The template AFTERWARDS: as documented above - no witness.
+ * (An addition to ABI version 7: look the symbol up.) */
+typedef struct {                          /* frozen */
+    const uint8_t *v;                     /* m x 32: committed values, as bpg_r1cs_assign takes them */
+    const uint8_t *param_values;          /* n_params x 32, in the order of param_rows */
+    uint8_t *transcript_state;            /* 203 B, in: commit == 0 after every "V" append, else BEFORE them; out: after the proof */
+    const uint8_t *v_blinding;            /* m x 32 */
+    const uint8_t *rng_seed;              /* 32 B */
+    uint32_t flags;
+    uint8_t *proof_out; uint64_t *proof_len;   /* in = capacity, out = bytes written */
+    uint8_t *commitments_out;             /* commit != 0: m x 32, the commitments in commit order */
+    const uint8_t *ck_values;             /* n_ck x 32, what bpg_r1cs_assign_checkpointed takes for this template */
+    uint64_t *first_mismatch;             /* NULL allowed; out: UINT64_MAX, or the lowest mismatching checkpoint of THIS item */
+} bpg_template_ck_item;
+bpg_status bpg_r1cs_prove_template_batch_checkpointed(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, const bpg_template_ck_item *items, int32_t commit,
+                                                      bpg_status *status_out);
 /* TEST HOOKS, no device needed.  bpg_test_template_schedule: the checks of bpg_r1cs_upload_template and the schedule as JSON {"levels", "segments",
  * "max_levels", "seg_first": [segments + 1], "seg_level": [...], "level_segments": [...]}: segment s is multipliers [seg_first[s], seg_first[s+1]), one
  * device lane walks it in order, and everything it reads from another segment lies at a lower level.  bpg_test_template_eval: the device's interpreter
@@ -382,6 +416,13 @@ bpg_status bpg_test_template_eval_checkpointed(const bpg_r1cs_instance *inst, co
                                                uint8_t *aL, uint8_t *aR, uint8_t *aO, uint64_t *first_mismatch);
 bpg_status bpg_test_template_packed(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
                                     const bpg_witness_checkpoints *checkpoints, uint32_t *stream_out, uint64_t cap, uint64_t *words_out);
+/* bpg_test_template_eval_batch_hinted for a program with checkpoints, as a wave of bpg_r1cs_prove_template_batch_checkpointed evaluates it: ck_values holds
+ * count x n_ck x 32 bytes, item-major; rows [0, n) of every item start as the poison value and the segments of every level run in reverse order (the discipline
+ * of bpg_test_template_eval_checkpointed), rows [n, N) are zero; then the comparison step per item: first_mismatch_out[k] (count of them) = UINT64_MAX, or the
+ * lowest checkpoint of item k whose value is not the circuit's own. */
+bpg_status bpg_test_template_eval_batch_checkpointed(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                                     const bpg_witness_checkpoints *checkpoints, uint64_t count, const uint8_t *v, const uint8_t *ck_values,
+                                                     uint8_t *aL, uint8_t *aR, uint8_t *aO, uint64_t *first_mismatch_out);
 bpg_status bpg_test_circuit_handle_hinted(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, bpg_circuit **out);
 /* A TEMPLATE REPEATED K TIMES ON THE DEVICE: one proof for K witnesses of one circuit shape.  bpg_r1cs_template_repeat makes a new resident TEMPLATE from a
  * template uploaded with bpg_r1cs_upload_template(_hinted): the circuit a host gets by assembling the template's gadget code `count` times in a row into ONE
