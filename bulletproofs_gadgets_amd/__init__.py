@@ -22,6 +22,7 @@ FLAG_COMPACT_1PHASE = 1
 FLAG_NO_1PHASE_DOMSEP = 2
 FLAG_EXPANDED_BLINDING = 4      # prover-only opt-in: s_L, s_R expanded from one TranscriptRng draw (include/bpg.h); not upstream's derivation
 VAR_MULTIPLIER_LEFT, VAR_MULTIPLIER_RIGHT, VAR_MULTIPLIER_OUTPUT, VAR_COMMITTED, VAR_ONE = 0, 1, 2, 3, 4
+VAR_INPUT = 5                   # a public input of the proof (Prover.input / Verifier.input): in instances and programs of templates with inputs only
 L = 2**252 + 27742317777372353535851937790883648493
 
 STATUS_NAMES = {0: "OK", 1: "INVALID_GENERATORS_LENGTH", 2: "FORMAT_ERROR", 3: "VERIFICATION_ERROR", 4: "INVALID_ARGUMENT",
@@ -497,13 +498,23 @@ class Context:
         finally:
             rc.free()
 
-    def upload_template(self, inst: "FlatInstance", program: "WitnessProgram", hints: "WitnessHints" = None, checkpoints=None):
+    def upload_template(self, inst: "FlatInstance", program: "WitnessProgram", hints: "WitnessHints" = None, checkpoints=None, inputs=None):
         """bpg_r1cs_upload_template: the instance (with or without a witness) plus its witness program; ResidentCircuit.assign gives it fresh witnesses.
         hints (a circuit with range proofs, Prover.witness_program(hints=True)): bpg_r1cs_upload_template_hinted.
         checkpoints (bpg_r1cs_upload_template_checkpointed): multiplier Variables whose values the caller hands to assign(..., checkpoints=values); the
-        segments that read them stop waiting for the ones that compute them."""
+        segments that read them stop waiting for the ones that compute them.
+        inputs (bpg_r1cs_upload_template_inputs; an instance from Prover.template_instance): the values of the public inputs the instance and the program
+        name (kind VAR_INPUT), as many as the template is to take with every assign(..., inputs=values); an int: that many, for an instance without a witness."""
         h = C.c_void_p()
         cs, cp = inst.cstruct(), program.cstruct()
+        n_in = 0 if inputs is None else inputs if isinstance(inputs, int) else (len(inputs) // 32 if isinstance(inputs, (bytes, bytearray)) else len(inputs))
+        if n_in:
+            iv = None if isinstance(inputs, int) else _scalars32("inputs", inputs, n_in)
+            ch = hints.cstruct() if hints is not None and len(hints) else None
+            ck = _checkpoints_cstruct(checkpoints or [])
+            _chk(lib().bpg_r1cs_upload_template_inputs(self._h, C.byref(cs), C.byref(cp), C.byref(ch) if ch is not None else None, C.byref(ck),
+                                                       C.c_uint64(n_in), iv, C.byref(h)))
+            return ResidentCircuit(self, h, inst.n, inst.m, n_params=len(program.param_rows), q=inst.q, n_ck=len(checkpoints or []), n_inputs=n_in)
         if checkpoints is not None and len(checkpoints):
             ch = hints.cstruct() if hints is not None and len(hints) else None
             ck = _checkpoints_cstruct(checkpoints)
@@ -955,24 +966,47 @@ class _TemplateCkItem(C.Structure):
     _fields_ = _TemplateCommitItem._fields_ + [("ck_values", C.c_char_p), ("first_mismatch", C.POINTER(C.c_uint64))]
 
 
+class _TemplateInItem(C.Structure):
+    """bpg_template_in_item (frozen): bpg_template_ck_item and the item's public input values."""
+    _fields_ = _TemplateCkItem._fields_ + [("input_values", C.c_char_p)]
+
+
 class ResidentCircuit:
-    def __init__(self, ctx, h, n, m, n_params=None, q=None, n_ck=0):
+    def __init__(self, ctx, h, n, m, n_params=None, q=None, n_ck=0, n_inputs=0):
         self.ctx, self._h, self.n, self.m = ctx, h, n, m
+        self.n_inputs = n_inputs            # public input values assign() takes (a template uploaded with inputs: Prover.input)
         self.n_ck = n_ck                    # checkpoint values assign() takes (a template uploaded with checkpoints; a repeat of one: count x as many)
         self.n_params = n_params            # None: a plain upload; a number: a circuit template (Prover.template / Context.upload_template)
         self.q = q                          # constraint rows (None: made by a caller that did not say)
         self.layout = None                  # Context.join: the parts of the join and where each starts (join_layout)
 
-    def assign(self, values, params=(), checkpoints=None):
+    def assign(self, values, params=(), checkpoints=None, inputs=None):
         """bpg_r1cs_assign: a fresh witness for a circuit template - the m committed values (and the constant term of every parameter row); the device
         computes a_L, a_R, a_O.  The caller commits to the same values and proves with prove().
         checkpoints (bpg_r1cs_assign_checkpointed, a template uploaded with checkpoints): their values, in the order they were named (a repeat: item-major).
         A value that is not what the circuit computes raises BpgError(CHECKPOINT_MISMATCH) whose .first_mismatch is the lowest such flat index; the circuit
-        then holds no witness."""
+        then holds no witness.
+        inputs (bpg_r1cs_assign_inputs, a template with public inputs): their values in input order - the bound, the set, the siblings of THIS proof."""
         v = _scalars32("values", values, self.m)
         pv = bytes(params) if isinstance(params, (bytes, bytearray)) else b"".join(_exact("params", x, 32) for x in params)
         if len(pv) % 32:
             raise ValueError("params must be a multiple of 32 bytes")
+        if inputs is not None:
+            iv = bytes(inputs) if isinstance(inputs, (bytes, bytearray)) else b"".join(_exact("inputs", x, 32) for x in inputs)
+            if len(iv) % 32:
+                raise ValueError("inputs must be a multiple of 32 bytes")
+            ck = b"" if checkpoints is None else (bytes(checkpoints) if isinstance(checkpoints, (bytes, bytearray)) else b"".join(_exact("checkpoints", x, 32) for x in checkpoints))
+            if len(ck) % 32:
+                raise ValueError("checkpoints must be a multiple of 32 bytes")
+            first = C.c_uint64()
+            st = lib().bpg_r1cs_assign_inputs(self.ctx._h, self._h, C.c_uint64(self.m), v if self.m else None, C.c_uint64(len(pv) // 32), pv if pv else None,
+                                              C.c_uint64(len(ck) // 32), ck if ck else None, C.byref(first), C.c_uint64(len(iv) // 32), iv if iv else None)
+            if st != 0:
+                e = BpgError(st, lib().bpg_last_error().decode())
+                if st == ERR_CHECKPOINT_MISMATCH:
+                    e.first_mismatch = int(first.value)
+                raise e
+            return
         if checkpoints is not None:
             ck = bytes(checkpoints) if isinstance(checkpoints, (bytes, bytearray)) else b"".join(_exact("checkpoints", x, 32) for x in checkpoints)
             if len(ck) % 32:
@@ -1119,6 +1153,47 @@ class ResidentCircuit:
                 arr[k].commitments_out = C.cast(coms[k], C.c_void_p)
         status = (C.c_int32 * max(n, 1))()
         rc = lib().bpg_r1cs_prove_template_batch_checkpointed(self.ctx._h, self._h, C.c_uint64(n), arr, C.c_int32(1 if commit else 0), status)
+        st = [status[k] for k in range(n)]
+        first = [None if f.value == 2**64 - 1 else int(f.value) for f in firsts]
+        bad = [k for k in range(n) if st[k] != 0]
+        if rc != 0 and not (return_status and bad):
+            e = BpgError(rc, lib().bpg_last_error().decode())
+            if bad:                                             # (a whole-call refusal fills no status)
+                e.item = bad[0]
+                if st[bad[0]] == ERR_CHECKPOINT_MISMATCH:
+                    e.first_mismatch = first[bad[0]]
+            raise e
+        res = []
+        for k in range(n):
+            ts, out, ln = keep[k][:3]
+            if st[k] != 0:
+                res.append((None, ts.raw[:203], None) if commit else (None, ts.raw[:203]))
+            elif commit:
+                res.append((out.raw[:ln.value], ts.raw[:203], coms[k].raw[:32 * self.m]))
+            else:
+                res.append((out.raw[:ln.value], ts.raw[:203]))
+        return (res, st, first) if return_status else res
+
+    def prove_batch_inputs(self, items, commit=False, return_status=False):
+        """bpg_r1cs_prove_template_batch_inputs: prove_batch_checkpointed for a template with public inputs - items = [(values, params, transcript_state,
+        v_blinding, rng_seed, flags, checkpoints, inputs)], inputs what assign(inputs=...) takes for that item (checkpoints None on a template without).
+        Results, errors and return_status as for prove_batch_checkpointed; on a template without inputs it is that call."""
+        arr, keep = self._template_items([it[:6] for it in items], _TemplateInItem)
+        n = len(items)
+        coms = [_buf(32 * self.m) for _ in range(n)] if commit else []
+        firsts = [C.c_uint64(2**64 - 1) for _ in range(n)]
+        held = []
+        join = lambda name, x: None if x is None else (bytes(x) if isinstance(x, (bytes, bytearray)) else b"".join(_exact(name, y, 32) for y in x))
+        for k in range(n):
+            ck, iv = join("checkpoints", items[k][6]), join("inputs", items[k][7])
+            held.append((ck, iv))
+            arr[k].ck_values = ck if ck else None
+            arr[k].input_values = iv if iv else None
+            arr[k].first_mismatch = C.pointer(firsts[k])
+            if commit:
+                arr[k].commitments_out = C.cast(coms[k], C.c_void_p)
+        status = (C.c_int32 * max(n, 1))()
+        rc = lib().bpg_r1cs_prove_template_batch_inputs(self.ctx._h, self._h, C.c_uint64(n), arr, C.c_int32(1 if commit else 0), status)
         st = [status[k] for k in range(n)]
         first = [None if f.value == 2**64 - 1 else int(f.value) for f in firsts]
         bad = [k for k in range(n) if st[k] != 0]
@@ -1351,6 +1426,23 @@ class Prover:
         m = view.m
         return FlatInstance(view, v=C.string_at(v, 32 * m) if m else b"", v_blinding=C.string_at(vb, 32 * m) if m else b"")
 
+    def input(self, value: bytes) -> "Variable":
+        """bpg_prover_input: a public input of this proof with this value - a Variable (kind VAR_INPUT) to name wherever a constant stood (the bound of
+        LessThan, an instance set, instance siblings).  To prove() it is that constant; template() keeps it a variable whose value every assign brings."""
+        var = C.c_uint32()
+        _chk(lib().bpg_prover_input(self._h, _exact("value", value, 32), C.byref(var)))
+        self._n_inputs = getattr(self, "_n_inputs", 0) + 1
+        return Variable(var.value)
+
+    def template_instance(self):
+        """bpg_prover_template_instance -> (FlatInstance whose rows keep their input terms, the values of the inputs in input order)."""
+        view, v, vb, n_in, iv = R1CSInstance(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_void_p()
+        _chk(lib().bpg_prover_template_instance(self._h, C.byref(view), C.byref(v), C.byref(vb), C.byref(n_in), C.byref(iv)))
+        m = view.m
+        inst = FlatInstance(view, v=C.string_at(v, 32 * m) if m else b"", v_blinding=C.string_at(vb, 32 * m) if m else b"")
+        raw = C.string_at(iv, 32 * n_in.value) if n_in.value else b""
+        return inst, [raw[32 * i:32 * i + 32] for i in range(n_in.value)]
+
     def witness_program(self, hints=False):
         """bpg_prover_witness_program: how every multiplier's assignment follows from committed values and earlier multipliers (owned copy).
         INVALID_ARGUMENT for a circuit with free multipliers (allocate / allocate_multiplier) or with none.
@@ -1401,6 +1493,9 @@ class Prover:
         prog.param_rows = prog.param_rows + [int(r) for r in param_rows]
         if ctx is None:
             raise BpgError(4, "template: no device context")
+        if getattr(self, "_n_inputs", 0):       # public inputs: the rows keep their input terms, and assign(..., inputs=) brings the values
+            inst, values = self.template_instance()
+            return ctx.upload_template(inst, prog, hints, checkpoints=list(checkpoints), inputs=values)
         return ctx.upload_template(self.instance(), prog, hints, checkpoints=list(checkpoints))
 
     def start_blinding(self, rng_seed: bytes = None, max_multipliers: int = 1 << 20):
@@ -1441,6 +1536,12 @@ class Verifier:
     def commit(self, com: bytes):
         var = C.c_uint32()
         _chk(lib().bpg_verifier_commit(self._h, com, C.byref(var)))
+        return Variable(var.value)
+
+    def input(self, value: bytes) -> "Variable":
+        """bpg_verifier_input: the verifier's side of Prover.input - the same values in the same order."""
+        var = C.c_uint32()
+        _chk(lib().bpg_verifier_input(self._h, _exact("value", value, 32), C.byref(var)))
         return Variable(var.value)
 
     def get_num_vars(self): return lib().bpg_verifier_num_vars(self._h)

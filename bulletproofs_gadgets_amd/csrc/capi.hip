@@ -111,9 +111,9 @@ void Prover::start_blinding(const uint8_t rng_seed[32], uint64_t max_multipliers
 // ---------------------------------------------------------------------------------------- handles
 struct bpg_ctx { Engine *engine; };
 struct bpg_merkle { DeviceMerkle *t; };
-struct bpg_circuit { DeviceCircuit *dc; uint64_t n, m; bool is_template = false; uint64_t n_params = 0; uint64_t n_ck = 0; };     // dc == nullptr: bpg_test_circuit_handle
+struct bpg_circuit { DeviceCircuit *dc; uint64_t n, m; bool is_template = false; uint64_t n_params = 0; uint64_t n_ck = 0; uint64_t n_in = 0; };     // dc == nullptr: bpg_test_circuit_handle
 struct bpg_transcript { Transcript t; };
-struct bpg_prover { Prover *p; FlatCircuit flat; std::vector<uint8_t> v_bytes, vb_bytes; WitnessProgram program; };
+struct bpg_prover { Prover *p; FlatCircuit flat; std::vector<uint8_t> v_bytes, vb_bytes, in_bytes; WitnessProgram program; };
 struct bpg_verifier { Verifier *v; FlatCircuit flat; };
 struct bpg_gadget { std::unique_ptr<Gadget> g; };
 struct bpg_buffer { OpBuffer b; };
@@ -136,7 +136,7 @@ static LinearCombination lc_from(const bpg_lc *lc) {
     REQUIRE(lc && (lc->n == 0 || lc->terms));
     LinearCombination out;
     for (uint64_t i = 0; i < lc->n; i++) {
-        if ((lc->terms[i].var >> 29) > BPG_VAR_ONE) throw std::invalid_argument("linear combination holds an unknown variable kind");
+        if ((lc->terms[i].var >> 29) > BPG_VAR_INPUT) throw std::invalid_argument("linear combination holds an unknown variable kind");
         out.terms.emplace_back(Variable::unpack(lc->terms[i].var), Scalar::from_bits(lc->terms[i].coeff));
     }
     return out;
@@ -264,6 +264,7 @@ bpg_status bpg_r1cs_upload(bpg_ctx *ctx, const bpg_r1cs_instance *inst, bpg_circ
     return guard([&] {
         REQUIRE(ctx && out); *out = nullptr;
         const FlatView f = as_view(inst, true);                  // no host copy: the instance goes to the device as it is
+        Engine::check_instance(f);                               // (a public input among its terms: refused here, before the context is touched)
         DeviceCircuit *dc = ctx->engine->upload(f);
         *out = new bpg_circuit{dc, f.n, f.m};
     });
@@ -290,14 +291,20 @@ bpg_status bpg_r1cs_upload_template_hinted(bpg_ctx *ctx, const bpg_r1cs_instance
 }
 bpg_status bpg_r1cs_upload_template_checkpointed(bpg_ctx *ctx, const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
                                                  const bpg_witness_checkpoints *checkpoints, bpg_circuit **out) {
+    return bpg_r1cs_upload_template_inputs(ctx, inst, program, hints, checkpoints, 0, nullptr, out);
+}
+bpg_status bpg_r1cs_upload_template_inputs(bpg_ctx *ctx, const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                           const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, const uint8_t *input_values, bpg_circuit **out) {
     return guard([&] {
         REQUIRE(out); *out = nullptr;
         REQUIRE(ctx && inst && program);
         const FlatView f = as_view(inst, false);
-        const WitnessProgramView w = program_view(program, hints, checkpoints);
-        const TemplatePlan plan = Engine::plan_template(f, w);      // every check, the level cap included, before the context is touched
+        WitnessProgramView w = program_view(program, hints, checkpoints);
+        if (n_inputs >= (1ull << 29)) throw std::invalid_argument("template: too many public inputs (the variable index has 29 bits)");
+        w.n_inputs = n_inputs;
+        const TemplatePlan plan = Engine::plan_template(f, w, input_values);      // every check, the level cap included, before the context is touched
         DeviceCircuit *dc = ctx->engine->upload_template(f, plan);
-        bpg_circuit *c = new bpg_circuit{dc, f.n, f.m}; c->is_template = true; c->n_params = w.n_params; c->n_ck = w.n_ck;
+        bpg_circuit *c = new bpg_circuit{dc, f.n, f.m}; c->is_template = true; c->n_params = w.n_params; c->n_ck = w.n_ck; c->n_in = n_inputs;
         *out = c;
     });
 }
@@ -312,6 +319,7 @@ static void assign_checks(bpg_ctx *ctx, bpg_circuit *c, uint64_t m, const uint8_
 bpg_status bpg_r1cs_assign(bpg_ctx *ctx, bpg_circuit *c, uint64_t m, const uint8_t *v, uint64_t n_params, const uint8_t *param_values) {
     return guard([&] {
         assign_checks(ctx, c, m, v, n_params, param_values);
+        if (c->n_in) throw std::invalid_argument("assign: the template has public inputs and needs their values (bpg_r1cs_assign_inputs)");
         if (c->n_ck) throw std::invalid_argument("assign: the template was uploaded with checkpoints and needs their values (bpg_r1cs_assign_checkpointed)");
         if (!c->dc) throw std::invalid_argument("assign: the handle has no device state (bpg_test_circuit_handle)");
         ctx->engine->assign(c->dc, v, param_values);
@@ -319,14 +327,24 @@ bpg_status bpg_r1cs_assign(bpg_ctx *ctx, bpg_circuit *c, uint64_t m, const uint8
 }
 bpg_status bpg_r1cs_assign_checkpointed(bpg_ctx *ctx, bpg_circuit *c, uint64_t m, const uint8_t *v, uint64_t n_params, const uint8_t *param_values,
                                         uint64_t n_ck, const uint8_t *ck_values, uint64_t *first_mismatch) {
+    if (c && c->is_template && c->n_in) {       // its arguments carry no input values: refused as plain assign refuses a checkpointed template
+        if (first_mismatch) *first_mismatch = UINT64_MAX;
+        return guard([&] { throw std::invalid_argument("assign: the template has public inputs and needs their values (bpg_r1cs_assign_inputs)"); });
+    }
+    return bpg_r1cs_assign_inputs(ctx, c, m, v, n_params, param_values, n_ck, ck_values, first_mismatch, 0, nullptr);
+}
+bpg_status bpg_r1cs_assign_inputs(bpg_ctx *ctx, bpg_circuit *c, uint64_t m, const uint8_t *v, uint64_t n_params, const uint8_t *param_values,
+                                  uint64_t n_ck, const uint8_t *ck_values, uint64_t *first_mismatch, uint64_t n_inputs, const uint8_t *input_values) {
     if (first_mismatch) *first_mismatch = UINT64_MAX;
     uint64_t first = Engine::CHECKPOINTS_HOLD;
     const bpg_status st = guard([&] {
         assign_checks(ctx, c, m, v, n_params, param_values);
         if (n_ck != c->n_ck) throw std::invalid_argument("assign: n_ck does not match the template (" + std::to_string(c->n_ck) + " checkpoint values)");
         REQUIRE(n_ck == 0 || ck_values);
+        if (n_inputs != c->n_in) throw std::invalid_argument("assign: n_inputs does not match the template (" + std::to_string(c->n_in) + " public inputs)");
+        if (n_inputs && !input_values) throw std::invalid_argument("assign: the template has " + std::to_string(n_inputs) + " public inputs and input_values is null");
         if (!c->dc) throw std::invalid_argument("assign: the handle has no device state (bpg_test_circuit_handle)");
-        first = ctx->engine->assign_checkpointed(c->dc, v, param_values, ck_values);
+        first = ctx->engine->assign_inputs(c->dc, v, param_values, ck_values, input_values);
     });
     if (st != BPG_OK || first == Engine::CHECKPOINTS_HOLD) return st;
     if (first_mismatch) *first_mismatch = first;
@@ -354,6 +372,81 @@ bpg_status bpg_test_template_schedule_checkpointed(const bpg_r1cs_instance *inst
         const std::string r = witness_schedule_json(Engine::plan_template(as_view(inst, false), program_view(program, hints, checkpoints)).schedule);
         if (r.size() + 1 > cap) throw std::invalid_argument("template_schedule: buffer too small (" + std::to_string(r.size() + 1) + " bytes needed)");
         std::memcpy(out, r.c_str(), r.size() + 1);
+    });
+}
+static WitnessProgramView program_view_inputs(const bpg_witness_program *w, const bpg_witness_hints *h, const bpg_witness_checkpoints *k, uint64_t n_inputs) {
+    WitnessProgramView v = program_view(w, h, k);
+    if (n_inputs >= (1ull << 29)) throw std::invalid_argument("template: too many public inputs (the variable index has 29 bits)");
+    v.n_inputs = n_inputs;
+    return v;
+}
+bpg_status bpg_test_template_schedule_inputs(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                             const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, char *out, uint64_t cap) {
+    return guard([&] {
+        REQUIRE(inst && program && out && cap);
+        const std::string r = witness_schedule_json(Engine::plan_template(as_view(inst, false, true), program_view_inputs(program, hints, checkpoints, n_inputs)).schedule);
+        if (r.size() + 1 > cap) throw std::invalid_argument("template_schedule: buffer too small (" + std::to_string(r.size() + 1) + " bytes needed)");
+        std::memcpy(out, r.c_str(), r.size() + 1);
+    });
+}
+bpg_status bpg_test_template_packed_inputs(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                           const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, uint32_t *stream_out, uint64_t cap, uint64_t *words_out) {
+    return guard([&] {
+        REQUIRE(inst && program && words_out && (cap == 0 || stream_out));
+        const TemplatePlan T = Engine::plan_template(as_view(inst, false, true), program_view_inputs(program, hints, checkpoints, n_inputs));
+        *words_out = T.packed.stream.size();
+        if (cap < T.packed.stream.size()) { if (cap) throw std::invalid_argument("template_packed: buffer too small (" + std::to_string(T.packed.stream.size()) + " words needed)"); return; }
+        std::memcpy(stream_out, T.packed.stream.data(), T.packed.stream.size() * 4);
+    });
+}
+bpg_status bpg_test_template_eval_inputs(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                         const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, const uint8_t *v, const uint8_t *ck_values,
+                                         const uint8_t *input_values, uint8_t *aL, uint8_t *aR, uint8_t *aO, uint64_t *first_mismatch) {
+    return guard([&] {
+        REQUIRE(inst && program && aL && aR && aO && first_mismatch && (inst->m == 0 || v));
+        REQUIRE(!checkpoints || checkpoints->n_checkpoints == 0 || ck_values);
+        if (n_inputs && !input_values) throw std::invalid_argument("template_eval: the program has " + std::to_string(n_inputs) + " public inputs and input_values is null");
+        *first_mismatch = Engine::template_eval_checkpointed_host(as_view(inst, false), program_view_inputs(program, hints, checkpoints, n_inputs), v, ck_values, aL, aR, aO, input_values);
+    });
+}
+bpg_status bpg_test_template_eval_batch_inputs(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                               const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, uint64_t count, const uint8_t *v,
+                                               const uint8_t *ck_values, const uint8_t *input_values, uint8_t *aL, uint8_t *aR, uint8_t *aO,
+                                               uint64_t *first_mismatch_out) {
+    return guard([&] {
+        REQUIRE(inst && program && aL && aR && aO && (inst->m == 0 || count == 0 || v) && (count == 0 || first_mismatch_out));
+        REQUIRE(!checkpoints || checkpoints->n_checkpoints == 0 || count == 0 || ck_values);
+        if (n_inputs && count && !input_values) throw std::invalid_argument("template_eval_batch: the program has " + std::to_string(n_inputs) + " public inputs and input_values is null");
+        Engine::template_eval_batch_checkpointed_host(as_view(inst, false), program_view_inputs(program, hints, checkpoints, n_inputs), count, v, ck_values, aL, aR, aO,
+                                                      first_mismatch_out, input_values);
+    });
+}
+bpg_status bpg_test_template_inputs_instance(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, uint64_t n_inputs,
+                                             const uint8_t *param_values, const uint8_t *input_values, uint64_t *row_ptr, uint64_t row_cap, uint32_t *term_var,
+                                             uint32_t *term_coef, uint64_t term_cap, uint8_t *coef, uint64_t coef_cap, uint64_t *nnz_out, uint64_t *ncoef_out) {
+    return guard([&] {
+        REQUIRE(inst && program && row_ptr && nnz_out && ncoef_out);
+        const FlatCircuit f = Engine::template_inputs_instance_host(as_view(inst, false), program_view_inputs(program, hints, nullptr, n_inputs), param_values, input_values);
+        const uint64_t nnz = f.term_var.size(), ncoef = f.coef.size() / 32;
+        if (row_cap < f.row_ptr.size()) throw std::invalid_argument("template_inputs_instance: row_ptr too short (" + std::to_string(f.row_ptr.size()) + " entries needed)");
+        if (term_cap < nnz || (nnz && (!term_var || !term_coef))) throw std::invalid_argument("template_inputs_instance: term_var / term_coef too short (" + std::to_string(nnz) + " entries needed)");
+        if (coef_cap < ncoef || (ncoef && !coef)) throw std::invalid_argument("template_inputs_instance: coef too short (" + std::to_string(ncoef) + " scalars needed)");
+        std::memcpy(row_ptr, f.row_ptr.data(), f.row_ptr.size() * 8);
+        if (nnz) { std::memcpy(term_var, f.term_var.data(), nnz * 4); std::memcpy(term_coef, f.term_coef.data(), nnz * 4); }
+        if (ncoef) std::memcpy(coef, f.coef.data(), ncoef * 32);
+        *nnz_out = nnz; *ncoef_out = ncoef;
+    });
+}
+bpg_status bpg_test_circuit_handle_inputs(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                          const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, bpg_circuit **out) {
+    return guard([&] {
+        REQUIRE(out); *out = nullptr;
+        REQUIRE(inst && program);
+        const FlatView f = as_view(inst, false, true);
+        const WitnessProgramView w = program_view_inputs(program, hints, checkpoints, n_inputs);
+        (void)Engine::plan_template(f, w);
+        bpg_circuit *c = new bpg_circuit{nullptr, f.n, f.m}; c->is_template = true; c->n_params = w.n_params; c->n_ck = w.n_ck; c->n_in = n_inputs;
+        *out = c;
     });
 }
 bpg_status bpg_test_template_eval_checkpointed(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
@@ -423,6 +516,7 @@ bpg_status bpg_r1cs_template_repeat(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t co
         REQUIRE(ctx && tmpl);
         if (count == 0) throw std::invalid_argument("template_repeat: count must be at least 1");
         if (!tmpl->is_template) throw std::invalid_argument("template_repeat: the circuit is not a template (bpg_r1cs_upload_template)");
+        if (tmpl->n_in) throw std::invalid_argument("template_repeat: the template has public inputs (a repeat carries none: prove its items in a batch, bpg_r1cs_prove_template_batch_inputs)");
         if (!tmpl->dc) throw std::invalid_argument("template_repeat: the handle has no device state (bpg_test_circuit_handle)");
         if (Engine::is_join(tmpl->dc)) throw std::invalid_argument("template_repeat: the circuit is a join (join its parts with larger counts instead)");
         DeviceCircuit *dc = ctx->engine->repeat_template(tmpl->dc, count);          // count 0, a repeat, sizes: refused there, before any device work
@@ -443,6 +537,7 @@ bpg_status bpg_r1cs_template_join(bpg_ctx *ctx, uint64_t n_parts, const bpg_temp
             if (!t) throw std::invalid_argument(at + "null template");
             if (parts[p].count == 0) throw std::invalid_argument(at + "count must be at least 1");
             if (!t->is_template) throw std::invalid_argument(at + "the circuit is not a template (bpg_r1cs_upload_template)");
+            if (t->n_in) throw std::invalid_argument(at + "the template has public inputs (a join carries none)");
             if (!t->dc) throw std::invalid_argument(at + "the handle has no device state (bpg_test_circuit_handle)");
             src.emplace_back(t->dc, parts[p].count);
         }
@@ -641,7 +736,10 @@ bpg_status bpg_r1cs_prove_batch(bpg_ctx *ctx, uint64_t count, const bpg_batch_it
 
 // the whole call is refused before anything is written or launched; a handle without device state first, whatever else was passed
 // (checkpointed: bpg_r1cs_prove_template_batch_checkpointed, whose items carry the values the two frozen calls have no place for)
-static bpg_status template_batch_refusal(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, const void *items, bpg_status *status_out, bool checkpointed = false) {
+static bpg_status template_batch_refusal(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, const void *items, bpg_status *status_out, bool checkpointed = false,
+                                         bool with_inputs = false) {
+    // (a template with public inputs handed to a call whose items carry none: the one refusal that comes before the handle's, so that it can be seen without a device)
+    if (tmpl && tmpl->is_template && tmpl->n_in && !with_inputs) { g_last_error = "prove_template_batch: the template has public inputs, and a batch item carries no values for them (bpg_r1cs_prove_template_batch_inputs, or bpg_r1cs_assign_inputs + bpg_r1cs_prove_resident)"; return BPG_ERR_INVALID_ARGUMENT; }
     if (tmpl && !tmpl->dc) { g_last_error = "prove_template_batch: the handle has no device state (bpg_test_circuit_handle)"; return BPG_ERR_INVALID_ARGUMENT; }
     if (!ctx || !tmpl || (count && (!items || !status_out))) { g_last_error = "null or invalid argument: ctx, tmpl, items and status_out"; return BPG_ERR_INVALID_ARGUMENT; }
     if (!tmpl->is_template) { g_last_error = "prove_template_batch: the circuit is not a template (bpg_r1cs_upload_template)"; return BPG_ERR_INVALID_ARGUMENT; }
@@ -651,11 +749,12 @@ static bpg_status template_batch_refusal(bpg_ctx *ctx, bpg_circuit *tmpl, uint64
 // items that passed template_batch_refusal (none: BPG_OK, nothing touched).  coms == nullptr: bpg_r1cs_prove_template_batch.  Else bpg_r1cs_prove_template_batch_commit: the
 // transcript states are those BEFORE the "V" appends and coms[k] receives item k's m encodings (the caller checked m > 0).
 // cks != nullptr: bpg_r1cs_prove_template_batch_checkpointed on a template with checkpoints - cks[k] item k's n_ck values, firsts[k] (null allowed) where its
-// lowest mismatch goes.  A mismatching item fails alone on either path, with nothing of it written
+// lowest mismatch goes.  A mismatching item fails alone on either path, with nothing of it written.
+// ins != nullptr: bpg_r1cs_prove_template_batch_inputs on a template with public inputs - ins[k] item k's n_inputs values
 static bpg_status template_batch(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, const bpg_template_item *items, uint8_t *const *coms, bpg_status *status_out,
-                                 const uint8_t *const *cks = nullptr, uint64_t *const *firsts = nullptr) {
+                                 const uint8_t *const *cks = nullptr, uint64_t *const *firsts = nullptr, const uint8_t *const *ins = nullptr) {
     if (!count) { g_last_error.clear(); return BPG_OK; }
-    const uint64_t m = tmpl->m, n = tmpl->n, n_params = tmpl->n_params, n_ck = cks ? tmpl->n_ck : 0;
+    const uint64_t m = tmpl->m, n = tmpl->n, n_params = tmpl->n_params, n_ck = cks ? tmpl->n_ck : 0, n_in = ins ? tmpl->n_in : 0;
     for (uint64_t k = 0; k < count && firsts; k++) if (firsts[k]) *firsts[k] = UINT64_MAX;
     std::vector<bpg_status> st(count, BPG_OK);
     std::vector<std::string> msg(count);
@@ -673,6 +772,7 @@ static bpg_status template_batch(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count
             REQUIRE(it.transcript_state && it.rng_seed && it.proof_out && it.proof_len && (m == 0 || it.v_blinding));
             if (coms && !coms[k]) throw std::invalid_argument("prove_template_batch_commit: an item without a commitment buffer");
             if (n_ck && !cks[k]) throw std::invalid_argument("prove_template_batch_checkpointed: an item without checkpoint values (the template takes " + std::to_string(n_ck) + ")");
+            if (n_in && !ins[k]) throw std::invalid_argument("prove_template_batch_inputs: an item without input values (the template takes " + std::to_string(n_in) + ")");
             if (*it.proof_len < bpg_proof_size(n, it.flags)) throw std::invalid_argument("prove: proof buffer too small");
             require_gens_capacity(ctx->engine->gens_capacity(), n, " (call bpg_gens_ensure)");
         });
@@ -684,6 +784,7 @@ static bpg_status template_batch(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count
         for (uint64_t i = 0; i < m; i++) vb[k][i] = Scalar::from_bytes_mod_order(it.v_blinding + 32 * i);
         Engine::ProveItem p; p.T = &T[k]; p.vb = &vb[k]; p.seed = it.rng_seed; p.flags = it.flags; p.values = it.v; p.params = it.param_values;
         if (n_ck) p.ck = cks[k];
+        if (n_in) p.inputs = ins[k];
         lock.push_back(std::move(p)); lock_at.push_back(k);
     }
     if (!lock.empty()) {
@@ -727,8 +828,9 @@ static bpg_status template_batch(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count
             for (uint64_t i = 0; i < m; i++) t.append_point("V", &scom[(j * m + i) * 32]);
             t.export_state(state);
         }
-        st[k] = n_ck ? bpg_r1cs_assign_checkpointed(ctx, tmpl, m, it.v, n_params, it.param_values, n_ck, cks[k], firsts ? firsts[k] : nullptr)
-                     : bpg_r1cs_assign(ctx, tmpl, m, it.v, n_params, it.param_values);
+        st[k] = n_in ? bpg_r1cs_assign_inputs(ctx, tmpl, m, it.v, n_params, it.param_values, n_ck, n_ck ? cks[k] : nullptr, firsts ? firsts[k] : nullptr, n_in, ins[k])
+                : n_ck ? bpg_r1cs_assign_checkpointed(ctx, tmpl, m, it.v, n_params, it.param_values, n_ck, cks[k], firsts ? firsts[k] : nullptr)
+                       : bpg_r1cs_assign(ctx, tmpl, m, it.v, n_params, it.param_values);
         if (st[k] == BPG_OK) st[k] = bpg_r1cs_prove_resident(ctx, tmpl, coms ? state : it.transcript_state, m, it.v_blinding, it.rng_seed, it.flags, it.proof_out, it.proof_len, nullptr);
         if (st[k] != BPG_OK) { msg[k] = g_last_error; continue; }
         if (coms) { std::memcpy(it.transcript_state, state, sizeof state); std::memcpy(coms[k], &scom[j * m * 32], m * 32); }
@@ -773,6 +875,24 @@ bpg_status bpg_r1cs_prove_template_batch_checkpointed(bpg_ctx *ctx, bpg_circuit 
     return template_batch(ctx, tmpl, count, plain.data(), commit && tmpl->m ? coms.data() : nullptr, status_out, tmpl->n_ck ? cks.data() : nullptr, firsts.data());
 }
 
+bpg_status bpg_r1cs_prove_template_batch_inputs(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, const bpg_template_in_item *items, int32_t commit,
+                                                bpg_status *status_out) {
+    const bpg_status s = template_batch_refusal(ctx, tmpl, count, items, status_out, true, true);
+    if (s != BPG_OK) return s;
+    std::vector<bpg_template_item> plain(count);
+    std::vector<uint8_t *> coms(count);
+    std::vector<const uint8_t *> cks(count), ins(count);
+    std::vector<uint64_t *> firsts(count);
+    for (uint64_t k = 0; k < count; k++) {
+        const bpg_template_in_item &it = items[k];
+        plain[k] = bpg_template_item{it.v, it.param_values, it.transcript_state, it.v_blinding, it.rng_seed, it.flags, it.proof_out, it.proof_len};
+        coms[k] = it.commitments_out; cks[k] = it.ck_values; firsts[k] = it.first_mismatch; ins[k] = it.input_values;
+    }
+    // a template without inputs: exactly bpg_r1cs_prove_template_batch_checkpointed, byte for byte (input_values is not looked at)
+    return template_batch(ctx, tmpl, count, plain.data(), commit && tmpl->m ? coms.data() : nullptr, status_out, tmpl->n_ck ? cks.data() : nullptr, firsts.data(),
+                          tmpl->n_in ? ins.data() : nullptr);
+}
+
 bpg_status bpg_test_append_commitments(const uint8_t state_in[BPG_TRANSCRIPT_STATE_BYTES], uint64_t m, const uint8_t *coms, uint8_t state_out[BPG_TRANSCRIPT_STATE_BYTES]) {
     return guard([&] {
         REQUIRE(state_in && state_out && (m == 0 || coms));
@@ -788,6 +908,7 @@ bpg_status bpg_r1cs_verify(bpg_ctx *ctx, const bpg_r1cs_instance *inst, uint8_t 
         REQUIRE(ctx && ts && proof && seed && (m == 0 || V));
         const FlatView f = as_view(inst, false, true);           // verifier side: no assignments
         if (f.m != m) throw std::invalid_argument("verify: m does not match the instance");
+        Engine::check_instance(f);
         DeviceCircuit *dc = ctx->engine->upload(f);
         Transcript T = Transcript::from_state(ts);
         R1CSError e;
@@ -989,6 +1110,26 @@ bpg_status bpg_prover_instance(bpg_prover *p, bpg_r1cs_instance *out, const uint
     });
 }
 
+bpg_status bpg_prover_input(bpg_prover *p, const uint8_t value[32], uint32_t *var_out) {
+    return guard([&] { REQUIRE(p && value); const Variable x = p->p->input(Scalar::from_bits(value)); if (var_out) *var_out = x.packed(); });
+}
+bpg_status bpg_prover_template_instance(bpg_prover *p, bpg_r1cs_instance *out, const uint8_t **v_out, const uint8_t **vb_out, uint64_t *n_inputs_out,
+                                        const uint8_t **inputs_out) {
+    return guard([&] {
+        REQUIRE(p && out && n_inputs_out && inputs_out);
+        p->p->flush_commitments();
+        p->flat = p->p->flatten(true);
+        view(p->flat, out);
+        const size_t m = p->p->num_committed(), ni = p->p->inputs().size();
+        p->v_bytes.resize(m * 32 + 1); p->vb_bytes.resize(m * 32 + 1); p->in_bytes.resize(ni * 32 + 1);
+        for (size_t i = 0; i < m; i++) { p->p->v()[i].to_bytes(&p->v_bytes[32 * i]); p->p->v_blinding()[i].to_bytes(&p->vb_bytes[32 * i]); }
+        for (size_t i = 0; i < ni; i++) p->p->inputs()[i].to_bytes(&p->in_bytes[32 * i]);
+        if (v_out) *v_out = p->v_bytes.data();
+        if (vb_out) *vb_out = p->vb_bytes.data();
+        *n_inputs_out = ni; *inputs_out = p->in_bytes.data();
+    });
+}
+
 static void put_program(const WitnessProgram &w, bpg_witness_program *out) {
     out->lc_ptr = w.lc_ptr.data(); out->term_var = w.term_var.data(); out->term_coef = w.term_coef.data();
     out->n_params = w.param_rows.size(); out->param_rows = w.param_rows.data();
@@ -1071,6 +1212,9 @@ bpg_status bpg_verifier_new(bpg_transcript *t, bpg_verifier **out) {
 void bpg_verifier_free(bpg_verifier *v) { if (v) { delete v->v; delete v; } }
 bpg_status bpg_verifier_commit(bpg_verifier *v, const uint8_t com[32], uint32_t *var_out) {
     return guard([&] { REQUIRE(v && com); Variable x = v->v->commit(com); if (var_out) *var_out = x.packed(); });
+}
+bpg_status bpg_verifier_input(bpg_verifier *v, const uint8_t value[32], uint32_t *var_out) {
+    return guard([&] { REQUIRE(v && value); const Variable x = v->v->input(Scalar::from_bits(value)); if (var_out) *var_out = x.packed(); });
 }
 uint64_t bpg_verifier_num_vars(const bpg_verifier *v) { return v ? v->v->get_num_vars() : 0; }
 bpg_status bpg_verifier_instance(bpg_verifier *v, bpg_r1cs_instance *out, const uint8_t **commitments_out) {

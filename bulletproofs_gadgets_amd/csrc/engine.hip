@@ -168,6 +168,10 @@ struct DeviceCircuit {
     // checkpoints (WitnessProgramView::ck_var): the variables, and the values of the last assign_checkpointed (a repeat: rep_count x n_ck of them)
     uint64_t n_ck = 0;
     DevBuf wit_ck_var, wit_ck;
+    // public inputs (WitnessProgramView::n_inputs): the values of the last assign_inputs, and the derived coefficient slots [slot_first, slot_first + n_slots) of
+    // `coef` with the (input, coefficient index) pair of each (host/template.hpp InputSlot), which k_input_slots reads
+    uint64_t n_in = 0, slot_first = 0, n_slots = 0;
+    DevBuf wit_in, in_slots;
     bool wit_v_set = false;                 // wit_v holds the values of an assign() (a template uploaded WITH its witness has a_L, a_R, a_O and no values yet)
     std::vector<uint32_t> wit_level_ptr;    // level l = segments [wit_level_ptr[l], wit_level_ptr[l + 1]) of wit_segs
     uint64_t n_params = 0, param_first = 0;
@@ -202,7 +206,7 @@ struct DeviceCircuit {
     X(k_tt_bases) X(k_tt_multiples) X(k_tt_bases8) X(k_tt_multiples8) X(k_tt_round8) X(k_tt_factors) X(k_tt_advance) X(k_tt_round) X(k_tt_finish) X(k_blind_expand) X(k_tt_commit3) X(k_tt_commit3_finish) X(k_csc_count) X(k_csc_fill) X(k_csc_colptr) X(k_merge_insert) X(k_merge_plan) X(k_merge_groups) X(k_merge_members) X(k_merge_sum) \
     X(k_bt_commit3) X(k_bt_commit3_finish) X(k_bt_compress) X(k_bt_exp) X(k_bt_poly_t) X(k_bt_poly_eval) X(k_bt_factors) X(k_bt_advance) X(k_bt_round) \
     X(k_bt_finish) X(k_bt_fold_scalars) X(k_witness_eval) X(k_witness_eval_batch) X(k_bt_commit_v) X(k_repeat_colptr) X(k_repeat_entries) X(k_repeat_coef) X(k_witness_eval_repeat) X(k_witness_ck_verify) X(k_witness_ck_verify_batch) \
-    X(k_join_colptr) X(k_join_entries) X(k_join_coef) X(k_witness_eval_join) X(k_witness_ck_verify_join) \
+    X(k_join_colptr) X(k_join_entries) X(k_join_coef) X(k_witness_eval_join) X(k_witness_ck_verify_join) X(k_input_slots) \
     X(k_mimc_sponge) X(k_merkle_leaves) X(k_merkle_level) X(k_merkle_top) X(k_merkle_level_list) X(k_merkle_set_leaves) X(k_merkle_paths) X(k_merkle_export) \
     X(k_rowview_count) X(k_rowview_fill) X(k_rowview_long) X(k_check_mul) X(k_check_rows) X(k_check_rows_long) X(k_check_count)
 enum KernelId {
@@ -1143,7 +1147,7 @@ void Engine::Impl::transpose_csr(const uint64_t *rp, const uint32_t *tv, const u
                       W.starts + nvar, ent_row, ent_coef);
 }
 
-void Engine::check_instance(const FlatView &c) {
+void Engine::check_instance(const FlatView &c, uint64_t n_inputs) {
     const uint64_t n = c.n, m = c.m, q = c.q, nnz = c.nnz, ncoef = c.ncoef;
     const bool has_witness = !(!c.aL && !c.aR && !c.aO && n > 0);
     if (has_witness && n > 0 && (!c.aL || !c.aR || !c.aO)) throw std::invalid_argument("upload: witness vectors must hold n scalars");
@@ -1156,16 +1160,20 @@ void Engine::check_instance(const FlatView &c) {
         if (c.term_coef[k] >= ncoef) throw std::invalid_argument("upload: coefficient index out of range");
         if (kind <= 2) { if (idx >= n) throw std::invalid_argument("upload: multiplier index out of range"); }
         else if (kind == 3) { if (idx >= m) throw std::invalid_argument("upload: committed index out of range"); }
-        else if (kind != 4) throw std::invalid_argument("upload: bad variable kind");
+        else if (kind == Variable::Input && n_inputs) {
+            if (idx >= n_inputs) throw std::invalid_argument("upload: term " + std::to_string(k) + " names public input " + std::to_string(idx) + " (the template takes " + std::to_string(n_inputs) + ")");
+        }
+        else if (kind != 4) throw std::invalid_argument("upload: bad variable kind (term " + std::to_string(k) + " has kind " + std::to_string(kind) +
+                                                        (kind == Variable::Input ? ": a public input, which only bpg_r1cs_upload_template_inputs takes)" : ")"));
     }
     for (uint64_t r = 0; r < q; r++) if (c.row_ptr[r] > c.row_ptr[r + 1]) throw std::invalid_argument("upload: malformed CSR");
 }
 
 DeviceCircuit *Engine::upload(const FlatView &c) {
+    check_instance(c);                              // every refusal before the device is touched
     HIPCHK(hipSetDevice(device_));
     Impl &I = *impl_;
     const uint64_t n = c.n, m = c.m, q = c.q, nnz = c.nnz, ncoef = c.ncoef;
-    check_instance(c);
     const bool has_witness = !(!c.aL && !c.aR && !c.aO && n > 0);
     // transposition CSR (by constraint) -> CSC (by variable) on the device (transpose_csr);
     // columns: [0,n) left, [n,2n) right, [2n,3n) output, [3n,3n+m) committed, 3n+m = the constant terms (only the verifier's w_c needs them)
@@ -1220,16 +1228,18 @@ void Engine::free_circuit(DeviceCircuit *c) {
 }
 
 // ------------------------------------------------------------------------------------------------ circuit templates (host/template.hpp, hip/k_witness.cuh)
-TemplatePlan Engine::plan_template(const FlatView &c, const WitnessProgramView &p) {
-    check_instance(c);
+TemplatePlan Engine::plan_template(const FlatView &c, const WitnessProgramView &p, const uint8_t *input_values) {
+    check_instance(c, p.n_inputs);
     check_witness_program(c, p);
+    if (p.n_inputs && !input_values && c.n && c.aL) throw std::invalid_argument("template: the instance carries a witness and no values were given for its " + std::to_string(p.n_inputs) + " public inputs");
     TemplatePlan T;
     T.schedule = build_witness_schedule(c.n, c.m, p);
     // BPG_WIT_HINT_SHARE=0 (measurement only, tools/diag/range_template.py): every bit hint reduces its source again
     const bool share = !env_present("BPG_WIT_HINT_SHARE") || env_int_strict("BPG_WIT_HINT_SHARE", 0, 1) != 0;
     T.packed = pack_witness_program(c, p, T.schedule, share);       // the classes come from the caller's table: slots are constants of rows only
-    T.slotted = with_parameter_slots(c, p);
+    T.slotted = with_parameter_slots(c, p, &T.in_slots, input_values);
     T.n_params = p.n_params; T.param_first = c.ncoef;
+    T.n_inputs = p.n_inputs; T.slot_first = c.ncoef + p.n_params;
     T.ck_var.assign(p.ck_var, p.ck_var + p.n_ck);
     return T;
 }
@@ -1256,10 +1266,13 @@ void Engine::template_eval_host(const FlatView &c, const WitnessProgramView &p, 
 
 // TEST HOOK (bpg_test_template_eval_checkpointed): poison, every level's segments in reverse order, then the step of k_witness_ck_verify
 uint64_t Engine::template_eval_checkpointed_host(const FlatView &c, const WitnessProgramView &p, const uint8_t *v, const uint8_t *ck_values,
-                                                 uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out) {
-    const TemplatePlan T = plan_template(c, p);
+                                                 uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out, const uint8_t *input_values) {
+    if (p.n_inputs && !input_values) throw std::invalid_argument("template_eval: the program has public inputs and no values were given for them");
+    FlatView rows = c; rows.aL = rows.aR = rows.aO = nullptr;       // (the hook evaluates: a witness in the instance is not looked at)
+    const TemplatePlan T = plan_template(rows, p);
     const PackedWitnessProgram &P = T.packed;
     const std::vector<scm> coef = scalars_from_bytes(c.coef, c.ncoef), vv = scalars_from_bytes(v, c.m), ck = scalars_from_bytes(ck_values, p.n_ck);
+    const std::vector<scm> in = scalars_from_bytes(input_values, p.n_inputs);
     static const uint8_t kPoison[32] = {0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a,
                                         0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x0a};
     const scm poison = scalars_from_bytes(kPoison, 1)[0];
@@ -1267,7 +1280,8 @@ uint64_t Engine::template_eval_checkpointed_host(const FlatView &c, const Witnes
     const std::vector<uint32_t> &lp = T.schedule.level_ptr;
     for (size_t l = 0; l + 1 < lp.size(); l++)
         for (uint32_t s = lp[l + 1]; s-- > lp[l];)
-            witness_eval_segment(P.segs[s].first, P.segs[s].count, P.stream.data() + P.segs[s].stream, coef.data(), vv.data(), aL.data(), aR.data(), aO.data(), ck.data());
+            witness_eval_segment(P.segs[s].first, P.segs[s].count, P.stream.data() + P.segs[s].stream, coef.data(), vv.data(), aL.data(), aR.data(), aO.data(), ck.data(),
+                                 in.data());
     uint64_t first = CHECKPOINTS_HOLD;
     for (uint64_t k = p.n_ck; k-- > 0;) if (!witness_ck_holds(p.ck_var[k], ck[k], aL.data(), aR.data(), aO.data())) first = k;
     scalars_to_bytes(aL, aL_out); scalars_to_bytes(aR, aR_out); scalars_to_bytes(aO, aO_out);
@@ -1295,13 +1309,16 @@ void Engine::template_eval_batch_host(const FlatView &c, const WitnessProgramVie
 // discipline of template_eval_checkpointed_host - rows [0, n) of every item poisoned, the segments of every level in reverse order (per segment every
 // item, as a launch has them) - then the step of k_witness_ck_verify_batch: first_out[k] = the lowest mismatching checkpoint of item k, or CHECKPOINTS_HOLD
 void Engine::template_eval_batch_checkpointed_host(const FlatView &c, const WitnessProgramView &p, uint64_t count, const uint8_t *v, const uint8_t *ck_values,
-                                                   uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out, uint64_t *first_out) {
-    const TemplatePlan T = plan_template(c, p);
+                                                   uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out, uint64_t *first_out, const uint8_t *input_values) {
+    if (p.n_inputs && count && !input_values) throw std::invalid_argument("template_eval_batch: the program has public inputs and no values were given for them");
+    FlatView rows = c; rows.aL = rows.aR = rows.aO = nullptr;
+    const TemplatePlan T = plan_template(rows, p);
     const PackedWitnessProgram &P = T.packed;
     const uint64_t N = padded_size(c.n);
     if (count > (1ull << 26) / N) throw std::invalid_argument("template_eval_batch: too many items");
     if (p.n_ck && count && !ck_values) throw std::invalid_argument("template_eval_batch: the program has checkpoints and no values were given for them");
     const std::vector<scm> coef = scalars_from_bytes(c.coef, c.ncoef), vv = scalars_from_bytes(v, count * c.m), ck = scalars_from_bytes(ck_values, count * p.n_ck);
+    const std::vector<scm> in = scalars_from_bytes(input_values, count * p.n_inputs);
     static const uint8_t kPoison[32] = {0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a,
                                         0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x0a};
     const scm poison = scalars_from_bytes(kPoison, 1)[0];
@@ -1313,7 +1330,8 @@ void Engine::template_eval_batch_checkpointed_host(const FlatView &c, const Witn
         for (uint32_t s = lp[l + 1]; s-- > lp[l];)
             for (uint64_t k = 0; k < count; k++)
                 witness_eval_segment(P.segs[s].first, P.segs[s].count, P.stream.data() + P.segs[s].stream, coef.data(), vv.data() + k * c.m,
-                                     aL.data() + k * N, aR.data() + k * N, aO.data() + k * N, p.n_ck ? ck.data() + k * p.n_ck : nullptr);
+                                     aL.data() + k * N, aR.data() + k * N, aO.data() + k * N, p.n_ck ? ck.data() + k * p.n_ck : nullptr,
+                                     p.n_inputs ? in.data() + k * p.n_inputs : nullptr);
     for (uint64_t k = 0; k < count; k++) {
         first_out[k] = CHECKPOINTS_HOLD;
         for (uint64_t j = p.n_ck; j-- > 0;)
@@ -1338,8 +1356,30 @@ DeviceCircuit *Engine::upload_template(const FlatView &c, const TemplatePlan &T)
         d->wit_ck_var.ensure(d->n_ck * 4); d->wit_ck.ensure(d->n_ck * sizeof(scm));
         I.h2d(d->wit_ck_var.p, T.ck_var.data(), d->n_ck * 4);
     }
+    d->n_in = T.n_inputs; d->slot_first = T.slot_first; d->n_slots = T.in_slots.size();
+    if (d->n_in) {
+        d->wit_in.ensure(d->n_in * sizeof(scm)); d->in_slots.ensure((d->n_slots ? d->n_slots : 1) * sizeof(InputSlot));
+        if (d->n_slots) I.h2d(d->in_slots.p, T.in_slots.data(), d->n_slots * sizeof(InputSlot));
+    }
     HIPCHK(hipStreamSynchronize(I.st));
     return d.release();
+}
+
+// TEST HOOK (bpg_test_template_inputs_instance): the rows with their slots, the parameter slots as an assign of param_values leaves them and the derived slots as
+// k_input_slots leaves them - its product on the scalars of the device code, compiled for the host
+FlatCircuit Engine::template_inputs_instance_host(const FlatView &c, const WitnessProgramView &p, const uint8_t *param_values, const uint8_t *input_values) {
+    if (p.n_inputs && !input_values) throw std::invalid_argument("template_inputs_instance: the program has public inputs and no values were given for them");
+    if (p.n_params && !param_values) throw std::invalid_argument("template_inputs_instance: the program has parameter rows and no values were given for them");
+    FlatView rows = c; rows.aL = rows.aR = rows.aO = nullptr;
+    TemplatePlan T = plan_template(rows, p);
+    FlatCircuit f = std::move(T.slotted);
+    const std::vector<scm> par = scalars_from_bytes(param_values, p.n_params), in = scalars_from_bytes(input_values, p.n_inputs);
+    std::vector<scm> coef = scalars_from_bytes(f.coef.data(), f.coef.size() / 32);
+    for (uint64_t k = 0; k < p.n_params; k++) coef[T.param_first + k] = par[k];
+    for (size_t s = 0; s < T.in_slots.size(); s++) coef[T.slot_first + s] = witness_input_slot(coef[T.in_slots[s].ci], in[T.in_slots[s].p]);
+    coef.resize(f.coef.size() / 32);
+    if (!coef.empty()) scalars_to_bytes(coef, f.coef.data());
+    return f;
 }
 
 uint64_t Engine::checkpoints_per_item(const DeviceCircuit *d) { return d ? d->n_ck : 0; }
@@ -1348,18 +1388,23 @@ void Engine::assign(DeviceCircuit *d, const uint8_t *v, const uint8_t *param_val
     (void)assign_checkpointed(d, v, param_values, nullptr);
 }
 uint64_t Engine::assign_checkpointed(DeviceCircuit *d, const uint8_t *v, const uint8_t *param_values, const uint8_t *ck_values) {
+    if (d && d->n_in) throw std::invalid_argument("assign: the template has public inputs and needs their values (bpg_r1cs_assign_inputs)");
+    return assign_inputs(d, v, param_values, ck_values, nullptr);
+}
+uint64_t Engine::assign_inputs(DeviceCircuit *d, const uint8_t *v, const uint8_t *param_values, const uint8_t *ck_values, const uint8_t *input_values) {
     if (!d || !d->is_template) throw std::invalid_argument("assign: the circuit is not a template (bpg_r1cs_upload_template)");
     const uint64_t items = d->rep_count ? d->rep_count : 1, total_ck = d->n_ck * items;
     if (total_ck && !ck_values) throw std::invalid_argument("assign: the template has checkpoints and no values were given for them");
+    if (d->n_in && !input_values) throw std::invalid_argument("assign: the template has public inputs and no values were given for them");
     HIPCHK(hipSetDevice(device_));
     Impl &I = *impl_;
     // the previous witness is gone from here on: a failure below must not leave its caches behind either
     drop_witness(d);                                // (the equal-scalar sets belong to the witness they were built from)
-    const uint64_t cnt[3] = {d->m, d->n_params, total_ck};
-    const uint8_t *src[3] = {v, param_values, ck_values};
-    scm *dst[3] = {d->wit_v.as<scm>(), d->coef.as<scm>() + d->param_first, d->wit_ck.as<scm>()};       // checkpoint values go up and into Montgomery form as v does
-    I.small_sc.ensure((std::max(std::max(cnt[0], cnt[1]), cnt[2]) + 1) * 32);
-    for (int k = 0; k < 3; k++) {
+    const uint64_t cnt[4] = {d->m, d->n_params, total_ck, d->n_in};
+    const uint8_t *src[4] = {v, param_values, ck_values, input_values};
+    scm *dst[4] = {d->wit_v.as<scm>(), d->coef.as<scm>() + d->param_first, d->wit_ck.as<scm>(), d->wit_in.as<scm>()};       // checkpoint values and inputs go up and into Montgomery form as v does
+    I.small_sc.ensure((std::max(std::max(cnt[0], cnt[1]), std::max(cnt[2], cnt[3])) + 1) * 32);
+    for (int k = 0; k < 4; k++) {
         if (!cnt[k]) continue;
         I.h2d(I.small_sc.p, src[k], cnt[k] * 32);
         BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(cnt[k], 256)), dim3(256), I.small_sc.as<uint32_t>(), dst[k], (uint32_t)cnt[k]);
@@ -1367,6 +1412,10 @@ uint64_t Engine::assign_checkpointed(DeviceCircuit *d, const uint8_t *v, const u
         HIPCHK(hipStreamSynchronize(I.st));                                     // small_sc is staged again below
     }
     const scm *ck = total_ck ? d->wit_ck.as<scm>() : nullptr;
+    const scm *in = d->n_in ? d->wit_in.as<scm>() : nullptr;
+    // the derived slots of the rows, before anything reads a constant term: coef[ci] * x_p, a lane per slot
+    if (d->n_slots) BPG_LAUNCH(I, k_input_slots, dim3(cdiv(d->n_slots, 256)), dim3(256), d->in_slots.as<uint2>(), (uint32_t)d->n_slots, (uint32_t)d->slot_first, 0u,
+                               (uint32_t)d->n_in, (uint64_t)d->n_slots, in, d->coef.as<scm>());
     // a join: ONE launch per level for all its parts (levels 0 .. the most any part has), that level's rows of the block table
     for (size_t l = 0; l + 1 < d->join_level_ptr.size(); l++) {
         const uint32_t b0 = d->join_level_ptr[l], nb = d->join_level_ptr[l + 1] - b0;
@@ -1385,7 +1434,7 @@ uint64_t Engine::assign_checkpointed(DeviceCircuit *d, const uint8_t *v, const u
         }
         const uint32_t lanes = std::min(64u, std::max(1u, cdiv(ns, I.wit_waves)));
         BPG_LAUNCH(I, k_witness_eval, dim3(cdiv(ns, lanes)), dim3(lanes), d->wit_segs.as<uint4>() + s0, ns, d->wit_stream.as<uint32_t>(), d->coef.as<scm>(),
-                   d->wit_v.as<scm>(), ck, d->aL.as<scm>(), d->aR.as<scm>(), d->aO.as<scm>());
+                   d->wit_v.as<scm>(), ck, in, d->aL.as<scm>(), d->aR.as<scm>(), d->aO.as<scm>());
     }
     uint64_t first = CHECKPOINTS_HOLD;
     if (total_ck) {                                 // were the caller's values the circuit's own?  one launch, one 8-byte read-back
@@ -1504,6 +1553,7 @@ DeviceCircuit *Engine::repeat_template(DeviceCircuit *src, uint64_t count) {
     if (!src) throw std::invalid_argument("template_repeat: no circuit");
     if (!src->is_template) throw std::invalid_argument("template_repeat: the circuit is not a template (bpg_r1cs_upload_template)");
     if (src->rep_count) throw std::invalid_argument("template_repeat: the circuit is itself a repeat (repeat the template it was made from)");
+    if (src->n_in) throw std::invalid_argument("template_repeat: the template has public inputs (a repeat carries none: prove its items in a batch, bpg_r1cs_prove_template_batch_inputs)");
     check_repeat_sizes(count, src->n, src->m, src->q, src->nnz, src->param_first, src->n_params);
     HIPCHK(hipSetDevice(device_));
     Impl &I = *impl_;
@@ -1639,6 +1689,7 @@ DeviceCircuit *Engine::join_templates(const std::vector<std::pair<DeviceCircuit 
         if (!s->is_template) throw std::invalid_argument(at + "the circuit is not a template (bpg_r1cs_upload_template)");
         if (s->rep_count) throw std::invalid_argument(at + "the circuit is itself a repeat (name the template it was made from and a count)");
         if (!s->join_parts.empty()) throw std::invalid_argument(at + "the circuit is itself a join (name its parts instead)");
+        if (s->n_in) throw std::invalid_argument(at + "the template has public inputs (a join carries none)");
         if (s->device != device_) throw std::invalid_argument(at + "the circuit lives on the device of another context");
         if (src[p].second >= (1ull << 32)) throw std::invalid_argument(at + "the joined multipliers are too many (below 2^27)");
         JoinPart &P = parts[p];
@@ -2499,6 +2550,8 @@ void Engine::drop_witness(DeviceCircuit *d) {
 void Engine::prove_template_batch(DeviceCircuit *d, size_t count, ProveItem *items, bool commit, bool checkpointed) {
     if (!template_lockstep(d)) throw std::logic_error("prove_template_batch: the circuit is not a template with a host copy of its rows");
     if (d->n_ck && !checkpointed) throw std::invalid_argument("prove_template_batch: the template has checkpoints, and a batch item carries no values for them");
+    for (size_t k = 0; k < count && d->n_in; k++)
+        if (!items[k].inputs) throw std::invalid_argument("prove_template_batch: the template has public inputs, and an item carries no values for them");
     drop_witness(d);
     for (size_t k = 0; k < count; k++) {
         if (!items[k].values && d->m) throw std::invalid_argument("prove_template_batch: an item without committed values");
@@ -2514,12 +2567,13 @@ void Engine::prove_template_batch(DeviceCircuit *d, size_t count, ProveItem *ite
 namespace {
 using ProveItem = Engine::ProveItem;
 // ---- wave planning: groups of equal lg N, waves of at most `cap` bytes of device state (and index ranges the 29-bit variable field of the upload holds)
-// n_ck: the checkpoint values every item of a checkpointed template wave brings (raw in the pinned area and its mirror, reduced behind them, 4 bytes of result)
-std::vector<std::vector<ProveItem *>> plan_waves(size_t count, ProveItem *items, uint64_t cap, uint64_t n_ck) {
+// n_ck: the checkpoint values every item of a checkpointed template wave brings (raw in the pinned area and its mirror, reduced behind them, 4 bytes of result);
+// n_in: the public inputs every item of a wave of a template with inputs brings (raw, mirrored and reduced likewise; their derived slots are coefficients of f)
+std::vector<std::vector<ProveItem *>> plan_waves(size_t count, ProveItem *items, uint64_t cap, uint64_t n_ck, uint64_t n_in) {
     std::vector<size_t> order(count);
     for (size_t k = 0; k < count; k++) order[k] = k;
     std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return ceil_log2(items[a].flat->n) < ceil_log2(items[b].flat->n); });
-    auto item_bytes = [&](const FlatView &f, uint64_t N) { return 28 * N * 32 + f.q * 48 + f.nnz * 24 + f.ncoef * 64 + f.m * 32 + n_ck * 64 + (n_ck ? 4 : 0) + 1024; };
+    auto item_bytes = [&](const FlatView &f, uint64_t N) { return 28 * N * 32 + f.q * 48 + f.nnz * 24 + f.ncoef * 64 + f.m * 32 + n_ck * 64 + (n_ck ? 4 : 0) + n_in * 64 + 1024; };
     std::vector<std::vector<ProveItem *>> waves;
     for (size_t g0 = 0; g0 < count;) {
         const uint32_t lgN = ceil_log2(items[order[g0]].flat->n);
@@ -2540,18 +2594,18 @@ std::vector<std::vector<ProveItem *>> plan_waves(size_t count, ProveItem *items,
 // from_values: the witness area holds the items' committed values (a template wave) where a host-assembled wave uploads 3 K N witness scalars;
 // commit: the reduced blindings of the commitments lie right behind them, and the two go up ahead of the rest (up_begin).  n_ck > 0 (a checkpointed
 // template wave): K n_ck checkpoint values, item-major, behind those and ahead of the coefficients - inside the range a committing wave sends ahead, because
-// it queues the witness evaluation before upload()
+// it queues the witness evaluation before upload().  n_in > 0 (a template with public inputs): K n_in input values, item-major, right behind them
 struct WaveLayout {
-    size_t K; uint32_t lgN; uint64_t N, KN, qT, nnzT, ncoefT, mT, ckT, ncols, nvar, qmax = 0;
+    size_t K; uint32_t lgN; uint64_t N, KN, qT, nnzT, ncoefT, mT, ckT, inT, ncols, nvar, qmax = 0;
     std::vector<uint64_t> rbase, ebase, cbase, vbase;
     uint32_t nblkC, nblkR, pblocks;
     // pinned upload area [0, up_bytes), mirrored 1:1 on the device, then the read-back area
-    size_t o_wit, o_vbl, o_ck, o_coef, o_raw, o_rp, o_tv, o_tc, o_nk, o_qk, o_rb, o_bsc, o_bases, up_begin, up_bytes, o_back, pin_bytes;
+    size_t o_wit, o_vbl, o_ck, o_in, o_coef, o_raw, o_rp, o_tv, o_tc, o_nk, o_qk, o_rb, o_bsc, o_bases, up_begin, up_bytes, o_back, pin_bytes;
     // device, behind the mirror: the scalar vectors, the transposed matrix and the workspace
     size_t d_abc, d_coef, d_sLR, d_ypow, d_yinv, d_z, d_w, d_lv, d_rv, d_fG, d_fH, d_c, d_tpart, d_t, d_ab, d_colptr, d_erow, d_ecoef, d_counts, d_starts, d_cursor,
-           d_rowc, d_rowcs, d_bsum, d_part, d_pts, d_comp, d_misc, d_v, d_vcom, d_ck, d_ckfirst, dev_bytes;
-    WaveLayout(const std::vector<ProveItem *> &W, bool from_values, bool commit, uint64_t n_ck)
-        : K(W.size()), lgN(ceil_log2(W[0]->flat->n)), N(1ull << lgN), KN(K * N), ckT(from_values ? K * n_ck : 0), rbase(K + 1), ebase(K + 1), cbase(K + 1), vbase(K + 1) {
+           d_rowc, d_rowcs, d_bsum, d_part, d_pts, d_comp, d_misc, d_v, d_vcom, d_ck, d_ckfirst, d_in, dev_bytes;
+    WaveLayout(const std::vector<ProveItem *> &W, bool from_values, bool commit, uint64_t n_ck, uint64_t n_in)
+        : K(W.size()), lgN(ceil_log2(W[0]->flat->n)), N(1ull << lgN), KN(K * N), ckT(from_values ? K * n_ck : 0), inT(from_values ? K * n_in : 0), rbase(K + 1), ebase(K + 1), cbase(K + 1), vbase(K + 1) {
         for (size_t k = 0; k < K; k++) {
             const FlatView &f = *W[k]->flat;
             rbase[k + 1] = rbase[k] + f.q; ebase[k + 1] = ebase[k] + f.nnz; cbase[k + 1] = cbase[k] + f.ncoef; vbase[k + 1] = vbase[k] + f.m;
@@ -2563,7 +2617,7 @@ struct WaveLayout {
         nblkC = cdiv(16 * N, 256); nblkR = cdiv(8 * N, 256); pblocks = std::min<uint32_t>(cdiv(N, 256), 1024);
         size_t off = 0;
         auto take = [&](size_t b) { const size_t o = off; off += Engine::Impl::al256(b ? b : 1); return o; };
-        o_wit = take(from_values ? mT * 32 : 3 * KN * 32); o_vbl = take(commit ? mT * 32 : 0); o_ck = take(ckT * 32); o_coef = take(ncoefT * 32); o_raw = take(2 * KN * 64);
+        o_wit = take(from_values ? mT * 32 : 3 * KN * 32); o_vbl = take(commit ? mT * 32 : 0); o_ck = take(ckT * 32); o_in = inT ? take(inT * 32) : off; o_coef = take(ncoefT * 32); o_raw = take(2 * KN * 64);
         o_rp = take((qT + 1) * 8); o_tv = take(nnzT * 4); o_tc = take(nnzT * 4); o_nk = take(K * 4); o_qk = take(K * 4); o_rb = take(K * 4);
         o_bsc = take(K * BSC * 32); o_bases = take(K * 3 * 32);
         up_begin = commit ? o_coef : 0; up_bytes = off;
@@ -2577,6 +2631,7 @@ struct WaveLayout {
         d_bsum = take((std::max(cdiv(nvar, SCAN_CHUNK), cdiv(qT ? qT : 1, SCAN_CHUNK)) + 2) * 4); d_part = take((size_t)K * std::max(3 * nblkC, 2 * nblkR) * sizeof(ge_ext));
         d_pts = take(K * 3 * sizeof(ge_ext)); d_comp = take(K * 3 * 32); d_misc = take(64); d_v = take(from_values ? mT * 32 : 0);
         d_vcom = take(commit ? mT * 32 : 0); d_ck = take(ckT * 32); d_ckfirst = take(ckT ? K * 4 : 0);
+        d_in = inT ? take(inT * 32) : off;
         dev_bytes = off;
     }
 };
@@ -2602,7 +2657,7 @@ struct Wave {
     std::vector<std::array<Scalar, 7>> tk, tbk;
 
     Wave(Engine &E_, Engine::Impl &I_, StageThreads &pool_, const BatchTables &B_, const std::vector<ProveItem *> &W_, const DeviceCircuit *tmpl_, bool commit_)
-        : E(E_), I(I_), pool(pool_), B(B_), W(W_), tmpl(tmpl_), commit(commit_), L(W, tmpl_ != nullptr, commit_, tmpl_ ? tmpl_->n_ck : 0), K(L.K), N(L.N), KN(L.KN), lgN(L.lgN),
+        : E(E_), I(I_), pool(pool_), B(B_), W(W_), tmpl(tmpl_), commit(commit_), L(W, tmpl_ != nullptr, commit_, tmpl_ ? tmpl_->n_ck : 0, tmpl_ ? tmpl_->n_in : 0), K(L.K), N(L.N), KN(L.KN), lgN(L.lgN),
           ib(K), ob(K), sb(K), y(K), yinv(K), z(K), u(K), uinv(K), tk(K), tbk(K) {
         I.bt_pin.ensure(L.pin_bytes); I.bt_dev.ensure(L.dev_bytes);
         pin = I.bt_pin.as<uint8_t>(); dev = I.bt_dev.as<uint8_t>(); back = pin + L.o_back; comp = dev + L.d_comp;
@@ -2620,6 +2675,7 @@ struct Wave {
     void reduce_values() {
         if (L.mT) BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(L.mT, 256)), dim3(256), D<const uint32_t>(L.o_wit), D<scm>(L.d_v), (uint32_t)L.mT);
         if (L.ckT) BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(L.ckT, 256)), dim3(256), D<const uint32_t>(L.o_ck), D<scm>(L.d_ck), (uint32_t)L.ckT);
+        if (L.inT) BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(L.inT, 256)), dim3(256), D<const uint32_t>(L.o_in), D<scm>(L.d_in), (uint32_t)L.inT);
     }
     void eval_witnesses() {
         const uint64_t n = tmpl->n;
@@ -2628,7 +2684,8 @@ struct Wave {
         for (size_t l = 0; l + 1 < tmpl->wit_level_ptr.size(); l++) {
             const uint32_t s0 = tmpl->wit_level_ptr[l], ns = tmpl->wit_level_ptr[l + 1] - s0;
             BPG_LAUNCH(I, k_witness_eval_batch, dim3(cdiv(K, 64), ns), dim3(64), tmpl->wit_segs.as<uint4>() + s0, tmpl->wit_stream.as<uint32_t>(),
-                       tmpl->coef.as<scm>(), D<const scm>(L.d_v), D<const scm>(L.d_ck), n_ck, (uint32_t)tmpl->m, lgN, (uint32_t)K, aL, aR, aO);
+                       tmpl->coef.as<scm>(), D<const scm>(L.d_v), D<const scm>(L.d_ck), n_ck, D<const scm>(L.d_in), L.inT ? (uint32_t)tmpl->n_in : 0u, (uint32_t)tmpl->m, lgN,
+                       (uint32_t)K, aL, aR, aO);
         }
         if (!n_ck) return;
         HIPCHK(hipMemsetAsync(dev + L.d_ckfirst, 0xff, K * 4, I.st));
@@ -2671,6 +2728,7 @@ struct Wave {
     // item k's checkpoint values, raw, at its place in the wave's list (a committing wave: before the range goes up ahead of the rest)
     void pack_checkpoints(size_t k) {
         if (L.ckT) std::memcpy(pin + L.o_ck + 32 * k * tmpl->n_ck, W[k]->ck, 32 * tmpl->n_ck);
+        if (L.inT) std::memcpy(pin + L.o_in + 32 * k * tmpl->n_in, W[k]->inputs, 32 * tmpl->n_in);       // the item's public inputs travel beside them
     }
     // what item k uploads for its witness: the three vectors padded to N, or (a template) its committed values and its constant terms in the parameter
     // slots of ITS range of the wave's coefficient table
@@ -2730,6 +2788,11 @@ struct Wave {
         if (!tmpl) BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(3 * KN, 256)), dim3(256), D<const uint32_t>(L.o_wit), aL, (uint32_t)(3 * KN));
         else if (!commit) { reduce_values(); eval_witnesses(); }       // (a committing wave queued them behind its commitments)
         if (L.ncoefT) BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(L.ncoefT, 256)), dim3(256), D<const uint32_t>(L.o_coef), D<scm>(L.d_coef), (uint32_t)L.ncoefT);
+        // a template with public inputs: every item's derived slots in ITS range of the table (all items share the template's rows: one stride), where the
+        // parameter slots were patched on the host - before the flattening reads a constant term
+        if (L.inT && tmpl->n_slots) BPG_LAUNCH(I, k_input_slots, dim3(cdiv(K * tmpl->n_slots, 256)), dim3(256), tmpl->in_slots.as<uint2>(), (uint32_t)tmpl->n_slots,
+                                               (uint32_t)tmpl->slot_first, (uint32_t)W[0]->flat->ncoef, (uint32_t)tmpl->n_in, (uint64_t)(K * tmpl->n_slots),
+                                               D<const scm>(L.d_in), D<scm>(L.d_coef));
         BPG_LAUNCH(I, k_sc_from_wide, dim3(cdiv(2 * KN, 256)), dim3(256), D<const uint32_t>(L.o_raw), sL, (uint32_t)(2 * KN), stale);
     }
     // ---- stage 5: the block-diagonal CSR -> CSC in one pass, as upload() transposes a single instance
@@ -2875,7 +2938,7 @@ void Engine::prove_batch(size_t count, ProveItem *items, DeviceCircuit *tmpl, bo
     I.tt_build(I.gens, I.gens + gens_cap_, I.bases.as<ge_niels>(), M0T, true);
     const BatchTables B{I.tt_table_p, I.ped_table.as<ge_pniels>(), I.ped_table.as<ge_pniels>() + (size_t)TT_WINDOWS * TT_MULTS, M0T, I.shared_now ? 0u : 1u};
     StageThreads pool(std::min<uint32_t>(batch_host_threads(), (uint32_t)std::max<size_t>(1, count / 8)));
-    for (const std::vector<ProveItem *> &W : plan_waves(count, items, (uint64_t)I.batch_wave_mb << 20, tmpl ? tmpl->n_ck : 0)) {
+    for (const std::vector<ProveItem *> &W : plan_waves(count, items, (uint64_t)I.batch_wave_mb << 20, tmpl ? tmpl->n_ck : 0, tmpl ? tmpl->n_in : 0)) {
         Wave w(*this, I, pool, B, W, tmpl, commit);
         w.make_commitments();
         w.pack_and_draw();

@@ -83,9 +83,11 @@ public:
     void free_circuit(DeviceCircuit *c);
     // Circuit template (include/bpg.h bpg_r1cs_upload_template): upload() plus the witness program, packed and scheduled (host/template.hpp), in HBM.  The
     // witness arrays are allocated either way; a witness in `c` is uploaded as upload() does, so the first proof needs no assign().  Each parameter row's
-    // constant terms become one coefficient slot of its own.  Constants that flow into multiplications are part of the program and stay fixed.
+    // constant terms become one coefficient slot of its own.  Constants that flow into multiplications are part of the program and stay fixed - unless they
+    // are PUBLIC INPUTS (p.n_inputs > 0, include/bpg.h bpg_r1cs_upload_template_inputs): terms of kind Variable::Input in the rows and in the program, whose
+    // values every assign brings.  input_values (n_inputs x 32): those of the witness `c` carries (needed then; null: the derived slots start at zero).
     // plan_template: every host-side check (instance and program: std::invalid_argument) and the schedule, packed program and parameter slots, no device work.
-    static TemplatePlan plan_template(const FlatView &c, const WitnessProgramView &p);
+    static TemplatePlan plan_template(const FlatView &c, const WitnessProgramView &p, const uint8_t *input_values = nullptr);
     DeviceCircuit *upload_template(const FlatView &c, const TemplatePlan &plan);
     // A fresh witness for a template: m committed values (32 bytes each, any 256-bit value: reduced mod l on the device) and the constant term of every
     // parameter row; a_L, a_R, a_O are computed on the device (k_witness_eval, one launch per schedule level), everything cached for the previous witness
@@ -99,6 +101,11 @@ public:
     static constexpr uint64_t CHECKPOINTS_HOLD = ~0ull;
     uint64_t assign_checkpointed(DeviceCircuit *c, const uint8_t *v, const uint8_t *param_values, const uint8_t *ck_values);
     static uint64_t checkpoints_per_item(const DeviceCircuit *c);   // n_ck of the template (a repeat: of its source; it takes count x n_ck values)
+    // The same for a template with public inputs (include/bpg.h bpg_r1cs_assign_inputs): input_values are its n_inputs values (32 bytes each, reduced mod l on the
+    // device).  They go up as v does; k_input_slots writes coef[ci] * x_p into every derived slot before a level runs, and the levels read the inputs wherever the
+    // program names one.  A template without inputs takes null and is assign_checkpointed().  assign() / assign_checkpointed() on a template with inputs:
+    // std::invalid_argument.
+    uint64_t assign_inputs(DeviceCircuit *c, const uint8_t *v, const uint8_t *param_values, const uint8_t *ck_values, const uint8_t *input_values);
     // Which multiplier, which constraint row does the resident witness break (include/bpg.h bpg_r1cs_check; hip/k_check.cuh): a_L * a_R against a_O per multiplier, and
     // every row of the matrix over the operand vector [a_L | a_R | a_O | v | 1].  v: m x 32 bytes (reduced mod l on the device), or null on a template: the values
     // of its last assign().  rows_out receives the lowest min(cap, bad_rows) bad rows, ascending.  The first check of a circuit derives a row-major view of its
@@ -110,12 +117,17 @@ public:
     // segment side by side, into the wave layout (count x N x 32 bytes per vector, item-major, N = padded size, padding rows zero); v: count x m x 32
     // test hook (bpg_test_template_eval_checkpointed): template_eval_host for a program with checkpoints, made to show what in-order execution on one thread
     // hides - a_L, a_R, a_O start as a poison value, the segments of every level run in REVERSE order, then the verify step; returns the first mismatch
-    static uint64_t template_eval_checkpointed_host(const FlatView &c, const WitnessProgramView &p, const uint8_t *v, const uint8_t *ck_values, uint8_t *aL, uint8_t *aR, uint8_t *aO);
+    // input_values (bpg_test_template_eval_inputs): the n_inputs public inputs of a program with inputs, reduced as assign_inputs reduces them
+    static uint64_t template_eval_checkpointed_host(const FlatView &c, const WitnessProgramView &p, const uint8_t *v, const uint8_t *ck_values, uint8_t *aL, uint8_t *aR, uint8_t *aO,
+                                                    const uint8_t *input_values = nullptr);
     static void template_eval_batch_host(const FlatView &c, const WitnessProgramView &p, uint64_t count, const uint8_t *v, uint8_t *aL, uint8_t *aR, uint8_t *aO);
     // test hook (bpg_test_template_eval_batch_checkpointed): the two combined - the batched interpreter with count x n_ck checkpoint values (item-major) under
     // the poison / reverse-order discipline, then the step of k_witness_ck_verify_batch: first_out[k] = item k's lowest mismatch, or CHECKPOINTS_HOLD
     static void template_eval_batch_checkpointed_host(const FlatView &c, const WitnessProgramView &p, uint64_t count, const uint8_t *v, const uint8_t *ck_values,
-                                                      uint8_t *aL, uint8_t *aR, uint8_t *aO, uint64_t *first_out);
+                                                      uint8_t *aL, uint8_t *aR, uint8_t *aO, uint64_t *first_out, const uint8_t *input_values = nullptr);
+    // test hook (bpg_test_template_inputs_instance): the resident rows of a template with inputs as an assign of input_values leaves them - every input term a
+    // constant term on its derived slot, the slot holding what k_input_slots writes (the same product, compiled for the host)
+    static FlatCircuit template_inputs_instance_host(const FlatView &c, const WitnessProgramView &p, const uint8_t *param_values, const uint8_t *input_values);
     // A template repeated `count` times (include/bpg.h bpg_r1cs_template_repeat; hip/k_repeat.cuh): a new resident template of count x (n, q, m, n_params), built on
     // the device from the source's resident matrix - copy k at multipliers k n.., committed values k m.., rows k q.., parameter slots k n_params.., everything else
     // shared.  It owns copies of all it needs, holds no witness and no host rows; assign() evaluates it with the source's program, a lane per (segment, item).
@@ -188,6 +200,7 @@ public:
         // checkpoint that is not the circuit's own value, or CHECKPOINTS_HOLD.  An item that reports one rode its wave to the end and leaves with an EMPTY
         // proof and no commitments; its T is spent (the caller proves on a copy and exports it on success only)
         const uint8_t *ck = nullptr; uint64_t ck_first = ~0ull;
+        const uint8_t *inputs = nullptr;        // a template with public inputs: the item's n_inputs values (n_inputs x 32, as assign_inputs takes them)
     };
     // does a proof of n multipliers with these flags take the lockstep path (0 < n, padded N <= 2^tt_orig_lg, no expanded blinding)
     bool lockstep_eligible(uint64_t n, uint32_t flags) const;
@@ -208,7 +221,8 @@ public:
     // what a template batch leaves behind on either path: no witness, no equal-scalar sets
     static void drop_witness(DeviceCircuit *tmpl);
     // the host-side checks of an instance (CSR shape, index ranges, sizes), which upload() and plan_template() start with: std::invalid_argument, no device work
-    static void check_instance(const FlatView &c);
+    // n_inputs: terms of kind Variable::Input that name inputs [0, n_inputs) are legal (a template with inputs); 0, every other caller: the kind is refused
+    static void check_instance(const FlatView &c, uint64_t n_inputs = 0);
     // MiMC sponges and Merkle trees on the device (include/bpg.h, "MiMC Merkle trees"; hip/k_mimc.cuh).  Every argument is checked before the device is touched
     // (std::invalid_argument); the calls run on the context's stream and return synchronised.
     // mimc_sponge_1 of count items of `blocks` 32-byte blocks each (any 256-bit value, taken mod l) -> count canonical scalars

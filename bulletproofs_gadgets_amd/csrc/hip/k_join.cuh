@@ -72,7 +72,7 @@ BPG_HD void witness_eval_join_lane(const JoinPart &P, uint32_t first, uint32_t c
                                    scm *aL, scm *aR, scm *aO, const scm *ck) {
     const size_t b = (size_t)P.base_n + (size_t)k * P.n;
     witness_eval_segment(first, count, rec, coef + P.base_shared, v + P.base_m + (size_t)k * P.m, aL + b, aR + b, aO + b,
-                         ck ? ck + P.base_ck + (size_t)k * P.n_ck : nullptr);
+                         ck ? ck + P.base_ck + (size_t)k * P.n_ck : nullptr, nullptr);      // (a template with public inputs is never a part: no inputs)
 }
 
 #if defined(__HIPCC__)

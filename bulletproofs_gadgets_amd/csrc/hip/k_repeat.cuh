@@ -40,7 +40,7 @@ BPG_HD uint64_t repeat_entry_pos(uint64_t K, uint64_t k, uint64_t s0, uint64_t s
 BPG_HD void witness_eval_repeat_lane(uint32_t first, uint32_t count, const uint32_t *rec, const scm *coef, const scm *v, uint32_t n, uint32_t m, uint64_t k,
                                      scm *aL, scm *aR, scm *aO, const scm *ck = nullptr, uint32_t n_ck = 0) {
     const size_t b = (size_t)k * n;
-    witness_eval_segment(first, count, rec, coef, v + (size_t)k * m, aL + b, aR + b, aO + b, ck ? ck + (size_t)k * n_ck : nullptr);
+    witness_eval_segment(first, count, rec, coef, v + (size_t)k * m, aL + b, aR + b, aO + b, ck ? ck + (size_t)k * n_ck : nullptr, nullptr);     // (no inputs: such a template is not repeated)
 }
 
 #if defined(__HIPCC__)

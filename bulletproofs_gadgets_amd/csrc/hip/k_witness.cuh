@@ -13,6 +13,9 @@
 // A term of kind WIT_KIND_CHECKPOINT reads `ck`, the values the caller handed to assign (Engine::assign_checkpointed), by its position in the checkpoint
 // list - never a_L, a_R, a_O and never the register copy of the last multiplier, whoever computes that variable.  So a level still reads only what an earlier
 // launch, the lane itself or the caller wrote.  k_witness_ck_verify, after the last level, compares every checkpoint with what the circuit computed for it.
+// A term of kind WIT_KIND_INPUT reads `in`, the public inputs the caller handed to assign (Engine::assign_inputs), by the input's index - a word of the record,
+// the same for every lane that walks it, so the items of a batch stay convergent: only the value differs.  The ROWS of the matrix never name an input: their
+// input terms are constant terms on derived coefficient slots, which k_input_slots fills per item before anything reads constant terms.
 #pragma once
 #include "sc.cuh"
 #include "../host/witness_record.hpp"
@@ -23,7 +26,7 @@ struct WitPrev { scm l, r, o; uint32_t idx; };
 
 // sum of `count` terms at t[0 .. 2 count): (packed variable, class << 30 | coefficient index)
 BPG_HD scm witness_eval_lc(const uint32_t *t, uint32_t count, const WitPrev &prev, const scm *coef, const scm *v, const scm *aL, const scm *aR, const scm *aO,
-                           const scm *ck) {
+                           const scm *ck, const scm *in) {
     scm acc = sc_zero();
     for (uint32_t k = 0; k < count; k++) {
         const uint32_t var = t[2 * k], cw = t[2 * k + 1];
@@ -34,7 +37,7 @@ BPG_HD scm witness_eval_lc(const uint32_t *t, uint32_t count, const WitPrev &pre
         }
         scm x;
         if (kind <= 2 && idx == prev.idx) x = kind == 0 ? prev.l : kind == 1 ? prev.r : prev.o;
-        else x = (kind == 0 ? aL : kind == 1 ? aR : kind == 2 ? aO : kind == WIT_KIND_CHECKPOINT ? ck : v)[idx];
+        else x = (kind == 0 ? aL : kind == 1 ? aR : kind == 2 ? aO : kind == WIT_KIND_CHECKPOINT ? ck : kind == WIT_KIND_INPUT ? in : v)[idx];
         if (cls == WIT_COEF_PLUS_ONE) acc = sc_add(acc, x);
         else if (cls == WIT_COEF_MINUS_ONE) acc = sc_sub(acc, x);
         else acc = sc_add(acc, sc_mont_mul(coef[ci], x));
@@ -50,16 +53,17 @@ BPG_HD uint32_t witness_bit(const uint32_t *w, uint32_t bit) {
     return (x >> (bit & 31u)) & 1u;
 }
 
-// multipliers [first, first + count) from the records at `rec`; ck: the checkpoint values (null for a program without checkpoints: no term names one)
+// multipliers [first, first + count) from the records at `rec`; ck: the checkpoint values (null for a program without checkpoints: no term names one);
+// in: the item's public inputs, canonical Montgomery form (null for a program without inputs, likewise)
 BPG_HD void witness_eval_segment(uint32_t first, uint32_t count, const uint32_t *rec, const scm *coef, const scm *v, scm *aL, scm *aR, scm *aO,
-                                 const scm *ck = nullptr) {
+                                 const scm *ck = nullptr, const scm *in = nullptr) {
     WitPrev prev; prev.l = prev.r = prev.o = sc_zero(); prev.idx = 0xffffffffu;
     uint32_t src[8];                                                // canonical words of the last hint source (the packer never shares across segments)
     BPG_UNROLL for (int k = 0; k < 8; k++) src[k] = 0;
     for (uint32_t i = first; i < first + count; i++) {
         const uint32_t nl = rec[0], w1 = rec[1];
         if (w1 & WIT_HINT_BIT_PAIR) {
-            if (!(w1 & WIT_HINT_SAME_SOURCE)) sc_to_words(src, witness_eval_lc(rec + 2, nl, prev, coef, v, aL, aR, aO, ck));
+            if (!(w1 & WIT_HINT_SAME_SOURCE)) sc_to_words(src, witness_eval_lc(rec + 2, nl, prev, coef, v, aL, aR, aO, ck, in));
             const uint32_t set = 0u - witness_bit(src, w1 & WIT_HINT_ARG_MASK);     // all ones when the bit is set
             const scm one = SC_R1();
             scm l, r;
@@ -70,8 +74,8 @@ BPG_HD void witness_eval_segment(uint32_t first, uint32_t count, const uint32_t 
             continue;
         }
         const uint32_t same = w1 & WIT_SAME_AS_LEFT, nr = w1 & WIT_RIGHT_COUNT_MASK;
-        const scm l = witness_eval_lc(rec + 2, nl, prev, coef, v, aL, aR, aO, ck);
-        const scm r = same ? l : witness_eval_lc(rec + 2 + 2 * nl, nr, prev, coef, v, aL, aR, aO, ck);
+        const scm l = witness_eval_lc(rec + 2, nl, prev, coef, v, aL, aR, aO, ck, in);
+        const scm r = same ? l : witness_eval_lc(rec + 2 + 2 * nl, nr, prev, coef, v, aL, aR, aO, ck, in);
         const scm o = sc_mont_mul(l, r);
         aL[i] = l; aR[i] = r; aO[i] = o;
         prev.l = l; prev.r = r; prev.o = o; prev.idx = i;
@@ -88,15 +92,35 @@ BPG_HD bool witness_ck_holds(uint32_t var, const scm &given, const scm *aL, cons
     return diff == 0;
 }
 
+// what a derived coefficient slot of a template with public inputs holds: coef[ci] * x_p, both canonical Montgomery form (k_input_slots; the host hook
+// bpg_test_template_inputs_instance calls the same function)
+BPG_HD scm witness_input_slot(const scm &c, const scm &x) { return sc_mont_mul(c, x); }
+
 #if defined(__HIPCC__)     // the kernels; everything above also compiles for the host alone (tests/hostcheck/template_repeat.cpp)
 // segs: (first multiplier, count, first record word, -) per segment of ONE level.  Blocks are small (the engine spreads a level's few hundred lanes
 // over many waves: a lane alone in its wave reads one cache line per load, 64 lanes read 64).
 __global__ void __launch_bounds__(64) k_witness_eval(const uint4 *__restrict__ segs, uint32_t nseg, const uint32_t *__restrict__ stream,
-                                                     const scm *__restrict__ coef, const scm *__restrict__ v, const scm *__restrict__ ck, scm *aL, scm *aR, scm *aO) {
+                                                     const scm *__restrict__ coef, const scm *__restrict__ v, const scm *__restrict__ ck,
+                                                     const scm *__restrict__ in, scm *aL, scm *aR, scm *aO) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= nseg) return;
     const uint4 sd = segs[s];
-    witness_eval_segment(sd.x, sd.y, stream + sd.z, coef, v, aL, aR, aO, ck);
+    witness_eval_segment(sd.x, sd.y, stream + sd.z, coef, v, aL, aR, aO, ck, in);
+}
+
+// The derived coefficient slots of a template with public inputs (host/template.hpp with_parameter_slots): one lane per (item, slot), flat index t = item * n_slots
+// + s.  slots[s] = (input p, coefficient index ci); the slot holds coef[ci] * x_p.  Item k's table starts at coef + k * stride (assign: one item; a lockstep
+// wave: the items' ranges of the wave's table), its slots at slot_first in it, its inputs at in + k * n_in.  Both factors are canonical Montgomery form and so
+// is the product.  A slot is never a factor (ci names the caller's table, below the parameter slots), so no lane reads what another writes.
+__global__ void __launch_bounds__(256) k_input_slots(const uint2 *__restrict__ slots, uint32_t n_slots, uint32_t slot_first, uint32_t stride, uint32_t n_in,
+                                                     uint64_t total, const scm *__restrict__ in, scm *coef) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const uint64_t item = t / n_slots;
+    const uint32_t s = (uint32_t)(t - item * n_slots);
+    const uint2 sl = slots[s];
+    scm *tab = coef + (size_t)item * stride;
+    tab[slot_first + s] = witness_input_slot(tab[sl.y], in[(size_t)item * n_in + sl.x]);
 }
 
 // After the last level of a checkpointed assign: one lane per (item, checkpoint), flat index t = item * n_ck + k; item's vectors at item * n (a plain template:
@@ -118,14 +142,16 @@ __global__ void __launch_bounds__(256) k_witness_ck_verify(const uint32_t *__res
 // alone in its cache lines.)  The stream and the coefficient table are the template's own: a program reads no parameter slot.
 // ck: item k's n_ck checkpoint values at ck[k * n_ck ..) (a checkpointed template; n_ck = 0: none, ck is not read).  The position a term names is a word of the
 // record - wave-uniform like everything else the lanes walk; only the values differ.
+// in: item k's n_in public inputs at in[k * n_in ..) (n_in = 0: none, in is not read); the index a term names is again a word of the record.
 __global__ void __launch_bounds__(64) k_witness_eval_batch(const uint4 *__restrict__ segs, const uint32_t *__restrict__ stream, const scm *__restrict__ coef,
-                                                           const scm *__restrict__ v, const scm *__restrict__ ck, uint32_t n_ck, uint32_t m, uint32_t lgN, uint32_t K,
-                                                           scm *aL, scm *aR, scm *aO) {
+                                                           const scm *__restrict__ v, const scm *__restrict__ ck, uint32_t n_ck, const scm *__restrict__ in,
+                                                           uint32_t n_in, uint32_t m, uint32_t lgN, uint32_t K, scm *aL, scm *aR, scm *aO) {
     const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
     if (item >= K) return;
     const uint4 sd = segs[blockIdx.y];
     const size_t b = (size_t)item << lgN;
-    witness_eval_segment(sd.x, sd.y, stream + sd.z, coef, v + (size_t)item * m, aL + b, aR + b, aO + b, n_ck ? ck + (size_t)item * n_ck : nullptr);
+    witness_eval_segment(sd.x, sd.y, stream + sd.z, coef, v + (size_t)item * m, aL + b, aR + b, aO + b, n_ck ? ck + (size_t)item * n_ck : nullptr,
+                         n_in ? in + (size_t)item * n_in : nullptr);
 }
 
 // After the last level of a checkpointed wave: one lane per (item, checkpoint), flat index t = item * n_ck + k, item's vectors at item << lgN.  The lowest

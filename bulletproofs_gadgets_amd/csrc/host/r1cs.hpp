@@ -20,7 +20,8 @@
 namespace bpg {
 
 struct Variable {
-    enum Kind : uint32_t { MultiplierLeft = 0, MultiplierRight = 1, MultiplierOutput = 2, Committed = 3, One = 4 };
+    // Input: public value idx of THIS proof (Prover::input / Verifier::input) - a constant to the proof system, a variable to a circuit template
+    enum Kind : uint32_t { MultiplierLeft = 0, MultiplierRight = 1, MultiplierOutput = 2, Committed = 3, One = 4, Input = 5 };
     Kind kind; uint32_t idx;
     static Variable one() { return Variable{One, 0}; }
     uint32_t packed() const { return (static_cast<uint32_t>(kind) << 29) | idx; }
@@ -160,6 +161,8 @@ struct WitnessProgramView {
     // assign; every term that names it reads the caller's value (host/template.hpp), and the device compares it with what the circuit computed
     uint64_t n_ck = 0;
     const uint32_t *ck_var = nullptr;
+    // Public inputs (bpg_r1cs_upload_template_inputs): terms of kind Variable::Input name inputs [0, n_inputs); 0: the program may hold no such term
+    uint64_t n_inputs = 0;
     WitnessProgramView() {}
     explicit WitnessProgramView(const WitnessProgram &w)
         : lc_ptr(w.lc_ptr.data()), term_var(w.term_var.data()), term_coef(w.term_coef.data()), n_params(w.param_rows.size()), param_rows(w.param_rows.data()),
@@ -192,13 +195,46 @@ protected:
         for (auto &t : lc.terms) { term_var_.push_back(t.first.packed()); term_coef_.push_back(intern(t.second)); }
         row_ptr_.push_back(term_var_.size());
     }
-    void export_rows(FlatCircuit &f) const {
+    // Public inputs (Variable::Input): the values of this assembly, in the order input() made them
+    std::vector<Scalar> inputs_;
+    // resolve (every export but a template's): a term (Input p, c) leaves as the constant term (One, c * x_p), its product in the table behind the
+    // dictionary's own entries - so nothing that reads an instance ever meets an input, and an assembly without inputs exports what it always did
+    void export_rows(FlatCircuit &f, bool resolve = true) const {
         f.row_ptr = row_ptr_; f.term_var = term_var_; f.term_coef = term_coef_;
         f.coef.resize(coef_.size() * 32);
         for (size_t i = 0; i < coef_.size(); i++) coef_[i].to_bytes(&f.coef[32 * i]);
+        if (inputs_.empty()) {
+            for (uint32_t v : f.term_var) if ((v >> 29) == Variable::Input) throw std::invalid_argument("a constraint names public input " + std::to_string(v & 0x1fffffffu) + ", and this assembly has made none");
+            return;
+        }
+        std::unordered_map<Scalar, uint32_t, KeyHash> derived;
+        for (size_t k = 0; k < f.term_var.size(); k++) {
+            if ((f.term_var[k] >> 29) != Variable::Input) continue;
+            const uint32_t p = f.term_var[k] & 0x1fffffffu;
+            if (p >= inputs_.size()) throw std::invalid_argument("a constraint names public input " + std::to_string(p) + " of " + std::to_string(inputs_.size()));
+            if (!resolve) continue;
+            const Scalar c = coef_[f.term_coef[k]] * inputs_[p];
+            uint32_t id;
+            const auto own = coef_index_.find(c);
+            if (own != coef_index_.end()) id = own->second;
+            else {
+                const auto it = derived.find(c);
+                if (it != derived.end()) id = it->second;
+                else { id = (uint32_t)(f.coef.size() / 32); f.coef.resize(f.coef.size() + 32); c.to_bytes(&f.coef[32 * (size_t)id]); derived.emplace(c, id); }
+            }
+            f.term_var[k] = Variable::one().packed(); f.term_coef[k] = id;
+        }
     }
 public:
     size_t num_constraints() const { return row_ptr_.size() - 1; }
+    // A public input of this proof: a scalar prover and verifier both know, named in linear combinations like any variable.  To the proof it is the constant
+    // c * x wherever a term (input, c) stands; a circuit template keeps the term and takes x with every assign (include/bpg.h bpg_prover_input).
+    Variable input(const Scalar &x) {
+        if (inputs_.size() >= 0x1fffffffu) throw std::invalid_argument("input: too many public inputs");
+        inputs_.push_back(x.is_canonical() ? x : x.reduced());
+        return Variable{Variable::Input, (uint32_t)(inputs_.size() - 1)};
+    }
+    const std::vector<Scalar> &inputs() const { return inputs_; }
 };
 
 class Engine;   // engine.hip
@@ -275,6 +311,7 @@ public:
     }
     void constrain(const LinearCombination &lc) override { push_row(lc); }
     // recorded when lc is exactly ONE multiplier variable with coefficient one plus constants that sum to zero (a sponge state is `cube.o + 0`); else ignored
+    // (a committed term or a public input beside it: ignored - the value is then no multiplier's own)
     void note_value(const LinearCombination &lc, uint32_t tag) override {
         const Variable *var = nullptr;
         Scalar constant;
@@ -308,6 +345,7 @@ public:
             case Variable::MultiplierRight: if (idx >= aR_.size()) throw std::invalid_argument("linear combination refers to an unallocated multiplier"); x = &aR_[idx]; break;
             case Variable::MultiplierOutput: if (idx >= aO_.size()) throw std::invalid_argument("linear combination refers to an unallocated multiplier"); x = &aO_[idx]; break;
             case Variable::Committed: if (idx >= v_.size()) throw std::invalid_argument("linear combination refers to an uncommitted variable"); x = &v_[idx]; break;
+            case Variable::Input: if (idx >= inputs_.size()) throw std::invalid_argument("linear combination refers to a public input this prover has not made"); x = &inputs_[idx]; break;
             default: throw std::invalid_argument("linear combination holds an unknown variable kind");
             }
             static const Scalar MINUS_ONE = -Scalar::one();
@@ -318,12 +356,13 @@ public:
         return acc;
     }
 
-    FlatCircuit flatten() {
+    // keep_inputs (bpg_prover_template_instance): the rows keep their input terms, for a template; else they leave as constants (export_rows)
+    FlatCircuit flatten(bool keep_inputs = false) {
         resolve_hints();
         FlatCircuit f; f.n = aL_.size(); f.m = v_.size();
         f.aL.resize(f.n * 32); f.aR.resize(f.n * 32); f.aO.resize(f.n * 32);
         for (size_t i = 0; i < f.n; i++) { red(aL_[i]).to_bytes(&f.aL[32 * i]); red(aR_[i]).to_bytes(&f.aR[32 * i]); red(aO_[i]).to_bytes(&f.aO[32 * i]); }
-        export_rows(f);
+        export_rows(f, !keep_inputs);
         return f;
     }
 

@@ -17,6 +17,11 @@
 // never another lane's.  (A sponge whose block states are checkpointed: every block a segment at level 0.  A Merkle path whose node hashes are: two levels.)
 // Whether the caller's values ARE what the circuit computes is checked on the device after the last level (k_witness_ck_verify).  No checkpoints: the
 // schedule and the stream are bit for bit what they were.
+// A PUBLIC INPUT (Variable::Input, WitnessProgramView::n_inputs) is a value the caller hands to assign and nothing in the circuit computes.  It is read like a
+// committed value: a level-0 source, and a multiplier that names an input its segment has not named opens a segment.  (LessThan against a public bound: the
+// 4 segments on 1 level of LessThan against a constant; a hint run whose source is one input term is a lane of its own.)  The packer writes such a term with
+// the packed kind WIT_KIND_INPUT.  In the ROWS a term (input p, coefficient index ci) becomes a constant term on a DERIVED coefficient slot that every assign
+// fills with coef[ci] * x_p (with_parameter_slots, k_input_slots).  No inputs: schedule, stream and slot layout are bit for bit what they were.
 #pragma once
 #include <cstdint>
 #include <stdexcept>
@@ -56,7 +61,11 @@ inline void check_witness_program(const FlatView &c, const WitnessProgramView &p
             if (p.term_coef[k] >= c.ncoef) throw std::invalid_argument("template: coefficient index out of range in the witness program");
             if (kind <= 2) { if (idx >= i) throw std::invalid_argument("template: multiplier " + std::to_string(i) + " refers to multiplier " + std::to_string(idx) + " (a multiplier may read only earlier multipliers and committed values)"); }
             else if (kind == 3) { if (idx >= c.m) throw std::invalid_argument("template: committed index out of range in the witness program"); }
-            else if (kind != 4) throw std::invalid_argument("template: bad variable kind in the witness program");
+            else if (kind == Variable::Input && p.n_inputs) {
+                if (idx >= p.n_inputs) throw std::invalid_argument("template: multiplier " + std::to_string(i) + " names public input " + std::to_string(idx) + " (the template takes " + std::to_string(p.n_inputs) + ")");
+            }
+            else if (kind != 4) throw std::invalid_argument("template: bad variable kind in the witness program (term " + std::to_string(k) + ", of multiplier " + std::to_string(i) + ", has kind " + std::to_string(kind) +
+                                                            (kind == Variable::Input ? ": a public input, which only bpg_r1cs_upload_template_inputs takes)" : ")"));
         }
     if (p.n_hints && (!p.hint_mul || !p.hint_kind || !p.hint_arg)) throw std::invalid_argument("template: n_hints without hint arrays");
     for (uint64_t k = 0; k < p.n_hints; k++) {
@@ -65,7 +74,9 @@ inline void check_witness_program(const FlatView &c, const WitnessProgramView &p
         if (k && p.hint_mul[k - 1] >= i) throw std::invalid_argument("template: hinted multipliers must be strictly ascending");
         if (p.hint_kind[k] != WITNESS_HINT_BIT_PAIR) throw std::invalid_argument("template: unknown hint kind " + std::to_string(p.hint_kind[k]));
         if (p.hint_arg[k] >= 256) throw std::invalid_argument("template: hint bit " + std::to_string(p.hint_arg[k]) + " (a scalar has 256 bits)");
-        if (p.lc_ptr[2 * i + 1] != p.lc_ptr[2 * i + 2]) throw std::invalid_argument("template: hinted multiplier " + std::to_string(i) + " has a right list (its left list is the source, the right list is empty)");
+        if (p.lc_ptr[2 * i + 1] != p.lc_ptr[2 * i + 2])
+            throw std::invalid_argument("template: hinted multiplier " + std::to_string(i) + " has a right list" + ((p.term_var[p.lc_ptr[2 * i + 1]] >> 29) == Variable::Input ? " that names a public input" : "") +
+                                        " (its left list is the source, the right list is empty)");
     }
     if (p.n_params && !p.param_rows) throw std::invalid_argument("template: n_params without param_rows");
     for (uint64_t k = 0; k < p.n_params; k++) {
@@ -104,7 +115,7 @@ inline bool hint_same_source(const WitnessProgramView &p, uint64_t k) {
 inline WitnessSchedule build_witness_schedule(uint64_t n, uint64_t m, const WitnessProgramView &p) {
     WitnessSchedule S;
     const uint32_t NONE = UINT32_MAX;
-    std::vector<uint32_t> seg_of(n), seen_mul(n, NONE), seen_v(m, NONE), seen_ck(p.n_ck, NONE);    // seen_*: the last segment that named this value from outside
+    std::vector<uint32_t> seg_of(n), seen_mul(n, NONE), seen_v(m, NONE), seen_ck(p.n_ck, NONE), seen_in(p.n_inputs, NONE);    // seen_*: the last segment that named this value from outside
     const std::unordered_map<uint32_t, uint32_t> ck_at = checkpoint_index(p);
     auto ck_of = [&](uint32_t var) { if (ck_at.empty()) return NONE; const auto it = ck_at.find(var); return it == ck_at.end() ? NONE : it->second; };
     uint32_t seg = NONE, first = 0;
@@ -116,6 +127,7 @@ inline WitnessSchedule build_witness_schedule(uint64_t n, uint64_t m, const Witn
             const uint32_t kind = p.term_var[k] >> 29, idx = p.term_var[k] & 0x1fffffffu;
             const uint32_t ck = kind <= 2 ? ck_of(p.term_var[k]) : NONE;
             if (kind == 3) cut = seen_v[idx] != seg;
+            else if (kind == Variable::Input) cut = seen_in[idx] != seg;
             else if (ck != NONE) cut = seen_ck[ck] != seg;
             else if (kind <= 2 && idx < first) cut = seen_mul[idx] != seg;
         }
@@ -125,6 +137,7 @@ inline WitnessSchedule build_witness_schedule(uint64_t n, uint64_t m, const Witn
             const uint32_t kind = p.term_var[k] >> 29, idx = p.term_var[k] & 0x1fffffffu;
             const uint32_t ck = kind <= 2 ? ck_of(p.term_var[k]) : NONE;
             if (kind == 3) seen_v[idx] = seg;
+            else if (kind == Variable::Input) seen_in[idx] = seg;                    // the caller's value: a level-0 source
             else if (ck != NONE) seen_ck[ck] = seg;                                  // the caller's value: no level, whoever computes it
             else if (kind <= 2 && idx < first) { seen_mul[idx] = seg; S.seg_level[seg] = std::max(S.seg_level[seg], S.seg_level[seg_of[idx]] + 1); }
         }
@@ -175,6 +188,7 @@ inline PackedWitnessProgram pack_witness_program(const FlatView &c, const Witnes
     PackedWitnessProgram P;
     const std::unordered_map<uint32_t, uint32_t> ck_at = checkpoint_index(p);
     auto packed_var = [&](uint32_t var) {
+        if ((var >> 29) == Variable::Input) return WIT_KIND_INPUT << 29 | (var & 0x1fffffffu);
         if (ck_at.empty()) return var;
         const auto it = ck_at.find(var);
         return it == ck_at.end() ? var : (WIT_KIND_CHECKPOINT << 29 | it->second);
@@ -223,7 +237,37 @@ inline PackedWitnessProgram pack_witness_program(const FlatView &c, const Witnes
 
 // Parameter rows (bpg_witness_program.param_rows): row r's constant terms become ONE term on a coefficient slot of its own, ncoef + k for parameter k, which
 // starts at the sum of the constants it replaces (zero when the row had none) and is overwritten by every assign().  The other terms keep their order.
-inline FlatCircuit with_parameter_slots(const FlatView &c, const WitnessProgramView &p) {
+// Input terms (bpg_r1cs_upload_template_inputs): a term (input p, coefficient index ci) of a row becomes a constant term on a DERIVED slot, one per distinct pair
+// (p, ci) in the order the rows name them, laid out behind the parameter slots: slot s is coefficient ncoef + n_params + s and holds coef[ci] * x_p, which
+// every assign writes (k_input_slots).  derived (out): the pairs, slot by slot.  input_values (n_inputs x 32, may be null): what the slots start with.
+struct InputSlot { uint32_t p, ci; };
+inline FlatCircuit with_parameter_slots(const FlatView &c, const WitnessProgramView &p, std::vector<InputSlot> *derived = nullptr, const uint8_t *input_values = nullptr) {
+    if (p.n_inputs) {
+        if (!derived) throw std::logic_error("template: input slots without a list to keep them in");
+        // the parameter pass first, over the caller's table: it folds the constants of a parameter row and keeps every other term, input terms among them, as
+        // it is - an input term beside a parameter slot stays a term of its own
+        WitnessProgramView q = p; q.n_inputs = 0;
+        FlatCircuit f = with_parameter_slots(c, q);
+        const uint64_t first = c.ncoef + p.n_params, room = (uint64_t)WIT_COEF_INDEX_MASK + 1 - std::min<uint64_t>(first, WIT_COEF_INDEX_MASK);
+        std::unordered_map<uint64_t, uint32_t> slot_of;
+        for (size_t k = 0; k < f.term_var.size(); k++) {
+            if ((f.term_var[k] >> 29) != Variable::Input) continue;
+            const uint32_t ip = f.term_var[k] & 0x1fffffffu, ci = f.term_coef[k];
+            if (ip >= p.n_inputs) throw std::invalid_argument("template: a constraint names public input " + std::to_string(ip) + " (the template takes " + std::to_string(p.n_inputs) + ")");
+            const auto at = slot_of.emplace((uint64_t)ip << 32 | ci, (uint32_t)derived->size());
+            if (at.second) {
+                if (derived->size() >= room) throw std::invalid_argument("template: the derived coefficient slots of the public inputs are too many");
+                derived->push_back(InputSlot{ip, ci});
+            }
+            f.term_var[k] = Variable::one().packed(); f.term_coef[k] = (uint32_t)(first + at.first->second);
+        }
+        f.coef.resize(32 * (first + derived->size()));
+        for (size_t s = 0; s < derived->size() && input_values; s++) {
+            const Scalar x = Scalar::from_bytes_mod_order(c.coef + 32 * (size_t)(*derived)[s].ci) * Scalar::from_bytes_mod_order(input_values + 32 * (size_t)(*derived)[s].p);
+            x.to_bytes(&f.coef[32 * (first + s)]);
+        }
+        return f;
+    }
     FlatCircuit f; f.n = c.n; f.m = c.m;
     std::vector<int64_t> param_of(c.q, -1);
     for (uint64_t k = 0; k < p.n_params; k++) param_of[p.param_rows[k]] = (int64_t)k;
@@ -253,6 +297,9 @@ struct TemplatePlan {
     FlatCircuit slotted;            // the instance's rows with parameter slots (no witness)
     uint64_t n_params = 0, param_first = 0;
     std::vector<uint32_t> ck_var;   // the checkpointed variables, in the caller's order (empty: none)
+    // public inputs: how many values assign takes, and the derived coefficient slots [slot_first, slot_first + in_slots.size()) of the rows, kept resident
+    uint64_t n_inputs = 0, slot_first = 0;
+    std::vector<InputSlot> in_slots;
 };
 
 }  // namespace bpg

@@ -9,6 +9,8 @@
 // The flags leave 29 bits for a right-term count.
 // A term that names a CHECKPOINTED variable (bpg_witness_checkpoints) carries the kind WIT_KIND_CHECKPOINT and, as its index, the position in the checkpoint
 // list: the reader takes the value the caller handed to assign.  The kind exists in this stream only; the variable kinds of include/bpg.h stay 0..4.
+// A term that names a PUBLIC INPUT of the proof (Variable::Input, bpg_r1cs_upload_template_inputs) carries the kind WIT_KIND_INPUT and the input's index: the
+// reader takes the value the caller handed to assign, as it does for a checkpoint.  This kind too exists in this stream only (the instance says 5, BPG_VAR_INPUT).
 #pragma once
 #include <cstdint>
 
@@ -18,6 +20,6 @@ constexpr uint32_t WIT_SAME_AS_LEFT = 1u << 31, WIT_HINT_BIT_PAIR = 1u << 30, WI
 constexpr uint32_t WIT_RIGHT_COUNT_MASK = WIT_HINT_SAME_SOURCE - 1u, WIT_HINT_ARG_MASK = 0xffu;
 constexpr uint32_t WIT_CLASS_SHIFT = 30, WIT_COEF_INDEX_MASK = (1u << WIT_CLASS_SHIFT) - 1u;
 constexpr uint32_t WIT_COEF_GENERAL = 0, WIT_COEF_PLUS_ONE = 1, WIT_COEF_MINUS_ONE = 2;
-constexpr uint32_t WIT_KIND_CHECKPOINT = 5;
+constexpr uint32_t WIT_KIND_CHECKPOINT = 5, WIT_KIND_INPUT = 6;
 
 }  // namespace bpg

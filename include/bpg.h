@@ -57,6 +57,11 @@ typedef int32_t bpg_status;
 #define BPG_VAR_MULTIPLIER_OUTPUT 2u
 #define BPG_VAR_COMMITTED 3u
 #define BPG_VAR_ONE 4u
+/* A PUBLIC INPUT of the proof (bpg_prover_input / bpg_verifier_input; "Public inputs in circuit templates" below): legal in term_var of an instance and of a
+ * witness program ONLY for bpg_r1cs_upload_template_inputs.  Every other entry point that takes an instance or a program - bpg_r1cs_upload, bpg_r1cs_prove,
+ * bpg_r1cs_verify, bpg_r1cs_verify_batch, bpg_r1cs_prove_batch, the pool, the older template uploads - refuses the kind before any device work with
+ * BPG_ERR_INVALID_ARGUMENT, and bpg_last_error names the term.  (bpg_prover_instance and bpg_verifier_instance never export it: see below.) */
+#define BPG_VAR_INPUT 5u
 #define BPG_TRANSCRIPT_STATE_BYTES 203        /* STROBE-128: 200 state bytes, pos, pos_begin, cur_flags */
 
 typedef struct bpg_ctx bpg_ctx;
@@ -82,7 +87,7 @@ typedef struct {
 
 /* ---------------------------------------------------------------------------------------------------- PART 1: hot path */
 /* ABI version of this header.  Rules: structs the CALLER allocates either carry a struct_size (bpg_config: fields are only ever added at the end and
- * read when struct_size covers them) or are frozen (bpg_timings, bpg_r1cs_instance, bpg_batch_item, bpg_template_item, bpg_template_commit_item, bpg_template_ck_item, bpg_witness_program, bpg_witness_hints, bpg_witness_checkpoints, bpg_check_report, bpg_term, bpg_lc); a field never changes type or
+ * read when struct_size covers them) or are frozen (bpg_timings, bpg_r1cs_instance, bpg_batch_item, bpg_template_item, bpg_template_commit_item, bpg_template_ck_item, bpg_template_in_item, bpg_witness_program, bpg_witness_hints, bpg_witness_checkpoints, bpg_check_report, bpg_term, bpg_lc); a field never changes type or
  * meaning.  BPG_ABI_VERSION grows when something a version-7 host relies on is extended (a new field, a new flag value); functions ADDED since
  * version 7 (bpg_r1cs_prove_batch, the circuit-template calls) did not raise it: a host that needs one looks the symbol up (dlsym) and treats its
  * absence as "not supported".  A host checks bpg_abi_version() >= the BPG_ABI_VERSION it was compiled against. */
@@ -219,8 +224,10 @@ bpg_status bpg_r1cs_prove_batch(bpg_ctx *ctx, uint64_t count, const bpg_batch_it
  * combinations handed to multiply(), WITHOUT the -a_L[i] / -a_R[i] terms the constraint rows carry.  A term may name committed values, the constant One
  * and multipliers below i.  param_rows names constraint rows whose CONSTANT TERM changes with the witness (the root in `hash - root = 0`, the image of a
  * preimage proof, the right-hand side of an equality): each such row's constant terms are replaced by one term on a coefficient slot of its own, which
- * starts at their sum (zero for a row without one) and is overwritten by every bpg_r1cs_assign.  Constants that flow INTO MULTIPLICATIONS (instance
- * leaves of a Merkle pattern, MiMC keys, round constants) are part of the program and stay fixed for the life of the template.
+ * starts at their sum (zero for a row without one) and is overwritten by every bpg_r1cs_assign.  Constants that flow INTO MULTIPLICATIONS are part of
+ * the program.  Those the gadget code itself brings - MiMC keys, round constants - stay fixed for the life of the template.  The instance values of a
+ * statement - the public bound of LessThan, the right-hand side of Inequality, an instance set, the instance siblings of a Merkle pattern - need not:
+ * assemble them as PUBLIC INPUTS (bpg_prover_input, below) and every assign brings their values.
  *
  * bpg_r1cs_upload_template = bpg_r1cs_upload plus the program: the witness of `inst`, if it carries one, is uploaded as usual (the first proof needs no
  * assign); with aL = aR = aO = NULL the circuit has no witness until the first bpg_r1cs_assign (proving it before: BPG_ERR_MISSING_ASSIGNMENT).
@@ -384,6 +391,79 @@ typedef struct {                          /* frozen */
 } bpg_template_ck_item;
 bpg_status bpg_r1cs_prove_template_batch_checkpointed(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, const bpg_template_ck_item *items, int32_t commit,
                                                       bpg_status *status_out);
+/* PUBLIC INPUTS in circuit templates: instance values that change per proof.  (Additions to ABI version 7; the frozen structs are unchanged.)
+ * A public input is a scalar x_p known to prover and verifier.  bpg_prover_input / bpg_verifier_input hand its value over and return a variable of kind
+ * BPG_VAR_INPUT, index p counting from 0, which is named in linear combinations like any variable: a caller passes it wherever it passed a constant before
+ * (right_hand of LessThan and Inequality, instance_vars of SetMembership and MerkleTree256, root, image).  Gadget code does not change.  To the proof system
+ * a term (input p, c) IS the constant c x_p: a proof made from a template with inputs X is byte for byte the proof of a fresh host assembly with those constants
+ * (the transcript holds no constraint, the prover reads no constant term).
+ * RESOLVED EXPORT: bpg_prover_instance, bpg_verifier_instance and everything built on them (bpg_prover_prove, bpg_verifier_verify, the oracle) fold every such
+ * term into a constant term on the product c x_p (new products behind the table's own entries); they never show kind 5, and an assembly without inputs
+ * exports bit for bit what it always did.  TEMPLATE EXPORT: bpg_prover_template_instance keeps the terms (coefficients interned as for any term), returns the
+ * n_inputs values in input order, and bpg_prover_witness_program(_hinted) on such a prover keeps them in the program too, hint sources included.
+ * bpg_r1cs_upload_template_inputs: bpg_r1cs_upload_template_checkpointed for such an instance and program.  n_inputs == 0 makes it that call (same schedule,
+ * same record stream).  input_values (n_inputs x 32): the inputs of the witness `inst` carries; NULL only when it carries none.  An input is read like a
+ * committed value: a level-0 source of the schedule (LessThan against a public bound: the 4 segments on 1 level of LessThan against a constant).  In the rows
+ * a term (input p, coefficient index ci) becomes a constant term on a DERIVED coefficient slot, one per distinct pair, behind the parameter slots; every assign
+ * fills it with coef[ci] x_p on the device (k_input_slots) before anything reads a constant term.  Refused besides, with BPG_ERR_INVALID_ARGUMENT before any
+ * device work and bpg_last_error naming the reason: an input index >= n_inputs (in a row or in the program), an input term in a hint's right list (which is
+ * empty), NULL input_values for an instance with a witness, more derived slots than the coefficient index holds (2^30 with the table and the parameters).
+ * bpg_r1cs_assign_inputs: bpg_r1cs_assign_checkpointed plus the n_inputs values (32 bytes each, any value below 2^255, reduced mod l on the device as v is).
+ * n_inputs must match the template; input_values non-NULL when n_inputs > 0.  CANONICAL INPUTS ONLY: as for the bit hints above, byte identity with a host
+ * assembly is promised when the value handed over is canonical (below l) - the host's range_proof reads the raw bytes of the assignment it was handed, the
+ * device the canonical representative.  A refused or mismatching call leaves the circuit without a witness; the equal-scalar sets are dropped as by every assign.
+ * bpg_r1cs_prove_template_batch_inputs: bpg_r1cs_prove_template_batch_checkpointed with the frozen struct bpg_template_in_item - the eleven fields of
+ * bpg_template_ck_item, same order and meaning, then input_values, what bpg_r1cs_assign_inputs takes for this template.  Each item is byte for byte
+ * bpg_r1cs_assign_inputs + bpg_r1cs_prove_resident for it alone (commitments first when commit is set).  A NULL input_values with n_inputs > 0 fails that item
+ * alone.  In a lockstep wave the inputs travel beside the checkpoint values, the witness evaluation reads item k's inputs, and one launch of k_input_slots
+ * writes every item's derived slots into its range of the wave's coefficient table.  Items off the lockstep path (N > 2^14, BPG_TT_ORIG_LG=0, expanded
+ * blinding) run bpg_r1cs_assign_inputs + bpg_r1cs_prove_resident in item order.  On a template WITHOUT inputs it is that call, byte for byte.
+ * On a template WITH inputs: bpg_r1cs_assign, bpg_r1cs_assign_checkpointed, bpg_r1cs_prove_template_batch, _commit and _checkpointed are refused with
+ * BPG_ERR_INVALID_ARGUMENT before any work (their arguments carry no input values), as the frozen calls refuse a checkpointed template;
+ * bpg_r1cs_template_repeat and bpg_r1cs_template_join refuse it as a source (a repeat or join with per-item inputs is out of scope here), and with them the
+ * repeat-based batch check of the Python layer; bpg_r1cs_prove_resident, bpg_r1cs_verify_resident and bpg_r1cs_check serve it as any template -
+ * bpg_r1cs_verify_resident checks against the inputs of the last assign. */
+typedef struct {                          /* frozen */
+    const uint8_t *v;                     /* m x 32: committed values, as bpg_r1cs_assign takes them */
+    const uint8_t *param_values;          /* n_params x 32, in the order of param_rows */
+    uint8_t *transcript_state;            /* 203 B, in: commit == 0 after every "V" append, else BEFORE them; out: after the proof */
+    const uint8_t *v_blinding;            /* m x 32 */
+    const uint8_t *rng_seed;              /* 32 B */
+    uint32_t flags;
+    uint8_t *proof_out; uint64_t *proof_len;   /* in = capacity, out = bytes written */
+    uint8_t *commitments_out;             /* commit != 0: m x 32, the commitments in commit order */
+    const uint8_t *ck_values;             /* n_ck x 32, what bpg_r1cs_assign_checkpointed takes for this template */
+    uint64_t *first_mismatch;             /* NULL allowed; out: UINT64_MAX, or the lowest mismatching checkpoint of THIS item */
+    const uint8_t *input_values;          /* n_inputs x 32, what bpg_r1cs_assign_inputs takes for this template */
+} bpg_template_in_item;
+bpg_status bpg_r1cs_upload_template_inputs(bpg_ctx *ctx, const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                           const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, const uint8_t *input_values /* n_inputs x 32 */,
+                                           bpg_circuit **out);
+bpg_status bpg_r1cs_assign_inputs(bpg_ctx *ctx, bpg_circuit *c, uint64_t m, const uint8_t *v, uint64_t n_params, const uint8_t *param_values,
+                                  uint64_t n_ck, const uint8_t *ck_values, uint64_t *first_mismatch, uint64_t n_inputs, const uint8_t *input_values /* n_inputs x 32 */);
+bpg_status bpg_r1cs_prove_template_batch_inputs(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, const bpg_template_in_item *items, int32_t commit,
+                                                bpg_status *status_out);
+/* The hooks below for a program with public inputs (no device): n_inputs as bpg_r1cs_upload_template_inputs takes it, input_values n_inputs x 32 (the batch
+ * hook: count x n_inputs x 32, item-major).  The eval hooks are their _checkpointed siblings - the same interpreter compiled for the host, the same poison of
+ * a_L, a_R, a_O, the same reverse segment order within a level.  bpg_test_template_inputs_instance: the resident rows, row-major, as an assign of param_values
+ * and input_values leaves them (the counterpart of bpg_test_template_repeat_instance: every input term a constant term on its derived slot).
+ * bpg_test_circuit_handle_inputs: bpg_test_circuit_handle_hinted for such a program. */
+bpg_status bpg_test_template_schedule_inputs(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                             const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, char *out, uint64_t cap);
+bpg_status bpg_test_template_packed_inputs(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                           const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, uint32_t *stream_out, uint64_t cap, uint64_t *words_out);
+bpg_status bpg_test_template_eval_inputs(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                         const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, const uint8_t *v, const uint8_t *ck_values,
+                                         const uint8_t *input_values, uint8_t *aL, uint8_t *aR, uint8_t *aO, uint64_t *first_mismatch);
+bpg_status bpg_test_template_eval_batch_inputs(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                               const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, uint64_t count, const uint8_t *v,
+                                               const uint8_t *ck_values, const uint8_t *input_values, uint8_t *aL, uint8_t *aR, uint8_t *aO,
+                                               uint64_t *first_mismatch_out);
+bpg_status bpg_test_template_inputs_instance(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, uint64_t n_inputs,
+                                             const uint8_t *param_values, const uint8_t *input_values, uint64_t *row_ptr, uint64_t row_cap, uint32_t *term_var,
+                                             uint32_t *term_coef, uint64_t term_cap, uint8_t *coef, uint64_t coef_cap, uint64_t *nnz_out, uint64_t *ncoef_out);
+bpg_status bpg_test_circuit_handle_inputs(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                          const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, bpg_circuit **out);
 /* TEST HOOKS, no device needed.  bpg_test_template_schedule: the checks of bpg_r1cs_upload_template and the schedule as JSON {"levels", "segments",
  * "max_levels", "seg_first": [segments + 1], "seg_level": [...], "level_segments": [...]}: segment s is multipliers [seg_first[s], seg_first[s+1]), one
  * device lane walks it in order, and everything it reads from another segment lies at a lower level.  bpg_test_template_eval: the device's interpreter
@@ -633,6 +713,13 @@ bpg_status bpg_prover_witness_program(bpg_prover *p, bpg_witness_program *out);
  * bpg_prover_allocate_bit: ConstraintSystem::allocate_bit for hosts that drive the mirror directly - the multiplier range_proof makes for bit `bit` (0..255)
  * of `source`, whose assigned value is source_value (raw little-endian bytes, as range_proof reads them): a_L = 1 - b, a_R = b.  It adds no constraint. */
 bpg_status bpg_prover_witness_program_hinted(bpg_prover *p, bpg_witness_program *program_out, bpg_witness_hints *hints_out);
+/* Public inputs ("Public inputs in circuit templates" above).  bpg_prover_input: a new input with this value (Scalar::from_bits semantics, kept reduced mod l),
+ * *var_out = BPG_VAR_INPUT << 29 | p.  bpg_prover_template_instance: bpg_prover_instance with the input terms KEPT in the rows (kind 5), for
+ * bpg_r1cs_upload_template_inputs; *n_inputs_out and *inputs_out (n_inputs x 32, input order) are this prover's inputs.  The pointers stay valid until the
+ * prover is next mutated or freed.  Without inputs it exports what bpg_prover_instance exports. */
+bpg_status bpg_prover_input(bpg_prover *p, const uint8_t value[32], uint32_t *var_out);
+bpg_status bpg_prover_template_instance(bpg_prover *p, bpg_r1cs_instance *inst_out, const uint8_t **v_out, const uint8_t **v_blinding_out, uint64_t *n_inputs_out,
+                                        const uint8_t **inputs_out);
 /* Checkpoint candidates (bpg_witness_checkpoints).  A gadget that computes a value its caller may know anyway says so through ConstraintSystem::note_value;
  * MimcHash256 - and MerkleTree256 through it - notes the sponge state after every absorbed block, tag = the block index, bit 31 set on the sponge's last block
  * (its digest: a Merkle node).  A prover keeps the note when the value is exactly one multiplier variable; it costs no multiplier, constraint or transcript byte.
@@ -680,6 +767,7 @@ bpg_status bpg_prover_prove(bpg_prover *p, uint64_t gens_capacity, const uint8_t
 bpg_status bpg_verifier_new(bpg_transcript *t, bpg_verifier **out);                             /* Verifier::new */
 void bpg_verifier_free(bpg_verifier *v);
 bpg_status bpg_verifier_commit(bpg_verifier *v, const uint8_t com[32], uint32_t *var_out);       /* Verifier::commit */
+bpg_status bpg_verifier_input(bpg_verifier *v, const uint8_t value[32], uint32_t *var_out);      /* the verifier's side of bpg_prover_input */
 uint64_t bpg_verifier_num_vars(const bpg_verifier *v);                                          /* fork getter, verifier.rs:89 */
 bpg_status bpg_verifier_instance(bpg_verifier *v, bpg_r1cs_instance *out, const uint8_t **commitments_out);
 /* Verifier::verify(&proof, &pc_gens, &bp_gens) on the GPU of ctx */
