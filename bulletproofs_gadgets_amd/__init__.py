@@ -421,6 +421,24 @@ class Context:
                                      out, ev, C.c_uint64(cap)))
         return [out.raw[32 * m:32 * m + 32] for m in range(nmsm)], json.loads(ev.value.decode())
 
+    FOLD_KERNELS = ("k_fold_points_wnaf", "k_fold_points_quadw", "k_fold_points_quad", "k_fold_points_split", "k_fold_points_regw", "k_fold_points_reg",
+                    "k_fold_points")          # the values of `kernel` in test_fold, in order (csrc/host/fold_plan.hpp FoldKernel)
+
+    def test_fold(self, kernel, lgMr, rounds, first, n, sG, sH, u_ch):
+        """bpg_test_fold: the generator fold of one group of `rounds` rounds on the context's own generator tables, through the prover's launch path.  kernel: -1
+        (the chooser's), 0..6 or a name of FOLD_KERNELS; sG, sH: 2^rounds - 1 canonical 32-byte scalars each (lists, or their concatenations); u_ch: 32 bytes.
+        Returns (the 2 * 2^lgMr compressed points, G side then H side; the evidence dict: what was launched)."""
+        import json
+        if isinstance(kernel, str):
+            kernel = self.FOLD_KERNELS.index(kernel)
+        count = 2 << lgMr if 0 <= lgMr <= 26 else 2             # a larger Mr is beyond any generator table: refused before anything is written
+        out, ev = _buf(32 * count), _buf(1024)
+        nbytes = 32 * ((1 << min(max(rounds, 1), 5)) - 1)          # what the library reads of sG, sH (None goes through as NULL: a refusal)
+        join = lambda name, s: None if s is None else _exact(name, s if isinstance(s, (bytes, bytearray)) else b"".join(s), nbytes)
+        _chk(lib().bpg_test_fold(self._h, C.c_int32(kernel), C.c_uint32(lgMr), C.c_uint32(rounds), C.c_uint32(first), C.c_uint64(n), join("sG", sG), join("sH", sH),
+                                 None if u_ch is None else _exact("u_ch", u_ch, 32), out, ev, C.c_uint64(1024)))
+        return [out.raw[32 * i:32 * i + 32] for i in range(count)], json.loads(ev.value.decode())
+
     def test_fe_ops(self, op, a_list, b_list):
         n = len(a_list)
         out = _buf(32 * n)

@@ -231,6 +231,17 @@ bpg_status bpg_test_msm(bpg_ctx *ctx, uint32_t nmsm, uint32_t nseg, const bpg_ms
     });
 }
 
+bpg_status bpg_test_fold(bpg_ctx *ctx, int32_t kernel, uint32_t lgMr, uint32_t rounds, uint32_t first, uint64_t n, const uint8_t *sG, const uint8_t *sH,
+                         const uint8_t u_ch[32], uint8_t *out, char *evidence, uint64_t cap) {
+    return guard([&] {
+        if (!ctx) throw DeviceError("test_fold: no device context (the fold runs on the GPU only)");
+        REQUIRE(sG && sH && u_ch && out && evidence && cap >= 512);
+        const std::string r = ctx->engine->test_fold(kernel, lgMr, rounds, first, n, sG, sH, u_ch, out);
+        if (r.size() + 1 > cap) throw std::invalid_argument("test_fold: evidence buffer too small (" + std::to_string(r.size() + 1) + " bytes needed)");
+        std::memcpy(evidence, r.c_str(), r.size() + 1);
+    });
+}
+
 bpg_status bpg_test_decompress(bpg_ctx *ctx, uint64_t n, const uint8_t *in, uint32_t *ok_out, uint8_t *xy_out) {
     return guard([&] {
         if (!ctx) throw DeviceError("test_decompress: no device context (k_decompress runs on the GPU only)");

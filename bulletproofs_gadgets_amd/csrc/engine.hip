@@ -526,6 +526,7 @@ struct Engine::Impl {
     }
     MsmRun msm_last{};                                      // the plan of the last msm() call (host side only: read by the test hook Engine::test_msm after its stream sync, never on the proving path)
     DevBuf test_skip;                                       // skip bitmaps of Engine::test_msm
+    DevBuf test_fold_tab;                                   // the folded table of Engine::test_fold (the prover's own go to ipa_tabA / ipa_tabB)
     std::vector<h51::pt> msm_points(const MsmTicket &t) const {
         std::vector<h51::pt> out(t.nmsm);
         const uint32_t *w = reinterpret_cast<const uint32_t *>(h_wsums.as<uint8_t>() + (size_t)t.slot * WS_SLOT_BYTES);
@@ -564,6 +565,11 @@ struct Engine::Impl {
     struct CscWork { uint32_t *counts, *starts, *cursor, *rowconst, *rowconst_start, *bsum; };
     void transpose_csr(const uint64_t *rp, const uint32_t *tv, const uint32_t *tc, uint64_t q, uint64_t nmul, uint64_t m, const CscWork &W,
                        uint64_t *col_ptr, uint32_t *ent_row, uint32_t *ent_coef, uint32_t *totals);
+    // The generator fold of one group, from the choice of the kernel to the normalised table in dst (2 * shape.Mr points: G side, then H side): what
+    // inner_product() runs after the last round of a group, and what the test hook Engine::test_fold runs on scalars of its caller's choosing.
+    struct FoldRun { FoldKernel kernel; int32_t top; uint32_t nsteps[2], tail[2]; };           // what was launched: top of the bitmap and width-w kernels, step counts of the step kernels
+    FoldRun fold_launch(const FoldShape &shape, const FoldKernel *forced, uint64_t g_M, uint64_t n, const Scalar &u_ch, const std::vector<Scalar> &sG,
+                       const std::vector<Scalar> &sH, const ge_niels *Gst, const ge_niels *Hst, ge_niels *dst);
     void inner_product(Transcript &T, std::vector<uint8_t> &proof, uint64_t n, uint64_t N, const Scalar &yinv, const Scalar &u_ch, const Scalar &w,
                        const ge_niels *Gtab, const ge_niels *Htab, const ge_niels *Bn, ProveTimings *tm, double &t0);
 };
@@ -1123,6 +1129,66 @@ std::string Engine::test_msm(uint32_t nmsm, uint32_t nseg, const MsmSegSpec *seg
     j += "\"starts\": [";
     for (size_t i = 0; i < st.size(); i++) { if (i) j += ","; j += std::to_string(st[i]); }
     j += "]}";
+    return j;
+}
+
+// The generator fold of one group on scalars the caller chose (include/bpg.h bpg_test_fold): Impl::fold_launch() as inner_product() calls it, on the context's own
+// generator tables, then the 2 * Mr folded points compressed.  Returns the JSON evidence of what was launched.
+std::string Engine::test_fold(int32_t kernel, uint32_t lgMr, uint32_t rounds, uint32_t first, uint64_t n, const uint8_t *sG_bytes, const uint8_t *sH_bytes,
+                              const uint8_t u_ch_bytes[32], uint8_t *out) {
+    // every argument is checked here, before anything is queued: no index the caller chose reaches a kernel unchecked
+    if (!sG_bytes || !sH_bytes || !u_ch_bytes || !out) throw std::invalid_argument("test_fold: null pointer");
+    if (rounds < 1 || rounds > 5) throw std::invalid_argument("test_fold: a group has 1..5 rounds");
+    if (first > 1) throw std::invalid_argument("test_fold: first is 0 or 1");
+    if (kernel < -1 || kernel > (int32_t)FoldKernel::Mem) throw std::invalid_argument("test_fold: kernel is -1 (the chooser's) or 0..6");
+    if (lgMr > 31 || (1ull << (lgMr + rounds)) > gens_cap_) throw std::invalid_argument("test_fold: the group-start tables reach beyond the generator tables");
+    const uint64_t g_M = 1ull << (lgMr + rounds);
+    const uint32_t Mr = 1u << lgMr, nterms = (1u << rounds) - 1u;
+    if (first && (n <= g_M / 2 || n > g_M)) throw std::invalid_argument("test_fold: a first group has g_M/2 < n <= g_M");
+    std::vector<Scalar> sG(nterms), sH(nterms);
+    Scalar u_ch; std::memcpy(u_ch.w, u_ch_bytes, 32);
+    if (!u_ch.is_canonical()) throw std::invalid_argument("test_fold: u_ch is not canonical");
+    for (uint32_t t = 0; t < nterms; t++) {
+        std::memcpy(sG[t].w, sG_bytes + 32 * (size_t)t, 32); std::memcpy(sH[t].w, sH_bytes + 32 * (size_t)t, 32);
+        if (!sG[t].is_canonical() || !sH[t].is_canonical()) throw std::invalid_argument("test_fold: scalar " + std::to_string(t) + " is not canonical");
+    }
+    // a forced kernel: wherever choose_fold could name it under some setting of the knobs (its structural conditions; the size thresholds are dropped)
+    const FoldKernel fk = (FoldKernel)(kernel < 0 ? 0 : kernel);
+    if (kernel >= 0) {
+        bool fits = true;
+        switch (fk) {
+        case FoldKernel::QuadW: fits = !first && Mr % 64 == 0 && nterms <= 7; break;
+        case FoldKernel::RegW: fits = !first && Mr % 256 == 0 && nterms <= 7; break;
+        case FoldKernel::Quad: fits = nterms <= 7; break;
+        case FoldKernel::Split: fits = nterms >= 3 && nterms <= 15; break;
+        case FoldKernel::Reg: fits = nterms == 1 || nterms == 3 || nterms == 7 || nterms == 15; break;
+        case FoldKernel::Wnaf: fits = impl_->fold_wnaf >= 3; break;
+        case FoldKernel::Mem: break;
+        }
+        if (!fits) throw std::invalid_argument("test_fold: the chooser never names this kernel for this shape");
+    }
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    I.shared_now = I.shared_variants();
+    if (kernel >= 0 && fk == FoldKernel::Wnaf && !I.odd_ensure()) throw std::invalid_argument("test_fold: no table of odd multiples fits this device");
+    I.test_fold_tab.ensure((size_t)2 * Mr * sizeof(ge_niels)); I.comp.ensure((size_t)2 * Mr * 32);
+    const FoldShape shape{Mr, nterms, first != 0, true};
+    const Impl::FoldRun run = I.fold_launch(shape, kernel >= 0 ? &fk : nullptr, g_M, n, u_ch, sG, sH, I.gens, I.gens + gens_cap_, I.test_fold_tab.as<ge_niels>());
+    BPG_LAUNCH(I, k_compress_niels, dim3(cdiv(2 * Mr, 64)), dim3(64), I.test_fold_tab.as<ge_niels>(), I.comp.as<uint8_t>(), 2 * Mr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, I.comp.p, (size_t)2 * Mr * 32, hipMemcpyDeviceToHost, I.st));
+    HIPCHK(hipStreamSynchronize(I.st));
+    static const char *const name_of[] = {"k_fold_points_wnaf", "k_fold_points_quadw", "k_fold_points_quad", "k_fold_points_split", "k_fold_points_regw",
+                                          "k_fold_points_reg", "k_fold_points"};           // in the order of FoldKernel
+    std::string j = "{\"kernel\": \""; j += name_of[(int)run.kernel]; j += "\"";
+    auto u = [&](const char *k, int64_t v) { j += ", \""; j += k; j += "\": "; j += std::to_string(v); };
+    u("Mr", Mr); u("nterms", nterms); u("first", first); u("n", (int64_t)n);
+    if (run.kernel == FoldKernel::QuadW || run.kernel == FoldKernel::RegW) {
+        j += ", \"nsteps\": [" + std::to_string(run.nsteps[0]) + ", " + std::to_string(run.nsteps[1]) + "]";
+        j += ", \"tail\": [" + std::to_string(run.tail[0]) + ", " + std::to_string(run.tail[1]) + "]";
+    } else u("top", run.top);
+    if (run.kernel == FoldKernel::Wnaf) { u("wnaf", I.eff_wnaf); u("parts", I.eff_parts); u("part_bits", I.fold_part_bits()); }
+    j += "}";
     return j;
 }
 
@@ -1906,6 +1972,74 @@ void Engine::Impl::merge_witness(DeviceCircuit *c, const ge_niels *Gtab, const g
     merge_ms_last = now_ms() - t0;
 }
 
+// ------------------------------------------------------------------------------------------------ generator fold of one group
+// dst[i] = Gst[i] + sum_t sG_t Gst[i + t*Mr], dst[Mr + i] the same on Hst with sH (host/fold_plan.hpp): which kernel folds (forced: the test hook names
+// one), the scalars recoded for that kernel and uploaded, one launch, the roofline bookkeeping, the normalisation.  The caller waits for the stream.
+Engine::Impl::FoldRun Engine::Impl::fold_launch(const FoldShape &shape, const FoldKernel *forced, uint64_t g_M, uint64_t n, const Scalar &u_ch,
+                                               const std::vector<Scalar> &sG, const std::vector<Scalar> &sH, const ge_niels *Gst, const ge_niels *Hst, ge_niels *dst) {
+    Impl &I = *this;
+    const uint32_t Mr = shape.Mr, nterms = shape.nterms;
+    const bool g_first = shape.first;
+    I.scratch_ext.ensure((size_t)2 * Mr * sizeof(ge_ext));         // the folded points before their normalisation (2^18 of them after the first group of three rounds at 2^20)
+    // the group-start tables are the original generators: width-w NAF against their precomputed odd multiples (k_fold_points_wnaf) -
+    // unless no table fits the budget of this device, in which case the other kernels fold them
+    const FoldKnobs knobs = I.fold_knobs();
+    const FoldKernel kernel = forced ? *forced : choose_fold(shape, knobs, fold_wants_tables(shape, knobs) && I.odd_ensure());
+    static const int kid_of[] = {KID_k_fold_points_wnaf, KID_k_fold_points_quadw, KID_k_fold_points_quad, KID_k_fold_points_split, KID_k_fold_points_regw,
+                                 KID_k_fold_points_reg, KID_k_fold_points};          // in the order of FoldKernel
+    const int fold_kid = kid_of[(int)kernel];
+    const dim3 grid(cdiv(2 * Mr, 256)), grid64(cdiv(2 * Mr, 64)), block(256);     // one lane per output; four lanes per output (and the split kernel)
+    ge_ext *fo = I.scratch_ext.as<ge_ext>();
+    // the scalars in the format the kernel reads, written to pinned memory and uploaded
+    FoldRecode rc; FoldWnaf fw; FoldQuadW fq; FoldGroup fg;
+    const bool wnaf = kernel == FoldKernel::Wnaf, steps = kernel == FoldKernel::QuadW || kernel == FoldKernel::RegW;
+    PinBuf &hbuf = steps ? I.h_qsteps : I.h_naf;
+    DevBuf &dbuf = steps ? I.qsteps : I.naf;
+    const size_t bytes = wnaf ? fold_wnaf_bytes(nterms, I.eff_parts) : steps ? (size_t)2 * QW_MAXSTEPS * 4 : fold_naf_words(nterms) * 4;
+    hbuf.ensure(bytes); dbuf.ensure(bytes);
+    FoldRun run{kernel, -1, {0, 0}, {0, 0}};
+    if (wnaf) {                                         // width-w NAF digits per part, against the odd multiples odd_ensure() settled on
+        rc = fold_recode_wnaf(sG, sH, u_ch, Mr, n, g_first, I.eff_wnaf, I.eff_parts, I.fold_part_bits(), hbuf.as<int8_t>());
+        fw.Mr = Mr; fw.nterms = nterms; fw.first_group = g_first; fw.n = (uint32_t)n; fw.cap = (uint32_t)gens_cap; fw.top = rc.top;
+        fw.parts = I.eff_parts; fw.NM = 1u << (I.eff_wnaf - 2);
+        run.top = fw.top;
+    } else if (steps) {                                 // width-4 NAF steps; the multiples the kernel makes live in the arena - no multiscalar sum of this context is in flight during a fold
+        rc = fold_recode_steps(sG, sH, Mr, hbuf.as<uint32_t>(), fq);
+        I.arena.ensure((size_t)3 * nterms * 2 * Mr * sizeof(ge_pniels));
+        for (int c = 0; c < 2; c++) { run.nsteps[c] = fq.nsteps[c]; run.tail[c] = fq.tail[c]; }
+    } else {                                            // plain NAF bitmaps
+        rc = fold_recode_naf(sG, sH, u_ch, Mr, n, g_first, hbuf.as<uint32_t>());
+        fg.Mr = Mr; fg.nterms = nterms; fg.first_group = g_first; fg.n = (uint32_t)n; fg.top = rc.top;
+        run.top = fg.top;
+    }
+    HIPCHK(hipMemcpyAsync(dbuf.p, hbuf.p, bytes, hipMemcpyHostToDevice, st));
+    const uint32_t *nf = dbuf.as<uint32_t>();
+    double device_bytes = 96.0 * 2 * g_M + 128.0 * 2 * Mr;          // 2*g_M points read at 96 B, 2*Mr written at 128 B
+    switch (kernel) {
+    case FoldKernel::Wnaf:
+        BPG_LAUNCH(I, k_fold_points_wnaf, grid, block, I.gens, I.gens_odd, fo, nf, fw);
+        device_bytes = 96.0 * (2.0 * Mr + rc.adds_fm / 7.0) + 128.0 * 2 * Mr;       // one point read per output and per addition
+        break;
+    case FoldKernel::QuadW: BPG_LAUNCH(I, k_fold_points_quadw, grid64, block, Gst, Hst, fo, nf, reinterpret_cast<fe *>(I.arena_at(0)), fq); break;
+    case FoldKernel::Quad: BPG_LAUNCH(I, k_fold_points_quad, grid64, block, Gst, Hst, fo, nf, fg); break;
+    case FoldKernel::Split: BPG_LAUNCH(I, k_fold_points_split, grid64, block, Gst, Hst, fo, nf, fg); break;
+    case FoldKernel::RegW: BPG_LAUNCH(I, k_fold_points_regw, grid, block, Gst, Hst, fo, nf, reinterpret_cast<ge_pniels *>(I.arena_at(0)), fq); break;
+    case FoldKernel::Reg:       // addends in registers: one instantiation per group size (r = 1..4)
+        if (nterms == 1) BPG_LAUNCH_ID(I, fold_kid, k_fold_points_reg<1>, grid, block, Gst, Hst, fo, nf, fg);
+        else if (nterms == 3) BPG_LAUNCH_ID(I, fold_kid, k_fold_points_reg<3>, grid, block, Gst, Hst, fo, nf, fg);
+        else if (nterms == 7) BPG_LAUNCH_ID(I, fold_kid, k_fold_points_reg<7>, grid, block, Gst, Hst, fo, nf, fg);
+        else BPG_LAUNCH_ID(I, fold_kid, k_fold_points_reg<15>, grid, block, Gst, Hst, fo, nf, fg);
+        break;
+    case FoldKernel::Mem: BPG_LAUNCH(I, k_fold_points, grid, block, Gst, Hst, fo, nf, fg); break;
+    }
+    // bookkeeping for the roofline: 2*g_M points read + 2*Mr written at 32 B (information content) resp. in the device formats; field
+    // multiplications: 8 per doubling, 7 per mixed addition (the split variant runs the doublings once per wave of a block)
+    I.prof_note(fold_kid, 32.0 * (2.0 * g_M + 2.0 * Mr), device_bytes,
+                2.0 * Mr * (8.0 * (rc.top + 1) * (kernel == FoldKernel::Split ? (nterms < 4 ? nterms : 4) : 1) + 7.0) + rc.adds_fm);
+    BPG_LAUNCH(I, k_normalize_niels, dim3(cdiv(cdiv(2 * Mr, NORM_K), 256)), dim3(256), I.scratch_ext.as<ge_ext>(), dst, 2 * Mr);
+    return run;
+}
+
 // ------------------------------------------------------------------------------------------------ inner-product argument
 // InnerProductProof::create (dalek inner_product_proof.rs) on l(x) = lv, r(x) = rv with G_factors = (1.., u..), H_factors = y^-i * G_factors
 // and Q = w * B: appends L_k, R_k (lg N pairs) and the final a, b to `proof`.  Rounds above 2^tt_lg generators: grouped folds with
@@ -2031,60 +2165,7 @@ void Engine::Impl::inner_product(Transcript &T, std::vector<uint8_t> &proof, uin
             std::vector<Scalar> sG, sH;
             fold_group_scalars(g_us, yinv_pow2, g_M, g_r, sG, sH);
             ge_niels *dst = (g_index & 1) ? I.ipa_tabB.as<ge_niels>() : I.ipa_tabA.as<ge_niels>();
-            I.scratch_ext.ensure((size_t)2 * Mr * sizeof(ge_ext));         // the folded points before their normalisation (2^18 of them after the first group of three rounds at 2^20)
-            // the group-start tables are the original generators: width-w NAF against their precomputed odd multiples (k_fold_points_wnaf) -
-            // unless no table fits the budget of this device, in which case the other kernels fold them
-            const FoldShape shape{Mr, nterms, g_first, Gst == Gtab && Hst == Htab && Gtab == I.gens};
-            const FoldKnobs knobs = I.fold_knobs();
-            const FoldKernel kernel = choose_fold(shape, knobs, fold_wants_tables(shape, knobs) && I.odd_ensure());
-            static const int kid_of[] = {KID_k_fold_points_wnaf, KID_k_fold_points_quadw, KID_k_fold_points_quad, KID_k_fold_points_split, KID_k_fold_points_regw,
-                                         KID_k_fold_points_reg, KID_k_fold_points};          // in the order of FoldKernel
-            const int fold_kid = kid_of[(int)kernel];
-            const dim3 grid(cdiv(2 * Mr, 256)), grid64(cdiv(2 * Mr, 64)), block(256);     // one lane per output; four lanes per output (and the split kernel)
-            ge_ext *fo = I.scratch_ext.as<ge_ext>();
-            // the scalars in the format the kernel reads, written to pinned memory and uploaded
-            FoldRecode rc; FoldWnaf fw; FoldQuadW fq; FoldGroup fg;
-            const bool wnaf = kernel == FoldKernel::Wnaf, steps = kernel == FoldKernel::QuadW || kernel == FoldKernel::RegW;
-            PinBuf &hbuf = steps ? I.h_qsteps : I.h_naf;
-            DevBuf &dbuf = steps ? I.qsteps : I.naf;
-            const size_t bytes = wnaf ? fold_wnaf_bytes(nterms, I.eff_parts) : steps ? (size_t)2 * QW_MAXSTEPS * 4 : fold_naf_words(nterms) * 4;
-            hbuf.ensure(bytes); dbuf.ensure(bytes);
-            if (wnaf) {                                         // width-w NAF digits per part, against the odd multiples odd_ensure() settled on
-                rc = fold_recode_wnaf(sG, sH, u_ch, Mr, n, g_first, I.eff_wnaf, I.eff_parts, I.fold_part_bits(), hbuf.as<int8_t>());
-                fw.Mr = Mr; fw.nterms = nterms; fw.first_group = g_first; fw.n = (uint32_t)n; fw.cap = (uint32_t)gens_cap; fw.top = rc.top;
-                fw.parts = I.eff_parts; fw.NM = 1u << (I.eff_wnaf - 2);
-            } else if (steps) {                                 // width-4 NAF steps; the multiples the kernel makes live in the arena - no multiscalar sum of this context is in flight during a fold
-                rc = fold_recode_steps(sG, sH, Mr, hbuf.as<uint32_t>(), fq);
-                I.arena.ensure((size_t)3 * nterms * 2 * Mr * sizeof(ge_pniels));
-            } else {                                            // plain NAF bitmaps
-                rc = fold_recode_naf(sG, sH, u_ch, Mr, n, g_first, hbuf.as<uint32_t>());
-                fg.Mr = Mr; fg.nterms = nterms; fg.first_group = g_first; fg.n = (uint32_t)n; fg.top = rc.top;
-            }
-            HIPCHK(hipMemcpyAsync(dbuf.p, hbuf.p, bytes, hipMemcpyHostToDevice, st));
-            const uint32_t *nf = dbuf.as<uint32_t>();
-            double device_bytes = 96.0 * 2 * g_M + 128.0 * 2 * Mr;          // 2*g_M points read at 96 B, 2*Mr written at 128 B
-            switch (kernel) {
-            case FoldKernel::Wnaf:
-                BPG_LAUNCH(I, k_fold_points_wnaf, grid, block, I.gens, I.gens_odd, fo, nf, fw);
-                device_bytes = 96.0 * (2.0 * Mr + rc.adds_fm / 7.0) + 128.0 * 2 * Mr;       // one point read per output and per addition
-                break;
-            case FoldKernel::QuadW: BPG_LAUNCH(I, k_fold_points_quadw, grid64, block, Gst, Hst, fo, nf, reinterpret_cast<fe *>(I.arena_at(0)), fq); break;
-            case FoldKernel::Quad: BPG_LAUNCH(I, k_fold_points_quad, grid64, block, Gst, Hst, fo, nf, fg); break;
-            case FoldKernel::Split: BPG_LAUNCH(I, k_fold_points_split, grid64, block, Gst, Hst, fo, nf, fg); break;
-            case FoldKernel::RegW: BPG_LAUNCH(I, k_fold_points_regw, grid, block, Gst, Hst, fo, nf, reinterpret_cast<ge_pniels *>(I.arena_at(0)), fq); break;
-            case FoldKernel::Reg:       // addends in registers: one instantiation per group size (r = 1..4)
-                if (nterms == 1) BPG_LAUNCH_ID(I, fold_kid, k_fold_points_reg<1>, grid, block, Gst, Hst, fo, nf, fg);
-                else if (nterms == 3) BPG_LAUNCH_ID(I, fold_kid, k_fold_points_reg<3>, grid, block, Gst, Hst, fo, nf, fg);
-                else if (nterms == 7) BPG_LAUNCH_ID(I, fold_kid, k_fold_points_reg<7>, grid, block, Gst, Hst, fo, nf, fg);
-                else BPG_LAUNCH_ID(I, fold_kid, k_fold_points_reg<15>, grid, block, Gst, Hst, fo, nf, fg);
-                break;
-            case FoldKernel::Mem: BPG_LAUNCH(I, k_fold_points, grid, block, Gst, Hst, fo, nf, fg); break;
-            }
-            // bookkeeping for the roofline: 2*g_M points read + 2*Mr written at 32 B (information content) resp. in the device formats; field
-            // multiplications: 8 per doubling, 7 per mixed addition (the split variant runs the doublings once per wave of a block)
-            I.prof_note(fold_kid, 32.0 * (2.0 * g_M + 2.0 * Mr), device_bytes,
-                        2.0 * Mr * (8.0 * (rc.top + 1) * (kernel == FoldKernel::Split ? (nterms < 4 ? nterms : 4) : 1) + 7.0) + rc.adds_fm);
-            BPG_LAUNCH(I, k_normalize_niels, dim3(cdiv(cdiv(2 * Mr, NORM_K), 256)), dim3(256), I.scratch_ext.as<ge_ext>(), dst, 2 * Mr);
+            I.fold_launch(FoldShape{Mr, nterms, g_first, Gst == Gtab && Hst == Htab && Gtab == I.gens}, nullptr, g_M, n, u_ch, sG, sH, Gst, Hst, dst);
             HIPCHK(hipGetLastError());
             I.wait_stream();                               // h_naf is reused by the next group
             Gst = dst; Hst = dst + Mr;

@@ -77,6 +77,11 @@ public:
     // call took and the device state it left (starts[] of every bucket, the heavy and medium list counts)
     struct MsmSegSpec { uint32_t table, result; uint64_t first; uint32_t len, lgblk; const uint32_t *skip; };
     std::string test_msm(uint32_t nmsm, uint32_t nseg, const MsmSegSpec *segs, const uint8_t *scalars, uint8_t *out);
+    // the generator fold of one group of the inner-product argument on scalars the caller chose (include/bpg.h bpg_test_fold): the launch path of the prover
+    // on the context's own tables (G at 0, H at capacity; 2^(lgMr + rounds) points each), kernel = -1 (the chooser's) or a FoldKernel; out = 2 * 2^lgMr
+    // compressed points, G side first; returns a JSON text of what was launched
+    std::string test_fold(int32_t kernel, uint32_t lgMr, uint32_t rounds, uint32_t first, uint64_t n, const uint8_t *sG, const uint8_t *sH, const uint8_t u_ch[32],
+                          uint8_t *out);
 
     DeviceCircuit *upload(const FlatView &c);
     DeviceCircuit *upload(const FlatCircuit &c) { return upload(FlatView(c)); }

@@ -1,7 +1,8 @@
 // The generator fold of one group of rounds of the inner-product argument, decided and recoded before anything is launched: the group scalars, which
 // of the seven fold kernels of hip/k_ipa.cuh takes the fold (choose_fold), and the scalars in the format that kernel reads (plain NAF bitmaps,
 // width-w NAF digits per part, width-4 step lists).  No HIP and no device here: tests/hostcheck/plans.cpp checks the chooser row by row and the
-// recoders against integer arithmetic on the CPU; Engine::Impl::inner_product() uploads what the recoders wrote and launches what the chooser named.
+// recoders against integer arithmetic on the CPU; Engine::Impl::fold_launch() uploads what the recoders wrote and launches what the chooser named, for
+// inner_product() and for the test hook bpg_test_fold alike.
 #pragma once
 #include <algorithm>
 #include <array>

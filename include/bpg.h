@@ -640,6 +640,22 @@ typedef struct {
 bpg_status bpg_test_msm(bpg_ctx *ctx, uint32_t nmsm, uint32_t nseg, const bpg_msm_seg *segs, const uint8_t *scalars, uint8_t *out,
                         char *evidence, uint64_t cap);
 
+/* test hook: the generator fold of one group of rounds of the inner-product argument, on scalars the caller chooses, through the launch path of the prover
+ * (kernel choice, recoding, upload, launch, normalisation).  The group-start tables are the context's own generator tables, G from generator 0 and H from
+ * generator 0, g_M = 2^(lgMr + rounds) <= capacity points each; Mr = 2^lgMr, nterms = 2^rounds - 1 with rounds 1..5.  sG, sH: nterms canonical 32-byte
+ * scalars each - the scalars of terms 1..nterms themselves, not challenges: out[i] = G[i] + sum_t sG_t G[i + t*Mr], out[Mr + i] the same on H with sH.  first = 1:
+ * the lanes with i + t*Mr >= n take s_t * u_ch (the padding generators of a first group), and g_M/2 < n <= g_M; first = 0: n and u_ch are not used.
+ * kernel: -1 = what the chooser picks under the context's knobs; 0..6 force k_fold_points_wnaf, _quadw, _quad, _split, _regw, _reg, k_fold_points - accepted
+ * exactly where the chooser could name that kernel under some setting of the knobs (quadw: first = 0, Mr % 64 == 0, nterms <= 7; regw: first = 0,
+ * Mr % 256 == 0, nterms <= 7; quad: nterms <= 7; split: 3..15 terms; reg: 1, 3, 7 or 15 terms; wnaf: BPG_FOLD_WNAF >= 3 and a table of odd multiples fits).
+ * out = 2 * Mr compressed points, G side then H side, normalised as the prover normalises them.  evidence (cap >= 512) = JSON text: the kernel's name, Mr,
+ * nterms, first, n; top (the length of the doubling chain less one) for the bitmap and width-w kernels; nsteps[2], tail[2] for the step kernels; wnaf, parts,
+ * part_bits as settled for k_fold_points_wnaf.  Every argument is checked before a launch (BPG_ERR_INVALID_ARGUMENT: a NULL pointer, a non-canonical scalar,
+ * rounds outside 1..5, g_M beyond the capacity, n out of range, a forced kernel outside its conditions); a NULL ctx is BPG_ERR_DEVICE.
+ * (An addition to ABI version 7: look the symbol up.) */
+bpg_status bpg_test_fold(bpg_ctx *ctx, int32_t kernel, uint32_t lgMr, uint32_t rounds, uint32_t first, uint64_t n, const uint8_t *sG, const uint8_t *sH,
+                         const uint8_t u_ch[32], uint8_t *out, char *evidence, uint64_t cap);
+
 /* test hook: k_decompress, the verifier's RFC 9496 decoder, on n encodings of 32 bytes, launched as bpg_r1cs_verify launches it.  ok_out[i] = 1 when
  * encoding i is accepted; xy_out holds, for EVERY entry, the affine x || y (32 + 32 bytes, canonical) the kernel wrote, recovered on the host from
  * its halved Niels form (x = ypx - ymx, y = ypx + ymx) - meaningful where ok_out[i] = 1.  Arguments are checked before any launch

@@ -128,6 +128,14 @@ def test_pedersen_bases_and_commitments(ctx, golden):
     got = ctx.pedersen_commit(vs, rr)
     for v, r, g in zip(vs, rr, got):
         assert g == O.pedersen_commit(v, r)
+    # k_pedersen's signed nibbles (ped_digit: a digit above 8 is taken as digit - 16 with a carry into the next window): values and blindings below 2^255 of one
+    # repeated nibble - all eights (no digit carries, every digit is the table's last multiple), all nines (every digit carries), all sevens (none does), a
+    # carry chain from the second window into the highest above a lowest digit of exactly 8 (0x7ff..f8), and a lone eight in the highest window but one
+    nib = [int("0" + d * 63, 16) for d in "897"] + [(1 << 255) - 8, 8 * 16**62]
+    nib = [x.to_bytes(32, "little") for x in nib]
+    vs, rr = [v for v in nib for _ in nib], [r for _ in nib for r in nib]
+    for v, r, g in zip(vs, rr, ctx.pedersen_commit(vs, rr)):
+        assert g == O.pedersen_commit(v, r), (v[::-1].hex(), r[::-1].hex())
 
 
 def test_generators_match_golden_and_oracle(ctx, golden):

@@ -17,6 +17,16 @@ def test_msm_planner_fold_chooser_and_recoders_under_the_sanitizers(tmp_path):
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stderr == "", r.stdout[-2000:] + r.stderr
     assert r.stdout.split()[-1] == "ok"
+    # the chosen scalars the program built by the rules of tests/fold_cases.py are the ones that module builds: the recoders were checked on the very values
+    # the fold kernels are run on (test_fold_kernels_gpu.py)
+    import re
+    import fold_cases as F
+    built = {name: int(value, 16) for name, value in re.findall(r"^chosen \[(.+)\] ([0-9a-f]{64})$", r.stdout, re.M)}
+    want = dict(F.named())
+    for w in range(3, 9):
+        want.update(F.width_patterns(w))
+        want.update({"w%d parts %d %s" % (w, parts, kind): F.parts_extreme(w, parts, kind) for parts in (1, 2, 4, 8) for kind in F.PARTS_KINDS})
+    assert len(want) == 19 + 6 * 24 + 1 and built == want
 
 
 def test_the_engine_keeps_no_plan_state_between_calls():
