@@ -439,6 +439,36 @@ class Context:
                                  None if u_ch is None else _exact("u_ch", u_ch, 32), out, ev, C.c_uint64(1024)))
         return [out.raw[32 * i:32 * i + 32] for i in range(count)], json.loads(ev.value.decode())
 
+    def test_tail(self, lgM0, tables, first, n, a, b, yinv, u_ch, gamma0, eta0, w, u):
+        """bpg_test_tail: the table-driven tail of the inner-product argument on the context's own generators G[0, M0), H[0, M0) and B, through the prover's freeze
+        and per-round steps.  tables: 0 (4-bit tables of the original generators), 1 (4-bit tables in the arena, as for folded generators), 2 (8-bit tables);
+        a, b: 2^lgM0 canonical 32-byte scalars each and u: one challenge per sub-round (lists, or their concatenations); the others: 32 bytes.  Returns ([(L_j, R_j)]
+        per sub-round, the folded a, the folded b as lists of 32-byte scalars, the evidence dict: what was launched)."""
+        import json
+        M0 = 1 << lgM0 if 0 <= lgM0 <= 14 else 1                 # a larger M0 is refused before anything is read or written
+        join = lambda name, s, count: None if s is None else _exact(name, s if isinstance(s, (bytes, bytearray)) else b"".join(s), 32 * count)
+        ub = None if u is None else (u if isinstance(u, (bytes, bytearray)) else b"".join(u))
+        rounds = 0 if ub is None else len(ub) // 32
+        left = M0 >> min(rounds, lgM0) if 0 <= lgM0 <= 14 else 1
+        lr, ab, ev = _buf(64 * max(rounds, 1)), _buf(64 * left), _buf(1024)
+        one = lambda name, s: None if s is None else _exact(name, s, 32)
+        _chk(lib().bpg_test_tail(self._h, C.c_uint32(lgM0), C.c_uint32(tables), C.c_uint32(first), C.c_uint64(n), join("a", a, M0), join("b", b, M0), one("yinv", yinv),
+                                 one("u_ch", u_ch), one("gamma0", gamma0), one("eta0", eta0), one("w", w), C.c_uint32(rounds), ub, lr, ab, ev, C.c_uint64(1024)))
+        cut = lambda raw, k: [raw[32 * i:32 * i + 32] for i in range(k)]
+        return ([(lr.raw[64 * j:64 * j + 32], lr.raw[64 * j + 32:64 * j + 64]) for j in range(rounds)], cut(ab.raw, left), cut(ab.raw[32 * left:], left),
+                json.loads(ev.value.decode()))
+
+    def test_commit3(self, lgM0, n, aL, aR, aO, sL, sR, blind):
+        """bpg_test_commit3: A_I, A_O, S from the window tables of the context's own generators G[0, M0), H[0, M0) (k_tt_commit3 and its finish).  aL .. sR: n
+        canonical 32-byte scalars each, blind: three (lists, or their concatenations).  Returns ([A_I, A_O, S] encoded, the evidence dict)."""
+        import json
+        count = n if isinstance(n, int) and 0 <= n <= 1 << 14 else 0
+        join = lambda name, s, k: None if s is None else _exact(name, s if isinstance(s, (bytes, bytearray)) else b"".join(s), 32 * k)
+        out, ev = _buf(96), _buf(1024)
+        _chk(lib().bpg_test_commit3(self._h, C.c_uint32(lgM0), C.c_uint64(n), join("aL", aL, count), join("aR", aR, count), join("aO", aO, count), join("sL", sL, count),
+                                    join("sR", sR, count), join("blind", blind, 3), out, ev, C.c_uint64(1024)))
+        return [out.raw[32 * k:32 * k + 32] for k in range(3)], json.loads(ev.value.decode())
+
     def test_fe_ops(self, op, a_list, b_list):
         n = len(a_list)
         out = _buf(32 * n)

@@ -242,6 +242,29 @@ bpg_status bpg_test_fold(bpg_ctx *ctx, int32_t kernel, uint32_t lgMr, uint32_t r
     });
 }
 
+bpg_status bpg_test_tail(bpg_ctx *ctx, uint32_t lgM0, uint32_t tables, uint32_t first, uint64_t n, const uint8_t *a, const uint8_t *b, const uint8_t yinv[32],
+                         const uint8_t u_ch[32], const uint8_t gamma0[32], const uint8_t eta0[32], const uint8_t w[32], uint32_t rounds, const uint8_t *u,
+                         uint8_t *lr_out, uint8_t *ab_out, char *evidence, uint64_t cap) {
+    return guard([&] {
+        if (!ctx) throw DeviceError("test_tail: no device context (the tail runs on the GPU only)");
+        REQUIRE(a && b && yinv && u_ch && gamma0 && eta0 && w && u && lr_out && ab_out && evidence && cap >= 512);
+        const std::string r = ctx->engine->test_tail(lgM0, tables, first, n, a, b, yinv, u_ch, gamma0, eta0, w, rounds, u, lr_out, ab_out);
+        if (r.size() + 1 > cap) throw std::invalid_argument("test_tail: evidence buffer too small (" + std::to_string(r.size() + 1) + " bytes needed)");
+        std::memcpy(evidence, r.c_str(), r.size() + 1);
+    });
+}
+
+bpg_status bpg_test_commit3(bpg_ctx *ctx, uint32_t lgM0, uint64_t n, const uint8_t *aL, const uint8_t *aR, const uint8_t *aO, const uint8_t *sL, const uint8_t *sR,
+                            const uint8_t blind[96], uint8_t out[96], char *evidence, uint64_t cap) {
+    return guard([&] {
+        if (!ctx) throw DeviceError("test_commit3: no device context (the commitments run on the GPU only)");
+        REQUIRE(aL && aR && aO && sL && sR && blind && out && evidence && cap >= 512);
+        const std::string r = ctx->engine->test_commit3(lgM0, n, aL, aR, aO, sL, sR, blind, out);
+        if (r.size() + 1 > cap) throw std::invalid_argument("test_commit3: evidence buffer too small (" + std::to_string(r.size() + 1) + " bytes needed)");
+        std::memcpy(evidence, r.c_str(), r.size() + 1);
+    });
+}
+
 bpg_status bpg_test_decompress(bpg_ctx *ctx, uint64_t n, const uint8_t *in, uint32_t *ok_out, uint8_t *xy_out) {
     return guard([&] {
         if (!ctx) throw DeviceError("test_decompress: no device context (k_decompress runs on the GPU only)");

@@ -572,6 +572,23 @@ struct Engine::Impl {
                        const std::vector<Scalar> &sH, const ge_niels *Gst, const ge_niels *Hst, ge_niels *dst);
     void inner_product(Transcript &T, std::vector<uint8_t> &proof, uint64_t n, uint64_t N, const Scalar &yinv, const Scalar &u_ch, const Scalar &w,
                        const ge_niels *Gtab, const ge_niels *Htab, const ge_niels *Bn, ProveTimings *tm, double &t0);
+    // The table-driven tail of the inner-product argument (hip/k_ipa.cuh k_tt_*): what inner_product() runs from the round that freezes the generators, and what
+    // the test hook Engine::test_tail runs on scalars of its caller's choosing.  tail_freeze: window tables of G[0..M0), H[0..M0), B (and the 8-bit ones of the
+    // original generators where try_wide and the budget allow), the per-point factors, the first coefficient tables.  tail_round: sub-round S.j on a, b of mcur
+    // values each - the previous challenge applied first (tail_advance) when j > 0 - with L and R encoded into lr.  tail_challenge: the challenge drawn from them.
+    // tail_last_fold: after the last round only the scalar fold remains.
+    struct TailState { uint32_t lgM0 = 0, j = 0, cur = 0; Scalar u, uinv; const ge_pniels *wide = nullptr; };
+    static uint32_t tail_nblk(uint32_t M0) { return cdiv((uint64_t)M0 * 8, 256); }
+    void tail_freeze(TailState &S, uint32_t M0, bool first, uint64_t n, const scm &uch_m, const Scalar &Gamma, const Scalar &Eta, const ge_niels *Gst,
+                     const ge_niels *Hst, const ge_niels *Bn, bool original, bool try_wide);
+    void tail_advance(TailState &S, scm *a, scm *b, uint64_t mcur);
+    void tail_round(TailState &S, scm *a, scm *b, uint64_t mcur, const scm &w_m, uint32_t quad_sums, uint8_t lr[64]);
+    void tail_challenge(TailState &S, const Scalar &u) { S.u = u; S.uinv = u.invert(); S.j++; }
+    void tail_last_fold(const TailState &S, scm *a, scm *b, uint64_t h);
+    // A_I, A_O, S of a circuit of n multipliers on the window tables of the original generators G[0..M0), H[0..M0) (tt_build(.., M0, true) went before), the three
+    // blindings in extras[0..2]: k_tt_commit3 and its finish, encoded into pts.  prove() and the test hook Engine::test_commit3.
+    static uint32_t commit3_nblk(uint32_t M0) { return cdiv((uint64_t)M0 * 16, 256); }
+    void commit3(const scm *aL, const scm *aR, const scm *aO, const scm *sL, const scm *sR, uint64_t n, uint32_t M0, uint32_t quad_sums, uint8_t pts[96]);
 };
 
 // Environment knobs are read ONCE, here, before anything touches the device: a value that does not parse or lies outside its range is an error
@@ -1188,6 +1205,106 @@ std::string Engine::test_fold(int32_t kernel, uint32_t lgMr, uint32_t rounds, ui
         j += ", \"tail\": [" + std::to_string(run.tail[0]) + ", " + std::to_string(run.tail[1]) + "]";
     } else u("top", run.top);
     if (run.kernel == FoldKernel::Wnaf) { u("wnaf", I.eff_wnaf); u("parts", I.eff_parts); u("part_bits", I.fold_part_bits()); }
+    j += "}";
+    return j;
+}
+
+// The table-driven tail on scalars the caller chose (include/bpg.h bpg_test_tail): Impl::tail_freeze() and `rounds` times Impl::tail_round() as inner_product()
+// calls them, on the context's own generators G[0, M0), H[0, M0) and the Pedersen base B.  Returns the JSON evidence of what was launched.
+std::string Engine::test_tail(uint32_t lgM0, uint32_t tables, uint32_t first, uint64_t n, const uint8_t *a_bytes, const uint8_t *b_bytes, const uint8_t yinv_bytes[32],
+                              const uint8_t u_ch_bytes[32], const uint8_t gamma0_bytes[32], const uint8_t eta0_bytes[32], const uint8_t w_bytes[32], uint32_t rounds,
+                              const uint8_t *u_bytes, uint8_t *lr_out, uint8_t *ab_out) {
+    // every argument is checked here, before anything is queued: no index the caller chose reaches a kernel unchecked
+    if (!a_bytes || !b_bytes || !yinv_bytes || !u_ch_bytes || !gamma0_bytes || !eta0_bytes || !w_bytes || !u_bytes || !lr_out || !ab_out)
+        throw std::invalid_argument("test_tail: null pointer");
+    if (lgM0 < 1 || lgM0 > 14 || (1ull << lgM0) > gens_cap_) throw std::invalid_argument("test_tail: M0 is 2 .. 2^14 and at most the capacity of the generator tables");
+    if (tables > 2) throw std::invalid_argument("test_tail: tables is 0 (original generators), 1 (folded-style, in the arena) or 2 (wide, 8-bit windows)");
+    if (first > 1) throw std::invalid_argument("test_tail: first is 0 or 1");
+    if (rounds < 1 || rounds > lgM0) throw std::invalid_argument("test_tail: rounds is 1 .. lgM0");
+    const uint32_t M0 = 1u << lgM0;
+    if (first && (n <= M0 / 2 || n > M0)) throw std::invalid_argument("test_tail: a first round has M0/2 < n <= M0");
+    auto scalar = [](const uint8_t *p, const char *what, bool nonzero) {
+        Scalar s; std::memcpy(s.w, p, 32);
+        if (!s.is_canonical()) throw std::invalid_argument(std::string("test_tail: ") + what + " is not canonical");
+        if (nonzero && (s.w[0] | s.w[1] | s.w[2] | s.w[3]) == 0) throw std::invalid_argument(std::string("test_tail: ") + what + " is zero");
+        return s;
+    };
+    const Scalar yinv = scalar(yinv_bytes, "yinv", true), u_ch = scalar(u_ch_bytes, "u_ch", false), Gamma = scalar(gamma0_bytes, "gamma0", false),
+                 Eta = scalar(eta0_bytes, "eta0", false), w = scalar(w_bytes, "w", false);
+    std::vector<Scalar> us(rounds);
+    for (uint32_t k = 0; k < rounds; k++) us[k] = scalar(u_bytes + 32 * (size_t)k, "a challenge u", true);
+    for (uint32_t i = 0; i < M0; i++) { scalar(a_bytes + 32 * (size_t)i, "a scalar of a", false); scalar(b_bytes + 32 * (size_t)i, "a scalar of b", false); }
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    I.shared_now = I.shared_variants();
+    // 8-bit tables asked for: refused where the prover would fall back to the 4-bit ones, so that no case passes on other tables than it names
+    if (tables == 2 && !I.wide_ensure(M0)) throw std::invalid_argument("test_tail: no 8-bit window tables for this M0 (M0 < 64, or the table budget)");
+    I.small_sc.ensure((size_t)2 * M0 * 32); I.lv.ensure((size_t)M0 * sizeof(scm)); I.rv.ensure((size_t)M0 * sizeof(scm)); I.yinvpow.ensure((size_t)M0 * sizeof(scm));
+    I.msm_result.ensure(4 * sizeof(ge_ext)); I.h_small.ensure(1 << 16);
+    scm *a = I.lv.as<scm>(), *b = I.rv.as<scm>();
+    I.h2d(I.small_sc.p, a_bytes, (size_t)M0 * 32); I.h2d(I.small_sc.as<uint8_t>() + (size_t)M0 * 32, b_bytes, (size_t)M0 * 32);
+    BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(M0, 256)), dim3(256), I.small_sc.as<uint32_t>(), a, M0);
+    BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(M0, 256)), dim3(256), I.small_sc.as<uint32_t>() + (size_t)M0 * 8, b, M0);
+    I.exp_tables({{yinv, I.yinvpow.as<scm>(), M0}});
+    const uint32_t quad_sums = I.shared_now ? 0u : 1u;
+    const ge_niels *G = I.gens, *H = I.gens + gens_cap_;
+    Impl::TailState S;
+    I.tail_freeze(S, M0, first != 0, n, to_scm(u_ch), Gamma, Eta, G, H, I.bases.as<ge_niels>(), tables != 1, tables == 2);
+    if ((tables == 2) != (S.wide != nullptr)) throw std::logic_error("test_tail: the tail settled on other tables than asked for");
+    uint64_t mcur = M0;
+    for (uint32_t k = 0; k < rounds; k++) {
+        I.tail_round(S, a, b, mcur, to_scm(w), quad_sums, lr_out + 64 * (size_t)k);
+        I.tail_challenge(S, us[k]);
+        mcur /= 2;
+    }
+    // the last challenge: as the next round would apply it, or as the scalar fold after the last round of a proof does
+    if (rounds == lgM0) I.tail_last_fold(S, a, b, mcur); else I.tail_advance(S, a, b, mcur);
+    HIPCHK(hipGetLastError());
+    std::vector<scm> ab(2 * mcur);
+    HIPCHK(hipMemcpyAsync(ab.data(), a, mcur * sizeof(scm), hipMemcpyDeviceToHost, I.st));
+    HIPCHK(hipMemcpyAsync(ab.data() + mcur, b, mcur * sizeof(scm), hipMemcpyDeviceToHost, I.st));
+    HIPCHK(hipStreamSynchronize(I.st));
+    for (uint64_t i = 0; i < 2 * mcur; i++) from_scm(ab[i]).to_bytes(ab_out + 32 * i);
+    std::string j = "{\"kernel\": \""; j += S.wide ? "k_tt_round8" : "k_tt_round"; j += "\"";
+    auto ev = [&](const char *k, int64_t v) { j += ", \""; j += k; j += "\": "; j += std::to_string(v); };
+    ev("tables", tables); ev("M0", M0); ev("nblk", Impl::tail_nblk(M0)); ev("quad", quad_sums);
+    j += "}";
+    return j;
+}
+
+// A_I, A_O, S on scalars the caller chose (include/bpg.h bpg_test_commit3): Impl::commit3() as prove() calls it, on the window tables of the context's own
+// generators G[0, M0), H[0, M0).  Returns the JSON evidence of what was launched.
+std::string Engine::test_commit3(uint32_t lgM0, uint64_t n, const uint8_t *aL, const uint8_t *aR, const uint8_t *aO, const uint8_t *sL, const uint8_t *sR,
+                                 const uint8_t *blind, uint8_t out[96]) {
+    if (!aL || !aR || !aO || !sL || !sR || !blind || !out) throw std::invalid_argument("test_commit3: null pointer");
+    if (lgM0 > 14 || (1ull << lgM0) > gens_cap_) throw std::invalid_argument("test_commit3: M0 is 1 .. 2^14 and at most the capacity of the generator tables");
+    const uint32_t M0 = 1u << lgM0;
+    if (n < 1 || n > M0) throw std::invalid_argument("test_commit3: n is 1 .. M0");
+    const uint8_t *vec[5] = {aL, aR, aO, sL, sR};
+    for (int v = 0; v < 5; v++) for (uint64_t i = 0; i < n; i++) {
+        Scalar s; std::memcpy(s.w, vec[v] + 32 * i, 32);
+        if (!s.is_canonical()) throw std::invalid_argument("test_commit3: scalar " + std::to_string(i) + " of vector " + std::to_string(v) + " is not canonical");
+    }
+    for (int k = 0; k < 3; k++) {
+        Scalar s; std::memcpy(s.w, blind + 32 * k, 32);
+        if (!s.is_canonical()) throw std::invalid_argument("test_commit3: blinding " + std::to_string(k) + " is not canonical");
+    }
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    I.shared_now = I.shared_variants();
+    const uint64_t total = 5 * n + 3;
+    I.small_sc.ensure(total * 32); I.sLR.ensure(5 * n * sizeof(scm)); I.extras.ensure(16 * sizeof(scm));
+    I.msm_result.ensure(4 * sizeof(ge_ext)); I.h_small.ensure(1 << 16);
+    for (int v = 0; v < 5; v++) I.h2d(I.small_sc.as<uint8_t>() + (size_t)v * n * 32, vec[v], n * 32);
+    I.h2d(I.small_sc.as<uint8_t>() + 5 * n * 32, blind, 96);
+    scm *d = I.sLR.as<scm>();
+    BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(5 * n, 256)), dim3(256), I.small_sc.as<uint32_t>(), d, (uint32_t)(5 * n));
+    BPG_LAUNCH(I, k_sc_from_bytes, dim3(1), dim3(256), I.small_sc.as<uint32_t>() + 5 * n * 8, I.extras.as<scm>(), 3u);
+    const uint32_t quad_sums = I.shared_now ? 0u : 1u;
+    I.tt_build(I.gens, I.gens + gens_cap_, I.bases.as<ge_niels>(), M0, true);
+    I.commit3(d, d + n, d + 2 * n, d + 3 * n, d + 4 * n, n, M0, quad_sums, out);
+    std::string j = "{";
+    j += "\"M0\": " + std::to_string(M0) + ", \"n\": " + std::to_string(n) + ", \"nblk\": " + std::to_string(Impl::commit3_nblk(M0)) + ", \"quad\": " + std::to_string(quad_sums);
     j += "}";
     return j;
 }
@@ -2040,6 +2157,57 @@ Engine::Impl::FoldRun Engine::Impl::fold_launch(const FoldShape &shape, const Fo
     return run;
 }
 
+// ------------------------------------------------------------------------------------------------ table-driven tail and commitments
+void Engine::Impl::tail_freeze(TailState &S, uint32_t M0, bool first, uint64_t n, const scm &uch_m, const Scalar &Gamma, const Scalar &Eta, const ge_niels *Gst,
+                               const ge_niels *Hst, const ge_niels *Bn, bool original, bool try_wide) {
+    S.lgM0 = ceil_log2(M0); S.j = 0; S.cur = 0;
+    tt_f.ensure((size_t)2 * M0 * sizeof(scm)); tt_c.ensure((size_t)4 * M0 * sizeof(scm));
+    tt_build(Gst, Hst, Bn, M0, original);
+    S.wide = try_wide ? wide_ensure(M0) : nullptr;                             // original generators: 8-bit windows, built once per device
+    BPG_LAUNCH((*this), k_tt_factors, dim3(cdiv(M0, 256)), dim3(256), yinvpow.as<scm>(), uch_m, (uint32_t)first, (uint32_t)n, M0, to_scm(Gamma), to_scm(Eta),
+               tt_f.as<scm>(), tt_f.as<scm>() + M0, tt_c.as<scm>());
+}
+// apply the previous round's challenge: fold a, b (2*mcur -> mcur) and double the coefficient tables
+void Engine::Impl::tail_advance(TailState &S, scm *a, scm *b, uint64_t mcur) {
+    const uint32_t M0 = 1u << S.lgM0;
+    scm *c0 = tt_c.as<scm>() + (size_t)S.cur * 2 * M0, *c1 = tt_c.as<scm>() + (size_t)(S.cur ^ 1u) * 2 * M0;
+    BPG_LAUNCH((*this), k_tt_advance, dim3(cdiv(std::max<uint64_t>(mcur, 1ull << (S.j - 1)), 256)), dim3(256), a, b, to_scm(S.u), to_scm(S.uinv), (uint32_t)mcur,
+               c0, c1, 1u << (S.j - 1), M0);
+    S.cur ^= 1u;
+}
+void Engine::Impl::tail_round(TailState &S, scm *a, scm *b, uint64_t mcur, const scm &w_m, uint32_t quad_sums, uint8_t lr[64]) {
+    const uint32_t M0 = 1u << S.lgM0;
+    const uint64_t h = mcur / 2;
+    if (S.j > 0) tail_advance(S, a, b, mcur);
+    const scm *c0 = tt_c.as<scm>() + (size_t)S.cur * 2 * M0;
+    const uint32_t nblk = tail_nblk(M0);
+    if (S.wide) BPG_LAUNCH((*this), k_tt_round8, dim3(nblk, 2), dim3(256), S.wide, a, b, tt_f.as<scm>(), tt_f.as<scm>() + M0, c0, S.lgM0, S.j, tt_partial.as<ge_ext>(), quad_sums);
+    else BPG_LAUNCH((*this), k_tt_round, dim3(nblk, 2), dim3(256), tt_table_p, a, b, tt_f.as<scm>(), tt_f.as<scm>() + M0, c0, S.lgM0, S.j,
+               tt_partial.as<ge_ext>(), quad_sums);
+    BPG_LAUNCH((*this), k_tt_finish, dim3(2), dim3(256), tt_partial.as<ge_ext>(), nblk, a, b, (uint32_t)h, w_m,
+               tt_table_p + (size_t)2 * M0 * TT_WINDOWS * TT_MULTS, msm_result.as<ge_ext>(), quad_sums);
+    HIPCHK(hipGetLastError());
+    uint32_t *hp = reinterpret_cast<uint32_t *>(h_small.as<uint8_t>() + 16384);       // L, R as extended points; encoded on the host
+    HIPCHK(hipMemcpyAsync(hp, msm_result.p, 2 * sizeof(ge_ext), hipMemcpyDeviceToHost, st));
+    wait_stream();
+    h51::pt_compress(lr, h51::pt_from_device(hp)); h51::pt_compress(lr + 32, h51::pt_from_device(hp + 32));
+}
+void Engine::Impl::tail_last_fold(const TailState &S, scm *a, scm *b, uint64_t h) {
+    BPG_LAUNCH((*this), k_ipa_fold_scalars, dim3(cdiv(h, 256)), dim3(256), a, b, to_scm(S.u), to_scm(S.uinv), (uint32_t)h);
+    HIPCHK(hipGetLastError());
+}
+void Engine::Impl::commit3(const scm *aL, const scm *aR, const scm *aO, const scm *sL, const scm *sR, uint64_t n, uint32_t M0, uint32_t quad_sums, uint8_t pts[96]) {
+    const uint32_t nblk = commit3_nblk(M0);
+    BPG_LAUNCH((*this), k_tt_commit3, dim3(nblk, 3), dim3(256), tt_table_p, aL, aR, aO, sL, sR, (uint32_t)n, M0, tt_partial.as<ge_ext>(), quad_sums);
+    BPG_LAUNCH((*this), k_tt_commit3_finish, dim3(3), dim3(256), tt_partial.as<ge_ext>(), nblk, extras.as<scm>(),
+               ped_table.as<ge_pniels>() + (size_t)TT_WINDOWS * TT_MULTS, msm_result.as<ge_ext>(), quad_sums);
+    HIPCHK(hipGetLastError());
+    uint32_t *hp = reinterpret_cast<uint32_t *>(h_small.as<uint8_t>() + 16384);           // three extended points; encoded on the host
+    HIPCHK(hipMemcpyAsync(hp, msm_result.p, 3 * sizeof(ge_ext), hipMemcpyDeviceToHost, st));
+    wait_stream();
+    for (int k = 0; k < 3; k++) h51::pt_compress(pts + 32 * k, h51::pt_from_device(hp + 32 * k));
+}
+
 // ------------------------------------------------------------------------------------------------ inner-product argument
 // InnerProductProof::create (dalek inner_product_proof.rs) on l(x) = lv, r(x) = rv with G_factors = (1.., u..), H_factors = y^-i * G_factors
 // and Q = w * B: appends L_k, R_k (lg N pairs) and the final a, b to `proof`.  Rounds above 2^tt_lg generators: grouped folds with
@@ -2065,7 +2233,7 @@ void Engine::Impl::inner_product(Transcript &T, std::vector<uint8_t> &proof, uin
     uint64_t mcur = N;
     // table-driven tail state (kernels.cuh "table-driven IPA tail")
     const uint32_t quad_sums = I.shared_now ? 0u : 1u;                 // the block sums of the tail kernels: quad layout for a proof alone (k_points.cuh ge_block_sum_store)
-    bool tt_on = false; uint32_t tt_j = 0, tt_lgM0 = 0, tt_cur = 0; Scalar tt_u, tt_uinv; const ge_pniels *tt_wide = nullptr;
+    bool tt_on = false; Impl::TailState tt;
     // grouped-fold state
     const uint32_t GRP_STRIDE = 64;
     uint32_t g_j = 0, g_r = 1, g_cur = 0, g_index = 0; uint64_t g_M = N; bool g_first = true; std::vector<Scalar> g_us;
@@ -2074,43 +2242,18 @@ void Engine::Impl::inner_product(Transcript &T, std::vector<uint8_t> &proof, uin
         const bool first = round == 0;
         if (!tt_on && ((I.tt_lg > 0 && mcur <= (1ull << I.tt_lg)) || (first && I.tt_orig_lg > 0 && mcur <= (1ull << I.tt_orig_lg)))) {
             // freeze the generators at this level: window tables for G[0..M0), H[0..M0) and B
-            tt_on = true; tt_lgM0 = ceil_log2(mcur); tt_j = 0; tt_cur = 0;
-            const uint32_t M0 = (uint32_t)mcur;
-            I.tt_f.ensure((size_t)2 * M0 * sizeof(scm)); I.tt_c.ensure((size_t)4 * M0 * sizeof(scm));
-            I.tt_build(Gst, Hst, Bn, M0, Gst == Gtab && Hst == Htab);          // no-op when this context already holds them (N <= 2^tt_orig_lg)
-            tt_wide = (Gst == Gtab && Hst == Htab && Gtab == I.gens) ? I.wide_ensure(M0) : nullptr;       // original generators: 8-bit windows, built once per device
-            BPG_LAUNCH(I, k_tt_factors, dim3(cdiv(M0, 256)), dim3(256), I.yinvpow.as<scm>(), uch_m, (uint32_t)first, (uint32_t)n, M0, to_scm(Gamma), to_scm(Eta),
-                       I.tt_f.as<scm>(), I.tt_f.as<scm>() + M0, I.tt_c.as<scm>());
+            tt_on = true;
+            const bool original = Gst == Gtab && Hst == Htab;                  // their tables: a no-op when this context already holds them (N <= 2^tt_orig_lg)
+            I.tail_freeze(tt, (uint32_t)mcur, first, n, uch_m, Gamma, Eta, Gst, Hst, Bn, original, original && Gtab == I.gens);
         }
         if (tt_on) {
-            const uint32_t M0 = 1u << tt_lgM0;
-            scm *c0 = I.tt_c.as<scm>() + (size_t)tt_cur * 2 * M0, *c1 = I.tt_c.as<scm>() + (size_t)(tt_cur ^ 1u) * 2 * M0;
-            if (tt_j > 0) {     // apply the previous round's challenge: fold a, b (2*mcur -> mcur) and double the coefficient tables
-                BPG_LAUNCH(I, k_tt_advance, dim3(cdiv(std::max<uint64_t>(mcur, 1ull << (tt_j - 1)), 256)), dim3(256), a, b, to_scm(tt_u), to_scm(tt_uinv), (uint32_t)mcur,
-                           c0, c1, 1u << (tt_j - 1), M0);
-                tt_cur ^= 1u; std::swap(c0, c1);
-            }
-            const uint32_t nblk = cdiv((uint64_t)M0 * 8, 256);
-            if (tt_wide) BPG_LAUNCH(I, k_tt_round8, dim3(nblk, 2), dim3(256), tt_wide, a, b, I.tt_f.as<scm>(), I.tt_f.as<scm>() + M0, c0, tt_lgM0, tt_j, I.tt_partial.as<ge_ext>(), quad_sums);
-            else BPG_LAUNCH(I, k_tt_round, dim3(nblk, 2), dim3(256), I.tt_table_p, a, b, I.tt_f.as<scm>(), I.tt_f.as<scm>() + M0, c0, tt_lgM0, tt_j,
-                       I.tt_partial.as<ge_ext>(), quad_sums);
-            BPG_LAUNCH(I, k_tt_finish, dim3(2), dim3(256), I.tt_partial.as<ge_ext>(), nblk, a, b, (uint32_t)h, w_m,
-                       I.tt_table_p + (size_t)2 * M0 * TT_WINDOWS * TT_MULTS, I.msm_result.as<ge_ext>(), quad_sums);
-            HIPCHK(hipGetLastError());
             uint8_t lr[64];
-            uint32_t *hp = reinterpret_cast<uint32_t *>(I.h_small.as<uint8_t>() + 16384);       // L, R as extended points; encoded on the host
-            HIPCHK(hipMemcpyAsync(hp, I.msm_result.p, 2 * sizeof(ge_ext), hipMemcpyDeviceToHost, st));
-            I.wait_stream();
-            h51::pt_compress(lr, h51::pt_from_device(hp)); h51::pt_compress(lr + 32, h51::pt_from_device(hp + 32));
+            I.tail_round(tt, a, b, mcur, w_m, quad_sums, lr);
             lap(tm ? &tm->ipa_msm : nullptr);
             proof.insert(proof.end(), lr, lr + 64);
-            tt_u = fs_ipa_round(T, lr, lr + 32); tt_uinv = tt_u.invert();
-            tt_j++;
+            I.tail_challenge(tt, fs_ipa_round(T, lr, lr + 32));
             mcur = h;
-            if (round + 1 == lgN) {   // last round: only the scalar fold remains
-                BPG_LAUNCH(I, k_ipa_fold_scalars, dim3(cdiv(h, 256)), dim3(256), a, b, to_scm(tt_u), to_scm(tt_uinv), (uint32_t)h);
-                HIPCHK(hipGetLastError());
-            }
+            if (round + 1 == lgN) I.tail_last_fold(tt, a, b, h);   // last round: only the scalar fold remains
             continue;
         }
         // ---- grouped fold rounds (kernels.cuh k_ipa_prep / k_fold_points): sub-round g_j of a group of g_r rounds on tables of size g_M
@@ -2462,16 +2605,7 @@ std::vector<uint8_t> Engine::prove(DeviceCircuit *c, Transcript &T, const std::v
     lap(tm ? &tm->msm_aiao : nullptr);
     uint8_t pts[96];
     if (tabled) {
-        const uint32_t M0 = (uint32_t)N, nblk = cdiv((uint64_t)M0 * 16, 256);
-        BPG_LAUNCH(I, k_tt_commit3, dim3(nblk, 3), dim3(256), I.tt_table_p, c->aL.as<scm>(), c->aR.as<scm>(), c->aO.as<scm>(), sL, sR,
-                   (uint32_t)n, M0, I.tt_partial.as<ge_ext>(), I.shared_now ? 0u : 1u);
-        BPG_LAUNCH(I, k_tt_commit3_finish, dim3(3), dim3(256), I.tt_partial.as<ge_ext>(), nblk, I.extras.as<scm>(),
-                   I.ped_table.as<ge_pniels>() + (size_t)TT_WINDOWS * TT_MULTS, I.msm_result.as<ge_ext>(), I.shared_now ? 0u : 1u);
-        HIPCHK(hipGetLastError());
-        uint32_t *hp = reinterpret_cast<uint32_t *>(I.h_small.as<uint8_t>() + 16384);           // three extended points; encoded on the host
-        HIPCHK(hipMemcpyAsync(hp, I.msm_result.p, 3 * sizeof(ge_ext), hipMemcpyDeviceToHost, st));
-        I.wait_stream();
-        for (int k = 0; k < 3; k++) h51::pt_compress(pts + 32 * k, h51::pt_from_device(hp + 32 * k));
+        I.commit3(c->aL.as<scm>(), c->aR.as<scm>(), c->aO.as<scm>(), sL, sR, n, (uint32_t)N, I.shared_now ? 0u : 1u, pts);
     } else if (merged) {
         MsmJob J = job_new();
         push_AI(J); push_AO(J);

@@ -82,6 +82,15 @@ public:
     // compressed points, G side first; returns a JSON text of what was launched
     std::string test_fold(int32_t kernel, uint32_t lgMr, uint32_t rounds, uint32_t first, uint64_t n, const uint8_t *sG, const uint8_t *sH, const uint8_t u_ch[32],
                           uint8_t *out);
+    // the table-driven tail of the inner-product argument on scalars the caller chose (include/bpg.h bpg_test_tail): the freeze and `rounds` sub-rounds as
+    // inner_product() runs them, on G[0, M0), H[0, M0) and B of the context; lr_out = 2 * rounds encodings (L_0, R_0, L_1, ..), ab_out = the folded a then the
+    // folded b (M0 >> rounds canonical scalars each); returns a JSON text of what was launched
+    std::string test_tail(uint32_t lgM0, uint32_t tables, uint32_t first, uint64_t n, const uint8_t *a, const uint8_t *b, const uint8_t yinv[32], const uint8_t u_ch[32],
+                          const uint8_t gamma0[32], const uint8_t eta0[32], const uint8_t w[32], uint32_t rounds, const uint8_t *u, uint8_t *lr_out, uint8_t *ab_out);
+    // A_I, A_O, S from the window tables of the original generators on scalars the caller chose (include/bpg.h bpg_test_commit3): n values per vector,
+    // blind = the three blindings; out = the three encodings; returns a JSON text of what was launched
+    std::string test_commit3(uint32_t lgM0, uint64_t n, const uint8_t *aL, const uint8_t *aR, const uint8_t *aO, const uint8_t *sL, const uint8_t *sR,
+                             const uint8_t *blind, uint8_t out[96]);
 
     DeviceCircuit *upload(const FlatView &c);
     DeviceCircuit *upload(const FlatCircuit &c) { return upload(FlatView(c)); }

@@ -158,13 +158,7 @@ __global__ void __launch_bounds__(256) k_tt_advance(scm *__restrict__ a, scm *__
         cnext[M0 + 2 * i] = sc_mont_mul(e, u); cnext[M0 + 2 * i + 1] = sc_mont_mul(e, uinv);
     }
 }
-// signed 4-bit digits without a carry chain: nibble w of (s + 0x88..8) minus 8 lies in [-8, 7]
-__device__ __forceinline__ void tt_biased_words(uint32_t w[8], const scm &s) {
-    sc_to_words(w, s);
-    uint64_t carry = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) { uint64_t t = (uint64_t)w[k] + 0x88888888ull + carry; w[k] = (uint32_t)t; carry = t >> 32; }
-}
+// (signed 4-bit digits without a carry chain: tt_biased_words, sc.cuh)
 // sub-round j of the tail (h = M0 >> (j+1)): blockIdx.y = 0 accumulates L, 1 accumulates R; thread = (base point, 8 windows)
 __global__ void __launch_bounds__(256) k_tt_round(const ge_pniels *__restrict__ table, const scm *__restrict__ a, const scm *__restrict__ b,
                                                   const scm *__restrict__ fG, const scm *__restrict__ fH, const scm *__restrict__ c,
@@ -232,13 +226,7 @@ __global__ void __launch_bounds__(256) k_tt_multiples8(const ge_ext *__restrict_
 #pragma unroll 1
     for (uint32_t k = 1; k < TT8_MULTS; k++) { cur = ge_add_pniels_signed(cur, n1, 0); dst[k] = ge_to_pniels(cur); }
 }
-// signed 8-bit digits without a carry chain: byte w of (s + 0x80..80) minus 128 lies in [-128, 127]
-__device__ __forceinline__ void tt8_biased_words(uint32_t w[8], const scm &s) {
-    sc_to_words(w, s);
-    uint64_t carry = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) { uint64_t t = (uint64_t)w[k] + 0x80808080ull + carry; w[k] = (uint32_t)t; carry = t >> 32; }
-}
+// (signed 8-bit digits without a carry chain: tt8_biased_words, sc.cuh)
 __global__ void __launch_bounds__(256) k_tt_round8(const ge_pniels *__restrict__ table, const scm *__restrict__ a, const scm *__restrict__ b,
                                                    const scm *__restrict__ fG, const scm *__restrict__ fH, const scm *__restrict__ c,
                                                    uint32_t lgM0, uint32_t j, ge_ext *__restrict__ partial /* [2][gridDim.x] */, uint32_t quad) {

@@ -173,4 +173,19 @@ BPG_HD void sc_to_words(uint32_t *w, const scm &a) {
     BPG_UNROLL for (int i = 0; i < 8; i++) w[i] = r.v[i];
 }
 
+// The signed window digits of the table-driven kernels (k_ipa.cuh k_tt_*, k_batch.cuh k_bt_*), without a carry chain between the windows.  Host and device:
+// tests/hostcheck compiles these for the host and tests/test_tail_cases_host.py compares them with an integer model.
+// signed 4-bit digits: nibble w of (s + 0x88..8) minus 8 lies in [-8, 7]
+BPG_HD void tt_biased_words(uint32_t w[8], const scm &s) {
+    sc_to_words(w, s);
+    uint64_t carry = 0;
+    BPG_UNROLL for (int k = 0; k < 8; k++) { uint64_t t = (uint64_t)w[k] + 0x88888888ull + carry; w[k] = (uint32_t)t; carry = t >> 32; }
+}
+// signed 8-bit digits: byte w of (s + 0x80..80) minus 128 lies in [-128, 127]
+BPG_HD void tt8_biased_words(uint32_t w[8], const scm &s) {
+    sc_to_words(w, s);
+    uint64_t carry = 0;
+    BPG_UNROLL for (int k = 0; k < 8; k++) { uint64_t t = (uint64_t)w[k] + 0x80808080ull + carry; w[k] = (uint32_t)t; carry = t >> 32; }
+}
+
 }  // namespace bpg

@@ -656,6 +656,31 @@ bpg_status bpg_test_msm(bpg_ctx *ctx, uint32_t nmsm, uint32_t nseg, const bpg_ms
 bpg_status bpg_test_fold(bpg_ctx *ctx, int32_t kernel, uint32_t lgMr, uint32_t rounds, uint32_t first, uint64_t n, const uint8_t *sG, const uint8_t *sH,
                          const uint8_t u_ch[32], uint8_t *out, char *evidence, uint64_t cap);
 
+/* test hook: the table-driven tail of the inner-product argument (k_tt_bases, k_tt_multiples, k_tt_factors, k_tt_advance, k_tt_round or k_tt_round8, k_tt_finish)
+ * on scalars the caller chooses, through the freeze and per-round steps of the prover, on the context's own generators G[0, M0), H[0, M0) (M0 = 2^lgM0, 2 .. 2^14,
+ * at most the capacity) and the Pedersen base B.  tables: 0 = the context's 4-bit window tables of the original generators (they stay with the context, as after
+ * a proof of M0 multipliers), 1 = 4-bit tables built in the arena, as for folded generators, 2 = the 8-bit tables of the original generators - refused where the
+ * prover would fall back to the 4-bit ones (M0 < 64, or the table budget: BPG_TT_WIDE_GB), so that no case passes on other tables than it names.  a, b: M0
+ * canonical scalars each.  The virtual generators start as G0[p] = gamma0 * fG[p] * G_p, H0[p] = eta0 * yinv^p * fG[p] * H_p with fG[p] = u_ch where first = 1
+ * and p >= n (then M0/2 < n <= M0; first = 0: n and u_ch are not used), else 1.  Sub-round j (h = M0 >> (j+1)) gives
+ *     L_j = sum_{i<h} a[i] Gj[h+i] + b[h+i] Hj[i] + <a_lo, b_hi> w B,   R_j = sum_{i<h} a[h+i] Gj[i] + b[i] Hj[h+i] + <a_hi, b_lo> w B
+ * and then folds with u = u[j]: a'[i] = a[i] u + a[h+i] / u, b'[i] = b[i] / u + b[h+i] u, G'[i] = G[i] / u + u G[h+i], H'[i] = u H[i] + H[h+i] / u.
+ * rounds: 1 .. lgM0 sub-rounds.  lr_out = 2 * rounds encodings L_0, R_0, L_1, ..; ab_out = the folded a, then the folded b, after the last challenge
+ * (M0 >> rounds canonical scalars each).  evidence (cap >= 512) = JSON text: kernel (k_tt_round or k_tt_round8), tables, M0, nblk (blocks per sum of the round
+ * kernel: k_tt_finish adds its B windows to a partial from 256 on, else takes them as they are), quad (the block-sum layout: 1 for a proof alone).  Every
+ * argument is checked before a launch (BPG_ERR_INVALID_ARGUMENT: a NULL pointer, a non-canonical scalar, yinv = 0, a challenge of 0, lgM0, tables, first, n or
+ * rounds out of range); a NULL ctx is BPG_ERR_DEVICE.  (An addition to ABI version 7: look the symbol up.) */
+bpg_status bpg_test_tail(bpg_ctx *ctx, uint32_t lgM0, uint32_t tables, uint32_t first, uint64_t n, const uint8_t *a, const uint8_t *b, const uint8_t yinv[32],
+                         const uint8_t u_ch[32], const uint8_t gamma0[32], const uint8_t eta0[32], const uint8_t w[32], uint32_t rounds, const uint8_t *u,
+                         uint8_t *lr_out, uint8_t *ab_out, char *evidence, uint64_t cap);
+/* test hook: A_I = <aL, G> + <aR, H> + blind[0] B_blinding, A_O = <aO, G> + blind[1] B_blinding, S = <sL, G> + <sR, H> + blind[2] B_blinding from the context's
+ * window tables of the original generators G[0, M0), H[0, M0) (k_tt_commit3, k_tt_commit3_finish, as a proof of at most 2^14 multipliers computes them):
+ * M0 = 2^lgM0 (1 .. 2^14, at most the capacity), n = 1 .. M0 canonical scalars per vector, blind = three canonical scalars.  out = the three encodings;
+ * evidence (cap >= 512) = JSON text: M0, n, nblk (blocks per sum: the finish kernel adds its blinding windows to a partial from 256 on), quad.  Arguments are
+ * checked before a launch (BPG_ERR_INVALID_ARGUMENT); a NULL ctx is BPG_ERR_DEVICE.  (An addition to ABI version 7: look the symbol up.) */
+bpg_status bpg_test_commit3(bpg_ctx *ctx, uint32_t lgM0, uint64_t n, const uint8_t *aL, const uint8_t *aR, const uint8_t *aO, const uint8_t *sL, const uint8_t *sR,
+                            const uint8_t blind[96], uint8_t out[96], char *evidence, uint64_t cap);
+
 /* test hook: k_decompress, the verifier's RFC 9496 decoder, on n encodings of 32 bytes, launched as bpg_r1cs_verify launches it.  ok_out[i] = 1 when
  * encoding i is accepted; xy_out holds, for EVERY entry, the affine x || y (32 + 32 bytes, canonical) the kernel wrote, recovered on the host from
  * its halved Niels form (x = ypx - ymx, y = ypx + ymx) - meaningful where ok_out[i] = 1.  Arguments are checked before any launch

@@ -39,6 +39,14 @@ void hc_sc_op(int op, uint8_t *out, const uint8_t *a, const uint8_t *b) {
     switch (op) { case 0: r = sc_mont_mul(x, y); break; case 1: r = sc_add(x, y); break; case 2: r = sc_sub(x, y); break; default: r = sc_neg(x); break; }
     sc_to_words(w, r); memcpy(out, w, 32);
 }
+// the signed window digits the table-driven kernels read (sc.cuh tt_biased_words / tt8_biased_words), extracted as k_tt_round / k_tt_round8 extract them: wide = 0:
+// 64 digits of 4 bits, wide = 1: 32 digits of 8 bits, least significant first, of the scalar `in` (32 bytes, any value: reduced mod l on the way in)
+void hc_tt_digits(int wide, int32_t *out, const uint8_t *in) {
+    uint32_t w[8]; memcpy(w, in, 32);
+    const scm s = sc_from_words(w);
+    if (wide) { tt8_biased_words(w, s); for (int k = 0; k < 32; k++) out[k] = (int32_t)((w[k >> 2] >> (8 * (k & 3))) & 255u) - 128; }
+    else { tt_biased_words(w, s); for (int k = 0; k < 64; k++) out[k] = (int32_t)((w[k >> 3] >> (4 * (k & 7))) & 15u) - 8; }
+}
 void hc_from_uniform(uint8_t *out, const uint8_t *in64) { uint32_t w[16]; memcpy(w, in64, 64); ge_compress(out, ge_from_uniform_words(w)); }
 // double-and-add k*P + (P as niels via inversion) exercising dbl / madd / msub / add / to_niels / compress
 void hc_scalarmul_uniform(uint8_t *out, const uint8_t *k32, const uint8_t *in64) {
