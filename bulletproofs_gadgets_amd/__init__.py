@@ -719,6 +719,41 @@ def test_verify_replay(n, m, gens_capacity, transcript_state, proof, seed, flags
     return status.value, bool(decided.value)
 
 
+def _script_bytes(script):
+    """a script of challenges (y, z, u, x, w, u_1 .. u_lgN: 32-byte scalars) -> (bytes, count); the library checks what it holds"""
+    script = [bytes(s) for s in script]
+    if any(len(s) != 32 for s in script):
+        raise ValueError("every script entry is a 32-byte scalar")
+    return b"".join(script), len(script)
+
+
+def _script_arrays(scripts):
+    """one script per item -> (const uint8_t *const *, uint64_t *, keep-alive)"""
+    packed = [_script_bytes(s) for s in scripts]
+    n = max(len(packed), 1)
+    ptrs, lens = (C.c_char_p * n)(), (C.c_uint64 * n)()
+    for k, (b, ln) in enumerate(packed):
+        ptrs[k], lens[k] = b, ln
+    return ptrs, lens, packed
+
+
+def test_verify_replay_scripted(n, m, gens_capacity, transcript_state, proof, seed, flags=0, script=None):
+    """bpg_test_verify_replay_scripted (no device): test_verify_replay on a transcript that hands out `script` (None: a plain transcript) ->
+    (status, transcript state after, the challenges the replay drew - zero where it did not get -, script entries consumed).  Raises BpgError
+    (INVALID_ARGUMENT) for a script the hooks refuse."""
+    N = 1
+    while N < n:
+        N *= 2
+    count = 5 + N.bit_length() - 1
+    ts = _buf(203); ts.raw = _exact("transcript_state", transcript_state, 203)
+    status, consumed, ch = C.c_int32(-1), C.c_uint64(0), _buf(32 * count)
+    proof = bytes(proof)
+    sb, sn = _script_bytes(script) if script is not None else (None, 0)
+    _chk(lib().bpg_test_verify_replay_scripted(C.c_uint64(n), C.c_uint64(m), C.c_uint64(gens_capacity), ts, proof, C.c_uint64(len(proof)), _exact("seed", seed, 32),
+                                               C.c_uint32(flags), sb, C.c_uint64(sn), C.byref(status), ch, C.byref(consumed)))
+    return status.value, ts.raw[:203], [ch.raw[32 * k:32 * k + 32] for k in range(count)], consumed.value
+
+
 def test_check_host(inst, v=None, max_rows=16) -> "CheckReport":
     """bpg_test_check_host (no device): the definition of bpg_r1cs_check in host C++ on an instance with its witness; v: the m committed values (None: inst.v)"""
     v = inst.v if v is None else v
@@ -882,6 +917,24 @@ def _context_verify_batch(self, items, batch_seed=None, return_status=False):
 Context.verify_batch = _context_verify_batch
 
 
+def _context_test_verify_batch_scripted(self, items, scripts, batch_seed=None):
+    """bpg_test_verify_batch_scripted: verify_batch(items) with item k's transcript handing out scripts[k] (the weights stay real) ->
+    (call status, statuses, transcript states after).  A scripted acceptance says nothing about a statement.  A refused call raises BpgError."""
+    if len(scripts) != len(items):
+        raise ValueError("one script per item")
+    arr, states, keep = _verify_items(items)
+    ptrs, lens, keep2 = _script_arrays(scripts)
+    n = len(items)
+    status = (C.c_int32 * max(n, 1))()
+    rc = lib().bpg_test_verify_batch_scripted(self._h, C.c_uint64(n), arr, ptrs, lens, _seed32(batch_seed), status)
+    if rc not in (0, 1, 2, 3):
+        _chk(rc)
+    return rc, [status[k] for k in range(n)], [ts.raw[:203] for ts in states]
+
+
+Context.test_verify_batch_scripted = _context_test_verify_batch_scripted
+
+
 def _context_join(self, parts):
     """bpg_r1cs_template_join: parts = [(template, count)] -> ONE resident template that holds count_0 copies of part 0, then count_1 of part 1, ... - the
     circuit of one host assembly of the parts' gadget code in that order, made on the device from the resident templates (a mixed statement, one proof).
@@ -968,6 +1021,22 @@ def _context_prove_batch(self, items, return_status=False):
 
 
 Context.prove_batch = _context_prove_batch
+
+
+def _context_test_prove_batch_scripted(self, items, scripts):
+    """bpg_test_prove_batch_scripted: prove_batch(items), every item in lockstep, with item k's transcript handing out scripts[k] ->
+    [(proof, transcript state after)].  NOT sound proofs.  Raises BpgError: a script the hook refuses or an item off the lockstep path refuses the whole call."""
+    if len(scripts) != len(items):
+        raise ValueError("one script per item")
+    arr, keep = _batch_items(items)
+    ptrs, lens, keep2 = _script_arrays(scripts)
+    n = len(items)
+    status = (C.c_int32 * max(n, 1))()
+    _chk(lib().bpg_test_prove_batch_scripted(self._h, C.c_uint64(n), arr, ptrs, lens, status))
+    return [(k[2].raw[:k[3].value], k[1].raw[:203]) for k in keep]
+
+
+Context.test_prove_batch_scripted = _context_test_prove_batch_scripted
 
 
 class ProverPool:
@@ -1126,6 +1195,28 @@ class ResidentCircuit:
         _chk(lib().bpg_r1cs_prove_resident(self.ctx._h, self._h, ts, C.c_uint64(self.m), v_blinding, rng_seed, C.c_uint32(flags),
                                            out, C.byref(ln), C.byref(tm) if timings else None))
         return (out.raw[:ln.value], ts.raw[:203], tm.as_dict()) if timings else (out.raw[:ln.value], ts.raw[:203])
+
+    def test_prove_scripted(self, transcript_state, v_blinding, script, rng_seed=None, flags=0):
+        """bpg_test_prove_scripted: prove() with the transcript handing out `script` (y, z, u, x, w, u_1 .. u_lgN) -> (proof, state after).  NOT a sound proof."""
+        ts = _buf(203); ts.raw = _exact("transcript_state", transcript_state, 203)
+        v_blinding, rng_seed = _exact("v_blinding", v_blinding, 32 * self.m), _seed32(rng_seed)
+        cap = lib().bpg_proof_size(self.n, flags)
+        out = _buf(cap); ln = C.c_uint64(cap)
+        sb, sn = _script_bytes(script)
+        _chk(lib().bpg_test_prove_scripted(self.ctx._h, self._h, ts, C.c_uint64(self.m), v_blinding, rng_seed, C.c_uint32(flags), sb, C.c_uint64(sn), out, C.byref(ln)))
+        return out.raw[:ln.value], ts.raw[:203]
+
+    def test_verify_scripted(self, transcript_state, commitments, proof, script, seed=None, flags=0):
+        """bpg_test_verify_scripted: verify() with the transcript handing out `script` -> (status as verify() gives it, state after).  Raises BpgError for a
+        refused script."""
+        ts = _buf(203); ts.raw = _exact("transcript_state", transcript_state, 203)
+        seed, commitments, proof = _seed32(seed), _exact("commitments", commitments, 32 * self.m), bytes(proof)
+        sb, sn = _script_bytes(script)
+        rc = lib().bpg_test_verify_scripted(self.ctx._h, self._h, ts, C.c_uint64(self.m), commitments, proof, C.c_uint64(len(proof)), seed, C.c_uint32(flags),
+                                            sb, C.c_uint64(sn))
+        if rc not in (0, 1, 2, 3):
+            _chk(rc)
+        return rc, ts.raw[:203]
 
     def _template_items(self, items, struct=_TemplateItem):
         """bpg_template_item array of [(values, params, transcript_state, v_blinding, rng_seed, flags)] and the buffers it points into:

@@ -211,7 +211,7 @@ bpg_status bpg_pedersen_commit(bpg_ctx *ctx, uint64_t k, const uint8_t *v, const
     return guard([&] { REQUIRE(ctx && (k == 0 || (v && blind && out))); ctx->engine->pedersen_commit(k, v, blind, out); });
 }
 bpg_status bpg_test_fe_ops(bpg_ctx *ctx, int32_t op, uint64_t n, const uint8_t *a, const uint8_t *b, uint8_t *out) {
-    return guard([&] { REQUIRE(ctx && op >= 0 && op <= 6 && (n == 0 || (a && b && out))); ctx->engine->test_fe_ops(op, n, a, b, out); });
+    return guard([&] { REQUIRE(ctx && op >= 0 && op <= 10 && (n == 0 || (a && b && out))); ctx->engine->test_fe_ops(op, n, a, b, out); });
 }
 bpg_status bpg_msm_gens(bpg_ctx *ctx, uint64_t first, uint64_t count, const uint8_t *s, const uint8_t *t, uint8_t out[32]) {
     return guard([&] { REQUIRE(ctx && out && (count == 0 || (s && t))); ctx->engine->msm_gens(first, count, s, t, out); });
@@ -282,6 +282,21 @@ bpg_status bpg_test_verify_replay(uint64_t n, uint64_t m, uint64_t gens_capacity
         static const uint8_t none = 0;
         const R1CSError e = Engine::test_verify_replay(n, m, gens_capacity, T, proof ? proof : &none, proof_len, seed, flags);
         *status_out = (bpg_status)e; *decided_out = e != R1CSError::None;
+    });
+}
+bpg_status bpg_test_verify_replay_scripted(uint64_t n, uint64_t m, uint64_t gens_capacity, uint8_t ts[BPG_TRANSCRIPT_STATE_BYTES], const uint8_t *proof,
+                                           uint64_t proof_len, const uint8_t seed[32], uint32_t flags, const uint8_t *script, uint64_t script_len,
+                                           bpg_status *status_out, uint8_t *challenges_out, uint64_t *consumed_out) {
+    return guard([&] {
+        REQUIRE(ts && seed && status_out && challenges_out && consumed_out && (proof_len == 0 || proof));
+        if (n > (1ull << 32)) throw std::invalid_argument("test_verify_replay_scripted: n above 2^32");
+        Transcript T = Transcript::from_state(ts);
+        if (script) Engine::script_transcript(T, n, script, script_len);
+        std::memset(challenges_out, 0, 32 * (5 + (size_t)ceil_log2(padded_size(n))));
+        static const uint8_t none = 0;
+        const R1CSError e = Engine::test_verify_replay_scripted(n, m, gens_capacity, T, proof ? proof : &none, proof_len, seed, flags, challenges_out, consumed_out);
+        T.export_state(ts);
+        *status_out = (bpg_status)e;
     });
 }
 bpg_status bpg_profile_set(bpg_ctx *ctx, int32_t mode) { return guard([&] { REQUIRE(ctx && mode >= 0 && mode <= 2); ctx->engine->profile_set(mode); }); }
@@ -678,14 +693,16 @@ static void copy_timings(const ProveTimings &t, bpg_timings *o) {
     o->ipa_msm = t.ipa_msm; o->ipa_fold = t.ipa_fold; o->ipa_sync = t.ipa_sync;
 }
 
-bpg_status bpg_r1cs_prove_resident(bpg_ctx *ctx, bpg_circuit *c, uint8_t ts[BPG_TRANSCRIPT_STATE_BYTES], uint64_t m, const uint8_t *v_blinding,
-                                   const uint8_t seed[32], uint32_t flags, uint8_t *proof_out, uint64_t *proof_len, bpg_timings *timings) {
+// script: null everywhere but in the bpg_test_*_scripted hooks, which run the same body on a transcript that hands out the challenges their caller chose
+static bpg_status prove_resident(bpg_ctx *ctx, bpg_circuit *c, uint8_t ts[BPG_TRANSCRIPT_STATE_BYTES], uint64_t m, const uint8_t *v_blinding, const uint8_t seed[32],
+                                 uint32_t flags, uint8_t *proof_out, uint64_t *proof_len, bpg_timings *timings, const uint8_t *script, uint64_t script_len) {
     return guard([&] {
         REQUIRE(ctx && c && c->dc && ts && seed && proof_out && proof_len && (m == 0 || v_blinding));
         if (m != c->m) throw std::invalid_argument("prove: m does not match the uploaded circuit");
         if (*proof_len < bpg_proof_size(c->n, flags)) throw std::invalid_argument("prove: proof buffer too small");
         require_gens_capacity(ctx->engine->gens_capacity(), c->n, " (call bpg_gens_ensure)");
         Transcript T = Transcript::from_state(ts);
+        if (script) Engine::script_transcript(T, c->n, script, script_len);
         std::vector<Scalar> vb(m);
         for (uint64_t i = 0; i < m; i++) vb[i] = Scalar::from_bytes_mod_order(v_blinding + 32 * i);
         ProveTimings tm;
@@ -694,6 +711,15 @@ bpg_status bpg_r1cs_prove_resident(bpg_ctx *ctx, bpg_circuit *c, uint8_t ts[BPG_
         T.export_state(ts);
         copy_timings(tm, timings);
     });
+}
+bpg_status bpg_r1cs_prove_resident(bpg_ctx *ctx, bpg_circuit *c, uint8_t ts[BPG_TRANSCRIPT_STATE_BYTES], uint64_t m, const uint8_t *v_blinding,
+                                   const uint8_t seed[32], uint32_t flags, uint8_t *proof_out, uint64_t *proof_len, bpg_timings *timings) {
+    return prove_resident(ctx, c, ts, m, v_blinding, seed, flags, proof_out, proof_len, timings, nullptr, 0);
+}
+bpg_status bpg_test_prove_scripted(bpg_ctx *ctx, bpg_circuit *c, uint8_t ts[BPG_TRANSCRIPT_STATE_BYTES], uint64_t m, const uint8_t *v_blinding, const uint8_t seed[32],
+                                   uint32_t flags, const uint8_t *script, uint64_t script_len, uint8_t *proof_out, uint64_t *proof_len) {
+    if (!script) { g_last_error = "null or invalid argument: script"; return BPG_ERR_INVALID_ARGUMENT; }
+    return prove_resident(ctx, c, ts, m, v_blinding, seed, flags, proof_out, proof_len, nullptr, script, script_len);
 }
 
 bpg_status bpg_r1cs_prove(bpg_ctx *ctx, const bpg_r1cs_instance *inst, uint8_t ts[BPG_TRANSCRIPT_STATE_BYTES], uint64_t m, const uint8_t *v_blinding,
@@ -719,9 +745,22 @@ static bpg_status batch_status(const std::vector<bpg_status> &st, const std::vec
     return first;
 }
 
-bpg_status bpg_r1cs_prove_batch(bpg_ctx *ctx, uint64_t count, const bpg_batch_item *items, bpg_status *status_out) {
+// scripts: null everywhere but in bpg_test_prove_batch_scripted - one script per item, every item through Engine::prove_batch (an item that would take the
+// single path is refused), and a bad script refuses the whole call before anything is launched
+static bpg_status prove_batch(bpg_ctx *ctx, uint64_t count, const bpg_batch_item *items, bpg_status *status_out, const uint8_t *const *scripts, const uint64_t *script_lens) {
     if (!ctx || (count && (!items || !status_out))) { g_last_error = "null or invalid argument: ctx, items and status_out"; return BPG_ERR_INVALID_ARGUMENT; }
     if (!count) { g_last_error.clear(); return BPG_OK; }
+    if (scripts) {
+        const bpg_status s = guard([&] {
+            for (uint64_t k = 0; k < count; k++) {
+                REQUIRE(items[k].inst && scripts[k]);
+                Transcript probe;
+                Engine::script_transcript(probe, items[k].inst->n, scripts[k], script_lens[k]);
+                if (!ctx->engine->lockstep_eligible(items[k].inst->n, items[k].flags)) throw std::invalid_argument("prove_batch_scripted: item " + std::to_string(k) + " is not lockstep-eligible");
+            }
+        });
+        if (s != BPG_OK) return s;
+    }
     std::vector<bpg_status> st(count, BPG_OK);
     std::vector<std::string> msg(count);
     std::vector<FlatView> views(count);
@@ -744,6 +783,7 @@ bpg_status bpg_r1cs_prove_batch(bpg_ctx *ctx, uint64_t count, const bpg_batch_it
         if (st[k] != BPG_OK) { msg[k] = g_last_error; continue; }
         if (!ctx->engine->lockstep_eligible(views[k].n, it.flags)) { single_at.push_back(k); continue; }
         T[k] = Transcript::from_state(it.transcript_state);
+        if (scripts) Engine::script_transcript(T[k], views[k].n, scripts[k], script_lens[k]);       // (checked above: does not throw)
         vb[k].resize(it.m);
         for (uint64_t i = 0; i < it.m; i++) vb[k][i] = Scalar::from_bytes_mod_order(it.v_blinding + 32 * i);
         Engine::ProveItem p; p.flat = &views[k]; p.T = &T[k]; p.vb = &vb[k]; p.seed = it.rng_seed; p.flags = it.flags;
@@ -766,6 +806,14 @@ bpg_status bpg_r1cs_prove_batch(bpg_ctx *ctx, uint64_t count, const bpg_batch_it
         if (st[k] != BPG_OK) msg[k] = g_last_error;
     }
     return batch_status(st, msg, status_out);
+}
+bpg_status bpg_r1cs_prove_batch(bpg_ctx *ctx, uint64_t count, const bpg_batch_item *items, bpg_status *status_out) {
+    return prove_batch(ctx, count, items, status_out, nullptr, nullptr);
+}
+bpg_status bpg_test_prove_batch_scripted(bpg_ctx *ctx, uint64_t count, const bpg_batch_item *items, const uint8_t *const *scripts, const uint64_t *script_lens,
+                                         bpg_status *status_out) {
+    if (count && (!scripts || !script_lens)) { g_last_error = "null or invalid argument: scripts and script_lens"; return BPG_ERR_INVALID_ARGUMENT; }
+    return prove_batch(ctx, count, items, status_out, count ? scripts : nullptr, script_lens);
 }
 
 // the whole call is refused before anything is written or launched; a handle without device state first, whatever else was passed
@@ -953,19 +1001,31 @@ bpg_status bpg_r1cs_verify(bpg_ctx *ctx, const bpg_r1cs_instance *inst, uint8_t 
     });
 }
 
-bpg_status bpg_r1cs_verify_resident(bpg_ctx *ctx, bpg_circuit *c, uint8_t ts[BPG_TRANSCRIPT_STATE_BYTES], uint64_t m, const uint8_t *V,
-                                    const uint8_t *proof, uint64_t proof_len, const uint8_t seed[32], uint32_t flags) {
+static bpg_status verify_resident(bpg_ctx *ctx, bpg_circuit *c, uint8_t ts[BPG_TRANSCRIPT_STATE_BYTES], uint64_t m, const uint8_t *V, const uint8_t *proof,
+                                  uint64_t proof_len, const uint8_t seed[32], uint32_t flags, const uint8_t *script, uint64_t script_len) {
     return guard([&] {
         REQUIRE(ctx && c && c->dc && ts && proof && seed && (m == 0 || V));
         if (m != c->m) throw std::invalid_argument("verify: m does not match the uploaded circuit");
         Transcript T = Transcript::from_state(ts);
+        if (script) Engine::script_transcript(T, c->n, script, script_len);
         const R1CSError e = ctx->engine->verify(c->dc, T, V, proof, proof_len, seed, flags);
         T.export_state(ts);
         if (e != R1CSError::None) throw R1CSException(e, e == R1CSError::VerificationError ? "proof rejected" : e == R1CSError::FormatError ? "malformed proof" : "generator capacity below padded circuit size");
     });
 }
 
-bpg_status bpg_r1cs_verify_batch(bpg_ctx *ctx, uint64_t count, const bpg_verify_item *items, const uint8_t batch_seed[32], bpg_status *status_out) {
+bpg_status bpg_r1cs_verify_resident(bpg_ctx *ctx, bpg_circuit *c, uint8_t ts[BPG_TRANSCRIPT_STATE_BYTES], uint64_t m, const uint8_t *V,
+                                    const uint8_t *proof, uint64_t proof_len, const uint8_t seed[32], uint32_t flags) {
+    return verify_resident(ctx, c, ts, m, V, proof, proof_len, seed, flags, nullptr, 0);
+}
+bpg_status bpg_test_verify_scripted(bpg_ctx *ctx, bpg_circuit *c, uint8_t ts[BPG_TRANSCRIPT_STATE_BYTES], uint64_t m, const uint8_t *V, const uint8_t *proof,
+                                    uint64_t proof_len, const uint8_t seed[32], uint32_t flags, const uint8_t *script, uint64_t script_len) {
+    if (!script) { g_last_error = "null or invalid argument: script"; return BPG_ERR_INVALID_ARGUMENT; }
+    return verify_resident(ctx, c, ts, m, V, proof, proof_len, seed, flags, script, script_len);
+}
+
+static bpg_status verify_batch(bpg_ctx *ctx, uint64_t count, const bpg_verify_item *items, const uint8_t batch_seed[32], bpg_status *status_out,
+                               const uint8_t *const *scripts, const uint64_t *script_lens) {
     return guard([&] {
         REQUIRE(ctx);
         if (!count) return;
@@ -991,6 +1051,7 @@ bpg_status bpg_r1cs_verify_batch(bpg_ctx *ctx, uint64_t count, const bpg_verify_
                 e.dc = it.circuit->dc;
             }
             T[k] = Transcript::from_state(it.transcript_state);
+            if (scripts) { REQUIRE(scripts[k]); Engine::script_transcript(T[k], it.inst ? views[k].n : it.circuit->n, scripts[k], script_lens[k]); }
             e.T = &T[k]; e.V = it.V; e.proof = it.proof; e.proof_len = it.proof_len; e.seed = it.seed; e.flags = it.flags;
         }
         std::vector<R1CSError> st(count);
@@ -1006,6 +1067,14 @@ bpg_status bpg_r1cs_verify_batch(bpg_ctx *ctx, uint64_t count, const bpg_verify_
             throw R1CSException(e, "item " + std::to_string(first) + ": " + (e == R1CSError::VerificationError ? "proof rejected" : e == R1CSError::FormatError ? "malformed proof" : "generator capacity below padded circuit size"));
         }
     });
+}
+bpg_status bpg_r1cs_verify_batch(bpg_ctx *ctx, uint64_t count, const bpg_verify_item *items, const uint8_t batch_seed[32], bpg_status *status_out) {
+    return verify_batch(ctx, count, items, batch_seed, status_out, nullptr, nullptr);
+}
+bpg_status bpg_test_verify_batch_scripted(bpg_ctx *ctx, uint64_t count, const bpg_verify_item *items, const uint8_t *const *scripts, const uint64_t *script_lens,
+                                          const uint8_t batch_seed[32], bpg_status *status_out) {
+    if (count && (!scripts || !script_lens)) { g_last_error = "null or invalid argument: scripts and script_lens"; return BPG_ERR_INVALID_ARGUMENT; }
+    return verify_batch(ctx, count, items, batch_seed, status_out, count ? scripts : nullptr, script_lens);
 }
 
 // ---------------------------------------------------------------------------------------- batch pool

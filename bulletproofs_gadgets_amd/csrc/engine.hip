@@ -3249,6 +3249,32 @@ R1CSError Engine::test_verify_replay(uint64_t n, uint64_t m, uint64_t gens_cap, 
     return verify_replay(n, m, gens_cap, T, proof, proof_len, seed, flags, R);
 }
 
+// The scripted transcript of the bpg_test_*_scripted hooks: y, z, u, x, w, u_1 .. u_lgN for a circuit of n multipliers, checked before anything is launched
+void Engine::script_transcript(Transcript &T, uint64_t n, const uint8_t *script, uint64_t script_len) {
+    const uint32_t lgN = ceil_log2(padded_size(n));
+    if (!script) throw std::invalid_argument("scripted: null script");
+    if (script_len != 5 + (uint64_t)lgN) throw std::invalid_argument("scripted: a script for lg N = " + std::to_string(lgN) + " has " + std::to_string(5 + lgN) + " entries (y, z, u, x, w, u_1 .. u_lgN), not " + std::to_string(script_len));
+    std::vector<Scalar> s(script_len);
+    for (uint64_t k = 0; k < script_len; k++) {
+        std::memcpy(s[k].w, script + 32 * k, 32);
+        if (!s[k].is_canonical()) throw std::invalid_argument("scripted: entry " + std::to_string(k) + " is not canonical");
+        if ((k == 0 || k >= 5) && (s[k].w[0] | s[k].w[1] | s[k].w[2] | s[k].w[3]) == 0) throw std::invalid_argument("scripted: entry " + std::to_string(k) + " is zero (y and every u_k are inverted)");
+    }
+    T.attach_script(std::move(s));
+}
+
+// bpg_test_verify_replay_scripted: the same replay, with the challenges it drew (y, z, u, x, w, u_1 .. u_lgN as far as it got) and how many script entries it took
+R1CSError Engine::test_verify_replay_scripted(uint64_t n, uint64_t m, uint64_t gens_cap, Transcript &T, const uint8_t *proof, size_t proof_len, const uint8_t seed[32],
+                                              uint32_t flags, uint8_t *challenges_out, uint64_t *consumed_out) {
+    VerifyReplay R;
+    const R1CSError e = verify_replay(n, m, gens_cap, T, proof, proof_len, seed, flags, R);
+    const Scalar *five[5] = {&R.y, &R.z, &R.u_ch, &R.x, &R.w};
+    for (int k = 0; k < 5; k++) five[k]->to_bytes(challenges_out + 32 * k);
+    for (size_t k = 0; k < R.uk.size(); k++) R.uk[k].to_bytes(challenges_out + 32 * (5 + k));
+    *consumed_out = T.script_cursor();
+    return e;
+}
+
 R1CSError Engine::verify(DeviceCircuit *c, Transcript &T, const uint8_t *V, const uint8_t *proof, size_t proof_len, const uint8_t seed[32], uint32_t flags) {
     HIPCHK(hipSetDevice(device_));
     Impl &I = *impl_;
@@ -3310,12 +3336,12 @@ void Engine::verify_batch(size_t count, const VerifyItem *items, const uint8_t b
     I.shared_now = I.shared_variants();
     // ---- host phase: format checks and Fiat-Shamir replay of every item (the states before, for the item-by-item pass of a rejected batch)
     std::vector<VerifyReplay> R(count);
-    std::vector<std::array<uint8_t, 203>> before(count);
+    std::vector<Transcript> before(count);                      // (copies, not exported states: a scripted transcript of the test hooks keeps its script)
     std::vector<uint8_t> live(count, 0);
     for (size_t k = 0; k < count; k++) {
         const VerifyItem &it = items[k];
         const uint64_t n = it.dc ? it.dc->n : it.flat->n, m = it.dc ? it.dc->m : it.flat->m;
-        it.T->export_state(before[k].data());
+        before[k] = *it.T;
         status_out[k] = verify_replay(n, m, gens_cap_, *it.T, it.proof, it.proof_len, it.seed, it.flags, R[k]);
         live[k] = status_out[k] == R1CSError::None;
     }
@@ -3420,7 +3446,7 @@ void Engine::verify_batch(size_t count, const VerifyItem *items, const uint8_t b
     for (size_t k = 0; k < count; k++) {
         if (!live[k]) continue;
         const VerifyItem &it = items[k];
-        *it.T = Transcript::from_state(before[k].data());
+        *it.T = before[k];
         DeviceCircuit *c = it.dc;
         const bool own = c == nullptr;
         if (own) c = upload(*it.flat);

@@ -189,6 +189,14 @@ public:
     // unit-test hook (bpg_test_verify_replay): R1CSProof::from_bytes and the Fiat-Shamir replay alone - None means "left to the device"; no device work
     static R1CSError test_verify_replay(uint64_t n, uint64_t m, uint64_t gens_cap, Transcript &T, const uint8_t *proof, size_t proof_len,
                                         const uint8_t seed[32], uint32_t flags);
+    // test seam (include/bpg.h bpg_test_prove_scripted and its siblings): attach to T a script of challenges y, z, u, x, w, u_1 .. u_lgN for a circuit of n
+    // multipliers (host/merlin.hpp Transcript::attach_script), after which prove(), prove_batch(), verify() and verify_batch() run on T as on any transcript.
+    // Refused (std::invalid_argument): a length other than 5 + lg N, a non-canonical entry, y or a u_k of zero.  No device work.
+    static void script_transcript(Transcript &T, uint64_t n, const uint8_t *script, uint64_t script_len);
+    // unit-test hook (bpg_test_verify_replay_scripted): test_verify_replay, plus the challenges the replay drew (challenges_out: (5 + lg N) x 32, zero where it
+    // did not get) and the number of script entries T gave out
+    static R1CSError test_verify_replay_scripted(uint64_t n, uint64_t m, uint64_t gens_cap, Transcript &T, const uint8_t *proof, size_t proof_len,
+                                                 const uint8_t seed[32], uint32_t flags, uint8_t *challenges_out, uint64_t *consumed_out);
     // Verifier::verify on a resident (assignment-free) circuit. transcript: state after Verifier::new + every "V" append.
     R1CSError verify(DeviceCircuit *c, Transcript &transcript, const uint8_t *V, const uint8_t *proof, size_t proof_len,
                      const uint8_t seed[32], uint32_t flags);

@@ -180,17 +180,22 @@ __global__ void k_init_bases(const uint32_t *__restrict__ hash64, ge_niels *__re
 // unit-test hook for the device field arithmetic (the inline-asm paths cannot be compiled for the host):
 // op 0 mul, 1 sq, 2 add, 3 sub, 4 invert, 5 chain (mixed ops on weakly reduced intermediates); inputs are raw 256-bit values;
 // op 6: the SCALAR Montgomery product sc_mont_mul(a, b) = a b / 2^256 mod l (sc.cuh device path), raw words out
+// op 7 sc_add(a, b), 8 sc_sub(a, b), 9 sc_neg(a) (operands below l), 10 sc_to_words(a) = a / 2^256 mod l: the device code of the other scalar operations, raw words out
 __global__ void __launch_bounds__(64) k_test_fe(const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, uint8_t *__restrict__ out, uint32_t n, uint32_t op) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     fe x, y, r;
 #pragma unroll
     for (int k = 0; k < 8; k++) { x.v[k] = a[8 * i + k]; y.v[k] = b[8 * i + k]; }
-    if (op == 6) {
-        scm sa, sb;
+    if (op >= 6) {
+        scm sa, sb, sr;
 #pragma unroll
         for (int k = 0; k < 8; k++) { sa.v[k] = x.v[k]; sb.v[k] = y.v[k]; }
-        const scm sr = sc_mont_mul(sa, sb);
+        if (op == 6) sr = sc_mont_mul(sa, sb);
+        else if (op == 7) sr = sc_add(sa, sb);
+        else if (op == 8) sr = sc_sub(sa, sb);
+        else if (op == 9) sr = sc_neg(sa);
+        else sc_to_words(sr.v, sa);
         uint32_t *o = reinterpret_cast<uint32_t *>(out + 32 * (size_t)i);
 #pragma unroll
         for (int k = 0; k < 8; k++) o[k] = sr.v[k];

@@ -7,7 +7,9 @@
 #pragma once
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <string>
+#include <vector>
 #if defined(__x86_64__)
 #include <immintrin.h>
 #endif
@@ -454,7 +456,18 @@ public:
     void innerproduct_domain_sep(uint64_t n) { append_message("dom-sep", reinterpret_cast<const uint8_t *>("ipp v1"), 6); append_u64("n", n); }
     void append_scalar(const char *label, const Scalar &s) { append_message(label, s.as_bytes(), 32); }
     void append_point(const char *label, const uint8_t p[32]) { append_message(label, p, 32); }
-    Scalar challenge_scalar(const char *label) { uint8_t b[64]; challenge_bytes(label, b, 64); return Scalar::from_wide(b); }
+    // absorbs and squeezes as always, so the state evolves as it always does; under a script (tests only, below) the squeezed value is dropped and the next
+    // script entry returned in its place
+    Scalar challenge_scalar(const char *label) {
+        uint8_t b[64]; challenge_bytes(label, b, 64);
+        if (script_ && cursor_ < script_->size()) return (*script_)[cursor_++];
+        return Scalar::from_wide(b);
+    }
+    // TEST SEAM (include/bpg.h bpg_test_*_scripted): challenge_scalar returns these canonical scalars, in order, until they run out.  Copies of a transcript carry
+    // the script and the cursor along; export_state / from_state never do, so no transcript that crossed the C ABI has one.  build_rng never looks at it.
+    void attach_script(std::vector<Scalar> script) { script_ = std::make_shared<const std::vector<Scalar>>(std::move(script)); cursor_ = 0; }
+    bool scripted() const { return script_ != nullptr; }
+    size_t script_cursor() const { return cursor_; }
 
     // build_rng().rekey_with_witness_bytes("v_blinding", ..)*.finalize(seed)
     TranscriptRng build_rng(const std::vector<Scalar> &v_blinding, const uint8_t seed[32]) const {
@@ -471,6 +484,8 @@ public:
     }
 private:
     Strobe128 s_;
+    std::shared_ptr<const std::vector<Scalar>> script_;
+    size_t cursor_ = 0;
 };
 
 }  // namespace bpg

@@ -606,7 +606,8 @@ bpg_status bpg_profile_report(bpg_ctx *ctx, char *out, uint64_t cap);
 bpg_status bpg_bench_fe_mul(bpg_ctx *ctx, uint32_t iters, double *mults_per_second);
 
 /* test hook: device field arithmetic on n pairs of raw 256-bit values; op 0 mul, 1 sq, 2 add, 3 sub, 4 invert, 5 mixed chain; canonical output;
- * op 6: the scalar-field Montgomery product a b / 2^256 mod l of the device (one operand below l), eight raw words out */
+ * op 6: the scalar-field Montgomery product a b / 2^256 mod l of the device (one operand below l), eight raw words out;
+ * op 7 a + b, 8 a - b, 9 -a mod l (operands below l) and 10 a / 2^256 mod l: the device code of the other scalar operations, eight raw words out */
 bpg_status bpg_test_fe_ops(bpg_ctx *ctx, int32_t op, uint64_t n, const uint8_t *a, const uint8_t *b, uint8_t *out);
 /* test hook: the next blinding stream started on ctx (bpg_blinding_begin) records a failed upload of its first block, as a failing hipMemcpyAsync
  * would: the prove that adopts it must fail with BPG_ERR_DEVICE instead of reading a stale device slab */
@@ -693,6 +694,30 @@ bpg_status bpg_test_decompress(bpg_ctx *ctx, uint64_t n, const uint8_t *in, uint
  * not written.  (An addition to ABI version 7.) */
 bpg_status bpg_test_verify_replay(uint64_t n, uint64_t m, uint64_t gens_capacity, const uint8_t transcript_state[BPG_TRANSCRIPT_STATE_BYTES],
                                   const uint8_t *proof, uint64_t proof_len, const uint8_t seed[32], uint32_t flags, bpg_status *status_out, int32_t *decided_out);
+
+/* test hooks: proofs under a SCRIPTED transcript.  Each call runs exactly what its production sibling runs - bpg_r1cs_prove_resident, bpg_r1cs_prove_batch (the
+ * lockstep path only), bpg_r1cs_verify_resident, bpg_r1cs_verify_batch - on a transcript that absorbs and squeezes as always, so that its 203-byte state evolves
+ * as in the sibling, but whose challenge_scalar RETURNS the next entry of `script` instead of the squeezed value.  script = 5 + lg N canonical scalars of 32
+ * bytes in the order y, z, u, x, w, u_1 .. u_lgN (N = n padded to a power of two); the batch calls take one script per item (scripts[k], script_lens[k]), and
+ * the weights of bpg_test_verify_batch_scripted stay the real ones.  Outputs are the sibling's: proof bytes, the transcript state after, the status.
+ * THE RESULT OF A SCRIPTED CALL IS NOT A SOUND PROOF, and an accepted scripted verification says nothing about a statement: whoever chooses the challenges
+ * can forge.  The script lives in the call's own transcript object and never crosses the ABI: no production entry point can end up with one.
+ * Refused before any launch (BPG_ERR_INVALID_ARGUMENT; a batch call as a whole): a NULL script, script_len != 5 + lg N, a non-canonical entry, y = 0 or a
+ * u_k = 0 (both are inverted; z, u, x, w may be 0); in bpg_test_prove_batch_scripted also an item that bpg_r1cs_prove_batch would prove on the single path.
+ * bpg_test_verify_replay_scripted needs no device: bpg_test_verify_replay on a scripted transcript (script NULL: on a plain one), which also writes the state
+ * after into transcript_state, the challenges the replay drew into challenges_out ((5 + lg N) x 32 bytes, zero where it did not get) and the number of script
+ * entries it took into *consumed_out.  (Additions to ABI version 7: look the symbols up.) */
+bpg_status bpg_test_prove_scripted(bpg_ctx *ctx, bpg_circuit *circuit, uint8_t transcript_state[BPG_TRANSCRIPT_STATE_BYTES], uint64_t m, const uint8_t *v_blinding,
+                                   const uint8_t rng_seed[32], uint32_t flags, const uint8_t *script, uint64_t script_len, uint8_t *proof_out, uint64_t *proof_len);
+bpg_status bpg_test_prove_batch_scripted(bpg_ctx *ctx, uint64_t count, const bpg_batch_item *items, const uint8_t *const *scripts, const uint64_t *script_lens,
+                                         bpg_status *status_out);
+bpg_status bpg_test_verify_scripted(bpg_ctx *ctx, bpg_circuit *circuit, uint8_t transcript_state[BPG_TRANSCRIPT_STATE_BYTES], uint64_t m, const uint8_t *V,
+                                    const uint8_t *proof, uint64_t proof_len, const uint8_t seed[32], uint32_t flags, const uint8_t *script, uint64_t script_len);
+bpg_status bpg_test_verify_batch_scripted(bpg_ctx *ctx, uint64_t count, const bpg_verify_item *items, const uint8_t *const *scripts, const uint64_t *script_lens,
+                                          const uint8_t batch_seed[32], bpg_status *status_out);
+bpg_status bpg_test_verify_replay_scripted(uint64_t n, uint64_t m, uint64_t gens_capacity, uint8_t transcript_state[BPG_TRANSCRIPT_STATE_BYTES], const uint8_t *proof,
+                                           uint64_t proof_len, const uint8_t seed[32], uint32_t flags, const uint8_t *script, uint64_t script_len,
+                                           bpg_status *status_out, uint8_t *challenges_out, uint64_t *consumed_out);
 
 /* ---------------------------------------------------------------------------------------------------- PART 2: host mirror
  * merlin::Transcript, bulletproofs::r1cs::{Prover, Verifier}, and the reference's Gadget trait with BoundsCheck,

@@ -63,6 +63,7 @@ void merlin_append(merlin_transcript *t, const char *label, const uint8_t *msg, 
 
 void merlin_init(merlin_transcript *t, const uint8_t *label, size_t len) {
     strobe_new(&t->s, "Merlin v1.0");
+    t->script = NULL; t->script_len = t->script_pos = 0;
     merlin_append(t, "dom-sep", label, len);
 }
 
@@ -80,6 +81,7 @@ void merlin_challenge_bytes(merlin_transcript *t, const char *label, uint8_t *ou
 
 void merlin_challenge_scalar(merlin_transcript *t, const char *label, sc *out) {
     uint8_t b[64]; merlin_challenge_bytes(t, label, b, 64); sc_frombytes_wide(out, b);
+    if (t->script && t->script_pos < t->script_len) sc_frombytes_mod_order(out, t->script + 32 * t->script_pos++);
 }
 
 void merlin_rng_begin(merlin_rng *r, const merlin_transcript *t) { r->s = t->s; }

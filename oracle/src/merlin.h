@@ -8,7 +8,9 @@
 #include "sc.h"
 
 typedef struct { uint8_t st[200]; uint8_t pos, pos_begin, cur_flags; } strobe128;   /* 203 bytes, packed */
-typedef struct { strobe128 s; } merlin_transcript;
+/* script (tests of chosen challenges): NULL, or script_len canonical scalars of 32 bytes that merlin_challenge_scalar hands out in order, from
+ * script_pos on, INSTEAD of the value it squeezed - the state evolves as without one.  Whoever fills .s by memcpy sets these fields too. */
+typedef struct { strobe128 s; const uint8_t *script; uint64_t script_len, script_pos; } merlin_transcript;
 typedef struct { strobe128 s; } merlin_rng;
 
 void merlin_init(merlin_transcript *t, const uint8_t *label, size_t len);

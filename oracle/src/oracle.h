@@ -61,6 +61,13 @@ int orc_r1cs_prove(const orc_gens *g, uint8_t tstate[203], const orc_circuit *c,
                    const uint8_t seed[32], uint32_t flags, uint8_t *proof, uint64_t *proof_len);
 int orc_r1cs_verify(const orc_gens *g, uint8_t tstate[203], const orc_circuit *c, const uint8_t *V,
                     const uint8_t *proof, uint64_t proof_len, const uint8_t seed[32], uint32_t flags);
+/* The same two under a SCRIPT of challenges (tests of chosen challenges): script = 5 + lg N canonical scalars y, z, u, x, w, u_1 .. u_lgN that every challenge
+ * draw returns, in order, in place of the value the transcript squeezed; the transcript state evolves as without one.  NULL: no script.  ORC_ERR_ARG for a
+ * wrong length, a non-canonical entry, y = 0 or a u_k = 0.  A scripted proof proves nothing. */
+int orc_r1cs_prove_scripted(const orc_gens *g, uint8_t tstate[203], const orc_circuit *c, const uint8_t *v_blinding, const uint8_t seed[32],
+                            uint32_t flags, const uint8_t *script, uint64_t script_len, uint8_t *proof, uint64_t *proof_len);
+int orc_r1cs_verify_scripted(const orc_gens *g, uint8_t tstate[203], const orc_circuit *c, const uint8_t *V, const uint8_t *proof, uint64_t proof_len,
+                             const uint8_t seed[32], uint32_t flags, const uint8_t *script, uint64_t script_len);
 /* 1 when a_L o a_R = a_O and every constraint evaluates to 0 on (aL,aR,aO,v) */
 int orc_r1cs_satisfied(const orc_circuit *c, const uint8_t *v);
 

@@ -209,8 +209,25 @@ static void ipp_create(merlin_transcript *T, const ge *Q, const sc *Gf, const sc
 }
 
 /* ------------------------------------------------------------------------------------------------ prove */
+/* 0 when script is NULL (no script) or holds 5 + lgN canonical scalars with y and every u_k non-zero */
+static int script_bad(const uint8_t *script, uint64_t script_len, size_t lgN) {
+    if (!script) return 0;
+    if (script_len != 5 + lgN) return 1;
+    for (uint64_t k = 0; k < script_len; k++) {
+        sc raw, red; sc_frombytes_raw(&raw, script + 32 * k); sc_reduce(&red, &raw);
+        if (!sc_eq(&raw, &red)) return 1;
+        if ((k == 0 || k >= 5) && sc_iszero(&red)) return 1;
+    }
+    return 0;
+}
+
 int orc_r1cs_prove(const orc_gens *g, uint8_t tstate[203], const orc_circuit *c, const uint8_t *v_blinding,
                    const uint8_t seed[32], uint32_t flags, uint8_t *proof, uint64_t *proof_len) {
+    return orc_r1cs_prove_scripted(g, tstate, c, v_blinding, seed, flags, NULL, 0, proof, proof_len);
+}
+
+int orc_r1cs_prove_scripted(const orc_gens *g, uint8_t tstate[203], const orc_circuit *c, const uint8_t *v_blinding, const uint8_t seed[32],
+                            uint32_t flags, const uint8_t *script, uint64_t script_len, uint8_t *proof, uint64_t *proof_len) {
     ped_init();
     if (!circuit_ok(c)) return ORC_ERR_ARG;
     const size_t n = c->n, m = c->m;
@@ -220,9 +237,11 @@ int orc_r1cs_prove(const orc_gens *g, uint8_t tstate[203], const orc_circuit *c,
     const size_t need = (compact ? 1 + 11 * 32 : 14 * 32) + (2 * lgN + 2) * 32;
     if (*proof_len < need) return ORC_ERR_ARG;
     if (g->cap < N) return ORC_ERR_GENS_LENGTH;
+    if (script_bad(script, script_len, lgN)) return ORC_ERR_ARG;
     void (*big_msm)(ge *, const sc *, const ge *, size_t) = (flags & ORC_FLAG_FAST_MSM) ? msm_vartime : msm_straus_ct;
 
     merlin_transcript T; memcpy(&T.s, tstate, 203);
+    T.script = script; T.script_len = script_len; T.script_pos = 0;
     merlin_append_u64(&T, "m", m);
 
     sc *vb = (sc *)malloc((m ? m : 1) * sizeof(sc));
@@ -365,12 +384,18 @@ int orc_r1cs_prove(const orc_gens *g, uint8_t tstate[203], const orc_circuit *c,
 /* ------------------------------------------------------------------------------------------------ verify */
 int orc_r1cs_verify(const orc_gens *g, uint8_t tstate[203], const orc_circuit *c, const uint8_t *V,
                     const uint8_t *proof, uint64_t proof_len, const uint8_t seed[32], uint32_t flags) {
+    return orc_r1cs_verify_scripted(g, tstate, c, V, proof, proof_len, seed, flags, NULL, 0);
+}
+
+int orc_r1cs_verify_scripted(const orc_gens *g, uint8_t tstate[203], const orc_circuit *c, const uint8_t *V, const uint8_t *proof, uint64_t proof_len,
+                             const uint8_t seed[32], uint32_t flags, const uint8_t *script, uint64_t script_len) {
     ped_init();
     if (!circuit_ok(c)) return ORC_ERR_ARG;
     const size_t n = c->n, m = c->m, N = next_pow2(n);
     size_t lgN = 0; while (((size_t)1 << lgN) < N) lgN++;
     const int compact = (flags & ORC_FLAG_COMPACT_1PHASE) != 0;
     const size_t need = (compact ? 1 + 11 * 32 : 14 * 32) + (2 * lgN + 2) * 32;
+    if (script_bad(script, script_len, lgN)) return ORC_ERR_ARG;
     if (proof_len != need) return ORC_ERR_FORMAT;
     if (g->cap < N) return ORC_ERR_GENS_LENGTH;
     const uint8_t *in = proof;
@@ -391,6 +416,7 @@ int orc_r1cs_verify(const orc_gens *g, uint8_t tstate[203], const orc_circuit *c
       sc_frombytes_raw(&ipb, in); sc_reduce(&r, &ipb); if (!sc_eq(&r, &ipb)) return ORC_ERR_FORMAT; in += 32; }
 
     merlin_transcript T; memcpy(&T.s, tstate, 203);
+    T.script = script; T.script_len = script_len; T.script_pos = 0;
     merlin_append_u64(&T, "m", m);
     /* validate_and_append_point: identity encodings are rejected for first-phase and T points */
     if (!memcmp(pAI, ident, 32) || !memcmp(pAO, ident, 32) || !memcmp(pS, ident, 32)) return ORC_ERR_VERIFY;
@@ -491,19 +517,19 @@ int orc_r1cs_verify(const orc_gens *g, uint8_t tstate[203], const orc_circuit *c
 /* ------------------------------------------------------------------------------------------------ primitives for tests */
 void orc_transcript_init(uint8_t ts[203], const uint8_t *label, uint64_t len) { merlin_transcript t; merlin_init(&t, label, len); memcpy(ts, &t.s, 203); }
 void orc_transcript_append(uint8_t ts[203], const char *label, const uint8_t *msg, uint64_t len) {
-    merlin_transcript t; memcpy(&t.s, ts, 203); merlin_append(&t, label, msg, len); memcpy(ts, &t.s, 203);
+    merlin_transcript t; memcpy(&t.s, ts, 203); t.script = NULL; t.script_len = t.script_pos = 0; merlin_append(&t, label, msg, len); memcpy(ts, &t.s, 203);
 }
 void orc_transcript_append_u64(uint8_t ts[203], const char *label, uint64_t v) {
-    merlin_transcript t; memcpy(&t.s, ts, 203); merlin_append_u64(&t, label, v); memcpy(ts, &t.s, 203);
+    merlin_transcript t; memcpy(&t.s, ts, 203); t.script = NULL; t.script_len = t.script_pos = 0; merlin_append_u64(&t, label, v); memcpy(ts, &t.s, 203);
 }
 void orc_transcript_challenge(uint8_t ts[203], const char *label, uint8_t *out, uint64_t len) {
-    merlin_transcript t; memcpy(&t.s, ts, 203); merlin_challenge_bytes(&t, label, out, len); memcpy(ts, &t.s, 203);
+    merlin_transcript t; memcpy(&t.s, ts, 203); t.script = NULL; t.script_len = t.script_pos = 0; merlin_challenge_bytes(&t, label, out, len); memcpy(ts, &t.s, 203);
 }
 void orc_transcript_challenge_scalar(uint8_t ts[203], const char *label, uint8_t out[32]) {
-    merlin_transcript t; memcpy(&t.s, ts, 203); sc s; merlin_challenge_scalar(&t, label, &s); sc_tobytes(out, &s); memcpy(ts, &t.s, 203);
+    merlin_transcript t; memcpy(&t.s, ts, 203); t.script = NULL; t.script_len = t.script_pos = 0; sc s; merlin_challenge_scalar(&t, label, &s); sc_tobytes(out, &s); memcpy(ts, &t.s, 203);
 }
 void orc_rng_scalars(const uint8_t ts[203], uint64_t m, const uint8_t *vb, const uint8_t seed[32], uint64_t count, uint8_t *out) {
-    merlin_transcript t; memcpy(&t.s, ts, 203);
+    merlin_transcript t; memcpy(&t.s, ts, 203); t.script = NULL; t.script_len = t.script_pos = 0;
     merlin_rng r; merlin_rng_begin(&r, &t);
     for (uint64_t i = 0; i < m; i++) merlin_rng_rekey(&r, "v_blinding", vb + 32 * i, 32);
     merlin_rng_finalize(&r, seed);

@@ -65,6 +65,10 @@ def lib():
                                         C.c_char_p, C.POINTER(C.c_uint64)]
         _lib.orc_r1cs_verify.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(Circuit), C.c_char_p, C.c_char_p, C.c_uint64,
                                          C.c_char_p, C.c_uint32]
+        _lib.orc_r1cs_prove_scripted.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(Circuit), C.c_char_p, C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint64,
+                                                 C.c_char_p, C.POINTER(C.c_uint64)]
+        _lib.orc_r1cs_verify_scripted.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(Circuit), C.c_char_p, C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint32,
+                                                  C.c_char_p, C.c_uint64]
         _lib.orc_r1cs_satisfied.argtypes = [C.POINTER(Circuit), C.c_char_p]
         _lib.orc_msm.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_char_p, C.c_int]
         _lib.orc_rng_scalars.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_char_p, C.c_uint64, C.c_char_p]
@@ -235,21 +239,35 @@ def proof_size(n, flags=0):
     return (1 + 11 * 32 if flags & FLAG_COMPACT_1PHASE else 14 * 32) + (2 * lg + 2) * 32
 
 
-def prove(gens, tstate, circ, v_blinding, seed, flags=0):
-    """Returns (rc, proof_bytes, tstate_after)."""
+def _script(script):
+    """None, or a list of 32-byte scalars (or their concatenation) -> (bytes, count)"""
+    script = script if isinstance(script, (bytes, bytearray)) else b"".join(script)
+    assert len(script) % 32 == 0
+    return bytes(script), len(script) // 32
+
+
+def prove(gens, tstate, circ, v_blinding, seed, flags=0, script=None):
+    """Returns (rc, proof_bytes, tstate_after).  script: the challenges y, z, u, x, w, u_1 .. u_lgN that every draw returns in place of the squeezed value."""
     ts = _buf(203); ts.raw = bytes(tstate)
     cap = proof_size(circ.n, flags)
     out = _buf(cap)
     ln = C.c_uint64(cap)
     cs = circ.cstruct()
-    rc = lib().orc_r1cs_prove(gens.h, ts, C.byref(cs), v_blinding, seed, flags, out, C.byref(ln))
+    if script is None:
+        rc = lib().orc_r1cs_prove(gens.h, ts, C.byref(cs), v_blinding, seed, flags, out, C.byref(ln))
+    else:
+        sb, sn = _script(script)
+        rc = lib().orc_r1cs_prove_scripted(gens.h, ts, C.byref(cs), v_blinding, seed, flags, sb, sn, out, C.byref(ln))
     return rc, out.raw[:ln.value], ts.raw
 
 
-def verify(gens, tstate, circ, V, proof, seed=bytes(32), flags=0):
+def verify(gens, tstate, circ, V, proof, seed=bytes(32), flags=0, script=None):
     ts = _buf(203); ts.raw = bytes(tstate)
     cs = circ.cstruct()
-    return lib().orc_r1cs_verify(gens.h, ts, C.byref(cs), V, proof, len(proof), seed, flags)
+    if script is None:
+        return lib().orc_r1cs_verify(gens.h, ts, C.byref(cs), V, proof, len(proof), seed, flags)
+    sb, sn = _script(script)
+    return lib().orc_r1cs_verify_scripted(gens.h, ts, C.byref(cs), V, proof, len(proof), seed, flags, sb, sn)
 
 
 def satisfied(circ, v):
