@@ -558,6 +558,8 @@ class Context:
         n_in = 0 if inputs is None else inputs if isinstance(inputs, int) else (len(inputs) // 32 if isinstance(inputs, (bytes, bytearray)) else len(inputs))
         if n_in:
             iv = None if isinstance(inputs, int) else _scalars32("inputs", inputs, n_in)
+            if iv is None:                                  # no values: the shape alone (a verifier's upload).  The struct must not claim a witness then
+                cs.aL = cs.aR = cs.aO = None
             ch = hints.cstruct() if hints is not None and len(hints) else None
             ck = _checkpoints_cstruct(checkpoints or [])
             _chk(lib().bpg_r1cs_upload_template_inputs(self._h, C.byref(cs), C.byref(cp), C.byref(ch) if ch is not None else None, C.byref(ck),
@@ -798,10 +800,12 @@ def join_layout(dims):
     """[(n, m, q, n_params, n_ck, count)] -> per part a dict of these and the five bases (base_n, base_m, base_q, base_n_params, base_n_ck): where the part's
     first copy starts in the joined multipliers, committed values, constraint rows, parameters and checkpoints (include/bpg.h bpg_r1cs_template_join)"""
     names = ("n", "m", "q", "n_params", "n_ck")
-    base, out = dict.fromkeys(names, 0), []
+    base, out = dict.fromkeys(names + ("n_inputs",), 0), []
     for d in dims:
         part = dict(zip(names + ("count",), (int(x) for x in d)))
-        for k in names:
+        if len(d) > 6:                      # Context.join_inputs: the public inputs of the part's template as well
+            part["n_inputs"] = int(d[6])
+        for k in names + (("n_inputs",) if len(d) > 6 else ()):
             part["base_" + k] = base[k]
             base[k] += part["count"] * part[k]
         out.append(part)
@@ -867,6 +871,115 @@ def test_template_eval_repeat(inst, program, hints, count, values):
     v = _scalars32("values", values, count * inst.m)
     _chk(lib().bpg_test_template_eval_repeat(C.byref(cs), C.byref(cp), C.byref(ch) if ch is not None else None, C.c_uint64(count), v if v else None, *out))
     return tuple(o.raw[:32 * count * inst.n] for o in out)
+
+
+class TestJoinInputsPart(C.Structure):
+    """bpg_test_join_inputs_part: one part of the join test hooks for programs with public inputs."""
+    _fields_ = TestJoinPart._fields_ + [("n_inputs", C.c_uint64)]
+
+
+def _hook_instance_buffers(rows, terms, ncoef, sizes=None):
+    """the four output buffers of an instance hook at the sizes given (sizes = (rows, terms, ncoef) overrides the caller's formulas).  The arrays start as
+    0xff so that a refused call can be shown to have written nothing."""
+    import numpy as np
+    if sizes is not None:
+        rows, terms, ncoef = sizes
+    return (np.full(max(rows, 1), 2**64 - 1, np.uint64), np.full(max(terms, 1), 2**32 - 1, np.uint32), np.full(max(terms, 1), 2**32 - 1, np.uint32),
+            C.create_string_buffer(b"\xff" * (32 * max(ncoef, 1)), 32 * max(ncoef, 1)), rows, terms, ncoef)
+
+
+def test_template_repeat_inputs_instance(inst, program, hints, n_inputs, count, param_values=None, input_values=None, n_slots=0, sizes=None, buffers=None):
+    """bpg_test_template_repeat_inputs_instance (no device): test_template_repeat_instance for a template with n_inputs public inputs, as an assign of
+    param_values and input_values (count x n_inputs scalars, item-major) leaves it.  n_slots: the template's derived slots (the coefficient table holds
+    ncoef + count x (n_params + n_slots) scalars).  sizes = (row_ptr entries, term entries, coef scalars): the capacities to hand over instead of the
+    formulas' own; buffers: a list that receives the four arrays -> (row_ptr, term_var, term_coef, coef bytes)"""
+    cs, cp = inst.cstruct(), program.cstruct()
+    cs.aL = cs.aR = cs.aO = None
+    ch = hints.cstruct() if hints is not None and len(hints) else None
+    npar = len(program.param_rows)
+    row_ptr, tv, tc, coef, rows, terms, ncoef = _hook_instance_buffers(count * inst.q + 1, count * (inst.nnz + npar), inst.ncoef + count * (npar + n_slots), sizes)
+    if buffers is not None:
+        buffers += [row_ptr, tv, tc, coef]
+    nnz, nc = C.c_uint64(), C.c_uint64()
+    pv = None if param_values is None else _scalars32("param_values", param_values, count * npar)
+    iv = None if input_values is None else _scalars32("input_values", input_values, count * n_inputs)
+    _chk(lib().bpg_test_template_repeat_inputs_instance(C.byref(cs), C.byref(cp), C.byref(ch) if ch is not None else None, C.c_uint64(n_inputs), C.c_uint64(count), pv, iv,
+                                                        C.c_void_p(row_ptr.ctypes.data), C.c_uint64(rows), C.c_void_p(tv.ctypes.data), C.c_void_p(tc.ctypes.data),
+                                                        C.c_uint64(terms), coef, C.c_uint64(ncoef), C.byref(nnz), C.byref(nc)))
+    return row_ptr, tv[:nnz.value].copy(), tc[:nnz.value].copy(), coef.raw[:32 * nc.value]
+
+
+def test_template_eval_repeat_inputs(inst, program, hints, checkpoints, n_inputs, count, values, ck_values=None, input_values=None):
+    """bpg_test_template_eval_repeat_inputs (no device): the repeat-layout interpreter compiled for the host for a source with inputs and / or checkpoints
+    (poisoned vectors; segments and items of a level in reverse) -> (a_L, a_R, a_O, first mismatching flat checkpoint index or None)"""
+    cs, cp = inst.cstruct(), program.cstruct()
+    cs.aL = cs.aR = cs.aO = None
+    ch = hints.cstruct() if hints is not None and len(hints) else None
+    cks = list(checkpoints or [])
+    ck = _checkpoints_cstruct(cks) if cks else None
+    out = [_buf(32 * count * inst.n) for _ in range(3)]
+    v = _scalars32("values", values, count * inst.m)
+    ckv = None if ck_values is None else _scalars32("ck_values", ck_values, count * len(cks))
+    iv = None if input_values is None else _scalars32("input_values", input_values, count * n_inputs)
+    first = C.c_uint64()
+    _chk(lib().bpg_test_template_eval_repeat_inputs(C.byref(cs), C.byref(cp), C.byref(ch) if ch is not None else None, C.byref(ck) if ck is not None else None,
+                                                    C.c_uint64(n_inputs), C.c_uint64(count), v if v else None, ckv if ckv else None, iv if iv else None, *out,
+                                                    C.byref(first)))
+    return tuple(o.raw[:32 * count * inst.n] for o in out) + (None if first.value == 2**64 - 1 else int(first.value),)
+
+
+def _test_join_inputs_parts(parts):
+    """[(inst, program, hints, count, checkpoint variables or None, n_inputs)] -> (bpg_test_join_inputs_part array, keep-alive, layout dims with n_inputs last)"""
+    arr, keep, dims = (TestJoinInputsPart * max(len(parts), 1))(), [], []
+    for k, (inst, program, hints, count, cks, n_inputs) in enumerate(parts):
+        cks = list(cks or [])
+        cs, cp = inst.cstruct(), program.cstruct()
+        cs.aL = cs.aR = cs.aO = None
+        ch = hints.cstruct() if hints is not None and len(hints) else None
+        ck = _checkpoints_cstruct(cks) if cks else None
+        keep.append((cs, cp, ch, ck))
+        arr[k].inst, arr[k].program, arr[k].count, arr[k].n_inputs = C.pointer(cs), C.pointer(cp), count, n_inputs
+        if ch is not None:
+            arr[k].hints = C.pointer(ch)
+        if ck is not None:
+            arr[k].checkpoints = C.pointer(ck)
+        dims.append((inst.n, inst.m, inst.q, len(program.param_rows), len(cks), count, n_inputs))
+    return arr, keep, dims
+
+
+def test_template_join_inputs_instance(parts, param_values=None, input_values=None, n_slots=(), sizes=None, buffers=None):
+    """bpg_test_template_join_inputs_instance (no device): test_template_join_instance where parts = [(inst, program, hints, count, checkpoints, n_inputs)]
+    may have public inputs; input_values: the joined inputs, part-major then item-major; n_slots: per part the derived slots of its template.  Buffers of
+    the sizes the formulas give (sizes / buffers as for the repeat hook) -> (row_ptr, term_var, term_coef, coef bytes)"""
+    arr, keep, dims = _test_join_inputs_parts(parts)
+    n_slots = list(n_slots) + [0] * (len(parts) - len(n_slots))
+    rows = sum(d[5] * d[2] for d in dims) + 1
+    terms = sum(part[3] * (part[0].nnz + len(part[1].param_rows)) for part in parts)
+    ncoef = sum(part[0].ncoef + part[3] * (len(part[1].param_rows) + ns) for part, ns in zip(parts, n_slots))
+    npar, nin = sum(d[5] * d[3] for d in dims), sum(d[5] * d[6] for d in dims)
+    row_ptr, tv, tc, coef, rows, terms, ncoef = _hook_instance_buffers(rows, terms, ncoef, sizes)
+    if buffers is not None:
+        buffers += [row_ptr, tv, tc, coef]
+    nnz, nc = C.c_uint64(), C.c_uint64()
+    pv = None if param_values is None else _scalars32("param_values", param_values, npar)
+    iv = None if input_values is None else _scalars32("input_values", input_values, nin)
+    _chk(lib().bpg_test_template_join_inputs_instance(C.c_uint64(len(parts)), arr, pv, iv, C.c_void_p(row_ptr.ctypes.data), C.c_uint64(rows), C.c_void_p(tv.ctypes.data),
+                                                      C.c_void_p(tc.ctypes.data), C.c_uint64(terms), coef, C.c_uint64(ncoef), C.byref(nnz), C.byref(nc)))
+    return row_ptr, tv[:nnz.value].copy(), tc[:nnz.value].copy(), coef.raw[:32 * nc.value]
+
+
+def test_template_eval_join_inputs(parts, values, ck_values=None, input_values=None):
+    """bpg_test_template_eval_join_inputs (no device): test_template_eval_join where parts (as for test_template_join_inputs_instance) may have public inputs
+    -> (a_L, a_R, a_O, first mismatching flat checkpoint index or None)"""
+    arr, keep, dims = _test_join_inputs_parts(parts)
+    n, m, nck, nin = (sum(d[5] * d[i] for d in dims) for i in (0, 1, 4, 6))
+    out = [_buf(32 * n) for _ in range(3)]
+    v = _scalars32("values", values, m)
+    ck = None if ck_values is None else _scalars32("ck_values", ck_values, nck)
+    iv = None if input_values is None else _scalars32("input_values", input_values, nin)
+    first = C.c_uint64()
+    _chk(lib().bpg_test_template_eval_join_inputs(C.c_uint64(len(parts)), arr, v if v else None, ck if ck else None, iv if iv else None, *out, C.byref(first)))
+    return tuple(o.raw[:32 * n] for o in out) + (None if first.value == 2**64 - 1 else int(first.value),)
 
 
 class VerifyItem(C.Structure):
@@ -956,6 +1069,28 @@ def _context_join(self, parts):
 
 
 Context.join = _context_join
+
+
+def _context_join_inputs(self, parts):
+    """bpg_r1cs_template_join_inputs: Context.join where any part may be a template with public inputs.  .layout also carries n_inputs and base_n_inputs per
+    part; assign(values, params, checkpoints=, inputs=) takes the concatenated lists, part-major then item-major.  Without inputs in any part it is join()."""
+    parts = [(t, int(c)) for t, c in parts]
+    arr = (TemplatePart * max(len(parts), 1))()
+    for k, (t, c) in enumerate(parts):
+        if c < 0 or c >= 2**64:
+            raise ValueError("count out of range")
+        arr[k].tmpl, arr[k].count = (t._h if t is not None else None), c
+    h = C.c_void_p()
+    _chk(lib().bpg_r1cs_template_join_inputs(self._h, C.c_uint64(len(parts)), arr, C.byref(h)))
+    layout = join_layout([(t.n, t.m, t.q or 0, t.n_params, t.n_ck, c, t.n_inputs) for t, c in parts])
+    tot = lambda k: sum(p["count"] * p[k] for p in layout)
+    res = ResidentCircuit(self, h, tot("n"), tot("m"), n_params=tot("n_params"), q=None if any(t.q is None for t, _ in parts) else tot("q"), n_ck=tot("n_ck"),
+                          n_inputs=tot("n_inputs"))
+    res.layout = layout
+    return res
+
+
+Context.join_inputs = _context_join_inputs
 
 
 def verify_batch(ctx, verifiers, proofs, bp_gens, seeds=None, flags=0, batch_seed=None):
@@ -1122,6 +1257,8 @@ class ResidentCircuit:
                 e = BpgError(st, lib().bpg_last_error().decode())
                 if st == ERR_CHECKPOINT_MISMATCH:
                     e.first_mismatch = int(first.value)
+                    if self.layout is not None:             # a join: (part, item, checkpoint of the part's template); the message names them too
+                        e.place = _join_place(self.layout, e.first_mismatch, "n_ck")
                 raise e
             return
         if checkpoints is not None:
@@ -1150,6 +1287,44 @@ class ResidentCircuit:
         _chk(lib().bpg_r1cs_template_repeat(self.ctx._h, self._h, C.c_uint64(count), C.byref(h)))
         return ResidentCircuit(self.ctx, h, count * self.n, count * self.m, n_params=count * self.n_params, q=None if self.q is None else count * self.q,
                                n_ck=count * self.n_ck)
+
+    def repeat_inputs(self, count) -> "ResidentCircuit":
+        """bpg_r1cs_template_repeat_inputs: repeat() for a template with public inputs - `count` statements against `count` different public values as ONE
+        proof.  assign(values, params, checkpoints=, inputs=) then takes count x n_inputs inputs as well, item-major.  Without inputs it is repeat()."""
+        h = C.c_void_p()
+        _chk(lib().bpg_r1cs_template_repeat_inputs(self.ctx._h, self._h, C.c_uint64(count), C.byref(h)))
+        return ResidentCircuit(self.ctx, h, count * self.n, count * self.m, n_params=count * self.n_params, q=None if self.q is None else count * self.q,
+                               n_ck=count * self.n_ck, n_inputs=count * self.n_inputs)
+
+    def set_inputs(self, inputs):
+        """bpg_r1cs_set_inputs: the verifier's half of assign(inputs=) - the public inputs go up and the derived coefficient slots are filled, nothing else.
+        The circuit is left without a witness; verify() then checks against these inputs."""
+        iv = bytes(inputs) if isinstance(inputs, (bytes, bytearray)) else b"".join(_exact("inputs", x, 32) for x in inputs)
+        if len(iv) % 32:
+            raise ValueError("inputs must be a multiple of 32 bytes")
+        _chk(lib().bpg_r1cs_set_inputs(self.ctx._h, self._h, C.c_uint64(len(iv) // 32), iv if iv else None))
+
+    def check_batch_inputs(self, items, max_rows=16):
+        """check_batch for a template with public inputs: items = [(values, params, inputs)] -> per item the violated rows OF THE TEMPLATE.  Composition of
+        repeat_inputs(), assign(inputs=) and ONE check() per chunk; this template's own witness and inputs are left alone."""
+        if self.q is None:
+            raise ValueError("check_batch_inputs needs the template's row count (a circuit from Context.upload_template or Prover.template)")
+        out = []
+        per = max(1, self.CHECK_BATCH_ROWS // max(self.q, 1))
+        join = lambda x: bytes(x) if isinstance(x, (bytes, bytearray)) else b"".join(bytes(y) for y in x)
+        for first in range(0, len(items), per):
+            chunk = items[first:first + per]
+            rep = self.repeat_inputs(len(chunk))
+            try:
+                rep.assign(b"".join(join(v) for v, _, _ in chunk), b"".join(join(p) for _, p, _ in chunk), inputs=b"".join(join(i) for _, _, i in chunk))
+                found = [[] for _ in chunk]
+                for k, r in rep.check(None, len(chunk) * self.q).items(self.q):
+                    if len(found[k]) < max_rows:
+                        found[k].append(r)
+                out += found
+            finally:
+                rep.free()
+        return out
 
     def check(self, values=None, max_rows=16) -> "CheckReport":
         """bpg_r1cs_check: which multipliers (a_L * a_R against a_O) and which constraint rows does the resident witness break - evaluated on the device, the

@@ -559,21 +559,35 @@ bpg_status bpg_test_circuit_handle_hinted(const bpg_r1cs_instance *inst, const b
         *out = c;
     });
 }
-bpg_status bpg_r1cs_template_repeat(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, bpg_circuit **out) {
+// bpg_r1cs_template_repeat and bpg_r1cs_template_repeat_inputs: the second serves a source with public inputs, the first refuses it
+static bpg_status template_repeat(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, bpg_circuit **out, bool with_inputs) {
     return guard([&] {
         REQUIRE(out); *out = nullptr;
         REQUIRE(ctx && tmpl);
         if (count == 0) throw std::invalid_argument("template_repeat: count must be at least 1");
         if (!tmpl->is_template) throw std::invalid_argument("template_repeat: the circuit is not a template (bpg_r1cs_upload_template)");
-        if (tmpl->n_in) throw std::invalid_argument("template_repeat: the template has public inputs (a repeat carries none: prove its items in a batch, bpg_r1cs_prove_template_batch_inputs)");
+        if (tmpl->n_in && !with_inputs) throw std::invalid_argument("template_repeat: the template has public inputs (a repeat carries none: prove its items in a batch, bpg_r1cs_prove_template_batch_inputs)");
         if (!tmpl->dc) throw std::invalid_argument("template_repeat: the handle has no device state (bpg_test_circuit_handle)");
         if (Engine::is_join(tmpl->dc)) throw std::invalid_argument("template_repeat: the circuit is a join (join its parts with larger counts instead)");
-        DeviceCircuit *dc = ctx->engine->repeat_template(tmpl->dc, count);          // count 0, a repeat, sizes: refused there, before any device work
+        DeviceCircuit *dc = ctx->engine->repeat_template(tmpl->dc, count, with_inputs);          // count 0, a repeat, sizes: refused there, before any device work
         bpg_circuit *c = new bpg_circuit{dc, count * tmpl->n, count * tmpl->m}; c->is_template = true; c->n_params = count * tmpl->n_params; c->n_ck = count * tmpl->n_ck;
+        c->n_in = count * tmpl->n_in;
         *out = c;
     });
 }
-bpg_status bpg_r1cs_template_join(bpg_ctx *ctx, uint64_t n_parts, const bpg_template_part *parts, bpg_circuit **out) {
+bpg_status bpg_r1cs_template_repeat(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, bpg_circuit **out) { return template_repeat(ctx, tmpl, count, out, false); }
+bpg_status bpg_r1cs_template_repeat_inputs(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, bpg_circuit **out) { return template_repeat(ctx, tmpl, count, out, true); }
+bpg_status bpg_r1cs_set_inputs(bpg_ctx *ctx, bpg_circuit *c, uint64_t n_inputs, const uint8_t *input_values) {
+    return guard([&] {
+        REQUIRE(ctx && c);
+        if (!c->is_template || !c->n_in) throw std::invalid_argument("set_inputs: the circuit is not a template with public inputs (bpg_r1cs_upload_template_inputs)");
+        if (n_inputs != c->n_in) throw std::invalid_argument("set_inputs: n_inputs does not match the template (" + std::to_string(c->n_in) + " public inputs)");
+        if (!input_values) throw std::invalid_argument("set_inputs: the template has " + std::to_string(n_inputs) + " public inputs and input_values is null");
+        if (!c->dc) throw std::invalid_argument("set_inputs: the handle has no device state (bpg_test_circuit_handle)");
+        ctx->engine->set_inputs(c->dc, input_values);
+    });
+}
+static bpg_status template_join(bpg_ctx *ctx, uint64_t n_parts, const bpg_template_part *parts, bpg_circuit **out, bool with_inputs) {
     return guard([&] {
         REQUIRE(out); *out = nullptr;
         REQUIRE(ctx && parts);
@@ -586,19 +600,22 @@ bpg_status bpg_r1cs_template_join(bpg_ctx *ctx, uint64_t n_parts, const bpg_temp
             if (!t) throw std::invalid_argument(at + "null template");
             if (parts[p].count == 0) throw std::invalid_argument(at + "count must be at least 1");
             if (!t->is_template) throw std::invalid_argument(at + "the circuit is not a template (bpg_r1cs_upload_template)");
-            if (t->n_in) throw std::invalid_argument(at + "the template has public inputs (a join carries none)");
+            if (t->n_in && !with_inputs) throw std::invalid_argument(at + "the template has public inputs (a join carries none)");
             if (!t->dc) throw std::invalid_argument(at + "the handle has no device state (bpg_test_circuit_handle)");
             src.emplace_back(t->dc, parts[p].count);
         }
-        DeviceCircuit *dc = ctx->engine->join_templates(src);                       // a repeat, a join, another device, sizes: refused there, before any device work
+        DeviceCircuit *dc = ctx->engine->join_templates(src, with_inputs);          // a repeat, a join, another device, sizes: refused there, before any device work
         bpg_circuit *c = new bpg_circuit{dc, 0, 0}; c->is_template = true;
         for (uint64_t p = 0; p < n_parts; p++) {
             const bpg_circuit *t = parts[p].tmpl;
             c->n += parts[p].count * t->n; c->m += parts[p].count * t->m; c->n_params += parts[p].count * t->n_params; c->n_ck += parts[p].count * t->n_ck;
+            c->n_in += parts[p].count * t->n_in;
         }
         *out = c;
     });
 }
+bpg_status bpg_r1cs_template_join(bpg_ctx *ctx, uint64_t n_parts, const bpg_template_part *parts, bpg_circuit **out) { return template_join(ctx, n_parts, parts, out, false); }
+bpg_status bpg_r1cs_template_join_inputs(bpg_ctx *ctx, uint64_t n_parts, const bpg_template_part *parts, bpg_circuit **out) { return template_join(ctx, n_parts, parts, out, true); }
 static std::vector<Engine::JoinSource> join_sources(uint64_t n_parts, const bpg_test_join_part *parts) {
     if (n_parts == 0) throw std::invalid_argument("template_join: no parts (n_parts must be at least 1)");
     if (n_parts > 256) throw std::invalid_argument("template_join: too many parts (" + std::to_string(n_parts) + "; at most 256)");
@@ -634,6 +651,67 @@ bpg_status bpg_test_template_eval_join(uint64_t n_parts, const bpg_test_join_par
         for (const Engine::JoinSource &s : src) m += s.c.m;
         REQUIRE(m == 0 || v);
         *first_mismatch = Engine::template_eval_join_host(src, v, ck_values, aL, aR, aO);
+    });
+}
+static std::vector<Engine::JoinSource> join_sources_inputs(uint64_t n_parts, const bpg_test_join_inputs_part *parts) {
+    if (n_parts == 0) throw std::invalid_argument("template_join: no parts (n_parts must be at least 1)");
+    if (n_parts > 256) throw std::invalid_argument("template_join: too many parts (" + std::to_string(n_parts) + "; at most 256)");
+    std::vector<Engine::JoinSource> src;
+    for (uint64_t p = 0; p < n_parts; p++) {
+        if (!parts[p].inst || !parts[p].program) throw std::invalid_argument("template_join: part " + std::to_string(p) + ": null instance or program");
+        src.push_back({as_view(parts[p].inst, false, true), program_view_inputs(parts[p].program, parts[p].hints, parts[p].checkpoints, parts[p].n_inputs), parts[p].count});
+    }
+    return src;
+}
+// the outputs of an instance hook, after its sizes were checked against the caller's capacities
+static void instance_out(const FlatCircuit &f, uint64_t *row_ptr, uint32_t *term_var, uint32_t *term_coef, uint8_t *coef, uint64_t *nnz_out, uint64_t *ncoef_out) {
+    const uint64_t nnz = f.term_var.size(), ncoef = f.coef.size() / 32;
+    std::memcpy(row_ptr, f.row_ptr.data(), f.row_ptr.size() * 8);
+    if (nnz) { std::memcpy(term_var, f.term_var.data(), nnz * 4); std::memcpy(term_coef, f.term_coef.data(), nnz * 4); }
+    if (ncoef) std::memcpy(coef, f.coef.data(), ncoef * 32);
+    *nnz_out = nnz; *ncoef_out = ncoef;
+}
+bpg_status bpg_test_template_join_inputs_instance(uint64_t n_parts, const bpg_test_join_inputs_part *parts, const uint8_t *param_values, const uint8_t *input_values,
+                                                  uint64_t *row_ptr, uint64_t row_cap, uint32_t *term_var, uint32_t *term_coef, uint64_t term_cap, uint8_t *coef,
+                                                  uint64_t coef_cap, uint64_t *nnz_out, uint64_t *ncoef_out) {
+    return guard([&] {
+        REQUIRE(parts && row_ptr && nnz_out && ncoef_out);
+        const uint64_t caps[3] = {row_cap, (term_var && term_coef) ? term_cap : 0, coef ? coef_cap : 0};       // every size is known before a row is made: refused, nothing written
+        const FlatCircuit f = Engine::template_join_instance_host(join_sources_inputs(n_parts, parts), param_values, input_values, caps);
+        instance_out(f, row_ptr, term_var, term_coef, coef, nnz_out, ncoef_out);
+    });
+}
+bpg_status bpg_test_template_eval_join_inputs(uint64_t n_parts, const bpg_test_join_inputs_part *parts, const uint8_t *v, const uint8_t *ck_values,
+                                              const uint8_t *input_values, uint8_t *aL, uint8_t *aR, uint8_t *aO, uint64_t *first_mismatch) {
+    return guard([&] {
+        REQUIRE(parts && aL && aR && aO && first_mismatch);
+        const std::vector<Engine::JoinSource> src = join_sources_inputs(n_parts, parts);
+        uint64_t m = 0;
+        for (const Engine::JoinSource &s : src) m += s.c.m;
+        REQUIRE(m == 0 || v);
+        *first_mismatch = Engine::template_eval_join_host(src, v, ck_values, aL, aR, aO, input_values);
+    });
+}
+bpg_status bpg_test_template_repeat_inputs_instance(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, uint64_t n_inputs,
+                                                    uint64_t count, const uint8_t *param_values, const uint8_t *input_values, uint64_t *row_ptr, uint64_t row_cap,
+                                                    uint32_t *term_var, uint32_t *term_coef, uint64_t term_cap, uint8_t *coef, uint64_t coef_cap, uint64_t *nnz_out,
+                                                    uint64_t *ncoef_out) {
+    return guard([&] {
+        REQUIRE(inst && program && row_ptr && nnz_out && ncoef_out);
+        const uint64_t caps[3] = {row_cap, (term_var && term_coef) ? term_cap : 0, coef ? coef_cap : 0};
+        const FlatCircuit f = Engine::template_repeat_inputs_instance_host(as_view(inst, false, true), program_view_inputs(program, hints, nullptr, n_inputs), count, param_values,
+                                                                           input_values, caps);
+        instance_out(f, row_ptr, term_var, term_coef, coef, nnz_out, ncoef_out);
+    });
+}
+bpg_status bpg_test_template_eval_repeat_inputs(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                                const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, uint64_t count, const uint8_t *v, const uint8_t *ck_values,
+                                                const uint8_t *input_values, uint8_t *aL, uint8_t *aR, uint8_t *aO, uint64_t *first_mismatch) {
+    return guard([&] {
+        REQUIRE(inst && program && aL && aR && aO && first_mismatch && (inst->m == 0 || count == 0 || v));
+        REQUIRE(!checkpoints || checkpoints->n_checkpoints == 0 || count == 0 || ck_values);
+        *first_mismatch = Engine::template_eval_repeat_inputs_host(as_view(inst, false, true), program_view_inputs(program, hints, checkpoints, n_inputs), count, v, ck_values,
+                                                                   input_values, aL, aR, aO);
     });
 }
 bpg_status bpg_r1cs_check(bpg_ctx *ctx, bpg_circuit *c, uint64_t m, const uint8_t *v, uint64_t cap, uint64_t *rows_out, uint64_t *n_rows_out, bpg_check_report *report) {

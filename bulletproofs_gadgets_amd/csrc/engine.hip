@@ -170,7 +170,11 @@ struct DeviceCircuit {
     DevBuf wit_ck_var, wit_ck;
     // public inputs (WitnessProgramView::n_inputs): the values of the last assign_inputs, and the derived coefficient slots [slot_first, slot_first + n_slots) of
     // `coef` with the (input, coefficient index) pair of each (host/template.hpp InputSlot), which k_input_slots reads
+    // A repeat or join WITH inputs (repeat_template / join_templates, with_inputs): n_in and n_slots are the totals over all items, in_slots the sources' pair lists
+    // one after the other, and k_input_slots_join fills the slots from slot_parts descriptors in join_desc (a repeat: one, made for this kernel alone; 0: a
+    // single template, k_input_slots).  The derived slots are STICKY state of the circuit: they stand as the last assign_inputs or set_inputs left them.
     uint64_t n_in = 0, slot_first = 0, n_slots = 0;
+    uint32_t slot_parts = 0;
     DevBuf wit_in, in_slots;
     bool wit_v_set = false;                 // wit_v holds the values of an assign() (a template uploaded WITH its witness has a_L, a_R, a_O and no values yet)
     std::vector<uint32_t> wit_level_ptr;    // level l = segments [wit_level_ptr[l], wit_level_ptr[l + 1]) of wit_segs
@@ -182,7 +186,7 @@ struct DeviceCircuit {
     FlatView host_view;
     // a template repeated on the device (repeat_template, hip/k_repeat.cuh): rep_count copies of a source template of rep_n multipliers and rep_m committed
     // values, whose packed program (wit_stream, wit_segs, wit_level_ptr: copies of the source's) assign() walks once per (segment, item).  0: not a repeat.
-    uint64_t rep_count = 0, rep_n = 0, rep_m = 0;
+    uint64_t rep_count = 0, rep_n = 0, rep_m = 0, rep_in = 0;       // rep_in: the public inputs of ONE item (n_in = rep_count x rep_in)
     // templates joined on the device (join_templates, hip/k_join.cuh): the descriptors of the parts (host copy and device array), the parts' programs one after
     // the other in wit_stream / wit_segs / wit_ck_var, and the block table of assign(): level l = blocks [join_level_ptr[l], join_level_ptr[l + 1]) of join_blocks.
     // n_ck is the total over all parts and items.  No part: not a join.
@@ -206,7 +210,7 @@ struct DeviceCircuit {
     X(k_tt_bases) X(k_tt_multiples) X(k_tt_bases8) X(k_tt_multiples8) X(k_tt_round8) X(k_tt_factors) X(k_tt_advance) X(k_tt_round) X(k_tt_finish) X(k_blind_expand) X(k_tt_commit3) X(k_tt_commit3_finish) X(k_csc_count) X(k_csc_fill) X(k_csc_colptr) X(k_merge_insert) X(k_merge_plan) X(k_merge_groups) X(k_merge_members) X(k_merge_sum) \
     X(k_bt_commit3) X(k_bt_commit3_finish) X(k_bt_compress) X(k_bt_exp) X(k_bt_poly_t) X(k_bt_poly_eval) X(k_bt_factors) X(k_bt_advance) X(k_bt_round) \
     X(k_bt_finish) X(k_bt_fold_scalars) X(k_witness_eval) X(k_witness_eval_batch) X(k_bt_commit_v) X(k_repeat_colptr) X(k_repeat_entries) X(k_repeat_coef) X(k_witness_eval_repeat) X(k_witness_ck_verify) X(k_witness_ck_verify_batch) \
-    X(k_join_colptr) X(k_join_entries) X(k_join_coef) X(k_witness_eval_join) X(k_witness_ck_verify_join) X(k_input_slots) \
+    X(k_join_colptr) X(k_join_entries) X(k_join_coef) X(k_witness_eval_join) X(k_witness_ck_verify_join) X(k_input_slots) X(k_input_slots_join) \
     X(k_mimc_sponge) X(k_merkle_leaves) X(k_merkle_level) X(k_merkle_top) X(k_merkle_level_list) X(k_merkle_set_leaves) X(k_merkle_paths) X(k_merkle_export) \
     X(k_rowview_count) X(k_rowview_fill) X(k_rowview_long) X(k_check_mul) X(k_check_rows) X(k_check_rows_long) X(k_check_count)
 enum KernelId {
@@ -261,6 +265,7 @@ struct Engine::Impl {
     DevBuf ck_first;                            // assign_checkpointed: the lowest mismatching checkpoint (8 bytes)
     uint32_t check_threshold = CHECK_ROW_THRESHOLD;     // rows of more terms get a wave each (BPG_CHECK_THRESHOLD)
     void rowview_build(DeviceCircuit *c);
+    void fill_input_slots(DeviceCircuit *c);    // assign_inputs, set_inputs: the derived coefficient slots from the resident inputs, one launch
     // One arena for the large per-stream buffers whose lifetimes never overlap in stream order (round 5: 20 proving streams held 2.9 GB each):
     //   an MSM:        [digits | entries1] (dead once k_msm_sort2 has run) overlaid by the sweep's partial sums (slots); entries behind them
     //   poly phase:    flattened weights, powers of z and y (between the S sums and the first round of the inner-product argument)
@@ -1597,13 +1602,12 @@ uint64_t Engine::assign_inputs(DeviceCircuit *d, const uint8_t *v, const uint8_t
     const scm *ck = total_ck ? d->wit_ck.as<scm>() : nullptr;
     const scm *in = d->n_in ? d->wit_in.as<scm>() : nullptr;
     // the derived slots of the rows, before anything reads a constant term: coef[ci] * x_p, a lane per slot
-    if (d->n_slots) BPG_LAUNCH(I, k_input_slots, dim3(cdiv(d->n_slots, 256)), dim3(256), d->in_slots.as<uint2>(), (uint32_t)d->n_slots, (uint32_t)d->slot_first, 0u,
-                               (uint32_t)d->n_in, (uint64_t)d->n_slots, in, d->coef.as<scm>());
+    I.fill_input_slots(d);
     // a join: ONE launch per level for all its parts (levels 0 .. the most any part has), that level's rows of the block table
     for (size_t l = 0; l + 1 < d->join_level_ptr.size(); l++) {
         const uint32_t b0 = d->join_level_ptr[l], nb = d->join_level_ptr[l + 1] - b0;
         BPG_LAUNCH(I, k_witness_eval_join, dim3(nb), dim3(64), d->join_blocks.as<uint4>() + b0, d->join_desc.as<JoinPart>(), d->wit_segs.as<uint4>(),
-                   d->wit_stream.as<uint32_t>(), d->coef.as<scm>(), d->wit_v.as<scm>(), ck, d->aL.as<scm>(), d->aR.as<scm>(), d->aO.as<scm>());
+                   d->wit_stream.as<uint32_t>(), d->coef.as<scm>(), d->wit_v.as<scm>(), ck, in, d->aL.as<scm>(), d->aR.as<scm>(), d->aO.as<scm>());
     }
     // a level's lanes are few (a 512-leaf tree: at most 256): spread them over waves until every SIMD of the device has one
     for (size_t l = 0; l + 1 < d->wit_level_ptr.size(); l++) {
@@ -1612,7 +1616,8 @@ uint64_t Engine::assign_inputs(DeviceCircuit *d, const uint8_t *v, const uint8_t
             const uint32_t K = (uint32_t)d->rep_count;
             const uint32_t bps = cdiv(K, 64);                                       // 64 consecutive items of a segment per block, as k_witness_eval_batch has them
             BPG_LAUNCH(I, k_witness_eval_repeat, dim3(ns * bps), dim3(64), d->wit_segs.as<uint4>() + s0, ns, bps, d->wit_stream.as<uint32_t>(), d->coef.as<scm>(),
-                       d->wit_v.as<scm>(), ck, (uint32_t)d->n_ck, (uint32_t)d->rep_n, (uint32_t)d->rep_m, K, d->aL.as<scm>(), d->aR.as<scm>(), d->aO.as<scm>());
+                       d->wit_v.as<scm>(), ck, (uint32_t)d->n_ck, in, (uint32_t)d->rep_in, (uint32_t)d->rep_n, (uint32_t)d->rep_m, K, d->aL.as<scm>(), d->aR.as<scm>(),
+                       d->aO.as<scm>());
             continue;
         }
         const uint32_t lanes = std::min(64u, std::max(1u, cdiv(ns, I.wit_waves)));
@@ -1638,6 +1643,32 @@ uint64_t Engine::assign_inputs(DeviceCircuit *d, const uint8_t *v, const uint8_t
     if (first != CHECKPOINTS_HOLD) return first;    // an inconsistent witness is never provable: the circuit stays without one (drop_witness above)
     d->has_witness = true; d->wit_v_set = true;
     return first;
+}
+// the derived slots from the inputs in wit_in, queued on the stream: one launch, whichever kind of template (a single one: k_input_slots; a repeat or join:
+// k_input_slots_join over its descriptors)
+void Engine::Impl::fill_input_slots(DeviceCircuit *d) {
+    if (!d->n_slots) return;
+    if (d->slot_parts)
+        BPG_LAUNCH((*this), k_input_slots_join, dim3(cdiv(d->n_slots, 256)), dim3(256), d->join_desc.as<JoinPart>(), d->slot_parts, (uint64_t)d->n_slots,
+                   d->in_slots.as<uint32_t>(), d->wit_in.as<scm>(), d->coef.as<scm>());
+    else
+        BPG_LAUNCH((*this), k_input_slots, dim3(cdiv(d->n_slots, 256)), dim3(256), d->in_slots.as<uint2>(), (uint32_t)d->n_slots, (uint32_t)d->slot_first, 0u,
+                   (uint32_t)d->n_in, (uint64_t)d->n_slots, d->wit_in.as<scm>(), d->coef.as<scm>());
+}
+// The verifier's half of assign_inputs (include/bpg.h bpg_r1cs_set_inputs): the inputs go up and into Montgomery form, the derived slots are filled, nothing else
+// happens.  The circuit is left WITHOUT a witness: whatever a_L, a_R, a_O hold was computed under other inputs.
+void Engine::set_inputs(DeviceCircuit *d, const uint8_t *input_values) {
+    if (!d || !d->is_template || !d->n_in) throw std::invalid_argument("set_inputs: the circuit is not a template with public inputs (bpg_r1cs_upload_template_inputs)");
+    if (!input_values) throw std::invalid_argument("set_inputs: the template has public inputs and no values were given for them");
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    drop_witness(d);
+    I.small_sc.ensure((d->n_in + 1) * 32);
+    I.h2d(I.small_sc.p, input_values, d->n_in * 32);
+    BPG_LAUNCH(I, k_sc_from_bytes, dim3(cdiv(d->n_in, 256)), dim3(256), I.small_sc.as<uint32_t>(), d->wit_in.as<scm>(), (uint32_t)d->n_in);
+    I.fill_input_slots(d);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(I.st));
 }
 // ------------------------------------------------------------------------------------------------ R1CS check on the device (hip/k_check.cuh, host/check.hpp)
 // The row-major view of a resident matrix, from its column-major form: entries per row, an exclusive scan, (column, coefficient slot) pairs per row, and the
@@ -1718,7 +1749,7 @@ CheckReport Engine::check(DeviceCircuit *c, const uint8_t *v, uint64_t cap, uint
 // ------------------------------------------------------------------------------------------------ a template repeated on the device (hip/k_repeat.cuh)
 namespace {
 // what the instance format and the device layout hold (check_instance, the 29-bit variable index, 32-bit entry and row indices, the packer's slot index)
-void check_repeat_sizes(uint64_t count, uint64_t n, uint64_t m, uint64_t q, uint64_t nnz, uint64_t shared_coef, uint64_t n_params) {
+void check_repeat_sizes(uint64_t count, uint64_t n, uint64_t m, uint64_t q, uint64_t nnz, uint64_t shared_coef, uint64_t n_params, uint64_t n_slots = 0, uint64_t n_in = 0) {
     if (count == 0) throw std::invalid_argument("template_repeat: count must be at least 1");
     auto over = [&](uint64_t a, uint64_t limit) { return a && count > (limit - 1) / a; };       // count * a >= limit
     if (over(n, 1ull << 27)) throw std::invalid_argument("template_repeat: count x n multipliers are too many (below 2^27)");
@@ -1728,20 +1759,26 @@ void check_repeat_sizes(uint64_t count, uint64_t n, uint64_t m, uint64_t q, uint
     if (over(3 * n + m, (1ull << 32) - 1)) throw std::invalid_argument("template_repeat: the repeated circuit has too many columns");
     if (over(n_params, (uint64_t)WIT_COEF_INDEX_MASK + 1 - std::min<uint64_t>(shared_coef, WIT_COEF_INDEX_MASK)))
         throw std::invalid_argument("template_repeat: count x n_params coefficient slots are too many");
+    // a source with public inputs: shared + count (n_params + n_slots) coefficient indices below 2^30, count n_inputs below the 29-bit variable index
+    if (n_slots && over(n_params + n_slots, (uint64_t)WIT_COEF_INDEX_MASK + 1 - std::min<uint64_t>(shared_coef, WIT_COEF_INDEX_MASK)))
+        throw std::invalid_argument("template_repeat: count x (n_params + n_slots) coefficient slots are too many (shared + count x (" + std::to_string(n_params) + " + " +
+                                    std::to_string(n_slots) + ") must stay below 2^30)");
+    if (over(n_in, 1ull << 29)) throw std::invalid_argument("template_repeat: count x n_inputs public inputs exceed the 29-bit variable index");
 }
 }  // namespace
 
-DeviceCircuit *Engine::repeat_template(DeviceCircuit *src, uint64_t count) {
+DeviceCircuit *Engine::repeat_template(DeviceCircuit *src, uint64_t count, bool with_inputs) {
     // every refusal first: nothing below this block runs for a refused call
     if (!src) throw std::invalid_argument("template_repeat: no circuit");
     if (!src->is_template) throw std::invalid_argument("template_repeat: the circuit is not a template (bpg_r1cs_upload_template)");
     if (src->rep_count) throw std::invalid_argument("template_repeat: the circuit is itself a repeat (repeat the template it was made from)");
-    if (src->n_in) throw std::invalid_argument("template_repeat: the template has public inputs (a repeat carries none: prove its items in a batch, bpg_r1cs_prove_template_batch_inputs)");
-    check_repeat_sizes(count, src->n, src->m, src->q, src->nnz, src->param_first, src->n_params);
+    if (src->n_in && !with_inputs) throw std::invalid_argument("template_repeat: the template has public inputs (a repeat carries none: prove its items in a batch, bpg_r1cs_prove_template_batch_inputs)");
+    check_repeat_sizes(count, src->n, src->m, src->q, src->nnz, src->param_first, src->n_params, src->n_slots, src->n_in);
     HIPCHK(hipSetDevice(device_));
     Impl &I = *impl_;
-    const uint64_t K = count, n = K * src->n, m = K * src->m, q = K * src->q, nnz = K * src->nnz, ncols = 3 * n + m + 1, ncoef = src->param_first + K * src->n_params;
-    const RepeatDims D{(uint32_t)src->n, (uint32_t)src->m, (uint32_t)src->q, (uint32_t)src->param_first, (uint32_t)src->n_params};
+    const uint64_t K = count, n = K * src->n, m = K * src->m, q = K * src->q, nnz = K * src->nnz, ncols = 3 * n + m + 1;
+    const uint64_t ncoef = src->param_first + K * (src->n_params + src->n_slots);
+    const RepeatDims D{(uint32_t)src->n, (uint32_t)src->m, (uint32_t)src->q, (uint32_t)src->param_first, (uint32_t)src->n_params, (uint32_t)src->n_slots, (uint32_t)K};
     std::unique_ptr<DeviceCircuit> d(new DeviceCircuit());
     d->n = n; d->m = m; d->q = q; d->ncols = ncols; d->nnz = nnz; d->const_begin = K * src->const_begin; d->has_witness = false;
     d->is_template = true; d->n_params = K * src->n_params; d->param_first = src->param_first; d->wit_level_ptr = src->wit_level_ptr;
@@ -1756,6 +1793,19 @@ DeviceCircuit *Engine::repeat_template(DeviceCircuit *src, uint64_t count) {
         d->wit_ck_var.ensure(d->n_ck * 4); d->wit_ck.ensure(K * d->n_ck * sizeof(scm));
         HIPCHK(hipMemcpyAsync(d->wit_ck_var.p, src->wit_ck_var.p, d->n_ck * 4, hipMemcpyDeviceToDevice, I.st));
     }
+    if (src->n_in) {                                // the source's inputs, per item: K n_in values and K n_slots derived slots, item-major, behind all parameter slots
+        d->rep_in = src->n_in; d->n_in = K * src->n_in; d->n_slots = K * src->n_slots; d->slot_first = src->param_first + K * src->n_params;
+        d->wit_in.ensure(d->n_in * sizeof(scm)); d->in_slots.ensure((src->n_slots ? src->n_slots : 1) * sizeof(InputSlot));
+        if (src->n_slots) {                         // its own copy of the (input, coefficient index) pairs, and the one descriptor k_input_slots_join walks
+            HIPCHK(hipMemcpyAsync(d->in_slots.p, src->in_slots.p, src->n_slots * sizeof(InputSlot), hipMemcpyDeviceToDevice, I.st));
+            JoinPart P;
+            std::memset(&P, 0, sizeof P);
+            P.count = (uint32_t)K; P.n_in = (uint32_t)src->n_in; P.n_slots = (uint32_t)src->n_slots; P.base_dslot = (uint32_t)d->slot_first;
+            d->join_desc.ensure(sizeof P);
+            I.h2d(d->join_desc.p, &P, sizeof P);
+            d->slot_parts = 1;
+        }
+    }
     const uint32_t gy = (uint32_t)std::min<uint64_t>(K, 1024);           // copies beyond the grid's y extent are a loop in the kernels
     BPG_LAUNCH(I, k_repeat_colptr, dim3(cdiv(3 * src->n + src->m + 1, 256), gy), dim3(256), src->col_ptr.as<uint64_t>(), D, (uint32_t)K, d->col_ptr.as<uint64_t>());
     if (src->nnz) BPG_LAUNCH(I, k_repeat_entries, dim3(cdiv(src->nnz, 256), gy), dim3(256), src->col_ptr.as<uint64_t>(), src->ent_row.as<uint32_t>(),
@@ -1768,11 +1818,18 @@ DeviceCircuit *Engine::repeat_template(DeviceCircuit *src, uint64_t count) {
 
 namespace {
 // the rows of the repeat from the template's rows with their parameter slots: what k_repeat_* leave in HBM, row-major
-FlatCircuit repeat_rows(const TemplatePlan &T, uint64_t count) {
+FlatCircuit repeat_rows(const TemplatePlan &T, uint64_t count, const uint64_t *caps = nullptr) {
     const FlatCircuit &s = T.slotted;
     const uint64_t q = s.row_ptr.size() - 1, nnz = s.term_var.size();
-    check_repeat_sizes(count, s.n, s.m, q, nnz, T.param_first, T.n_params);
-    const RepeatDims D{(uint32_t)s.n, (uint32_t)s.m, (uint32_t)q, (uint32_t)T.param_first, (uint32_t)T.n_params};
+    const uint64_t n_slots = T.in_slots.size();
+    check_repeat_sizes(count, s.n, s.m, q, nnz, T.param_first, T.n_params, n_slots, T.n_inputs);
+    if (caps) {                                     // the caller's buffers against the size formulas, before a row is made
+        if (caps[0] < count * q + 1) throw std::invalid_argument("template_repeat_instance: row_ptr too short (" + std::to_string(count * q + 1) + " entries needed)");
+        if (caps[1] < count * nnz) throw std::invalid_argument("template_repeat_instance: term_var / term_coef too short (" + std::to_string(count * nnz) + " entries needed)");
+        if (caps[2] < T.param_first + count * (T.n_params + n_slots))
+            throw std::invalid_argument("template_repeat_instance: coef too short (" + std::to_string(T.param_first + count * (T.n_params + n_slots)) + " scalars needed)");
+    }
+    const RepeatDims D{(uint32_t)s.n, (uint32_t)s.m, (uint32_t)q, (uint32_t)T.param_first, (uint32_t)T.n_params, (uint32_t)n_slots, (uint32_t)count};
     FlatCircuit f; f.n = count * s.n; f.m = count * s.m;
     f.row_ptr.reserve(count * q + 1); f.term_var.reserve(count * nnz); f.term_coef.reserve(count * nnz);
     for (uint64_t k = 0; k < count; k++)
@@ -1786,10 +1843,70 @@ FlatCircuit repeat_rows(const TemplatePlan &T, uint64_t count) {
             f.row_ptr.push_back(f.term_var.size());
         }
     f.coef.assign(s.coef.begin(), s.coef.begin() + 32 * T.param_first);
-    for (uint64_t k = 0; k < count; k++) f.coef.insert(f.coef.end(), s.coef.begin() + 32 * T.param_first, s.coef.end());
+    const auto par_end = s.coef.begin() + 32 * (T.param_first + T.n_params);
+    for (uint64_t k = 0; k < count; k++) f.coef.insert(f.coef.end(), s.coef.begin() + 32 * T.param_first, par_end);
+    for (uint64_t k = 0; k < count; k++) f.coef.insert(f.coef.end(), par_end, s.coef.end());       // the derived slots of a source with inputs, as they stand
     return f;
 }
+// what the eval hooks fill a_L, a_R, a_O with before a level runs
+const uint8_t kEvalPoison[32] = {0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a,
+                                 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x5a, 0xa5, 0x0a};
 }  // namespace
+// TEST HOOK (bpg_test_template_repeat_inputs_instance): template_repeat_instance_host for a program with public inputs - the rows as k_repeat_* leave them, the
+// parameter slots as an assign of param_values leaves them (null: as the template's rows carry them) and item k's derived slots as k_input_slots_join fills them
+// from input_values (count x n_inputs x 32, item-major): the same lane function, compiled for the host, over the same one-part descriptor.  caps: the caller's
+// row_ptr / term / coef capacities, checked against the size formulas before anything is built.
+FlatCircuit Engine::template_repeat_inputs_instance_host(const FlatView &c, const WitnessProgramView &p, uint64_t count, const uint8_t *param_values, const uint8_t *input_values,
+                                                         const uint64_t caps[3]) {
+    if (p.n_inputs && !input_values) throw std::invalid_argument("template_repeat_inputs_instance: the program has public inputs and no values were given for them");
+    FlatView rows = c; rows.aL = rows.aR = rows.aO = nullptr;
+    const TemplatePlan T = plan_template(rows, p);
+    FlatCircuit f = repeat_rows(T, count, caps);
+    if (param_values)
+        for (uint64_t i = 0; i < count * T.n_params; i++) Scalar::from_bytes_mod_order(param_values + 32 * i).to_bytes(&f.coef[32 * (T.param_first + i)]);
+    const uint64_t n_slots = T.in_slots.size();
+    if (n_slots) {
+        JoinPart P;
+        std::memset(&P, 0, sizeof P);
+        P.count = (uint32_t)count; P.n_in = (uint32_t)T.n_inputs; P.n_slots = (uint32_t)n_slots; P.base_dslot = (uint32_t)(T.param_first + count * T.n_params);
+        std::vector<scm> coef = scalars_from_bytes(f.coef.data(), f.coef.size() / 32);
+        const std::vector<scm> in = scalars_from_bytes(input_values, count * T.n_inputs);
+        for (uint64_t t = count * n_slots; t-- > 0;) join_input_slot_lane(&P, 1, t, reinterpret_cast<const uint32_t *>(T.in_slots.data()), in.data(), coef.data());
+        coef.resize(f.coef.size() / 32);
+        scalars_to_bytes(coef, f.coef.data());
+    }
+    return f;
+}
+// TEST HOOK (bpg_test_template_eval_repeat_inputs): k_witness_eval_repeat on the host for a source with inputs and / or checkpoints, under the discipline of
+// template_eval_checkpointed_host - poisoned vectors, the segments of every level and the items of every segment in REVERSE order, then the step of
+// k_witness_ck_verify; returns the first mismatching flat checkpoint index (item-major) or CHECKPOINTS_HOLD
+uint64_t Engine::template_eval_repeat_inputs_host(const FlatView &c, const WitnessProgramView &p, uint64_t count, const uint8_t *v, const uint8_t *ck_values,
+                                                  const uint8_t *input_values, uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out) {
+    if (p.n_inputs && !input_values) throw std::invalid_argument("template_eval_repeat_inputs: the program has public inputs and no values were given for them");
+    if (p.n_ck && !ck_values) throw std::invalid_argument("template_eval_repeat_inputs: the program has checkpoints and no values were given for them");
+    FlatView rows = c; rows.aL = rows.aR = rows.aO = nullptr;
+    const TemplatePlan T = plan_template(rows, p);
+    const PackedWitnessProgram &P = T.packed;
+    check_repeat_sizes(count, c.n, c.m, c.q, T.slotted.term_var.size(), T.param_first, T.n_params, T.in_slots.size(), T.n_inputs);
+    const std::vector<scm> coef = scalars_from_bytes(c.coef, c.ncoef), vv = scalars_from_bytes(v, count * c.m), ck = scalars_from_bytes(ck_values, count * p.n_ck);
+    const std::vector<scm> in = scalars_from_bytes(input_values, count * p.n_inputs);
+    const scm poison = scalars_from_bytes(kEvalPoison, 1)[0];
+    std::vector<scm> aL(count * c.n, poison), aR(count * c.n, poison), aO(count * c.n, poison);
+    const std::vector<uint32_t> &lp = T.schedule.level_ptr;
+    for (size_t l = 0; l + 1 < lp.size(); l++)
+        for (uint32_t s = lp[l + 1]; s-- > lp[l];)
+            for (uint64_t k = count; k-- > 0;)
+                witness_eval_repeat_lane(P.segs[s].first, P.segs[s].count, P.stream.data() + P.segs[s].stream, coef.data(), vv.data(), (uint32_t)c.n, (uint32_t)c.m, k,
+                                         aL.data(), aR.data(), aO.data(), p.n_ck ? ck.data() : nullptr, (uint32_t)p.n_ck, p.n_inputs ? in.data() : nullptr, (uint32_t)p.n_inputs);
+    uint64_t first = CHECKPOINTS_HOLD;
+    for (uint64_t t = count * p.n_ck; t-- > 0;) {
+        const size_t b = (size_t)(t / p.n_ck) * c.n;
+        if (!witness_ck_holds(p.ck_var[t % p.n_ck], ck[t], aL.data() + b, aR.data() + b, aO.data() + b)) first = t;
+    }
+    aL.resize(count * c.n); aR.resize(count * c.n); aO.resize(count * c.n);
+    scalars_to_bytes(aL, aL_out); scalars_to_bytes(aR, aR_out); scalars_to_bytes(aO, aO_out);
+    return first;
+}
 // TEST HOOK (bpg_test_template_repeat_instance): the repeated instance, row-major, as it stands after an assign of param_values (count x n_params x 32,
 // item-major, reduced as assign() reduces them; null: the slots keep the constants the template's rows carried)
 FlatCircuit Engine::template_repeat_instance_host(const FlatView &c, const WitnessProgramView &p, uint64_t count, const uint8_t *param_values) {
@@ -1823,7 +1940,7 @@ namespace {
 void check_join_sizes(const std::vector<JoinPart> &parts) {
     if (parts.empty()) throw std::invalid_argument("template_join: no parts (n_parts must be at least 1)");
     if (parts.size() > 256) throw std::invalid_argument("template_join: too many parts (" + std::to_string(parts.size()) + "; at most 256)");
-    uint64_t n = 0, m = 0, q = 0, nnz = 0, cols = 0, coefs = 0, ck = 0;
+    uint64_t n = 0, m = 0, q = 0, nnz = 0, cols = 0, coefs = 0, ck = 0, ins = 0;
     // total + count * a stays below limit
     auto add = [](uint64_t &total, uint64_t a, uint64_t count, uint64_t limit) { if (a && count > (limit - 1 - total) / a) return false; total += count * a; return true; };
     for (size_t p = 0; p < parts.size(); p++) {
@@ -1838,6 +1955,8 @@ void check_join_sizes(const std::vector<JoinPart> &parts) {
         if (!add(coefs, P.shared, 1, (uint64_t)WIT_COEF_INDEX_MASK + 1) || !add(coefs, P.n_params, P.count, (uint64_t)WIT_COEF_INDEX_MASK + 1))
             throw std::invalid_argument(at + "the joined coefficient slots are too many");
         if (!add(ck, P.n_ck, P.count, 1ull << 32)) throw std::invalid_argument(at + "the joined checkpoints are too many (below 2^32)");
+        if (!add(coefs, P.n_slots, P.count, (uint64_t)WIT_COEF_INDEX_MASK + 1)) throw std::invalid_argument(at + "the joined coefficient slots are too many (derived slots of the public inputs included)");
+        if (!add(ins, P.n_in, P.count, 1ull << 29)) throw std::invalid_argument(at + "the joined public inputs exceed the 29-bit variable index");
     }
 }
 // the block table of a join's assign(): per level, per part that has the level, per segment of it, a block for every 64 items - (part, segment in the joined
@@ -1859,7 +1978,7 @@ void join_block_table(const std::vector<JoinPart> &parts, const std::vector<cons
 }
 }  // namespace
 
-DeviceCircuit *Engine::join_templates(const std::vector<std::pair<DeviceCircuit *, uint64_t>> &src) {
+DeviceCircuit *Engine::join_templates(const std::vector<std::pair<DeviceCircuit *, uint64_t>> &src, bool with_inputs) {
     // every refusal first: nothing below this block runs for a refused call
     if (src.empty()) throw std::invalid_argument("template_join: no parts (n_parts must be at least 1)");
     if (src.size() > 256) throw std::invalid_argument("template_join: too many parts (" + std::to_string(src.size()) + "; at most 256)");
@@ -1872,13 +1991,14 @@ DeviceCircuit *Engine::join_templates(const std::vector<std::pair<DeviceCircuit 
         if (!s->is_template) throw std::invalid_argument(at + "the circuit is not a template (bpg_r1cs_upload_template)");
         if (s->rep_count) throw std::invalid_argument(at + "the circuit is itself a repeat (name the template it was made from and a count)");
         if (!s->join_parts.empty()) throw std::invalid_argument(at + "the circuit is itself a join (name its parts instead)");
-        if (s->n_in) throw std::invalid_argument(at + "the template has public inputs (a join carries none)");
+        if (s->n_in && !with_inputs) throw std::invalid_argument(at + "the template has public inputs (a join carries none)");
         if (s->device != device_) throw std::invalid_argument(at + "the circuit lives on the device of another context");
         if (src[p].second >= (1ull << 32)) throw std::invalid_argument(at + "the joined multipliers are too many (below 2^27)");
         JoinPart &P = parts[p];
         std::memset(&P, 0, sizeof P);
         P.n = (uint32_t)s->n; P.m = (uint32_t)s->m; P.q = (uint32_t)s->q; P.shared = (uint32_t)s->param_first; P.n_params = (uint32_t)s->n_params;
         P.n_ck = (uint32_t)s->n_ck; P.count = (uint32_t)src[p].second;
+        P.n_in = (uint32_t)s->n_in; P.n_slots = (uint32_t)s->n_slots;
         P.sec[4] = s->const_begin; P.sec[5] = s->nnz;
     }
     check_join_sizes(parts);
@@ -1901,7 +2021,7 @@ DeviceCircuit *Engine::join_templates(const std::vector<std::pair<DeviceCircuit 
     std::unique_ptr<DeviceCircuit> d(new DeviceCircuit());
     std::vector<uint32_t> table;
     join_block_table(parts, levels, table, d->join_level_ptr);
-    const uint64_t n = T.n, m = T.m, nnz = T.nnz, ncols = 3 * n + m + 1, ncoef = T.shared + T.n_params;
+    const uint64_t n = T.n, m = T.m, nnz = T.nnz, ncols = 3 * n + m + 1, ncoef = T.shared + T.n_params + T.n_slots;
     d->device = device_;
     d->n = n; d->m = m; d->q = T.q; d->ncols = ncols; d->nnz = nnz; d->const_begin = parts[0].sec_base[4]; d->has_witness = false;
     d->is_template = true; d->n_params = T.n_params; d->param_first = T.shared; d->n_ck = T.n_ck;
@@ -1910,6 +2030,12 @@ DeviceCircuit *Engine::join_templates(const std::vector<std::pair<DeviceCircuit 
     d->coef.ensure((ncoef ? ncoef : 1) * sizeof(scm));
     d->wit_stream.ensure((nwords ? nwords : 1) * 4); d->wit_segs.ensure((nsegs ? nsegs : 1) * sizeof(WitnessSegment)); d->wit_v.ensure((m ? m : 1) * sizeof(scm));
     if (T.n_ck) { d->wit_ck_var.ensure(nckv * 4); d->wit_ck.ensure(T.n_ck * sizeof(scm)); }
+    if (T.n_in) {                                   // the joined inputs, the derived slots behind all parameter slots, and the parts' (input, coefficient index) pairs
+        uint64_t pairs = 0;
+        for (const JoinPart &P : parts) pairs += P.n_slots;
+        d->n_in = T.n_in; d->n_slots = T.n_slots; d->slot_first = T.shared + T.n_params; d->slot_parts = T.n_slots ? (uint32_t)parts.size() : 0;
+        d->wit_in.ensure(T.n_in * sizeof(scm)); d->in_slots.ensure((pairs ? pairs : 1) * sizeof(InputSlot));
+    }
     d->join_desc.ensure(parts.size() * sizeof(JoinPart)); d->join_blocks.ensure((table.empty() ? 4 : table.size()) * 4);
     I.h2d(d->join_desc.p, parts.data(), parts.size() * sizeof(JoinPart));
     if (!table.empty()) I.h2d(d->join_blocks.p, table.data(), table.size() * 4);
@@ -1920,12 +2046,13 @@ DeviceCircuit *Engine::join_templates(const std::vector<std::pair<DeviceCircuit 
         if (s->wit_stream.cap) HIPCHK(hipMemcpyAsync(d->wit_stream.as<uint32_t>() + P.stream_first, s->wit_stream.p, s->wit_stream.cap, hipMemcpyDeviceToDevice, I.st));
         if (s->wit_segs.cap) HIPCHK(hipMemcpyAsync(d->wit_segs.as<WitnessSegment>() + P.seg_first, s->wit_segs.p, s->wit_segs.cap, hipMemcpyDeviceToDevice, I.st));
         if (P.n_ck) HIPCHK(hipMemcpyAsync(d->wit_ck_var.as<uint32_t>() + P.ck_var_first, s->wit_ck_var.p, (size_t)P.n_ck * 4, hipMemcpyDeviceToDevice, I.st));
+        if (P.n_slots) HIPCHK(hipMemcpyAsync(d->in_slots.as<InputSlot>() + P.slot_list_first, s->in_slots.p, (size_t)P.n_slots * sizeof(InputSlot), hipMemcpyDeviceToDevice, I.st));
         const uint32_t gy = std::min<uint32_t>(P.count, 1024);              // copies beyond the grid's y extent are a loop in the kernels
         BPG_LAUNCH(I, k_join_colptr, dim3(cdiv(3 * s->n + s->m + 1, 256), gy), dim3(256), s->col_ptr.as<uint64_t>(), desc, (uint32_t)p, (uint32_t)n, (uint32_t)m, nnz,
                    d->col_ptr.as<uint64_t>());
         if (s->nnz) BPG_LAUNCH(I, k_join_entries, dim3(cdiv(s->nnz, 256), gy), dim3(256), s->ent_row.as<uint32_t>(), s->ent_coef.as<uint32_t>(), desc, (uint32_t)p,
                                d->ent_row.as<uint32_t>(), d->ent_coef.as<uint32_t>());
-        const uint64_t pc = (uint64_t)P.shared + (uint64_t)P.count * P.n_params;
+        const uint64_t pc = (uint64_t)P.shared + (uint64_t)P.count * ((uint64_t)P.n_params + P.n_slots);
         if (pc) BPG_LAUNCH(I, k_join_coef, dim3(cdiv(pc, 256)), dim3(256), s->coef.as<scm>(), desc, (uint32_t)p, d->coef.as<scm>());
     }
     HIPCHK(hipGetLastError());
@@ -1953,12 +2080,15 @@ HostJoin plan_join(const std::vector<Engine::JoinSource> &src) {
     for (size_t p = 0; p < src.size(); p++) {
         if (src[p].count == 0 || src[p].count >= (1ull << 32))
             throw std::invalid_argument("template_join: part " + std::to_string(p) + (src[p].count ? ": the joined multipliers are too many (below 2^27)" : ": count must be at least 1"));
-        J.plans.push_back(Engine::plan_template(src[p].c, src[p].p));
+        FlatView rows = src[p].c;
+        if (src[p].p.n_inputs) rows.aL = rows.aR = rows.aO = nullptr;       // (a part with inputs: the hooks evaluate, a witness in the instance is not looked at)
+        J.plans.push_back(Engine::plan_template(rows, src[p].p));
         const TemplatePlan &T = J.plans.back();
         JoinPart &P = J.parts[p];
         std::memset(&P, 0, sizeof P);
         P.n = (uint32_t)T.slotted.n; P.m = (uint32_t)T.slotted.m; P.q = (uint32_t)(T.slotted.row_ptr.size() - 1); P.shared = (uint32_t)T.param_first;
         P.n_params = (uint32_t)T.n_params; P.n_ck = (uint32_t)T.ck_var.size(); P.count = (uint32_t)src[p].count;
+        P.n_in = (uint32_t)T.n_inputs; P.n_slots = (uint32_t)T.in_slots.size();
         P.sec[5] = T.slotted.term_var.size();
     }
     check_join_sizes(J.parts);
@@ -1968,11 +2098,18 @@ HostJoin plan_join(const std::vector<Engine::JoinSource> &src) {
 }  // namespace
 // TEST HOOK (bpg_test_template_join_instance): the joined instance, row-major - what k_join_* leave in HBM - as it stands after an assign of param_values (the
 // joined slots' values in order; null: every slot keeps the constant its part's rows carried)
-FlatCircuit Engine::template_join_instance_host(const std::vector<JoinSource> &src, const uint8_t *param_values) {
+FlatCircuit Engine::template_join_instance_host(const std::vector<JoinSource> &src, const uint8_t *param_values, const uint8_t *input_values, const uint64_t *caps) {
     const HostJoin J = plan_join(src);
+    if (J.T.n_in && !input_values) throw std::invalid_argument("template_join_inputs_instance: a part has public inputs and no values were given for them");
+    if (caps) {                                     // the caller's buffers against the size formulas, before a row is made
+        if (caps[0] < J.T.q + 1) throw std::invalid_argument("template_join_instance: row_ptr too short (" + std::to_string(J.T.q + 1) + " entries needed)");
+        if (caps[1] < J.T.nnz) throw std::invalid_argument("template_join_instance: term_var / term_coef too short (" + std::to_string(J.T.nnz) + " entries needed)");
+        if (caps[2] < J.T.shared + J.T.n_params + J.T.n_slots)
+            throw std::invalid_argument("template_join_instance: coef too short (" + std::to_string(J.T.shared + J.T.n_params + J.T.n_slots) + " scalars needed)");
+    }
     FlatCircuit f; f.n = J.T.n; f.m = J.T.m;
     f.row_ptr.reserve(J.T.q + 1); f.term_var.reserve(J.T.nnz); f.term_coef.reserve(J.T.nnz);
-    f.coef.assign(32 * (J.T.shared + J.T.n_params), 0);
+    f.coef.assign(32 * (J.T.shared + J.T.n_params + J.T.n_slots), 0);
     for (size_t p = 0; p < J.parts.size(); p++) {
         const FlatCircuit &s = J.plans[p].slotted;
         const JoinPart &P = J.parts[p];
@@ -1992,13 +2129,24 @@ FlatCircuit Engine::template_join_instance_host(const std::vector<JoinSource> &s
     }
     if (param_values)
         for (uint64_t i = 0; i < J.T.n_params; i++) Scalar::from_bytes_mod_order(param_values + 32 * i).to_bytes(&f.coef[32 * (J.T.shared + i)]);
+    if (J.T.n_slots) {                              // the derived slots as k_input_slots_join fills them: the same lane function over the same descriptors
+        std::vector<uint32_t> pairs;
+        for (const TemplatePlan &T : J.plans) for (const InputSlot &sl : T.in_slots) { pairs.push_back(sl.p); pairs.push_back(sl.ci); }
+        std::vector<scm> coef = scalars_from_bytes(f.coef.data(), f.coef.size() / 32);
+        const std::vector<scm> in = scalars_from_bytes(input_values, J.T.n_in);
+        for (uint64_t t = J.T.n_slots; t-- > 0;) join_input_slot_lane(J.parts.data(), (uint32_t)J.parts.size(), t, pairs.data(), in.data(), coef.data());
+        scalars_to_bytes(coef, f.coef.data());
+    }
     return f;
 }
 // TEST HOOK (bpg_test_template_eval_join): k_witness_eval_join and k_witness_ck_verify_join on the host, in the order that shows what in-order execution
 // hides - poisoned vectors, the levels in order and within a level the parts and their segments in REVERSE order, then the verify step; returns the first
 // mismatch.  v: the joined committed values; ck_values: the joined checkpoint values (null when no part has any)
-uint64_t Engine::template_eval_join_host(const std::vector<JoinSource> &src, const uint8_t *v, const uint8_t *ck_values, uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out) {
+uint64_t Engine::template_eval_join_host(const std::vector<JoinSource> &src, const uint8_t *v, const uint8_t *ck_values, uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out,
+                                         const uint8_t *input_values) {
     const HostJoin J = plan_join(src);
+    if (J.T.n_in && !input_values) throw std::invalid_argument("template_eval_join_inputs: a part has public inputs and no values were given for them");
+    const std::vector<scm> in = scalars_from_bytes(input_values, J.T.n_in);
     if (J.T.n_ck && !ck_values) throw std::invalid_argument("template_eval_join: a part has checkpoints and no values were given for them");
     std::vector<scm> coef(J.T.shared ? J.T.shared : 1);
     size_t nlev = 0;
@@ -2020,7 +2168,7 @@ uint64_t Engine::template_eval_join_host(const std::vector<JoinSource> &src, con
             for (uint32_t s = lp[l + 1]; s-- > lp[l];)
                 for (uint64_t k = J.parts[p].count; k-- > 0;)
                     witness_eval_join_lane(J.parts[p], P.segs[s].first, P.segs[s].count, P.stream.data() + P.segs[s].stream, coef.data(), vv.data(), k,
-                                           aL.data(), aR.data(), aO.data(), J.T.n_ck ? ck.data() : nullptr);
+                                           aL.data(), aR.data(), aO.data(), J.T.n_ck ? ck.data() : nullptr, J.T.n_in ? in.data() : nullptr);
         }
     uint64_t first = CHECKPOINTS_HOLD;
     for (uint64_t t = J.T.n_ck; t-- > 0;) {

@@ -120,6 +120,9 @@ public:
     // program names one.  A template without inputs takes null and is assign_checkpointed().  assign() / assign_checkpointed() on a template with inputs:
     // std::invalid_argument.
     uint64_t assign_inputs(DeviceCircuit *c, const uint8_t *v, const uint8_t *param_values, const uint8_t *ck_values, const uint8_t *input_values);
+    // The verifier's half of it (include/bpg.h bpg_r1cs_set_inputs): the n_inputs values go up and the derived slots are filled - one launch - and nothing else; the
+    // circuit is left without a witness.  Any template with inputs: single, repeat or join.  Refused (std::invalid_argument): no inputs, null values.
+    void set_inputs(DeviceCircuit *c, const uint8_t *input_values);
     // Which multiplier, which constraint row does the resident witness break (include/bpg.h bpg_r1cs_check; hip/k_check.cuh): a_L * a_R against a_O per multiplier, and
     // every row of the matrix over the operand vector [a_L | a_R | a_O | v | 1].  v: m x 32 bytes (reduced mod l on the device), or null on a template: the values
     // of its last assign().  rows_out receives the lowest min(cap, bad_rows) bad rows, ascending.  The first check of a circuit derives a row-major view of its
@@ -146,26 +149,39 @@ public:
     // the device from the source's resident matrix - copy k at multipliers k n.., committed values k m.., rows k q.., parameter slots k n_params.., everything else
     // shared.  It owns copies of all it needs, holds no witness and no host rows; assign() evaluates it with the source's program, a lane per (segment, item).
     // Refused (std::invalid_argument, before any device work): not a template, a repeat, count 0, sizes beyond the instance format.
-    DeviceCircuit *repeat_template(DeviceCircuit *tmpl, uint64_t count);
+    // with_inputs (bpg_r1cs_template_repeat_inputs): a source with public inputs is served - count x n_inputs values, item-major, and count x n_slots derived
+    // coefficient slots behind ALL parameter slots, filled per item by k_input_slots_join; false: such a source is refused, as the frozen call refuses it.
+    DeviceCircuit *repeat_template(DeviceCircuit *tmpl, uint64_t count, bool with_inputs = false);
     static bool is_repeat(const DeviceCircuit *c);
     // test hooks (bpg_test_template_repeat_instance, bpg_test_template_eval_repeat): the repeated rows as k_repeat_* leave them, and the repeat-layout interpreter
     // (k_witness_eval_repeat) compiled for the host; no device
     static FlatCircuit template_repeat_instance_host(const FlatView &c, const WitnessProgramView &p, uint64_t count, const uint8_t *param_values);
     static void template_eval_repeat_host(const FlatView &c, const WitnessProgramView &p, uint64_t count, const uint8_t *v, uint8_t *aL, uint8_t *aR, uint8_t *aO);
+    // the same two for a source with public inputs and / or checkpoints (bpg_test_template_repeat_inputs_instance, bpg_test_template_eval_repeat_inputs): the derived
+    // slots as k_input_slots_join fills them; the interpreter from poisoned vectors, segments and items in reverse order, then the comparison step.  caps: row_ptr,
+    // term and coef capacities of the caller, checked against the size formulas before anything is built (null: not checked)
+    static FlatCircuit template_repeat_inputs_instance_host(const FlatView &c, const WitnessProgramView &p, uint64_t count, const uint8_t *param_values,
+                                                            const uint8_t *input_values, const uint64_t caps[3] = nullptr);
+    static uint64_t template_eval_repeat_inputs_host(const FlatView &c, const WitnessProgramView &p, uint64_t count, const uint8_t *v, const uint8_t *ck_values,
+                                                     const uint8_t *input_values, uint8_t *aL, uint8_t *aR, uint8_t *aO);
     // Templates joined (include/bpg.h bpg_r1cs_template_join; hip/k_join.cuh): a new resident template that holds count_0 copies of part 0, then count_1 of part 1,
     // and so on - the circuit of ONE host assembly of the parts' gadget code in that order - built on the device from the parts' resident matrices.  It owns copies
     // of all it needs, holds no witness and no host rows; assign() evaluates every part's program in ONE launch per level (the most levels any part has).
     // Refused (std::invalid_argument that names the part, before any device work): no part or more than 256, a null part, count 0, not a template, a repeat or a
     // join, a part on another device, totals beyond the instance format.
-    DeviceCircuit *join_templates(const std::vector<std::pair<DeviceCircuit *, uint64_t>> &parts);
+    // with_inputs (bpg_r1cs_template_join_inputs): parts with public inputs are served - inputs and derived slots part-major, then item-major; false: refused.
+    DeviceCircuit *join_templates(const std::vector<std::pair<DeviceCircuit *, uint64_t>> &parts, bool with_inputs = false);
     static bool is_join(const DeviceCircuit *c);
     // flat index of the joined checkpoint list -> (part, item, checkpoint of the part's template); false: not a join, or no such index
     static bool join_checkpoint_place(const DeviceCircuit *c, uint64_t flat, uint64_t *part, uint64_t *item, uint64_t *ck);
     // test hooks (bpg_test_template_join_instance, bpg_test_template_eval_join): the joined rows as k_join_* leave them, and the join-layout interpreter
     // (k_witness_eval_join, k_witness_ck_verify_join) compiled for the host; no device
     struct JoinSource { FlatView c; WitnessProgramView p; uint64_t count; };
-    static FlatCircuit template_join_instance_host(const std::vector<JoinSource> &parts, const uint8_t *param_values);
-    static uint64_t template_eval_join_host(const std::vector<JoinSource> &parts, const uint8_t *v, const uint8_t *ck_values, uint8_t *aL, uint8_t *aR, uint8_t *aO);
+    // input_values (bpg_test_template_join_inputs_instance, bpg_test_template_eval_join_inputs): the joined public inputs when a part's program has any; caps as above
+    static FlatCircuit template_join_instance_host(const std::vector<JoinSource> &parts, const uint8_t *param_values, const uint8_t *input_values = nullptr,
+                                                   const uint64_t *caps = nullptr);
+    static uint64_t template_eval_join_host(const std::vector<JoinSource> &parts, const uint8_t *v, const uint8_t *ck_values, uint8_t *aL, uint8_t *aR, uint8_t *aO,
+                                            const uint8_t *input_values = nullptr);
     // Prover::prove on a resident circuit. transcript: state after Prover::new + every "V" append (updated in place).
     std::vector<uint8_t> prove(DeviceCircuit *c, Transcript &transcript, const std::vector<Scalar> &v_blinding,
                                const uint8_t rng_seed[32], uint32_t flags, ProveTimings *timings = nullptr);

@@ -2,6 +2,8 @@
 // a row into one prover.  Copy k of the template lives at
 //   multiplier i -> k n + i        committed value j -> k m + j        constraint row r -> k q + r
 //   parameter slot param_first + p -> param_first + k n_params + p     One and every other coefficient -> itself
+//   derived slot param_first + n_params + s of a source with public inputs -> param_first + K n_params + k n_slots + s (behind ALL parameter slots), and item k
+//   reads its own n_in inputs at k n_in: the table is [shared | K n_params parameter slots | K n_slots derived slots]
 // (repeat_map below: the ONE place that knows this, shared by the kernels, the host hooks of engine.hip and tests/hostcheck/template_repeat.cpp).
 // The resident matrix is column-major (k_scalars.cuh: columns left | right | output | committed | constants, entries = (row, coefficient slot)), so the
 // replication works on columns: the five SECTIONS of the source's entry list are each written K times, copy after copy, which keeps every column's entries
@@ -15,13 +17,15 @@
 
 namespace bpg {
 
-struct RepeatDims { uint32_t n, m, q, param_first, n_params; };      // of the SOURCE template; its coefficient table is [0, param_first) shared | n_params slots
+// of the SOURCE template; its coefficient table is [0, param_first) shared | n_params slots | n_slots derived slots (public inputs; 0: none, and count is not read)
+struct RepeatDims { uint32_t n, m, q, param_first, n_params, n_slots, count; };
 
 // copy k of (packed variable, coefficient slot, row) of the source
 BPG_HD void repeat_map(const RepeatDims &d, uint32_t k, uint32_t var, uint32_t coef, uint32_t row, uint32_t &var_out, uint32_t &coef_out, uint32_t &row_out) {
     const uint32_t kind = var >> 29, idx = var & 0x1fffffffu;
     var_out = kind <= 2 ? (kind << 29 | (k * d.n + idx)) : kind == 3 ? (kind << 29 | (k * d.m + idx)) : var;
-    coef_out = coef >= d.param_first ? coef + k * d.n_params : coef;     // (only constant terms of parameter rows name a slot)
+    if (d.n_slots && coef >= d.param_first + d.n_params) coef_out = coef + (d.count - 1) * d.n_params + k * d.n_slots;      // a derived slot: behind every item's parameters
+    else coef_out = coef >= d.param_first ? coef + k * d.n_params : coef;     // (only constant terms name a slot)
     row_out = k * d.q + row;
 }
 // column of a packed variable in a matrix over n multipliers and m committed values (csc_col of k_scalars.cuh), and the packed variable of a column
@@ -36,11 +40,11 @@ BPG_HD uint32_t repeat_var_of(uint32_t col, uint32_t n, uint32_t m) {
 BPG_HD uint64_t repeat_entry_pos(uint64_t K, uint64_t k, uint64_t s0, uint64_t s1, uint64_t e) { return K * s0 + k * (s1 - s0) + (e - s0); }
 
 // one lane of the repeat evaluation: segment sd = (first, count, stream word) of the source for item k
-// (ck, n_ck: the checkpoint values of a checkpointed source, item k's at ck + k n_ck; null, 0 otherwise)
+// (ck, n_ck: the checkpoint values of a checkpointed source, item k's at ck + k n_ck; null, 0 otherwise.  in, n_in: the public inputs likewise, item k's at in + k n_in)
 BPG_HD void witness_eval_repeat_lane(uint32_t first, uint32_t count, const uint32_t *rec, const scm *coef, const scm *v, uint32_t n, uint32_t m, uint64_t k,
-                                     scm *aL, scm *aR, scm *aO, const scm *ck = nullptr, uint32_t n_ck = 0) {
+                                     scm *aL, scm *aR, scm *aO, const scm *ck = nullptr, uint32_t n_ck = 0, const scm *in = nullptr, uint32_t n_in = 0) {
     const size_t b = (size_t)k * n;
-    witness_eval_segment(first, count, rec, coef, v + (size_t)k * m, aL + b, aR + b, aO + b, ck ? ck + (size_t)k * n_ck : nullptr, nullptr);     // (no inputs: such a template is not repeated)
+    witness_eval_segment(first, count, rec, coef, v + (size_t)k * m, aL + b, aR + b, aO + b, ck ? ck + (size_t)k * n_ck : nullptr, in ? in + (size_t)k * n_in : nullptr);
 }
 
 #if defined(__HIPCC__)
@@ -78,21 +82,21 @@ __global__ void __launch_bounds__(256) k_repeat_entries(const uint64_t *__restri
         row_out[pos] = row; coef_out[pos] = coef;
     }
 }
-// the coefficient table: the shared part once, the source's parameter slots (as they stand) once per copy
+// the coefficient table: the shared part once, the source's parameter slots (as they stand) once per copy, then its derived slots (as they stand) once per copy
 __global__ void __launch_bounds__(256) k_repeat_coef(const scm *__restrict__ coef, RepeatDims d, uint32_t K, scm *__restrict__ out) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (uint64_t)d.param_first + (uint64_t)K * d.n_params) return;
-    out[i] = coef[i < d.param_first ? i : d.param_first + (i - d.param_first) % d.n_params];
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, par_end = (uint64_t)d.param_first + (uint64_t)K * d.n_params;
+    if (i >= par_end + (uint64_t)K * d.n_slots) return;
+    out[i] = coef[i < d.param_first ? i : i < par_end ? d.param_first + (i - d.param_first) % d.n_params : d.param_first + d.n_params + (i - par_end) % d.n_slots];
 }
 // One launch per schedule level of the SOURCE; segs = that level's segments.  A block holds 64 consecutive ITEMS of one segment, the lane
 // map of k_witness_eval_batch: same records, same classes, no divergence; blocks_per_seg = ceil(K / 64) blocks per segment, segment-major in x.
 __global__ void __launch_bounds__(64) k_witness_eval_repeat(const uint4 *__restrict__ segs, uint32_t nseg, uint32_t blocks_per_seg, const uint32_t *__restrict__ stream,
                                                             const scm *__restrict__ coef, const scm *__restrict__ v, const scm *__restrict__ ck, uint32_t n_ck,
-                                                            uint32_t n, uint32_t m, uint32_t K, scm *aL, scm *aR, scm *aO) {
+                                                            const scm *__restrict__ in, uint32_t n_in, uint32_t n, uint32_t m, uint32_t K, scm *aL, scm *aR, scm *aO) {
     const uint32_t s = blockIdx.x / blocks_per_seg, item = (blockIdx.x % blocks_per_seg) * blockDim.x + threadIdx.x;
     if (s >= nseg || item >= K) return;
     const uint4 sd = segs[s];
-    witness_eval_repeat_lane(sd.x, sd.y, stream + sd.z, coef, v, n, m, item, aL, aR, aO, ck, n_ck);
+    witness_eval_repeat_lane(sd.x, sd.y, stream + sd.z, coef, v, n, m, item, aL, aR, aO, ck, n_ck, in, n_in);
 }
 #endif  // __HIPCC__
 

@@ -15,7 +15,8 @@
 // launch, the lane itself or the caller wrote.  k_witness_ck_verify, after the last level, compares every checkpoint with what the circuit computed for it.
 // A term of kind WIT_KIND_INPUT reads `in`, the public inputs the caller handed to assign (Engine::assign_inputs), by the input's index - a word of the record,
 // the same for every lane that walks it, so the items of a batch stay convergent: only the value differs.  The ROWS of the matrix never name an input: their
-// input terms are constant terms on derived coefficient slots, which k_input_slots fills per item before anything reads constant terms.
+// input terms are constant terms on derived coefficient slots, which k_input_slots fills per item before anything reads constant terms (a repeat or join
+// with inputs: k_input_slots_join of k_join.cuh, a lane per (part, item, slot)).
 #pragma once
 #include "sc.cuh"
 #include "../host/witness_record.hpp"

@@ -420,8 +420,8 @@ bpg_status bpg_r1cs_prove_template_batch_checkpointed(bpg_ctx *ctx, bpg_circuit 
  * blinding) run bpg_r1cs_assign_inputs + bpg_r1cs_prove_resident in item order.  On a template WITHOUT inputs it is that call, byte for byte.
  * On a template WITH inputs: bpg_r1cs_assign, bpg_r1cs_assign_checkpointed, bpg_r1cs_prove_template_batch, _commit and _checkpointed are refused with
  * BPG_ERR_INVALID_ARGUMENT before any work (their arguments carry no input values), as the frozen calls refuse a checkpointed template;
- * bpg_r1cs_template_repeat and bpg_r1cs_template_join refuse it as a source (a repeat or join with per-item inputs is out of scope here), and with them the
- * repeat-based batch check of the Python layer; bpg_r1cs_prove_resident, bpg_r1cs_verify_resident and bpg_r1cs_check serve it as any template -
+ * bpg_r1cs_template_repeat and bpg_r1cs_template_join refuse it as a source, and with them the repeat-based batch check of the Python layer
+ * (bpg_r1cs_template_repeat_inputs and bpg_r1cs_template_join_inputs below serve it, with per-item inputs); bpg_r1cs_prove_resident, bpg_r1cs_verify_resident and bpg_r1cs_check serve it as any template -
  * bpg_r1cs_verify_resident checks against the inputs of the last assign. */
 typedef struct {                          /* frozen */
     const uint8_t *v;                     /* m x 32: committed values, as bpg_r1cs_assign takes them */
@@ -570,6 +570,54 @@ bpg_status bpg_test_template_join_instance(uint64_t n_parts, const bpg_test_join
                                            uint64_t *ncoef_out);
 bpg_status bpg_test_template_eval_join(uint64_t n_parts, const bpg_test_join_part *parts, const uint8_t *v, const uint8_t *ck_values, uint8_t *aL_out,
                                        uint8_t *aR_out, uint8_t *aO_out, uint64_t *first_mismatch);
+/* PUBLIC INPUTS THROUGH REPEAT AND JOIN: K statements against K different public values - bounds, sets, roots, sibling lists - as ONE proof.  The frozen calls
+ * above keep refusing a template with public inputs; the capability comes through the entry points below.  On a template WITHOUT inputs each is its older
+ * sibling byte for byte.  (Additions to ABI version 7: look the symbols up.)
+ * bpg_r1cs_template_repeat_inputs: bpg_r1cs_template_repeat for a template uploaded with bpg_r1cs_upload_template_inputs.  Sizes as for the repeat, plus
+ * n_inputs' = count n_inputs, item-major.  With n_slots derived slots in the source (one per distinct (input, coefficient) pair of its rows) the coefficient
+ * table becomes [shared | count n_params parameter slots | count n_slots derived slots]: item k's derived slot s sits at param_first + count n_params +
+ * k n_slots + s, and item k's copies of the rows name item k's slots.  The result starts without a witness, its derived slots stand as the source's, and it
+ * owns copies of everything it needs, the source's (input, coefficient index) list included.  Refused as bpg_r1cs_template_repeat refuses, and besides:
+ * shared + count (n_params + n_slots) >= 2^30 coefficient indices, count n_inputs >= 2^29 - before any device work, named in bpg_last_error.
+ * bpg_r1cs_template_join_inputs: bpg_r1cs_template_join where any part may have inputs, over the same frozen bpg_template_part.  Inputs are ordered part-major,
+ * then item-major - the order of values, parameters and checkpoints.  The table is [shared of each part | parameter slots as in the join | derived slots,
+ * part-major, item-major]; a part without inputs contributes nothing to either new range; the same template may be named by several parts.
+ * bpg_r1cs_assign_inputs on such a repeat or join takes the n_inputs' values in that order, with its usual semantics (canonical values for byte identity; a
+ * refused or mismatching call leaves no witness; the equal-scalar sets are dropped).  ONE launch (k_input_slots_join, a lane per (part, item, slot)) writes
+ * coef[shared_p + ci] x_(p, k, input) into every derived slot before anything reads a constant term, and the levels hand every item its own inputs: as many
+ * launches as the repeat or join has without inputs.  bpg_r1cs_assign and bpg_r1cs_assign_checkpointed refuse it as they refuse a single template with inputs.
+ * bpg_r1cs_prove_resident, bpg_r1cs_verify_resident, bpg_r1cs_verify_batch (as one item), bpg_r1cs_check and bpg_r1cs_free serve it as any template;
+ * bpg_r1cs_prove_template_batch_inputs proves its items one at a time, as for every repeat; it is no source of a further repeat or join.
+ * bpg_r1cs_set_inputs: the VERIFIER's half of bpg_r1cs_assign_inputs, on any template with inputs (single, repeat or join).  It uploads and reduces the
+ * n_inputs values and fills the derived slots - one small launch - and does nothing else.  The circuit is left WITHOUT a witness: bpg_r1cs_prove_resident and
+ * bpg_r1cs_check then return BPG_ERR_MISSING_ASSIGNMENT, bpg_r1cs_verify_resident checks against these inputs.  The derived slots are sticky state of the
+ * circuit: they stand as the last bpg_r1cs_assign_inputs or bpg_r1cs_set_inputs left them.  Refused with BPG_ERR_INVALID_ARGUMENT before any device work: a
+ * wrong n_inputs, NULL input_values, a circuit without inputs, a handle without device state.  A verifying service uploads the shape once - from an instance
+ * without a witness, which bpg_r1cs_upload_template_inputs accepts - repeats it, and checks the one proof of K statements after this one call. */
+bpg_status bpg_r1cs_template_repeat_inputs(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t count, bpg_circuit **out);
+bpg_status bpg_r1cs_template_join_inputs(bpg_ctx *ctx, uint64_t n_parts, const bpg_template_part *parts, bpg_circuit **out);
+bpg_status bpg_r1cs_set_inputs(bpg_ctx *ctx, bpg_circuit *c, uint64_t n_inputs, const uint8_t *input_values /* n_inputs x 32 */);
+/* TEST HOOKS, no device needed: the four repeat and join hooks above for programs with public inputs (n_inputs per template; input_values: the n_inputs' values
+ * in the order bpg_r1cs_assign_inputs takes them; hints and checkpoints may be NULL).  The instance hooks give the rows as an assign of param_values (NULL: the
+ * constants of the templates' rows) and input_values leaves them: row-major, every input term a constant term on its derived slot, the slot filled by the lane
+ * function of k_input_slots_join compiled for the host.  coef: *ncoef_out = shared + n_params' + n_slots' scalars.  Every size is known before a row is made: a
+ * buffer that is one entry short is refused, named, and nothing is written.  The eval hooks are the repeat- and join-layout interpreters compiled for the host
+ * from poisoned vectors: levels in order, within a level parts, segments and items in REVERSE order, then the comparison step (*first_mismatch: the lowest
+ * mismatching flat checkpoint index, UINT64_MAX: none).  A join part for them is a new struct: bpg_test_join_part is frozen. */
+typedef struct { const bpg_r1cs_instance *inst; const bpg_witness_program *program; const bpg_witness_hints *hints; const bpg_witness_checkpoints *checkpoints;
+                 uint64_t count; uint64_t n_inputs; } bpg_test_join_inputs_part;
+bpg_status bpg_test_template_repeat_inputs_instance(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, uint64_t n_inputs,
+                                                    uint64_t count, const uint8_t *param_values, const uint8_t *input_values, uint64_t *row_ptr, uint64_t row_cap,
+                                                    uint32_t *term_var, uint32_t *term_coef, uint64_t term_cap, uint8_t *coef, uint64_t coef_cap, uint64_t *nnz_out,
+                                                    uint64_t *ncoef_out);
+bpg_status bpg_test_template_eval_repeat_inputs(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                                const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, uint64_t count, const uint8_t *v, const uint8_t *ck_values,
+                                                const uint8_t *input_values, uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out, uint64_t *first_mismatch);
+bpg_status bpg_test_template_join_inputs_instance(uint64_t n_parts, const bpg_test_join_inputs_part *parts, const uint8_t *param_values, const uint8_t *input_values,
+                                                  uint64_t *row_ptr, uint64_t row_cap, uint32_t *term_var, uint32_t *term_coef, uint64_t term_cap, uint8_t *coef,
+                                                  uint64_t coef_cap, uint64_t *nnz_out, uint64_t *ncoef_out);
+bpg_status bpg_test_template_eval_join_inputs(uint64_t n_parts, const bpg_test_join_inputs_part *parts, const uint8_t *v, const uint8_t *ck_values,
+                                              const uint8_t *input_values, uint8_t *aL_out, uint8_t *aR_out, uint8_t *aO_out, uint64_t *first_mismatch);
 
 /* R1CS CHECK ON THE DEVICE: is the resident witness satisfying, and if not, where does it fail.  (An addition to ABI version 7: look the symbol up.)
  * The witness of a template never visits the host (bpg_r1cs_assign, bpg_r1cs_template_repeat), and a proof of an unsatisfying witness is made all the same - the
