@@ -1393,6 +1393,15 @@ class ResidentCircuit:
             _chk(rc)
         return rc, ts.raw[:203]
 
+    def test_weights(self, z):
+        """bpg_test_weights: the verifier's flattened weights of this circuit at z (32 canonical bytes), through the code verify() runs ->
+        (w_L, w_R, w_O, w_V as lists of 32-byte scalars, w_c)."""
+        n, m = self.n, self.m
+        out = _buf(32 * (3 * n + m + 1))
+        _chk(lib().bpg_test_weights(self.ctx._h, self._h, None if z is None else _exact("z", z, 32), out))
+        w = [out.raw[32 * k:32 * k + 32] for k in range(3 * n + m + 1)]
+        return w[:n], w[n:2 * n], w[2 * n:3 * n], w[3 * n:3 * n + m], w[3 * n + m]
+
     def _template_items(self, items, struct=_TemplateItem):
         """bpg_template_item array of [(values, params, transcript_state, v_blinding, rng_seed, flags)] and the buffers it points into:
         (transcript state, proof buffer, proof length, values, params, v_blinding, seed) per item.  values / params of None stay NULL.

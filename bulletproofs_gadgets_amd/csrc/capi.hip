@@ -265,6 +265,15 @@ bpg_status bpg_test_commit3(bpg_ctx *ctx, uint32_t lgM0, uint64_t n, const uint8
     });
 }
 
+bpg_status bpg_test_weights(bpg_ctx *ctx, bpg_circuit *c, const uint8_t z[32], uint8_t *out) {
+    return guard([&] {
+        if (!ctx) throw DeviceError("test_weights: no device context (the weights are flattened on the GPU only)");
+        REQUIRE(c && z && out);
+        if (!c->dc) throw std::invalid_argument("test_weights: the handle has no device state (bpg_test_circuit_handle)");
+        ctx->engine->test_weights(c->dc, z, out);
+    });
+}
+
 bpg_status bpg_test_decompress(bpg_ctx *ctx, uint64_t n, const uint8_t *in, uint32_t *ok_out, uint8_t *xy_out) {
     return guard([&] {
         if (!ctx) throw DeviceError("test_decompress: no device context (k_decompress runs on the GPU only)");

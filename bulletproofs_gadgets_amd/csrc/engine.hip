@@ -27,6 +27,7 @@
 #include "host/fe51.hpp"
 #include "host/chain.hpp"
 #include "host/fiat_shamir.hpp"
+#include "host/csc_work.hpp"
 #include "hip/kernels.cuh"
 
 namespace bpg {
@@ -566,6 +567,22 @@ struct Engine::Impl {
             E.base[k] = to_scm(t.base); E.out[k] = t.out; E.count[k] = (uint32_t)t.count; E.lgT[k] = lgT; lgmax = std::max(lgmax, lgT); k++;
         }
         BPG_LAUNCH((*this), k_exp_table, dim3(cdiv(1u << lgmax, 256), k), dim3(256), E);
+    }
+    // flattened_constraints(z) of a resident circuit: z^j for j <= q into zpow, then w_L | w_R | w_O | w_V | w_c (3 n + m + 1 scalars) into w - k_flatten over the
+    // variable columns, the grid-wide k_flatten_const reduction over the constant column into w[3 n + m].  beside: one more power table for the same launch
+    // (the verifier's y^-i).  What verify_prep() runs, and what the test hook Engine::test_weights runs on a z of its caller's choosing.
+    void flatten_weights(const DeviceCircuit *c, const Scalar &z, scm *zpow, scm *w, const PowTable *beside) {
+        red_partial.ensure((size_t)4096 * sizeof(scm));                     // [0,1024): delta partials, [1024,1536): w_c partials
+        if (beside) exp_tables({*beside, {z, zpow, c->q + 1}}); else exp_tables({{z, zpow, c->q + 1}});      // (y^-i,) z^j: one launch
+        if (c->ncols > 1)
+            BPG_LAUNCH((*this), k_flatten, dim3(cdiv(c->ncols - 1, 256)), dim3(256), c->col_ptr.as<uint64_t>(), c->ent_row.as<uint32_t>(), c->ent_coef.as<uint32_t>(),
+                       c->coef.as<scm>(), zpow, w, (uint32_t)(c->ncols - 1), (uint32_t)(3 * c->n));
+        // w_c: grid-wide reduction over the constant-term entries
+        const uint64_t e0 = c->const_begin, e1 = c->nnz;
+        const uint32_t cb = std::max<uint32_t>(1, std::min<uint32_t>(cdiv(e1 - e0, 256), 512));
+        BPG_LAUNCH((*this), k_flatten_const, dim3(cb), dim3(256), c->ent_row.as<uint32_t>(), c->ent_coef.as<uint32_t>(), c->coef.as<scm>(), zpow, e0, e1,
+                   red_partial.as<scm>() + 1024);
+        BPG_LAUNCH((*this), k_reduce_partials, dim3(1), dim3(256), red_partial.as<scm>() + 1024, cb, 1u, w + c->ncols - 1);
     }
     struct CscWork { uint32_t *counts, *starts, *cursor, *rowconst, *rowconst_start, *bsum; };
     void transpose_csr(const uint64_t *rp, const uint32_t *tv, const uint32_t *tc, uint64_t q, uint64_t nmul, uint64_t m, const CscWork &W,
@@ -1277,6 +1294,27 @@ std::string Engine::test_tail(uint32_t lgM0, uint32_t tables, uint32_t first, ui
     return j;
 }
 
+// The verifier's flattened weights of a resident circuit at a z the caller chose (include/bpg.h bpg_test_weights): Impl::flatten_weights() as verify_prep() calls
+// it, laid out in the arena as there.  out = 3 n + m + 1 canonical scalars w_L | w_R | w_O | w_V | w_c.
+void Engine::test_weights(DeviceCircuit *c, const uint8_t z_bytes[32], uint8_t *out) {
+    if (!c || !z_bytes || !out) throw std::invalid_argument("test_weights: null pointer");
+    Scalar z;
+    std::memcpy(z.w, z_bytes, 32);
+    if (!z.is_canonical()) throw std::invalid_argument("test_weights: z is not canonical");
+    if (c->device != device_) throw std::invalid_argument("test_weights: the circuit lives on another device");
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    const size_t b_w = Impl::al256(c->ncols * sizeof(scm)), b_z = Impl::al256((c->q + 2) * sizeof(scm));
+    I.arena.ensure(b_w + b_z);
+    scm *const w = reinterpret_cast<scm *>(I.arena_at(0)), *const zpow = reinterpret_cast<scm *>(I.arena_at(b_w));
+    I.flatten_weights(c, z, zpow, w, nullptr);
+    HIPCHK(hipGetLastError());
+    std::vector<scm> h(c->ncols);
+    HIPCHK(hipMemcpyAsync(h.data(), w, c->ncols * sizeof(scm), hipMemcpyDeviceToHost, I.st));
+    HIPCHK(hipStreamSynchronize(I.st));
+    for (uint64_t k = 0; k < c->ncols; k++) from_scm(h[k]).to_bytes(out + 32 * k);
+}
+
 // A_I, A_O, S on scalars the caller chose (include/bpg.h bpg_test_commit3): Impl::commit3() as prove() calls it, on the window tables of the context's own
 // generators G[0, M0), H[0, M0).  Returns the JSON evidence of what was launched.
 std::string Engine::test_commit3(uint32_t lgM0, uint64_t n, const uint8_t *aL, const uint8_t *aR, const uint8_t *aO, const uint8_t *sL, const uint8_t *sR,
@@ -1316,11 +1354,13 @@ std::string Engine::test_commit3(uint32_t lgM0, uint64_t n, const uint8_t *aL, c
 
 // ------------------------------------------------------------------------------------------------ circuit upload
 // CSR (by constraint) -> CSC (by variable) on the stream: q rows over nmul multipliers per side (columns [0, 3 nmul)) and m committed variables, the constant
-// terms as the last column.  W: counts, starts, cursor (3 nmul + m + 2 words each), rowconst, rowconst_start (q + 2 words), the scans' block sums.
+// terms as the last column.  W: counts, starts, cursor, rowconst, rowconst_start and the scans' block sums, each of the size host/csc_work.hpp gives for
+// (3 nmul + m, q) - the second scan uses counts as scratch for q words, so a tall matrix (q > 3 nmul + m) needs more of it than the columns do.
 // totals[0] = first entry of the constant-terms column, totals[1] = entries written: the caller reads them back and checks that none was lost
 void Engine::Impl::transpose_csr(const uint64_t *rp, const uint32_t *tv, const uint32_t *tc, uint64_t q, uint64_t nmul, uint64_t m, const CscWork &W,
                                  uint64_t *col_ptr, uint32_t *ent_row, uint32_t *ent_coef, uint32_t *totals) {
     const uint64_t nvar = 3 * nmul + m;
+    static_assert(CSC_SCAN_CHUNK == SCAN_CHUNK, "host/csc_work.hpp sizes the block sums for the chunk of k_scan_apply");
     const uint32_t nb1 = cdiv(nvar ? nvar : 1, SCAN_CHUNK), nb2 = cdiv(q ? q : 1, SCAN_CHUNK);
     HIPCHK(hipMemsetAsync(W.counts, 0, (nvar + 1) * 4, st));
     HIPCHK(hipMemsetAsync(W.rowconst, 0, (q + 1) * 4, st));
@@ -1376,9 +1416,9 @@ DeviceCircuit *Engine::upload(const FlatView &c) {
         // the CSR arrays travel as they are; workspace: the MSM sort buffers (no MSM runs on this context during an upload)
         I.arena.ensure((nnz ? nnz : 1) * 8);                                // term_var | term_coef
         I.plain.ensure((q + 2) * 8 + 64);                                   // row_ptr
-        I.counts.ensure((std::max<uint64_t>(nvar, q) + 2) * 4); I.starts.ensure((std::max<uint64_t>(nvar, q) + 2) * 4);
-        I.cursor.ensure((std::max<uint64_t>(nvar, q) + 2) * 4); I.heavy.ensure((q + 2) * 4); I.tile_hist.ensure((q + 2) * 4 + 64);
-        I.blocksum.ensure((size_t)(std::max(cdiv(nvar ? nvar : 1, SCAN_CHUNK), cdiv(q ? q : 1, SCAN_CHUNK)) + 2) * 4);
+        const CscWorkWords ws = csc_work_words(nvar, q);                     // (host/csc_work.hpp: the one size rule, shared with the lockstep wave)
+        I.counts.ensure(ws.counts * 4); I.starts.ensure(ws.starts * 4); I.cursor.ensure(ws.cursor * 4);
+        I.heavy.ensure(ws.rowconst * 4); I.tile_hist.ensure(ws.rowconst_start * 4); I.blocksum.ensure(ws.bsum * 4);
         I.extras.ensure(16 * sizeof(scm));
         uint32_t *tv = I.arena.as<uint32_t>(), *tc = tv + (nnz ? nnz : 1);
         uint64_t *rp = I.plain.as<uint64_t>();
@@ -2989,9 +3029,12 @@ struct WaveLayout {
         d_abc = take(3 * KN * 32); d_coef = take(ncoefT * 32); d_sLR = take(2 * KN * 32); d_ypow = take(KN * 32); d_yinv = take(KN * 32);
         d_z = take((qT + 1) * 32); d_w = take(ncols * 32); d_lv = take(KN * 32); d_rv = take(KN * 32); d_fG = take(KN * 32); d_fH = take(KN * 32);
         d_c = take(4 * KN * 32); d_tpart = take((size_t)pblocks * 6 * K * 32); d_t = take(6 * K * 32); d_ab = take(2 * K * 32);
-        d_colptr = take((ncols + 1) * 8); d_erow = take(nnzT * 4); d_ecoef = take(nnzT * 4); d_counts = take((nvar + 2) * 4);
-        d_starts = take((nvar + 2) * 4); d_cursor = take((nvar + 2) * 4); d_rowc = take((qT + 2) * 4); d_rowcs = take((qT + 2) * 4);
-        d_bsum = take((std::max(cdiv(nvar, SCAN_CHUNK), cdiv(qT ? qT : 1, SCAN_CHUNK)) + 2) * 4); d_part = take((size_t)K * std::max(3 * nblkC, 2 * nblkR) * sizeof(ge_ext));
+        // the transposition workspace by the one size rule (host/csc_work.hpp): counts is the second scan's scratch too, qT words of it.  (It was nvar + 2
+        // words here: a wave of tall items - more rows than 3 K N + mT - had that scan write on into starts and cursor, which k_csc_colptr and k_csc_fill read)
+        const CscWorkWords ws = csc_work_words(nvar, qT);
+        d_colptr = take((ncols + 1) * 8); d_erow = take(nnzT * 4); d_ecoef = take(nnzT * 4); d_counts = take(ws.counts * 4);
+        d_starts = take(ws.starts * 4); d_cursor = take(ws.cursor * 4); d_rowc = take(ws.rowconst * 4); d_rowcs = take(ws.rowconst_start * 4);
+        d_bsum = take(ws.bsum * 4); d_part = take((size_t)K * std::max(3 * nblkC, 2 * nblkR) * sizeof(ge_ext));
         d_pts = take(K * 3 * sizeof(ge_ext)); d_comp = take(K * 3 * 32); d_misc = take(64); d_v = take(from_values ? mT * 32 : 0);
         d_vcom = take(commit ? mT * 32 : 0); d_ck = take(ckT * 32); d_ckfirst = take(ckT ? K * 4 : 0);
         d_in = inT ? take(inT * 32) : off;
@@ -3352,25 +3395,16 @@ void verify_small_scalars(const VerifyReplay &R, const scm *wV, const Scalar &de
 // arena, read by k_verify_scalars(_acc) and nothing later.  ch: the proof's challenges on the device
 struct VerifyVecs { scm *wL, *wR, *wO, *wV, *svec; };
 VerifyVecs verify_prep(Engine::Impl &I, const DeviceCircuit *c, const VerifyReplay &R, const IpaChallenges *ch) {
-    const uint64_t n = c->n, m = c->m, q = c->q, N = R.N;
+    const uint64_t n = c->n, q = c->q, N = R.N;
     I.red_partial.ensure((size_t)4096 * sizeof(scm)); I.red_out.ensure(16 * sizeof(scm));      // [0,1024): delta partials, [1024,1536): w_c partials
     I.yinvpow.ensure(N * sizeof(scm));
     // powers of z, the flattened weights and the s vector are read by k_verify_scalars and earlier kernels only: in the arena, ahead of the one MSM
     const size_t b_w = Engine::Impl::al256(c->ncols * sizeof(scm)), b_z = Engine::Impl::al256((q + 2) * sizeof(scm)), b_y = Engine::Impl::al256(N * sizeof(scm));
     I.arena.ensure(b_w + b_z + b_y);
     scm *const wAll_p = reinterpret_cast<scm *>(I.arena_at(0)), *const zpow_p = reinterpret_cast<scm *>(I.arena_at(b_w)), *const ypow_p = reinterpret_cast<scm *>(I.arena_at(b_w + b_z));
-    I.exp_tables({{R.yinv, I.yinvpow.as<scm>(), N}, {R.z, zpow_p, q + 1}});      // y^-i, z^j: one launch
-    if (c->ncols > 1)
-        BPG_LAUNCH(I, k_flatten, dim3(cdiv(c->ncols - 1, 256)), dim3(256), c->col_ptr.as<uint64_t>(), c->ent_row.as<uint32_t>(), c->ent_coef.as<uint32_t>(),
-                   c->coef.as<scm>(), zpow_p, wAll_p, (uint32_t)(c->ncols - 1), (uint32_t)(3 * n));
+    const Engine::Impl::PowTable yinv_table{R.yinv, I.yinvpow.as<scm>(), N};
+    I.flatten_weights(c, R.z, zpow_p, wAll_p, &yinv_table);          // y^-i and z^j in one launch, then the weights
     scm *wL = wAll_p, *wR = wL + n, *wO = wR + n, *wV = wO + n;      // wV[m] = w_c
-    {   // w_c: grid-wide reduction over the constant-term entries
-        const uint64_t e0 = c->const_begin, e1 = c->nnz;
-        const uint32_t cb = std::max<uint32_t>(1, std::min<uint32_t>(cdiv(e1 - e0, 256), 512));
-        BPG_LAUNCH(I, k_flatten_const, dim3(cb), dim3(256), c->ent_row.as<uint32_t>(), c->ent_coef.as<uint32_t>(), c->coef.as<scm>(), zpow_p, e0, e1,
-                   I.red_partial.as<scm>() + 1024);
-        BPG_LAUNCH(I, k_reduce_partials, dim3(1), dim3(256), I.red_partial.as<scm>() + 1024, cb, 1u, wV + m);
-    }
     BPG_LAUNCH(I, k_ipa_s, dim3(cdiv(N, 256)), dim3(256), ch, ypow_p, R.lgN, (uint32_t)N);
     return VerifyVecs{wL, wR, wO, wV, ypow_p};
 }

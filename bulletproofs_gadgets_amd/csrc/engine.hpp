@@ -91,6 +91,10 @@ public:
     // blind = the three blindings; out = the three encodings; returns a JSON text of what was launched
     std::string test_commit3(uint32_t lgM0, uint64_t n, const uint8_t *aL, const uint8_t *aR, const uint8_t *aO, const uint8_t *sL, const uint8_t *sR,
                              const uint8_t *blind, uint8_t out[96]);
+    // the verifier's flattened weights of a resident circuit at a z the caller chose (include/bpg.h bpg_test_weights): the powers of z, k_flatten and the
+    // k_flatten_const reduction as verify() runs them; out = 3 n + m + 1 canonical scalars w_L | w_R | w_O | w_V | w_c.  Refused before any launch
+    // (std::invalid_argument): a null pointer, a non-canonical z, a circuit of another device
+    void test_weights(DeviceCircuit *c, const uint8_t z[32], uint8_t *out);
 
     DeviceCircuit *upload(const FlatView &c);
     DeviceCircuit *upload(const FlatCircuit &c) { return upload(FlatView(c)); }

@@ -729,6 +729,13 @@ bpg_status bpg_test_tail(bpg_ctx *ctx, uint32_t lgM0, uint32_t tables, uint32_t 
  * checked before a launch (BPG_ERR_INVALID_ARGUMENT); a NULL ctx is BPG_ERR_DEVICE.  (An addition to ABI version 7: look the symbol up.) */
 bpg_status bpg_test_commit3(bpg_ctx *ctx, uint32_t lgM0, uint64_t n, const uint8_t *aL, const uint8_t *aR, const uint8_t *aO, const uint8_t *sL, const uint8_t *sR,
                             const uint8_t blind[96], uint8_t out[96], char *evidence, uint64_t cap);
+/* test hook: the verifier's flattened weights of a resident circuit (any handle with device state: a plain upload, a template, a repeat, a join) at a z the
+ * caller chooses - the powers of z (k_exp_table), k_flatten over the variable columns and the k_flatten_const / k_reduce_partials reduction over the constant
+ * column, through the one function bpg_r1cs_verify_resident calls for them.  out = 3 n + m + 1 canonical scalars of 32 bytes: w_L (n) | w_R (n) | w_O (n) |
+ * w_V (m) | w_c, where row j weighs z^(j+1) and committed and constant terms change side (w_V and w_c come out negated).  The witness, if any, is not read.
+ * Checked before a launch (BPG_ERR_INVALID_ARGUMENT: a NULL pointer, a non-canonical z, a handle without device state or of another device); a NULL ctx is
+ * BPG_ERR_DEVICE and writes nothing.  (An addition to ABI version 7: look the symbol up.) */
+bpg_status bpg_test_weights(bpg_ctx *ctx, bpg_circuit *circuit, const uint8_t z[32], uint8_t *out);
 
 /* test hook: k_decompress, the verifier's RFC 9496 decoder, on n encodings of 32 bytes, launched as bpg_r1cs_verify launches it.  ok_out[i] = 1 when
  * encoding i is accepted; xy_out holds, for EVERY entry, the affine x || y (32 + 32 bytes, canonical) the kernel wrote, recovered on the host from
