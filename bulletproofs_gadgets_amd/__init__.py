@@ -988,6 +988,12 @@ class VerifyItem(C.Structure):
                 ("proof", C.c_char_p), ("proof_len", C.c_uint64), ("seed", C.c_char_p), ("flags", C.c_uint32)]
 
 
+class VerifyResidentItem(C.Structure):
+    """bpg_verify_resident_item (frozen): one proof of bpg_r1cs_verify_resident_batch."""
+    _fields_ = [("transcript_state", C.c_void_p), ("V", C.c_char_p), ("proof", C.c_char_p), ("proof_len", C.c_uint64), ("seed", C.c_char_p), ("flags", C.c_uint32),
+                ("param_values", C.c_char_p), ("input_values", C.c_char_p)]
+
+
 def _verify_items(items):
     """[(FlatInstance | ResidentCircuit, transcript_state, commitments, proof, seed=None, flags=0)] -> (VerifyItem array, state buffers, keep-alive)"""
     n = len(items)
@@ -1543,6 +1549,54 @@ class ResidentCircuit:
         ts = _buf(203); ts.raw = _exact("transcript_state", transcript_state, 203)
         seed, commitments, proof = _seed32(seed), _exact("commitments", commitments, 32 * self.m), bytes(proof)
         return lib().bpg_r1cs_verify_resident(self.ctx._h, self._h, ts, C.c_uint64(self.m), commitments, proof, C.c_uint64(len(proof)), seed, C.c_uint32(flags))
+
+    def verify_batch(self, items, batch_seed=None, return_status=False):
+        """bpg_r1cs_verify_resident_batch: K proofs of THIS circuit in lockstep launches.  items = [(transcript_state, commitments, proof, seed=None, flags=0,
+        params=None, inputs=None)]; params / inputs: the item's own parameter values (n_params x 32 bytes) and public inputs (n_inputs x 32 bytes), or None for
+        the circuit's standing slots (a single template only) -> (statuses, transcript states after), each status what verify() gives for that item alone with
+        its constants standing.  return_status=True: (call status, statuses, states).  A refused call (INVALID_ARGUMENT) or a device failure raises BpgError."""
+        n = len(items)
+        arr = (VerifyResidentItem * max(n, 1))()
+        states, keep = [], []
+        for k, it in enumerate(items):
+            it = tuple(it) + (None, 0, None, None)[len(it) - 3:]
+            state, coms, proof, seed, flags, params, inputs = it
+            ts = _buf(203); ts.raw = _exact("transcript_state", state, 203)
+            coms, proof, seed = _exact("commitments", coms, 32 * self.m), bytes(proof), _seed32(seed)
+            # (lengths are held to the circuit's where it has such values; where it has none the library refuses the item)
+            params = None if params is None else b"".join(params) if isinstance(params, (list, tuple)) else bytes(params)
+            inputs = None if inputs is None else b"".join(inputs) if isinstance(inputs, (list, tuple)) else bytes(inputs)
+            if params is not None and self.n_params:
+                params = _exact("params", params, 32 * self.n_params)
+            if inputs is not None and self.n_inputs:
+                inputs = _exact("inputs", inputs, 32 * self.n_inputs)
+            arr[k].transcript_state = C.cast(ts, C.c_void_p); arr[k].V = coms; arr[k].proof = proof; arr[k].proof_len = len(proof); arr[k].seed = seed
+            arr[k].flags = flags; arr[k].param_values = params; arr[k].input_values = inputs
+            states.append(ts); keep.append((coms, proof, seed, params, inputs))
+        status = (C.c_int32 * max(n, 1))()
+        rc = lib().bpg_r1cs_verify_resident_batch(self.ctx._h, self._h, C.c_uint64(n), arr, _seed32(batch_seed), status)
+        if rc not in (0, 1, 2, 3):
+            _chk(rc)
+        out = ([status[k] for k in range(n)], [ts.raw[:203] for ts in states])
+        return (rc,) + out if return_status else out
+
+    def test_verify_wave_scalars(self, challenges, params=None, inputs=None):
+        """bpg_test_verify_wave_scalars: the wave kernels of verify_batch() on challenge records of the caller's choosing.  challenges = one record per item:
+        a list of 7 + 2 lg N scalars of 32 bytes (y^-1, z, x, u, a, b, rho, u_1 .. u_lgN, their inverses); params / inputs: None or one byte string per item
+        -> (g, h as lists of N 32-byte scalars, slots = per item the list [w_V .. | w_c | delta], evidence dict)."""
+        import json
+        K = len(challenges)
+        N = 1
+        while N < self.n:
+            N *= 2
+        ch = b"".join(b"".join(rec) for rec in challenges)
+        g, h, small, ev = _buf(32 * N), _buf(32 * N), _buf(32 * K * (self.m + 2)), _buf(4096)
+        pv = None if params is None else b"".join(params)
+        iv = None if inputs is None else b"".join(inputs)
+        _chk(lib().bpg_test_verify_wave_scalars(self.ctx._h, self._h, C.c_uint64(K), ch, pv, iv, g, h, small, ev, C.c_uint64(4096)))
+        cut = lambda b, cnt: [b.raw[32 * k:32 * k + 32] for k in range(cnt)]
+        sl = cut(small, K * (self.m + 2))
+        return cut(g, N), cut(h, N), [sl[k * (self.m + 2):(k + 1) * (self.m + 2)] for k in range(K)], json.loads(ev.value.decode())
 
     def free(self):
         if self._h:

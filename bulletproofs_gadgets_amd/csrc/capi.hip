@@ -1164,6 +1164,59 @@ bpg_status bpg_test_verify_batch_scripted(bpg_ctx *ctx, uint64_t count, const bp
     return verify_batch(ctx, count, items, batch_seed, status_out, count ? scripts : nullptr, script_lens);
 }
 
+// K proofs of ONE resident circuit in lockstep launches (Engine::verify_resident_batch).  Every argument first: a refused call launches nothing and touches
+// neither status_out nor a transcript state
+bpg_status bpg_r1cs_verify_resident_batch(bpg_ctx *ctx, bpg_circuit *c, uint64_t count, const bpg_verify_resident_item *items, const uint8_t batch_seed[32],
+                                          bpg_status *status_out) {
+    return guard([&] {
+        const std::string fn = "verify_resident_batch: ";
+        if (!c) throw std::invalid_argument(fn + "null circuit");
+        if (count && (!items || !status_out || !batch_seed)) throw std::invalid_argument(fn + "null items, status_out or batch_seed with count > 0");
+        if (count > (1ull << 32)) throw std::invalid_argument(fn + "more than 2^32 items");
+        for (uint64_t k = 0; k < count; k++) {
+            const bpg_verify_resident_item &it = items[k];
+            const char *what = !it.transcript_state ? "transcript_state" : !it.proof ? "proof" : !it.seed ? "seed" : (c->m && !it.V) ? "V" : nullptr;
+            if (what) throw std::invalid_argument(fn + "item " + std::to_string(k) + ": null " + what);
+        }
+        if (!c->dc) throw std::invalid_argument(fn + "the handle has no device state (bpg_test_circuit_handle)");
+        REQUIRE(ctx);
+        std::vector<Transcript> T(count);
+        std::vector<Engine::ResidentVerifyItem> ei(count);
+        for (uint64_t k = 0; k < count; k++) {
+            const bpg_verify_resident_item &it = items[k];
+            Engine::ResidentVerifyItem &e = ei[k];
+            e.V = it.V; e.proof = it.proof; e.proof_len = it.proof_len; e.seed = it.seed; e.flags = it.flags; e.params = it.param_values; e.inputs = it.input_values;
+        }
+        ctx->engine->check_resident_batch(c->dc, count, ei.data());            // another context or device, constants the circuit cannot take
+        if (!count) return;
+        for (uint64_t k = 0; k < count; k++) { T[k] = Transcript::from_state(items[k].transcript_state); ei[k].T = &T[k]; }
+        std::vector<R1CSError> st(count);
+        ctx->engine->verify_resident_batch(c->dc, count, ei.data(), batch_seed, st.data());
+        uint64_t first = count;
+        for (uint64_t k = 0; k < count; k++) {
+            T[k].export_state(items[k].transcript_state);
+            status_out[k] = (bpg_status)st[k];
+            if (first == count && st[k] != R1CSError::None) first = k;
+        }
+        if (first < count) {
+            const R1CSError e = st[first];
+            throw R1CSException(e, "item " + std::to_string(first) + ": " + (e == R1CSError::VerificationError ? "proof rejected" : e == R1CSError::FormatError ? "malformed proof" : "generator capacity below padded circuit size"));
+        }
+    });
+}
+bpg_status bpg_test_verify_wave_scalars(bpg_ctx *ctx, bpg_circuit *c, uint64_t count, const uint8_t *challenges, const uint8_t *param_values, const uint8_t *input_values,
+                                        uint8_t *g_out, uint8_t *h_out, uint8_t *small_out, char *evidence, uint64_t cap) {
+    return guard([&] {
+        if (!ctx) throw DeviceError("test_verify_wave_scalars: no device context (the wave runs on the GPU only)");
+        REQUIRE(c && challenges && g_out && h_out && small_out && evidence);
+        if (!c->dc) throw std::invalid_argument("test_verify_wave_scalars: the handle has no device state (bpg_test_circuit_handle)");
+        if (cap < 1024) throw std::invalid_argument("test_verify_wave_scalars: evidence buffer too small (1024 bytes needed)");
+        const std::string r = ctx->engine->test_verify_wave_scalars(c->dc, count, challenges, param_values, input_values, g_out, h_out, small_out);
+        if (r.size() + 1 > cap) throw std::invalid_argument("test_verify_wave_scalars: evidence buffer too small (" + std::to_string(r.size() + 1) + " bytes needed)");
+        std::memcpy(evidence, r.c_str(), r.size() + 1);
+    });
+}
+
 // ---------------------------------------------------------------------------------------- batch pool
 struct bpg_pool { std::vector<bpg_ctx *> ctxs; };
 bpg_status bpg_pool_create(int32_t device, uint32_t workers, uint64_t gens_capacity, bpg_pool **out) { return bpg_pool_create_ex(device, workers, gens_capacity, nullptr, out); }

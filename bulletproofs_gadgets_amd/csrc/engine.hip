@@ -28,6 +28,7 @@
 #include "host/chain.hpp"
 #include "host/fiat_shamir.hpp"
 #include "host/csc_work.hpp"
+#include "host/verify_wave_plan.hpp"
 #include "hip/kernels.cuh"
 
 namespace bpg {
@@ -195,6 +196,7 @@ struct DeviceCircuit {
     DevBuf join_desc, join_blocks;
     std::vector<uint32_t> join_level_ptr;
     int device = 0;                         // the device the buffers live on
+    const void *owner = nullptr;            // the Engine that made the circuit (verify_resident_batch refuses a circuit of another context)
     // row-major view of the matrix for check() (hip/k_check.cuh), derived from the column-major one at the first check and kept until the circuit is freed (the
     // matrix never changes; parameter values live in `coef`, which the view indexes): rv_ptr = q + 1 row starts, rv_ent = nnz pairs (column, coefficient slot),
     // rv_long = [count | the rows of more than rv_threshold terms].  Plain device memory: no part of the table budget.
@@ -213,7 +215,8 @@ struct DeviceCircuit {
     X(k_bt_finish) X(k_bt_fold_scalars) X(k_witness_eval) X(k_witness_eval_batch) X(k_bt_commit_v) X(k_repeat_colptr) X(k_repeat_entries) X(k_repeat_coef) X(k_witness_eval_repeat) X(k_witness_ck_verify) X(k_witness_ck_verify_batch) \
     X(k_join_colptr) X(k_join_entries) X(k_join_coef) X(k_witness_eval_join) X(k_witness_ck_verify_join) X(k_input_slots) X(k_input_slots_join) \
     X(k_mimc_sponge) X(k_merkle_leaves) X(k_merkle_level) X(k_merkle_top) X(k_merkle_level_list) X(k_merkle_set_leaves) X(k_merkle_paths) X(k_merkle_export) \
-    X(k_rowview_count) X(k_rowview_fill) X(k_rowview_long) X(k_check_mul) X(k_check_rows) X(k_check_rows_long) X(k_check_count)
+    X(k_rowview_count) X(k_rowview_fill) X(k_rowview_long) X(k_check_mul) X(k_check_rows) X(k_check_rows_long) X(k_check_count) \
+    X(k_vw_exp) X(k_vw_tails) X(k_vw_flatten) X(k_vw_small) X(k_vw_scalars) X(k_vw_reduce)
 enum KernelId {
 #define X(n) KID_##n,
     BPG_KERNELS(X)
@@ -316,6 +319,10 @@ struct Engine::Impl {
     DevBuf stale_flag;              // one word, zero unless k_sc_from_wide met a poisoned (never uploaded) draw: checked before a proof leaves prove()
     DevBuf ipa_s, ipa_tabA, ipa_tabB, naf, qsteps, vfy_in, vfy_pts, vfy_ok, vfy_sc, vfy_ch;
     DevBuf vfy_small;               // verify_batch: per proof [w_V (m) | w_c | delta]
+    // verify_resident_batch (hip/k_vwave.cuh): the items' own parameter and input values as bytes, what each brings (flags), the circuit's standing tail
+    // (copied before the first wave; the item-by-item pass of a rejected batch restores the table from it), one item's tail for that pass
+    DevBuf vw_raw, vw_flags, vw_standing, vw_tail1;
+    uint32_t cu_count = 256;        // compute units of the device the context is created on: the block target of k_vw_scalars (host/verify_wave_plan.hpp)
     // table-driven IPA tail (kernels.cuh k_tt_*): frozen-generator window tables, per-point factors, coefficient tables
     DevBuf tt_bases, tt_table, tt_f, tt_c, tt_partial, grp_c, ped_table, s_parts;
     // tt_table holds the tables of the ORIGINAL generators G[0..M0), H[0..M0) when tt_orig_M0 != 0: they survive across proofs (a circuit
@@ -709,6 +716,7 @@ Engine::Engine(int device, const EngineConfig &cfg) : device_(device) {
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) {
             if (!resident_set) K->sweep_blocks_resident = (uint32_t)cus * 4u;
             K->wit_waves = (uint32_t)cus * 4u;
+            K->cu_count = (uint32_t)cus;
             if (!env_present("BPG_WINDOW_QUAD_BLOCKS")) K->window_quad_blocks = (uint32_t)cus + (uint32_t)cus / 8u;
         }
     }
@@ -1408,6 +1416,7 @@ DeviceCircuit *Engine::upload(const FlatView &c) {
     const uint64_t ncols = 3 * n + m + 1, nvar = ncols - 1;
     std::unique_ptr<DeviceCircuit> d(new DeviceCircuit());       // (the device is current: a failure below frees what it holds as it leaves)
     d->device = device_;
+    d->owner = this;
     d->n = n; d->m = m; d->q = q; d->ncols = ncols; d->has_witness = has_witness;
     d->aL.ensure((n ? n : 1) * sizeof(scm)); d->aR.ensure((n ? n : 1) * sizeof(scm)); d->aO.ensure((n ? n : 1) * sizeof(scm));
     d->col_ptr.ensure((ncols + 1) * 8); d->ent_row.ensure((nnz ? nnz : 1) * 4); d->ent_coef.ensure((nnz ? nnz : 1) * 4);
@@ -1821,6 +1830,7 @@ DeviceCircuit *Engine::repeat_template(DeviceCircuit *src, uint64_t count, bool 
     const RepeatDims D{(uint32_t)src->n, (uint32_t)src->m, (uint32_t)src->q, (uint32_t)src->param_first, (uint32_t)src->n_params, (uint32_t)src->n_slots, (uint32_t)K};
     std::unique_ptr<DeviceCircuit> d(new DeviceCircuit());
     d->n = n; d->m = m; d->q = q; d->ncols = ncols; d->nnz = nnz; d->const_begin = K * src->const_begin; d->has_witness = false;
+    d->owner = this;
     d->is_template = true; d->n_params = K * src->n_params; d->param_first = src->param_first; d->wit_level_ptr = src->wit_level_ptr;
     d->rep_count = K; d->rep_n = src->n; d->rep_m = src->m; d->n_ck = src->n_ck;
     d->aL.ensure(n * sizeof(scm)); d->aR.ensure(n * sizeof(scm)); d->aO.ensure(n * sizeof(scm));
@@ -2062,7 +2072,7 @@ DeviceCircuit *Engine::join_templates(const std::vector<std::pair<DeviceCircuit 
     std::vector<uint32_t> table;
     join_block_table(parts, levels, table, d->join_level_ptr);
     const uint64_t n = T.n, m = T.m, nnz = T.nnz, ncols = 3 * n + m + 1, ncoef = T.shared + T.n_params + T.n_slots;
-    d->device = device_;
+    d->device = device_; d->owner = this;
     d->n = n; d->m = m; d->q = T.q; d->ncols = ncols; d->nnz = nnz; d->const_begin = parts[0].sec_base[4]; d->has_witness = false;
     d->is_template = true; d->n_params = T.n_params; d->param_first = T.shared; d->n_ck = T.n_ck;
     d->aL.ensure((n ? n : 1) * sizeof(scm)); d->aR.ensure((n ? n : 1) * sizeof(scm)); d->aO.ensure((n ? n : 1) * sizeof(scm));
@@ -3635,6 +3645,293 @@ void Engine::verify_batch(size_t count, const VerifyItem *items, const uint8_t b
         try { status_out[k] = verify(c, *it.T, it.V, it.proof, it.proof_len, it.seed, it.flags); } catch (...) { if (own) free_circuit(c); throw; }
         if (own) free_circuit(c);
     }
+}
+
+// ------------------------------------------------------------------------------------------------ lockstep verification (hip/k_vwave.cuh, host/verify_wave_plan.hpp)
+// K proofs of ONE resident circuit (include/bpg.h bpg_r1cs_verify_resident_batch): the verification equations weighted and summed into one MSM as in
+// verify_batch, but every device stage is one launch per WAVE of items instead of seven stream operations per item, and the replays run on the host
+// threads the proving waves use.  Per call: the replays, one k_decompress, the upload of one challenge record per item, the read-back of the K small
+// slots, the small scalars on the host, one MSM.  Per wave: k_vw_exp, (k_vw_tails,) k_vw_flatten, k_vw_small, k_vw_scalars, k_vw_reduce - six launches at
+// most, whatever K and N.  Three host synchronisations: after the decompression, before the small terms, after the MSM.
+namespace {
+struct VwCall { VerifyWavePlan P; uint64_t launches[6] = {0, 0, 0, 0, 0, 0}; };       // k_vw_exp, _tails, _flatten, _small, _scalars, _reduce
+constexpr const char *kVwNames[6] = {"k_vw_exp", "k_vw_tails", "k_vw_flatten", "k_vw_small", "k_vw_scalars", "k_vw_reduce"};
+uint64_t vw_tail_len(const DeviceCircuit *c) { return c->n_params + c->n_slots; }
+// The device side of the call from the challenge records to the accumulators, queued on the stream and not waited for: lv, rv (N scalars each, zeroed here)
+// and vfy_small (K slots [w_V | w_c | delta]).  h_ch: K records of P.ch_len scalars (hip/k_vwave.cuh).  raw / flags: K x (n_params + n_in) x 32 bytes and K
+// words when some item brings constants of its own, else null.  The wave's regions live in the arena and are read by nothing after k_vw_reduce.
+VwCall verify_wave_launch(Engine::Impl &I, const DeviceCircuit *c, uint64_t K, const std::vector<scm> &h_ch, const std::vector<uint8_t> *raw, const std::vector<uint32_t> *flags) {
+    hipStream_t st = I.st;
+    const uint64_t n = c->n, m = c->m, N = padded_size(n), n_tail = raw ? vw_tail_len(c) : 0, n_raw = c->n_params + c->n_in;
+    VwCall R;
+    R.P = plan_verify_wave(n, m, c->q, N, n_tail, K, I.batch_wave_mb, I.cu_count);
+    const VerifyWavePlan &P = R.P;
+    if (h_ch.size() != K * P.ch_len) throw std::logic_error("verify wave: challenge records do not match the plan");
+    I.vfy_ch.ensure(P.bytes_ch); I.vfy_small.ensure(P.bytes_small); I.lv.ensure(N * sizeof(scm)); I.rv.ensure(N * sizeof(scm)); I.arena.ensure(P.total);
+    I.h2d(I.vfy_ch.p, h_ch.data(), P.bytes_ch);
+    if (n_tail) {
+        I.vw_raw.ensure(std::max<size_t>(raw->size(), 32)); I.vw_flags.ensure(K * 4); I.vw_standing.ensure(n_tail * sizeof(scm));
+        if (!raw->empty()) I.h2d(I.vw_raw.p, raw->data(), raw->size());
+        I.h2d(I.vw_flags.p, flags->data(), K * 4);
+        HIPCHK(hipMemcpyAsync(I.vw_standing.p, c->coef.as<scm>() + c->param_first, n_tail * sizeof(scm), hipMemcpyDeviceToDevice, st));
+    }
+    HIPCHK(hipMemsetAsync(I.lv.p, 0, N * sizeof(scm), st));
+    HIPCHK(hipMemsetAsync(I.rv.p, 0, N * sizeof(scm), st));
+    scm *const w = reinterpret_cast<scm *>(I.arena_at(P.off_w)), *const ypow = reinterpret_cast<scm *>(I.arena_at(P.off_y)), *const zpow = reinterpret_cast<scm *>(I.arena_at(P.off_z)),
+        *const tails = n_tail ? reinterpret_cast<scm *>(I.arena_at(P.off_tail)) : nullptr, *const part = reinterpret_cast<scm *>(I.arena_at(P.off_part));
+    const uint32_t nz = (uint32_t)P.z_len, lgTy = std::min<uint32_t>(ceil_log2(N), 16), lgTz = std::min<uint32_t>(ceil_log2(nz), 16), ncols = (uint32_t)P.w_len;
+    const uint32_t bxN = cdiv(N, 256);
+    for (uint64_t wv = 0; wv < P.waves; wv++) {
+        const uint64_t k0 = wv * P.per_wave, items = P.wave_items(wv);
+        const VerifyWaveChunks &C = P.wave_chunks(wv);
+        const scm *ch = I.vfy_ch.as<scm>() + k0 * P.ch_len;
+        BPG_LAUNCH(I, k_vw_exp, dim3(cdiv(1u << std::max(lgTy, lgTz), 256), 2, (uint32_t)items), dim3(256), ch, (uint32_t)P.ch_len, ypow, (uint32_t)N, lgTy, zpow, nz, lgTz);
+        R.launches[0]++;
+        if (n_tail) {
+            BPG_LAUNCH(I, k_vw_tails, dim3(cdiv(items * n_tail, 256)), dim3(256), I.vw_flags.as<uint32_t>() + k0, I.vw_raw.as<uint32_t>() + 8 * k0 * n_raw, (uint32_t)n_raw,
+                       c->in_slots.as<uint32_t>(), c->coef.as<scm>(), I.vw_standing.as<scm>(), (uint32_t)c->n_params, (uint32_t)n_tail, items * n_tail, tails);
+            R.launches[1]++;
+        }
+        BPG_LAUNCH(I, k_vw_flatten, dim3(cdiv(items * ncols, 256)), dim3(256), c->col_ptr.as<uint64_t>(), c->ent_row.as<uint32_t>(), c->ent_coef.as<uint32_t>(), c->coef.as<scm>(),
+                   zpow, nz, w, ncols, (uint32_t)(3 * n), items * ncols);
+        R.launches[2]++;
+        BPG_LAUNCH(I, k_vw_small, dim3((uint32_t)items), dim3(256), c->ent_row.as<uint32_t>(), c->ent_coef.as<uint32_t>(), c->coef.as<scm>(), tails, (uint32_t)c->param_first,
+                   (uint32_t)n_tail, c->const_begin, c->nnz, zpow, nz, ypow, w, (uint32_t)n, (uint32_t)m, (uint32_t)N, I.vfy_small.as<scm>() + k0 * P.small_len);
+        R.launches[3]++;
+        BPG_LAUNCH(I, k_vw_scalars, dim3(bxN, C.chunks), dim3(256), ch, (uint32_t)P.ch_len, w, ypow, (uint32_t)n, (uint32_t)m, (uint32_t)N, P.lgN, items, C.per_chunk, part);
+        R.launches[4]++;
+        BPG_LAUNCH(I, k_vw_reduce, dim3(bxN), dim3(256), part, C.chunks, (uint32_t)N, I.lv.as<scm>(), I.rv.as<scm>());
+        R.launches[5]++;
+        HIPCHK(hipGetLastError());
+        {   // the profile's bookkeeping: bytes a kernel must move (scalars of 32 bytes, matrix entries of 8 + the coefficient and the power they name) and its
+            // Montgomery products, per wave
+            const double it = (double)items, var_ent = (double)c->const_begin, const_ent = (double)(c->nnz - c->const_begin), dN = (double)N, dn = (double)n;
+            const double b_exp = 32.0 * it * (dN + nz), b_fl = it * (72.0 * var_ent + 32.0 * ncols), b_sm = it * (72.0 * const_ent + 96.0 * dn + 32.0 * (m + 2.0));
+            const double b_part = 64.0 * C.chunks * dN, b_sc = it * 32.0 * (dN + 3.0 * dn + (double)P.ch_len) + b_part;
+            I.prof_note(KID_k_vw_exp, b_exp, b_exp, it * (dN + nz + 2.0 * (lgTy + lgTz)));
+            if (n_tail) I.prof_note(KID_k_vw_tails, 64.0 * it * n_tail, 64.0 * it * n_tail, 2.0 * it * n_tail);
+            I.prof_note(KID_k_vw_flatten, b_fl, b_fl, it * var_ent);
+            I.prof_note(KID_k_vw_small, b_sm, b_sm, it * (const_ent + 2.0 * dn));
+            I.prof_note(KID_k_vw_scalars, b_sc, b_sc, it * dN * (2.0 * P.lgN + 8.0));
+            I.prof_note(KID_k_vw_reduce, b_part + 128.0 * dN, b_part + 128.0 * dN, 0.0);
+        }
+    }
+    return R;
+}
+std::string vw_evidence(const VwCall &R) {
+    const VerifyWavePlan &P = R.P;
+    std::string j = "{";
+    auto ev = [&](const char *k, uint64_t v) { if (j.size() > 1) j += ", "; j += "\""; j += k; j += "\": "; j += std::to_string(v); };
+    ev("n", P.n); ev("N", P.N); ev("count", P.count); ev("n_tail", P.n_tail); ev("item_bytes", P.item_bytes); ev("waves", P.waves); ev("items_per_wave", P.per_wave);
+    ev("chunks", P.full.chunks); ev("items_per_chunk", P.full.per_chunk); ev("last_wave_items", P.wave_items(P.waves - 1)); ev("last_chunks", P.last.chunks);
+    ev("last_items_per_chunk", P.last.per_chunk); ev("target_blocks", P.target_blocks); ev("wave_bytes", P.total);
+    j += ", \"launches\": {";
+    for (int k = 0; k < 6; k++) { if (k) j += ", "; j += "\""; j += kVwNames[k]; j += "\": "; j += std::to_string(R.launches[k]); }
+    j += "}}";
+    return j;
+}
+// who may bring what (include/bpg.h): per-item constants on a SINGLE template only, parameter values where there are parameter rows, inputs where there are inputs
+void vw_check_constants(const DeviceCircuit *c, bool params, bool inputs, const std::string &who) {
+    if (!params && !inputs) return;
+    if (!c->is_template || c->rep_count || !c->join_parts.empty())
+        throw std::invalid_argument(who + ": per-item constants are served on a single template only (a repeat or a join is verified on its standing constants)");
+    if (params && !c->n_params) throw std::invalid_argument(who + ": param_values on a circuit without parameter rows");
+    if (inputs && !c->n_in) throw std::invalid_argument(who + ": input_values on a circuit without public inputs");
+}
+}  // namespace
+
+void Engine::check_resident_batch(const DeviceCircuit *c, size_t count, const ResidentVerifyItem *items) const {
+    if (!c) throw std::invalid_argument("verify_resident_batch: null circuit");
+    if (c->device != device_ || (c->owner && c->owner != this)) throw std::invalid_argument("verify_resident_batch: the circuit was uploaded on another context");
+    for (size_t k = 0; k < count; k++) {
+        vw_check_constants(c, items[k].params != nullptr, items[k].inputs != nullptr, "verify_resident_batch: item " + std::to_string(k));
+        if (!c->n && (items[k].params || items[k].inputs)) throw std::invalid_argument("verify_resident_batch: item " + std::to_string(k) + ": constants on a circuit without multipliers");
+    }
+}
+
+void Engine::verify_resident_batch(DeviceCircuit *c, size_t count, const ResidentVerifyItem *items, const uint8_t batch_seed[32], R1CSError *status_out) {
+    check_resident_batch(c, count, items);
+    if (!count) return;
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    hipStream_t st = I.st;
+    I.shared_now = I.shared_variants();
+    const uint64_t n = c->n, m = c->m, n_par = c->n_params, n_in = c->n_in, n_raw = n_par + n_in;
+    bool constants = false;
+    for (size_t k = 0; k < count; k++) constants |= items[k].params || items[k].inputs;
+    const uint64_t n_tail = constants ? vw_tail_len(c) : 0;
+    // the item-by-item pass: a circuit without multipliers as a whole, and the live items of a rejected sum.  An item's own constants are written into the table
+    // for its verification; the standing tail (vw_standing, copied before the first wave) is back in place before the next item without constants and at the end
+    bool dirty = false;
+    auto restore = [&] { if (dirty) { HIPCHK(hipMemcpyAsync(c->coef.as<scm>() + c->param_first, I.vw_standing.p, n_tail * sizeof(scm), hipMemcpyDeviceToDevice, st)); HIPCHK(hipStreamSynchronize(st)); dirty = false; } };
+    auto alone = [&](size_t k, uint64_t j) {         // j: the item's place among the records of the waves
+        const ResidentVerifyItem &it = items[k];
+        if (it.params || it.inputs) {
+            I.vw_tail1.ensure(n_tail * sizeof(scm));
+            BPG_LAUNCH(I, k_vw_tails, dim3(cdiv(n_tail, 256)), dim3(256), I.vw_flags.as<uint32_t>() + j, I.vw_raw.as<uint32_t>() + 8 * j * n_raw, (uint32_t)n_raw,
+                       c->in_slots.as<uint32_t>(), c->coef.as<scm>(), I.vw_standing.as<scm>(), (uint32_t)n_par, (uint32_t)n_tail, n_tail, I.vw_tail1.as<scm>());
+            HIPCHK(hipGetLastError());
+            dirty = true;
+            HIPCHK(hipMemcpyAsync(c->coef.as<scm>() + c->param_first, I.vw_tail1.p, n_tail * sizeof(scm), hipMemcpyDeviceToDevice, st));
+        } else restore();
+        status_out[k] = verify(c, *it.T, it.V, it.proof, it.proof_len, it.seed, it.flags);
+    };
+    if (n == 0) {       // no generator lanes to share: the existing path, item by item (no template has n = 0, so no item brings constants)
+        for (size_t k = 0; k < count; k++) alone(k, 0);
+        return;
+    }
+    // ---- host phase: format checks and Fiat-Shamir replay of every item on the host threads of the proving waves
+    std::vector<VerifyReplay> R(count);
+    std::vector<Transcript> before(count);
+    std::vector<uint8_t> live(count, 0);
+    StageThreads pool(std::min<uint32_t>(batch_host_threads(), (uint32_t)std::max<size_t>(1, count / 8)));
+    pool.run(count, [&](size_t lo, size_t hi) {
+        for (size_t k = lo; k < hi; k++) {
+            const ResidentVerifyItem &it = items[k];
+            before[k] = *it.T;
+            status_out[k] = verify_replay(n, m, gens_cap_, *it.T, it.proof, it.proof_len, it.seed, it.flags, R[k]);
+            live[k] = status_out[k] == R1CSError::None;
+        }
+    });
+    // ---- the weights: verify_batch's transcript (count, every proof and its replayed state, finalised with batch_seed); an item's own constants go in behind its
+    // state, so a call without any draws verify_batch's weights
+    std::vector<Scalar> rho(count);
+    {
+        static const char label[] = "bpg-verify-batch-v1";
+        Transcript B(reinterpret_cast<const uint8_t *>(label), sizeof label - 1);
+        B.append_u64("count", count);
+        for (size_t k = 0; k < count; k++) {
+            uint8_t s[203]; items[k].T->export_state(s);
+            B.append_message("proof", items[k].proof, items[k].proof_len);
+            B.append_message("state", s, 203);
+            if (items[k].params) B.append_message("params", items[k].params, n_par * 32);
+            if (items[k].inputs) B.append_message("inputs", items[k].inputs, n_in * 32);
+        }
+        TranscriptRng rng = B.build_rng({}, batch_seed);
+        for (size_t k = 0; k < count; k++) rho[k] = rng.random_scalar();
+    }
+    // ---- every live item's points in one decompression (the first synchronisation): items with a bad point leave here
+    const uint32_t np1 = (uint32_t)(6 + m + 5 + 2 * ceil_log2(padded_size(n)));
+    std::vector<uint32_t> pt_off(count + 1, 0);
+    for (size_t k = 0; k < count; k++) pt_off[k + 1] = pt_off[k] + (live[k] ? np1 : 0);
+    const uint32_t npts = pt_off[count];
+    if (!npts) return;
+    {
+        std::vector<uint8_t> hpts((size_t)npts * 32);
+        pool.run(count, [&](size_t lo, size_t hi) { for (size_t k = lo; k < hi; k++) if (live[k]) verify_points(R[k], items[k].V, &hpts[(size_t)pt_off[k] * 32]); });
+        I.vfy_in.ensure((size_t)npts * 32); I.vfy_pts.ensure((size_t)npts * sizeof(ge_niels)); I.vfy_ok.ensure((size_t)npts * 4);
+        I.h2d(I.vfy_in.p, hpts.data(), hpts.size());
+        BPG_LAUNCH(I, k_decompress, dim3(cdiv(npts, 64)), dim3(64), I.vfy_in.as<uint8_t>(), I.vfy_pts.as<ge_niels>(), I.vfy_ok.as<uint32_t>(), npts);
+        HIPCHK(hipGetLastError());
+        std::vector<uint32_t> h_ok(npts);
+        HIPCHK(hipMemcpyAsync(h_ok.data(), I.vfy_ok.p, (size_t)npts * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (size_t k = 0; k < count; k++) {
+            if (!live[k]) continue;
+            for (uint32_t j = pt_off[k]; j < pt_off[k + 1]; j++)
+                if (!h_ok[j]) { status_out[k] = R1CSError::VerificationError; live[k] = 0; break; }     // optional_multiscalar_mul: a point failed to decompress
+        }
+    }
+    // ---- the waves: one challenge record per live item, in item order
+    std::vector<size_t> lk;                                     // live items
+    for (size_t k = 0; k < count; k++) if (live[k]) lk.push_back(k);
+    const uint64_t K = lk.size();
+    if (!K) return;
+    const uint32_t lgN = R[lk[0]].lgN;
+    const uint64_t ch_len = VW_CH_FIXED + 2 * (uint64_t)lgN;
+    std::vector<scm> h_ch(K * ch_len);
+    std::vector<uint8_t> raw; std::vector<uint32_t> flags;
+    if (constants) { raw.assign(K * n_raw * 32, 0); flags.assign(K, 0); }
+    pool.run(K, [&](size_t lo, size_t hi) {
+        for (size_t j = lo; j < hi; j++) {
+            const VerifyReplay &r = R[lk[j]];
+            scm *h = &h_ch[j * ch_len];
+            h[VW_YINV] = to_scm(r.yinv); h[VW_Z] = to_scm(r.z); h[VW_X] = to_scm(r.x); h[VW_UCH] = to_scm(r.u_ch); h[VW_A] = to_scm(r.ipa); h[VW_B] = to_scm(r.ipb);
+            h[VW_RHO] = to_scm(rho[lk[j]]);
+            for (uint32_t t = 0; t < lgN; t++) { h[VW_CH_FIXED + t] = to_scm(r.uk[t]); h[VW_CH_FIXED + lgN + t] = to_scm(r.ukinv[t]); }
+            if (!constants) continue;
+            const ResidentVerifyItem &it = items[lk[j]];
+            if (it.params) { std::memcpy(&raw[j * n_raw * 32], it.params, n_par * 32); flags[j] |= VW_HAS_PARAMS; }
+            if (it.inputs) { std::memcpy(&raw[(j * n_raw + n_par) * 32], it.inputs, n_in * 32); flags[j] |= VW_HAS_INPUTS; }
+        }
+    });
+    const VwCall run = verify_wave_launch(I, c, K, h_ch, constants ? &raw : nullptr, constants ? &flags : nullptr);
+    const uint64_t N = run.P.N;
+    // ---- small terms (the second synchronisation): every live item's point scalars times rho_k; the B, B_blinding scalars summed over the items
+    const size_t slot_len = (size_t)m + 2;
+    std::vector<scm> h_slots(K * slot_len);
+    HIPCHK(hipMemcpyAsync(h_slots.data(), I.vfy_small.p, h_slots.size() * sizeof(scm), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::vector<scm> hs(npts + 2);
+    std::memset(hs.data(), 0, hs.size() * sizeof(scm));                // points of items that left at the decompression: scalar 0, no bucket entries
+    std::vector<Scalar> sB(K), sBb(K);
+    pool.run(K, [&](size_t lo, size_t hi) {
+        std::vector<Scalar> hsv;
+        for (size_t j = lo; j < hi; j++) {
+            const size_t k = lk[j];
+            const scm *sl = &h_slots[j * slot_len];
+            verify_small_scalars(R[k], sl, from_scm(sl[m + 1]), &rho[k], hsv);
+            for (uint32_t t = 0; t < np1; t++) hs[pt_off[k] + t] = to_scm(hsv[t]);
+            sB[j] = hsv[np1]; sBb[j] = hsv[np1 + 1];
+        }
+    });
+    Scalar tB, tBb;
+    for (size_t j = 0; j < K; j++) { tB = tB + sB[j]; tBb = tBb + sBb[j]; }
+    hs[npts] = to_scm(tB); hs[npts + 1] = to_scm(tBb);
+    I.vfy_sc.ensure((size_t)(npts + 2) * sizeof(scm));
+    I.h2d(I.vfy_sc.p, hs.data(), hs.size() * sizeof(scm));
+    if (verify_msm(I, N, npts)) return;                                // one MSM for the whole call (the third synchronisation): every live item is accepted
+    // ---- a rejected sum: each live item alone, from its state before, for its exact status
+    try {
+        for (size_t j = 0; j < K; j++) { *items[lk[j]].T = before[lk[j]]; alone(lk[j], j); }
+    } catch (...) { try { restore(); } catch (...) {} throw; }
+    restore();
+}
+
+// bpg_test_verify_wave_scalars: verify_wave_launch on challenge records the caller chose
+std::string Engine::test_verify_wave_scalars(DeviceCircuit *c, uint64_t count, const uint8_t *challenges, const uint8_t *param_values, const uint8_t *input_values,
+                                             uint8_t *g_out, uint8_t *h_out, uint8_t *small_out) {
+    if (!c || !challenges || !g_out || !h_out || !small_out) throw std::invalid_argument("test_verify_wave_scalars: null pointer");
+    if (c->device != device_ || (c->owner && c->owner != this)) throw std::invalid_argument("test_verify_wave_scalars: the circuit was uploaded on another context");
+    if (!count || count > (1u << 20)) throw std::invalid_argument("test_verify_wave_scalars: 1 .. 2^20 items");
+    if (!c->n) throw std::invalid_argument("test_verify_wave_scalars: a circuit without multipliers has no wave (it is verified item by item)");
+    vw_check_constants(c, param_values != nullptr, input_values != nullptr, "test_verify_wave_scalars");
+    const uint64_t N = padded_size(c->n), n_par = c->n_params, n_in = c->n_in, n_raw = n_par + n_in;
+    const uint32_t lgN = ceil_log2(N);
+    const uint64_t ch_len = VW_CH_FIXED + 2 * (uint64_t)lgN;
+    std::vector<scm> h_ch(count * ch_len);
+    for (uint64_t k = 0; k < count; k++) for (uint64_t t = 0; t < ch_len; t++) {
+        Scalar s; std::memcpy(s.w, challenges + 32 * (k * ch_len + t), 32);
+        const std::string at = "test_verify_wave_scalars: item " + std::to_string(k) + ", entry " + std::to_string(t);
+        if (!s.is_canonical()) throw std::invalid_argument(at + " is not canonical");
+        if ((t == VW_YINV || t >= VW_CH_FIXED) && s.is_zero_mod_l()) throw std::invalid_argument(at + " is zero (y^-1 and every u_k have inverses)");
+        h_ch[k * ch_len + t] = to_scm(s);
+    }
+    for (uint64_t k = 0; k < count; k++) for (uint32_t t = 0; t < lgN; t++) {
+        const Scalar one = from_scm(h_ch[k * ch_len + VW_CH_FIXED + t]) * from_scm(h_ch[k * ch_len + VW_CH_FIXED + lgN + t]);
+        if (!(one == Scalar::one())) throw std::invalid_argument("test_verify_wave_scalars: item " + std::to_string(k) + ": entry u^-1_" + std::to_string(t) + " is not the inverse of u_" + std::to_string(t));
+    }
+    const bool constants = param_values || input_values;
+    std::vector<uint8_t> raw; std::vector<uint32_t> flags;
+    if (constants) {
+        raw.assign(count * n_raw * 32, 0); flags.assign(count, (param_values ? VW_HAS_PARAMS : 0u) | (input_values ? VW_HAS_INPUTS : 0u));
+        for (uint64_t k = 0; k < count; k++) {
+            if (param_values) std::memcpy(&raw[k * n_raw * 32], param_values + k * n_par * 32, n_par * 32);
+            if (input_values) std::memcpy(&raw[(k * n_raw + n_par) * 32], input_values + k * n_in * 32, n_in * 32);
+        }
+    }
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    const VwCall run = verify_wave_launch(I, c, count, h_ch, constants ? &raw : nullptr, constants ? &flags : nullptr);
+    const size_t slot_len = (size_t)c->m + 2;
+    std::vector<scm> g(N), h(N), sl(count * slot_len);
+    HIPCHK(hipMemcpyAsync(g.data(), I.lv.p, N * sizeof(scm), hipMemcpyDeviceToHost, I.st));
+    HIPCHK(hipMemcpyAsync(h.data(), I.rv.p, N * sizeof(scm), hipMemcpyDeviceToHost, I.st));
+    HIPCHK(hipMemcpyAsync(sl.data(), I.vfy_small.p, sl.size() * sizeof(scm), hipMemcpyDeviceToHost, I.st));
+    HIPCHK(hipStreamSynchronize(I.st));
+    for (uint64_t i = 0; i < N; i++) { from_scm(g[i]).to_bytes(g_out + 32 * i); from_scm(h[i]).to_bytes(h_out + 32 * i); }
+    for (size_t i = 0; i < sl.size(); i++) from_scm(sl[i]).to_bytes(small_out + 32 * i);
+    return vw_evidence(run);
 }
 
 // ------------------------------------------------------------------------------------------------ MiMC sponges and Merkle trees (hip/k_mimc.cuh)

@@ -230,6 +230,25 @@ public:
     // Every proof's verification equation weighted by a random rho_k, all of them in ONE multiscalar multiplication; status_out[k] is what verify()
     // returns for item k alone (a rejected batch is re-verified item by item).
     void verify_batch(size_t count, const VerifyItem *items, const uint8_t batch_seed[32], R1CSError *status_out);
+    // One proof of a lockstep verification (include/bpg.h bpg_r1cs_verify_resident_batch): the arguments of verify() on the call's ONE resident circuit, plus the
+    // item's own parameter values (n_params x 32) and public inputs (n_inputs x 32), either null: the circuit's standing slots.
+    struct ResidentVerifyItem {
+        Transcript *T = nullptr; const uint8_t *V = nullptr; const uint8_t *proof = nullptr; size_t proof_len = 0; const uint8_t *seed = nullptr; uint32_t flags = 0;
+        const uint8_t *params = nullptr, *inputs = nullptr;
+    };
+    // K proofs of one resident circuit, weighted as verify_batch weighs them, with a constant number of launches per wave of items (hip/k_vwave.cuh,
+    // host/verify_wave_plan.hpp) and the replays on the host threads of the proving waves; status_out[k] is what verify() returns for item k alone with its
+    // constants standing.  The circuit's coefficient table holds afterwards what it held before; a resident witness is neither read nor dropped.
+    // check_resident_batch: what the call refuses before any device work (std::invalid_argument): a null circuit, one of another context or device, per-item
+    // constants on anything but a single template, parameter values without parameter rows, inputs without public inputs.
+    void check_resident_batch(const DeviceCircuit *c, size_t count, const ResidentVerifyItem *items) const;
+    void verify_resident_batch(DeviceCircuit *c, size_t count, const ResidentVerifyItem *items, const uint8_t batch_seed[32], R1CSError *status_out);
+    // test hook (bpg_test_verify_wave_scalars): the device side of verify_resident_batch from k_vw_exp to k_vw_reduce, through the function the call runs, on
+    // challenge records the caller chose (count x (7 + 2 lg N) canonical scalars: y^-1, z, x, u, a, b, rho, u_k, u_k^-1); param_values / input_values: null or
+    // one set per item.  g_out, h_out: the accumulators (N canonical scalars each); small_out: count slots [w_V (m) | w_c | delta]; returns a JSON text of the
+    // plan it took.  Refused before a launch (std::invalid_argument): a non-canonical entry, y^-1 or a u_k of zero, a u_k^-1 that is not the inverse
+    std::string test_verify_wave_scalars(DeviceCircuit *c, uint64_t count, const uint8_t *challenges, const uint8_t *param_values, const uint8_t *input_values,
+                                         uint8_t *g_out, uint8_t *h_out, uint8_t *small_out);
     // One proof of a lockstep batch (include/bpg.h bpg_r1cs_prove_batch): an instance with its witness that passed the checks of bpg_r1cs_prove and
     // lockstep_eligible(); T is updated in place and proof filled exactly as prove() does for the item alone.  An item of prove_template_batch has no
     // instance of its own: its witness source is the template plus `values` (m x 32 committed values) and `params` (n_params x 32), and flat is left null.

@@ -17,6 +17,10 @@
 //                                       k_tt_multiples, k_tt_factors, then k_tt_advance, k_tt_round, k_tt_finish per round
 //   f1  Verifier::verify                k_decompress, k_flatten_const, k_ipa_s, k_verify_scalars + one MSM
 //       batch verification              the same per proof with k_verify_scalars_acc (weighted g_i, h_i added into two shared accumulators) + one MSM per batch
+//       lockstep verification           (k_vwave.cuh; K proofs of ONE resident circuit) per wave, whatever K and N: k_vw_exp (y^-i, z^j of every item), k_vw_tails (per-item
+//                                       parameter and derived coefficient slots, only when an item brings constants), k_vw_flatten (a lane per (item, column)),
+//                                       k_vw_small (a block per item: w_V, w_c, delta), k_vw_scalars (a lane per generator index, the wave's items in chunks,
+//                                       s_i formed in registers), k_vw_reduce (chunk sums into the call's accumulators) + one MSM per call
 //       lockstep batch proving          (N <= 2^tt_orig_lg, k_batch.cuh) one launch per stage for every proof of a wave: the upload kernels on one block-diagonal
 //                                       matrix, k_bt_commit3(_finish), k_bt_compress, k_bt_exp, k_flatten, k_bt_poly_t, k_pedersen, k_bt_poly_eval, k_bt_factors,
 //                                       then k_bt_advance, k_bt_round, k_bt_finish, k_bt_compress per round and k_bt_fold_scalars
@@ -38,7 +42,7 @@
 //                                       matrix, once per circuit: k_rowview_count, k_scan_blocksums / _apply, k_rowview_fill, k_rowview_long; per check: k_check_mul (a lane
 //                                       per multiplier), k_check_rows (a lane per short row, the wave's ballot = one word of the violation bitmap), k_check_rows_long (a
 //                                       wave per long row), k_check_count (bad rows and the first of them)
-// The kernels live in k_points.cuh, k_scalars.cuh, k_ipa.cuh, k_verify.cuh, k_msm.cuh, k_merge.cuh, k_batch.cuh, k_witness.cuh, k_repeat.cuh, k_join.cuh, k_mimc.cuh and k_check.cuh, included at the end of
+// The kernels live in k_points.cuh, k_scalars.cuh, k_ipa.cuh, k_verify.cuh, k_msm.cuh, k_merge.cuh, k_batch.cuh, k_witness.cuh, k_repeat.cuh, k_join.cuh, k_mimc.cuh, k_check.cuh and k_vwave.cuh, included at the end of
 // this file in that order.
 // Data layout in HBM: scalars = 8 x u32 Montgomery form, 32 B each, AoS (lane i <-> element i: 2 x 16 B coalesced
 // loads); generator tables = affine Niels (y+x, y-x, 2dxy), 96 B per point, G at [0,N) and H at [N,2N); window tables =
@@ -88,3 +92,4 @@ __device__ __forceinline__ uint32_t msm_point_index(const MsmSegs &S, uint32_t s
 #include "k_join.cuh"
 #include "k_mimc.cuh"
 #include "k_check.cuh"
+#include "k_vwave.cuh"

@@ -183,6 +183,43 @@ typedef struct {
 } bpg_verify_item;
 bpg_status bpg_r1cs_verify_batch(bpg_ctx *ctx, uint64_t count, const bpg_verify_item *items, const uint8_t batch_seed[32], bpg_status *status_out);
 
+/* Lockstep verification: K proofs of ONE resident circuit with a constant number of launches per wave of items.  bpg_r1cs_verify_batch gives every item a
+ * replay on one host thread and at least seven stream operations of its own; a service that checks many proofs of one shape keeps the circuit resident and
+ * calls this instead.  The replays run on the host threads the proving waves use; all live items' points are decoded in one launch; then, per wave of at
+ * most BPG_BATCH_WAVE_MB of device state (0: one item per wave), at most six launches whatever K and N compute every item's y^-i and z^j, its flattened
+ * weights, w_c and delta, and the rho-weighted G / H scalars of all items into two accumulators; the K small slots come back in one copy, and ONE multiscalar
+ * multiplication of 2 N + K (npts + 2) terms decides.  Three host synchronisations.  A rejected sum re-verifies every live item alone, as
+ * bpg_r1cs_verify_batch does.
+ *   status_out[k] = exactly what bpg_r1cs_verify_resident returns for item k alone on this circuit with that item's constants standing - after
+ *                   bpg_r1cs_set_inputs(input_values) and / or a write of param_values into the parameter slots, where the item gives them;
+ *                   transcript_state is left as that call leaves it.
+ *   return value  = BPG_OK when every item is accepted, else the status of the first failing item.
+ * THE CIRCUIT IS NEVER CHANGED: per-item constants live in the call's own buffers, and after the call, accepted or rejected, the coefficient table holds
+ * what it held before (the item-by-item pass of a rejected sum writes an item's constants into the table and puts the standing parameter and derived
+ * slots back).  A resident witness is neither read nor dropped.
+ * Served: any handle with device state (plain upload, template, repeat, join) when every item leaves param_values and input_values NULL; per-item
+ * param_values / input_values on a SINGLE template only.  A circuit without multipliers (n = 0) is served inside the call item by item.
+ * The whole call is refused with BPG_ERR_INVALID_ARGUMENT - nothing launched, status_out and every transcript state untouched, bpg_last_error names the
+ * item and the reason - for: a NULL circuit; NULL items, status_out or batch_seed with count > 0; a NULL transcript_state, proof or seed, or a NULL V with
+ * m > 0, in any item; a handle without device state (bpg_test_circuit_handle); a NULL ctx (as bpg_r1cs_verify_batch); a circuit of another context or
+ * device; per-item constants on a repeat or a join; param_values on a circuit without parameter rows; input_values on a circuit without public inputs.
+ * These checks come first, in this order; count == 0 then returns BPG_OK with nothing launched.
+ * The weights are bpg_r1cs_verify_batch's: a Merlin transcript "bpg-verify-batch-v1" over count, every proof and its replayed state, finalised with
+ * batch_seed (fresh randomness in production, as there); an item that brings constants has their bytes absorbed behind its state under the labels
+ * "params" / "inputs", so a call without per-item constants draws the very weights bpg_r1cs_verify_batch draws for the same items.
+ * (An addition to ABI version 7: look the symbol up.) */
+typedef struct {                       /* frozen */
+    uint8_t *transcript_state;         /* 203 B in/out, as bpg_r1cs_verify_resident */
+    const uint8_t *V;                  /* m x 32 (m is the circuit's) */
+    const uint8_t *proof; uint64_t proof_len;
+    const uint8_t *seed;               /* 32 B */
+    uint32_t flags;                    /* dialect flags of this item */
+    const uint8_t *param_values;       /* NULL: the circuit's standing parameter slots; else n_params x 32, as bpg_r1cs_assign takes them */
+    const uint8_t *input_values;       /* NULL: the standing derived slots; else n_inputs x 32, as bpg_r1cs_set_inputs takes them */
+} bpg_verify_resident_item;
+bpg_status bpg_r1cs_verify_resident_batch(bpg_ctx *ctx, bpg_circuit *circuit, uint64_t count, const bpg_verify_resident_item *items,
+                                          const uint8_t batch_seed[32], bpg_status *status_out);
+
 /* A batch of INDEPENDENT proofs on one GPU.  One proof keeps the device busy for ~45 ms of 340 (the rest is the host's serial Merlin
  * TranscriptRng chain, upstream-exact), so a pool of `workers` engine contexts + host threads proves items concurrently: the chain of
  * one proof overlaps the kernels of the others (8 workers: ~5x the single-proof rate on a 2^20 circuit).  Each item is what
@@ -736,6 +773,17 @@ bpg_status bpg_test_commit3(bpg_ctx *ctx, uint32_t lgM0, uint64_t n, const uint8
  * Checked before a launch (BPG_ERR_INVALID_ARGUMENT: a NULL pointer, a non-canonical z, a handle without device state or of another device); a NULL ctx is
  * BPG_ERR_DEVICE and writes nothing.  (An addition to ABI version 7: look the symbol up.) */
 bpg_status bpg_test_weights(bpg_ctx *ctx, bpg_circuit *circuit, const uint8_t z[32], uint8_t *out);
+/* test hook: the device side of bpg_r1cs_verify_resident_batch from k_vw_exp to k_vw_reduce, through the function the call runs, on challenge records the
+ * caller chooses.  challenges = count records of 7 + 2 lg N canonical scalars of 32 bytes: y^-1, z, x, u (the factor of the padding generators), a, b, rho,
+ * then u_1 .. u_lgN, then their inverses (N = n padded to a power of two).  param_values / input_values: NULL (the standing slots) or one set per item
+ * (count x n_params x 32, count x n_inputs x 32), on a single template.  g_out, h_out = the two accumulators, N canonical scalars each: sum_k rho_k g_k,i
+ * and sum_k rho_k h_k,i with the padding lanes times u; small_out = count slots [w_V (m) | w_c | delta].  evidence (cap >= 1024) = JSON text of the plan
+ * the call took: n, N, count, n_tail, item_bytes, waves, items_per_wave, chunks, items_per_chunk, the last wave's figures, target_blocks, wave_bytes and
+ * launches per kernel.  Refused before a launch (BPG_ERR_INVALID_ARGUMENT): a NULL pointer, count = 0 or above 2^20, a circuit without multipliers or of
+ * another context, a non-canonical entry, y^-1 = 0 or a u_k = 0, a u_k^-1 that is not the inverse of u_k, constants the circuit cannot take; a NULL ctx
+ * is BPG_ERR_DEVICE and writes nothing.  (An addition to ABI version 7: look the symbol up.) */
+bpg_status bpg_test_verify_wave_scalars(bpg_ctx *ctx, bpg_circuit *circuit, uint64_t count, const uint8_t *challenges, const uint8_t *param_values,
+                                        const uint8_t *input_values, uint8_t *g_out, uint8_t *h_out, uint8_t *small_out, char *evidence, uint64_t cap);
 
 /* test hook: k_decompress, the verifier's RFC 9496 decoder, on n encodings of 32 bytes, launched as bpg_r1cs_verify launches it.  ok_out[i] = 1 when
  * encoding i is accepted; xy_out holds, for EVERY entry, the affine x || y (32 + 32 bytes, canonical) the kernel wrote, recovered on the host from
