@@ -500,9 +500,11 @@ class Context:
         raw = out.raw                 # one copy of the buffer, not one per item
         return [raw[32 * i:32 * i + 32] for i in range(count)]
 
-    def merkle_tree(self, leaves) -> "MerkleTree":
-        """bpg_merkle_build: the full MiMC Merkle tree over 2^depth leaves (a list of 32-byte values, or their concatenation), resident on the GPU."""
-        return MerkleTree(self, leaves)
+    def merkle_tree(self, leaves, depth=None, empty=None) -> "MerkleTree":
+        """Without `depth`, bpg_merkle_build: the full MiMC Merkle tree over 2^depth leaves (a list of 32-byte values, or their concatenation), resident on
+        the GPU.  With `depth`, bpg_merkle_build_partial: a tree of capacity 2^depth over any len(leaves) <= 2^depth leaves, none included, whose other
+        leaves hold `empty` (32 bytes, taken mod l; None = zero) - the tree MerkleTree.append grows."""
+        return MerkleTree(self, leaves, depth, empty)
 
     def profile_set(self, mode):
         _chk(lib().bpg_profile_set(self._h, C.c_int32(mode)))
@@ -614,21 +616,59 @@ class Context:
 
 
 class MerkleTree:
-    """A full binary MiMC Merkle tree resident on the GPU of a context (bpg_merkle_*): node = mimc_sponge([left, right]) over the children as they are,
-    which is what MerkleTree256 constrains for a "(W W)" node.  Level 0 is the root, level `depth` the leaves."""
+    """A binary MiMC Merkle tree of capacity 2^depth resident on the GPU of a context (bpg_merkle_*): node = mimc_sponge([left, right]) over the children
+    as they are, which is what MerkleTree256 constrains for a "(W W)" node.  Level 0 is the root, level `depth` the leaves.  It holds `size` leaves; the
+    leaves from `size` on hold one `empty` value, so every node is that of the tree over the padded list, and append() puts more leaves behind the last."""
 
-    def __init__(self, ctx: "Context", leaves):
+    def __init__(self, ctx: "Context", leaves, depth=None, empty=None):
         data = bytes(leaves) if isinstance(leaves, (bytes, bytearray)) else b"".join(_exact("leaf", x, 32) for x in leaves)
         n = len(data) // 32
-        if len(data) % 32 or n < 1 or n & (n - 1):
-            raise ValueError("a full tree has 2^depth leaves of 32 bytes each")
-        self.ctx, self.depth, self._h = ctx, n.bit_length() - 1, C.c_void_p()
-        _chk(lib().bpg_merkle_build(ctx._h, C.c_uint32(self.depth), data, C.byref(self._h)))
+        if depth is None:
+            if empty is not None:
+                raise ValueError("`empty` belongs to a tree built with `depth`")
+            if len(data) % 32 or n < 1 or n & (n - 1):
+                raise ValueError("a tree built without `depth` has 2^depth leaves of 32 bytes each")
+            self.ctx, self.depth, self._h = ctx, n.bit_length() - 1, C.c_void_p()
+            _chk(lib().bpg_merkle_build(ctx._h, C.c_uint32(self.depth), data, C.byref(self._h)))
+            return
+        if len(data) % 32:
+            raise ValueError("leaves are 32 bytes each")
+        empty = None if empty is None else _exact("empty", empty, 32)
+        self.ctx, self.depth, self._h = ctx, int(depth), C.c_void_p()
+        _chk(lib().bpg_merkle_build_partial(ctx._h, C.c_uint32(self.depth), C.c_uint64(n), data if n else None, empty, C.byref(self._h)))
 
     def _handle(self):
         if not self._h:
             raise ValueError("this tree has been freed")
         return self._h
+
+    @property
+    def size(self):
+        """The number of leaves the tree holds (bpg_merkle_size): leaves [size, capacity) hold the empty value."""
+        out = C.c_uint64()
+        _chk(lib().bpg_merkle_size(self.ctx._h, self._handle(), C.byref(out), None))
+        return out.value
+
+    @property
+    def capacity(self):
+        return 1 << self.depth
+
+    def append(self, leaves, return_root=False):
+        """bpg_merkle_append: the leaves go behind the last one and only their ancestors are recomputed; returns the index of the first new leaf, and the new
+        root with it when return_root is set."""
+        data = bytes(leaves) if isinstance(leaves, (bytes, bytearray)) else b"".join(_exact("leaf", x, 32) for x in leaves)
+        if len(data) % 32:
+            raise ValueError("leaves are 32 bytes each")
+        first, root = C.c_uint64(), _buf(32)
+        _chk(lib().bpg_merkle_append(self.ctx._h, self._handle(), C.c_uint64(len(data) // 32), data if data else None, C.byref(first), root if return_root else None))
+        return (first.value, root.raw) if return_root else first.value
+
+    def empty_nodes(self):
+        """bpg_merkle_empty_nodes: [E_0, ..., E_depth], E_k = a subtree without a leaf k levels above the leaves (E_0 = the empty value, reduced)."""
+        out = _buf(32 * (self.depth + 1))
+        _chk(lib().bpg_merkle_empty_nodes(self.ctx._h, self._handle(), out))
+        raw = out.raw
+        return [raw[32 * k:32 * k + 32] for k in range(self.depth + 1)]
 
     def root(self):
         out = _buf(32)

@@ -1624,6 +1624,25 @@ bpg_status bpg_merkle_build(bpg_ctx *ctx, uint32_t depth, const uint8_t *leaves,
         *out = h.release();
     });
 }
+bpg_status bpg_merkle_build_partial(bpg_ctx *ctx, uint32_t depth, uint64_t size, const uint8_t *leaves, const uint8_t empty[32], bpg_merkle **out) {
+    return guard([&] {
+        REQUIRE(out); *out = nullptr;
+        REQUIRE(depth >= 1 && depth <= 24 && size <= (1ull << depth) && (leaves || size == 0));       // the arguments first: each is refused whatever the context
+        REQUIRE(ctx);
+        std::unique_ptr<bpg_merkle> h(new bpg_merkle{nullptr});
+        h->t = ctx->engine->merkle_build_partial(depth, size, leaves, empty);
+        *out = h.release();
+    });
+}
+bpg_status bpg_merkle_append(bpg_ctx *ctx, bpg_merkle *t, uint64_t count, const uint8_t *leaves, uint64_t *first_index_out, uint8_t root_out[32]) {
+    return guard([&] { REQUIRE(leaves || count == 0); REQUIRE(ctx && t); ctx->engine->merkle_append(t->t, count, leaves, first_index_out, root_out); });
+}
+bpg_status bpg_merkle_size(bpg_ctx *ctx, bpg_merkle *t, uint64_t *size_out, uint32_t *depth_out) {
+    return guard([&] { REQUIRE(size_out || depth_out); REQUIRE(ctx && t); ctx->engine->merkle_size(t->t, size_out, depth_out); });
+}
+bpg_status bpg_merkle_empty_nodes(bpg_ctx *ctx, bpg_merkle *t, uint8_t *out) {
+    return guard([&] { REQUIRE(out); REQUIRE(ctx && t); ctx->engine->merkle_empty_nodes(t->t, out); });
+}
 bpg_status bpg_merkle_root(bpg_ctx *ctx, bpg_merkle *t, uint8_t out[32]) { return guard([&] { REQUIRE(ctx && t && out); ctx->engine->merkle_nodes(t->t, 0, 0, 1, out); }); }
 bpg_status bpg_merkle_nodes(bpg_ctx *ctx, bpg_merkle *t, uint32_t level, uint64_t first, uint64_t count, uint8_t *out) {
     return guard([&] { REQUIRE(ctx && t && (out || count == 0)); ctx->engine->merkle_nodes(t->t, level, first, count, out); });

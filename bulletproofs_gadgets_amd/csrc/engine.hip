@@ -29,6 +29,7 @@
 #include "host/fiat_shamir.hpp"
 #include "host/csc_work.hpp"
 #include "host/verify_wave_plan.hpp"
+#include "host/merkle_plan.hpp"
 #include "hip/kernels.cuh"
 
 namespace bpg {
@@ -214,7 +215,7 @@ struct DeviceCircuit {
     X(k_bt_commit3) X(k_bt_commit3_finish) X(k_bt_compress) X(k_bt_exp) X(k_bt_poly_t) X(k_bt_poly_eval) X(k_bt_factors) X(k_bt_advance) X(k_bt_round) \
     X(k_bt_finish) X(k_bt_fold_scalars) X(k_witness_eval) X(k_witness_eval_batch) X(k_bt_commit_v) X(k_repeat_colptr) X(k_repeat_entries) X(k_repeat_coef) X(k_witness_eval_repeat) X(k_witness_ck_verify) X(k_witness_ck_verify_batch) \
     X(k_join_colptr) X(k_join_entries) X(k_join_coef) X(k_witness_eval_join) X(k_witness_ck_verify_join) X(k_input_slots) X(k_input_slots_join) \
-    X(k_mimc_sponge) X(k_merkle_leaves) X(k_merkle_level) X(k_merkle_top) X(k_merkle_level_list) X(k_merkle_set_leaves) X(k_merkle_paths) X(k_merkle_export) \
+    X(k_mimc_sponge) X(k_merkle_leaves) X(k_merkle_level) X(k_merkle_top) X(k_merkle_level_list) X(k_merkle_set_leaves) X(k_merkle_paths) X(k_merkle_export) X(k_merkle_fill_empty) X(k_merkle_level_range) X(k_merkle_climb) \
     X(k_rowview_count) X(k_rowview_fill) X(k_rowview_long) X(k_check_mul) X(k_check_rows) X(k_check_rows_long) X(k_check_count) \
     X(k_vw_exp) X(k_vw_tails) X(k_vw_flatten) X(k_vw_small) X(k_vw_scalars) X(k_vw_reduce)
 enum KernelId {
@@ -241,7 +242,7 @@ struct Engine::Impl {
     std::vector<Event> prof_pool;
     double prof_ms[KID_COUNT] = {0};
     std::vector<float> prof_wit_ms;     // the first 1024 k_witness_eval / k_witness_eval_repeat / k_witness_eval_join launches since the last reset, in launch order (a launch = a level of an assign)
-    std::vector<std::pair<int, float>> prof_merkle_ms;   // the first 512 launches of the tree-hashing kernels (k_merkle_level, _top, _level_list) since the last reset, in launch order
+    std::vector<std::pair<int, float>> prof_merkle_ms;   // the first 512 launches of the tree-hashing kernels (k_merkle_level, _top, _level_list, _level_range, _climb) since the last reset, in launch order
     uint64_t prof_count[KID_COUNT] = {0};
     double prof_alg_bytes[KID_COUNT] = {0}, prof_act_bytes[KID_COUNT] = {0}, prof_fm[KID_COUNT] = {0};
     bool prof_on(int id) const { return prof_mode == 2 || (prof_mode == 1 && (id == KID_k_fold_points || id == KID_k_fold_points_reg || id == KID_k_fold_points_split || id == KID_k_fold_points_wnaf || id == KID_k_fold_points_quad || id == KID_k_fold_points_quadw || id == KID_k_fold_points_regw || id == KID_k_bucket_chunks)); }
@@ -252,7 +253,7 @@ struct Engine::Impl {
     void prof_collect() {
         if (prof_open.empty()) return;
         HIPCHK(hipStreamSynchronize(st));
-        for (ProfRec &r : prof_open) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, r.a, r.b)); prof_ms[r.id] += ms; prof_count[r.id]++; if ((r.id == KID_k_witness_eval || r.id == KID_k_witness_eval_repeat || r.id == KID_k_witness_eval_join) && prof_wit_ms.size() < 1024) prof_wit_ms.push_back(ms); if ((r.id == KID_k_merkle_level || r.id == KID_k_merkle_top || r.id == KID_k_merkle_level_list) && prof_merkle_ms.size() < 512) prof_merkle_ms.emplace_back(r.id, ms); prof_pool.push_back(std::move(r.a)); prof_pool.push_back(std::move(r.b)); }
+        for (ProfRec &r : prof_open) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, r.a, r.b)); prof_ms[r.id] += ms; prof_count[r.id]++; if ((r.id == KID_k_witness_eval || r.id == KID_k_witness_eval_repeat || r.id == KID_k_witness_eval_join) && prof_wit_ms.size() < 1024) prof_wit_ms.push_back(ms); if ((r.id == KID_k_merkle_level || r.id == KID_k_merkle_top || r.id == KID_k_merkle_level_list || r.id == KID_k_merkle_level_range || r.id == KID_k_merkle_climb) && prof_merkle_ms.size() < 512) prof_merkle_ms.emplace_back(r.id, ms); prof_pool.push_back(std::move(r.a)); prof_pool.push_back(std::move(r.b)); }
         prof_open.clear();
     }
     void prof_reset() { prof_collect(); for (int i = 0; i < KID_COUNT; i++) { prof_ms[i] = 0; prof_count[i] = 0; prof_alg_bytes[i] = prof_act_bytes[i] = prof_fm[i] = 0; } prof_wit_ms.clear(); prof_merkle_ms.clear(); }
@@ -3940,11 +3941,29 @@ const std::vector<Scalar> &mimc_round_constants();      // host/gadgets.hpp (def
 struct DeviceMerkle {
     Engine *owner = nullptr; uint32_t depth = 0;
     DevBuf tree;            // 2^(depth+1) scm in heap order, Montgomery form; entry 0 is unused
+    // leaves [0, size) are the caller's, leaves [size, 2^depth) hold `empty` (bpg_merkle_build: size = 2^depth, empty = 0)
+    uint64_t size = 0;
+    scm empty = sc_zero();
+    std::vector<scm> empty_nodes;       // E_0 .. E_depth, host copy; a tree of bpg_merkle_build computes it when bpg_merkle_empty_nodes first asks
 };
 
 namespace {
 void merkle_orphan(DeviceMerkle *t) { t->tree.release(); t->owner = nullptr; }
 constexpr uint32_t kMerkleMaxDepth = 24;
+static_assert(MERKLE_MAX_DEPTH == kMerkleMaxDepth && MERKLE_CLIMB_PARENTS == BPG_MERKLE_TOP_PARENTS, "host/merkle_plan.hpp plans for the kernels of hip/k_mimc.cuh");
+// E_0 = empty, E_{k+1} = node(E_k, E_k) with the BPG_HD arithmetic of hip/k_mimc.cuh on the host: ~53 us a node, where the device pays a latency floor each
+std::vector<scm> merkle_empty_chain(uint32_t depth, const scm &empty) {
+    static const std::vector<scm> rc = [] {
+        const std::vector<Scalar> &plain = mimc_round_constants();
+        std::vector<scm> h(plain.size());
+        for (size_t i = 0; i < plain.size(); i++) h[i] = to_scm(plain[i]);
+        return h;
+    }();
+    std::vector<scm> E(depth + 1);
+    E[0] = empty;
+    for (uint32_t k = 0; k < depth; k++) E[k + 1] = mimc_node(E[k], E[k], rc.data());
+    return E;
+}
 constexpr uint64_t kSpongeMaxBlocks = 1ull << 22;                  // blocks of one item: 128 MB of input, what one piece of a call stages
 constexpr double kNodeProducts = 4.0 * BPG_MIMC_ROUNDS;             // Montgomery products of one two-block node
 // the round constants of the context's device, converted and uploaded by the first context that asks
@@ -4003,7 +4022,7 @@ DeviceMerkle *Engine::merkle_build(uint32_t depth, const uint8_t *leaves) {
     if (bytes + (64u << 20) > free_b)             // the tree and some room to work in: a failed 1 GB hipMalloc is a worse way to find out
         throw DeviceError("merkle_build: a tree of depth " + std::to_string(depth) + " takes " + std::to_string(bytes >> 20) + " MB and the device has " + std::to_string(free_b >> 20) + " MB free");
     std::unique_ptr<DeviceMerkle> t(new DeviceMerkle());
-    t->owner = this; t->depth = depth;
+    t->owner = this; t->depth = depth; t->size = nleaves;
     try {
         t->tree.ensure(bytes);
         scm *tree = t->tree.as<scm>();
@@ -4023,6 +4042,95 @@ DeviceMerkle *Engine::merkle_build(uint32_t depth, const uint8_t *leaves) {
     } catch (...) { (void)hipStreamSynchronize(I.st); throw; }         // (the tree goes with `t`, after this wait)
     I.trees.push_back(t.get());
     return t.release();
+}
+
+namespace {
+// New leaves into place as merkle_build puts them there (a copy, then k_merkle_leaves on that interval), then the launches of the plan: the wide steps
+// bottom-up and the climb.  Nothing else hashes a growing tree.
+void merkle_grow(Engine::Impl &I, scm *tree, const MerkleGrowPlan &P, const uint8_t *leaves, const scm *rc) {
+    const uint64_t count = P.new_size - P.old_size;
+    if (!count) return;
+    scm *at = tree + (1ull << P.depth) + P.old_size;
+    HIPCHK(hipMemcpyAsync(at, leaves, (size_t)count * 32, hipMemcpyHostToDevice, I.st));
+    BPG_LAUNCH(I, k_merkle_leaves, dim3(cdiv(count, 256)), dim3(256), at, (uint32_t)count);
+    for (uint32_t k = 0; k < P.n_wide; k++) {
+        const MerkleWideStep &w = P.wide[k];
+        BPG_LAUNCH(I, k_merkle_level_range, dim3(cdiv(w.count, 256)), dim3(256), tree, w.first, w.count, rc);
+        note_nodes(I, KID_k_merkle_level_range, w.count);
+    }
+    if (!P.climb || P.climb_lo < 2 || P.climb_hi < P.climb_lo || (P.climb_hi >> 1) - (P.climb_lo >> 1) >= BPG_MERKLE_TOP_PARENTS)
+        throw std::logic_error("merkle plan: new leaves without a climb that fits one block");
+    BPG_LAUNCH(I, k_merkle_climb, dim3(1), dim3(256), tree, P.climb_lo, P.climb_hi, rc);
+    note_nodes(I, KID_k_merkle_climb, P.climb_evals);
+    HIPCHK(hipGetLastError());
+}
+}  // namespace
+
+DeviceMerkle *Engine::merkle_build_partial(uint32_t depth, uint64_t size, const uint8_t *leaves, const uint8_t *empty) {
+    if (depth < 1 || depth > kMerkleMaxDepth) throw std::invalid_argument("merkle_build_partial: depth must be 1..24");
+    if (size > (1ull << depth)) throw std::invalid_argument("merkle_build_partial: more leaves than 2^depth");
+    if (size && !leaves) throw std::invalid_argument("merkle_build_partial: null leaves");
+    const MerkleGrowPlan P = plan_merkle_grow(depth, 0, size);
+    std::unique_ptr<DeviceMerkle> t(new DeviceMerkle());
+    t->owner = this; t->depth = depth; t->size = size;
+    if (empty) { uint32_t w[8]; std::memcpy(w, empty, 32); t->empty = sc_from_words(w); }
+    t->empty_nodes = merkle_empty_chain(depth, t->empty);
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    const scm *rc = mimc_rc(I, device_);
+    const size_t bytes = ((size_t)2 << depth) * sizeof(scm);
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    if (bytes + (64u << 20) > free_b)
+        throw DeviceError("merkle_build_partial: a tree of depth " + std::to_string(depth) + " takes " + std::to_string(bytes >> 20) + " MB and the device has " + std::to_string(free_b >> 20) + " MB free");
+    try {
+        t->tree.ensure(bytes);
+        scm *tree = t->tree.as<scm>();
+        I.mk_in.ensure(t->empty_nodes.size() * sizeof(scm));
+        HIPCHK(hipMemsetAsync(tree, 0, sizeof(scm), I.st));             // entry 0 is no node
+        HIPCHK(hipMemcpyAsync(I.mk_in.p, t->empty_nodes.data(), t->empty_nodes.size() * sizeof(scm), hipMemcpyHostToDevice, I.st));
+        // every empty subtree first, the root included when there is no leaf: the rightmost occupied node of a level may read an empty right child
+        BPG_LAUNCH(I, k_merkle_fill_empty, dim3(cdiv(2ull << depth, 256)), dim3(256), tree, depth, (uint32_t)size, I.mk_in.as<scm>());
+        I.prof_note(KID_k_merkle_fill_empty, (double)bytes, (double)bytes, 0.0);
+        merkle_grow(I, tree, P, leaves, rc);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(I.st));
+    } catch (...) { (void)hipStreamSynchronize(I.st); throw; }
+    I.trees.push_back(t.get());
+    return t.release();
+}
+
+void Engine::merkle_append(DeviceMerkle *t, uint64_t count, const uint8_t *leaves, uint64_t *first_index_out, uint8_t *root_out) {
+    if (!t || t->owner != this) throw std::invalid_argument("merkle_append: not a tree of this context");
+    if (count > (1ull << t->depth) - t->size) throw std::invalid_argument("merkle_append: the tree holds " + std::to_string(t->size) + " of 2^" + std::to_string(t->depth) + " leaves: no room for " + std::to_string(count) + " more");
+    if (count && !leaves) throw std::invalid_argument("merkle_append: null leaves");
+    const uint64_t first = t->size;
+    if (count) {
+        const MerkleGrowPlan P = plan_merkle_grow(t->depth, first, first + count);
+        HIPCHK(hipSetDevice(device_));
+        Impl &I = *impl_;
+        const scm *rc = mimc_rc(I, device_);
+        try {
+            merkle_grow(I, t->tree.as<scm>(), P, leaves, rc);
+            HIPCHK(hipStreamSynchronize(I.st));
+        } catch (...) { (void)hipStreamSynchronize(I.st); throw; }
+        t->size = first + count;
+    }
+    if (first_index_out) *first_index_out = first;          // before the read-back: should that fail on the device, the leaves are in and the caller knows where
+    if (root_out) merkle_nodes(t, 0, 0, 1, root_out);
+}
+
+void Engine::merkle_size(DeviceMerkle *t, uint64_t *size_out, uint32_t *depth_out) {
+    if (!t || t->owner != this) throw std::invalid_argument("merkle_size: not a tree of this context");
+    if (size_out) *size_out = t->size;
+    if (depth_out) *depth_out = t->depth;
+}
+
+void Engine::merkle_empty_nodes(DeviceMerkle *t, uint8_t *out) {
+    if (!t || t->owner != this) throw std::invalid_argument("merkle_empty_nodes: not a tree of this context");
+    if (!out) throw std::invalid_argument("merkle_empty_nodes: null output");
+    if (t->empty_nodes.empty()) t->empty_nodes = merkle_empty_chain(t->depth, t->empty);
+    for (size_t k = 0; k < t->empty_nodes.size(); k++) { uint32_t w[8]; sc_to_words(w, t->empty_nodes[k]); std::memcpy(out + 32 * k, w, 32); }
 }
 
 // The tree's memory is released on the context that built it, whichever caller frees it; a tree whose context is gone already (the destructor released its
@@ -4092,7 +4200,7 @@ void Engine::merkle_update(DeviceMerkle *t, uint64_t count, const uint64_t *indi
     // every check first: a refused call leaves the tree as it was
     std::vector<uint32_t> cur(count);
     for (uint64_t i = 0; i < count; i++) {
-        if (indices[i] >> d) throw std::invalid_argument("merkle_update: leaf index " + std::to_string(indices[i]) + " is beyond 2^depth");
+        if (indices[i] >= t->size) throw std::invalid_argument("merkle_update: leaf index " + std::to_string(indices[i]) + " is beyond the " + std::to_string(t->size) + " leaves the tree holds");     // (a full tree: 2^depth)
         cur[i] = (uint32_t)indices[i];
     }
     // one staging buffer: [new leaves, 32 bytes each | their indices | the parents to recompute, level d-1 first: heap indices, sorted, each once]

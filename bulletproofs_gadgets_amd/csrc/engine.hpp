@@ -293,7 +293,14 @@ public:
     void merkle_nodes(DeviceMerkle *t, uint32_t level, uint64_t first, uint64_t count, uint8_t *out);      // level 0 = the root, level depth = the leaves
     // count x depth x 32, the leaf's sibling first; ancestors (bpg_merkle_path_nodes): the nodes ON each path instead, the leaf's parent first, the root last
     void merkle_paths(DeviceMerkle *t, uint64_t count, const uint64_t *indices, uint8_t *siblings_out, bool ancestors = false);
-    void merkle_update(DeviceMerkle *t, uint64_t count, const uint64_t *indices, const uint8_t *leaves);   // distinct indices; only their ancestors are recomputed
+    void merkle_update(DeviceMerkle *t, uint64_t count, const uint64_t *indices, const uint8_t *leaves);   // distinct indices below the tree's size; only their ancestors are recomputed
+    // A tree that grows: capacity 2^depth, `size` leaves, the rest `empty` (NULL = zero) - node for node the full tree over leaves || empty x (2^depth - size).
+    // The empty subtrees are constants the host computes and k_merkle_fill_empty writes; only the ancestors of real leaves are hashed, by the launches of
+    // host/merkle_plan.hpp and by nothing else.  append puts leaves at [size, size + count) and recomputes exactly their ancestors, each once.
+    DeviceMerkle *merkle_build_partial(uint32_t depth, uint64_t size, const uint8_t *leaves, const uint8_t *empty);
+    void merkle_append(DeviceMerkle *t, uint64_t count, const uint8_t *leaves, uint64_t *first_index_out, uint8_t *root_out);
+    void merkle_size(DeviceMerkle *t, uint64_t *size_out, uint32_t *depth_out);
+    void merkle_empty_nodes(DeviceMerkle *t, uint8_t *out);         // (depth + 1) x 32: out[k] = an empty subtree k levels above the leaves; host only
     static void merkle_free(DeviceMerkle *t);       // on the tree's own context; a tree that outlived its context lost its memory then and is only deleted
     void synchronize();
     // HIP-event profile on the engine's own stream: mode 0 off, 1 = dominant kernel (k_fold_points) only, 2 = all kernels

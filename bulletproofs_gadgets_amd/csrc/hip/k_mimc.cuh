@@ -92,6 +92,44 @@ __global__ void __launch_bounds__(256) k_merkle_level_list(scm *tree, const uint
     const scm left = tree[2 * h], right = tree[2 * h + 1];
     tree[h] = mimc_node(left, right, rc);
 }
+// Trees that grow (bpg_merkle_build_partial, bpg_merkle_append): capacity 2^depth, `size` leaves, and every leaf from `size` on holds one `empty` value.  A
+// subtree without a leaf is then one of depth + 1 constants - E[0] = empty, E[s + 1] = node(E[s], E[s]) - which the host computes (a chain of `depth`
+// nodes is `depth` latency floors here and a millisecond there) and this kernel writes wherever they belong: one lane per heap node h >= 1; with L the
+// level of h, j = h - 2^L its place in the level and s = depth - L its height, the subtree of h holds leaves [j 2^s, (j + 1) 2^s), so it is empty exactly
+// when j >= ceil(size / 2^s).  Occupied nodes are left alone.  32 bytes per lane in two 16-byte stores; entry 0 of the array is no node.
+__global__ void __launch_bounds__(256) k_merkle_fill_empty(scm *tree, uint32_t depth, uint32_t size, const scm *__restrict__ E) {
+    const uint32_t h = blockIdx.x * blockDim.x + threadIdx.x;          // depth <= 24: the heap has at most 2^25 nodes, size <= 2^24
+    if (h < 1u || h >= (2u << depth)) return;
+    const uint32_t L = 31u - (uint32_t)__clz((int)h), j = h - (1u << L), s = depth - L;
+    if (j < ((size + (1u << s) - 1u) >> s)) return;
+    const uint4 *src = reinterpret_cast<const uint4 *>(E[s].v);
+    const uint4 a = src[0], b = src[1];
+    uint4 *dst = reinterpret_cast<uint4 *>(tree[h].v);
+    dst[0] = a; dst[1] = b;
+}
+// the node function of k_merkle_level over an interval of one level: lane t < count computes heap node first + t from its two children
+__global__ void __launch_bounds__(256) k_merkle_level_range(scm *tree, uint32_t first, uint32_t count, const scm *__restrict__ rc) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count) return;
+    const uint32_t h = first + t;
+    const scm left = tree[2 * h], right = tree[2 * h + 1];
+    tree[h] = mimc_node(left, right, rc);
+}
+// From the dirty children [lo, hi] of one level (2 <= lo <= hi, both of that level, at most BPG_MERKLE_TOP_PARENTS parents above them) to the root in one
+// launch of ONE 256-lane block, as k_merkle_top goes: per level the interval halves, lane t <= hi - lo computes node lo + t, and a block barrier that every
+// lane reaches separates the levels - the loads and the store are guarded, the barrier is not.  lo and hi are kernel arguments, so the trip count is
+// uniform; an interval never widens on the way up.  The loop ends with the root (lo == hi == 1).
+__global__ void __launch_bounds__(256) k_merkle_climb(scm *tree, uint32_t lo, uint32_t hi, const scm *__restrict__ rc) {
+    do {
+        lo >>= 1; hi >>= 1;
+        if (threadIdx.x <= hi - lo) {
+            const uint32_t h = lo + threadIdx.x;
+            const scm left = tree[2 * h], right = tree[2 * h + 1];
+            tree[h] = mimc_node(left, right, rc);
+        }
+        __syncthreads();
+    } while (lo > 1u);
+}
 // new leaves of an update: leaf index[i] = raw[i] (32 bytes, any 256-bit value) in Montgomery form; the indices are distinct
 __global__ void __launch_bounds__(256) k_merkle_set_leaves(scm *tree, uint32_t depth, const uint32_t *__restrict__ index, const uint32_t *__restrict__ raw, uint32_t count) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -37,7 +37,9 @@
 //       MiMC sponges, Merkle trees       (k_mimc.cuh; no row of the survey: the native hash in front of Prover::commit) k_mimc_sponge: one lane per item; a tree of 2^d leaves in
 //                                       one heap-ordered array: k_merkle_leaves, k_merkle_level (one launch per level, one lane per parent), k_merkle_top (the levels of at
 //                                       most 256 parents in one launch), k_merkle_level_list + k_merkle_set_leaves (leaf updates: the ancestors only), k_merkle_paths
-//                                       (sibling lists, or the nodes on the paths), k_merkle_export (nodes as bytes)
+//                                       (sibling lists, or the nodes on the paths), k_merkle_export (nodes as bytes); trees that grow (capacity 2^d, n leaves):
+//                                       k_merkle_fill_empty (the empty-subtree constants, once per build), k_merkle_level_range (an interval of one level),
+//                                       k_merkle_climb (from at most 256 dirty parents to the root in one launch) - launched from host/merkle_plan.hpp
 //       R1CS check                       (k_check.cuh; bpg_r1cs_check: which multiplier, which constraint does the resident witness break) the row-major view of the resident
 //                                       matrix, once per circuit: k_rowview_count, k_scan_blocksums / _apply, k_rowview_fill, k_rowview_long; per check: k_check_mul (a lane
 //                                       per multiplier), k_check_rows (a lane per short row, the wave's ballot = one word of the violation bitmap), k_check_rows_long (a

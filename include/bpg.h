@@ -995,17 +995,42 @@ bpg_status bpg_be_to_scalars(const uint8_t *be, uint64_t len, uint8_t *out, uint
  *                          may be given more than once.
  *   bpg_merkle_update      replaces leaf indices[i] by leaves[i] and recomputes only the ancestors of the replaced leaves, level by level, each once.  The indices
  *                          of one call are distinct: a repeated index is refused (there is no "last one wins"), and a refused call leaves the tree as it was.
+ *                          An index at or above the tree's size (below) is refused; for a tree of bpg_merkle_build that is 2^depth.
+ * Trees that grow - an accumulator of fixed depth (the path circuit is a template of one depth) whose n leaves arrive over time:
+ *   bpg_merkle_build_partial  a tree of capacity 2^depth (depth 1..24, the memory check of bpg_merkle_build) holding `size` <= 2^depth leaves; every leaf from
+ *                          `size` on holds `empty` (any 256-bit value taken mod l, as a leaf is; NULL = zero).  The layout rule: every node of the resident
+ *                          array equals the node of bpg_merkle_build over leaves || empty x (2^depth - size), so root, nodes, paths and path_nodes serve
+ *                          it unchanged and no circuit, template or verifier can tell.  A subtree without a leaf is one of depth + 1 constants, E_0 = empty,
+ *                          E_{k+1} = node(E_k, E_k), computed on the host and written by one bandwidth-bound kernel; only the ancestors of real leaves
+ *                          are hashed.  size may be 0 (leaves may then be NULL): the root is E_depth and no node function runs on the device.
+ *   bpg_merkle_append      puts `count` leaves at [size, size + count) and recomputes exactly the ancestors of the new leaves, each once: one launch per
+ *                          level whose dirty range holds more than 256 parents, then ONE launch from there to the root.  *first_index_out = the old size,
+ *                          root_out = the new root (either may be NULL).  count == 0 is BPG_OK and only fills the outputs.  A tree of bpg_merkle_build
+ *                          has size 2^depth: it takes no append.
+ *   bpg_merkle_size        the number of leaves and the depth (either output may be NULL, not both).
+ *   bpg_merkle_empty_nodes E_0 .. E_depth as (depth + 1) x 32 canonical bytes: out[k] = an empty subtree k levels above the leaves - the sibling a path meets
+ *                          wherever it borders the empty region.  Works on every tree (bpg_merkle_build: empty = 0, computed at the first call); no device work.
+ * size > 2^depth, size + count > 2^depth and a NULL `leaves` with a non-zero count are BPG_ERR_INVALID_ARGUMENT like the rest below; a refused
+ * bpg_merkle_build_partial sets *out to NULL, and a refused call leaves the tree as it was and writes no output.
  * A depth of 0 or above 24, a NULL pointer, an index >= 2^depth, a level above depth, nodes beyond a level and count x blocks_per_item == 0 are
  * BPG_ERR_INVALID_ARGUMENT before the device is touched.  The calls run on the context's stream and return synchronised; a tree belongs to the context that built
  * it (another context's tree is BPG_ERR_INVALID_ARGUMENT); like every call on a context they are not re-entrant.  bpg_merkle_free releases the tree on the context
  * that built it, whatever ctx is passed (NULL included).  Destroying a context releases the device memory of the trees it still holds: their handles stay valid
  * for bpg_merkle_free alone, and every other call on them is BPG_ERR_INVALID_ARGUMENT.
- * Out of scope: trees that are not full, the byte-preimage padding of mimc_hash on the device (pad on the host with bpg_be_to_scalars / bpg_mimc_hash's rules
+ * Out of scope: a sparse layout (the array is 2^(depth+1) scalars whatever the size: 1 GB at depth 24), going under the latency floor of a narrow level (a
+ * level narrower than the device still costs one node's 1,944 dependent products: an append of a few leaves is `depth` such floors in one launch), hashing
+ * records into leaves on the device, the byte-preimage padding of mimc_hash on the device (pad on the host with bpg_be_to_scalars / bpg_mimc_hash's rules
  * and hand the blocks over), flags of the file drivers, and a tree spread over more than one GPU.  (Additions to ABI version 7: no struct changes.) */
 typedef struct bpg_merkle bpg_merkle;
 bpg_status bpg_mimc_sponge(const uint8_t *blocks, uint64_t n_blocks, uint8_t out[32]);
 bpg_status bpg_mimc_sponge_many(bpg_ctx *ctx, uint64_t count, uint64_t blocks_per_item, const uint8_t *in, uint8_t *out);
 bpg_status bpg_merkle_build(bpg_ctx *ctx, uint32_t depth, const uint8_t *leaves /* 2^depth x 32 */, bpg_merkle **out);
+bpg_status bpg_merkle_build_partial(bpg_ctx *ctx, uint32_t depth, uint64_t size, const uint8_t *leaves /* size x 32; NULL allowed when size == 0 */,
+                                    const uint8_t empty[32] /* NULL = zero */, bpg_merkle **out);
+bpg_status bpg_merkle_append(bpg_ctx *ctx, bpg_merkle *t, uint64_t count, const uint8_t *leaves /* count x 32 */,
+                             uint64_t *first_index_out /* NULL allowed */, uint8_t root_out[32] /* NULL allowed */);
+bpg_status bpg_merkle_size(bpg_ctx *ctx, bpg_merkle *t, uint64_t *size_out, uint32_t *depth_out /* either may be NULL, not both */);
+bpg_status bpg_merkle_empty_nodes(bpg_ctx *ctx, bpg_merkle *t, uint8_t *out /* (depth + 1) x 32: out[k] = an empty subtree k levels above the leaves */);
 bpg_status bpg_merkle_root(bpg_ctx *ctx, bpg_merkle *t, uint8_t out[32]);
 bpg_status bpg_merkle_nodes(bpg_ctx *ctx, bpg_merkle *t, uint32_t level, uint64_t first, uint64_t count, uint8_t *out);
 bpg_status bpg_merkle_paths(bpg_ctx *ctx, bpg_merkle *t, uint64_t count, const uint64_t *indices, uint8_t *siblings_out /* count x depth x 32 */);
