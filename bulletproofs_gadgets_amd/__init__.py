@@ -23,6 +23,7 @@ FLAG_NO_1PHASE_DOMSEP = 2
 FLAG_EXPANDED_BLINDING = 4      # prover-only opt-in: s_L, s_R expanded from one TranscriptRng draw (include/bpg.h); not upstream's derivation
 VAR_MULTIPLIER_LEFT, VAR_MULTIPLIER_RIGHT, VAR_MULTIPLIER_OUTPUT, VAR_COMMITTED, VAR_ONE = 0, 1, 2, 3, 4
 VAR_INPUT = 5                   # a public input of the proof (Prover.input / Verifier.input): in instances and programs of templates with inputs only
+VAR_GATED = 6                   # input * variable (Prover.gate / Verifier.gate): in instances and programs of templates with gates only
 L = 2**252 + 27742317777372353535851937790883648493
 
 STATUS_NAMES = {0: "OK", 1: "INVALID_GENERATORS_LENGTH", 2: "FORMAT_ERROR", 3: "VERIFICATION_ERROR", 4: "INVALID_ARGUMENT",
@@ -69,6 +70,19 @@ def _checkpoints_cstruct(checkpoints):
 
 
 HINT_BIT_PAIR = 1
+
+
+class WitnessGatesView(C.Structure):
+    """bpg_witness_gates: the gate table of a template - gate k is input gate_input[k] times the variable gate_var[k] (kind 0..3)."""
+    _fields_ = [("n_gates", C.c_uint64), ("gate_var", C.POINTER(C.c_uint32)), ("gate_input", C.POINTER(C.c_uint32))]
+
+
+def _gates_cstruct(gates):
+    """[(Variable of kind 0..3, input index)] -> (bpg_witness_gates, keep-alive)"""
+    n = len(gates)
+    gv = (C.c_uint32 * max(n, 1))(*[int(g[0]) for g in gates])
+    gi = (C.c_uint32 * max(n, 1))(*[int(g[1]) for g in gates])
+    return WitnessGatesView(n, C.cast(gv, C.POINTER(C.c_uint32)), C.cast(gi, C.POINTER(C.c_uint32))), (gv, gi)
 
 
 class CheckReportView(C.Structure):
@@ -548,13 +562,15 @@ class Context:
         finally:
             rc.free()
 
-    def upload_template(self, inst: "FlatInstance", program: "WitnessProgram", hints: "WitnessHints" = None, checkpoints=None, inputs=None):
+    def upload_template(self, inst: "FlatInstance", program: "WitnessProgram", hints: "WitnessHints" = None, checkpoints=None, inputs=None, gates=None):
         """bpg_r1cs_upload_template: the instance (with or without a witness) plus its witness program; ResidentCircuit.assign gives it fresh witnesses.
         hints (a circuit with range proofs, Prover.witness_program(hints=True)): bpg_r1cs_upload_template_hinted.
         checkpoints (bpg_r1cs_upload_template_checkpointed): multiplier Variables whose values the caller hands to assign(..., checkpoints=values); the
         segments that read them stop waiting for the ones that compute them.
         inputs (bpg_r1cs_upload_template_inputs; an instance from Prover.template_instance): the values of the public inputs the instance and the program
-        name (kind VAR_INPUT), as many as the template is to take with every assign(..., inputs=values); an int: that many, for an instance without a witness."""
+        name (kind VAR_INPUT), as many as the template is to take with every assign(..., inputs=values); an int: that many, for an instance without a witness.
+        gates (bpg_r1cs_upload_template_gated; Prover.gates()): [(gated Variable, input index)], the table the terms of kind VAR_GATED in the instance and
+        the program name.  Such a template is served by assign, prove, verify, set_inputs, check, prove_batch_inputs and verify_batch; repeat and join refuse it."""
         h = C.c_void_p()
         cs, cp = inst.cstruct(), program.cstruct()
         n_in = 0 if inputs is None else inputs if isinstance(inputs, int) else (len(inputs) // 32 if isinstance(inputs, (bytes, bytearray)) else len(inputs))
@@ -564,9 +580,18 @@ class Context:
                 cs.aL = cs.aR = cs.aO = None
             ch = hints.cstruct() if hints is not None and len(hints) else None
             ck = _checkpoints_cstruct(checkpoints or [])
-            _chk(lib().bpg_r1cs_upload_template_inputs(self._h, C.byref(cs), C.byref(cp), C.byref(ch) if ch is not None else None, C.byref(ck),
-                                                       C.c_uint64(n_in), iv, C.byref(h)))
-            return ResidentCircuit(self, h, inst.n, inst.m, n_params=len(program.param_rows), q=inst.q, n_ck=len(checkpoints or []), n_inputs=n_in)
+            if gates:
+                gs, _keep = _gates_cstruct(gates)
+                _chk(lib().bpg_r1cs_upload_template_gated(self._h, C.byref(cs), C.byref(cp), C.byref(ch) if ch is not None else None, C.byref(ck),
+                                                          C.c_uint64(n_in), iv, C.byref(gs), C.byref(h)))
+            else:
+                _chk(lib().bpg_r1cs_upload_template_inputs(self._h, C.byref(cs), C.byref(cp), C.byref(ch) if ch is not None else None, C.byref(ck),
+                                                           C.c_uint64(n_in), iv, C.byref(h)))
+            rc = ResidentCircuit(self, h, inst.n, inst.m, n_params=len(program.param_rows), q=inst.q, n_ck=len(checkpoints or []), n_inputs=n_in)
+            rc.n_gates = len(gates or [])
+            return rc
+        if gates:
+            raise BpgError(4, "upload_template: gates without public inputs (a gate is input * variable)")
         if checkpoints is not None and len(checkpoints):
             ch = hints.cstruct() if hints is not None and len(hints) else None
             ck = _checkpoints_cstruct(checkpoints)
@@ -700,6 +725,12 @@ class MerkleTree:
         _chk(lib().bpg_merkle_path_nodes(self.ctx._h, self._handle(), C.c_uint64(k), (C.c_uint64 * max(k, 1))(*indices), out))
         raw = out.raw
         return [[raw[32 * (i * d + j):32 * (i * d + j) + 32] for j in range(d)] for i in range(k)]
+
+    def path_inputs(self, indices):
+        """The public inputs of a MerklePath256 template for every leaf index: paths() and root() through merkle_path_inputs, one list of 4 * depth + 1
+        scalars per index - what assign(inputs=), prove_batch_inputs and verify_batch take."""
+        root = self.root()
+        return [merkle_path_inputs(i, sib, root) for i, sib in zip(indices, self.paths(indices))]
 
     def update(self, indices, leaves):
         """Replace leaf indices[i] by leaves[i] (distinct indices) and recompute their ancestors."""
@@ -1851,6 +1882,20 @@ class Prover:
         self._n_inputs = getattr(self, "_n_inputs", 0) + 1
         return Variable(var.value)
 
+    def gate(self, x: "Variable", var: "Variable") -> "Variable":
+        """bpg_prover_gate: the variable whose value is x * var (kind VAR_GATED) - x a public input of this prover, var a multiplier variable or a committed
+        value.  Named in linear combinations like any variable; prove() and instance() see (var, coefficient * x), template() keeps the gate and every
+        assign brings x: ONE template for circuits that differ in which terms are switched on (MerklePath256: a path for every leaf index)."""
+        out = C.c_uint32()
+        _chk(lib().bpg_prover_gate(self._h, C.c_uint32(int(x)), C.c_uint32(int(var)), C.byref(out)))
+        return Variable(out.value)
+
+    def gates(self):
+        """bpg_prover_gates: the gate table -> [(gated Variable, input index)], in the order gate() made them."""
+        gv = WitnessGatesView()
+        _chk(lib().bpg_prover_gates(self._h, C.byref(gv)))
+        return [(Variable(gv.gate_var[k]), int(gv.gate_input[k])) for k in range(gv.n_gates)]
+
     def template_instance(self):
         """bpg_prover_template_instance -> (FlatInstance whose rows keep their input terms, the values of the inputs in input order)."""
         view, v, vb, n_in, iv = R1CSInstance(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_void_p()
@@ -1912,7 +1957,7 @@ class Prover:
             raise BpgError(4, "template: no device context")
         if getattr(self, "_n_inputs", 0):       # public inputs: the rows keep their input terms, and assign(..., inputs=) brings the values
             inst, values = self.template_instance()
-            return ctx.upload_template(inst, prog, hints, checkpoints=list(checkpoints), inputs=values)
+            return ctx.upload_template(inst, prog, hints, checkpoints=list(checkpoints), inputs=values, gates=self.gates() or None)       # (a gadget may have made the gates: ask the prover)
         return ctx.upload_template(self.instance(), prog, hints, checkpoints=list(checkpoints))
 
     def start_blinding(self, rng_seed: bytes = None, max_multipliers: int = 1 << 20):
@@ -1960,6 +2005,12 @@ class Verifier:
         var = C.c_uint32()
         _chk(lib().bpg_verifier_input(self._h, _exact("value", value, 32), C.byref(var)))
         return Variable(var.value)
+
+    def gate(self, x: "Variable", var: "Variable") -> "Variable":
+        """bpg_verifier_gate: the verifier's side of Prover.gate - the same gates in the same order."""
+        out = C.c_uint32()
+        _chk(lib().bpg_verifier_gate(self._h, C.c_uint32(int(x)), C.c_uint32(int(var)), C.byref(out)))
+        return Variable(out.value)
 
     def get_num_vars(self): return lib().bpg_verifier_num_vars(self._h)
 
@@ -2142,6 +2193,35 @@ class MerkleTree256(Gadget):
         _chk(lib().bpg_merkle_tree256_new(C.byref(r), iv, C.c_uint64(len(instance_vars)), wv, C.c_uint64(len(witness_vars)),
                                           pattern.encode(), C.byref(h)))
         super().__init__(h)
+
+
+class MerklePath256(Gadget):
+    """A Merkle path whose leaf index is a public input: ONE circuit (and one template) for every leaf of a tree of depth len(levels).
+    levels[j] = (nb_j, b_j, c1_j, c2_j): four Variables from Prover.input / Verifier.input per level, bottom level first; leaf: the leaf's Variable (a
+    committed value or a multiplier variable); root: a linear combination (the last input).  With the input values of merkle_path_inputs it is
+    MerkleTree256 for that index's pattern with instance siblings, proof for proof.  It makes gates: prove() / verify() on a Prover / Verifier, no buffer.
+    A verifier must build the input values with merkle_path_inputs (or MerkleTree.path_inputs) from an index and siblings: arbitrary values state
+    something else than membership."""
+    def __init__(self, root, leaf, levels):
+        h = C.c_void_p()
+        r = LinearCombination.of(root)._c()
+        flat = [int(v) for lv in levels for v in lv]
+        if len(flat) != 4 * len(levels):
+            raise ValueError("a level is (nb, b, c1, c2)")
+        arr = (C.c_uint32 * max(len(flat), 1))(*flat)
+        _chk(lib().bpg_merkle_path256_new(C.byref(r), C.c_uint32(int(leaf)), arr, C.c_uint64(len(levels)), C.byref(h)))
+        super().__init__(h)
+
+
+def merkle_path_inputs(index, siblings, root):
+    """bpg_merkle_path_inputs: the 4 * depth + 1 public inputs of MerklePath256 for leaf `index` with `siblings` (bottom level first, as MerkleTree.paths
+    gives them) under `root`: per level (1 - b, b, sibling if b else 0, 0 if b else sibling) with b = bit j of the index, then the root."""
+    d = len(siblings)
+    out = _buf(32 * (4 * d + 1))
+    sib = b"".join(_exact("sibling", x, 32) for x in siblings)
+    _chk(lib().bpg_merkle_path_inputs(C.c_uint64(index), sib if d else None, C.c_uint64(d), _exact("root", root, 32), out))
+    raw = out.raw
+    return [raw[32 * k:32 * k + 32] for k in range(4 * d + 1)]
 
 
 class Equality(Gadget):

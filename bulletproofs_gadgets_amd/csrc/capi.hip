@@ -111,9 +111,9 @@ void Prover::start_blinding(const uint8_t rng_seed[32], uint64_t max_multipliers
 // ---------------------------------------------------------------------------------------- handles
 struct bpg_ctx { Engine *engine; };
 struct bpg_merkle { DeviceMerkle *t; };
-struct bpg_circuit { DeviceCircuit *dc; uint64_t n, m; bool is_template = false; uint64_t n_params = 0; uint64_t n_ck = 0; uint64_t n_in = 0; };     // dc == nullptr: bpg_test_circuit_handle
+struct bpg_circuit { DeviceCircuit *dc; uint64_t n, m; bool is_template = false; uint64_t n_params = 0; uint64_t n_ck = 0; uint64_t n_in = 0; uint64_t n_gates = 0; };     // dc == nullptr: bpg_test_circuit_handle
 struct bpg_transcript { Transcript t; };
-struct bpg_prover { Prover *p; FlatCircuit flat; std::vector<uint8_t> v_bytes, vb_bytes, in_bytes; WitnessProgram program; };
+struct bpg_prover { Prover *p; FlatCircuit flat; std::vector<uint8_t> v_bytes, vb_bytes, in_bytes; WitnessProgram program; std::vector<uint32_t> gate_var, gate_input; };
 struct bpg_verifier { Verifier *v; FlatCircuit flat; };
 struct bpg_gadget { std::unique_ptr<Gadget> g; };
 struct bpg_buffer { OpBuffer b; };
@@ -136,7 +136,7 @@ static LinearCombination lc_from(const bpg_lc *lc) {
     REQUIRE(lc && (lc->n == 0 || lc->terms));
     LinearCombination out;
     for (uint64_t i = 0; i < lc->n; i++) {
-        if ((lc->terms[i].var >> 29) > BPG_VAR_INPUT) throw std::invalid_argument("linear combination holds an unknown variable kind");
+        if ((lc->terms[i].var >> 29) > BPG_VAR_GATED) throw std::invalid_argument("linear combination holds an unknown variable kind");
         out.terms.emplace_back(Variable::unpack(lc->terms[i].var), Scalar::from_bits(lc->terms[i].coeff));
     }
     return out;
@@ -340,6 +340,8 @@ static WitnessProgramView program_view(const bpg_witness_program *w, const bpg_w
     if (k) { v.n_ck = k->n_checkpoints; v.ck_var = k->vars; }
     return v;
 }
+static WitnessProgramView program_view_inputs(const bpg_witness_program *w, const bpg_witness_hints *h, const bpg_witness_checkpoints *k, uint64_t n_inputs,
+                                              const bpg_witness_gates *g);
 bpg_status bpg_r1cs_upload_template(bpg_ctx *ctx, const bpg_r1cs_instance *inst, const bpg_witness_program *program, bpg_circuit **out) {
     return bpg_r1cs_upload_template_hinted(ctx, inst, program, nullptr, out);
 }
@@ -353,16 +355,19 @@ bpg_status bpg_r1cs_upload_template_checkpointed(bpg_ctx *ctx, const bpg_r1cs_in
 }
 bpg_status bpg_r1cs_upload_template_inputs(bpg_ctx *ctx, const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
                                            const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, const uint8_t *input_values, bpg_circuit **out) {
+    return bpg_r1cs_upload_template_gated(ctx, inst, program, hints, checkpoints, n_inputs, input_values, nullptr, out);
+}
+bpg_status bpg_r1cs_upload_template_gated(bpg_ctx *ctx, const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                          const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, const uint8_t *input_values,
+                                          const bpg_witness_gates *gates, bpg_circuit **out) {
     return guard([&] {
         REQUIRE(out); *out = nullptr;
         REQUIRE(ctx && inst && program);
         const FlatView f = as_view(inst, false);
-        WitnessProgramView w = program_view(program, hints, checkpoints);
-        if (n_inputs >= (1ull << 29)) throw std::invalid_argument("template: too many public inputs (the variable index has 29 bits)");
-        w.n_inputs = n_inputs;
+        const WitnessProgramView w = program_view_inputs(program, hints, checkpoints, n_inputs, gates);
         const TemplatePlan plan = Engine::plan_template(f, w, input_values);      // every check, the level cap included, before the context is touched
         DeviceCircuit *dc = ctx->engine->upload_template(f, plan);
-        bpg_circuit *c = new bpg_circuit{dc, f.n, f.m}; c->is_template = true; c->n_params = w.n_params; c->n_ck = w.n_ck; c->n_in = n_inputs;
+        bpg_circuit *c = new bpg_circuit{dc, f.n, f.m}; c->is_template = true; c->n_params = w.n_params; c->n_ck = w.n_ck; c->n_in = n_inputs; c->n_gates = w.n_gates;
         *out = c;
     });
 }
@@ -432,59 +437,84 @@ bpg_status bpg_test_template_schedule_checkpointed(const bpg_r1cs_instance *inst
         std::memcpy(out, r.c_str(), r.size() + 1);
     });
 }
-static WitnessProgramView program_view_inputs(const bpg_witness_program *w, const bpg_witness_hints *h, const bpg_witness_checkpoints *k, uint64_t n_inputs) {
+static WitnessProgramView program_view_inputs(const bpg_witness_program *w, const bpg_witness_hints *h, const bpg_witness_checkpoints *k, uint64_t n_inputs,
+                                              const bpg_witness_gates *g) {
     WitnessProgramView v = program_view(w, h, k);
     if (n_inputs >= (1ull << 29)) throw std::invalid_argument("template: too many public inputs (the variable index has 29 bits)");
     v.n_inputs = n_inputs;
+    if (g && g->n_gates) {
+        if (!g->gate_var || !g->gate_input) throw std::invalid_argument("template: n_gates without gate_var / gate_input");
+        if (!n_inputs) throw std::invalid_argument("template: gates without public inputs (a gate is input * variable)");
+        v.n_gates = g->n_gates; v.gate_var = g->gate_var; v.gate_input = g->gate_input;
+    }
     return v;
 }
-bpg_status bpg_test_template_schedule_inputs(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
-                                             const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, char *out, uint64_t cap) {
+bpg_status bpg_test_template_schedule_gated(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                             const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, const bpg_witness_gates *gates, char *out, uint64_t cap) {
     return guard([&] {
         REQUIRE(inst && program && out && cap);
-        const std::string r = witness_schedule_json(Engine::plan_template(as_view(inst, false, true), program_view_inputs(program, hints, checkpoints, n_inputs)).schedule);
+        const std::string r = witness_schedule_json(Engine::plan_template(as_view(inst, false, true), program_view_inputs(program, hints, checkpoints, n_inputs, gates)).schedule);
         if (r.size() + 1 > cap) throw std::invalid_argument("template_schedule: buffer too small (" + std::to_string(r.size() + 1) + " bytes needed)");
         std::memcpy(out, r.c_str(), r.size() + 1);
     });
 }
-bpg_status bpg_test_template_packed_inputs(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
-                                           const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, uint32_t *stream_out, uint64_t cap, uint64_t *words_out) {
+bpg_status bpg_test_template_schedule_inputs(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                             const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, char *out, uint64_t cap) {
+    return bpg_test_template_schedule_gated(inst, program, hints, checkpoints, n_inputs, nullptr, out, cap);
+}
+bpg_status bpg_test_template_packed_gated(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                           const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, const bpg_witness_gates *gates, uint32_t *stream_out, uint64_t cap, uint64_t *words_out) {
     return guard([&] {
         REQUIRE(inst && program && words_out && (cap == 0 || stream_out));
-        const TemplatePlan T = Engine::plan_template(as_view(inst, false, true), program_view_inputs(program, hints, checkpoints, n_inputs));
+        const TemplatePlan T = Engine::plan_template(as_view(inst, false, true), program_view_inputs(program, hints, checkpoints, n_inputs, gates));
         *words_out = T.packed.stream.size();
         if (cap < T.packed.stream.size()) { if (cap) throw std::invalid_argument("template_packed: buffer too small (" + std::to_string(T.packed.stream.size()) + " words needed)"); return; }
         std::memcpy(stream_out, T.packed.stream.data(), T.packed.stream.size() * 4);
     });
 }
-bpg_status bpg_test_template_eval_inputs(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
-                                         const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, const uint8_t *v, const uint8_t *ck_values,
+bpg_status bpg_test_template_packed_inputs(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                           const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, uint32_t *stream_out, uint64_t cap, uint64_t *words_out) {
+    return bpg_test_template_packed_gated(inst, program, hints, checkpoints, n_inputs, nullptr, stream_out, cap, words_out);
+}
+bpg_status bpg_test_template_eval_gated(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                         const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, const bpg_witness_gates *gates, const uint8_t *v, const uint8_t *ck_values,
                                          const uint8_t *input_values, uint8_t *aL, uint8_t *aR, uint8_t *aO, uint64_t *first_mismatch) {
     return guard([&] {
         REQUIRE(inst && program && aL && aR && aO && first_mismatch && (inst->m == 0 || v));
         REQUIRE(!checkpoints || checkpoints->n_checkpoints == 0 || ck_values);
         if (n_inputs && !input_values) throw std::invalid_argument("template_eval: the program has " + std::to_string(n_inputs) + " public inputs and input_values is null");
-        *first_mismatch = Engine::template_eval_checkpointed_host(as_view(inst, false), program_view_inputs(program, hints, checkpoints, n_inputs), v, ck_values, aL, aR, aO, input_values);
+        *first_mismatch = Engine::template_eval_checkpointed_host(as_view(inst, false), program_view_inputs(program, hints, checkpoints, n_inputs, gates), v, ck_values, aL, aR, aO, input_values);
     });
 }
-bpg_status bpg_test_template_eval_batch_inputs(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
-                                               const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, uint64_t count, const uint8_t *v,
+bpg_status bpg_test_template_eval_inputs(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                         const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, const uint8_t *v, const uint8_t *ck_values,
+                                         const uint8_t *input_values, uint8_t *aL, uint8_t *aR, uint8_t *aO, uint64_t *first_mismatch) {
+    return bpg_test_template_eval_gated(inst, program, hints, checkpoints, n_inputs, nullptr, v, ck_values, input_values, aL, aR, aO, first_mismatch);
+}
+bpg_status bpg_test_template_eval_batch_gated(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                               const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, const bpg_witness_gates *gates, uint64_t count, const uint8_t *v,
                                                const uint8_t *ck_values, const uint8_t *input_values, uint8_t *aL, uint8_t *aR, uint8_t *aO,
                                                uint64_t *first_mismatch_out) {
     return guard([&] {
         REQUIRE(inst && program && aL && aR && aO && (inst->m == 0 || count == 0 || v) && (count == 0 || first_mismatch_out));
         REQUIRE(!checkpoints || checkpoints->n_checkpoints == 0 || count == 0 || ck_values);
         if (n_inputs && count && !input_values) throw std::invalid_argument("template_eval_batch: the program has " + std::to_string(n_inputs) + " public inputs and input_values is null");
-        Engine::template_eval_batch_checkpointed_host(as_view(inst, false), program_view_inputs(program, hints, checkpoints, n_inputs), count, v, ck_values, aL, aR, aO,
+        Engine::template_eval_batch_checkpointed_host(as_view(inst, false), program_view_inputs(program, hints, checkpoints, n_inputs, gates), count, v, ck_values, aL, aR, aO,
                                                       first_mismatch_out, input_values);
     });
 }
-bpg_status bpg_test_template_inputs_instance(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, uint64_t n_inputs,
+bpg_status bpg_test_template_eval_batch_inputs(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                               const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, uint64_t count, const uint8_t *v,
+                                               const uint8_t *ck_values, const uint8_t *input_values, uint8_t *aL, uint8_t *aR, uint8_t *aO,
+                                               uint64_t *first_mismatch_out) {
+    return bpg_test_template_eval_batch_gated(inst, program, hints, checkpoints, n_inputs, nullptr, count, v, ck_values, input_values, aL, aR, aO, first_mismatch_out);
+}
+bpg_status bpg_test_template_gated_instance(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, uint64_t n_inputs, const bpg_witness_gates *gates,
                                              const uint8_t *param_values, const uint8_t *input_values, uint64_t *row_ptr, uint64_t row_cap, uint32_t *term_var,
                                              uint32_t *term_coef, uint64_t term_cap, uint8_t *coef, uint64_t coef_cap, uint64_t *nnz_out, uint64_t *ncoef_out) {
     return guard([&] {
         REQUIRE(inst && program && row_ptr && nnz_out && ncoef_out);
-        const FlatCircuit f = Engine::template_inputs_instance_host(as_view(inst, false), program_view_inputs(program, hints, nullptr, n_inputs), param_values, input_values);
+        const FlatCircuit f = Engine::template_inputs_instance_host(as_view(inst, false), program_view_inputs(program, hints, nullptr, n_inputs, gates), param_values, input_values);
         const uint64_t nnz = f.term_var.size(), ncoef = f.coef.size() / 32;
         if (row_cap < f.row_ptr.size()) throw std::invalid_argument("template_inputs_instance: row_ptr too short (" + std::to_string(f.row_ptr.size()) + " entries needed)");
         if (term_cap < nnz || (nnz && (!term_var || !term_coef))) throw std::invalid_argument("template_inputs_instance: term_var / term_coef too short (" + std::to_string(nnz) + " entries needed)");
@@ -495,17 +525,26 @@ bpg_status bpg_test_template_inputs_instance(const bpg_r1cs_instance *inst, cons
         *nnz_out = nnz; *ncoef_out = ncoef;
     });
 }
-bpg_status bpg_test_circuit_handle_inputs(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
-                                          const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, bpg_circuit **out) {
+bpg_status bpg_test_template_inputs_instance(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, uint64_t n_inputs,
+                                             const uint8_t *param_values, const uint8_t *input_values, uint64_t *row_ptr, uint64_t row_cap, uint32_t *term_var,
+                                             uint32_t *term_coef, uint64_t term_cap, uint8_t *coef, uint64_t coef_cap, uint64_t *nnz_out, uint64_t *ncoef_out) {
+    return bpg_test_template_gated_instance(inst, program, hints, n_inputs, nullptr, param_values, input_values, row_ptr, row_cap, term_var, term_coef, term_cap, coef, coef_cap, nnz_out, ncoef_out);
+}
+bpg_status bpg_test_circuit_handle_gated(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                          const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, const bpg_witness_gates *gates, bpg_circuit **out) {
     return guard([&] {
         REQUIRE(out); *out = nullptr;
         REQUIRE(inst && program);
         const FlatView f = as_view(inst, false, true);
-        const WitnessProgramView w = program_view_inputs(program, hints, checkpoints, n_inputs);
+        const WitnessProgramView w = program_view_inputs(program, hints, checkpoints, n_inputs, gates);
         (void)Engine::plan_template(f, w);
-        bpg_circuit *c = new bpg_circuit{nullptr, f.n, f.m}; c->is_template = true; c->n_params = w.n_params; c->n_ck = w.n_ck; c->n_in = n_inputs;
+        bpg_circuit *c = new bpg_circuit{nullptr, f.n, f.m}; c->is_template = true; c->n_params = w.n_params; c->n_ck = w.n_ck; c->n_in = n_inputs; c->n_gates = w.n_gates;
         *out = c;
     });
+}
+bpg_status bpg_test_circuit_handle_inputs(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                          const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, bpg_circuit **out) {
+    return bpg_test_circuit_handle_gated(inst, program, hints, checkpoints, n_inputs, nullptr, out);
 }
 bpg_status bpg_test_template_eval_checkpointed(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
                                                const bpg_witness_checkpoints *checkpoints, const uint8_t *v, const uint8_t *ck_values,
@@ -575,6 +614,7 @@ static bpg_status template_repeat(bpg_ctx *ctx, bpg_circuit *tmpl, uint64_t coun
         REQUIRE(ctx && tmpl);
         if (count == 0) throw std::invalid_argument("template_repeat: count must be at least 1");
         if (!tmpl->is_template) throw std::invalid_argument("template_repeat: the circuit is not a template (bpg_r1cs_upload_template)");
+        if (tmpl->n_gates) throw std::invalid_argument("template_repeat: the template has gated variables (a repeat carries none yet: prove its items in a batch, bpg_r1cs_prove_template_batch_inputs)");
         if (tmpl->n_in && !with_inputs) throw std::invalid_argument("template_repeat: the template has public inputs (a repeat carries none: prove its items in a batch, bpg_r1cs_prove_template_batch_inputs)");
         if (!tmpl->dc) throw std::invalid_argument("template_repeat: the handle has no device state (bpg_test_circuit_handle)");
         if (Engine::is_join(tmpl->dc)) throw std::invalid_argument("template_repeat: the circuit is a join (join its parts with larger counts instead)");
@@ -609,6 +649,7 @@ static bpg_status template_join(bpg_ctx *ctx, uint64_t n_parts, const bpg_templa
             if (!t) throw std::invalid_argument(at + "null template");
             if (parts[p].count == 0) throw std::invalid_argument(at + "count must be at least 1");
             if (!t->is_template) throw std::invalid_argument(at + "the circuit is not a template (bpg_r1cs_upload_template)");
+            if (t->n_gates) throw std::invalid_argument(at + "the template has gated variables (a join carries none yet)");
             if (t->n_in && !with_inputs) throw std::invalid_argument(at + "the template has public inputs (a join carries none)");
             if (!t->dc) throw std::invalid_argument(at + "the handle has no device state (bpg_test_circuit_handle)");
             src.emplace_back(t->dc, parts[p].count);
@@ -668,7 +709,7 @@ static std::vector<Engine::JoinSource> join_sources_inputs(uint64_t n_parts, con
     std::vector<Engine::JoinSource> src;
     for (uint64_t p = 0; p < n_parts; p++) {
         if (!parts[p].inst || !parts[p].program) throw std::invalid_argument("template_join: part " + std::to_string(p) + ": null instance or program");
-        src.push_back({as_view(parts[p].inst, false, true), program_view_inputs(parts[p].program, parts[p].hints, parts[p].checkpoints, parts[p].n_inputs), parts[p].count});
+        src.push_back({as_view(parts[p].inst, false, true), program_view_inputs(parts[p].program, parts[p].hints, parts[p].checkpoints, parts[p].n_inputs, nullptr), parts[p].count});
     }
     return src;
 }
@@ -708,7 +749,7 @@ bpg_status bpg_test_template_repeat_inputs_instance(const bpg_r1cs_instance *ins
     return guard([&] {
         REQUIRE(inst && program && row_ptr && nnz_out && ncoef_out);
         const uint64_t caps[3] = {row_cap, (term_var && term_coef) ? term_cap : 0, coef ? coef_cap : 0};
-        const FlatCircuit f = Engine::template_repeat_inputs_instance_host(as_view(inst, false, true), program_view_inputs(program, hints, nullptr, n_inputs), count, param_values,
+        const FlatCircuit f = Engine::template_repeat_inputs_instance_host(as_view(inst, false, true), program_view_inputs(program, hints, nullptr, n_inputs, nullptr), count, param_values,
                                                                            input_values, caps);
         instance_out(f, row_ptr, term_var, term_coef, coef, nnz_out, ncoef_out);
     });
@@ -719,7 +760,7 @@ bpg_status bpg_test_template_eval_repeat_inputs(const bpg_r1cs_instance *inst, c
     return guard([&] {
         REQUIRE(inst && program && aL && aR && aO && first_mismatch && (inst->m == 0 || count == 0 || v));
         REQUIRE(!checkpoints || checkpoints->n_checkpoints == 0 || count == 0 || ck_values);
-        *first_mismatch = Engine::template_eval_repeat_inputs_host(as_view(inst, false, true), program_view_inputs(program, hints, checkpoints, n_inputs), count, v, ck_values,
+        *first_mismatch = Engine::template_eval_repeat_inputs_host(as_view(inst, false, true), program_view_inputs(program, hints, checkpoints, n_inputs, nullptr), count, v, ck_values,
                                                                    input_values, aL, aR, aO);
     });
 }
@@ -1356,6 +1397,18 @@ bpg_status bpg_prover_instance(bpg_prover *p, bpg_r1cs_instance *out, const uint
 bpg_status bpg_prover_input(bpg_prover *p, const uint8_t value[32], uint32_t *var_out) {
     return guard([&] { REQUIRE(p && value); const Variable x = p->p->input(Scalar::from_bits(value)); if (var_out) *var_out = x.packed(); });
 }
+bpg_status bpg_prover_gate(bpg_prover *p, uint32_t x, uint32_t var, uint32_t *var_out) {
+    return guard([&] { REQUIRE(p); const Variable g = p->p->gate(Variable::unpack(x), Variable::unpack(var)); if (var_out) *var_out = g.packed(); });
+}
+bpg_status bpg_prover_gates(bpg_prover *p, bpg_witness_gates *out) {
+    return guard([&] {
+        REQUIRE(p && out);
+        p->gate_var.clear(); p->gate_input.clear();
+        for (auto &g : p->p->gates()) { p->gate_var.push_back(g.first); p->gate_input.push_back(g.second); }
+        p->gate_var.push_back(0); p->gate_input.push_back(0);       // (never a null pointer)
+        out->n_gates = p->p->gates().size(); out->gate_var = p->gate_var.data(); out->gate_input = p->gate_input.data();
+    });
+}
 bpg_status bpg_prover_template_instance(bpg_prover *p, bpg_r1cs_instance *out, const uint8_t **v_out, const uint8_t **vb_out, uint64_t *n_inputs_out,
                                         const uint8_t **inputs_out) {
     return guard([&] {
@@ -1459,6 +1512,9 @@ bpg_status bpg_verifier_commit(bpg_verifier *v, const uint8_t com[32], uint32_t 
 bpg_status bpg_verifier_input(bpg_verifier *v, const uint8_t value[32], uint32_t *var_out) {
     return guard([&] { REQUIRE(v && value); const Variable x = v->v->input(Scalar::from_bits(value)); if (var_out) *var_out = x.packed(); });
 }
+bpg_status bpg_verifier_gate(bpg_verifier *v, uint32_t x, uint32_t var, uint32_t *var_out) {
+    return guard([&] { REQUIRE(v); const Variable g = v->v->gate(Variable::unpack(x), Variable::unpack(var)); if (var_out) *var_out = g.packed(); });
+}
 uint64_t bpg_verifier_num_vars(const bpg_verifier *v) { return v ? v->v->get_num_vars() : 0; }
 bpg_status bpg_verifier_instance(bpg_verifier *v, bpg_r1cs_instance *out, const uint8_t **commitments_out) {
     return guard([&] { REQUIRE(v && out); v->flat = v->v->flatten(); view(v->flat, out); if (commitments_out) *commitments_out = v->v->commitments().data(); });
@@ -1496,6 +1552,26 @@ bpg_status bpg_merkle_tree256_new(const bpg_lc *root, const bpg_lc *inst, uint64
         for (uint64_t i = 0; i < n_inst; i++) iv.push_back(lc_from(&inst[i]));
         for (uint64_t i = 0; i < n_wit; i++) wv.push_back(lc_from(&wit[i]));
         *out = new bpg_gadget{std::unique_ptr<Gadget>(new MerkleTree256(lc_from(root), iv, wv, Pattern::parse(pattern)))};
+    });
+}
+bpg_status bpg_merkle_path256_new(const bpg_lc *root, uint32_t leaf, const uint32_t *levels, uint64_t depth, bpg_gadget **out) {
+    return guard([&] {
+        REQUIRE(out && (depth == 0 || levels));
+        if (depth > Pattern::MAX_DEPTH) throw std::invalid_argument("MerklePath256: deeper than 64 levels");
+        std::vector<MerklePath256::Level> lv;
+        for (uint64_t j = 0; j < depth; j++)
+            lv.push_back({Variable::unpack(levels[4 * j]), Variable::unpack(levels[4 * j + 1]), Variable::unpack(levels[4 * j + 2]), Variable::unpack(levels[4 * j + 3])});
+        *out = new bpg_gadget{std::unique_ptr<Gadget>(new MerklePath256(lc_from(root), Variable::unpack(leaf), lv))};
+    });
+}
+bpg_status bpg_merkle_path_inputs(uint64_t index, const uint8_t *siblings, uint64_t depth, const uint8_t root[32], uint8_t *inputs_out) {
+    return guard([&] {
+        REQUIRE(root && inputs_out && (depth == 0 || siblings));
+        if (depth > Pattern::MAX_DEPTH) throw std::invalid_argument("merkle_path_inputs: deeper than 64 levels");
+        std::vector<Scalar> sib(depth);
+        for (uint64_t j = 0; j < depth; j++) sib[j] = Scalar::from_bits(siblings + 32 * j);
+        const std::vector<Scalar> in = merkle_path_inputs(index, sib, Scalar::from_bits(root));
+        for (size_t k = 0; k < in.size(); k++) std::memcpy(inputs_out + 32 * k, in[k].as_bytes(), 32);
     });
 }
 static std::vector<LinearCombination> lcs_from(const bpg_lc *a, uint64_t n) { std::vector<LinearCombination> o; for (uint64_t i = 0; i < n; i++) o.push_back(lc_from(&a[i])); return o; }

@@ -177,6 +177,8 @@ struct DeviceCircuit {
     // one after the other, and k_input_slots_join fills the slots from slot_parts descriptors in join_desc (a repeat: one, made for this kernel alone; 0: a
     // single template, k_input_slots).  The derived slots are STICKY state of the circuit: they stand as the last assign_inputs or set_inputs left them.
     uint64_t n_in = 0, slot_first = 0, n_slots = 0;
+    // gates (WitnessProgramView::n_gates): with any, variable columns of the matrix name derived slots too (host/template.hpp); repeat, join and check_batch refuse
+    uint64_t n_gates = 0;
     uint32_t slot_parts = 0;
     DevBuf wit_in, in_slots;
     bool wit_v_set = false;                 // wit_v holds the values of an assign() (a template uploaded WITH its witness has a_L, a_R, a_O and no values yet)
@@ -1384,7 +1386,7 @@ void Engine::Impl::transpose_csr(const uint64_t *rp, const uint32_t *tv, const u
                       W.starts + nvar, ent_row, ent_coef);
 }
 
-void Engine::check_instance(const FlatView &c, uint64_t n_inputs) {
+void Engine::check_instance(const FlatView &c, uint64_t n_inputs, uint64_t n_gates) {
     const uint64_t n = c.n, m = c.m, q = c.q, nnz = c.nnz, ncoef = c.ncoef;
     const bool has_witness = !(!c.aL && !c.aR && !c.aO && n > 0);
     if (has_witness && n > 0 && (!c.aL || !c.aR || !c.aO)) throw std::invalid_argument("upload: witness vectors must hold n scalars");
@@ -1400,8 +1402,12 @@ void Engine::check_instance(const FlatView &c, uint64_t n_inputs) {
         else if (kind == Variable::Input && n_inputs) {
             if (idx >= n_inputs) throw std::invalid_argument("upload: term " + std::to_string(k) + " names public input " + std::to_string(idx) + " (the template takes " + std::to_string(n_inputs) + ")");
         }
+        else if (kind == Variable::Gated && n_gates) {
+            if (idx >= n_gates) throw std::invalid_argument("upload: term " + std::to_string(k) + " names gate " + std::to_string(idx) + " (the template has " + std::to_string(n_gates) + ")");
+        }
         else if (kind != 4) throw std::invalid_argument("upload: bad variable kind (term " + std::to_string(k) + " has kind " + std::to_string(kind) +
-                                                        (kind == Variable::Input ? ": a public input, which only bpg_r1cs_upload_template_inputs takes)" : ")"));
+                                                        (kind == Variable::Input ? ": a public input, which only bpg_r1cs_upload_template_inputs takes)" :
+                                                         kind == Variable::Gated ? ": a gated variable, which only bpg_r1cs_upload_template_gated takes)" : ")"));
     }
     for (uint64_t r = 0; r < q; r++) if (c.row_ptr[r] > c.row_ptr[r + 1]) throw std::invalid_argument("upload: malformed CSR");
 }
@@ -1467,7 +1473,7 @@ void Engine::free_circuit(DeviceCircuit *c) {
 
 // ------------------------------------------------------------------------------------------------ circuit templates (host/template.hpp, hip/k_witness.cuh)
 TemplatePlan Engine::plan_template(const FlatView &c, const WitnessProgramView &p, const uint8_t *input_values) {
-    check_instance(c, p.n_inputs);
+    check_instance(c, p.n_inputs, p.n_gates);
     check_witness_program(c, p);
     if (p.n_inputs && !input_values && c.n && c.aL) throw std::invalid_argument("template: the instance carries a witness and no values were given for its " + std::to_string(p.n_inputs) + " public inputs");
     TemplatePlan T;
@@ -1477,7 +1483,7 @@ TemplatePlan Engine::plan_template(const FlatView &c, const WitnessProgramView &
     T.packed = pack_witness_program(c, p, T.schedule, share);       // the classes come from the caller's table: slots are constants of rows only
     T.slotted = with_parameter_slots(c, p, &T.in_slots, input_values);
     T.n_params = p.n_params; T.param_first = c.ncoef;
-    T.n_inputs = p.n_inputs; T.slot_first = c.ncoef + p.n_params;
+    T.n_inputs = p.n_inputs; T.slot_first = c.ncoef + p.n_params; T.n_gates = p.n_gates;
     T.ck_var.assign(p.ck_var, p.ck_var + p.n_ck);
     return T;
 }
@@ -1594,7 +1600,7 @@ DeviceCircuit *Engine::upload_template(const FlatView &c, const TemplatePlan &T)
         d->wit_ck_var.ensure(d->n_ck * 4); d->wit_ck.ensure(d->n_ck * sizeof(scm));
         I.h2d(d->wit_ck_var.p, T.ck_var.data(), d->n_ck * 4);
     }
-    d->n_in = T.n_inputs; d->slot_first = T.slot_first; d->n_slots = T.in_slots.size();
+    d->n_in = T.n_inputs; d->slot_first = T.slot_first; d->n_slots = T.in_slots.size(); d->n_gates = T.n_gates;
     if (d->n_in) {
         d->wit_in.ensure(d->n_in * sizeof(scm)); d->in_slots.ensure((d->n_slots ? d->n_slots : 1) * sizeof(InputSlot));
         if (d->n_slots) I.h2d(d->in_slots.p, T.in_slots.data(), d->n_slots * sizeof(InputSlot));
@@ -1822,6 +1828,7 @@ DeviceCircuit *Engine::repeat_template(DeviceCircuit *src, uint64_t count, bool 
     if (!src) throw std::invalid_argument("template_repeat: no circuit");
     if (!src->is_template) throw std::invalid_argument("template_repeat: the circuit is not a template (bpg_r1cs_upload_template)");
     if (src->rep_count) throw std::invalid_argument("template_repeat: the circuit is itself a repeat (repeat the template it was made from)");
+    if (src->n_gates) throw std::invalid_argument("template_repeat: the template has gated variables (a repeat carries none yet: prove its items in a batch, bpg_r1cs_prove_template_batch_inputs)");
     if (src->n_in && !with_inputs) throw std::invalid_argument("template_repeat: the template has public inputs (a repeat carries none: prove its items in a batch, bpg_r1cs_prove_template_batch_inputs)");
     check_repeat_sizes(count, src->n, src->m, src->q, src->nnz, src->param_first, src->n_params, src->n_slots, src->n_in);
     HIPCHK(hipSetDevice(device_));
@@ -2042,6 +2049,7 @@ DeviceCircuit *Engine::join_templates(const std::vector<std::pair<DeviceCircuit 
         if (!s->is_template) throw std::invalid_argument(at + "the circuit is not a template (bpg_r1cs_upload_template)");
         if (s->rep_count) throw std::invalid_argument(at + "the circuit is itself a repeat (name the template it was made from and a count)");
         if (!s->join_parts.empty()) throw std::invalid_argument(at + "the circuit is itself a join (name its parts instead)");
+        if (s->n_gates) throw std::invalid_argument(at + "the template has gated variables (a join carries none yet)");
         if (s->n_in && !with_inputs) throw std::invalid_argument(at + "the template has public inputs (a join carries none)");
         if (s->device != device_) throw std::invalid_argument(at + "the circuit lives on the device of another context");
         if (src[p].second >= (1ull << 32)) throw std::invalid_argument(at + "the joined multipliers are too many (below 2^27)");
@@ -3694,7 +3702,7 @@ VwCall verify_wave_launch(Engine::Impl &I, const DeviceCircuit *c, uint64_t K, c
             R.launches[1]++;
         }
         BPG_LAUNCH(I, k_vw_flatten, dim3(cdiv(items * ncols, 256)), dim3(256), c->col_ptr.as<uint64_t>(), c->ent_row.as<uint32_t>(), c->ent_coef.as<uint32_t>(), c->coef.as<scm>(),
-                   zpow, nz, w, ncols, (uint32_t)(3 * n), items * ncols);
+                   c->n_gates ? tails : nullptr, (uint32_t)c->param_first, (uint32_t)n_tail, zpow, nz, w, ncols, (uint32_t)(3 * n), items * ncols);
         R.launches[2]++;
         BPG_LAUNCH(I, k_vw_small, dim3((uint32_t)items), dim3(256), c->ent_row.as<uint32_t>(), c->ent_coef.as<uint32_t>(), c->coef.as<scm>(), tails, (uint32_t)c->param_first,
                    (uint32_t)n_tail, c->const_begin, c->nnz, zpow, nz, ypow, w, (uint32_t)n, (uint32_t)m, (uint32_t)N, I.vfy_small.as<scm>() + k0 * P.small_len);

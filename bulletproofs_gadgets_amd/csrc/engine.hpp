@@ -283,7 +283,7 @@ public:
     static void drop_witness(DeviceCircuit *tmpl);
     // the host-side checks of an instance (CSR shape, index ranges, sizes), which upload() and plan_template() start with: std::invalid_argument, no device work
     // n_inputs: terms of kind Variable::Input that name inputs [0, n_inputs) are legal (a template with inputs); 0, every other caller: the kind is refused
-    static void check_instance(const FlatView &c, uint64_t n_inputs = 0);
+    static void check_instance(const FlatView &c, uint64_t n_inputs = 0, uint64_t n_gates = 0);
     // MiMC sponges and Merkle trees on the device (include/bpg.h, "MiMC Merkle trees"; hip/k_mimc.cuh).  Every argument is checked before the device is touched
     // (std::invalid_argument); the calls run on the context's stream and return synchronised.
     // mimc_sponge_1 of count items of `blocks` 32-byte blocks each (any 256-bit value, taken mod l) -> count canonical scalars

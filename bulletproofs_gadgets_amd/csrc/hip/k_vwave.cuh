@@ -77,17 +77,25 @@ __global__ void __launch_bounds__(256) k_vw_tails(const uint32_t *__restrict__ f
     tails[t] = vw_tail_entry(j, flags[k], n_params, raw + 8 * k * n_raw, slots, coef, standing);
 }
 // flattened_constraints(z_k) of every item: a lane per (item, column c < ncols = 3 n + m), columns >= first_neg_col negated, exactly as k_flatten.  Variable
-// columns never name a parameter or derived slot (host/template.hpp makes those constant terms), so they read the shared table only
+// columns of a template WITHOUT gates never name a parameter or derived slot (host/template.hpp makes those constant terms): tails == nullptr, the shared
+// table throughout.  With gates a column entry may sit on a derived slot (coefficient * input): an index at or above tail_first then comes from the item's
+// tail, as in k_vw_small.  The engine passes tails only for a circuit with gates whose items bring constants
 __global__ void __launch_bounds__(256) k_vw_flatten(const uint64_t *__restrict__ col_ptr, const uint32_t *__restrict__ ent_row, const uint32_t *__restrict__ ent_coef,
-                                                    const scm *__restrict__ coef, const scm *__restrict__ zpow, uint32_t nz, scm *__restrict__ w, uint32_t ncols,
+                                                    const scm *__restrict__ coef, const scm *__restrict__ tails, uint32_t tail_first, uint32_t n_tail,
+                                                    const scm *__restrict__ zpow, uint32_t nz, scm *__restrict__ w, uint32_t ncols,
                                                     uint32_t first_neg_col, uint64_t total) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= total) return;
     const uint64_t k = t / ncols;
     const uint32_t c = (uint32_t)(t - k * ncols);
     const scm *__restrict__ zp = zpow + k * nz;
+    const scm *__restrict__ tk = tails ? tails + k * n_tail : nullptr;
     scm acc = sc_zero();
-    for (uint64_t e = col_ptr[c]; e < col_ptr[c + 1]; e++) acc = sc_add(acc, sc_mont_mul(coef[ent_coef[e]], zp[ent_row[e] + 1]));
+    for (uint64_t e = col_ptr[c]; e < col_ptr[c + 1]; e++) {
+        const uint32_t ci = ent_coef[e];
+        const scm cf = (tk && ci >= tail_first) ? tk[ci - tail_first] : coef[ci];
+        acc = sc_add(acc, sc_mont_mul(cf, zp[ent_row[e] + 1]));
+    }
     w[t] = (c >= first_neg_col) ? sc_neg(acc) : acc;
 }
 // a block per item: w_c = - sum over the constant column [e0, e1) of coef * z^(row + 1) - a coefficient below tail_first from the shared table, one at or

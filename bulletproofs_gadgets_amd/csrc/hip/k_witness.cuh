@@ -17,6 +17,9 @@
 // the same for every lane that walks it, so the items of a batch stay convergent: only the value differs.  The ROWS of the matrix never name an input: their
 // input terms are constant terms on derived coefficient slots, which k_input_slots fills per item before anything reads constant terms (a repeat or join
 // with inputs: k_input_slots_join of k_join.cuh, a lane per (part, item, slot)).
+// A GATED term (class WIT_COEF_GATED, two term slots: host/witness_record.hpp) is coefficient * in[p] * x: x is fetched as for any term - the previous
+// multiplier's registers, aL / aR / aO, v or ck -, multiplied by the input the first slot names, and the second slot's class decides as before whether a
+// product with the coefficient follows.  One product under +-1, two under a general coefficient; which branch is taken is again a word of the record.
 #pragma once
 #include "sc.cuh"
 #include "../host/witness_record.hpp"
@@ -31,7 +34,8 @@ BPG_HD scm witness_eval_lc(const uint32_t *t, uint32_t count, const WitPrev &pre
     scm acc = sc_zero();
     for (uint32_t k = 0; k < count; k++) {
         const uint32_t var = t[2 * k], cw = t[2 * k + 1];
-        const uint32_t kind = var >> 29, idx = var & 0x1fffffffu, cls = cw >> WIT_CLASS_SHIFT, ci = cw & WIT_COEF_INDEX_MASK;
+        const uint32_t kind = var >> 29, idx = var & 0x1fffffffu;
+        uint32_t cls = cw >> WIT_CLASS_SHIFT, ci = cw & WIT_COEF_INDEX_MASK;
         if (kind == 4) {                                            // the constant One: the coefficient itself, no product
             acc = sc_add(acc, cls == WIT_COEF_PLUS_ONE ? SC_R1() : cls == WIT_COEF_MINUS_ONE ? sc_neg(SC_R1()) : coef[ci]);
             continue;
@@ -39,6 +43,12 @@ BPG_HD scm witness_eval_lc(const uint32_t *t, uint32_t count, const WitPrev &pre
         scm x;
         if (kind <= 2 && idx == prev.idx) x = kind == 0 ? prev.l : kind == 1 ? prev.r : prev.o;
         else x = (kind == 0 ? aL : kind == 1 ? aR : kind == 2 ? aO : kind == WIT_KIND_CHECKPOINT ? ck : kind == WIT_KIND_INPUT ? in : v)[idx];
+        if (cls == WIT_COEF_GATED) {                                // coefficient * in[p] * x: p stands where the coefficient index does, the term's own
+            x = sc_mont_mul(in[ci], x);                             // class and index in the next slot (a word of the record: the same for every lane)
+            k++;
+            const uint32_t cw2 = t[2 * k + 1];
+            cls = cw2 >> WIT_CLASS_SHIFT; ci = cw2 & WIT_COEF_INDEX_MASK;
+        }
         if (cls == WIT_COEF_PLUS_ONE) acc = sc_add(acc, x);
         else if (cls == WIT_COEF_MINUS_ONE) acc = sc_sub(acc, x);
         else acc = sc_add(acc, sc_mont_mul(coef[ci], x));

@@ -232,6 +232,54 @@ private:
     MimcHash256 gadget_;
 };
 
+// ------------------------------------------------------------------------------------------ a Merkle path whose leaf index is a public input
+// One circuit for EVERY leaf index of a tree of depth D = levels.size(): per level four public inputs (nb, b, c1, c2), bottom level first, and with h the
+// running hash (the leaf at level 0) the node absorbs  gate(nb, h) + c1  as its first block and  gate(b, h) + c2  as its second.  With the inputs of
+// merkle_path_inputs - b = bit j of the index, nb = 1 - b, the sibling in c1 (b = 1) or c2 (b = 0), zero in the other - that is the reference's circuit for
+// the index's pattern ("(h I)" where the bit is 0, "(I h)" where it is 1) with the siblings as instance values: the same multipliers in the same order, the
+// same meaning row by row, the same proof.  Sponge, note_value calls and multiplier order are MimcHash256::mimc_sponge's.
+// A verifier MUST build the inputs with merkle_path_inputs from an index and siblings: arbitrary values (b = nb = 1, say) state something else.
+class MerklePath256 : public Gadget {
+public:
+    struct Level { Variable nb, b, c1, c2; };
+    MerklePath256(const LinearCombination &root, const Variable &leaf, const std::vector<Level> &levels) : root_(root), leaf_(leaf), levels_(levels) {
+        if (levels.empty()) throw std::invalid_argument("MerklePath256: a path has at least one level");
+        if (levels.size() > Pattern::MAX_DEPTH) throw std::invalid_argument("MerklePath256: deeper than 64 levels");
+    }
+    std::vector<Scalar> preprocess(const std::vector<Scalar> &) const override { return {}; }
+    void assemble(ConstraintSystem &cs, const std::vector<Variable> &, const Derived &) const override {
+        Variable h = leaf_;
+        LinearCombination state;
+        for (const Level &l : levels_) {
+            state = gadget_.mimc_sponge(cs, {LinearCombination(cs.gate(l.nb, h)) + LinearCombination(l.c1), LinearCombination(cs.gate(l.b, h)) + LinearCombination(l.c2)});
+            const Variable *out = nullptr;              // the sponge's state is one multiplier output (plus the zero key)
+            for (auto &t : state.terms) if (t.first.kind <= Variable::MultiplierOutput) out = &t.first;
+            if (!out) throw std::logic_error("MerklePath256: the sponge state names no multiplier");
+            h = *out;
+        }
+        cs.constrain(state - root_);
+    }
+private:
+    LinearCombination root_;
+    Variable leaf_;
+    std::vector<Level> levels_;
+    MimcHash256 gadget_;
+};
+// the 4 D + 1 public inputs of MerklePath256 for leaf `index` with `siblings` (bottom level first) under `root`: (nb, b, c1, c2) per level, then the root.
+// Selections, not arithmetic: every value is 0, 1, a sibling or the root
+inline std::vector<Scalar> merkle_path_inputs(uint64_t index, const std::vector<Scalar> &siblings, const Scalar &root) {
+    if (siblings.size() > Pattern::MAX_DEPTH) throw std::invalid_argument("merkle_path_inputs: deeper than 64 levels");
+    if (siblings.size() < 64 && (index >> siblings.size())) throw std::invalid_argument("merkle_path_inputs: the index has more bits than the path has levels");
+    std::vector<Scalar> in;
+    for (size_t j = 0; j < siblings.size(); j++) {
+        const bool b = (index >> j) & 1;
+        in.push_back(b ? Scalar::zero() : Scalar::one()); in.push_back(b ? Scalar::one() : Scalar::zero());
+        in.push_back(b ? siblings[j] : Scalar::zero()); in.push_back(b ? Scalar::zero() : siblings[j]);
+    }
+    in.push_back(root);
+    return in;
+}
+
 // ------------------------------------------------------------------------------------------ equality_gadget.rs
 // LEFT = RIGHT limb by limb; LEFT is a witness (variables), RIGHT witness or instance (linear combinations)
 class Equality : public Gadget {
@@ -361,6 +409,7 @@ class OpBuffer : public ConstraintSystem {
 public:
     OpBuffer(uint64_t first_multiplier, bool prover_side) : next_(first_multiplier), prover_(prover_side) {}
     MulVars multiply(LinearCombination left, LinearCombination right) override {
+        no_gates(left); no_gates(right);
         BufferedOp op; op.kind = BufferedOp::Multiply; op.a = std::move(left); op.b = std::move(right); ops_.push_back(std::move(op));
         return vars(next_++);
     }
@@ -370,11 +419,15 @@ public:
         BufferedOp op; op.kind = BufferedOp::AllocateMultiplier; op.some = some && prover_; op.l = l; op.r = r; ops_.push_back(std::move(op));
         return vars(next_++);
     }
-    void constrain(const LinearCombination &lc) override { BufferedOp op; op.kind = BufferedOp::Constrain; op.a = lc; ops_.push_back(std::move(op)); }
+    void constrain(const LinearCombination &lc) override { no_gates(lc); BufferedOp op; op.kind = BufferedOp::Constrain; op.a = lc; ops_.push_back(std::move(op)); }
     void rewind() { cached_.push_back(std::move(ops_)); ops_.clear(); }                              // cs_buffer.rs:75-78
     const std::vector<std::vector<BufferedOp>> &cache() const { return cached_; }
     uint64_t next_multiplier() const { return next_; }
 private:
+    // a gate belongs to the gate table of ONE prover or verifier; a recording has none, and its multiplier indices shift when it is replayed
+    static void no_gates(const LinearCombination &lc) {
+        for (auto &t : lc.terms) if (t.first.kind == Variable::Gated) throw std::invalid_argument("a constraint buffer takes no gated variables (gate " + std::to_string(t.first.idx) + "): gates belong to a prover or a verifier");
+    }
     static MulVars vars(uint64_t i) { uint32_t k = (uint32_t)i; return MulVars{{Variable::MultiplierLeft, k}, {Variable::MultiplierRight, k}, {Variable::MultiplierOutput, k}}; }
     uint64_t next_; bool prover_;
     std::vector<BufferedOp> ops_;

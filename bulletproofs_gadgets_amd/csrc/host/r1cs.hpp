@@ -21,7 +21,8 @@ namespace bpg {
 
 struct Variable {
     // Input: public value idx of THIS proof (Prover::input / Verifier::input) - a constant to the proof system, a variable to a circuit template
-    enum Kind : uint32_t { MultiplierLeft = 0, MultiplierRight = 1, MultiplierOutput = 2, Committed = 3, One = 4, Input = 5 };
+    // Gated: entry idx of THIS assembly's gate table (Prover::gate / Verifier::gate): the product of a public input and a variable of kind 0..3
+    enum Kind : uint32_t { MultiplierLeft = 0, MultiplierRight = 1, MultiplierOutput = 2, Committed = 3, One = 4, Input = 5, Gated = 6 };
     Kind kind; uint32_t idx;
     static Variable one() { return Variable{One, 0}; }
     uint32_t packed() const { return (static_cast<uint32_t>(kind) << 29) | idx; }
@@ -113,6 +114,9 @@ public:
     // variable as a candidate CHECKPOINT of a circuit template (bpg_witness_checkpoints); to everybody else it is nothing.  It adds no multiplier, no
     // constraint and no transcript byte.
     virtual void note_value(const LinearCombination &lc, uint32_t tag) { (void)lc; (void)tag; }
+    // x * var as a variable (Variable::Gated): x a public input of the assembly, var a multiplier variable or a committed value.  A Prover and a Verifier keep
+    // a gate table; a recording buffer has none and refuses
+    virtual Variable gate(const Variable &x, const Variable &var) { (void)x; (void)var; throw std::invalid_argument("gate: this constraint system keeps no gate table (gates belong to a prover or a verifier)"); }
 };
 
 // Flattened instance handed to the engine / exported for the oracle (layout of include/bpg.h bpg_r1cs_upload)
@@ -163,6 +167,10 @@ struct WitnessProgramView {
     const uint32_t *ck_var = nullptr;
     // Public inputs (bpg_r1cs_upload_template_inputs): terms of kind Variable::Input name inputs [0, n_inputs); 0: the program may hold no such term
     uint64_t n_inputs = 0;
+    // Gates (bpg_r1cs_upload_template_gated): a term of kind Variable::Gated names gate k < n_gates, the product of input gate_input[k] and the variable
+    // gate_var[k] (kind 0..3); the ROWS of the instance name the same table.  0: neither may hold such a term
+    uint64_t n_gates = 0;
+    const uint32_t *gate_var = nullptr, *gate_input = nullptr;
     WitnessProgramView() {}
     explicit WitnessProgramView(const WitnessProgram &w)
         : lc_ptr(w.lc_ptr.data()), term_var(w.term_var.data()), term_coef(w.term_coef.data()), n_params(w.param_rows.size()), param_rows(w.param_rows.data()),
@@ -205,12 +213,18 @@ protected:
         for (size_t i = 0; i < coef_.size(); i++) coef_[i].to_bytes(&f.coef[32 * i]);
         if (inputs_.empty()) {
             for (uint32_t v : f.term_var) if ((v >> 29) == Variable::Input) throw std::invalid_argument("a constraint names public input " + std::to_string(v & 0x1fffffffu) + ", and this assembly has made none");
+                                          else if ((v >> 29) == Variable::Gated) throw std::invalid_argument("a constraint names gate " + std::to_string(v & 0x1fffffffu) + ", and this assembly has made none");
             return;
         }
         std::unordered_map<Scalar, uint32_t, KeyHash> derived;
         for (size_t k = 0; k < f.term_var.size(); k++) {
-            if ((f.term_var[k] >> 29) != Variable::Input) continue;
-            const uint32_t p = f.term_var[k] & 0x1fffffffu;
+            const uint32_t kind = f.term_var[k] >> 29;
+            if (kind != Variable::Input && kind != Variable::Gated) continue;
+            uint32_t p = f.term_var[k] & 0x1fffffffu, to = Variable::one().packed();
+            if (kind == Variable::Gated) {          // (gate g, c) leaves as (var_g, c * x_p): the same products, the same table
+                if (p >= gates_.size()) throw std::invalid_argument("a constraint names gate " + std::to_string(p) + " of " + std::to_string(gates_.size()));
+                to = gates_[p].first; p = gates_[p].second;
+            }
             if (p >= inputs_.size()) throw std::invalid_argument("a constraint names public input " + std::to_string(p) + " of " + std::to_string(inputs_.size()));
             if (!resolve) continue;
             const Scalar c = coef_[f.term_coef[k]] * inputs_[p];
@@ -222,8 +236,23 @@ protected:
                 if (it != derived.end()) id = it->second;
                 else { id = (uint32_t)(f.coef.size() / 32); f.coef.resize(f.coef.size() + 32); c.to_bytes(&f.coef[32 * (size_t)id]); derived.emplace(c, id); }
             }
-            f.term_var[k] = Variable::one().packed(); f.term_coef[k] = id;
+            f.term_var[k] = to; f.term_coef[k] = id;
         }
+    }
+    // Gates (Variable::Gated): (packed variable of kind 0..3, input index) per gate, in the order gate() made them
+    std::vector<std::pair<uint32_t, uint32_t>> gates_;
+    // n_mul, n_committed: what the assembly has allocated so far (a gate names what exists)
+    Variable make_gate(const Variable &x, const Variable &var, size_t n_mul, size_t n_committed) {
+        if (x.kind != Variable::Input) throw std::invalid_argument("gate: x is no public input (kind " + std::to_string((uint32_t)x.kind) + "; a gate is input * variable)");
+        if (x.idx >= inputs_.size()) throw std::invalid_argument("gate: x names public input " + std::to_string(x.idx) + " of " + std::to_string(inputs_.size()) + " (an input of another assembly?)");
+        if (var.kind > Variable::Committed)
+            throw std::invalid_argument(std::string("gate: the gated variable is ") + (var.kind == Variable::One ? "the constant One (name the input itself)" : var.kind == Variable::Input ? "a public input (a product of two inputs is no linear term)" :
+                                        var.kind == Variable::Gated ? "a gate (gates do not nest)" : "of an unknown kind") + "; a gate takes a multiplier variable or a committed value");
+        if (var.kind == Variable::Committed ? var.idx >= n_committed : var.idx >= n_mul)
+            throw std::invalid_argument("gate: the gated variable's index " + std::to_string(var.idx) + " is out of range (" + std::to_string(var.kind == Variable::Committed ? n_committed : n_mul) + " allocated)");
+        if (gates_.size() >= 0x1fffffffu) throw std::invalid_argument("gate: too many gates");
+        gates_.emplace_back(var.packed(), x.idx);
+        return Variable{Variable::Gated, (uint32_t)(gates_.size() - 1)};
     }
 public:
     size_t num_constraints() const { return row_ptr_.size() - 1; }
@@ -235,6 +264,7 @@ public:
         return Variable{Variable::Input, (uint32_t)(inputs_.size() - 1)};
     }
     const std::vector<Scalar> &inputs() const { return inputs_; }
+    const std::vector<std::pair<uint32_t, uint32_t>> &gates() const { return gates_; }
 };
 
 class Engine;   // engine.hip
@@ -332,28 +362,40 @@ public:
     const std::vector<Scalar> &v_blinding() const { return vb_; }
     Transcript *transcript() { return t_; }
 
+    // g = gate(x, var): the variable whose value is x * var - x a public input of this prover, var a multiplier variable or a committed value.  Named in
+    // linear combinations like any variable; a resolved export shows (var, c * x), a template keeps the term and takes x with every assign
+    Variable gate(const Variable &x, const Variable &var) override { return make_gate(x, var, aL_.size(), v_.size()); }
+
     Scalar eval(const LinearCombination &lc) const {
         Scalar acc;
         for (auto &t : lc.terms) {
             if (t.first.kind == Variable::One) { acc += t.second; continue; }     // a constant term: c * 1 (round constants, keys) without the product
-            const Scalar *x;
             static const Scalar ONE = Scalar::one();
-            // a stale or foreign variable (another prover's, a packed value from the C ABI) must not index past the vectors: dalek panics here
-            const size_t idx = t.first.idx;
-            switch (t.first.kind) {
-            case Variable::MultiplierLeft: if (idx >= aL_.size()) throw std::invalid_argument("linear combination refers to an unallocated multiplier"); x = &aL_[idx]; break;
-            case Variable::MultiplierRight: if (idx >= aR_.size()) throw std::invalid_argument("linear combination refers to an unallocated multiplier"); x = &aR_[idx]; break;
-            case Variable::MultiplierOutput: if (idx >= aO_.size()) throw std::invalid_argument("linear combination refers to an unallocated multiplier"); x = &aO_[idx]; break;
-            case Variable::Committed: if (idx >= v_.size()) throw std::invalid_argument("linear combination refers to an uncommitted variable"); x = &v_[idx]; break;
-            case Variable::Input: if (idx >= inputs_.size()) throw std::invalid_argument("linear combination refers to a public input this prover has not made"); x = &inputs_[idx]; break;
-            default: throw std::invalid_argument("linear combination holds an unknown variable kind");
+            if (t.first.kind == Variable::Gated) {                                  // c * x_p * value
+                if (t.first.idx >= gates_.size()) throw std::invalid_argument("linear combination refers to a gate this prover has not made");
+                const auto &g = gates_[t.first.idx];
+                acc += t.second * inputs_[g.second] * value_of(Variable::unpack(g.first));
+                continue;
             }
+            const Scalar *x = &value_of(t.first);
             static const Scalar MINUS_ONE = -Scalar::one();
             if (t.second == ONE) acc += *x;                          // most coefficients of the gadgets are +-1: skip the multiplication
             else if (t.second == MINUS_ONE) acc -= *x;
             else acc += t.second * *x;
         }
         return acc;
+    }
+    // a stale or foreign variable (another prover's, a packed value from the C ABI) must not index past the vectors: dalek panics here
+    const Scalar &value_of(const Variable &var) const {
+        const size_t idx = var.idx;
+        switch (var.kind) {
+        case Variable::MultiplierLeft: if (idx >= aL_.size()) throw std::invalid_argument("linear combination refers to an unallocated multiplier"); return aL_[idx];
+        case Variable::MultiplierRight: if (idx >= aR_.size()) throw std::invalid_argument("linear combination refers to an unallocated multiplier"); return aR_[idx];
+        case Variable::MultiplierOutput: if (idx >= aO_.size()) throw std::invalid_argument("linear combination refers to an unallocated multiplier"); return aO_[idx];
+        case Variable::Committed: if (idx >= v_.size()) throw std::invalid_argument("linear combination refers to an uncommitted variable"); return v_[idx];
+        case Variable::Input: if (idx >= inputs_.size()) throw std::invalid_argument("linear combination refers to a public input this prover has not made"); return inputs_[idx];
+        default: throw std::invalid_argument("linear combination holds an unknown variable kind");
+        }
     }
 
     // keep_inputs (bpg_prover_template_instance): the rows keep their input terms, for a template; else they leave as constants (export_rows)
@@ -456,6 +498,8 @@ public:
         return MulVars{{Variable::MultiplierLeft, i}, {Variable::MultiplierRight, i}, {Variable::MultiplierOutput, i}};
     }
     void constrain(const LinearCombination &lc) override { push_row(lc); }
+    // the verifier's side of Prover::gate: the same gates in the same order
+    Variable gate(const Variable &x, const Variable &var) override { return make_gate(x, var, num_vars_, V_.size() / 32); }
     size_t get_num_vars() const { return num_vars_; }
     const std::vector<uint8_t> &commitments() const { return V_; }
     Transcript *transcript() { return t_; }

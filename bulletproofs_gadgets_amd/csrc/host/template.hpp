@@ -22,6 +22,11 @@
 // 4 segments on 1 level of LessThan against a constant; a hint run whose source is one input term is a lane of its own.)  The packer writes such a term with
 // the packed kind WIT_KIND_INPUT.  In the ROWS a term (input p, coefficient index ci) becomes a constant term on a DERIVED coefficient slot that every assign
 // fills with coef[ci] * x_p (with_parameter_slots, k_input_slots).  No inputs: schedule, stream and slot layout are bit for bit what they were.
+// A GATED term (Variable::Gated, WitnessProgramView::n_gates) is coefficient * input p_k * variable var_k for entry k of the gate table.  To the schedule it is
+// two reads: var_k under that variable's rules (committed, outside multiplier, checkpoint) and input p_k under the input's.  The packer writes it on two term
+// slots (witness_record.hpp).  In the ROWS the term (gate k, ci) becomes (var_k, derived slot of the pair (p_k, ci)) - the slot list, order rule and
+// de-duplication map of the constant input terms, so a pair a constant term and a gated term both use has ONE slot, and everything that fills slots
+// (k_input_slots, the tails of a verify wave, the per-item ranges of a proving wave) stays as it is.  No gates: schedule, stream and slots are bit for bit what they were.
 #pragma once
 #include <cstdint>
 #include <stdexcept>
@@ -47,8 +52,21 @@ struct WitnessSchedule {
 };
 
 // Every check on a program against its instance (shape, index ranges, forward references, parameter rows): std::invalid_argument, no device work.
+// the gate table against the instance's sizes (before anything indexes it)
+inline void check_gate_table(const FlatView &c, const WitnessProgramView &p) {
+    if (!p.n_gates) return;
+    if (!p.gate_var || !p.gate_input) throw std::invalid_argument("template: n_gates without gate_var / gate_input");
+    if (p.n_gates >= (1ull << 29)) throw std::invalid_argument("template: too many gates (the variable index has 29 bits)");
+    for (uint64_t k = 0; k < p.n_gates; k++) {
+        const uint32_t kind = p.gate_var[k] >> 29, idx = p.gate_var[k] & 0x1fffffffu;
+        if (kind > 3) throw std::invalid_argument("template: gate " + std::to_string(k) + " gates a variable of kind " + std::to_string(kind) + " (a gate takes a multiplier variable or a committed value)");
+        if (kind == 3 ? idx >= c.m : idx >= c.n) throw std::invalid_argument("template: gate " + std::to_string(k) + " gates a variable out of range");
+        if (p.gate_input[k] >= p.n_inputs) throw std::invalid_argument("template: gate " + std::to_string(k) + " names public input " + std::to_string(p.gate_input[k]) + " (the template takes " + std::to_string(p.n_inputs) + ")");
+    }
+}
 inline void check_witness_program(const FlatView &c, const WitnessProgramView &p) {
     if (c.n == 0) throw std::invalid_argument("template: the circuit has no multipliers");
+    check_gate_table(c, p);
     if (!p.lc_ptr) throw std::invalid_argument("template: the witness program has no lc_ptr");
     if (p.lc_ptr[0] != 0) throw std::invalid_argument("template: lc_ptr[0] must be 0");
     for (uint64_t k = 0; k < 2 * c.n; k++) if (p.lc_ptr[k] > p.lc_ptr[k + 1]) throw std::invalid_argument("template: lc_ptr must not decrease");
@@ -64,8 +82,14 @@ inline void check_witness_program(const FlatView &c, const WitnessProgramView &p
             else if (kind == Variable::Input && p.n_inputs) {
                 if (idx >= p.n_inputs) throw std::invalid_argument("template: multiplier " + std::to_string(i) + " names public input " + std::to_string(idx) + " (the template takes " + std::to_string(p.n_inputs) + ")");
             }
+            else if (kind == Variable::Gated && p.n_gates) {
+                if (idx >= p.n_gates) throw std::invalid_argument("template: multiplier " + std::to_string(i) + " names gate " + std::to_string(idx) + " (the template has " + std::to_string(p.n_gates) + ")");
+                const uint32_t gk = p.gate_var[idx] >> 29, gi = p.gate_var[idx] & 0x1fffffffu;
+                if (gk <= 2 && gi >= i) throw std::invalid_argument("template: multiplier " + std::to_string(i) + " refers to multiplier " + std::to_string(gi) + " through gate " + std::to_string(idx) + " (a multiplier may read only earlier multipliers and committed values)");
+            }
             else if (kind != 4) throw std::invalid_argument("template: bad variable kind in the witness program (term " + std::to_string(k) + ", of multiplier " + std::to_string(i) + ", has kind " + std::to_string(kind) +
-                                                            (kind == Variable::Input ? ": a public input, which only bpg_r1cs_upload_template_inputs takes)" : ")"));
+                                                            (kind == Variable::Input ? ": a public input, which only bpg_r1cs_upload_template_inputs takes)" :
+                                                             kind == Variable::Gated ? ": a gated variable, which only bpg_r1cs_upload_template_gated takes)" : ")"));
         }
     if (p.n_hints && (!p.hint_mul || !p.hint_kind || !p.hint_arg)) throw std::invalid_argument("template: n_hints without hint arrays");
     for (uint64_t k = 0; k < p.n_hints; k++) {
@@ -124,8 +148,14 @@ inline WitnessSchedule build_witness_schedule(uint64_t n, uint64_t m, const Witn
         bool cut = (seg == NONE);
         if (h < p.n_hints && p.hint_mul[h] == i) { cut = cut || !hint_same_source(p, h); h++; }
         for (uint64_t k = p.lc_ptr[2 * i]; k < p.lc_ptr[2 * i + 2] && !cut; k++) {
-            const uint32_t kind = p.term_var[k] >> 29, idx = p.term_var[k] & 0x1fffffffu;
-            const uint32_t ck = kind <= 2 ? ck_of(p.term_var[k]) : NONE;
+            uint32_t var = p.term_var[k];
+            if ((var >> 29) == Variable::Gated) {                                    // two reads: the input, then the gated variable under its own rules
+                cut = seen_in[p.gate_input[var & 0x1fffffffu]] != seg;
+                if (cut) break;
+                var = p.gate_var[var & 0x1fffffffu];
+            }
+            const uint32_t kind = var >> 29, idx = var & 0x1fffffffu;
+            const uint32_t ck = kind <= 2 ? ck_of(var) : NONE;
             if (kind == 3) cut = seen_v[idx] != seg;
             else if (kind == Variable::Input) cut = seen_in[idx] != seg;
             else if (ck != NONE) cut = seen_ck[ck] != seg;
@@ -134,8 +164,10 @@ inline WitnessSchedule build_witness_schedule(uint64_t n, uint64_t m, const Witn
         if (cut) { seg = (uint32_t)S.seg_first.size(); first = (uint32_t)i; S.seg_first.push_back(first); S.seg_level.push_back(0); }
         seg_of[i] = seg;
         for (uint64_t k = p.lc_ptr[2 * i]; k < p.lc_ptr[2 * i + 2]; k++) {
-            const uint32_t kind = p.term_var[k] >> 29, idx = p.term_var[k] & 0x1fffffffu;
-            const uint32_t ck = kind <= 2 ? ck_of(p.term_var[k]) : NONE;
+            uint32_t var = p.term_var[k];
+            if ((var >> 29) == Variable::Gated) { seen_in[p.gate_input[var & 0x1fffffffu]] = seg; var = p.gate_var[var & 0x1fffffffu]; }
+            const uint32_t kind = var >> 29, idx = var & 0x1fffffffu;
+            const uint32_t ck = kind <= 2 ? ck_of(var) : NONE;
             if (kind == 3) seen_v[idx] = seg;
             else if (kind == Variable::Input) seen_in[idx] = seg;                    // the caller's value: a level-0 source
             else if (ck != NONE) seen_ck[ck] = seg;                                  // the caller's value: no level, whoever computes it
@@ -200,6 +232,12 @@ inline PackedWitnessProgram pack_witness_program(const FlatView &c, const Witnes
         for (uint64_t k = a; k < b; k++) {
             const uint32_t cl = cls[p.term_coef[k]];
             if (cl == 3) continue;
+            if ((p.term_var[k] >> 29) == Variable::Gated) {                          // two slots: (variable, GATED | input), (-, class | coefficient index)
+                const uint32_t g = p.term_var[k] & 0x1fffffffu;
+                P.stream.push_back(packed_var(p.gate_var[g])); P.stream.push_back(WIT_COEF_GATED << WIT_CLASS_SHIFT | p.gate_input[g]);
+                P.stream.push_back(0); P.stream.push_back(cl << WIT_CLASS_SHIFT | p.term_coef[k]); cnt += 2;
+                continue;
+            }
             P.stream.push_back(packed_var(p.term_var[k])); P.stream.push_back(cl << WIT_CLASS_SHIFT | p.term_coef[k]); cnt++;
         }
         return cnt;
@@ -221,7 +259,7 @@ inline PackedWitnessProgram pack_witness_program(const FlatView &c, const Witnes
         }
         bool same = (l1 - l0 == r1 - l1);
         for (uint64_t k = 0; same && k < l1 - l0; k++) same = p.term_var[l0 + k] == p.term_var[l1 + k] && p.term_coef[l0 + k] == p.term_coef[l1 + k];
-        if (r1 - l1 > WIT_RIGHT_COUNT_MASK) throw std::invalid_argument("template: witness program too large");
+        if (2 * (r1 - l1) > WIT_RIGHT_COUNT_MASK) throw std::invalid_argument("template: witness program too large");
         const uint32_t nl = emit(l0, l1);
         const uint32_t nr = same ? 0u : emit(l1, r1);
         P.stream[h] = nl; P.stream[h + 1] = same ? WIT_SAME_AS_LEFT : nr;
@@ -251,15 +289,21 @@ inline FlatCircuit with_parameter_slots(const FlatView &c, const WitnessProgramV
         const uint64_t first = c.ncoef + p.n_params, room = (uint64_t)WIT_COEF_INDEX_MASK + 1 - std::min<uint64_t>(first, WIT_COEF_INDEX_MASK);
         std::unordered_map<uint64_t, uint32_t> slot_of;
         for (size_t k = 0; k < f.term_var.size(); k++) {
-            if ((f.term_var[k] >> 29) != Variable::Input) continue;
-            const uint32_t ip = f.term_var[k] & 0x1fffffffu, ci = f.term_coef[k];
+            const uint32_t tk = f.term_var[k] >> 29;
+            if (tk != Variable::Input && tk != Variable::Gated) continue;
+            uint32_t ip = f.term_var[k] & 0x1fffffffu, to = Variable::one().packed();
+            const uint32_t ci = f.term_coef[k];
+            if (tk == Variable::Gated) {            // (gate g, ci) -> (var_g, slot of (p_g, ci)): the pair's slot, whoever named the pair first
+                if (ip >= p.n_gates) throw std::invalid_argument("template: a constraint names gate " + std::to_string(ip) + " (the template has " + std::to_string(p.n_gates) + ")");
+                to = p.gate_var[ip]; ip = p.gate_input[ip];
+            }
             if (ip >= p.n_inputs) throw std::invalid_argument("template: a constraint names public input " + std::to_string(ip) + " (the template takes " + std::to_string(p.n_inputs) + ")");
             const auto at = slot_of.emplace((uint64_t)ip << 32 | ci, (uint32_t)derived->size());
             if (at.second) {
                 if (derived->size() >= room) throw std::invalid_argument("template: the derived coefficient slots of the public inputs are too many");
                 derived->push_back(InputSlot{ip, ci});
             }
-            f.term_var[k] = Variable::one().packed(); f.term_coef[k] = (uint32_t)(first + at.first->second);
+            f.term_var[k] = to; f.term_coef[k] = (uint32_t)(first + at.first->second);
         }
         f.coef.resize(32 * (first + derived->size()));
         for (size_t s = 0; s < derived->size() && input_values; s++) {
@@ -300,6 +344,7 @@ struct TemplatePlan {
     // public inputs: how many values assign takes, and the derived coefficient slots [slot_first, slot_first + in_slots.size()) of the rows, kept resident
     uint64_t n_inputs = 0, slot_first = 0;
     std::vector<InputSlot> in_slots;
+    uint64_t n_gates = 0;           // gates of the program and the rows (0: none; a template with gates is refused by repeat, join and check_batch)
 };
 
 }  // namespace bpg

@@ -501,6 +501,62 @@ bpg_status bpg_test_template_inputs_instance(const bpg_r1cs_instance *inst, cons
                                              uint32_t *term_coef, uint64_t term_cap, uint8_t *coef, uint64_t coef_cap, uint64_t *nnz_out, uint64_t *ncoef_out);
 bpg_status bpg_test_circuit_handle_inputs(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
                                           const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, bpg_circuit **out);
+/* ---- Gated variables: a term whose coefficient is a public input of the proof (an addition to ABI version 7).
+ *
+ * g = bpg_prover_gate(x, var) / bpg_verifier_gate(x, var): a new variable of kind BPG_VAR_GATED whose value is x * var.  x is a variable of kind
+ * BPG_VAR_INPUT made by THIS prover or verifier, var a variable of kind 0..3 (a multiplier variable or a committed value) that exists already; the index of g
+ * is the gate's position in the object's gate table of (var, input) pairs, in call order.  g is named in linear combinations like any variable, under any
+ * coefficient (the bpg_lc layout does not change).  Refused with BPG_ERR_INVALID_ARGUMENT: an x that is no input of this object, a var of kind One, Input or
+ * Gated, an index out of range.  Constraint buffers (bpg_buffer, bpg_or_*) offer no gates and refuse a combination that names one.
+ *
+ * Every RESOLVED export - bpg_prover_instance, bpg_prover_prove, bpg_verifier_verify, bpg_verifier_instance - treats a term (gate k, c) as (var_k, c * x_p),
+ * the product in the coefficient table behind the table's own entries exactly as an input's product is: no such export shows kind 6, and with the values
+ * bpg_merkle_path_inputs makes a gated circuit IS the ungated circuit of those values.  bpg_prover_template_instance and bpg_prover_witness_program(_hinted)
+ * KEEP gated terms (hint sources included); bpg_prover_gates exports the table beside them (pointers valid until the next call on the prover).
+ *
+ * bpg_r1cs_upload_template_gated: bpg_r1cs_upload_template_inputs plus the gate table; gates == NULL or n_gates == 0 makes it that call (same schedule, record
+ * stream and slot layout, bit for bit).  In the rows a term (gate k, ci) becomes (var_k, derived slot of the pair (p_k, ci)): the slot list of the constant
+ * input terms, one slot per distinct pair whoever names it.  The resulting template is served by bpg_r1cs_assign_inputs (with checkpoints: a gate over a
+ * checkpointed variable reads the caller's value), bpg_r1cs_prove_resident, bpg_r1cs_verify_resident, bpg_r1cs_set_inputs, bpg_r1cs_check,
+ * bpg_r1cs_prove_template_batch_inputs and bpg_r1cs_verify_resident_batch with per-item input_values.  bpg_r1cs_template_repeat(_inputs) and
+ * bpg_r1cs_template_join(_inputs) refuse it (BPG_ERR_INVALID_ARGUMENT, before any device work).  Kind 6 in an instance or program handed to any other entry
+ * point is refused the way kind 5 is.
+ *
+ * bpg_merkle_path256_new: the Merkle path gadget whose leaf index is a public input - `levels` holds 4 variables of kind BPG_VAR_INPUT per level, bottom level
+ * first: (nb, b, c1, c2); the node above running hash h absorbs gate(nb, h) + c1, then gate(b, h) + c2; `leaf` is a variable of kind 0..3.  It makes gates, so
+ * it is assembled with bpg_gadget_prove / bpg_gadget_verify only.  bpg_merkle_path_inputs: the 4 * depth + 1 input values for leaf `index` (bit j of it: b_j;
+ * nb_j = 1 - b_j; the sibling in c1_j where b_j = 1, in c2_j where it is 0, zero in the other; then the root).  A verifier MUST build its inputs with this
+ * call from an index and siblings: arbitrary input values state something else than membership. */
+#define BPG_VAR_GATED 6u
+typedef struct {
+    uint64_t n_gates;
+    const uint32_t *gate_var;             /* n_gates: packed variable of kind 0..3 */
+    const uint32_t *gate_input;           /* n_gates: index of the public input */
+} bpg_witness_gates;
+bpg_status bpg_r1cs_upload_template_gated(bpg_ctx *ctx, const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                          const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, const uint8_t *input_values /* n_inputs x 32 */,
+                                          const bpg_witness_gates *gates, bpg_circuit **out);
+bpg_status bpg_merkle_path_inputs(uint64_t index, const uint8_t *siblings /* depth x 32 */, uint64_t depth, const uint8_t root[32],
+                                  uint8_t *inputs_out /* (4 * depth + 1) x 32 */);
+/* the _inputs hooks above for a program with gates: the same calls with the gate table (NULL: the _inputs hook itself) */
+bpg_status bpg_test_template_schedule_gated(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                            const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, const bpg_witness_gates *gates, char *out, uint64_t cap);
+bpg_status bpg_test_template_packed_gated(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                          const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, const bpg_witness_gates *gates, uint32_t *stream_out,
+                                          uint64_t cap, uint64_t *words_out);
+bpg_status bpg_test_template_eval_gated(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                        const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, const bpg_witness_gates *gates, const uint8_t *v,
+                                        const uint8_t *ck_values, const uint8_t *input_values, uint8_t *aL, uint8_t *aR, uint8_t *aO, uint64_t *first_mismatch);
+bpg_status bpg_test_template_eval_batch_gated(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                              const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, const bpg_witness_gates *gates, uint64_t count,
+                                              const uint8_t *v, const uint8_t *ck_values, const uint8_t *input_values, uint8_t *aL, uint8_t *aR, uint8_t *aO,
+                                              uint64_t *first_mismatch_out);
+bpg_status bpg_test_template_gated_instance(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints, uint64_t n_inputs,
+                                            const bpg_witness_gates *gates, const uint8_t *param_values, const uint8_t *input_values, uint64_t *row_ptr,
+                                            uint64_t row_cap, uint32_t *term_var, uint32_t *term_coef, uint64_t term_cap, uint8_t *coef, uint64_t coef_cap,
+                                            uint64_t *nnz_out, uint64_t *ncoef_out);
+bpg_status bpg_test_circuit_handle_gated(const bpg_r1cs_instance *inst, const bpg_witness_program *program, const bpg_witness_hints *hints,
+                                         const bpg_witness_checkpoints *checkpoints, uint64_t n_inputs, const bpg_witness_gates *gates, bpg_circuit **out);
 /* TEST HOOKS, no device needed.  bpg_test_template_schedule: the checks of bpg_r1cs_upload_template and the schedule as JSON {"levels", "segments",
  * "max_levels", "seg_first": [segments + 1], "seg_level": [...], "level_segments": [...]}: segment s is multipliers [seg_first[s], seg_first[s+1]), one
  * device lane walks it in order, and everything it reads from another segment lies at a lower level.  bpg_test_template_eval: the device's interpreter
@@ -937,6 +993,11 @@ bpg_status bpg_verifier_new(bpg_transcript *t, bpg_verifier **out);             
 void bpg_verifier_free(bpg_verifier *v);
 bpg_status bpg_verifier_commit(bpg_verifier *v, const uint8_t com[32], uint32_t *var_out);       /* Verifier::commit */
 bpg_status bpg_verifier_input(bpg_verifier *v, const uint8_t value[32], uint32_t *var_out);      /* the verifier's side of bpg_prover_input */
+/* Gated variables ("Gated variables" above): x of kind BPG_VAR_INPUT, var of kind 0..3, *var_out = BPG_VAR_GATED << 29 | position in the gate table */
+bpg_status bpg_prover_gate(bpg_prover *p, uint32_t x, uint32_t var, uint32_t *var_out);
+bpg_status bpg_verifier_gate(bpg_verifier *v, uint32_t x, uint32_t var, uint32_t *var_out);
+bpg_status bpg_prover_gates(bpg_prover *p, bpg_witness_gates *out);
+bpg_status bpg_merkle_path256_new(const bpg_lc *root, uint32_t leaf, const uint32_t *levels /* 4 x depth */, uint64_t depth, bpg_gadget **out);
 uint64_t bpg_verifier_num_vars(const bpg_verifier *v);                                          /* fork getter, verifier.rs:89 */
 bpg_status bpg_verifier_instance(bpg_verifier *v, bpg_r1cs_instance *out, const uint8_t **commitments_out);
 /* Verifier::verify(&proof, &pc_gens, &bp_gens) on the GPU of ctx */
