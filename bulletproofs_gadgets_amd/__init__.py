@@ -514,11 +514,13 @@ class Context:
         raw = out.raw                 # one copy of the buffer, not one per item
         return [raw[32 * i:32 * i + 32] for i in range(count)]
 
-    def merkle_tree(self, leaves, depth=None, empty=None) -> "MerkleTree":
+    def merkle_tree(self, leaves, depth=None, empty=None, reserve=None) -> "MerkleTree":
         """Without `depth`, bpg_merkle_build: the full MiMC Merkle tree over 2^depth leaves (a list of 32-byte values, or their concatenation), resident on
         the GPU.  With `depth`, bpg_merkle_build_partial: a tree of capacity 2^depth over any len(leaves) <= 2^depth leaves, none included, whose other
-        leaves hold `empty` (32 bytes, taken mod l; None = zero) - the tree MerkleTree.append grows."""
-        return MerkleTree(self, leaves, depth, empty)
+        leaves hold `empty` (32 bytes, taken mod l; None = zero) - the tree MerkleTree.append grows.  With `depth` and `reserve`,
+        bpg_merkle_build_prefix: the same tree in the prefix layout, depth up to 32, with room for `reserve` <= min(2^depth, 2^24) leaves and about 64
+        bytes of device memory per reserved leaf; append grows the reserve as needed."""
+        return MerkleTree(self, leaves, depth, empty, reserve)
 
     def profile_set(self, mode):
         _chk(lib().bpg_profile_set(self._h, C.c_int32(mode)))
@@ -645,9 +647,11 @@ class MerkleTree:
     as they are, which is what MerkleTree256 constrains for a "(W W)" node.  Level 0 is the root, level `depth` the leaves.  It holds `size` leaves; the
     leaves from `size` on hold one `empty` value, so every node is that of the tree over the padded list, and append() puts more leaves behind the last."""
 
-    def __init__(self, ctx: "Context", leaves, depth=None, empty=None):
+    def __init__(self, ctx: "Context", leaves, depth=None, empty=None, reserve=None):
         data = bytes(leaves) if isinstance(leaves, (bytes, bytearray)) else b"".join(_exact("leaf", x, 32) for x in leaves)
         n = len(data) // 32
+        if depth is None and reserve is not None:
+            raise ValueError("`reserve` belongs to a tree built with `depth`")
         if depth is None:
             if empty is not None:
                 raise ValueError("`empty` belongs to a tree built with `depth`")
@@ -660,6 +664,9 @@ class MerkleTree:
             raise ValueError("leaves are 32 bytes each")
         empty = None if empty is None else _exact("empty", empty, 32)
         self.ctx, self.depth, self._h = ctx, int(depth), C.c_void_p()
+        if reserve is not None:
+            _chk(lib().bpg_merkle_build_prefix(ctx._h, C.c_uint32(self.depth), C.c_uint64(int(reserve)), C.c_uint64(n), data if n else None, empty, C.byref(self._h)))
+            return
         _chk(lib().bpg_merkle_build_partial(ctx._h, C.c_uint32(self.depth), C.c_uint64(n), data if n else None, empty, C.byref(self._h)))
 
     def _handle(self):
@@ -677,6 +684,17 @@ class MerkleTree:
     @property
     def capacity(self):
         return 1 << self.depth
+
+    @property
+    def reserved(self):
+        """bpg_merkle_reserved: (the leaves there is room for, the device bytes the tree holds); a tree of the dense layout: (2^depth, its array)."""
+        r, b = C.c_uint64(), C.c_uint64()
+        _chk(lib().bpg_merkle_reserved(self.ctx._h, self._handle(), C.byref(r), C.byref(b)))
+        return r.value, b.value
+
+    def reserve(self, n):
+        """bpg_merkle_reserve: room for at least n leaves in a tree of the prefix layout (a no-op when there is; a reserve never shrinks)."""
+        _chk(lib().bpg_merkle_reserve(self.ctx._h, self._handle(), C.c_uint64(int(n))))
 
     def append(self, leaves, return_root=False):
         """bpg_merkle_append: the leaves go behind the last one and only their ancestors are recomputed; returns the index of the first new leaf, and the new

@@ -1710,6 +1710,22 @@ bpg_status bpg_merkle_build_partial(bpg_ctx *ctx, uint32_t depth, uint64_t size,
         *out = h.release();
     });
 }
+bpg_status bpg_merkle_build_prefix(bpg_ctx *ctx, uint32_t depth, uint64_t reserve, uint64_t size, const uint8_t *leaves, const uint8_t empty[32], bpg_merkle **out) {
+    return guard([&] {
+        REQUIRE(out); *out = nullptr;
+        REQUIRE(depth >= 1 && depth <= 32 && reserve >= 1 && reserve <= (1ull << 24) && reserve <= (1ull << depth) && size <= reserve && (leaves || size == 0));
+        REQUIRE(ctx);
+        std::unique_ptr<bpg_merkle> h(new bpg_merkle{nullptr});
+        h->t = ctx->engine->merkle_build_prefix(depth, reserve, size, leaves, empty);
+        *out = h.release();
+    });
+}
+bpg_status bpg_merkle_reserve(bpg_ctx *ctx, bpg_merkle *t, uint64_t leaves) {
+    return guard([&] { REQUIRE(leaves <= (1ull << 24)); REQUIRE(ctx && t); ctx->engine->merkle_reserve(t->t, leaves); });
+}
+bpg_status bpg_merkle_reserved(bpg_ctx *ctx, bpg_merkle *t, uint64_t *reserve_out, uint64_t *bytes_out) {
+    return guard([&] { REQUIRE(reserve_out || bytes_out); REQUIRE(ctx && t); ctx->engine->merkle_reserved(t->t, reserve_out, bytes_out); });
+}
 bpg_status bpg_merkle_append(bpg_ctx *ctx, bpg_merkle *t, uint64_t count, const uint8_t *leaves, uint64_t *first_index_out, uint8_t root_out[32]) {
     return guard([&] { REQUIRE(leaves || count == 0); REQUIRE(ctx && t); ctx->engine->merkle_append(t->t, count, leaves, first_index_out, root_out); });
 }

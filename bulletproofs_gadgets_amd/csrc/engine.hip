@@ -30,6 +30,7 @@
 #include "host/csc_work.hpp"
 #include "host/verify_wave_plan.hpp"
 #include "host/merkle_plan.hpp"
+#include "host/merkle_prefix_plan.hpp"
 #include "hip/kernels.cuh"
 
 namespace bpg {
@@ -218,6 +219,7 @@ struct DeviceCircuit {
     X(k_bt_finish) X(k_bt_fold_scalars) X(k_witness_eval) X(k_witness_eval_batch) X(k_bt_commit_v) X(k_repeat_colptr) X(k_repeat_entries) X(k_repeat_coef) X(k_witness_eval_repeat) X(k_witness_ck_verify) X(k_witness_ck_verify_batch) \
     X(k_join_colptr) X(k_join_entries) X(k_join_coef) X(k_witness_eval_join) X(k_witness_ck_verify_join) X(k_input_slots) X(k_input_slots_join) \
     X(k_mimc_sponge) X(k_merkle_leaves) X(k_merkle_level) X(k_merkle_top) X(k_merkle_level_list) X(k_merkle_set_leaves) X(k_merkle_paths) X(k_merkle_export) X(k_merkle_fill_empty) X(k_merkle_level_range) X(k_merkle_climb) \
+    X(k_mpx_fill) X(k_mpx_range) X(k_mpx_climb) X(k_mpx_list) X(k_mpx_set_leaves) X(k_mpx_paths) X(k_mpx_export) X(k_mpx_relayout) \
     X(k_rowview_count) X(k_rowview_fill) X(k_rowview_long) X(k_check_mul) X(k_check_rows) X(k_check_rows_long) X(k_check_count) \
     X(k_vw_exp) X(k_vw_tails) X(k_vw_flatten) X(k_vw_small) X(k_vw_scalars) X(k_vw_reduce)
 enum KernelId {
@@ -244,7 +246,7 @@ struct Engine::Impl {
     std::vector<Event> prof_pool;
     double prof_ms[KID_COUNT] = {0};
     std::vector<float> prof_wit_ms;     // the first 1024 k_witness_eval / k_witness_eval_repeat / k_witness_eval_join launches since the last reset, in launch order (a launch = a level of an assign)
-    std::vector<std::pair<int, float>> prof_merkle_ms;   // the first 512 launches of the tree-hashing kernels (k_merkle_level, _top, _level_list, _level_range, _climb) since the last reset, in launch order
+    std::vector<std::pair<int, float>> prof_merkle_ms;   // the first 512 launches of the tree-hashing kernels (k_merkle_level, _top, _level_list, _level_range, _climb, k_mpx_range, _climb, _list) since the last reset, in launch order
     uint64_t prof_count[KID_COUNT] = {0};
     double prof_alg_bytes[KID_COUNT] = {0}, prof_act_bytes[KID_COUNT] = {0}, prof_fm[KID_COUNT] = {0};
     bool prof_on(int id) const { return prof_mode == 2 || (prof_mode == 1 && (id == KID_k_fold_points || id == KID_k_fold_points_reg || id == KID_k_fold_points_split || id == KID_k_fold_points_wnaf || id == KID_k_fold_points_quad || id == KID_k_fold_points_quadw || id == KID_k_fold_points_regw || id == KID_k_bucket_chunks)); }
@@ -255,7 +257,7 @@ struct Engine::Impl {
     void prof_collect() {
         if (prof_open.empty()) return;
         HIPCHK(hipStreamSynchronize(st));
-        for (ProfRec &r : prof_open) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, r.a, r.b)); prof_ms[r.id] += ms; prof_count[r.id]++; if ((r.id == KID_k_witness_eval || r.id == KID_k_witness_eval_repeat || r.id == KID_k_witness_eval_join) && prof_wit_ms.size() < 1024) prof_wit_ms.push_back(ms); if ((r.id == KID_k_merkle_level || r.id == KID_k_merkle_top || r.id == KID_k_merkle_level_list || r.id == KID_k_merkle_level_range || r.id == KID_k_merkle_climb) && prof_merkle_ms.size() < 512) prof_merkle_ms.emplace_back(r.id, ms); prof_pool.push_back(std::move(r.a)); prof_pool.push_back(std::move(r.b)); }
+        for (ProfRec &r : prof_open) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, r.a, r.b)); prof_ms[r.id] += ms; prof_count[r.id]++; if ((r.id == KID_k_witness_eval || r.id == KID_k_witness_eval_repeat || r.id == KID_k_witness_eval_join) && prof_wit_ms.size() < 1024) prof_wit_ms.push_back(ms); if ((r.id == KID_k_merkle_level || r.id == KID_k_merkle_top || r.id == KID_k_merkle_level_list || r.id == KID_k_merkle_level_range || r.id == KID_k_merkle_climb || r.id == KID_k_mpx_range || r.id == KID_k_mpx_climb || r.id == KID_k_mpx_list) && prof_merkle_ms.size() < 512) prof_merkle_ms.emplace_back(r.id, ms); prof_pool.push_back(std::move(r.a)); prof_pool.push_back(std::move(r.b)); }
         prof_open.clear();
     }
     void prof_reset() { prof_collect(); for (int i = 0; i < KID_COUNT; i++) { prof_ms[i] = 0; prof_count[i] = 0; prof_alg_bytes[i] = prof_act_bytes[i] = prof_fm[i] = 0; } prof_wit_ms.clear(); prof_merkle_ms.clear(); }
@@ -3953,10 +3955,15 @@ struct DeviceMerkle {
     uint64_t size = 0;
     scm empty = sc_zero();
     std::vector<scm> empty_nodes;       // E_0 .. E_depth, host copy; a tree of bpg_merkle_build computes it when bpg_merkle_empty_nodes first asks
+    // the prefix layout (bpg_merkle_build_prefix; host/merkle_prefix_plan.hpp): `tree` holds merkle_prefix_slots(dims) scm, height 0 (the leaves) first, and
+    // `etab` E_0 .. E_depth on the device, what a node that is not stored reads as.  Both go with the tree, on merkle_orphan too.
+    bool prefix = false;
+    MerklePrefixDims dims{};
+    DevBuf etab;
 };
 
 namespace {
-void merkle_orphan(DeviceMerkle *t) { t->tree.release(); t->owner = nullptr; }
+void merkle_orphan(DeviceMerkle *t) { t->tree.release(); t->etab.release(); t->owner = nullptr; }
 constexpr uint32_t kMerkleMaxDepth = 24;
 static_assert(MERKLE_MAX_DEPTH == kMerkleMaxDepth && MERKLE_CLIMB_PARENTS == BPG_MERKLE_TOP_PARENTS, "host/merkle_plan.hpp plans for the kernels of hip/k_mimc.cuh");
 // E_0 = empty, E_{k+1} = node(E_k, E_k) with the BPG_HD arithmetic of hip/k_mimc.cuh on the host: ~53 us a node, where the device pays a latency floor each
@@ -4110,6 +4117,7 @@ DeviceMerkle *Engine::merkle_build_partial(uint32_t depth, uint64_t size, const 
 
 void Engine::merkle_append(DeviceMerkle *t, uint64_t count, const uint8_t *leaves, uint64_t *first_index_out, uint8_t *root_out) {
     if (!t || t->owner != this) throw std::invalid_argument("merkle_append: not a tree of this context");
+    if (t->prefix) return merkle_append_prefix(t, count, leaves, first_index_out, root_out);
     if (count > (1ull << t->depth) - t->size) throw std::invalid_argument("merkle_append: the tree holds " + std::to_string(t->size) + " of 2^" + std::to_string(t->depth) + " leaves: no room for " + std::to_string(count) + " more");
     if (count && !leaves) throw std::invalid_argument("merkle_append: null leaves");
     const uint64_t first = t->size;
@@ -4148,7 +4156,7 @@ void Engine::merkle_free(DeviceMerkle *t) {
     if (Engine *e = t->owner) {
         (void)hipSetDevice(e->device_);
         (void)hipStreamSynchronize(e->impl_->st);
-        t->tree.release();
+        t->tree.release(); t->etab.release();
         std::vector<DeviceMerkle *> &live = e->impl_->trees;
         live.erase(std::remove(live.begin(), live.end(), t), live.end());
     }
@@ -4162,12 +4170,15 @@ void Engine::merkle_nodes(DeviceMerkle *t, uint32_t level, uint64_t first, uint6
     if (!out) throw std::invalid_argument("merkle_nodes: null output");
     HIPCHK(hipSetDevice(device_));
     Impl &I = *impl_;
-    const scm *src = t->tree.as<scm>() + (1ull << level) + first;
+    const scm *src = t->prefix ? nullptr : t->tree.as<scm>() + (1ull << level) + first;
     const uint64_t per = 1ull << 20;
     I.mk_out.ensure((size_t)std::min(count, per) * 32);
     for (uint64_t at = 0; at < count; at += per) {          // stream order keeps a piece's kernel behind the copy of the piece before
         const uint32_t n = (uint32_t)std::min(per, count - at);
-        BPG_LAUNCH(I, k_merkle_export, dim3(cdiv(n, 256)), dim3(256), src + at, n, I.mk_out.as<uint32_t>());
+        if (t->prefix)                                      // level 0 is the root: height depth - level; positions beyond the stored width read the table
+            BPG_LAUNCH(I, k_mpx_export, dim3(cdiv(n, 256)), dim3(256), t->tree.as<scm>(), t->dims, t->etab.as<scm>(), t->depth - level, first + at, n, I.mk_out.as<uint32_t>());
+        else
+            BPG_LAUNCH(I, k_merkle_export, dim3(cdiv(n, 256)), dim3(256), src + at, n, I.mk_out.as<uint32_t>());
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(out + (size_t)at * 32, I.mk_out.p, (size_t)n * 32, hipMemcpyDeviceToHost, I.st));
     }
@@ -4192,7 +4203,10 @@ void Engine::merkle_paths(DeviceMerkle *t, uint64_t count, const uint64_t *indic
     for (uint64_t at = 0; at < count; at += per) {
         const uint32_t n = (uint32_t)std::min(per, count - at);
         HIPCHK(hipMemcpyAsync(I.mk_in.p, idx.data() + at, (size_t)n * 4, hipMemcpyHostToDevice, I.st));
-        BPG_LAUNCH(I, k_merkle_paths, dim3(cdiv((uint64_t)n * d, 256)), dim3(256), t->tree.as<scm>(), d, I.mk_in.as<uint32_t>(), n, ancestors ? 1u : 0u, I.mk_out.as<uint32_t>());
+        if (t->prefix)
+            BPG_LAUNCH(I, k_mpx_paths, dim3(cdiv((uint64_t)n * d, 256)), dim3(256), t->tree.as<scm>(), t->dims, t->etab.as<scm>(), I.mk_in.as<uint32_t>(), n, ancestors ? 1u : 0u, I.mk_out.as<uint32_t>());
+        else
+            BPG_LAUNCH(I, k_merkle_paths, dim3(cdiv((uint64_t)n * d, 256)), dim3(256), t->tree.as<scm>(), d, I.mk_in.as<uint32_t>(), n, ancestors ? 1u : 0u, I.mk_out.as<uint32_t>());
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(out + (size_t)at * row, I.mk_out.p, (size_t)n * row, hipMemcpyDeviceToHost, I.st));
     }
@@ -4218,7 +4232,7 @@ void Engine::merkle_update(DeviceMerkle *t, uint64_t count, const uint64_t *indi
     std::memcpy(stage.data() + idx_off, cur.data(), (size_t)count * 4);
     std::sort(cur.begin(), cur.end());
     if (std::adjacent_find(cur.begin(), cur.end()) != cur.end()) throw std::invalid_argument("merkle_update: a leaf index is given twice");
-    for (uint32_t &h : cur) h += 1u << d;
+    if (!t->prefix) for (uint32_t &h : cur) h += 1u << d;    // (the prefix layout keeps positions: halving a leaf's index lv + 1 times is its ancestor of height lv + 1)
     std::vector<uint32_t> level_count(d);
     for (uint32_t lv = 0; lv < d; lv++) {                   // lv levels above the leaves' parents
         for (uint32_t &h : cur) h >>= 1;
@@ -4234,9 +4248,22 @@ void Engine::merkle_update(DeviceMerkle *t, uint64_t count, const uint64_t *indi
     I.mk_in.ensure(stage.size());
     scm *tree = t->tree.as<scm>();
     HIPCHK(hipMemcpyAsync(I.mk_in.p, stage.data(), stage.size(), hipMemcpyHostToDevice, I.st));
+    const uint32_t *list = reinterpret_cast<const uint32_t *>(I.mk_in.as<uint8_t>() + lists_off);
+    if (t->prefix) {                                        // the same lists as positions: list lv holds the parents of height lv + 1, all occupied, so stored
+        const scm *E = t->etab.as<scm>();
+        BPG_LAUNCH(I, k_mpx_set_leaves, dim3(cdiv(count, 256)), dim3(256), tree, t->dims, reinterpret_cast<const uint32_t *>(I.mk_in.as<uint8_t>() + idx_off),
+                   I.mk_in.as<uint32_t>(), (uint32_t)count);
+        for (uint32_t lv = 0; lv < d; lv++) {
+            BPG_LAUNCH(I, k_mpx_list, dim3(cdiv(level_count[lv], 256)), dim3(256), tree, t->dims, lv, list, level_count[lv], rc, E);
+            note_nodes(I, KID_k_mpx_list, level_count[lv]);
+            list += level_count[lv];
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(I.st));
+        return;
+    }
     BPG_LAUNCH(I, k_merkle_set_leaves, dim3(cdiv(count, 256)), dim3(256), tree, d, reinterpret_cast<const uint32_t *>(I.mk_in.as<uint8_t>() + idx_off),
                I.mk_in.as<uint32_t>(), (uint32_t)count);
-    const uint32_t *list = reinterpret_cast<const uint32_t *>(I.mk_in.as<uint8_t>() + lists_off);
     for (uint32_t lv = 0; lv < d; lv++) {
         BPG_LAUNCH(I, k_merkle_level_list, dim3(cdiv(level_count[lv], 256)), dim3(256), tree, list, level_count[lv], rc);
         note_nodes(I, KID_k_merkle_level_list, level_count[lv]);
@@ -4244,6 +4271,128 @@ void Engine::merkle_update(DeviceMerkle *t, uint64_t count, const uint64_t *indi
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(I.st));
+}
+
+// ------------------------------------------------------------------------------------------------ Merkle trees in the prefix layout (hip/k_merkle_prefix.cuh)
+namespace {
+static_assert(MERKLE_PREFIX_CLIMB_PARENTS == BPG_MERKLE_TOP_PARENTS, "host/merkle_prefix_plan.hpp plans for the one block of k_mpx_climb");
+// the memory check of the other builders, on the bytes that are about to be allocated
+void mpx_memory_check(const char *what, uint32_t depth, uint64_t reserve, uint64_t bytes) {
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    if (bytes + (64u << 20) > free_b)
+        throw DeviceError(std::string(what) + ": a tree of depth " + std::to_string(depth) + " with room for " + std::to_string(reserve) + " leaves takes " + std::to_string(bytes >> 20) +
+                          " MB and the device has " + std::to_string(free_b >> 20) + " MB free");
+}
+// New leaves into place (a copy, then k_merkle_leaves on that interval of height 0), then the launches of the plan: the wide steps bottom-up and the climb.
+// Nothing else hashes a growing prefix tree.  What a launch would touch is checked against the dimensions first.
+void mpx_grow(Engine::Impl &I, DeviceMerkle *t, const MerklePrefixGrowPlan &P, const uint8_t *leaves, const scm *rc) {
+    const uint64_t count = P.new_size - P.old_size;
+    if (!count) return;
+    const MerklePrefixDims &d = t->dims;
+    if (P.depth != d.depth || P.reserve != d.reserve || P.new_size > d.reserve) throw std::logic_error("merkle prefix plan: not a plan for this tree");
+    scm *buf = t->tree.as<scm>();
+    const scm *E = t->etab.as<scm>();
+    scm *at = buf + d.off[0] + P.old_size;
+    HIPCHK(hipMemcpyAsync(at, leaves, (size_t)count * 32, hipMemcpyHostToDevice, I.st));
+    BPG_LAUNCH(I, k_merkle_leaves, dim3(cdiv(count, 256)), dim3(256), at, (uint32_t)count);
+    for (uint32_t k = 0; k < P.n_wide; k++) {
+        const MerklePrefixWideStep &w = P.wide[k];
+        if (w.height >= d.depth || !w.count || (uint64_t)w.first + w.count > d.width[w.height + 1]) throw std::logic_error("merkle prefix plan: a wide step beyond the stored width");
+        BPG_LAUNCH(I, k_mpx_range, dim3(cdiv(w.count, 256)), dim3(256), buf, d, w.height, w.first, w.count, rc, E);
+        note_nodes(I, KID_k_mpx_range, w.count);
+    }
+    if (!P.climb || P.climb_height >= d.depth || P.climb_hi < P.climb_lo || P.climb_hi >= d.width[P.climb_height] || (P.climb_hi >> 1) - (P.climb_lo >> 1) >= BPG_MERKLE_TOP_PARENTS)
+        throw std::logic_error("merkle prefix plan: new leaves without a climb that fits one block");
+    BPG_LAUNCH(I, k_mpx_climb, dim3(1), dim3(256), buf, d, P.climb_height, P.climb_lo, P.climb_hi, rc, E);
+    note_nodes(I, KID_k_mpx_climb, P.climb_evals);
+    HIPCHK(hipGetLastError());
+}
+// The tree into a buffer with room for `reserve` > the present reserve leaves: the new buffer first, one launch of k_mpx_relayout, then the old buffer goes.
+// Should anything fail the tree keeps its buffer and its reserve.
+void mpx_relayout(Engine::Impl &I, DeviceMerkle *t, uint64_t reserve) {
+    const MerklePrefixDims to = merkle_prefix_dims(t->depth, reserve);
+    const uint32_t slots = merkle_prefix_slots(to);
+    mpx_memory_check("merkle_reserve", t->depth, reserve, 32ull * slots);
+    DevBuf grown;
+    try {
+        grown.ensure((size_t)slots * sizeof(scm));
+        BPG_LAUNCH(I, k_mpx_relayout, dim3(cdiv(slots, 256)), dim3(256), grown.as<scm>(), to, t->tree.as<scm>(), t->dims, t->etab.as<scm>());
+        I.prof_note(KID_k_mpx_relayout, 64.0 * slots, 64.0 * slots, 0.0);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(I.st));
+    } catch (...) { (void)hipStreamSynchronize(I.st); throw; }         // (`grown` goes after this wait)
+    t->tree = std::move(grown);                                         // releases the old buffer
+    t->dims = to;
+}
+}  // namespace
+
+DeviceMerkle *Engine::merkle_build_prefix(uint32_t depth, uint64_t reserve, uint64_t size, const uint8_t *leaves, const uint8_t *empty) {
+    if (depth < 1 || depth > MERKLE_PREFIX_MAX_DEPTH) throw std::invalid_argument("merkle_build_prefix: depth must be 1..32");
+    if (reserve < 1 || reserve > merkle_prefix_limit(depth)) throw std::invalid_argument("merkle_build_prefix: reserve must be 1..min(2^depth, 2^24)");
+    if (size > reserve) throw std::invalid_argument("merkle_build_prefix: more leaves than the reserve");
+    if (size && !leaves) throw std::invalid_argument("merkle_build_prefix: null leaves");
+    const MerklePrefixGrowPlan P = plan_merkle_prefix_grow(depth, reserve, 0, size);
+    std::unique_ptr<DeviceMerkle> t(new DeviceMerkle());
+    t->owner = this; t->depth = depth; t->size = size; t->prefix = true;
+    t->dims = merkle_prefix_dims(depth, reserve);
+    if (empty) { uint32_t w[8]; std::memcpy(w, empty, 32); t->empty = sc_from_words(w); }
+    t->empty_nodes = merkle_empty_chain(depth, t->empty);
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    const scm *rc = mimc_rc(I, device_);
+    mpx_memory_check("merkle_build_prefix", depth, reserve, merkle_prefix_bytes(t->dims));
+    try {
+        const uint32_t slots = merkle_prefix_slots(t->dims);
+        t->tree.ensure((size_t)slots * sizeof(scm));
+        t->etab.ensure(t->empty_nodes.size() * sizeof(scm));
+        HIPCHK(hipMemcpyAsync(t->etab.p, t->empty_nodes.data(), t->empty_nodes.size() * sizeof(scm), hipMemcpyHostToDevice, I.st));
+        // every stored slot without a leaf below it first, the root included when there is no leaf: the invariant of the layout
+        BPG_LAUNCH(I, k_mpx_fill, dim3(cdiv(slots, 256)), dim3(256), t->tree.as<scm>(), t->dims, (uint32_t)size, t->etab.as<scm>());
+        I.prof_note(KID_k_mpx_fill, 32.0 * slots, 32.0 * slots, 0.0);
+        mpx_grow(I, t.get(), P, leaves, rc);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(I.st));
+    } catch (...) { (void)hipStreamSynchronize(I.st); throw; }         // (the buffers go with `t`, after this wait)
+    I.trees.push_back(t.get());
+    return t.release();
+}
+
+// bpg_merkle_append on a prefix tree: a tree that outgrows its reserve takes min(limit, max(2 reserve, size + count)) first, then grows from the plan
+void Engine::merkle_append_prefix(DeviceMerkle *t, uint64_t count, const uint8_t *leaves, uint64_t *first_index_out, uint8_t *root_out) {
+    const uint64_t limit = merkle_prefix_limit(t->depth);
+    if (count > limit - t->size) throw std::invalid_argument("merkle_append: the tree holds " + std::to_string(t->size) + " of at most min(2^" + std::to_string(t->depth) + ", 2^24) leaves: no room for " + std::to_string(count) + " more");
+    if (count && !leaves) throw std::invalid_argument("merkle_append: null leaves");
+    const uint64_t first = t->size;
+    if (count) {
+        HIPCHK(hipSetDevice(device_));
+        Impl &I = *impl_;
+        const scm *rc = mimc_rc(I, device_);
+        if (first + count > t->dims.reserve) mpx_relayout(I, t, std::min<uint64_t>(limit, std::max<uint64_t>(2ull * t->dims.reserve, first + count)));
+        const MerklePrefixGrowPlan P = plan_merkle_prefix_grow(t->depth, t->dims.reserve, first, first + count);
+        try {
+            mpx_grow(I, t, P, leaves, rc);
+            HIPCHK(hipStreamSynchronize(I.st));
+        } catch (...) { (void)hipStreamSynchronize(I.st); throw; }
+        t->size = first + count;
+    }
+    if (first_index_out) *first_index_out = first;
+    if (root_out) merkle_nodes(t, 0, 0, 1, root_out);
+}
+
+void Engine::merkle_reserve(DeviceMerkle *t, uint64_t leaves) {
+    if (!t || t->owner != this) throw std::invalid_argument("merkle_reserve: not a tree of this context");
+    if (!t->prefix) throw std::invalid_argument("merkle_reserve: a tree in the dense layout holds all of its 2^depth leaves already");
+    if (leaves > merkle_prefix_limit(t->depth)) throw std::invalid_argument("merkle_reserve: beyond min(2^depth, 2^24) leaves");
+    if (leaves <= t->dims.reserve) return;
+    HIPCHK(hipSetDevice(device_));
+    mpx_relayout(*impl_, t, leaves);
+}
+
+void Engine::merkle_reserved(DeviceMerkle *t, uint64_t *reserve_out, uint64_t *bytes_out) {
+    if (!t || t->owner != this) throw std::invalid_argument("merkle_reserved: not a tree of this context");
+    if (reserve_out) *reserve_out = t->prefix ? t->dims.reserve : (1ull << t->depth);
+    if (bytes_out) *bytes_out = t->prefix ? merkle_prefix_bytes(t->dims) : (2ull << t->depth) * sizeof(scm);
 }
 
 }  // namespace bpg

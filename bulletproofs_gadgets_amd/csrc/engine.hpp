@@ -302,6 +302,15 @@ public:
     void merkle_size(DeviceMerkle *t, uint64_t *size_out, uint32_t *depth_out);
     void merkle_empty_nodes(DeviceMerkle *t, uint8_t *out);         // (depth + 1) x 32: out[k] = an empty subtree k levels above the leaves; host only
     static void merkle_free(DeviceMerkle *t);       // on the tree's own context; a tree that outlived its context lost its memory then and is only deleted
+    // The prefix layout (host/merkle_prefix_plan.hpp; hip/k_merkle_prefix.cuh): depth 1..32, room for `reserve` <= min(2^depth, 2^24) leaves, only the occupied
+    // prefix of every level stored and everything else read as an empty-subtree constant - node for node the tree merkle_build_partial builds, in
+    // 32 x (sum of the stored widths + depth + 1) bytes.  Every call above serves such a tree; append grows the reserve when the tree outgrows it.
+    DeviceMerkle *merkle_build_prefix(uint32_t depth, uint64_t reserve, uint64_t size, const uint8_t *leaves, const uint8_t *empty);
+    void merkle_reserve(DeviceMerkle *t, uint64_t leaves);          // room for at least `leaves`: a new buffer, one relayout launch, the old buffer released; a dense tree is refused
+    void merkle_reserved(DeviceMerkle *t, uint64_t *reserve_out, uint64_t *bytes_out);     // a dense tree: 2^depth and its array
+private:
+    void merkle_append_prefix(DeviceMerkle *t, uint64_t count, const uint8_t *leaves, uint64_t *first_index_out, uint8_t *root_out);
+public:
     void synchronize();
     // HIP-event profile on the engine's own stream: mode 0 off, 1 = dominant kernel (k_fold_points) only, 2 = all kernels
     void profile_set(int mode);

@@ -40,11 +40,15 @@
 //                                       (sibling lists, or the nodes on the paths), k_merkle_export (nodes as bytes); trees that grow (capacity 2^d, n leaves):
 //                                       k_merkle_fill_empty (the empty-subtree constants, once per build), k_merkle_level_range (an interval of one level),
 //                                       k_merkle_climb (from at most 256 dirty parents to the root in one launch) - launched from host/merkle_plan.hpp
+//       Merkle trees, prefix layout      (k_merkle_prefix.cuh; depth up to 32, only the occupied prefix of every level stored, host/merkle_prefix_plan.hpp) k_mpx_fill (the
+//                                       empty-subtree constants into stored, unoccupied slots), k_mpx_range (an interval of one height), k_mpx_climb (from at most 256
+//                                       dirty parents through up to 32 heights to the root in one launch), k_mpx_list + k_mpx_set_leaves (leaf updates), k_mpx_paths,
+//                                       k_mpx_export (both fall back to the tree's table of constants for a node that is not stored), k_mpx_relayout (a larger reserve)
 //       R1CS check                       (k_check.cuh; bpg_r1cs_check: which multiplier, which constraint does the resident witness break) the row-major view of the resident
 //                                       matrix, once per circuit: k_rowview_count, k_scan_blocksums / _apply, k_rowview_fill, k_rowview_long; per check: k_check_mul (a lane
 //                                       per multiplier), k_check_rows (a lane per short row, the wave's ballot = one word of the violation bitmap), k_check_rows_long (a
 //                                       wave per long row), k_check_count (bad rows and the first of them)
-// The kernels live in k_points.cuh, k_scalars.cuh, k_ipa.cuh, k_verify.cuh, k_msm.cuh, k_merge.cuh, k_batch.cuh, k_witness.cuh, k_repeat.cuh, k_join.cuh, k_mimc.cuh, k_check.cuh and k_vwave.cuh, included at the end of
+// The kernels live in k_points.cuh, k_scalars.cuh, k_ipa.cuh, k_verify.cuh, k_msm.cuh, k_merge.cuh, k_batch.cuh, k_witness.cuh, k_repeat.cuh, k_join.cuh, k_mimc.cuh, k_merkle_prefix.cuh, k_check.cuh and k_vwave.cuh, included at the end of
 // this file in that order.
 // Data layout in HBM: scalars = 8 x u32 Montgomery form, 32 B each, AoS (lane i <-> element i: 2 x 16 B coalesced
 // loads); generator tables = affine Niels (y+x, y-x, 2dxy), 96 B per point, G at [0,N) and H at [N,2N); window tables =
@@ -93,5 +97,6 @@ __device__ __forceinline__ uint32_t msm_point_index(const MsmSegs &S, uint32_t s
 #include "k_repeat.cuh"
 #include "k_join.cuh"
 #include "k_mimc.cuh"
+#include "k_merkle_prefix.cuh"
 #include "k_check.cuh"
 #include "k_vwave.cuh"

@@ -1071,14 +1071,31 @@ bpg_status bpg_be_to_scalars(const uint8_t *be, uint64_t len, uint8_t *out, uint
  *   bpg_merkle_size        the number of leaves and the depth (either output may be NULL, not both).
  *   bpg_merkle_empty_nodes E_0 .. E_depth as (depth + 1) x 32 canonical bytes: out[k] = an empty subtree k levels above the leaves - the sibling a path meets
  *                          wherever it borders the empty region.  Works on every tree (bpg_merkle_build: empty = 0, computed at the first call); no device work.
+ * Deep trees - the prefix layout, a second layout behind the same handle: a tree that only grows by append occupies a prefix of every level, and everything
+ * right of the prefix is one of the constants E_k, so only the prefix is stored and depth stops being a memory question:
+ *   bpg_merkle_build_prefix  a tree of capacity 2^depth, depth 1..32, with room for `reserve` leaves (1 <= reserve <= min(2^depth, 2^24)) holding `size` <=
+ *                          reserve of them; `empty` as above.  Height s above the leaves stores max(1, ceil(reserve / 2^s)) nodes, so the tree holds
+ *                          32 x (the sum of those widths over s = 0..depth, plus the depth + 1 constants) bytes of device memory - about 64 bytes per
+ *                          reserved leaf: depth 32 with reserve 2^20 is 64 MB (the memory check applies to that count).  Node for node it is the tree
+ *                          bpg_merkle_build_partial would build: root, nodes, paths, path_nodes, update, append, size, empty_nodes and free serve both
+ *                          layouts under the same argument rules - any level, any node of a level, any leaf index below 2^depth; what is not stored
+ *                          reads as its constant - and no circuit, template or verifier can tell.  update still reaches the leaves below `size` only.
+ *   bpg_merkle_reserve     room for at least `leaves` leaves: a new buffer, ONE launch that moves every stored node and fills the new slots with their
+ *                          constants, then the old buffer is released (both exist for that moment).  A no-op when the reserve is enough already; a
+ *                          reserve never shrinks.  Refused: a tree of the dense layout (bpg_merkle_build, _build_partial), `leaves` > min(2^depth, 2^24).
+ *   bpg_merkle_reserved    the reserve and the device bytes the tree holds (either output may be NULL, not both).  A dense tree reports 2^depth and the
+ *                          32 x 2^(depth+1) bytes of its array.
+ *   bpg_merkle_append on such a tree takes size + count <= min(2^depth, 2^24); a tree that outgrows its reserve first reserves min(that limit,
+ *                          max(2 x reserve, size + count)) and then grows as above (wide launches, then one that climbs through up to 32 levels).  A
+ *                          refused append leaves the tree and its reserve as they were.
  * size > 2^depth, size + count > 2^depth and a NULL `leaves` with a non-zero count are BPG_ERR_INVALID_ARGUMENT like the rest below; a refused
  * bpg_merkle_build_partial sets *out to NULL, and a refused call leaves the tree as it was and writes no output.
- * A depth of 0 or above 24, a NULL pointer, an index >= 2^depth, a level above depth, nodes beyond a level and count x blocks_per_item == 0 are
+ * A depth of 0 or above 24 (bpg_merkle_build_prefix: above 32; a reserve of 0, above 2^depth or above 2^24; size > reserve), a NULL pointer, an index >= 2^depth, a level above depth, nodes beyond a level and count x blocks_per_item == 0 are
  * BPG_ERR_INVALID_ARGUMENT before the device is touched.  The calls run on the context's stream and return synchronised; a tree belongs to the context that built
  * it (another context's tree is BPG_ERR_INVALID_ARGUMENT); like every call on a context they are not re-entrant.  bpg_merkle_free releases the tree on the context
  * that built it, whatever ctx is passed (NULL included).  Destroying a context releases the device memory of the trees it still holds: their handles stay valid
  * for bpg_merkle_free alone, and every other call on them is BPG_ERR_INVALID_ARGUMENT.
- * Out of scope: a sparse layout (the array is 2^(depth+1) scalars whatever the size: 1 GB at depth 24), going under the latency floor of a narrow level (a
+ * Out of scope: more than 2^24 leaves held, shrinking a reserve, keyed (non-prefix) sparse trees, going under the latency floor of a narrow level (a
  * level narrower than the device still costs one node's 1,944 dependent products: an append of a few leaves is `depth` such floors in one launch), hashing
  * records into leaves on the device, the byte-preimage padding of mimc_hash on the device (pad on the host with bpg_be_to_scalars / bpg_mimc_hash's rules
  * and hand the blocks over), flags of the file drivers, and a tree spread over more than one GPU.  (Additions to ABI version 7: no struct changes.) */
@@ -1090,6 +1107,10 @@ bpg_status bpg_merkle_build_partial(bpg_ctx *ctx, uint32_t depth, uint64_t size,
                                     const uint8_t empty[32] /* NULL = zero */, bpg_merkle **out);
 bpg_status bpg_merkle_append(bpg_ctx *ctx, bpg_merkle *t, uint64_t count, const uint8_t *leaves /* count x 32 */,
                              uint64_t *first_index_out /* NULL allowed */, uint8_t root_out[32] /* NULL allowed */);
+bpg_status bpg_merkle_build_prefix(bpg_ctx *ctx, uint32_t depth, uint64_t reserve, uint64_t size, const uint8_t *leaves /* size x 32; NULL allowed when size == 0 */,
+                                   const uint8_t empty[32] /* NULL = zero */, bpg_merkle **out);
+bpg_status bpg_merkle_reserve(bpg_ctx *ctx, bpg_merkle *t, uint64_t leaves);
+bpg_status bpg_merkle_reserved(bpg_ctx *ctx, bpg_merkle *t, uint64_t *reserve_out, uint64_t *bytes_out /* either may be NULL, not both */);
 bpg_status bpg_merkle_size(bpg_ctx *ctx, bpg_merkle *t, uint64_t *size_out, uint32_t *depth_out /* either may be NULL, not both */);
 bpg_status bpg_merkle_empty_nodes(bpg_ctx *ctx, bpg_merkle *t, uint8_t *out /* (depth + 1) x 32: out[k] = an empty subtree k levels above the leaves */);
 bpg_status bpg_merkle_root(bpg_ctx *ctx, bpg_merkle *t, uint8_t out[32]);
