@@ -7,7 +7,7 @@ correct only while the lifetimes never overlap in stream order.  A test of one f
 
     Op            family, variant, prepare() -> Expect (cached for the process, never touches a context), run(env) -> result, same(want, got)
     CATALOGUE     family -> its variants, in rotation order
-    build_walk    an Eulerian circuit of the complete directed graph on the families, loops included: all 13 x 13 ordered pairs are adjacent, 170 steps
+    build_walk    an Eulerian circuit of the complete directed graph on the families, loops included: all 16 x 16 ordered pairs are adjacent, 257 steps
     PINNED        short hand-written orders for the interactions the engine's code suggests, each with its reason
     run_walk      one context (or two of one device, dealt the steps alternately), the resident set uploaded once, a comparison after every step
     replay        run_walk on a list of "family/variant" names - what a WalkMismatch prints
@@ -18,7 +18,8 @@ mimc_sponge, the generator chain), the device-less host assembly with the oracle
 
 Sizes are the smallest that take a distinct memory path and stay at N <= 1024: a 40-bit range proof (N = 64), the 64-bit BoundsCheck (n = N = 128), the
 one-block MiMC preimage (n = 972, N = 1024: 52 padding generators, the size that takes the bucket-method path once BPG_TT_LG / BPG_TT_ORIG_LG say so), the
-8-bit BoundsCheck (n = 16) and SetMembership (n = 6) for repeats and joins, the 36-multiplier checkpoint chain, LessThan against a public bound (N = 512)."""
+8-bit BoundsCheck (n = 16) and SetMembership (n = 6) for repeats and joins, the 36-multiplier checkpoint chain, LessThan against a public bound (N = 512), the
+hand-made gate circuit (n = 10, N = 16), three Inequality statements against three public values (n = 9), a depth-11 tree grown to 606 leaves in both layouts."""
 import contextlib
 import copy
 import ctypes as C
@@ -31,6 +32,8 @@ import bulletproofs_gadgets_amd as bpg
 from bulletproofs_gadgets_amd import workloads
 import oracle_lib as O
 import checkpoint_cases as CK
+import gate_cases as GC
+import repeat_inputs_cases as RC
 import template_inputs_cases as TC
 from test_template_repeat_host import CIRCUITS, SET_INSTANCE, bounds8_item, constant_term
 
@@ -225,6 +228,66 @@ def less_than(left, bound, as_inputs, tag):
     return c
 
 
+@functools.lru_cache(maxsize=None)
+def hand(inputs, values, tag="hand10"):
+    """the UNGATED yardstick of the hand-made gate circuit: gate_cases.hand10 with the public values baked in as constants, coefficient by coefficient - an
+    assembly that knows nothing of inputs or gates.  n = 10, N = 16, m = 2, 13 rows"""
+    a = GC.hand10(inputs, values, False, prover_cls=HostProver, tag=tag)
+    c = HostCase(a.prover, a.transcript, a.commitments, b"hand10")
+    assert (c.inst.n, c.N, c.inst.m) == (GC.HAND_N, 16, 2)
+    return c
+
+
+def hand_vector(k):
+    return hand(GC.HAND_INPUTS[k], GC.HAND_VALUES[k])
+
+
+def hand_inputs(k):
+    return [sc(x) for x in GC.HAND_INPUTS[k]]
+
+
+@functools.lru_cache(maxsize=None)
+def hand_template():
+    """the GATED assembly of vector 0: the public values are inputs, the products input * variable are gates"""
+    return GC.hand10(GC.HAND_INPUTS[0], GC.HAND_VALUES[0], True, prover_cls=HostProver)
+
+
+REPEAT_INPUTS_PARTS = (("inequality", tuple(RC.ARGS["inequality"][:3])),)      # the smallest repeat of repeat_inputs_cases: K = 3, n = 9, N = 16, m = 12
+
+
+@functools.lru_cache(maxsize=None)
+def inequality3():
+    """ONE host assembly of three Inequality statements with their three public right-hand sides baked in as constants, and the verifier's replay of it"""
+    parts = [(name, list(args)) for name, args in REPEAT_INPUTS_PARTS]
+    with host_assembly():
+        a = RC.Assembly(parts, False, prover_cls=HostProver, tag="walk-repeat")
+    c = HostCase(a.prover, a.transcript, a.commitments, b"Inequality")
+    v = RC.replay(parts, a.commitments)
+    c.vinst, c.vstate = v.instance(), v.transcript.state
+    assert c.vstate == c.state and c.vinst.commitments == c.coms and (c.inst.n, c.N) == (9, 16)
+    c.inputs, c.params = list(a.inputs), list(a.params)
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def inequality_template():
+    """the gadget code assembled once with the right-hand side as an input, from an item no statement of the walk uses"""
+    with host_assembly():
+        return RC.template_of("inequality", prover_cls=HostProver)
+
+
+class Crossed:
+    """the statement of `rows` claimed for the commitments of `held` (the transcript before a proof holds the label and the commitments, nothing of the
+    rows): what a verifier who is handed other constants than the prover's judges.  Stands where a HostCase stands in a claim."""
+    def __init__(self, rows, held):
+        assert rows.inst.m == held.inst.m and rows.N == held.N and rows.label == held.label
+        self.inst, self.vinst, self.N, self.label = rows.inst, rows.vinst, rows.N, rows.label
+        self.state, self.vstate, self.coms = held.state, held.vstate, held.coms
+
+    verify = HostCase.verify
+    claim = HostCase.claim
+
+
 TREE_DEPTH = 9                                  # 2^9 leaves: the depth that straddles the hand-over from the per-level kernel to the top kernel
 
 
@@ -254,6 +317,91 @@ def tree_paths(levels, indices):
     return [[levels[k][(i >> k) ^ 1] for k in range(TREE_DEPTH)] for i in indices]
 
 
+# ---- the growing tree: capacity 2^11, 5 -> 6 -> 606 leaves, then four leaves replaced: the final state F, in the dense and in the prefix layout
+GROW_DEPTH = 11
+GROW_SIZES = (5, 6, 606)
+GROW_EMPTY = rs("gtree empty", 0)               # the empty value: a fixed non-zero scalar, reduced
+GROW_RESERVE = 7                                # the prefix tree's first reserve: odd; 6 leaves fit, 606 do not, and the regrow is to max(2 * 7, 606) = 606
+GROW_UPDATE = [0, 5, 6, 605]                    # a leaf of the build, the leaf of the first append, the first and the last leaf of the second
+GROW_PATHS = [0, 5, 6, 7, 605, 606, 607, 1024, 2047]      # occupied leaves, the first empty leaf, siblings that are empty subtrees, the far right
+# What the second append launches, by plan_merkle_grow(11, 6, 606) of csrc/host/merkle_plan.hpp (tests/hostcheck/merkle_plan.cpp holds the plan to brute
+# force; no Python hook exposes it): the new leaves are the heap nodes 2048 + 6 .. 2048 + 605 = 2054 .. 2653, their parents 1027 .. 1326 are 300 > 256
+# nodes: ONE wide step (k_merkle_level_range; k_mpx_range at height 0) writes level 10; the parents of those, 513 .. 663, are 151 <= 256 nodes: the climb
+# (k_merkle_climb / k_mpx_climb) is entered with the children of level 10 and writes level 9 and everything above.  Levels 10 and 9 are the two sides of
+# that hand-over.  The build (5 leaves: parents 1024 .. 1026) and the first append (one leaf) are the fill and a climb, and a climb, only.
+GROW_LEVELS = (10, 9)
+assert (2048 + 605) // 2 - (2048 + 6) // 2 + 1 == 300 > 256 >= 1326 // 2 - 1027 // 2 + 1 == 151
+
+
+def grow_leaves():
+    return [bpg.be_to_scalar(b"\x03" + workloads.synth("walk-gtree", i, 31)) for i in range(GROW_SIZES[-1])]
+
+
+def grow_new_leaves():
+    return [bpg.be_to_scalar(b"\x02" + workloads.synth("walk-gtree-new", i, 31)) for i in range(len(GROW_UPDATE))]
+
+
+@functools.lru_cache(maxsize=None)
+def grow_empty_chain():
+    """E_0 = the empty value, E_(k+1) = the ORACLE's sponge over (E_k, E_k): a subtree without a leaf, k levels above the leaves"""
+    E = [GROW_EMPTY]
+    for _ in range(GROW_DEPTH):
+        E.append(O.mimc_sponge(E[-1] + E[-1]))
+    return E
+
+
+class GrowModel:
+    """a sparse model of the tree that holds the first `size` leaves: heights[s] = the OCCUPIED nodes s levels above the leaves, hashed by the oracle's sponge;
+    an occupied node whose right child is not occupied reads E_s, and every node that is not occupied is E_s"""
+    def __init__(self, size, updated):
+        leaves = grow_leaves()[:size]
+        if updated:
+            for i, leaf in zip(GROW_UPDATE, grow_new_leaves()):
+                leaves[i] = leaf
+        E = grow_empty_chain()
+        self.size, self.heights = size, [leaves]
+        for s in range(GROW_DEPTH):
+            lo = self.heights[-1]
+            self.heights.append([O.mimc_sponge(lo[2 * j] + (lo[2 * j + 1] if 2 * j + 1 < len(lo) else E[s])) for j in range((len(lo) + 1) // 2)])
+        assert len(self.heights[GROW_DEPTH]) == 1
+
+    def node(self, s, j):
+        return self.heights[s][j] if j < len(self.heights[s]) else grow_empty_chain()[s]
+
+    def root(self):
+        return self.node(GROW_DEPTH, 0)
+
+    def read(self):
+        """what grow_read returns of a tree in this state"""
+        D = GROW_DEPTH
+        return (self.size, self.root(), list(grow_empty_chain()),
+                [[self.node(k, (i >> k) ^ 1) for k in range(D)] for i in GROW_PATHS],
+                [[self.node(k + 1, i >> (k + 1)) for k in range(D)] for i in GROW_PATHS],
+                [[self.node(D - level, j) for j in range(1 << level)] for level in GROW_LEVELS])
+
+
+@functools.lru_cache(maxsize=None)
+def grow_model(size, updated):
+    return GrowModel(size, updated)
+
+
+def grow_read(tree):
+    return (tree.size, tree.root(), tree.empty_nodes(), tree.paths(GROW_PATHS), tree.path_nodes(GROW_PATHS), [tree.nodes(level) for level in GROW_LEVELS])
+
+
+def grow_final_tree(ctx):
+    """F in the dense layout, built in one call over the 606 final leaves: by plan_merkle_grow(11, 0, 606) a wide step of 303 parents, then the climb"""
+    leaves = grow_leaves()
+    for i, leaf in zip(GROW_UPDATE, grow_new_leaves()):
+        leaves[i] = leaf
+    return ctx.merkle_tree(leaves, depth=GROW_DEPTH, empty=GROW_EMPTY)
+
+
+def prefix_bytes(reserve):
+    """32 x (sum of the stored widths W_s = max(1, ceil(reserve / 2^s)), s = 0 .. depth, + the depth + 1 constants of the empty table)"""
+    return 32 * (sum(max(1, -(-reserve // (1 << s))) for s in range(GROW_DEPTH + 1)) + GROW_DEPTH + 1)
+
+
 # ------------------------------------------------------------------------------------------------ the resident set of a walk
 RESIDENT = {                                    # name -> how a context gets it; uploaded in this order ("b64" before "mimc": PINNED relies on it)
     "rp40": lambda ctx: ctx.upload(rp40().inst),
@@ -265,6 +413,8 @@ RESIDENT = {                                    # name -> how a context gets it;
     "t_chain": lambda ctx: chain(1).prover.template(ctx, param_rows=chain(1).param_rows, checkpoints=chain(1).ck_vars),
     "t_lt": lambda ctx: less_than(5, 1000, True, "walk-tmpl").prover.template(ctx),
     "tree": lambda ctx: ctx.merkle_tree(tree_levels(False)[0]),
+    "t_hand": lambda ctx: hand_template().prover.template(ctx),
+    "gtree": grow_final_tree,
 }
 
 
@@ -724,6 +874,29 @@ def _():
     return prepare, run
 
 
+@op("repeat_join_check", "repeat_inputs")
+def _():
+    seed = rng("repeat inputs")
+
+    def prepare():
+        want = inequality3().prove(seed)
+        return Expect(want, [inequality3().claim(want[0])])
+
+    def run(env):
+        c = inequality3()
+        tmpl = inequality_template().prover.template(env.ctx)
+        try:
+            rep = tmpl.repeat_inputs(3)
+        finally:
+            tmpl.free()                         # the source goes before the repeat is first used
+        try:
+            rep.assign(c.inst.v, c.params, inputs=c.inputs)         # three witnesses against three public values, item-major
+            return rep.prove(c.state, c.inst.v_blinding, seed)
+        finally:
+            rep.free()
+    return prepare, run
+
+
 # ---- 11: Merkle trees and sponges
 def _tree_op(variant, updated, act, **kw):
     @op("merkle", variant, uses=["tree"], **kw)
@@ -859,8 +1032,231 @@ _lost_upload("fail_upload", "bpg_test_fail_next_upload", "upload")       # the u
 _lost_upload("drop_upload", "bpg_test_drop_next_upload", "stale")        # the copies are skipped without one: the slab's canary withholds the proof
 
 
+# ---- 14: a growing tree, dense and prefix layout: every mutating variant ends in the same final state F
+def _grow_rebuild(env, reserve):
+    """free + build over 5 leaves + append 1 + append 600 + the update -> (what the appends returned, the reserve in between and at the end)"""
+    leaves = grow_leaves()
+    env.res["gtree"].free()
+    tree = env.res["gtree"] = env.ctx.merkle_tree(leaves[:GROW_SIZES[0]], depth=GROW_DEPTH, empty=GROW_EMPTY, reserve=reserve)
+    appended = [tree.append(leaves[GROW_SIZES[0]:GROW_SIZES[1]], return_root=True)]
+    held = [tree.reserved] if reserve else []
+    appended.append(tree.append(leaves[GROW_SIZES[1]:GROW_SIZES[2]], return_root=True))
+    tree.update(GROW_UPDATE, grow_new_leaves())
+    if reserve:
+        tree.reserve(GROW_SIZES[1])             # room there is already: a reserve never shrinks
+        held.append(tree.reserved)
+    return appended, held
+
+
+def _grow_op(variant, reserve, held):
+    @op("merkle_grow", variant, uses=["gtree"], uploads=["gtree"], effect=lambda env: env.reupload("gtree"))
+    def _():
+        def prepare():
+            appended = [(GROW_SIZES[k], grow_model(GROW_SIZES[k + 1], False).root()) for k in range(2)]
+            return Expect((appended, held, grow_model(GROW_SIZES[2], True).read()))
+
+        def run(env):
+            appended, got = _grow_rebuild(env, reserve)
+            return appended, got, grow_read(env.res["gtree"])
+        return prepare, run
+
+
+_grow_op("dense", None, [])
+# the first append fits the reserve of 7; the second regrows to exactly 606, where the stored width of height 1 is 303, odd: node (2, 151) reads its
+# right child from the empty table
+_grow_op("prefix", GROW_RESERVE, [(GROW_RESERVE, prefix_bytes(GROW_RESERVE)), (GROW_SIZES[2], prefix_bytes(GROW_SIZES[2]))])
+
+
+@op("merkle_grow", "read", uses=["gtree"])
+def _():
+    def prepare():
+        return Expect(grow_model(GROW_SIZES[2], True).read())
+
+    def run(env):
+        tree = env.res["gtree"]                 # in whichever layout the last rebuild left it
+        tree.update(GROW_UPDATE, grow_new_leaves())         # (the same four leaves every time: idempotent)
+        return grow_read(tree)
+    return prepare, run
+
+
+# ---- 15: a gated template: ONE circuit for every input vector; every expectation is the oracle's proof of the ungated yardstick
+def _hand_seed(k):
+    return rng("gates vector %d" % k)
+
+
+@op("gates", "assign_prove", uses=["t_hand"])
+def _():
+    ORDER = (1, 2, 3, 0)
+
+    def other(k):
+        """the statement of the NEXT vector's inputs claimed for vector k's commitments"""
+        return Crossed(hand(GC.HAND_INPUTS[(k + 1) % 4], GC.HAND_VALUES[k]), hand_vector(k))
+
+    def prepare():
+        want, claims = [], []
+        for k in ORDER:
+            c = hand_vector(k)
+            proof, after = c.prove(_hand_seed(k))
+            st = (c.verify(proof), other(k).verify(proof))
+            assert st == (0, 3)
+            want.append((True, proof, after) + st)
+            claims += [c.claim(proof), other(k).claim(proof, 3)]
+        return Expect(want, claims)
+
+    def run(env):
+        t, out = env.res["t_hand"], []
+        for k in ORDER:
+            c = hand_vector(k)
+            t.assign(c.inst.v, inputs=hand_inputs(k))
+            ok = t.check().ok
+            proof, after = t.prove(c.state, c.inst.v_blinding, _hand_seed(k))
+            good = t.verify(c.state, c.coms, proof)
+            t.set_inputs(hand_inputs((k + 1) % 4))          # the verifier's half: other inputs, another statement
+            out.append((ok, proof, after, good, t.verify(c.state, c.coms, proof)))
+        t.set_inputs(hand_inputs(ORDER[-1]))                # the standing slots are this variant's own last inputs, whatever ran before
+        return out
+    return prepare, run
+
+
+@op("gates", "wave", uses=["t_hand"])
+def _():
+    K = 65                                      # item 64: one past a 64-lane block
+
+    def inputs(k):
+        return ((7 * k + 1) * 2 ** (3 * k % 250) % L, k % 2, L - 1 - k, 2 ** 252 + 9 + k)
+
+    def cases():
+        return [hand(inputs(k), ((k + 2) % L, (L - 5 * k - 1) % L), "b%d" % k) for k in range(K)]
+
+    def prepare():
+        cs = cases()
+        proofs = [c.prove(rng("gates wave %d" % k)) for k, c in enumerate(cs)]
+        return Expect((proofs, [p + (c.coms,) for p, c in zip(proofs, cs)]), [c.claim(p[0]) for c, p in zip(cs, proofs)])
+
+    def run(env):
+        pre, out = state_before(b"hand10"), []
+        for commit in (False, True):
+            items = [(c.inst.v, [], pre if commit else c.state, c.inst.v_blinding, rng("gates wave %d" % k), 0, None, [sc(x) for x in inputs(k)])
+                     for k, c in enumerate(cases())]
+            out.append(env.res["t_hand"].prove_batch_inputs(items, commit=commit))
+        return tuple(out)
+    return prepare, run
+
+
+@op("gates", "check", uses=["t_hand"])
+def _():
+    VECTOR = 2                                  # inputs (2^252 + 9, l - 1, 0, 1): the gated term 5 x_2 v_1 of row 7 is switched off
+
+    def other_values():
+        """the witness of vector 2 with its second committed value raised by one.  assign() computes every multiplier from the committed values, so no
+        assign can break a row of this circuit (no row ties a multiplier to anything but the terms it is computed from): a row breaks where the committed
+        values are not the ones the multipliers were computed from, which is what check(values) is given"""
+        v = hand_vector(VECTOR).inst.v
+        return v[:32] + sc(int.from_bytes(v[32:64], "little") + 1)
+
+    def prepare():
+        c = hand_vector(VECTOR)
+        good, bad = bpg.test_check_host(c.inst), bpg.test_check_host(c.inst, other_values())
+        assert good.ok and bad.bad_multipliers == 0 and bad.rows == [0, 5]     # the rows that name v_1 under a coefficient that is not zero
+        return Expect((bad, bad.rows, good, good.rows), checks=[(c.inst, c.inst.v, good), (c.inst, other_values(), bad)])
+
+    def run(env):
+        c, t = hand_vector(VECTOR), env.res["t_hand"]
+        t.assign(c.inst.v, inputs=hand_inputs(VECTOR))
+        bad = t.check(other_values())
+        t.assign(c.inst.v, inputs=hand_inputs(VECTOR))
+        good = t.check()
+        return bad, bad.rows, good, good.rows
+    return prepare, run
+
+
+# ---- 16: lockstep verification on one resident circuit.  Verdicts are the oracle verifier's.  The state after an item is the state after the oracle's
+# proof wherever the verifier replays what the prover absorbed: every commitment of the proof and t_x, t_x_blinding, e_blinding, but neither of the last two
+# scalars a and b, and nothing of the circuit's constants - so also for a proof with a changed a and for a good proof under wrong constants
+def _wave_seed(k):
+    return rng("verify wave item %d" % k)
+
+
+@op("verify_wave", "plain", uses=["b64"])
+def _():
+    TRUNCATED = 4
+
+    def items():
+        c = b64(1)
+        good = [c.prove(rng("verify wave plain %d" % k)) for k in range(3)]
+        bad = flipped(good[1][0], len(good[1][0]) - 40)            # byte 24 of a
+        return c, [good[0], (bad, good[1][1]), good[1], good[2], (good[0][0][:-1], None)]
+
+    def prepare():
+        c, its = items()
+        st = [c.verify(p) for p, _ in its]
+        assert st == [0, 3, 0, 0, 2]
+        return Expect((st, [after for k, (_, after) in enumerate(its) if k != TRUNCATED]), [c.claim(p, s) for (p, _), s in zip(its, st)])
+
+    def run(env):
+        c, its = items()
+        st, states = env.res["b64"].verify_batch([(c.state, c.coms, p, _wave_seed(k)) for k, (p, _) in enumerate(its)], batch_seed=rng("verify wave plain"))
+        return st, [s for k, s in enumerate(states) if k != TRUNCATED]
+    return prepare, run
+
+
+@op("verify_wave", "inputs", uses=["t_lt"])
+def _():
+    PAIRS = [(10, 500), (2**125 - 3, 2**126 - 1), (0, 1), (77, 5000)]          # the statements (and so the cached proofs) of template_ck_inputs/inputs_commit
+    STANDING = 2                                # the bound that stands in the circuit while the wave runs; the wave's LAST item brings another
+
+    def cases():
+        return [less_than(left, bound, False, "walk-%d" % k) for k, (left, bound) in enumerate(PAIRS)]
+
+    def items():
+        """(the statement a verifier with these inputs judges, the bound it is given, the proof, the state after)"""
+        cs = cases()
+        out = [(c, PAIRS[k][1]) + c.prove(rng("inputs %d" % k)) for k, c in enumerate(cs)]
+        return out + [(Crossed(cs[3], cs[0]), PAIRS[3][1]) + cs[0].prove(rng("inputs 0"))]      # a good proof and the wrong bound
+
+    def standing():
+        """two proofs judged alone under the standing bound: the one made against it, and another"""
+        cs = cases()
+        return [(cs[STANDING], cs[STANDING].prove(rng("inputs %d" % STANDING))[0]), (Crossed(cs[STANDING], cs[3]), cs[3].prove(rng("inputs 3"))[0])]
+
+    def prepare():
+        st = [c.verify(proof) for c, _, proof, _ in items()]
+        alone = [c.verify(proof) for c, proof in standing()]
+        assert st == [0, 0, 0, 0, 3] and alone == [0, 3]
+        return Expect((alone, st, [after for _, _, _, after in items()], alone),
+                      [c.claim(proof, s) for (c, _, proof, _), s in zip(items(), st)] + [c.claim(proof, s) for (c, proof), s in zip(standing(), alone)])
+
+    def run(env):
+        t = env.res["t_lt"]
+        t.set_inputs([TC.sc(PAIRS[STANDING][1])])
+        alone = lambda: [t.verify(c.state, c.coms, proof) for c, proof in standing()]
+        before = alone()
+        st, states = t.verify_batch([(c.state, c.coms, proof, _wave_seed(k), 0, None, [TC.sc(bound)]) for k, (c, bound, proof, _) in enumerate(items())],
+                                    batch_seed=rng("verify wave inputs"))
+        return before, st, states, alone()      # the wave must not have written the circuit's table
+    return prepare, run
+
+
+@op("verify_wave", "gated", uses=["t_hand"])
+def _():
+    def items():
+        """(the statement, the vector whose inputs the item brings, the proof, the state after)"""
+        out = [(hand_vector(k), k) + hand_vector(k).prove(_hand_seed(k)) for k in range(4)]
+        return out + [(Crossed(hand(GC.HAND_INPUTS[2], GC.HAND_VALUES[1]), hand_vector(1)), 2) + hand_vector(1).prove(_hand_seed(1))]
+
+    def prepare():
+        st = [c.verify(proof) for c, _, proof, _ in items()]
+        assert st == [0, 0, 0, 0, 3]
+        return Expect((st, [after for _, _, _, after in items()]), [c.claim(proof, s) for (c, _, proof, _), s in zip(items(), st)])
+
+    def run(env):
+        return env.res["t_hand"].verify_batch([(c.state, c.coms, proof, _wave_seed(k), 0, None, hand_inputs(v)) for k, (c, v, proof, _) in enumerate(items())],
+                                              batch_seed=rng("verify wave gated"))
+    return prepare, run
+
+
 FAMILIES = list(CATALOGUE)
-assert len(FAMILIES) == 13
+assert len(FAMILIES) == 16
 
 
 # ------------------------------------------------------------------------------------------------ walks
@@ -883,8 +1279,8 @@ def with_variants(families):
 
 
 def build_walk(seed):
-    """An Eulerian circuit of the complete directed graph on the families with a loop at every one (in-degree = out-degree = 13 everywhere, so one exists):
-    randomised Hierholzer.  13 x 13 edges -> 170 steps in which every ordered pair of families, a family after itself included, is adjacent exactly once."""
+    """An Eulerian circuit of the complete directed graph on the families with a loop at every one (in-degree = out-degree = 16 everywhere, so one exists):
+    randomised Hierholzer.  16 x 16 edges -> 257 steps in which every ordered pair of families, a family after itself included, is adjacent exactly once."""
     rnd = random.Random(seed)
     out = {f: rnd.sample(FAMILIES, len(FAMILIES)) for f in FAMILIES}         # the unused edges f -> g, in the order they will be taken
     stack, circuit = [rnd.choice(FAMILIES)], []
@@ -917,6 +1313,18 @@ PINNED = [
      ["template_ck_inputs/ck_batch", "verify_batch/bad_small"]),
     ("a circuit freed and uploaded again, then a proof of one that was uploaded before it",
      ["lifecycle/reupload_mimc", "prove_tabled/b64_a"]),
+    ("a relayout's new buffer (the old one freed in the middle of an append) and the arena of a folded proof, then the tree read again",
+     ["merkle_grow/prefix", "prove_folded/seed_a", "merkle_grow/read"]),
+    ("tables swapped under a growing tree and a gated template before either is touched",
+     ["lifecycle/grow", "merkle_grow/read", "gates/wave"]),
+    ("two trees on one pair of staging buffers (mk_in / mk_out): the lists of an update and the paths of the other tree in between",
+     ["merkle/update", "merkle_grow/read", "merkle/update"]),
+    ("standing slots of one template between a verification wave with per-item inputs and a proving wave",
+     ["verify_wave/inputs", "template_ck_inputs/inputs_commit", "verify_wave/inputs"]),
+    ("lv / rv and the arena sized by a verification wave between two proofs that sized them too",
+     ["prove_folded/seed_a", "verify_wave/plain", "prove_folded/seed_b"]),
+    ("coefficient class 3 (a gated two-slot term in the packed stream) between waves that never saw that class",
+     ["gates/wave", "lockstep/mixed_a", "gates/assign_prove"]),
 ]
 
 

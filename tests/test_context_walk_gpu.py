@@ -1,5 +1,5 @@
-"""One context walked through every family of entry points in many orders, byte-exact (tests/context_walk.py): three Eulerian walks of 170 steps - every
-family of operations after every family, itself included - and the pinned short orders, under four context profiles.  Every step's result is compared with
+"""One context walked through every family of entry points in many orders, byte-exact (tests/context_walk.py): three Eulerian walks of 257 steps - every
+one of the sixteen families of operations after every family, itself included - and the fifteen pinned short orders, under four context profiles.  Every step's result is compared with
 an expectation computed on the CPU before the context existed; at the end the census of device buffers, pinned buffers, streams and events is what it was.
 
 Profiles (environment knobs a context reads when it is created):

@@ -21,8 +21,9 @@ def model_factory(world, cls=W.ModelContext):
 
 
 # ------------------------------------------------------------------------------------------------ coverage and lifetimes
-def test_the_catalogue_has_thirteen_families_of_two_to_four_variants():
-    assert len(W.FAMILIES) == 13 and len(set(W.FAMILIES)) == 13
+def test_the_catalogue_has_sixteen_families_of_two_to_four_variants():
+    assert len(W.FAMILIES) == 16 and len(set(W.FAMILIES)) == 16
+    assert W.FAMILIES[13:] == ["merkle_grow", "gates", "verify_wave"] and [o.variant for o in W.CATALOGUE["repeat_join_check"]][-1] == "repeat_inputs"
     for f in W.FAMILIES:
         assert 2 <= len(W.CATALOGUE[f]) <= 4, f
     assert len({o.name for o in ALL_OPS}) == len(ALL_OPS)
@@ -31,9 +32,9 @@ def test_the_catalogue_has_thirteen_families_of_two_to_four_variants():
 @pytest.mark.parametrize("seed", WALK_SEEDS)
 def test_every_ordered_pair_of_families_is_adjacent(walks, seed):
     steps = walks[seed]
-    assert len(steps) == 13 * 13 + 1 and steps[0][0] == steps[-1][0]
+    assert len(steps) == 16 * 16 + 1 == 257 and steps[0][0] == steps[-1][0]
     pairs = {(a[0], b[0]) for a, b in zip(steps, steps[1:])}
-    assert pairs == {(f, g) for f in W.FAMILIES for g in W.FAMILIES}            # 169 pairs on 169 edges: each exactly once, a family after itself included
+    assert pairs == {(f, g) for f in W.FAMILIES for g in W.FAMILIES}            # 256 pairs on 256 edges: each exactly once, a family after itself included
     assert {"%s/%s" % s for s in steps} == set(W.OPS), "every variant of every family occurs"
     assert sum(s == ("lifecycle", "grow") for s in steps) <= W.MAX_GROWS
     assert steps == W.build_walk(seed), "a walk is a function of its seed"
@@ -44,7 +45,7 @@ def test_the_walks_differ():
 
 
 def test_pinned_orders_name_operations_and_say_why():
-    assert len(W.PINNED) >= 8
+    assert len(W.PINNED) >= 15
     for reason, names in W.PINNED:
         assert reason and all(n in W.OPS for n in names), (reason, names)
     assert ["prove_tabled", "prove_folded", "prove_tabled", "prove_folded"] in [[n.split("/")[0] for n in names] for _, names in W.PINNED]
@@ -71,6 +72,55 @@ def test_pinned_orders_do_what_their_reasons_say():
     names = pinned("freed and uploaded again")
     up, after = W.OPS[names[0]], W.OPS[names[1]]
     assert up.uploads and not set(up.uploads) & set(after.uses) and list(W.RESIDENT).index(after.uses[0]) < list(W.RESIDENT).index(up.uploads[0])
+    # the growing tree and the gated template are first touched after the grow of step 0, neither by a step that uploads it
+    late = W.first_used_after_a_grow(pinned("tables swapped under a growing tree"))
+    assert late == [("gtree", -1, 0, 1), ("t_hand", -1, 0, 2)]
+    # the tree that the relayout gave a new buffer is read again, not rebuilt, behind the folded proof
+    names = pinned("relayout")
+    assert W.OPS[names[0]].uploads == ("gtree",) and W.OPS[names[1]].family == "prove_folded" and W.OPS[names[2]].uses == ("gtree",) and not W.OPS[names[2]].uploads
+    # two different trees, neither uploaded again, in alternation
+    names = pinned("staging buffers")
+    assert [W.OPS[n].uses for n in names] == [("tree",), ("gtree",), ("tree",)] and not any(W.OPS[n].uploads for n in names)
+    # the same template on all three steps, the proving wave in the middle
+    names = pinned("standing slots")
+    assert names[0] == names[2] and {W.OPS[n].uses for n in names} == {("t_lt",)} and W.OPS[names[1]].family == "template_ck_inputs"
+    names = pinned("lv / rv")
+    assert [W.OPS[n].family for n in names] == ["prove_folded", "verify_wave", "prove_folded"] and names[0] != names[2]
+    names = pinned("coefficient class 3")
+    assert [W.OPS[n].uses for n in names] == [("t_hand",), (), ("t_hand",)] and W.OPS[names[1]].family == "lockstep"
+
+
+def test_the_sparse_tree_model_is_the_padded_tree():
+    """the model of the growing tree against brute force: the full tree over the leaves padded with the empty value to 2^11, every node by the oracle's
+    sponge; the states the appends pass through and the final one; and the reserve formula on the example of csrc/host/merkle_prefix_plan.hpp"""
+    D = W.GROW_DEPTH
+    for size, updated in ((W.GROW_SIZES[1], False), (W.GROW_SIZES[2], False), (W.GROW_SIZES[2], True)):
+        m = W.grow_model(size, updated)
+        levels = [m.heights[0] + [W.GROW_EMPTY] * ((1 << D) - size)]
+        while len(levels[-1]) > 1:
+            lo = levels[-1]
+            levels.append([O.mimc_sponge(lo[i] + lo[i + 1]) for i in range(0, len(lo), 2)])
+        assert all(m.node(s, j) == levels[s][j] for s in range(D + 1) for j in range(1 << (D - s))), (size, updated)
+        assert W.grow_empty_chain()[:D] == [levels[s][-1] for s in range(D)]         # the rightmost subtree of every height below the root holds no leaf
+        got = m.read()
+        assert got[0] == size and got[1] == levels[D][0]
+        assert got[3] == [[levels[k][(i >> k) ^ 1] for k in range(D)] for i in W.GROW_PATHS]
+        assert got[4] == [[levels[k + 1][i >> (k + 1)] for k in range(D)] for i in W.GROW_PATHS] and all(p[-1] == levels[D][0] for p in got[4])
+        assert got[5] == [levels[D - level] for level in W.GROW_LEVELS]
+    final, before = W.grow_model(606, True), W.grow_model(606, False)
+    assert [final.heights[0][i] != before.heights[0][i] for i in W.GROW_UPDATE] == [True] * 4 and final.root() != before.root()
+    assert len({W.grow_model(6, False).root(), before.root(), final.root(), W.grow_empty_chain()[D]}) == 4
+    # W_s of reserve 7 at depth 11: 7, 4, 2, 1 and eight times 1 = 22 slots, + 12 constants; of 606: 606, 303 (odd: the edge), 152, 76, 38, 19, 10, 5, 3, 2, 1, 1
+    assert W.prefix_bytes(7) == 32 * (22 + 12) and W.prefix_bytes(606) == 32 * (1216 + 12)
+    assert W.GROW_RESERVE < W.GROW_SIZES[2] == max(2 * W.GROW_RESERVE, W.GROW_SIZES[2]) and W.GROW_SIZES[1] <= W.GROW_RESERVE
+
+
+def test_no_expectation_reads_a_context():
+    """prepare() of every operation names neither the walk's environment nor a context"""
+    import inspect
+    for o in ALL_OPS:
+        src = inspect.getsource(o._prepare)
+        assert "env." not in src and "ctx." not in src and "env)" not in src, o.name
 
 
 @pytest.mark.parametrize("seed", WALK_SEEDS)
@@ -133,7 +183,7 @@ def test_expectations_stand_on_the_oracle(o):
 def test_the_catalogue_holds_good_and_bad_proofs_and_reports():
     claims = [c for o in ALL_OPS for c in o.prepare().claims]
     checks = [c for o in ALL_OPS for c in o.prepare().checks]
-    assert sum(s == 0 for _, _, s in claims) >= 40 and sum(s != 0 for _, _, s in claims) >= 20
+    assert sum(s == 0 for _, _, s in claims) >= 133 and sum(s != 0 for _, _, s in claims) >= 32
     assert {s for _, _, s in claims} == {0, O.ERR_FORMAT, O.ERR_VERIFY}
     assert any(r.ok for _, _, r in checks) and any(not r.ok for _, _, r in checks)
 
