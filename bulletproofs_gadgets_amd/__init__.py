@@ -514,13 +514,15 @@ class Context:
         raw = out.raw                 # one copy of the buffer, not one per item
         return [raw[32 * i:32 * i + 32] for i in range(count)]
 
-    def merkle_tree(self, leaves, depth=None, empty=None, reserve=None) -> "MerkleTree":
+    def merkle_tree(self, leaves, depth=None, empty=None, reserve=None, keys=None) -> "MerkleTree":
         """Without `depth`, bpg_merkle_build: the full MiMC Merkle tree over 2^depth leaves (a list of 32-byte values, or their concatenation), resident on
         the GPU.  With `depth`, bpg_merkle_build_partial: a tree of capacity 2^depth over any len(leaves) <= 2^depth leaves, none included, whose other
         leaves hold `empty` (32 bytes, taken mod l; None = zero) - the tree MerkleTree.append grows.  With `depth` and `reserve`,
         bpg_merkle_build_prefix: the same tree in the prefix layout, depth up to 32, with room for `reserve` <= min(2^depth, 2^24) leaves and about 64
-        bytes of device memory per reserved leaf; append grows the reserve as needed."""
-        return MerkleTree(self, leaves, depth, empty, reserve)
+        bytes of device memory per reserved leaf; append grows the reserve as needed.  With `depth` and `keys` (distinct ints below 2^depth, any order, one
+        per leaf; [] with no leaves: the empty keyed tree), bpg_merkle_build_keyed: leaves[i] sits at key keys[i] and every other leaf holds `empty`;
+        MerkleTree.put inserts and replaces."""
+        return MerkleTree(self, leaves, depth, empty, reserve, keys)
 
     def profile_set(self, mode):
         _chk(lib().bpg_profile_set(self._h, C.c_int32(mode)))
@@ -645,11 +647,26 @@ class Context:
 class MerkleTree:
     """A binary MiMC Merkle tree of capacity 2^depth resident on the GPU of a context (bpg_merkle_*): node = mimc_sponge([left, right]) over the children
     as they are, which is what MerkleTree256 constrains for a "(W W)" node.  Level 0 is the root, level `depth` the leaves.  It holds `size` leaves; the
-    leaves from `size` on hold one `empty` value, so every node is that of the tree over the padded list, and append() puts more leaves behind the last."""
+    leaves from `size` on hold one `empty` value, so every node is that of the tree over the padded list, and append() puts more leaves behind the last.
+    A keyed tree (`keyed` is True; Context.merkle_tree(..., keys=)) holds its leaves at arbitrary keys below 2^depth instead and `empty` everywhere else:
+    `size` is the number of keys held, put() inserts and replaces, update() replaces only, and every read works as on the other layouts."""
 
-    def __init__(self, ctx: "Context", leaves, depth=None, empty=None, reserve=None):
+    def __init__(self, ctx: "Context", leaves, depth=None, empty=None, reserve=None, keys=None):
         data = bytes(leaves) if isinstance(leaves, (bytes, bytearray)) else b"".join(_exact("leaf", x, 32) for x in leaves)
         n = len(data) // 32
+        self.keyed = keys is not None
+        if self.keyed:
+            keys = [int(k) for k in keys]
+            if depth is None:
+                raise ValueError("`keys` belong to a tree built with `depth`")
+            if reserve is not None:
+                raise ValueError("a keyed tree has no `reserve`")
+            if len(data) % 32 or len(keys) != n:
+                raise ValueError("one 32-byte leaf per key")
+            empty = None if empty is None else _exact("empty", empty, 32)
+            self.ctx, self.depth, self._h = ctx, int(depth), C.c_void_p()
+            _chk(lib().bpg_merkle_build_keyed(ctx._h, C.c_uint32(self.depth), C.c_uint64(n), (C.c_uint64 * n)(*keys) if n else None, data if n else None, empty, C.byref(self._h)))
+            return
         if depth is None and reserve is not None:
             raise ValueError("`reserve` belongs to a tree built with `depth`")
         if depth is None:
@@ -757,6 +774,44 @@ class MerkleTree:
         if len(data) != 32 * k:
             raise ValueError("one 32-byte leaf per index")
         _chk(lib().bpg_merkle_update(self.ctx._h, self._handle(), C.c_uint64(k), (C.c_uint64 * max(k, 1))(*indices), data))
+
+    def put(self, keys, leaves, return_root=False):
+        """bpg_merkle_put on a keyed tree: the leaf of a held key is replaced, a key that is not held is inserted (distinct keys, any order); only the
+        ancestors of the put keys are recomputed.  Returns how many keys were inserted, and the new root with it when return_root is set."""
+        keys = [int(k) for k in keys]
+        k = len(keys)
+        data = bytes(leaves) if isinstance(leaves, (bytes, bytearray)) else b"".join(_exact("leaf", x, 32) for x in leaves)
+        if len(data) != 32 * k:
+            raise ValueError("one 32-byte leaf per key")
+        inserted, root = C.c_uint64(), _buf(32)
+        _chk(lib().bpg_merkle_put(self.ctx._h, self._handle(), C.c_uint64(k), (C.c_uint64 * k)(*keys) if k else None, data if k else None, C.byref(inserted),
+                                  root if return_root else None))
+        return (inserted.value, root.raw) if return_root else inserted.value
+
+    def get(self, keys):
+        """bpg_merkle_get: (the leaves at `keys`, whether each key is held).  A key that is not held reads as the empty value; on a dense or prefix tree
+        a key is a leaf index, held when it is below `size`."""
+        keys = [int(k) for k in keys]
+        k = len(keys)
+        out, held = _buf(32 * k), _buf(max(k, 1))
+        _chk(lib().bpg_merkle_get(self.ctx._h, self._handle(), C.c_uint64(k), (C.c_uint64 * max(k, 1))(*keys), out, held))
+        raw, h = out.raw, held.raw
+        return [raw[32 * i:32 * i + 32] for i in range(k)], [bool(h[i]) for i in range(k)]
+
+    def keys(self, first=0, count=None):
+        """bpg_merkle_keys: held keys in ascending order, `count` of them from the `first` one (default: the rest).  Dense and prefix trees: key i = i."""
+        if count is None:
+            count = self.size - first
+        out = (C.c_uint64 * max(count, 1))()
+        _chk(lib().bpg_merkle_keys(self.ctx._h, self._handle(), C.c_uint64(first), C.c_uint64(count), out))
+        return [int(out[i]) for i in range(count)]
+
+    @property
+    def node_counts(self):
+        """bpg_merkle_node_counts of a keyed tree: ([stored nodes of height 0 (the leaves), ..., of height depth (the root)], device bytes held)."""
+        counts, b = (C.c_uint64 * (self.depth + 1))(), C.c_uint64()
+        _chk(lib().bpg_merkle_node_counts(self.ctx._h, self._handle(), counts, C.byref(b)))
+        return [int(x) for x in counts], b.value
 
     def free(self):
         if getattr(self, "_h", None):

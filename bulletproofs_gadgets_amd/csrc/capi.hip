@@ -1748,6 +1748,35 @@ bpg_status bpg_merkle_path_nodes(bpg_ctx *ctx, bpg_merkle *t, uint64_t count, co
 bpg_status bpg_merkle_update(bpg_ctx *ctx, bpg_merkle *t, uint64_t count, const uint64_t *indices, const uint8_t *leaves) {
     return guard([&] { REQUIRE(ctx && t && (count == 0 || (indices && leaves))); ctx->engine->merkle_update(t->t, count, indices, leaves); });
 }
+// ---- keyed trees: depth, pointers, key range, duplicates and the 2^24 bound are checked (and the keys sorted) before the context or the tree is looked at
+bpg_status bpg_merkle_build_keyed(bpg_ctx *ctx, uint32_t depth, uint64_t count, const uint64_t *keys, const uint8_t *leaves, const uint8_t empty[32], bpg_merkle **out) {
+    return guard([&] {
+        REQUIRE(out); *out = nullptr;
+        REQUIRE(depth >= 1 && depth <= 32 && count <= (1ull << 24) && count <= (1ull << depth) && ((keys && leaves) || count == 0));
+        const std::vector<uint32_t> order = Engine::merkle_key_order(depth, count, keys);
+        REQUIRE(ctx);
+        std::unique_ptr<bpg_merkle> h(new bpg_merkle{nullptr});
+        h->t = ctx->engine->merkle_build_keyed(depth, count, keys, leaves, empty, &order);
+        *out = h.release();
+    });
+}
+bpg_status bpg_merkle_put(bpg_ctx *ctx, bpg_merkle *t, uint64_t count, const uint64_t *keys, const uint8_t *leaves, uint64_t *inserted_out, uint8_t root_out[32]) {
+    return guard([&] {
+        REQUIRE(count <= (1ull << 24) && ((keys && leaves) || count == 0));
+        const std::vector<uint32_t> order = Engine::merkle_key_order(32, count, keys);         // the tree's own depth is checked once the tree is known to be one
+        REQUIRE(ctx && t);
+        ctx->engine->merkle_put(t->t, count, keys, leaves, inserted_out, root_out, false, &order);
+    });
+}
+bpg_status bpg_merkle_get(bpg_ctx *ctx, bpg_merkle *t, uint64_t count, const uint64_t *keys, uint8_t *leaves_out, uint8_t *held_out) {
+    return guard([&] { REQUIRE((keys && leaves_out) || count == 0); REQUIRE(ctx && t); ctx->engine->merkle_get(t->t, count, keys, leaves_out, held_out); });
+}
+bpg_status bpg_merkle_keys(bpg_ctx *ctx, bpg_merkle *t, uint64_t first, uint64_t count, uint64_t *keys_out) {
+    return guard([&] { REQUIRE(keys_out || count == 0); REQUIRE(first <= (1ull << 24) && count <= (1ull << 24)); REQUIRE(ctx && t); ctx->engine->merkle_keys(t->t, first, count, keys_out); });
+}
+bpg_status bpg_merkle_node_counts(bpg_ctx *ctx, bpg_merkle *t, uint64_t *counts_out, uint64_t *bytes_out) {
+    return guard([&] { REQUIRE(counts_out || bytes_out); REQUIRE(ctx && t); ctx->engine->merkle_node_counts(t->t, counts_out, bytes_out); });
+}
 void bpg_merkle_free(bpg_ctx *ctx, bpg_merkle *t) {
     (void)ctx;                      // the tree knows its context: its memory is released there whatever is passed here
     if (!t) return;

@@ -220,6 +220,7 @@ struct DeviceCircuit {
     X(k_join_colptr) X(k_join_entries) X(k_join_coef) X(k_witness_eval_join) X(k_witness_ck_verify_join) X(k_input_slots) X(k_input_slots_join) \
     X(k_mimc_sponge) X(k_merkle_leaves) X(k_merkle_level) X(k_merkle_top) X(k_merkle_level_list) X(k_merkle_set_leaves) X(k_merkle_paths) X(k_merkle_export) X(k_merkle_fill_empty) X(k_merkle_level_range) X(k_merkle_climb) \
     X(k_mpx_fill) X(k_mpx_range) X(k_mpx_climb) X(k_mpx_list) X(k_mpx_set_leaves) X(k_mpx_paths) X(k_mpx_export) X(k_mpx_relayout) \
+    X(k_mkx_classify) X(k_mkx_scan_sums) X(k_mkx_scan_top) X(k_mkx_scatter) X(k_mkx_merge) X(k_mkx_set_leaves) X(k_mkx_level) X(k_mkx_climb) X(k_mkx_paths) X(k_mkx_export) X(k_mkx_get) X(k_mkx_keys) X(k_mkx_gather) \
     X(k_rowview_count) X(k_rowview_fill) X(k_rowview_long) X(k_check_mul) X(k_check_rows) X(k_check_rows_long) X(k_check_count) \
     X(k_vw_exp) X(k_vw_tails) X(k_vw_flatten) X(k_vw_small) X(k_vw_scalars) X(k_vw_reduce)
 enum KernelId {
@@ -246,7 +247,7 @@ struct Engine::Impl {
     std::vector<Event> prof_pool;
     double prof_ms[KID_COUNT] = {0};
     std::vector<float> prof_wit_ms;     // the first 1024 k_witness_eval / k_witness_eval_repeat / k_witness_eval_join launches since the last reset, in launch order (a launch = a level of an assign)
-    std::vector<std::pair<int, float>> prof_merkle_ms;   // the first 512 launches of the tree-hashing kernels (k_merkle_level, _top, _level_list, _level_range, _climb, k_mpx_range, _climb, _list) since the last reset, in launch order
+    std::vector<std::pair<int, float>> prof_merkle_ms;   // the first 512 launches of the tree-hashing kernels (k_merkle_level, _top, _level_list, _level_range, _climb, k_mpx_range, _climb, _list, k_mkx_level, _climb) since the last reset, in launch order
     uint64_t prof_count[KID_COUNT] = {0};
     double prof_alg_bytes[KID_COUNT] = {0}, prof_act_bytes[KID_COUNT] = {0}, prof_fm[KID_COUNT] = {0};
     bool prof_on(int id) const { return prof_mode == 2 || (prof_mode == 1 && (id == KID_k_fold_points || id == KID_k_fold_points_reg || id == KID_k_fold_points_split || id == KID_k_fold_points_wnaf || id == KID_k_fold_points_quad || id == KID_k_fold_points_quadw || id == KID_k_fold_points_regw || id == KID_k_bucket_chunks)); }
@@ -257,7 +258,7 @@ struct Engine::Impl {
     void prof_collect() {
         if (prof_open.empty()) return;
         HIPCHK(hipStreamSynchronize(st));
-        for (ProfRec &r : prof_open) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, r.a, r.b)); prof_ms[r.id] += ms; prof_count[r.id]++; if ((r.id == KID_k_witness_eval || r.id == KID_k_witness_eval_repeat || r.id == KID_k_witness_eval_join) && prof_wit_ms.size() < 1024) prof_wit_ms.push_back(ms); if ((r.id == KID_k_merkle_level || r.id == KID_k_merkle_top || r.id == KID_k_merkle_level_list || r.id == KID_k_merkle_level_range || r.id == KID_k_merkle_climb || r.id == KID_k_mpx_range || r.id == KID_k_mpx_climb || r.id == KID_k_mpx_list) && prof_merkle_ms.size() < 512) prof_merkle_ms.emplace_back(r.id, ms); prof_pool.push_back(std::move(r.a)); prof_pool.push_back(std::move(r.b)); }
+        for (ProfRec &r : prof_open) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, r.a, r.b)); prof_ms[r.id] += ms; prof_count[r.id]++; if ((r.id == KID_k_witness_eval || r.id == KID_k_witness_eval_repeat || r.id == KID_k_witness_eval_join) && prof_wit_ms.size() < 1024) prof_wit_ms.push_back(ms); if ((r.id == KID_k_merkle_level || r.id == KID_k_merkle_top || r.id == KID_k_merkle_level_list || r.id == KID_k_merkle_level_range || r.id == KID_k_merkle_climb || r.id == KID_k_mpx_range || r.id == KID_k_mpx_climb || r.id == KID_k_mpx_list || r.id == KID_k_mkx_level || r.id == KID_k_mkx_climb) && prof_merkle_ms.size() < 512) prof_merkle_ms.emplace_back(r.id, ms); prof_pool.push_back(std::move(r.a)); prof_pool.push_back(std::move(r.b)); }
         prof_open.clear();
     }
     void prof_reset() { prof_collect(); for (int i = 0; i < KID_COUNT; i++) { prof_ms[i] = 0; prof_count[i] = 0; prof_alg_bytes[i] = prof_act_bytes[i] = prof_fm[i] = 0; } prof_wit_ms.clear(); prof_merkle_ms.clear(); }
@@ -268,6 +269,7 @@ struct Engine::Impl {
     // this context built and has not freed (the destructor releases their device memory; bpg_merkle_free then only deletes the handle)
     std::shared_ptr<MimcConstants> mimc;
     DevBuf mk_in, mk_out;
+    DevBuf mkx_dirty, mkx_fresh, mkx_flags, mkx_sums, mkx_totals, mkx_merge;    // a put into a keyed tree (hip/k_merkle_keyed.cuh): dirty lists, brand-new positions, scan scratch, a merge in place
     std::vector<DeviceMerkle *> trees;
     // check() (hip/k_check.cuh): the caller's committed values of a plain upload, the violation bitmap (a bit per row), the four counters of the report
     DevBuf chk_v, chk_bitmap, chk_report;
@@ -3960,10 +3962,28 @@ struct DeviceMerkle {
     bool prefix = false;
     MerklePrefixDims dims{};
     DevBuf etab;
+    // the keyed layout (bpg_merkle_build_keyed; host/merkle_keyed_plan.hpp): height s (0 = the leaves) holds kcnt[s] sorted positions in kpos[s] beside their
+    // values in kval[s], with room for kcap[s]; `etab` as above; `size` = kcnt[0], the keys held.  `tree` is not used.
+    bool keyed = false;
+    DevBuf kpos[MERKLE_KEYED_MAX_DEPTH + 1], kval[MERKLE_KEYED_MAX_DEPTH + 1];
+    uint32_t kcnt[MERKLE_KEYED_MAX_DEPTH + 1] = {0}, kcap[MERKLE_KEYED_MAX_DEPTH + 1] = {0};
+    void release() { tree.release(); etab.release(); for (DevBuf &b : kpos) b.release(); for (DevBuf &b : kval) b.release(); }
 };
 
 namespace {
-void merkle_orphan(DeviceMerkle *t) { t->tree.release(); t->etab.release(); t->owner = nullptr; }
+void merkle_orphan(DeviceMerkle *t) { t->release(); t->owner = nullptr; }
+// a keyed tree as its kernels take it, and the device bytes it holds: 36 bytes per entry of room at every height, and the table of constants
+MkxView mkx_view(const DeviceMerkle *t) {
+    MkxView V{};
+    V.depth = t->depth;
+    for (uint32_t s = 0; s <= t->depth; s++) { V.pos[s] = t->kpos[s].as<uint32_t>(); V.val[s] = t->kval[s].as<scm>(); V.cnt[s] = t->kcnt[s]; }
+    return V;
+}
+uint64_t mkx_bytes(const DeviceMerkle *t) {
+    uint64_t b = 32ull * (t->depth + 1);
+    for (uint32_t s = 0; s <= t->depth; s++) b += (uint64_t)t->kcap[s] * (sizeof(uint32_t) + sizeof(scm));
+    return b;
+}
 constexpr uint32_t kMerkleMaxDepth = 24;
 static_assert(MERKLE_MAX_DEPTH == kMerkleMaxDepth && MERKLE_CLIMB_PARENTS == BPG_MERKLE_TOP_PARENTS, "host/merkle_plan.hpp plans for the kernels of hip/k_mimc.cuh");
 // E_0 = empty, E_{k+1} = node(E_k, E_k) with the BPG_HD arithmetic of hip/k_mimc.cuh on the host: ~53 us a node, where the device pays a latency floor each
@@ -4117,6 +4137,7 @@ DeviceMerkle *Engine::merkle_build_partial(uint32_t depth, uint64_t size, const 
 
 void Engine::merkle_append(DeviceMerkle *t, uint64_t count, const uint8_t *leaves, uint64_t *first_index_out, uint8_t *root_out) {
     if (!t || t->owner != this) throw std::invalid_argument("merkle_append: not a tree of this context");
+    if (t->keyed) throw std::invalid_argument("merkle_append: a keyed tree has no last leaf to append behind (bpg_merkle_put inserts keys)");
     if (t->prefix) return merkle_append_prefix(t, count, leaves, first_index_out, root_out);
     if (count > (1ull << t->depth) - t->size) throw std::invalid_argument("merkle_append: the tree holds " + std::to_string(t->size) + " of 2^" + std::to_string(t->depth) + " leaves: no room for " + std::to_string(count) + " more");
     if (count && !leaves) throw std::invalid_argument("merkle_append: null leaves");
@@ -4156,7 +4177,7 @@ void Engine::merkle_free(DeviceMerkle *t) {
     if (Engine *e = t->owner) {
         (void)hipSetDevice(e->device_);
         (void)hipStreamSynchronize(e->impl_->st);
-        t->tree.release(); t->etab.release();
+        t->release();
         std::vector<DeviceMerkle *> &live = e->impl_->trees;
         live.erase(std::remove(live.begin(), live.end(), t), live.end());
     }
@@ -4170,12 +4191,15 @@ void Engine::merkle_nodes(DeviceMerkle *t, uint32_t level, uint64_t first, uint6
     if (!out) throw std::invalid_argument("merkle_nodes: null output");
     HIPCHK(hipSetDevice(device_));
     Impl &I = *impl_;
-    const scm *src = t->prefix ? nullptr : t->tree.as<scm>() + (1ull << level) + first;
+    const scm *src = (t->prefix || t->keyed) ? nullptr : t->tree.as<scm>() + (1ull << level) + first;
     const uint64_t per = 1ull << 20;
     I.mk_out.ensure((size_t)std::min(count, per) * 32);
     for (uint64_t at = 0; at < count; at += per) {          // stream order keeps a piece's kernel behind the copy of the piece before
         const uint32_t n = (uint32_t)std::min(per, count - at);
-        if (t->prefix)                                      // level 0 is the root: height depth - level; positions beyond the stored width read the table
+        if (t->keyed) {                                     // every node by lookup among the stored positions of height depth - level
+            const uint32_t s = t->depth - level;
+            BPG_LAUNCH(I, k_mkx_export, dim3(cdiv(n, 256)), dim3(256), t->kpos[s].as<uint32_t>(), t->kval[s].as<scm>(), t->kcnt[s], t->etab.as<scm>() + s, first + at, n, I.mk_out.as<uint32_t>());
+        } else if (t->prefix)                                   // level 0 is the root: height depth - level; positions beyond the stored width read the table
             BPG_LAUNCH(I, k_mpx_export, dim3(cdiv(n, 256)), dim3(256), t->tree.as<scm>(), t->dims, t->etab.as<scm>(), t->depth - level, first + at, n, I.mk_out.as<uint32_t>());
         else
             BPG_LAUNCH(I, k_merkle_export, dim3(cdiv(n, 256)), dim3(256), src + at, n, I.mk_out.as<uint32_t>());
@@ -4203,8 +4227,10 @@ void Engine::merkle_paths(DeviceMerkle *t, uint64_t count, const uint64_t *indic
     for (uint64_t at = 0; at < count; at += per) {
         const uint32_t n = (uint32_t)std::min(per, count - at);
         HIPCHK(hipMemcpyAsync(I.mk_in.p, idx.data() + at, (size_t)n * 4, hipMemcpyHostToDevice, I.st));
-        if (t->prefix)
-            BPG_LAUNCH(I, k_mpx_paths, dim3(cdiv((uint64_t)n * d, 256)), dim3(256), t->tree.as<scm>(), t->dims, t->etab.as<scm>(), I.mk_in.as<uint32_t>(), n, ancestors ? 1u : 0u, I.mk_out.as<uint32_t>());
+        if (t->keyed)
+            BPG_LAUNCH(I, k_mkx_paths, dim3(cdiv((uint64_t)n * d, 256)), dim3(256), mkx_view(t), t->etab.as<scm>(), I.mk_in.as<uint32_t>(), n, ancestors ? 1u : 0u, I.mk_out.as<uint32_t>());
+        else if (t->prefix)
+            BPG_LAUNCH(I, k_mpx_paths,dim3(cdiv((uint64_t)n * d, 256)), dim3(256), t->tree.as<scm>(), t->dims, t->etab.as<scm>(), I.mk_in.as<uint32_t>(), n, ancestors ? 1u : 0u, I.mk_out.as<uint32_t>());
         else
             BPG_LAUNCH(I, k_merkle_paths, dim3(cdiv((uint64_t)n * d, 256)), dim3(256), t->tree.as<scm>(), d, I.mk_in.as<uint32_t>(), n, ancestors ? 1u : 0u, I.mk_out.as<uint32_t>());
         HIPCHK(hipGetLastError());
@@ -4217,6 +4243,7 @@ void Engine::merkle_update(DeviceMerkle *t, uint64_t count, const uint64_t *indi
     if (!t || t->owner != this) throw std::invalid_argument("merkle_update: not a tree of this context");
     if (!count) return;
     if (!indices || !leaves) throw std::invalid_argument("merkle_update: null pointer");
+    if (t->keyed) return merkle_put(t, count, indices, leaves, nullptr, nullptr, true);       // a put restricted to held keys
     const uint32_t d = t->depth;
     if (count > (1ull << d)) throw std::invalid_argument("merkle_update: more leaves than the tree has (an index is given twice)");
     // every check first: a refused call leaves the tree as it was
@@ -4382,6 +4409,7 @@ void Engine::merkle_append_prefix(DeviceMerkle *t, uint64_t count, const uint8_t
 
 void Engine::merkle_reserve(DeviceMerkle *t, uint64_t leaves) {
     if (!t || t->owner != this) throw std::invalid_argument("merkle_reserve: not a tree of this context");
+    if (t->keyed) throw std::invalid_argument("merkle_reserve: a keyed tree grows its arrays height by height as keys are put");
     if (!t->prefix) throw std::invalid_argument("merkle_reserve: a tree in the dense layout holds all of its 2^depth leaves already");
     if (leaves > merkle_prefix_limit(t->depth)) throw std::invalid_argument("merkle_reserve: beyond min(2^depth, 2^24) leaves");
     if (leaves <= t->dims.reserve) return;
@@ -4391,8 +4419,237 @@ void Engine::merkle_reserve(DeviceMerkle *t, uint64_t leaves) {
 
 void Engine::merkle_reserved(DeviceMerkle *t, uint64_t *reserve_out, uint64_t *bytes_out) {
     if (!t || t->owner != this) throw std::invalid_argument("merkle_reserved: not a tree of this context");
+    if (t->keyed) {                                         // (held keys, bytes held)
+        if (reserve_out) *reserve_out = t->size;
+        if (bytes_out) *bytes_out = mkx_bytes(t);
+        return;
+    }
     if (reserve_out) *reserve_out = t->prefix ? t->dims.reserve : (1ull << t->depth);
     if (bytes_out) *bytes_out = t->prefix ? merkle_prefix_bytes(t->dims) : (2ull << t->depth) * sizeof(scm);
+}
+
+// ------------------------------------------------------------------------------------------------ Merkle trees in the keyed layout (hip/k_merkle_keyed.cuh)
+static_assert(MERKLE_KEYED_CLIMB_PARENTS == BPG_MERKLE_TOP_PARENTS, "host/merkle_keyed_plan.hpp plans for the one block of k_mkx_climb");
+
+// The host's whole share of a put: the permutation that sorts the keys.  Refused: a key at or beyond 2^depth, a key given twice.  No device, no tree.
+std::vector<uint32_t> Engine::merkle_key_order(uint32_t depth, uint64_t count, const uint64_t *keys) {
+    if (depth < 1 || depth > MERKLE_KEYED_MAX_DEPTH || count > MERKLE_KEYED_MAX_KEYS || (count && !keys)) throw std::invalid_argument("merkle keys: depth must be 1..32, at most 2^24 keys");
+    std::vector<uint32_t> order((size_t)count);
+    for (uint32_t i = 0; i < count; i++) {
+        if (keys[i] >> depth) throw std::invalid_argument("merkle keys: key " + std::to_string(keys[i]) + " is beyond 2^depth");
+        order[i] = i;
+    }
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return keys[a] < keys[b]; });
+    for (uint32_t i = 1; i < count; i++)
+        if (keys[order[i]] == keys[order[i - 1]]) throw std::invalid_argument("merkle keys: key " + std::to_string(keys[order[i]]) + " is given twice");
+    return order;
+}
+
+DeviceMerkle *Engine::merkle_build_keyed(uint32_t depth, uint64_t count, const uint64_t *keys, const uint8_t *leaves, const uint8_t *empty, const std::vector<uint32_t> *sorted_order) {
+    if (depth < 1 || depth > MERKLE_KEYED_MAX_DEPTH) throw std::invalid_argument("merkle_build_keyed: depth must be 1..32");
+    if (count > MERKLE_KEYED_MAX_KEYS) throw std::invalid_argument("merkle_build_keyed: more than 2^24 keys");
+    if (count && (!keys || !leaves)) throw std::invalid_argument("merkle_build_keyed: null keys or leaves");
+    std::unique_ptr<DeviceMerkle> t(new DeviceMerkle());
+    t->owner = this; t->depth = depth; t->keyed = true;
+    if (empty) { uint32_t w[8]; std::memcpy(w, empty, 32); t->empty = sc_from_words(w); }
+    t->empty_nodes = merkle_empty_chain(depth, t->empty);
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    try {
+        // the empty tree: the table of constants and no stored node; then the one mechanism
+        t->etab.ensure(t->empty_nodes.size() * sizeof(scm));
+        HIPCHK(hipMemcpyAsync(t->etab.p, t->empty_nodes.data(), t->empty_nodes.size() * sizeof(scm), hipMemcpyHostToDevice, I.st));
+        HIPCHK(hipStreamSynchronize(I.st));
+        merkle_put(t.get(), count, keys, leaves, nullptr, nullptr, false, sorted_order);
+    } catch (...) { (void)hipStreamSynchronize(I.st); throw; }         // (the buffers go with `t`, after this wait)
+    I.trees.push_back(t.get());
+    return t.release();
+}
+
+// The one mechanism of a keyed tree.  Host: sort the keys (the leaves follow), refuse duplicates and keys beyond 2^depth.  Device: the structure bottom-up
+// (classify, scan, scatter per height; one read-back of two counts per height, at most `depth` of them), then every allocation, then the merges, then the
+// hashing from plan_merkle_keyed_hash.  Nothing is stored into the tree before the last check and the last allocation.
+void Engine::merkle_put(DeviceMerkle *t, uint64_t count, const uint64_t *keys, const uint8_t *leaves, uint64_t *inserted_out, uint8_t *root_out, bool held_only,
+                        const std::vector<uint32_t> *sorted_order) {
+    if (!t || t->owner != this) throw std::invalid_argument("merkle_put: not a tree of this context");
+    if (!t->keyed) throw std::invalid_argument("merkle_put: not a keyed tree (bpg_merkle_append and bpg_merkle_update serve the dense and the prefix layout)");
+    if (count > MERKLE_KEYED_MAX_KEYS) throw std::invalid_argument("merkle_put: more than 2^24 keys");
+    if (count && (!keys || !leaves)) throw std::invalid_argument("merkle_put: null pointer");
+    const uint32_t D = t->depth;
+    uint64_t inserted = 0;
+    if (count) {
+        const uint32_t m0 = (uint32_t)count;
+        for (uint32_t i = 0; i < m0; i++)
+            if (keys[i] >> D) throw std::invalid_argument("merkle_put: key " + std::to_string(keys[i]) + " is beyond 2^depth");
+        const std::vector<uint32_t> own = (sorted_order && sorted_order->size() == m0) ? std::vector<uint32_t>() : merkle_key_order(D, count, keys);
+        const std::vector<uint32_t> &order = own.empty() ? *sorted_order : own;
+        std::vector<uint32_t> sorted(m0);
+        for (uint32_t i = 0; i < m0; i++) sorted[i] = (uint32_t)keys[order[i]];
+        std::vector<uint8_t> stage((size_t)m0 * 32);
+        for (uint32_t i = 0; i < m0; i++) std::memcpy(stage.data() + 32 * (size_t)i, leaves + 32 * (size_t)order[i], 32);
+
+        HIPCHK(hipSetDevice(device_));
+        Impl &I = *impl_;
+        const scm *rc = mimc_rc(I, device_);
+        const scm *E = t->etab.as<scm>();
+        // where the dirty list and the brand-new positions of height s go: at most min(count, what the height can hold) entries each
+        uint64_t off[MERKLE_KEYED_MAX_DEPTH + 2] = {0};
+        for (uint32_t s = 0; s <= D; s++) off[s + 1] = off[s] + std::min<uint64_t>(m0, merkle_keyed_limit(D, s));
+        const uint32_t tiles0 = (uint32_t)cdiv(m0, MERKLE_KEYED_SCAN_TILE);
+        uint32_t dirty[MERKLE_KEYED_MAX_DEPTH + 1] = {0}, fresh[MERKLE_KEYED_MAX_DEPTH + 1] = {0};
+        std::vector<DevBuf> npos(D + 1), nval(D + 1), retired;
+        try {
+            I.mkx_dirty.ensure(off[D + 1] * 4); I.mkx_fresh.ensure(off[D + 1] * 4);
+            I.mkx_flags.ensure((size_t)m0 * sizeof(uint2)); I.mkx_sums.ensure((size_t)tiles0 * sizeof(uint2)); I.mkx_totals.ensure((D + 1) * sizeof(uint2));
+            I.mk_in.ensure(stage.size());
+            uint32_t *dl = I.mkx_dirty.as<uint32_t>(), *fl = I.mkx_fresh.as<uint32_t>();
+            uint2 *flags = I.mkx_flags.as<uint2>(), *sums = I.mkx_sums.as<uint2>(), *totals = I.mkx_totals.as<uint2>();
+            HIPCHK(hipMemcpyAsync(dl, sorted.data(), (size_t)m0 * 4, hipMemcpyHostToDevice, I.st));
+            HIPCHK(hipMemcpyAsync(I.mk_in.p, stage.data(), stage.size(), hipMemcpyHostToDevice, I.st));
+            // ---- the structure, read-only on the tree: per height held or brand-new, the brand-new positions, the dirty list of the height above
+            dirty[0] = m0;
+            bool classify = true;
+            for (uint32_t s = 0; s < D; s++) {
+                const uint32_t m = dirty[s], tiles = (uint32_t)cdiv(m, MERKLE_KEYED_SCAN_TILE);
+                BPG_LAUNCH(I, k_mkx_classify, dim3(cdiv(m, 256)), dim3(256), t->kpos[s].as<uint32_t>(), t->kcnt[s], dl + off[s], m, classify ? 1u : 0u, 1u, flags);
+                BPG_LAUNCH(I, k_mkx_scan_sums, dim3(tiles), dim3(256), flags, m, sums);
+                BPG_LAUNCH(I, k_mkx_scan_top, dim3(1), dim3(256), sums, tiles, totals + s);
+                BPG_LAUNCH(I, k_mkx_scatter, dim3(tiles), dim3(256), dl + off[s], flags, m, sums, fl + off[s], dl + off[s + 1]);
+                HIPCHK(hipGetLastError());
+                uint2 tot;
+                HIPCHK(hipMemcpyAsync(&tot, totals + s, sizeof tot, hipMemcpyDeviceToHost, I.st));
+                HIPCHK(hipStreamSynchronize(I.st));
+                fresh[s] = tot.x; dirty[s + 1] = tot.y;
+                if (fresh[s] > m || !tot.y || tot.y > m || (uint64_t)tot.y > merkle_keyed_limit(D, s + 1)) throw std::logic_error("merkle_put: a scan total beyond its list");
+                if (s == 0) {
+                    if (held_only && fresh[0]) throw std::invalid_argument("merkle_update: a key that the tree does not hold (bpg_merkle_put inserts keys)");
+                    if ((uint64_t)t->kcnt[0] + fresh[0] > MERKLE_KEYED_MAX_KEYS) throw std::invalid_argument("merkle_put: the tree would hold more than 2^24 keys");
+                }
+                if (!fresh[s]) classify = false;            // a brand-new parent has only brand-new dirty children: nothing above is brand-new
+            }
+            fresh[D] = (classify && !t->kcnt[D]) ? 1u : 0u;  // the root is brand-new exactly when the tree held no key
+            const MerkleKeyedHashPlan P = plan_merkle_keyed_hash(D, dirty);
+            // ---- every allocation before the first store: new arrays for the heights that outgrow theirs, the scratch of a merge that stays in place
+            uint64_t grow_bytes = 0, scratch = 0;
+            uint32_t cap[MERKLE_KEYED_MAX_DEPTH + 1];
+            for (uint32_t s = 0; s <= D; s++) {
+                cap[s] = t->kcap[s];
+                if (!fresh[s]) continue;
+                const uint64_t need = (uint64_t)t->kcnt[s] + fresh[s];
+                if (need > merkle_keyed_limit(D, s)) throw std::logic_error("merkle_put: more positions than a height has");
+                cap[s] = merkle_keyed_capacity(t->kcap[s], need, merkle_keyed_limit(D, s));
+                if (cap[s] != t->kcap[s]) grow_bytes += (uint64_t)cap[s] * (sizeof(uint32_t) + sizeof(scm)); else scratch = std::max<uint64_t>(scratch, need);
+            }
+            if (grow_bytes) {
+                size_t free_b = 0, total_b = 0;
+                HIPCHK(hipMemGetInfo(&free_b, &total_b));
+                if (grow_bytes + (64u << 20) > free_b)
+                    throw DeviceError("merkle_put: the tree needs " + std::to_string(grow_bytes >> 20) + " MB more and the device has " + std::to_string(free_b >> 20) + " MB free");
+            }
+            for (uint32_t s = 0; s <= D; s++)
+                if (cap[s] != t->kcap[s]) { npos[s].ensure((size_t)cap[s] * sizeof(uint32_t)); nval[s].ensure((size_t)cap[s] * sizeof(scm)); }
+            I.mkx_merge.ensure(scratch * (sizeof(uint32_t) + sizeof(scm)));
+            // ---- the merges, bottom-up; a height that keeps its arrays merges into the scratch and is copied back in stream order
+            for (uint32_t s = 0; s <= D; s++) {
+                if (!fresh[s]) continue;
+                const uint32_t cnt = t->kcnt[s], total = cnt + fresh[s];
+                const uint32_t *fresh_s = fl + off[s];
+                if (s == D) HIPCHK(hipMemsetAsync(fl + off[D], 0, 4, I.st));       // the root's one position, 0, was never scattered (no launch at height D)
+                const bool grown = cap[s] != t->kcap[s];
+                uint32_t *dpos = grown ? npos[s].as<uint32_t>() : I.mkx_merge.as<uint32_t>() + 8 * (size_t)total;
+                scm *dval = grown ? nval[s].as<scm>() : I.mkx_merge.as<scm>();
+                BPG_LAUNCH(I, k_mkx_merge, dim3(cdiv(total, 256)), dim3(256), t->kpos[s].as<uint32_t>(), t->kval[s].as<scm>(), cnt, fresh_s, fresh[s], dpos, dval, E + s);
+                I.prof_note(KID_k_mkx_merge, 72.0 * total, 72.0 * total, 0.0);
+                HIPCHK(hipGetLastError());
+                if (grown) {
+                    retired.push_back(std::move(t->kpos[s])); retired.push_back(std::move(t->kval[s]));     // released after the wait below: the merge reads them
+                    t->kpos[s] = std::move(npos[s]); t->kval[s] = std::move(nval[s]);
+                    t->kcap[s] = cap[s];
+                } else {
+                    HIPCHK(hipMemcpyAsync(t->kpos[s].p, dpos, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToDevice, I.st));
+                    HIPCHK(hipMemcpyAsync(t->kval[s].p, dval, (size_t)total * sizeof(scm), hipMemcpyDeviceToDevice, I.st));
+                }
+                t->kcnt[s] = total;
+            }
+            inserted = fresh[0];
+            t->size = t->kcnt[0];
+            // ---- the hashing: the leaves, the wide heights bottom-up, the climb
+            BPG_LAUNCH(I, k_mkx_set_leaves, dim3(cdiv(m0, 256)), dim3(256), t->kpos[0].as<uint32_t>(), t->kval[0].as<scm>(), t->kcnt[0], dl, I.mk_in.as<uint32_t>(), m0);
+            for (uint32_t k = 0; k < P.n_wide; k++) {
+                const uint32_t s = P.wide[k].height;
+                if (s >= D || P.wide[k].count != dirty[s + 1]) throw std::logic_error("merkle keyed plan: a wide step that is not a dirty list");
+                BPG_LAUNCH(I, k_mkx_level, dim3(cdiv(dirty[s + 1], 256)), dim3(256), t->kpos[s].as<uint32_t>(), t->kval[s].as<scm>(), t->kcnt[s], t->kpos[s + 1].as<uint32_t>(),
+                           t->kval[s + 1].as<scm>(), t->kcnt[s + 1], dl + off[s + 1], dirty[s + 1], E + s, rc);
+                note_nodes(I, KID_k_mkx_level, dirty[s + 1]);
+            }
+            if (!P.climb || P.climb_height >= D) throw std::logic_error("merkle keyed plan: keys without a climb");
+            MkxDirty L{};
+            for (uint32_t s = P.climb_height + 1; s <= D; s++) {
+                if (dirty[s] > BPG_MERKLE_TOP_PARENTS) throw std::logic_error("merkle keyed plan: a climb height that does not fit one block");
+                L.list[s] = dl + off[s]; L.m[s] = dirty[s];
+            }
+            BPG_LAUNCH(I, k_mkx_climb, dim3(1), dim3(256), mkx_view(t), L, P.climb_height, E, rc);
+            note_nodes(I, KID_k_mkx_climb, P.climb_evals);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipStreamSynchronize(I.st));
+        } catch (...) { (void)hipStreamSynchronize(I.st); throw; }         // (`npos`, `nval` and `retired` go after this wait)
+    }
+    if (inserted_out) *inserted_out = inserted;
+    if (root_out) merkle_nodes(t, 0, 0, 1, root_out);
+}
+
+void Engine::merkle_get(DeviceMerkle *t, uint64_t count, const uint64_t *keys, uint8_t *leaves_out, uint8_t *held_out) {
+    if (!t || t->owner != this) throw std::invalid_argument("merkle_get: not a tree of this context");
+    if (!count) return;
+    if (!keys || !leaves_out) throw std::invalid_argument("merkle_get: null pointer");
+    std::vector<uint32_t> idx(count);
+    for (uint64_t i = 0; i < count; i++) {
+        if (keys[i] >> t->depth) throw std::invalid_argument("merkle_get: key " + std::to_string(keys[i]) + " is beyond 2^depth");
+        idx[i] = (uint32_t)keys[i];
+    }
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    const uint64_t per = 1ull << 20;
+    const size_t n_max = (size_t)std::min(count, per);
+    I.mk_in.ensure(n_max * 4); I.mk_out.ensure(n_max * 33);           // [leaves | held bytes]
+    for (uint64_t at = 0; at < count; at += per) {
+        const uint32_t n = (uint32_t)std::min(per, count - at);
+        HIPCHK(hipMemcpyAsync(I.mk_in.p, idx.data() + at, (size_t)n * 4, hipMemcpyHostToDevice, I.st));
+        uint8_t *held_dev = I.mk_out.as<uint8_t>() + n_max * 32;
+        if (t->keyed)
+            BPG_LAUNCH(I, k_mkx_get, dim3(cdiv(n, 256)), dim3(256), t->kpos[0].as<uint32_t>(), t->kval[0].as<scm>(), t->kcnt[0], t->etab.as<scm>(), I.mk_in.as<uint32_t>(), n, I.mk_out.as<uint32_t>(), held_dev);
+        else if (t->prefix)                                 // a leaf right of the reserve is not stored: E_0
+            BPG_LAUNCH(I, k_mkx_gather, dim3(cdiv(n, 256)), dim3(256), t->tree.as<scm>() + t->dims.off[0], (uint64_t)t->dims.width[0], t->etab.as<scm>(), I.mk_in.as<uint32_t>(), n, I.mk_out.as<uint32_t>());
+        else
+            BPG_LAUNCH(I, k_mkx_gather, dim3(cdiv(n, 256)), dim3(256), t->tree.as<scm>() + (1ull << t->depth), 1ull << t->depth, (const scm *)nullptr, I.mk_in.as<uint32_t>(), n, I.mk_out.as<uint32_t>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(leaves_out + (size_t)at * 32, I.mk_out.p, (size_t)n * 32, hipMemcpyDeviceToHost, I.st));
+        if (t->keyed && held_out) HIPCHK(hipMemcpyAsync(held_out + at, held_dev, n, hipMemcpyDeviceToHost, I.st));
+        HIPCHK(hipStreamSynchronize(I.st));
+    }
+    if (!t->keyed && held_out) for (uint64_t i = 0; i < count; i++) held_out[i] = keys[i] < t->size ? 1 : 0;         // held = index < size
+}
+
+void Engine::merkle_keys(DeviceMerkle *t, uint64_t first, uint64_t count, uint64_t *keys_out) {
+    if (!t || t->owner != this) throw std::invalid_argument("merkle_keys: not a tree of this context");
+    if (first > t->size || count > t->size - first) throw std::invalid_argument("merkle_keys: a run beyond the " + std::to_string(t->size) + " keys the tree holds");
+    if (!count) return;
+    if (!keys_out) throw std::invalid_argument("merkle_keys: null output");
+    if (!t->keyed) { for (uint64_t i = 0; i < count; i++) keys_out[i] = first + i; return; }       // key i = i
+    HIPCHK(hipSetDevice(device_));
+    Impl &I = *impl_;
+    I.mk_out.ensure((size_t)count * 8);
+    BPG_LAUNCH(I, k_mkx_keys, dim3(cdiv(count, 256)), dim3(256), t->kpos[0].as<uint32_t>(), (uint32_t)first, (uint32_t)count, I.mk_out.as<uint64_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(keys_out, I.mk_out.p, (size_t)count * 8, hipMemcpyDeviceToHost, I.st));
+    HIPCHK(hipStreamSynchronize(I.st));
+}
+
+void Engine::merkle_node_counts(DeviceMerkle *t, uint64_t *counts_out, uint64_t *bytes_out) {
+    if (!t || t->owner != this) throw std::invalid_argument("merkle_node_counts: not a tree of this context");
+    if (!t->keyed) throw std::invalid_argument("merkle_node_counts: not a keyed tree (bpg_merkle_reserved tells what the other layouts hold)");
+    if (counts_out) for (uint32_t s = 0; s <= t->depth; s++) counts_out[s] = t->kcnt[s];
+    if (bytes_out) *bytes_out = mkx_bytes(t);
 }
 
 }  // namespace bpg

@@ -307,7 +307,20 @@ public:
     // 32 x (sum of the stored widths + depth + 1) bytes.  Every call above serves such a tree; append grows the reserve when the tree outgrows it.
     DeviceMerkle *merkle_build_prefix(uint32_t depth, uint64_t reserve, uint64_t size, const uint8_t *leaves, const uint8_t *empty);
     void merkle_reserve(DeviceMerkle *t, uint64_t leaves);          // room for at least `leaves`: a new buffer, one relayout launch, the old buffer released; a dense tree is refused
-    void merkle_reserved(DeviceMerkle *t, uint64_t *reserve_out, uint64_t *bytes_out);     // a dense tree: 2^depth and its array
+    void merkle_reserved(DeviceMerkle *t, uint64_t *reserve_out, uint64_t *bytes_out);     // a dense tree: 2^depth and its array; a keyed tree: the keys held and its bytes
+    // The keyed layout (host/merkle_keyed_plan.hpp; hip/k_merkle_keyed.cuh): depth 1..32, up to 2^24 distinct keys below 2^depth, one leaf per key and `empty`
+    // everywhere else - node for node the tree merkle_build builds over that 2^depth-entry list.  Height s stores the nodes with a held key below them as
+    // sorted positions beside their values; everything else reads as an empty-subtree constant.  Every read call above serves such a tree; update takes held
+    // keys only; append and reserve refuse it.  put replaces the leaf of a held key and inserts a key that is not held (held_only: refuses the latter).
+    // merkle_key_order: the permutation that sorts the keys of one call (refuses a key beyond 2^depth and a key given twice; no device); build and put take
+    // one that the caller made already instead of sorting again.
+    static std::vector<uint32_t> merkle_key_order(uint32_t depth, uint64_t count, const uint64_t *keys);
+    DeviceMerkle *merkle_build_keyed(uint32_t depth, uint64_t count, const uint64_t *keys, const uint8_t *leaves, const uint8_t *empty, const std::vector<uint32_t> *sorted_order = nullptr);
+    void merkle_put(DeviceMerkle *t, uint64_t count, const uint64_t *keys, const uint8_t *leaves, uint64_t *inserted_out, uint8_t *root_out, bool held_only = false,
+                    const std::vector<uint32_t> *sorted_order = nullptr);
+    void merkle_get(DeviceMerkle *t, uint64_t count, const uint64_t *keys, uint8_t *leaves_out, uint8_t *held_out);       // any layout: dense and prefix hold index < size
+    void merkle_keys(DeviceMerkle *t, uint64_t first, uint64_t count, uint64_t *keys_out);                                 // held keys, ascending; dense and prefix: key i = i
+    void merkle_node_counts(DeviceMerkle *t, uint64_t *counts_out, uint64_t *bytes_out);                                   // depth + 1 stored-node counts, height 0 first; keyed trees only
 private:
     void merkle_append_prefix(DeviceMerkle *t, uint64_t count, const uint8_t *leaves, uint64_t *first_index_out, uint8_t *root_out);
 public:

@@ -44,11 +44,17 @@
 //                                       empty-subtree constants into stored, unoccupied slots), k_mpx_range (an interval of one height), k_mpx_climb (from at most 256
 //                                       dirty parents through up to 32 heights to the root in one launch), k_mpx_list + k_mpx_set_leaves (leaf updates), k_mpx_paths,
 //                                       k_mpx_export (both fall back to the tree's table of constants for a node that is not stored), k_mpx_relayout (a larger reserve)
+//       Merkle trees, keyed layout       (k_merkle_keyed.cuh; leaves at any 32-bit key, per height the sorted positions that have a held key below them beside their values,
+//                                       host/merkle_keyed_plan.hpp) the structure of a put: k_mkx_classify (held or brand-new, head flags), k_mkx_scan_sums / k_mkx_scan_top /
+//                                       k_mkx_scatter (the scan in three launches: brand-new positions and the next height's dirty list), k_mkx_merge (old and brand-new
+//                                       entries into a height's new arrays); its hashing: k_mkx_set_leaves, k_mkx_level (a height of more than 256 dirty parents),
+//                                       k_mkx_climb (from at most 256 dirty parents to the root in one launch); reads by lookup: k_mkx_paths, k_mkx_export, k_mkx_get,
+//                                       k_mkx_keys, and k_mkx_gather (bpg_merkle_get on the other two layouts)
 //       R1CS check                       (k_check.cuh; bpg_r1cs_check: which multiplier, which constraint does the resident witness break) the row-major view of the resident
 //                                       matrix, once per circuit: k_rowview_count, k_scan_blocksums / _apply, k_rowview_fill, k_rowview_long; per check: k_check_mul (a lane
 //                                       per multiplier), k_check_rows (a lane per short row, the wave's ballot = one word of the violation bitmap), k_check_rows_long (a
 //                                       wave per long row), k_check_count (bad rows and the first of them)
-// The kernels live in k_points.cuh, k_scalars.cuh, k_ipa.cuh, k_verify.cuh, k_msm.cuh, k_merge.cuh, k_batch.cuh, k_witness.cuh, k_repeat.cuh, k_join.cuh, k_mimc.cuh, k_merkle_prefix.cuh, k_check.cuh and k_vwave.cuh, included at the end of
+// The kernels live in k_points.cuh, k_scalars.cuh, k_ipa.cuh, k_verify.cuh, k_msm.cuh, k_merge.cuh, k_batch.cuh, k_witness.cuh, k_repeat.cuh, k_join.cuh, k_mimc.cuh, k_merkle_prefix.cuh, k_merkle_keyed.cuh, k_check.cuh and k_vwave.cuh, included at the end of
 // this file in that order.
 // Data layout in HBM: scalars = 8 x u32 Montgomery form, 32 B each, AoS (lane i <-> element i: 2 x 16 B coalesced
 // loads); generator tables = affine Niels (y+x, y-x, 2dxy), 96 B per point, G at [0,N) and H at [N,2N); window tables =
@@ -98,5 +104,6 @@ __device__ __forceinline__ uint32_t msm_point_index(const MsmSegs &S, uint32_t s
 #include "k_join.cuh"
 #include "k_mimc.cuh"
 #include "k_merkle_prefix.cuh"
+#include "k_merkle_keyed.cuh"
 #include "k_check.cuh"
 #include "k_vwave.cuh"

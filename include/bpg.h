@@ -1088,6 +1088,27 @@ bpg_status bpg_be_to_scalars(const uint8_t *be, uint64_t len, uint8_t *out, uint
  *   bpg_merkle_append on such a tree takes size + count <= min(2^depth, 2^24); a tree that outgrows its reserve first reserves min(that limit,
  *                          max(2 x reserve, size + count)) and then grows as above (wide launches, then one that climbs through up to 32 levels).  A
  *                          refused append leaves the tree and its reserve as they were.
+ * Keyed trees - the third layout behind the same handle: leaves at any key, for a set addressed by an arbitrary 32-bit key (a revocation list, a nullifier
+ * set, an allow-list keyed by account number).  A tree of depth 1..32 holds n <= 2^24 distinct keys below 2^depth, one leaf per key; every other leaf holds
+ * `empty`.  Node for node it is the tree bpg_merkle_build would build over the 2^depth-entry list that is `empty` everywhere but at the keys: root, nodes,
+ * paths, path_nodes, path inputs, circuits, templates and verifiers cannot tell the layouts apart, and a path of an absent key proves `empty` there.
+ * Height s above the leaves stores exactly the nodes with a held key below them (the distinct values key >> s, ascending, beside their 32-byte values); what
+ * is not stored reads as E_s.  Memory follows the sum of those counts - for random keys about n x (depth - lg n + 2) nodes of 36 bytes - plus the slack of
+ * a doubling policy per height (csrc/host/merkle_keyed_plan.hpp).
+ *   bpg_merkle_build_keyed the empty tree, then bpg_merkle_put of the `count` keys (any order) and their leaves; `empty` as above.
+ *   bpg_merkle_put         replaces the leaf of a held key and inserts a key that is not held; *inserted_out = how many were inserted, root_out = the new
+ *                          root.  The host sorts the keys; the device classifies them, merges brand-new positions into the arrays of every height
+ *                          (reallocating a height that outgrows its room), and hashes exactly the proper ancestors of the put keys, each once.  count == 0
+ *                          is BPG_OK and only fills the outputs.  A leaf equal to `empty` keeps its key held (no root or path differs from the absent key's).
+ *   bpg_merkle_get         the leaves at `count` keys (any key below 2^depth; `empty`, reduced, where none is held) and held_out[i] = 1 or 0.  On a dense
+ *                          or prefix tree: held = index < size.
+ *   bpg_merkle_keys        held keys in ascending order, the run [first, first + count) of them (first + count <= the keys held).  Dense and prefix: key i = i.
+ *   bpg_merkle_node_counts the stored nodes per height, height 0 first (depth + 1 counts), and the device bytes held (either may be NULL, not both).
+ * On a keyed tree bpg_merkle_size gives the keys held, bpg_merkle_reserved (keys held, bytes held), bpg_merkle_update takes held keys only (a key that is not
+ * held is BPG_ERR_INVALID_ARGUMENT and nothing changes); bpg_merkle_append and bpg_merkle_reserve refuse it.  bpg_merkle_put and bpg_merkle_node_counts
+ * refuse dense and prefix trees.  Refused before the device is touched: depth 0 or above 32, a NULL pointer with a non-zero count, a key >= 2^depth, a key
+ * given twice in one call, more than 2^24 keys in one call; a put that would make the tree hold more than 2^24 keys, or outgrow the device's free memory,
+ * is refused before the first store to the tree.  A refused build sets *out to NULL.
  * size > 2^depth, size + count > 2^depth and a NULL `leaves` with a non-zero count are BPG_ERR_INVALID_ARGUMENT like the rest below; a refused
  * bpg_merkle_build_partial sets *out to NULL, and a refused call leaves the tree as it was and writes no output.
  * A depth of 0 or above 24 (bpg_merkle_build_prefix: above 32; a reserve of 0, above 2^depth or above 2^24; size > reserve), a NULL pointer, an index >= 2^depth, a level above depth, nodes beyond a level and count x blocks_per_item == 0 are
@@ -1095,7 +1116,8 @@ bpg_status bpg_be_to_scalars(const uint8_t *be, uint64_t len, uint8_t *out, uint
  * it (another context's tree is BPG_ERR_INVALID_ARGUMENT); like every call on a context they are not re-entrant.  bpg_merkle_free releases the tree on the context
  * that built it, whatever ctx is passed (NULL included).  Destroying a context releases the device memory of the trees it still holds: their handles stay valid
  * for bpg_merkle_free alone, and every other call on them is BPG_ERR_INVALID_ARGUMENT.
- * Out of scope: more than 2^24 leaves held, shrinking a reserve, keyed (non-prefix) sparse trees, going under the latency floor of a narrow level (a
+ * Out of scope: more than 2^24 leaves or keys held, shrinking a reserve, removing keys from a keyed tree and reclaiming their storage, keys wider than
+ * 32 bits, sorting incoming keys on the device, hashing records into keys, going under the latency floor of a narrow level (a
  * level narrower than the device still costs one node's 1,944 dependent products: an append of a few leaves is `depth` such floors in one launch), hashing
  * records into leaves on the device, the byte-preimage padding of mimc_hash on the device (pad on the host with bpg_be_to_scalars / bpg_mimc_hash's rules
  * and hand the blocks over), flags of the file drivers, and a tree spread over more than one GPU.  (Additions to ABI version 7: no struct changes.) */
@@ -1122,6 +1144,13 @@ bpg_status bpg_merkle_paths(bpg_ctx *ctx, bpg_merkle *t, uint64_t count, const u
 bpg_status bpg_mimc_sponge_states(const uint8_t *blocks, uint64_t n_blocks, uint8_t *out /* n_blocks x 32 */);
 bpg_status bpg_merkle_path_nodes(bpg_ctx *ctx, bpg_merkle *t, uint64_t count, const uint64_t *indices, uint8_t *out /* count x depth x 32 */);
 bpg_status bpg_merkle_update(bpg_ctx *ctx, bpg_merkle *t, uint64_t count, const uint64_t *indices, const uint8_t *leaves /* count x 32 */);
+bpg_status bpg_merkle_build_keyed(bpg_ctx *ctx, uint32_t depth, uint64_t count, const uint64_t *keys, const uint8_t *leaves /* count x 32; both NULL allowed when count == 0 */,
+                                  const uint8_t empty[32] /* NULL = zero */, bpg_merkle **out);
+bpg_status bpg_merkle_put(bpg_ctx *ctx, bpg_merkle *t, uint64_t count, const uint64_t *keys, const uint8_t *leaves /* count x 32 */, uint64_t *inserted_out /* NULL allowed */,
+                          uint8_t root_out[32] /* NULL allowed */);
+bpg_status bpg_merkle_get(bpg_ctx *ctx, bpg_merkle *t, uint64_t count, const uint64_t *keys, uint8_t *leaves_out /* count x 32 */, uint8_t *held_out /* count bytes, NULL allowed */);
+bpg_status bpg_merkle_keys(bpg_ctx *ctx, bpg_merkle *t, uint64_t first, uint64_t count, uint64_t *keys_out);   /* held keys in ascending order, run [first, first + count) */
+bpg_status bpg_merkle_node_counts(bpg_ctx *ctx, bpg_merkle *t, uint64_t *counts_out /* depth + 1, height 0 first; NULL allowed */, uint64_t *bytes_out /* NULL allowed, not both */);
 void bpg_merkle_free(bpg_ctx *ctx, bpg_merkle *t);
 /* test hook: `count` 64-byte TranscriptRng draws (merlin build_rng().rekey_with_witness_bytes("v_blinding")*.finalize(seed)), after
  * `skip` draws through the generic STROBE operations; bulk != 0 uses the prover's in-register bulk path. Same bytes either way. */
