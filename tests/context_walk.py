@@ -7,8 +7,8 @@ correct only while the lifetimes never overlap in stream order.  A test of one f
 
     Op            family, variant, prepare() -> Expect (cached for the process, never touches a context), run(env) -> result, same(want, got)
     CATALOGUE     family -> its variants, in rotation order
-    build_walk    an Eulerian circuit of the complete directed graph on the families, loops included: all 16 x 16 ordered pairs are adjacent, 257 steps
-    PINNED        short hand-written orders for the interactions the engine's code suggests, each with its reason
+    build_walk    an Eulerian circuit of the complete directed graph on the families, loops included: all 17 x 17 ordered pairs are adjacent, 290 steps
+    PINNED        short hand-written orders for the interactions the engine's code suggests, each with its reason; PINNED_TWO: such orders for two contexts
     run_walk      one context (or two of one device, dealt the steps alternately), the resident set uploaded once, a comparison after every step
     replay        run_walk on a list of "family/variant" names - what a WalkMismatch prints
 
@@ -19,7 +19,8 @@ mimc_sponge, the generator chain), the device-less host assembly with the oracle
 Sizes are the smallest that take a distinct memory path and stay at N <= 1024: a 40-bit range proof (N = 64), the 64-bit BoundsCheck (n = N = 128), the
 one-block MiMC preimage (n = 972, N = 1024: 52 padding generators, the size that takes the bucket-method path once BPG_TT_LG / BPG_TT_ORIG_LG say so), the
 8-bit BoundsCheck (n = 16) and SetMembership (n = 6) for repeats and joins, the 36-multiplier checkpoint chain, LessThan against a public bound (N = 512), the
-hand-made gate circuit (n = 10, N = 16), three Inequality statements against three public values (n = 9), a depth-11 tree grown to 606 leaves in both layouts."""
+hand-made gate circuit (n = 10, N = 16), three Inequality statements against three public values (n = 9), a depth-11 tree grown to 606 leaves in both layouts,
+a depth-11 keyed tree of 122 keys (7, then 100 more past the minimum capacity of 64, then 25 of which 15 are new)."""
 import contextlib
 import copy
 import ctypes as C
@@ -33,6 +34,7 @@ from bulletproofs_gadgets_amd import workloads
 import oracle_lib as O
 import checkpoint_cases as CK
 import gate_cases as GC
+import keyed_cases as KC
 import repeat_inputs_cases as RC
 import template_inputs_cases as TC
 from test_template_repeat_host import CIRCUITS, SET_INSTANCE, bounds8_item, constant_term
@@ -402,6 +404,61 @@ def prefix_bytes(reserve):
     return 32 * (sum(max(1, -(-reserve // (1 << s))) for s in range(GROW_DEPTH + 1)) + GROW_DEPTH + 1)
 
 
+# ---- the keyed tree: depth 11, 7 -> 107 -> 122 keys, then six leaves replaced: the final state, by that history or built in one call
+KEYED_DEPTH = 11
+KEYED_EMPTY = rs("ktree empty", 0)              # non-zero, like GROW_EMPTY
+KEYED_LEVELS = (11, 7)                          # the 2,048 leaves, and the 128 nodes of height 4, where stored nodes and empty subtrees alternate
+
+
+@functools.lru_cache(maxsize=None)
+def keyed_steps():
+    """[(key, leaf), ...] of the build (seven keys as drawn, the last key of the tree among them), of the put of 100 new keys, of the put of 10 held and
+    15 new keys, and of the update of six held keys.  Key 0 is never held."""
+    draws = [k for k in KC.rand_keys(b"walk ktree", 140, KEYED_DEPTH) if k not in (0, (1 << KEYED_DEPTH) - 1)][:121]
+    build = draws[:3] + [(1 << KEYED_DEPTH) - 1] + draws[3:6]
+    more = draws[6:106]
+    mixed = build[1:4] + draws[106:114] + more[5:12] + draws[114:121]
+    update = [build[3], build[5], more[0], more[50], draws[110], draws[120]]
+    leaf = lambda tag, keys: [(k, rs("ktree %s" % tag, k)) for k in keys]
+    return leaf("build", build), leaf("more", more), leaf("mixed", mixed), leaf("update", update)
+
+
+KEYED_ABSENT = 0
+# held keys (the two ends of the tree's keys, a key of every step), absent keys beside them, the edges 0 and 2^11 - 1, the middle of the tree
+KEYED_PROBE = sorted({0, 1, 1023, 1024, 2046, 2047} | {k + d for step in keyed_steps() for k, _ in (step[0], step[-1]) for d in (0, 1) if k + d < 1 << KEYED_DEPTH})
+
+
+@functools.lru_cache(maxsize=None)
+def keyed_model():
+    """the final state, by the ORACLE's sponge: the model of tests/keyed_cases.py after the four steps"""
+    m = KC.KeyedModel(KEYED_DEPTH, KEYED_EMPTY)
+    for step in keyed_steps():
+        m.put([k for k, _ in step], [leaf for _, leaf in step])
+    held, probe = set(m.keys()), KEYED_PROBE
+    assert len(held) == 122 and KEYED_ABSENT not in held and (1 << KEYED_DEPTH) - 1 in held and any(k in held for k in probe) and any(k not in held for k in probe)
+    return m
+
+
+def keyed_model_read():
+    """what keyed_read returns of a tree in the final state"""
+    m, P = keyed_model(), KEYED_PROBE
+    sib = [m.siblings(i) for i in P]
+    return (len(m.keys()), m.root(), list(m.E), m.keys(), m.get(P), sib, [m.on_path(i) for i in P], [bpg.merkle_path_inputs(i, s, m.root()) for i, s in zip(P, sib)],
+            [m.level(level) for level in KEYED_LEVELS], m.counts())
+
+
+def keyed_read(tree):
+    P = KEYED_PROBE
+    return (tree.size, tree.root(), tree.empty_nodes(), tree.keys(), tree.get(P), tree.paths(P), tree.path_nodes(P), tree.path_inputs(P),
+            [tree.nodes(level) for level in KEYED_LEVELS], tree.node_counts[0])
+
+
+def keyed_final_tree(ctx):
+    """the final state built in ONE call over the 122 keys in ascending order (other capacities than the history's, the same nodes)"""
+    m = keyed_model()
+    return ctx.merkle_tree(m.get(m.keys())[0], depth=KEYED_DEPTH, empty=KEYED_EMPTY, keys=m.keys())
+
+
 # ------------------------------------------------------------------------------------------------ the resident set of a walk
 RESIDENT = {                                    # name -> how a context gets it; uploaded in this order ("b64" before "mimc": PINNED relies on it)
     "rp40": lambda ctx: ctx.upload(rp40().inst),
@@ -415,6 +472,7 @@ RESIDENT = {                                    # name -> how a context gets it;
     "tree": lambda ctx: ctx.merkle_tree(tree_levels(False)[0]),
     "t_hand": lambda ctx: hand_template().prover.template(ctx),
     "gtree": grow_final_tree,
+    "ktree": keyed_final_tree,
 }
 
 
@@ -1255,8 +1313,80 @@ def _():
     return prepare, run
 
 
+# ---- 17: a keyed tree: every mutating variant ends in the same final state; expectations from keyed_cases.KeyedModel (the oracle's sponge, memoised)
+def _keyed_rebuild(env):
+    """free + build over seven unsorted keys + 100 new keys (arrays retired and replaced) + 25 mixed keys (merged in the scratch) + the update
+    -> (the keys each put inserted, the root after each step, node_counts at the end)"""
+    env.res["ktree"].free()
+    steps = keyed_steps()
+    tree = env.res["ktree"] = env.ctx.merkle_tree([leaf for _, leaf in steps[0]], depth=KEYED_DEPTH, empty=KEYED_EMPTY, keys=[k for k, _ in steps[0]])
+    inserted, roots = [], [tree.root()]
+    for step in steps[1:3]:
+        n, root = tree.put([k for k, _ in step], [leaf for _, leaf in step], return_root=True)
+        inserted.append(n); roots.append(root)
+    tree.update([k for k, _ in steps[3]], [leaf for _, leaf in steps[3]])
+    roots.append(tree.root())
+    return inserted, roots, tree.node_counts
+
+
+@op("merkle_keyed", "rebuild", uses=["ktree"], uploads=["ktree"], effect=lambda env: env.reupload("ktree"))
+def _():
+    def prepare():
+        m, inserted, roots, caps = KC.KeyedModel(KEYED_DEPTH, KEYED_EMPTY), [], [], [0] * (KEYED_DEPTH + 1)
+        kinds = []
+        for step in keyed_steps():
+            before = m.counts()
+            inserted.append(m.put([k for k, _ in step], [leaf for _, leaf in step])[0])
+            roots.append(m.root())
+            kind, caps = KC.merge_kinds(caps, before, m.counts(), KEYED_DEPTH)
+            kinds.append(kind[0])
+        # what the steps are for: the 100 new keys outgrow the minimum capacity at the leaves, the 25 mixed keys fit the room that made, the update inserts nothing
+        assert kinds == ["grows", "grows", "in place", None] and inserted == [7, 100, 15, 0] and caps[0] == 2 * KC.MIN_CAPACITY
+        assert roots[-1] == keyed_model().root() and m.counts() == keyed_model().counts()
+        return Expect((inserted[1:3], roots, (m.counts(), 36 * sum(caps) + 32 * (KEYED_DEPTH + 1)), keyed_model_read()))
+
+    def run(env):
+        return _keyed_rebuild(env) + (keyed_read(env.res["ktree"]),)
+    return prepare, run
+
+
+@op("merkle_keyed", "refuse", uses=["ktree"])
+def _():
+    def calls(tree):
+        absent, held = KEYED_ABSENT, keyed_steps()[3][0][0]
+        return [lambda: tree.update([held, absent], [sc(1), sc(2)]),            # refused after the structure of height 0 ran: a key that is not held
+                lambda: tree.put([held, absent, held], [sc(1), sc(2), sc(3)]),  # a key given twice
+                lambda: tree.put([absent, 1 << KEYED_DEPTH], [sc(1), sc(2)])]   # a key of 2^depth
+
+    def prepare():
+        return Expect(([ERR_INVALID] * 3, keyed_model_read()))
+
+    def run(env):
+        tree, st = env.res["ktree"], []
+        for call in calls(tree):
+            try:
+                call()
+                st.append(0)
+            except bpg.BpgError as e:
+                st.append(e.status)
+        return st, keyed_read(tree)
+    return prepare, run
+
+
+@op("merkle_keyed", "read", uses=["ktree"])
+def _():
+    def prepare():
+        return Expect(keyed_model_read())
+
+    def run(env):
+        tree = env.res["ktree"]
+        tree.update([k for k, _ in keyed_steps()[3]], [leaf for _, leaf in keyed_steps()[3]])      # (the same six leaves every time: idempotent)
+        return keyed_read(tree)
+    return prepare, run
+
+
 FAMILIES = list(CATALOGUE)
-assert len(FAMILIES) == 16
+assert len(FAMILIES) == 17
 
 
 # ------------------------------------------------------------------------------------------------ walks
@@ -1279,8 +1409,8 @@ def with_variants(families):
 
 
 def build_walk(seed):
-    """An Eulerian circuit of the complete directed graph on the families with a loop at every one (in-degree = out-degree = 16 everywhere, so one exists):
-    randomised Hierholzer.  16 x 16 edges -> 257 steps in which every ordered pair of families, a family after itself included, is adjacent exactly once."""
+    """An Eulerian circuit of the complete directed graph on the families with a loop at every one (in-degree = out-degree = 17 everywhere, so one exists):
+    randomised Hierholzer.  17 x 17 edges -> 290 steps in which every ordered pair of families, a family after itself included, is adjacent exactly once."""
     rnd = random.Random(seed)
     out = {f: rnd.sample(FAMILIES, len(FAMILIES)) for f in FAMILIES}         # the unused edges f -> g, in the order they will be taken
     stack, circuit = [rnd.choice(FAMILIES)], []
@@ -1325,6 +1455,20 @@ PINNED = [
      ["prove_folded/seed_a", "verify_wave/plain", "prove_folded/seed_b"]),
     ("coefficient class 3 (a gated two-slot term in the packed stream) between waves that never saw that class",
      ["gates/wave", "lockstep/mixed_a", "gates/assign_prove"]),
+    ("a keyed rebuild behind a prefix rebuild: the put stages its leaves in mk_in and exports its roots through mk_out right after an append used both, and its hashing follows k_mpx_* in the tree-hashing profile slots",
+     ["merkle_grow/prefix", "merkle_keyed/rebuild", "merkle_grow/read", "merkle_keyed/read"]),
+    ("a keyed rebuild ahead of a prefix rebuild: the append finds mk_in and mk_out as the put's leaves, paths and levels left them, and both trees are read again",
+     ["merkle_keyed/rebuild", "merkle_grow/prefix", "merkle_keyed/read", "merkle_grow/read"]),
+    ("a refused update stops after the structure of height 0 wrote the dirty list, the flags, the tile sums and the totals: the next put trusts none of it, and a folded proof takes the arena in between",
+     ["merkle_keyed/refuse", "merkle_keyed/read", "prove_folded/seed_a", "merkle_keyed/rebuild", "merkle_keyed/refuse", "merkle_keyed/read"]),
+    ("the scratch of a keyed put (mkx_dirty .. mkx_merge) sized by a rebuild, then a put of one tile into it after the dense tree's update went through the shared mk_in / mk_out",
+     ["merkle_keyed/rebuild", "merkle/update", "merkle_keyed/read", "merkle_keyed/rebuild"]),
+]
+
+# orders for TWO contexts of one device (step i goes to context i mod 2)
+PINNED_TWO = [
+    ("a keyed rebuild dealt to the second context: every context has put scratch of its own, and the first context's tree, last touched before the other's rebuild, reads back unchanged",
+     ["merkle_keyed/read", "merkle_keyed/rebuild", "merkle_keyed/read", "merkle_keyed/read", "merkle_grow/read", "merkle_keyed/refuse", "merkle_keyed/read", "merkle_keyed/rebuild"]),
 ]
 
 

@@ -1,10 +1,14 @@
 """What the tests of keyed MiMC Merkle trees share (test_merkle_keyed_host.py, test_merkle_keyed_gpu.py): a model of the layout hashed by the oracle's
-sponge, brute force over the full padded list, and the catalogue of key sets.
+sponge, brute force over the full padded list, the catalogue of key sets, and the put scenarios (a base and one or two puts that reach one path of the
+structure phase each: tiles_mixed, in_place, second_trip) with the integer-only model of what a put classifies, scans and merges.
 
 The model is the layout as include/bpg.h states it: per height s (0 = the leaves) a dict {position: value} of the nodes that have a held key below them;
 what is absent reads as E_s.  A put writes the leaves and recomputes the proper ancestors of the put keys, each once, bottom-up; it returns how many keys
 were inserted and how often it evaluated the node function, height by height: |{k >> s : k put}| for s = 1..depth."""
+import collections
+import functools
 import hashlib
+import random
 import oracle_lib as O
 import pyref as R
 
@@ -156,3 +160,180 @@ def chosen_sets(depth):
 
 
 DEEP_KEYS = [0, 1, 2**31 - 1, 2**31, 2**32 - 2, 2**32 - 1]
+
+
+# ---------------------------------------------------------------------------------------------------------------- put scenarios, and what of a put is integers only
+TILE = 1024                                                    # MERKLE_KEYED_SCAN_TILE: the flags one block of the scan kernels covers
+TOP_TILES = 256                                                # tile sums k_mkx_scan_top scans per trip
+MIN_CAPACITY = 64                                              # MERKLE_KEYED_MIN_CAPACITY
+Scenario = collections.namedtuple("Scenario", "name depth base puts")      # base: the keys the tree is built over; puts: [(keys, "held" | "new" | "mixed")]
+
+
+def put_flags(held, keys):
+    """flags.x of k_mkx_classify at height 0, in the order the device sees the put: per SORTED key 1 when it is brand-new (not held)"""
+    return [0 if k in held else 1 for k in sorted(keys)]
+
+
+def tile_counts(flags):
+    """per scan tile (the flags it covers, how many of them are set)"""
+    return [(len(flags[i:i + TILE]), sum(flags[i:i + TILE])) for i in range(0, len(flags), TILE)]
+
+
+def put_lists(held, keys, depth):
+    """per height s = 0..depth of a put of `keys` into a tree that holds `held`: (the dirty positions |{k >> s}|, how many of them are brand-new), by sets"""
+    out = []
+    for s in range(depth + 1):
+        stored, dirty = {k >> s for k in held}, {k >> s for k in keys}
+        out.append((len(dirty), len(dirty - stored)))
+    return out
+
+
+def put_lists_np(held, keys, depth):
+    """put_lists by numpy.unique and numpy.isin on integer arrays (nothing is hashed): what depth 19 needs to stay quick"""
+    import numpy as np
+    h, k, out = np.unique(np.asarray(held, dtype=np.int64)), np.unique(np.asarray(keys, dtype=np.int64)), []
+    for s in range(depth + 1):
+        out.append((len(k), int(len(k) - np.isin(k, h, assume_unique=True).sum())))
+        h, k = np.unique(h >> 1), np.unique(k >> 1)
+    return out
+
+
+def counts_np(held, depth):
+    """counts_of by numpy.unique"""
+    import numpy as np
+    h, out = np.unique(np.asarray(held, dtype=np.int64)), []
+    for s in range(depth + 1):
+        out.append(len(h))
+        h = np.unique(h >> 1)
+    return out
+
+
+def classified(lists):
+    """the heights Engine::merkle_put runs k_mkx_classify at with classify == 1: height 0, and every height up to and including the first that finds no
+    brand-new position.  Above it flags.x is written as zeros without a lookup (classify == 0); the root (height depth) has no launch."""
+    out = []
+    for s, (_, fresh) in enumerate(lists[:-1]):
+        out.append(s)
+        if not fresh:
+            break
+    return out
+
+
+def capacity(cap, need, limit):
+    """merkle_keyed_capacity of csrc/host/merkle_keyed_plan.hpp"""
+    return cap if need <= cap else max(need, min(limit, max(MIN_CAPACITY, 2 * cap, need)))
+
+
+def capacities(caps, counts, depth):
+    """the room per height after a put that leaves `counts` nodes stored in arrays that had room for `caps`"""
+    return [capacity(c, n, min(1 << (depth - s), 1 << 24)) for s, (c, n) in enumerate(zip(caps, counts))]
+
+
+def merge_kinds(caps, before, after, depth):
+    """per height of a put that takes the stored counts from `before` to `after`: None (no brand-new position: no merge), "grows" (new arrays, the old
+    ones retired) or "in place" (merged into the context's scratch and copied back) -> (the kinds, the room afterwards)"""
+    new_caps = capacities(caps, after, depth)
+    return [None if a == b else ("grows" if nc != c else "in place") for c, nc, b, a in zip(caps, new_caps, before, after)], new_caps
+
+
+# the pairs of "tiles mixed": what the two keys 2q, 2q + 1 of a pair are.  '.' not held, not put; 'h' held, not put; 'H' held and put; 'N' not held and put
+# (brand-new).  A pair with an 'N' has an 'h' or 'H' beside it, so EVERY dirty position of height 1 is held: height 1 is the first height without a
+# brand-new position and everything above runs with classify == 0.  The weights keep the base near 3,000 keys.
+_PAIRS = (("HH", 1.0), ("HN", 5.0), ("NH", 5.0), ("H.", 0.75), (".H", 0.75), ("Hh", 0.1), ("hH", 0.1), ("Nh", 0.5), ("hN", 0.5), ("..", 0.5), ("h.", 0.05), (".h", 0.05))
+_TILES_SEED = 13
+
+
+def _tiles_rule(i, flag, flags):
+    """may sorted put key i carry this brand-new flag?  tile 0 all held, tile 1 all brand-new, a change at 2,047 | 2,048 and at 3,071 | 3,072"""
+    if i < TILE:
+        return flag == 0
+    if i < 2 * TILE:
+        return flag == 1
+    if i == 2 * TILE:
+        return flag == 0
+    if i == 3 * TILE:
+        return flag != flags[i - 1]
+    return i < 4 * TILE
+
+
+@functools.lru_cache(maxsize=None)
+def tiles_mixed(last):
+    """Depth 13: a base of about 3,000 keys and ONE put of 4,097 keys whose brand-new flags, in sorted order, are by scan tile: none, all, irregular,
+    irregular, and a tile of one flag - `last` = "new" or "held" says which.  Both variants share the base and the first 4,096 keys.  The pairs of keys
+    are drawn left to right from a seeded generator, each kind of pair (_PAIRS) allowed where _tiles_rule allows its flags."""
+    assert last in ("new", "held")
+    depth, rnd = 13, random.Random(_TILES_SEED)
+    base, put, flags, q = [], [], [], 0
+    while len(put) < 4 * TILE:
+        def fits(kind):
+            f = list(flags)
+            for c in kind:
+                if c in "HN":
+                    if not _tiles_rule(len(f), 1 if c == "N" else 0, f):
+                        return False
+                    f.append(1 if c == "N" else 0)
+            return True
+        allowed = [(kind, 8 * w if kind == "HH" and len(put) < TILE else w) for kind, w in _PAIRS if fits(kind)]      # (tile 0 has no "HN": mostly "HH" there)
+        x = rnd.random() * sum(w for _, w in allowed)
+        for kind, w in allowed:
+            x -= w
+            if x < 0:
+                break
+        for side, c in enumerate(kind):
+            if c in "hH":
+                base.append(2 * q + side)
+            if c in "HN":
+                put.append(2 * q + side); flags.append(1 if c == "N" else 0)
+        q += 1
+    base.append(2 * q)                                          # the pair of the last key: its left key is held, its right key is not
+    put.append(2 * q + (1 if last == "new" else 0))
+    assert 2 * q + 1 < 1 << depth
+    rnd.shuffle(base)
+    return Scenario("tiles mixed, the last key %s" % last, depth, tuple(base), ((tuple(put), "mixed"),))
+
+
+@functools.lru_cache(maxsize=None)
+def in_place():
+    """Depth 13: 3,000 keys; 1,500 new ones, which make the low heights outgrow their arrays (height 0: 3,000 -> room for 6,000); then 1,000 keys of which
+    500 are held, which fit the room there is: every height that gains a position merges in the context's scratch, each with another total"""
+    keys = rand_keys(b"in place", 5000, 13)
+    base, more, late = keys[:3000], keys[3000:4500], keys[4500:]
+    mixed = base[100:400] + late[:250] + more[200:400] + late[250:]
+    return Scenario("in place", 13, tuple(base), ((tuple(more), "new"), (tuple(mixed), "mixed")))
+
+
+@functools.lru_cache(maxsize=None)
+def second_trip(last):
+    """Depth 19: a base of 2^17 keys; put A of exactly 262,144 keys = 256 scan tiles, ONE trip of k_mkx_scan_top; put B of exactly 262,145 keys = 257 tiles:
+    the second trip holds one tile of one flag, the largest key of B, which is brand-new or held as `last` says.  100,000 keys of A and 130,000 of the
+    other keys of B are held when they are put.  Keys as drawn, not sorted."""
+    import numpy as np
+    assert last in ("new", "held")
+    depth, n = 19, 1 << 19
+    rs = np.random.RandomState(19)
+    perm = rs.permutation(n)
+    base, rest = perm[:1 << 17], perm[1 << 17:]
+    a = np.concatenate([base[:100000], rest[:162144]])
+    rs.shuffle(a)
+    held, free = np.concatenate([base, rest[:162144]]), rest[162144:]
+    top = {"held": int(held.max()), "new": int(free.max())}
+    below = min(top.values())                                    # every other key of B is below both candidates for its last key
+    held_part, new_part = rs.permutation(held), free
+    b = np.concatenate([held_part[held_part < below][:130000], new_part[new_part < below][:132144], [top[last]]])
+    rs.shuffle(b)
+    assert len(a) == 262144 and len(b) == 262145
+    return Scenario("second trip, the last key %s" % last, depth, tuple(base.tolist()), ((tuple(a.tolist()), "mixed"), (tuple(b.tolist()), "mixed")))
+
+
+def scenario_states(sc):
+    """the keys held before every put of a scenario, and after the last one: [set, ...]"""
+    held, out = set(sc.base), []
+    for keys, _ in sc.puts:
+        out.append(set(held))
+        held |= set(keys)
+    return out + [held]
+
+
+def kind_of(held, keys):
+    fresh = sum(1 for k in keys if k not in held)
+    return "held" if not fresh else ("new" if fresh == len(keys) else "mixed")

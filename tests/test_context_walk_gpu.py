@@ -1,5 +1,6 @@
-"""One context walked through every family of entry points in many orders, byte-exact (tests/context_walk.py): three Eulerian walks of 257 steps - every
-one of the sixteen families of operations after every family, itself included - and the fifteen pinned short orders, under four context profiles.  Every step's result is compared with
+"""One context walked through every family of entry points in many orders, byte-exact (tests/context_walk.py): three Eulerian walks of 290 steps - every
+one of the seventeen families of operations after every family, itself included - and the nineteen pinned short orders, under four context profiles, and the
+pinned order for two contexts.  Every step's result is compared with
 an expectation computed on the CPU before the context existed; at the end the census of device buffers, pinned buffers, streams and events is what it was.
 
 Profiles (environment knobs a context reads when it is created):
@@ -70,6 +71,14 @@ def test_pinned_orders(monkeypatch, profile):
             assert seen["tt_orig_lg"] == {14} and seen["merge_equal"] == {1}, (reason, seen)
         else:
             assert seen["tt_orig_lg"] == {6} and seen["tt_lg"] == {4} and seen["merge_equal"] == {1}, (reason, seen)
+
+
+def test_pinned_orders_on_two_contexts():
+    for reason, names in W.PINNED_TWO:
+        try:
+            W.run_walk(make_context, names, contexts=2)
+        except W.WalkMismatch as e:
+            raise AssertionError("pinned order for two contexts (%s): %s" % (reason, e)) from e
 
 
 def test_original_tables_are_found_again_after_a_folded_proof(monkeypatch):

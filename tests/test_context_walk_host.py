@@ -21,9 +21,10 @@ def model_factory(world, cls=W.ModelContext):
 
 
 # ------------------------------------------------------------------------------------------------ coverage and lifetimes
-def test_the_catalogue_has_sixteen_families_of_two_to_four_variants():
-    assert len(W.FAMILIES) == 16 and len(set(W.FAMILIES)) == 16
-    assert W.FAMILIES[13:] == ["merkle_grow", "gates", "verify_wave"] and [o.variant for o in W.CATALOGUE["repeat_join_check"]][-1] == "repeat_inputs"
+def test_the_catalogue_has_seventeen_families_of_two_to_four_variants():
+    assert len(W.FAMILIES) == 17 and len(set(W.FAMILIES)) == 17
+    assert W.FAMILIES[13:] == ["merkle_grow", "gates", "verify_wave", "merkle_keyed"] and [o.variant for o in W.CATALOGUE["merkle_keyed"]] == ["rebuild", "refuse", "read"]
+    assert [o.variant for o in W.CATALOGUE["repeat_join_check"]][-1] == "repeat_inputs"
     for f in W.FAMILIES:
         assert 2 <= len(W.CATALOGUE[f]) <= 4, f
     assert len({o.name for o in ALL_OPS}) == len(ALL_OPS)
@@ -32,9 +33,9 @@ def test_the_catalogue_has_sixteen_families_of_two_to_four_variants():
 @pytest.mark.parametrize("seed", WALK_SEEDS)
 def test_every_ordered_pair_of_families_is_adjacent(walks, seed):
     steps = walks[seed]
-    assert len(steps) == 16 * 16 + 1 == 257 and steps[0][0] == steps[-1][0]
+    assert len(steps) == 17 * 17 + 1 == 290 and steps[0][0] == steps[-1][0]
     pairs = {(a[0], b[0]) for a, b in zip(steps, steps[1:])}
-    assert pairs == {(f, g) for f in W.FAMILIES for g in W.FAMILIES}            # 256 pairs on 256 edges: each exactly once, a family after itself included
+    assert pairs == {(f, g) for f in W.FAMILIES for g in W.FAMILIES}            # 289 pairs on 289 edges: each exactly once, a family after itself included
     assert {"%s/%s" % s for s in steps} == set(W.OPS), "every variant of every family occurs"
     assert sum(s == ("lifecycle", "grow") for s in steps) <= W.MAX_GROWS
     assert steps == W.build_walk(seed), "a walk is a function of its seed"
@@ -45,8 +46,8 @@ def test_the_walks_differ():
 
 
 def test_pinned_orders_name_operations_and_say_why():
-    assert len(W.PINNED) >= 15
-    for reason, names in W.PINNED:
+    assert len(W.PINNED) >= 19 and len(W.PINNED_TWO) >= 1
+    for reason, names in W.PINNED + W.PINNED_TWO:
         assert reason and all(n in W.OPS for n in names), (reason, names)
     assert ["prove_tabled", "prove_folded", "prove_tabled", "prove_folded"] in [[n.split("/")[0] for n in names] for _, names in W.PINNED]
 
@@ -88,6 +89,52 @@ def test_pinned_orders_do_what_their_reasons_say():
     assert [W.OPS[n].family for n in names] == ["prove_folded", "verify_wave", "prove_folded"] and names[0] != names[2]
     names = pinned("coefficient class 3")
     assert [W.OPS[n].uses for n in names] == [("t_hand",), (), ("t_hand",)] and W.OPS[names[1]].family == "lockstep"
+    # the keyed rebuild directly after the prefix rebuild, and directly before it; both trees are then read, not rebuilt
+    names = pinned("behind a prefix rebuild")
+    assert names[:2] == ["merkle_grow/prefix", "merkle_keyed/rebuild"] and [W.OPS[n].uploads for n in names[2:]] == [(), ()] and {W.OPS[n].uses for n in names[2:]} == {("gtree",), ("ktree",)}
+    names = pinned("ahead of a prefix rebuild")
+    assert names[:2] == ["merkle_keyed/rebuild", "merkle_grow/prefix"] and [W.OPS[n].uploads for n in names[2:]] == [(), ()] and {W.OPS[n].uses for n in names[2:]} == {("gtree",), ("ktree",)}
+    # the refusals, the tree read behind them, then a proving family
+    names = pinned("a refused update")
+    assert names[:2] == ["merkle_keyed/refuse", "merkle_keyed/read"] and W.OPS[names[2]].family == "prove_folded" and not W.OPS[names[0]].uploads
+    names = pinned("sized by a rebuild")
+    assert [W.OPS[n].uses for n in names] == [("ktree",), ("tree",), ("ktree",), ("ktree",)]
+    # two contexts: the rebuild (an odd step) is the second context's, and the first context reads its own tree before and after it
+    (reason, names), = W.PINNED_TWO
+    first, second = names[0::2], names[1::2]
+    assert second[0] == "merkle_keyed/rebuild" and first[0] == first[1] == "merkle_keyed/read" and "merkle_keyed/rebuild" not in first[:3]
+    assert "merkle_keyed/read" in second[1:] and W.OPS[second[0]].uploads == ("ktree",)
+
+
+def test_the_keyed_tree_model_is_the_padded_tree():
+    """the final state of the keyed tree against brute force over the 2^11 padded leaves (the oracle's sponge); what the steps of a rebuild are for, by
+    integers: the second step makes the leaves outgrow the minimum capacity, the third fits the room that made and has both kinds of key"""
+    K, D = W.KC, W.KEYED_DEPTH
+    steps = W.keyed_steps()
+    held = {}
+    for step in steps:
+        held.update(step)
+    m = W.keyed_model()
+    want = K.brute_levels(D, held, W.KEYED_EMPTY)
+    assert all(m.level(level) == want[level] for level in range(D + 1)) and m.keys() == sorted(held) and m.counts() == K.counts_of(held, D)
+    m.check_invariant()
+    sizes, kinds, now = [], [], set()
+    for step in steps:
+        keys = [k for k, _ in step]
+        assert len(set(keys)) == len(keys)
+        kinds.append(K.kind_of(now, keys))
+        now |= set(keys)
+        sizes.append(len(now))
+    assert sizes == [7, 107, 122, 122] and kinds == ["new", "new", "mixed", "held"] and [k for k, _ in steps[0]] != sorted(k for k, _ in steps[0])
+    assert sizes[0] < K.MIN_CAPACITY < sizes[1] and sizes[2] <= 2 * K.MIN_CAPACITY
+    got = W.keyed_model_read()
+    assert got[0] == 122 and got[1] == want[0][0] and got[3] == sorted(held)
+    assert got[4] == ([want[D][i] for i in W.KEYED_PROBE], [i in held for i in W.KEYED_PROBE]) and {0, 2**D - 1} <= set(W.KEYED_PROBE)
+    assert got[5] == [[want[D - s][(i >> s) ^ 1] for s in range(D)] for i in W.KEYED_PROBE]
+    assert got[6] == [[want[D - s][i >> s] for s in range(1, D + 1)] for i in W.KEYED_PROBE]
+    assert got[8] == [want[level] for level in W.KEYED_LEVELS]
+    level7 = [p in {k >> 4 for k in held} for p in range(128)]
+    assert any(level7) and not all(level7)                                   # a whole level with stored nodes and empty subtrees
 
 
 def test_the_sparse_tree_model_is_the_padded_tree():
@@ -209,7 +256,7 @@ def direct_check(inst, v, max_rows=16):
 
 # ------------------------------------------------------------------------------------------------ the harness can fail
 def all_walks(walks):
-    return [(("walk %d" % seed), steps) for seed, steps in walks.items()] + [(reason, names) for reason, names in W.PINNED]
+    return [(("walk %d" % seed), steps) for seed, steps in walks.items()] + [(reason, names) for reason, names in W.PINNED + W.PINNED_TWO]
 
 
 def test_the_model_context_passes_every_walk(walks):

@@ -2,8 +2,8 @@
 bpg_merkle_* call on such a tree; the kernels of csrc/hip/k_merkle_keyed.cuh with the index rules of csrc/host/merkle_keyed_plan.hpp).
 
 Up to depth 16 the reference is the dense tree of the padded list on the same device (Context.merkle_tree(padded, depth=...): code this layout does not
-touch): every output is compared byte for byte.  Beyond that it is the model of tests/keyed_cases.py, hashed by the oracle's sponge.  There are no
-tolerances.
+touch): every output is compared byte for byte - and again at depth 19, where a put has more than 256 scan tiles (section 10: the put scenarios of
+tests/keyed_cases.py, compared whole).  At depth 32 it is the model of tests/keyed_cases.py, hashed by the oracle's sponge.  There are no tolerances.
 
 The census of live resources is process-wide, so the scenario that ends with a census of zero runs in a child process: this file run as
 `python tests/test_merkle_keyed_gpu.py child` prints one JSON line."""
@@ -113,9 +113,10 @@ def logged(ctx, fn):
     return res, {k: rep.get(k, {}).get("count", 0) for k in names}, {k: rep.get(k, {}).get("field_mults", 0) / NODE_PRODUCTS for k in names}
 
 
-def check_log(count, evals, keys, depth):
-    """what a put of `keys` launches and hashes: the model's evaluations; one launch per height above 256 dirty parents, and one climb"""
-    want = K.evals_of(keys, depth) if keys else [0] * depth
+def check_log(count, evals, keys, depth, want=None):
+    """what a put of `keys` launches and hashes: the model's evaluations (`want`, where the caller has them already); one launch per height above 256 dirty
+    parents, and one climb"""
+    want = want or (K.evals_of(keys, depth) if keys else [0] * depth)
     assert evals["k_mkx_level"] + evals["k_mkx_climb"] == sum(want), (evals, want)
     assert evals["k_mkx_level"] == sum(m for m in want if m > K.TOP)
     assert count["k_mkx_level"] + count["k_mkx_climb"] == K.hashing_launches(want), (count, want)
@@ -260,6 +261,136 @@ def test_put_600_scattered_keys_depth12(ctx):
     d = dense(ctx, held, depth, le(3))
     same_tree(t, d, held, [0, 1, 2, 1023, 1024, 1028, n - 1])
     t.free(); d.free()
+
+
+# ---------------------------------------------------------------------------------------------------------------- 10: put scenarios, the WHOLE tree after every step
+# The scenarios of keyed_cases (tiles_mixed, in_place, second_trip); test_merkle_keyed_host.py asserts on the CPU that each reaches the device path it is
+# for.  A brand-new position that the scan ranks one slot off lands in the middle of a tile, so nothing here is sampled at depth 13.
+def whole_tree(t, d, held, caps, depth):
+    """every node, every key and every leaf of keyed tree t against dense tree d of the padded list, and the bytes held against the capacity policy"""
+    n = 1 << depth
+    same_tree(t, d, held, sorted({i for k in sorted(held)[::97] for i in (k - 1, k, k + 1) if 0 <= i < n} | {0, n - 1}), full=True)
+    leaves, is_held = t.get(range(n))
+    assert leaves == d.nodes(depth) and is_held == [k in held for k in range(n)]
+    assert t.node_counts[1] == held_bytes(caps, depth)
+
+
+def run_scenario(ctx, sc, empty):
+    """a keyed tree over the scenario's base, then every put of it, compared whole after every step; -> the merge kinds of every put, height by height"""
+    depth = sc.depth
+    held = {k: K.leaf_of(k) for k in sc.base}
+    t = keyed(ctx, held, depth, empty, order=list(sc.base))
+    caps = K.capacities([0] * (depth + 1), K.counts_of(held, depth), depth)
+    d = dense(ctx, held, depth, empty)
+    whole_tree(t, d, held, caps, depth)
+    d.free()
+    seen = []
+    for r, (keys, kind) in enumerate(sc.puts):
+        keys = list(keys)
+        leaves = K.rand_scalars(b"scenario %s %d" % (sc.name.encode(), r), len(keys))
+        assert K.kind_of(held, keys) == kind
+        lists, before = K.put_lists(held, keys, depth), K.counts_of(held, depth)
+        (inserted, root), count, evals = logged(ctx, lambda: t.put(keys, leaves, return_root=True))
+        held.update(zip(keys, leaves))
+        kinds, caps = K.merge_kinds(caps, before, K.counts_of(held, depth), depth)
+        seen.append(kinds)
+        assert inserted == lists[0][1]
+        check_log(count, evals, keys, depth)
+        assert count["k_mkx_merge"] == sum(1 for k in kinds if k) == sum(1 for _, fresh in lists if fresh), (count, kinds)
+        assert count["k_mkx_classify"] == count["k_mkx_scan_sums"] == count["k_mkx_scan_top"] == count["k_mkx_scatter"] == depth      # one of each per height below the root
+        d = dense(ctx, held, depth, empty)
+        assert root == d.root()
+        whole_tree(t, d, held, caps, depth)
+        d.free()
+    t.free()
+    return seen
+
+
+@pytest.mark.parametrize("last", ["new", "held"])
+def test_tiles_mixed_depth13(ctx, last):
+    """ONE put of 4,097 sorted keys into a tree of 3,416: brand-new flags by scan tile none / all / irregular / irregular / one flag, so the rank of a
+    brand-new key is its tile's offset (0, 0, 1,024, 1,466, 1,927) plus an irregular rank inside the tile; height 1 finds nothing brand-new and from height
+    2 on the flags are written without a lookup (classify == 0) over a list of 1,594 positions, two tiles"""
+    kinds, = run_scenario(ctx, K.tiles_mixed(last), le(R.L - 7))
+    assert kinds == ["grows"] + [None] * 13                                  # (3,416 + 1,928 or 1,927 leaves outgrow the room for 3,416)
+
+
+def test_in_place_depth13(ctx):
+    """3,000 keys, 1,500 new ones that retire the arrays of heights 0..3, then 1,000 mixed keys that merge in the context's scratch at heights 0, 1 and 2:
+    totals of 5,000, 3,511 and 2,014 entries, so every height splits the scratch (values first, positions behind them) at another place, over 20, 14 and 8 blocks"""
+    seen = run_scenario(ctx, K.in_place(), None)
+    assert seen == [["grows"] * 4 + [None] * 10, ["in place"] * 3 + [None] * 11]
+
+
+def oracle_root(depth, key, leaf, siblings):
+    """the root that the oracle's sponge gives a leaf and its path: `depth` hashes"""
+    cur = leaf
+    for s in range(depth):
+        cur = O.mimc_sponge(siblings[s] + cur) if key >> s & 1 else O.mimc_sponge(cur + siblings[s])
+    return cur
+
+
+@pytest.mark.parametrize("last", ["new", "held"])
+def test_second_trip_depth19(ctx, last):
+    """2^17 keys, then put A of 262,144 keys (256 tile sums: one trip of k_mkx_scan_top) and put B of 262,145 (257: the second trip scans one tile of one
+    flag on top of the carry of the first 256), both with mixed flags.  The reference is the dense tree of this device over the 2^19 padded list, and for
+    the probe keys the oracle's sponge along get() and paths().  Leaves are 252 random bits, kept as one array of 2^19 rows beside a mask of held keys."""
+    import numpy as np
+    sc = K.second_trip(last)
+    depth, n, empty = sc.depth, 1 << sc.depth, le(R.L - 19)
+    rs = np.random.RandomState(1900 + len(last))
+
+    def fresh_leaves(count):
+        a = np.frombuffer(rs.bytes(32 * count), dtype=np.uint8).reshape(count, 32).copy()
+        a[:, 31] &= 0x0f
+        return a
+    table, mask = np.tile(np.frombuffer(empty, dtype=np.uint8), (n, 1)), np.zeros(n, dtype=bool)
+    base = np.array(sc.base)
+    table[base], mask[base] = fresh_leaves(len(base)), True
+    t = ctx.merkle_tree(table[base].tobytes(), depth=depth, empty=empty, keys=sc.base)
+    caps = K.capacities([0] * (depth + 1), K.counts_np(base, depth), depth)
+    for r, (keys, kind) in enumerate(sc.puts):
+        keys, order = list(keys), sorted(keys)
+        ka = np.array(keys)
+        lists, before = K.put_lists_np(np.flatnonzero(mask), ka, depth), K.counts_np(np.flatnonzero(mask), depth)
+        prev = mask.copy()
+        leaves = fresh_leaves(len(keys))
+        (inserted, root), count, evals = logged(ctx, lambda: t.put(keys, leaves.tobytes(), return_root=True))
+        table[ka], mask[ka] = leaves, True
+        now = np.flatnonzero(mask)
+        after = K.counts_np(now, depth)
+        kinds, caps = K.merge_kinds(caps, before, after, depth)
+        assert inserted == lists[0][1] and 0 < inserted < len(keys) and kind == "mixed"
+        check_log(count, evals, keys, depth, want=[m for m, _ in lists[1:]])
+        assert count["k_mkx_merge"] == sum(1 for k in kinds if k) and count["k_mkx_scan_top"] == depth
+        d = ctx.merkle_tree(table.tobytes(), depth=depth, empty=empty)
+        assert root == d.root() == t.root()
+        assert t.size == len(now) and t.keys() == now.tolist()
+        counts, nbytes = t.node_counts
+        assert counts == after and nbytes == held_bytes(caps, depth)
+        for level in range(13):                                              # whole levels from the root down to level 12
+            assert t.nodes(level) == d.nodes(level), (r, level)
+        # the lowest levels: 4,096 nodes around the ancestors of the keys at the end of the dirty list (indices 262,143 and 262,144 of put B), of the key in
+        # the middle of it, and of the first one
+        for level in range(13, depth + 1):
+            width = 1 << level
+            for k in (order[-1], order[len(order) // 2], order[0]):
+                first = max(0, min((k >> (depth - level)) - 2048, width - 4096))
+                assert t.nodes(level, first, 4096) == d.nodes(level, first, 4096), (r, level, first)
+        got, is_held = t.get(keys)                                           # every put key holds its leaf
+        assert b"".join(got) == leaves.tobytes() and all(is_held)
+        # the oracle, directly: held, brand-new and absent keys; the last keys of the sorted put and their neighbours
+        absent = [int(k) for k in np.flatnonzero(~mask)[[0, -1]]]
+        probe = sorted(set(order[-2:] + [k ^ 1 for k in order[-2:]] + [order[0], order[len(order) // 2], next(k for k in order if prev[k]), next(k for k in order if not prev[k])]
+                           + absent + [int(base[0])]))
+        got, is_held = t.get(probe)
+        assert is_held == [bool(mask[k]) for k in probe] and got == [table[k].tobytes() if mask[k] else red(empty) for k in probe]
+        if r == 1:
+            assert bool(prev[order[-1]]) == (last == "held") and not prev[order[-2]]
+        for k, leaf, sib in zip(probe, got, t.paths(probe)):
+            assert oracle_root(depth, k, leaf, sib) == root, (r, k)
+        d.free()
+    t.free()
 
 
 # ---------------------------------------------------------------------------------------------------------------- 5: depth 32 against the model

@@ -1,6 +1,7 @@
 """CPU tests of keyed Merkle trees (no GPU needed): the model of tests/keyed_cases.py against brute force with the oracle's sponge, csrc/host/
 merkle_keyed_plan.hpp - the index rules the kernels of csrc/hip/k_merkle_keyed.cuh run, and the hashing plan - replayed on host arrays against brute
-force, and what the five new C calls declare, export and refuse before they touch a device."""
+force, that every put scenario of keyed_cases reaches the device path it is for (by integers alone), and what the five new C calls declare, export and
+refuse before they touch a device."""
 import ctypes as C
 import itertools
 import re
@@ -67,6 +68,88 @@ def test_model_put_sequences(depth):
 
 def test_launch_rule_of_the_model():
     assert K.hashing_launches([0] * 5) == 0 and K.hashing_launches([256, 128, 1]) == 1 and K.hashing_launches([257, 129, 1]) == 2 and K.hashing_launches([600, 300, 150]) == 3
+
+
+# ---------------------------------------------------------------------------------------------------------------- the put scenarios reach what they are for
+# Conditions of the GPU tests (test_merkle_keyed_gpu.py), by integers alone: the seeds are chosen so that they hold.
+def test_integer_models_agree():
+    """put_lists (sets), put_lists_np and counts_np (numpy.unique) against counts_of and evals_of"""
+    held, keys = K.rand_keys(b"models held", 900, 13), K.rand_keys(b"models put", 700, 13)
+    lists = K.put_lists(held, keys, 13)
+    assert lists == K.put_lists_np(held, keys, 13) and [m for m, _ in lists[1:]] == K.evals_of(keys, 13)
+    after = K.counts_of(set(held) | set(keys), 13)
+    assert K.counts_np(held + keys, 13) == after and [b + f for b, (_, f) in zip(K.counts_of(held, 13), lists)] == after
+    assert K.classified([(5, 2), (4, 1), (3, 0), (2, 0), (1, 0)]) == [0, 1, 2] and K.classified([(5, 0), (3, 0), (1, 0)]) == [0] and K.classified([(2, 2), (1, 1)]) == [0]
+    assert [K.capacity(0, 3, 8192), K.capacity(64, 65, 8192), K.capacity(3000, 4500, 8192), K.capacity(2462, 3295, 4096), K.capacity(6000, 5000, 8192), K.capacity(0, 3, 2)] == [64, 128, 6000, 4096, 6000, 3]
+
+
+@pytest.mark.parametrize("last", ["new", "held"])
+def test_scenario_tiles_mixed(last):
+    sc = K.tiles_mixed(last)
+    held, (keys, kind) = set(sc.base), sc.puts[0]
+    assert sc.depth == 13 and len(held) == len(sc.base) == 3416 and len(keys) == 4097 == len(set(keys)) and list(keys) == sorted(keys) and max(keys) < 1 << 13
+    assert K.kind_of(held, keys) == kind == "mixed"
+    flags = K.put_flags(held, keys)
+    # by scan tile: none, all, irregular, irregular, a tile of one flag
+    assert K.tile_counts(flags) == [(1024, 0), (1024, 1024), (1024, 442), (1024, 461), (1, 1 if last == "new" else 0)]
+    assert (flags[2047], flags[2048]) == (1, 0) and flags[3071] != flags[3072]
+    for tile in (2, 3):                                                     # irregular: the flag changes hundreds of times inside the tile, and no run is long
+        f = flags[tile * K.TILE:(tile + 1) * K.TILE]
+        assert sum(a != b for a, b in zip(f, f[1:])) > 512 and "1" * 10 not in "".join(map(str, f)) and "0" * 10 not in "".join(map(str, f))
+    assert K.tiles_mixed("new").base == K.tiles_mixed("held").base and K.tiles_mixed("new").puts[0][0][:4096] == K.tiles_mixed("held").puts[0][0][:4096]
+    lists = K.put_lists(held, keys, 13)
+    # height 0 has both kinds of flag; height 1 is the first without a brand-new position (every dirty pair holds a key), so from height 2 on classify == 0,
+    # and the dirty list of height 2 is still longer than a tile
+    assert 0 < lists[0][1] < lists[0][0] and K.classified(lists) == [0, 1]
+    assert lists[1] == (2718, 0) and lists[2] == (1594, 0) and lists[2][0] > K.TILE
+    assert [s for s, (m, _) in enumerate(lists) if m > K.TILE] == [0, 1, 2]
+
+
+def test_scenario_in_place():
+    sc = K.in_place()
+    states = K.scenario_states(sc)
+    assert sc.depth == 13 and [len(s) for s in states] == [3000, 4500, 5000] and [len(k) for k, _ in sc.puts] == [1500, 1000]
+    assert [K.kind_of(states[r], keys) for r, (keys, _) in enumerate(sc.puts)] == [kind for _, kind in sc.puts] == ["new", "mixed"]
+    assert sum(1 for k in sc.puts[1][0] if k in states[1]) == 500
+    caps = K.capacities([0] * 14, K.counts_of(states[0], 13), 13)
+    assert caps[:4] == [3000, 2462, 1729, 1003] and caps[4:] == [512 >> s for s in range(10)]
+    # the 1,500 new keys: heights 0..3 outgrow their arrays (height 0 takes twice its room, the others all their height can hold), nothing above gains a node
+    kinds, caps = K.merge_kinds(caps, K.counts_of(states[0], 13), K.counts_of(states[1], 13), 13)
+    assert kinds == ["grows"] * 4 + [None] * 10 and caps[:4] == [6000, 4096, 2048, 1024]
+    # the 1,000 mixed keys: heights 0, 1 and 2 gain positions and keep their arrays
+    after = K.counts_of(states[2], 13)
+    kinds, caps2 = K.merge_kinds(caps, K.counts_of(states[1], 13), after, 13)
+    assert kinds == ["in place"] * 3 + [None] * 11 and caps2 == caps
+    totals = [after[s] for s, kind in enumerate(kinds) if kind == "in place"]
+    assert totals == [5000, 3511, 2014] and len(set(totals)) == len(totals) >= 3 and min(totals) > 256
+    lists = K.put_lists(states[1], sc.puts[1][0], 13)                       # and the flags of that put are mixed at every one of them
+    assert all(0 < lists[s][1] < lists[s][0] for s in range(3))
+
+
+@pytest.mark.parametrize("last", ["new", "held"])
+def test_scenario_second_trip(last):
+    sc = K.second_trip(last)
+    states = K.scenario_states(sc)
+    (a, _), (b, _) = sc.puts
+    assert sc.depth == 19 and len(states[0]) == 1 << 17 and len(a) == len(set(a)) == 262144 and len(b) == len(set(b)) == 262145 and max(a + b) < 1 << 19
+    assert K.second_trip("new").base == K.second_trip("held").base and K.second_trip("new").puts[0] == K.second_trip("held").puts[0]
+    cdiv = lambda x, y: -(-x // y)
+    trips = lambda m: cdiv(cdiv(m, K.TILE), K.TOP_TILES)                    # trips of k_mkx_scan_top over the tile sums of a list of m flags
+    for r, keys in enumerate((a, b)):
+        held = sum(1 for k in keys if k in states[r])
+        assert len(keys) // 4 < held < 3 * len(keys) // 4, (r, held)
+        lists = K.put_lists_np(sorted(states[r]), keys, 19)
+        if r == 0:
+            assert [m for m, _ in lists[1:]] == K.evals_of(keys, 19)
+        assert cdiv(lists[0][0], K.TILE) == (256, 257)[r]
+        # a second trip needs a dirty list above 262,144: none of A's heights has one, and of B's height 0 alone (height 1 has 2^18 positions in all)
+        assert [s for s, (m, _) in enumerate(lists) if m > K.TILE * K.TOP_TILES] == ([], [0])[r]
+        assert [trips(m) for m, _ in lists[:2]] == ([1, 1], [2, 1])[r]
+        assert all(0 < f < m for m, f in lists[:4]) and len(K.classified(lists)) >= 4         # mixed flags over many tiles at the lowest heights
+        assert K.counts_np(sorted(states[r + 1]), 19) == [c + f for c, (_, f) in zip(K.counts_np(sorted(states[r]), 19), lists)]
+    order = sorted(b)
+    assert [k in states[1] for k in order[-2:]] == [False, last == "held"]   # the one flag of tile 256, and its neighbour at dirty index 262,143
+    assert order[-1] >> 1 != order[-2] >> 1                                  # (the last key starts a parent of its own: head flag 1 in that tile)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the plan header on host arrays
